@@ -10,6 +10,12 @@ Metric (BASELINE.json): crystals/s of full training steps (forward + loss + back
 Phonon-DOS model, --layers 3 --transformer 2 --hidden 128, batch 64 crystals per GPU (weak
 scaling: N GPUs train on a global batch of 64*N), synthetic crystal graphs that are
 pre-collated and resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (`value`, `ms_per_step`, ...).  Everything
+else - the sanity checks of the timed run, the per-site roofline pass, the secondary workloads, the CPU baseline, the
+profile-derived figures - runs only with --full.  --dump-outputs DIR writes what the last timed step computed (loss, the two
+DOS predictions, parameters after AdamW and their gradients) as DIR/<name>.npy, so that two builds can be compared on
+identical seeded inputs.
 """
 import argparse
 import json
@@ -42,6 +48,9 @@ SHUFFLE_BUCKET = (16, 320)
 PROMOTE = float(os.environ.get("DOSX_BENCH_PROMOTE", "0.08"))   # Trainer(promote=...) of the --shuffle runs
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s
 MFMA_F32_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: fp32-input MFMA dense peak
+# --dump-outputs: elements kept per array.  The Electron-DOS models have 9.4 M / 14.2 M parameters, so their parameters and
+# gradients are written as the same fixed, seeded sample of positions (float32: 16 MB per array, < 64 MB in all)
+DUMP_MAX_ELEMS = 4 << 20
 
 
 def build_model(kind, L, T, H, device):
@@ -307,9 +316,30 @@ def compact_record(out: dict, sites: list, budget: int = LINE_BUDGET) -> dict:
     return rec
 
 
-def run_workload(name, *, device, world, rank, dp, mode, shuffle, steps, warmup, bucket, pool, instrument=True):
+def step_outputs(trainer, loss):
+    """What the last step handed its caller, as float32 numpy arrays: the loss, the two DOS predictions (the model's forward
+    returns dos_global, x, dos_system), the parameters after AdamW and their gradients (live parameters, module order,
+    flattened; a seeded sample of DUMP_MAX_ELEMS positions when larger)."""
+    import numpy as np
+    dos_global, _, dos_system = trainer.last_outputs
+    fp = trainer._fp
+    names = [n for n, _ in trainer.model.named_parameters() if n in fp.P]
+    arrays = {"loss": loss.detach().reshape(1), "dos_global": dos_global, "dos_system": dos_system,
+              "params": torch.cat([fp.P[n].reshape(-1) for n in names]), "grads": torch.cat([fp.G[n].reshape(-1) for n in names])}
+    out = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    n = out["params"].size
+    if n > DUMP_MAX_ELEMS:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ELEMS, replace=False))
+        out["params"], out["grads"] = out["params"][idx], out["grads"][idx]
+    return out
+
+
+def run_workload(name, *, device, world, rank, dp, mode, shuffle, steps, warmup, bucket, pool, instrument=True, full=True,
+                 outputs=False):
     """Train `steps` timed steps of configuration `name` (after `warmup` untimed ones) and return the measurements of this
-    rank: elapsed seconds, host enqueue seconds, per-site kernel timing of the replayed step, slot statistics."""
+    rank: elapsed seconds, host enqueue seconds, per-site kernel timing of the replayed step, slot statistics.
+    full=False: only the timed steps (no sanity checks, no host-enqueue measurement; `instrument` is then ignored).
+    outputs=True: `outputs` holds step_outputs() of the last timed step."""
     import numpy as np
     import torch.distributed as td
     from dostransformer_amd import ops
@@ -393,54 +423,60 @@ def run_workload(name, *, device, world, rank, dp, mode, shuffle, steps, warmup,
     for i in range(warmup):
         do_step()
     sync()
-    # eager mode: per-kernel HIP-event timing over the timed region itself (same stream as the launches);
+    # (--full) eager mode: per-kernel HIP-event timing over the timed region itself (same stream as the launches);
     # graph / replay mode: the timed region re-issues recorded launches (no per-kernel events possible), so the
     # kernel timing comes from an instrumented pass of the same steps right after it.
-    ops.KERNEL_TIMER.reset(enabled=not use_graph)
+    ops.KERNEL_TIMER.reset(enabled=full and not use_graph)
     hits0, miss0, prom0 = trainer.slot_hits, trainer.slot_misses, trainer.slot_promoted
     if shuffle:
         real_dims.clear()
     # `check` (what the timed steps did, read AFTER the timed region): the parameters as they stand now ...
-    params_before = trainer._fp.flat.clone() if trainer._fp is not None else None
+    params_before = trainer._fp.flat.clone() if (full and trainer._fp is not None) else None
     torch.cuda.synchronize()
     loss_first = loss = None
     t0 = time.perf_counter()
     for i in range(steps):
         loss = do_step()
-        if i == 0:
+        if full and i == 0:
             loss_first = loss.detach().clone()       # (the loss lives in the bucket's static buffer: one 4-byte device copy)
     host = time.perf_counter() - t0                  # the host is done enqueueing here; the GPU may still be running
     torch.cuda.synchronize()
     if dp is not None:
         td.barrier()
     elapsed = time.perf_counter() - t0
-    # ... the device loss of the first and the last timed step, every parameter finite, the parameters moved
-    fp_now = trainer._fp.flat
-    check = {"loss_first": _round_sig(float(loss_first), 6), "loss_last": _round_sig(float(loss), 6),
-             "finite": bool(torch.isfinite(fp_now).all()) and bool(torch.isfinite(loss_first)) and bool(torch.isfinite(loss)),
-             "params_changed_frac": None if params_before is None else
-             round(float((fp_now != params_before).float().mean()), 4),
-             "replay_eq_eager": None}
-    del params_before
-    ops.KERNEL_TIMER.enabled = False
+    # (read before anything below runs another step: the loss and the predictions live in the bucket's static buffers)
+    outs = step_outputs(trainer, loss) if outputs else None
     hits, misses, promoted = trainer.slot_hits - hits0, trainer.slot_misses - miss0, trainer.slot_promoted - prom0
     n_slots = len(trainer._slots)
-    # host time to ENQUEUE one step with an empty queue in front of it (inside the timed loop the host also blocks on the
-    # HIP queue's back pressure whenever it runs ahead of the GPU, so `host` above is an upper bound, not the enqueue cost)
-    enq = []
-    for i in range(9):
+    check = host_enqueue = None
+    if not full:
+        instrument = False
+    else:
+        # ... the device loss of the first and the last timed step, every parameter finite, the parameters moved
+        fp_now = trainer._fp.flat
+        check = {"loss_first": _round_sig(float(loss_first), 6), "loss_last": _round_sig(float(loss), 6),
+                 "finite": bool(torch.isfinite(fp_now).all()) and bool(torch.isfinite(loss_first)) and bool(torch.isfinite(loss)),
+                 "params_changed_frac": None if params_before is None else
+                 round(float((fp_now != params_before).float().mean()), 4),
+                 "replay_eq_eager": None}
+        del params_before
+        ops.KERNEL_TIMER.enabled = False
+        # host time to ENQUEUE one step with an empty queue in front of it (inside the timed loop the host also blocks on the
+        # HIP queue's back pressure whenever it runs ahead of the GPU, so `host` above is an upper bound, not the enqueue cost)
+        enq = []
+        for i in range(9):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            do_step()
+            enq.append(time.perf_counter() - t1)
         torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        do_step()
-        enq.append(time.perf_counter() - t1)
-    torch.cuda.synchronize()
-    enq.sort()
-    host_enqueue = enq[len(enq) // 2]
-    if shuffle:
-        del real_dims[-9:]
+        enq.sort()
+        host_enqueue = enq[len(enq) // 2]
+        if shuffle:
+            del real_dims[-9:]
     # ... and ONE step on the same batch from the same state issued both ways - the replayed launch list (three streams) and the
     # eager, single-stream marshalling of every call from Python - must leave the same parameters (state restored afterwards)
-    if mode == "replay" and not shuffle and dp is None:
+    if full and mode == "replay" and not shuffle and dp is None:
         fp = trainer._fp
         saved = (fp.flat.clone(), trainer._m.clone(), trainer._v.clone(), trainer.step_count)
 
@@ -514,6 +550,7 @@ def run_workload(name, *, device, world, rank, dp, mode, shuffle, steps, warmup,
                    "staged_through_host": bool(dp.staged)}
     res = {"kind": kind, "L": L, "T": T, "H": H, "B": B, "n_global": n_global, "elapsed": elapsed, "host": host, "host_enqueue": host_enqueue,
            "roof": roof, "n_inst": n_inst, "flops_step": flops_step, "prepare_steps": n_prep, "dp_info": dp_info, "check": check,
+           "outputs": outs,
            "slots": {"hits": hits, "misses": misses, "hit_rate": round(hits / max(hits + misses, 1), 4),
                      "promoted": promoted, "live": n_slots, "max": trainer.max_slots} if use_graph else None}
     del trainer, model
@@ -675,14 +712,21 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="phonon_h128_b64", choices=sorted(CONFIGS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the checks of the timed run, the host-enqueue time, the instrumented per-site "
+                         "roofline pass, the secondary workloads, the CPU baseline and the profile-derived figures; without it "
+                         "the run only sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, dos_global, dos_system, params, grads) as DIR/<name>.npy "
+                         "(float32; parameters and gradients as a fixed, seeded sample when larger than %d elements)" % DUMP_MAX_ELEMS)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary measurements of the default run (eDOS H256 line, --shuffle line)")
+                    help="--full: skip the secondary measurements (eDOS H256 line, --shuffle line)")
     ap.add_argument("--no-dp1", action="store_true",
-                    help="skip the `dp1_nccl` secondary (the headline workload through the data-parallel step on a 1-rank RCCL "
+                    help="--full: skip the `dp1_nccl` secondary (the headline workload through the data-parallel step on a 1-rank RCCL "
                          "group: it initialises a process group inside this process)")
     ap.add_argument("--kernels-out", default=os.path.join(ROOT, "bench_kernels_last.json"),
-                    help="side file for the full per-site kernel table (never on the stdout line)")
+                    help="--full: side file for the full per-site kernel table (never on the stdout line)")
     ap.add_argument("--launch", choices=["replay", "eager", "graph"], default="replay",
                     help="replay: re-issue a recorded launch list on static buffers (3 HIP streams); eager: marshal "
                          "every launch from Python; graph: torch/HIP graph replay")
@@ -719,7 +763,7 @@ def main():
     if world > 1 or args.force_dist:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29531")
-        if args.dist_backend == "nccl" and world > 1 and rank == 0 and "NCCL_DEBUG" not in os.environ:
+        if args.full and args.dist_backend == "nccl" and world > 1 and rank == 0 and "NCCL_DEBUG" not in os.environ:
             # SURVEY.md §5 "verify which algorithm RCCL selects": the tuner's decision per collective size goes to a side
             # file on rank 0 (one short line per collective; read back after the timed region, see rccl_choices)
             import tempfile
@@ -735,18 +779,24 @@ def main():
     mode = "graph" if args.graph else args.launch
     bucket = tuple(args.bucket) if args.bucket else (SHUFFLE_BUCKET if args.shuffle else (8, 128))
     common = dict(device=device, world=world, rank=rank, dp=dp, mode=mode, pool=args.pool)
-    r = run_workload(args.config, shuffle=args.shuffle, steps=args.steps, warmup=args.warmup, bucket=bucket, **common)
+    r = run_workload(args.config, shuffle=args.shuffle, steps=args.steps, warmup=args.warmup, bucket=bucket,
+                     instrument=args.full, full=args.full, outputs=bool(args.dump_outputs) and rank == 0, **common)
     kind, L, T, H, B, n_global = r["kind"], r["L"], r["T"], r["H"], r["B"], r["n_global"]
+    if r["outputs"] is not None:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for k, v in r["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, f"{k}.npy"), v)
 
     t = torch.tensor([r["elapsed"], r["host"]], dtype=torch.float64, device=device if args.dist_backend == "nccl" else "cpu")
     if dp is not None:
         td.all_reduce(t, op=td.ReduceOp.MAX)
     elapsed, host = float(t[0]), float(t[1])
 
-    # secondary measurements of the DEFAULT run (one GPU, default configuration): the other single-GPU BASELINE
+    # secondary measurements of a --full run (one GPU, default configuration): the other single-GPU BASELINE
     # configuration and the steady-state (fresh batch every step) figure, so that the driver's record holds them too
     secondary = {}
-    if world == 1 and dp is None and not args.no_secondary and args.config == "phonon_h128_b64" and not args.shuffle \
+    if args.full and world == 1 and dp is None and not args.no_secondary and args.config == "phonon_h128_b64" and not args.shuffle \
             and mode == "replay":
         def brief(x, steps):
             ms = 1e3 * x["elapsed"] / steps
@@ -818,9 +868,9 @@ def main():
     if rank == 0:
         roof = r["roof"]
         n_inst = r["n_inst"]
-        kernels, traffic_src = load_traffic(args.config) if (world == 1 and not args.shuffle) \
+        kernels, traffic_src = load_traffic(args.config) if (args.full and world == 1 and not args.shuffle) \
             else ({}, "traffic is profiled for the single-GPU fixed-batch runs only")
-        kernel_only = load_kernel_only(args.config) if (world == 1 and not args.shuffle) else {}
+        kernel_only = load_kernel_only(args.config) if (args.full and world == 1 and not args.shuffle) else {}
         for rec in roof["all"] + ([roof["dominant"]] if roof["dominant"] else []):
             rec["traffic"] = traffic_of(kernels, rec["kernel"])
             rec["us_per_step"] = round(1e3 * rec["total_ms"] / max(n_inst, 1), 2)
@@ -859,38 +909,40 @@ def main():
             # x3 for fwd+bwd) / measured step time / fp32 MFMA dense peak
             "step_frac": round(flops_step / (ms_step * 1e-3) / (MFMA_F32_PEAK_TFLOPS * 1e12), 4),
             "step_gflop": round(flops_step / 1e9, 2),
-            # host time to enqueue one replayed step into an EMPTY queue (median of 9): the margin to the GPU step; and the
-            # per-step time of the timed loop's host side (includes blocking on the queue's back pressure)
-            "host_ms_per_step": round(1e3 * r["host_enqueue"], 4),
+            # the per-step time of the timed loop's host side (includes blocking on the queue's back pressure)
             "host_loop_ms_per_step": round(1e3 * host / args.steps, 4),
-            "roofline": dom,
-            "traffic_source": traffic_src[:100],
-            # the DOSX_* switches in effect ({} = the shipped defaults) and the sanity checks of the timed run (run_workload)
+            # the DOSX_* switches in effect ({} = the shipped defaults)
             "env": env_switches,
-            "check": r["check"],
         }
-        if world == 1 and args.config == "phonon_h128_b64":
-            out["north_star"] = load_north_star()
-        if r["slots"] is not None:
-            out["slots"] = r["slots"]
-        if r["dp_info"] is not None:
-            out["dp"] = dict(r["dp_info"], rccl=rccl_choices(rccl_log, world))
-            if rccl_log is not None:          # (the tuner's side file has been read: do not leave it in the temp directory)
-                try:
-                    os.unlink(rccl_log)
-                except OSError:
-                    pass
-        if secondary:
-            out["secondary"] = secondary
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(kind, L, T, H, B, args.cpu_budget)
-        try:
-            with open(args.kernels_out, "w") as f:
-                json.dump({"config": args.config, "ms_per_step": ms_step, "instrumented_steps": n_inst, "sites": roof["all"]}, f, indent=1)
-            out["kernels_file"] = os.path.relpath(args.kernels_out, ROOT)
-        except OSError as ex:
-            print(f"bench.py: could not write {args.kernels_out}: {ex}", file=sys.stderr)
-        line = json.dumps(compact_record(out, roof["all"]))
+        if not args.full:
+            line = json.dumps(out)
+        else:
+            # host time to enqueue one replayed step into an EMPTY queue (median of 9): the margin to the GPU step; the
+            # sanity checks of the timed run (run_workload)
+            out.update({"host_ms_per_step": round(1e3 * r["host_enqueue"], 4), "roofline": dom,
+                        "traffic_source": traffic_src[:100], "check": r["check"]})
+            if world == 1 and args.config == "phonon_h128_b64":
+                out["north_star"] = load_north_star()
+            if r["slots"] is not None:
+                out["slots"] = r["slots"]
+            if r["dp_info"] is not None:
+                out["dp"] = dict(r["dp_info"], rccl=rccl_choices(rccl_log, world))
+                if rccl_log is not None:          # (the tuner's side file has been read: do not leave it in the temp directory)
+                    try:
+                        os.unlink(rccl_log)
+                    except OSError:
+                        pass
+            if secondary:
+                out["secondary"] = secondary
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(kind, L, T, H, B, args.cpu_budget)
+            try:
+                with open(args.kernels_out, "w") as f:
+                    json.dump({"config": args.config, "ms_per_step": ms_step, "instrumented_steps": n_inst, "sites": roof["all"]}, f, indent=1)
+                out["kernels_file"] = os.path.relpath(args.kernels_out, ROOT)
+            except OSError as ex:
+                print(f"bench.py: could not write {args.kernels_out}: {ex}", file=sys.stderr)
+            line = json.dumps(compact_record(out, roof["all"]))
         sys.stdout.flush()
         os.write(real_stdout, (line + "\n").encode())
     if dp is not None:

@@ -3,7 +3,6 @@ import copy
 import ctypes as C
 import math
 import numpy as np
-import pytest
 import torch
 import torch.nn.functional as F
 from tests.util import rmse  # noqa: F401
@@ -205,10 +204,10 @@ def _sliver_case(o, _lib, Gemm, M, N, K, mapped, res):
     a, w = rnd(rows_a, K, seed=1), rnd(K, N, seed=2)
     r = rnd(M, N, seed=3) if res else None
     out = torch.full((M, N), float("nan"), device=DEV)
-    B = max(M // 51, 1)
-    rm = o.rowmap(d=B, m=2 * B, c=1, off=B) if (mapped and M % 51 == 0) else None
-    if mapped and rm is None:
-        pytest.skip("row-map case needs M = 51 * B")
+    S = 51 if M % 51 == 0 else 201          # rows = energies x crystals: Phonon-DOS (51) or Electron-DOS (201) heads
+    B = max(M // S, 1)
+    assert not mapped or M % S == 0, "row-map case needs M = 51 * B or 201 * B"
+    rm = o.rowmap(d=B, m=2 * B, c=1, off=B) if mapped else None
     o.gemm(M, N, [o.seg(a, rmap=rm)], w, out, w_layout=1, res=r)
     torch.cuda.synchronize()
     idx = torch.arange(M, device=DEV)

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -192,10 +193,11 @@ def test_rccl_tuning_lines_are_parsed(tmp_path):
 
 @pytest.mark.gpu
 def test_bare_two_rank_bench_launches_itself(tmp_path):
-    """VERDICT r3 item 1's acceptance line, from a clean environment (no RANK / WORLD_SIZE): one JSON line, rc 0, n_gpus 2."""
+    """VERDICT r3 item 1's acceptance line, from a clean environment (no RANK / WORLD_SIZE): one JSON line, rc 0, n_gpus 2
+    (--full: the record's `dp` object)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--share-gpu",
-                        "--steps", "6", "--warmup", "2", "--config", "phonon_h64_b8", "--no-cpu-baseline"],
+                        "--steps", "6", "--warmup", "2", "--config", "phonon_h64_b8", "--no-cpu-baseline", "--full"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = p.stdout.decode().strip().splitlines()
@@ -209,11 +211,10 @@ def test_bare_two_rank_bench_launches_itself(tmp_path):
 
 @pytest.mark.gpu
 def test_bench_default_line_is_one_small_json_record(tmp_path):
-    """The driver's own invocation shape (no flags except fewer steps): exactly one stdout line, < 4000 bytes, parseable,
-    with the roofline object, the cpu baseline and the secondaries; the per-site table is in the side file (< 6000 bytes: the driver
-    keeps an 8 KB tail)."""
+    """The --full invocation (fewer steps): exactly one stdout line, < 6000 bytes (the driver keeps an 8 KB tail), parseable,
+    with the roofline object, the cpu baseline and the secondaries; the per-site table is in the side file."""
     kout = tmp_path / "kernels.json"
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "16", "--warmup", "8", "--cpu-budget", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "16", "--warmup", "8", "--cpu-budget", "2",
                         "--kernels-out", str(kout)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=1500)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = p.stdout.decode().strip().splitlines()
@@ -246,6 +247,68 @@ def test_bench_default_line_is_one_small_json_record(tmp_path):
         assert sb[k]["us"] > 0 and sb[k]["speedup"] > 0.9 and sb[k]["err"] <= max(2e-5, 4 * sb[k]["err_fp32"]), sb[k]
     table = json.loads(kout.read_text())
     assert len(table["sites"]) >= 10 and not any(s["site"].startswith("gemm[M") for s in table["sites"])
+
+
+HEADLINE_KEYS = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+DUMP_NAMES = ("loss", "dos_global", "dos_system", "params", "grads")
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints only the headline record: no checks, no roofline pass, no
+    secondaries, no CPU baseline, no side file.  --dump-outputs writes the last timed step's loss, predictions, parameters and
+    gradients as float32 .npy files under 64 MB; two runs with the same arguments compute the same outputs."""
+    kout = tmp_path / "kernels.json"
+    recs = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                            "--kernels-out", str(kout), "--dump-outputs", str(tmp_path / run)],
+                           cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
+        lines = p.stdout.decode().strip().splitlines()
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    assert all(k in rec for k in HEADLINE_KEYS), rec
+    assert rec["unit"] == "crystals/s" and rec["higher_is_better"] is True and rec["dtype"] == "f32"
+    assert rec["metric"] == "crystals/sec training throughput (Phonon DOS, hidden=128)"
+    assert rec["steps"] == 5 and rec["warmup"] == 2 and rec["ms_per_step"] > 0
+    assert abs(rec["value"] - 64 / (rec["ms_per_step"] * 1e-3)) < 1e-2 * rec["value"]
+    for k in ("check", "roofline", "secondary", "cpu_baseline", "north_star", "host_ms_per_step", "kernels_file"):
+        assert k not in rec, k
+    assert not kout.exists()
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in DUMP_NAMES}
+    b = {n: np.load(tmp_path / "b" / f"{n}.npy") for n in DUMP_NAMES}
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(f"{n}.npy" for n in DUMP_NAMES)
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in DUMP_NAMES) < 64 << 20
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["dos_global"].shape == a["dos_system"].shape == (64, 51) and a["params"].shape == a["grads"].shape
+    assert np.abs(a["grads"]).max() > 0
+    for n in DUMP_NAMES:
+        assert np.array_equal(a[n], b[n]), n
+
+
+def test_step_outputs_are_float32_and_sample_large_models(monkeypatch):
+    """bench.step_outputs: the live parameters in module order (dead ones left out), their gradients at the same positions, and
+    for a model over DUMP_MAX_ELEMS the same seeded sample of positions every time."""
+    from types import SimpleNamespace
+    import torch
+    import bench
+    model = torch.nn.Module()
+    model.w = torch.nn.Parameter(torch.arange(6, dtype=torch.float32).reshape(2, 3))
+    model.dead = torch.nn.Parameter(torch.full((4,), -1.0))
+    model.b = torch.nn.Parameter(torch.arange(6, 10, dtype=torch.float32))
+    fp = SimpleNamespace(P={"b": model.b.data, "w": model.w.data}, G={"b": -model.b.data, "w": -model.w.data})
+    dos = torch.rand(3, 51, dtype=torch.float64)
+    tr = SimpleNamespace(last_outputs=(dos, None, 2 * dos), _fp=fp, model=model)
+    out = bench.step_outputs(tr, torch.tensor(0.5))
+    assert sorted(out) == sorted(DUMP_NAMES) and all(v.dtype == np.float32 for v in out.values())
+    assert out["loss"].tolist() == [0.5] and out["dos_global"].shape == (3, 51)
+    assert out["params"].tolist() == list(range(10)) and out["grads"].tolist() == [-float(i) for i in range(10)]
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 4)
+    s1, s2 = bench.step_outputs(tr, torch.tensor(0.5)), bench.step_outputs(tr, torch.tensor(0.5))
+    assert s1["params"].shape == (4,) and np.array_equal(s1["params"], s2["params"])
+    assert np.array_equal(s1["grads"], -s1["params"]) and np.all(np.diff(s1["params"]) > 0)
 
 
 def test_north_star_tool_classifies_the_attention_launches(tmp_path):

@@ -27,13 +27,15 @@ def _free_port():
     return p
 
 
-def _run_ranks(out, world, suite):
+def _run_ranks(out, world, suite, gpu_per_rank=False):
+    """`world` dp_worker.py ranks; they share cuda:0, or with gpu_per_rank rank r sees GPU r alone (as its cuda:0)."""
     port = _free_port()
     env = dict(os.environ)
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
+    envs = [dict(env, HIP_VISIBLE_DEVICES=str(r)) if gpu_per_rank else env for r in range(world)]
     logf = [open(os.path.join(out, f"rank{r}.log"), "wb") for r in range(world)]     # (files, not pipes: 8 chatty ranks must not block)
     procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "dp_worker.py"), str(r), str(world), str(port), str(out), suite],
-                              env=env, cwd=ROOT, stdout=logf[r], stderr=subprocess.STDOUT) for r in range(world)]
+                              env=envs[r], cwd=ROOT, stdout=logf[r], stderr=subprocess.STDOUT) for r in range(world)]
     try:
         for p in procs:
             p.wait(timeout=1500)
@@ -56,7 +58,11 @@ def two_rank_run(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def eight_rank_full_run(tmp_path_factory):
-    return _run_ranks(str(tmp_path_factory.mktemp("dp8")), 8, "full")
+    # one rank per GPU: eight ranks and this process on ONE GPU are more processes than a GPU shared with other users admits
+    n = torch.cuda.device_count()
+    if n < 8:
+        pytest.skip(f"needs 8 GPUs (one per rank), found {n}")
+    return _run_ranks(str(tmp_path_factory.mktemp("dp8")), 8, "full", gpu_per_rank=True)
 
 
 @pytest.mark.parametrize("kind,mode", [("phonon", "eager"), ("phonon", "replay"), ("edos", "eager"), ("edos", "replay"),
@@ -135,12 +141,12 @@ def test_bench_two_ranks_share_gpu(tmp_path):
 @pytest.mark.parametrize("kind,mode", [("phonon", "replay"), ("edos", "replay")])
 def test_eight_rank_full_size_configs_match_single_process(eight_rank_full_run, kind, mode):
     """BASELINE.json configs[3] (Phonon-DOS L3 T2 H128, global batch 512) and configs[4] (Electron-DOS H256 T4, global batch
-    256) at FULL global size with the 8 ranks of the 8-GPU configuration - 8 fresh processes that share the box's one
-    MI355X over gloo, each training on its `shard_batch` shard (64 resp. 32 crystals) - against a single-process `Trainer` on
+    256) at FULL global size with the 8 ranks of the 8-GPU configuration - 8 fresh processes, one per GPU, over gloo, each
+    training on its `shard_batch` shard (64 resp. 32 crystals) - against a single-process `Trainer` on
     the un-sharded batch (it fits one GPU): global loss (`main_phDOS.py:109-114` is ONE rmse over all B*51 elements), the
     all-reduced step-0 gradients, the parameters after 2 AdamW steps (step 0 runs eagerly while the replay plan - split
     around the SSE and early-bucket collectives - is recorded, step 1 replays it); replicas bit-identical to each other.  No scaling claim
-    (one GPU, host-staged sums): this proves the 8-way sharded step computes the full-batch step."""
+    (host-staged sums): this proves the 8-way sharded step computes the full-batch step."""
     from dostransformer_amd.batch import collate
     from dostransformer_amd.train import Trainer
     from tests.dp_worker import SUITES, make_crystals, make_model, suite_steps

@@ -25,10 +25,11 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("pkv", [False, True])
 def test_attention_fwd_bwd(Sq, Bq, Nk, Bk, H, bcast, pkv, drop):
     """pkv: the dq kernel also produces the per-tile dK + dV partials and a reduction kernel finishes the key gradient
-    (Nk <= 64; DosxAttn.dkv_part) instead of the streamed dkv kernel behind the dscores round trip."""
+    (Nk <= 64; DosxAttn.dkv_part) instead of the streamed dkv kernel behind the dscores round trip.  Beyond the shapes that
+    path covers, a given dkv_part is left alone and the streamed dkv kernel runs (include/dosx.h)."""
     from dostransformer_amd import _lib
-    if pkv and not _lib.load().dosx_attention_pkv_supported(Nk, H):
-        pytest.skip("partial-dKV path covers Nk <= 64")
+    pkv_path = pkv and bool(_lib.load().dosx_attention_pkv_supported(Nk, H))
+    assert pkv_path or not pkv or Nk > 64
     o = ops()
     from dostransformer_amd._lib import Attn
     qs, qb = (1, 0) if bcast else (Bq, 1)
@@ -64,18 +65,23 @@ def test_attention_fwd_bwd(Sq, Bq, Nk, Bk, H, bcast, pkv, drop):
     dx = torch.empty(Sq * Bq, H, device=DEV)
     dsc = torch.empty(Bq, Sq, Nk, device=DEV)
     dkv = torch.zeros(Nk * Bk, H, device=DEV)
-    nqt, nkt = (Sq + 31) // 32, ((Nk + 15) // 16 if pkv else (Nk + 31) // 32)
+    nqt, nkt = (Sq + 31) // 32, ((Nk + 15) // 16 if pkv_path else (Nk + 31) // 32)
     part = torch.empty(Bq * nqt + Bk * nkt, 2 * H, device=DEV)
     a.dout, a.dx, a.dscores, a.dkvhat, a.dkv_accumulate = dout.data_ptr(), dx.data_ptr(), dsc.data_ptr(), dkv.data_ptr(), 1
     a.partials_q = part.data_ptr()
     a.partials_kv = part.data_ptr() + 4 * Bq * nqt * 2 * H
     if pkv:
         kvp = torch.full((Bq * nqt * Nk, H), float("nan"), device=DEV)
-        a.dkv_part, a.dscores = kvp.data_ptr(), None
+        a.dkv_part = kvp.data_ptr()
+    if pkv_path:
+        a.dscores = None
         dkv += 0.5                           # accumulate flag: the reduction adds onto what is there
     o.attention_bwd(a)
-    if pkv:
+    if pkv_path:
         dkv -= 0.5
+    elif pkv:
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(kvp).all())  # the streamed dkv kernel ran: the partial-dKV scratch is untouched
     ps = part.double().sum(0)
     if bcast:
         dxr = dx.double().reshape(Sq, Bq, H).sum(1)

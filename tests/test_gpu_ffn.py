@@ -340,8 +340,8 @@ def test_encoder_layer_with_attention_inside_the_ffn_launch(Sq, Bq, Nk, Bk, H, b
     the gradients through the (unchanged) backward agree."""
     from dostransformer_amd import functional as Fn
     o = ops()
-    if form == "rows" and Nk > 16:
-        pytest.skip("the per-row form takes at most 16 keys")
+    # the per-row form takes at most 16 keys: beyond them the policy must fall back to the attention kernel + dosx_ffn_fwd
+    assert form != "rows" or Nk <= 16 or not o.ffn_att_supported(H, Nk)
     T = 2
     gen = torch.Generator().manual_seed(Sq * 7 + Nk)
     P, G = {}, {}

@@ -37,7 +37,11 @@ def test_g2_encoder(mode):
     (y * torch.from_numpy(z[f"{mode}/w"])).sum().backward()
     assert maxabs(x.grad, z[f"{mode}/dx"]) < 1e-5
     if mode == "cross":
-        assert maxabs(kv.grad, z["cross/dkv"]) < 1e-5
+        # dK/dV sums over every query and reaches |511|, where one fp32 ulp is 3e-5: 1e-5 alone holds only for the CPU kernels
+        # that wrote the golden file (another vector width or host sums in another order: 6e-5 .. 9e-5, 2-3 ulps), so the bound
+        # is 1e-5 plus 1e-6 of the tensor's scale
+        dkv = z["cross/dkv"]
+        assert maxabs(kv.grad, dkv) < 1e-5 + 1e-6 * np.abs(dkv).max()
     dead = set(str(s) for s in z[f"{mode}/dead"])
     for k, v in p.items():
         if k == "version":

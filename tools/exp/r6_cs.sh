@@ -19,7 +19,7 @@ rm -rf "$O/trace"
 cd "$R"
 for i in 1 2 3; do
   for v in 0 1; do
-    DOSX_MLP_LN_CS=$v timeout 300 python bench.py --allow-env --no-secondary --no-cpu-baseline --steps 200 2> /dev/null | \
+    DOSX_MLP_LN_CS=$v timeout 300 python bench.py --full --allow-env --no-secondary --no-cpu-baseline --steps 200 2> /dev/null | \
       python -c "import json,sys; r=json.loads(sys.stdin.read()); print('cs=$v', r['ms_per_step'], r['check'])" | tee -a "$O/ab.log"
   done
 done

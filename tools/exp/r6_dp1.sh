@@ -8,7 +8,7 @@ cd "$R"
 timeout 600 python -m pytest tests/test_gpu_predict.py -x -q 2>&1 | tail -3
 run() {
   name=$1; shift
-  env "$@" timeout 300 python bench.py --allow-env --no-secondary --no-cpu-baseline --steps 200 ${EXTRA:-} 2> /dev/null | \
+  env "$@" timeout 300 python bench.py --full --allow-env --no-secondary --no-cpu-baseline --steps 200 ${EXTRA:-} 2> /dev/null | \
     python -c "import json,sys; r=json.loads(sys.stdin.read()); print('$name', r['ms_per_step'], r.get('dp',{}).get('plan'))" | tee -a "$O/ab.log"
 }
 for i in 1 2 3; do

@@ -7,7 +7,7 @@ mkdir -p "$O"
 cd "$R"
 run() {
   name=$1; shift
-  env "$@" timeout 300 python bench.py --allow-env --no-secondary --no-cpu-baseline --shuffle --steps 200 2> /dev/null | \
+  env "$@" timeout 300 python bench.py --full --allow-env --no-secondary --no-cpu-baseline --shuffle --steps 200 2> /dev/null | \
     python -c "import json,sys; r=json.loads(sys.stdin.read()); s={x['site']: x['us_per_step'] for x in r['top_sites']}; print('$name', r['ms_per_step'], r['value'], r['check']['loss_last'], s.get('edge_mlp_fwd[H128]'), s.get('edge_mlp_bwd[H128]'))" | tee -a "$O/ab.log"
 }
 for i in 1 2 3; do

@@ -11,7 +11,7 @@ tail -6 "$O/pytest.log"
 for i in 1 2 3; do
   for v in "0 0" "1 0" "1 1"; do
     set -- $v
-    DOSX_NODE_CHAIN=$1 DOSX_DENSE_CHAIN=$2 timeout 300 python bench.py --allow-env --no-secondary --no-cpu-baseline --steps 200 2> /dev/null | \
+    DOSX_NODE_CHAIN=$1 DOSX_DENSE_CHAIN=$2 timeout 300 python bench.py --full --allow-env --no-secondary --no-cpu-baseline --steps 200 2> /dev/null | \
       python -c "import json,sys; r=json.loads(sys.stdin.read()); print('node_chain=$1 dense_chain=$2', r['ms_per_step'], r['check']['loss_last'], r['check']['replay_eq_eager'])" | tee -a "$O/ab.log"
   done
 done

@@ -6,7 +6,7 @@ mkdir -p "$O"
 cd "$R"
 run() {   # name, env...
   name=$1; shift
-  env "$@" timeout 300 python bench.py --allow-env --no-secondary --no-cpu-baseline --steps 200 2> /dev/null | \
+  env "$@" timeout 300 python bench.py --full --allow-env --no-secondary --no-cpu-baseline --steps 200 2> /dev/null | \
     python -c "import json,sys; r=json.loads(sys.stdin.read()); print('$name', r['ms_per_step'], r['check']['loss_last'], r['check']['replay_eq_eager'])" | tee -a "$O/ab.log"
 }
 for i in 1 2 3; do

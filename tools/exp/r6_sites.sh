@@ -7,7 +7,7 @@ O="$R/gpurun_out/r6_sites"
 mkdir -p "$O"
 cd "$R"
 for v in 0 1; do
-  env $V=$v timeout 300 python bench.py --allow-env --no-secondary --no-cpu-baseline --steps 100 --kernels-out "$O/sites_$v.json" 2> /dev/null > "$O/bench_$v.json"
+  env $V=$v timeout 300 python bench.py --full --allow-env --no-secondary --no-cpu-baseline --steps 100 --kernels-out "$O/sites_$v.json" 2> /dev/null > "$O/bench_$v.json"
 done
 python - <<PY
 import json

@@ -16,7 +16,7 @@ cd "$ROOT"
 cd /tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 900 rocprofv3 --pmc $c --output-format csv -d "$OUT/pmc_$c" -o pmc -- \
-    python3 "$ROOT/bench.py" --steps 20 --warmup 10 --no-cpu-baseline --no-secondary --kernels-out "$OUT/pmc_$c.kernels.json" > "$OUT/pmc_$c.log" 2>&1 < /dev/null
+    python3 "$ROOT/bench.py" --full --steps 20 --warmup 10 --no-cpu-baseline --no-secondary --kernels-out "$OUT/pmc_$c.kernels.json" > "$OUT/pmc_$c.log" 2>&1 < /dev/null
 done
 ff=$(find "$OUT/pmc_FETCH_SIZE" -name "*counter_collection.csv" | head -1)
 fw=$(find "$OUT/pmc_WRITE_SIZE" -name "*counter_collection.csv" | head -1)
@@ -29,7 +29,7 @@ fi
 # the same two passes over the Electron-DOS configuration: its sites carry `traffic` too
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 900 rocprofv3 --pmc $c --output-format csv -d "$OUT/pmc_edos_$c" -o pmc -- \
-    python3 "$ROOT/bench.py" --config edos_h256_b64 --steps 10 --warmup 5 --no-cpu-baseline --no-secondary --kernels-out "$OUT/pmc_edos_$c.kernels.json" > "$OUT/pmc_edos_$c.log" 2>&1 < /dev/null
+    python3 "$ROOT/bench.py" --full --config edos_h256_b64 --steps 10 --warmup 5 --no-cpu-baseline --no-secondary --kernels-out "$OUT/pmc_edos_$c.kernels.json" > "$OUT/pmc_edos_$c.log" 2>&1 < /dev/null
 done
 ef=$(find "$OUT/pmc_edos_FETCH_SIZE" -name "*counter_collection.csv" | head -1)
 ew=$(find "$OUT/pmc_edos_WRITE_SIZE" -name "*counter_collection.csv" | head -1)
@@ -40,9 +40,9 @@ fi
 # north_star IN THE STEP (round 6): MFMA-busy of every kernel of the replayed cfg2 and cfg3 steps (one pass each; program directly
 # after `--`), summarised per symbol + the launches that contain the attention / the scatter-add (tools/pmc_step.py)
 timeout 900 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d "$OUT/pmc_mfma_step" -o pmc -- \
-  python3 "$ROOT/bench.py" --steps 20 --warmup 10 --no-cpu-baseline --no-secondary --kernels-out "$OUT/pmc_mfma_step.kernels.json" > "$OUT/pmc_mfma_step.log" 2>&1 < /dev/null
+  python3 "$ROOT/bench.py" --full --steps 20 --warmup 10 --no-cpu-baseline --no-secondary --kernels-out "$OUT/pmc_mfma_step.kernels.json" > "$OUT/pmc_mfma_step.log" 2>&1 < /dev/null
 timeout 900 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d "$OUT/pmc_mfma_step_edos" -o pmc -- \
-  python3 "$ROOT/bench.py" --config edos_h256_b64 --steps 10 --warmup 5 --no-cpu-baseline --no-secondary --kernels-out "$OUT/pmc_mfma_step_edos.kernels.json" > "$OUT/pmc_mfma_step_edos.log" 2>&1 < /dev/null
+  python3 "$ROOT/bench.py" --full --config edos_h256_b64 --steps 10 --warmup 5 --no-cpu-baseline --no-secondary --kernels-out "$OUT/pmc_mfma_step_edos.kernels.json" > "$OUT/pmc_mfma_step_edos.log" 2>&1 < /dev/null
 ms=$(find "$OUT/pmc_mfma_step" -name "*counter_collection.csv" | head -1)
 me=$(find "$OUT/pmc_mfma_step_edos" -name "*counter_collection.csv" | head -1)
 if [ -n "$ms" ] && [ -f "$S/${R}_pmc_traffic.json" ]; then
@@ -77,7 +77,7 @@ fi
 # tools/kernel_only.py -> profiles/<round>_kernel_only*.json, hash-tagged)
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o st -- \
-  python3 "$ROOT/bench.py" --steps 100 --warmup 20 --no-cpu-baseline --no-secondary --kernels-out "$OUT/trace.kernels.json" > "$OUT/trace.log" 2>&1 < /dev/null
+  python3 "$ROOT/bench.py" --full --steps 100 --warmup 20 --no-cpu-baseline --no-secondary --kernels-out "$OUT/trace.kernels.json" > "$OUT/trace.log" 2>&1 < /dev/null
 f=$(find "$OUT/trace" -name "*kernel_stats.csv" | head -1)
 if [ -n "$f" ]; then
   cp "$f" "$S/${R}_bench_phonon_h128_b64_kernel_stats.csv"
@@ -85,7 +85,7 @@ if [ -n "$f" ]; then
   cp "$S/${R}_kernel_only.json" "$ROOT/profiles/${R}_kernel_only.json"
 fi
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_edos" -o st -- \
-  python3 "$ROOT/bench.py" --config edos_h256_b64 --steps 40 --warmup 10 --no-cpu-baseline --no-secondary --kernels-out "$OUT/trace_edos.kernels.json" > "$OUT/trace_edos.log" 2>&1 < /dev/null
+  python3 "$ROOT/bench.py" --full --config edos_h256_b64 --steps 40 --warmup 10 --no-cpu-baseline --no-secondary --kernels-out "$OUT/trace_edos.kernels.json" > "$OUT/trace_edos.log" 2>&1 < /dev/null
 f=$(find "$OUT/trace_edos" -name "*kernel_stats.csv" | head -1)
 if [ -n "$f" ]; then
   cp "$f" "$S/${R}_bench_edos_h256_b64_kernel_stats.csv"
@@ -94,15 +94,15 @@ if [ -n "$f" ]; then
 fi
 cd "$ROOT"
 # THE bench line (the driver's invocation: default flags; secondaries = eDOS H256 + shuffle inside the same record) + its per-site table
-timeout 600 python3 bench.py --kernels-out "$S/${R}_bench_phonon_h128_b64_sites.json" > "$S/${R}_bench_phonon_h128_b64.json" 2> "$OUT/bench_phonon.err" < /dev/null
-timeout 400 python3 bench.py --shuffle --no-cpu-baseline --no-secondary --kernels-out "$OUT/shuffle.kernels.json" > "$S/${R}_bench_phonon_h128_b64_shuffle.json" 2> "$OUT/bench_shuffle.err" < /dev/null
-timeout 500 python3 bench.py --config edos_h256_b64 --kernels-out "$S/${R}_bench_edos_h256_b64_sites.json" > "$S/${R}_bench_edos_h256_b64.json" 2> "$OUT/bench_edos.err" < /dev/null
+timeout 600 python3 bench.py --full --kernels-out "$S/${R}_bench_phonon_h128_b64_sites.json" > "$S/${R}_bench_phonon_h128_b64.json" 2> "$OUT/bench_phonon.err" < /dev/null
+timeout 400 python3 bench.py --full --shuffle --no-cpu-baseline --no-secondary --kernels-out "$OUT/shuffle.kernels.json" > "$S/${R}_bench_phonon_h128_b64_shuffle.json" 2> "$OUT/bench_shuffle.err" < /dev/null
+timeout 500 python3 bench.py --full --config edos_h256_b64 --kernels-out "$S/${R}_bench_edos_h256_b64_sites.json" > "$S/${R}_bench_edos_h256_b64.json" 2> "$OUT/bench_edos.err" < /dev/null
 timeout 300 python3 tools/bench_wgroup.py > "$S/${R}_wgrad_groups.log" 2> /dev/null < /dev/null
 # the three launches of a factored message-passing layer alone + their phase stamps (stamps build, if it travelled)
 timeout 200 python3 tools/bench_edge.py phonon 64 2> /dev/null < /dev/null | grep -v amdgpu.ids > "$S/${R}_edge_kernels.log"
 [ -f dostransformer_amd/csrc/build/libdosx_stamps.so ] && DOSX_LIB=dostransformer_amd/csrc/build/libdosx_stamps.so timeout 200 python3 tools/bench_edge.py phonon 64 2> /dev/null < /dev/null | grep -E "wave 0" >> "$S/${R}_edge_kernels.log"
 # the N > 1 bench path on this one GPU (two ranks share cuda:0 over gloo: plumbing check of the split replay plan, no scaling meaning)
-timeout 400 python3 bench.py --gpus 2 --dist-backend gloo --share-gpu --steps 20 --warmup 5 --no-cpu-baseline > "$S/${R}_bench_2ranks_shared_gpu.json" 2> "$OUT/bench_2ranks.err" < /dev/null
+timeout 400 python3 bench.py --full --gpus 2 --dist-backend gloo --share-gpu --steps 20 --warmup 5 --no-cpu-baseline > "$S/${R}_bench_2ranks_shared_gpu.json" 2> "$OUT/bench_2ranks.err" < /dev/null
 timeout 600 python3 tools/bench_kernels.py > "$S/${R}_kernel_microbench.log" 2> "$OUT/microbench.err" < /dev/null
 timeout 200 python3 tools/predict_latency.py 2> /dev/null | grep "^predict" >> "$S/${R}_kernel_microbench.log"
 ls -la "$S"
