@@ -21,6 +21,7 @@ from torch import nn
 
 from . import functional as Fn
 from . import ops
+from ._lib import DosxError
 from .batch import GraphMeta, graph_meta
 
 _DEAD = re.compile(r"(\.self_attn\.)|(\.node_mlp_1\.)|(^alpha$)")
@@ -50,9 +51,10 @@ def is_last_param(name: str) -> bool:
 
 
 class FlatParams:
-    """Flat fp32 parameter + gradient storage for the live parameters of a module."""
+    """Flat parameter + gradient storage for the live parameters of a module: fp32, or fp64 for a module that runs the
+    float64 program (FusedModel._flat_dtype)."""
 
-    def __init__(self, module: nn.Module, device: torch.device, extra_dead=()):
+    def __init__(self, module: nn.Module, device: torch.device, extra_dead=(), dtype: torch.dtype = torch.float32):
         live = [(n, p) for n, p in module.named_parameters() if not (is_dead_param(n) or n in extra_dead)]
         # layout: [ last bucket (encoders + layer 0) | mid bucket (rest of the GNN trunk) | early bucket (everything else) ],
         # each in module order; [last | mid] together are the "late" slice flat[:n_late]
@@ -70,15 +72,16 @@ class FlatParams:
         self.names, self.offsets, self.total = names, offs, tot
         self.n_late = n_late          # floats: flat[:n_late] is the GNN trunk, flat[n_late:] the early bucket
         self.n_last = n_last          # floats: flat[:n_last] the last bucket, flat[n_last:n_late] the mid bucket
-        self.flat = torch.zeros(tot, device=device, dtype=torch.float32)
-        self.grad = torch.zeros(tot, device=device, dtype=torch.float32)
+        self.dtype = dtype
+        self.flat = torch.zeros(tot, device=device, dtype=dtype)
+        self.grad = torch.zeros(tot, device=device, dtype=dtype)
         self.P: Dict[str, torch.Tensor] = {}
         self.G: Dict[str, torch.Tensor] = {}
         self.params: Dict[str, nn.Parameter] = {}
         with torch.no_grad():
             for n, p, o in zip(names, params, offs):
                 view = self.flat[o:o + p.numel()].view(p.shape)
-                view.copy_(p.detach().to(device=device, dtype=torch.float32))
+                view.copy_(p.detach().to(device=device, dtype=dtype))
                 p.data = view
                 self.P[n] = view
                 self.G[n] = self.grad[o:o + p.numel()].view(p.shape)
@@ -87,11 +90,11 @@ class FlatParams:
             if n not in self.P and p.device != device:
                 p.data = p.data.to(device)
         self.anchor = params[0]
-        self.anchor_ptr = self.flat.data_ptr() + 4 * offs[0]
+        self.anchor_ptr = self.flat.data_ptr() + self.flat.element_size() * offs[0]
 
     def intact(self, device: torch.device) -> bool:
         return self.flat.device == device and self.anchor.data_ptr() == self.anchor_ptr and \
-            self.anchor.dtype == torch.float32
+            self.anchor.dtype == self.dtype
 
     def publish_grads(self, G: Dict[str, torch.Tensor], accumulate_into_existing: bool) -> None:
         for n, p in self.params.items():
@@ -137,15 +140,37 @@ class FusedModel(nn.Module):
     backward through the libdosx programs."""
 
     _flat: Optional[FlatParams] = None
+    _has_f64_program = False      # a float64 phonon module of this class runs functional64 (else: the fp32 program, as before)
 
     def _extra_dead(self, g) -> Tuple[str, ...]:
         return ()
+
+    def _flat_dtype(self, g=None) -> torch.dtype:
+        """float64 for a Graphnetwork_phonon whose live parameters are all float64 (the reference's phonon setup,
+        main_phDOS.py:15-16), float32 otherwise - as before for every other module: eDOS modules compute in fp32 whatever
+        their dtype (their reference is fp32, data/mat2graph.py:127-131), and DOSTransformer_phonon has no float64 program
+        yet, so a float64 one keeps today's fp32 computation with float64 outputs.  Raises DosxError where a module that
+        would run the float64 program cannot."""
+        if not self._has_f64_program or self._cfg.kind != "phonon":
+            return torch.float32
+        dead = self._extra_dead(g)
+        dts = {p.dtype for n, p in self.named_parameters() if not (is_dead_param(n) or n in dead)}
+        if torch.float64 not in dts:
+            return torch.float32
+        name = type(self).__name__
+        if len(dts) > 1:
+            raise DosxError(f"{name}: live parameters mix {sorted(str(d) for d in dts)}; a float64 module needs all of them "
+                            f"float64 (.double())")
+        from .functional64 import MAX_HIDDEN
+        if self._cfg.H > MAX_HIDDEN:
+            raise DosxError(f"{name}: the float64 program takes hidden <= {MAX_HIDDEN}, got {self._cfg.H}")
+        return torch.float64
 
     def _ensure_flat(self, device: torch.device, g) -> FlatParams:
         dead = self._extra_dead(g)
         fp = self._flat
         if fp is None or not fp.intact(device) or getattr(self, "_flat_dead", ()) != dead:
-            fp = FlatParams(self, device, dead)
+            fp = FlatParams(self, device, dead, self._flat_dtype(g))
             object.__setattr__(self, "_flat", fp)
             object.__setattr__(self, "_flat_dead", dead)
         return fp
@@ -168,6 +193,8 @@ class FusedModel(nn.Module):
             out = _ModelFn.apply(fp.anchor, self, g, m)
         else:
             out = self._program_fwd(fp.P, g, m)[:-1]
+        if fp.dtype == torch.float64:
+            return out              # the float64 program: float64 outputs whatever the batch dtype
         # The kernels compute in fp32.  A float64 batch (the phonon reference sets the default dtype to float64,
         # main_phDOS.py:15-16) gets float64 outputs back, like upstream: the caller's MSELoss against its float64 target
         # then back-propagates a float64 gradient, which this (autograd-aware) cast turns into the fp32 one the backward

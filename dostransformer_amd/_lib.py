@@ -278,6 +278,31 @@ class Collate(C.Structure):
                [(k, C.c_void_p) for k in ("out_tile_ptr", "tile_off_all", "tile_e_all", "tile_n_all", "seg_tile", "tile_p_all")]
 
 
+class Seg64(C.Structure):
+    _fields_ = [("p", C.c_void_p), ("ld", C.c_int32), ("width", C.c_int32), ("map", RowMap)]
+
+
+class Gemm64(C.Structure):
+    _fields_ = [
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("nseg", C.c_int32),
+        ("a", Seg64 * 3),
+        ("w", C.c_void_p), ("ldw", C.c_int32), ("w_layout", C.c_int32),
+        ("act", C.c_int32), ("alpha", C.c_void_p), ("bias", C.c_void_p),
+        ("out", C.c_void_p), ("ldo", C.c_int32), ("pre", C.c_void_p),
+        ("res", C.c_void_p), ("ldr", C.c_int32),
+    ]
+
+
+class Wgrad64(C.Structure):
+    _fields_ = [
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
+        ("dy", C.c_void_p), ("lddy", C.c_int32),
+        ("nseg", C.c_int32), ("x", Seg64 * 3),
+        ("dw", C.c_void_p), ("ldd", C.c_int32), ("accumulate", C.c_int32), ("nsplit", C.c_int32),
+        ("partials", C.c_void_p),
+    ]
+
+
 class Call(C.Structure):
     _fields_ = [("op", C.c_int32), ("nint", C.c_int32), ("nflt", C.c_int32), ("reserved", C.c_int32),
                 ("iarg", C.c_int64 * 19), ("farg", C.c_double * 6)]
@@ -387,6 +412,19 @@ _SIGS = {
     "dosx_embed_rows_bwd": [_P, _I, _P, _P, _I, _I, _I, _P],
     "dosx_reduce_rows": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "dosx_act_bwd": [_P, _P, _F, _P, _L, _P],
+    "dosx_gemm_f64": [C.POINTER(Gemm64), _P],
+    "dosx_wgrad_f64": [C.POINTER(Wgrad64), _P],
+    "dosx_colsum_f64": [_P, _I, _I, _I, _P, _P, _I, _P],
+    "dosx_layernorm_f64": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "dosx_layernorm_bwd_f64": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "dosx_act_bwd_f64": [_P, _P, _I, _I, _P, _P, _P, _I, _I, _P],
+    "dosx_edge_feat_sh1_f64": [_P, _P, _I, _D, _P],
+    "dosx_segment_mean_f64": [_P, _P, _P, _I, _I, _P],
+    "dosx_segment_mean_bwd_f64": [_P, _I, _P, _P, _P, _P, _I, _I, _P],
+    "dosx_gather_bwd_f64": [_P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _P],
+    "dosx_graph_pool_f64": [_P, _P, _P, _I, _I, _P],
+    "dosx_rows_add_f64": [_P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P],
+    "dosx_reduce_rows_f64": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "dosx_last_error": [],
     "dosx_version": [],
 }

@@ -8,6 +8,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import functional as Fn
+from . import functional64 as F64
 from ._fused import FusedModel
 
 
@@ -76,6 +77,7 @@ class DOSTransformerBase(FusedModel):
 class GraphnetworkBase(FusedModel):
     _cfg: Fn.ModelCfg
     _returns_x: bool
+    _has_f64_program = True       # Graphnetwork_phonon (the kind check of _flat_dtype keeps the eDOS Graphnetwork in fp32)
 
     def _extra_dead(self, g) -> Tuple[str, ...]:
         # Encoder picks node_encoder or node_encoder_prompt by input width
@@ -86,11 +88,19 @@ class GraphnetworkBase(FusedModel):
         return tuple(f"{unused}.{s}" for s in ("0.weight", "0.bias", "1.weight", "2.weight", "2.bias"))
 
     def _program_fwd(self, P, g, m):
+        if P["embeddings.weight"].dtype == torch.float64:
+            dos, ctx = F64.graphnetwork_phonon_fwd(P, self._cfg, g, m)
+            return dos, ctx
         dos, xL, ctx = Fn.graphnetwork_fwd(P, self._cfg, g, m)
         return (dos, xL, ctx) if self._returns_x else (dos, ctx)
 
     def _program_bwd(self, P, G, m, saved, grads, sink):
         ddos = grads[0]
+        if P["embeddings.weight"].dtype == torch.float64:
+            if ddos is None:
+                ddos = torch.zeros(m.num_graphs, self._cfg.S, device=P["embeddings.weight"].device, dtype=torch.float64)
+            F64.graphnetwork_phonon_bwd(P, G, self._cfg, m, saved, ddos)
+            return
         dx = grads[1] if self._returns_x else None
         if ddos is None:
             ddos = torch.zeros(m.num_graphs, self._cfg.S, device=P["embeddings.weight"].device)

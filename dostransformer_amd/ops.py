@@ -1563,3 +1563,173 @@ def neighbor_list(pos: torch.Tensor, cell: torch.Tensor, atom_ptr: torch.Tensor,
         edge_ptr[1:] = incl[ends]
     out["edge_ptr"] = edge_ptr
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# float64 program (csrc/f64.hip, include/dosx.h "float64 program"): thin wrappers, used by functional64.py
+# ---------------------------------------------------------------------------------------------------------------------
+ACT64_NONE, ACT64_RELU, ACT64_LEAKY, ACT64_PRELU = 0, 1, 2, 3
+COLSUM64_ROWS = 256                    # DOSX_COLSUM64_ROWS
+_WGRAD64_ROWS = 512                    # rows of M per split of dosx_wgrad_f64
+
+
+def _chk_f64(*ts):
+    for t in ts:
+        if t is not None and (t.dtype != torch.float64 or not t.is_cuda or t.stride(-1) != 1):
+            raise TypeError(f"dosx fp64 ops need float64 CUDA tensors with unit inner stride, got {t.dtype} on {t.device}")
+
+
+def _chk_c64(*ts):
+    """fp64 operands the kernels index with their logical row width (no row stride argument): must be contiguous."""
+    _chk_f64(*ts)
+    for t in ts:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"dosx fp64 op needs a contiguous operand here, got shape {tuple(t.shape)} strides {t.stride()}")
+
+
+def alloc64(device, *shape) -> torch.Tensor:
+    return torch.empty(shape, device=device, dtype=torch.float64)
+
+
+def seg64(t: torch.Tensor, rmap: Optional[RowMap] = None) -> _lib.Seg64:
+    """A K-segment: all columns of the 2-D fp64 tensor (or column slice) ``t``, rows through ``rmap``."""
+    _chk_f64(t)
+    assert t.dim() == 2
+    return _lib.Seg64(t.data_ptr(), t.stride(0), t.shape[1], rmap if rmap is not None else ident())
+
+
+def gemm64(M: int, N: int, segs: Sequence[_lib.Seg64], w: torch.Tensor, out: torch.Tensor, *, w_layout: int = 0,
+           bias=None, act: int = ACT64_NONE, alpha=None, pre=None, res=None) -> torch.Tensor:
+    """out[M,N] = act(cat(segs) @ op(w) + bias) + res; ``pre`` (optional) receives acc + bias.  w_layout 0: w[N,K], 1: w[K,N]."""
+    _chk_f64(w, out, bias, alpha, pre, res)
+    assert pre is None or pre.stride(0) == out.stride(0), "pre shares the row stride of out (DosxGemm64.ldo)"
+    d = _lib.Gemm64()
+    d.M, d.N, d.K, d.nseg = M, N, sum(s.width for s in segs), len(segs)
+    for i, s in enumerate(segs):
+        d.a[i] = s
+    d.w, d.ldw, d.w_layout = w.data_ptr(), w.stride(0), w_layout
+    d.act, d.alpha, d.bias = act, _p(alpha), _p(bias)
+    d.out, d.ldo, d.pre = out.data_ptr(), out.stride(0), _p(pre)
+    d.res, d.ldr = _p(res), (res.stride(0) if res is not None else 0)
+    _call("dosx_gemm_f64", C.byref(d), _stream())
+    return out
+
+
+def wgrad64(M: int, dy: torch.Tensor, segs: Sequence[_lib.Seg64], dw: torch.Tensor, accumulate: bool = False) -> None:
+    """dw[N,K] (+)= dy[M,N]^T @ cat(segs)[M,K], split over M with a fixed-order reduction of the splits."""
+    _chk_f64(dy, dw)
+    N, K = dw.shape
+    d = _lib.Wgrad64()
+    d.M, d.N, d.K = M, N, K
+    d.dy, d.lddy = dy.data_ptr(), dy.stride(0)
+    d.nseg = len(segs)
+    for i, s in enumerate(segs):
+        d.x[i] = s
+    d.dw, d.ldd, d.accumulate = dw.data_ptr(), dw.stride(0), int(accumulate)
+    d.nsplit = max(1, min(64, M // _WGRAD64_ROWS))
+    part = alloc64(dw.device, d.nsplit, N, K) if d.nsplit > 1 else None
+    d.partials = _p(part)
+    _call("dosx_wgrad_f64", C.byref(d), _stream())
+
+
+def colsum64(src: torch.Tensor, out: torch.Tensor, accumulate: bool = False) -> None:
+    """out[N] (+)= src[M,N].sum(0), rows added in order."""
+    _chk_f64(src)
+    _chk_c64(out)
+    M, N = src.shape
+    part = alloc64(src.device, (M + COLSUM64_ROWS - 1) // COLSUM64_ROWS, N) if M > COLSUM64_ROWS else None
+    _call("dosx_colsum_f64", src.data_ptr(), M, N, src.stride(0), _p(part), out.data_ptr(), int(accumulate), _stream())
+
+
+def layernorm64(z: torch.Tensor, gamma, beta, alpha=None):
+    """(xhat, rstd, prelu(LN(z)) or LN(z)) of z [M,W], eps 1e-5."""
+    _chk_c64(z, gamma, beta, alpha)
+    M, W = z.shape
+    xhat, rstd, out = alloc64(z.device, M, W), alloc64(z.device, M), alloc64(z.device, M, W)
+    _call("dosx_layernorm_f64", z.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _p(alpha), xhat.data_ptr(), rstd.data_ptr(),
+          out.data_ptr(), M, W, _stream())
+    return xhat, rstd, out
+
+
+def layernorm_bwd64(dout: torch.Tensor, xhat, rstd, gamma, beta, alpha=None):
+    """(dz [M,W], part [M, 2W+1]): column sums of part are dgamma | dbeta | dalpha."""
+    _chk_c64(dout, xhat, rstd, gamma, beta, alpha)
+    M, W = xhat.shape
+    dz, part = alloc64(xhat.device, M, W), alloc64(xhat.device, M, 2 * W + 1)
+    _call("dosx_layernorm_bwd_f64", dout.data_ptr(), xhat.data_ptr(), rstd.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+          _p(alpha), dz.data_ptr(), part.data_ptr(), M, W, _stream())
+    return dz, part
+
+
+def act_bwd64(dy: torch.Tensor, z: torch.Tensor, act: int, alpha=None):
+    """(dz, part): dz = dy * act'(z); part [M,1] the per-row dalpha terms for ACT64_PRELU (else None)."""
+    _chk_c64(dy, alpha)                  # dy: row stride W; z: its own row stride
+    _chk_f64(z)
+    M, W = dy.shape
+    dz = alloc64(dy.device, M, W)
+    part = alloc64(dy.device, M, 1) if act == ACT64_PRELU else None
+    _call("dosx_act_bwd_f64", dy.data_ptr(), z.data_ptr(), z.stride(0), act, _p(alpha), dz.data_ptr(), _p(part), M, W,
+          _stream())
+    return dz, part
+
+
+def edge_feat_sh1_64(edge_vec: torch.Tensor, r_max: float = 4.0) -> torch.Tensor:
+    _chk_c64(edge_vec)
+    assert edge_vec.dim() == 2 and edge_vec.shape[1] == 3, tuple(edge_vec.shape)
+    E = edge_vec.shape[0]
+    out = alloc64(edge_vec.device, E, 4)
+    _call("dosx_edge_feat_sh1_f64", edge_vec.data_ptr(), out.data_ptr(), E, C.c_double(r_max), _stream())
+    return out
+
+
+def segment_mean64(src: torch.Tensor, rowptr: torch.Tensor, N: int) -> torch.Tensor:
+    _chk_c64(src)
+    out = alloc64(src.device, N, src.shape[1])
+    _call("dosx_segment_mean_f64", src.data_ptr(), rowptr.data_ptr(), out.data_ptr(), N, src.shape[1], _stream())
+    return out
+
+
+def segment_mean_bwd64(dagg: torch.Tensor, dst, rowptr, res: Optional[torch.Tensor], E: int) -> torch.Tensor:
+    _chk_f64(dagg)
+    _chk_c64(res)
+    H = dagg.shape[1]
+    out = alloc64(dagg.device, E, H)
+    _call("dosx_segment_mean_bwd_f64", dagg.data_ptr(), dagg.stride(0), dst.data_ptr(), rowptr.data_ptr(), _p(res),
+          out.data_ptr(), E, H, _stream())
+    return out
+
+
+def gather_bwd64(dcat: torch.Tensor, m, base0: Optional[torch.Tensor], base1: Optional[torch.Tensor], N: int, H: int):
+    _chk_f64(dcat, base0, base1)
+    dx = alloc64(dcat.device, N, H)
+    _call("dosx_gather_bwd_f64", dcat.data_ptr(), dcat.stride(0), m.rowptr_src.data_ptr(), m.perm_src.data_ptr(),
+          m.rowptr_dst.data_ptr(), _p(base0), base0.stride(0) if base0 is not None else 0, _p(base1),
+          base1.stride(0) if base1 is not None else 0, dx.data_ptr(), N, H, _stream())
+    return dx
+
+
+def graph_pool64(x: torch.Tensor, graph_ptr: torch.Tensor, B: int) -> torch.Tensor:
+    _chk_c64(x)
+    out = alloc64(x.device, B, x.shape[1])
+    _call("dosx_graph_pool_f64", x.data_ptr(), graph_ptr.data_ptr(), out.data_ptr(), B, x.shape[1], _stream())
+    return out
+
+
+def rows_add64(M: int, a: torch.Tensor, b: Optional[torch.Tensor] = None, ia=None, ib=None) -> torch.Tensor:
+    """out[r] = a[ia[r] or r] + b[ib[r] or r], [M, width of a]."""
+    _chk_f64(a, b)
+    W = a.shape[1]
+    out = alloc64(a.device, M, W)
+    _call("dosx_rows_add_f64", a.data_ptr(), a.stride(0), _p(ia), _p(b), b.stride(0) if b is not None else 0, _p(ib),
+          out.data_ptr(), W, M, W, _stream())
+    return out
+
+
+def reduce_rows64(src: torch.Tensor, n_out: int, n_red: int, stride_out: int, stride_red: int) -> torch.Tensor:
+    """out[i] = sum_{j < n_red} src[i * stride_out + j * stride_red] (rows added in order of j)."""
+    _chk_f64(src)
+    W = src.shape[1]
+    out = alloc64(src.device, n_out, W)
+    _call("dosx_reduce_rows_f64", src.data_ptr(), src.stride(0), out.data_ptr(), W, n_out, n_red, stride_out, stride_red, W, 0,
+          _stream())
+    return out

@@ -967,6 +967,103 @@ int dosx_reduce_rows(const float* src, int ld_src, float* dst, int ld_dst, int n
 /* out = dy * (y > 0 ? 1 : slope): backward of F.leaky_relu (DOSTransformer_phonon.py:95) from its output. */
 int dosx_act_bwd(const float* dy, const float* y, float slope, float* out, int64_t n, dosx_stream_t stream);
 
+/* ---- float64 program (csrc/f64.hip) -------------------------------------------------------------------------------------
+ * The phonon reference computes in float64 (main_phDOS.py:15-16).  A Graphnetwork_phonon whose live parameters are float64
+ * runs these entry points instead of the fp32 ones above.  Everything here is fp64 row-major (index data int32) and
+ * deterministic: no atomics on data, every reduction in a fixed order.  Matrix products use v_mfma_f64_16x16x4_f64. */
+
+/* One K-segment of an fp64 operand: columns [0, width) of rows map(r) of p (row stride ld doubles). */
+typedef struct DosxSeg64 {
+  const double* p;
+  int32_t ld;
+  int32_t width;
+  DosxRowMap map;
+} DosxSeg64;
+
+/* act of dosx_gemm_f64 */
+enum { DOSX_ACT64_NONE = 0, DOSX_ACT64_RELU = 1, DOSX_ACT64_LEAKY = 2 /* slope 0.01 */, DOSX_ACT64_PRELU = 3 /* *alpha */ };
+
+/* out[M,N] = act(cat_k(A segments)[M,K] * op(W) + bias) + res
+ *   w_layout 0: W[N,K] (y = x W^T, nn.Linear forward); 1: W[K,N] (dx = dy W, input gradients).
+ *   pre (optional): the pre-activation acc + bias, [M, ldo]; res (optional): [M, ldr] added after the activation.
+ * K = sum of the segment widths (any value >= 1: the k tail of every segment is zero-padded). */
+typedef struct DosxGemm64 {
+  int32_t M, N, K;
+  int32_t nseg;
+  DosxSeg64 a[3];
+  const double* w;
+  int32_t ldw;
+  int32_t w_layout;
+  int32_t act;
+  const double* alpha; /* device scalar, ACT64_PRELU */
+  const double* bias;  /* [N] or NULL */
+  double* out;
+  int32_t ldo;
+  double* pre;
+  const double* res;
+  int32_t ldr;
+} DosxGemm64;
+
+/* dw[N,K] (+)= dy[M,N]^T * cat_k(X segments)[M,K]  (weight gradient of y = x W^T).  M is cut into nsplit row ranges; with
+ * nsplit > 1 each range writes its own slice of partials [nsplit, N, K] and a second launch adds the slices in order. */
+typedef struct DosxWgrad64 {
+  int32_t M, N, K;
+  const double* dy;
+  int32_t lddy;
+  int32_t nseg;
+  DosxSeg64 x[3];
+  double* dw;
+  int32_t ldd;
+  int32_t accumulate;
+  int32_t nsplit;
+  double* partials; /* [nsplit, N, K], needed when nsplit > 1 */
+} DosxWgrad64;
+
+int dosx_gemm_f64(const DosxGemm64* desc_host, dosx_stream_t stream);
+int dosx_wgrad_f64(const DosxWgrad64* desc_host, dosx_stream_t stream);
+/* out[0:N] (+)= column sums of src[M,N] (row stride ld), rows added in order.  partials: [ceil(M/DOSX_COLSUM64_ROWS), N]
+ * scratch, needed when M > DOSX_COLSUM64_ROWS. */
+#define DOSX_COLSUM64_ROWS 256
+int dosx_colsum_f64(const double* src, int M, int N, int ld, double* partials, double* out, int accumulate,
+                    dosx_stream_t stream);
+/* LayerNorm (eps 1e-5) of z[M,W] with affine gamma / beta, then PReLU(*alpha) when alpha != NULL:
+ * out = prelu(xhat * gamma + beta); saves xhat [M,W] and rstd [M].  W <= 1024. */
+int dosx_layernorm_f64(const double* z, const double* gamma, const double* beta, const double* alpha, double* xhat,
+                       double* rstd, double* out, int M, int W, dosx_stream_t stream);
+/* Backward of dosx_layernorm_f64: dz [M,W] from dout; part [M, 2W+1] = per row dout_y*xhat | dout_y | dalpha term
+ * (dosx_colsum_f64 of part gives dgamma | dbeta | dalpha). */
+int dosx_layernorm_bwd_f64(const double* dout, const double* xhat, const double* rstd, const double* gamma,
+                           const double* beta, const double* alpha, double* dz, double* part, int M, int W,
+                           dosx_stream_t stream);
+/* Activation backward from the pre-activation z [M,W] (rows of stride ld): dz = dy * act'(z).  act: ACT64_*; for PRELU,
+ * part [M] gets the per-row dalpha term sum_c dy*z*(z<0) (NULL otherwise). */
+int dosx_act_bwd_f64(const double* dy, const double* z, int ld, int act, const double* alpha, double* dz, double* part,
+                     int M, int W, dosx_stream_t stream);
+/* out[e] = smooth_cutoff(|v|/r_max) * [1, sqrt3 v/max(|v|,1e-12)]  (DOSTransformer_phonon.py:74-77), out [E,4] */
+int dosx_edge_feat_sh1_f64(const double* edge_vec, double* out, int E, double r_max, dosx_stream_t stream);
+/* out[n] = sum_{e in [rowptr[n], rowptr[n+1])} src[e] / max(in-degree, 1)  (scatter_mean over destinations) */
+int dosx_segment_mean_f64(const double* src, const int32_t* rowptr, double* out, int N, int H, dosx_stream_t stream);
+/* Backward of the mean aggregation plus the edge residual: out[e] = res[e] + dagg[dst[e]] / max(in-degree(dst[e]), 1)
+ * (res may be NULL; dagg rows of stride ld_dagg). */
+int dosx_segment_mean_bwd_f64(const double* dagg, int ld_dagg, const int32_t* dst, const int32_t* rowptr,
+                              const double* res, double* out, int E, int H, dosx_stream_t stream);
+/* Gradient of the node operands of cat[x[src], x[dst], .] as CSR sums in a fixed order:
+ * dx[n] = base0[n] + base1[n] + sum_{k in [rowptr_src[n], rowptr_src[n+1])} dcat[perm_src[k], 0:H]
+ *                             + sum_{e in [rowptr_dst[n], rowptr_dst[n+1])} dcat[e, H:2H]
+ * (base0 / base1 optional, rows of stride ld0 / ld1; dcat rows of stride ldc). */
+int dosx_gather_bwd_f64(const double* dcat, int ldc, const int32_t* rowptr_src, const int32_t* perm_src,
+                        const int32_t* rowptr_dst, const double* base0, int ld0, const double* base1, int ld1,
+                        double* dx, int N, int H, dosx_stream_t stream);
+/* out[b] = sum_{n in [graph_ptr[b], graph_ptr[b+1])} x[n]  (scatter_sum over crystals, nodes in crystal order) */
+int dosx_graph_pool_f64(const double* x, const int32_t* graph_ptr, double* out, int B, int H, dosx_stream_t stream);
+/* out[r] = a[ia ? ia[r] : r] + b[ib ? ib[r] : r]  (rows of width W; b optional): residual adds and the backward of a
+ * row broadcast (dx += dpool[node_graph]) */
+int dosx_rows_add_f64(const double* a, int lda, const int32_t* ia, const double* b, int ldb, const int32_t* ib,
+                      double* out, int ldo, int M, int W, dosx_stream_t stream);
+/* dst[i, 0:width] (+)= sum_{j < n_red} src[(i*stride_out + j*stride_red), 0:width]  (fp64 dosx_reduce_rows) */
+int dosx_reduce_rows_f64(const double* src, int ld_src, double* dst, int ld_dst, int n_out, int n_red, int stride_out,
+                         int stride_red, int width, int accumulate, dosx_stream_t stream);
+
 const char* dosx_last_error(void);
 int dosx_version(void);
 
