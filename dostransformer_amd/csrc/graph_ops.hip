@@ -574,8 +574,10 @@ __global__ __launch_bounds__(256) void gather_add_rownorm_kernel(const float* __
   if (lane == 0) rstd_out[r] = rstd;
 }
 
-__global__ __launch_bounds__(256) void mask_residual_kernel(const float* __restrict__ a, int lda, const float* __restrict__ mask,
-                                                            const float* __restrict__ res, int ldr, float* __restrict__ out,
+// `a` and `out` may be the same rows (in place, functional.py: the dropped feed-forward activation), so neither is __restrict__:
+// each lane reads an element before it writes it, and lanes touch disjoint elements.
+__global__ __launch_bounds__(256) void mask_residual_kernel(const float* a, int lda, const float* __restrict__ mask,
+                                                            const float* __restrict__ res, int ldr, float* out,
                                                             int ldo, float* __restrict__ stats, int M, int H) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);

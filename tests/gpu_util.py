@@ -23,6 +23,24 @@ def err(a, b):
     a, b = a.detach(), b.detach()
     return float((a.double() - b.double()).abs().max() / (b.double().abs().max() + 1e-12))
 
+EPS32 = 2.0 ** -24       # unit roundoff of fp32
+
+
+def bound_ratio(got, ref64, scale64, c, what=None):
+    """Worst element-wise |got - ref64| / (c * 2**-24 * scale64); <= 1 passes.  ref64: the float64 result on the same (fp32)
+    inputs; scale64 (broadcast against ref64): each element's own operand magnitude - sum of |a|.|b| for products and sums, the
+    row's scale for row normalisations - so a wrong small row is judged on its own size, not against the largest row (err()).
+    A zero bound demands an exact result; NaN / Inf in `got` fail.  Prints the ratio when `what` names the check."""
+    d = (got.detach().double() - ref64.detach().double()).abs()
+    lim = (c * EPS32) * torch.as_tensor(scale64, dtype=torch.float64, device=d.device).expand_as(d)
+    inf = torch.full_like(d, math.inf)
+    r = torch.where(lim > 0, d / torch.where(lim > 0, lim, torch.ones_like(lim)), torch.where(d > 0, inf, torch.zeros_like(d)))
+    r = torch.where(torch.isnan(d), inf, r)
+    worst = float(r.max()) if r.numel() else 0.0
+    if what is not None:
+        print(f"bound[{what}]: worst error / (c={c} x 2^-24 x scale) = {worst:.3g}")
+    return worst
+
 def prelu(x, a):
     return torch.where(x >= 0, x, a * x)
 

@@ -27,6 +27,59 @@ def test_attention_fwd_bwd(Sq, Bq, Nk, Bk, H, bcast, pkv, drop):
     """pkv: the dq kernel also produces the per-tile dK + dV partials and a reduction kernel finishes the key gradient
     (Nk <= 64; DosxAttn.dkv_part) instead of the streamed dkv kernel behind the dscores round trip.  Beyond the shapes that
     path covers, a given dkv_part is left alone and the streamed dkv kernel runs (include/dosx.h)."""
+    _attention_case(Sq, Bq, Nk, Bk, H, bcast, pkv, drop)
+
+
+# Template boundaries of dosx_attention_fwd / _bwd (csrc/attention.hip), checked from both sides.  With the crystal-aligned
+# kernels off (aligned mode 0): keys per lane of the row phases NJ = 1 (Nk <= 16), 3 (17..48), 4 (49..64), 13 (65..208),
+# 20 (209..320), the general kernels beyond 320; the streamed dkv kernel's key group kg = 2 above 32 keys; QT = 32 query rows
+# per workgroup (Sq 1 / 32 / 33).  LDS residency (fwd_smem / dq_smem against 160 KiB): the forward keeps every key chunk
+# resident for all Nk <= 64 up to H 256 (H 256, Nk 64: 131 KiB) and never beyond 64 keys; the partial-dK/dV path fits for
+# all Nk <= 64 up to H 256 (H 256, Nk 64: 147 KiB: pkv_supported) and never beyond; the dq kernel with it keeps the keys
+# resident at H 128 (Nk 64: 104 KiB) and at H 256 up to 32 keys (157 KiB) but not from 33 keys (172 KiB); without it at every
+# Nk <= 64.  Default mode: the forward of Nk <= 64 at H 64 / 128 / 256 runs csrc/attention_aligned.hip instead (keys padded to
+# 16, 32 query rows per tile), and with pkv the one-launch backward (dkv_cnt) runs there too; elsewhere attention.hip's.
+BOUNDARY_SHAPES = [
+    (51, 4, 16, 4, 128, False),    # NJ 1, last
+    (51, 4, 17, 4, 128, False),    # NJ 3, first
+    (33, 3, 32, 3, 256, False),    # NJ 3, kg 1 (last), pkv dq resident at H 256 (last)
+    (33, 3, 33, 3, 256, False),    # NJ 3, kg 2 (first), pkv dq NOT resident at H 256 (first)
+    (32, 2, 48, 2, 64, False),     # NJ 3, last; one full query tile
+    (51, 2, 49, 2, 64, False),     # NJ 4, first
+    (70, 3, 64, 3, 128, False),    # NJ 4, last; pkv dq resident at H 128
+    (70, 3, 64, 3, 256, False),    # NJ 4, last; pkv dq not resident at H 256
+    (51, 2, 65, 2, 128, False),    # NJ 13, first: no pkv, no resident forward
+    (20, 3, 208, 3, 64, False),    # NJ 13, last
+    (20, 3, 209, 3, 64, False),    # NJ 20, first
+    (9, 2, 320, 2, 128, False),    # NJ 20, last fused shape (MAX_FUSED_NK)
+    (1, 4, 16, 2, 128, False),     # one query row, Bq = 2 Bk
+    (1, 3, 64, 3, 256, False),     # one query row at H 256
+    (32, 2, 33, 2, 128, False),    # exactly one query tile
+    (33, 2, 48, 2, 16, False),     # H 16: never aligned
+    (33, 2, 17, 1, 64, True),      # broadcast query rows, two query tiles
+    (51, 6, 64, 3, 64, True),      # broadcast, Bq = 2 Bk, 64 keys
+]
+
+
+@pytest.mark.parametrize("Sq,Bq,Nk,Bk,H,bcast", BOUNDARY_SHAPES)
+@pytest.mark.parametrize("drop", [0.0, 0.35])
+@pytest.mark.parametrize("pkv", [False, True])
+@pytest.mark.parametrize("mode", ["streamed", "default"])
+def test_attention_fwd_bwd_at_template_boundaries(Sq, Bq, Nk, Bk, H, bcast, pkv, drop, mode):
+    """test_attention_fwd_bwd's assertions at each side of the template boundaries: aligned mode 0 (attention.hip's streamed
+    templates at every shape) and the default mode (the crystal-aligned kernels where they take the shape)."""
+    from dostransformer_amd import _lib
+    lib = _lib.load()
+    assert bool(lib.dosx_attention_pkv_supported(Nk, H)) == (Nk <= 64)
+    prev = lib.dosx_attention_aligned_mode(0 if mode == "streamed" else -1)
+    try:
+        _attention_case(Sq, Bq, Nk, Bk, H, bcast, pkv, drop, one_launch=(mode == "default"))
+    finally:
+        lib.dosx_attention_aligned_mode(prev)
+
+
+def _attention_case(Sq, Bq, Nk, Bk, H, bcast, pkv, drop, one_launch=False):
+    """one_launch: with the partial-dK/dV path, also hand the backward its crystal counters (DosxAttn.dkv_cnt)."""
     from dostransformer_amd import _lib
     pkv_path = pkv and bool(_lib.load().dosx_attention_pkv_supported(Nk, H))
     assert pkv_path or not pkv or Nk > 64
@@ -76,6 +129,8 @@ def test_attention_fwd_bwd(Sq, Bq, Nk, Bk, H, bcast, pkv, drop):
     if pkv_path:
         a.dscores = None
         dkv += 0.5                           # accumulate flag: the reduction adds onto what is there
+        if one_launch:
+            a.dkv_cnt = o.COUNTERS.take(DEV, Bk)
     o.attention_bwd(a)
     if pkv_path:
         dkv -= 0.5

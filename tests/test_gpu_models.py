@@ -230,6 +230,52 @@ GRAD_TOL = {("phonon", 64, 1, 8): 3e-3, ("phonon", 128, 2, 16): 3e-3, ("edos", 6
 GRAD_TOL_P99 = {"phonon": 1e-3, "edos": 1e-3}
 GRAD_TOL_MEDIAN = {"phonon": 1e-4, "edos": 1e-4}
 
+# eDOS against the float64 oracle on the same fp32 batch and parameters cast exactly: the phonon bounds (max, 99th percentile
+# over tensors of >= 256 elements, median), per output and gradient tensor relative to its maximum.  Plain fp32 arithmetic
+# (torch on the CPU) stays at <= 9.8e-4 / 9.6e-5 / 2.2e-5 of it over the eDOS cases below.  MI355X: <= 2.9e-3 / 1.2e-4 / 2.3e-5;
+# the maximum (embeddings.weight, H256 T2 B64) sits in 2 of its 201 rows - activation-gate flips, not a
+# uniform error: the same case with the split-bf16 feed-forward GEMMs gives 1.7e-4.
+F64_MAX, F64_P99, F64_MEDIAN = 3e-3, 1e-3, 1e-4
+
+
+def _oracle_f64(kind, params, g32, L, T, beta=1.0):
+    """(outputs, gradients) of the float64 oracle on float64 copies of the fp32 `params` and of the fp32 batch `g32`."""
+    from oracle import dos_oracle as O
+    g64 = g32.to("cpu", dtype=torch.float64)
+    leaves = {k: v.detach().to(torch.float64).requires_grad_(True) for k, v in params.items()
+              if v.is_floating_point() and k != "version" and not k.endswith(".version")}
+    if kind == "phonon":
+        dg, x, ds = O.dostransformer_phonon_forward(leaves, g64, L, T)
+        loss = O.loss_phonon(dg, ds, g64.phdos, beta)
+    else:
+        dg, x, ds = O.dostransformer_forward(leaves, g64, L, T)
+        loss = O.loss_edos(dg, ds, g64.y_ft, beta)
+    names = list(leaves)
+    gr = torch.autograd.grad(loss, [leaves[k] for k in names], allow_unused=True)
+    return (dg.detach(), x.detach(), ds.detach()), dict(zip(names, gr))
+
+
+def _f64_errors(label, outs, G, ref):
+    """Per output / live gradient tensor |got - ref64| / max|ref64|: prints and returns the worst (max, tensor), (p99, tensor)
+    and (median, tensor), the last two over tensors of >= 256 elements."""
+    outs64, grads64 = ref
+    pairs = list(zip(("dos_global", "x_nodes", "dos_system"), outs, outs64))
+    pairs += [(k, G[k], g) for k, g in grads64.items() if g is not None]
+    worst, worst99, worst50, rows = (0.0, None), (0.0, None), (0.0, None), None
+    for name, got, r in pairs:
+        d = (got.detach().cpu().double() - r.double()).abs() / (r.abs().max() + 1e-6)
+        e = d.reshape(-1)
+        if float(e.max()) > worst[0]:        # where the worst tensor errs by more than 1e-4: a few rows (an activation-gate flip
+            rows = (d.reshape(d.shape[0], -1) > 1e-4).any(1).nonzero().flatten().tolist()   # moves one row) or everywhere
+        worst = max(worst, (float(e.max()), name))
+        if e.numel() >= 256:
+            worst99 = max(worst99, (float(torch.quantile(e[:1 << 24], 0.99)), name))
+            worst50 = max(worst50, (float(e.median()), name))
+    rows = rows or []
+    print(f"fp64-oracle {label}: worst {worst[0]:.3e} at {worst[1]} (rows above 1e-4: {rows[:8]}{' ...' if len(rows) > 8 else ''} "
+          f"of {len(rows)}); p99 {worst99[0]:.3e} at {worst99[1]}; median {worst50[0]:.3e} at {worst50[1]}")
+    return worst, worst99, worst50
+
 
 @pytest.mark.parametrize("kind,H,T,B", [("phonon", 64, 1, 8), ("phonon", 128, 2, 16), ("edos", 64, 2, 6),
                                          ("edos", 256, 2, 4),
@@ -258,6 +304,8 @@ def test_against_oracle_live(kind, H, T, B):
         fwd = O.dostransformer_forward
     params = {k: (v.detach().clone().to(ref_dt) if v.is_floating_point() else v.clone())
               for k, v in model.state_dict().items()}
+    # (before O.train_step below updates `params`; the fp32 batch of the same seed, cast)
+    ref64 = _oracle_f64(kind, params, synth.edos_batch(B, seed=12, dtype=torch.float32), 3, T) if kind == "edos" else None
     model = model.to(DEV)
     g = g.to(DEV)
     with torch.no_grad():
@@ -289,6 +337,9 @@ def test_against_oracle_live(kind, H, T, B):
     assert worst[0] < tol, worst
     assert worst99[0] < GRAD_TOL_P99[kind], worst99
     assert worst50[0] < GRAD_TOL_MEDIAN[kind], worst50
+    if ref64 is not None:
+        w, w99, w50 = _f64_errors(f"{kind} H{H} T{T} B{B}", (dg, xn, ds), fp.G, ref64)
+        assert w[0] < F64_MAX and w99[0] < F64_P99 and w50[0] < F64_MEDIAN, (w, w99, w50)
     tr.optimizer_step()
     # Adam's first step moves every element by ~lr*sign(g): where |g| is at the noise floor of the fp32
     # (GPU) vs fp64 (oracle) gradient the sign itself is ill-conditioned, so compare the update only
@@ -832,6 +883,7 @@ def test_models_with_overfull_nodes_match_the_oracle(kind):
     dg, xn, ds_ = tr.last_outputs
     rmse = lambda a, b: float(torch.sqrt(((a.double().cpu() - b.double()) ** 2).mean()))
     assert rmse(dg, rg) < 1e-4 and rmse(ds_, rs) < 1e-4 and rmse(xn, rx) < 1e-4 * max(1.0, float(rx.abs().max()))
+    ref64 = _oracle_f64(kind, params, collate(_fat_crystals(kind, B, 9, torch.float32)), 3, 1) if kind == "edos" else None
     ref_loss, grads = O.train_step(kind, params, {}, g_ref, 3, 1, lr=1e-3, beta=1.0)
     assert abs(float(loss) - float(ref_loss)) < 2e-4
     fp = model.flat_params()
@@ -839,6 +891,9 @@ def test_models_with_overfull_nodes_match_the_oracle(kind):
         if gr is not None:
             e = float((fp.G[k].cpu().double() - gr.double()).abs().max() / (gr.abs().max() + 1e-6))
             assert e < 3e-3, (k, e)
+    if ref64 is not None:
+        w, w99, w50 = _f64_errors(f"overfull {kind}", (dg, xn, ds_), fp.G, ref64)
+        assert w[0] < F64_MAX and w99[0] < F64_P99 and w50[0] < F64_MEDIAN, (w, w99, w50)
     # eager, replay and device-collated replay: same trajectory, bit for bit
     sd0 = {k: v.detach().clone() for k, v in model.state_dict().items()}
     outs = []
@@ -1076,6 +1131,11 @@ def test_models_with_hidden_beyond_256_match_the_oracle(kind, H):
     big = [t for t in errs if t[2] > 1e-3 and fp.G[t[1]].numel() > 100000]
     assert not big, big                     # a large tensor whose TYPICAL error is large would be a kernel bug
     assert sum(1 for t in errs if t[0] > 3e-3) <= 6, errs[:8]
+    if kind == "edos":                      # against the float64 oracle on the same fp32 batch and parameters, cast
+        _, w99, _ = _f64_errors(f"hidden {H} {kind}", (dg, xn, ds_), fp.G, _oracle_f64(kind, params, collate(cs_of(B, 11, torch.float32)), L, T))
+        # 99th percentile over tensors of >= 256 elements: 2.6e-4 on MI355X (transformer.layers.0.layer_norms.0.weight), the
+        # bound ~4 x that (= the phonon p99 bound); the maximum is held by the 3e-2 above (gate flips)
+        assert w99[0] < F64_P99, w99
     sd0 = {k: v.detach().clone() for k, v in model.state_dict().items()}
     outs = []
     gd = g.to(DEV)

@@ -315,3 +315,27 @@ def test_bucket_promotion_picks_the_smallest_live_bucket_that_fits():
     assert promote_key(live, (400, 7900) + rest, 0.08) is None                        # ... and just beyond
     assert promote_key(live, (464, 9280, 16, 12, 16, True), 0.5) is None              # other batch size: never
     assert promote_key([], (448, 8960) + rest, 0.08) is None
+
+
+def test_bound_ratio_judges_each_row_on_its_own_scale():
+    """tests/gpu_util.bound_ratio (the element-wise measure of the GPU kernel tests): a 1e-4 relative error in one element of a
+    small row next to large rows fails it, where the global err() - max error / max of the tensor - would pass."""
+    from tests.gpu_util import EPS32, bound_ratio, err
+    g = torch.Generator().manual_seed(0)
+    mags = torch.tensor([1e3, 1e3, 1e-2, 1e3], dtype=torch.float64)[:, None]
+    ref = (torch.randn(4, 64, generator=g, dtype=torch.float64) * mags).float()           # an fp32 result ...
+    scale = ref.double().abs().mean(1, keepdim=True)                                     # ... and each row's own scale
+    assert bound_ratio(ref, ref.double(), scale, 8) == 0.0
+    bad = ref.clone()
+    bad[2, 5] *= 1 + 1e-4
+    assert err(bad, ref) < 2e-5                                                          # the global measure accepts it
+    assert bound_ratio(bad, ref.double(), scale, 8) > 1.0                                # the row's own scale does not
+    ok = ref.clone()
+    ok[2, 5] += 4 * EPS32 * float(scale[2])                                              # half the bound of c = 8
+    assert 0.4 < bound_ratio(ok, ref.double(), scale, 8) <= 0.5 + 1e-6
+    nan = ref.clone()
+    nan[0, 0] = float("nan")
+    assert bound_ratio(nan, ref.double(), scale, 8) == float("inf")
+    zero = torch.zeros(3)                                                                # a zero bound demands exact zeros
+    assert bound_ratio(zero, torch.zeros(3, dtype=torch.float64), 0.0, 8) == 0.0
+    assert bound_ratio(zero + 1e-30, torch.zeros(3, dtype=torch.float64), 0.0, 8) == float("inf")
