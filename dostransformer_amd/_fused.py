@@ -166,10 +166,15 @@ class FusedModel(nn.Module):
             raise DosxError(f"{name}: the float64 program takes hidden <= {MAX_HIDDEN}, got {self._cfg.H}")
         return torch.float64
 
+    def _wanted_flat_dtype(self) -> Optional[torch.dtype]:
+        """The flat dtype a module's program switch asks for (DOSTransformerBase.set_program_dtype), None: no switch."""
+        return None
+
     def _ensure_flat(self, device: torch.device, g) -> FlatParams:
         dead = self._extra_dead(g)
         fp = self._flat
-        if fp is None or not fp.intact(device) or getattr(self, "_flat_dead", ()) != dead:
+        want = self._wanted_flat_dtype()
+        if fp is None or not fp.intact(device) or getattr(self, "_flat_dead", ()) != dead or (want is not None and fp.dtype != want):
             fp = FlatParams(self, device, dead, self._flat_dtype(g))
             object.__setattr__(self, "_flat", fp)
             object.__setattr__(self, "_flat_dead", dead)

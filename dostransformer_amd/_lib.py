@@ -303,6 +303,12 @@ class Wgrad64(C.Structure):
     ]
 
 
+class Attn64(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("Sq", "Bq", "Nk", "Bk", "H", "flags")] + \
+               [(k, C.c_void_p) for k in ("q", "x", "kvhat", "gamma0", "beta0", "drop_mask", "out", "probs", "dout", "dq", "ds",
+                                          "dkvhat", "part")] + [("accumulate", C.c_int32)]
+
+
 class Call(C.Structure):
     _fields_ = [("op", C.c_int32), ("nint", C.c_int32), ("nflt", C.c_int32), ("reserved", C.c_int32),
                 ("iarg", C.c_int64 * 19), ("farg", C.c_double * 6)]
@@ -425,6 +431,11 @@ _SIGS = {
     "dosx_graph_pool_f64": [_P, _P, _P, _I, _I, _P],
     "dosx_rows_add_f64": [_P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P],
     "dosx_reduce_rows_f64": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
+    "dosx_attention_f64": [C.POINTER(Attn64), _P],
+    "dosx_attention_bwd_f64": [C.POINTER(Attn64), _P],
+    "dosx_dense_rows_f64": [_P, _P, _P, _P, _I, _I, _I, _P],
+    "dosx_dense_rows_bwd_f64": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "dosx_index_sum_f64": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P],
     "dosx_last_error": [],
     "dosx_version": [],
 }

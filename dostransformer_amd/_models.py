@@ -9,7 +9,8 @@ import torch
 
 from . import functional as Fn
 from . import functional64 as F64
-from ._fused import FusedModel
+from ._fused import FusedModel, is_dead_param
+from ._lib import DosxError
 
 
 _SEED_MOD = 2 ** 62
@@ -31,6 +32,52 @@ def dos_device(P):
 class DOSTransformerBase(FusedModel):
     """forward(g) -> (dos_global [B,S], x [N,H], dos_system [B,S])   (`DOSTransformer_phonon.py:66-119`)."""
     _cfg: Fn.ModelCfg
+    _program_dtype = torch.float32
+
+    # ---- which program the module runs ----------------------------------------------------------------------------------
+    @property
+    def program_dtype(self) -> torch.dtype:
+        """The dtype the next forward computes in: torch.float32 (the default, whatever the parameters' dtype) or
+        torch.float64 after set_program_dtype(torch.float64) (functional64: the phonon reference's float64 training)."""
+        return self._program_dtype
+
+    def set_program_dtype(self, dtype: torch.dtype):
+        """Select the fp32 program (torch.float32, the default) or the float64 one (torch.float64: DOSTransformer_phonon
+        with float64 live parameters and hidden <= functional64.MAX_HIDDEN).  The flat parameters are re-homed on the next
+        call.  Returns self."""
+        if dtype == torch.float64:
+            self._check_f64_program()
+        elif dtype != torch.float32:
+            raise DosxError(f"{type(self).__name__}.set_program_dtype: torch.float32 or torch.float64, got {dtype}")
+        object.__setattr__(self, "_program_dtype", dtype)
+        return self
+
+    def _check_f64_program(self) -> None:
+        name = type(self).__name__
+        if self._cfg.kind != "phonon":
+            raise DosxError(f"{name}: only DOSTransformer_phonon has a float64 program (the eDOS reference trains in fp32)")
+        dts = {p.dtype for n, p in self.named_parameters() if not is_dead_param(n)}
+        if dts != {torch.float64}:
+            raise DosxError(f"{name}: the float64 program needs every live parameter float64 (.double()), got "
+                            f"{sorted(str(d) for d in dts)}")
+        if self._cfg.H > F64.MAX_HIDDEN:
+            raise DosxError(f"{name}: the float64 program takes hidden <= {F64.MAX_HIDDEN}, got {self._cfg.H}")
+
+    def _flat_dtype(self, g=None) -> torch.dtype:
+        if self._program_dtype != torch.float64:
+            return torch.float32
+        self._check_f64_program()
+        return torch.float64
+
+    def _wanted_flat_dtype(self):
+        return self._program_dtype
+
+    def _require_fp32_program(self, who: str) -> None:
+        """The drivers that run the fp32 program on the flat buffer (train.Trainer, predict.Predictor) refuse a module set to
+        float64."""
+        if self._program_dtype == torch.float64:
+            raise DosxError(f"{who} runs the fp32 program; {type(self).__name__} is set to float64 (set_program_dtype): use "
+                            f"model(batch), loss.backward() and torch.optim.AdamW")
 
     def _check_train_flags(self):
         pass          # (kept for callers of round 1: attention dropout is implemented now)
@@ -53,6 +100,12 @@ class DOSTransformerBase(FusedModel):
         return p, seed
 
     def _program_fwd(self, P, g, m, bump_seed: bool = True, per_crystal_keys: bool = False):
+        if P["embeddings.weight"].dtype == torch.float64:
+            if per_crystal_keys:
+                raise DosxError("per_crystal_keys: fp32 program only")
+            dos, xL, ctx = F64.dostransformer_phonon_fwd(P, self._cfg, g, m, drop=self._dropout(dos_device(P), bump_seed))
+            B = m.num_graphs
+            return dos[:B], xL, dos[B:], (ctx, dos)
         dos, xL, ctx = Fn.dostransformer_fwd(P, self._cfg, g, m, drop=self._dropout(dos_device(P), bump_seed),
                                              per_crystal_keys=per_crystal_keys)
         B = m.num_graphs
@@ -67,6 +120,9 @@ class DOSTransformerBase(FusedModel):
             ddos[:B].copy_(dg)
         if ds is not None:
             ddos[B:].copy_(ds)
+        if dos.dtype == torch.float64:
+            F64.dostransformer_phonon_bwd(P, G, self._cfg, m, ctx, ddos, dx)
+            return
         Fn.dostransformer_bwd(P, G, self._cfg, m, ctx, ddos, None if dx is None else dx.float().contiguous(), sink)
 
     def forward(self, g):

@@ -1,11 +1,14 @@
-"""float64 forward / backward program of ``Graphnetwork_phonon`` (`embedder_phDOS/graphnetwork_phonon.py:48-72`).
+"""float64 forward / backward programs of ``Graphnetwork_phonon`` (`embedder_phDOS/graphnetwork_phonon.py:48-72`) and
+``DOSTransformer_phonon`` (`embedder_phDOS/DOSTransformer_phonon.py:66-119`).
 
 The phonon reference computes in float64 (main_phDOS.py:15-16).  A module whose live parameters are float64 runs this
 program instead of the fp32 one in ``functional.py``: the same steps as ``oracle.graphnetwork_phonon_forward`` in order,
 each a libdosx fp64 kernel (csrc/f64.hip), with the backward written out step by step in reverse.  Straight-line on the
 current stream, no fused-path heuristics; every reduction has a fixed order, so two runs are bitwise equal.
 
-Edges are processed in the destination-sorted order of ``GraphMeta`` (``edge_perm`` maps the caller's order to it).
+Edges are processed in the destination-sorted order of ``GraphMeta`` (``edge_perm`` maps the caller's order to it).  The
+transformer half of DOSTransformer_phonon keeps crystal-major rows: b * S + s for the energy rows, b * nmax + j for the
+zero-padded dense key rows.
 """
 from __future__ import annotations
 
@@ -14,13 +17,17 @@ from typing import Dict, Optional
 import torch
 
 from .batch import GraphMeta
-from .ops import (ACT64_LEAKY, ACT64_PRELU, act_bwd64, alloc64, colsum64, edge_feat_sh1_64, gather_bwd64, gemm64,
-                  graph_pool64, layernorm64, layernorm_bwd64, reduce_rows64, rows_add64, rowmap, seg64, segment_mean64,
-                  segment_mean_bwd64, wgrad64)
+from . import functional as Fn
+from . import ops
+from .ops import (ACT64_LEAKY, ACT64_PRELU, ACT64_RELU, act_bwd64, alloc64, attention64, attention_bwd64, colsum64,
+                  dense_rows64, dense_rows_bwd64, edge_feat_sh1_64, gather_bwd64, gemm64, graph_pool64, index_sum64,
+                  layernorm64, layernorm_bwd64, reduce_rows64, rows_add64, rowmap, seg64, segment_mean64, segment_mean_bwd64,
+                  wgrad64)
 
 Params = Dict[str, torch.Tensor]
 
 MAX_HIDDEN = 512          # the LayerNorm rows of the edge / node MLPs are 2H wide, dosx_layernorm_f64 takes up to 1024
+SOFTMAX64 = False         # tests only: the attention softmax in fp64 instead of the reference's fp32 (DOSX_ATTN64_SOFTMAX_F64)
 
 
 def _f64(t: torch.Tensor) -> torch.Tensor:
@@ -159,3 +166,160 @@ def graphnetwork_phonon_bwd(P: Params, G: Params, cfg, m: GraphMeta, saved, ddos
         de = torch.zeros(m.num_edges, H, device=dev, dtype=torch.float64)
     _mlp_prelu_bwd(P, G, "GN_encoder.edge_encoder", ce, de)
     _mlp_prelu_bwd(P, G, enc, cx, dx)
+
+
+# ---- DOSTransformer_phonon ------------------------------------------------------------------------------------------------
+def _gnn_trunk_fwd(P: Params, cfg, g, m: GraphMeta, enc: str):
+    vec = g.edge_vec
+    if m.edge_perm is not None:
+        vec = vec[m.edge_perm]
+    e0 = edge_feat_sh1_64(_f64(vec), 4.0)                                              # r_max = 4
+    x, cx = _mlp_prelu_fwd(P, enc, _f64(g.x))
+    e, ce = _mlp_prelu_fwd(P, "GN_encoder.edge_encoder", e0)
+    layers = []
+    for l in range(cfg.L):
+        x, e, c = _processor_fwd(P, f"stacked_processor.{l}", x, e, m)
+        layers.append(c)
+    return x, (enc, cx, ce, layers)
+
+
+def _gnn_trunk_bwd(P: Params, G: Params, cfg, m: GraphMeta, ctx, dx: torch.Tensor) -> None:
+    enc, cx, ce, layers = ctx
+    de = None
+    for l in reversed(range(cfg.L)):
+        dx, de = _processor_bwd(P, G, f"stacked_processor.{l}", layers[l], dx, de, m)
+    if de is None:                                                                    # L = 0: nothing reaches the edges
+        de = torch.zeros(m.num_edges, cfg.H, device=dx.device, dtype=torch.float64)
+    _mlp_prelu_bwd(P, G, "GN_encoder.edge_encoder", ce, de)
+    _mlp_prelu_bwd(P, G, enc, cx, dx)
+
+
+def _encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, kvhat: torch.Tensor, Nk: int, Bk: int, T: int, drop):
+    """TransformerEncoder (layers/transformer.py:46-79,120-157) on the query rows x [Bq*Sq, H] (row bq * Sq + s) over the
+    normalised key rows kvhat [Bk*Nk, H], which stay the same for every layer (:72-73).  drop: None or (p, seed_dev,
+    stream_base): attention dropout, one [Bq, Sq, Nk] multiplier mask per layer drawn like the fp32 program's."""
+    rows, H = x.shape
+    lay = []
+    for t in range(T):
+        lp = f"{pre}.layers.{t}"
+        g0, b0 = P[lp + ".layer_norms.0.weight"], P[lp + ".layer_norms.0.bias"]
+        xhq, rsq, q = layernorm64(x, g0, b0)
+        mask = None
+        if drop is not None:
+            mask = torch.empty(Bq, Sq, Nk, device=x.device, dtype=torch.float32)
+            ops.dropout_mask(mask, drop[0], drop[1], drop[2] + t)
+            if Fn.DROP_MASK_LOG is not None:
+                Fn.DROP_MASK_LOG.append((pre, t, mask))
+        x1, probs = attention64(q, x, kvhat, g0, b0, Sq, Bq, Nk, Bk, mask, SOFTMAX64)
+        xh1, rs1, y1 = layernorm64(x1, P[lp + ".layer_norms.1.weight"], P[lp + ".layer_norms.1.bias"])
+        h = gemm64(rows, 4 * H, [seg64(y1)], P[lp + ".fc1.weight"], alloc64(x.device, rows, 4 * H), bias=P[lp + ".fc1.bias"],
+                   act=ACT64_RELU)
+        x2 = gemm64(rows, H, [seg64(h)], P[lp + ".fc2.weight"], alloc64(x.device, rows, H), bias=P[lp + ".fc2.bias"], res=x1)
+        lay.append((xhq, rsq, q, mask, probs, xh1, rs1, y1, h))
+        x = x2
+    xhf, rsf, y = layernorm64(x, P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"])
+    return y, (pre, lay, xhf, rsf, Sq, Bq, Nk, Bk, kvhat)
+
+
+def _encoder_bwd(P: Params, G: Params, ctx, dy: torch.Tensor, dkvhat: torch.Tensor, kacc: bool) -> torch.Tensor:
+    """Gradient of the query rows; every layer's key + value gradient (times gamma0) goes into dkvhat, the first one written
+    unless kacc (accumulate) - the key rows of the dense batch are read by two encoders."""
+    pre, lay, xhf, rsf, Sq, Bq, Nk, Bk, kvhat = ctx
+    rows, H = dy.shape
+    dev = dy.device
+
+    def ln_grads(key, part, acc=False):
+        colsum64(part[:, :H], G[key + ".weight"], acc)
+        colsum64(part[:, H:2 * H], G[key + ".bias"], acc)
+
+    dx, part = layernorm_bwd64(dy, xhf, rsf, P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"])
+    ln_grads(pre + ".layer_norm", part)
+    for t in reversed(range(len(lay))):
+        lp = f"{pre}.layers.{t}"
+        xhq, rsq, q, mask, probs, xh1, rs1, y1, h = lay[t]
+        g0, b0 = P[lp + ".layer_norms.0.weight"], P[lp + ".layer_norms.0.bias"]
+        # x2 = x1 + fc2(relu(fc1(LN1(x1))))
+        _linear_grads(G, lp + ".fc2", rows, dx, [seg64(h)])
+        dh = gemm64(rows, 4 * H, [seg64(dx)], P[lp + ".fc2.weight"], alloc64(dev, rows, 4 * H), w_layout=1)
+        dhz, _ = act_bwd64(dh, h, ACT64_RELU)                    # relu(z) > 0 exactly where z > 0
+        _linear_grads(G, lp + ".fc1", rows, dhz, [seg64(y1)])
+        dy1 = gemm64(rows, H, [seg64(dhz)], P[lp + ".fc1.weight"], alloc64(dev, rows, H), w_layout=1)
+        dz1, part1 = layernorm_bwd64(dy1, xh1, rs1, P[lp + ".layer_norms.1.weight"], P[lp + ".layer_norms.1.bias"])
+        ln_grads(lp + ".layer_norms.1", part1)
+        dx1 = rows_add64(rows, dx, dz1)
+        # x1 = x + attention(LN0(x), LN0(keys))
+        dq, partk, _ = attention_bwd64(dx1, q, kvhat, g0, b0, probs, Sq, Bq, Nk, Bk, dkvhat, mask, SOFTMAX64, kacc)
+        kacc = True
+        dzq, partq = layernorm_bwd64(dq, xhq, rsq, g0, b0)
+        ln_grads(lp + ".layer_norms.0", partq)
+        ln_grads(lp + ".layer_norms.0", partk, True)
+        dx = rows_add64(rows, dx1, dzq)
+    return dx
+
+
+def dostransformer_phonon_fwd(P: Params, cfg, g, m: GraphMeta, drop=None):
+    """-> (dos [2B, S] (rows [0,B) global, [B,2B) system), x_L [N, H], saved context).  drop: None or (p, seed_dev)."""
+    H, S, T, B = cfg.H, cfg.S, cfg.T, m.num_graphs
+    nmax = m.n_max
+    dr = (lambda base: None) if drop is None else (lambda base: (drop[0], drop[1], base))
+    xL, ctrunk = _gnn_trunk_fwd(P, cfg, g, m, "GN_encoder.node_encoder")                # :74-84
+    dev = xL.device
+    kv_n, rstd_n = dense_rows64(xL, m.graph_ptr, B, nmax)                               # :86-87, the keys' LN0 without affine
+    # energies (:71,143): embedding row s for every crystal, crystal-major
+    e_idx = (torch.arange(B * S, device=dev, dtype=torch.int32) % S).contiguous()
+    E1, c1 = _encoder_fwd(P, "transformer", rows_add64(B * S, P["embeddings.weight"], ia=e_idx), S, B, kv_n, nmax, B, T, dr(0))
+    pool = graph_pool64(xL, m.graph_ptr, B)                                              # :90, :180-181
+    graph = gemm64(B, H, [seg64(pool)], P["GN_decoder.mlp.0.weight"], alloc64(dev, B, H), bias=P["GN_decoder.mlp.0.bias"])
+    sysidx = g.system.to(device=dev, dtype=torch.int32).contiguous()
+    prow = rows_add64(B, P["prompt_token.weight"], ia=sysidx)                            # :105
+    # heads (:93-117): rows [0, B*S) the global branch, [B*S, 2B*S) the system branch
+    perB = rowmap(d=S, m=1, c=0)
+    BS = B * S
+    dosin, pre = alloc64(dev, 2 * BS, H), alloc64(dev, 2 * BS, H)
+    seg_g = [seg64(E1), seg64(graph, perB)]
+    seg_s = [seg64(E1), seg64(graph, perB), seg64(prow, perB)]
+    gemm64(BS, H, seg_g, P["fc.weight"], dosin[:BS], bias=P["fc.bias"], act=ACT64_LEAKY, pre=pre[:BS])
+    gemm64(BS, H, seg_s, P["fc_prompt.weight"], dosin[BS:], bias=P["fc_prompt.bias"], act=ACT64_LEAKY, pre=pre[BS:])
+    # both branches through each shared encoder at once: Bq = 2B, global crystals first (the masks' layout)
+    ptr_s = torch.arange(0, 2 * BS + 1, S, device=dev, dtype=torch.int32)
+    kv_s, rstd_s = dense_rows64(dosin, ptr_s, 2 * B, S)                                  # self attention: its own rows
+    hs, c2 = _encoder_fwd(P, "transformer_self", dosin, S, 2 * B, kv_s, S, 2 * B, T, dr(64))
+    hsrc, c3 = _encoder_fwd(P, "transformer_source", hs, S, 2 * B, kv_n, nmax, B, T, dr(128))
+    dos = gemm64(2 * BS, 1, [seg64(hsrc)], P["out_layer.weight"], alloc64(dev, 2 * BS, 1), bias=P["out_layer.bias"])
+    ctx = (ctrunk, kv_n, rstd_n, c1, pool, graph, prow, sysidx, seg_g, seg_s, pre, dosin, ptr_s, kv_s, rstd_s, c2, c3, hsrc, E1)
+    return dos.view(2 * B, S), xL, ctx
+
+
+def dostransformer_phonon_bwd(P: Params, G: Params, cfg, m: GraphMeta, ctx, ddos: torch.Tensor,
+                              dx_ext: Optional[torch.Tensor]) -> None:
+    """Writes the gradient of every live parameter into G from ddos [2B, S] and the gradient of x_L (or None)."""
+    (ctrunk, kv_n, rstd_n, c1, pool, graph, prow, sysidx, seg_g, seg_s, pre, dosin, ptr_s, kv_s, rstd_s, c2, c3, hsrc,
+     E1) = ctx
+    H, S, B, N = cfg.H, cfg.S, m.num_graphs, m.num_nodes
+    nmax = m.n_max
+    BS = B * S
+    dev = dosin.device
+    dout = ddos.to(torch.float64).contiguous().view(2 * BS, 1)
+    _linear_grads(G, "out_layer", 2 * BS, dout, [seg64(hsrc)])
+    dh = gemm64(2 * BS, H, [seg64(dout)], P["out_layer.weight"], alloc64(dev, 2 * BS, H), w_layout=1)
+    dkv_n = alloc64(dev, B * nmax, H)
+    dh = _encoder_bwd(P, G, c3, dh, dkv_n, False)
+    dkv_s = alloc64(dev, 2 * BS, H)
+    ddosin = _encoder_bwd(P, G, c2, dh, dkv_s, False)
+    dense_rows_bwd64(dkv_s, kv_s, rstd_s, ptr_s, ddosin, 2 * B, S)                      # keys of the self attention
+    dpre, _ = act_bwd64(ddosin, pre, ACT64_LEAKY)
+    _linear_grads(G, "fc", BS, dpre[:BS], seg_g)
+    _linear_grads(G, "fc_prompt", BS, dpre[BS:], seg_s)
+    dcat_g = gemm64(BS, 2 * H, [seg64(dpre[:BS])], P["fc.weight"], alloc64(dev, BS, 2 * H), w_layout=1)
+    K = P["fc_prompt.weight"].shape[1]
+    dcat_s = gemm64(BS, K, [seg64(dpre[BS:])], P["fc_prompt.weight"], alloc64(dev, BS, K), w_layout=1)
+    dE1 = rows_add64(BS, dcat_g[:, :H], dcat_s[:, :H])
+    dgraph = reduce_rows64(rows_add64(BS, dcat_g[:, H:], dcat_s[:, H:2 * H]), B, S, S, 1)
+    index_sum64(reduce_rows64(dcat_s[:, 2 * H:], B, S, S, 1), sysidx, G["prompt_token.weight"])
+    _linear_grads(G, "GN_decoder.mlp.0", B, dgraph, [seg64(pool)])
+    dpool = gemm64(B, H, [seg64(dgraph)], P["GN_decoder.mlp.0.weight"], alloc64(dev, B, H), w_layout=1)
+    dx0 = _encoder_bwd(P, G, c1, dE1, dkv_n, True)
+    reduce_rows64(dx0, S, B, 1, S, out=G["embeddings.weight"])                         # energy s: rows b * S + s
+    dx = rows_add64(N, dpool, None if dx_ext is None else dx_ext.to(torch.float64).contiguous(), ia=m.node_graph)
+    dense_rows_bwd64(dkv_n, kv_n, rstd_n, m.graph_ptr, dx, B, nmax)
+    _gnn_trunk_bwd(P, G, cfg, m, ctrunk, dx)

@@ -1725,11 +1725,94 @@ def rows_add64(M: int, a: torch.Tensor, b: Optional[torch.Tensor] = None, ia=Non
     return out
 
 
-def reduce_rows64(src: torch.Tensor, n_out: int, n_red: int, stride_out: int, stride_red: int) -> torch.Tensor:
-    """out[i] = sum_{j < n_red} src[i * stride_out + j * stride_red] (rows added in order of j)."""
-    _chk_f64(src)
+def reduce_rows64(src: torch.Tensor, n_out: int, n_red: int, stride_out: int, stride_red: int,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[i] = sum_{j < n_red} src[i * stride_out + j * stride_red] (rows added in order of j); ``out`` [n_out, width]
+    optional (a gradient slot, say)."""
+    _chk_f64(src, out)
     W = src.shape[1]
-    out = alloc64(src.device, n_out, W)
-    _call("dosx_reduce_rows_f64", src.data_ptr(), src.stride(0), out.data_ptr(), W, n_out, n_red, stride_out, stride_red, W, 0,
-          _stream())
+    if out is None:
+        out = alloc64(src.device, n_out, W)
+    assert out.shape[0] == n_out and out.shape[1] == W
+    _call("dosx_reduce_rows_f64", src.data_ptr(), src.stride(0), out.data_ptr(), out.stride(0), n_out, n_red, stride_out,
+          stride_red, W, 0, _stream())
+    return out
+
+
+# float64 attention of DOSTransformer_phonon (csrc/f64_attention.hip)
+ATTN64_MAX_H = 512                     # DOSX_ATTN64_MAX_H
+ATTN64_SOFTMAX_F64 = 1                 # DOSX_ATTN64_SOFTMAX_F64
+
+
+def _attn64_desc(q, kvhat, gamma0, beta0, Sq: int, Bq: int, Nk: int, Bk: int, mask, softmax64: bool) -> _lib.Attn64:
+    _chk_c64(q, kvhat, gamma0, beta0)
+    H = q.shape[1]
+    if not (1 <= H <= ATTN64_MAX_H) or Sq < 1 or Nk < 1 or Bk < 1 or Bq % Bk:
+        raise ValueError(f"attention64: Sq={Sq} Bq={Bq} Nk={Nk} Bk={Bk} H={H}")
+    if q.shape[0] != Bq * Sq or tuple(kvhat.shape) != (Bk * Nk, H) or gamma0.numel() != H or beta0.numel() != H:
+        raise ValueError(f"attention64: q {tuple(q.shape)}, kvhat {tuple(kvhat.shape)} for Sq={Sq} Bq={Bq} Nk={Nk} Bk={Bk}")
+    if mask is not None and (mask.dtype != torch.float32 or not mask.is_contiguous() or tuple(mask.shape) != (Bq, Sq, Nk)):
+        raise ValueError(f"attention64: the dropout mask must be a contiguous float32 [Bq, Sq, Nk] tensor")
+    d = _lib.Attn64()
+    d.Sq, d.Bq, d.Nk, d.Bk, d.H = Sq, Bq, Nk, Bk, H
+    d.flags = ATTN64_SOFTMAX_F64 if softmax64 else 0
+    d.q, d.kvhat, d.gamma0, d.beta0, d.drop_mask = q.data_ptr(), kvhat.data_ptr(), gamma0.data_ptr(), beta0.data_ptr(), _p(mask)
+    return d
+
+
+def attention64(q: torch.Tensor, x: torch.Tensor, kvhat: torch.Tensor, gamma0, beta0, Sq: int, Bq: int, Nk: int, Bk: int,
+                mask: Optional[torch.Tensor] = None, softmax64: bool = False):
+    """(out, probs): out = x + (softmax(q k^T / sqrt(H)) o mask) v with k = v = kvhat * gamma0 + beta0 (include/dosx.h:
+    DosxAttn64 for the row layouts); probs [Bq, Sq, Nk] the un-dropped probabilities the backward reads."""
+    d = _attn64_desc(q, kvhat, gamma0, beta0, Sq, Bq, Nk, Bk, mask, softmax64)
+    _chk_c64(x)
+    assert x.shape == q.shape
+    out, probs = alloc64(q.device, *q.shape), alloc64(q.device, Bq, Sq, Nk)
+    d.x, d.out, d.probs = x.data_ptr(), out.data_ptr(), probs.data_ptr()
+    _call("dosx_attention_f64", C.byref(d), _stream())
+    return out, probs
+
+
+def attention_bwd64(dout: torch.Tensor, q: torch.Tensor, kvhat: torch.Tensor, gamma0, beta0, probs: torch.Tensor, Sq: int, Bq: int,
+                    Nk: int, Bk: int, dkvhat: torch.Tensor, mask: Optional[torch.Tensor] = None, softmax64: bool = False,
+                    accumulate: bool = False):
+    """(dq [Bq*Sq, H], part [Bk*Nk, 2H], ds [Bq, Sq, Nk]); dkvhat (+)= the key + value gradient times gamma0.  Column sums
+    of part are the key side's dgamma0 | dbeta0; ds is the gradient of the scaled scores."""
+    d = _attn64_desc(q, kvhat, gamma0, beta0, Sq, Bq, Nk, Bk, mask, softmax64)
+    _chk_c64(dout, probs, dkvhat)
+    assert dout.shape == q.shape and dkvhat.shape == kvhat.shape and tuple(probs.shape) == (Bq, Sq, Nk)
+    H = q.shape[1]
+    dq, ds, part = alloc64(q.device, *q.shape), alloc64(q.device, Bq, Sq, Nk), alloc64(q.device, Bk * Nk, 2 * H)
+    d.probs, d.dout, d.dq, d.ds = probs.data_ptr(), dout.data_ptr(), dq.data_ptr(), ds.data_ptr()
+    d.dkvhat, d.part, d.accumulate = dkvhat.data_ptr(), part.data_ptr(), int(accumulate)
+    _call("dosx_attention_bwd_f64", C.byref(d), _stream())
+    return dq, part, ds
+
+
+def dense_rows64(x: torch.Tensor, graph_ptr: torch.Tensor, B: int, nmax: int):
+    """(rows [B*nmax, H], rstd [N]): the normalised (no affine) rows of to_dense_batch(x), zero rows for the padding."""
+    _chk_c64(x)
+    assert graph_ptr.dtype == torch.int32 and graph_ptr.numel() >= B + 1
+    N, H = x.shape
+    out, rstd = alloc64(x.device, B * nmax, H), alloc64(x.device, N)
+    _call("dosx_dense_rows_f64", x.data_ptr(), graph_ptr.data_ptr(), out.data_ptr(), rstd.data_ptr(), B, nmax, H, _stream())
+    return out, rstd
+
+
+def dense_rows_bwd64(dout: torch.Tensor, xhat: torch.Tensor, rstd: torch.Tensor, graph_ptr: torch.Tensor, dx: torch.Tensor,
+                     B: int, nmax: int, accumulate: bool = True) -> torch.Tensor:
+    """dx[n] (+)= the LayerNorm (no affine) backward of node n's dense row; padding rows reach nothing."""
+    _chk_c64(dout, xhat, rstd, dx)
+    assert graph_ptr.dtype == torch.int32 and dout.shape == xhat.shape and dout.shape[0] == B * nmax
+    _call("dosx_dense_rows_bwd_f64", dout.data_ptr(), xhat.data_ptr(), rstd.data_ptr(), graph_ptr.data_ptr(), dx.data_ptr(), B,
+          nmax, dx.shape[1], int(accumulate), _stream())
+    return dx
+
+
+def index_sum64(src: torch.Tensor, idx: torch.Tensor, out: torch.Tensor, accumulate: bool = False) -> torch.Tensor:
+    """out[i] (+)= sum of the rows r of src with idx[r] == i, in order of r (fixed order: no atomics)."""
+    _chk_f64(src, out)
+    assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == src.shape[0] and out.shape[1] == src.shape[1]
+    _call("dosx_index_sum_f64", src.data_ptr(), src.stride(0), idx.data_ptr(), src.shape[0], out.data_ptr(), out.stride(0),
+          out.shape[0], src.shape[1], int(accumulate), _stream())
     return out

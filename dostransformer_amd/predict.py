@@ -32,6 +32,7 @@ class Predictor:
     def __init__(self, model: DOSTransformerBase, bucket=(8, 128), per_crystal_keys: bool = False):
         if not isinstance(model, DOSTransformerBase):
             raise TypeError("Predictor drives DOSTransformer / DOSTransformer_phonon modules")
+        model._require_fp32_program("Predictor")
         self.model = model
         self.bucket = tuple(bucket)
         self.per_crystal_keys = bool(per_crystal_keys)
@@ -67,6 +68,7 @@ class Predictor:
         dev = model._module_device()
         if dev.type != "cuda":
             raise RuntimeError("Predictor runs only on an MI355X through libdosx (no CPU fallback)")
+        model._require_fp32_program("Predictor")
         fp = model._ensure_flat(dev, g)
         if fp is not self._fp:                # parameters were re-homed: recorded pointers are stale
             self._fp, self._slots = fp, {}

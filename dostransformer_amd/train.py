@@ -187,6 +187,7 @@ class Trainer:
                  bucket=(8, 128), max_slots: int = 32, promote: float = 0.0):
         if not isinstance(model, DOSTransformerBase):
             raise TypeError("Trainer drives DOSTransformer / DOSTransformer_phonon modules")
+        model._require_fp32_program("Trainer")
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, betas, eps
         self.dist = dist
         self.graph = graph
@@ -353,6 +354,7 @@ class Trainer:
             self._bump_dropout_seed()
         model = self.model
         dev = model._module_device()
+        model._require_fp32_program("Trainer")
         fp = model._ensure_flat(dev, g)
         self._state(fp)
         m = graph_meta(g, dev)
@@ -487,6 +489,7 @@ class Trainer:
     def _graph_step(self, g: CrystalBatch, n_global: Optional[int]) -> torch.Tensor:
         model = self.model
         dev = model._module_device()
+        model._require_fp32_program("Trainer")
         fp = model._ensure_flat(dev, g)
         self._state(fp)
         m = g.meta
@@ -518,6 +521,7 @@ class Trainer:
             return self.step(ds.collate(indices, n_max=n_max), n_global)
         model = self.model
         dev = model._module_device()
+        model._require_fp32_program("Trainer")
         fp = model._ensure_flat(dev, None)
         self._state(fp)
         idx, N, E, n_max = ds.bucket_dims(indices, n_max)

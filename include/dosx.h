@@ -1064,6 +1064,50 @@ int dosx_rows_add_f64(const double* a, int lda, const int32_t* ia, const double*
 int dosx_reduce_rows_f64(const double* src, int ld_src, double* dst, int ld_dst, int n_out, int n_red, int stride_out,
                          int stride_red, int width, int accumulate, dosx_stream_t stream);
 
+/* ---- float64 attention of DOSTransformer_phonon (csrc/f64_attention.hip) -----------------------------------------------
+ * One encoder layer's attention half (layers/multihead_attention.py:49-76, transformer.py:131-137), single head, no
+ * projections: out = x + (softmax(q k^T * H^-1/2) o drop_mask) v with k = v = kvhat * gamma0 + beta0.  Query rows are
+ * crystal-major, row bq * Sq + s of q / x / out / dout / dq; key rows row bk * Nk + j of kvhat / dkvhat, with
+ * bk = bq % Bk (Bq a multiple of Bk); probabilities, masks and ds are [Bq, Sq, Nk].  The scores and both products are
+ * fp64; the softmax follows the reference: scores rounded to fp32, softmax in fp32 (accurate expf), promoted - and its
+ * backward the autograd mirror (dP o mask rounded to fp32, p (dP - sum p dP) in fp32, promoted, times H^-1/2).
+ * DOSX_ATTN64_SOFTMAX_F64 computes the softmax and its backward in fp64 instead (a test hook, not the reference). */
+#define DOSX_ATTN64_MAX_H 512
+#define DOSX_ATTN64_SOFTMAX_F64 1
+typedef struct DosxAttn64 {
+  int32_t Sq, Bq, Nk, Bk, H;
+  int32_t flags;            /* DOSX_ATTN64_* */
+  const double* q;          /* [Bq*Sq, H] LayerNorm 0 of the query rows */
+  const double* x;          /* [Bq*Sq, H] the residual (forward) */
+  const double* kvhat;      /* [Bk*Nk, H] normalised key rows (zero rows: padding keys, k = v = beta0) */
+  const double* gamma0;     /* [H] */
+  const double* beta0;      /* [H] */
+  const float* drop_mask;   /* [Bq, Sq, Nk] dropout multipliers applied after the softmax, or NULL */
+  double* out;              /* [Bq*Sq, H] x + attn (forward) */
+  double* probs;            /* [Bq, Sq, Nk] the un-dropped probabilities (written by the forward, read by the backward) */
+  const double* dout;       /* [Bq*Sq, H] gradient of the attention output (backward) */
+  double* dq;               /* [Bq*Sq, H] gradient of q (backward) */
+  double* ds;               /* [Bq, Sq, Nk] scratch: gradient of the scores (backward) */
+  double* dkvhat;           /* [Bk*Nk, H] (+)= dkv * gamma0, dkv the summed key + value gradient (backward) */
+  double* part;             /* [Bk*Nk, 2H] per key row dkv * kvhat | dkv: column sums are dgamma0 | dbeta0 (backward) */
+  int32_t accumulate;       /* dkvhat += instead of = */
+} DosxAttn64;
+/* forward: writes out and probs */
+int dosx_attention_f64(const DosxAttn64* desc_host, dosx_stream_t stream);
+/* backward: dq and ds per query tile, then a second launch reduces each key tile's dkv over every query row that reads it,
+ * in a fixed order (crystals bk, bk + Bk, ..., rows in order) */
+int dosx_attention_bwd_f64(const DosxAttn64* desc_host, dosx_stream_t stream);
+/* to_dense_batch + parameter-free LayerNorm (eps 1e-5): out[b*nmax + j] = normalised x[graph_ptr[b] + j] for
+ * j < graph_ptr[b+1] - graph_ptr[b], else a zero row; rstd [N] per node.  H <= 1024. */
+int dosx_dense_rows_f64(const double* x, const int32_t* graph_ptr, double* out, double* rstd, int B, int nmax, int H,
+                        dosx_stream_t stream);
+/* its backward: dx[n] (+)= rstd (g - mean(g) - xhat mean(g xhat)) of the dense row of node n (ghost rows are dropped) */
+int dosx_dense_rows_bwd_f64(const double* dout, const double* xhat, const double* rstd, const int32_t* graph_ptr, double* dx,
+                            int B, int nmax, int H, int accumulate, dosx_stream_t stream);
+/* dst[i, 0:W] (+)= sum over r < n_src with idx[r] == i, in order of r, of src[r, 0:W]  (embedding gradient) */
+int dosx_index_sum_f64(const double* src, int ld_src, const int32_t* idx, int n_src, double* dst, int ld_dst, int n_dst,
+                       int W, int accumulate, dosx_stream_t stream);
+
 const char* dosx_last_error(void);
 int dosx_version(void);
 
