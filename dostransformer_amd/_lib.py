@@ -10,7 +10,15 @@ import os
 from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("DOSX_LIB") or os.path.join(_HERE, "csrc", "libdosx.so")   # DOSX_LIB: diagnostic builds only
+
+
+def from_environ(name: str, default: str = "") -> str:
+    """The ONE place where the package reads a process variable: DOSX_LIB, DOSX_FFN_BF16X3, DOSX_DP_MID_BUCKET, DOSX_DP_CHECK
+    (tests/test_host_logic.py holds that list).  Every other form choice is a plain module attribute."""
+    return os.environ.get(name, default)
+
+
+LIB_PATH = from_environ("DOSX_LIB") or os.path.join(_HERE, "csrc", "libdosx.so")   # DOSX_LIB: diagnostic builds only
 
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int32)

@@ -14,7 +14,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from ._lib import Attn, Seg
+from ._lib import Attn, Seg, from_environ
 from ._lib import load as _lib_load
 from .batch import GraphMeta
 from .ops import (ACT_LEAKY, ACT_RELU, EPI_LN, EPI_PRELU_BWD, EPI_PRELU_LN_BWD, EPI_PRELU_LN_BWD_SEG, EPI_RELU_MASK, EPI_ROWLN_BWD, EPI_SEGSUM,
@@ -61,9 +61,49 @@ def pack_params(P: Params) -> Params:
     return out
 
 
+# ------------------------------------------------------------------------------------------------
+# Form switches.  Every form below is live: production reaches it at some shape, and the tests set these attributes to force
+# a form at shapes where production would pick the other one.  Only _FFN_BF16X3 can be set from outside the process; an A/B of
+# another one sets the attribute in its job script.  (The forms that were measured and rejected are gone; DESIGN.md 5.1 keeps their numbers.)
+# ------------------------------------------------------------------------------------------------
+_FACTOR_EDGE_WGRAD = True      # EdgeModel first Linear factored into node / edge parts (round 4, profiles/r04_ab_factor_edge.log)
+_FACTOR_MIN_GF = 0.5           # ... from this many GF of the un-factored product where the one-launch kernels do not apply (_factor_edge)
+_FACTOR_FUSED = True           # ... with the gathers / node sums inside dosx_gemm's epilogues (round 5, HISTORY.md)
+_EDGE_ONE_LAUNCH = True        # ... and the whole EdgeModel forward as one launch, hidden <= 128 (profiles/r05_edge_kernels.log)
+_EDGE_ONE_LAUNCH_BWD = True    # ... and its backward (profiles/r05_edge_kernels.log)
+_FACTOR_LAST = True            # last layer: aggregate per node, then the second Linear (profiles/r04_ab_factor_last.log)
+_FACTOR_LAST_MIN_GF = 1.3      # ... from this many GF of that Linear's E-row product (_factor_last)
+_FACTOR_HEADS = True           # output heads: per-crystal K-segments multiplied once per crystal (profiles/r04_ab_factor_heads.log)
+_FACTOR_HEADS_MIN_GF = 1.0     # ... from this many GF of saved products (_factor_heads)
+_FUSED_ATT_FFN = True          # <= 16-key attention inside dosx_ffn_fwd (profiles/r04_kernel_microbench.log, `layer`)
+_ATT_FFN_MAX_ROWS = 4096       # ... while the feed-forward launch runs 16-row workgroups (same log)
+_ATT_ALIGNED = True            # crystal-aligned tiles, <= 64 keys (DosxFfn.att_aligned; profiles/r04_ab_att_aligned.log)
+_ATT_ALIGNED_MAX_WGS = 256     # ... while that grid is one round of workgroups
+_ATT_ROWS_FIRST = True         # <= 16 keys and <= 4096 rows: the per-row form wins over the aligned one (round 5, HISTORY.md)
+_FUSED_ATT_BWD = True          # attention backward inside dosx_ffn_bwd, crystal-aligned tiles (round 5)
+_FFN_MULTI = True              # an encoder stack's layers in one forward launch (profiles/r06_ab_run7.log)
+_FUSED_FIN_BWD = True          # final LayerNorm (+ output layer) backward inside the last layer's ffn_bwd launch
+_FUSED_HEAD_FWD = True         # final LayerNorm + output layer inside the last ffn_fwd launch
+# OPT-IN (off by default; every default program is exact fp32): the plain GEMMs of an UNFUSED feed-forward half (hidden > 128:
+# fc1 forward on the LayerNorm-1 rows the attention kernel left behind, fc2 forward, fc2's input gradient with the ReLU mask) on the
+# split-bf16 kernel (csrc/gemm_bf16x3.hip: three bf16 terms per fp32 element, fp32 accumulate - fp32-level accuracy, not bitwise the
+# fp32-FMA chain).  bench.py reports the Electron-DOS step under it as `secondary.edos_h256_b64_split_bf16`; the oracle-live tests run
+# under it with their tolerances unchanged (tests/test_gpu_models.py).  fc1's input gradient keeps dosx_gemm (LayerNorm-backward
+# epilogue).  DESIGN.md 5.3.
+_FFN_BF16X3 = from_environ("DOSX_FFN_BF16X3", "0") == "1"
+
 # M-splits of the weight gradients that run alone at the end of the step (round 3: 1.2918 -> 1.2841 ms per cfg2 step with 32,
-# 1.2845 with 16; 0 = the throughput-oriented count of dosx_wgrad_splits, tools/exp/ab_tail.sh)
-_TAIL_SPLITS = int(__import__("os").environ.get("DOSX_WGRAD_TAIL_SPLITS", "32"))
+# 1.2845 with 16)
+_TAIL_SPLITS = 32
+# hidden <= this: the early gradient bucket's flush (transformers / heads: `mid_hook`) BEHIND the last layer's NodeModel backward launch
+# instead of in front of it - that launch then does not start under a freshly launched weight-gradient group: 1.0726 -> 1.0690 ms per
+# cfg2 step, three interleaved rounds (profiles/r06_ab_run4.log).  Hidden 256 (cfg3 / its T4 shard, profiles/r06_ab_run9.log): 6.968 ->
+# 6.997 and 6.875 -> 6.912 ms - the NodeModel backward is a row-tile kernel there and the early group is 4x the work
+_MID_HOOK_LATE_MAX_H = 128
+# Unfused feed-forward layers (hidden > 128), FORWARD: tail rows of at most this many as a concurrent two-GEMM chain.  Electron-DOS step
+# 7.535 -> 7.473 ms (four interleaved rounds, profiles/r04_ab_ffn_tail.log); the same split in the backward pass, where the weight-
+# gradient groups already fill every gap, gave the gain back (7.526 ms) and is not built in.
+_FFN_TAIL_MAX = 2048
 
 
 def _wgrad_linear(sink: GradSink, G: Params, wkey: str, bkey: Optional[str], M: int, N: int, dy: Seg,
@@ -74,7 +114,7 @@ def _wgrad_linear(sink: GradSink, G: Params, wkey: str, bkey: Optional[str], M: 
         return
     K = sum(s.width for s in segs)
     ns = ops.wgrad_splits(M, N, K)
-    if _TAIL_SPLITS > 0 and tail:
+    if tail:
         # (tail: a weight gradient of the LAST group of the step - its dY exists only at the very end of the backward pass
         #  and it runs with the GPU to itself: latency, not throughput, is what counts there)
         ns = max(ns, min(_TAIL_SPLITS, max(M // 128, 1)))
@@ -124,13 +164,6 @@ def mlp_prelu_bwd(P: Params, G: Params, key: str, ctx, dy: torch.Tensor, sink: G
     _wgrad_linear(sink, G, key + ".0.weight", key + ".0.bias", M, H, seg(dz), a.segs, keep=(dz,), tail=tail)
 
 
-_ENC_BWD_PAIR = __import__("os").environ.get("DOSX_ENC_BWD_PAIR", "1") == "1"
-# the next layer's node products inside the NodeModel launch (DosxMlpLn.w3): measured 1.1014 vs 1.1018 ms at cfg2, 6.978 vs 6.963 ms
-# Electron-DOS (three / two interleaved pairs) - the launch it removes costs what the longer kernel adds; off
-_PQ_IN_NODE_MLP = __import__("os").environ.get("DOSX_PQ_IN_NODE_MLP", "0") == "1"
-_PQ_IN_NODE_MLP_CS = __import__("os").environ.get("DOSX_PQ_IN_NODE_MLP_CS", "1") == "1"     # ... inside the column-split NodeModel launch
-
-
 def mlp_prelu_bwd_pair(P: Params, G: Params, first, second, sink: GradSink, tail: bool = False):
     """The backward of TWO encoder MLPs (first / second = (key, ctx, dy)) whose output gradients exist at the same time - the
     node and the edge encoder at the tail of the step: their two input-gradient products as ONE launch (dosx_gemm_pair: each at
@@ -168,11 +201,11 @@ def _factor_edge(E: int, H: int, m=None) -> bool:
     the layer (hidden 64 / 128, a batch `m` with node-aligned row tiles) ALWAYS - the factored layer is then fewer launches
     (backward: 3 instead of 5) as well as fewer flops, also at the CPU-reference shape (Phonon-DOS H 64, 8 crystals: 0.573 ->
     0.557 ms per step, tools/exp/r5_ab_small.sh); (b) otherwise (gathered addends / destination sums inside dosx_gemm's
-    epilogues) from DOSX_FACTOR_MIN_GF = 0.5 GF."""
+    epilogues) from _FACTOR_MIN_GF = 0.5 GF."""
     if not _FACTOR_EDGE_WGRAD:
         return False
     if (m is not None and getattr(m, "seg_tile", None) is not None and _FACTOR_FUSED and _EDGE_ONE_LAUNCH and _EDGE_ONE_LAUNCH_BWD
-            and _FACTOR_DGRAD and _FACTOR_ONE_LAUNCH_ALWAYS and ops.edge_mlp_supported(H)):
+            and ops.edge_mlp_supported(H)):
         return True
     return 2.0 * E * (2 * H) * (3 * H) >= _FACTOR_MIN_GF * 1e9
 
@@ -185,14 +218,14 @@ def _factor_fused(m, H: int) -> bool:
 
 def _factor_heads(rows: int, H: int) -> bool:
     """Whether the two output heads multiply their per-crystal K-segments (graph, prompt) once per crystal instead of once per
-    energy: from DOSX_FACTOR_HEADS_MIN_GF (1) GF of saved products - the Electron-DOS shapes (4.2 / 2.1 GF); the Phonon-DOS
+    energy: from _FACTOR_HEADS_MIN_GF (1) GF of saved products - the Electron-DOS shapes (4.2 / 2.1 GF); the Phonon-DOS
     benchmark shape (0.27 GF) and small-batch inference keep the two launches fewer."""
     return _FACTOR_HEADS and 2.0 * rows * H * (2.5 * H) >= _FACTOR_HEADS_MIN_GF * 1e9
 
 
 def _factor_last(E: int, H: int) -> bool:
     """Whether the LAST message-passing layer aggregates its activations per node in front of its second Linear (mlp_ln_fwd,
-    aggsum): from DOSX_FACTOR_LAST_MIN_GF GF of that Linear's E-row product."""
+    aggsum): from _FACTOR_LAST_MIN_GF GF of that Linear's E-row product."""
     return _FACTOR_LAST and not _wide_ln(H) and 2.0 * E * (2 * H) * H >= _FACTOR_LAST_MIN_GF * 1e9
 
 
@@ -318,7 +351,7 @@ def mlp_ln_bwd(P: Params, G: Params, key: str, ctx, dy: torch.Tensor, sink: Grad
     assert fused or not add_dy
     assert pre is None or fused           # (pre: what produces dy, in the same column-split launch - see node_chain_ok)
     wide = _wide_ln(H) or agg_first is not None
-    fac_dgrad = a.factor is not None and _factor_edge(M, H, a.factor[2]) and _FACTOR_DGRAD and not fused
+    fac_dgrad = a.factor is not None and _factor_edge(M, H, a.factor[2]) and not fused
     # round 5: the destination-node sums of dz (the factored weight / input gradients below need them) inside the dgrad GEMM's
     # epilogue, on the batch's node-aligned row tiles - one partial row per tile
     seg_bwd = (fac_dgrad and agg_first is None and not wide and _factor_fused(a.factor[2], H) and a.factor[2].seg_tile is not None
@@ -354,117 +387,79 @@ def mlp_ln_bwd(P: Params, G: Params, key: str, ctx, dy: torch.Tensor, sink: Grad
     sink.add(part, 0, G[key + ".1.weight"], rows, pld, 2 * H)
     sink.add(part, 2 * H, G[key + ".1.bias"], rows, pld, 2 * H)
     sink.add(part, pld - 1, G[key + ".2.weight"], rows, pld, 1)
-    fac = a.factor
-    aggS = aggD = None
-    if fac is not None and _factor_edge(M, H, fac[2]) and (key + ".0.weight" in G or fac_dgrad):
-        # The first Linear reads cat[x[row], x[col], e] (DOSTransformer_phonon.py:193-195): its weight gradient is
-        #   sum_e dz_e (x) [x[row(e)] | x[col(e)] | e_e]  =  [ sum_n S_n (x) x_n | sum_n D_n (x) x_n | sum_e dz_e (x) e_e ],
-        # S_n / D_n = the sums of dz over the edges that leave / enter node n.  The two node blocks become N-row jobs (20 x
-        # fewer rows at 20 edges per node) behind two memory-bound segment sums that run on the weight-gradient stream in
-        # front of the group; the edge block keeps its E rows on a third of the columns.  Three jobs write the three column
-        # blocks of the one gradient (DosxWgrad.ldd); fixed summation orders, like everything else here.
-        x, e, m = fac
-        N_, E_ = m.num_nodes, m.num_edges
-        aggS = sink.scratch(N_, 2 * H)
-        aggD = aggD_epi if aggD_epi is not None else sink.scratch(N_, 2 * H)
-
-        # (the source sums: by the caller's dosx_node_grad launch when that form runs, gnn_bwd)
-        node_one = fac_dgrad and _NODE_GRAD_ONE_LAUNCH and _factor_fused(m, H) and H in (64, 128, 256)
-
-        def node_sums(dz=dz, aggS=aggS, aggD=aggD, m=m, with_dst=aggD_epi is None, with_src=not node_one):
-            if with_src:
-                ops.segment_reduce_perm(dz, m.rowptr_src, m.perm_src, aggS, N_, E_, 2 * H)
-            if with_dst:                               # (else: written by the dgrad GEMM's epilogue above)
-                ops.segment_reduce(dz, m.rowptr_dst, None, aggD, None, None, N_, E_, 2 * H)
-        if fac_dgrad:
-            node_sums()                                # the input gradient below reads them too: on the main stream, now
-            sink._keep.append(dz)
-        else:
-            sink.defer_pre(node_sums, keep=(dz,))
-        if key + ".0.weight" in G:
-            Gw = G[key + ".0.weight"]                  # [2H, 3H]
-
-            # the source block's job reads aggS.  With node_one that is written LATER, by the caller's dosx_node_grad launch:
-            # the job is handed back as a closure and gnn_bwd describes it behind that launch, so that no flush between here and
-            # there can launch it early
-            def src_job(Gw=Gw, aggS=aggS, x=x):
-                with ops.graph_rows():
-                    _wgrad_linear(sink, G, key + ".0.weight", None, N_, 2 * H, seg(aggS), [seg(x)], keep=(aggS, x), dst=Gw[:, :H])
-            if not node_one:
-                src_job()
-                src_job = None
-            with ops.graph_rows():
-                _wgrad_linear(sink, G, key + ".0.weight", None, N_, 2 * H, seg(aggD), [seg(x)], keep=(aggD, x), dst=Gw[:, H:2 * H])
-                _wgrad_linear(sink, G, key + ".0.weight", key + ".0.bias", M, 2 * H, seg(dz), [seg(e)], keep=(dz, e), dst=Gw[:, 2 * H:])
-        else:
-            src_job = None
-    else:
-        src_job = None
+    if not fac_dgrad:
         _wgrad_linear(sink, G, key + ".0.weight", key + ".0.bias", M, 2 * H, seg(dz), a.segs, keep=(dz,))
-    if fac_dgrad:
-        # ... and the INPUT gradient factored the same way: dL/de = dz Wc (+ the incoming edge-state gradient) is the only
-        # E-row product left (a third of the columns of the [E,3H] concat gradient); the node parts come from the node sums,
-        # sum_{e: row(e) = n} dz_e Wa = S_n Wa - the caller (gnn_bwd) multiplies N rows instead of gathering E of them back
-        W0 = P[key + ".0.weight"]
-        de_new = _empty(dev, M, H)
-        ops.gemm(M, H, [seg(dz)], W0[:, 2 * H:], de_new, w_layout=1, res=res)
-        return ("factored", de_new, aggS, aggD, dz if node_one else None, src_job if node_one else None, False)
-    if not fused:
-        ops.gemm(M, a.K, [seg(dz)], P[key + ".0.weight"], dcat, w_layout=1, res=res, res_col0=res_col0 if res is not None else 0)
-    return dcat
+        if not fused:
+            ops.gemm(M, a.K, [seg(dz)], P[key + ".0.weight"], dcat, w_layout=1, res=res, res_col0=res_col0 if res is not None else 0)
+        return dcat
+    # The first Linear reads cat[x[row], x[col], e] (DOSTransformer_phonon.py:193-195): its weight gradient is
+    #   sum_e dz_e (x) [x[row(e)] | x[col(e)] | e_e]  =  [ sum_n S_n (x) x_n | sum_n D_n (x) x_n | sum_e dz_e (x) e_e ],
+    # S_n / D_n = the sums of dz over the edges that leave / enter node n.  The two node blocks become N-row jobs (20 x
+    # fewer rows at 20 edges per node) behind two memory-bound segment sums - on the main stream, now: the input gradient
+    # reads them too; the edge block keeps its E rows on a third of the columns.  Three jobs write the three column
+    # blocks of the one gradient (DosxWgrad.ldd); fixed summation orders, like everything else here.
+    x, e, m = a.factor
+    N_, E_ = m.num_nodes, m.num_edges
+    aggS = sink.scratch(N_, 2 * H)
+    aggD = aggD_epi if aggD_epi is not None else sink.scratch(N_, 2 * H)
+    node_one = _factor_fused(m, H) and H in (64, 128, 256)
+    if not node_one:                               # (else: by the caller's dosx_node_grad launch, gnn_bwd)
+        ops.segment_reduce_perm(dz, m.rowptr_src, m.perm_src, aggS, N_, E_, 2 * H)
+    if aggD_epi is None:                           # (else: written by the dgrad GEMM's epilogue above)
+        ops.segment_reduce(dz, m.rowptr_dst, None, aggD, None, None, N_, E_, 2 * H)
+    sink._keep.append(dz)
+    src_job = None
+    if key + ".0.weight" in G:
+        Gw = G[key + ".0.weight"]                  # [2H, 3H]
 
-
-# Round 6: the N-row launch in front of a NodeModel backward - the node side of the later layer's input gradient (dosx_node_grad),
-# or the dense-key / pooled-decoder backward in front of the last layer's - runs INSIDE that column-split launch (DosxMlpLnBwd.pre)
-# (measured, tools/exp/r6_run2.sh / r6_run3.sh, cfg2 step, three interleaved rounds each: the dense-key launch absorbed 1.0940 ->
-#  1.0726 ms - kept; the node side absorbed as well 1.0893 -> 1.1018 ms, with the layer's weight-gradient group flushed behind the
-#  launch instead of in front of it 1.1102 ms - three in-launch exchanges under a weight-gradient group cost more than the launch
-#  they save: off)
-_NODE_CHAIN = __import__("os").environ.get("DOSX_NODE_CHAIN", "0") == "1"
-_DENSE_CHAIN = __import__("os").environ.get("DOSX_DENSE_CHAIN", "1") == "1"
-# ... and the layer's weight-gradient group is then flushed BEHIND that launch (it runs alone, all CUs) instead of in front of it
-# the early gradient bucket's flush (transformers / heads: `mid_hook`) BEHIND the last layer's NodeModel backward launch instead of
-# in front of it - that launch then does not start under a freshly launched weight-gradient group: 1.0726 -> 1.0690 ms per cfg2
-# step, three interleaved rounds (tools/exp/r6_run4.sh).  Hidden 256 (cfg3 / its T4 shard, tools/exp/r6_run9.sh): 6.968 -> 6.997
-# and 6.875 -> 6.912 ms - the NodeModel backward is a row-tile kernel there and the early group is 4x the work: hidden <= 128 only
-_MID_HOOK_LATE = __import__("os").environ.get("DOSX_MID_HOOK_LATE", "1") == "1"
-_MID_HOOK_LATE_MAX_H = 128
-_EDGE_ENC_ONE_LAUNCH = __import__("os").environ.get("DOSX_EDGE_ENC_ONE_LAUNCH", "1") == "1"
-_FFN_MULTI = __import__("os").environ.get("DOSX_FFN_MULTI", "1") == "1"   # an encoder stack's layers in one forward launch
-_ENC_CS = __import__("os").environ.get("DOSX_ENC_CS", "1") == "1"        # node encoder + layer 0's node products: one column-split launch
+        # the source block's job reads aggS.  With node_one that is written LATER, by the caller's dosx_node_grad launch:
+        # the job is handed back as a closure and gnn_bwd describes it behind that launch, so that no flush between here and
+        # there can launch it early
+        def src_job(Gw=Gw, aggS=aggS, x=x):
+            with ops.graph_rows():
+                _wgrad_linear(sink, G, key + ".0.weight", None, N_, 2 * H, seg(aggS), [seg(x)], keep=(aggS, x), dst=Gw[:, :H])
+        if not node_one:
+            src_job()
+            src_job = None
+        with ops.graph_rows():
+            _wgrad_linear(sink, G, key + ".0.weight", None, N_, 2 * H, seg(aggD), [seg(x)], keep=(aggD, x), dst=Gw[:, H:2 * H])
+            _wgrad_linear(sink, G, key + ".0.weight", key + ".0.bias", M, 2 * H, seg(dz), [seg(e)], keep=(dz, e), dst=Gw[:, 2 * H:])
+    # ... and the INPUT gradient factored the same way: dL/de = dz Wc (+ the incoming edge-state gradient) is the only
+    # E-row product left (a third of the columns of the [E,3H] concat gradient); the node parts come from the node sums,
+    # sum_{e: row(e) = n} dz_e Wa = S_n Wa - the caller (gnn_bwd) multiplies N rows instead of gathering E of them back
+    W0 = P[key + ".0.weight"]
+    de_new = _empty(dev, M, H)
+    ops.gemm(M, H, [seg(dz)], W0[:, 2 * H:], de_new, w_layout=1, res=res)
+    return ("factored", de_new, aggS, aggD, dz if node_one else None, src_job, False)
 
 
 def dev_of(P: Params):
     return next(iter(P.values())).device
 
 
-_HEADS_BWD_ONE_LAUNCH = __import__("os").environ.get("DOSX_HEADS_BWD_ONE_LAUNCH", "1") == "1"
-_HEADS_BWD_MAX_H = int(__import__("os").environ.get("DOSX_HEADS_BWD_MAX_H", "128"))
-_FLUSH_AFTER_CHAIN = __import__("os").environ.get("DOSX_FLUSH_AFTER_CHAIN", "0") == "1"
-
-
 def node_chain_ok(cxn, N: int, H: int) -> bool:
     """Whether the NodeModel backward described by ``cxn`` (mlp_ln_fwd's context) will run as the column-split one-launch kernel
     on a contiguous [N, H] gradient - the form that takes ``pre``."""
     a = cxn[0]
-    return (_mlp_ln_fused(a, N, H) and a.aggsum is None and ops.MLP_LN_CS_BWD != "0" and ops.mlp_ln_cs(N, 2 * H, 2 * H, H))
+    return _mlp_ln_fused(a, N, H) and a.aggsum is None and ops.mlp_ln_cs(N, 2 * H, 2 * H, H)
 
 
 def edge_bwd_one_launch_ok(a: SegList, M: int, H: int) -> bool:
     """Whether the EdgeModel's backward runs as ONE launch (csrc/edge_mlp.hip, edge_bwd_kernel): factored first Linear, the
     batch's node-aligned row tiles, hidden 64 / 128, per-edge second Linear."""
-    return (a.factor is not None and a.aggsum is None and _factor_edge(M, H, a.factor[2]) and _FACTOR_DGRAD and _factor_fused(a.factor[2], H)
+    return (a.factor is not None and a.aggsum is None and _factor_edge(M, H, a.factor[2]) and _factor_fused(a.factor[2], H)
             and _EDGE_ONE_LAUNCH_BWD and a.factor[2].seg_tile is not None and ops.edge_mlp_supported(H))
 
 
 def edge_mlp_bwd_one_launch(P: Params, G: Params, key: str, ctx, dagg: torch.Tensor, de_next: Optional[torch.Tensor], scale,
                             sink: GradSink):
     """dagg [N, H] (a strided view): gradient of the aggregate; de_next: gradient of e_{l+1} or None.  Returns what
-    mlp_ln_bwd's factored branch returns: ("factored", dL/de_l [E,H], aggS, aggD)."""
+    mlp_ln_bwd's factored branch returns: ("factored", dL/de_l [E,H], aggS, aggD, dz, src_job, early) - the source sums aggS are
+    made by the caller's dosx_node_grad launch (gnn_bwd)."""
     a, xhat, rstd, M, H = ctx
     x, e, m = a.factor
     dev = xhat.device
-    N_, E_ = m.num_nodes, m.num_edges
+    N_ = m.num_nodes
     gam, bet, alpha = P[key + ".1.weight"], P[key + ".1.bias"], P[key + ".2.weight"]
     W0 = P[key + ".0.weight"]
     rows = int(m.seg_tile.shape[1]) - 1
@@ -479,9 +474,6 @@ def edge_mlp_bwd_one_launch(P: Params, G: Params, key: str, ctx, dagg: torch.Ten
     sink.add(part, 0, G[key + ".1.weight"], rows, pld, 2 * H)
     sink.add(part, 2 * H, G[key + ".1.bias"], rows, pld, 2 * H)
     sink.add(part, pld - 1, G[key + ".2.weight"], rows, pld, 1)
-    node_one = _NODE_GRAD_ONE_LAUNCH          # the source sums are then made by the caller's dosx_node_grad launch (gnn_bwd)
-    if not node_one:
-        ops.segment_reduce_perm(dz, m.rowptr_src, m.perm_src, aggS, N_, E_, 2 * H)
     sink._keep.extend(t for t in (dz, dagg, de_next) if t is not None)
     src_job = None
     if key + ".0.weight" in G:
@@ -490,14 +482,15 @@ def edge_mlp_bwd_one_launch(P: Params, G: Params, key: str, ctx, dagg: torch.Ten
         def src_job(Gw=Gw, aggS=aggS, x=x):           # the source block's job reads aggS: described once that exists (see gnn_bwd)
             with ops.graph_rows():
                 _wgrad_linear(sink, G, key + ".0.weight", None, N_, 2 * H, seg(aggS), [seg(x)], keep=(aggS, x), dst=Gw[:, :H])
-        if not node_one:             # (aggS exists: made by the segment_reduce_perm launch above)
-            src_job()
-            src_job = None
         with ops.graph_rows():
             _wgrad_linear(sink, G, key + ".0.weight", None, N_, 2 * H, seg(aggD), [seg(x)], keep=(aggD, x), dst=Gw[:, H:2 * H])
             _wgrad_linear(sink, G, key + ".0.weight", key + ".0.bias", M, 2 * H, seg(dz), [seg(e)], keep=(dz, e), dst=Gw[:, 2 * H:])
-    # last field: whether the layer's weight-gradient group may be flushed IN FRONT of the caller's node-side launch (gnn_bwd)
-    return ("factored", de_new, aggS, aggD, dz if node_one else None, src_job, node_one and _GNN_FLUSH_BEFORE_NODE)
+    # last field (early): the layer's weight-gradient group is flushed IN FRONT of the caller's node-side launch (dosx_node_grad: 57
+    # workgroups) and runs under it and the next NodeModel backward (27 workgroups) - the two windows of the GNN backward that leave
+    # most CUs idle - instead of behind them, under the next EdgeModel backward (213 workgroups of a CU each); only the source block's
+    # job, which reads the source sums that launch makes, moves to the next group: 1.187 -> 1.173 ms per cfg2 step (three interleaved
+    # pairs, round 5)
+    return ("factored", de_new, aggS, aggD, dz, src_job, True)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -531,10 +524,10 @@ def gnn_fwd(P: Params, m: GraphMeta, x: torch.Tensor, e: torch.Tensor, L: int, m
         a_n = SegList([seg(x), seg(agg)], [x, agg], plain=(x, agg))
         pq_next = None
         # (round 6: with the COLUMN-SPLIT NodeModel launch - an eighth of the extra weights per workgroup, one more in-launch
-        #  exchange - it pays: always there; the one-workgroup-per-tile form keeps the launch, DOSX_PQ_IN_NODE_MLP)
-        cs_node = ops.mlp_ln_cs(N, 2 * H, 2 * H, H) and ops.mlp_ln_fwd_supported(N, 2 * H, 2 * H, H) and _PQ_IN_NODE_MLP_CS
-        if (l + 1 < L and _factor_edge(E, H, m) and ops.mlp_ln_fwd_supported(N, 2 * H, 2 * H, H) and
-                (cs_node or (_PQ_IN_NODE_MLP and (2 * H) % 256 == 0))):
+        #  exchange - it pays: always there; in the one-workgroup-per-tile form the launch it removes costs what the longer kernel
+        #  adds - 1.1014 vs 1.1018 ms at cfg2, 6.978 vs 6.963 ms Electron-DOS - and the products keep their own launch)
+        cs_node = ops.mlp_ln_cs(N, 2 * H, 2 * H, H) and ops.mlp_ln_fwd_supported(N, 2 * H, 2 * H, H)
+        if l + 1 < L and _factor_edge(E, H, m) and cs_node:
             # the next layer's node products (x_new Wa^T | x_new Wb^T) ride in this NodeModel launch: one launch fewer per layer
             pq_ready = _empty(dev, N, 4 * H)
             pq_next = (P[f"stacked_processor.{l + 1}.edge_model.edge_mlp.0.weight"], pq_ready)
@@ -544,18 +537,17 @@ def gnn_fwd(P: Params, m: GraphMeta, x: torch.Tensor, e: torch.Tensor, L: int, m
     return x, ctxs
 
 
-_SPLIT_LATE_FLUSH = int(__import__("os").environ.get("DOSX_SPLIT_LATE_FLUSH", "1"))
-
-
 def gnn_bwd(P: Params, G: Params, m: GraphMeta, ctxs, dx: torch.Tensor, sink: GradSink, L: int, mean: bool, H: int, dx_pre=None):
     """Returns (dL/dx_0 [N,H], dL/de_0 as a strided [E,H] view or None).
     dx_pre: None, or (pre, launch): ``dx`` has NOT been computed yet - ``pre`` is the ops.mlp_ln_bwd ``pre`` dictionary that makes
     it inside the last layer's NodeModel backward launch, ``launch()`` the stand-alone launch for when that form does not apply."""
     N, E = m.num_nodes, m.num_edges
     dev = dx.device
-    pending = None          # the `pre` of the NEXT NodeModel backward: this layer's node-side launch, deferred into it
+    pending = None          # the `pre` of the last layer's NodeModel backward
     if dx_pre is not None:
-        if _DENSE_CHAIN and node_chain_ok(ctxs[L - 1][1], N, H) and dx.is_contiguous():
+        # round 6: the dense-key / pooled-decoder backward in front of the last layer's NodeModel backward runs INSIDE that column-split
+        # launch (DosxMlpLnBwd.pre): 1.0940 -> 1.0726 ms per cfg2 step, three interleaved rounds (profiles/r06_ab_run2.log / r06_ab_run3.log)
+        if node_chain_ok(ctxs[L - 1][1], N, H) and dx.is_contiguous():
             pending = dx_pre[0]
         else:
             dx_pre[1]()
@@ -574,11 +566,9 @@ def gnn_bwd(P: Params, G: Params, m: GraphMeta, ctxs, dx: torch.Tensor, sink: Gr
         pre = f"stacked_processor.{l}"
         cxe, cxn = ctxs[l]
         # factored edge layer + one-launch NodeModel backward: the residual path's dx rides on the first H columns of dcat_n
-        fold_dx = (cxe[0].factor is not None and _factor_edge(E, H, m) and _FACTOR_DGRAD and _factor_fused(m, H)
+        fold_dx = (cxe[0].factor is not None and _factor_edge(E, H, m) and _factor_fused(m, H)
                    and mlp_ln_bwd_fused(cxn[0], N, H, dx))
         dcat_n = mlp_ln_bwd(P, G, pre + ".node_model.node_mlp_2", cxn, dx, sink, add_dy=fold_dx, pre=pending)          # [N, 2H]
-        if pending is not None and pending.get("flush_after"):
-            flush_side(l)
         pending = None
         hook1 = getattr(sink, "after_first_node", None)
         if hook1 is not None:
@@ -610,17 +600,13 @@ def gnn_bwd(P: Params, G: Params, m: GraphMeta, ctxs, dx: torch.Tensor, sink: Gr
             if node_one:
                 src_job = dcat_e[5]                    # the source block's weight-gradient job: reads the sums the launch below makes
                 early = bool(dcat_e[6])                # the layer's group starts BEFORE the node-side launch, under it
-                chain = _NODE_CHAIN and l > 0 and node_chain_ok(ctxs[l - 1][1], N, H)
-                do_flush = early and sink.wside is not None and (l == 0 or (_SPLIT_LATE_FLUSH == 1 and l == 1) or (_SPLIT_LATE_FLUSH == 2 and l >= 1))
-                if do_flush and not (chain and _FLUSH_AFTER_CHAIN):
+                if early and sink.wside is not None and l <= 1:
                     flush_side(l)
-                # source sums of dz + both node products + the residual terms: ONE launch (csrc/edge_mlp.hip, node_grad_kernel) -
-                # or, round 6, the front part of the NEXT layer's NodeModel backward launch (DosxMlpLnBwd.pre = 1)
-                if chain:
-                    pending = dict(kind="node_grad", dz=dcat_e[4], rowptr_src=m.rowptr_src, perm_src=m.perm_src, aggd=aggD, w=W0,
-                                   res=dcat_n[:, :H], res2=None if fold_dx else dx, aggs=aggS, flush_after=do_flush and _FLUSH_AFTER_CHAIN)
-                else:
-                    ops.node_grad(N, H, dcat_e[4], m.rowptr_src, m.perm_src, aggD, W0, dcat_n[:, :H], None if fold_dx else dx, aggS, dx_old)
+                # source sums of dz + both node products + the residual terms: ONE launch (csrc/edge_mlp.hip, node_grad_kernel)
+                # (round 6 measured it inside the NEXT layer's NodeModel backward launch, DosxMlpLnBwd.pre = 1: 1.0893 -> 1.1018 ms per
+                #  cfg2 step, profiles/r06_ab_run3.log - three in-launch exchanges under a weight-gradient group cost more than the launch
+                #  they save; not built in)
+                ops.node_grad(N, H, dcat_e[4], m.rowptr_src, m.perm_src, aggD, W0, dcat_n[:, :H], None if fold_dx else dx, aggS, dx_old)
                 sink._keep.extend([dcat_n, dx, dcat_e[4], aggD])
                 if src_job is not None:
                     src_job()                          # (described BEHIND the launch that writes its operand; early: next group)
@@ -646,14 +632,14 @@ def gnn_bwd(P: Params, G: Params, m: GraphMeta, ctxs, dx: torch.Tensor, sink: Gr
                 ops.mask_residual(dcat_n[:, :H], None, t2, dx_old, None, N, H)
                 sink._keep.extend([dcat_n, t1, t2, dx])
             dx, de = dx_old, de_new
-            if sink.side is not None and ((_SPLIT_LATE_FLUSH == 1 and l == 1) or (_SPLIT_LATE_FLUSH == 2 and l >= 1)):
+            if sink.side is not None and l == 1:
                 flush_side(l)
             continue
         ops.gather_bwd(dcat_e, dcat_n.data_ptr(), 2 * H, dx, m.rowptr_dst, m.rowptr_src, m.perm_src, None, dx_old,
                        None, N, E, H)
         sink._keep.append(dcat_n)
         dx, de = dx_old, dcat_e[:, 2 * H:]
-        if sink.side is not None and ((_SPLIT_LATE_FLUSH == 1 and l == 1) or (_SPLIT_LATE_FLUSH == 2 and l >= 1)):
+        if sink.side is not None and l == 1:
             # the weight gradients of the layers finished so far go to the side stream NOW, underneath the first layer's
             # backward, instead of all of them at the tail of the step where nothing else is left to overlap with
             flush_side(l)
@@ -775,7 +761,7 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
             if stack:                       # (this layer launches its attention on its own: what is pending goes first)
                 ops.ffn_fwd_multi(stack)
                 stack.clear()
-            if _LN1_IN_ATTN and not ops.ffn_supported(H) and Nk <= 320:
+            if not ops.ffn_supported(H) and Nk <= 320:
                 # unfused feed-forward half (hidden > 128): the attention kernel also writes LN1 of its output rows - they are
                 # in its registers with their statistics - and fc1 reads a plain operand instead of normalising its A tile in the
                 # prologue of every one of its 4H / 128 column tiles (M = 25728: 163 -> 139 us, DosxAttn.ln1_out)
@@ -845,76 +831,24 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
     return x, (lay, fin, Sq, Bq, Nk, Bk, H, T, kvhat)
 
 
-# Unfused feed-forward layers (hidden > 128), FORWARD: tail rows as a concurrent two-GEMM chain.  Electron-DOS step 7.535 ->
-# 7.473 ms (four interleaved rounds, profiles/r04_ab_ffn_tail.log); the same split in the backward pass, where the weight-
-# gradient groups already fill every gap, gave the gain back (7.526 ms) and is not built in.
-# OPT-IN (off by default; every default program is exact fp32): the plain GEMMs of an UNFUSED feed-forward half (hidden > 128:
-# fc1 forward on the LayerNorm-1 rows the attention kernel left behind, fc2 forward, fc2's input gradient with the ReLU mask) on the
-# split-bf16 kernel (csrc/gemm_bf16x3.hip: three bf16 terms per fp32 element, fp32 accumulate - fp32-level accuracy, not bitwise the
-# fp32-FMA chain).  bench.py reports the Electron-DOS step under it as `secondary.edos_h256_b64_split_bf16`; the oracle-live tests run
-# under it with their tolerances unchanged (tests/test_gpu_models.py).  fc1's input gradient keeps dosx_gemm (LayerNorm-backward epilogue).
-_FFN_BF16X3 = __import__("os").environ.get("DOSX_FFN_BF16X3", "0") == "1"
-
-
 def _bf16x3_ok(rows: int, n: int, k: int) -> bool:
     return _FFN_BF16X3 and ops.gemm_bf16x3_supported(rows, n, k)
 
 
-_FFN_TAIL = int(__import__("os").environ.get("DOSX_FFN_TAIL", "1"))
-_FFN_TAIL_MAX = int(__import__("os").environ.get("DOSX_FFN_TAIL_MAX", "2048"))
-
-
 def _ffn_tail_start(rows: int, H: int) -> int:
     """First row of the tail of an unfused feed-forward layer (0: no split): the part beyond the last full round of 256
-    workgroups of 64 x 128 tiles of the H-wide GEMM (H = 256: 8192 rows), when it is small (<= DOSX_FFN_TAIL_MAX rows)."""
+    workgroups of 64 x 128 tiles of the H-wide GEMM (H = 256: 8192 rows), when it is small (<= _FFN_TAIL_MAX rows)."""
     gy = (H + 127) // 128
-    if not _FFN_TAIL or 256 % gy:
+    if 256 % gy:
         return 0
     per_round = 256 // gy * 64
     mt = rows // per_round * per_round
     return mt if mt > 0 and 0 < rows - mt <= _FFN_TAIL_MAX else 0
 
 
-_FUSED_FFN_BWD = __import__("os").environ.get("DOSX_FUSED_FFN_BWD", "1") == "1"
-_LN1_IN_ATTN = __import__("os").environ.get("DOSX_LN1_IN_ATTN", "1") == "1"
-_LN1_WGRAD = __import__("os").environ.get("DOSX_LN1_WGRAD", "0") == "1"     # (measured: 7.033 vs 7.036 ms - nothing; off)
-_FACTOR_EDGE_WGRAD = __import__("os").environ.get("DOSX_FACTOR_EDGE_WGRAD", "1") == "1"   # EdgeModel first Linear factored into node / edge parts
-_FACTOR_FUSED = __import__("os").environ.get("DOSX_FACTOR_FUSED", "1") == "1"               # ... with the gathers / node sums inside dosx_gemm's epilogues (round 5)
-_EDGE_ONE_LAUNCH = __import__("os").environ.get("DOSX_EDGE_ONE_LAUNCH", "1") == "1"       # ... and the whole EdgeModel forward as one launch (H <= 128)
-_EDGE_ONE_LAUNCH_BWD = __import__("os").environ.get("DOSX_EDGE_ONE_LAUNCH_BWD", "1") == "1"   # ... and its backward
-_NODE_GRAD_ONE_LAUNCH = __import__("os").environ.get("DOSX_NODE_GRAD_ONE_LAUNCH", "1") == "1"   # ... and the node side of the input gradient
-_FACTOR_ONE_LAUNCH_ALWAYS = __import__("os").environ.get("DOSX_FACTOR_ONE_LAUNCH_ALWAYS", "1") == "1"   # ... at every size where they apply
-# a layer's weight-gradient group is flushed BEFORE its node-side launch (dosx_node_grad: 57 workgroups) and runs under it and the
-# next NodeModel backward (27 workgroups) - the two windows of the GNN backward that leave most CUs idle - instead of behind them,
-# under the next EdgeModel backward (213 workgroups of a CU each); only the source block's job, which reads the source sums that
-# launch makes, moves to the next group: 1.187 -> 1.173 ms per cfg2 step (three interleaved pairs, tools/exp/r5_ab_flush.sh)
-_GNN_FLUSH_BEFORE_NODE = __import__("os").environ.get("DOSX_GNN_FLUSH_BEFORE_NODE", "1") == "1"
-_FACTOR_MIN_GF = float(__import__("os").environ.get("DOSX_FACTOR_MIN_GF", "0.5" if _FACTOR_FUSED else "4"))
-_FACTOR_DGRAD = __import__("os").environ.get("DOSX_FACTOR_DGRAD", "1") == "1"             # ... and its input gradient
-_FACTOR_HEADS = __import__("os").environ.get("DOSX_FACTOR_HEADS", "1") == "1"             # heads: per-crystal K-segments multiplied once per crystal
-_FACTOR_HEADS_MIN_GF = float(__import__("os").environ.get("DOSX_FACTOR_HEADS_MIN_GF", "1"))
-_FACTOR_LAST = __import__("os").environ.get("DOSX_FACTOR_LAST", "1") == "1"               # last layer: aggregate, then the second Linear
-_FACTOR_LAST_MIN_GF = float(__import__("os").environ.get("DOSX_FACTOR_LAST_MIN_GF", "1.3"))
-_FUSED_ATT_FFN = __import__("os").environ.get("DOSX_FUSED_ATT_FFN", "1") == "1"       # <= 16-key attention inside dosx_ffn_fwd
-_ATT_FFN_MAX_ROWS = int(__import__("os").environ.get("DOSX_ATT_FFN_MAX_ROWS", "4096"))
-_ATT_ALIGNED = __import__("os").environ.get("DOSX_ATT_ALIGNED", "1") == "1"           # crystal-aligned tiles (DosxFfn.att_aligned)
-_ATT_ALIGNED_MAX_WGS = int(__import__("os").environ.get("DOSX_ATT_ALIGNED_MAX_WGS", "256"))
-_ATT_ROWS_FIRST = __import__("os").environ.get("DOSX_ATT_ROWS_FIRST", "1") == "1"     # <= 16 keys and <= 4096 rows: the per-row form
-_FUSED_ATT_BWD = __import__("os").environ.get("DOSX_FUSED_ATT_BWD", "1") == "1"        # attention backward inside dosx_ffn_bwd (crystal-aligned tiles)
-_FUSED_DKV = __import__("os").environ.get("DOSX_FUSED_DKV", "1") == "1"
-# the self encoder's weight-gradient group starts BEHIND the small head kernels (rownorm_bwd_act, the two dE1 dgrads) instead of in
-# front of them: "1" / "0", or "auto" = where the heads' weight gradients are not factored (their B-row jobs read a row sum that
-# is made later, on the side stream).  Round 3: no gain (DESIGN.md 3.4); round 5, with the encoder layers' backward one launch
-# each: 1.1224-1.1284 vs 1.1298-1.1331 ms per cfg2 step, three interleaved pairs (tools/exp/r5_ab_rowsfirst.sh)
-_LATE_SELF_FLUSH = __import__("os").environ.get("DOSX_LATE_SELF_FLUSH", "auto")
-_FUSED_FIN_BWD = __import__("os").environ.get("DOSX_FUSED_FIN_BWD", "1") == "1"
-_FUSED_HEAD_FWD = __import__("os").environ.get("DOSX_FUSED_HEAD_FWD", "1") == "1"
-_FUSED_HEAD_NORM = __import__("os").environ.get("DOSX_FUSED_HEAD_NORM", "1") == "1"     # DosxGemm.norm_out in the two heads
-
-
 def head_fused_bwd(H: int, T: int) -> bool:
     """Whether encoder_bwd(head=...) runs the output layer + final LayerNorm backward inside its first ffn_bwd launch."""
-    return bool(ops.ffn_supported(H) and _FUSED_FFN_BWD and _FUSED_FIN_BWD and T > 0)
+    return bool(ops.ffn_supported(H) and _FUSED_FIN_BWD and T > 0)
 
 
 def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor], dkvhat: torch.Tensor, sink: GradSink,
@@ -931,7 +865,7 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
     rows = Sq * Bq
     r32 = _rows32(rows)
     dx = dy
-    fused_all = ops.ffn_supported(H) and _FUSED_FFN_BWD
+    fused_all = ops.ffn_supported(H)
     last_plain = T > 0 and lay[T - 1][9] is None            # (a layer on the relu / res dropout path runs unfused)
     fused = fused_all and last_plain
     fin_fused = None        # the final LayerNorm's backward rides in the last layer's ffn_bwd launch (csrc/ffn.hip)
@@ -971,7 +905,7 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
         small = bool(_lib_load().dosx_attention_pkv_supported(int(Nk), int(H)))
         # round 5: the attention half's backward INSIDE the feed-forward half's launch (crystal-aligned tiles, DosxFfnBwd.att_*):
         # the layer's backward is one launch and dL/dx1 never reaches HBM - while that grid is one round of workgroups
-        att_in_ffn = (fused and small and _FUSED_DKV and _FUSED_ATT_BWD and ops.ffn_att_bwd_supported(H, Nk, Sq, Bq)
+        att_in_ffn = (fused and small and _FUSED_ATT_BWD and ops.ffn_att_bwd_supported(H, Nk, Sq, Bq)
                       and ops.ffn_att_bwd_partial_rows(Sq, Bq) <= _ATT_ALIGNED_MAX_WGS)
         att_bwd_args = None
         if att_in_ffn:
@@ -1005,12 +939,9 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
             if fm is not None and fm[1] is not None:       # h is the dropped activation: [h > 0] = [relu > 0][M2 > 0]; x 1/(1-p)
                 ops.mask_residual(dh, fm[1], None, dh, None, rows, 4 * H)
         # fc1 (+ LN1 backward + residual)
-        xln = getattr(x1, "_dosx_ln1", None) if _LN1_WGRAD else None
-        if xln is not None:         # the forward left LN1(x1) behind (DosxAttn.ln1_out): a plain operand for the weight gradient too
-            _wgrad_linear(sink, G, lp + ".fc1.weight", lp + ".fc1.bias", rows, 4 * H, seg(dh), [seg(xln)], keep=(dh, xln))
-        else:
-            _wgrad_linear(sink, G, lp + ".fc1.weight", lp + ".fc1.bias", rows, 4 * H, seg(dh), [seg(x1)], keep=(dh,),
-                          pro=PRO_ROWLN, pro_gamma=g1, pro_beta=b1, pro_stats=st1)
+        # (the rows LN1(x1) that the forward's attention kernel may have left behind as a plain operand: measured 7.033 vs 7.036 ms - nothing)
+        _wgrad_linear(sink, G, lp + ".fc1.weight", lp + ".fc1.bias", rows, 4 * H, seg(dh), [seg(x1)], keep=(dh,),
+                      pro=PRO_ROWLN, pro_gamma=g1, pro_beta=b1, pro_stats=st1)
         if not fused:
             rgp = ops.gemm_partial_rows(rows, H, EPI_ROWLN_BWD)
             part = sink.scratch(rgp, 2 * H)
@@ -1053,7 +984,7 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
             a.partials_kv = part.data_ptr() + 4 * Bq * nqt * 2 * H
             a.flags = flags
             return a
-        if small and _FUSED_DKV:
+        if small:
             # ONE launch: every (query tile, crystal) workgroup publishes its share of dK + dV and the last one of a key
             # crystal to arrive finishes that crystal's key gradient (include/dosx.h: DosxAttn.dkv_cnt) - no reduction
             # launch, no side-stream round trip
@@ -1288,7 +1219,7 @@ def _gnn_trunk_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta, node_key: str):
     H, N, E, B = cfg.H, m.num_nodes, m.num_edges, m.num_graphs
     xin = _f32(g.x)
     pq0 = None
-    if (_ENC_CS and cfg.L >= 1 and m.seg_tile is not None and _factor_edge(E, H, m) and xin.shape[1] == P[node_key + ".0.weight"].shape[1]
+    if (cfg.L >= 1 and m.seg_tile is not None and _factor_edge(E, H, m) and xin.shape[1] == P[node_key + ".0.weight"].shape[1]
             and ops.enc_cs_supported(N, xin.shape[1], H)):
         # round 6: Linear -> PReLU -> Linear of the node encoder AND layer 0's node products in one column-split launch
         z0, x0, pq0 = _empty(dev_of(P), N, H), _empty(dev_of(P), N, H), _empty(dev_of(P), N, 4 * H)
@@ -1303,7 +1234,7 @@ def _gnn_trunk_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta, node_key: str):
         if m.edge_perm is not None:
             vec = vec[m.edge_perm]
         ek = "GN_encoder.edge_encoder"
-        if _EDGE_ENC_ONE_LAUNCH and ops.edge_enc_supported(H):
+        if ops.edge_enc_supported(H):
             # round 6: features, both Linear layers and the PReLU between them in ONE launch (csrc/heads.hip: edge_enc_fwd_kernel)
             ea, z0, e0 = ops.edge_enc_fwd(vec, P[ek + ".0.weight"], P[ek + ".0.bias"], P[ek + ".1.weight"], P[ek + ".2.weight"], P[ek + ".2.bias"], 4.0)
             ce = (SegList([seg(ea)], [ea]), z0, E, H)
@@ -1332,7 +1263,7 @@ def _gnn_trunk_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, dxL: 
                    sink: GradSink, dx_pre=None):
     cn, ce, cu, cg, node_key = ctx
     dx0, de0 = gnn_bwd(P, G, m, cg, dxL, sink, cfg.L, cfg.mean, cfg.H, dx_pre=dx_pre)
-    if _ENC_BWD_PAIR and de0 is not None and cn[3] == ce[3]:
+    if de0 is not None and cn[3] == ce[3]:
         mlp_prelu_bwd_pair(P, G, (node_key, cn, dx0), ("GN_encoder.edge_encoder", ce, de0), sink, tail=True)
         if cu is not None and du_seg is not None:
             mlp_prelu_bwd(P, G, "GN_encoder.global_encoder", cu, None, sink, dy_seg=du_seg, tail=True)
@@ -1438,7 +1369,7 @@ def dostransformer_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta, drop=None, per
     # plain rows (DosxGemm.norm_out) - no dosx_rownorm launch between the heads and the encoder
     kvs = _empty(dev, S * 2 * B, H)
     rstd_s = _empty(dev, S * 2 * B)
-    nk = dict(norm_out=kvs, norm_rstd=rstd_s) if _FUSED_HEAD_NORM else {}
+    nk = dict(norm_out=kvs, norm_rstd=rstd_s)
     if fh:
         hg = dict(segs=[seg(E1)], w=P["fc.weight"][:, :H], res=box["qg"], res_map=modB, res_pre=True)
         hs = dict(segs=[seg(E1)], w=P["fc_prompt.weight"][:, :H], res=box["qs"], res_map=modB, res_pre=True)
@@ -1448,8 +1379,6 @@ def dostransformer_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta, drop=None, per
                        out_map=rowmap(d=B, m=2 * B, c=1, off=0), **hg, **nk),
                   dict(M=S * B, N=H, out=dosin, bias=P["fc_prompt.bias"], act=ACT_LEAKY,
                        act_slope=0.01, out_map=rowmap(d=B, m=2 * B, c=1, off=B), **hs, **nk))
-    if not _FUSED_HEAD_NORM:
-        ops.rownorm(dosin, kvs, rstd_s, S * 2 * B, H)
     hs, c2 = encoder_fwd(P, "transformer_self", dosin, S, 2 * B, 2 * B, 1, kvs, S, 2 * B, H, T, drop=dr(64))
     xhat_f = _empty(dev, S * 2 * B, H)
     rstd_f = _empty(dev, S * 2 * B)
@@ -1503,7 +1432,11 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
         sink.flush_on_side()                  # (weight-gradient stream: this encoder's jobs run under the next one's backward)
     dkvs = _empty(dev, rows2, H)              # self-attention: every row is a key row, the first layer overwrites
     ddosin = encoder_bwd(P, G, "transformer_self", c2, dhs, dkvs, sink, dkv_fresh=True, kv_needed_next=True)
-    late_flush = _LATE_SELF_FLUSH in ("1", "2") or (_LATE_SELF_FLUSH == "auto" and len(a_g.keep) <= 2)
+    # the self encoder's weight-gradient group starts BEHIND the small head kernels (rownorm_bwd_act, the two dE1 dgrads) instead of in
+    # front of them where the heads' weight gradients are not factored (their B-row jobs read a row sum that is made later, on the side
+    # stream): 1.1224-1.1284 vs 1.1298-1.1331 ms per cfg2 step, three interleaved pairs (round 5); with factored heads (Electron-DOS)
+    # behind them lost, cfg3 6.977 -> 6.999 ms (profiles/r06_ab_run10.log)
+    late_flush = len(a_g.keep) <= 2
     if sink.wside is not None and not late_flush:
         sink.flush_on_side()
     sink.join()          # dkvs is produced on the side stream
@@ -1511,10 +1444,9 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
     Wfc, Wfp = P["fc.weight"], P["fc_prompt.weight"]
     # round 6: ... and the two heads' input-gradient products behind it in the SAME launch (csrc/heads.hip): three launch-bound
     # kernels between two encoders' backward as one
-    # (measured, tools/exp/r6_run5.sh, three interleaved rounds: cfg2 1.0672 -> 1.0576 ms; Electron-DOS hidden 256 6.971 -> 7.009 ms -
+    # (measured, profiles/r06_ab_run5.log, three interleaved rounds: cfg2 1.0672 -> 1.0576 ms; Electron-DOS hidden 256 6.971 -> 7.009 ms -
     #  at 12864 rows x 512 k the 64-row-tile GEMMs re-use the weights better than 3216 16-row workgroups: hidden <= 128 only)
-    heads_one = (_HEADS_BWD_ONE_LAUNCH and H <= _HEADS_BWD_MAX_H and ops.heads_bwd_supported(H) and ddosin.is_contiguous()
-                 and dkvs.is_contiguous())
+    heads_one = H <= 128 and ops.heads_bwd_supported(H) and ddosin.is_contiguous() and dkvs.is_contiguous()
     dE1 = _empty(dev, S * B, H)
     if heads_one:
         ops.heads_bwd(S, B, H, dkvs, kvs, rstd_s, ddosin, dosin, 0.01, dpre, Wfc, Wfp, dE1)
@@ -1522,9 +1454,6 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
         ops.rownorm_bwd_act(dkvs, kvs, rstd_s, ddosin, dosin, 0.01, dpre, rows2, H)
     map0, map1 = rowmap(d=B, m=2 * B, c=1, off=0), rowmap(d=B, m=2 * B, c=1, off=B)
     R = _empty(dev, 2 * B, H)            # sum over the energy axis of dpre (filled on the side stream below)
-    # (forward factored; R is filled later, on the side stream: deferred jobs only - and not with the late-flush experiment,
-    #  whose flush_on_side() below would launch the B-row jobs before the reduce_rows that writes R is even queued)
-    r_jobs = None
     if len(a_g.keep) > 2 and "fc.weight" in G and "fc_prompt.weight" in G:
         # the same factoring for the weight gradients: the column blocks that multiply the per-crystal inputs are
         # (sum_s dpre[s, b]) (x) [graph_b (| prompt_b)] - B-row jobs on R - and only the E1 block keeps its S * B rows
@@ -1533,27 +1462,20 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
         _wgrad_linear(sink, G, "fc.weight", "fc.bias", S * B, H, seg(dpre, rmap=map0), [seg(E1_)], keep=(dpre, E1_), dst=Gfc[:, :H])
         _wgrad_linear(sink, G, "fc_prompt.weight", "fc_prompt.bias", S * B, H, seg(dpre, rmap=map1), [seg(E1_)], keep=(dpre,),
                       dst=Gfp[:, :H])
-
-        def r_jobs():
-            _wgrad_linear(sink, G, "fc.weight", None, B, H, seg(R[:B]), [seg(graph_)], keep=(R, graph_), dst=Gfc[:, H:])
-            _wgrad_linear(sink, G, "fc_prompt.weight", None, B, H, seg(R[B:]), [seg(graph_), seg(prow)], keep=(R, prow), dst=Gfp[:, H:])
-        if not late_flush:
-            r_jobs()
-            r_jobs = None
+        # (R is filled later, on the side stream: deferred jobs - this form never runs with the late flush below, which would launch
+        #  them before the reduce_rows that writes R is even queued)
+        _wgrad_linear(sink, G, "fc.weight", None, B, H, seg(R[:B]), [seg(graph_)], keep=(R, graph_), dst=Gfc[:, H:])
+        _wgrad_linear(sink, G, "fc_prompt.weight", None, B, H, seg(R[B:]), [seg(graph_), seg(prow)], keep=(R, prow), dst=Gfp[:, H:])
     else:
         _wgrad_linear(sink, G, "fc.weight", "fc.bias", S * B, H, seg(dpre, rmap=map0), a_g.segs, keep=(dpre,))
         _wgrad_linear(sink, G, "fc_prompt.weight", "fc_prompt.bias", S * B, H, seg(dpre, rmap=map1), a_s.segs, keep=(dpre,))
     if not heads_one:
         ops.gemm(S * B, H, [seg(dpre, rmap=map0)], Wfc[:, :H], dE1, w_layout=1)
         ops.gemm(S * B, H, [seg(dpre, rmap=map1)], Wfp[:, :H], dE1, w_layout=1, res=dE1)
-    if sink.wside is not None and late_flush and _LATE_SELF_FLUSH != "2":
-        # experiment: the self encoder's weight gradients (+ the two heads') start behind the small head kernels above
-        # instead of in front of them (where the group's long-lived workgroups make these 8-15 us kernels wait)
+    if sink.wside is not None and late_flush:
+        # the self encoder's weight gradients (+ the two heads') start behind the small head kernels above instead of in front of
+        # them (where the group's long-lived workgroups make these 8-15 us kernels wait)
         sink.flush_on_side()
-    if r_jobs is not None:
-        # (late flush: the B-row jobs read R, which the side stream fills below - they are described BEHIND that flush and go with
-        #  the next one, which every mode places behind the join with the side stream)
-        r_jobs()
     # graph / prompt inputs are constant over the energy axis: reduce over s first, then a [2B,H] GEMM.  Their
     # consumers (decoder backward, prompt-embedding gradient) come after the first encoder's backward: side stream.
     dgraph = _empty(dev, B, H)
@@ -1573,8 +1495,6 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
     sink.on_side(_const_inputs_bwd, (dpre, R, dgraph, dprow))
     # first encoder (queries = energy embeddings broadcast over the batch)
     dX1 = encoder_bwd(P, G, "transformer", c1, dE1, dkv, sink, kv_needed_next=True)
-    if sink.wside is not None and _LATE_SELF_FLUSH == "2":
-        sink.flush_on_side()             # (experiment: the self encoder's group together with the first encoder's, under the GNN backward)
     # Every gradient of the transformer stacks, the heads and the embeddings is complete (or queued on the side
     # stream) here; what follows only touches the GNN trunk's parameters.  mid_hook: data-parallel training reduces
     # and all-reduces that early bucket now, underneath the GNN backward (train.Trainer).
@@ -1583,8 +1503,8 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
     sink.on_side(lambda: ops.reduce_rows(dX1.data_ptr(), H, G["embeddings.weight"].data_ptr(), H, S, B, B, 1, H), (dX1,))
     late_hook = None
     if mid_hook is not None:          # (after the join: the early bucket's reduction must not sit between the main
-        if _MID_HOOK_LATE and H <= _MID_HOOK_LATE_MAX_H and dx_ext is None and cfg.L >= 1:
-            late_hook = mid_hook      # (experiment: behind the last layer's NodeModel backward launch, gnn_bwd)
+        if H <= _MID_HOOK_LATE_MAX_H and dx_ext is None and cfg.L >= 1:
+            late_hook = mid_hook      # (behind the last layer's NodeModel backward launch, gnn_bwd)
         else:
             mid_hook(sink)            #  stream and the dk/dv kernels it is waiting for)
     # node embeddings: dense keys + pooled decoder input (+ external grad on the returned x)

@@ -520,11 +520,11 @@ def ffn_bwd(M: int, H: int, dy: torch.Tensor, h: torch.Tensor, x: torch.Tensor, 
           w=lambda: (f"ffn_bwd[H{H}{',att' if nk_att else ''}]", "ffn_bwd_kernel", "mfma", 16.0 * M * H * H + 10.0 * M * nk_att * H))
 
 
-MLP_LN_MAX_ROWS = int(__import__("os").environ.get("DOSX_MLP_LN_MAX_ROWS", "4096"))
-MLP_LN_MAX_KN = int(__import__("os").environ.get("DOSX_MLP_LN_MAX_KN", str(256 * 256)))
+MLP_LN_MAX_ROWS = 4096
+MLP_LN_MAX_KN = 256 * 256           # (tests lower / raise it to force the other form at a given shape)
 # the FORWARD kernel alone also at hidden 256 (round 5: weight chunks four deep - 37.4 us against 30 + 13.5 + a launch gap for the
 # two GEMMs at 1554 rows; the backward stays on its two GEMMs there: 39.7 against 35.0)
-MLP_LN_MAX_KN_FWD = int(__import__("os").environ.get("DOSX_MLP_LN_MAX_KN_FWD", str(512 * 512)))
+MLP_LN_MAX_KN_FWD = 512 * 512
 
 
 def mlp_ln_supported(M: int, K: int, NH: int, NO: int) -> bool:
@@ -541,20 +541,13 @@ def mlp_ln_fwd_supported(M: int, K: int, NH: int, NO: int) -> bool:
 
 
 # Column-split form of the one-launch NodeModel kernels (round 6, include/dosx.h: DosxMlpLn.cs_buf): hidden / 16 workgroups per
-# 16-row tile instead of one, while that grid stays a single round of small workgroups
-MLP_LN_CS = __import__("os").environ.get("DOSX_MLP_LN_CS", "1") == "1"
-MLP_LN_CS_MAX_WGS = int(__import__("os").environ.get("DOSX_MLP_LN_CS_MAX_WGS", "512"))
-# ... the BACKWARD launch: "pre" (default) = only where it absorbs the launch in front of it (DosxMlpLnBwd.pre), "1" = always, "0" =
-# never.  Inside the step the backward N-row launches share the GPU with a weight-gradient group: 232 small workgroups that wait
-# for each other then cost MORE than 29 large ones (1.0940 vs 1.0855 ms per cfg2 step, three interleaved rounds) - unlike in the
-# forward pass, where the chip is otherwise idle (1.1018 -> 1.0940 with the forward launches alone) - but absorbing the dense-key
-# backward launch in front of the last layer's NodeModel backward pays well beyond that (1.0726; tools/exp/r6_run3.sh)
-MLP_LN_CS_BWD = __import__("os").environ.get("DOSX_MLP_LN_CS_BWD", "pre")
+# 16-row tile instead of one, while that grid stays a single round of small workgroups (profiles/r06_ab_cs.log)
+MLP_LN_CS_MAX_WGS = 512
 
 
 def mlp_ln_cs(M: int, K: int, NH: int, NO: int) -> bool:
     """Whether mlp_ln_fwd / mlp_ln_bwd run the column-split form for this block."""
-    return bool(MLP_LN_CS and M > 0 and _lib.load().dosx_mlp_ln_cs_supported(int(K), int(NH), int(NO))
+    return bool(M > 0 and _lib.load().dosx_mlp_ln_cs_supported(int(K), int(NH), int(NO))
                 and ((int(M) + 15) // 16) * (int(NO) // 16) <= MLP_LN_CS_MAX_WGS)
 
 
@@ -602,10 +595,13 @@ def mlp_ln_bwd_partial_rows(M: int) -> int:
 
 
 def mlp_ln_bwd_cs(M: int, K: int, NH: int, NO: int, dcat: torch.Tensor, with_pre: bool = False) -> bool:
-    """Whether mlp_ln_bwd runs the column-split form for this block and this dcat layout (``with_pre``: it is asked to absorb the
-    launch in front of it)."""
-    on = MLP_LN_CS_BWD == "1" or (MLP_LN_CS_BWD == "pre" and with_pre)
-    return on and mlp_ln_cs(M, K, NH, NO) and int(dcat.stride(0)) % 2 == 0 and dcat.data_ptr() % 8 == 0
+    """Whether mlp_ln_bwd runs the column-split form for this block and this dcat layout: only where it is asked to absorb the
+    launch in front of it (``with_pre``, DosxMlpLnBwd.pre).  Inside the step the backward N-row launches share the GPU with a
+    weight-gradient group: 232 small workgroups that wait for each other then cost MORE than 29 large ones (1.0940 vs 1.0855 ms per
+    cfg2 step, three interleaved rounds) - unlike in the forward pass, where the chip is otherwise idle (1.1018 -> 1.0940 with the
+    forward launches alone) - but absorbing the dense-key backward launch in front of the last layer's NodeModel backward pays well
+    beyond that (1.0726; profiles/r06_ab_run3.log)."""
+    return with_pre and mlp_ln_cs(M, K, NH, NO) and int(dcat.stride(0)) % 2 == 0 and dcat.data_ptr() % 8 == 0
 
 
 def mlp_ln_bwd(M: int, dy: torch.Tensor, xhat: torch.Tensor, rstd: torch.Tensor, w1, w2, gamma, beta, alpha, dz: torch.Tensor,
@@ -862,9 +858,6 @@ def wgrad_grouped(descs: Sequence[Wgrad]) -> None:
     grad_flush(descs, ())
 
 
-_LPT = __import__("os").environ.get("DOSX_WGRAD_LPT", "1") == "1"
-
-
 def concurrent(device, side_fn, main_fn) -> None:
     """``side_fn`` (kernel launches) on the side stream NEXT TO ``main_fn`` on the current one: both ordered after
     everything issued so far on the current stream, which waits for the side work at the end.  Recorded like every stream
@@ -905,12 +898,11 @@ class GradSink:
     # at BASELINE sizes every kernel is one partial wave of workgroups, two streams simply fill more CUs.
     # Off for eagerly issued steps (the host cannot feed two streams from Python: no gain), switched on by
     # train.Trainer while it records a replayed step (1.80 vs 1.88 ms serialised).
-    use_side_stream = __import__("os").environ.get("DOSX_SIDE_STREAM", "0") == "1"
-    # ... and the grouped weight-gradient launches + slab reductions on a THIRD stream of their own, flushed after every
+    use_side_stream = False
+    # ... with the grouped weight-gradient launches + slab reductions on a THIRD stream of their own (`wside`), flushed after every
     # encoder stack / GNN layer pair: queued on the side stream they sat in front of the key-gradient reductions the main
     # stream joins on, on their own stream they fill the CUs the latency-bound dgrad chain leaves idle (cfg2: 1.443 ->
     # 1.412 ms; round 1 had measured a third stream for the dk/dv CHAIN as a loss: that chain is on the critical path)
-    use_wgrad_stream = __import__("os").environ.get("DOSX_WGRAD_STREAM", "1") == "1"
     _side_streams: dict = {}
 
     def __init__(self, device):
@@ -925,11 +917,10 @@ class GradSink:
             if key not in GradSink._side_streams:
                 GradSink._side_streams[key] = torch.cuda.Stream(device=device)
             self.side = GradSink._side_streams[key]
-            if GradSink.use_wgrad_stream:          # a third stream for the grouped weight gradients + slab reductions
-                k2 = key + ("w",)
-                if k2 not in GradSink._side_streams:
-                    GradSink._side_streams[k2] = torch.cuda.Stream(device=device)
-                self.wside = GradSink._side_streams[k2]
+            k2 = key + ("w",)                      # a third stream for the grouped weight gradients + slab reductions
+            if k2 not in GradSink._side_streams:
+                GradSink._side_streams[k2] = torch.cuda.Stream(device=device)
+            self.wside = GradSink._side_streams[k2]
         self._forked = False
         self._wforked = False
 
@@ -940,8 +931,8 @@ class GradSink:
 
     @staticmethod
     def grad_stream(device):
-        """The stream the gradient reductions of recorded programs run on (weight-gradient stream, else the side stream)."""
-        return GradSink._side_streams.get((str(device), False, "w")) or GradSink._side_streams.get((str(device), False))
+        """The stream the gradient reductions of recorded programs run on: the weight-gradient stream (None before the first recording)."""
+        return GradSink._side_streams.get((str(device), False, "w"))
 
     # Weight-gradient jobs are collected and issued as ONE grouped launch at the next flush instead of one kernel each on
     # the side stream (interleaved they cost the dgrad chain ~0.45 ms per step of interference: round 1).
@@ -955,34 +946,13 @@ class GradSink:
     def _take_wjobs(self):
         jobs = getattr(self, "_wjobs", [])
         self._wjobs = []
-        if jobs and _LPT:      # biggest jobs first: the tail of the grid is then made of the small ones
-            jobs = sorted(jobs, key=lambda g: -(g.M * g.N * g.K))
-        return jobs
-
-    def run_grouped(self) -> None:
-        self._run_pre()
-        jobs = self._take_wjobs()
-        if jobs:
-            wgrad_grouped(jobs)
-
-    def defer_pre(self, fn, keep=()) -> None:
-        """``fn`` (kernel launches) runs on the stream of the next flush, right in front of its grouped launch: producers of
-        operands that only the deferred weight-gradient jobs read (the per-node sums of functional.mlp_ln_bwd)."""
-        self._keep.extend(keep)
-        if not hasattr(self, "_pre"):
-            self._pre = []
-        self._pre.append(fn)
-
-    def _run_pre(self) -> None:
-        for fn in getattr(self, "_pre", []):
-            fn()
-        self._pre = []
+        # biggest jobs first: the tail of the grid is then made of the small ones
+        return sorted(jobs, key=lambda g: -(g.M * g.N * g.K))
 
     def _flush_launch(self, rjobs) -> None:
         """ONE launch for a flush point: the pending weight-gradient jobs (finished mode: they write the gradients
         themselves) + the first wave of row-partial reductions; reductions that share a destination with an earlier one
         follow in launches of their own (they accumulate)."""
-        self._run_pre()
         wjobs = self._take_wjobs()
         # finished-mode jobs that target the same gradient: the later ones accumulate, each in a later launch
         waves_w: List[list] = []
@@ -1039,30 +1009,25 @@ class GradSink:
                           int(count), 1 if accumulate else 0))
 
     def flush_on_side(self):
-        """Reduce the jobs collected so far WITHOUT joining: the reduction is queued on the side stream behind the
-        weight-gradient kernels it depends on (and behind everything the main stream has issued up to here), so the
-        main stream runs on.  Used for the early gradient bucket of data-parallel training."""
-        if self.wside is not None:
-            # own stream: ordered after everything issued so far on the main AND the side stream (the slabs of the
-            # attention key gradients are produced there), never in front of the kernels the main stream joins on
-            jobs, self.jobs = self.jobs, []
-            for src in ([self.main, self.side] if self._forked else [self.main]):
-                ev = torch.cuda.Event()
-                ev.record(src)
-                self.wside.wait_event(ev)
-                if RECORDER.active:
-                    RECORDER.prog.append((ev.record, (src,)))
-                    RECORDER.prog.append((self.wside.wait_event, (ev,)))
-            with torch.cuda.stream(self.wside):
-                self._flush_launch(jobs)
-            self._wforked = True
-            return
+        """Launch the weight-gradient jobs described so far and reduce the partials collected so far WITHOUT joining: on the
+        weight-gradient stream, behind everything the main and the side stream have issued up to here, so the main stream
+        runs on.  Also used for the early gradient bucket of data-parallel training."""
         jobs, self.jobs = self.jobs, []
-        if self.side is None:
+        if self.wside is None:               # (one stream: eagerly issued steps)
             self._flush_launch(jobs)
-        else:
-            self.run_grouped()
-            self.on_side(lambda: self._reduce(jobs))
+            return
+        # own stream: ordered after everything issued so far on the main AND the side stream (the slabs of the
+        # attention key gradients are produced there), never in front of the kernels the main stream joins on
+        for src in ([self.main, self.side] if self._forked else [self.main]):
+            ev = torch.cuda.Event()
+            ev.record(src)
+            self.wside.wait_event(ev)
+            if RECORDER.active:
+                RECORDER.prog.append((ev.record, (src,)))
+                RECORDER.prog.append((self.wside.wait_event, (ev,)))
+        with torch.cuda.stream(self.wside):
+            self._flush_launch(jobs)
+        self._wforked = True
 
     def flush(self):
         self.join()              # (first: deferred weight-gradient jobs may read tensors produced on the side stream)
@@ -1269,7 +1234,7 @@ def rownorm_bwd_act(dxhat, xhat, rstd, dx_in, y, slope, out, M, H):
 
 def enc_cs_supported(M: int, Fa: int, H: int) -> bool:
     """Whether the node encoder + first node products run as ONE column-split launch (include/dosx.h: DosxEncCs)."""
-    return bool(MLP_LN_CS and M > 0 and _lib.load().dosx_enc_cs_supported(int(Fa), int(H))
+    return bool(M > 0 and _lib.load().dosx_enc_cs_supported(int(Fa), int(H))
                 and ((int(M) + 15) // 16) * (int(H) // 16) <= MLP_LN_CS_MAX_WGS)
 
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# what the data-parallel step costs one rank (1-rank RCCL group) with / without the mid gradient bucket and the late early-bucket hook
+# what the data-parallel step costs one rank (1-rank RCCL group) with / without the mid gradient bucket
 set -u
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/../.." && pwd)}
 O="$R/gpurun_out/r6_dp1"
@@ -15,6 +15,4 @@ for i in 1 2 3; do
   EXTRA="" run "single" DOSX_X=0
   EXTRA="--force-dist" run "dp1 mid+late" DOSX_X=0
   EXTRA="--force-dist" run "dp1 nomid+late" DOSX_DP_MID_BUCKET=0
-  EXTRA="--force-dist" run "dp1 mid, hook early" DOSX_MID_HOOK_LATE=0
-  EXTRA="--force-dist" run "dp1 nomid, hook early" DOSX_DP_MID_BUCKET=0 DOSX_MID_HOOK_LATE=0
 done

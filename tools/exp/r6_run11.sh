@@ -14,7 +14,6 @@ run() {
 for i in 1 2 3; do
   run "exact fp32            " edos_h256_b64 40 DOSX_X=0
   run "split-bf16 ffn        " edos_h256_b64 40 DOSX_FFN_BF16X3=1
-  run "split-bf16 ffn, notail" edos_h256_b64 40 DOSX_FFN_BF16X3=1 DOSX_FFN_TAIL=0
   run "exact fp32            " edos_h256_t4_b32 40 DOSX_X=0
   run "split-bf16 ffn        " edos_h256_t4_b32 40 DOSX_FFN_BF16X3=1
 done
