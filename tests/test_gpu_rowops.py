@@ -12,44 +12,10 @@ import itertools
 import pytest
 import torch
 
-from tests.gpu_util import DEV, bound_ratio, ops, rnd
+from tests.gpu_util import (DEV, H_GRAPH, H_ROW4, LN_EPS, ROWS, SENT, _in_slice, _norm64, _outside_untouched, _rows, bound_ratio, ops,
+                            rnd)
 
 pytestmark = pytest.mark.gpu
-
-H_GRAPH = [4, 16, 64, 128, 256, 260, 384, 512, 1024]   # CHECK_H (graph_ops.hip): powers of two below 256, multiples of 4 from 256
-H_ROW4 = H_GRAPH + [12, 100]                           # CHECK_H4 (rowops.hip) and gather_add_rownorm (W <= 1024): any multiple of 4
-ROWS = [1, 3, 4, 5, 2051]
-SENT = -7.25                                           # sentinel around strided operands / outputs
-LN_EPS = 1e-5
-
-
-def _rows(M, H, seed, special=True):
-    """[M, H] fp32 rows whose magnitudes span 1e-3 .. 1e3 (a wrong small row must show next to large ones); with `special`,
-    row 0 is constant (variance 0) and row 1 sits on a common offset of 1e3 x its spread (pins the two-pass variance)."""
-    x = rnd(M, H, seed=seed).double() * torch.logspace(-3, 3, M, dtype=torch.float64, device=DEV)[:, None]
-    if special and M >= 3:
-        x[0] = 0.7
-        x[1] = 1e3 + rnd(H, seed=seed + 1).double()
-    return x.float()
-
-
-def _in_slice(M, H, pad=8):
-    """A sentinel-filled [M, H + pad] buffer and its column slice [:, 4:4+H] (16-byte aligned, row stride H + pad)."""
-    buf = torch.full((M, H + pad), SENT, device=DEV)
-    return buf, buf[:, 4:4 + H]
-
-
-def _outside_untouched(buf, H):
-    keep = torch.ones_like(buf, dtype=torch.bool)
-    keep[:, 4:4 + H] = False
-    return bool((buf[keep] == SENT).all())
-
-
-def _norm64(x64):
-    """float64 two-pass row normalisation: (xhat, mean, rstd)."""
-    mean = x64.mean(1, keepdim=True)
-    rstd = 1.0 / torch.sqrt(((x64 - mean) ** 2).mean(1, keepdim=True) + LN_EPS)
-    return (x64 - mean) * rstd, mean, rstd
 
 
 # row normalisations: the mean is off by <= 13 eps mean|x| (summation depth) + 1 (division); the two-pass variance by <= 13 + 3

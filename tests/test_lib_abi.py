@@ -72,6 +72,57 @@ def test_argument_validation_needs_no_gpu():
     assert lib.dosx_ffn_bwd_partial_rows(3264) == 204 and lib.dosx_ffn_bwd_partial_rows(6528) == 204
 
 
+def test_tail_entry_points_validate_before_any_launch():
+    """The loss / AdamW / utility entry points refuse bad sizes, null pointers and misaligned buffers through DOSX_CHECK_ARG
+    (rc -22 and a message naming the entry point), which stands in front of every launch; the pointers here are never
+    dereferenced."""
+    from dostransformer_amd import _lib
+    lib = _lib.load()
+    A, B, D, E = 0x10000, 0x20000, 0x30000, 0x40000          # 16-byte aligned fake device addresses
+
+    def refused(rc, msg):
+        assert rc == -22, rc
+        assert msg in lib.dosx_last_error(), lib.dosx_last_error()
+
+    adam = lambda p, g, m, v, n, step: lib.dosx_adamw(p, g, m, v, n, 1e-3, 0.9, 0.999, 1e-8, 1e-2, step, 1.0, None)
+    assert adam(A, B, D, E, 0, 1) == 0 and adam(None, None, None, None, 0, 0) == 0     # n = 0: nothing to do
+    refused(adam(A, B, D, E, 8, 0), b"dosx_adamw: bad args")
+    refused(adam(A, B, D, E, 8, -3), b"dosx_adamw: bad args")
+    refused(adam(None, B, D, E, 8, 1), b"dosx_adamw: bad args")
+    for bad in range(4):
+        ptrs = [A, B, D, E]
+        ptrs[bad] += 4
+        refused(adam(*ptrs, 8, 1), b"dosx_adamw: buffers must be 16-byte aligned")
+    refused(lib.dosx_sse2(A, B, D, E, 0, None), b"dosx_sse2: bad args")
+    refused(lib.dosx_sse2(A, B, D, E, -5, None), b"dosx_sse2: bad args")
+    refused(lib.dosx_sse2(A, B, D, None, 51, None), b"dosx_sse2: bad args")
+    refused(lib.dosx_sse2(None, B, D, E, 51, None), b"dosx_sse2: bad args")
+    refused(lib.dosx_loss_phonon(A, B, D, None, 0.7, E, E, None, 0, None), b"dosx_loss_phonon: bad args")
+    refused(lib.dosx_loss_phonon(A, B, None, None, 0.7, E, E, None, 51, None), b"dosx_loss_phonon: bad args")
+    refused(lib.dosx_loss_phonon(A, B, D, None, 0.7, None, E, None, 51, None), b"dosx_loss_phonon: bad args")
+    refused(lib.dosx_loss_phonon_bwd(A, B, D, E, 0.7, 51.0, E, E, None, 0, None), b"dosx_loss_phonon_bwd: bad args")
+    refused(lib.dosx_loss_phonon_bwd(A, B, D, E, 0.7, 0.0, E, E, None, 51, None), b"dosx_loss_phonon_bwd: bad args")
+    refused(lib.dosx_loss_phonon_bwd(A, B, D, None, 0.7, 51.0, E, E, None, 51, None), b"dosx_loss_phonon_bwd: bad args")
+    refused(lib.dosx_loss_edos(A, B, D, 0.5, 0, 201, 4, E, E, E, None), b"dosx_loss_edos: bad args")
+    refused(lib.dosx_loss_edos(A, B, D, 0.5, 4, 0, 4, E, E, E, None), b"dosx_loss_edos: bad args")
+    refused(lib.dosx_loss_edos(A, B, D, 0.5, 4, 201, 0, E, E, E, None), b"dosx_loss_edos: bad args")
+    refused(lib.dosx_loss_edos(A, B, D, 0.5, 4, 201, -1, E, E, E, None), b"dosx_loss_edos: bad args")
+    refused(lib.dosx_loss_edos(A, B, D, 0.5, 4, 201, 4, E, E, None, None), b"dosx_loss_edos: bad args")
+    refused(lib.dosx_sum(A, 0, B, None), b"dosx_sum: bad args")
+    refused(lib.dosx_sum(None, 7, B, None), b"dosx_sum: bad args")
+    refused(lib.dosx_sum(A, 7, None, None), b"dosx_sum: bad args")
+    assert lib.dosx_act_bwd(A, B, 0.01, D, 0, None) == 0
+    for n in (1, 6, 1023):
+        refused(lib.dosx_act_bwd(A, B, 0.01, D, n, None), b"dosx_act_bwd: bad args (n must be a multiple of 4)")
+    refused(lib.dosx_act_bwd(A, None, 0.01, D, 8, None), b"dosx_act_bwd: bad args")
+    assert lib.dosx_reduce_rows(A, 32, B, 32, 0, 4, 4, 1, 32, 0, None) == 0
+    refused(lib.dosx_reduce_rows(A, 32, B, 32, 5, 4, 4, 1, 30, 0, None), b"dosx_reduce_rows: bad args")       # width
+    refused(lib.dosx_reduce_rows(A, 32, B, 32, 5, 4, 4, 1, 0, 0, None), b"dosx_reduce_rows: bad args")
+    refused(lib.dosx_reduce_rows(A, 34, B, 32, 5, 4, 4, 1, 32, 0, None), b"dosx_reduce_rows: bad args")       # ld_src
+    refused(lib.dosx_reduce_rows(A, 32, B, 33, 5, 4, 4, 1, 32, 0, None), b"dosx_reduce_rows: bad args")       # ld_dst
+    refused(lib.dosx_reduce_rows(None, 32, B, 32, 5, 4, 4, 1, 32, 0, None), b"dosx_reduce_rows: bad args")
+
+
 def test_product_path_fails_loudly_without_gpu():
     import torch
     from dostransformer_amd import synth
