@@ -314,7 +314,7 @@ class Wgrad64(C.Structure):
 class Attn64(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("Sq", "Bq", "Nk", "Bk", "H", "flags")] + \
                [(k, C.c_void_p) for k in ("q", "x", "kvhat", "gamma0", "beta0", "drop_mask", "out", "probs", "dout", "dq", "ds",
-                                          "dkvhat", "part")] + [("accumulate", C.c_int32)]
+                                          "dkvhat", "part")] + [("accumulate", C.c_int32), ("key_ptr", C.c_void_p)]
 
 
 class Call(C.Structure):

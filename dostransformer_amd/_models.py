@@ -33,6 +33,7 @@ class DOSTransformerBase(FusedModel):
     """forward(g) -> (dos_global [B,S], x [N,H], dos_system [B,S])   (`DOSTransformer_phonon.py:66-119`)."""
     _cfg: Fn.ModelCfg
     _program_dtype = torch.float32
+    _per_crystal_keys = False
 
     # ---- which program the module runs ----------------------------------------------------------------------------------
     @property
@@ -50,6 +51,26 @@ class DOSTransformerBase(FusedModel):
         elif dtype != torch.float32:
             raise DosxError(f"{type(self).__name__}.set_program_dtype: torch.float32 or torch.float64, got {dtype}")
         object.__setattr__(self, "_program_dtype", dtype)
+        if dtype != torch.float64:
+            object.__setattr__(self, "_per_crystal_keys", False)        # a switch of the float64 program only
+        return self
+
+    @property
+    def per_crystal_keys(self) -> bool:
+        """True: the float64 program attends over each crystal's own atoms (set_per_crystal_keys)."""
+        return self._per_crystal_keys
+
+    def set_per_crystal_keys(self, flag: bool):
+        """float64 program only.  True: the two encoders that attend over atoms (transformer, transformer_source) see each
+        crystal's own atoms, not the rows that pad it to the batch's largest crystal, so a batch of B crystals gives the B
+        DOS vectors the reference gives at batch_size = 1 (main_phDOS.py:52-55) and its gradient is the sum of those B
+        per-sample gradients - forward and backward, attention dropout included.  False (the default): the reference's
+        batched forward, padding rows as keys.  Returns self."""
+        if flag and self._program_dtype != torch.float64:
+            raise DosxError(f"{type(self).__name__}.set_per_crystal_keys: a switch of the float64 program "
+                            f"(set_program_dtype(torch.float64), DOSTransformer_phonon only); the fp32 program has it for "
+                            f"inference as Predictor(model, per_crystal_keys=True)")
+        object.__setattr__(self, "_per_crystal_keys", bool(flag))
         return self
 
     def _check_f64_program(self) -> None:
@@ -101,9 +122,10 @@ class DOSTransformerBase(FusedModel):
 
     def _program_fwd(self, P, g, m, bump_seed: bool = True, per_crystal_keys: bool = False):
         if P["embeddings.weight"].dtype == torch.float64:
-            if per_crystal_keys:
-                raise DosxError("per_crystal_keys: fp32 program only")
-            dos, xL, ctx = F64.dostransformer_phonon_fwd(P, self._cfg, g, m, drop=self._dropout(dos_device(P), bump_seed))
+            # (the per_crystal_keys argument is predict.Predictor's and reaches the fp32 program only: the float64 program
+            #  follows the module's own switch)
+            dos, xL, ctx = F64.dostransformer_phonon_fwd(P, self._cfg, g, m, drop=self._dropout(dos_device(P), bump_seed),
+                                                         per_crystal_keys=self._per_crystal_keys)
             B = m.num_graphs
             return dos[:B], xL, dos[B:], (ctx, dos)
         dos, xL, ctx = Fn.dostransformer_fwd(P, self._cfg, g, m, drop=self._dropout(dos_device(P), bump_seed),

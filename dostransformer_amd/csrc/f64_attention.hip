@@ -45,12 +45,18 @@ __device__ __forceinline__ double kv_at(const DosxAttn64& d, const double* row, 
   return row[h] * d.gamma0[h] + d.beta0[h];
 }
 
-// C[s][j] (+)= sum_h A[s][h] * kv[j][h] for 16 rows [s0, s0+16) of A (row stride H) and 16 keys [j0, j0+16)
+// live keys of key crystal bk: all Nk without key_ptr, else its own count clamped to [0, Nk] (wave-uniform)
+__device__ __forceinline__ int live_keys(const DosxAttn64& d, int bk) {
+  if (d.key_ptr == nullptr) return d.Nk;
+  return min(max(d.key_ptr[bk + 1] - d.key_ptr[bk], 0), d.Nk);
+}
+
+// C[s][j] (+)= sum_h A[s][h] * kv[j][h] for 16 rows [s0, s0+16) of A (row stride H) and 16 keys [j0, j0+16) below n
 __device__ __forceinline__ f64x4 rows_times_keys(const DosxAttn64& d, const double* A, int nrows, int s0, const double* kv,
-                                                 int j0, int lane) {
+                                                 int n, int j0, int lane) {
   const int r = lane & 15, kl = lane >> 4;
   const double* arow = s0 + r < nrows ? A + (int64_t)(s0 + r) * d.H : nullptr;
-  const double* krow = j0 + r < d.Nk ? kv + (int64_t)(j0 + r) * d.H : nullptr;
+  const double* krow = j0 + r < n ? kv + (int64_t)(j0 + r) * d.H : nullptr;
   f64x4 acc = {0.0, 0.0, 0.0, 0.0};
   for (int h0 = 0; h0 < d.H; h0 += 4) {
     const int h = h0 + kl;
@@ -62,15 +68,15 @@ __device__ __forceinline__ f64x4 rows_times_keys(const DosxAttn64& d, const doub
   return acc;
 }
 
-// out[s][c0 + 0..63] = sum_j W[s][j] * (mask) * kv[j][c] for the 16 query rows of the tile (W rows of stride Nk)
+// out[s][c0 + 0..63] = sum_{j < n} W[s][j] * (mask) * kv[j][c] for the 16 query rows of the tile (W rows of stride Nk)
 __device__ __forceinline__ void weights_times_values(const DosxAttn64& d, const double* W, const float* M, int Sq, int s0,
-                                                     const double* kv, int c0, int lane, f64x4 acc[4]) {
+                                                     const double* kv, int n, int c0, int lane, f64x4 acc[4]) {
   const int r = lane & 15, kl = lane >> 4;
   const int sa = s0 + r;
   for (int t = 0; t < 4; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
-  for (int j0 = 0; j0 < d.Nk; j0 += 4) {
+  for (int j0 = 0; j0 < n; j0 += 4) {
     const int j = j0 + kl;
-    const bool jin = j < d.Nk;
+    const bool jin = j < n;
     double a = 0.0;
     if (sa < Sq && jin) {
       a = W[(int64_t)sa * d.Nk + j];
@@ -87,6 +93,8 @@ __device__ __forceinline__ void weights_times_values(const DosxAttn64& d, const 
 
 // Forward.  Workgroup: query rows [s0, s0+16) of crystal bq; 4 waves.  1) scores * H^-1/2 into probs (waves take key
 // tiles in turn); 2) softmax of each row in place (a wave per row); 3) out = x + (p o mask) . v (waves take 64 columns).
+// With key_ptr only the n live keys of the crystal exist: every loop ends at n, nothing past it is read, probs[s][j >= n]
+// is written as 0.0 (n = 0: out = x).
 __global__ __launch_bounds__(256) void attn64_fwd_kernel(DosxAttn64 d, double scale) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int bq = blockIdx.y, s0 = blockIdx.x * kQ, bk = bq % d.Bk;
@@ -97,12 +105,13 @@ __global__ __launch_bounds__(256) void attn64_fwd_kernel(DosxAttn64 d, double sc
   const float* M = d.drop_mask ? d.drop_mask + q0 * Nk : nullptr;
   const double* Q = d.q + q0 * H;
   const int r = lane & 15, kl = lane >> 4;
+  const int n = live_keys(d, bk);
 
-  for (int j0 = wv * 16; j0 < Nk; j0 += 64) {
-    const f64x4 acc = rows_times_keys(d, Q, Sq, s0, kv, j0, lane);
+  for (int j0 = wv * 16; j0 < n; j0 += 64) {
+    const f64x4 acc = rows_times_keys(d, Q, Sq, s0, kv, n, j0, lane);
     for (int i = 0; i < 4; ++i) {
       const int s = s0 + kl + 4 * i, j = j0 + r;
-      if (s < Sq && j < Nk) P[(int64_t)s * Nk + j] = acc[i] * scale;
+      if (s < Sq && j < n) P[(int64_t)s * Nk + j] = acc[i] * scale;
     }
   }
   __syncthreads();
@@ -111,36 +120,37 @@ __global__ __launch_bounds__(256) void attn64_fwd_kernel(DosxAttn64 d, double sc
     double* row = P + (int64_t)(s0 + rr) * Nk;
     if (d.flags & DOSX_ATTN64_SOFTMAX_F64) {
       double mx = -INFINITY;
-      for (int j = lane; j < Nk; j += 64) mx = fmax(mx, row[j]);
+      for (int j = lane; j < n; j += 64) mx = fmax(mx, row[j]);
       mx = wave_max64(mx);
       double sum = 0.0;
-      for (int j = lane; j < Nk; j += 64) {
+      for (int j = lane; j < n; j += 64) {
         const double e = exp(row[j] - mx);
         row[j] = e;
         sum += e;
       }
       sum = wave_sum64(sum);
-      for (int j = lane; j < Nk; j += 64) row[j] = row[j] / sum;
+      for (int j = lane; j < n; j += 64) row[j] = row[j] / sum;
     } else {
       // F.softmax(w.float(), -1).type_as(w) (multihead_attention.py:69): fp32 scores, fp32 softmax, promoted
       float mx = -INFINITY;
-      for (int j = lane; j < Nk; j += 64) mx = fmaxf(mx, (float)row[j]);
+      for (int j = lane; j < n; j += 64) mx = fmaxf(mx, (float)row[j]);
       mx = wave_max32(mx);
       float sum = 0.0f;
-      for (int j = lane; j < Nk; j += 64) {
+      for (int j = lane; j < n; j += 64) {
         const float e = expf((float)row[j] - mx);
         row[j] = (double)e;
         sum += e;
       }
       sum = wave_sum32(sum);
-      for (int j = lane; j < Nk; j += 64) row[j] = (double)((float)row[j] / sum);
+      for (int j = lane; j < n; j += 64) row[j] = (double)((float)row[j] / sum);
     }
+    for (int j = n + lane; j < Nk; j += 64) row[j] = 0.0;
   }
   __syncthreads();
 
   for (int c0 = wv * 64; c0 < H; c0 += 256) {
     f64x4 acc[4];
-    weights_times_values(d, P, M, Sq, s0, kv, c0, lane, acc);
+    weights_times_values(d, P, M, Sq, s0, kv, n, c0, lane, acc);
     for (int t = 0; t < 4; ++t) {
       const int h = c0 + 16 * t + r;
       if (h >= H) continue;
@@ -153,7 +163,7 @@ __global__ __launch_bounds__(256) void attn64_fwd_kernel(DosxAttn64 d, double sc
 }
 
 // Backward, query side.  Same tiling as the forward: 1) dP = dout . v^T, times the mask, into ds; 2) the softmax backward
-// of each row in place, times H^-1/2; 3) dq = ds . k.
+// of each row in place, times H^-1/2; 3) dq = ds . k.  With key_ptr the same bounds as the forward; ds[s][j >= n] = 0.0.
 __global__ __launch_bounds__(256) void attn64_dq_kernel(DosxAttn64 d, double scale) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int bq = blockIdx.y, s0 = blockIdx.x * kQ, bk = bq % d.Bk;
@@ -165,12 +175,13 @@ __global__ __launch_bounds__(256) void attn64_dq_kernel(DosxAttn64 d, double sca
   const float* M = d.drop_mask ? d.drop_mask + q0 * Nk : nullptr;
   const double* DO = d.dout + q0 * H;
   const int r = lane & 15, kl = lane >> 4;
+  const int n = live_keys(d, bk);
 
-  for (int j0 = wv * 16; j0 < Nk; j0 += 64) {
-    const f64x4 acc = rows_times_keys(d, DO, Sq, s0, kv, j0, lane);
+  for (int j0 = wv * 16; j0 < n; j0 += 64) {
+    const f64x4 acc = rows_times_keys(d, DO, Sq, s0, kv, n, j0, lane);
     for (int i = 0; i < 4; ++i) {
       const int s = s0 + kl + 4 * i, j = j0 + r;
-      if (s < Sq && j < Nk) {
+      if (s < Sq && j < n) {
         const int64_t o = (int64_t)s * Nk + j;
         DS[o] = M != nullptr ? acc[i] * (double)M[o] : acc[i];
       }
@@ -183,26 +194,27 @@ __global__ __launch_bounds__(256) void attn64_dq_kernel(DosxAttn64 d, double sca
     double* row = DS + (int64_t)(s0 + rr) * Nk;
     if (d.flags & DOSX_ATTN64_SOFTMAX_F64) {
       double dot = 0.0;
-      for (int j = lane; j < Nk; j += 64) dot += prow[j] * row[j];
+      for (int j = lane; j < n; j += 64) dot += prow[j] * row[j];
       dot = wave_sum64(dot);
-      for (int j = lane; j < Nk; j += 64) row[j] = prow[j] * (row[j] - dot) * scale;
+      for (int j = lane; j < n; j += 64) row[j] = prow[j] * (row[j] - dot) * scale;
     } else {
       // autograd of the forward's casts: the fp64 gradient rounded to fp32, softmax backward p (g - sum p g) in fp32,
       // promoted, then the fp64 scaling's backward
       float dot = 0.0f;
-      for (int j = lane; j < Nk; j += 64) dot += (float)prow[j] * (float)row[j];
+      for (int j = lane; j < n; j += 64) dot += (float)prow[j] * (float)row[j];
       dot = wave_sum32(dot);
-      for (int j = lane; j < Nk; j += 64) {
+      for (int j = lane; j < n; j += 64) {
         const float g = (float)row[j];
         row[j] = (double)((g - dot) * (float)prow[j]) * scale;
       }
     }
+    for (int j = n + lane; j < Nk; j += 64) row[j] = 0.0;
   }
   __syncthreads();
 
   for (int c0 = wv * 64; c0 < H; c0 += 256) {
     f64x4 acc[4];
-    weights_times_values(d, DS, nullptr, Sq, s0, kv, c0, lane, acc);
+    weights_times_values(d, DS, nullptr, Sq, s0, kv, n, c0, lane, acc);
     for (int t = 0; t < 4; ++t) {
       const int h = c0 + 16 * t + r;
       if (h >= H) continue;
@@ -216,6 +228,8 @@ __global__ __launch_bounds__(256) void attn64_dq_kernel(DosxAttn64 d, double sca
 
 // Backward, key side: dkv[j] = sum over every query row that reads key j (crystals bq = bk, bk + Bk, ... in order, rows s
 // in order) of ds[s][j] q[s] + (p o mask)[s][j] dout[s].  A wave owns 16 keys x 64 columns; nothing else writes them.
+// With key_ptr the rows j >= n of the crystal read nothing: their part rows are written as zeros, their dkvhat rows as
+// zeros unless accumulate (then left alone); a wave whose whole tile is past n skips the query loop.
 __global__ __launch_bounds__(256) void attn64_dkv_kernel(DosxAttn64 d) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int bk = blockIdx.y, j0 = (blockIdx.x * 4 + wv) * kQ, c0 = blockIdx.z * 64;
@@ -223,9 +237,10 @@ __global__ __launch_bounds__(256) void attn64_dkv_kernel(DosxAttn64 d) {
   const int Sq = d.Sq, Nk = d.Nk, H = d.H;
   const int r = lane & 15, kl = lane >> 4;
   const int ja = j0 + r;
+  const int n = live_keys(d, bk);
   f64x4 acc[4];
   for (int t = 0; t < 4; ++t) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
-  for (int bq = bk; bq < d.Bq; bq += d.Bk) {
+  for (int bq = bk; bq < d.Bq && j0 < n; bq += d.Bk) {
     const int64_t q0 = (int64_t)bq * Sq;
     const double* DS = d.ds + q0 * Nk;
     const double* P = d.probs + q0 * Nk;
@@ -234,7 +249,7 @@ __global__ __launch_bounds__(256) void attn64_dkv_kernel(DosxAttn64 d) {
       const int s = sb + kl;
       const bool sin = s < Sq;
       double a1 = 0.0, a2 = 0.0;
-      if (sin && ja < Nk) {
+      if (sin && ja < n) {
         const int64_t o = (int64_t)s * Nk + ja;
         a1 = DS[o];
         a2 = M != nullptr ? P[o] * (double)M[o] : P[o];
@@ -256,8 +271,14 @@ __global__ __launch_bounds__(256) void attn64_dkv_kernel(DosxAttn64 d) {
       const int j = j0 + kl + 4 * i;
       if (j >= Nk) continue;
       const int64_t row = (int64_t)bk * Nk + j;
-      const double g = acc[t][i];
       double* o = d.dkvhat + row * H + h;
+      if (j >= n) {
+        if (!d.accumulate) *o = 0.0;
+        d.part[row * 2 * H + h] = 0.0;
+        d.part[row * 2 * H + H + h] = 0.0;
+        continue;
+      }
+      const double g = acc[t][i];
       const double v = g * d.gamma0[h];
       *o = d.accumulate ? *o + v : v;
       d.part[row * 2 * H + h] = g * d.kvhat[row * H + h];

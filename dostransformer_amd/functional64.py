@@ -194,10 +194,12 @@ def _gnn_trunk_bwd(P: Params, G: Params, cfg, m: GraphMeta, ctx, dx: torch.Tenso
     _mlp_prelu_bwd(P, G, enc, cx, dx)
 
 
-def _encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, kvhat: torch.Tensor, Nk: int, Bk: int, T: int, drop):
+def _encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, kvhat: torch.Tensor, Nk: int, Bk: int, T: int, drop,
+                 key_ptr: Optional[torch.Tensor] = None):
     """TransformerEncoder (layers/transformer.py:46-79,120-157) on the query rows x [Bq*Sq, H] (row bq * Sq + s) over the
     normalised key rows kvhat [Bk*Nk, H], which stay the same for every layer (:72-73).  drop: None or (p, seed_dev,
-    stream_base): attention dropout, one [Bq, Sq, Nk] multiplier mask per layer drawn like the fp32 program's."""
+    stream_base): attention dropout, one [Bq, Sq, Nk] multiplier mask per layer drawn like the fp32 program's.  key_ptr
+    (int32 [Bk + 1]): each key crystal's own row count - the padding rows past it take no part (DosxAttn64.key_ptr)."""
     rows, H = x.shape
     lay = []
     for t in range(T):
@@ -210,7 +212,7 @@ def _encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, kvhat: 
             ops.dropout_mask(mask, drop[0], drop[1], drop[2] + t)
             if Fn.DROP_MASK_LOG is not None:
                 Fn.DROP_MASK_LOG.append((pre, t, mask))
-        x1, probs = attention64(q, x, kvhat, g0, b0, Sq, Bq, Nk, Bk, mask, SOFTMAX64)
+        x1, probs = attention64(q, x, kvhat, g0, b0, Sq, Bq, Nk, Bk, mask, SOFTMAX64, key_ptr)
         xh1, rs1, y1 = layernorm64(x1, P[lp + ".layer_norms.1.weight"], P[lp + ".layer_norms.1.bias"])
         h = gemm64(rows, 4 * H, [seg64(y1)], P[lp + ".fc1.weight"], alloc64(x.device, rows, 4 * H), bias=P[lp + ".fc1.bias"],
                    act=ACT64_RELU)
@@ -218,13 +220,13 @@ def _encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, kvhat: 
         lay.append((xhq, rsq, q, mask, probs, xh1, rs1, y1, h))
         x = x2
     xhf, rsf, y = layernorm64(x, P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"])
-    return y, (pre, lay, xhf, rsf, Sq, Bq, Nk, Bk, kvhat)
+    return y, (pre, lay, xhf, rsf, Sq, Bq, Nk, Bk, kvhat, key_ptr)
 
 
 def _encoder_bwd(P: Params, G: Params, ctx, dy: torch.Tensor, dkvhat: torch.Tensor, kacc: bool) -> torch.Tensor:
     """Gradient of the query rows; every layer's key + value gradient (times gamma0) goes into dkvhat, the first one written
     unless kacc (accumulate) - the key rows of the dense batch are read by two encoders."""
-    pre, lay, xhf, rsf, Sq, Bq, Nk, Bk, kvhat = ctx
+    pre, lay, xhf, rsf, Sq, Bq, Nk, Bk, kvhat, key_ptr = ctx
     rows, H = dy.shape
     dev = dy.device
 
@@ -248,7 +250,7 @@ def _encoder_bwd(P: Params, G: Params, ctx, dy: torch.Tensor, dkvhat: torch.Tens
         ln_grads(lp + ".layer_norms.1", part1)
         dx1 = rows_add64(rows, dx, dz1)
         # x1 = x + attention(LN0(x), LN0(keys))
-        dq, partk, _ = attention_bwd64(dx1, q, kvhat, g0, b0, probs, Sq, Bq, Nk, Bk, dkvhat, mask, SOFTMAX64, kacc)
+        dq, partk, _ = attention_bwd64(dx1, q, kvhat, g0, b0, probs, Sq, Bq, Nk, Bk, dkvhat, mask, SOFTMAX64, kacc, key_ptr)
         kacc = True
         dzq, partq = layernorm_bwd64(dq, xhq, rsq, g0, b0)
         ln_grads(lp + ".layer_norms.0", partq)
@@ -257,17 +259,22 @@ def _encoder_bwd(P: Params, G: Params, ctx, dy: torch.Tensor, dkvhat: torch.Tens
     return dx
 
 
-def dostransformer_phonon_fwd(P: Params, cfg, g, m: GraphMeta, drop=None):
-    """-> (dos [2B, S] (rows [0,B) global, [B,2B) system), x_L [N, H], saved context).  drop: None or (p, seed_dev)."""
+def dostransformer_phonon_fwd(P: Params, cfg, g, m: GraphMeta, drop=None, per_crystal_keys: bool = False):
+    """-> (dos [2B, S] (rows [0,B) global, [B,2B) system), x_L [N, H], saved context).  drop: None or (p, seed_dev).
+    per_crystal_keys: the two encoders that attend over atoms see each crystal's own atoms only, not the rows that pad it to
+    the batch's largest crystal - every crystal gets what the reference gives it at batch_size = 1 (main_phDOS.py:52-55),
+    and the backward is the sum of those per-sample gradients.  The dropout masks keep their [Bq, S, nmax] layout."""
     H, S, T, B = cfg.H, cfg.S, cfg.T, m.num_graphs
     nmax = m.n_max
+    kp = m.graph_ptr if per_crystal_keys else None
     dr = (lambda base: None) if drop is None else (lambda base: (drop[0], drop[1], base))
     xL, ctrunk = _gnn_trunk_fwd(P, cfg, g, m, "GN_encoder.node_encoder")                # :74-84
     dev = xL.device
     kv_n, rstd_n = dense_rows64(xL, m.graph_ptr, B, nmax)                               # :86-87, the keys' LN0 without affine
     # energies (:71,143): embedding row s for every crystal, crystal-major
     e_idx = (torch.arange(B * S, device=dev, dtype=torch.int32) % S).contiguous()
-    E1, c1 = _encoder_fwd(P, "transformer", rows_add64(B * S, P["embeddings.weight"], ia=e_idx), S, B, kv_n, nmax, B, T, dr(0))
+    E1, c1 = _encoder_fwd(P, "transformer", rows_add64(B * S, P["embeddings.weight"], ia=e_idx), S, B, kv_n, nmax, B, T, dr(0),
+                          kp)
     pool = graph_pool64(xL, m.graph_ptr, B)                                              # :90, :180-181
     graph = gemm64(B, H, [seg64(pool)], P["GN_decoder.mlp.0.weight"], alloc64(dev, B, H), bias=P["GN_decoder.mlp.0.bias"])
     sysidx = g.system.to(device=dev, dtype=torch.int32).contiguous()
@@ -284,7 +291,7 @@ def dostransformer_phonon_fwd(P: Params, cfg, g, m: GraphMeta, drop=None):
     ptr_s = torch.arange(0, 2 * BS + 1, S, device=dev, dtype=torch.int32)
     kv_s, rstd_s = dense_rows64(dosin, ptr_s, 2 * B, S)                                  # self attention: its own rows
     hs, c2 = _encoder_fwd(P, "transformer_self", dosin, S, 2 * B, kv_s, S, 2 * B, T, dr(64))
-    hsrc, c3 = _encoder_fwd(P, "transformer_source", hs, S, 2 * B, kv_n, nmax, B, T, dr(128))
+    hsrc, c3 = _encoder_fwd(P, "transformer_source", hs, S, 2 * B, kv_n, nmax, B, T, dr(128), kp)
     dos = gemm64(2 * BS, 1, [seg64(hsrc)], P["out_layer.weight"], alloc64(dev, 2 * BS, 1), bias=P["out_layer.bias"])
     ctx = (ctrunk, kv_n, rstd_n, c1, pool, graph, prow, sysidx, seg_g, seg_s, pre, dosin, ptr_s, kv_s, rstd_s, c2, c3, hsrc, E1)
     return dos.view(2 * B, S), xL, ctx

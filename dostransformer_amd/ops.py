@@ -1709,7 +1709,8 @@ ATTN64_MAX_H = 512                     # DOSX_ATTN64_MAX_H
 ATTN64_SOFTMAX_F64 = 1                 # DOSX_ATTN64_SOFTMAX_F64
 
 
-def _attn64_desc(q, kvhat, gamma0, beta0, Sq: int, Bq: int, Nk: int, Bk: int, mask, softmax64: bool) -> _lib.Attn64:
+def _attn64_desc(q, kvhat, gamma0, beta0, Sq: int, Bq: int, Nk: int, Bk: int, mask, softmax64: bool,
+                 key_ptr=None) -> _lib.Attn64:
     _chk_c64(q, kvhat, gamma0, beta0)
     H = q.shape[1]
     if not (1 <= H <= ATTN64_MAX_H) or Sq < 1 or Nk < 1 or Bk < 1 or Bq % Bk:
@@ -1718,18 +1719,24 @@ def _attn64_desc(q, kvhat, gamma0, beta0, Sq: int, Bq: int, Nk: int, Bk: int, ma
         raise ValueError(f"attention64: q {tuple(q.shape)}, kvhat {tuple(kvhat.shape)} for Sq={Sq} Bq={Bq} Nk={Nk} Bk={Bk}")
     if mask is not None and (mask.dtype != torch.float32 or not mask.is_contiguous() or tuple(mask.shape) != (Bq, Sq, Nk)):
         raise ValueError(f"attention64: the dropout mask must be a contiguous float32 [Bq, Sq, Nk] tensor")
+    if key_ptr is not None and (not isinstance(key_ptr, torch.Tensor) or key_ptr.dtype != torch.int32 or
+                                key_ptr.device != q.device or not key_ptr.is_contiguous() or key_ptr.numel() != Bk + 1):
+        raise ValueError(f"attention64: key_ptr must be a contiguous int32 tensor of Bk + 1 = {Bk + 1} entries on {q.device}")
     d = _lib.Attn64()
     d.Sq, d.Bq, d.Nk, d.Bk, d.H = Sq, Bq, Nk, Bk, H
     d.flags = ATTN64_SOFTMAX_F64 if softmax64 else 0
     d.q, d.kvhat, d.gamma0, d.beta0, d.drop_mask = q.data_ptr(), kvhat.data_ptr(), gamma0.data_ptr(), beta0.data_ptr(), _p(mask)
+    d.key_ptr = _p(key_ptr)
     return d
 
 
 def attention64(q: torch.Tensor, x: torch.Tensor, kvhat: torch.Tensor, gamma0, beta0, Sq: int, Bq: int, Nk: int, Bk: int,
-                mask: Optional[torch.Tensor] = None, softmax64: bool = False):
+                mask: Optional[torch.Tensor] = None, softmax64: bool = False, key_ptr: Optional[torch.Tensor] = None):
     """(out, probs): out = x + (softmax(q k^T / sqrt(H)) o mask) v with k = v = kvhat * gamma0 + beta0 (include/dosx.h:
-    DosxAttn64 for the row layouts); probs [Bq, Sq, Nk] the un-dropped probabilities the backward reads."""
-    d = _attn64_desc(q, kvhat, gamma0, beta0, Sq, Bq, Nk, Bk, mask, softmax64)
+    DosxAttn64 for the row layouts); probs [Bq, Sq, Nk] the un-dropped probabilities the backward reads.  key_ptr (int32
+    [Bk + 1] on the device): key crystal bk has key_ptr[bk+1] - key_ptr[bk] keys, the rows past them take no part and get
+    probability exactly 0."""
+    d = _attn64_desc(q, kvhat, gamma0, beta0, Sq, Bq, Nk, Bk, mask, softmax64, key_ptr)
     _chk_c64(x)
     assert x.shape == q.shape
     out, probs = alloc64(q.device, *q.shape), alloc64(q.device, Bq, Sq, Nk)
@@ -1740,10 +1747,11 @@ def attention64(q: torch.Tensor, x: torch.Tensor, kvhat: torch.Tensor, gamma0, b
 
 def attention_bwd64(dout: torch.Tensor, q: torch.Tensor, kvhat: torch.Tensor, gamma0, beta0, probs: torch.Tensor, Sq: int, Bq: int,
                     Nk: int, Bk: int, dkvhat: torch.Tensor, mask: Optional[torch.Tensor] = None, softmax64: bool = False,
-                    accumulate: bool = False):
+                    accumulate: bool = False, key_ptr: Optional[torch.Tensor] = None):
     """(dq [Bq*Sq, H], part [Bk*Nk, 2H], ds [Bq, Sq, Nk]); dkvhat (+)= the key + value gradient times gamma0.  Column sums
-    of part are the key side's dgamma0 | dbeta0; ds is the gradient of the scaled scores."""
-    d = _attn64_desc(q, kvhat, gamma0, beta0, Sq, Bq, Nk, Bk, mask, softmax64)
+    of part are the key side's dgamma0 | dbeta0; ds is the gradient of the scaled scores.  key_ptr as in attention64: ds and
+    part are zero past a crystal's keys, dkvhat too unless accumulate (then those rows are left alone)."""
+    d = _attn64_desc(q, kvhat, gamma0, beta0, Sq, Bq, Nk, Bk, mask, softmax64, key_ptr)
     _chk_c64(dout, probs, dkvhat)
     assert dout.shape == q.shape and dkvhat.shape == kvhat.shape and tuple(probs.shape) == (Bq, Sq, Nk)
     H = q.shape[1]

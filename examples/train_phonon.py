@@ -7,6 +7,12 @@ default it trains on synthetic structures; pass --pickle with a list of
 {symbols, positions, cell, phdos, crystal_system, mp_id} dicts to use real ones.
 
     python examples/train_phonon.py --epochs 5 --crystals 512
+
+--float64 trains as the reference does (main_phDOS.py:15-16,52-55,92): the float64 program, eager, torch.optim.AdamW, and
+every crystal attending over its own atoms only (set_per_crystal_keys), so a batch of B crystals is B of the reference's
+batch-size-1 samples in one pass - the loss is the sum of their per-crystal terms (main_phDOS.py:109-114 crystal by crystal).
+
+    python examples/train_phonon.py --float64 --epochs 2 --crystals 128 --hidden 64
 """
 import argparse
 import os
@@ -39,13 +45,15 @@ def main(argv=None):
     ap.add_argument("--pickle", default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="phonon_best.pt")
+    ap.add_argument("--float64", action="store_true", help="the reference's float64 training with per-crystal keys")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.manual_seed(args.seed)
 
     entries = pickle.load(open(args.pickle, "rb")) if args.pickle else synth.phonon_structures(args.crystals, args.seed)
     t0 = time.perf_counter()
-    crystals = featurize.build_data_all(entries, r_max=args.r_max, device=dev, dtype=torch.float32)
+    crystals = featurize.build_data_all(entries, r_max=args.r_max, device=dev,
+                                        dtype=torch.float64 if args.float64 else torch.float32)
     print(f"{len(crystals)} crystals -> graphs in {time.perf_counter() - t0:.2f} s "
           f"({sum(c['edge_index'].shape[1] for c in crystals)} edges)")
     perm = np.random.default_rng(args.seed).permutation(len(crystals))
@@ -53,6 +61,8 @@ def main(argv=None):
     split = {"valid": perm[:n_val], "test": perm[n_val:2 * n_val], "train": perm[2 * n_val:]}
     ds = {k: DeviceDataset([crystals[i] for i in idx], dev) for k, idx in split.items()}
 
+    if args.float64:
+        return train_float64(args, ds, dev)
     model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).to(dev)
     # coarse shape buckets: reshuffled batches then fall into a few dozen (N, E, n_max) buckets that are all recorded
     # within the first epoch (ghost padding is exact; it costs a few per cent of extra rows)
@@ -75,6 +85,42 @@ def main(argv=None):
             best = rmse
             checkpoint.save(args.out, model, trainer)
             t = evaluate.test_phonon(predictor, ds["test"].batches(args.batch_size))
+            print(f"            test rmse {t[0]:.4f} mse {t[1]:.4f} mae {t[2]:.4f} r2 {t[3]:.4f}   (saved {args.out})")
+    return {"best_valid_rmse": best, "train_loss": history}
+
+
+def train_float64(args, ds, dev):
+    """Eager float64 training: model(batch), loss.backward(), torch.optim.AdamW (the fp32 drivers Trainer / Predictor refuse
+    a float64 module).  evaluate.test_phonon takes the module itself."""
+    model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).double()
+    model = model.set_program_dtype(torch.float64).set_per_crystal_keys(True).to(dev)
+    opt = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=1e-2)       # main_phDOS.py:92
+    best, history = float("inf"), []
+    for epoch in range(args.epochs):
+        model.train()
+        t0, total, seen = time.perf_counter(), torch.zeros((), dtype=torch.float64, device=dev), 0
+        for batch in ds["train"].batches(args.batch_size, shuffle=True, seed=args.seed + epoch):
+            dos_global, _, dos_system = model(batch)
+            y = batch.phdos.reshape(dos_global.shape[0], -1).to(torch.float64)
+            # the reference's loss of one batch-size-1 sample, for every crystal of the batch; summed, so the gradient is
+            # the sum of the per-sample gradients
+            per_crystal = (torch.sqrt(((dos_global - y) ** 2).mean(dim=1)) +
+                           args.beta * torch.sqrt(((dos_system - y) ** 2).mean(dim=1)))
+            opt.zero_grad()
+            per_crystal.sum().backward()
+            opt.step()
+            total += per_crystal.detach().sum()
+            seen += batch.num_graphs
+        loss = float(total) / max(seen, 1)                          # one host read per epoch
+        dt = time.perf_counter() - t0
+        history.append(loss)
+        rmse, mse, mae, r2v = evaluate.test_phonon(model, ds["valid"].batches(args.batch_size))
+        print(f"[epoch {epoch + 1}/{args.epochs}] loss per crystal {loss:.4f} | {seen / dt:8.0f} crystals/s | "
+              f"valid rmse {rmse:.4f} mse {mse:.4f} mae {mae:.4f} r2 {r2v:.4f}")
+        if rmse < best:
+            best = rmse
+            checkpoint.save(args.out, model)
+            t = evaluate.test_phonon(model, ds["test"].batches(args.batch_size))
             print(f"            test rmse {t[0]:.4f} mse {t[1]:.4f} mae {t[2]:.4f} r2 {t[3]:.4f}   (saved {args.out})")
     return {"best_valid_rmse": best, "train_loss": history}
 

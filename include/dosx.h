@@ -1071,7 +1071,12 @@ int dosx_reduce_rows_f64(const double* src, int ld_src, double* dst, int ld_dst,
  * bk = bq % Bk (Bq a multiple of Bk); probabilities, masks and ds are [Bq, Sq, Nk].  The scores and both products are
  * fp64; the softmax follows the reference: scores rounded to fp32, softmax in fp32 (accurate expf), promoted - and its
  * backward the autograd mirror (dP o mask rounded to fp32, p (dP - sum p dP) in fp32, promoted, times H^-1/2).
- * DOSX_ATTN64_SOFTMAX_F64 computes the softmax and its backward in fp64 instead (a test hook, not the reference). */
+ * DOSX_ATTN64_SOFTMAX_F64 computes the softmax and its backward in fp64 instead (a test hook, not the reference).
+ * key_ptr (device, [Bk + 1], or NULL: every key row takes part, the reference's unmasked padding): key crystal bk has
+ * n = key_ptr[bk+1] - key_ptr[bk] keys (clamped to [0, Nk]), the rows j >= n do not exist for any query crystal that reads
+ * it - what the reference computes for that crystal alone in a batch of one.  Nothing of kvhat, probs, ds or drop_mask
+ * past n is read; probs, ds and part are written as 0.0 there, dkvhat as 0.0 unless accumulate (then left alone); n = 0
+ * gives out = x. */
 #define DOSX_ATTN64_MAX_H 512
 #define DOSX_ATTN64_SOFTMAX_F64 1
 typedef struct DosxAttn64 {
@@ -1091,6 +1096,7 @@ typedef struct DosxAttn64 {
   double* dkvhat;           /* [Bk*Nk, H] (+)= dkv * gamma0, dkv the summed key + value gradient (backward) */
   double* part;             /* [Bk*Nk, 2H] per key row dkv * kvhat | dkv: column sums are dgamma0 | dbeta0 (backward) */
   int32_t accumulate;       /* dkvhat += instead of = */
+  const int32_t* key_ptr;   /* [Bk + 1] device: per-crystal key counts (the batch's graph_ptr), or NULL */
 } DosxAttn64;
 /* forward: writes out and probs */
 int dosx_attention_f64(const DosxAttn64* desc_host, dosx_stream_t stream);
