@@ -121,6 +121,7 @@ class FfnBwd(C.Structure):
         ("att_partials_q", C.c_void_p), ("att_partials_kv", C.c_void_p), ("att_dkv_part", C.c_void_p), ("att_dkv_cnt", C.c_void_p),
         ("att_dkvhat", C.c_void_p), ("att_dkv_accumulate", C.c_int32),
         ("att_Nk", C.c_int32), ("att_Bk", C.c_int32), ("att_Bq", C.c_int32), ("att_Sq", C.c_int32), ("att_qs", C.c_int32), ("att_qb", C.c_int32),
+        ("att_key_ptr", C.c_void_p),
     ]
 
 

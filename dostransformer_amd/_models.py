@@ -68,8 +68,8 @@ class DOSTransformerBase(FusedModel):
         batched forward, padding rows as keys.  Returns self."""
         if flag and self._program_dtype != torch.float64:
             raise DosxError(f"{type(self).__name__}.set_per_crystal_keys: a switch of the float64 program "
-                            f"(set_program_dtype(torch.float64), DOSTransformer_phonon only); the fp32 program has it for "
-                            f"inference as Predictor(model, per_crystal_keys=True)")
+                            f"(set_program_dtype(torch.float64), DOSTransformer_phonon only); the fp32 program has it as "
+                            f"Predictor(model, per_crystal_keys=True) and Trainer(model, per_crystal_keys=True)")
         object.__setattr__(self, "_per_crystal_keys", bool(flag))
         return self
 
@@ -122,8 +122,8 @@ class DOSTransformerBase(FusedModel):
 
     def _program_fwd(self, P, g, m, bump_seed: bool = True, per_crystal_keys: bool = False):
         if P["embeddings.weight"].dtype == torch.float64:
-            # (the per_crystal_keys argument is predict.Predictor's and reaches the fp32 program only: the float64 program
-            #  follows the module's own switch)
+            # (the per_crystal_keys argument is predict.Predictor's and train.Trainer's and reaches the fp32 program only: the
+            #  float64 program follows the module's own switch)
             dos, xL, ctx = F64.dostransformer_phonon_fwd(P, self._cfg, g, m, drop=self._dropout(dos_device(P), bump_seed),
                                                          per_crystal_keys=self._per_crystal_keys)
             B = m.num_graphs

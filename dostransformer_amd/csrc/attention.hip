@@ -106,16 +106,26 @@ struct StreamGeo {
   int CHB;     // floats of one chunk buffer
 };
 
+// The bound of the staging waves' buffer loads of kvhat, which return zeros beyond it.  With per-crystal key counts (KP): the
+// bytes up to the end of key row nk - 1 of crystal bk (row j of crystal bk lies at (j * Bk + bk) * H) - the rows past the crystal's
+// own keys are never fetched and enter both products as zeros; else the whole key set.
+template <bool KP>
+__device__ __forceinline__ uint32_t live_key_bytes(const DosxAttn& a, int bk, int nk) {
+  if constexpr (KP) return nk > 0 ? (uint32_t)((((size_t)(nk - 1) * a.Bk + bk + 1) * a.H) * 4) : 0u;
+  else return (uint32_t)((size_t)a.Nk * a.Bk * a.H * 4);
+}
+
 // The staging waves' whole job.  `sync()` is the workgroup barrier; the matrix waves execute the mirror-image
 // sequence in stream_matrix_*().  Barrier schedule:  [K prologue] B | nkc x (B) | [V prologue] B | B | nvc x (B)
-__device__ __forceinline__ void stream_stage(const DosxAttn& a, const Geo& g, const StreamGeo& sg, float* CH, int bk, int st) {
-  const int H = a.H, Nk = a.Nk;
-  const __amdgpu_buffer_rsrc_t rK =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.kvhat, 0, (uint32_t)((size_t)Nk * a.Bk * H * 4), 0x00020000);
+template <bool KP>
+__device__ __forceinline__ void stream_stage(const DosxAttn& a, const Geo& g, const StreamGeo& sg, float* CH, int bk, int st, int nk) {
+  const int H = a.H;
+  const int nlt = dosx_live_tiles<KP, 5>(nk, g.NKP / 32);      // 32-key row blocks that hold live keys (sg.nvc is the same count)
+  const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)a.kvhat, 0, live_key_bytes<KP>(a, bk, nk), 0x00020000);
   const int jr = st >> 3, q4 = (st & 7) * 4;
   // ---- K chunks: Ks[j][0..31] = kvhat[j*Bk+bk][32c .. 32c+31], j = jr + 32 i
   {
-    const int nrb = g.NKP / 32;
+    const int nrb = nlt;
     uint32_t voff[SKR];
 #pragma unroll
     for (int i = 0; i < SKR; ++i) voff[i] = (uint32_t)((((size_t)(jr + 32 * i) * a.Bk + bk) * H + q4) * 4);
@@ -205,17 +215,18 @@ constexpr int MAX_KCH = 8;             // H <= 256
 
 __host__ __device__ inline int resident_k_floats(const Geo& g) { return (g.HP / 32) * g.NKP * LDK; }
 
-__device__ __forceinline__ void stage_resident(const DosxAttn& a, const Geo& g, const StreamGeo& sg, float* CH, int bk, int st) {
-  const int H = a.H, Nk = a.Nk;
-  const __amdgpu_buffer_rsrc_t rK =
-      __builtin_amdgcn_make_buffer_rsrc((void*)a.kvhat, 0, (uint32_t)((size_t)Nk * a.Bk * H * 4), 0x00020000);
+template <bool KP>
+__device__ __forceinline__ void stage_resident(const DosxAttn& a, const Geo& g, const StreamGeo& sg, float* CH, int bk, int st, int nk) {
+  const int H = a.H;
+  const int nlt = dosx_live_tiles<KP, 5>(nk, g.NKP / 32);      // 32-key tiles that hold live keys: the others are not fetched
+  const __amdgpu_buffer_rsrc_t rK = __builtin_amdgcn_make_buffer_rsrc((void*)a.kvhat, 0, live_key_bytes<KP>(a, bk, nk), 0x00020000);
   const int jr = st >> 3, q4 = (st & 7) * 4;
-  const int nkc = g.HP / 32, nrb = g.NKP / 32, kcf = g.NKP * LDK;
+  const int nkc = g.HP / 32, nrb = nlt, kcf = g.NKP * LDK;
   float4 rk[MAX_KCH][2], rv[SVC][2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     if (t < nrb) {
-      const uint32_t vk = (uint32_t)((((size_t)(jr + 32 * t) * a.Bk + bk) * H + q4) * 4);   // key row (rows >= Nk: zeros by the bounds)
+      const uint32_t vk = (uint32_t)((((size_t)(jr + 32 * t) * a.Bk + bk) * H + q4) * 4);   // key row (rows >= nk: zeros by the bounds)
 #pragma unroll
       for (int c = 0; c < MAX_KCH; ++c)
         if (c < nkc) rk[c][t] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rK, vk, c * (KC * 4), 0));
@@ -245,13 +256,14 @@ __device__ __forceinline__ void stage_resident(const DosxAttn& a, const Geo& g, 
         if (i < nkc) st4(CH + t * sg.CHB + jr * g.LDH + q4 + 32 * i, rv[i][t]);
     }
   __syncthreads();                     // softmax done, V visible
-  for (int c = 0; c < nrb; ++c) __syncthreads();       // one per V chunk (stream_pv)
+  for (int c = 0; c < sg.nvc; ++c) __syncthreads();    // one per V chunk (stream_pv)
 }
 
 // matrix wave w: Sp[w][32][36] = Qs[:, its feature chunks] . K[key tile w % tiles]^T   (partial over its share of the features)
-__device__ __forceinline__ void qk_resident(const float* As, int LDH, const float* CH, int nkc, int NKP, float* Sp, int tid) {
+__device__ __forceinline__ void qk_resident(const float* As, int LDH, const float* CH, int nkc, int NKP, float* Sp, int tid, int nlt) {
   const int lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hh = lane >> 5;
   const int nkt = NKP >> 5, jt = wave % nkt, step = 4 / nkt, kcf = NKP * LDK;
+  if (jt >= nlt) return;               // (per-crystal counts: a key tile without live keys - its partial tiles are never read)
   f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -282,9 +294,8 @@ __device__ __forceinline__ float resident_score(const float* prow, int j, int NK
 
 // matrix waves: S[32][NKP] = A[32][HP] . kvhat^T, one barrier per streamed feature chunk
 __device__ __forceinline__ void stream_qk(f32x16 (&acc)[MAX_KT], const float* As, int LDH, const float* CH, const StreamGeo& sg,
-                                          int NKP, int tid) {
+                                          int nkt, int tid) {       // nkt: 32-key tiles to multiply (those with live keys)
   const int lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hh = lane >> 5;
-  const int nkt = NKP / 32;
 #pragma unroll
   for (int t = 0; t < MAX_KT; ++t)
 #pragma unroll
@@ -338,9 +349,8 @@ __device__ __forceinline__ void stream_pv(f32x16 (&acc)[MAX_CT], const float* Ps
   }
 }
 
-__device__ __forceinline__ void store_scores1(const f32x16 (&acc)[MAX_KT], float* Ss, int LDS_, int NKP, int tid) {
+__device__ __forceinline__ void store_scores1(const f32x16 (&acc)[MAX_KT], float* Ss, int LDS_, int nkt, int tid) {
   const int lane = tid & 63, wave = tid >> 6, l31 = lane & 31, hh = lane >> 5;
-  const int nkt = NKP / 32;
 #pragma unroll
   for (int t = 0; t < MAX_KT; ++t) {
     const int jt = wave + 4 * t;
@@ -350,7 +360,7 @@ __device__ __forceinline__ void store_scores1(const f32x16 (&acc)[MAX_KT], float
   }
 }
 
-template <int NJ, bool RESIDENT>
+template <int NJ, bool RESIDENT, bool KP>
 __global__ __launch_bounds__(512) void attn_fwd_stream_kernel(const DosxAttn a) {
   DOSX_SET_MAIN_PRIO();
   extern __shared__ __align__(16) float sm[];
@@ -363,11 +373,14 @@ __global__ __launch_bounds__(512) void attn_fwd_stream_kernel(const DosxAttn a) 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q16 = lane & 15;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const int s0 = blockIdx.x * QT, bq = blockIdx.y, bk = bq % a.Bk;
+  const int nk0 = dosx_live_keys<KP>(a.key_ptr, bk, a.Nk);     // KP: the crystal's own keys (DosxAttn.key_ptr), else Nk
+  const int nlt = dosx_live_tiles<KP, 5>(nk0, g.NKP / 32);     // 32-key tiles with live keys: the others take no loads and no MFMAs
+  sg.nvc = nlt;
   // RESIDENT (Nk <= 64 when it fits the LDS): keys resident, Q.K^T split over the features (see qk_resident)
   float* Sp = CH + max(2 * sg.CHB, resident_k_floats(g));      // [4][32][36] partial score tiles (RESIDENT only)
   if (wave_u >= 4) {
-    if constexpr (RESIDENT) stage_resident(a, g, sg, CH, bk, tid - 256);
-    else stream_stage(a, g, sg, CH, bk, tid - 256);
+    if constexpr (RESIDENT) stage_resident<KP>(a, g, sg, CH, bk, tid - 256, nk0);
+    else stream_stage<KP>(a, g, sg, CH, bk, tid - 256, nk0);
     return;                                         // (the epilogue barrier below counts live waves only)
   }
   const int H = a.H, Sq = a.Sq, Nk = a.Nk;
@@ -439,22 +452,21 @@ __global__ __launch_bounds__(512) void attn_fwd_stream_kernel(const DosxAttn a) 
   __syncthreads();
 
   if constexpr (RESIDENT) {
-    qk_resident(Qs, g.LDH, CH, sg.nkc, g.NKP, Sp, tid);
+    qk_resident(Qs, g.LDH, CH, sg.nkc, g.NKP, Sp, tid, nlt);
   } else {
     f32x16 sacc[MAX_KT];
-    stream_qk(sacc, Qs, g.LDH, CH, sg, g.NKP, tid);
-    store_scores1(sacc, Ss, g.LDS_, g.NKP, tid);
+    stream_qk(sacc, Qs, g.LDH, CH, sg, nlt, tid);
+    store_scores1(sacc, Ss, g.LDS_, nlt, tid);
   }
   __syncthreads();
 
   float psum[RP];
 #pragma unroll
-  for (int p = 0; p < RP; ++p) psum[p] = 1.f;
+  for (int p = 0; p < RP; ++p) psum[p] = dosx_psum_one<KP>(nk0);    // (rows of P sum to 1 - or to 0 for a crystal without keys)
   // ---- exact fp32 softmax over the Nk keys (padded atoms included, like the reference; key_ptr: the crystal's own keys only) ----
   {
     const float scale = rsqrtf((float)H);
-    const int bk_ = bq % a.Bk;
-    const int nk = a.key_ptr ? min(a.key_ptr[bk_ + 1] - a.key_ptr[bk_], Nk) : Nk;
+    const int nk = KP ? nk0 : dosx_live_keys_fwd<KP>(a.key_ptr, bq % a.Bk, Nk);
     float v[RP][NJ], mx[RP], sum[RP];
 #pragma unroll
     for (int p = 0; p < RP; ++p) {
@@ -465,8 +477,8 @@ __global__ __launch_bounds__(512) void attn_fwd_stream_kernel(const DosxAttn a) 
       for (int jj = 0; jj < NJ; ++jj) {
         const int j = q16 + 16 * jj;
         float sc_ = 0.f;
-        if constexpr (RESIDENT) { if (j < Nk) sc_ = resident_score(prow, j, g.NKP); }
-        else sc_ = row[j];
+        if constexpr (RESIDENT) { if (j < (KP ? nk : Nk)) sc_ = resident_score(prow, j, g.NKP); }
+        else sc_ = (!KP || j < nk) ? row[j] : 0.f;             // (KP: the score tiles past the live ones were never written)
         const float t = j < nk ? sc_ * scale : -INFINITY;          // (nk: the crystal's own key count with DosxAttn.key_ptr, else Nk)
         v[p][jj] = t;
         mx[p] = fmaxf(mx[p], t);
@@ -485,7 +497,7 @@ __global__ __launch_bounds__(512) void attn_fwd_stream_kernel(const DosxAttn a) 
       }
     }
 #pragma unroll
-    for (int p = 0; p < RP; ++p) sum[p] = 1.f / row16_sum(sum[p]);
+    for (int p = 0; p < RP; ++p) sum[p] = dosx_softmax_inv<KP>(row16_sum(sum[p]));
     // attention dropout (multihead_attention.py:70: F.dropout on the softmax output): the saved probabilities stay the
     // un-dropped P (the backward needs them), the P.V product takes P' = P o M, M in {0, 1/(1-p)} read from drop_mask
     float mk[RP][NJ];
@@ -500,7 +512,7 @@ __global__ __launch_bounds__(512) void attn_fwd_stream_kernel(const DosxAttn a) 
 #pragma unroll
         for (int jj = 0; jj < NJ; ++jj) {
           const int j = q16 + 16 * jj;
-          mk[p][jj] = a.drop_mask[((size_t)bq * Sq + s) * Nk + (j < Nk ? j : 0)];
+          mk[p][jj] = dosx_key_entry<KP>(a.drop_mask, ((size_t)bq * Sq + s) * Nk, j, nk, Nk, 1.f);
         }
       }
     }
@@ -513,7 +525,7 @@ __global__ __launch_bounds__(512) void attn_fwd_stream_kernel(const DosxAttn a) 
       for (int jj = 0; jj < NJ; ++jj) {
         const int j = q16 + 16 * jj;
         if (j >= g.NKP) continue;
-        const float pr = v[p][jj] * sum[p];           // 0 beyond Nk
+        const float pr = v[p][jj] * sum[p];           // 0 beyond nk
         const float prm = pr * mk[p][jj];
         row[j] = prm;
         t += prm;
@@ -611,11 +623,11 @@ __global__ __launch_bounds__(512) void attn_fwd_stream_kernel(const DosxAttn a) 
 // <= 12 atoms, self attention over 51 bins): that kernel re-streamed every dO / x row and the dS round trip through HBM
 // behind one barrier per 16 queries - 27 us per launch for 0.08 GF - where this costs 32-64 MFMAs per wave.
 constexpr int DKR = 16;          // key rows per reduction group = partial-sum rows per crystal: ceil(Nk / 16)
-template <bool SC1>
+template <bool SC1, bool KP>
 __device__ __forceinline__ void dkv_reduce_group(const DosxAttn& a, const int nqt, const int grp, const int ngroups,
                                                  const int bk, float (*Pp)[2 * 256], const int tid);
 
-template <int NJ, bool PKV, bool RESIDENT>
+template <int NJ, bool PKV, bool RESIDENT, bool KP>
 __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(const DosxAttn a) {
   DOSX_SET_MAIN_PRIO();
   extern __shared__ __align__(16) float sm[];
@@ -633,9 +645,12 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(const DosxAttn 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q16 = lane & 15;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const int s0 = blockIdx.x * QT, bq = blockIdx.y, bk = bq % a.Bk;
+  const int nk = dosx_live_keys<KP>(a.key_ptr, bk, a.Nk);      // KP: the crystal's own keys (DosxAttn.key_ptr), else Nk
+  const int nlt = dosx_live_tiles<KP, 5>(nk, g.NKP / 32);      // 32-key tiles with live keys: the others take no loads and no MFMAs
+  sg.nvc = nlt;
   if (wave_u >= 4) {
-    if constexpr (RESIDENT) stage_resident(a, g, sg, CH, bk, tid - 256);
-    else stream_stage(a, g, sg, CH, bk, tid - 256);
+    if constexpr (RESIDENT) stage_resident<KP>(a, g, sg, CH, bk, tid - 256, nk);
+    else stream_stage<KP>(a, g, sg, CH, bk, tid - 256, nk);
     return;
   }
   const int H = a.H, Sq = a.Sq, Nk = a.Nk;
@@ -661,7 +676,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(const DosxAttn 
 #pragma unroll
     for (int jj = 0; jj < NJ; ++jj) {
       const int j = q16 + 16 * jj;
-      pr[p][jj] = a.probs[((size_t)bq * Sq + s) * Nk + (j < Nk ? j : 0)];
+      pr[p][jj] = dosx_key_entry<KP>(a.probs, ((size_t)bq * Sq + s) * Nk, j, nk, Nk, 0.f);
     }
   }
   // attention dropout: dP = M o dP' with dP' = dO.V^T.  Without a mask the row constant dO.beta0 of dP' cancels in
@@ -680,7 +695,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(const DosxAttn 
 #pragma unroll
       for (int jj = 0; jj < NJ; ++jj) {
         const int j = q16 + 16 * jj;
-        mk[p][jj] = a.drop_mask[((size_t)bq * Sq + s) * Nk + (j < Nk ? j : 0)];
+        mk[p][jj] = dosx_key_entry<KP>(a.drop_mask, ((size_t)bq * Sq + s) * Nk, j, nk, Nk, 1.f);
       }
       float t = 0.f;
 #pragma unroll
@@ -712,11 +727,11 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(const DosxAttn 
 
   // dP (up to a row constant) = (dO gamma) . k̂^T
   if constexpr (RESIDENT) {
-    qk_resident(Ds, g.LDH, CH, sg.nkc, g.NKP, Sp, tid);
+    qk_resident(Ds, g.LDH, CH, sg.nkc, g.NKP, Sp, tid, nlt);
   } else {
     f32x16 sacc[MAX_KT];
-    stream_qk(sacc, Ds, g.LDH, CH, sg, g.NKP, tid);
-    store_scores1(sacc, Ss, g.LDS_, g.NKP, tid);
+    stream_qk(sacc, Ds, g.LDH, CH, sg, nlt, tid);
+    store_scores1(sacc, Ss, g.LDS_, nlt, tid);
   }
   __syncthreads();
 
@@ -733,10 +748,10 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(const DosxAttn 
       for (int jj = 0; jj < NJ; ++jj) {
         const int j = q16 + 16 * jj;
         float t = 0.f;
-        if constexpr (RESIDENT) { if (j < Nk) t = resident_score(prow, j, g.NKP); }
-        else t = j < Nk ? row[j] : 0.f;
+        if constexpr (RESIDENT) { if (j < nk) t = resident_score(prow, j, g.NKP); }
+        else t = j < nk ? row[j] : 0.f;
         if (a.drop_mask) t = (t + cq[p]) * mk[p][jj];
-        if (j < Nk) dot[p] += pr[p][jj] * t;
+        if (j < nk) dot[p] += pr[p][jj] * t;
         dp[p][jj] = t;
       }
     }
@@ -750,9 +765,9 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(const DosxAttn 
       for (int jj = 0; jj < NJ; ++jj) {
         const int j = q16 + 16 * jj;
         if (j >= g.NKP) continue;
-        const float ds = (j < Nk && s < Sq) ? pr[p][jj] * (dp[p][jj] - dot[p]) * scale : 0.f;
+        const float ds = (j < nk && s < Sq) ? pr[p][jj] * (dp[p][jj] - dot[p]) * scale : 0.f;
         row[j] = ds;
-        if constexpr (PKV) Ps2[lr * g.LDS_ + j] = (j < Nk && s < Sq) ? pr[p][jj] * mk[p][jj] : 0.f;   // dV takes P' = P o M
+        if constexpr (PKV) Ps2[lr * g.LDS_ + j] = (j < nk && s < Sq) ? pr[p][jj] * mk[p][jj] : 0.f;   // dV takes P' = P o M
         else if (j < Nk && s < Sq) a.dscores[((size_t)bq * Sq + s) * Nk + j] = ds;
       }
       if (NJ * 16 < g.NKP) {
@@ -889,6 +904,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(const DosxAttn 
         const float b2 = Ql[(mm + hh) * g.LDH + ct * 32 + l31];
 #pragma unroll
         for (int kt = 0; kt < NKT; ++kt) {
+          if (KP && kt >= nlt) continue;                // (a key tile without live keys: its share stays zero and unpublished)
           dacc[kt][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[kt], b1, dacc[kt][t], 0, 0, 0);
           dacc2[kt][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(sa[kt], b2, dacc2[kt][t], 0, 0, 0);
         }
@@ -905,7 +921,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(const DosxAttn 
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int j = kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-          if (j < Nk && col < H) {
+          if (j < (KP ? nk : Nk) && col < H) {         // (KP: the reduction reads the rows of live keys only)
             const float v = dacc[kt][t][r] + dacc2[kt][t][r];
             if (fused) __hip_atomic_store(part + (size_t)j * H + col, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sc1
             else part[(size_t)j * H + col] = v;
@@ -930,7 +946,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(const DosxAttn 
         const int ngroups = (Nk + DKR - 1) / DKR;
         float (*PpR)[2 * 256] = reinterpret_cast<float (*)[2 * 256]>(sm);
         for (int grp = 0; grp < ngroups; ++grp) {
-          dkv_reduce_group<true>(a, (int)gridDim.x, grp, ngroups, bk, PpR, tid);
+          dkv_reduce_group<true, KP>(a, (int)gridDim.x, grp, ngroups, bk, PpR, tid);
           __syncthreads();
         }
         if (tid == 0) __hip_atomic_store(a.dkv_cnt + bk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -949,7 +965,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(const DosxAttn 
 // number of times every dO / x row is re-read.  All 8 waves run the row epilogue.
 constexpr int DQC = 16;    // queries per streamed chunk
 
-template <int KG>
+template <int KG, bool KP>
 __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const DosxAttn a) {
   extern __shared__ __align__(16) float sm[];
   const Geo g = make_geo(a.H, a.Nk);
@@ -961,7 +977,9 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const DosxAttn a) {
   const int H = a.H, Sq = a.Sq, Nk = a.Nk;
   const int nct = g.HP / 32;
   const bool raw_q = (a.flags & DOSX_ATTN_RAW_Q) != 0;
-  const int nchunks = (Sq + DQC - 1) / DQC, nit = (a.Bq / a.Bk) * nchunks;
+  const int nk = dosx_live_keys<KP>(a.key_ptr, bk, Nk);      // KP: the crystal's own keys (DosxAttn.key_ptr), else Nk
+  // (KP: a key group wholly past the crystal's keys streams nothing - its rows get zeros from the epilogue)
+  const int nchunks = (Sq + DQC - 1) / DQC, nit = (KP && j0 >= nk) ? 0 : (a.Bq / a.Bk) * nchunks;
 
   // epilogue operands, fetched up front by every wave: this wave's 4*KG key rows (quarter wave per row)
   float4 kh[KG][KCB], dk0[KG][KCB], g0[KCB];
@@ -969,13 +987,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const DosxAttn a) {
   for (int k = 0; k < KCB; ++k) g0[k] = ld4(a.gamma0 + ((q16 * 4 + 64 * k) < H ? (q16 * 4 + 64 * k) : 0));
 #pragma unroll
   for (int p = 0; p < KG; ++p) {
-    const int j = min(j0 + wave * 4 * KG + p * 4 + (lane >> 4), Nk - 1);
+    const int jr = j0 + wave * 4 * KG + p * 4 + (lane >> 4), j = min(jr, Nk - 1);
     const size_t krow = ((size_t)j * a.Bk + bk) * H;
 #pragma unroll
     for (int k = 0; k < KCB; ++k) {
       const int c = q16 * 4 + 64 * k, cc = c < H ? c : 0;
-      kh[p][k] = ld4(a.kvhat + krow + cc);
-      dk0[p][k] = a.dkv_accumulate ? ld4(a.dkvhat + krow + cc) : f4zero();
+      kh[p][k] = (!KP || jr < nk) ? ld4(a.kvhat + krow + cc) : f4zero();
+      dk0[p][k] = (a.dkv_accumulate && (!KP || jr < nk)) ? ld4(a.dkvhat + krow + cc) : f4zero();
     }
   }
 
@@ -1008,7 +1026,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const DosxAttn a) {
       bq4[k] = ld4(a.beta0 + cc);
     }
 #pragma unroll
-    for (int u = 0; u < 2 * KG; ++u) vP[u] = (uint32_t)(((size_t)row * Nk + min(j0 + (st & 15) + 16 * u, Nk - 1)) * 4);
+    for (int u = 0; u < 2 * KG; ++u) vP[u] = (uint32_t)(((size_t)row * Nk + min(j0 + (st & 15) + 16 * u, (KP ? max(nk, 1) : Nk) - 1)) * 4);
     const uint32_t vT = (uint32_t)((size_t)row * a.Bq * 8);
     struct Set {
       float4 d[KCB], x[KCB];
@@ -1063,7 +1081,7 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const DosxAttn a) {
 #pragma unroll
       for (int u = 0; u < 2 * KG; ++u) {
         const int jl = (st & 15) + 16 * u;
-        const bool ok = q.rok && (j0 + jl) < Nk;
+        const bool ok = q.rok && (j0 + jl) < nk;
         Pc[row * LDP + jl] = ok ? (has_mask ? q.pp[u] * q.mm[u] : q.pp[u]) : 0.f;
         Sc[row * LDP + jl] = ok ? q.ss[u] : 0.f;
       }
@@ -1161,6 +1179,12 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const DosxAttn a) {
       for (int k = 0; k < KCB; ++k) {
         const int c = q16 * 4 + 64 * k;
         if (c >= H) continue;
+        if constexpr (KP) {
+          if (j >= nk) {               // not a key of this crystal: no gradient (left alone when accumulating)
+            if (!a.dkv_accumulate) st4(a.dkvhat + krow + c, f4zero());
+            continue;
+          }
+        }
         const float4 d = ld4(R + lr * g.LDH + c), xh = kh[p][k];
         pg[k].x += d.x * xh.x; pg[k].y += d.y * xh.y; pg[k].z += d.z * xh.z; pg[k].w += d.w * xh.w;
         pb[k] = f4add(pb[k], d);
@@ -1206,13 +1230,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const DosxAttn a) {
 // One group of DKR key rows of crystal bk, by 256 threads (tid256); Pp: [16][512] floats of LDS; ngroups = ceil(Nk / DKR).
 // SC1: the partials were published by OTHER workgroups of this launch (fused form: the last arriving dq workgroup of a
 // crystal runs this) - every load of them is then an sc1 load (bypasses this CU's L1).  Contains a barrier.
-template <bool SC1>
+template <bool SC1, bool KP>
 __device__ __forceinline__ void dkv_reduce_group(const DosxAttn& a, const int nqt, const int grp, const int ngroups,
                                                  const int bk, float (*Pp)[2 * 256], const int tid) {
   const int lane = tid & 63, wave = tid >> 6, q16 = lane & 15, slot = wave * 4 + (lane >> 4);
   const int H = a.H, Nk = a.Nk, rep = a.Bq / a.Bk;
   const int j = grp * DKR + slot;
-  const bool jv = j < Nk;
+  const bool jv = j < dosx_live_keys<KP>(a.key_ptr, bk, Nk);  // (KP: a row past the crystal's own keys is no key - zeros)
   const int jc = jv ? j : 0;
   const size_t krow = ((size_t)jc * a.Bk + bk) * H;
   float4 g0[KCB], d[KCB], kh[KCB], d0[KCB];
@@ -1220,11 +1244,11 @@ __device__ __forceinline__ void dkv_reduce_group(const DosxAttn& a, const int nq
   for (int k = 0; k < KCB; ++k) {
     const int c = q16 * 4 + 64 * k, cc = c < H ? c : 0;
     g0[k] = ld4(a.gamma0 + cc);
-    kh[k] = ld4(a.kvhat + krow + cc);
-    d0[k] = a.dkv_accumulate ? ld4(a.dkvhat + krow + cc) : f4zero();
+    kh[k] = (!KP || jv) ? ld4(a.kvhat + krow + cc) : f4zero();
+    d0[k] = (a.dkv_accumulate && (!KP || jv)) ? ld4(a.dkvhat + krow + cc) : f4zero();
     d[k] = f4zero();
   }
-  const int np = rep * nqt;                          // partials of this key row, in (i, tile) order
+  const int np = (KP && !jv) ? 0 : rep * nqt;        // partials of this key row, in (i, tile) order (none for a row that is no key)
   const size_t pstride = (size_t)Nk * H;             // between consecutive tiles of one query batch entry
   const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)a.dkv_part, 0, 0x7fffffff, 0x00020000);
   for (int p0 = 0; p0 < np; p0 += 4) {
@@ -1259,6 +1283,9 @@ __device__ __forceinline__ void dkv_reduce_group(const DosxAttn& a, const int nq
       st4(a.dkvhat + krow + c, make_float4(d[k].x * g0[k].x + d0[k].x, d[k].y * g0[k].y + d0[k].y,
                                            d[k].z * g0[k].z + d0[k].z, d[k].w * g0[k].w + d0[k].w));
     }
+    if constexpr (KP) {
+      if (!jv && j < Nk && c < H && !a.dkv_accumulate) st4(a.dkvhat + ((size_t)j * a.Bk + bk) * H + c, f4zero());
+    }
     if (c < 256) {
       st4(&Pp[slot][c], pg);
       st4(&Pp[slot][256 + c], pb);
@@ -1275,9 +1302,10 @@ __device__ __forceinline__ void dkv_reduce_group(const DosxAttn& a, const int nq
   }
 }
 
+template <bool KP>
 __global__ __launch_bounds__(256) void attn_dkv_reduce_kernel(const DosxAttn a, int nqt) {
   __shared__ float Pp[16][2 * 256];                 // per quarter-wave slot: [dgamma | dbeta] (H <= 256)
-  dkv_reduce_group<false>(a, nqt, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y, Pp, (int)threadIdx.x);
+  dkv_reduce_group<false, KP>(a, nqt, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y, Pp, (int)threadIdx.x);
 }
 
 size_t fwd_smem(const Geo& g, bool resident = false) {      // (resident: all key chunks at once + the four partial score tiles)
@@ -1344,7 +1372,6 @@ extern "C" int dosx_attention_fwd(const DosxAttn* ap, dosx_stream_t stream) {
   DOSX_CHECK_ARG(!a.ln1_out || (a.out_stats && a.ln1_gamma && a.ln1_beta && a.Nk <= MAX_FUSED_NK && !(a.flags & DOSX_ATTN_NO_RESIDUAL)),
                  "dosx_attention_fwd: ln1_out needs out_stats, ln1_gamma / ln1_beta, <= %d keys and the residual", MAX_FUSED_NK);
   if (const int rc = dosx_detail::attn_aligned_fwd(a, to_stream(stream))) return rc < 0 ? rc : 0;
-  DOSX_CHECK_ARG(!a.key_ptr || a.Nk <= MAX_FUSED_NK, "dosx_attention_fwd: key_ptr (per-crystal key counts) needs <= %d keys", MAX_FUSED_NK);
   if (a.Nk > MAX_FUSED_NK) return dosx_detail::attn_general_fwd(a, to_stream(stream));
   const Geo g = make_geo(a.H, a.Nk);
   const bool res = fwd_resident(a);
@@ -1354,21 +1381,24 @@ extern "C" int dosx_attention_fwd(const DosxAttn* ap, dosx_stream_t stream) {
   // (NJ = keys per lane of the row phases, in units of 16.  3: 33-48 keys - the 41-key Electron-DOS cross attention - runs
   //  the softmax phases on 48 instead of 64 entries per row; the MFMA tiles stay 32 keys wide)
   const int nj = a.Nk <= 16 ? 1 : (a.Nk <= 48 ? attn_nj3() : (a.Nk <= 64 ? 4 : (a.Nk <= 208 ? 13 : 20)));
-#define DOSX_FWDS(NJ_, RES_)                                                                                \
+  const bool kp = a.key_ptr != nullptr;          // per-crystal key counts: the KP instantiations
+#define DOSX_FWDS1(NJ_, RES_, KP_)                                                                          \
   do {                                                                                                      \
     static bool attr_set = false;                                                                           \
     if (!attr_set) {                                                                                        \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_stream_kernel<NJ_, RES_>),          \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_stream_kernel<NJ_, RES_, KP_>),     \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                    \
       attr_set = true;                                                                                      \
     }                                                                                                       \
-    hipLaunchKernelGGL((attn_fwd_stream_kernel<NJ_, RES_>), grid, dim3(512), smem, to_stream(stream), a);   \
+    hipLaunchKernelGGL((attn_fwd_stream_kernel<NJ_, RES_, KP_>), grid, dim3(512), smem, to_stream(stream), a); \
   } while (0)
+#define DOSX_FWDS(NJ_, RES_) do { if (kp) DOSX_FWDS1(NJ_, RES_, true); else DOSX_FWDS1(NJ_, RES_, false); } while (0)
   if (nj == 1) { if (res) DOSX_FWDS(1, true); else DOSX_FWDS(1, false); }
   else if (nj == 3) { if (res) DOSX_FWDS(3, true); else DOSX_FWDS(3, false); }
   else if (nj == 4) { if (res) DOSX_FWDS(4, true); else DOSX_FWDS(4, false); }
   else if (nj == 13) DOSX_FWDS(13, false); else DOSX_FWDS(20, false);
 #undef DOSX_FWDS
+#undef DOSX_FWDS1
   DOSX_LAUNCH_CHECK();
   return 0;
 }
@@ -1380,7 +1410,6 @@ extern "C" int dosx_attention_bwd(const DosxAttn* ap, dosx_stream_t stream) {
   DOSX_CHECK_ARG(a.dout && a.dx && (a.dscores || pkv_ok(a)) && a.dkvhat && a.partials_q && a.partials_kv,
                  "dosx_attention_bwd: null operand");
   if (const int rc = dosx_detail::attn_aligned_bwd(a, to_stream(stream))) return rc < 0 ? rc : 0;
-  DOSX_CHECK_ARG(!a.key_ptr, "dosx_attention_bwd: key_ptr (per-crystal key counts) is a forward-only mode");
   if (a.Nk > MAX_FUSED_NK) return dosx_detail::attn_general_bwd(a, to_stream(stream));
   const Geo g = make_geo(a.H, a.Nk);
   const int kg = a.Nk > 32 ? 2 : 1;
@@ -1396,42 +1425,53 @@ extern "C" int dosx_attention_bwd(const DosxAttn* ap, dosx_stream_t stream) {
   DOSX_CHECK_ARG(s1 <= 160 * 1024 && s2 <= 160 * 1024, "dosx_attention_bwd: LDS need %zu/%zu > 160 KiB", s1, s2);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<1>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<1, false>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<2>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<2, false>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<1, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel<2, true>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set = true;
   }
   const dim3 grid(ceil_div(a.Sq, QT), a.Bq);
+  const bool kp = a.key_ptr != nullptr;          // per-crystal key counts: the KP instantiations
   if (!(a.flags & DOSX_ATTN_BWD_DKV_HALF)) {
     const int nj = a.Nk <= 16 ? 1 : (a.Nk <= 48 ? attn_nj3() : (a.Nk <= 64 ? 4 : (a.Nk <= 208 ? 13 : 20)));
-#define DOSX_DQS(NJ_, PKV_, RES_)                                                                           \
+#define DOSX_DQS1(NJ_, PKV_, RES_, KP_)                                                                     \
   do {                                                                                                      \
     static bool attr_dq = false;                                                                            \
     if (!attr_dq) {                                                                                         \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_stream_kernel<NJ_, PKV_, RES_>), \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_dq_stream_kernel<NJ_, PKV_, RES_, KP_>), \
                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                    \
       attr_dq = true;                                                                                       \
     }                                                                                                       \
-    hipLaunchKernelGGL((attn_bwd_dq_stream_kernel<NJ_, PKV_, RES_>), grid, dim3(512), s1, to_stream(stream), a); \
+    hipLaunchKernelGGL((attn_bwd_dq_stream_kernel<NJ_, PKV_, RES_, KP_>), grid, dim3(512), s1, to_stream(stream), a); \
   } while (0)
+#define DOSX_DQS(NJ_, PKV_, RES_) do { if (kp) DOSX_DQS1(NJ_, PKV_, RES_, true); else DOSX_DQS1(NJ_, PKV_, RES_, false); } while (0)
 #define DOSX_DQS2(NJ_, PKV_) do { if (res) DOSX_DQS(NJ_, PKV_, true); else DOSX_DQS(NJ_, PKV_, false); } while (0)
     if (pkv) { if (nj == 1) DOSX_DQS2(1, true); else if (nj == 3) DOSX_DQS2(3, true); else DOSX_DQS2(4, true); }
     else if (nj == 1) DOSX_DQS2(1, false); else if (nj == 3) DOSX_DQS2(3, false); else if (nj == 4) DOSX_DQS2(4, false); else if (nj == 13) DOSX_DQS(13, false, false);
     else DOSX_DQS(20, false, false);
 #undef DOSX_DQS2
 #undef DOSX_DQS
+#undef DOSX_DQS1
     DOSX_LAUNCH_CHECK();
   }
   if (fused) {
     // nothing else to launch
   } else if (!(a.flags & DOSX_ATTN_BWD_DQ_HALF) && pkv) {
-    hipLaunchKernelGGL(attn_dkv_reduce_kernel, dim3(ceil_div(a.Nk, DKR), a.Bk), dim3(256), 0, to_stream(stream), a,
-                       ceil_div(a.Sq, QT));
+    if (kp) hipLaunchKernelGGL(attn_dkv_reduce_kernel<true>, dim3(ceil_div(a.Nk, DKR), a.Bk), dim3(256), 0, to_stream(stream), a,
+                               ceil_div(a.Sq, QT));
+    else hipLaunchKernelGGL(attn_dkv_reduce_kernel<false>, dim3(ceil_div(a.Nk, DKR), a.Bk), dim3(256), 0, to_stream(stream), a,
+                            ceil_div(a.Sq, QT));
     DOSX_LAUNCH_CHECK();
   } else if (!(a.flags & DOSX_ATTN_BWD_DQ_HALF)) {
-    if (kg == 2) hipLaunchKernelGGL((attn_bwd_dkv_kernel<2>), dim3(ceil_div(a.Nk, 64), a.Bk), dim3(512), s2, to_stream(stream), a);
-    else hipLaunchKernelGGL((attn_bwd_dkv_kernel<1>), dim3(ceil_div(a.Nk, 32), a.Bk), dim3(512), s2, to_stream(stream), a);
+    if (kg == 2 && kp) hipLaunchKernelGGL((attn_bwd_dkv_kernel<2, true>), dim3(ceil_div(a.Nk, 64), a.Bk), dim3(512), s2, to_stream(stream), a);
+    else if (kg == 2) hipLaunchKernelGGL((attn_bwd_dkv_kernel<2, false>), dim3(ceil_div(a.Nk, 64), a.Bk), dim3(512), s2, to_stream(stream), a);
+    else if (kp) hipLaunchKernelGGL((attn_bwd_dkv_kernel<1, true>), dim3(ceil_div(a.Nk, 32), a.Bk), dim3(512), s2, to_stream(stream), a);
+    else hipLaunchKernelGGL((attn_bwd_dkv_kernel<1, false>), dim3(ceil_div(a.Nk, 32), a.Bk), dim3(512), s2, to_stream(stream), a);
     DOSX_LAUNCH_CHECK();
   }
   return 0;

@@ -166,7 +166,7 @@ __device__ __forceinline__ void al_kn_phase(const float* __restrict__ Ss, const 
 // ------------------------------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------------------------------
-template <int NG>
+template <int NG, bool KP>
 __global__ __launch_bounds__(512) void attn_al_fwd_kernel(const DosxAttn a, const AlGeo geo) {
   DOSX_SET_MAIN_PRIO();
   extern __shared__ __align__(16) float sm[];
@@ -175,7 +175,8 @@ __global__ __launch_bounds__(512) void attn_al_fwd_kernel(const DosxAttn a, cons
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q16 = lane & 15, l15 = q16, g4 = lane >> 4;
   const int wpc = geo.wpc, KS = geo.KS;
   const int bq = blockIdx.x / wpc, w = blockIdx.x - bq * wpc, bk = bq % a.Bk;
-  const int nk = a.key_ptr ? min(a.key_ptr[bk + 1] - a.key_ptr[bk], Nk) : Nk;      // keys this crystal attends over
+  const int nk = dosx_live_keys_fwd<KP>(a.key_ptr, bk, Nk);      // keys this crystal attends over (DosxAttn.key_ptr), else Nk
+  const int nctL = dosx_live_tiles<KP, 4>(nk, NkP >> 4);         // 16-key tiles with live keys: the others take no loads and no MFMAs
   const int nqt = (Sq + R - 1) / R;
   float* Ks = sm;                      // [NkP][LDK]
   float* Qs = Ks + NkP * LDK;          // [R][LDK]   q o g0 -> O
@@ -200,21 +201,21 @@ __global__ __launch_bounds__(512) void attn_al_fwd_kernel(const DosxAttn a, cons
   ASTAMP(0);
   float4 xr[NG], xn[NG];
   load_x(w, xr);
-  {   // the crystal's key rows -> Ks (rows beyond Nk zero), behind the first tile's rows
+  {   // the crystal's key rows -> Ks (rows beyond its nk keys zero, never fetched), behind the first tile's rows
     const int h4 = H >> 2;
     float4 kr[2 * NG];                 // NkP * h4 <= 64 * 16 NG = 2 NG float4 per thread
 #pragma unroll
     for (int i = 0; i < 2 * NG; ++i) {
       const int e = tid + 512 * i, j = e / h4, c = (e - j * h4) * 4;
-      kr[i] = (e < NkP * h4 && j < Nk) ? ld4(a.kvhat + ((size_t)j * a.Bk + bk) * H + c) : f4zero();
+      kr[i] = (e < NkP * h4 && j < (KP ? nk : Nk)) ? ld4(a.kvhat + ((size_t)j * a.Bk + bk) * H + c) : f4zero();
     }
 #pragma unroll
     for (int i = 0; i < 2 * NG; ++i) {
       const int e = tid + 512 * i, j = e / h4, c = (e - j * h4) * 4;
-      if (e < NkP * h4) st4(Ks + j * LDK + c, kr[i]);
+      if (e < 16 * nctL * h4) st4(Ks + j * LDK + c, kr[i]);
     }
   }
-  const int nctS = NkP >> 4, njobsS = (R / 16) * nctS, klen = H / KS;
+  const int nctS = nctL, njobsS = (R / 16) * nctS, klen = H / KS;       // (the score jobs: live key tiles only)
   for (int t = w; t < nqt; t += wpc) {
     const int s = min(t * R + lr, Sq - 1);
     const bool rv = (t * R + lr) < Sq;
@@ -276,7 +277,7 @@ __global__ __launch_bounds__(512) void attn_al_fwd_kernel(const DosxAttn a, cons
         v[jj] = e;
         sum += e;
       }
-      const float inv = 1.f / row16_sum(sum);
+      const float inv = dosx_softmax_inv<KP>(row16_sum(sum));
       const size_t prow = ((size_t)bq * Sq + s) * Nk;
       float ps = 0.f;
 #pragma unroll
@@ -285,20 +286,20 @@ __global__ __launch_bounds__(512) void attn_al_fwd_kernel(const DosxAttn a, cons
         if (j >= NkP) continue;
         float pm = 0.f;
         if (j < Nk) {
-          const float pr = v[jj] * inv;
-          pm = a.drop_mask ? pr * a.drop_mask[prow + j] : pr;
+          const float pr = v[jj] * inv;                // (0 beyond nk)
+          pm = (a.drop_mask && (!KP || j < nk)) ? pr * a.drop_mask[prow + j] : pr;
           if (rv) a.probs[prow + j] = pr;              // the un-dropped P (the backward reads it)
         }
-        Sr[j] = pm;                                    // (zeros beyond Nk: the padded keys of the second product)
+        Sr[j] = pm;                                    // (zeros beyond nk: the padded keys of the second product)
         ps += pm;
       }
-      psum = a.drop_mask ? row16_sum(ps) : 1.f;
+      psum = a.drop_mask ? row16_sum(ps) : dosx_psum_one<KP>(nk);
     }
     ASTAMP(so + 5);
     __syncthreads();
     ASTAMP(so + 6);
     // ---- D: O = (P o mask) . Ks -> Qs ----
-    al_kn_phase<NG, LDK>(Sc, Ks, Qs, NkP >> 4, wave, l15, g4);
+    al_kn_phase<NG, LDK>(Sc, Ks, Qs, nctL, wave, l15, g4);
     ASTAMP(so + 7);
     __syncthreads();
     ASTAMP(so + 8);
@@ -357,14 +358,15 @@ __global__ __launch_bounds__(512) void attn_al_fwd_kernel(const DosxAttn a, cons
 // <= 64 key rows at once (two per quarter-wave slot), key-side chain rule, dkvhat (+)=, and per group of 16 key rows the
 // [dgamma | dbeta] partial row (slots added in row order: the layout dosx_attention_bwd's dkv_part path documents).
 // Pp: [64][2 * 64 NG] floats of LDS.  Contains a barrier.
-template <int NG>
+template <int NG, bool KP>
 __device__ __forceinline__ void al_dkv_reduce(const DosxAttn& a, const int nqt, const int wpc, const int bk, float* __restrict__ Pp,
                                               const int tid) {
   constexpr int HP = 64 * NG, U = NG <= 2 ? 4 : 2;
   const int lane = tid & 63, q16 = lane & 15, slot = tid >> 4;                 // 32 slots
   constexpr int H = 64 * NG;
   const int Nk = a.Nk, rep = a.Bq / a.Bk, ngroups = (Nk + 15) / 16;
-  const int np = rep * wpc;
+  const int nk = dosx_live_keys<KP>(a.key_ptr, bk, Nk);  // (KP: a row past the crystal's own keys is no key - zeros)
+  const int np = (KP && slot >= nk) ? 0 : rep * wpc;     // (KP: neither of this slot's rows is a key - nothing to sum)
   const size_t pstride = (size_t)Nk * H;
   const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)a.dkv_part, 0, 0x7fffffff, 0x00020000);
   float4 g0[NG], d[2][NG], kh[2][NG], d0[2][NG];
@@ -375,13 +377,13 @@ __device__ __forceinline__ void al_dkv_reduce(const DosxAttn& a, const int nqt, 
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
     const int j = slot + 32 * p;
-    jv[p] = j < Nk;
+    jv[p] = j < nk;
     krow[p] = ((size_t)(jv[p] ? j : 0) * a.Bk + bk) * H;
 #pragma unroll
     for (int k = 0; k < NG; ++k) {
       const int c = q16 * 4 + 64 * k, cc = c < H ? c : 0;
-      kh[p][k] = ld4(a.kvhat + krow[p] + cc);
-      d0[p][k] = a.dkv_accumulate ? ld4(a.dkvhat + krow[p] + cc) : f4zero();
+      kh[p][k] = (!KP || jv[p]) ? ld4(a.kvhat + krow[p] + cc) : f4zero();
+      d0[p][k] = (a.dkv_accumulate && (!KP || jv[p])) ? ld4(a.dkvhat + krow[p] + cc) : f4zero();
       d[p][k] = f4zero();
     }
   }
@@ -396,7 +398,8 @@ __device__ __forceinline__ void al_dkv_reduce(const DosxAttn& a, const int nqt, 
 #pragma unroll
         for (int k = 0; k < NG; ++k) {
           const int c = q16 * 4 + 64 * k;
-          v[p][u][k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rP, (uint32_t)((off + (c < H ? c : 0)) * 4), 0, 16));   // sc1
+          v[p][u][k] = (KP && !jv[p]) ? f4zero()         // (no key: nothing was published for it, nothing is fetched)
+                                      : __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rP, (uint32_t)((off + (c < H ? c : 0)) * 4), 0, 16));   // sc1
         }
       }
 #pragma unroll
@@ -420,6 +423,10 @@ __device__ __forceinline__ void al_dkv_reduce(const DosxAttn& a, const int nqt, 
         st4(a.dkvhat + krow[p] + c, make_float4(d[p][k].x * g0[k].x + d0[p][k].x, d[p][k].y * g0[k].y + d0[p][k].y,
                                                 d[p][k].z * g0[k].z + d0[p][k].z, d[p][k].w * g0[k].w + d0[p][k].w));
       }
+      if constexpr (KP) {
+        if (!jv[p] && slot + 32 * p < Nk && c < H && !a.dkv_accumulate)
+          st4(a.dkvhat + ((size_t)(slot + 32 * p) * a.Bk + bk) * H + c, f4zero());
+      }
       st4(Pp + (slot + 32 * p) * 2 * HP + c, pg);
       st4(Pp + (slot + 32 * p) * 2 * HP + HP + c, pb);
     }
@@ -434,7 +441,7 @@ __device__ __forceinline__ void al_dkv_reduce(const DosxAttn& a, const int nqt, 
   }
 }
 
-template <int NG>
+template <int NG, bool KP>
 __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, const AlGeo geo) {
   DOSX_SET_MAIN_PRIO();
   extern __shared__ __align__(16) float sm[];
@@ -444,6 +451,8 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q16 = lane & 15, l15 = q16, g4 = lane >> 4;
   const int wpc = geo.wpc, KS = geo.KS;
   const int bq = blockIdx.x / wpc, w = blockIdx.x - bq * wpc, bk = bq % a.Bk;
+  const int nk = dosx_live_keys<KP>(a.key_ptr, bk, Nk);  // KP: the keys this crystal attends over (DosxAttn.key_ptr), else Nk
+  const int nctL = dosx_live_tiles<KP, 4>(nk, NkP >> 4); // 16-key tiles with live keys: the others take no loads and no MFMAs
   const int nqt = (Sq + R - 1) / R;
   float* Ks = sm;                      // [NkP][LDK]
   float* Os = Ks + NkP * LDK;          // [R][LDK]   dO rows
@@ -477,15 +486,15 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
 #pragma unroll
     for (int i = 0; i < 2 * NG; ++i) {
       const int e = tid + 512 * i, j = e / h4, c = (e - j * h4) * 4;
-      kr[i] = (e < NkP * h4 && j < Nk) ? ld4(a.kvhat + ((size_t)j * a.Bk + bk) * H + c) : f4zero();
+      kr[i] = (e < NkP * h4 && j < nk) ? ld4(a.kvhat + ((size_t)j * a.Bk + bk) * H + c) : f4zero();
     }
 #pragma unroll
     for (int i = 0; i < 2 * NG; ++i) {
       const int e = tid + 512 * i, j = e / h4, c = (e - j * h4) * 4;
-      if (e < NkP * h4) st4(Ks + j * LDK + c, kr[i]);
+      if (e < 16 * nctL * h4) st4(Ks + j * LDK + c, kr[i]);
     }
   }
-  const int nctS = NkP >> 4, njobsS = (R / 16) * nctS, klen = H / KS;
+  const int nctS = nctL, njobsS = (R / 16) * nctS, klen = H / KS;       // (dP, dq and key-gradient jobs: live key tiles only)
   constexpr int nct = H >> 4;
   f32x4 accK[NJW];
 #pragma unroll
@@ -512,9 +521,9 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
       const size_t prow = ((size_t)bq * Sq + s) * Nk;
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
-        const int j = q16 + 16 * jj, jc = j < Nk ? j : 0;
-        pr[jj] = a.probs[prow + jc];
-        mk[jj] = a.drop_mask ? a.drop_mask[prow + jc] : 1.f;
+        const int j = q16 + 16 * jj;
+        pr[jj] = dosx_key_entry<KP>(a.probs, prow, j, nk, Nk, 0.f);
+        mk[jj] = a.drop_mask ? dosx_key_entry<KP>(a.drop_mask, prow, j, nk, Nk, 1.f) : 1.f;
       }
     }
     // ---- a: dO -> Os (zeros beyond the data);  Ds = dO o g0;  cq = dO . b0 (dropout only) ----
@@ -548,12 +557,12 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
       for (int jj = 0; jj < 4; ++jj) {
         const int j = q16 + 16 * jj;
         float u = 0.f;
-        if (j < Nk) {
+        if (j < nk) {
           u = Sc[lr * 68 + j];
           if (KS > 1) u += Sc[R * 68 + lr * 68 + j];
         }
         if (a.drop_mask) u = (u + cq) * mk[jj];
-        if (j < Nk) dot += pr[jj] * u;
+        if (j < nk) dot += pr[jj] * u;
         dp[jj] = u;
       }
       dot = row16_sum(dot);
@@ -561,7 +570,7 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
       for (int jj = 0; jj < 4; ++jj) {
         const int j = q16 + 16 * jj;
         if (j >= NkP) continue;
-        const bool v = j < Nk && rv;
+        const bool v = j < nk && rv;
         Ss[lr * 68 + j] = v ? pr[jj] * (dp[jj] - dot) * scale : 0.f;
         Ps2[lr * 68 + j] = v ? pr[jj] * mk[jj] : 0.f;
       }
@@ -578,7 +587,7 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
     __syncthreads();
     ASTAMP(so + 6);
     // ---- d: dq = dS . Ks -> Ds ----
-    al_kn_phase<NG, LDK, (NG < 4)>(Ss, Ks, Ds, NkP >> 4, wave, l15, g4);
+    al_kn_phase<NG, LDK, (NG < 4)>(Ss, Ks, Ds, nctL, wave, l15, g4);
     ASTAMP(so + 7);
     __syncthreads();
     ASTAMP(so + 8);
@@ -663,7 +672,7 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
 #pragma unroll
       for (int i2 = 0; i2 < 4; ++i2) {
         const int j = 16 * jt + 4 * g4 + i2, col = 16 * ct + l15;
-        if (j < Nk) __hip_atomic_store(part + (size_t)j * H + col, accK[i][i2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sc1
+        if (j < (KP ? nk : Nk)) __hip_atomic_store(part + (size_t)j * H + col, accK[i][i2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sc1
       }
     }
   }
@@ -702,7 +711,7 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
   __syncthreads();                     // (the flag word is about to be overwritten by the reduction's LDS rows)
   if (last) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    al_dkv_reduce<NG>(a, nqt, wpc, bk, sm, tid);
+    al_dkv_reduce<NG, KP>(a, nqt, wpc, bk, sm, tid);
     if (tid == 0) __hip_atomic_store(a.dkv_cnt + bk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   ASTAMP(63);
@@ -763,21 +772,23 @@ int attn_aligned_fwd(const DosxAttn& a, hipStream_t st) {
   const size_t smem = al_fwd_smem(a, g);
   if (smem > 160 * 1024) return 0;
   const dim3 grid(a.Bq * g.wpc);
-#define DOSX_ALF(NG_)                                                                                                    \
+#define DOSX_ALF1(NG_, KP_)                                                                                              \
   do {                                                                                                                   \
     static bool attr_set = false;                                                                                        \
     if (!attr_set) {                                                                                                     \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_al_fwd_kernel<NG_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_al_fwd_kernel<NG_, KP_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
       attr_set = true;                                                                                                   \
     }                                                                                                                    \
-    hipLaunchKernelGGL((attn_al_fwd_kernel<NG_>), grid, dim3(512), smem, st, a, g);                                      \
+    hipLaunchKernelGGL((attn_al_fwd_kernel<NG_, KP_>), grid, dim3(512), smem, st, a, g);                                 \
   } while (0)
+#define DOSX_ALF(NG_) do { if (a.key_ptr) DOSX_ALF1(NG_, true); else DOSX_ALF1(NG_, false); } while (0)
   switch (ceil_div(a.H, 64)) {
     case 1: DOSX_ALF(1); break;
     case 2: DOSX_ALF(2); break;
     default: DOSX_ALF(4);
   }
 #undef DOSX_ALF
+#undef DOSX_ALF1
   DOSX_LAUNCH_CHECK();
   return 1;
 }
@@ -789,21 +800,23 @@ int attn_aligned_bwd(const DosxAttn& a, hipStream_t st) {
   const size_t smem = al_bwd_smem(a);
   if (smem > 160 * 1024 || (size_t)a.Bq * ceil_div(a.Sq, R) * a.Nk * a.H * 4 >= 0x7fffffffull) return 0;
   const dim3 grid(a.Bq * g.wpc);
-#define DOSX_ALB(NG_)                                                                                                    \
+#define DOSX_ALB1(NG_, KP_)                                                                                              \
   do {                                                                                                                   \
     static bool attr_set = false;                                                                                        \
     if (!attr_set) {                                                                                                     \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_al_bwd_kernel<NG_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_al_bwd_kernel<NG_, KP_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
       attr_set = true;                                                                                                   \
     }                                                                                                                    \
-    hipLaunchKernelGGL((attn_al_bwd_kernel<NG_>), grid, dim3(512), smem, st, a, g);                                      \
+    hipLaunchKernelGGL((attn_al_bwd_kernel<NG_, KP_>), grid, dim3(512), smem, st, a, g);                                 \
   } while (0)
+#define DOSX_ALB(NG_) do { if (a.key_ptr) DOSX_ALB1(NG_, true); else DOSX_ALB1(NG_, false); } while (0)
   switch (ceil_div(a.H, 64)) {
     case 1: DOSX_ALB(1); break;
     case 2: DOSX_ALB(2); break;
     default: DOSX_ALB(4);
   }
 #undef DOSX_ALB
+#undef DOSX_ALB1
   DOSX_LAUNCH_CHECK();
   return 1;
 }

@@ -60,24 +60,26 @@ __global__ __launch_bounds__(256) void attn_general_fwd_kernel(const DosxAttn a)
   if (a.qstats && lane == 0) { a.qstats[2 * row] = qr.mean; a.qstats[2 * row + 1] = qr.rstd; }
   float* pr = a.probs + ((size_t)bq * a.Sq + s) * Nk;
   const float* mk = a.drop_mask ? a.drop_mask + ((size_t)bq * a.Sq + s) * Nk : nullptr;
+  const int nk = (a.key_ptr ? dosx_live_keys<true>(a.key_ptr, bk, Nk) : Nk);        // the crystal's own keys (DosxAttn.key_ptr): every loop ends there
   // scores: lane (j % 64) owns key j (it writes and re-reads pr[j] itself)
   float mymax = -INFINITY;
-  for (int j = 0; j < Nk; ++j) {
+  for (int j = 0; j < nk; ++j) {
     const float4 kh = on ? ld4(a.kvhat + ((size_t)j * a.Bk + bk) * H + c) : f4zero();
     const float t = wave_sum(on ? f4dot(qr.q, affine(kh, g, b)) : 0.f) * scale;
     if (lane == (j & 63)) { pr[j] = t; mymax = fmaxf(mymax, t); }
   }
   const float m = wave_max(mymax);
   float mysum = 0.f;
-  for (int j = lane; j < Nk; j += 64) { const float e = expf(pr[j] - m); pr[j] = e; mysum += e; }
-  const float inv = 1.f / wave_sum(mysum);
-  for (int j = lane; j < Nk; j += 64) pr[j] *= inv;
+  for (int j = lane; j < nk; j += 64) { const float e = expf(pr[j] - m); pr[j] = e; mysum += e; }
+  const float inv = dosx_softmax_inv<true>(wave_sum(mysum));
+  for (int j = lane; j < nk; j += 64) pr[j] *= inv;
+  for (int j = nk + lane; j < Nk; j += 64) pr[j] = 0.f;
   // out = sum_j (P o M)[j] K[j]  (+ x)
   float4 acc = f4zero();
-  for (int j0 = 0; j0 < Nk; j0 += 64) {
+  for (int j0 = 0; j0 < nk; j0 += 64) {
     const int jl = j0 + lane;
-    const float w = jl < Nk ? (mk ? pr[jl] * mk[jl] : pr[jl]) : 0.f;
-    const int nj = min(64, Nk - j0);
+    const float w = jl < nk ? (mk ? pr[jl] * mk[jl] : pr[jl]) : 0.f;
+    const int nj = min(64, nk - j0);
     for (int jj = 0; jj < nj; ++jj) {
       const float wj = lane_bcast(w, jj);
       const float4 kh = on ? ld4(a.kvhat + ((size_t)(j0 + jj) * a.Bk + bk) * H + c) : f4zero();
@@ -105,6 +107,7 @@ __global__ __launch_bounds__(512) void attn_general_dq_kernel(const DosxAttn a) 
   const float scale = 1.f / sqrtf((float)H);
   const float4 g = on ? ld4(a.gamma0 + c) : f4zero(), b = on ? ld4(a.beta0 + c) : f4zero();
   float4 pg = f4zero(), pb = f4zero();
+  const int nk = (a.key_ptr ? dosx_live_keys<true>(a.key_ptr, bk, Nk) : Nk);        // the crystal's own keys (DosxAttn.key_ptr): every loop ends there
   for (int i = 0; i < 4; ++i) {
     const int s = (int)blockIdx.x * TR + wave * 4 + i;
     if (s >= a.Sq) break;
@@ -116,7 +119,7 @@ __global__ __launch_bounds__(512) void attn_general_dq_kernel(const DosxAttn a) 
     float* ds = a.dscores + ((size_t)bq * a.Sq + s) * Nk;
     // dP o M (owner lane keeps it in dscores), t = sum_j (dP o M)[j] P[j]
     float myt = 0.f;
-    for (int j = 0; j < Nk; ++j) {
+    for (int j = 0; j < nk; ++j) {
       const float4 kh = on ? ld4(a.kvhat + ((size_t)j * a.Bk + bk) * H + c) : f4zero();
       const float dp = wave_sum(on ? f4dot(dout, affine(kh, g, b)) : 0.f);
       if (lane == (j & 63)) {
@@ -126,13 +129,14 @@ __global__ __launch_bounds__(512) void attn_general_dq_kernel(const DosxAttn a) 
       }
     }
     const float t = wave_sum(myt);
-    for (int j = lane; j < Nk; j += 64) ds[j] = scale * pr[j] * (ds[j] - t);       // dS (multihead_attention.py:68-70 backwards)
+    for (int j = lane; j < nk; j += 64) ds[j] = scale * pr[j] * (ds[j] - t);       // dS (multihead_attention.py:68-70 backwards)
+    for (int j = nk + lane; j < Nk; j += 64) ds[j] = 0.f;
     // dq = sum_j dS[j] K[j]
     float4 dq = f4zero();
-    for (int j0 = 0; j0 < Nk; j0 += 64) {
+    for (int j0 = 0; j0 < nk; j0 += 64) {
       const int jl = j0 + lane;
-      const float w = jl < Nk ? ds[jl] : 0.f;
-      const int nj = min(64, Nk - j0);
+      const float w = jl < nk ? ds[jl] : 0.f;
+      const int nj = min(64, nk - j0);
       for (int jj = 0; jj < nj; ++jj) {
         const float wj = lane_bcast(w, jj);
         const float4 kh = on ? ld4(a.kvhat + ((size_t)(j0 + jj) * a.Bk + bk) * H + c) : f4zero();
@@ -174,9 +178,14 @@ __global__ __launch_bounds__(512) void attn_general_dkv_kernel(const DosxAttn a)
   const bool on = c < H;
   const float4 g = on ? ld4(a.gamma0 + c) : f4zero(), b = on ? ld4(a.beta0 + c) : f4zero();
   float4 pg = f4zero(), pb = f4zero();
+  const int nk = (a.key_ptr ? dosx_live_keys<true>(a.key_ptr, bk, Nk) : Nk);        // rows past the crystal's own keys: no reads, zero gradient
   for (int i = 0; i < 4; ++i) {
     const int j = (int)blockIdx.x * TR + wave * 4 + i;
     if (j >= Nk) break;
+    if (j >= nk) {
+      if (on && !a.dkv_accumulate) st4(a.dkvhat + ((size_t)j * a.Bk + bk) * H + c, f4zero());
+      continue;
+    }
     float4 dk = f4zero();
     for (int bq = bk; bq < a.Bq; bq += a.Bk)
       for (int s = 0; s < a.Sq; ++s) {

@@ -118,6 +118,52 @@ __device__ __forceinline__ float f4get(const float4& v, int i) {
   return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w;
 }
 
+// Live keys of key crystal bk (DosxAttn.key_ptr / DosxFfn.att_key_ptr / DosxFfnBwd.att_key_ptr): the crystal's own count clamped
+// to [0, Nk] with KP, all Nk without.  Uniform over a workgroup that serves one crystal.
+// The MFMA kernels take the per-crystal counts as a TEMPLATE flag KP (the host picks the instantiation by key_ptr != NULL): with
+// KP = false the count IS Nk and every helper below compiles to the code these kernels had before the counts existed - the
+// unflagged step keeps its registers and its instruction stream.
+template <bool KP>
+__device__ __forceinline__ int dosx_live_keys(const int32_t* key_ptr, int bk, int Nk) {
+  if constexpr (KP) return min(max(key_ptr[bk + 1] - key_ptr[bk], 0), Nk);
+  else return Nk;
+}
+// The forward kernels' count.  The host launches the KP instantiation whenever key_ptr is given, so in the KP = false
+// instantiation key_ptr is always NULL and the branch below is NEVER TAKEN: it is the expression those kernels carried before
+// the flag became a template parameter, kept because their measured register allocation (no scratch at 255-256 VGPRs in
+// ffn_fwd_multi_kernel) is the one the compiler finds with it.  Nothing else may rely on it.
+template <bool KP>
+__device__ __forceinline__ int dosx_live_keys_fwd(const int32_t* key_ptr, int bk, int Nk) {
+  if constexpr (KP) return min(max(key_ptr[bk + 1] - key_ptr[bk], 0), Nk);
+  else return key_ptr ? min(key_ptr[bk + 1] - key_ptr[bk], Nk) : Nk;
+}
+// Entry j of row `row0` (an element offset) of probs / drop_mask [.., Nk].  KP: nothing at j >= nk is read, `other` stands in;
+// else the clamped load of the unflagged kernels (an entry past Nk reads entry 0 and is masked by its consumer).
+template <bool KP>
+__device__ __forceinline__ float dosx_key_entry(const float* base, size_t row0, int j, int nk, int Nk, float other) {
+  if constexpr (KP) return j < nk ? base[row0 + j] : other;
+  else return base[row0 + (j < Nk ? j : 0)];
+}
+// 1 / s of a softmax denominator; KP: a crystal without keys (s == 0: every exponential was masked) gets all-zero probabilities
+template <bool KP>
+__device__ __forceinline__ float dosx_softmax_inv(float s) {
+  if constexpr (KP) return s > 0.f ? 1.f / s : 0.f;
+  else return 1.f / s;
+}
+// 16-key (SH = 4) / 32-key (SH = 5) tiles that hold live keys: the tile loops of the KP instantiations end here - a tile wholly
+// past the crystal's count takes no MFMA work and no key loads; without KP the padded key set's tile count `all`
+template <bool KP, int SH>
+__device__ __forceinline__ int dosx_live_tiles(int nk, int all) {
+  if constexpr (KP) return (nk + (1 << SH) - 1) >> SH;
+  else return all;
+}
+// sum of a row of P without dropout: 1 - or 0 for a crystal without keys
+template <bool KP>
+__device__ __forceinline__ float dosx_psum_one(int nk) {
+  if constexpr (KP) return nk > 0 ? 1.f : 0.f;
+  else return 1.f;
+}
+
 // Row statistics of a row held as `per` float4 per lane of one wave (whole row over 64 lanes).
 // Two-pass (mean, then centred second moment) like torch's LayerNorm; eps = 1e-5.
 #define DOSX_LN_EPS 1e-5f

@@ -37,6 +37,7 @@ constexpr int FBN = 128;         // columns per chunk / per column block
 // One query row of the fused attention prologue (ffn_fwd_kernel<.., ATT = true>), by one QUARTER wave: lane q16 owns the
 // float4 columns 4 q16 + 64 k (k < 2: H <= 128).  Writes probs / qstats / x1 / st1 of row m0 + lr and the LN1-normalised row
 // into the Xs tile.
+template <bool KP>
 __device__ __forceinline__ void ffn_att_row(const DosxFfn& a, float* __restrict__ Xs, const int LDX, const int lr, const int m0,
                                             const int lane) {
   const int H = a.H, M = a.M;
@@ -56,7 +57,7 @@ __device__ __forceinline__ void ffn_att_row(const DosxFfn& a, float* __restrict_
     const int r = m0 + lr, rc = min(r, M - 1);
     const bool rv = r < M;
     const int s = rc / Bq, bq = rc - s * Bq, bk = bq % Bk;
-    const int nk = a.att_key_ptr ? min(a.att_key_ptr[bk + 1] - a.att_key_ptr[bk], Nk) : Nk;      // keys this crystal attends over (DosxFfn.att_key_ptr)
+    const int nk = dosx_live_keys_fwd<KP>(a.att_key_ptr, bk, Nk);      // keys this crystal attends over (DosxFfn.att_key_ptr), else Nk
     const float* xrow = a.x + ((size_t)s * a.att_qs + (size_t)bq * a.att_qb) * a.ldx;
     float4 xr[2];
     float t = 0.f;
@@ -71,7 +72,7 @@ __device__ __forceinline__ void ffn_att_row(const DosxFfn& a, float* __restrict_
     for (int j = 0; j < 16; ++j) {
       const float* kr = a.att_kvhat + ((size_t)(j < Nk ? j : 0) * Bk + bk) * H;
 #pragma unroll
-      for (int k = 0; k < 2; ++k) kv[j][k] = on[k] ? ld4(kr + q16 * 4 + 64 * k) : f4zero();
+      for (int k = 0; k < 2; ++k) kv[j][k] = (on[k] && (!KP || j < nk)) ? ld4(kr + q16 * 4 + 64 * k) : f4zero();
     }
     const float mean = row16_sum(t) * invH;
     t = 0.f;
@@ -108,14 +109,14 @@ __device__ __forceinline__ void ffn_att_row(const DosxFfn& a, float* __restrict_
       sc[j] = e;
       sum += e;
     }
-    const float inv = 1.f / sum;
+    const float inv = dosx_softmax_inv<KP>(sum);
     const size_t prow = ((size_t)bq * Sq + s) * Nk;
     float psum = 0.f;
     float4 o[2] = {f4zero(), f4zero()};
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
-      const float pr = sc[j] * inv;                                   // 0 beyond Nk
-      const float mk = (a.att_mask && j < Nk) ? a.att_mask[prow + j] : 1.f;
+      const float pr = sc[j] * inv;                                   // 0 beyond nk
+      const float mk = (a.att_mask && j < (KP ? nk : Nk)) ? a.att_mask[prow + j] : 1.f;
       const float pm = pr * mk;
       psum += pm;
 #pragma unroll
@@ -124,7 +125,7 @@ __device__ __forceinline__ void ffn_att_row(const DosxFfn& a, float* __restrict_
       }
       if (rv && q16 == j && j < Nk) a.att_probs[prow + j] = pr;       // the un-dropped P (the backward reads it)
     }
-    if (!a.att_mask) psum = 1.f;
+    if (!a.att_mask) psum = dosx_psum_one<KP>(nk);
     float4 x1[2];
     t = 0.f;
 #pragma unroll
@@ -170,13 +171,14 @@ __device__ __forceinline__ void ffn_att_row(const DosxFfn& a, float* __restrict_
 //   E: one quarter wave per row - x1 = O o g0 + b0 sum(P) + x, both statistics, LN1(x1) -> Xs
 // All 8 waves run it (R = 32: four rows per wave, one pass; the staging waves have their first weight chunks in flight); four
 // workgroup barriers inside, the caller adds the one that frees the key / score region.
-template <int R>
+template <int R, bool KP>
 __device__ __forceinline__ void ffn_att_tile(const DosxFfn& a, float* __restrict__ Xs, const int LDX, float* __restrict__ Ks,
                                              float* __restrict__ Sc, float* __restrict__ Qs, const int al_s0, const int al_bq,
                                              const int tid) {
   const int H = a.H, LDK = a.H + 4;
   const int lane = tid & 63, wave = tid >> 6, q16 = lane & 15, l15 = lane & 15, g4 = lane >> 4;
   const int Nk = a.att_Nk, NkP = (Nk + 15) & ~15, Sq = a.att_Sq;
+  const int nk0 = dosx_live_keys<KP>(a.att_key_ptr, al_bq % a.att_Bk, Nk); // KP: the keys this crystal attends over (DosxFfn.att_key_ptr), else Nk
   const float scale = rsqrtf((float)H), invH = 1.f / (float)H;
   // this quarter wave's row (R = 16: waves 0-3 only)
   const int lr = wave * 4 + g4;
@@ -197,19 +199,19 @@ __device__ __forceinline__ void ffn_att_tile(const DosxFfn& a, float* __restrict
       g1[k] = ld4(a.gamma + cc); bb1[k] = ld4(a.beta + cc);
       xr[k] = on[k] ? ld4(xrow + c) : f4zero();
     }
-    {   // the crystal's key rows -> Ks (all 8 waves; rows beyond Nk zero): requested right behind the row operands above
+    {   // the crystal's key rows -> Ks (all 8 waves; rows beyond its nk keys zero, never fetched): requested right behind the row operands above
       const int bk = al_bq % a.att_Bk, h4 = H >> 2;
       const UDiv dh4(h4);
       float4 kr[4];                                  // NkP * h4 <= 64 * 32 = 4 float4 per thread
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int e = tid + 512 * i, j = dh4.div(e), c = (e - j * h4) * 4;
-        kr[i] = (e < NkP * h4 && j < Nk) ? ld4(a.att_kvhat + ((size_t)j * a.att_Bk + bk) * H + c) : f4zero();
+        kr[i] = (e < NkP * h4 && j < nk0) ? ld4(a.att_kvhat + ((size_t)j * a.att_Bk + bk) * H + c) : f4zero();
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int e = tid + 512 * i, j = dh4.div(e), c = (e - j * h4) * 4;
-        if (e < NkP * h4) st4(Ks + j * LDK + c, kr[i]);
+        if (e < 16 * dosx_live_tiles<KP, 4>(nk0, NkP >> 4) * h4) st4(Ks + j * LDK + c, kr[i]);
       }
     }
     float t = 0.f;
@@ -246,10 +248,12 @@ __device__ __forceinline__ void ffn_att_tile(const DosxFfn& a, float* __restrict
   while (KS > 1 && ((H % (16 * KS)) != 0 || LDK + (KS - 1) * 68 > 4 * H + 4)) KS >>= 1;   // (whole 16-wide MFMA steps; the partial tiles fit the T region)
   const int klen = H / KS;
   const UDiv dKS(KS);
+  // (per-crystal counts: the jobs of the 16-key tiles with live keys only - KS stays the padded key set's, it sizes the LDS)
+  const int nctL = dosx_live_tiles<KP, 4>(nk0, nctS), njobsL = (R / 16) * nctL;
   {
-    for (int unit = wave; unit < njobsS * KS; unit += 8) {
+    for (int unit = wave; unit < njobsL * KS; unit += 8) {
       const int job = dKS.div(unit), kq = unit - job * KS;
-      const int rt = job >= nctS ? job / nctS : 0, ct = job - rt * nctS;
+      const int rt = job >= nctL ? job / nctL : 0, ct = job - rt * nctL;
       const f32x4 acc = mma_kk<8>(Qs + (16 * rt + l15) * LDK + kq * klen + 4 * g4, Ks + (16 * ct + l15) * LDK + kq * klen + 4 * g4, klen >> 4);
       float* Sp = kq == 0 ? Sc : Qs + R * LDK + (kq - 1) * R * 68;      // (partials 1 .. KS - 1 behind the Q tile, in the T region)
 #pragma unroll
@@ -261,7 +265,7 @@ __device__ __forceinline__ void ffn_att_tile(const DosxFfn& a, float* __restrict
   // ---- C: softmax of this quarter wave's row (over the crystal's own nk <= Nk keys with DosxFfn.att_key_ptr) ----
   float psum = 1.f;
   const int bk_ = al_bq % a.att_Bk;
-  const int nk = a.att_key_ptr ? min(a.att_key_ptr[bk_ + 1] - a.att_key_ptr[bk_], Nk) : Nk;
+  const int nk = KP ? nk0 : dosx_live_keys_fwd<KP>(a.att_key_ptr, bk_, Nk);
   if (rowok) {
     float* Sr = Sc + lr * 68;
     float v[4], mx = -INFINITY;
@@ -283,7 +287,7 @@ __device__ __forceinline__ void ffn_att_tile(const DosxFfn& a, float* __restrict
       v[jj] = e;
       sum += e;
     }
-    const float inv = 1.f / row16_sum(sum);
+    const float inv = dosx_softmax_inv<KP>(row16_sum(sum));
     const size_t prow = ((size_t)al_bq * Sq + s) * Nk;
     float ps = 0.f;
 #pragma unroll
@@ -293,13 +297,13 @@ __device__ __forceinline__ void ffn_att_tile(const DosxFfn& a, float* __restrict
       float pm = 0.f;
       if (j < Nk) {
         const float pr = v[jj] * inv;
-        pm = a.att_mask ? pr * a.att_mask[prow + j] : pr;
+        pm = (a.att_mask && (!KP || j < nk)) ? pr * a.att_mask[prow + j] : pr;
         if (rv) a.att_probs[prow + j] = pr;            // the un-dropped P (the backward reads it)
       }
       Sr[j] = pm;                                      // (zeros beyond Nk: the padded keys of the second product)
       ps += pm;
     }
-    psum = a.att_mask ? row16_sum(ps) : 1.f;
+    psum = a.att_mask ? row16_sum(ps) : dosx_psum_one<KP>(nk);
   }
   FSTAMP(13);
   __syncthreads();
@@ -309,7 +313,7 @@ __device__ __forceinline__ void ffn_att_tile(const DosxFfn& a, float* __restrict
     const UDiv dnct(nct);
     for (int job = wave; job < njobs; job += 8) {
       const int rt = dnct.div(job), ct = job - rt * nct;
-      const f32x4 acc = mma_kn<4>(Sc + (16 * rt + l15) * 68 + 4 * g4, Ks + (4 * g4) * LDK + 16 * ct + l15, LDK, NkP >> 4);
+      const f32x4 acc = mma_kn<4>(Sc + (16 * rt + l15) * 68 + 4 * g4, Ks + (4 * g4) * LDK + 16 * ct + l15, LDK, nctL);
 #pragma unroll
       for (int i = 0; i < 4; ++i) Qs[(16 * rt + 4 * g4 + i) * LDK + 16 * ct + l15] = acc[i];
     }
@@ -372,8 +376,11 @@ __device__ __forceinline__ void ffn_att_tile(const DosxFfn& a, float* __restrict
 // rows are copied to LDS once (into the stage-buffer region, which the weight chunks take over after the prologue) - the 51-key
 // self attention and the 32-row launches, where the per-row global key fetch of ATT = 1 does not pay, take this form while the
 // grid stays one round of workgroups.
-template <bool HALF, int KB, int ATT>
+template <bool HALF, int KB, int ATTK>
 __device__ __forceinline__ void ffn_fwd_body(const DosxFfn& a, float* __restrict__ sm) {
+  // ATTK = ATT, or ATT + 2 with per-crystal key counts (DosxFfn.att_key_ptr: the KP forms of the attention prologue)
+  constexpr int ATT = ATTK >= 3 ? ATTK - 2 : ATTK;
+  constexpr bool KP = ATTK >= 3;
   constexpr int FBK = KB, FLDW = KB + 4;           // chunk width, padded row of a staged weight chunk
   constexpr int R = HALF ? 16 : 32;                // rows per workgroup
   constexpr int ER = R / 8;                        // epilogue rows per wave
@@ -466,7 +473,7 @@ __device__ __forceinline__ void ffn_fwd_body(const DosxFfn& a, float* __restrict
     issue(r0, 0);
     issue(r1, 1);
     if constexpr (ATT == 2) {
-      ffn_att_tile<R>(a, Xs, LDX, attKs, attSc, T, al_s0, al_bq, tid);
+      ffn_att_tile<R, KP>(a, Xs, LDX, attKs, attSc, T, al_s0, al_bq, tid);
       __syncthreads();                             // the attention prologue is done with the keys / scores in the stage buffers
     }
     store(ST, r0);
@@ -499,13 +506,13 @@ __device__ __forceinline__ void ffn_fwd_body(const DosxFfn& a, float* __restrict
       b1r[cb][1] = HALF ? a.b1[col + 16] : 0.f;
     }
     if constexpr (ATT == 2) {
-      ffn_att_tile<R>(a, Xs, LDX, attKs, attSc, T, al_s0, al_bq, tid);
+      ffn_att_tile<R, KP>(a, Xs, LDX, attKs, attSc, T, al_s0, al_bq, tid);
       __syncthreads();                             // keys / scores dead: the staging waves may store the first weight chunk
     } else if constexpr (ATT == 1) {
       // 16 rows per pass over the 4 matrix waves.  (All 8 waves in one pass - the staging waves taking rows 16-31 while their
       // first weight chunks are in flight - was built and spills: the 16 x 2 float4 key registers next to the staged chunks.)
 #pragma unroll
-      for (int p = 0; p < R / 16; ++p) ffn_att_row(a, Xs, LDX, p * 16 + wave * 4 + (lane >> 4), m0, lane);
+      for (int p = 0; p < R / 16; ++p) ffn_att_row<KP>(a, Xs, LDX, p * 16 + wave * 4 + (lane >> 4), m0, lane);
     } else {   // LN1(x) tile -> Xs  (row r = tid/8, 4-float groups tid%8 + 8 i)
       const int r = tid >> 3, rr = growc(min(r, R - 1));
       const float mean = a.stats[2 * (size_t)rr], rstd = a.stats[2 * (size_t)rr + 1];
@@ -758,10 +765,12 @@ struct AttBwdSm {
 // (query batch entry, tile) order, key-side chain rule, dkvhat (+)=, and per group of 16 key rows the [dg0 | db0] partial row,
 // slots added in row order - the arithmetic and orders of attention.hip's dkv_reduce_group.  Pp: [64][256] floats of LDS.
 // Contains a barrier.
+template <bool KP>
 __device__ __forceinline__ void ffn_dkv_reduce(const DosxFfnBwd& a, const int nqt, const int bk, float* __restrict__ Pp, const int tid) {
   const int lane = tid & 63, q16 = lane & 15, slot = tid >> 4;                 // 32 slots
   const int H = a.H, Nk = a.att_Nk, rep = a.att_Bq / a.att_Bk, ngroups = (Nk + 15) / 16;
-  const int np = rep * nqt;
+  const int nk = dosx_live_keys<KP>(a.att_key_ptr, bk, Nk);  // (KP: a row past the crystal's own keys is no key - zeros)
+  const int np = (KP && slot >= nk) ? 0 : rep * nqt;     // (KP: neither of this slot's rows is a key - nothing to sum)
   const UDiv dnqt(nqt);
   const size_t pstride = (size_t)Nk * H;
   const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)a.att_dkv_part, 0, 0x7fffffff, 0x00020000);
@@ -773,13 +782,13 @@ __device__ __forceinline__ void ffn_dkv_reduce(const DosxFfnBwd& a, const int nq
 #pragma unroll
   for (int p = 0; p < 2; ++p) {
     const int j = slot + 32 * p;
-    jv[p] = j < Nk;
+    jv[p] = j < nk;
     krow[p] = ((size_t)(jv[p] ? j : 0) * a.att_Bk + bk) * H;
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int c = q16 * 4 + 64 * k, cc = c < H ? c : 0;
-      kh[p][k] = ld4(a.att_kvhat + krow[p] + cc);
-      d0[p][k] = a.att_dkv_accumulate ? ld4(a.att_dkvhat + krow[p] + cc) : f4zero();
+      kh[p][k] = (!KP || jv[p]) ? ld4(a.att_kvhat + krow[p] + cc) : f4zero();
+      d0[p][k] = (a.att_dkv_accumulate && (!KP || jv[p])) ? ld4(a.att_dkvhat + krow[p] + cc) : f4zero();
       d[p][k] = f4zero();
     }
   }
@@ -794,7 +803,8 @@ __device__ __forceinline__ void ffn_dkv_reduce(const DosxFfnBwd& a, const int nq
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
           const int c = q16 * 4 + 64 * k;
-          v[p][u][k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rP, (uint32_t)((off + (c < H ? c : 0)) * 4), 0, 16));   // sc1
+          v[p][u][k] = (KP && !jv[p]) ? f4zero()         // (no key: nothing was published for it, nothing is fetched)
+                                      : __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rP, (uint32_t)((off + (c < H ? c : 0)) * 4), 0, 16));   // sc1
         }
       }
 #pragma unroll
@@ -818,6 +828,10 @@ __device__ __forceinline__ void ffn_dkv_reduce(const DosxFfnBwd& a, const int nq
         st4(a.att_dkvhat + krow[p] + c, make_float4(d[p][k].x * g0[k].x + d0[p][k].x, d[p][k].y * g0[k].y + d0[p][k].y,
                                                     d[p][k].z * g0[k].z + d0[p][k].z, d[p][k].w * g0[k].w + d0[p][k].w));
       }
+      if constexpr (KP) {
+        if (!jv[p] && slot + 32 * p < Nk && c < H && !a.att_dkv_accumulate)
+          st4(a.att_dkvhat + ((size_t)(slot + 32 * p) * a.att_Bk + bk) * H + c, f4zero());
+      }
       st4(Pp + (slot + 32 * p) * 256 + c, pg);
       st4(Pp + (slot + 32 * p) * 256 + 128 + c, pb);
     }
@@ -839,7 +853,7 @@ struct AttBwdRegs {
   float4 g0[2], b0[2], xr[2], kr[4];
   float mean, rstd, pr[4], mk[4];
 };
-template <int R>
+template <int R, bool KP>
 __device__ __forceinline__ void ffn_att_bwd_prefetch(const DosxFfnBwd& a, AttBwdRegs& q, const int al_s0, const int al_bq, const int tid) {
   const int H = a.H, lane = tid & 63, wave = tid >> 6, q16 = lane & 15, g4 = lane >> 4;
   const int Nk = a.att_Nk, NkP = (Nk + 15) & ~15, Sq = a.att_Sq, bk = al_bq % a.att_Bk;
@@ -855,27 +869,29 @@ __device__ __forceinline__ void ffn_att_bwd_prefetch(const DosxFfnBwd& a, AttBwd
   }
   q.mean = a.att_qstats[2 * orow]; q.rstd = a.att_qstats[2 * orow + 1];
   const size_t prow_ = ((size_t)al_bq * Sq + s) * Nk;
+  const int nk = dosx_live_keys<KP>(a.att_key_ptr, bk, Nk);  // KP: the keys this crystal attends over (DosxFfnBwd.att_key_ptr), else Nk
 #pragma unroll
   for (int jj = 0; jj < 4; ++jj) {
-    const int j = q16 + 16 * jj, jc = j < Nk ? j : 0;
-    q.pr[jj] = a.att_probs[prow_ + jc];
-    q.mk[jj] = a.att_mask ? a.att_mask[prow_ + jc] : 1.f;
+    const int j = q16 + 16 * jj;
+    q.pr[jj] = dosx_key_entry<KP>(a.att_probs, prow_, j, nk, Nk, 0.f);
+    q.mk[jj] = a.att_mask ? dosx_key_entry<KP>(a.att_mask, prow_, j, nk, Nk, 1.f) : 1.f;
   }
   const int h4 = H >> 2;
   const UDiv dh4(h4);
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int e = tid + 512 * i, j = dh4.div(e), c = (e - j * h4) * 4;
-    q.kr[i] = (e < NkP * h4 && j < Nk) ? ld4(a.att_kvhat + ((size_t)j * a.att_Bk + bk) * H + c) : f4zero();
+    q.kr[i] = (e < NkP * h4 && j < nk) ? ld4(a.att_kvhat + ((size_t)j * a.att_Bk + bk) * H + c) : f4zero();
   }
 }
 
-template <int R>
+template <int R, bool KP>
 __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __restrict__ sm, const AttBwdSm& L, const AttBwdRegs& q,
                                                  const int al_s0, const int al_bq, const int tile, const int nqt, const int tid) {
   const int H = a.H, LDK = a.H + 4;
   const int lane = tid & 63, wave = tid >> 6, q16 = lane & 15, l15 = lane & 15, g4 = lane >> 4;
   const int Nk = a.att_Nk, NkP = (Nk + 15) & ~15, Sq = a.att_Sq, bk = al_bq % a.att_Bk;
+  const int nk = dosx_live_keys<KP>(a.att_key_ptr, bk, Nk);  // (workgroup-uniform: the tile's rows share one key crystal)
   const float scale = rsqrtf((float)H), invH = 1.f / (float)H;
   const int lr = wave * 4 + g4;                        // this quarter wave's row (R = 16: waves 0-3 only)
   const bool rowok = lr < R;
@@ -899,7 +915,7 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int e = tid + 512 * i, j = dh4.div(e), c = (e - j * h4) * 4;
-      if (e < NkP * h4) st4(L.Ks + j * LDK + c, q.kr[i]);
+      if (e < 16 * dosx_live_tiles<KP, 4>(nk, NkP >> 4) * h4) st4(L.Ks + j * LDK + c, q.kr[i]);
     }
   }
   FSTAMP(17);
@@ -926,9 +942,11 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
   while (KS > 1 && (H % (16 * KS)) != 0) KS >>= 1;
   const int klen = H / KS;
   const UDiv dKS(KS);
-  for (int unit = wave; unit < njobsS * KS; unit += 8) {
+  // (per-crystal counts: the jobs of the 16-key tiles with live keys only - KS stays the padded key set's, it sizes the LDS)
+  const int nctL = dosx_live_tiles<KP, 4>(nk, nctS), njobsL = (R / 16) * nctL;
+  for (int unit = wave; unit < njobsL * KS; unit += 8) {
     const int job = dKS.div(unit), kq = unit - job * KS;
-    const int rt = job >= nctS ? job / nctS : 0, ct = job - rt * nctS;
+    const int rt = job >= nctL ? job / nctL : 0, ct = job - rt * nctL;
     const f32x4 acc = mma_kk<8>(L.Ds + (16 * rt + l15) * LDK + kq * klen + 4 * g4, L.Ks + (16 * ct + l15) * LDK + kq * klen + 4 * g4, klen >> 4);
     float* Sq_ = kq == 0 ? L.Sc : L.Sp + (kq - 1) * R * 68;
 #pragma unroll
@@ -943,12 +961,12 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
     for (int jj = 0; jj < 4; ++jj) {
       const int j = q16 + 16 * jj;
       float t = 0.f;
-      if (j < Nk) {
+      if (j < nk) {
         t = L.Sc[lr * 68 + j];
         for (int kq = 1; kq < KS; ++kq) t += L.Sp[(kq - 1) * R * 68 + lr * 68 + j];
       }
       if (a.att_mask) t = (t + cq) * mk[jj];
-      if (j < Nk) dot += pr[jj] * t;
+      if (j < nk) dot += pr[jj] * t;
       dp[jj] = t;
     }
     dot = row16_sum(dot);
@@ -956,7 +974,7 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
     for (int jj = 0; jj < 4; ++jj) {
       const int j = q16 + 16 * jj;
       if (j >= NkP) continue;
-      const bool v = j < Nk && rv;
+      const bool v = j < nk && rv;
       L.Ss[lr * 68 + j] = v ? pr[jj] * (dp[jj] - dot) * scale : 0.f;
       L.Ps2[lr * 68 + j] = v ? pr[jj] * mk[jj] : 0.f;
     }
@@ -969,7 +987,7 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
     const UDiv dnct(nct);
     for (int job = wave; job < njobs; job += 8) {
       const int rt = dnct.div(job), ct = job - rt * nct;
-      const f32x4 acc = mma_kn<4>(L.Ss + (16 * rt + l15) * 68 + 4 * g4, L.Ks + (4 * g4) * LDK + 16 * ct + l15, LDK, NkP >> 4);
+      const f32x4 acc = mma_kn<4>(L.Ss + (16 * rt + l15) * 68 + 4 * g4, L.Ks + (4 * g4) * LDK + 16 * ct + l15, LDK, nctL);
 #pragma unroll
       for (int i = 0; i < 4; ++i) L.Ds[(16 * rt + 4 * g4 + i) * LDK + 16 * ct + l15] = acc[i];
     }
@@ -1036,7 +1054,7 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
   // ---- f: this tile's share of dK + dV: [NkP keys] x [R queries] . [R queries] x [H] -> its slot of dkv_part (write-through) ----
   {
     float* part = a.att_dkv_part + ((size_t)al_bq * nqt + tile) * (size_t)Nk * H;
-    const int nct = H >> 4, njobs = nctS * nct;
+    const int nct = H >> 4, njobs = nctL * nct;
     const UDiv dnct(nct);
     for (int job = wave; job < njobs; job += 8) {
       const int jt = dnct.div(job), ct = job - jt * nct;
@@ -1056,7 +1074,7 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int j = 16 * jt + 4 * g4 + i, col = 16 * ct + l15;
-        if (j < Nk) __hip_atomic_store(part + (size_t)j * H + col, acc[i] + acc2[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sc1
+        if (j < (KP ? nk : Nk)) __hip_atomic_store(part + (size_t)j * H + col, acc[i] + acc2[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // sc1
       }
     }
   }
@@ -1074,7 +1092,7 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
   FSTAMP(27);
   if (last) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    ffn_dkv_reduce(a, nqt, bk, sm, tid);
+    ffn_dkv_reduce<KP>(a, nqt, bk, sm, tid);
     if (tid == 0) __hip_atomic_store(a.att_dkv_cnt + bk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     FSTAMP(28);
   }
@@ -1088,8 +1106,11 @@ constexpr int BLDW = FBN + 4;    // 132: padded rows of a k-major weight chunk
 // ATT = 2 (round 5): CRYSTAL-ALIGNED tiles like ffn_fwd_kernel<.., 2> (a workgroup = R consecutive query rows s of ONE query
 // batch entry, row r = s * Bq + bq, grid = Bq x ceil(Sq / R)), and the attention half's backward behind the row epilogue
 // (ffn_att_bwd_tile): dx1 never reaches HBM, the layer's backward is one launch.
-template <bool HALF, int KB, int ATT = 0>
+template <bool HALF, int KB, int ATTK = 0>
 __global__ __launch_bounds__(512, DOSX_FFN_BWD_OCC) void ffn_bwd_kernel(const DosxFfnBwd a) {
+  // ATTK = ATT, or 4 = ATT 2 with per-crystal key counts (DosxFfnBwd.att_key_ptr: the KP forms of the attention epilogue)
+  constexpr int ATT = ATTK >= 3 ? ATTK - 2 : ATTK;
+  constexpr bool KP = ATTK >= 3;
   DOSX_SET_MAIN_PRIO();
   extern __shared__ __align__(16) float sm[];
   constexpr int FBK = KB;
@@ -1408,7 +1429,7 @@ __global__ __launch_bounds__(512, DOSX_FFN_BWD_OCC) void ffn_bwd_kernel(const Do
     }
   }
   AttBwdRegs attq;
-  if constexpr (ATT == 2) ffn_att_bwd_prefetch<R>(a, attq, al_s0, al_bq, tid);
+  if constexpr (ATT == 2) ffn_att_bwd_prefetch<R, KP>(a, attq, al_s0, al_bq, tid);
   {
     // column sums of the 8 waves: [8][npv][128] (+ 8 scalars) in the dh tile's LDS (dead since the second product)
     float* Ps = T;
@@ -1456,7 +1477,7 @@ __global__ __launch_bounds__(512, DOSX_FFN_BWD_OCC) void ffn_bwd_kernel(const Do
     L.Pp = L.Sp;
     (void)NkP;
     FSTAMP(16);
-    ffn_att_bwd_tile<R>(a, sm, L, attq, al_s0, al_bq, al_tile, al_tpc, tid);
+    ffn_att_bwd_tile<R, KP>(a, sm, L, attq, al_s0, al_bq, al_tile, al_tpc, tid);
     FSTAMP(29);
   }
 }
@@ -1516,6 +1537,7 @@ static int ffn_fwd_prepare(const DosxFfn& a, FfnPlan& pl) {
   const int R = pl.half ? 16 : 32;
   pl.kb = ffn_chunk(H);
   pl.mode = aligned ? 2 : (att ? 1 : 0);
+  if (att && a.att_key_ptr) pl.mode += 2;          // 3 / 4: the per-crystal key-count instantiations of modes 1 / 2
   pl.smem = sizeof(float) * ((size_t)R * (H + 4) + (size_t)R * (H4 + 4) + 2 * (size_t)FBN * (pl.kb + 4));
   if (aligned)
     DOSX_CHECK_ARG(a.att_Nk <= 64 && ((size_t)((a.att_Nk + 15) & ~15) * (H + 4) + (size_t)R * 68) <= 2 * (size_t)FBN * (pl.kb + 4),
@@ -1532,6 +1554,10 @@ static int ffn_fwd_prepare(const DosxFfn& a, FfnPlan& pl) {
     DOSX_FFN_ATTR(false, 32, 2); DOSX_FFN_ATTR(true, 32, 2); DOSX_FFN_ATTR(false, 64, 2); DOSX_FFN_ATTR(true, 64, 2);
     DOSX_FFN_ATTR2(false, 32, 1); DOSX_FFN_ATTR2(true, 32, 1); DOSX_FFN_ATTR2(false, 64, 1); DOSX_FFN_ATTR2(true, 64, 1);
     DOSX_FFN_ATTR2(false, 32, 2); DOSX_FFN_ATTR2(true, 32, 2); DOSX_FFN_ATTR2(false, 64, 2); DOSX_FFN_ATTR2(true, 64, 2);
+    DOSX_FFN_ATTR(false, 32, 3); DOSX_FFN_ATTR(true, 32, 3); DOSX_FFN_ATTR(false, 64, 3); DOSX_FFN_ATTR(true, 64, 3);
+    DOSX_FFN_ATTR(false, 32, 4); DOSX_FFN_ATTR(true, 32, 4); DOSX_FFN_ATTR(false, 64, 4); DOSX_FFN_ATTR(true, 64, 4);
+    DOSX_FFN_ATTR2(false, 32, 3); DOSX_FFN_ATTR2(true, 32, 3); DOSX_FFN_ATTR2(false, 64, 3); DOSX_FFN_ATTR2(true, 64, 3);
+    DOSX_FFN_ATTR2(false, 32, 4); DOSX_FFN_ATTR2(true, 32, 4); DOSX_FFN_ATTR2(false, 64, 4); DOSX_FFN_ATTR2(true, 64, 4);
 #undef DOSX_FFN_ATTR
 #undef DOSX_FFN_ATTR2
     attr_set = true;
@@ -1543,10 +1569,10 @@ static int ffn_fwd_prepare(const DosxFfn& a, FfnPlan& pl) {
   do {                                                                                                                     \
     const dim3 grid_(pl.grid);                                                                                             \
     hipStream_t st_ = to_stream(stream);                                                                                   \
-    if (pl.half && pl.kb == 64) { if (pl.mode == 2) hipLaunchKernelGGL((KERNEL<true, 64, 2>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 1) hipLaunchKernelGGL((KERNEL<true, 64, 1>), grid_, dim3(512), pl.smem, st_, ARG); else hipLaunchKernelGGL((KERNEL<true, 64, 0>), grid_, dim3(512), pl.smem, st_, ARG); } \
-    else if (pl.half) { if (pl.mode == 2) hipLaunchKernelGGL((KERNEL<true, 32, 2>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 1) hipLaunchKernelGGL((KERNEL<true, 32, 1>), grid_, dim3(512), pl.smem, st_, ARG); else hipLaunchKernelGGL((KERNEL<true, 32, 0>), grid_, dim3(512), pl.smem, st_, ARG); } \
-    else if (pl.kb == 64) { if (pl.mode == 2) hipLaunchKernelGGL((KERNEL<false, 64, 2>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 1) hipLaunchKernelGGL((KERNEL<false, 64, 1>), grid_, dim3(512), pl.smem, st_, ARG); else hipLaunchKernelGGL((KERNEL<false, 64, 0>), grid_, dim3(512), pl.smem, st_, ARG); } \
-    else { if (pl.mode == 2) hipLaunchKernelGGL((KERNEL<false, 32, 2>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 1) hipLaunchKernelGGL((KERNEL<false, 32, 1>), grid_, dim3(512), pl.smem, st_, ARG); else hipLaunchKernelGGL((KERNEL<false, 32, 0>), grid_, dim3(512), pl.smem, st_, ARG); } \
+    if (pl.half && pl.kb == 64) { if (pl.mode == 4) hipLaunchKernelGGL((KERNEL<true, 64, 4>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 3) hipLaunchKernelGGL((KERNEL<true, 64, 3>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 2) hipLaunchKernelGGL((KERNEL<true, 64, 2>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 1) hipLaunchKernelGGL((KERNEL<true, 64, 1>), grid_, dim3(512), pl.smem, st_, ARG); else hipLaunchKernelGGL((KERNEL<true, 64, 0>), grid_, dim3(512), pl.smem, st_, ARG); } \
+    else if (pl.half) { if (pl.mode == 4) hipLaunchKernelGGL((KERNEL<true, 32, 4>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 3) hipLaunchKernelGGL((KERNEL<true, 32, 3>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 2) hipLaunchKernelGGL((KERNEL<true, 32, 2>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 1) hipLaunchKernelGGL((KERNEL<true, 32, 1>), grid_, dim3(512), pl.smem, st_, ARG); else hipLaunchKernelGGL((KERNEL<true, 32, 0>), grid_, dim3(512), pl.smem, st_, ARG); } \
+    else if (pl.kb == 64) { if (pl.mode == 4) hipLaunchKernelGGL((KERNEL<false, 64, 4>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 3) hipLaunchKernelGGL((KERNEL<false, 64, 3>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 2) hipLaunchKernelGGL((KERNEL<false, 64, 2>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 1) hipLaunchKernelGGL((KERNEL<false, 64, 1>), grid_, dim3(512), pl.smem, st_, ARG); else hipLaunchKernelGGL((KERNEL<false, 64, 0>), grid_, dim3(512), pl.smem, st_, ARG); } \
+    else { if (pl.mode == 4) hipLaunchKernelGGL((KERNEL<false, 32, 4>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 3) hipLaunchKernelGGL((KERNEL<false, 32, 3>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 2) hipLaunchKernelGGL((KERNEL<false, 32, 2>), grid_, dim3(512), pl.smem, st_, ARG); else if (pl.mode == 1) hipLaunchKernelGGL((KERNEL<false, 32, 1>), grid_, dim3(512), pl.smem, st_, ARG); else hipLaunchKernelGGL((KERNEL<false, 32, 0>), grid_, dim3(512), pl.smem, st_, ARG); } \
   } while (0)
 
 extern "C" int dosx_ffn_fwd(const DosxFfn* ap, dosx_stream_t stream) {
@@ -1588,7 +1614,9 @@ extern "C" int dosx_ffn_fwd_multi(const DosxFfn* descs, int n, dosx_stream_t str
     const dim3 grid_(pl.grid);
     hipStream_t st_ = to_stream(stream);
 #define DOSX_FFN_GO2(HALF_, KB_) \
-    do { if (pl.mode == 2) hipLaunchKernelGGL((ffn_fwd_multi_kernel<HALF_, KB_, 2>), grid_, dim3(512), pl.smem, st_, A); \
+    do { if (pl.mode == 4) hipLaunchKernelGGL((ffn_fwd_multi_kernel<HALF_, KB_, 4>), grid_, dim3(512), pl.smem, st_, A); \
+         else if (pl.mode == 3) hipLaunchKernelGGL((ffn_fwd_multi_kernel<HALF_, KB_, 3>), grid_, dim3(512), pl.smem, st_, A); \
+         else if (pl.mode == 2) hipLaunchKernelGGL((ffn_fwd_multi_kernel<HALF_, KB_, 2>), grid_, dim3(512), pl.smem, st_, A); \
          else hipLaunchKernelGGL((ffn_fwd_multi_kernel<HALF_, KB_, 1>), grid_, dim3(512), pl.smem, st_, A); } while (0)
     if (pl.half && pl.kb == 64) DOSX_FFN_GO2(true, 64);
     else if (pl.half) DOSX_FFN_GO2(true, 32);
@@ -1665,10 +1693,14 @@ extern "C" int dosx_ffn_bwd(const DosxFfnBwd* ap, dosx_stream_t stream) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_bwd_kernel<true, 64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_bwd_kernel<false, 64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_bwd_kernel<true, 64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_bwd_kernel<false, 64, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_bwd_kernel<true, 64, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set = true;
   }
   const dim3 grid(att ? a.att_Bq * ceil_div(a.att_Sq, R) : ceil_div(a.M, R));
-  if (att && half) hipLaunchKernelGGL((ffn_bwd_kernel<true, 64, 2>), grid, dim3(512), smem, to_stream(stream), a);
+  if (att && a.att_key_ptr && half) hipLaunchKernelGGL((ffn_bwd_kernel<true, 64, 4>), grid, dim3(512), smem, to_stream(stream), a);
+  else if (att && a.att_key_ptr) hipLaunchKernelGGL((ffn_bwd_kernel<false, 64, 4>), grid, dim3(512), smem, to_stream(stream), a);
+  else if (att && half) hipLaunchKernelGGL((ffn_bwd_kernel<true, 64, 2>), grid, dim3(512), smem, to_stream(stream), a);
   else if (att) hipLaunchKernelGGL((ffn_bwd_kernel<false, 64, 2>), grid, dim3(512), smem, to_stream(stream), a);
   else if (half && kb == 64) hipLaunchKernelGGL((ffn_bwd_kernel<true, 64>), grid, dim3(512), smem, to_stream(stream), a);
   else if (half) hipLaunchKernelGGL((ffn_bwd_kernel<true, 32>), grid, dim3(512), smem, to_stream(stream), a);

@@ -675,8 +675,9 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
     head = (gamma, beta, w, b, xhat [rows,H], rstd [rows], dos [Bq,Sq]) (with final_ln False, head_fused_fwd(H, T)): the
     model head - LayerNorm + H->1 output layer on the encoder's output - in the last layer's ffn_fwd epilogue; the
     encoder output itself is then not materialised (None is returned for it).
-    key_ptr [Bk + 1] int32 (inference only; DosxAttn.key_ptr): crystal bk attends over its first key_ptr[bk + 1] - key_ptr[bk] key
-    rows only - the batch's graph_ptr makes a batched forward equal the reference's batch-size-1 evaluation (utils.py:61-143).
+    key_ptr [Bk + 1] int32 (DosxAttn.key_ptr; forward and encoder_bwd, with or without attention dropout): crystal bk attends over
+    its first key_ptr[bk + 1] - key_ptr[bk] key rows only - the batch's graph_ptr makes a batched pass equal the reference's
+    batch-size-1 passes (main_phDOS.py:52-55, utils.py:61-143).  Not with relu / res dropout (fdrop).
     fdrop = (p_relu, p_res, seed_dev, stream_base) or None: relu / res dropout of the layer (transformer.py:137,145-147) in
     training mode.  The layer then runs UNFUSED - attention without its residual epilogue, the two feed-forward GEMMs, and
     ops.mask_residual for the three "dropout -> add residual" steps - with one explicit multiplier mask per dropout site."""
@@ -698,7 +699,7 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
         a = _attn_desc(Sq, Bq, Nk, Bk, H, qs, qb, x, kvhat, g0, b0)
         a.out, a.probs, a.qstats, a.out_stats = x1.data_ptr(), probs.data_ptr(), qstats.data_ptr(), st1.data_ptr()
         if key_ptr is not None:
-            assert key_ptr.dtype == torch.int32 and key_ptr.numel() >= Bk + 1 and fdrop is None and drop is None
+            assert key_ptr.dtype == torch.int32 and key_ptr.numel() >= Bk + 1 and fdrop is None
             a.key_ptr = key_ptr.data_ptr()
         mask = None
         if drop is not None and drop[0] > 0.0:
@@ -828,7 +829,7 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
         ops.layernorm(x, P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"], y, xhat, rstd, rows, H)
         fin = (xhat, rstd)
         x = y
-    return x, (lay, fin, Sq, Bq, Nk, Bk, H, T, kvhat)
+    return x, (lay, fin, Sq, Bq, Nk, Bk, H, T, kvhat, key_ptr)
 
 
 def _bf16x3_ok(rows: int, n: int, k: int) -> bool:
@@ -860,7 +861,7 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
     (only when head_fused_bwd(H, T)): the encoder's output went through LN -> H->1 output layer (ops.ln_rowdot) and ddos is
     the gradient of that layer's output; their backward runs inside the last layer's ffn_bwd launch.
     Returns the gradient w.r.t. the (expanded [Sq*Bq, H]) query input."""
-    lay, fin, Sq, Bq, Nk, Bk, H, T, kvhat = ctx
+    lay, fin, Sq, Bq, Nk, Bk, H, T, kvhat, key_ptr = ctx
     dev = kvhat.device
     rows = Sq * Bq
     r32 = _rows32(rows)
@@ -917,7 +918,7 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
             att_bwd_args = dict(x=x_in, kvhat=kvhat, gamma0=g0, beta0=b0, probs=probs, qstats=qstats, mask=mask, dxin=dxin_a,
                                 partials_q=part_a.data_ptr(), partials_kv=part_a.data_ptr() + 4 * Bq * nqt_al * 2 * H, dkv_part=kvp_a,
                                 dkv_cnt=ops.COUNTERS.take(dev, Bk), dkvhat=dkvhat, accumulate=0 if (dkv_fresh and t == T - 1) else 1,
-                                Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=qs, qb=qb)
+                                Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=qs, qb=qb, key_ptr=key_ptr)
         if fused:           # both dgrad GEMMs + ReLU mask + LN1 backward + residual in one launch (csrc/ffn.hip)
             rgp = ops.ffn_att_bwd_partial_rows(Sq, Bq) if att_in_ffn else ops.ffn_bwd_partial_rows(rows)
             with_fin = fin_fused is not None and t == T - 1
@@ -983,6 +984,8 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
             a.partials_q = part.data_ptr()
             a.partials_kv = part.data_ptr() + 4 * Bq * nqt * 2 * H
             a.flags = flags
+            if key_ptr is not None:
+                a.key_ptr = key_ptr.data_ptr()
             return a
         if small:
             # ONE launch: every (query tile, crystal) workgroup publishes its share of dK + dV and the last one of a key
@@ -1316,14 +1319,16 @@ def dostransformer_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta, drop=None, per
     """Forward of DOSTransformer_phonon / DOSTransformer (DOSTransformer_phonon.py:66-119,
     DOSTransformer.py:45-93).  Returns (dos [2B,S] : rows [0,B) global, [B,2B) system; x_L; ctx).
     drop: None (eval mode / attn_drop 0) or (p, seed_dev): attention dropout of the three encoders.
-    per_crystal_keys (inference only): the two cross attentions attend over each crystal's OWN atoms instead of the batch's
-    zero-padded Nmax rows - what the reference computes at batch size 1, its evaluation setting (main_eDOS.py:55-56,
-    utils.py:61-143; SURVEY.md 0.3: the padded rows take part in the softmax, so outputs depend on the batch's Nmax)."""
+    per_crystal_keys (train.Trainer / predict.Predictor; forward and dostransformer_bwd, with or without attention dropout, any
+    atom count): the two cross attentions attend over each crystal's OWN atoms instead of the batch's zero-padded Nmax rows -
+    what the reference computes at batch size 1, where it trains the phonon model and evaluates both (main_phDOS.py:52-55,
+    main_eDOS.py:55-56, utils.py:61-143; SURVEY.md 0.3: the padded rows take part in the softmax, so outputs depend on the
+    batch's Nmax).  The dropout masks are drawn on [Bq, S, n_max] as without the flag.  hidden <= ops.ATTN_MAX_H only."""
     dr = (lambda base: None) if drop is None else (lambda base: (drop[0], drop[1], base))
     H, S, T, B, N = cfg.H, cfg.S, cfg.T, m.num_graphs, m.num_nodes
-    if per_crystal_keys and (drop is not None or H > ops.ATTN_MAX_H or m.n_max > 320):
+    if per_crystal_keys and H > ops.ATTN_MAX_H:
         from ._lib import DosxError
-        raise DosxError("per_crystal_keys: inference mode (no dropout), hidden <= 256 and at most 320 atoms per crystal")
+        raise DosxError(f"per_crystal_keys: hidden <= {ops.ATTN_MAX_H} (the attention kernels' row width), got {H}")
     kp = m.graph_ptr if per_crystal_keys else None
     if H > ops.ATTN_MAX_H:
         return _dostransformer_fwd_wide(P, cfg, g, m, dr)

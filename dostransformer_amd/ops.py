@@ -505,7 +505,8 @@ def ffn_bwd(M: int, H: int, dy: torch.Tensor, h: torch.Tensor, x: torch.Tensor, 
     nk_att = 0
     if att is not None:
         # the attention half's backward in the same launch (include/dosx.h: DosxFfnBwd.att_*): att = dict(x, kvhat, gamma0, beta0,
-        # probs, qstats, mask, dxin, partials_q, partials_kv, dkv_part, dkv_cnt, dkvhat, accumulate, Nk, Bk, Bq, Sq, qs, qb)
+        # probs, qstats, mask, dxin, partials_q, partials_kv, dkv_part, dkv_cnt, dkvhat, accumulate, Nk, Bk, Bq, Sq, qs, qb,
+        # key_ptr=None)
         a.att_x, a.att_ldxin = att["x"].data_ptr(), int(att["x"].stride(0))
         a.att_kvhat, a.att_gamma0, a.att_beta0 = att["kvhat"].data_ptr(), att["gamma0"].data_ptr(), att["beta0"].data_ptr()
         a.att_probs, a.att_qstats, a.att_mask = att["probs"].data_ptr(), att["qstats"].data_ptr(), _p(att.get("mask"))
@@ -515,6 +516,8 @@ def ffn_bwd(M: int, H: int, dy: torch.Tensor, h: torch.Tensor, x: torch.Tensor, 
         a.att_dkvhat, a.att_dkv_accumulate = att["dkvhat"].data_ptr(), int(att["accumulate"])
         a.att_Nk, a.att_Bk, a.att_Bq, a.att_Sq = int(att["Nk"]), int(att["Bk"]), int(att["Bq"]), int(att["Sq"])
         a.att_qs, a.att_qb = int(att["qs"]), int(att["qb"])
+        if att.get("key_ptr") is not None:
+            a.att_key_ptr = att["key_ptr"].data_ptr()
         nk_att = a.att_Nk
     _call("dosx_ffn_bwd", C.byref(a), _stream(),
           w=lambda: (f"ffn_bwd[H{H}{',att' if nk_att else ''}]", "ffn_bwd_kernel", "mfma", 16.0 * M * H * H + 10.0 * M * nk_att * H))

@@ -24,7 +24,7 @@ import torch
 
 from . import functional as Fn
 from . import ops
-from ._lib import from_environ
+from ._lib import DosxError, from_environ
 from ._models import DOSTransformerBase, _SEED_MOD, rank_seed_offset
 from .batch import CrystalBatch, GraphMeta, bucket_sizes, graph_meta, pad_batch, seg_tile_bound
 
@@ -180,14 +180,24 @@ class Trainer:
     ``dist``: optional :class:`dostransformer_amd.dist.DataParallel` — shards are per-rank batches,
     gradients are summed over ranks (loss kernels already divide by the GLOBAL element/crystal
     count), the phonon loss exchanges its two SSE scalars before the backward pass.
+
+    ``per_crystal_keys=True`` (same spelling as :class:`dostransformer_amd.predict.Predictor`): ``transformer`` and
+    ``transformer_source`` attend over each crystal's own atoms, forward and backward, instead of the rows that pad it to the
+    batch's largest crystal - the step then learns what the reference computes at ``batch_size = 1``, where it trains the
+    phonon model and evaluates both (`main_phDOS.py:52-55`, `main_eDOS.py:55-56`); for eDOS the phantom node counts as an atom, as
+    it does there.  Eager, ``replay=True`` and ``graph=True`` alike (the bucket's own ``graph_ptr`` is the operand); the loss is
+    unchanged.  Not under data parallelism.
     """
 
     def __init__(self, model: DOSTransformerBase, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2,
                  betas=(0.9, 0.999), eps: float = 1e-8, dist=None, graph: bool = False, replay: bool = False,
-                 bucket=(8, 128), max_slots: int = 32, promote: float = 0.0):
+                 bucket=(8, 128), max_slots: int = 32, promote: float = 0.0, per_crystal_keys: bool = False):
         if not isinstance(model, DOSTransformerBase):
             raise TypeError("Trainer drives DOSTransformer / DOSTransformer_phonon modules")
         model._require_fp32_program("Trainer")
+        if per_crystal_keys and dist is not None:
+            raise DosxError("Trainer(per_crystal_keys=True) is a single-GPU mode: not with dist (data parallelism)")
+        self._per_crystal_keys = bool(per_crystal_keys)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, betas, eps
         self.dist = dist
         self.graph = graph
@@ -216,6 +226,11 @@ class Trainer:
         self._seen = {}
         self.kernel_timer = None          # ops._KernelTimer: replayed programs then run through dosx_replay_timed
         self._ds_checked = []             # datasets whose per-rank size was compared across the ranks (step_dataset)
+
+    @property
+    def per_crystal_keys(self) -> bool:
+        """True: the two cross attentions attend over each crystal's own atoms (fixed at construction)."""
+        return self._per_crystal_keys
 
     def _state(self, fp):
         """AdamW moments laid out like ``fp``.  When the parameters are re-homed (module moved to another device after
@@ -248,7 +263,8 @@ class Trainer:
             st_n_global = m.num_graphs
         model, dev, cfg = self.model, fp.flat.device, self.model._cfg
         B, S = m.num_graphs, cfg.S
-        dg, xL, ds, (ctx, dos) = model._program_fwd(fp.P, g, m, bump_seed=False)     # (step() bumps the dropout seed)
+        dg, xL, ds, (ctx, dos) = model._program_fwd(fp.P, g, m, bump_seed=False,     # (step() bumps the dropout seed)
+                                                    per_crystal_keys=self._per_crystal_keys)
         st = {"ctx": ctx, "dos": dos, "out": (dg, xL, ds), "B": B, "S": S}
         if self.kind == "phonon":
             st["y"] = Fn._f32(g.phdos).reshape(B, S)

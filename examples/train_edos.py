@@ -46,6 +46,8 @@ def parse_args(argv=None):
     ap.add_argument("--pickle", default=None)
     ap.add_argument("--eval_batch_size", type=int, default=1, help="main_eDOS.py:55-56 evaluates at batch size 1")
     ap.add_argument("--out", default="edos_best.pt")
+    ap.add_argument("--per-crystal-keys", action="store_true",
+                    help="train over each crystal's own atoms (and its phantom node) - what the batch-size-1 evaluation computes")
     return ap.parse_args(argv)
 
 
@@ -69,7 +71,8 @@ def main(argv=None):
     # coarse shape buckets: reshuffled batches fall into a few dozen (N, E) buckets, each recorded once (ghost padding is
     # exact); every batch pads its keys to the training set's largest crystal so that n_max is not a bucket dimension
     bucket = (32, 512)
-    trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=bucket, promote=0.08)      # AdamW(lr, weight_decay=1e-2), `:91`
+    trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=bucket, promote=0.08,
+                      per_crystal_keys=args.per_crystal_keys)      # AdamW(lr, weight_decay=1e-2), `:91`
     predictor = Predictor(model, bucket=bucket)
     criterion_2 = torch.nn.L1Loss()                                                       # `main_eDOS.py:93`
     nmax_train = int(ds["train"].n_nodes.max())

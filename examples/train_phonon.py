@@ -46,6 +46,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="phonon_best.pt")
     ap.add_argument("--float64", action="store_true", help="the reference's float64 training with per-crystal keys")
+    ap.add_argument("--per-crystal-keys", action="store_true",
+                    help="fp32 trainer: attend over each crystal's own atoms - what the reference's batch_size = 1 training computes")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.manual_seed(args.seed)
@@ -66,7 +68,8 @@ def main(argv=None):
     model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).to(dev)
     # coarse shape buckets: reshuffled batches then fall into a few dozen (N, E, n_max) buckets that are all recorded
     # within the first epoch (ghost padding is exact; it costs a few per cent of extra rows)
-    trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=(32, 1024), promote=0.08)
+    trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=(32, 1024), promote=0.08,
+                      per_crystal_keys=args.per_crystal_keys)
     predictor = Predictor(model, bucket=(32, 1024))
     best, history = float("inf"), []
     for epoch in range(args.epochs):

@@ -418,11 +418,18 @@ typedef struct DosxAttn {
   const float* ln1_gamma;
   const float* ln1_beta;
   float* ln1_out;      /* [Sq*Bq, H] */
-  /* round 6 (forward only): per-crystal key counts.  key_ptr [Bk + 1] (NULL: every crystal attends over all Nk
-   * key rows - padded rows included, like the reference's unmasked to_dense_batch): crystal bk attends over its FIRST
-   * key_ptr[bk + 1] - key_ptr[bk] key rows only (the batch's graph_ptr: its own atoms).  A batch of B crystals then gives what B
-   * batch-size-1 forwards give - the reference evaluates at batch_size = 1 (main_eDOS.py:55-56, utils.py:61-143), where
-   * Nmax = the crystal's own atom count - in one pass.  probs beyond a crystal's count are written as zeros.  Nk <= 320. */
+  /* Per-crystal key counts, forward and backward, every kernel form, any Nk.  key_ptr [Bk + 1] (NULL: every crystal attends
+   * over all Nk key rows - padded rows included, like the reference's unmasked to_dense_batch): key crystal bk = bq % Bk has
+   * n = clamp(key_ptr[bk + 1] - key_ptr[bk], 0, Nk) keys (the batch's graph_ptr: its own atoms); the rows j >= n do not exist.
+   * A batch of B crystals then computes what B batch-size-1 passes compute - the reference trains and evaluates the phonon
+   * model and evaluates the Electron-DOS model at batch_size = 1 (main_phDOS.py:52-55, main_eDOS.py:55-56).  The float64
+   * contract (DosxAttn64.key_ptr) in fp32:
+   *   - nothing at key index >= n is read from kvhat, probs, drop_mask or dscores;
+   *   - probs and dscores (when given) are written 0.0 at key index >= n;
+   *   - the key-side partial rows (partials_kv) of key tiles past n are written 0.0: column sums need no mask;
+   *   - dkvhat rows >= n are written 0.0 without dkv_accumulate and left alone with it;
+   *   - n = 0: out = x (forward), dx = dout (backward, with the residual), zero key gradients, no division by zero;
+   *   - key_ptr = [0, Nk, 2 Nk, ...] gives bitwise what NULL gives. */
   const int32_t* key_ptr;
 } DosxAttn;
 /* 1 if dosx_attention_bwd takes the partial-dKV path for this key count / width when dkv_part is given (else it needs
@@ -538,7 +545,7 @@ typedef struct DosxFfn {
    * (dosx_ffn_att_aligned_supported), e.g. the 51-key self attention over the energy bins; same outputs.  The caller chooses
    * it while that grid is about one round of workgroups: Sq is padded to the tile height per crystal. */
   int32_t att_aligned;
-  const int32_t* att_key_ptr;   /* as DosxAttn.key_ptr: per-crystal key counts of the fused attention half (forward only) */
+  const int32_t* att_key_ptr;   /* as DosxAttn.key_ptr: per-crystal key counts of the fused attention half */
 } DosxFfn;
 int dosx_ffn_supported(int H);
 int dosx_ffn_att_supported(int H, int Nk);   /* whether dosx_ffn_fwd takes the att_* fields for this shape (H, Nk <= 16) */
@@ -597,6 +604,7 @@ typedef struct DosxFfnBwd {
   float* att_partials_q; float* att_partials_kv; float* att_dkv_part; int32_t* att_dkv_cnt;
   float* att_dkvhat; int32_t att_dkv_accumulate;
   int32_t att_Nk, att_Bk, att_Bq, att_Sq, att_qs, att_qb;
+  const int32_t* att_key_ptr;   /* as DosxAttn.key_ptr: per-crystal key counts of the fused attention half's backward, or NULL */
 } DosxFfnBwd;
 int dosx_ffn_bwd_partial_rows(int M);
 int dosx_ffn_att_bwd_supported(int H, int Nk, int Sq, int Bq);   /* whether dosx_ffn_bwd takes the att_* fields for this shape */
