@@ -445,6 +445,8 @@ _SIGS = {
     "dosx_dense_rows_f64": [_P, _P, _P, _P, _I, _I, _I, _P],
     "dosx_dense_rows_bwd_f64": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "dosx_index_sum_f64": [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P],
+    "dosx_loss_phonon_f64": [_P, _P, _P, _D, _P, _P, _P, _P, _I, _P],
+    "dosx_adamw_f64": [_P, _P, _P, _P, _L, _D, _D, _D, _D, _D, _I, _P],
     "dosx_last_error": [],
     "dosx_version": [],
 }

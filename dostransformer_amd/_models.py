@@ -97,8 +97,8 @@ class DOSTransformerBase(FusedModel):
         """The drivers that run the fp32 program on the flat buffer (train.Trainer, predict.Predictor) refuse a module set to
         float64."""
         if self._program_dtype == torch.float64:
-            raise DosxError(f"{who} runs the fp32 program; {type(self).__name__} is set to float64 (set_program_dtype): use "
-                            f"model(batch), loss.backward() and torch.optim.AdamW")
+            raise DosxError(f"{who} runs the fp32 program; {type(self).__name__} is set to float64 (set_program_dtype): train "
+                            f"it with train64.Trainer64, or with model(batch), loss.backward() and torch.optim.AdamW")
 
     def _check_train_flags(self):
         pass          # (kept for callers of round 1: attention dropout is implemented now)

@@ -9,6 +9,10 @@ current stream, no fused-path heuristics; every reduction has a fixed order, so 
 Edges are processed in the destination-sorted order of ``GraphMeta`` (``edge_perm`` maps the caller's order to it).  The
 transformer half of DOSTransformer_phonon keeps crystal-major rows: b * S + s for the energy rows, b * nmax + j for the
 zero-padded dense key rows.
+
+train64.Trainer64 records this program (ops.RECORDER) and replays it on static buffers: every buffer the program creates goes
+through ops.alloc64 / ops.keep_alive, and the torch casts in its body (``_f64``, ``g.system.to(int32)``, ``ddos.to(float64)``)
+hand back their argument when it already has the dtype and layout the kernels read - which the slot buffers have.
 """
 from __future__ import annotations
 
@@ -189,7 +193,7 @@ def _gnn_trunk_bwd(P: Params, G: Params, cfg, m: GraphMeta, ctx, dx: torch.Tenso
     for l in reversed(range(cfg.L)):
         dx, de = _processor_bwd(P, G, f"stacked_processor.{l}", layers[l], dx, de, m)
     if de is None:                                                                    # L = 0: nothing reaches the edges
-        de = torch.zeros(m.num_edges, cfg.H, device=dx.device, dtype=torch.float64)
+        de = ops.keep_alive(torch.zeros(m.num_edges, cfg.H, device=dx.device, dtype=torch.float64))
     _mlp_prelu_bwd(P, G, "GN_encoder.edge_encoder", ce, de)
     _mlp_prelu_bwd(P, G, enc, cx, dx)
 
@@ -208,7 +212,7 @@ def _encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, kvhat: 
         xhq, rsq, q = layernorm64(x, g0, b0)
         mask = None
         if drop is not None:
-            mask = torch.empty(Bq, Sq, Nk, device=x.device, dtype=torch.float32)
+            mask = ops.keep_alive(torch.empty(Bq, Sq, Nk, device=x.device, dtype=torch.float32))
             ops.dropout_mask(mask, drop[0], drop[1], drop[2] + t)
             if Fn.DROP_MASK_LOG is not None:
                 Fn.DROP_MASK_LOG.append((pre, t, mask))
@@ -272,7 +276,7 @@ def dostransformer_phonon_fwd(P: Params, cfg, g, m: GraphMeta, drop=None, per_cr
     dev = xL.device
     kv_n, rstd_n = dense_rows64(xL, m.graph_ptr, B, nmax)                               # :86-87, the keys' LN0 without affine
     # energies (:71,143): embedding row s for every crystal, crystal-major
-    e_idx = (torch.arange(B * S, device=dev, dtype=torch.int32) % S).contiguous()
+    e_idx = ops.keep_alive((torch.arange(B * S, device=dev, dtype=torch.int32) % S).contiguous())
     E1, c1 = _encoder_fwd(P, "transformer", rows_add64(B * S, P["embeddings.weight"], ia=e_idx), S, B, kv_n, nmax, B, T, dr(0),
                           kp)
     pool = graph_pool64(xL, m.graph_ptr, B)                                              # :90, :180-181
@@ -288,7 +292,7 @@ def dostransformer_phonon_fwd(P: Params, cfg, g, m: GraphMeta, drop=None, per_cr
     gemm64(BS, H, seg_g, P["fc.weight"], dosin[:BS], bias=P["fc.bias"], act=ACT64_LEAKY, pre=pre[:BS])
     gemm64(BS, H, seg_s, P["fc_prompt.weight"], dosin[BS:], bias=P["fc_prompt.bias"], act=ACT64_LEAKY, pre=pre[BS:])
     # both branches through each shared encoder at once: Bq = 2B, global crystals first (the masks' layout)
-    ptr_s = torch.arange(0, 2 * BS + 1, S, device=dev, dtype=torch.int32)
+    ptr_s = ops.keep_alive(torch.arange(0, 2 * BS + 1, S, device=dev, dtype=torch.int32))
     kv_s, rstd_s = dense_rows64(dosin, ptr_s, 2 * B, S)                                  # self attention: its own rows
     hs, c2 = _encoder_fwd(P, "transformer_self", dosin, S, 2 * B, kv_s, S, 2 * B, T, dr(64))
     hsrc, c3 = _encoder_fwd(P, "transformer_source", hs, S, 2 * B, kv_n, nmax, B, T, dr(128), kp)

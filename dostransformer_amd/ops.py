@@ -1555,8 +1555,18 @@ def _chk_c64(*ts):
             raise ValueError(f"dosx fp64 op needs a contiguous operand here, got shape {tuple(t.shape)} strides {t.stride()}")
 
 
+def keep_alive(t: torch.Tensor) -> torch.Tensor:
+    """A tensor created inside a program by anything but alloc / alloc64 (a torch.empty dropout mask, an arange index): kept
+    alive for the recorded program while recording - the descriptors hold raw pointers, and the caching allocator would hand
+    a freed buffer to someone else."""
+    if RECORDER.active:
+        RECORDER.keep.append(t)
+    return t
+
+
 def alloc64(device, *shape) -> torch.Tensor:
-    return torch.empty(shape, device=device, dtype=torch.float64)
+    """Uninitialised fp64 device buffer (kept alive for the recorded program while recording, like alloc)."""
+    return keep_alive(torch.empty(shape, device=device, dtype=torch.float64))
 
 
 def seg64(t: torch.Tensor, rmap: Optional[RowMap] = None) -> _lib.Seg64:
@@ -1792,3 +1802,28 @@ def index_sum64(src: torch.Tensor, idx: torch.Tensor, out: torch.Tensor, accumul
     _call("dosx_index_sum_f64", src.data_ptr(), src.stride(0), idx.data_ptr(), src.shape[0], out.data_ptr(), out.stride(0),
           out.shape[0], src.shape[1], int(accumulate), _stream())
     return out
+
+
+# float64 training step (csrc/f64_train.hip), used by train64.Trainer64
+def loss_phonon64(pg: torch.Tensor, ps: torch.Tensor, y: torch.Tensor, beta: float, dpg: torch.Tensor, dps: torch.Tensor,
+                  loss: torch.Tensor, sse: Optional[torch.Tensor] = None) -> None:
+    """loss[0] = rmse(pg, y) + beta rmse(ps, y) over all elements, dpg / dps its gradient, sse (optional, 2 elements) the two sums
+    of squares (include/dosx.h: dosx_loss_phonon_f64).  An RMSE of exactly 0 gives a zero gradient."""
+    _chk_c64(pg, ps, y, dpg, dps, loss, sse)
+    count = pg.numel()
+    if not (ps.numel() == y.numel() == dpg.numel() == dps.numel() == count) or loss.numel() < 1 or \
+            (sse is not None and sse.numel() < 2):
+        raise ValueError(f"loss_phonon64: pg {tuple(pg.shape)}, ps {tuple(ps.shape)}, y {tuple(y.shape)}, dpg {tuple(dpg.shape)}, "
+                         f"dps {tuple(dps.shape)}, loss {tuple(loss.shape)}" + ("" if sse is None else f", sse {tuple(sse.shape)}"))
+    _call("dosx_loss_phonon_f64", pg.data_ptr(), ps.data_ptr(), y.data_ptr(), float(beta), dpg.data_ptr(), dps.data_ptr(),
+          loss.data_ptr(), _p(sse), count, _stream())
+
+
+def adamw64(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, n: int, lr: float, beta1: float, beta2: float,
+            eps: float, weight_decay: float, step: int) -> None:
+    """torch.optim.AdamW's update of the first n elements of the flat fp64 buffers (include/dosx.h: dosx_adamw_f64)."""
+    _chk_c64(p, g, m, v)
+    if min(p.numel(), g.numel(), m.numel(), v.numel()) < n:
+        raise ValueError(f"adamw64: n = {n} of buffers with {p.numel()}, {g.numel()}, {m.numel()}, {v.numel()} elements")
+    _call("dosx_adamw_f64", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), int(n), float(lr), float(beta1), float(beta2),
+          float(eps), float(weight_decay), int(step), _stream())

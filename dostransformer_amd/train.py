@@ -174,7 +174,82 @@ def promote_key(live_keys, key, tol: float):
     return best
 
 
-class Trainer:
+class _AdamWState:
+    """What Trainer and train64.Trainer64 share: the AdamW moments laid out like the model's flat parameters (in the flat
+    buffer's dtype), their checkpoint in ``torch.optim.AdamW`` vocabulary and the per-step bump of the dropout seed.  Expects
+    ``model``, ``_fp``, ``_m``, ``_v``, ``_slots``, ``step_count`` and the hyper-parameters ``lr``, ``betas``, ``eps``, ``wd``, ``beta``."""
+
+    def _state(self, fp):
+        """AdamW moments laid out like ``fp``.  When the parameters are re-homed (module moved to another device after
+        ``load_state_dict``, a different dead-parameter set, ...) the moments follow BY NAME instead of being reset:
+        ``step_count`` keeps counting, so zeroed moments would silently corrupt the bias correction."""
+        if self._fp is not fp:
+            m, v = torch.zeros_like(fp.flat), torch.zeros_like(fp.flat)
+            old = self._fp
+            if old is not None and self._m is not None:
+                old_off = dict(zip(old.names, old.offsets))
+                with torch.no_grad():
+                    for n, o in zip(fp.names, fp.offsets):
+                        oo = old_off.get(n)
+                        if oo is None:
+                            continue
+                        k = fp.P[n].numel()
+                        if old.P[n].numel() != k:
+                            raise RuntimeError(f"parameter {n} changed size under a running optimizer")
+                        m[o:o + k].copy_(self._m[oo:oo + k])
+                        v[o:o + k].copy_(self._v[oo:oo + k])
+            self._m, self._v, self._fp = m, v, fp
+            self._slots = OrderedDict()
+        return self._m, self._v
+
+    # ---- checkpoint / resume (SURVEY.md §8f-4; absent upstream) ------------------------------------
+    def state_dict(self) -> dict:
+        """Optimizer state keyed by the reference's parameter names, in ``torch.optim.AdamW`` vocabulary
+        (``exp_avg`` / ``exp_avg_sq`` / ``step``); together with ``model.state_dict()`` (reference key
+        layout, SURVEY.md §8b) this is a complete resume point."""
+        fp = self._fp if self._fp is not None else self.model.flat_params()
+        m, v = self._state(fp)
+        views = lambda buf: {n: buf[o:o + fp.P[n].numel()].view(fp.P[n].shape).detach().cpu().clone()
+                             for n, o in zip(fp.names, fp.offsets)}
+        # the dropout seed is stored WITHOUT the saving rank's offset (rank-independent base + steps taken): every rank of a
+        # resumed data-parallel job re-applies its own offset and goes on drawing the masks its uninterrupted self would have
+        seed = getattr(self.model, "_drop_seed", None)
+        return {"step": self.step_count, "exp_avg": views(m), "exp_avg_sq": views(v),
+                "drop_seed_base": None if seed is None else (int(seed.item()) - rank_seed_offset()) % _SEED_MOD,
+                "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "beta": self.beta}}
+
+    def load_state_dict(self, sd: dict) -> None:
+        fp = self._fp if self._fp is not None else self.model.flat_params()
+        m, v = self._state(fp)
+        missing = [n for n in fp.names if n not in sd["exp_avg"] or n not in sd["exp_avg_sq"]]
+        if missing:
+            raise KeyError(f"optimizer state lacks {missing[:3]}{'...' if len(missing) > 3 else ''}")
+        with torch.no_grad():
+            for n, o in zip(fp.names, fp.offsets):
+                k = fp.P[n].numel()
+                m[o:o + k].copy_(sd["exp_avg"][n].reshape(-1).to(m.device, m.dtype))
+                v[o:o + k].copy_(sd["exp_avg_sq"][n].reshape(-1).to(v.device, v.dtype))
+        self.step_count = int(sd["step"])
+        val = None
+        if sd.get("drop_seed_base") is not None:     # resume draws the masks THIS rank's uninterrupted run would have drawn
+            val = (int(sd["drop_seed_base"]) + rank_seed_offset()) % _SEED_MOD
+        elif sd.get("drop_seed") is not None:        # (files of round 3: the saving rank's own seed)
+            val = int(sd["drop_seed"])
+        if val is not None:
+            object.__setattr__(self.model, "_drop_seed", torch.tensor([val], dtype=torch.int64, device=m.device))
+        h = sd.get("hyper", {})
+        self.lr, self.eps, self.wd = h.get("lr", self.lr), h.get("eps", self.eps), h.get("weight_decay", self.wd)
+        self.betas, self.beta = tuple(h.get("betas", self.betas)), h.get("beta", self.beta)
+
+    def _bump_dropout_seed(self) -> None:
+        """Attention dropout draws its masks from a device-resident seed inside the (possibly recorded) program; one bump
+        per step, issued here so that it is never part of a recording."""
+        seed = getattr(self.model, "_drop_seed", None)
+        if seed is not None and self.model.training and getattr(self.model, "_attn_drop", 0.0) > 0.0:
+            seed.add_(1)
+
+
+class Trainer(_AdamWState):
     """AdamW(lr, weight_decay=1e-2) training of a DOSTransformer(_phonon) module, all on libdosx.
 
     ``dist``: optional :class:`dostransformer_amd.dist.DataParallel` — shards are per-rank batches,
@@ -231,29 +306,6 @@ class Trainer:
     def per_crystal_keys(self) -> bool:
         """True: the two cross attentions attend over each crystal's own atoms (fixed at construction)."""
         return self._per_crystal_keys
-
-    def _state(self, fp):
-        """AdamW moments laid out like ``fp``.  When the parameters are re-homed (module moved to another device after
-        ``load_state_dict``, a different dead-parameter set, ...) the moments follow BY NAME instead of being reset:
-        ``step_count`` keeps counting, so zeroed moments would silently corrupt the bias correction."""
-        if self._fp is not fp:
-            m, v = torch.zeros_like(fp.flat), torch.zeros_like(fp.flat)
-            old = self._fp
-            if old is not None and self._m is not None:
-                old_off = dict(zip(old.names, old.offsets))
-                with torch.no_grad():
-                    for n, o in zip(fp.names, fp.offsets):
-                        oo = old_off.get(n)
-                        if oo is None:
-                            continue
-                        k = fp.P[n].numel()
-                        if old.P[n].numel() != k:
-                            raise RuntimeError(f"parameter {n} changed size under a running optimizer")
-                        m[o:o + k].copy_(self._m[oo:oo + k])
-                        v[o:o + k].copy_(self._v[oo:oo + k])
-            self._m, self._v, self._fp = m, v, fp
-            self._slots = OrderedDict()
-        return self._m, self._v
 
     # ---- the step, split where the data-parallel collectives go --------------------------------
     def _part_a(self, fp, g, m, st_n_global: Optional[int] = None):
@@ -606,52 +658,6 @@ class Trainer:
         self.step_count += 1
         ops.adamw(fp.flat, fp.grad, m, v, fp.total, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
                   self.step_count, 1.0)
-
-    # ---- checkpoint / resume (absent upstream) ------------------------------------
-    def state_dict(self) -> dict:
-        """Optimizer state keyed by the reference's parameter names, in ``torch.optim.AdamW`` vocabulary
-        (``exp_avg`` / ``exp_avg_sq`` / ``step``); together with ``model.state_dict()`` (reference key
-        layout, SURVEY.md §8b) this is a complete resume point."""
-        fp = self._fp if self._fp is not None else self.model.flat_params()
-        m, v = self._state(fp)
-        views = lambda buf: {n: buf[o:o + fp.P[n].numel()].view(fp.P[n].shape).detach().cpu().clone()
-                             for n, o in zip(fp.names, fp.offsets)}
-        # the dropout seed is stored WITHOUT the saving rank's offset (rank-independent base + steps taken): every rank of a
-        # resumed data-parallel job re-applies its own offset and goes on drawing the masks its uninterrupted self would have
-        seed = getattr(self.model, "_drop_seed", None)
-        return {"step": self.step_count, "exp_avg": views(m), "exp_avg_sq": views(v),
-                "drop_seed_base": None if seed is None else (int(seed.item()) - rank_seed_offset()) % _SEED_MOD,
-                "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "beta": self.beta}}
-
-    def load_state_dict(self, sd: dict) -> None:
-        fp = self._fp if self._fp is not None else self.model.flat_params()
-        m, v = self._state(fp)
-        missing = [n for n in fp.names if n not in sd["exp_avg"] or n not in sd["exp_avg_sq"]]
-        if missing:
-            raise KeyError(f"optimizer state lacks {missing[:3]}{'...' if len(missing) > 3 else ''}")
-        with torch.no_grad():
-            for n, o in zip(fp.names, fp.offsets):
-                k = fp.P[n].numel()
-                m[o:o + k].copy_(sd["exp_avg"][n].reshape(-1).to(m.device, torch.float32))
-                v[o:o + k].copy_(sd["exp_avg_sq"][n].reshape(-1).to(v.device, torch.float32))
-        self.step_count = int(sd["step"])
-        val = None
-        if sd.get("drop_seed_base") is not None:     # resume draws the masks THIS rank's uninterrupted run would have drawn
-            val = (int(sd["drop_seed_base"]) + rank_seed_offset()) % _SEED_MOD
-        elif sd.get("drop_seed") is not None:        # (files of round 3: the saving rank's own seed)
-            val = int(sd["drop_seed"])
-        if val is not None:
-            object.__setattr__(self.model, "_drop_seed", torch.tensor([val], dtype=torch.int64, device=m.device))
-        h = sd.get("hyper", {})
-        self.lr, self.eps, self.wd = h.get("lr", self.lr), h.get("eps", self.eps), h.get("weight_decay", self.wd)
-        self.betas, self.beta = tuple(h.get("betas", self.betas)), h.get("beta", self.beta)
-
-    def _bump_dropout_seed(self) -> None:
-        """Attention dropout draws its masks from a device-resident seed inside the (possibly recorded) program; one bump
-        per step, issued here so that it is never part of a recording."""
-        seed = getattr(self.model, "_drop_seed", None)
-        if seed is not None and self.model.training and getattr(self.model, "_attn_drop", 0.0) > 0.0:
-            seed.add_(1)
 
     def step(self, g, n_global: Optional[int] = None) -> torch.Tensor:
         self._bump_dropout_seed()

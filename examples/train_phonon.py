@@ -13,6 +13,12 @@ every crystal attending over its own atoms only (set_per_crystal_keys), so a bat
 batch-size-1 samples in one pass - the loss is the sum of their per-crystal terms (main_phDOS.py:109-114 crystal by crystal).
 
     python examples/train_phonon.py --float64 --epochs 2 --crystals 128 --hidden 64
+
+--float64 --fused runs that training through train64.Trainer64 instead (float64 loss and AdamW kernels, no autograd;
+--replay: recorded launch lists, one per exact batch shape): per-crystal keys as above, with the reference's loss of the
+batch as a whole - ONE rmse over all of its B*51 elements per branch (main_phDOS.py:109-114).
+
+    python examples/train_phonon.py --float64 --fused --replay --epochs 2 --crystals 128 --hidden 64
 """
 import argparse
 import os
@@ -46,9 +52,15 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="phonon_best.pt")
     ap.add_argument("--float64", action="store_true", help="the reference's float64 training with per-crystal keys")
+    ap.add_argument("--fused", action="store_true", help="with --float64: train64.Trainer64 instead of autograd + torch.optim.AdamW")
+    ap.add_argument("--replay", action="store_true", help="with --float64 --fused: replay recorded launch lists (one per exact batch shape: reshuffled epochs mostly record)")
     ap.add_argument("--per-crystal-keys", action="store_true",
                     help="fp32 trainer: attend over each crystal's own atoms - what the reference's batch_size = 1 training computes")
     args = ap.parse_args(argv)
+    if args.fused and not args.float64:
+        ap.error("--fused selects the float64 trainer: use it with --float64 (the fp32 run is fused already)")
+    if args.replay and not args.fused:
+        ap.error("--replay belongs to --float64 --fused (the fp32 run always replays)")
     dev = torch.device("cuda:0")
     torch.manual_seed(args.seed)
 
@@ -64,7 +76,7 @@ def main(argv=None):
     ds = {k: DeviceDataset([crystals[i] for i in idx], dev) for k, idx in split.items()}
 
     if args.float64:
-        return train_float64(args, ds, dev)
+        return train_float64_fused(args, ds, dev) if args.fused else train_float64(args, ds, dev)
     model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).to(dev)
     # coarse shape buckets: reshuffled batches then fall into a few dozen (N, E, n_max) buckets that are all recorded
     # within the first epoch (ghost padding is exact; it costs a few per cent of extra rows)
@@ -123,6 +135,35 @@ def train_float64(args, ds, dev):
         if rmse < best:
             best = rmse
             checkpoint.save(args.out, model)
+            t = evaluate.test_phonon(model, ds["test"].batches(args.batch_size))
+            print(f"            test rmse {t[0]:.4f} mse {t[1]:.4f} mae {t[2]:.4f} r2 {t[3]:.4f}   (saved {args.out})")
+    return {"best_valid_rmse": best, "train_loss": history}
+
+
+def train_float64_fused(args, ds, dev):
+    """float64 training through train64.Trainer64: forward program, loss kernel, backward program, flat AdamW - the loss stays
+    on the device, one host read per epoch.  The checkpoint carries the optimizer state (Trainer64.state_dict)."""
+    from dostransformer_amd.train64 import Trainer64
+    model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).double()
+    model = model.set_program_dtype(torch.float64).set_per_crystal_keys(True).to(dev)
+    trainer = Trainer64(model, lr=args.lr, beta=args.beta, replay=args.replay)
+    best, history = float("inf"), []
+    for epoch in range(args.epochs):
+        model.train()
+        t0, losses, seen = time.perf_counter(), [], 0
+        for batch in ds["train"].batches(args.batch_size, shuffle=True, seed=args.seed + epoch):
+            losses.append(trainer.step(batch).clone())            # (replay: the loss lives in the slot's static buffer)
+            seen += batch.num_graphs
+        loss = float(torch.stack(losses).mean())                  # one host read per epoch
+        dt = time.perf_counter() - t0
+        history.append(loss)
+        rmse, mse, mae, r2v = evaluate.test_phonon(model, ds["valid"].batches(args.batch_size))
+        print(f"[epoch {epoch + 1}/{args.epochs}] loss {loss:.4f} | {seen / dt:8.0f} crystals/s | "
+              f"valid rmse {rmse:.4f} mse {mse:.4f} mae {mae:.4f} r2 {r2v:.4f}"
+              + (f" | slots {trainer.slot_misses} recorded, {trainer.slot_hits} replayed" if args.replay else ""))
+        if rmse < best:
+            best = rmse
+            checkpoint.save(args.out, model, trainer)
             t = evaluate.test_phonon(model, ds["test"].batches(args.batch_size))
             print(f"            test rmse {t[0]:.4f} mse {t[1]:.4f} mae {t[2]:.4f} r2 {t[3]:.4f}   (saved {args.out})")
     return {"best_valid_rmse": best, "train_loss": history}

@@ -1122,6 +1122,25 @@ int dosx_dense_rows_bwd_f64(const double* dout, const double* xhat, const double
 int dosx_index_sum_f64(const double* src, int ld_src, const int32_t* idx, int n_src, double* dst, int ld_dst, int n_dst,
                        int W, int accumulate, dosx_stream_t stream);
 
+/* ---- float64 training step (csrc/f64_train.hip) --------------------------------------------------------------------------
+ * The tail of train64.Trainer64's step: phonon loss + gradient and the flat AdamW update on double operands.
+ *
+ * dosx_loss_phonon_f64: the float64 twin of dosx_loss_phonon (main_phDOS.py:109-114), one launch, one workgroup:
+ *     loss[0] = sqrt(mean (pg-y)^2) + beta sqrt(mean (ps-y)^2)           mean over the `count` = B*S elements
+ *     dpg = (pg-y) / (count rmse_g),   dps = beta (ps-y) / (count rmse_s)
+ *   sse (may be NULL) receives the two sums of squares.  Fixed-order reduction: two runs are bitwise equal.  IEEE sqrt and /.
+ *   An RMSE of exactly 0 has no gradient direction: that branch's gradient is written as zeros, never NaN (torch's autograd
+ *   gives 0/0 there; dosx_loss_phonon documents no convention for the case).  Single process only: no count_global.
+ * dosx_adamw_f64: torch.optim.AdamW's single-tensor update on flat double buffers, in torch's operation order:
+ *     p *= 1 - lr wd;  m += (g - m)(1 - beta1);  v = v beta2 + (1 - beta2) g g;
+ *     denom = sqrt(v) / sqrt(bc2) + eps;  p -= (lr / bc1) m / denom;         bc_k = 1 - beta_k^step, in double on the host
+ *   `step` is the 1-based step count (>= 1); p, g, m, v 16-byte aligned (16-byte accesses); n = 0 is a no-op.
+ * Both refuse NULL operands (sse excepted), count <= 0, n < 0, step < 1 and misaligned buffers with -22 and a message. */
+int dosx_loss_phonon_f64(const double* pg, const double* ps, const double* y, double beta, double* dpg, double* dps,
+                         double* loss, double* sse, int count, dosx_stream_t stream);
+int dosx_adamw_f64(double* p, const double* g, double* m, double* v, int64_t n, double lr, double beta1, double beta2,
+                   double eps, double weight_decay, int step, dosx_stream_t stream);
+
 const char* dosx_last_error(void);
 int dosx_version(void);
 
