@@ -452,23 +452,104 @@ __global__ void collate_pad_gather_kernel(const DosxCollate d) {
   }
 }
 
+// The same rows for the float64 program's bucket (train64.Trainer64.step_dataset): x [N_pad,Fa], edge features [E_pad,Fe]
+// and targets [B,S] hold T = double behind the descriptor's feature pointers, system stays int32.  A pure copy, so it is laid
+// out for the memory system: one wave per row of x / of the targets - the row's source is looked up once, then the lanes move
+// consecutive 16-byte vectors of it (`vec`: both tables 16-byte aligned and the row a whole number of vectors; 118 doubles are
+// 59 of them) - and one wave per 64 consecutive edges, a thread per edge.  No division per element; ghost rows are zeros.
+template <typename T>
+__device__ __forceinline__ void collate_copy_row(T* __restrict__ dst, const T* __restrict__ src, int W, bool vec, int lane) {
+  constexpr int V = 16 / sizeof(T);
+  typedef T vec_t __attribute__((ext_vector_type(V)));
+  if (vec) {
+    vec_t* dv = reinterpret_cast<vec_t*>(dst);
+    const vec_t* sv = reinterpret_cast<const vec_t*>(src);
+    for (int i = lane; i < W / V; i += 64) {
+      vec_t v;
+      for (int j = 0; j < V; ++j) v[j] = T(0);
+      if (src) v = sv[i];
+      dv[i] = v;
+    }
+  } else {
+    for (int c = lane; c < W; c += 64) dst[c] = src ? src[c] : T(0);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void collate_pad_gather_rows_kernel(const DosxCollate d, int vec_x, int vec_t) {
+  const T* x_all = reinterpret_cast<const T*>(d.x_all);
+  const T* edge_all = reinterpret_cast<const T*>(d.edge_feat_all);
+  const T* target_all = reinterpret_cast<const T*>(d.target_all);
+  T* x = reinterpret_cast<T*>(d.x);
+  T* edge = reinterpret_cast<T*>(d.edge_feat);
+  T* target = reinterpret_cast<T*>(d.target);
+  const int lane = threadIdx.x & 63;
+  const int64_t spans = ((int64_t)d.E_pad + 63) / 64;
+  const int64_t items = (int64_t)d.N_pad + d.B + spans, step = (int64_t)gridDim.x * 4;
+  for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < items; w += step) {       // wave-uniform
+    if (w < d.N_pad) {
+      const int r = d.node_row[w];
+      collate_copy_row<T>(x + w * d.Fa, r >= 0 ? x_all + (int64_t)r * d.Fa : nullptr, d.Fa, vec_x != 0, lane);
+    } else if (w < (int64_t)d.N_pad + d.B) {
+      const int b = (int)(w - d.N_pad), c = d.sel[b];
+      if (d.S > 0) collate_copy_row<T>(target + (int64_t)b * d.S, target_all + (int64_t)c * d.S, d.S, vec_t != 0, lane);
+      if (lane == 0) d.system[b] = d.system_all[c];
+    } else {
+      const int64_t e = (w - d.N_pad - d.B) * 64 + lane;
+      if (e < d.E_pad) {
+        const int r = d.edge_row[e];
+        for (int c = 0; c < d.Fe; ++c) edge[e * d.Fe + c] = r >= 0 ? edge_all[(int64_t)r * d.Fe + c] : T(0);
+      }
+    }
+  }
+}
+
 }  // namespace
 
-extern "C" int dosx_collate_padded(const DosxCollate* dp, dosx_stream_t stream) {
-  DOSX_CHECK_ARG(dp != nullptr, "dosx_collate_padded: null descriptor");
+// The descriptor checks the two entries share: -> 0 or the error code
+static int collate_padded_check(const DosxCollate* dp, const char* who) {
+  DOSX_CHECK_ARG(dp != nullptr, "%s: null descriptor", who);
   const DosxCollate& d = *dp;
   DOSX_CHECK_ARG(d.B > 0 && d.N >= d.B && d.E >= 0 && d.N_pad > d.N && d.E_pad >= d.E && d.n_max > 0,
-                 "dosx_collate_padded: bad sizes B=%d N=%d E=%d N_pad=%d E_pad=%d n_max=%d (needs >= 1 ghost node)", d.B, d.N, d.E,
+                 "%s: bad sizes B=%d N=%d E=%d N_pad=%d E_pad=%d n_max=%d (needs >= 1 ghost node)", who, d.B, d.N, d.E,
                  d.N_pad, d.E_pad, d.n_max);
-  DOSX_CHECK_ARG(d.Fa > 0 && d.Fe > 0 && d.S >= 0 && d.n_glob >= 0, "dosx_collate_padded: bad widths");
+  DOSX_CHECK_ARG(d.Fa > 0 && d.Fe > 0 && d.S >= 0 && d.n_glob >= 0, "%s: bad widths", who);
   DOSX_CHECK_ARG(d.sel && d.out_node_ptr && d.out_edge_ptr && d.node_ptr_all && d.edge_ptr_all && d.src_all && d.dst_all &&
                      d.perm_src_all && d.rowptr_dst_all && d.rowptr_src_all && d.inv_deg_all && d.x_all && d.edge_feat_all &&
                      d.system_all && (d.S == 0 || d.target_all) && (d.n_glob == 0 || d.glob_all),
-                 "dosx_collate_padded: null input");
+                 "%s: null input", who);
   DOSX_CHECK_ARG(d.x && d.edge_feat && d.system && (d.S == 0 || d.target) && (d.n_glob == 0 || d.glob) && d.src && d.dst &&
                      d.perm_src && d.rowptr_dst && d.rowptr_src && d.graph_ptr && d.node_graph && d.dense_row && d.inv_deg &&
                      d.node_row && d.edge_row,
-                 "dosx_collate_padded: null output");
+                 "%s: null output", who);
+  return 0;
+}
+
+extern "C" int dosx_collate_padded_f64(const DosxCollate* dp, dosx_stream_t stream) {
+  if (int rc = collate_padded_check(dp, "dosx_collate_padded_f64")) return rc;
+  const DosxCollate& d = *dp;
+  DOSX_CHECK_ARG(d.n_glob == 0, "dosx_collate_padded_f64: n_glob=%d (the float64 program is the phonon one: no globals)", d.n_glob);
+  DOSX_CHECK_ARG(d.seg_tile == nullptr, "dosx_collate_padded_f64: seg_tile must be NULL (the float64 program has no tiled message GEMM)");
+  auto al8 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; };
+  DOSX_CHECK_ARG(al8(d.x_all) && al8(d.edge_feat_all) && al8(d.target_all) && al8(d.x) && al8(d.edge_feat) && al8(d.target),
+                 "dosx_collate_padded_f64: a float64 table is not 8-byte aligned");
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const int vec_x = d.Fa % 2 == 0 && al16(d.x_all) && al16(d.x);
+  const int vec_t = d.S > 0 && d.S % 2 == 0 && al16(d.target_all) && al16(d.target);
+  hipStream_t s = to_stream(stream);
+  hipLaunchKernelGGL(collate_pad_nodes_kernel, dim3(ceil_div(d.N_pad + 1, 256)), dim3(256), 0, s, d);
+  if (d.E_pad > 0) hipLaunchKernelGGL(collate_pad_edges_kernel, dim3(ceil_div(d.E_pad, 256)), dim3(256), 0, s, d);
+  const int64_t items = (int64_t)d.N_pad + d.B + ((int64_t)d.E_pad + 63) / 64;
+  int64_t blocks = (items + 3) / 4;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(collate_pad_gather_rows_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, s, d, vec_x, vec_t);
+  DOSX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int dosx_collate_padded(const DosxCollate* dp, dosx_stream_t stream) {
+  if (int rc = collate_padded_check(dp, "dosx_collate_padded")) return rc;
+  const DosxCollate& d = *dp;
   hipStream_t s = to_stream(stream);
   hipLaunchKernelGGL(collate_pad_nodes_kernel, dim3(ceil_div(d.N_pad + 1, 256)), dim3(256), 0, s, d);
   if (d.E_pad > 0) hipLaunchKernelGGL(collate_pad_edges_kernel, dim3(ceil_div(d.E_pad, 256)), dim3(256), 0, s, d);

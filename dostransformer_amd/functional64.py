@@ -13,6 +13,13 @@ zero-padded dense key rows.
 train64.Trainer64 records this program (ops.RECORDER) and replays it on static buffers: every buffer the program creates goes
 through ops.alloc64 / ops.keep_alive, and the torch casts in its body (``_f64``, ``g.system.to(int32)``, ``ddos.to(float64)``)
 hand back their argument when it already has the dtype and layout the kernels read - which the slot buffers have.
+
+The DOSTransformer_phonon program is padding-safe: it runs on a ghost-padded batch (``batch.pad_batch``, or a bucket filled by
+``DeviceDataset.collate_into``).  Forward, no kernel reduces across rows other than over a node's own edges (CSR row pointers) or
+a crystal's own atoms (``graph_ptr``), so the real rows are bitwise those of the unpadded batch; backward, the sum pool's
+gradient reads a spare zero row B for the ghost nodes (``_dpool_rows``) and every gradient that reaches a ghost row is an exact
+zero, so the parameter gradients differ from the unpadded ones only by how the row sums of ``wgrad64`` / ``colsum64`` are
+grouped.  (Graphnetwork_phonon's program is not: its sum-pool backward still indexes [B, H] rows.)
 """
 from __future__ import annotations
 
@@ -173,6 +180,21 @@ def graphnetwork_phonon_bwd(P: Params, G: Params, cfg, m: GraphMeta, saved, ddos
 
 
 # ---- DOSTransformer_phonon ------------------------------------------------------------------------------------------------
+def _is_padded(g) -> bool:
+    """A ghost-padded batch (batch.pad_batch) or bucket (train64._Slot64.empty): it carries its real node count."""
+    return getattr(g, "real_nodes", None) is not None
+
+
+def _dpool_rows(dev, B: int, H: int, padded: bool) -> torch.Tensor:
+    """The sum pool's gradient buffer, [B + 1, H]: the GEMM writes rows [0, B); row B is what a ghost node's ``node_graph``
+    entry (= B, batch.pad_batch) gathers.  It is zeroed here by torch - once, when the buffer is made, and so outside a recorded
+    launch list, which keeps the buffer alive and never writes that row again.  An unpadded batch never reads it."""
+    dpool = alloc64(dev, B + 1, H)
+    if padded:
+        dpool[B:].zero_()
+    return dpool
+
+
 def _gnn_trunk_fwd(P: Params, cfg, g, m: GraphMeta, enc: str):
     vec = g.edge_vec
     if m.edge_perm is not None:
@@ -297,7 +319,8 @@ def dostransformer_phonon_fwd(P: Params, cfg, g, m: GraphMeta, drop=None, per_cr
     hs, c2 = _encoder_fwd(P, "transformer_self", dosin, S, 2 * B, kv_s, S, 2 * B, T, dr(64))
     hsrc, c3 = _encoder_fwd(P, "transformer_source", hs, S, 2 * B, kv_n, nmax, B, T, dr(128), kp)
     dos = gemm64(2 * BS, 1, [seg64(hsrc)], P["out_layer.weight"], alloc64(dev, 2 * BS, 1), bias=P["out_layer.bias"])
-    ctx = (ctrunk, kv_n, rstd_n, c1, pool, graph, prow, sysidx, seg_g, seg_s, pre, dosin, ptr_s, kv_s, rstd_s, c2, c3, hsrc, E1)
+    ctx = (ctrunk, kv_n, rstd_n, c1, pool, graph, prow, sysidx, seg_g, seg_s, pre, dosin, ptr_s, kv_s, rstd_s, c2, c3, hsrc, E1,
+           _is_padded(g))
     return dos.view(2 * B, S), xL, ctx
 
 
@@ -305,7 +328,7 @@ def dostransformer_phonon_bwd(P: Params, G: Params, cfg, m: GraphMeta, ctx, ddos
                               dx_ext: Optional[torch.Tensor]) -> None:
     """Writes the gradient of every live parameter into G from ddos [2B, S] and the gradient of x_L (or None)."""
     (ctrunk, kv_n, rstd_n, c1, pool, graph, prow, sysidx, seg_g, seg_s, pre, dosin, ptr_s, kv_s, rstd_s, c2, c3, hsrc,
-     E1) = ctx
+     E1, padded) = ctx
     H, S, B, N = cfg.H, cfg.S, m.num_graphs, m.num_nodes
     nmax = m.n_max
     BS = B * S
@@ -328,7 +351,7 @@ def dostransformer_phonon_bwd(P: Params, G: Params, cfg, m: GraphMeta, ctx, ddos
     dgraph = reduce_rows64(rows_add64(BS, dcat_g[:, H:], dcat_s[:, H:2 * H]), B, S, S, 1)
     index_sum64(reduce_rows64(dcat_s[:, 2 * H:], B, S, S, 1), sysidx, G["prompt_token.weight"])
     _linear_grads(G, "GN_decoder.mlp.0", B, dgraph, [seg64(pool)])
-    dpool = gemm64(B, H, [seg64(dgraph)], P["GN_decoder.mlp.0.weight"], alloc64(dev, B, H), w_layout=1)
+    dpool = gemm64(B, H, [seg64(dgraph)], P["GN_decoder.mlp.0.weight"], _dpool_rows(dev, B, H, padded), w_layout=1)
     dx0 = _encoder_bwd(P, G, c1, dE1, dkv_n, True)
     reduce_rows64(dx0, S, B, 1, S, out=G["embeddings.weight"])                         # energy s: rows b * S + s
     dx = rows_add64(N, dpool, None if dx_ext is None else dx_ext.to(torch.float64).contiguous(), ia=m.node_graph)

@@ -133,6 +133,21 @@ class DeviceDataset:
             self._tables32 = t
         return t
 
+    def _f64_tables(self):
+        """float64 / int32 device tables of a phonon dataset for the float64 program's buckets (train64.Trainer64.step_dataset):
+        the resident tensors themselves when the dataset was built with ``dtype=torch.float64`` (``.to`` / ``.contiguous()``
+        hand back their argument then - no copy, and no fp32 copy either); built once, on first use."""
+        t = getattr(self, "_tables64", None)
+        if t is None:
+            if "edge_vec" not in self._edge or "phdos" not in self._graph or "system" not in self._graph:
+                raise ValueError("DeviceDataset: the float64 collate needs a phonon dataset (edge_vec, phdos, system)")
+            f64 = lambda v: v.to(torch.float64).contiguous()
+            t = {"x": f64(self._x), "edge": f64(self._edge["edge_vec"]), "edge_key": "edge_vec",
+                 "target": f64(self._graph["phdos"]), "target_key": "phdos", "glob": None,
+                 "system": self._graph["system"].to(torch.int32).contiguous()}
+            self._tables64 = t
+        return t
+
     def bucket_dims(self, indices, n_max: Optional[int] = None):
         """(idx, N, E, n_max) of a selection, from host-side counts only."""
         idx = np.asarray(list(indices), np.int64)
@@ -148,10 +163,18 @@ class DeviceDataset:
         """Write the batch of crystals ``idx`` into the STATIC ghost-padded buffers of ``g`` (a bucket of
         ``train.Trainer``): one small host->device copy (selection + prefix sums) and one ``dosx_collate_padded`` call
         (3 launches).  The result is what ``pad_batch(self.collate(idx), N_pad, E_pad)`` holds in the fields the kernels read
-        (tests/test_gpu_graph.py::test_collate_into_matches_pad_batch)."""
+        (tests/test_gpu_graph.py::test_collate_into_matches_pad_batch).  A bucket whose ``x`` is float64 (``train64.Trainer64``)
+        is filled from the float64 tables by ``dosx_collate_padded_f64``; it has no tile table."""
         from ._lib import Collate
         import ctypes as C
-        t = self._f32_tables()
+        f64 = g.x.dtype == torch.float64
+        t = self._f64_tables() if f64 else self._f32_tables()
+        if f64:
+            for k in ("x", t["edge_key"], t["target_key"]):
+                if g[k].dtype != torch.float64 or not g[k].is_contiguous():
+                    raise ValueError(f"collate_into: field {k} of a float64 bucket must be float64 and contiguous, got {g[k].dtype}")
+            if g.meta.seg_tile is not None:
+                raise ValueError("collate_into: a float64 bucket has no message-GEMM tile table (seg_tile)")
         m = g.meta
         B = int(idx.shape[0])
         nn, ne = self.n_nodes[idx], self.n_edges[idx]
@@ -190,6 +213,10 @@ class DeviceDataset:
             d.tile_off_all, d.tile_e_all, d.tile_n_all = self._tile_off.data_ptr(), self._tile_e.data_ptr(), self._tile_n.data_ptr()
             d.tile_p_all = self._tile_p.data_ptr()
             d.seg_tile = m.seg_tile.data_ptr()
+        if f64:
+            ops._call("dosx_collate_padded_f64", C.byref(d), ops._stream(),
+                      w=lambda: ("collate_padded_f64", "collate_pad", "hbm", 16.0 * (d.N_pad * d.Fa + d.E_pad * d.Fe)))
+            return
         ops._call("dosx_collate_padded", C.byref(d), ops._stream(),
                   w=lambda: ("collate_padded", "collate_pad", "hbm", 8.0 * (d.N_pad * d.Fa + d.E_pad * d.Fe)))
 

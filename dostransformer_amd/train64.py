@@ -6,14 +6,21 @@ flat float64 AdamW kernel.  No autograd graph, no torch loss ops, no per-paramet
 the fp32 program: the first step on a batch shape runs normally on static buffers while every libdosx call is recorded;
 later steps of that shape copy the batch into the buffers and replay the list from C.
 
-Limits: single GPU (no ``dist``), no HIP-graph mode, no ``Predictor`` counterpart, and slots are keyed by the batch's EXACT
-shape (N, E, B, n_max).  The float64 program is not padding-safe - ``rows_add64(..., ia=node_graph)`` would read row B of a
-[B, H] buffer for a ghost node - so ghost-padded batches (``batch.pad_batch``) are refused and there is no ``bucket`` /
-``promote`` / ``step_dataset``.
+Slots are keyed by the batch's EXACT shape (N, E, B, n_max) by default, and ghost-padded batches are refused.
+``Trainer64(bucket=(node_step, edge_step))`` keys them by shape BUCKET instead, as the fp32 ``Trainer`` does: the float64
+program is padding-safe (functional64), so an unpadded batch is ghost-padded (``batch.pad_batch`` - exact) to
+``batch.bucket_sizes(N, E, *bucket)`` and every batch of a bucket replays one recording; without ``replay`` an already padded
+batch is run as it is.  ``step_dataset(ds, indices)`` collates a selection of a device-resident float64
+``loader.DeviceDataset`` straight into the bucket's static buffers (``dosx_collate_padded_f64``) - a shuffled epoch then
+replays - and ``promote`` lets a bucket that is asked for the first time run in a slightly larger live one instead of
+recording.  ``predict.Predictor64`` is the forward-only counterpart.
+
+Limits: single GPU (no ``dist``), no HIP-graph mode.
 """
 from __future__ import annotations
 
 from collections import OrderedDict
+from typing import Optional
 
 import torch
 
@@ -21,30 +28,65 @@ from . import functional64 as F64
 from . import ops
 from ._lib import DosxError
 from ._models import DOSTransformerBase
-from .batch import CrystalBatch, GraphMeta, graph_meta
-from .train import _AdamWState, _Loaded, _META_TENSORS
+from .batch import CrystalBatch, GraphMeta, bucket_sizes, graph_meta, pad_batch
+from .train import _AdamWState, _Loaded, _META_TENSORS, promote_key
 
 _F64_FIELDS = ("x", "edge_vec", "phdos")
 
 
 class _Slot64:
-    """Static buffers + recorded program of one exact batch shape: what the float64 program reads, in the dtype it reads it
-    (float64 contiguous features and targets, int32 ``system``, clones of the GraphMeta tensors) - so that the casts in the
-    body of ``functional64`` are no-ops on them and the recording holds libdosx calls only."""
+    """Static buffers + recorded program of one batch shape (exact, or a ghost-padded bucket): what the float64 program reads,
+    in the dtype it reads it (float64 contiguous features and targets, int32 ``system``, clones of the GraphMeta tensors) - so
+    that the casts in the body of ``functional64`` are no-ops on them and the recording holds libdosx calls only.  The
+    buffers of a padded shape carry ``real_nodes`` (the real node count of the batch they hold), like a ``pad_batch`` batch."""
 
-    def __init__(self, g, m: GraphMeta, device):
-        f = {k: torch.empty(g[k].shape, dtype=torch.float64, device=device) for k in _F64_FIELDS}
+    def __init__(self, g, m: GraphMeta, device, fields=_F64_FIELDS):
+        f = {k: torch.empty(g[k].shape, dtype=torch.float64, device=device) for k in fields}
         f["system"] = torch.empty(g["system"].shape, dtype=torch.int32, device=device)
         meta = GraphMeta(num_nodes=m.num_nodes, num_edges=m.num_edges, num_graphs=m.num_graphs, n_max=m.n_max, edge_perm=None,
                          seg_tile=None, **{k: torch.empty_like(getattr(m, k), device=device) for k in _META_TENSORS})
-        self.g = CrystalBatch(f, m.num_graphs, meta)
+        self._setup(CrystalBatch(f, m.num_graphs, meta), fields)
+
+    def _setup(self, g: CrystalBatch, fields) -> None:
+        self.fields = tuple(fields)
+        self.g = g
         self.prog = self.loss = self.out = None
+        self.scratch = None
         self._loaded = None
 
-    @staticmethod
-    def _signature(g, m: GraphMeta) -> _Loaded:
+    @classmethod
+    def empty(cls, device, B: int, n_pad: int, e_pad: int, n_max: int, Fa: int, Fe: int, S: int) -> "_Slot64":
+        """Uninitialised static buffers of a bucket, to be filled by ``DeviceDataset.collate_into`` (no source batch)."""
+        f64 = lambda *s: torch.empty(*s, dtype=torch.float64, device=device)
+        i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=device)
+        f = {"x": f64(n_pad, Fa), "edge_vec": f64(e_pad, Fe), "phdos": f64(B, S), "system": i32(B)}
+        meta = GraphMeta(num_nodes=n_pad, num_edges=e_pad, num_graphs=B, n_max=n_max, edge_perm=None, src=i32(e_pad),
+                         dst=i32(e_pad), rowptr_dst=i32(n_pad + 1), perm_src=i32(e_pad), rowptr_src=i32(n_pad + 1),
+                         graph_ptr=i32(B + 1), node_graph=i32(n_pad), dense_row=i32(n_pad),
+                         inv_deg=torch.empty(n_pad, dtype=torch.float32, device=device), seg_tile=None)
+        self = cls.__new__(cls)
+        self._setup(CrystalBatch(f, B, meta), _F64_FIELDS)
+        return self
+
+    def collate_scratch(self):
+        """Index scratch of ``DeviceDataset.collate_into``, sized from the slot's own padded counts (made on first use)."""
+        if self.scratch is None:
+            m = self.g.meta
+            i32 = lambda n: torch.empty(n, dtype=torch.int32, device=m.src.device)
+            self.scratch = {"small": i32(4 * m.num_graphs + 3), "node_row": i32(m.num_nodes), "edge_row": i32(m.num_edges)}
+        return self.scratch
+
+    def set_real_nodes(self, n: Optional[int]) -> None:
+        object.__setattr__(self.g, "real_nodes", n)
+
+    @property
+    def real_nodes(self) -> int:
+        n = getattr(self.g, "real_nodes", None)
+        return self.g.meta.num_nodes if n is None else n
+
+    def _signature(self, g, m: GraphMeta) -> _Loaded:
         """Identity + in-place version of everything load() copies (train._Slot._signature)."""
-        return _Loaded(g, [g[k] for k in _F64_FIELDS + ("system",)] + [getattr(m, k) for k in _META_TENSORS])
+        return _Loaded(g, [g[k] for k in self.fields + ("system",)] + [getattr(m, k) for k in _META_TENSORS])
 
     def load(self, g, m: GraphMeta) -> None:
         """Copy a batch of this shape into the static buffers (nothing when they hold this very batch, unwritten since): one
@@ -54,9 +96,10 @@ class _Slot64:
         if sig == self._loaded:
             return
         self._loaded = None
+        self.set_real_nodes(getattr(g, "real_nodes", None))
         pairs = []
         sm = self.g.meta
-        for dst, src in [(self.g[k], g[k]) for k in _F64_FIELDS + ("system",)] + [(getattr(sm, k), getattr(m, k)) for k in _META_TENSORS]:
+        for dst, src in [(self.g[k], g[k]) for k in self.fields + ("system",)] + [(getattr(sm, k), getattr(m, k)) for k in _META_TENSORS]:
             if src.shape != dst.shape:
                 raise ValueError(f"batch field of shape {tuple(src.shape)} loaded into a slot recorded with {tuple(dst.shape)}")
             if src.dtype == dst.dtype and src.device == dst.device and src.is_contiguous():
@@ -76,21 +119,34 @@ class Trainer64(_AdamWState):
     recorded slot's key.  ``step(g)`` returns the loss as a 0-dim float64 device tensor; ``state_dict()`` /
     ``load_state_dict()`` use ``train.Trainer``'s vocabulary with float64 moments.  ``slot_hits`` / ``slot_misses`` count the
     replayed and the recorded steps of ``replay=True``; at most ``max_slots`` shapes stay recorded (least recently used out).
+
+    ``bucket=None``: one slot per exact batch shape, ghost-padded batches are refused.  ``bucket=(node_step, edge_step)``: with
+    ``replay`` an unpadded batch is ghost-padded to ``bucket_sizes(N, E, *bucket)`` (a batch that carries ``real_nodes`` is taken
+    as it is) and slots are keyed by the padded shape; without ``replay`` a padded batch is run as it is and nothing is padded.
+    ``promote``: the largest relative excess of node / edge rows at which ``step_dataset`` runs a bucket it sees for the first
+    time in a live larger one instead of recording it (``slot_promoted`` counts those steps; 0: never).
     """
 
     def __init__(self, model, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2, betas=(0.9, 0.999),
-                 eps: float = 1e-8, replay: bool = False, max_slots: int = 32):
+                 eps: float = 1e-8, replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0):
         self._require_f64(model)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, tuple(betas), eps
         self.replay = bool(replay)
         self.max_slots = int(max_slots)
         if self.max_slots < 1:
             raise ValueError(f"Trainer64: max_slots must be at least 1, got {max_slots}")
+        self.bucket = None if bucket is None else tuple(int(b) for b in bucket)
+        if self.bucket is not None and (len(self.bucket) != 2 or min(self.bucket) < 1):
+            raise ValueError(f"Trainer64: bucket is None or (node_step, edge_step), both at least 1, got {bucket}")
+        self.promote = float(promote)
+        if self.promote < 0.0:
+            raise ValueError(f"Trainer64: promote must not be negative, got {promote}")
         self.step_count = 0
         self._m = self._v = self._fp = None
         self.last_outputs = None
         self._slots: "OrderedDict[tuple, _Slot64]" = OrderedDict()
-        self.slot_hits = self.slot_misses = 0
+        self.slot_hits = self.slot_misses = self.slot_promoted = 0
+        self._seen = {}
 
     @staticmethod
     def _require_f64(model) -> None:
@@ -105,18 +161,18 @@ class Trainer64(_AdamWState):
     def _refuse(self, g) -> None:
         """What a step cannot run on - raised before anything (the dropout seed included) has changed."""
         self._require_f64(self.model)
-        if getattr(g, "real_nodes", None) is not None:
-            raise DosxError("Trainer64: ghost-padded batches (batch.pad_batch) are refused - the float64 program is not "
-                            "padding-safe (a ghost node's node_graph entry indexes past the per-crystal rows)")
+        if self.bucket is None and getattr(g, "real_nodes", None) is not None:
+            raise DosxError("Trainer64: ghost-padded batches (batch.pad_batch) are refused without bucket=(node_step, "
+                            "edge_step) - slots are keyed by the exact shape of an unpadded batch")
 
     def _prepare(self, g):
-        """-> (flat parameters, GraphMeta on the device, dropout operand); everything that may touch the host or torch's
-        RNG (first use: flattening, the dropout seed) happens here, in front of any recording."""
+        """-> (flat parameters, dropout operand); everything that may touch the host or torch's RNG (first use: flattening, the
+        dropout seed) happens here, in front of any recording."""
         model = self.model
         dev = model._module_device()
         fp = model._ensure_flat(dev, g)
         self._state(fp)
-        return fp, graph_meta(g, dev), model._dropout(dev, False)
+        return fp, model._dropout(dev, False)
 
     def _program(self, fp, g, m: GraphMeta, drop):
         """forward program, loss kernel, backward program on the batch ``g``: -> (loss, outputs)."""
@@ -129,42 +185,81 @@ class Trainer64(_AdamWState):
         F64.dostransformer_phonon_bwd(fp.P, fp.G, cfg, m, ctx, ddos, None)
         return loss[0], (dos[:B], xL, dos[B:])
 
+    def _set_outputs(self, out, n_real: Optional[int]) -> None:
+        """(dos_global, x_L, dos_system) of the step; the ghost rows of a padded batch's x_L are cut off."""
+        self.last_outputs = out if n_real is None else (out[0], out[1][:n_real], out[2])
+
     def forward_backward(self, g, _bump: bool = True) -> torch.Tensor:
         """Forward + loss + backward; leaves the gradients in the flat buffer.  Returns the loss (0-dim float64 device tensor)."""
         if _bump:                      # a direct forward_backward() + optimizer_step() loop draws fresh dropout masks too
             self._refuse(g)
             self._bump_dropout_seed()
-        fp, m, drop = self._prepare(g)
+        fp, drop = self._prepare(g)
+        m = graph_meta(g, fp.flat.device)
         with torch.no_grad():
             if self.replay:
                 return self._slot_step(fp, g, m, drop)
-            loss, self.last_outputs = self._program(fp, g, m, drop)
+            loss, out = self._program(fp, g, m, drop)
+            self._set_outputs(out, getattr(g, "real_nodes", None))
             return loss
 
     # ---- replay --------------------------------------------------------------------------------------------------------
-    def _slot_step(self, fp, g, m: GraphMeta, drop) -> torch.Tensor:
-        if m.edge_perm is not None:
-            raise ValueError("Trainer64(replay=True) needs batches with destination-sorted edges (collate(sort_edges=True))")
-        # what decides the launch list besides the shape: per-crystal keys, dropout on / off (train / eval mode, p > 0), the
-        # tests' fp64-softmax switch - a slot recorded under one setting is never replayed under another
-        key = (m.num_nodes, m.num_edges, m.num_graphs, m.n_max, bool(self.model.per_crystal_keys), drop is not None,
-               None if drop is None else drop[0], bool(F64.SOFTMAX64), float(self.beta))
+    def _key(self, n: int, e: int, B: int, n_max: int, drop) -> tuple:
+        """What decides the launch list: the (padded) shape, then per-crystal keys, dropout on / off (train / eval mode, p > 0),
+        the tests' fp64-softmax switch - a slot recorded under one setting is never replayed under another."""
+        return (n, e, B, n_max, bool(self.model.per_crystal_keys), drop is not None, None if drop is None else drop[0],
+                bool(F64.SOFTMAX64), float(self.beta))
+
+    def _lookup(self, key, allow_promote: bool = False):
+        """(slot or None) of a key, with the LRU / hit-rate bookkeeping of ``train.Trainer._lookup``.  ``allow_promote``
+        (step_dataset: the batch is collated straight into whatever bucket it gets): a bucket that is asked for the FIRST time
+        runs in the smallest live bucket that holds it with at most ``promote`` more node / edge rows, if there is one - the
+        shapes a reshuffled epoch shows once never pay for a recording, a shape that comes back is recorded on its second visit."""
         slot = self._slots.get(key)
+        if slot is None and allow_promote and self.promote > 0:
+            seen = self._seen.get(key, 0)
+            self._seen[key] = seen + 1
+            if seen == 0:
+                host = promote_key(self._slots.keys(), key, self.promote)
+                if host is not None:
+                    self.slot_hits += 1
+                    self.slot_promoted += 1
+                    self._slots.move_to_end(host)
+                    return self._slots[host]
         if slot is None:
             self.slot_misses += 1
             while len(self._slots) >= self.max_slots:          # evict the least recently used shape
                 self._slots.popitem(last=False)
-            slot = _Slot64(g, m, fp.flat.device)
-            slot.load(g, m)
-            self._record(slot, fp, drop)                       # this IS the step for this batch (run + record)
-            self._slots[key] = slot
         else:
             self.slot_hits += 1
             self._slots.move_to_end(key)
-            slot.load(g, m)
+        return slot
+
+    def _run_slot(self, slot: _Slot64, fp, drop, fresh: bool) -> torch.Tensor:
+        """The step on a slot whose static buffers hold the batch: recorded on first use, replayed afterwards."""
+        if fresh:
+            self._record(slot, fp, drop)                       # this IS the step for this batch (run + record)
+        else:
             slot.prog.run()
-        self.last_outputs = slot.out
+        self._set_outputs(slot.out, getattr(slot.g, "real_nodes", None))
         return slot.loss
+
+    def _slot_step(self, fp, g, m: GraphMeta, drop) -> torch.Tensor:
+        if m.edge_perm is not None:
+            raise ValueError("Trainer64(replay=True) needs batches with destination-sorted edges (collate(sort_edges=True))")
+        if self.bucket is not None and getattr(g, "real_nodes", None) is None:       # not padded yet: pad on the fly
+            g = pad_batch(g, *bucket_sizes(m.num_nodes, m.num_edges, *self.bucket))
+            m = g.meta
+        key = self._key(m.num_nodes, m.num_edges, m.num_graphs, m.n_max, drop)
+        slot = self._lookup(key)
+        fresh = slot is None
+        if fresh:
+            slot = _Slot64(g, m, fp.flat.device)
+        slot.load(g, m)
+        loss = self._run_slot(slot, fp, drop, fresh)
+        if fresh:
+            self._slots[key] = slot
+        return loss
 
     def _record(self, slot: _Slot64, fp, drop) -> None:
         """Run the step once on the slot's static buffers while recording every launch."""
@@ -186,6 +281,39 @@ class Trainer64(_AdamWState):
             if ops.RECORDER.active:
                 ops.RECORDER.end()
             ops.KERNEL_TIMER.enabled = timer_on
+
+    def step_dataset(self, ds, indices, n_max: Optional[int] = None) -> torch.Tensor:
+        """One training step on the crystals ``indices`` of a device-resident ``loader.DeviceDataset`` (float64 tables:
+        ``DeviceDataset(..., dtype=torch.float64)`` holds them without a copy).  With ``replay`` and ``bucket`` the batch is
+        collated by ``dosx_collate_padded_f64`` STRAIGHT INTO the static buffers of its shape bucket, ghost padding included, and
+        the bucket's recorded program is replayed (recorded on first use, or - ``promote`` - run in a live larger bucket):
+        bitwise ``step(pad_batch(ds.collate(indices, n_max=n_max), *bucket_sizes(N, E, *bucket)))``.  Otherwise it is
+        ``step(ds.collate(indices, n_max=n_max))``.  ``n_max`` may exceed the selection's largest crystal, so that one value
+        serves a whole dataset (with per-crystal keys and no dropout the numbers do not depend on it)."""
+        if not (self.replay and self.bucket is not None):
+            return self.step(ds.collate(indices, n_max=n_max))
+        self._require_f64(self.model)
+        idx, N, E, n_max = ds.bucket_dims(indices, n_max)
+        B = int(idx.shape[0])
+        n_pad, e_pad = bucket_sizes(N, E, *self.bucket)
+        self._bump_dropout_seed()
+        fp, drop = self._prepare(None)
+        key = self._key(n_pad, e_pad, B, n_max, drop)
+        slot = self._lookup(key, allow_promote=True)
+        fresh = slot is None
+        if fresh:
+            t = ds._f64_tables()
+            slot = _Slot64.empty(fp.flat.device, B, n_pad, e_pad, n_max, int(t["x"].shape[1]), int(t["edge"].shape[1]),
+                                 int(t["target"].shape[1]))
+        ds.collate_into(slot.g, idx, slot.collate_scratch())
+        slot._loaded = None                                        # (the static buffers now hold a batch no object stands for)
+        slot.set_real_nodes(N)
+        with torch.no_grad():
+            loss = self._run_slot(slot, fp, drop, fresh)
+        if fresh:
+            self._slots[key] = slot
+        self.optimizer_step()
+        return loss
 
     # ---- optimizer -----------------------------------------------------------------------------------------------------
     def optimizer_step(self) -> None:

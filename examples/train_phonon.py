@@ -14,9 +14,10 @@ batch-size-1 samples in one pass - the loss is the sum of their per-crystal term
 
     python examples/train_phonon.py --float64 --epochs 2 --crystals 128 --hidden 64
 
---float64 --fused runs that training through train64.Trainer64 instead (float64 loss and AdamW kernels, no autograd;
---replay: recorded launch lists, one per exact batch shape): per-crystal keys as above, with the reference's loss of the
-batch as a whole - ONE rmse over all of its B*51 elements per branch (main_phDOS.py:109-114).
+--float64 --fused runs that training through train64.Trainer64 instead (float64 loss and AdamW kernels, no autograd): per-crystal
+keys as above, with the reference's loss of the batch as a whole - ONE rmse over all of its B*51 elements per branch
+(main_phDOS.py:109-114).  --replay: recorded launch lists, one per ghost-padded shape bucket; every shuffled batch is collated on
+the GPU straight into its bucket's static buffers (Trainer64.step_dataset) and evaluation replays too (predict.Predictor64).
 
     python examples/train_phonon.py --float64 --fused --replay --epochs 2 --crystals 128 --hidden 64
 """
@@ -53,7 +54,7 @@ def main(argv=None):
     ap.add_argument("--out", default="phonon_best.pt")
     ap.add_argument("--float64", action="store_true", help="the reference's float64 training with per-crystal keys")
     ap.add_argument("--fused", action="store_true", help="with --float64: train64.Trainer64 instead of autograd + torch.optim.AdamW")
-    ap.add_argument("--replay", action="store_true", help="with --float64 --fused: replay recorded launch lists (one per exact batch shape: reshuffled epochs mostly record)")
+    ap.add_argument("--replay", action="store_true", help="with --float64 --fused: replay recorded launch lists, one per shape bucket (step_dataset + Predictor64)")
     ap.add_argument("--per-crystal-keys", action="store_true",
                     help="fp32 trainer: attend over each crystal's own atoms - what the reference's batch_size = 1 training computes")
     args = ap.parse_args(argv)
@@ -73,7 +74,8 @@ def main(argv=None):
     perm = np.random.default_rng(args.seed).permutation(len(crystals))
     n_val = max(1, len(perm) // 10)
     split = {"valid": perm[:n_val], "test": perm[n_val:2 * n_val], "train": perm[2 * n_val:]}
-    ds = {k: DeviceDataset([crystals[i] for i in idx], dev) for k, idx in split.items()}
+    ds = {k: DeviceDataset([crystals[i] for i in idx], dev, dtype=torch.float64 if args.float64 else None)
+          for k, idx in split.items()}
 
     if args.float64:
         return train_float64_fused(args, ds, dev) if args.fused else train_float64(args, ds, dev)
@@ -142,29 +144,40 @@ def train_float64(args, ds, dev):
 
 def train_float64_fused(args, ds, dev):
     """float64 training through train64.Trainer64: forward program, loss kernel, backward program, flat AdamW - the loss stays
-    on the device, one host read per epoch.  The checkpoint carries the optimizer state (Trainer64.state_dict)."""
+    on the device, one host read per epoch.  --replay: shape buckets as in the fp32 run, every shuffled selection collated on
+    the device straight into its bucket (step_dataset, one n_max for the whole dataset - with per-crystal keys the numbers do
+    not depend on it) and evaluation through Predictor64.  The checkpoint carries the optimizer state (Trainer64.state_dict)."""
+    from dostransformer_amd.predict import Predictor64
     from dostransformer_amd.train64 import Trainer64
     model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).double()
     model = model.set_program_dtype(torch.float64).set_per_crystal_keys(True).to(dev)
-    trainer = Trainer64(model, lr=args.lr, beta=args.beta, replay=args.replay)
+    bucket = (32, 1024)
+    trainer = Trainer64(model, lr=args.lr, beta=args.beta, replay=args.replay, bucket=bucket if args.replay else None,
+                        promote=0.08 if args.replay else 0.0)
+    evaluator = Predictor64(model, bucket=bucket) if args.replay else model
+    train = ds["train"]
+    n_max = int(train.n_nodes.max())
     best, history = float("inf"), []
     for epoch in range(args.epochs):
         model.train()
         t0, losses, seen = time.perf_counter(), [], 0
-        for batch in ds["train"].batches(args.batch_size, shuffle=True, seed=args.seed + epoch):
-            losses.append(trainer.step(batch).clone())            # (replay: the loss lives in the slot's static buffer)
-            seen += batch.num_graphs
+        order = np.random.default_rng(args.seed + epoch).permutation(len(train))
+        for i in range(0, len(order), args.batch_size):
+            sel = order[i:i + args.batch_size]
+            losses.append(trainer.step_dataset(train, sel, n_max=n_max).clone())     # (replay: the loss lives in the slot's buffer)
+            seen += len(sel)
         loss = float(torch.stack(losses).mean())                  # one host read per epoch
         dt = time.perf_counter() - t0
         history.append(loss)
-        rmse, mse, mae, r2v = evaluate.test_phonon(model, ds["valid"].batches(args.batch_size))
+        rmse, mse, mae, r2v = evaluate.test_phonon(evaluator, ds["valid"].batches(args.batch_size))
         print(f"[epoch {epoch + 1}/{args.epochs}] loss {loss:.4f} | {seen / dt:8.0f} crystals/s | "
               f"valid rmse {rmse:.4f} mse {mse:.4f} mae {mae:.4f} r2 {r2v:.4f}"
-              + (f" | slots {trainer.slot_misses} recorded, {trainer.slot_hits} replayed" if args.replay else ""))
+              + (f" | slots {trainer.slot_misses} recorded, {trainer.slot_hits} replayed ({trainer.slot_promoted} promoted)"
+                 if args.replay else ""))
         if rmse < best:
             best = rmse
             checkpoint.save(args.out, model, trainer)
-            t = evaluate.test_phonon(model, ds["test"].batches(args.batch_size))
+            t = evaluate.test_phonon(evaluator, ds["test"].batches(args.batch_size))
             print(f"            test rmse {t[0]:.4f} mse {t[1]:.4f} mae {t[2]:.4f} r2 {t[3]:.4f}   (saved {args.out})")
     return {"best_valid_rmse": best, "train_loss": history}
 

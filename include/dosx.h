@@ -905,6 +905,13 @@ typedef struct DosxCollate {
 } DosxCollate;
 int dosx_collate_padded(const DosxCollate* d, dosx_stream_t stream);
 
+/* The same collate into the bucket of the float64 program (train64.Trainer64.step_dataset): same descriptor, same index
+ * outputs, but x_all / edge_feat_all / target_all and x / edge_feat / target point at `double` tables and buffers (the `float*`
+ * fields carry their addresses; all 8-byte aligned); system stays int32, inv_deg stays float.  n_glob must be 0 and seg_tile
+ * NULL (the float64 program is the phonon one and has no tiled message GEMM).  Rows of x / target move as 16-byte vectors
+ * when the tables are 16-byte aligned and the row width is even. */
+int dosx_collate_padded_f64(const DosxCollate* d, dosx_stream_t stream);
+
 /* Periodic neighbour list of C crystals at once (replaces ASE's `neighbor_list("ijS", a, cutoff=r_max,
  * self_interaction=True)` + the edge_vec arithmetic of `utils.py:267-273` in build_data).  `pos [N][3]` Cartesian,
  * `cell [C][3][3]` lattice vectors as rows, crystal c owns atoms [atom_ptr[c], atom_ptr[c+1]) and the ordered atom
