@@ -100,6 +100,16 @@ class DOSTransformerBase(FusedModel):
             raise DosxError(f"{who} runs the fp32 program; {type(self).__name__} is set to float64 (set_program_dtype): train "
                             f"it with train64.Trainer64, or with model(batch), loss.backward() and torch.optim.AdamW")
 
+    def _require_f64_program(self, who: str) -> None:
+        """The drivers of the float64 program (train64.Trainer64, predict.Predictor64) take a DOSTransformer_phonon set to it and
+        nothing else; called on the class (``DOSTransformerBase._require_f64_program(model, who)``) for whatever they are given."""
+        ours = isinstance(self, DOSTransformerBase)
+        if not (ours and self._cfg.kind == "phonon" and self._program_dtype == torch.float64):
+            raise DosxError(f"{who} drives a DOSTransformer_phonon set to the float64 program "
+                            f"(model.double().set_program_dtype(torch.float64)), got {type(self).__name__}"
+                            + (f" with program_dtype {self._program_dtype}" if ours else "")
+                            + ": the fp32 program is train.Trainer's / predict.Predictor's")
+
     def _check_train_flags(self):
         pass          # (kept for callers of round 1: attention dropout is implemented now)
 

@@ -1186,7 +1186,7 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
         return t
     if ops.RECORDER.active:
         # a torch cast is not a libdosx call: it would run once while recording and never again on replay, so the
-        # replayed kernels would keep reading the first batch's converted copy (train._Slot stores fp32 for this reason)
+        # replayed kernels would keep reading the first batch's converted copy (slots.Slot stores fp32 for this reason)
         raise RuntimeError(f"recorded programs need float32 contiguous inputs, got {t.dtype} (contiguous={t.is_contiguous()})")
     return t.to(torch.float32).contiguous()
 

@@ -27,6 +27,7 @@ from typing import Dict, Optional
 
 import torch
 
+from ._lib import DosxError
 from .batch import GraphMeta
 from . import functional as Fn
 from . import ops
@@ -44,6 +45,14 @@ SOFTMAX64 = False         # tests only: the attention softmax in fp64 instead of
 def _f64(t: torch.Tensor) -> torch.Tensor:
     """A batch field as the program reads it: float64, contiguous (an fp32 batch is promoted here, once)."""
     return t.to(torch.float64).contiguous()
+
+
+def require_replayable(g, fields, device, who: str) -> None:
+    """A recorded program replays libdosx calls only: the torch casts in the body of this module must hand back the very
+    buffers (fields ``fields`` of the slot batch ``g``) they are given."""
+    cast = lambda k: g[k].to(device=device, dtype=torch.int32).contiguous() if k == "system" else _f64(g[k])
+    if not all(cast(k) is g[k] for k in fields):
+        raise DosxError(f"{who}: a slot buffer is not in the dtype / layout the float64 program reads")
 
 
 def _linear_grads(G: Params, key: str, M: int, dy: torch.Tensor, segs) -> None:
@@ -122,79 +131,7 @@ def _processor_bwd(P: Params, G: Params, pre: str, ctx, dx: torch.Tensor, de: Op
     return dx_in, de_in
 
 
-def graphnetwork_phonon_fwd(P: Params, cfg, g, m: GraphMeta):
-    """-> (dos [B, S], saved context)."""
-    H, S, B, L = cfg.H, cfg.S, m.num_graphs, cfg.L
-    vec = g.edge_vec
-    if m.edge_perm is not None:
-        vec = vec[m.edge_perm]
-    e0 = edge_feat_sh1_64(_f64(vec), 4.0)                                              # r_max = 4
-    xin = _f64(g.x)
-    enc = "GN_encoder.node_encoder" if xin.shape[1] == 118 else "GN_encoder.node_encoder_prompt"   # :150-153
-    x, cx = _mlp_prelu_fwd(P, enc, xin)
-    e, ce = _mlp_prelu_fwd(P, "GN_encoder.edge_encoder", e0)
-    layers = []
-    for l in range(L):
-        x, e, c = _processor_fwd(P, f"stacked_processor.{l}", x, e, m)
-        layers.append(c)
-    pool = graph_pool64(x, m.graph_ptr, B)
-    graph = gemm64(B, H, [seg64(pool)], P["GN_decoder.mlp.0.weight"], alloc64(x.device, B, H), bias=P["GN_decoder.mlp.0.bias"])
-    # head on cat[energies, graph] over the [S, B] rows r = s * B + b (graphnetwork_phonon.py:68-71)
-    emb = P["embeddings.weight"]
-    head = [seg64(emb, rowmap(d=B, m=1, c=0)), seg64(graph, rowmap(d=B, m=0, c=1))]
-    hid_pre, hid = alloc64(x.device, S * B, H), alloc64(x.device, S * B, H)
-    gemm64(S * B, H, head, P["out_layer.0.weight"], hid, bias=P["out_layer.0.bias"], act=ACT64_LEAKY, pre=hid_pre)
-    out = gemm64(S * B, 1, [seg64(hid)], P["out_layer.2.weight"], alloc64(x.device, S * B, 1), bias=P["out_layer.2.bias"])
-    dos = out.view(S, B).t().contiguous()
-    return dos, (enc, cx, ce, layers, pool, (head, graph), hid_pre, hid)     # graph: keeps the memory `head` points to
-
-
-def graphnetwork_phonon_bwd(P: Params, G: Params, cfg, m: GraphMeta, saved, ddos: torch.Tensor) -> None:
-    """Writes the gradient of every live parameter into G from ddos [B, S]."""
-    enc, cx, ce, layers, pool, (head, _), hid_pre, hid = saved
-    H, S, B, N = cfg.H, cfg.S, m.num_graphs, m.num_nodes
-    dev = ddos.device
-    rows = S * B
-    dout = ddos.to(torch.float64).t().contiguous().view(rows, 1)
-    _linear_grads(G, "out_layer.2", rows, dout, [seg64(hid)])
-    dhid = gemm64(rows, H, [seg64(dout)], P["out_layer.2.weight"], alloc64(dev, rows, H), w_layout=1)
-    dpre, _ = act_bwd64(dhid, hid_pre, ACT64_LEAKY)
-    _linear_grads(G, "out_layer.0", rows, dpre, head)
-    # input gradient of the head: the energies are broadcast over the crystals and the graph rows over the bins, so sum
-    # those rows first (in order), then one small product with each half of out_layer.0.weight
-    W0 = P["out_layer.0.weight"]
-    Rs = reduce_rows64(dpre, S, B, B, 1)
-    gemm64(S, H, [seg64(Rs)], W0[:, :H], G["embeddings.weight"], w_layout=1)
-    Rb = reduce_rows64(dpre, B, S, 1, B)
-    dgraph = gemm64(B, H, [seg64(Rb)], W0[:, H:], alloc64(dev, B, H), w_layout=1)
-    _linear_grads(G, "GN_decoder.mlp.0", B, dgraph, [seg64(pool)])
-    dpool = gemm64(B, H, [seg64(dgraph)], P["GN_decoder.mlp.0.weight"], alloc64(dev, B, H), w_layout=1)
-    dx = rows_add64(N, dpool, ia=m.node_graph)                                       # backward of the sum pool
-    de = None
-    for l in reversed(range(cfg.L)):
-        dx, de = _processor_bwd(P, G, f"stacked_processor.{l}", layers[l], dx, de, m)
-    if de is None:                                                                    # L = 0: nothing reaches the edges
-        de = torch.zeros(m.num_edges, H, device=dev, dtype=torch.float64)
-    _mlp_prelu_bwd(P, G, "GN_encoder.edge_encoder", ce, de)
-    _mlp_prelu_bwd(P, G, enc, cx, dx)
-
-
-# ---- DOSTransformer_phonon ------------------------------------------------------------------------------------------------
-def _is_padded(g) -> bool:
-    """A ghost-padded batch (batch.pad_batch) or bucket (train64._Slot64.empty): it carries its real node count."""
-    return getattr(g, "real_nodes", None) is not None
-
-
-def _dpool_rows(dev, B: int, H: int, padded: bool) -> torch.Tensor:
-    """The sum pool's gradient buffer, [B + 1, H]: the GEMM writes rows [0, B); row B is what a ghost node's ``node_graph``
-    entry (= B, batch.pad_batch) gathers.  It is zeroed here by torch - once, when the buffer is made, and so outside a recorded
-    launch list, which keeps the buffer alive and never writes that row again.  An unpadded batch never reads it."""
-    dpool = alloc64(dev, B + 1, H)
-    if padded:
-        dpool[B:].zero_()
-    return dpool
-
-
+# ---- encoders + message-passing layers, shared by the two models (DOSTransformer_phonon.py:74-84) ---------------------
 def _gnn_trunk_fwd(P: Params, cfg, g, m: GraphMeta, enc: str):
     vec = g.edge_vec
     if m.edge_perm is not None:
@@ -218,6 +155,62 @@ def _gnn_trunk_bwd(P: Params, G: Params, cfg, m: GraphMeta, ctx, dx: torch.Tenso
         de = ops.keep_alive(torch.zeros(m.num_edges, cfg.H, device=dx.device, dtype=torch.float64))
     _mlp_prelu_bwd(P, G, "GN_encoder.edge_encoder", ce, de)
     _mlp_prelu_bwd(P, G, enc, cx, dx)
+
+
+def graphnetwork_phonon_fwd(P: Params, cfg, g, m: GraphMeta):
+    """-> (dos [B, S], saved context)."""
+    H, S, B = cfg.H, cfg.S, m.num_graphs
+    enc = "GN_encoder.node_encoder" if g.x.shape[1] == 118 else "GN_encoder.node_encoder_prompt"   # :150-153
+    x, ctrunk = _gnn_trunk_fwd(P, cfg, g, m, enc)
+    pool = graph_pool64(x, m.graph_ptr, B)
+    graph = gemm64(B, H, [seg64(pool)], P["GN_decoder.mlp.0.weight"], alloc64(x.device, B, H), bias=P["GN_decoder.mlp.0.bias"])
+    # head on cat[energies, graph] over the [S, B] rows r = s * B + b (graphnetwork_phonon.py:68-71)
+    emb = P["embeddings.weight"]
+    head = [seg64(emb, rowmap(d=B, m=1, c=0)), seg64(graph, rowmap(d=B, m=0, c=1))]
+    hid_pre, hid = alloc64(x.device, S * B, H), alloc64(x.device, S * B, H)
+    gemm64(S * B, H, head, P["out_layer.0.weight"], hid, bias=P["out_layer.0.bias"], act=ACT64_LEAKY, pre=hid_pre)
+    out = gemm64(S * B, 1, [seg64(hid)], P["out_layer.2.weight"], alloc64(x.device, S * B, 1), bias=P["out_layer.2.bias"])
+    dos = out.view(S, B).t().contiguous()
+    return dos, (ctrunk, pool, (head, graph), hid_pre, hid)     # graph: keeps the memory `head` points to
+
+
+def graphnetwork_phonon_bwd(P: Params, G: Params, cfg, m: GraphMeta, saved, ddos: torch.Tensor) -> None:
+    """Writes the gradient of every live parameter into G from ddos [B, S]."""
+    ctrunk, pool, (head, _), hid_pre, hid = saved
+    H, S, B, N = cfg.H, cfg.S, m.num_graphs, m.num_nodes
+    dev = ddos.device
+    rows = S * B
+    dout = ddos.to(torch.float64).t().contiguous().view(rows, 1)
+    _linear_grads(G, "out_layer.2", rows, dout, [seg64(hid)])
+    dhid = gemm64(rows, H, [seg64(dout)], P["out_layer.2.weight"], alloc64(dev, rows, H), w_layout=1)
+    dpre, _ = act_bwd64(dhid, hid_pre, ACT64_LEAKY)
+    _linear_grads(G, "out_layer.0", rows, dpre, head)
+    # input gradient of the head: the energies are broadcast over the crystals and the graph rows over the bins, so sum
+    # those rows first (in order), then one small product with each half of out_layer.0.weight
+    W0 = P["out_layer.0.weight"]
+    Rs = reduce_rows64(dpre, S, B, B, 1)
+    gemm64(S, H, [seg64(Rs)], W0[:, :H], G["embeddings.weight"], w_layout=1)
+    Rb = reduce_rows64(dpre, B, S, 1, B)
+    dgraph = gemm64(B, H, [seg64(Rb)], W0[:, H:], alloc64(dev, B, H), w_layout=1)
+    _linear_grads(G, "GN_decoder.mlp.0", B, dgraph, [seg64(pool)])
+    dpool = gemm64(B, H, [seg64(dgraph)], P["GN_decoder.mlp.0.weight"], alloc64(dev, B, H), w_layout=1)
+    _gnn_trunk_bwd(P, G, cfg, m, ctrunk, rows_add64(N, dpool, ia=m.node_graph))       # backward of the sum pool
+
+
+# ---- DOSTransformer_phonon ------------------------------------------------------------------------------------------------
+def _is_padded(g) -> bool:
+    """A ghost-padded batch (batch.pad_batch) or bucket (slots.Slot.empty): it carries its real node count."""
+    return getattr(g, "real_nodes", None) is not None
+
+
+def _dpool_rows(dev, B: int, H: int, padded: bool) -> torch.Tensor:
+    """The sum pool's gradient buffer, [B + 1, H]: the GEMM writes rows [0, B); row B is what a ghost node's ``node_graph``
+    entry (= B, batch.pad_batch) gathers.  It is zeroed here by torch - once, when the buffer is made, and so outside a recorded
+    launch list, which keeps the buffer alive and never writes that row again.  An unpadded batch never reads it."""
+    dpool = alloc64(dev, B + 1, H)
+    if padded:
+        dpool[B:].zero_()
+    return dpool
 
 
 def _encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, kvhat: torch.Tensor, Nk: int, Bk: int, T: int, drop,

@@ -6,6 +6,7 @@ capturable in a HIP graph.  No arithmetic happens in Python.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import List, Optional, Sequence, Tuple
 
@@ -237,6 +238,25 @@ class Program:
 
 
 RECORDER = _Recorder()
+
+
+@contextlib.contextmanager
+def recording_scope(side_stream: Optional[bool] = None):
+    """Around the first step of a bucket (recorded between ``RECORDER.begin()`` / ``end()`` by the caller, or captured into a
+    HIP graph): the kernel timer is off - its events are not part of a replayed step - and, when given, ``side_stream`` is
+    ``GradSink.use_side_stream`` for the duration.  However the scope is left, a recorder that is still active is ended and
+    both switches get their values back."""
+    timer_on, side_before = KERNEL_TIMER.enabled, GradSink.use_side_stream
+    KERNEL_TIMER.enabled = False
+    if side_stream is not None:
+        GradSink.use_side_stream = side_stream
+    try:
+        yield
+    finally:
+        if RECORDER.active:
+            RECORDER.end()
+        GradSink.use_side_stream = side_before
+        KERNEL_TIMER.enabled = timer_on
 
 
 def _call(name: str, *args, w=None) -> None:

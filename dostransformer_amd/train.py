@@ -18,7 +18,7 @@ launches of a step cost the host ~20 us each when issued from Python; replay rem
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Dict, Optional
+from typing import Optional
 
 import torch
 
@@ -26,7 +26,8 @@ from . import functional as Fn
 from . import ops
 from ._lib import DosxError, from_environ
 from ._models import DOSTransformerBase, _SEED_MOD, rank_seed_offset
-from .batch import CrystalBatch, GraphMeta, bucket_sizes, graph_meta, pad_batch, seg_tile_bound
+from .batch import CrystalBatch, bucket_sizes, graph_meta, pad_batch
+from .slots import Slot, SlotCache
 
 # Data parallel: a THIRD gradient bucket (GN_decoder + message-passing layers L-1 .. 1: 1.9 of the GNN trunk's 3.0 MB at the
 # headline shape) all-reduced from the flush at layer 0, under layer 0's backward, so that only 1.1 MB stay behind the step
@@ -37,141 +38,6 @@ from .batch import CrystalBatch, GraphMeta, bucket_sizes, graph_meta, pad_batch,
 # 15 us on 8 xGMI-connected GPUs.  To be re-measured on a real multi-GPU node.
 _DP_MID_BUCKET = from_environ("DOSX_DP_MID_BUCKET", "0") == "1"
 _DP_CHECK = from_environ("DOSX_DP_CHECK", "0") == "1"
-_META_TENSORS = ("src", "dst", "rowptr_dst", "perm_src", "rowptr_src", "graph_ptr", "node_graph", "dense_row", "inv_deg")
-
-
-class _Loaded:
-    """What a bucket's static buffers currently hold: see _Slot._signature."""
-    __slots__ = ("g", "ts", "versions")
-
-    def __init__(self, g, ts):
-        self.g, self.ts, self.versions = g, tuple(ts), tuple(t._version for t in ts)
-
-    def __eq__(self, other):
-        return (isinstance(other, _Loaded) and self.g is other.g and len(self.ts) == len(other.ts)
-                and all(a is b for a, b in zip(self.ts, other.ts)) and self.versions == other.versions)
-
-    __hash__ = None
-
-
-class _Slot:
-    """Static buffers + captured graphs of one shape bucket."""
-
-    def __init__(self, g: CrystalBatch, kind: str, targets: bool = True):
-        m = g.meta
-        self.fields = ["x", "system"] + (["edge_vec"] if kind == "phonon" else ["edge_attr", "glob"])
-        if targets:
-            self.fields.append("phdos" if kind == "phonon" else "y_ft")
-        # Static buffers hold exactly what the kernels read: fp32 contiguous features, int32 indices.  load() then
-        # converts while it copies (the phonon pipeline is fp64 upstream, main_phDOS.py:15-16) and the recorded
-        # program never needs a cast of its own — a torch cast inside the recording would not be replayed.
-        f = {k: (g[k].to(torch.float32).contiguous().clone() if g[k].is_floating_point() else g[k].clone())
-             for k in self.fields}
-        f["system"] = f["system"].to(torch.int32)                   # what the kernels index with
-        f["edge_index"], f["batch"] = g.edge_index, g.batch         # never read by the kernels
-        meta = GraphMeta(num_nodes=m.num_nodes, num_edges=m.num_edges, num_graphs=m.num_graphs, n_max=m.n_max,
-                         edge_perm=None, seg_tile=None if m.seg_tile is None else m.seg_tile.clone(),
-                         **{k: getattr(m, k).clone() for k in _META_TENSORS})
-        self.g = CrystalBatch(f, g.num_graphs, meta)
-        self.graph_a = self.graph_b = None
-        self.prog_a = self.prog_b = None
-        self.plan = []
-        self.keep = None
-        self.scratch = None
-        self._loaded = self._signature(g)      # the static buffers hold THIS batch (cloned above)
-
-    def _signature(self, g: CrystalBatch):
-        """Identity + version of everything load() would copy from batch ``g``: the batch object and its source tensors
-        THEMSELVES (strong references, compared with ``is``) with torch's in-place version counters (any in-place write to a field
-        since the last load changes one).  Addresses are not identities: a batch collated after the previous one was freed gets the
-        same ``id()`` and - from the caching allocator - the same device pointers with version 0; holding the objects is what
-        keeps a later batch from being mistaken for this one (tests/test_gpu_step.py: an epoch of freshly collated batches)."""
-        m = g.meta
-        ts = [g[k] for k in self.fields] + [getattr(m, k) for k in _META_TENSORS] + ([m.seg_tile] if m.seg_tile is not None else [])
-        return _Loaded(g, ts)
-
-    @classmethod
-    def empty(cls, kind: str, device, B: int, n_pad: int, e_pad: int, n_max: int, Fa: int, Fe: int, S: int,
-              tiled: bool = False) -> "_Slot":
-        """Uninitialised static buffers of a bucket, to be filled by ``DeviceDataset.collate_into`` (no source batch)."""
-        f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=device)
-        i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=device)
-        f = {"x": f32(n_pad, Fa), "system": i32(B), "edge_index": None, "batch": None}
-        if kind == "phonon":
-            f["edge_vec"], f["phdos"] = f32(e_pad, Fe), f32(B, S)
-        else:
-            f["edge_attr"], f["glob"], f["y_ft"] = f32(e_pad, Fe), f32(2 * B), f32(B * S)
-        meta = GraphMeta(num_nodes=n_pad, num_edges=e_pad, num_graphs=B, n_max=n_max, edge_perm=None,
-                         src=i32(e_pad), dst=i32(e_pad), rowptr_dst=i32(n_pad + 1), perm_src=i32(e_pad),
-                         rowptr_src=i32(n_pad + 1), graph_ptr=i32(B + 1), node_graph=i32(n_pad), dense_row=i32(n_pad),
-                         inv_deg=f32(n_pad),
-                         seg_tile=i32(3, seg_tile_bound(n_pad, e_pad, B) + 1) if tiled else None)
-        self = cls.__new__(cls)
-        self.fields = [k for k in f if k not in ("edge_index", "batch")]
-        self.g = CrystalBatch(f, B, meta)
-        self.graph_a = self.graph_b = None
-        self.prog_a = self.prog_b = None
-        self.plan = []
-        self.keep = None
-        self.scratch = {"small": i32(4 * B + 3), "node_row": i32(n_pad), "edge_row": i32(e_pad)}
-        self._loaded = None
-        return self
-
-    def _as_slot_dtype(self, g: CrystalBatch, k: str) -> torch.Tensor:
-        """Field k of a batch in the dtype the bucket stores.  The int64 -> int32 copy of `system` (the reference's crystal-
-        system index, [B]) is cached on the batch object: batches are revisited every epoch, and a cast per visit is one
-        more kernel in front of every step."""
-        t = g[k]
-        if k != "system" or t.dtype == torch.int32 or not isinstance(g, CrystalBatch):
-            return t
-        c = getattr(g, "_system32", None)
-        if c is None or c[0] is not t:
-            c = (t, t.to(torch.int32))
-            object.__setattr__(g, "_system32", c)
-        return c[1]
-
-    def load(self, g: CrystalBatch) -> None:
-        """Copy a batch of this bucket's shape into the static buffers: ONE launch for everything that is already in
-        the kernels' format (fp32 / int32, contiguous, on the device); fields that need a dtype conversion (fp64
-        phonon data, int64 ``system``) or come from elsewhere go through ``Tensor.copy_``."""
-        # The bucket already holds this very batch (same object, no field written in place since): nothing to copy.  An epoch loop
-        # over pre-collated device-resident batches revisits each of them every epoch - the copy was one launch in front of every
-        # step (round 6); a batch that shares its bucket with another one is copied as before.
-        sig = self._signature(g)
-        if sig == getattr(self, "_loaded", None):
-            return
-        self._loaded = None
-        pairs = []
-        m, sm = g.meta, self.g.meta
-        items = [(self.g[k], self._as_slot_dtype(g, k)) for k in self.fields] + \
-                [(getattr(sm, k), getattr(m, k)) for k in _META_TENSORS]
-        if sm.seg_tile is not None:
-            if m.seg_tile is None or m.seg_tile.shape != sm.seg_tile.shape:
-                raise ValueError("batch without (matching) message-GEMM tile table loaded into a bucket recorded with one")
-            items.append((sm.seg_tile, m.seg_tile))
-        for dst, src in items:
-            if src.dtype == dst.dtype and src.device == dst.device and src.is_contiguous() and src.shape == dst.shape:
-                pairs.append((dst, src))
-            else:
-                dst.copy_(src.reshape(dst.shape) if src.numel() == dst.numel() else src, non_blocking=True)
-        ops.copy_many(pairs)
-        self._loaded = sig
-
-
-def promote_key(live_keys, key, tol: float):
-    """The live bucket key a batch of bucket ``key`` = (n_pad, e_pad, *rest) can run in: same ``rest`` (batch size, key-slot
-    count, global count, tiling), at least as many node and edge rows, at most ``tol`` (relative) more of either; the
-    smallest such by (edges, nodes), or None."""
-    n, e, rest = key[0], key[1], tuple(key[2:])
-    best = None
-    for k in live_keys:
-        if tuple(k[2:]) != rest or k[0] < n or k[1] < e:
-            continue
-        if k[0] > n * (1.0 + tol) + 1e-9 or k[1] > e * (1.0 + tol) + 1e-9:
-            continue
-        if best is None or (k[1], k[0]) < (best[1], best[0]):
-            best = k
-    return best
 
 
 class _AdamWState:
@@ -249,7 +115,7 @@ class _AdamWState:
             seed.add_(1)
 
 
-class Trainer(_AdamWState):
+class Trainer(_AdamWState, SlotCache):
     """AdamW(lr, weight_decay=1e-2) training of a DOSTransformer(_phonon) module, all on libdosx.
 
     ``dist``: optional :class:`dostransformer_amd.dist.DataParallel` — shards are per-rank batches,
@@ -292,7 +158,7 @@ class Trainer(_AdamWState):
         self.last_outputs = None
         # shape buckets seen so far -> static buffers + recorded program, least recently used first; bounded: with
         # per-epoch shuffling new (N, E) buckets keep appearing, each holding a step's worth of activations
-        self._slots: "OrderedDict[tuple, _Slot]" = OrderedDict()
+        self._slots: "OrderedDict[tuple, Slot]" = OrderedDict()
         self.max_slots = int(max_slots)
         self.slot_hits = self.slot_misses = self.slot_promoted = 0
         # largest relative excess of nodes / edges a first-time bucket accepts from a live one (step_dataset; 0 = every
@@ -435,19 +301,17 @@ class Trainer(_AdamWState):
             return self._part_b(fp, m, st, ng)
 
     # ---- graph path ------------------------------------------------------------------------------
-    def _capture(self, slot: _Slot, fp, ng: int) -> None:
-        timer_on = ops.KERNEL_TIMER.enabled
-        ops.KERNEL_TIMER.enabled = False
+    def _capture(self, slot: Slot, fp, ng: int) -> None:
         g, m = slot.g, slot.g.meta
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.no_grad():          # eager warm-up (lazy kernel attributes etc.)
-            st = self._part_a(fp, g, m, ng)
-            self._part_b(fp, m, st, ng)
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
         split = self.dist is not None and self.kind == "phonon"
-        with torch.no_grad():
+        with ops.recording_scope(), torch.no_grad():
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):                       # eager warm-up (lazy kernel attributes etc.)
+                st = self._part_a(fp, g, m, ng)
+                self._part_b(fp, m, st, ng)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
             slot.graph_a = torch.cuda.CUDAGraph()
             with torch.cuda.graph(slot.graph_a):
                 st = self._part_a(fp, g, m, ng)
@@ -459,73 +323,36 @@ class Trainer(_AdamWState):
                     loss = self._part_b(fp, m, st, ng)
         slot.keep = (st, loss)            # keeps the graph-owned outputs from being recycled
         slot.loss, slot.out, slot.sse = loss, st["out"], st.get("sse")
-        ops.KERNEL_TIMER.enabled = timer_on
 
-    def _record(self, slot: _Slot, fp, ng: int) -> None:
+    def _record(self, slot: Slot, fp, ng: int) -> None:
         """Run the step once on the slot's static buffers while recording every launch."""
-        timer_on = ops.KERNEL_TIMER.enabled
-        ops.KERNEL_TIMER.enabled = False
-        side_before = ops.GradSink.use_side_stream
-        ops.GradSink.use_side_stream = True          # replay is cheap enough on the host to feed two streams
         g, m = slot.g, slot.g.meta
         split = self.dist is not None and self.kind == "phonon"
-        try:
-            with torch.no_grad():
-                # the plan of a replayed step: recorded programs separated by the collectives (which are not
-                # libdosx calls): [fwd] (sse) [bwd up to the GNN] (early bucket all-reduce) [GNN bwd]
-                plan = []
-                self._rec_parts = []
+        # (replay is cheap enough on the host to feed two streams)
+        with ops.recording_scope(side_stream=True), torch.no_grad():
+            # the plan of a replayed step: recorded programs separated by the collectives (which are not
+            # libdosx calls): [fwd] (sse) [bwd up to the GNN] (early bucket all-reduce) [GNN bwd]
+            plan = []
+            self._rec_parts = []
+            ops.RECORDER.begin()
+            st = self._part_a(fp, g, m, ng)
+            if split:
+                plan.append(("prog", ops.RECORDER.end()))
+                plan.append(("sse", None))
+                self.dist.all_reduce_sse(st["sse"])
                 ops.RECORDER.begin()
-                st = self._part_a(fp, g, m, ng)
-                if split:
-                    plan.append(("prog", ops.RECORDER.end()))
-                    plan.append(("sse", None))
-                    self.dist.all_reduce_sse(st["sse"])
-                    ops.RECORDER.begin()
-                loss = self._part_b(fp, m, st, ng)
-                last = ops.RECORDER.end()
-                for part, coll in self._rec_parts:    # (_mid_hook / _gnn_hook closed these while recording)
-                    plan.append(("prog", part))
-                    plan.append((coll, None))
-                plan.append(("prog", last))
-                self._rec_parts = []
-                slot.plan = plan
-                slot.prog_a = plan[0][1]
-        finally:
-            if ops.RECORDER.active:
-                ops.RECORDER.end()
-            ops.GradSink.use_side_stream = side_before
-            ops.KERNEL_TIMER.enabled = timer_on
+            loss = self._part_b(fp, m, st, ng)
+            last = ops.RECORDER.end()
+            for part, coll in self._rec_parts:    # (_mid_hook / _gnn_hook closed these while recording)
+                plan.append(("prog", part))
+                plan.append((coll, None))
+            plan.append(("prog", last))
+            self._rec_parts = []
+        slot.plan, slot.prog = plan, plan[0][1]
         slot.keep = (st, loss)
         slot.loss, slot.out, slot.sse = loss, st["out"], st.get("sse")
 
-    def _lookup(self, key, allow_promote: bool = False):
-        """(slot or None) of a bucket key, with the LRU / hit-rate bookkeeping.  ``allow_promote`` (step_dataset: the batch is
-        collated straight into whatever bucket it gets): a bucket that is asked for the FIRST time runs
-        in the smallest live bucket that holds it with at most ``promote`` more nodes / edges, if there is one (ghost padding
-        is exact whatever the bucket): recording a launch list costs two to three steps, so the rare shapes of a reshuffled
-        epoch - seen once - never pay it, and a shape that comes back is recorded on its second visit."""
-        slot = self._slots.get(key)
-        if slot is None and allow_promote and self.promote > 0:
-            seen = self._seen.get(key, 0)
-            self._seen[key] = seen + 1
-            if seen == 0:
-                host = promote_key(self._slots.keys(), key, self.promote)
-                if host is not None:
-                    self.slot_hits += 1
-                    self.slot_promoted += 1
-                    self._slots.move_to_end(host)
-                    return self._slots[host]
-        if slot is None:
-            self.slot_misses += 1
-            while len(self._slots) >= self.max_slots:          # evict the least recently used bucket
-                self._slots.popitem(last=False)
-        else:
-            self.slot_hits += 1
-            self._slots.move_to_end(key)
-        return slot
-
-    def _run_slot(self, slot: _Slot, fp, ng: int, fresh: bool) -> torch.Tensor:
+    def _run_slot(self, slot: Slot, fp, ng: int, fresh: bool) -> torch.Tensor:
         """The step on a bucket whose static buffers hold the batch: record / capture on first use, replay afterwards."""
         if fresh and self.replay:
             self._record(slot, fp, ng)       # this IS the step for this batch (run + record)
@@ -571,13 +398,13 @@ class Trainer(_AdamWState):
         slot = self._lookup(key)
         fresh = slot is None
         if fresh:
-            slot = _Slot(g, self.kind)
-            self._slots[key] = slot
-            if not self.replay:
-                pass                          # (capture runs on the slot's own copy of this batch, then replays it)
+            slot = Slot(g, m, self.kind, torch.float32)       # (graph mode captures on the slot's own copy of this batch)
         else:
             slot.load(g)
-        return self._run_slot(slot, fp, ng, fresh)
+        loss = self._run_slot(slot, fp, ng, fresh)
+        if fresh:                             # (registered once recorded: a failed first step leaves no empty recording behind)
+            self._slots[key] = slot
+        return loss
 
     def step_dataset(self, ds, indices, n_global: Optional[int] = None, n_max: Optional[int] = None) -> torch.Tensor:
         """One training step on the crystals ``indices`` of a device-resident ``loader.DeviceDataset``: the batch is
@@ -623,18 +450,14 @@ class Trainer(_AdamWState):
         fresh = slot is None
         if fresh:
             t = ds._f32_tables()
-            slot = _Slot.empty(self.kind, dev, B, n_pad, e_pad, n_max, int(t["x"].shape[1]), int(t["edge"].shape[1]),
-                               int(t["target"].shape[1]), tiled=tiled)
-            self._slots[key] = slot
-        elif getattr(slot, "scratch", None) is None:               # bucket first filled from a batch object
-            i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
-            # (sized from the SLOT: a promoted host bucket is larger than the requested one, and the collate kernels write
-            #  node_row / edge_row up to the slot's own padded counts)
-            slot.scratch = {"small": i32(4 * B + 3), "node_row": i32(slot.g.meta.num_nodes), "edge_row": i32(slot.g.meta.num_edges)}
-        ds.collate_into(slot.g, idx, slot.scratch)
+            slot = Slot.empty(self.kind, dev, torch.float32, B, n_pad, e_pad, n_max, int(t["x"].shape[1]),
+                              int(t["edge"].shape[1]), int(t["target"].shape[1]), tiled=tiled)
+        ds.collate_into(slot.g, idx, slot.collate_scratch())
         slot._loaded = None                                        # (the static buffers now hold a batch no object stands for)
         self._bump_dropout_seed()
         loss = self._run_slot(slot, fp, ng, fresh)
+        if fresh:
+            self._slots[key] = slot
         self.optimizer_step()
         return loss
 

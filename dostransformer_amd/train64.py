@@ -28,89 +28,12 @@ from . import functional64 as F64
 from . import ops
 from ._lib import DosxError
 from ._models import DOSTransformerBase
-from .batch import CrystalBatch, GraphMeta, bucket_sizes, graph_meta, pad_batch
-from .train import _AdamWState, _Loaded, _META_TENSORS, promote_key
-
-_F64_FIELDS = ("x", "edge_vec", "phdos")
-
-
-class _Slot64:
-    """Static buffers + recorded program of one batch shape (exact, or a ghost-padded bucket): what the float64 program reads,
-    in the dtype it reads it (float64 contiguous features and targets, int32 ``system``, clones of the GraphMeta tensors) - so
-    that the casts in the body of ``functional64`` are no-ops on them and the recording holds libdosx calls only.  The
-    buffers of a padded shape carry ``real_nodes`` (the real node count of the batch they hold), like a ``pad_batch`` batch."""
-
-    def __init__(self, g, m: GraphMeta, device, fields=_F64_FIELDS):
-        f = {k: torch.empty(g[k].shape, dtype=torch.float64, device=device) for k in fields}
-        f["system"] = torch.empty(g["system"].shape, dtype=torch.int32, device=device)
-        meta = GraphMeta(num_nodes=m.num_nodes, num_edges=m.num_edges, num_graphs=m.num_graphs, n_max=m.n_max, edge_perm=None,
-                         seg_tile=None, **{k: torch.empty_like(getattr(m, k), device=device) for k in _META_TENSORS})
-        self._setup(CrystalBatch(f, m.num_graphs, meta), fields)
-
-    def _setup(self, g: CrystalBatch, fields) -> None:
-        self.fields = tuple(fields)
-        self.g = g
-        self.prog = self.loss = self.out = None
-        self.scratch = None
-        self._loaded = None
-
-    @classmethod
-    def empty(cls, device, B: int, n_pad: int, e_pad: int, n_max: int, Fa: int, Fe: int, S: int) -> "_Slot64":
-        """Uninitialised static buffers of a bucket, to be filled by ``DeviceDataset.collate_into`` (no source batch)."""
-        f64 = lambda *s: torch.empty(*s, dtype=torch.float64, device=device)
-        i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=device)
-        f = {"x": f64(n_pad, Fa), "edge_vec": f64(e_pad, Fe), "phdos": f64(B, S), "system": i32(B)}
-        meta = GraphMeta(num_nodes=n_pad, num_edges=e_pad, num_graphs=B, n_max=n_max, edge_perm=None, src=i32(e_pad),
-                         dst=i32(e_pad), rowptr_dst=i32(n_pad + 1), perm_src=i32(e_pad), rowptr_src=i32(n_pad + 1),
-                         graph_ptr=i32(B + 1), node_graph=i32(n_pad), dense_row=i32(n_pad),
-                         inv_deg=torch.empty(n_pad, dtype=torch.float32, device=device), seg_tile=None)
-        self = cls.__new__(cls)
-        self._setup(CrystalBatch(f, B, meta), _F64_FIELDS)
-        return self
-
-    def collate_scratch(self):
-        """Index scratch of ``DeviceDataset.collate_into``, sized from the slot's own padded counts (made on first use)."""
-        if self.scratch is None:
-            m = self.g.meta
-            i32 = lambda n: torch.empty(n, dtype=torch.int32, device=m.src.device)
-            self.scratch = {"small": i32(4 * m.num_graphs + 3), "node_row": i32(m.num_nodes), "edge_row": i32(m.num_edges)}
-        return self.scratch
-
-    def set_real_nodes(self, n: Optional[int]) -> None:
-        object.__setattr__(self.g, "real_nodes", n)
-
-    @property
-    def real_nodes(self) -> int:
-        n = getattr(self.g, "real_nodes", None)
-        return self.g.meta.num_nodes if n is None else n
-
-    def _signature(self, g, m: GraphMeta) -> _Loaded:
-        """Identity + in-place version of everything load() copies (train._Slot._signature)."""
-        return _Loaded(g, [g[k] for k in self.fields + ("system",)] + [getattr(m, k) for k in _META_TENSORS])
-
-    def load(self, g, m: GraphMeta) -> None:
-        """Copy a batch of this shape into the static buffers (nothing when they hold this very batch, unwritten since): one
-        launch for everything already in the buffers' format, ``Tensor.copy_`` for what needs a dtype conversion (an fp32
-        batch, the int64 ``system``) or comes from another device."""
-        sig = self._signature(g, m)
-        if sig == self._loaded:
-            return
-        self._loaded = None
-        self.set_real_nodes(getattr(g, "real_nodes", None))
-        pairs = []
-        sm = self.g.meta
-        for dst, src in [(self.g[k], g[k]) for k in self.fields + ("system",)] + [(getattr(sm, k), getattr(m, k)) for k in _META_TENSORS]:
-            if src.shape != dst.shape:
-                raise ValueError(f"batch field of shape {tuple(src.shape)} loaded into a slot recorded with {tuple(dst.shape)}")
-            if src.dtype == dst.dtype and src.device == dst.device and src.is_contiguous():
-                pairs.append((dst.view(torch.int32), src.view(torch.int32)) if dst.element_size() == 8 else (dst, src))
-            else:
-                dst.copy_(src, non_blocking=True)
-        ops.copy_many(pairs)
-        self._loaded = sig
+from .batch import GraphMeta, bucket_sizes, graph_meta, pad_batch
+from .slots import Slot, SlotCache
+from .train import _AdamWState
 
 
-class Trainer64(_AdamWState):
+class Trainer64(_AdamWState, SlotCache):
     """AdamW(lr, weight_decay=1e-2) training of a ``DOSTransformer_phonon`` set to the float64 program
     (``model.double().set_program_dtype(torch.float64)``), all on libdosx: what ``model(batch)`` -> torch loss ->
     ``loss.backward()`` -> ``torch.optim.AdamW`` computes, without autograd and the per-tensor optimizer.
@@ -129,7 +52,7 @@ class Trainer64(_AdamWState):
 
     def __init__(self, model, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2, betas=(0.9, 0.999),
                  eps: float = 1e-8, replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0):
-        self._require_f64(model)
+        DOSTransformerBase._require_f64_program(model, "Trainer64")
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, tuple(betas), eps
         self.replay = bool(replay)
         self.max_slots = int(max_slots)
@@ -144,23 +67,14 @@ class Trainer64(_AdamWState):
         self.step_count = 0
         self._m = self._v = self._fp = None
         self.last_outputs = None
-        self._slots: "OrderedDict[tuple, _Slot64]" = OrderedDict()
+        self._slots: "OrderedDict[tuple, Slot]" = OrderedDict()
         self.slot_hits = self.slot_misses = self.slot_promoted = 0
         self._seen = {}
-
-    @staticmethod
-    def _require_f64(model) -> None:
-        ok = isinstance(model, DOSTransformerBase) and model._cfg.kind == "phonon" and model.program_dtype == torch.float64
-        if not ok:
-            raise DosxError(f"Trainer64 drives a DOSTransformer_phonon set to the float64 program "
-                            f"(model.double().set_program_dtype(torch.float64)), got {type(model).__name__}"
-                            + (f" with program_dtype {model.program_dtype}" if isinstance(model, DOSTransformerBase) else "")
-                            + ": the fp32 program is train.Trainer's")
 
     # ---- the step ------------------------------------------------------------------------------------------------------
     def _refuse(self, g) -> None:
         """What a step cannot run on - raised before anything (the dropout seed included) has changed."""
-        self._require_f64(self.model)
+        DOSTransformerBase._require_f64_program(self.model, "Trainer64")
         if self.bucket is None and getattr(g, "real_nodes", None) is not None:
             raise DosxError("Trainer64: ghost-padded batches (batch.pad_batch) are refused without bucket=(node_step, "
                             "edge_step) - slots are keyed by the exact shape of an unpadded batch")
@@ -210,32 +124,7 @@ class Trainer64(_AdamWState):
         return (n, e, B, n_max, bool(self.model.per_crystal_keys), drop is not None, None if drop is None else drop[0],
                 bool(F64.SOFTMAX64), float(self.beta))
 
-    def _lookup(self, key, allow_promote: bool = False):
-        """(slot or None) of a key, with the LRU / hit-rate bookkeeping of ``train.Trainer._lookup``.  ``allow_promote``
-        (step_dataset: the batch is collated straight into whatever bucket it gets): a bucket that is asked for the FIRST time
-        runs in the smallest live bucket that holds it with at most ``promote`` more node / edge rows, if there is one - the
-        shapes a reshuffled epoch shows once never pay for a recording, a shape that comes back is recorded on its second visit."""
-        slot = self._slots.get(key)
-        if slot is None and allow_promote and self.promote > 0:
-            seen = self._seen.get(key, 0)
-            self._seen[key] = seen + 1
-            if seen == 0:
-                host = promote_key(self._slots.keys(), key, self.promote)
-                if host is not None:
-                    self.slot_hits += 1
-                    self.slot_promoted += 1
-                    self._slots.move_to_end(host)
-                    return self._slots[host]
-        if slot is None:
-            self.slot_misses += 1
-            while len(self._slots) >= self.max_slots:          # evict the least recently used shape
-                self._slots.popitem(last=False)
-        else:
-            self.slot_hits += 1
-            self._slots.move_to_end(key)
-        return slot
-
-    def _run_slot(self, slot: _Slot64, fp, drop, fresh: bool) -> torch.Tensor:
+    def _run_slot(self, slot: Slot, fp, drop, fresh: bool) -> torch.Tensor:
         """The step on a slot whose static buffers hold the batch: recorded on first use, replayed afterwards."""
         if fresh:
             self._record(slot, fp, drop)                       # this IS the step for this batch (run + record)
@@ -254,33 +143,22 @@ class Trainer64(_AdamWState):
         slot = self._lookup(key)
         fresh = slot is None
         if fresh:
-            slot = _Slot64(g, m, fp.flat.device)
-        slot.load(g, m)
+            slot = Slot(g, m, "phonon", torch.float64)
+        else:
+            slot.load(g, m)
         loss = self._run_slot(slot, fp, drop, fresh)
         if fresh:
             self._slots[key] = slot
         return loss
 
-    def _record(self, slot: _Slot64, fp, drop) -> None:
+    def _record(self, slot: Slot, fp, drop) -> None:
         """Run the step once on the slot's static buffers while recording every launch."""
         g, m = slot.g, slot.g.meta
-        dev = fp.flat.device
-        # a recorded program replays libdosx calls only: the torch casts in the body of functional64 must hand back the
-        # very tensors they are given
-        same = all(F64._f64(g[k]) is g[k] for k in _F64_FIELDS) and \
-            g.system.to(device=dev, dtype=torch.int32).contiguous() is g.system
-        if not same:
-            raise DosxError("Trainer64: a slot buffer is not in the dtype / layout the float64 program reads")
-        timer_on = ops.KERNEL_TIMER.enabled
-        ops.KERNEL_TIMER.enabled = False
-        try:
+        F64.require_replayable(g, slot.fields, fp.flat.device, "Trainer64")
+        with ops.recording_scope():
             ops.RECORDER.begin()
             slot.loss, slot.out = self._program(fp, g, m, drop)
             slot.prog = ops.RECORDER.end()
-        finally:
-            if ops.RECORDER.active:
-                ops.RECORDER.end()
-            ops.KERNEL_TIMER.enabled = timer_on
 
     def step_dataset(self, ds, indices, n_max: Optional[int] = None) -> torch.Tensor:
         """One training step on the crystals ``indices`` of a device-resident ``loader.DeviceDataset`` (float64 tables:
@@ -292,7 +170,7 @@ class Trainer64(_AdamWState):
         serves a whole dataset (with per-crystal keys and no dropout the numbers do not depend on it)."""
         if not (self.replay and self.bucket is not None):
             return self.step(ds.collate(indices, n_max=n_max))
-        self._require_f64(self.model)
+        DOSTransformerBase._require_f64_program(self.model, "Trainer64")
         idx, N, E, n_max = ds.bucket_dims(indices, n_max)
         B = int(idx.shape[0])
         n_pad, e_pad = bucket_sizes(N, E, *self.bucket)
@@ -303,8 +181,8 @@ class Trainer64(_AdamWState):
         fresh = slot is None
         if fresh:
             t = ds._f64_tables()
-            slot = _Slot64.empty(fp.flat.device, B, n_pad, e_pad, n_max, int(t["x"].shape[1]), int(t["edge"].shape[1]),
-                                 int(t["target"].shape[1]))
+            slot = Slot.empty("phonon", fp.flat.device, torch.float64, B, n_pad, e_pad, n_max, int(t["x"].shape[1]),
+                              int(t["edge"].shape[1]), int(t["target"].shape[1]))
         ds.collate_into(slot.g, idx, slot.collate_scratch())
         slot._loaded = None                                        # (the static buffers now hold a batch no object stands for)
         slot.set_real_nodes(N)

@@ -158,25 +158,25 @@ def test_collate_into_matches_pad_batch(kind):
     from dostransformer_amd import synth
     from dostransformer_amd.batch import bucket_sizes, collate, pad_batch
     from dostransformer_amd.loader import DeviceDataset
-    from dostransformer_amd.train import _Slot, _META_TENSORS
+    from dostransformer_amd.slots import Slot, META_TENSORS
     cs = synth.phonon_crystals(14, seed=41, dtype=torch.float32) if kind == "phonon" else synth.edos_crystals(14, seed=42, dtype=torch.float32)
     ds = DeviceDataset(cs, DEV)
     for sel in ([3, 0, 7], [11], list(range(14)), [5, 5, 2, 13]):
         idx, N, E, n_max = ds.bucket_dims(sel, n_max=45)
         n_pad, e_pad = bucket_sizes(N, E, 16, 256)
         t = ds._f32_tables()
-        slot = _Slot.empty(kind, DEV, len(sel), n_pad, e_pad, n_max, t["x"].shape[1], t["edge"].shape[1], t["target"].shape[1],
+        slot = Slot.empty(kind, DEV, torch.float32, len(sel), n_pad, e_pad, n_max, t["x"].shape[1], t["edge"].shape[1], t["target"].shape[1],
                            tiled=True)
-        for v in list(slot.g._fields.values()) + [getattr(slot.g.meta, k) for k in _META_TENSORS]:
+        for v in list(slot.g._fields.values()) + [getattr(slot.g.meta, k) for k in META_TENSORS]:
             if torch.is_tensor(v):
                 v.fill_(77)                                  # stale contents of a previous batch must all be overwritten
-        ds.collate_into(slot.g, idx, slot.scratch)
+        ds.collate_into(slot.g, idx, slot.collate_scratch())
         ref = pad_batch(collate([cs[i] for i in sel], n_max=45), n_pad, e_pad)
         torch.cuda.synchronize()
         for k in slot.fields:
             a, b = slot.g[k].cpu(), ref[k]
             assert torch.equal(a.reshape(-1), b.to(a.dtype).reshape(-1)), (k, sel)
-        for k in _META_TENSORS:
+        for k in META_TENSORS:
             assert torch.equal(getattr(slot.g.meta, k).cpu(), getattr(ref.meta, k)), (k, sel)
         assert (slot.g.meta.num_nodes, slot.g.meta.num_edges, slot.g.meta.n_max) == (ref.meta.num_nodes, ref.meta.num_edges, 45)
         # node-aligned row tiles of the message GEMM: round 6 - the device packs greedily over the whole batch like the host
@@ -216,7 +216,7 @@ def test_device_greedy_tiles_equal_the_host_table_with_overfull_and_isolated_nod
     from dostransformer_amd import synth
     from dostransformer_amd.batch import bucket_sizes, collate, pad_batch
     from dostransformer_amd.loader import DeviceDataset
-    from dostransformer_amd.train import _Slot
+    from dostransformer_amd.slots import Slot
     from tests.gpu_util import _fatten
     cs = synth.phonon_crystals(10, seed=51, dtype=torch.float32) if kind == "phonon" else synth.edos_crystals(10, seed=52, dtype=torch.float32)
     indeg = lambda c, n: int((c["edge_index"][1] == n).sum())
@@ -233,9 +233,9 @@ def test_device_greedy_tiles_equal_the_host_table_with_overfull_and_isolated_nod
     for sel in (list(range(10)), [1], [5], [3, 3, 1], [5, 0], [1, 5], [9, 8, 7, 6, 5, 4, 3, 2, 1, 0], [2, 2, 2]):
         idx, N, E, n_max = ds.bucket_dims(sel, n_max=64)
         n_pad, e_pad = bucket_sizes(N, E, 16, 256)
-        slot = _Slot.empty(kind, DEV, len(sel), n_pad, e_pad, n_max, t["x"].shape[1], t["edge"].shape[1], t["target"].shape[1], tiled=True)
+        slot = Slot.empty(kind, DEV, torch.float32, len(sel), n_pad, e_pad, n_max, t["x"].shape[1], t["edge"].shape[1], t["target"].shape[1], tiled=True)
         slot.g.meta.seg_tile.fill_(-7)
-        ds.collate_into(slot.g, idx, slot.scratch)
+        ds.collate_into(slot.g, idx, slot.collate_scratch())
         ref = pad_batch(collate([cs[i] for i in sel], n_max=64), n_pad, e_pad)
         torch.cuda.synchronize()
         assert torch.equal(slot.g.meta.rowptr_dst.cpu(), ref.meta.rowptr_dst)

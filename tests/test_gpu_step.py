@@ -25,7 +25,8 @@ def test_revisited_batch_is_not_copied_again_but_an_edited_one_is():
     or another batch of the same bucket - is copied as before.  Same parameters as a trainer that always copies."""
     from dostransformer_amd import ops, synth
     from dostransformer_amd.batch import bucket_sizes, collate, pad_batch
-    from dostransformer_amd.train import Trainer, _Slot
+    from dostransformer_amd.slots import Slot
+    from dostransformer_amd.train import Trainer
     cs = synth.phonon_crystals(6, seed=41, dtype=torch.float32)
     g = collate(cs)
     g = pad_batch(g, *bucket_sizes(g.meta.num_nodes, g.meta.num_edges, 8, 128)).to(DEV)
@@ -35,7 +36,7 @@ def test_revisited_batch_is_not_copied_again_but_an_edited_one_is():
     ta, tb = Trainer(m_a, lr=1e-3, replay=True), Trainer(m_b, lr=1e-3, replay=True)
     calls = []
     real = ops.copy_many
-    always = _Slot.load
+    always = Slot.load
 
     def counting(pairs):
         calls.append(len(pairs))
@@ -53,11 +54,11 @@ def test_revisited_batch_is_not_copied_again_but_an_edited_one_is():
             n0 = len(calls)
             la = float(ta.step(batch))
             n_copy = len(calls) - n0
-            _Slot.load = load_always
+            Slot.load = load_always
             try:
                 lb = float(tb.step(batch))
             finally:
-                _Slot.load = always
+                Slot.load = always
             assert abs(la - lb) <= 1e-6 * max(1.0, abs(lb)), (step, la, lb)
             # step 0 records (the slot clones the batch); 1, 2, 4: untouched revisit -> no copy; 3: edited -> copy; 5: other object -> copy
             assert n_copy == (1 if step in (3, 5) else 0), (step, n_copy)
@@ -74,12 +75,13 @@ def test_fresh_batches_at_recycled_addresses_are_copied():
     holds this batch" check skips the copy and the step silently trains on stale data (found by
     test_step_dataset_is_the_step_on_the_collated_batch in round 6).  The bucket compares the objects themselves."""
     from dostransformer_amd import ops, synth
-    from dostransformer_amd.train import Trainer, _Slot
+    from dostransformer_amd.slots import Slot
+    from dostransformer_amd.train import Trainer
     n_atoms = [3, 5, 2, 7, 4, 6]
     m_a, m_b = _phonon(), _phonon()
     m_b.load_state_dict(copy.deepcopy(m_a.state_dict()))
     ta, tb = Trainer(m_a, lr=1e-3, replay=True), Trainer(m_b, lr=1e-3, replay=True)
-    always = _Slot.load
+    always = Slot.load
 
     def load_always(self, gg):
         self._loaded = None
@@ -89,11 +91,11 @@ def test_fresh_batches_at_recycled_addresses_are_copied():
         g = synth.phonon_batch(6, seed=90 + k, dtype=torch.float32, n_atoms=n_atoms).to(DEV)
         ptrs.add(g.x.data_ptr())
         la = float(ta.step(g))
-        _Slot.load = load_always
+        Slot.load = load_always
         try:
             lb = float(tb.step(g))
         finally:
-            _Slot.load = always
+            Slot.load = always
         assert la == lb, (k, la, lb)
         del g
     assert len(ta._slots) == 1                          # one bucket throughout: every step after the first is a load + replay
@@ -448,3 +450,55 @@ def test_promotion_into_a_bucket_that_a_batch_object_filled():
         if a.is_floating_point():
             assert torch.isfinite(a).all(), k
             assert float((a - b).abs().max()) < 5e-3, k
+
+
+def _first_step_fails_then_records(make_trainer, dtype, module, name):
+    """The bucket's first step raises on the host (``module.name``, the backward program, patched to raise before it launches
+    anything): the exception propagates, no slot is registered, the recorder is closed, the kernel timer and the side-stream
+    switch are what they were, no optimizer step was counted.  The next step records again, and - the failed step never
+    reached the parameters, dropout is 0 - its loss is bitwise the first-step loss of a second trainer on an identically
+    initialised model."""
+    from dostransformer_amd import ops, synth
+    g = synth.phonon_batch(4, seed=61, dtype=dtype, n_atoms=[3, 5, 2, 4]).to(DEV)
+    tr, ref = make_trainer(), make_trainer()
+    real = getattr(module, name)
+    calls = []
+
+    def failing(*args, **kwargs):
+        calls.append(len(calls))
+        raise RuntimeError("injected host failure")
+    ops.KERNEL_TIMER.reset(True)                          # (a scope that forgets to restore it leaves it off)
+    side_before = ops.GradSink.use_side_stream
+    setattr(module, name, failing)
+    try:
+        with pytest.raises(RuntimeError, match="injected host failure"):
+            tr.step(g)
+        timer_after = ops.KERNEL_TIMER.enabled
+    finally:
+        setattr(module, name, real)
+        ops.KERNEL_TIMER.reset(False)
+    assert calls == [0]
+    assert len(tr._slots) == 0
+    assert not ops.RECORDER.active
+    assert timer_after is True and ops.GradSink.use_side_stream == side_before
+    assert tr.step_count == 0
+    loss = tr.step(g).item()
+    assert tr.slot_misses == 2 and len(tr._slots) == 1 and tr.step_count == 1
+    want = ref.step(g).item()
+    assert ref.slot_misses == 1 and loss == want, (loss, want)
+
+
+@pytest.mark.parametrize("mode", ["replay", "graph"])
+def test_failed_first_step_registers_no_slot(mode):
+    """Trainer(replay=True): the failure is inside the recording; Trainer(graph=True): inside the warm-up of the capture."""
+    from dostransformer_amd import functional
+    from dostransformer_amd.train import Trainer
+    make = lambda: Trainer(_phonon(), lr=1e-3, replay=(mode == "replay"), graph=(mode == "graph"))
+    _first_step_fails_then_records(make, torch.float32, functional, "dostransformer_bwd")
+
+
+def test_failed_first_step_registers_no_slot_float64():
+    from dostransformer_amd import functional64
+    from dostransformer_amd.train64 import Trainer64
+    make = lambda: Trainer64(_phonon().double().set_program_dtype(torch.float64), lr=1e-3, replay=True)
+    _first_step_fails_then_records(make, torch.float64, functional64, "dostransformer_phonon_bwd")

@@ -267,9 +267,9 @@ def test_collate_padded_f64_matches_pad_batch(dataset, front):
     no fp32 copy."""
     import numpy as np
     from dostransformer_amd.batch import pad_batch
-    from dostransformer_amd.train64 import _Slot64
+    from dostransformer_amd.slots import Slot
     ds = dataset
-    slot = _Slot64.empty(torch.device(DEV), 4, 48, 896, 19, 118, 3, S_)
+    slot = Slot.empty("phonon", torch.device(DEV), torch.float64, 4, 48, 896, 19, 118, 3, S_)
     guards = {}
     for k in ("x", "edge_vec", "phdos"):
         view, whole = _guarded(tuple(slot.g[k].shape), front)

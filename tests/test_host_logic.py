@@ -339,9 +339,9 @@ def test_only_the_documented_switches_read_the_environment():
 
 
 def test_bucket_promotion_picks_the_smallest_live_bucket_that_fits():
-    """train.promote_key: a first-time bucket runs in a live one of the same batch size / key-slot count / tiling with at
+    """slots.promote_key: a first-time bucket runs in a live one of the same batch size / key-slot count / tiling with at
     least as many rows and at most `tol` more of either, the smallest by (edges, nodes); never in a smaller or a foreign one."""
-    from dostransformer_amd.train import promote_key
+    from dostransformer_amd.slots import promote_key
     rest = (64, 12, 64, True)
     live = [(448, 8960) + rest, (464, 9280) + rest, (480, 9600) + rest, (464, 9280, 32, 12, 32, True), (432, 8640) + rest]
     assert promote_key(live, (448, 9280) + rest, 0.08) == (464, 9280) + rest          # exact edges, one node step up
@@ -376,3 +376,87 @@ def test_bound_ratio_judges_each_row_on_its_own_scale():
     zero = torch.zeros(3)                                                                # a zero bound demands exact zeros
     assert bound_ratio(zero, torch.zeros(3, dtype=torch.float64), 0.0, 8) == 0.0
     assert bound_ratio(zero + 1e-30, torch.zeros(3, dtype=torch.float64), 0.0, 8) == float("inf")
+
+
+@pytest.mark.parametrize("kind,dtype,tiled", [("phonon", torch.float32, True), ("edos", torch.float32, False),
+                                              ("phonon", torch.float64, False)])
+def test_empty_slot_has_the_buffers_the_collate_kernel_fills(kind, dtype, tiled):
+    """slots.Slot.empty on the CPU (no libdosx call): every field and index array DeviceDataset.collate_into writes, in the
+    slot's dtype and the bucket's padded shape, and the lazily made collate scratch."""
+    from dostransformer_amd.batch import seg_tile_bound
+    from dostransformer_amd.slots import META_TENSORS, Slot
+    B, n_pad, e_pad, n_max, Fa, Fe, S = 4, 48, 896, 19, 118, 3, 51
+    slot = Slot.empty(kind, "cpu", dtype, B, n_pad, e_pad, n_max, Fa, Fe, S, tiled=tiled)
+    g, m = slot.g, slot.g.meta
+    want = {"x": (n_pad, Fa), "system": (B,)}
+    want.update({"edge_vec": (e_pad, Fe), "phdos": (B, S)} if kind == "phonon" else
+                {"edge_attr": (e_pad, Fe), "glob": (2 * B,), "y_ft": (B * S,)})
+    assert list(slot.fields) == list(want)
+    for k, shape in want.items():
+        assert tuple(g[k].shape) == shape and g[k].dtype == (torch.int32 if k == "system" else dtype) and g[k].is_contiguous(), k
+    assert (m.num_nodes, m.num_edges, m.num_graphs, m.n_max, m.edge_perm) == (n_pad, e_pad, B, n_max, None)
+    shapes = {"src": e_pad, "dst": e_pad, "perm_src": e_pad, "rowptr_dst": n_pad + 1, "rowptr_src": n_pad + 1, "graph_ptr": B + 1,
+              "node_graph": n_pad, "dense_row": n_pad, "inv_deg": n_pad}
+    assert set(shapes) == set(META_TENSORS)
+    for k, n in shapes.items():
+        t = getattr(m, k)
+        assert tuple(t.shape) == (n,) and t.dtype == (torch.float32 if k == "inv_deg" else torch.int32), k
+    if tiled:
+        assert tuple(m.seg_tile.shape) == (3, seg_tile_bound(48, 896, 4) + 1) and m.seg_tile.dtype == torch.int32
+    else:
+        assert m.seg_tile is None
+    assert slot.real_nodes == 48
+    assert (slot.prog, slot.plan, slot.graph_a, slot.graph_b, slot.keep, slot.loss, slot.out, slot.sse) == \
+        (None, [], None, None, None, None, None, None)
+    sc = slot.collate_scratch()
+    assert {k: (tuple(v.shape), v.dtype) for k, v in sc.items()} == \
+        {"small": ((4 * B + 3,), torch.int32), "node_row": ((48,), torch.int32), "edge_row": ((896,), torch.int32)}
+    assert slot.collate_scratch() is sc
+
+
+def _lookup_walk(cache):
+    """A fixed key sequence through ``cache._lookup`` the way the trainers use it (a fresh slot is registered after its first
+    step); after every call (slot_hits, slot_misses, slot_promoted, live keys, least recently used first) against the rule worked
+    out by hand for max_slots = 2, promote = 0.08."""
+    rest = (8, 12, 8, True)
+    A, a, B, C = (400, 8000) + rest, (416, 8320) + rest, (432, 8640) + rest, (600, 12000) + rest
+    walk = [
+        (B, True, (0, 1, 0, [B]), None),        # nothing live to run in: recorded
+        (B, True, (1, 1, 0, [B]), B),           # hit
+        (a, True, (2, 1, 1, [B]), B),           # first visit, B holds it with <= 8 % more rows: promoted, not recorded
+        (a, True, (2, 2, 1, [B, a]), None),     # second visit: recorded
+        (B, True, (3, 2, 1, [a, B]), B),        # hit: B is the most recently used now
+        (C, True, (3, 3, 1, [B, C]), None),     # no live bucket is large enough: recorded, the oldest (a) evicted
+        (a, True, (3, 4, 1, [C, a]), None),     # a is gone and was seen before: recorded again, B evicted
+        (C, True, (4, 4, 1, [a, C]), C),        # hit
+        (A, True, (5, 4, 2, [C, a]), a),        # first visit: promoted into a (C is 50 % larger), which moves to the end
+        (A, False, (5, 5, 2, [a, A]), None),    # step(batch) never promotes: recorded, C evicted
+    ]
+    for k, (key, allow, want, host) in enumerate(walk):
+        slot = cache._lookup(key, allow_promote=allow)
+        if slot is None:
+            assert host is None, k
+            cache._slots[key] = ("slot of", key)
+        else:
+            assert slot == ("slot of", host), k
+        assert (cache.slot_hits, cache.slot_misses, cache.slot_promoted, list(cache._slots)) == want, k
+
+
+def test_shared_lookup_counts_hits_misses_promotions_and_evicts_the_oldest():
+    from collections import OrderedDict
+    from dostransformer_amd.embedder_phDOS.DOSTransformer_phonon import DOSTransformer_phonon
+    from dostransformer_amd.slots import SlotCache
+    from dostransformer_amd.train import Trainer
+    from dostransformer_amd.train64 import Trainer64
+
+    class Bare(SlotCache):
+        def __init__(self):
+            self._slots, self._seen, self.max_slots, self.promote = OrderedDict(), {}, 2, 0.08
+            self.slot_hits = self.slot_misses = self.slot_promoted = 0
+    _lookup_walk(Bare())
+    torch.manual_seed(0)
+    m32 = DOSTransformer_phonon(2, 1, 118, 4, 16, "cpu", 0.0)
+    m64 = DOSTransformer_phonon(2, 1, 118, 4, 16, "cpu", 0.0).double().set_program_dtype(torch.float64)
+    assert Trainer._lookup is SlotCache._lookup and Trainer64._lookup is SlotCache._lookup
+    _lookup_walk(Trainer(m32, replay=True, max_slots=2, promote=0.08))
+    _lookup_walk(Trainer64(m64, replay=True, bucket=(8, 128), max_slots=2, promote=0.08))

@@ -84,7 +84,8 @@ def _phonon(dtype=torch.float64, attn_drop=0.0):
 
 
 def test_trainer64_takes_bucket_and_promote():
-    from dostransformer_amd.train64 import Trainer64, _Slot64
+    from dostransformer_amd.slots import Slot
+    from dostransformer_amd.train64 import Trainer64
     m64 = _phonon().set_program_dtype(torch.float64)
     tr = Trainer64(m64)
     assert tr.bucket is None and tr.promote == 0.0 and tr.slot_promoted == 0
@@ -100,7 +101,7 @@ def test_trainer64_takes_bucket_and_promote():
     with pytest.raises(TypeError):
         Trainer64(m64, bucket=(8, 128), graph=True)
     assert callable(tr.step_dataset)
-    slot = _Slot64.empty("cpu", 4, 48, 896, 19, 118, 3, 51)
+    slot = Slot.empty("phonon", "cpu", torch.float64, 4, 48, 896, 19, 118, 3, 51)
     g, m = slot.g, slot.g.meta
     assert g.x.shape == (48, 118) and g.edge_vec.shape == (896, 3) and g.phdos.shape == (4, 51)
     assert all(g[k].dtype == torch.float64 for k in ("x", "edge_vec", "phdos")) and g.system.dtype == torch.int32

@@ -21,11 +21,11 @@ for side in (True, False):
     n = 50
     t0 = time.perf_counter()
     for _ in range(n):
-        slot.prog_a.run()
+        slot.prog.run()
     t_host = (time.perf_counter() - t0) / n
     torch.cuda.synchronize()
     t_all = (time.perf_counter() - t0) / n
-    print(f"entries {len(slot.prog_a)}: host enqueue {t_host*1e3:.3f} ms/step, with sync {t_all*1e3:.3f} ms/step")
+    print(f"entries {len(slot.prog)}: host enqueue {t_host*1e3:.3f} ms/step, with sync {t_all*1e3:.3f} ms/step")
     break
 # same program, all on one stream: rebuild with side stream disabled inside _record
 import types
@@ -34,14 +34,14 @@ def rec_noside(self, slot, fp, ng):
     o.RECORDER.begin()
     with torch.no_grad():
         st = self._part_a(fp, slot.g, slot.g.meta); loss = self._part_b(fp, slot.g.meta, st, ng)
-    slot.prog_a = o.RECORDER.end(); slot.keep = (st, loss); slot.loss, slot.out, slot.sse = loss, st["out"], st.get("sse")
+    slot.prog = o.RECORDER.end(); slot.keep = (st, loss); slot.loss, slot.out, slot.sse = loss, st["out"], st.get("sse")
 ops.GradSink.use_side_stream = False
 tr2 = Trainer(model, replay=True)
 tr2._record = types.MethodType(rec_noside, tr2)
 tr2.step(g); tr2.step(g)
 slot = list(tr2._slots.values())[0]
 torch.cuda.synchronize(); n = 50; t0 = time.perf_counter()
-for _ in range(n): slot.prog_a.run()
+for _ in range(n): slot.prog.run()
 t_host = (time.perf_counter() - t0) / n
 torch.cuda.synchronize(); t_all = (time.perf_counter() - t0) / n
-print(f"single stream: entries {len(slot.prog_a)}: host enqueue {t_host*1e3:.3f} ms/step, with sync {t_all*1e3:.3f} ms/step")
+print(f"single stream: entries {len(slot.prog)}: host enqueue {t_host*1e3:.3f} ms/step, with sync {t_all*1e3:.3f} ms/step")

@@ -47,6 +47,6 @@ for kind in ("phonon", "edos"):
         slot = next(iter(pred._slots.values())) if len(pred._slots) == 1 else list(pred._slots.values())[-1]
         gp = slot.g
         ld = lat(lambda: slot.load(gp))
-        rn = lat(lambda: slot.prog_a.run())
+        rn = lat(lambda: slot.prog.run())
         print(f"predict {kind:6s} B={B:3d}: eager {e:8.1f} us   replay {r:8.1f} us   ({B / r * 1e6:9.0f} crystals/s)"
-              f"   [load only {ld:6.1f} us, program only {rn:6.1f} us, {slot.prog_a._n} launches]", flush=True)
+              f"   [load only {ld:6.1f} us, program only {rn:6.1f} us, {slot.prog._n} launches]", flush=True)
