@@ -287,6 +287,13 @@ class Collate(C.Structure):
                [(k, C.c_void_p) for k in ("out_tile_ptr", "tile_off_all", "tile_e_all", "tile_n_all", "seg_tile", "tile_p_all")]
 
 
+class Knn(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("C", "N", "K", "G", "pbc_mask", "reserved")] + \
+               [(k, C.c_double) for k in ("radius", "tol", "pad_dist", "var")] + \
+               [(k, C.c_void_p) for k in ("pos", "cell", "atom_ptr", "centers", "nbr_idx", "nbr_shift", "nbr_dist", "nbr_count",
+                                          "edge_attr")]
+
+
 class Seg64(C.Structure):
     _fields_ = [("p", C.c_void_p), ("ld", C.c_int32), ("width", C.c_int32), ("map", RowMap)]
 
@@ -418,6 +425,7 @@ _SIGS = {
     "dosx_collate_padded_f64": [C.POINTER(Collate), _P],
     "dosx_neighbor_count": [_P, _P, _P, _P, _I, _L, _D, _I, _I, _P, _P],
     "dosx_neighbor_fill": [_P, _P, _P, _P, _I, _L, _D, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "dosx_knn_graph": [C.POINTER(Knn), _P],
     "dosx_replay_op": [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
     "dosx_replay": [C.POINTER(Call), _I, C.POINTER(C.c_int)],
     "dosx_replay_timed": [C.POINTER(Call), _I, C.POINTER(C.c_float), C.POINTER(C.c_int)],

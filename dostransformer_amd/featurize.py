@@ -11,15 +11,25 @@ consume, so a dataset goes  structures -> build_data_all -> DeviceDataset -> Tra
 Entries may be the reference's pandas rows (``entry.structure`` an ASE ``Atoms``: ``.symbols``, ``.positions``,
 ``.cell.array``; ``entry.phdos``, ``entry.crystal_system``, ``entry.mp_id``) or plain dicts with the keys
 ``symbols, positions, cell, phdos, crystal_system, mp_id``.
+
+Electron-DOS input featurisation (counterpart of `data/mat2graph.py:33-47,81-107,120-243`): ``build_edos_all`` turns
+structures into the crystal graphs of ``synth.edos_crystal`` — the 12 nearest periodic neighbours inside 8 Å of every atom
+with their 41 Gaussian distance features, all from ONE ``ops.knn_graph`` launch (pymatgen's ``get_all_neighbors``, the sort,
+the cut and ``GaussianDistance.expand`` of the reference; no pymatgen / mendeleev / sklearn / ASE) — and ``load_elem_feats``
+standardises an element-embedding table the way sklearn's ``scale`` does.  structures -> build_edos_all -> DeviceDataset ->
+Trainer / Predictor.
 """
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence
 
+import json
+
 import numpy as np
 import torch
 
 from . import ops
+from .synth import E_BINS
 
 SYMBOLS = ("H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr "
            "Nb Mo Tc Ru Rh Pd Ag Cd In Sn Sb Te I Xe Cs Ba La Ce Pr Nd Pm Sm Eu Gd Tb Dy Ho Er Tm Yb Lu Hf Ta W Re Os Ir Pt "
@@ -100,4 +110,95 @@ def build_data_all(entries: Sequence, r_max: float = 5.0, device="cuda:0", masse
             "phdos": torch.as_tensor(np.asarray(_get(e, "phdos"), np.float64)).reshape(1, -1).to(dtype),
             "system": torch.tensor(system), "mp_id": _get(e, "mp_id"),
         })
+    return out
+
+
+# `data/mat2graph.py:94-107` (lower-case names there; matched case-insensitively here)
+_SYSTEM_CODES = {k.lower(): v for k, v in CRYSTAL_SYSTEMS.items()}
+
+
+def load_elem_feats(path_or_mapping, symbols: Sequence[str] = tuple(SYMBOLS[:100])) -> np.ndarray:
+    """`data/mat2graph.py:33-47`: a JSON file (or a dict) ``{symbol: vector}`` -> the ``[len(symbols), F]`` float64 table of
+    the first 100 elements, column-standardised like sklearn's ``scale`` (mean 0, population standard deviation 1; a
+    zero-variance column is divided by 1).  No table ships with the package (the matscholar embedding is the reference's
+    asset)."""
+    if isinstance(path_or_mapping, dict):
+        embs = path_or_mapping
+    else:
+        with open(path_or_mapping) as f:
+            embs = json.load(f)
+    missing = [s for s in symbols if s not in embs]
+    if missing:
+        raise ValueError(f"element table has no entry for {missing[:5]}{' ...' if len(missing) > 5 else ''}")
+    tab = np.vstack([np.asarray(embs[s], np.float64) for s in symbols])
+    std = tab.std(axis=0)
+    std[std < 10 * np.finfo(np.float64).eps] = 1.0
+    return (tab - tab.mean(axis=0)) / std
+
+
+def build_edos_all(entries: Sequence[dict], elem_feats, radius: float = 8.0, max_num_nbr: int = 12, step: float = 0.2,
+                   device="cuda:0", normalize_target: bool = True) -> List[Dict[str, object]]:
+    """`data/mat2graph.py:81-107,120-243` for a whole dataset at once.  ``entries``: dicts with ``numbers`` (Z) or
+    ``symbols``, ``positions`` (Cartesian), ``cell`` (rows = lattice vectors) and optionally ``glob`` ([energy_per_atom,
+    formation_energy_per_atom]), ``crystal_system`` (name, any case), ``y_ft``, ``y``, ``mp_id``.  ``elem_feats [Zmax, F]``:
+    the standardised element table (``load_elem_feats``).  Returns one host dict per entry in the schema of
+    ``synth.edos_crystal``: x [n+1, F] fp32 (last row = the zero prompt node, `:155-158`, in no edge), edge_index
+    [2, K*n] int64 (row 0 = atom i K times, row 1 = its neighbours by rank; a padded rank points at atom 0, `:222-227`),
+    edge_attr [K*n, G] fp32, glob [2], system, y_ft [201] (divided by its maximum when ``normalize_target``, `:86-88`; zeros
+    when the entry has none), y_max, mp_id, pos — and y when the entry has one.  The order inside a distance tie is the key of
+    include/dosx.h (DosxKnn); the reference leaves it to pymatgen."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("build_edos_all runs the neighbour selection on an MI355X through libdosx (no CPU fallback)")
+    entries = list(entries)
+    if not entries:
+        return []
+    table = torch.as_tensor(np.asarray(elem_feats, np.float64))
+    if table.dim() != 2:
+        raise ValueError("elem_feats must be a [Z, F] table")
+    K = int(max_num_nbr)
+    numbers, pos = [], []
+    for c, e in enumerate(entries):
+        z = np.asarray(e["numbers"], np.int64) if "numbers" in e else \
+            np.array([_Z_OF.get(s, -1) + 1 for s in e["symbols"]], np.int64)
+        p = np.asarray(e["positions"], np.float64).reshape(-1, 3)
+        if z.ndim != 1 or z.shape[0] != p.shape[0] or p.shape[0] == 0:
+            raise ValueError(f"entry {c}: needs >= 1 atom and one atomic number per position")
+        if z.min() < 1 or z.max() > table.shape[0]:
+            raise ValueError(f"entry {c}: atomic number outside the element table (1..{table.shape[0]})")
+        numbers.append(z)
+        pos.append(p)
+    cell = np.stack([np.asarray(e["cell"], np.float64).reshape(3, 3) for e in entries])
+    n = np.array([p.shape[0] for p in pos], np.int64)
+    atom_ptr = np.concatenate([[0], np.cumsum(n)])
+    centers = np.arange(0.0, radius + step, step)                   # GaussianDistance(0, radius, step).filter, `:171,215`
+    kg = ops.knn_graph(torch.from_numpy(np.concatenate(pos)).to(dev), torch.from_numpy(cell).to(dev),
+                       torch.from_numpy(atom_ptr.astype(np.int32)).to(dev), radius=float(radius), k=K,
+                       centers=torch.from_numpy(centers).to(dev), var=float(step))
+    nbr = kg["nbr_idx"].cpu().long()
+    attr = kg["edge_attr"].cpu()
+    out = []
+    for c, e in enumerate(entries):
+        a, b, nc = int(atom_ptr[c]), int(atom_ptr[c + 1]), int(n[c])
+        x = torch.zeros(nc + 1, table.shape[1], dtype=torch.float32)
+        x[:nc] = table[torch.from_numpy(numbers[c] - 1)].float()
+        has_y = e.get("y_ft") is not None
+        y_ft = torch.tensor(np.asarray(e["y_ft"]), dtype=torch.float32).reshape(-1) if has_y else torch.zeros(E_BINS)
+        y_max = y_ft.max() if has_y else torch.tensor(0.0)
+        item = {
+            "x": x,
+            "edge_index": torch.stack([torch.arange(nc).repeat_interleave(K), nbr[a:b].reshape(-1)], 0),
+            "edge_attr": attr[a * K:b * K].clone(),
+            "glob": torch.tensor(np.asarray(e["glob"], np.float64), dtype=torch.float32).reshape(2) if e.get("glob") is not None
+            else torch.zeros(2),
+            "system": torch.tensor(_SYSTEM_CODES.get(str(e.get("crystal_system", "")).lower(), 6)),
+            "y_ft": y_ft / y_max if has_y and normalize_target else y_ft,
+            "y_max": y_max,
+            "mp_id": e.get("mp_id", f"entry-{c}"),
+            "pos": torch.from_numpy(pos[c]).float(),
+        }
+        if e.get("y") is not None:
+            y = torch.tensor(np.asarray(e["y"]), dtype=torch.float32).reshape(-1)
+            item["y"] = y / y.max() if normalize_target else y
+        out.append(item)
     return out

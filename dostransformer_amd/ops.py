@@ -1553,6 +1553,39 @@ def neighbor_list(pos: torch.Tensor, cell: torch.Tensor, atom_ptr: torch.Tensor,
     return out
 
 
+def knn_graph(pos: torch.Tensor, cell: torch.Tensor, atom_ptr: torch.Tensor, radius: float = 8.0, k: int = 12,
+              centers: Optional[torch.Tensor] = None, var: float = 0.2, tol: float = 1e-8, pbc=(True, True, True)):
+    """The ``k`` nearest periodic neighbours inside ``radius`` of every atom of C crystals, in one launch (include/dosx.h:
+    dosx_knn_graph; the job pymatgen's ``get_all_neighbors`` + sort + cut does in `data/mat2graph.py:193,216-232`).
+    ``pos [N,3]`` fp64, ``cell [C,3,3]`` fp64 (rows = lattice vectors), ``atom_ptr [C+1]`` int32, all on the GPU.  Returns a
+    dict of device tensors: ``nbr_idx [N,k]`` int32 (crystal-local), ``nbr_shift [N,k,3]`` int32, ``nbr_dist [N,k]`` fp64,
+    ``nbr_count [N]`` int32 (ranks from there on are the reference's padding: index 0 at ``radius + 1``), and with
+    ``centers [G]`` fp64 also ``edge_attr [N*k,G]`` fp32 = exp(-(dist - centers)^2 / var^2) (`:162-179`)."""
+    assert pos.is_cuda and pos.dtype == torch.float64 and cell.dtype == torch.float64 and atom_ptr.dtype == torch.int32
+    pos, cell, atom_ptr = pos.contiguous(), cell.contiguous(), atom_ptr.contiguous()
+    dev, Cn, N, k = pos.device, int(cell.shape[0]), int(pos.shape[0]), int(k)
+    assert pos.shape == (N, 3) and cell.shape == (Cn, 3, 3) and atom_ptr.shape == (Cn + 1,)
+    out = {"nbr_idx": torch.empty(N, k, dtype=torch.int32, device=dev),
+           "nbr_shift": torch.empty(N, k, 3, dtype=torch.int32, device=dev),
+           "nbr_dist": torch.empty(N, k, dtype=torch.float64, device=dev),
+           "nbr_count": torch.empty(N, dtype=torch.int32, device=dev)}
+    d = _lib.Knn()
+    d.C, d.N, d.K, d.pbc_mask = Cn, N, k, sum(1 << a for a in range(3) if pbc[a])
+    d.radius, d.tol, d.pad_dist, d.var = float(radius), float(tol), float(radius) + 1.0, float(var)
+    d.pos, d.cell, d.atom_ptr = pos.data_ptr(), cell.data_ptr(), atom_ptr.data_ptr()
+    if centers is not None:
+        assert centers.is_cuda and centers.dtype == torch.float64 and centers.dim() == 1
+        centers = centers.contiguous()
+        d.G, d.centers = int(centers.shape[0]), centers.data_ptr()
+        out["edge_attr"] = torch.empty(N * k, d.G, dtype=torch.float32, device=dev)
+        d.edge_attr = out["edge_attr"].data_ptr()
+    for key in ("nbr_idx", "nbr_shift", "nbr_dist", "nbr_count"):
+        setattr(d, key, out[key].data_ptr())
+    if N:                                            # (an empty tensor has a null address, which the entry point refuses)
+        _call("dosx_knn_graph", C.byref(d), _stream())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # float64 program (csrc/f64.hip, include/dosx.h "float64 program"): thin wrappers, used by functional64.py
 # ---------------------------------------------------------------------------------------------------------------------

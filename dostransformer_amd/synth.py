@@ -120,3 +120,25 @@ def phonon_structures(count: int, seed: int):
                     "cell": cell, "phdos": dos / dos.max(), "crystal_system": systems[int(rng.integers(0, 7))],
                     "mp_id": f"synth-{k}"})
     return out
+
+
+def edos_structures(count: int, seed: int):
+    """Synthetic Electron-DOS *structures* (what `data/mat2graph.py:69-107` load_dataset reads per material, after the CIF
+    is parsed): random triclinic cells of 2-40 atoms among the first 100 elements, with ``glob``, a crystal-system name and a
+    smooth 201-bin target.  Input of ``featurize.build_edos_all``."""
+    import numpy as np
+    from .featurize import CRYSTAL_SYSTEMS
+    rng = np.random.default_rng(seed)
+    systems = [s.lower() for s in CRYSTAL_SYSTEMS] + ["triclinic"]
+    grid = np.linspace(0.0, 1.0, E_BINS)
+    out = []
+    for k in range(count):
+        n = int(rng.integers(2, 41))
+        side = 2.6 * n ** (1.0 / 3.0)                               # ~17.6 cubic angstrom per atom
+        cell = np.diag(rng.uniform(0.8, 1.25, 3) * side) + rng.uniform(-0.12, 0.12, (3, 3)) * side
+        dos = sum(a * np.exp(-((grid - c) / w) ** 2) for a, c, w in
+                  zip(rng.uniform(0.2, 1.0, 4), rng.uniform(0.05, 0.95, 4), rng.uniform(0.03, 0.2, 4)))
+        out.append({"numbers": rng.integers(1, 101, n), "positions": rng.uniform(0, 1, (n, 3)) @ cell, "cell": cell,
+                    "glob": rng.normal(size=2), "crystal_system": systems[int(rng.integers(0, 7))],
+                    "y_ft": dos * rng.uniform(5.0, 50.0), "mp_id": f"synth-{k}"})
+    return out

@@ -5,9 +5,12 @@ reference driver `main_eDOS.py` (loop `:101-127`, evaluation / model selection /
 defaults are those of `utils.py:25-43`.  The Materials-Project graphs (`data/processed/dos_dataset_random.pt`, built by
 `data/mat2graph.py` from downloads) do not ship with the reference, so by default it trains on synthetic graphs of the same
 layout; pass --pickle with a list of {x [n+1,200] (phantom zero node last, `mat2graph.py:155-158`),
-edge_index [2,E], edge_attr [E,41], glob [2], system, y_ft [201], mp_id} dicts (tensors) to use real ones.
+edge_index [2,E], edge_attr [E,41], glob [2], system, y_ft [201], mp_id} dicts (tensors) to use real ones, or --structures N
+to start from N synthetic *structures* (atomic numbers, positions, cell) and build their graphs on the GPU with
+featurize.build_edos_all - the route a list of real structures takes (`data/mat2graph.py:120-243` without pymatgen).
 
     python examples/train_edos.py --epochs 10 --crystals 512 --batch_size 64
+    python examples/train_edos.py --structures 256 --epochs 1
 """
 import argparse
 import os
@@ -19,7 +22,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dostransformer_amd import checkpoint, evaluate, synth  # noqa: E402
+from dostransformer_amd import checkpoint, evaluate, featurize, synth  # noqa: E402
 from dostransformer_amd.embedder_eDOS.DOSTransformer import DOSTransformer  # noqa: E402
 from dostransformer_amd.loader import DeviceDataset  # noqa: E402
 from dostransformer_amd.predict import Predictor  # noqa: E402
@@ -44,6 +47,8 @@ def parse_args(argv=None):
     # (not upstream: the data source and the output file)
     ap.add_argument("--crystals", type=int, default=512, help="synthetic graphs to generate when no --pickle is given")
     ap.add_argument("--pickle", default=None)
+    ap.add_argument("--structures", type=int, default=0,
+                    help="build the graphs of this many synthetic structures with featurize.build_edos_all (0: off)")
     ap.add_argument("--eval_batch_size", type=int, default=1, help="main_eDOS.py:55-56 evaluates at batch size 1")
     ap.add_argument("--out", default="edos_best.pt")
     ap.add_argument("--per-crystal-keys", action="store_true",
@@ -58,7 +63,17 @@ def main(argv=None):
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)                                    # `main_eDOS.py:20-23`
 
-    crystals = pickle.load(open(args.pickle, "rb")) if args.pickle else synth.edos_crystals(args.crystals, args.seed, torch.float32)
+    if args.structures:
+        # structures -> graphs on the GPU; the element table stands in for the matscholar embedding (`mat2graph.py:33-47`)
+        table = featurize.load_elem_feats({s: v for s, v in zip(featurize.SYMBOLS[:100],
+                                                                np.random.default_rng(args.seed).normal(size=(100, 200)))})
+        t0 = time.perf_counter()
+        crystals = featurize.build_edos_all(synth.edos_structures(args.structures, args.seed), table, device=dev)
+        print(f"built {len(crystals)} crystal graphs from structures in {time.perf_counter() - t0:.2f} s")
+    elif args.pickle:
+        crystals = pickle.load(open(args.pickle, "rb"))
+    else:
+        crystals = synth.edos_crystals(args.crystals, args.seed, torch.float32)
     # 8 : 1 : 1 random split (`main_eDOS.py:42-49`, sklearn's train_test_split with random_state)
     perm = np.random.default_rng(args.random_state).permutation(len(crystals))
     n_hold = max(1, len(perm) // 10)
@@ -92,7 +107,7 @@ def main(argv=None):
         loss = float(torch.stack(losses).mean())                                          # one host read per epoch
         history.append(loss)
         print(f"[ epoch {epoch + 1}/{args.epochs} ]  Total Loss: {loss:.4f}   ({seen / (time.perf_counter() - t0):.0f} crystals/s)")
-        if (epoch + 1) % args.eval:
+        if (epoch + 1) % min(args.eval, args.epochs):              # (a run shorter than --eval evaluates at its last epoch)
             continue
         # `main_eDOS.py:132-152`: validate; a new best in RMSE or MAE re-evaluates the test split (and, here, saves)
         v_rmse, v_mse, v_mae, v_r2, _ = evaluate.test(predictor, ds["valid"].batches(args.eval_batch_size), criterion_2, evaluate.r2)

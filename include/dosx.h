@@ -928,6 +928,42 @@ int dosx_neighbor_fill(const double* pos, const double* cell, const int32_t* ato
                        int32_t* crystal, int32_t* src, int32_t* dst, int32_t* shift, double* edge_vec,
                        dosx_stream_t stream);
 
+/* The Electron-DOS crystal graph of C crystals at once (`data/mat2graph.py:120-243`: pymatgen's `get_all_neighbors(radius)`,
+ * sorted by distance, cut at max_num_nbr, Gaussian-expanded; pymatgen is neither in the reference tree nor pinned, so this
+ * comment is the contract - PARITY UNPINNED at that boundary, like ASE's for dosx_neighbor_*).  One launch, N*K edges out.
+ *   neighbour set  for atom i of a crystal: every periodic image (j, S) of an atom j of the same crystal, S an integer shift,
+ *                  with  tol*tol < r2 <= radius*radius ,  d = (pos[j]-pos[i]) + ((S0*a0 + S1*a1) + S2*a2) ,
+ *                  r2 = (dx*dx + dy*dy) + dz*dz  in float64 without fused multiply-adds (dosx_neighbor_*'s arithmetic, bit for
+ *                  bit).  The atom itself and a coincident atom are out (r2 <= tol*tol); images (i, i, S != 0) are in.  Bit k
+ *                  of `pbc_mask` = axis k is periodic (otherwise S_k = 0).
+ *   selection      the K smallest by the key (r2 compared as a number, then j, then S0, S1, S2), ascending.  The reference
+ *                  leaves the order inside a distance tie to pymatgen; this key fixes it.  Ranking is on r2, never on a root.
+ *   outputs        rank r of atom i is row i*K + r:  nbr_idx = j (crystal-local), nbr_shift = S, nbr_dist = sqrt(r2);
+ *                  nbr_count[i] = neighbours kept (<= K).  Ranks from nbr_count[i] on are the reference's padding
+ *                  (`:222-227`): nbr_idx 0, nbr_shift 0, nbr_dist = pad_dist (the reference's radius + 1).
+ *   edge_attr      (optional) row i*K + r, column g:  t = nbr_dist - centers[g];  (float) exp(-(t*t) / (var*var)) , float64
+ *                  without fused multiply-adds, rounded to float32 once (`:162-179,237`); padded ranks included.
+ * Atoms per crystal and box sizes are free, but a shift digit is held in 11 bits: a pair whose shift box passes |S_k| = 1023 on
+ * an axis (a cell below radius/1000, a position a thousand cells away, a singular cell) contributes no neighbour.  The result is
+ * a pure function of the crystal (no atomics, no dependence on scheduling).  Required: 1 <= K <= 16 and N*K < 2^31; refused
+ * with rc -22 before any launch: null descriptor, C <= 0, N < 0, K out of range, radius <= 0, tol < 0, a null
+ * pos / cell / atom_ptr / nbr_idx / nbr_shift / nbr_dist / nbr_count, and with edge_attr set G < 1, null centers, var <= 0.
+ * N == 0 returns 0 without a launch. */
+typedef struct DosxKnn {
+  int32_t C, N, K, G, pbc_mask, reserved;
+  double radius, tol, pad_dist, var;
+  const double* pos;        /* [N][3] Cartesian */
+  const double* cell;       /* [C][3][3], rows = lattice vectors */
+  const int32_t* atom_ptr;  /* [C+1] */
+  const double* centers;    /* [G] Gaussian centres, made by the host with numpy.arange so they are bitwise the reference's */
+  int32_t* nbr_idx;         /* [N][K] crystal-local neighbour index, 0 in the padding */
+  int32_t* nbr_shift;       /* [N][K][3], 0 in the padding */
+  double*  nbr_dist;        /* [N][K], pad_dist in the padding */
+  int32_t* nbr_count;       /* [N] real neighbours kept (<= K) */
+  float*   edge_attr;       /* [N*K][G], may be NULL (then G, centers, var are ignored) */
+} DosxKnn;
+int dosx_knn_graph(const DosxKnn* d, dosx_stream_t stream);
+
 /* Replay of a recorded launch list (the host side of train.Trainer(replay=True), see csrc/replay.cpp): `n` calls are
  * issued in order.  A call names its callee by `op` (from dosx_replay_op: every `int dosx_*` entry point of this header,
  * plus "hipEventRecord" / "hipStreamWaitEvent" for stream fork/join) and carries the callee's integer-class arguments in

@@ -288,6 +288,61 @@ def neighbor_case(name, C, r_max):
           f"set (count + scan + fill, incl. 2 host reads) | numpy brute force ~{t_cpu * 1e3:8.0f} ms (extrapolated from 20)")
 
 
+def knn_case(name, C, radius=8.0, k=12, reps=9):
+    """The Electron-DOS graph of a dataset (`data/mat2graph.py:193,216-232`): ops.knn_graph (one launch, N*k edges and their 41
+    features out) next to the composition it replaces - ops.neighbor_list at the same cutoff, then a per-atom sort / top-k in
+    torch (no features).  Medians of `reps` event-timed calls after a warm-up."""
+    import numpy as np
+    from dostransformer_amd import synth
+    st = synth.edos_structures(C, 0)
+    sizes = np.array([len(e["numbers"]) for e in st])
+    ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(DEV)
+    P = torch.from_numpy(np.concatenate([e["positions"] for e in st])).to(DEV)
+    L = torch.from_numpy(np.stack([e["cell"] for e in st])).to(DEV)
+    cen = torch.from_numpy(np.arange(0.0, radius + 0.2, 0.2)).to(DEV)
+    N = int(sizes.sum())
+    ptr64 = ptr.long()
+
+    def composed():
+        nl = ops.neighbor_list(P, L, ptr, radius, self_interaction=False)
+        v = nl["edge_vec"]
+        r2 = (v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]
+        atom = ptr64[nl["crystal"].long()] + nl["src"].long()
+        o1 = torch.argsort(r2, stable=True)
+        order = o1[torch.argsort(atom[o1], stable=True)]
+        a_sorted = atom[order]
+        start = torch.searchsorted(a_sorted, torch.arange(N, device=DEV))
+        keep = order[torch.arange(a_sorted.numel(), device=DEV) - start[a_sorted] < k]
+        return nl["dst"][keep], r2[keep].sqrt(), atom[keep], v.shape[0]
+
+    def median_ms(fn):
+        fn()
+        torch.cuda.synchronize()
+        ts = []
+        for _ in range(reps):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            fn()
+            e.record()
+            torch.cuda.synchronize()
+            ts.append(s.elapsed_time(e))
+        return sorted(ts)[len(ts) // 2], min(ts), max(ts)
+
+    t_knn = median_ms(lambda: ops.knn_graph(P, L, ptr, radius=radius, k=k, centers=cen))
+    t_bare = median_ms(lambda: ops.knn_graph(P, L, ptr, radius=radius, k=k))
+    t_cmp = median_ms(composed)
+    out = ops.knn_graph(P, L, ptr, radius=radius, k=k)
+    dst, dist, atom, generated = composed()
+    kept = int(out["nbr_count"].sum())
+    # same distances (the composition has no rule inside a tie, so indices are compared through the distances only)
+    real = torch.arange(k, device=DEV)[None, :] < out["nbr_count"][:, None]
+    same = kept == dist.numel() and bool((out["nbr_dist"][real] == dist).all())
+    print(f"knn   {name:24s} C={C} atoms={N} radius={radius} k={k}: knn_graph {t_knn[0]:8.3f} ms (min {t_knn[1]:.3f} max {t_knn[2]:.3f}; "
+          f"without features {t_bare[0]:8.3f} ms) | neighbor_list + torch sort/top-k {t_cmp[0]:8.3f} ms (min {t_cmp[1]:.3f} max "
+          f"{t_cmp[2]:.3f}) x{t_cmp[0] / t_knn[0]:.1f} | edges kept {kept} (+{N * k - kept} padded) of {generated} inside the radius "
+          f"= 1/{generated / max(kept, 1):.1f} | distances agree: {same}", flush=True)
+
+
 def node_mlp_case(name, M, H):
     """NodeModel MLP: the one-launch kernel (csrc/mlp2.hip) against the two dosx_gemm launches it replaces, fwd and bwd."""
     x, agg = torch.randn(M, H, device=DEV), torch.randn(M, H, device=DEV)
@@ -353,6 +408,8 @@ def main():
     if w in ("all", "neighbors"):
         neighbor_case("phonon-set sized", 1500, 4.0)
         neighbor_case("phonon-set sized", 1500, 6.0)
+    if w in ("all", "knn"):
+        knn_case("eDOS-set sized", 4096)
     if w in ("all", "collate"):
         collate_case("phonon 64 crystals", 64)
         collate_case("eDOS 64 crystals", 64, "edos")
