@@ -723,7 +723,7 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
                 return m_
             m1, m2, m3 = draw((rows, H), p_res, 0), draw((rows, 4 * H), p_relu, 1), draw((rows, H), p_res, 2)
             fm = (m1, m2, m3)
-            a.flags |= 2                                   # DOSX_ATTN_NO_RESIDUAL: out = the attention output alone
+            a.flags |= ops.ATTN_NO_RESIDUAL                # out = the attention output alone
             att = _empty(dev, rows, H)
             a.out = att.data_ptr()
             ops.attention_fwd(a)
@@ -977,7 +977,7 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
             a.probs, a.qstats = probs.data_ptr(), qstats.data_ptr()
             a.dout, a.dx, a.dkvhat, a.dkv_accumulate = dout_att.data_ptr(), dxin.data_ptr(), dkvhat.data_ptr(), acc
             if fm is not None:
-                flags |= 2                 # DOSX_ATTN_NO_RESIDUAL
+                flags |= ops.ATTN_NO_RESIDUAL
             a.dscores = dsc.data_ptr() if dsc is not None else None
             a.dkv_part = kvp.data_ptr() if kvp is not None else None
             a.drop_mask = mask.data_ptr() if mask is not None else None
@@ -998,8 +998,8 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
         else:
             # dq (feeds the next layer's backward) on the main stream; dk+dv (feeds only the key-gradient
             # consumers at the very end) on the side stream, in layer order so dkvhat accumulates in order
-            ops.attention_bwd(desc(8))          # DOSX_ATTN_BWD_DQ_HALF
-            a2 = desc(4)                        # DOSX_ATTN_BWD_DKV_HALF
+            ops.attention_bwd(desc(ops.ATTN_BWD_DQ_HALF))
+            a2 = desc(ops.ATTN_BWD_DKV_HALF)
             if kv_needed_next and t == 0:
                 # the caller consumes dkvhat right after this call: the LAST key-gradient kernel runs on the main stream
                 # (behind a join that is already satisfied - the earlier layers' reductions finished long ago) instead of
@@ -1050,7 +1050,7 @@ def encoder_kv_fwd(P: Params, pre: str, x: torch.Tensor, xk: torch.Tensor, xv: t
         if H <= ops.ATTN_MAX_H:
             scratch = _empty(dev, rows, H)
             a = _attn_desc(Sq, Bq, Nk, Bk, H, Bq, 1, q, k, ones, zeros)
-            a.flags = 1 | 2                                # RAW_Q | NO_RESIDUAL: q and k are already normalised
+            a.flags = ops.ATTN_RAW_Q | ops.ATTN_NO_RESIDUAL  # q and k are already normalised
             a.out, a.probs = scratch.data_ptr(), probs.data_ptr()
             ops.attention_fwd(a)                           # (only the softmax weights are used)
         else:                                              # wider rows: scores + row softmax

@@ -14,7 +14,7 @@ from torch.nn import Parameter
 from .. import ops
 from .._lib import Attn
 
-RAW_Q, NO_RESIDUAL = 1, 2
+RAW_Q, NO_RESIDUAL = ops.ATTN_RAW_Q, ops.ATTN_NO_RESIDUAL
 
 
 class _BareAttention(torch.autograd.Function):

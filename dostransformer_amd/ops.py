@@ -13,11 +13,18 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from ._lib import Ffn, BIG, Attn, Gemm, ReduceJob, RowMap, Seg, Wgrad
 
-PRO_NONE, PRO_PRELU, PRO_LN_PRELU, PRO_ROWLN = 0, 1, 2, 3
-EPI_BIAS_ACT, EPI_LN, EPI_PRELU_LN_BWD, EPI_RELU_MASK, EPI_ROWLN_BWD, EPI_PRELU_BWD, EPI_SEGSUM, EPI_PRELU_LN_BWD_SEG = 0, 1, 2, 3, 4, 5, 6, 7
+# include/dosx.h's enumerators under the package's names (the values come from the generated _abi.py, never from a literal here)
+PRO_NONE, PRO_PRELU, PRO_LN_PRELU, PRO_ROWLN = _abi.DOSX_PRO_NONE, _abi.DOSX_PRO_PRELU, _abi.DOSX_PRO_LN_PRELU, _abi.DOSX_PRO_ROWLN
+EPI_BIAS_ACT, EPI_LN, EPI_PRELU_LN_BWD, EPI_RELU_MASK = _abi.DOSX_EPI_BIAS_ACT, _abi.DOSX_EPI_LN, _abi.DOSX_EPI_PRELU_LN_BWD, _abi.DOSX_EPI_RELU_MASK
+EPI_ROWLN_BWD, EPI_PRELU_BWD, EPI_SEGSUM = _abi.DOSX_EPI_ROWLN_BWD, _abi.DOSX_EPI_PRELU_BWD, _abi.DOSX_EPI_SEGSUM
+EPI_PRELU_LN_BWD_SEG = _abi.DOSX_EPI_PRELU_LN_BWD_SEG
+ATTN_RAW_Q, ATTN_NO_RESIDUAL = _abi.DOSX_ATTN_RAW_Q, _abi.DOSX_ATTN_NO_RESIDUAL
+ATTN_BWD_DKV_HALF, ATTN_BWD_DQ_HALF = _abi.DOSX_ATTN_BWD_DKV_HALF, _abi.DOSX_ATTN_BWD_DQ_HALF
+# DosxGemm.act has no enumerator: the header gives its values in the comment of DOSX_EPI_BIAS_ACT ("act: 0 none, 1 relu, 2 leaky(slope)"),
+# which tests/test_lib_abi.py reads
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 
 
@@ -1348,8 +1355,8 @@ def attention_fwd(a: Attn):
 
 def attention_bwd(a: Attn):
     # dP = dO.K^T and dQ = dS.K (dq half), dK = dS^T.Q and dV = P^T.dO (dkv half): 4*Bq*Sq*Nk*H flops each half
-    halves = (0 if a.flags & 4 else 1) + (0 if a.flags & 8 else 1)
-    name = "attention_bwd" + ("_dkv" if (a.flags & 4) else ("_dq" if (a.flags & 8) else ""))
+    halves = (0 if a.flags & ATTN_BWD_DKV_HALF else 1) + (0 if a.flags & ATTN_BWD_DQ_HALF else 1)
+    name = "attention_bwd" + ("_dkv" if (a.flags & ATTN_BWD_DKV_HALF) else ("_dq" if (a.flags & ATTN_BWD_DQ_HALF) else ""))
     _call("dosx_attention_bwd", C.byref(a), _stream(),
           w=lambda: (f"{name}[{_attn_shape(a)}]", "attn_bwd", "mfma", 4.0 * halves * a.Bq * a.Sq * a.Nk * a.H))
 
@@ -1386,7 +1393,7 @@ def attention_weights(q, k, probs, Sq, Bq, Nk, Bk, H):
         scratch = torch.empty(Sq * Bq, H, device=dev)
         a = _lib.Attn()
         a.Sq, a.Bq, a.Nk, a.Bk, a.H = Sq, Bq, Nk, Bk, H
-        a.q_stride_s, a.q_stride_b, a.flags = Bq, 1, 1 | 2            # RAW_Q | NO_RESIDUAL
+        a.q_stride_s, a.q_stride_b, a.flags = Bq, 1, ATTN_RAW_Q | ATTN_NO_RESIDUAL
         a.x, a.kvhat, a.gamma0, a.beta0 = q.data_ptr(), k.data_ptr(), ones.data_ptr(), zeros.data_ptr()
         a.out, a.probs = scratch.data_ptr(), probs.data_ptr()
         attention_fwd(a)                                               # (its P.K output is discarded)
@@ -1589,8 +1596,8 @@ def knn_graph(pos: torch.Tensor, cell: torch.Tensor, atom_ptr: torch.Tensor, rad
 # ---------------------------------------------------------------------------------------------------------------------
 # float64 program (csrc/f64.hip, include/dosx.h "float64 program"): thin wrappers, used by functional64.py
 # ---------------------------------------------------------------------------------------------------------------------
-ACT64_NONE, ACT64_RELU, ACT64_LEAKY, ACT64_PRELU = 0, 1, 2, 3
-COLSUM64_ROWS = 256                    # DOSX_COLSUM64_ROWS
+ACT64_NONE, ACT64_RELU, ACT64_LEAKY, ACT64_PRELU = _abi.DOSX_ACT64_NONE, _abi.DOSX_ACT64_RELU, _abi.DOSX_ACT64_LEAKY, _abi.DOSX_ACT64_PRELU
+COLSUM64_ROWS = _abi.DOSX_COLSUM64_ROWS
 _WGRAD64_ROWS = 512                    # rows of M per split of dosx_wgrad_f64
 
 
@@ -1771,8 +1778,8 @@ def reduce_rows64(src: torch.Tensor, n_out: int, n_red: int, stride_out: int, st
 
 
 # float64 attention of DOSTransformer_phonon (csrc/f64_attention.hip)
-ATTN64_MAX_H = 512                     # DOSX_ATTN64_MAX_H
-ATTN64_SOFTMAX_F64 = 1                 # DOSX_ATTN64_SOFTMAX_F64
+ATTN64_MAX_H = _abi.DOSX_ATTN64_MAX_H
+ATTN64_SOFTMAX_F64 = _abi.DOSX_ATTN64_SOFTMAX_F64
 
 
 def _attn64_desc(q, kvhat, gamma0, beta0, Sq: int, Bq: int, Nk: int, Bk: int, mask, softmax64: bool,

@@ -1,41 +1,18 @@
 """CPU-only checks of the per-crystal key counts of the float64 attention (DosxAttn64.key_ptr) and of the module switch that
-uses them (DOSTransformerBase.set_per_crystal_keys): the ctypes mirror has the C layout with key_ptr behind accumulate, and
-the switch belongs to the float64 program of DOSTransformer_phonon alone."""
-import ctypes as C
-import os
-import subprocess
-
+uses them (DOSTransformerBase.set_per_crystal_keys): DosxAttn64 has key_ptr behind accumulate (its C layout is checked field by
+field in tests/test_lib_abi.py), and the switch belongs to the float64 program of DOSTransformer_phonon alone."""
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.util import dosx_lib as _lib
 
 
-def _lib():
-    from dostransformer_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib
-
-
-def test_attn64_key_ptr_matches_c_layout(tmp_path):
+def test_attn64_key_ptr_matches_c_layout():
     _l = _lib()
     fields = [f for f, _ in _l.Attn64._fields_]
     assert "key_ptr" in fields
     assert fields[-2:] == ["accumulate", "key_ptr"]                 # appended: every earlier offset stays
-    probe = tmp_path / "probe_key_ptr.c"
-    probe.write_text(
-        '#include <stdio.h>\n#include <stddef.h>\n#include "dosx.h"\n'
-        'int main(void){\n printf("%zu\\n", sizeof(DosxAttn64));\n' +
-        "".join(f' printf("%zu\\n", offsetof(DosxAttn64, {f}));\n' for f in fields) +
-        ' return 0; }\n')
-    exe = tmp_path / "probe_key_ptr"
-    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(probe), "-o", str(exe)], check=True)
-    out = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[0] == C.sizeof(_l.Attn64)
-    assert out[1:] == [getattr(_l.Attn64, f).offset for f in fields]
-    assert out[-1] == _l.Attn64.key_ptr.offset > _l.Attn64.accumulate.offset
+    assert max(getattr(_l.Attn64, f).offset for f in fields) == _l.Attn64.key_ptr.offset > _l.Attn64.accumulate.offset
     assert _l.Attn64().key_ptr is None                              # default: today's behaviour
 
 

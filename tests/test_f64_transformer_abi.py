@@ -1,54 +1,23 @@
 """CPU-only checks of the float64 attention entry points (csrc/f64_attention.hip) and of the program switch of
-DOSTransformer_phonon (set_program_dtype): declared, exported, replayable, the DosxAttn64 mirror has the C layout, arguments
-are refused before any launch, and which modules run which program."""
+DOSTransformer_phonon (set_program_dtype): declared by the header, arguments are refused before any launch, and which modules
+run which program.  (Exports, thunks, the DosxAttn64 layout and its constants: tests/test_lib_abi.py, for the whole header.)"""
 import ctypes as C
 import os
-import subprocess
 
 import pytest
 import torch
+
+from tests.util import dosx_lib as _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["dosx_attention_f64", "dosx_attention_bwd_f64", "dosx_dense_rows_f64", "dosx_dense_rows_bwd_f64",
            "dosx_index_sum_f64"]
 
 
-def _lib():
-    from dostransformer_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib
-
-
 def test_attention_f64_symbols_declared_exported_and_replayable():
-    _l = _lib()
-    lib = _l.load()
     header = open(os.path.join(ROOT, "include", "dosx.h")).read()
-    thunks = open(os.path.join(ROOT, "dostransformer_amd", "csrc", "replay_thunks.inc")).read()
     for n in SYMBOLS:
-        assert f"{n}(" in header, n
-        assert n in _l.EXPORTS, n
-        assert hasattr(lib, n), n
-        assert f"thunk_{n}(" in thunks, n
-
-
-def test_attn64_struct_matches_c_layout(tmp_path):
-    _l = _lib()
-    probe = tmp_path / "probe_attn64.c"
-    fields = [f for f, _ in _l.Attn64._fields_]
-    probe.write_text(
-        '#include <stdio.h>\n#include <stddef.h>\n#include "dosx.h"\n'
-        'int main(void){\n printf("%zu\\n", sizeof(DosxAttn64));\n' +
-        "".join(f' printf("%zu\\n", offsetof(DosxAttn64, {f}));\n' for f in fields) +
-        ' printf("%d %d\\n", DOSX_ATTN64_MAX_H, DOSX_ATTN64_SOFTMAX_F64);\n return 0; }\n')
-    exe = tmp_path / "probe_attn64"
-    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(probe), "-o", str(exe)], check=True)
-    out = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[0] == C.sizeof(_l.Attn64)
-    assert out[1:1 + len(fields)] == [getattr(_l.Attn64, f).offset for f in fields]
-    from dostransformer_amd import ops
-    assert out[1 + len(fields):] == [ops.ATTN64_MAX_H, ops.ATTN64_SOFTMAX_F64]
+        assert f"int {n}(" in header, n                  # `int`: replayable (every such entry has a thunk, test_lib_abi.py)
 
 
 def test_attention_f64_argument_validation_needs_no_gpu():

@@ -1,25 +1,19 @@
-"""CPU-only checks of the Electron-DOS graph builder's boundary: dosx_knn_graph (csrc/knn.hip) is declared, exported, replayable
-and prototyped; the ctypes mirror of DosxKnn has the C layout; every bad descriptor is refused before any launch; and the
+"""CPU-only checks of the Electron-DOS graph builder's boundary: dosx_knn_graph (csrc/knn.hip) is declared, replayable and
+prototyped; DosxKnn has the size and field order its contract states (exports, thunks, argument types and the C layout field by
+field: tests/test_lib_abi.py, for the whole header); every bad descriptor is refused before any launch; and the
 host side of featurize.build_edos_all (element table, device check, synthetic structures) behaves."""
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from tests.util import dosx_lib as _lib
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "dosx_knn_graph"
 POINTERS = ("pos", "cell", "atom_ptr", "centers", "nbr_idx", "nbr_shift", "nbr_dist", "nbr_count", "edge_attr")
-
-
-def _lib():
-    from dostransformer_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib
 
 
 def test_knn_graph_declared_exported_replayable_and_prototyped():
@@ -28,27 +22,18 @@ def test_knn_graph_declared_exported_replayable_and_prototyped():
     header = open(os.path.join(ROOT, "include", "dosx.h")).read()
     thunks = open(os.path.join(ROOT, "dostransformer_amd", "csrc", "replay_thunks.inc")).read()
     assert f"int {NAME}(const DosxKnn* d, dosx_stream_t stream);" in header
-    assert NAME in _l.EXPORTS and hasattr(lib, NAME)
-    assert f"thunk_{NAME}(" in thunks and f'{{"{NAME}", thunk_{NAME}, 2, 0}}' in thunks
+    assert f'{{"{NAME}", thunk_{NAME}, 2, 0}}' in thunks
     ni, nf = C.c_int(0), C.c_int(0)
     assert lib.dosx_replay_op(NAME.encode(), C.byref(ni), C.byref(nf)) >= 0 and (ni.value, nf.value) == (2, 0)
-    assert getattr(lib, NAME).argtypes == _l._SIGS[NAME]
+    assert getattr(lib, NAME).argtypes == [C.POINTER(_l.Knn), C.c_void_p]
     makefile = open(os.path.join(ROOT, "dostransformer_amd", "csrc", "Makefile")).read()
     assert makefile.count(" knn.hip") == 3                     # libdosx.so and the two diagnostic builds
 
 
-def test_knn_descriptor_matches_c_layout(tmp_path):
+def test_knn_descriptor_matches_c_layout():
     _l = _lib()
     fields = [k for k, _ in _l.Knn._fields_]
-    probe = tmp_path / "probe.c"
-    probe.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dosx.h"\nint main(void){\n'
-                     ' printf("%zu", sizeof(DosxKnn));\n' +
-                     "".join(f' printf(" %zu", offsetof(DosxKnn, {k}));\n' for k in fields) + " return 0; }\n")
-    exe = tmp_path / "probe"
-    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(probe), "-o", str(exe)], check=True)
-    out = [int(x) for x in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[0] == C.sizeof(_l.Knn) == 6 * 4 + 4 * 8 + 9 * 8
-    assert out[1:] == [getattr(_l.Knn, k).offset for k in fields]
+    assert C.sizeof(_l.Knn) == 6 * 4 + 4 * 8 + 9 * 8
     assert fields == ["C", "N", "K", "G", "pbc_mask", "reserved", "radius", "tol", "pad_dist", "var"] + list(POINTERS)
 
 

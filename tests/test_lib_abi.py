@@ -1,6 +1,7 @@
-"""CPU-only checks of the C-ABI boundary: libdosx.so loads, exports every symbol include/dosx.h
-declares, and the ctypes mirrors of its structs have the C layout (checked with a gcc-compiled
-probe of the real header).  No compute calls (there is no GPU here)."""
+"""CPU-only checks of the C-ABI boundary: libdosx.so loads and exports every symbol include/dosx.h declares; the GENERATED
+binding (dostransformer_amd/_abi.py, tools/gen_ctypes.py) is checked against the header as a whole - every field of every struct
+with a gcc-compiled probe of the real header, every argument of every prototype, every constant.  No compute calls (there is no
+GPU here)."""
 import ctypes as C
 import os
 import re
@@ -13,17 +14,81 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "dosx.h")
 
 
+def _gen(name):
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        return __import__(name)
+    finally:
+        sys.path.pop(0)
+
+
+def _code():
+    """include/dosx.h without its comments."""
+    return re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S))
+
+
 def _declared():
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(dosx_[a-z0-9_]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(dosx_[a-z0-9_]+)\s*\(", _code())))
+
+
+def _structs():
+    """[(C name, [(field type, field name, array length or None)])] of every struct of the header, parsed here (not by the generator)."""
+    out = []
+    for name, body in re.findall(r"typedef struct (Dosx\w+) \{(.*?)\} \1;", _code(), flags=re.S):
+        fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            ty, first = re.match(r"^(.*?)(\w+(?:\[\d+\])?(?: ?, ?\w+(?:\[\d+\])?)*)$", decl).groups()
+            for n in first.split(","):
+                m = re.match(r"^ ?(\w+)(?:\[(\d+)\])?$", n)
+                fields.append((ty.strip(), m.group(1), int(m.group(2)) if m.group(2) else None))
+        out.append((name, fields))
+    return out
+
+
+def _header_constants():
+    """{name: value} of every enumerator and integer #define DOSX_* of the header, parsed here (not by the generator)."""
+    code, out = _code(), {}
+    for body in re.findall(r"\benum\s*\{(.*?)\}", code, flags=re.S):
+        for name, val in re.findall(r"(DOSX_\w+)\s*=\s*(-?\d+)", body):
+            out[name] = int(val)
+        assert len(re.findall(r"DOSX_\w+", body)) == body.count("=") == len([e for e in body.split(",") if e.strip()])
+    for name, val in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(DOSX_\w+)[ \t]+(-?\d+)[ \t]*$", code, flags=re.M):
+        out[name] = int(val)
+    return out
+
+
+# C type -> (sizeof, class) on the one ABI the library is built for (LP64); the probe below confirms the sizes with gcc.
+# Independent of tools/gen_ctypes.py on purpose: what the binding declares is compared with what the HEADER declares.
+SCALARS = {"int": (4, "int"), "int32_t": (4, "int"), "int64_t": (8, "int"), "long long": (8, "int"), "unsigned long long": (8, "uint"),
+           "size_t": (8, "uint"), "float": (4, "float"), "double": (8, "float")}
+CODES = {"int": "bhilq", "uint": "BHILQ", "float": "fd"}         # ctypes' one-letter type codes per class
+
+
+def _assert_ctype(ct, c_type, by_value, where):
+    """``ct`` (a ctypes type) is what the declared C type asks for: scalar class and size, pointer-ness, which struct."""
+    from dostransformer_amd import _abi
+    t = " ".join(re.sub(r"\bconst\b", " ", c_type).replace("*", " * ").split())
+    if t.endswith(" *"):
+        base = t[:-2]
+        if base == "char":
+            assert ct is C.c_char_p, where
+        elif base.startswith("Dosx"):
+            assert not by_value and ct is C.POINTER(getattr(_abi, base[4:])) and ct._type_.__name__ == base[4:], where
+        else:
+            assert base in SCALARS or base == "void", where
+            assert ct is C.c_void_p, where
+    elif t == "dosx_stream_t":
+        assert not by_value and ct is C.c_void_p, where
+    elif t.startswith("Dosx"):
+        assert by_value and ct is getattr(_abi, t[4:]), where
+    else:
+        size, cls = SCALARS[t]
+        assert isinstance(getattr(ct, "_type_", None), str) and ct._type_ in CODES[cls] and C.sizeof(ct) == size, (where, ct)
 
 
 def test_library_exports_every_declared_symbol():
-    from dostransformer_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
+    from tests.util import dosx_lib
+    _lib = dosx_lib()
     lib = _lib.load()
     names = _declared()
     assert len(names) >= 30
@@ -34,26 +99,122 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_ctypes_structs_match_c_layout(tmp_path):
-    from dostransformer_amd import _lib
+    """THE check of the whole boundary's data side: one gcc probe over every field of every struct of include/dosx.h.  Each
+    ctypes mirror has the header's field names in the header's order, every field its C offset, size and type class, every
+    struct its C size."""
+    from dostransformer_amd import _abi, _lib
+    structs = _structs()
+    mirrors = {k: v for k, v in vars(_abi).items() if isinstance(v, type) and issubclass(v, C.Structure)}
+    assert len(structs) >= 24 and {n[4:] for n, _ in structs} == set(mirrors)
+    assert len(structs) == len(re.findall(r"\b(?:struct|union)\b", _code()))           # no struct the regex above missed
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "dosx.h"', "int main(void) {"]
+    lines += [f'  printf("%zu\\n", sizeof({t}));' for t in SCALARS]
+    for name, fields in structs:
+        lines.append(f'  printf("%zu\\n", sizeof({name}));')
+        lines += [f'  printf("%zu %zu\\n", offsetof({name}, {f}), sizeof((({name}*)0)->{f}));' for _, f, _ in fields]
     probe = tmp_path / "probe.c"
-    probe.write_text(
-        '#include <stdio.h>\n#include <stddef.h>\n#include "dosx.h"\n'
-        'int main(void){\n'
-        ' printf("%zu %zu %zu %zu %zu %zu %zu %zu\\n", sizeof(DosxRowMap), sizeof(DosxSeg), sizeof(DosxGemm), sizeof(DosxWgrad),'
-        ' sizeof(DosxReduceJob), sizeof(DosxAttn), sizeof(DosxFfn), sizeof(DosxCall));\n'
-        ' printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\\n", offsetof(DosxGemm, w), offsetof(DosxGemm, out_map), offsetof(DosxGemm, partials),'
-        ' offsetof(DosxWgrad, slab), offsetof(DosxAttn, x), offsetof(DosxAttn, partials_kv), offsetof(DosxFfn, out),'
-        ' offsetof(DosxCall, iarg), offsetof(DosxCall, farg));\n return 0; }\n')
+    probe.write_text("\n".join(lines + ["  return 0;", "}", ""]))
     exe = tmp_path / "probe"
     subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(probe), "-o", str(exe)], check=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
-    sizes = [int(x) for x in out[:8]]
-    offs = [int(x) for x in out[8:]]
-    assert sizes == [C.sizeof(_lib.RowMap), C.sizeof(_lib.Seg), C.sizeof(_lib.Gemm), C.sizeof(_lib.Wgrad),
-                     C.sizeof(_lib.ReduceJob), C.sizeof(_lib.Attn), C.sizeof(_lib.Ffn), C.sizeof(_lib.Call)]
-    assert offs == [_lib.Gemm.w.offset, _lib.Gemm.out_map.offset, _lib.Gemm.partials.offset, _lib.Wgrad.slab.offset,
-                    _lib.Attn.x.offset, _lib.Attn.partials_kv.offset, _lib.Ffn.out.offset, _lib.Call.iarg.offset,
-                    _lib.Call.farg.offset]
+    out = iter(subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    assert [int(next(out)) for _ in SCALARS] == [size for size, _ in SCALARS.values()]
+    for name, fields in structs:
+        cls = mirrors[name[4:]]
+        assert getattr(_lib, name[4:]) is cls                                           # re-exported under the same name
+        assert [f for f, _ in cls._fields_] == [f for _, f, _ in fields], name
+        assert C.sizeof(cls) == int(next(out)), name
+        for (c_type, f, n), (_, ct) in zip(fields, cls._fields_):
+            d = getattr(cls, f)
+            assert [d.offset, d.size] == [int(v) for v in next(out).split()], (name, f)
+            if n is not None:
+                assert issubclass(ct, C.Array) and ct._length_ == n, (name, f)
+                ct = ct._type_
+            _assert_ctype(ct, c_type, True, (name, f))
+    assert next(out, None) is None
+
+
+def test_argtypes_and_restypes_match_the_header_prototypes():
+    """THE check of the boundary's call side: for every prototype of include/dosx.h the loaded function's argtypes have the
+    prototype's arity and, argument by argument, its class (integer / floating point / address / descriptor pointer / string),
+    scalar size and descriptor type; restype likewise.  The expectation is computed here from the header text."""
+    from tests.util import dosx_lib
+    lib = dosx_lib().load()
+    gen = _gen("gen_replay_thunks")
+    decls = list(gen.declarations(gen.strip_comments(open(HEADER).read())))
+    assert [d[1] for d in decls] == list(dosx_lib().EXPORTS) and sorted(d[1] for d in decls) == _declared() and len(decls) >= 125
+    n_struct = 0
+    for ret, name, params, _ in decls:
+        fn = getattr(lib, name)
+        assert len(fn.argtypes) == len(params), name
+        for i, (ct, c_type) in enumerate(zip(fn.argtypes, params)):
+            _assert_ctype(ct, c_type, False, (name, i, c_type))
+            n_struct += "Dosx" in c_type
+        _assert_ctype(fn.restype, ret, False, (name, "return"))
+    assert n_struct == len(re.findall(r"\bconst Dosx\w+\s*\*", _code())) >= 32       # every descriptor pointer was seen as one
+    # spot facts straight from the header, so that the walk above cannot pass by checking nothing
+    assert lib.dosx_adamw_f64.argtypes[5] is C.c_double and lib.dosx_adamw.argtypes[5] is C.c_float
+    assert lib.dosx_softmax_fwd.argtypes[2] is C.c_int64 and lib.dosx_csr_build.argtypes[17] is C.c_size_t
+    assert lib.dosx_last_error.restype is C.c_char_p and lib.dosx_wgrad_scratch_floats.restype is C.c_int64
+    assert lib.dosx_version.restype is C.c_int and lib.dosx_version.argtypes == []
+
+
+def test_abi_py_is_what_the_generator_makes_of_the_header(tmp_path):
+    """dostransformer_amd/_abi.py is GENERATED (tools/gen_ctypes.py, run by csrc/Makefile): the committed file is the
+    generator's output for the committed header, byte for byte."""
+    gen = _gen("gen_ctypes")
+    committed = open(os.path.join(ROOT, "dostransformer_amd", "_abi.py")).read()
+    assert committed.startswith("# GENERATED by tools/gen_ctypes.py from include/dosx.h") and "do not edit" in committed.splitlines()[0]
+    sys.argv, argv = ["gen", HEADER, str(tmp_path / "abi.py")], sys.argv
+    try:
+        gen.main()
+    finally:
+        sys.argv = argv
+    assert (tmp_path / "abi.py").read_text() == committed
+    assert gen.generate(open(HEADER).read()) == committed                       # deterministic
+
+
+@pytest.mark.parametrize("line, what", [
+    ("typedef struct DosxA { int32_t n; uint8_t x; } DosxA;", "uint8_t"),                 # unknown field type
+    ("int dosx_f(const float* x, short n, dosx_stream_t stream);", "short"),            # unknown parameter type
+    ("unsigned dosx_f(int n);", "unsigned"),                                            # unknown return type
+    ("typedef struct DosxA { int32_t a[DOSX_N]; } DosxA;", "array size"),                # non-literal array size
+    ("typedef struct DosxA { int32_t a : 3; } DosxA;", "a : 3"),                         # bit-field
+    ("typedef struct DosxA { int32_t n; union { float f; int32_t i; } u; } DosxA;", "DosxA"),
+    ("typedef struct DosxA { int (*fn)(int); } DosxA;", "fn"),                           # function pointer
+    ("typedef struct DosxA { const float* p, q; } DosxA;", "one pointer"),               # `q` would not be a pointer
+    ("typedef struct DosxA { DosxA* next; } DosxA;", "DosxA*"),                          # no pointer-to-struct fields
+    ("enum { DOSX_X = 1 << 3 };", "DOSX_X"),                                            # not an integer literal
+])
+def test_generator_refuses_what_it_cannot_map(line, what):
+    """A declaration outside the header's closed set of types stops the generator, with the header line in the message."""
+    gen = _gen("gen_ctypes")
+    header = "#include <stdint.h>\n/* a comment\n   of two lines */\ntypedef void* dosx_stream_t;\n" + line + "\nint dosx_version(void);\n"
+    with pytest.raises(gen.Unmapped) as e:
+        gen.generate(header)
+    assert "dosx.h:5:" in str(e.value) and what in str(e.value) and line in str(e.value), str(e.value)
+    assert "SIGS = {" in gen.generate(header.replace(line, "int dosx_g(int n);"))       # the frame around the line is fine
+
+
+def test_python_constants_equal_the_header_enumerators():
+    """No Python literal restates the header: every PRO_* / EPI_* / ACT64_* / ATTN* / COLSUM64_* name of ops.py, and every
+    DOSX_* of _abi.py, has the value the header text gives its enumerator or #define."""
+    from dostransformer_amd import _abi, ops
+    from dostransformer_amd.layers import multihead_attention as mha
+    header = _header_constants()
+    assert len(header) >= 24 and header["DOSX_EPI_PRELU_LN_BWD_SEG"] == 7 and header["DOSX_OP_HIP_BASE"] == 1000
+    assert {k: v for k, v in vars(_abi).items() if k.startswith("DOSX_")} == header
+    named = [k for k in vars(ops) if re.match(r"(PRO|EPI|ACT64)_[A-Z]", k)]
+    assert len(named) == 4 + 8 + 4 and all("DOSX_" + k in header for k in named), named
+    shared = [k[5:] for k in header if hasattr(ops, k[5:])]
+    assert set(named) | {"ATTN_RAW_Q", "ATTN_NO_RESIDUAL", "ATTN_BWD_DKV_HALF", "ATTN_BWD_DQ_HALF", "COLSUM64_ROWS", "ATTN64_MAX_H",
+                         "ATTN64_SOFTMAX_F64"} == set(shared)
+    for k in shared:
+        assert getattr(ops, k) == header["DOSX_" + k], k
+    assert (mha.RAW_Q, mha.NO_RESIDUAL) == (header["DOSX_ATTN_RAW_Q"], header["DOSX_ATTN_NO_RESIDUAL"])
+    # DosxGemm.act has no enumerator; the header states its values in the comment of DOSX_EPI_BIAS_ACT
+    act = re.search(r"act: (\d) none, (\d) relu, (\d) leaky\(slope\)", open(HEADER).read())
+    assert (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LEAKY) == tuple(int(v) for v in act.groups())
+    assert [k for k in vars(ops) if re.match(r"ACT_[A-Z]", k)] == ["ACT_NONE", "ACT_RELU", "ACT_LEAKY"]
 
 
 def test_argument_validation_needs_no_gpu():

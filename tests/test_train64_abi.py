@@ -1,20 +1,15 @@
 """CPU-only checks of the float64 training step's entry points (csrc/f64_train.hip) and of train64.Trainer64's refusals:
-declared, exported, replayable, prototyped; arguments are refused before any launch; which modules Trainer64 takes."""
+declared, replayable, prototyped with double hyper-parameters; arguments are refused before any launch; which modules
+Trainer64 takes.  (Exports, thunks and argument types against the header: tests/test_lib_abi.py, for the whole header.)"""
 import os
 
 import pytest
 import torch
 
+from tests.util import dosx_lib as _lib
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ["dosx_loss_phonon_f64", "dosx_adamw_f64"]
-
-
-def _lib():
-    from dostransformer_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib
 
 
 def test_train64_symbols_declared_exported_replayable_and_prototyped():
@@ -22,16 +17,12 @@ def test_train64_symbols_declared_exported_replayable_and_prototyped():
     _l = _lib()
     lib = _l.load()
     header = open(os.path.join(ROOT, "include", "dosx.h")).read()
-    thunks = open(os.path.join(ROOT, "dostransformer_amd", "csrc", "replay_thunks.inc")).read()
     for n in SYMBOLS:
-        assert f"{n}(" in header, n
-        assert n in _l.EXPORTS, n
-        assert hasattr(lib, n), n
-        assert f"thunk_{n}(" in thunks, n
+        assert f"int {n}(" in header, n
         ni, nf = C.c_int(0), C.c_int(0)
         assert lib.dosx_replay_op(n.encode(), C.byref(ni), C.byref(nf)) >= 0, n
         args = getattr(lib, n).argtypes
-        assert args == _l._SIGS[n] and len(args) == ni.value + nf.value, n
+        assert len(args) == ni.value + nf.value, n
         assert sum(1 for t in args if t is C.c_double) == nf.value, n          # every hyper-parameter replays as a double
     assert _l._SIGS["dosx_loss_phonon_f64"].count(C.c_double) == 1 and _l._SIGS["dosx_adamw_f64"].count(C.c_double) == 5
 

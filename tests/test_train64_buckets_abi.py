@@ -1,5 +1,6 @@
 """CPU-only checks of the float64 trainer's shape buckets: the padded float64 collate entry (csrc/csr.hip) is declared,
-exported, replayable and prototyped and refuses bad descriptors before any launch; train64.Trainer64 takes ``bucket`` /
+replayable and prototyped like its fp32 twin (exports, thunks, argument types: tests/test_lib_abi.py) and refuses bad descriptors
+before any launch; train64.Trainer64 takes ``bucket`` /
 ``promote``; predict.Predictor64 takes only a float64-switched phonon module."""
 import ctypes as C
 import os
@@ -7,29 +8,20 @@ import os
 import pytest
 import torch
 
+from tests.util import dosx_lib as _lib
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "dosx_collate_padded_f64"
-
-
-def _lib():
-    from dostransformer_amd import _lib
-    if not os.path.exists(_lib.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    return _lib
 
 
 def test_collate_padded_f64_declared_exported_replayable_and_prototyped():
     _l = _lib()
     lib = _l.load()
     header = open(os.path.join(ROOT, "include", "dosx.h")).read()
-    thunks = open(os.path.join(ROOT, "dostransformer_amd", "csrc", "replay_thunks.inc")).read()
     assert f"int {NAME}(const DosxCollate* d, dosx_stream_t stream);" in header
-    assert NAME in _l.EXPORTS and hasattr(lib, NAME)
-    assert f"thunk_{NAME}(" in thunks
     ni, nf = C.c_int(0), C.c_int(0)
     assert lib.dosx_replay_op(NAME.encode(), C.byref(ni), C.byref(nf)) >= 0 and (ni.value, nf.value) == (2, 0)
-    assert getattr(lib, NAME).argtypes == _l._SIGS[NAME] == _l._SIGS["dosx_collate_padded"]
+    assert getattr(lib, NAME).argtypes == lib.dosx_collate_padded.argtypes == [C.POINTER(_l.Collate), C.c_void_p]
     # the descriptor is the fp32 entry's: its layout has not moved
     assert C.sizeof(_l.Collate) == 10 * 4 + 32 * 8 + 2 * 4 + 6 * 8 and _l.Collate.x_all.offset == 40 + 11 * 8
 

@@ -1,44 +1,15 @@
-"""Per-crystal keys of the fp32 trainer, the parts a machine without a GPU can check: the ctypes mirror of DosxFfnBwd against the
-C layout (att_key_ptr last), Trainer(per_crystal_keys=...) as an interface, and that model.set_per_crystal_keys stays the float64
-program's switch."""
-import ctypes as C
-import os
-import re
-import subprocess
-
+"""Per-crystal keys of the fp32 trainer, the parts a machine without a GPU can check: DosxFfnBwd ends in att_key_ptr (its C
+layout and field order are checked against the header in tests/test_lib_abi.py), Trainer(per_crystal_keys=...) as an interface,
+and that model.set_per_crystal_keys stays the float64 program's switch."""
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "dosx.h")
 
-
-def test_ffn_bwd_mirror_has_the_c_layout_with_att_key_ptr_last(tmp_path):
+def test_ffn_bwd_mirror_has_the_c_layout_with_att_key_ptr_last():
     from dostransformer_amd import _lib
     names = [n for n, _ in _lib.FfnBwd._fields_]
     assert names[-1] == "att_key_ptr"
-    # the C struct's own field order, from the header text
-    body = re.search(r"typedef struct DosxFfnBwd \{(.*?)\} DosxFfnBwd;", open(HEADER).read(), re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    c_names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        for part in decl.split(","):
-            c_names.append(re.search(r"(\w+)\s*$", part.strip()).group(1))
-    assert c_names == names
-    src = tmp_path / "layout.c"
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "dosx.h"', "int main(void) {",
-             '  printf("%zu\\n", sizeof(DosxFfnBwd));']
-    lines += [f'  printf("%zu\\n", offsetof(DosxFfnBwd, {n}));' for n in names]
-    lines += ["  return 0;", "}"]
-    src.write_text("\n".join(lines))
-    exe = tmp_path / "layout"
-    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)   # (as tests/test_lib_abi.py)
-    out = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[0] == C.sizeof(_lib.FfnBwd)
-    assert out[1:] == [getattr(_lib.FfnBwd, n).offset for n in names]
+    assert max(getattr(_lib.FfnBwd, n).offset for n in names) == _lib.FfnBwd.att_key_ptr.offset
 
 
 def _cpu_model():

@@ -1,4 +1,4 @@
-"""Shared helpers for the tests: golden-fixture loading."""
+"""Shared helpers for the tests: golden-fixture loading, and the binding module with its library in place."""
 import os
 
 import numpy as np
@@ -7,6 +7,15 @@ import torch
 from dostransformer_amd.batch import CrystalBatch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def dosx_lib():
+    """dostransformer_amd._lib with libdosx.so in place (built first when it is missing)."""
+    from dostransformer_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+    return _lib
 
 
 def load(name):
