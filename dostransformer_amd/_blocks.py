@@ -186,7 +186,7 @@ class NodeModel(nn.Module):
             dcat = Fn.mlp_ln_bwd(P, G, "node_mlp_2", c, grads[0], sink)                 # [N, 2H]
             de = ops.alloc(dcat.device, m.num_edges, H)
             ops.edge_grad_combine(None, dcat.data_ptr() + 4 * H, 2 * H, m.dst, m.inv_deg if mean else None, de, m.num_edges, H)
-            sink._keep.append(dcat)
+            sink.keep(dcat)
             if m.edge_perm is not None:
                 out = torch.empty_like(de)
                 out[m.edge_perm] = de
@@ -248,7 +248,7 @@ class Processor(nn.Module):
             dx = ops.alloc(dev, N, H)
             ops.gather_bwd(dcat_e, dcat_n.data_ptr(), 2 * H, None, m.rowptr_dst, m.rowptr_src, m.perm_src, None, dx, None,
                            N, E, H)
-            sink._keep.extend([dcat_n, dcat_e])
+            sink.keep(dcat_n, dcat_e)
             de = dcat_e[:, 2 * H:].contiguous()
             if m.edge_perm is not None:
                 out = torch.empty_like(de)
@@ -306,7 +306,7 @@ class Decoder(nn.Module):
             ops.gemm(B, K, [seg(dy)], P["mlp.0.weight"], dcat, w_layout=1)
             dx = ops.alloc(dev, N, H)
             ops.graph_pool_bwd(dcat.data_ptr() + 4 * (K - H), K, ngraph, dx, N, H, False)
-            sink._keep.append(dcat)
+            sink.keep(dcat)
             return [dx] + ([dcat[:, :K - H].contiguous()] if K > H else [])
 
         ins = [x] + ([glob] if glob is not None else [])

@@ -9,7 +9,9 @@ of ``2B`` "crystals" (branch-major inside the batch axis: bq = branch*B + b).
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence, Tuple
+import contextlib
+import enum
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -18,9 +20,164 @@ from ._lib import Attn, Seg, from_environ
 from ._lib import load as _lib_load
 from .batch import GraphMeta
 from .ops import (ACT_LEAKY, ACT_RELU, EPI_LN, EPI_PRELU_BWD, EPI_PRELU_LN_BWD, EPI_PRELU_LN_BWD_SEG, EPI_RELU_MASK, EPI_ROWLN_BWD, EPI_SEGSUM,
-                  PRO_LN_PRELU, PRO_PRELU, PRO_ROWLN, GradSink, rowmap, seg)
+                  PRO_LN_PRELU, PRO_PRELU, PRO_ROWLN, AttBwd, AttFwd, GradSink, Head, rowmap, seg)
 
 Params = Dict[str, torch.Tensor]
+
+
+# ------------------------------------------------------------------------------------------------
+# What a forward pass saves for its backward pass.  Plain records: the backward reads them by name.
+# ------------------------------------------------------------------------------------------------
+class MlpPreluCtx(NamedTuple):
+    """mlp_prelu_fwd: the input segments, the first Linear's output, rows, hidden."""
+    a: "SegList"
+    z: torch.Tensor
+    M: int
+    H: int
+
+
+class MlpLnCtx(NamedTuple):
+    """mlp_ln_fwd: the input segments, the normalised first Linear's output and its statistics, rows, hidden."""
+    a: "SegList"
+    xhat: torch.Tensor
+    rstd: torch.Tensor
+    M: int
+    H: int
+
+
+class GnnLayerCtx(NamedTuple):
+    """One message-passing layer of gnn_fwd: the contexts of its EdgeModel and its NodeModel."""
+    edge: MlpLnCtx
+    node: MlpLnCtx
+
+
+class TrunkCtx(NamedTuple):
+    """gnn_trunk_fwd: node / edge / global (eDOS; else None) encoder contexts, the layers' contexts, the node encoder's key."""
+    node: MlpPreluCtx
+    edge: MlpPreluCtx
+    glob: Optional[MlpPreluCtx]
+    layers: List[GnnLayerCtx]
+    node_key: str
+
+
+class FinalLN(NamedTuple):
+    """An encoder's final LayerNorm: normalised rows [rows, H] and their 1 / std [rows]."""
+    xhat: torch.Tensor
+    rstd: torch.Tensor
+
+
+class EncoderLayer(NamedTuple):
+    """One layer of encoder_fwd.  x: the layer's query input (rows at s * qs + b * qb); x1 / st1: the attention half's output and
+    its LayerNorm-1 statistics; h: relu(fc1) (dropped, under relu dropout); mask: the attention dropout mask or None;
+    fdrop_masks: (res1, relu, res2) masks when the layer ran on the relu / res dropout path, else None; ln1: LN1(x1) as a plain
+    operand when the attention kernel left it behind (unfused feed-forward half) - kept here because the tail rows read it on
+    the side stream."""
+    x: torch.Tensor
+    qs: int
+    qb: int
+    x1: torch.Tensor
+    probs: torch.Tensor
+    qstats: torch.Tensor
+    st1: torch.Tensor
+    h: torch.Tensor
+    mask: Optional[torch.Tensor]
+    fdrop_masks: Optional[tuple]
+    ln1: Optional[torch.Tensor]
+
+
+class EncoderCtx(NamedTuple):
+    layers: List[EncoderLayer]
+    fin: Optional[FinalLN]
+    Sq: int
+    Bq: int
+    Nk: int
+    Bk: int
+    H: int
+    T: int
+    kvhat: torch.Tensor
+    key_ptr: Optional[torch.Tensor]
+
+
+class EncoderKVLayer(NamedTuple):
+    """One layer of encoder_kv_fwd: LayerNorm 0 of queries / keys / values (output, normalised rows, 1 / std each), softmax weights,
+    attention dropout mask, the attention half's output + statistics, relu(fc1), the (res1, relu, res2) masks (None each)."""
+    q: torch.Tensor
+    qh: torch.Tensor
+    qr: torch.Tensor
+    k: torch.Tensor
+    kh: torch.Tensor
+    kr: torch.Tensor
+    v: torch.Tensor
+    vh: torch.Tensor
+    vr: torch.Tensor
+    probs: torch.Tensor
+    amask: Optional[torch.Tensor]
+    x1: torch.Tensor
+    st1: torch.Tensor
+    h: torch.Tensor
+    fdrop_masks: tuple
+
+
+class EncoderKVCtx(NamedTuple):
+    layers: List[EncoderKVLayer]
+    fin: Optional[FinalLN]
+    Sq: int
+    Bq: int
+    Nk: int
+    Bk: int
+    H: int
+    T: int
+
+
+class ModelCtx(NamedTuple):
+    """dostransformer_fwd (hidden <= ops.ATTN_MAX_H)."""
+    trunk: TrunkCtx
+    kvhat: torch.Tensor
+    rstd_n: torch.Tensor
+    c1: EncoderCtx
+    dec_segs: "SegList"
+    sysidx: torch.Tensor
+    prow: torch.Tensor
+    dosin: torch.Tensor
+    a_g: "SegList"
+    a_s: "SegList"
+    kvs: torch.Tensor
+    rstd_s: torch.Tensor
+    c2: EncoderCtx
+    c3: EncoderCtx
+    xhat_f: torch.Tensor
+    rstd_f: torch.Tensor
+    xL: torch.Tensor
+
+
+class WideModelCtx(NamedTuple):
+    """_dostransformer_fwd_wide (hidden > ops.ATTN_MAX_H: the unfused building blocks)."""
+    trunk: TrunkCtx
+    c1: EncoderKVCtx
+    dec_segs: "SegList"
+    sysidx: torch.Tensor
+    sidx: torch.Tensor
+    prow: torch.Tensor
+    dosin: torch.Tensor
+    a_g: "SegList"
+    a_s: "SegList"
+    c2: EncoderKVCtx
+    c3: EncoderKVCtx
+    xhat_f: torch.Tensor
+    rstd_f: torch.Tensor
+    xL: torch.Tensor
+    x0: torch.Tensor
+    dense: torch.Tensor
+    hsrc: torch.Tensor
+
+
+class GraphNetCtx(NamedTuple):
+    """graphnetwork_fwd."""
+    trunk: TrunkCtx
+    dec_segs: "SegList"
+    a: "SegList"
+    hid: torch.Tensor
+    xL: torch.Tensor
 
 
 def _empty(dev, *shape):
@@ -106,6 +263,23 @@ _MID_HOOK_LATE_MAX_H = 128
 _FFN_TAIL_MAX = 2048
 
 
+@contextlib.contextmanager
+def forms(**overrides):
+    """Scope in which the named form switches / size limits above have other values (tests and A/B job scripts force a form at a
+    shape where production picks the other one): ``with forms(_FFN_MULTI=False): ...``.  The previous values come back however
+    the scope is left; a name that is not one of this module's upper-case policy globals raises."""
+    g = globals()
+    bad = [k for k in overrides if not (k.startswith("_") and k.isupper() and k in g)]
+    if bad:
+        raise AttributeError(f"not a form switch of {__name__}: {bad}")
+    saved = {k: g[k] for k in overrides}
+    g.update(overrides)
+    try:
+        yield
+    finally:
+        g.update(saved)
+
+
 def _wgrad_linear(sink: GradSink, G: Params, wkey: str, bkey: Optional[str], M: int, N: int, dy: Seg,
                   segs: Sequence[Seg], keep=(), tail: bool = False, dst: Optional[torch.Tensor] = None, **pro) -> None:
     """dW (and db) of y = A W^T + b as split slabs + reduce jobs (launched on the sink's side stream;
@@ -144,12 +318,12 @@ def mlp_prelu_fwd(P: Params, key: str, a: SegList, M: int, H: int, z: Optional[t
     y = _empty(dev, M, H)
     ops.gemm(M, H, [seg(z)], P[key + ".2.weight"], y, pro=PRO_PRELU, pro_alpha=P[key + ".1.weight"],
              bias=P[key + ".2.bias"])
-    return y, (a, z, M, H)
+    return y, MlpPreluCtx(a, z, M, H)
 
 
 def mlp_prelu_bwd(P: Params, G: Params, key: str, ctx, dy: torch.Tensor, sink: GradSink, dy_seg: Optional[Seg] = None,
                   tail: bool = False):
-    a, z, M, H = ctx
+    a, z, M, H = ctx.a, ctx.z, ctx.M, ctx.H
     dev = z.device
     alpha = P[key + ".1.weight"]
     dys = dy_seg if dy_seg is not None else seg(dy)
@@ -170,7 +344,7 @@ def mlp_prelu_bwd_pair(P: Params, G: Params, first, second, sink: GradSink, tail
     its own tile height in one grid), the same weight-gradient jobs as mlp_prelu_bwd twice."""
     descs, later = [], []
     for key, ctx, dy in (first, second):
-        a, z, M, H = ctx
+        a, z, M, H = ctx.a, ctx.z, ctx.M, ctx.H
         alpha = P[key + ".1.weight"]
         _wgrad_linear(sink, G, key + ".2.weight", key + ".2.bias", M, H, seg(dy), [seg(z)], keep=(dy,), tail=tail,
                       pro=PRO_PRELU, pro_alpha=alpha)
@@ -256,7 +430,7 @@ def mlp_ln_fwd(P: Params, key: str, a: SegList, M: int, H: int, res: Optional[to
         ops.mlp_ln_fwd(M, a.plain[0], a.plain[1] if len(a.plain) > 1 else None, P[key + ".0.weight"], P[key + ".0.bias"],
                        P[key + ".1.weight"], P[key + ".1.bias"], P[key + ".2.weight"], P[key + ".3.weight"],
                        P[key + ".3.bias"], res, xhat, rstd, y, w3=w3, nb3=2 if w3 is not None else 0, pq=pq3)
-        return y, (a, xhat, rstd, M, H)
+        return y, MlpLnCtx(a, xhat, rstd, M, H)
     fac = a.factor
     if fac is not None and _factor_edge(M, H, fac[2]):
         # Large edge sets (throughput-bound): the first Linear FACTORED - Linear(cat[x[row], x[col], e]) = (x Wa^T)[row] +
@@ -278,7 +452,7 @@ def mlp_ln_fwd(P: Params, key: str, a: SegList, M: int, H: int, res: Optional[to
             ops.edge_mlp_fwd(M, H, e, pq, m.src, m.dst, W1[:, 2 * H:], P[key + ".0.bias"], P[key + ".1.weight"], P[key + ".1.bias"],
                              P[key + ".2.weight"], P[key + ".3.weight"], P[key + ".3.bias"], xhat, rstd, e_out, tile, rowptr, scale, agg)
             a.keep.append(pq)
-            return None, (a, xhat, rstd, M, H)
+            return None, MlpLnCtx(a, xhat, rstd, M, H)
         if _factor_fused(m, H):
             # the E-row product of K = H with the two gathered node rows added in front of its LayerNorm statistics
             ops.gemm(M, 2 * H, [seg(e)], W1[:, 2 * H:], xhat, bias=P[key + ".0.bias"], epi=EPI_LN, aux_out=rstd,
@@ -308,18 +482,18 @@ def mlp_ln_fwd(P: Params, key: str, a: SegList, M: int, H: int, res: Optional[to
                             P[key + ".3.bias"], S, R, N_, M, 2 * H, H)
         ops.gemm(N_, H, [seg(S)], P[key + ".3.weight"], agg, res=R)
         a.aggsum = (S, rowptr, scale, N_, R)
-        return None, (a, xhat, rstd, M, H)
+        return None, MlpLnCtx(a, xhat, rstd, M, H)
     if segsum is not None:
         tile, rowptr, scale, agg, e_in, e_out = segsum
         ops.gemm(M, H, [seg(xhat)], P[key + ".3.weight"], e_out, pro=PRO_LN_PRELU, pro_gamma=P[key + ".1.weight"],
                  pro_beta=P[key + ".1.bias"], pro_alpha=P[key + ".2.weight"], bias=P[key + ".3.bias"],
                  res=e_in if e_out is not None else None, epi=EPI_SEGSUM, seg_tile=tile, seg_rowptr=rowptr, seg_scale=scale,
                  seg_agg=agg)
-        return None, (a, xhat, rstd, M, H)
+        return None, MlpLnCtx(a, xhat, rstd, M, H)
     y = _empty(dev, M, H)
     ops.gemm(M, H, [seg(xhat)], P[key + ".3.weight"], y, pro=PRO_LN_PRELU, pro_gamma=P[key + ".1.weight"],
              pro_beta=P[key + ".1.bias"], pro_alpha=P[key + ".2.weight"], bias=P[key + ".3.bias"], res=res)
-    return y, (a, xhat, rstd, M, H)
+    return y, MlpLnCtx(a, xhat, rstd, M, H)
 
 
 def mlp_ln_bwd(P: Params, G: Params, key: str, ctx, dy: torch.Tensor, sink: GradSink, res: Optional[torch.Tensor] = None,
@@ -327,7 +501,7 @@ def mlp_ln_bwd(P: Params, G: Params, key: str, ctx, dy: torch.Tensor, sink: Grad
     """Returns dL/d(concatenated input) [M, K_in] (+ ``res`` added to its columns [res_col0, K_in)).
     add_dy (one-launch path only, see mlp_ln_bwd_fused): + dy on the first H columns - the residual connection around the
     block, x' = x + MLP(cat[x, .]), differentiated in the same launch."""
-    a, xhat, rstd, M, H = ctx
+    a, xhat, rstd, M, H = ctx.a, ctx.xhat, ctx.rstd, ctx.M, ctx.H
     dev = xhat.device
     gam, bet, alpha = P[key + ".1.weight"], P[key + ".1.bias"], P[key + ".2.weight"]
     agg_first = a.aggsum
@@ -343,7 +517,7 @@ def mlp_ln_bwd(P: Params, G: Params, key: str, ctx, dy: torch.Tensor, sink: Grad
         sink.add(daggc, 0, G[key + ".3.bias"], N_, H, H)
         dnode = _empty(dev, N_, 2 * H)
         ops.gemm(N_, 2 * H, [seg(dy)], P[key + ".3.weight"], dnode, w_layout=1)
-        sink._keep.append(dnode)
+        sink.keep(dnode)
     else:
         _wgrad_linear(sink, G, key + ".3.weight", key + ".3.bias", M, H, seg(dy), [seg(xhat)], keep=(dy,), pro=PRO_LN_PRELU,
                       pro_gamma=gam, pro_beta=bet, pro_alpha=alpha)
@@ -376,7 +550,7 @@ def mlp_ln_bwd(P: Params, G: Params, key: str, ctx, dy: torch.Tensor, sink: Grad
         dact = _empty(dev, M, 2 * H)
         ops.gemm(M, 2 * H, [seg(dy)], P[key + ".3.weight"], dact, w_layout=1)
         ops.ln_prelu_bwd(dact, xhat, rstd, gam, bet, alpha, dz, part, M, 2 * H)
-        sink._keep.append(dact)
+        sink.keep(dact)
     elif seg_bwd:
         ops.gemm(M, 2 * H, [seg(dy)], P[key + ".3.weight"], dz, w_layout=1, epi=EPI_PRELU_LN_BWD_SEG, aux=xhat,
                  aux_stats=rstd, epi_gamma=gam, epi_beta=bet, epi_alpha=alpha, partials=part, partial_ld=pld,
@@ -407,7 +581,7 @@ def mlp_ln_bwd(P: Params, G: Params, key: str, ctx, dy: torch.Tensor, sink: Grad
         ops.segment_reduce_perm(dz, m.rowptr_src, m.perm_src, aggS, N_, E_, 2 * H)
     if aggD_epi is None:                           # (else: written by the dgrad GEMM's epilogue above)
         ops.segment_reduce(dz, m.rowptr_dst, None, aggD, None, None, N_, E_, 2 * H)
-    sink._keep.append(dz)
+    sink.keep(dz)
     src_job = None
     if key + ".0.weight" in G:
         Gw = G[key + ".0.weight"]                  # [2H, 3H]
@@ -440,7 +614,7 @@ def dev_of(P: Params):
 def node_chain_ok(cxn, N: int, H: int) -> bool:
     """Whether the NodeModel backward described by ``cxn`` (mlp_ln_fwd's context) will run as the column-split one-launch kernel
     on a contiguous [N, H] gradient - the form that takes ``pre``."""
-    a = cxn[0]
+    a = cxn.a
     return _mlp_ln_fused(a, N, H) and a.aggsum is None and ops.mlp_ln_cs(N, 2 * H, 2 * H, H)
 
 
@@ -456,7 +630,7 @@ def edge_mlp_bwd_one_launch(P: Params, G: Params, key: str, ctx, dagg: torch.Ten
     """dagg [N, H] (a strided view): gradient of the aggregate; de_next: gradient of e_{l+1} or None.  Returns what
     mlp_ln_bwd's factored branch returns: ("factored", dL/de_l [E,H], aggS, aggD, dz, src_job, early) - the source sums aggS are
     made by the caller's dosx_node_grad launch (gnn_bwd)."""
-    a, xhat, rstd, M, H = ctx
+    a, xhat, rstd, M, H = ctx.a, ctx.xhat, ctx.rstd, ctx.M, ctx.H
     x, e, m = a.factor
     dev = xhat.device
     N_ = m.num_nodes
@@ -474,7 +648,7 @@ def edge_mlp_bwd_one_launch(P: Params, G: Params, key: str, ctx, dagg: torch.Ten
     sink.add(part, 0, G[key + ".1.weight"], rows, pld, 2 * H)
     sink.add(part, 2 * H, G[key + ".1.bias"], rows, pld, 2 * H)
     sink.add(part, pld - 1, G[key + ".2.weight"], rows, pld, 1)
-    sink._keep.extend(t for t in (dz, dagg, de_next) if t is not None)
+    sink.keep(dz, dagg, de_next)
     src_job = None
     if key + ".0.weight" in G:
         Gw = G[key + ".0.weight"]
@@ -532,7 +706,7 @@ def gnn_fwd(P: Params, m: GraphMeta, x: torch.Tensor, e: torch.Tensor, L: int, m
             pq_ready = _empty(dev, N, 4 * H)
             pq_next = (P[f"stacked_processor.{l + 1}.edge_model.edge_mlp.0.weight"], pq_ready)
         x_new, cxn = mlp_ln_fwd(P, pre + ".node_model.node_mlp_2", a_n, N, H, res=x, pq_next=pq_next)
-        ctxs.append((cxe, cxn))
+        ctxs.append(GnnLayerCtx(cxe, cxn))
         x, e = x_new, e_new
     return x, ctxs
 
@@ -547,7 +721,7 @@ def gnn_bwd(P: Params, G: Params, m: GraphMeta, ctxs, dx: torch.Tensor, sink: Gr
     if dx_pre is not None:
         # round 6: the dense-key / pooled-decoder backward in front of the last layer's NodeModel backward runs INSIDE that column-split
         # launch (DosxMlpLnBwd.pre): 1.0940 -> 1.0726 ms per cfg2 step, three interleaved rounds (profiles/r06_ab_run2.log / r06_ab_run3.log)
-        if node_chain_ok(ctxs[L - 1][1], N, H) and dx.is_contiguous():
+        if node_chain_ok(ctxs[L - 1].node, N, H) and dx.is_contiguous():
             pending = dx_pre[0]
         else:
             dx_pre[1]()
@@ -564,22 +738,22 @@ def gnn_bwd(P: Params, G: Params, m: GraphMeta, ctxs, dx: torch.Tensor, sink: Gr
             hook(sink)
     for l in reversed(range(L)):
         pre = f"stacked_processor.{l}"
-        cxe, cxn = ctxs[l]
+        cxe, cxn = ctxs[l].edge, ctxs[l].node
         # factored edge layer + one-launch NodeModel backward: the residual path's dx rides on the first H columns of dcat_n
-        fold_dx = (cxe[0].factor is not None and _factor_edge(E, H, m) and _factor_fused(m, H)
-                   and mlp_ln_bwd_fused(cxn[0], N, H, dx))
+        fold_dx = (cxe.a.factor is not None and _factor_edge(E, H, m) and _factor_fused(m, H)
+                   and mlp_ln_bwd_fused(cxn.a, N, H, dx))
         dcat_n = mlp_ln_bwd(P, G, pre + ".node_model.node_mlp_2", cxn, dx, sink, add_dy=fold_dx, pre=pending)          # [N, 2H]
         pending = None
         hook1 = getattr(sink, "after_first_node", None)
         if hook1 is not None:
             sink.after_first_node = None
             hook1(sink)
-        if edge_bwd_one_launch_ok(cxe[0], E, H):
+        if edge_bwd_one_launch_ok(cxe.a, E, H):
             # gather + add of the message gradient, both input-gradient products with the PReLU / LayerNorm backward between
             # them, the destination-node sums: one launch on the node-aligned row tiles (csrc/edge_mlp.hip)
             dcat_e = edge_mlp_bwd_one_launch(P, G, pre + ".edge_model.edge_mlp", cxe, dcat_n[:, H:], de, scale, sink)
         else:
-            if cxe[0].aggsum is not None:
+            if cxe.a.aggsum is not None:
                 assert de is None                        # (the last layer: no edge-state gradient arrives)
                 dmsg = dcat_n[:, H:]                     # dL/d agg [N,H]: mlp_ln_bwd expands it per edge inside its row kernel
             else:
@@ -607,7 +781,7 @@ def gnn_bwd(P: Params, G: Params, m: GraphMeta, ctxs, dx: torch.Tensor, sink: Gr
                 #  cfg2 step, profiles/r06_ab_run3.log - three in-launch exchanges under a weight-gradient group cost more than the launch
                 #  they save; not built in)
                 ops.node_grad(N, H, dcat_e[4], m.rowptr_src, m.perm_src, aggD, W0, dcat_n[:, :H], None if fold_dx else dx, aggS, dx_old)
-                sink._keep.extend([dcat_n, dx, dcat_e[4], aggD])
+                sink.keep(dcat_n, dx, dcat_e[4], aggD)
                 if src_job is not None:
                     src_job()                          # (described BEHIND the launch that writes its operand; early: next group)
                 if early:
@@ -623,21 +797,21 @@ def gnn_bwd(P: Params, G: Params, m: GraphMeta, ctxs, dx: torch.Tensor, sink: Gr
                     t1 = _empty(dev, N, H)
                     ops.gemm(N, H, [seg(aggS), seg(aggD)], W0[:, :H], t1, w_layout=1, w_seg_off=H, res=dx)
                     ops.mask_residual(dcat_n[:, :H], None, t1, dx_old, None, N, H)
-                    sink._keep.append(t1)
-                sink._keep.extend([dcat_n, dx])
+                    sink.keep(t1)
+                sink.keep(dcat_n, dx)
             else:
                 t1, t2 = _empty(dev, N, H), _empty(dev, N, H)
                 ops.gemm(N, H, [seg(aggS)], W0[:, :H], t1, w_layout=1, res=dx)
                 ops.gemm(N, H, [seg(aggD)], W0[:, H:2 * H], t2, w_layout=1, res=t1)
                 ops.mask_residual(dcat_n[:, :H], None, t2, dx_old, None, N, H)
-                sink._keep.extend([dcat_n, t1, t2, dx])
+                sink.keep(dcat_n, t1, t2, dx)
             dx, de = dx_old, de_new
             if sink.side is not None and l == 1:
                 flush_side(l)
             continue
         ops.gather_bwd(dcat_e, dcat_n.data_ptr(), 2 * H, dx, m.rowptr_dst, m.rowptr_src, m.perm_src, None, dx_old,
                        None, N, E, H)
-        sink._keep.append(dcat_n)
+        sink.keep(dcat_n)
         dx, de = dx_old, dcat_e[:, 2 * H:]
         if sink.side is not None and l == 1:
             # the weight gradients of the layers finished so far go to the side stream NOW, underneath the first layer's
@@ -667,13 +841,53 @@ def head_fused_fwd(H: int, T: int) -> bool:
     return bool(ops.ffn_supported(H) and _FUSED_HEAD_FWD and T > 0)
 
 
+class AttForm(enum.Enum):
+    """Where the attention half of an encoder layer's forward runs (attention_form_fwd)."""
+    STANDALONE = "stand-alone"              # dosx_attention_fwd, then the feed-forward half
+    ROWS_IN_FFN = "rows-in-ffn"             # per query row in the prologue of dosx_ffn_fwd (DosxFfn.att_*)
+    ALIGNED_IN_FFN = "aligned-in-ffn"       # ... on crystal-aligned tiles (DosxFfn.att_aligned)
+
+
+def attention_form_fwd(rows: int, Sq: int, Bq: int, Nk: int, H: int, fdrop) -> AttForm:
+    """The form encoder_fwd runs a layer's attention half in (rows = Sq * Bq; fdrop: relu / res dropout is on - the layer runs
+    unfused).  Host-only: the switches above and the library's support / tile-height functions."""
+    if fdrop is not None:
+        return AttForm.STANDALONE
+    # <= 16 keys per crystal (the cross attention over the atoms of a crystal): the attention half runs in the prologue of
+    # the feed-forward launch (DosxFfn.att_*) - one launch per layer; same saved tensors, the backward is unchanged
+    # ... while the feed-forward launch runs 16-row workgroups (<= 4096 rows: one pass of the row prologue, one launch
+    # 20.5 us against 6.9 + 16.4 us + a launch gap at M = 3264); with 32-row workgroups the prologue takes two passes and
+    # buys nothing (33.2 vs 33.1 us at M = 6528), at 200 k rows it loses to the MFMA attention kernel (828 vs 738 us):
+    # profiles/r04_kernel_microbench.log, `layer`
+    att_rows = _FUSED_ATT_FFN and rows <= _ATT_FFN_MAX_ROWS and ops.ffn_att_supported(H, Nk)
+    # ... and with CRYSTAL-ALIGNED tiles (round 5: a workgroup = consecutive query rows of ONE crystal, its <= 64 key rows
+    # staged in LDS once, scores and P.K on the MFMA): the 51-key self attention and the 32-row launches too, while that
+    # grid - Sq padded to the tile height per crystal - is one round of workgroups
+    if _FUSED_ATT_FFN and _ATT_ALIGNED and ops.ffn_supported(H) and ops.ffn_att_aligned_supported(H, Nk):
+        r_al = _lib_load().dosx_ffn_att_aligned_rows(int(Sq), int(Bq))      # (16 / 32: the library's own tile-height policy)
+        if Bq * ((Sq + r_al - 1) // r_al) <= _ATT_ALIGNED_MAX_WGS and not (att_rows and _ATT_ROWS_FIRST):
+            return AttForm.ALIGNED_IN_FFN
+    return AttForm.ROWS_IN_FFN if att_rows else AttForm.STANDALONE
+
+
+def attention_bwd_in_ffn(Sq: int, Bq: int, Nk: int, H: int, fdrop: bool) -> bool:
+    """Whether encoder_bwd runs a layer's attention backward inside its dosx_ffn_bwd launch (fdrop: the layer ran on the
+    relu / res dropout path, unfused).  Host-only, like attention_form_fwd."""
+    fused = ops.ffn_supported(H) and not fdrop
+    small = bool(_lib_load().dosx_attention_pkv_supported(int(Nk), int(H)))
+    # round 5: the attention half's backward INSIDE the feed-forward half's launch (crystal-aligned tiles, DosxFfnBwd.att_*):
+    # the layer's backward is one launch and dL/dx1 never reaches HBM - while that grid is one round of workgroups
+    return bool(fused and small and _FUSED_ATT_BWD and ops.ffn_att_bwd_supported(H, Nk, Sq, Bq)
+                and ops.ffn_att_bwd_partial_rows(Sq, Bq) <= _ATT_ALIGNED_MAX_WGS)
+
+
 def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int, qb: int, kvhat: torch.Tensor,
-                Nk: int, Bk: int, H: int, T: int, final_ln: bool = True, drop=None, head=None, fdrop=None, key_ptr=None):
+                Nk: int, Bk: int, H: int, T: int, final_ln: bool = True, drop=None, head: Optional[Head] = None, fdrop=None, key_ptr=None):
     """x: query rows (row (s,bq) at (s*qs + bq*qb)); kvhat: [Nk*Bk, H] normalised keys (stale across layers).
     drop: None or (p, seed_dev, stream_base): attention dropout in training mode (multihead_attention.py:70) - every
     layer draws its own [Bq,Sq,Nk] multiplier mask (ops.dropout_mask) that the backward re-uses.
-    head = (gamma, beta, w, b, xhat [rows,H], rstd [rows], dos [Bq,Sq]) (with final_ln False, head_fused_fwd(H, T)): the
-    model head - LayerNorm + H->1 output layer on the encoder's output - in the last layer's ffn_fwd epilogue; the
+    head = ops.Head(gamma, beta, xhat [rows,H], rstd [rows], w=, b=, dos= [Bq,Sq]) (with final_ln False, head_fused_fwd(H, T)):
+    the model head - LayerNorm + H->1 output layer on the encoder's output - in the last layer's ffn_fwd epilogue; the
     encoder output itself is then not materialised (None is returned for it).
     key_ptr [Bk + 1] int32 (DosxAttn.key_ptr; forward and encoder_bwd, with or without attention dropout): crystal bk attends over
     its first key_ptr[bk + 1] - key_ptr[bk] key rows only - the batch's graph_ptr makes a batched pass equal the reference's
@@ -689,6 +903,8 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
         fdrop = None
     assert fdrop is None or head is None
     stack = [] if _FFN_MULTI else None      # round 6: the stack's layers in one launch when every layer is row-local (see below)
+    form = attention_form_fwd(rows, Sq, Bq, Nk, H, fdrop)
+    att_fused, att_aligned = form is not AttForm.STANDALONE, form is AttForm.ALIGNED_IN_FFN
     for t in range(T):
         lp = f"{pre}.layers.{t}"
         g0, b0 = P[lp + ".layer_norms.0.weight"], P[lp + ".layer_norms.0.bias"]
@@ -739,24 +955,9 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
             ops.gemm(rows, H, [seg(h)], P[lp + ".fc2.weight"], y2, bias=P[lp + ".fc2.bias"])
             x2 = _empty(dev, rows, H)
             ops.mask_residual(y2, m3, x1, x2, None, rows, H)
-            lay.append((x, qs, qb, x1, probs, qstats, st1, h, mask, fm))
+            lay.append(EncoderLayer(x, qs, qb, x1, probs, qstats, st1, h, mask, fm, None))
             x, qs, qb = x2, Bq, 1
             continue
-        # <= 16 keys per crystal (the cross attention over the atoms of a crystal): the attention half runs in the prologue of
-        # the feed-forward launch (DosxFfn.att_*) - one launch per layer; same saved tensors, the backward is unchanged
-        # ... while the feed-forward launch runs 16-row workgroups (<= 4096 rows: one pass of the row prologue, one launch
-        # 20.5 us against 6.9 + 16.4 us + a launch gap at M = 3264); with 32-row workgroups the prologue takes two passes and
-        # buys nothing (33.2 vs 33.1 us at M = 6528), at 200 k rows it loses to the MFMA attention kernel (828 vs 738 us):
-        # profiles/r04_kernel_microbench.log, `layer`
-        att_fused = _FUSED_ATT_FFN and rows <= _ATT_FFN_MAX_ROWS and ops.ffn_att_supported(H, Nk)
-        # ... and with CRYSTAL-ALIGNED tiles (round 5: a workgroup = consecutive query rows of ONE crystal, its <= 64 key rows
-        # staged in LDS once, scores and P.K on the MFMA): the 51-key self attention and the 32-row launches too, while that
-        # grid - Sq padded to the tile height per crystal - is one round of workgroups
-        att_aligned = False
-        if _FUSED_ATT_FFN and _ATT_ALIGNED and fdrop is None and ops.ffn_supported(H) and ops.ffn_att_aligned_supported(H, Nk):
-            r_al = _lib_load().dosx_ffn_att_aligned_rows(int(Sq), int(Bq))      # (16 / 32: the library's own tile-height policy)
-            if Bq * ((Sq + r_al - 1) // r_al) <= _ATT_ALIGNED_MAX_WGS and not (att_fused and _ATT_ROWS_FIRST):
-                att_fused = att_aligned = True
         xln = None
         if not att_fused:
             if stack:                       # (this layer launches its attention on its own: what is pending goes first)
@@ -769,7 +970,6 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
                 xln = _empty(dev, rows, H)
                 a.ln1_gamma, a.ln1_beta = P[lp + ".layer_norms.1.weight"].data_ptr(), P[lp + ".layer_norms.1.bias"].data_ptr()
                 a.ln1_out = xln.data_ptr()
-                x1._dosx_ln1 = xln             # (eager mode: lives as long as the saved x1; the tail rows read it on the side stream)
             ops.attention_fwd(a)
         h = _empty(dev, rows, 4 * H)
         x2 = _empty(dev, rows, H)
@@ -778,17 +978,16 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
             # layer also applies the encoder's final LayerNorm in its row epilogue
             fin_args = None
             if final_ln and t == T - 1:
-                fin_fused = (_empty(dev, rows, H), _empty(dev, rows))
-                fin_args = (P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"]) + fin_fused
+                fin_fused = FinalLN(_empty(dev, rows, H), _empty(dev, rows))
+                fin_args = Head(P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"], fin_fused.xhat, fin_fused.rstd)
             elif head is not None and t == T - 1:
-                assert not final_ln and head_fused_fwd(H, T)
-                hg, hb, hw, hbias, hxh, hrs, hdos = head
-                fin_args = (hg, hb, hxh, hrs, hw, hbias, hdos, Sq, Bq)
+                assert not final_ln and head_fused_fwd(H, T) and head.w is not None
+                fin_args = head._replace(S=Sq, Bq=Bq)
                 x2 = None
             att_args = None
             if att_fused:
-                att_args = dict(kvhat=kvhat, gamma0=g0, beta0=b0, Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=qs, qb=qb, probs=probs,
-                                qstats=qstats, x1=x1, st1=st1, mask=mask, aligned=att_aligned, key_ptr=key_ptr)
+                att_args = AttFwd(kvhat=kvhat, gamma0=g0, beta0=b0, Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=qs, qb=qb, probs=probs,
+                                  qstats=qstats, x1=x1, st1=st1, mask=mask, aligned=att_aligned, key_ptr=key_ptr)
             ops.ffn_fwd(rows, H, x if att_fused else x1, None if att_fused else st1, P[lp + ".layer_norms.1.weight"],
                         P[lp + ".layer_norms.1.bias"], P[lp + ".fc1.weight"], P[lp + ".fc1.bias"], P[lp + ".fc2.weight"],
                         P[lp + ".fc2.bias"], h, x2, fin=fin_args, att=att_args, defer=stack if att_fused else None)
@@ -813,7 +1012,7 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
                 ops.concurrent(dev, lambda: ffn_rows(mt, rows), lambda: ffn_rows(0, mt))
             else:
                 ffn_rows(0, rows)
-        lay.append((x, qs, qb, x1, probs, qstats, st1, h, mask, None))
+        lay.append(EncoderLayer(x, qs, qb, x1, probs, qstats, st1, h, mask, None, xln))    # (xln: the tail rows read it on the side stream)
         x, qs, qb = x2, Bq, 1
     if stack:
         # every transformer layer attends over the ORIGINAL keys (transformer.py:72-73): with the attention half inside the launch a
@@ -827,9 +1026,9 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
         xhat = _empty(dev, rows, H)
         rstd = _empty(dev, rows)
         ops.layernorm(x, P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"], y, xhat, rstd, rows, H)
-        fin = (xhat, rstd)
+        fin = FinalLN(xhat, rstd)
         x = y
-    return x, (lay, fin, Sq, Bq, Nk, Bk, H, T, kvhat, key_ptr)
+    return x, EncoderCtx(lay, fin, Sq, Bq, Nk, Bk, H, T, kvhat, key_ptr)
 
 
 def _bf16x3_ok(rows: int, n: int, k: int) -> bool:
@@ -852,44 +1051,46 @@ def head_fused_bwd(H: int, T: int) -> bool:
     return bool(ops.ffn_supported(H) and _FUSED_FIN_BWD and T > 0)
 
 
-def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor], dkvhat: torch.Tensor, sink: GradSink,
-                dkv_fresh: bool = False, kv_needed_next: bool = False, head=None):
+def encoder_bwd(P: Params, G: Params, pre: str, ctx: EncoderCtx, dy: Optional[torch.Tensor], dkvhat: torch.Tensor, sink: GradSink,
+                dkv_fresh: bool = False, kv_needed_next: bool = False, head: Optional[Head] = None):
     """dy: grad of the encoder output (after the final LN if there is one).  Accumulates into dkvhat
     (``dkv_fresh``: dkvhat is uninitialised and every row of it is a key row — the first layer processed
     overwrites it, which saves the zero fill).
-    ``head = (gamma, beta, xhat, rstd, ddos [Bq,S], w, (G keys: ln weight, ln bias, out weight, out bias))`` with dy None
+    ``head = ops.Head(gamma, beta, xhat, rstd, w=, ddos= [Bq,S], keys=(G keys: ln weight, ln bias, out weight, out bias))`` with dy None
     (only when head_fused_bwd(H, T)): the encoder's output went through LN -> H->1 output layer (ops.ln_rowdot) and ddos is
     the gradient of that layer's output; their backward runs inside the last layer's ffn_bwd launch.
     Returns the gradient w.r.t. the (expanded [Sq*Bq, H]) query input."""
-    lay, fin, Sq, Bq, Nk, Bk, H, T, kvhat, key_ptr = ctx
+    fin, Sq, Bq, Nk, Bk, H, T, kvhat, key_ptr = ctx.fin, ctx.Sq, ctx.Bq, ctx.Nk, ctx.Bk, ctx.H, ctx.T, ctx.kvhat, ctx.key_ptr
     dev = kvhat.device
     rows = Sq * Bq
     r32 = _rows32(rows)
     dx = dy
     fused_all = ops.ffn_supported(H)
-    last_plain = T > 0 and lay[T - 1][9] is None            # (a layer on the relu / res dropout path runs unfused)
+    last_plain = T > 0 and ctx.layers[T - 1].fdrop_masks is None            # (a layer on the relu / res dropout path runs unfused)
     fused = fused_all and last_plain
     fin_fused = None        # the final LayerNorm's backward rides in the last layer's ffn_bwd launch (csrc/ffn.hip)
     fin_keys = (pre + ".layer_norm.weight", pre + ".layer_norm.bias")
     if head is not None:
         assert dy is None and fin is None and head_fused_bwd(H, T)
-        hg, hb, hx, hr, hd, hw, fin_keys = head
+        assert head.w is not None and head.ddos is not None
+        fin_keys = head.keys
         dx = _empty(dev, rows, H)
-        fin_fused = (hg, hx, hr, dx, hd, hw, hb, Sq, Bq)
+        fin_fused = head._replace(dy=dx, S=Sq, Bq=Bq)
     elif fin is not None and fused and _FUSED_FIN_BWD and T > 0 and dy.stride(1) == 1:
         dx = _empty(dev, rows, H)
-        fin_fused = (P[pre + ".layer_norm.weight"], fin[0], fin[1], dx)
+        fin_fused = Head(P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"], fin.xhat, fin.rstd, dy=dx)
     elif fin is not None:
-        xhat, rstd = fin
         part = sink.scratch(r32, 2 * H)
         dx = _empty(dev, rows, H)
-        ops.layernorm_bwd(dy, xhat, rstd, P[pre + ".layer_norm.weight"], dx, part, rows, H)
+        ops.layernorm_bwd(dy, fin.xhat, fin.rstd, P[pre + ".layer_norm.weight"], dx, part, rows, H)
         sink.add(part, 0, G[pre + ".layer_norm.weight"], r32, 2 * H, H)
         sink.add(part, H, G[pre + ".layer_norm.bias"], r32, 2 * H, H)
     nqt, nkt = (Sq + 31) // 32, (Nk + 31) // 32
     for t in reversed(range(T)):
         lp = f"{pre}.layers.{t}"
-        x_in, qs, qb, x1, probs, qstats, st1, h, mask, fm = lay[t]
+        lay = ctx.layers[t]
+        x_in, qs, qb, x1, st1, h = lay.x, lay.qs, lay.qb, lay.x1, lay.st1, lay.h
+        probs, qstats, mask, fm = lay.probs, lay.qstats, lay.mask, lay.fdrop_masks
         g1, b1 = P[lp + ".layer_norms.1.weight"], P[lp + ".layer_norms.1.bias"]
         g0, b0 = P[lp + ".layer_norms.0.weight"], P[lp + ".layer_norms.0.bias"]
         dx_res2 = dx                      # gradient of x2 (the residual path of the feed-forward half carries it unchanged)
@@ -904,10 +1105,7 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
         pld = 2 * H
         fused = fused_all and fm is None
         small = bool(_lib_load().dosx_attention_pkv_supported(int(Nk), int(H)))
-        # round 5: the attention half's backward INSIDE the feed-forward half's launch (crystal-aligned tiles, DosxFfnBwd.att_*):
-        # the layer's backward is one launch and dL/dx1 never reaches HBM - while that grid is one round of workgroups
-        att_in_ffn = (fused and small and _FUSED_ATT_BWD and ops.ffn_att_bwd_supported(H, Nk, Sq, Bq)
-                      and ops.ffn_att_bwd_partial_rows(Sq, Bq) <= _ATT_ALIGNED_MAX_WGS)
+        att_in_ffn = attention_bwd_in_ffn(Sq, Bq, Nk, H, fdrop=fm is not None)
         att_bwd_args = None
         if att_in_ffn:
             nqt_al = ops.ffn_att_bwd_partial_rows(Sq, Bq) // Bq                # query tiles per batch entry (16- or 32-row tiles)
@@ -915,10 +1113,10 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
             part_a = sink.scratch(npart_a, 2 * H)
             dxin_a = _empty(dev, rows, H)
             kvp_a = sink.scratch(Bq * nqt_al * Nk, H)
-            att_bwd_args = dict(x=x_in, kvhat=kvhat, gamma0=g0, beta0=b0, probs=probs, qstats=qstats, mask=mask, dxin=dxin_a,
-                                partials_q=part_a.data_ptr(), partials_kv=part_a.data_ptr() + 4 * Bq * nqt_al * 2 * H, dkv_part=kvp_a,
-                                dkv_cnt=ops.COUNTERS.take(dev, Bk), dkvhat=dkvhat, accumulate=0 if (dkv_fresh and t == T - 1) else 1,
-                                Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=qs, qb=qb, key_ptr=key_ptr)
+            att_bwd_args = AttBwd(x=x_in, kvhat=kvhat, gamma0=g0, beta0=b0, probs=probs, qstats=qstats, mask=mask, dxin=dxin_a,
+                                  partials_q=part_a.data_ptr(), partials_kv=part_a.data_ptr() + 4 * Bq * nqt_al * 2 * H, dkv_part=kvp_a,
+                                  dkv_cnt=ops.COUNTERS.take(dev, Bk), dkvhat=dkvhat, accumulate=0 if (dkv_fresh and t == T - 1) else 1,
+                                  Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=qs, qb=qb, key_ptr=key_ptr)
         if fused:           # both dgrad GEMMs + ReLU mask + LN1 backward + residual in one launch (csrc/ffn.hip)
             rgp = ops.ffn_att_bwd_partial_rows(Sq, Bq) if att_in_ffn else ops.ffn_bwd_partial_rows(rows)
             with_fin = fin_fused is not None and t == T - 1
@@ -957,7 +1155,7 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
         if att_in_ffn:          # (the attention half ran inside the ffn_bwd launch above)
             sink.add(part_a, 0, G[lp + ".layer_norms.0.weight"], npart_a, 2 * H, H)
             sink.add(part_a, H, G[lp + ".layer_norms.0.bias"], npart_a, 2 * H, H)
-            sink._keep.extend(t_ for t_ in (mask, x_in) if t_ is not None)
+            sink.keep(mask, x_in)
             dx = dxin_a
             continue
         npart = Bq * nqt + Bk * ((Nk + 15) // 16 if small else nkt)        # key-side partial rows: per 16 / 32 keys
@@ -994,7 +1192,7 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
             a1 = desc(0)
             a1.dkv_cnt = ops.COUNTERS.take(dev, Bk)
             ops.attention_bwd(a1)
-            sink._keep.extend(t_ for t_ in (mask,) if t_ is not None)
+            sink.keep(mask)
         else:
             # dq (feeds the next layer's backward) on the main stream; dk+dv (feeds only the key-gradient
             # consumers at the very end) on the side stream, in layer order so dkvhat accumulates in order
@@ -1006,13 +1204,13 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx, dy: Optional[torch.Tensor],
                 # bouncing main -> side -> main through two cross-queue events
                 sink.join()
                 ops.attention_bwd(a2)
-                sink._keep.extend(t_ for t_ in (dsc, mask) if t_ is not None)
+                sink.keep(dsc, mask)
             else:
                 sink.on_side(lambda a2=a2: ops.attention_bwd(a2), (dx1, dxin) + tuple(t_ for t_ in (dsc, mask) if t_ is not None))
         sink.add(part, 0, G[lp + ".layer_norms.0.weight"], npart, 2 * H, H)
         sink.add(part, H, G[lp + ".layer_norms.0.bias"], npart, 2 * H, H)
         if fm is not None:                 # + the residual path of the attention half
-            sink._keep.append(dout_att)
+            sink.keep(dout_att)
             dsum = _empty(dev, rows, H)
             ops.mask_residual(dxin, None, dx1, dsum, None, rows, H)
             dxin = dsum
@@ -1088,19 +1286,19 @@ def encoder_kv_fwd(P: Params, pre: str, x: torch.Tensor, xk: torch.Tensor, xv: t
         y2, x2 = _empty(dev, rows, H), _empty(dev, rows, H)
         ops.gemm(rows, H, [seg(h)], P[lp + ".fc2.weight"], y2, bias=P[lp + ".fc2.bias"])
         ops.mask_residual(y2, m3, x1, x2, None, rows, H)
-        lay.append((q, qh, qr, k, kh, kr, v, vh, vr, probs, amask, x1, st1, h, (m1, m2, m3)))
+        lay.append(EncoderKVLayer(q, qh, qr, k, kh, kr, v, vh, vr, probs, amask, x1, st1, h, (m1, m2, m3)))
         x = x2
     fin = None
     if final_ln:
         y, xhat, rstd = _empty(dev, rows, H), _empty(dev, rows, H), _empty(dev, rows)
         ops.layernorm(x, P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"], y, xhat, rstd, rows, H)
-        fin, x = (xhat, rstd), y
-    return x, (lay, fin, Sq, Bq, Nk, Bk, H, T)
+        fin, x = FinalLN(xhat, rstd), y
+    return x, EncoderKVCtx(lay, fin, Sq, Bq, Nk, Bk, H, T)
 
 
 def encoder_kv_bwd(P: Params, G: Params, pre: str, ctx, dy: torch.Tensor, sink: GradSink):
     """Returns (dx [Sq*Bq,H], dxk [Nk*Bk,H], dxv [Nk*Bk,H])."""
-    lay, fin, Sq, Bq, Nk, Bk, H, T = ctx
+    fin, Sq, Bq, Nk, Bk, H, T = ctx.fin, ctx.Sq, ctx.Bq, ctx.Nk, ctx.Bk, ctx.H, ctx.T
     dev = dy.device
     rows, krows = Sq * Bq, Nk * Bk
     r32, k32 = _rows32(rows), _rows32(krows)
@@ -1108,13 +1306,15 @@ def encoder_kv_bwd(P: Params, G: Params, pre: str, ctx, dy: torch.Tensor, sink: 
     if fin is not None:
         part = sink.scratch(r32, 2 * H)
         dx = _empty(dev, rows, H)
-        ops.layernorm_bwd(dy, fin[0], fin[1], P[pre + ".layer_norm.weight"], dx, part, rows, H)
+        ops.layernorm_bwd(dy, fin.xhat, fin.rstd, P[pre + ".layer_norm.weight"], dx, part, rows, H)
         sink.add(part, 0, G[pre + ".layer_norm.weight"], r32, 2 * H, H)
         sink.add(part, H, G[pre + ".layer_norm.bias"], r32, 2 * H, H)
     dxk = dxv = None
     for t in reversed(range(T)):
         lp = f"{pre}.layers.{t}"
-        q, qh, qr, k, kh, kr, v, vh, vr, probs, amask, x1, st1, h, (m1, m2, m3) = lay[t]
+        lay = ctx.layers[t]
+        q, qh, qr, k, kh, kr, v, vh, vr = lay.q, lay.qh, lay.qr, lay.k, lay.kh, lay.kr, lay.v, lay.vh, lay.vr
+        probs, amask, x1, st1, h, (m1, m2, m3) = lay.probs, lay.amask, lay.x1, lay.st1, lay.h, lay.fdrop_masks
         g0 = P[lp + ".layer_norms.0.weight"]
         g1, b1 = P[lp + ".layer_norms.1.weight"], P[lp + ".layer_norms.1.bias"]
         dx2 = dx
@@ -1167,7 +1367,7 @@ def encoder_kv_bwd(P: Params, G: Params, pre: str, ctx, dy: torch.Tensor, sink: 
             ops.mask_residual(dk_in, None, dxk, nk_, None, krows, H)
             ops.mask_residual(dv_in, None, dxv, nv_, None, krows, H)
             dxk, dxv = nk_, nv_
-        sink._keep.extend([datt, dv, dk, dq, dpd, ds, dxq, dk_in, dv_in, dx1, dyf])
+        sink.keep(datt, dv, dk, dq, dpd, ds, dxq, dk_in, dv_in, dx1, dyf)
     return dx, dxk, dxv
 
 
@@ -1228,7 +1428,7 @@ def _gnn_trunk_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta, node_key: str):
         z0, x0, pq0 = _empty(dev_of(P), N, H), _empty(dev_of(P), N, H), _empty(dev_of(P), N, 4 * H)
         ops.enc_cs_fwd(N, xin, P[node_key + ".0.weight"], P[node_key + ".0.bias"], P[node_key + ".1.weight"], P[node_key + ".2.weight"],
                        P[node_key + ".2.bias"], z0, x0, P["stacked_processor.0.edge_model.edge_mlp.0.weight"], pq0)
-        cn = (SegList([seg(xin)], [xin]), z0, N, H)
+        cn = MlpPreluCtx(SegList([seg(xin)], [xin]), z0, N, H)
     else:
         x0, cn = mlp_prelu_fwd(P, node_key, SegList([seg(xin)], [xin]), N, H)
     if cfg.kind == "phonon" and P["GN_encoder.edge_encoder.0.weight"].shape[1] == 4:
@@ -1240,7 +1440,7 @@ def _gnn_trunk_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta, node_key: str):
         if ops.edge_enc_supported(H):
             # round 6: features, both Linear layers and the PReLU between them in ONE launch (csrc/heads.hip: edge_enc_fwd_kernel)
             ea, z0, e0 = ops.edge_enc_fwd(vec, P[ek + ".0.weight"], P[ek + ".0.bias"], P[ek + ".1.weight"], P[ek + ".2.weight"], P[ek + ".2.bias"], 4.0)
-            ce = (SegList([seg(ea)], [ea]), z0, E, H)
+            ce = MlpPreluCtx(SegList([seg(ea)], [ea]), z0, E, H)
         else:
             ea, z0 = ops.edge_embed_sh1(vec, P[ek + ".0.weight"], P[ek + ".0.bias"], 4.0)
             e0, ce = mlp_prelu_fwd(P, ek, SegList([seg(ea)], [ea]), E, H, z=z0)
@@ -1253,7 +1453,7 @@ def _gnn_trunk_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta, node_key: str):
         u, cu = mlp_prelu_fwd(P, "GN_encoder.global_encoder", SegList([seg(glob)], [glob]), B, H)
 
     xL, cg = gnn_fwd(P, m, x0, e0, cfg.L, cfg.mean, H, pq0=pq0)
-    return xL, u, (cn, ce, cu, cg, node_key)
+    return xL, u, TrunkCtx(cn, ce, cu, cg, node_key)
 
 
 def gnn_trunk_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, dxL: torch.Tensor, du_seg: Optional[Seg],
@@ -1264,9 +1464,9 @@ def gnn_trunk_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, dxL: t
 
 def _gnn_trunk_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, dxL: torch.Tensor, du_seg: Optional[Seg],
                    sink: GradSink, dx_pre=None):
-    cn, ce, cu, cg, node_key = ctx
+    cn, ce, cu, cg, node_key = ctx.node, ctx.edge, ctx.glob, ctx.layers, ctx.node_key
     dx0, de0 = gnn_bwd(P, G, m, cg, dxL, sink, cfg.L, cfg.mean, cfg.H, dx_pre=dx_pre)
-    if de0 is not None and cn[3] == ce[3]:
+    if de0 is not None and cn.H == ce.H:
         mlp_prelu_bwd_pair(P, G, (node_key, cn, dx0), ("GN_encoder.edge_encoder", ce, de0), sink, tail=True)
         if cu is not None and du_seg is not None:
             mlp_prelu_bwd(P, G, "GN_encoder.global_encoder", cu, None, sink, dy_seg=du_seg, tail=True)
@@ -1311,7 +1511,7 @@ def decoder_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, segs: SegList
         dcat = decoder_dgrad(P, cfg, m, segs, dgraph)
     if dxL is not None:
         ops.graph_pool_bwd(dcat.data_ptr() + 4 * (K - H), K, m.node_graph, dxL, N, H, True, num_graphs=B)   # ghost nodes: zero
-    sink._keep.append(dcat)
+    sink.keep(dcat)
     return seg(dcat, width=H, col=0) if K == 2 * H else None
 
 
@@ -1391,13 +1591,14 @@ def dostransformer_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta, drop=None, per
     gf, bf = P["transformer_source.layer_norm.weight"], P["transformer_source.layer_norm.bias"]
     if head_fused_fwd(H, T):     # final LayerNorm + out_layer in the last ffn_fwd launch of the source encoder
         _, c3 = encoder_fwd(P, "transformer_source", hs, S, 2 * B, 2 * B, 1, kvhat, nmax, B, H, T, final_ln=False,
-                            drop=dr(128), head=(gf, bf, P["out_layer.weight"], P["out_layer.bias"], xhat_f, rstd_f, dos), key_ptr=kp)
+                            drop=dr(128), head=Head(gf, bf, xhat_f, rstd_f, w=P["out_layer.weight"], b=P["out_layer.bias"], dos=dos), key_ptr=kp)
     else:
         hsrc, c3 = encoder_fwd(P, "transformer_source", hs, S, 2 * B, 2 * B, 1, kvhat, nmax, B, H, T, final_ln=False,
                                drop=dr(128), key_ptr=kp)
         ops.ln_rowdot(hsrc, gf, bf, P["out_layer.weight"], P["out_layer.bias"], xhat_f, rstd_f, dos, S, 2 * B, H)
     a_g.keep.extend(t for t in (box.get("qg"), box.get("qs")) if t is not None)
-    ctx = (ctrunk, kvhat, rstd_n, c1, dec_segs, sysidx, prow, dosin, a_g, a_s, kvs, rstd_s, c2, c3, xhat_f, rstd_f, xL)
+    ctx = ModelCtx(trunk=ctrunk, kvhat=kvhat, rstd_n=rstd_n, c1=c1, dec_segs=dec_segs, sysidx=sysidx, prow=prow, dosin=dosin, a_g=a_g, a_s=a_s,
+                   kvs=kvs, rstd_s=rstd_s, c2=c2, c3=c3, xhat_f=xhat_f, rstd_f=rstd_f, xL=xL)
     return dos, xL, ctx
 
 
@@ -1405,9 +1606,11 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
                        dx_ext: Optional[torch.Tensor], sink: GradSink, mid_hook=None) -> None:
     """Backward; ddos [2B,S] (rows [0,B): d dos_global, [B,2B): d dos_system); dx_ext: optional
     gradient w.r.t. the returned node embeddings.  Writes every live parameter gradient into G."""
-    if ctx[0] == "wide":
+    if isinstance(ctx, WideModelCtx):
         return _dostransformer_bwd_wide(P, G, cfg, m, ctx, ddos, dx_ext, sink, mid_hook)
-    (ctrunk, kvhat, rstd_n, c1, dec_segs, sysidx, prow, dosin, a_g, a_s, kvs, rstd_s, c2, c3, xhat_f, rstd_f, xL) = ctx
+    ctrunk, kvhat, rstd_n, c1, c2, c3 = ctx.trunk, ctx.kvhat, ctx.rstd_n, ctx.c1, ctx.c2, ctx.c3
+    dec_segs, sysidx, prow, dosin, a_g, a_s = ctx.dec_segs, ctx.sysidx, ctx.prow, ctx.dosin, ctx.a_g, ctx.a_s
+    kvs, rstd_s, xhat_f, rstd_f = ctx.kvs, ctx.rstd_s, ctx.xhat_f, ctx.rstd_f
     H, S, B, N = cfg.H, cfg.S, m.num_graphs, m.num_nodes
     nmax = m.n_max
     dev = ddos.device
@@ -1418,8 +1621,8 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
     if head_fused_bwd(H, cfg.T) and ddos.is_contiguous():
         # output layer + final LayerNorm backward inside the source encoder's first ffn_bwd launch
         dx = None
-        head = (gf, bf, xhat_f, rstd_f, ddos, P["out_layer.weight"],
-                ("transformer_source.layer_norm.weight", "transformer_source.layer_norm.bias", "out_layer.weight", "out_layer.bias"))
+        head = Head(gf, bf, xhat_f, rstd_f, w=P["out_layer.weight"], ddos=ddos,
+                    keys=("transformer_source.layer_norm.weight", "transformer_source.layer_norm.bias", "out_layer.weight", "out_layer.bias"))
     else:
         pld = 3 * H + 1
         part = sink.scratch(r32, pld)
@@ -1526,7 +1729,7 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
         # (round 6: inside the last message-passing layer's NodeModel backward launch, when that runs column-split: gnn_bwd)
         dx_pre = (dict(kind="dense", dkv=dkv, kvhat=kvhat, rstd_nodes=rstd_n, dense_row=m.dense_row, dpool_ptr=dcat.data_ptr() + 4 * (Kd - H),
                        ld_dpool=Kd, node_graph=m.node_graph, num_graphs=B, ghost_row=nmax * B), dense_launch)
-        sink._keep.extend([dkv, dcat])
+        sink.keep(dkv, dcat)
     du_seg = decoder_bwd(P, G, cfg, m, dec_segs, dgraph, None, sink, dcat=dcat)
     if dx_ext is not None:
         dxL.add_(dx_ext)
@@ -1542,13 +1745,13 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
 # dense keys (dosx_dense_slots = to_dense_batch alone), plain GEMMs + row kernels for the 2H-wide LayerNorms of the GNN
 # blocks (mlp_ln_fwd / _bwd above).  One stream, no launch-saving tricks: a correctness path for rare shapes, pinned against
 # the oracle like every other path (tests/test_gpu_models.py).  Limit: hidden <= 512 (LayerNorm prologues of dosx_gemm).
-def _sum_rows(dev, terms, rows, H, keep):
+def _sum_rows(dev, terms, rows, H, sink: GradSink):
     """sum of equally shaped [rows, H] tensors (ops.mask_residual: out = res + a)"""
     acc = terms[0]
     for t in terms[1:]:
         out = _empty(dev, rows, H)
         ops.mask_residual(t, None, acc, out, None, rows, H)
-        keep.extend([t, acc])
+        sink.keep(t, acc)
         acc = out
     return acc
 
@@ -1584,19 +1787,20 @@ def _dostransformer_fwd_wide(P: Params, cfg: ModelCfg, g, m: GraphMeta, dr):
     xhat_f, rstd_f, dos = _empty(dev, S * 2 * B, H), _empty(dev, S * 2 * B), _empty(dev, 2 * B, S)
     ops.ln_rowdot(hsrc, P["transformer_source.layer_norm.weight"], P["transformer_source.layer_norm.bias"],
                   P["out_layer.weight"], P["out_layer.bias"], xhat_f, rstd_f, dos, S, 2 * B, H)
-    ctx = ("wide", ctrunk, c1, dec_segs, sysidx, sidx, prow, dosin, a_g, a_s, c2, c3, xhat_f, rstd_f, xL, x0, dense, hsrc)
+    ctx = WideModelCtx(trunk=ctrunk, c1=c1, dec_segs=dec_segs, sysidx=sysidx, sidx=sidx, prow=prow, dosin=dosin, a_g=a_g, a_s=a_s, c2=c2, c3=c3,
+                       xhat_f=xhat_f, rstd_f=rstd_f, xL=xL, x0=x0, dense=dense, hsrc=hsrc)
     return dos, xL, ctx
 
 
 def _dostransformer_bwd_wide(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, ddos: torch.Tensor,
                              dx_ext: Optional[torch.Tensor], sink: GradSink, mid_hook=None) -> None:
-    (_, ctrunk, c1, dec_segs, sysidx, sidx, prow, dosin, a_g, a_s, c2, c3, xhat_f, rstd_f, xL, x0, dense, hsrc) = ctx
+    ctrunk, c1, c2, c3, dec_segs, sysidx, prow = ctx.trunk, ctx.c1, ctx.c2, ctx.c3, ctx.dec_segs, ctx.sysidx, ctx.prow
+    dosin, a_g, a_s, xhat_f, rstd_f = ctx.dosin, ctx.a_g, ctx.a_s, ctx.xhat_f, ctx.rstd_f
     H, S, B, N = cfg.H, cfg.S, m.num_graphs, m.num_nodes
     nmax = m.n_max
     dev = ddos.device
     rows2 = S * 2 * B
     r32 = _rows32(rows2)
-    keep = sink._keep
     pld = 3 * H + 1
     part = sink.scratch(r32, pld)
     dx = _empty(dev, rows2, H)
@@ -1608,10 +1812,10 @@ def _dostransformer_bwd_wide(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, 
     sink.add(part, 3 * H, G["out_layer.bias"], r32, pld, 1)
     dhs, dk3, dv3 = encoder_kv_bwd(P, G, "transformer_source", c3, dx, sink)
     ddosin, dk2, dv2 = encoder_kv_bwd(P, G, "transformer_self", c2, dhs, sink)
-    dsum = _sum_rows(dev, [ddosin, dk2, dv2], rows2, H, keep)        # dosin is query, key and value of the self encoder
+    dsum = _sum_rows(dev, [ddosin, dk2, dv2], rows2, H, sink)        # dosin is query, key and value of the self encoder
     dpre = _empty(dev, rows2, H)
     ops.act_bwd(dsum, dosin, 0.01, dpre)                             # F.leaky_relu behind fc / fc_prompt
-    keep.extend([dx, dhs, dsum])
+    sink.keep(dx, dhs, dsum)
     map0, map1 = rowmap(d=B, m=2 * B, c=1, off=0), rowmap(d=B, m=2 * B, c=1, off=B)
     _wgrad_linear(sink, G, "fc.weight", "fc.bias", S * B, H, seg(dpre, rmap=map0), a_g.segs, keep=(dpre,))
     _wgrad_linear(sink, G, "fc_prompt.weight", "fc_prompt.bias", S * B, H, seg(dpre, rmap=map1), a_s.segs, keep=(dpre,))
@@ -1628,16 +1832,16 @@ def _dostransformer_bwd_wide(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, 
     ops.gemm(B, H, [seg(R[B:])], Wfp[:, H:2 * H], dgraph, w_layout=1, res=dgraph)
     ops.gemm(B, hp, [seg(R[B:])], Wfp[:, 2 * H:], dprow, w_layout=1)
     ops.embed_rows_bwd(dprow.data_ptr(), hp, sysidx, G[cfg.prompt_key], B, G[cfg.prompt_key].shape[0], hp)
-    keep.extend([R, dprow])
+    sink.keep(R, dprow)
     dX1, dk1, dv1 = encoder_kv_bwd(P, G, "transformer", c1, dE1, sink)
     ops.reduce_rows(dX1.data_ptr(), H, G["embeddings.weight"].data_ptr(), H, S, B, B, 1, H)       # sum over the batch
-    keep.extend([dX1, dE1])
+    sink.keep(dX1, dE1)
     if mid_hook is not None:
         mid_hook(sink)
-    ddense = _sum_rows(dev, [dk1, dv1, dk3, dv3], nmax * B, H, keep)
+    ddense = _sum_rows(dev, [dk1, dv1, dk3, dv3], nmax * B, H, sink)
     dxL = _empty(dev, N, H)
     ops.dense_slots_bwd(ddense, m.dense_row, dxL, N, H, False, ghost_row=nmax * B)
-    keep.append(ddense)
+    sink.keep(ddense)
     du_seg = decoder_bwd(P, G, cfg, m, dec_segs, dgraph, dxL, sink)
     if dx_ext is not None:
         dxL.add_(dx_ext)
@@ -1659,12 +1863,12 @@ def graphnetwork_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta):
     ops.gemm(S * B, H, a.segs, P["out_layer.0.weight"], hid, bias=P["out_layer.0.bias"], act=ACT_LEAKY, act_slope=0.01)
     dos = _empty(dev, B, S)
     ops.rowdot(hid, P["out_layer.2.weight"], P["out_layer.2.bias"], dos, S, B, H)
-    return dos, xL, (ctrunk, dec_segs, a, hid, xL)
+    return dos, xL, GraphNetCtx(ctrunk, dec_segs, a, hid, xL)
 
 
 def graphnetwork_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, ddos: torch.Tensor,
                      dx_ext: Optional[torch.Tensor], sink: GradSink) -> None:
-    ctrunk, dec_segs, a, hid, xL = ctx
+    ctrunk, dec_segs, a, hid = ctx.trunk, ctx.dec_segs, ctx.a, ctx.hid
     H, S, B, N = cfg.H, cfg.S, m.num_graphs, m.num_nodes
     dev = ddos.device
     rows = S * B

@@ -23,7 +23,7 @@ grouped.  (Graphnetwork_phonon's program is not: its sum-pool backward still ind
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
@@ -213,6 +213,57 @@ def _dpool_rows(dev, B: int, H: int, padded: bool) -> torch.Tensor:
     return dpool
 
 
+class _EncoderLayer64(NamedTuple):
+    """One layer of _encoder_fwd: LayerNorm 0 of the queries (normalised rows, 1 / std, output), the attention dropout mask or
+    None, the softmax weights, LayerNorm 1 of the attention half's output (normalised rows, 1 / std, output), relu(fc1)."""
+    xhq: torch.Tensor
+    rsq: torch.Tensor
+    q: torch.Tensor
+    mask: Optional[torch.Tensor]
+    probs: torch.Tensor
+    xh1: torch.Tensor
+    rs1: torch.Tensor
+    y1: torch.Tensor
+    h: torch.Tensor
+
+
+class _EncoderCtx64(NamedTuple):
+    pre: str
+    layers: List[_EncoderLayer64]
+    xhf: torch.Tensor                  # the final LayerNorm's normalised rows ...
+    rsf: torch.Tensor                  # ... and 1 / std
+    Sq: int
+    Bq: int
+    Nk: int
+    Bk: int
+    kvhat: torch.Tensor
+    key_ptr: Optional[torch.Tensor]
+
+
+class _ModelCtx64(NamedTuple):
+    """dostransformer_phonon_fwd.  padded: the batch is ghost-padded (_dpool_rows)."""
+    trunk: tuple
+    kv_n: torch.Tensor
+    rstd_n: torch.Tensor
+    c1: _EncoderCtx64
+    pool: torch.Tensor
+    graph: torch.Tensor
+    prow: torch.Tensor
+    sysidx: torch.Tensor
+    seg_g: list
+    seg_s: list
+    pre: torch.Tensor
+    dosin: torch.Tensor
+    ptr_s: torch.Tensor
+    kv_s: torch.Tensor
+    rstd_s: torch.Tensor
+    c2: _EncoderCtx64
+    c3: _EncoderCtx64
+    hsrc: torch.Tensor
+    E1: torch.Tensor
+    padded: bool
+
+
 def _encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, kvhat: torch.Tensor, Nk: int, Bk: int, T: int, drop,
                  key_ptr: Optional[torch.Tensor] = None):
     """TransformerEncoder (layers/transformer.py:46-79,120-157) on the query rows x [Bq*Sq, H] (row bq * Sq + s) over the
@@ -236,16 +287,16 @@ def _encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, kvhat: 
         h = gemm64(rows, 4 * H, [seg64(y1)], P[lp + ".fc1.weight"], alloc64(x.device, rows, 4 * H), bias=P[lp + ".fc1.bias"],
                    act=ACT64_RELU)
         x2 = gemm64(rows, H, [seg64(h)], P[lp + ".fc2.weight"], alloc64(x.device, rows, H), bias=P[lp + ".fc2.bias"], res=x1)
-        lay.append((xhq, rsq, q, mask, probs, xh1, rs1, y1, h))
+        lay.append(_EncoderLayer64(xhq, rsq, q, mask, probs, xh1, rs1, y1, h))
         x = x2
     xhf, rsf, y = layernorm64(x, P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"])
-    return y, (pre, lay, xhf, rsf, Sq, Bq, Nk, Bk, kvhat, key_ptr)
+    return y, _EncoderCtx64(pre, lay, xhf, rsf, Sq, Bq, Nk, Bk, kvhat, key_ptr)
 
 
 def _encoder_bwd(P: Params, G: Params, ctx, dy: torch.Tensor, dkvhat: torch.Tensor, kacc: bool) -> torch.Tensor:
     """Gradient of the query rows; every layer's key + value gradient (times gamma0) goes into dkvhat, the first one written
     unless kacc (accumulate) - the key rows of the dense batch are read by two encoders."""
-    pre, lay, xhf, rsf, Sq, Bq, Nk, Bk, kvhat, key_ptr = ctx
+    pre, Sq, Bq, Nk, Bk, kvhat, key_ptr = ctx.pre, ctx.Sq, ctx.Bq, ctx.Nk, ctx.Bk, ctx.kvhat, ctx.key_ptr
     rows, H = dy.shape
     dev = dy.device
 
@@ -253,11 +304,12 @@ def _encoder_bwd(P: Params, G: Params, ctx, dy: torch.Tensor, dkvhat: torch.Tens
         colsum64(part[:, :H], G[key + ".weight"], acc)
         colsum64(part[:, H:2 * H], G[key + ".bias"], acc)
 
-    dx, part = layernorm_bwd64(dy, xhf, rsf, P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"])
+    dx, part = layernorm_bwd64(dy, ctx.xhf, ctx.rsf, P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"])
     ln_grads(pre + ".layer_norm", part)
-    for t in reversed(range(len(lay))):
+    for t in reversed(range(len(ctx.layers))):
         lp = f"{pre}.layers.{t}"
-        xhq, rsq, q, mask, probs, xh1, rs1, y1, h = lay[t]
+        lay = ctx.layers[t]
+        q, mask, probs, y1, h = lay.q, lay.mask, lay.probs, lay.y1, lay.h
         g0, b0 = P[lp + ".layer_norms.0.weight"], P[lp + ".layer_norms.0.bias"]
         # x2 = x1 + fc2(relu(fc1(LN1(x1))))
         _linear_grads(G, lp + ".fc2", rows, dx, [seg64(h)])
@@ -265,13 +317,13 @@ def _encoder_bwd(P: Params, G: Params, ctx, dy: torch.Tensor, dkvhat: torch.Tens
         dhz, _ = act_bwd64(dh, h, ACT64_RELU)                    # relu(z) > 0 exactly where z > 0
         _linear_grads(G, lp + ".fc1", rows, dhz, [seg64(y1)])
         dy1 = gemm64(rows, H, [seg64(dhz)], P[lp + ".fc1.weight"], alloc64(dev, rows, H), w_layout=1)
-        dz1, part1 = layernorm_bwd64(dy1, xh1, rs1, P[lp + ".layer_norms.1.weight"], P[lp + ".layer_norms.1.bias"])
+        dz1, part1 = layernorm_bwd64(dy1, lay.xh1, lay.rs1, P[lp + ".layer_norms.1.weight"], P[lp + ".layer_norms.1.bias"])
         ln_grads(lp + ".layer_norms.1", part1)
         dx1 = rows_add64(rows, dx, dz1)
         # x1 = x + attention(LN0(x), LN0(keys))
         dq, partk, _ = attention_bwd64(dx1, q, kvhat, g0, b0, probs, Sq, Bq, Nk, Bk, dkvhat, mask, SOFTMAX64, kacc, key_ptr)
         kacc = True
-        dzq, partq = layernorm_bwd64(dq, xhq, rsq, g0, b0)
+        dzq, partq = layernorm_bwd64(dq, lay.xhq, lay.rsq, g0, b0)
         ln_grads(lp + ".layer_norms.0", partq)
         ln_grads(lp + ".layer_norms.0", partk, True)
         dx = rows_add64(rows, dx1, dzq)
@@ -312,16 +364,17 @@ def dostransformer_phonon_fwd(P: Params, cfg, g, m: GraphMeta, drop=None, per_cr
     hs, c2 = _encoder_fwd(P, "transformer_self", dosin, S, 2 * B, kv_s, S, 2 * B, T, dr(64))
     hsrc, c3 = _encoder_fwd(P, "transformer_source", hs, S, 2 * B, kv_n, nmax, B, T, dr(128), kp)
     dos = gemm64(2 * BS, 1, [seg64(hsrc)], P["out_layer.weight"], alloc64(dev, 2 * BS, 1), bias=P["out_layer.bias"])
-    ctx = (ctrunk, kv_n, rstd_n, c1, pool, graph, prow, sysidx, seg_g, seg_s, pre, dosin, ptr_s, kv_s, rstd_s, c2, c3, hsrc, E1,
-           _is_padded(g))
+    ctx = _ModelCtx64(trunk=ctrunk, kv_n=kv_n, rstd_n=rstd_n, c1=c1, pool=pool, graph=graph, prow=prow, sysidx=sysidx, seg_g=seg_g,
+                      seg_s=seg_s, pre=pre, dosin=dosin, ptr_s=ptr_s, kv_s=kv_s, rstd_s=rstd_s, c2=c2, c3=c3, hsrc=hsrc, E1=E1,
+                      padded=_is_padded(g))
     return dos.view(2 * B, S), xL, ctx
 
 
 def dostransformer_phonon_bwd(P: Params, G: Params, cfg, m: GraphMeta, ctx, ddos: torch.Tensor,
                               dx_ext: Optional[torch.Tensor]) -> None:
     """Writes the gradient of every live parameter into G from ddos [2B, S] and the gradient of x_L (or None)."""
-    (ctrunk, kv_n, rstd_n, c1, pool, graph, prow, sysidx, seg_g, seg_s, pre, dosin, ptr_s, kv_s, rstd_s, c2, c3, hsrc,
-     E1, padded) = ctx
+    ctrunk, c1, c2, c3, kv_n, rstd_n, kv_s, rstd_s, ptr_s = ctx.trunk, ctx.c1, ctx.c2, ctx.c3, ctx.kv_n, ctx.rstd_n, ctx.kv_s, ctx.rstd_s, ctx.ptr_s
+    pool, sysidx, seg_g, seg_s, pre, dosin, hsrc, padded = ctx.pool, ctx.sysidx, ctx.seg_g, ctx.seg_s, ctx.pre, ctx.dosin, ctx.hsrc, ctx.padded
     H, S, B, N = cfg.H, cfg.S, m.num_graphs, m.num_nodes
     nmax = m.n_max
     BS = B * S

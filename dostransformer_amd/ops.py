@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -335,21 +335,9 @@ def _set_segs(dst, segs: Sequence[Seg]):
         dst[i] = s
 
 
-def gemm(M: int, N: int, segs: Sequence[Seg], w: torch.Tensor, out: torch.Tensor, *, w_layout: int = 0,
-         pro: int = PRO_NONE, pro_gamma=None, pro_beta=None, pro_alpha=None, pro_stats=None,
-         epi: int = EPI_BIAS_ACT, act: int = ACT_NONE, act_slope: float = 0.01, bias=None,
-         out_map: Optional[RowMap] = None, res=None, res_map: Optional[RowMap] = None,
-         stats_out=None, aux_out=None, aux=None, aux_stats=None, epi_gamma=None, epi_beta=None,
-         epi_alpha=None, partials=None, partial_ld: int = 0, res_col0: int = 0, seg_tile=None, seg_rowptr=None,
-         seg_scale=None, seg_agg=None, keep: Optional[list] = None, norm_out=None, norm_rstd=None, res_pre: bool = False,
-         add_p=None, add_ip=None, add_q=None, add_iq=None, w_seg_off: int = 0) -> None:
-    """out[M,N] = epilogue(prologue(A) @ B); see include/dosx.h:DosxGemm."""
-    g = _gemm_desc(M, N, segs, w, out, w_layout=w_layout, pro=pro, pro_gamma=pro_gamma, pro_beta=pro_beta, pro_alpha=pro_alpha,
-                   pro_stats=pro_stats, epi=epi, act=act, act_slope=act_slope, bias=bias, out_map=out_map, res=res, res_map=res_map,
-                   stats_out=stats_out, aux_out=aux_out, aux=aux, aux_stats=aux_stats, epi_gamma=epi_gamma, epi_beta=epi_beta,
-                   epi_alpha=epi_alpha, partials=partials, partial_ld=partial_ld, res_col0=res_col0, seg_tile=seg_tile,
-                   seg_rowptr=seg_rowptr, seg_scale=seg_scale, seg_agg=seg_agg, norm_out=norm_out, norm_rstd=norm_rstd, res_pre=res_pre,
-                   add_p=add_p, add_ip=add_ip, add_q=add_q, add_iq=add_iq, w_seg_off=w_seg_off)
+def gemm(M: int, N: int, segs: Sequence[Seg], w: torch.Tensor, out: torch.Tensor, **kw) -> None:
+    """out[M,N] = epilogue(prologue(A) @ B); the keywords are :func:`_gemm_desc`'s."""
+    g = _gemm_desc(M, N, segs, w, out, **kw)
     _call("dosx_gemm", C.byref(g), _stream(), w=lambda: _gemm_work(g))
 
 
@@ -373,6 +361,7 @@ def _gemm_desc(M: int, N: int, segs: Sequence[Seg], w: torch.Tensor, out: torch.
                epi_alpha=None, partials=None, partial_ld: int = 0, res_col0: int = 0, seg_tile=None, seg_rowptr=None,
                seg_scale=None, seg_agg=None, norm_out=None, norm_rstd=None, res_pre: bool = False,
                add_p=None, add_ip=None, add_q=None, add_iq=None, w_seg_off: int = 0) -> "Gemm":
+    """The descriptor of out[M,N] = epilogue(prologue(A) @ B); see include/dosx.h:DosxGemm."""
     g = Gemm()
     g.M, g.N = int(M), int(N)
     g.K = int(sum(s.width for s in segs))
@@ -436,11 +425,88 @@ def ffn_att_aligned_supported(H: int, Nk: int) -> bool:
     return bool(_lib.load().dosx_ffn_att_aligned_supported(int(H), int(Nk)))
 
 
+class Head(NamedTuple):
+    """An encoder's final LayerNorm inside the feed-forward launches of its last layer (DosxFfn.fin_* / DosxFfnBwd.fin_*) and,
+    with ``w`` set, the model's H -> 1 output layer behind it.  Forward (ffn_fwd): reads gamma, beta (, w, b), writes xhat
+    [rows, H], rstd [rows] (, dos [Bq, S]).  Backward (ffn_bwd): reads gamma, xhat, rstd (, w, beta, ddos [Bq, S]) and writes
+    dy [rows, H], the gradient in front of the LayerNorm.  S, Bq: the row layout behind dos / ddos (row = s * Bq + bq).
+    keys: the names of the gradients (LayerNorm weight, bias (, output weight, bias)) - functional.encoder_bwd's, not read here."""
+    gamma: torch.Tensor
+    beta: torch.Tensor
+    xhat: torch.Tensor
+    rstd: torch.Tensor
+    w: Optional[torch.Tensor] = None
+    b: Optional[torch.Tensor] = None
+    dos: Optional[torch.Tensor] = None
+    ddos: Optional[torch.Tensor] = None
+    dy: Optional[torch.Tensor] = None
+    S: int = 0
+    Bq: int = 0
+    keys: Tuple[str, ...] = ()
+
+
+class AttFwd(NamedTuple):
+    """The attention half of an encoder layer inside dosx_ffn_fwd (include/dosx.h: DosxFfn.att_*): ffn_fwd's ``x`` is then the
+    layer input (query rows at s * qs + b * qb); probs, qstats, x1, st1 are written.  aligned: crystal-aligned tiles."""
+    kvhat: torch.Tensor
+    gamma0: torch.Tensor
+    beta0: torch.Tensor
+    Nk: int
+    Bk: int
+    Bq: int
+    Sq: int
+    qs: int
+    qb: int
+    probs: torch.Tensor
+    qstats: torch.Tensor
+    x1: torch.Tensor
+    st1: torch.Tensor
+    mask: Optional[torch.Tensor] = None
+    aligned: bool = False
+    key_ptr: Optional[torch.Tensor] = None
+
+
+class AttBwd(NamedTuple):
+    """The attention half's backward inside dosx_ffn_bwd (include/dosx.h: DosxFfnBwd.att_*).  partials_q / partials_kv / dkv_cnt
+    are device addresses (the two halves of one partial-row buffer; ops.COUNTERS.take)."""
+    x: torch.Tensor
+    kvhat: torch.Tensor
+    gamma0: torch.Tensor
+    beta0: torch.Tensor
+    probs: torch.Tensor
+    qstats: torch.Tensor
+    dxin: torch.Tensor
+    partials_q: int
+    partials_kv: int
+    dkv_part: torch.Tensor
+    dkv_cnt: int
+    dkvhat: torch.Tensor
+    accumulate: int
+    Nk: int
+    Bk: int
+    Bq: int
+    Sq: int
+    qs: int
+    qb: int
+    mask: Optional[torch.Tensor] = None
+    key_ptr: Optional[torch.Tensor] = None
+
+
 def ffn_fwd(M: int, H: int, x: torch.Tensor, stats: Optional[torch.Tensor], gamma, beta, w1, b1, w2, b2, h: torch.Tensor,
-            out: torch.Tensor, fin=None, att=None, defer: Optional[list] = None) -> None:
+            out: torch.Tensor, fin: Optional[Head] = None, att: Optional[AttFwd] = None, defer: Optional[list] = None) -> None:
     """out = x + fc2(relu(fc1(LN1(x)))), h = relu(fc1(LN1(x))) in one launch (include/dosx.h: DosxFfn).
-    ``fin = (gamma, beta, xhat, rstd)``: also apply the encoder's final LayerNorm (out = LN(...), xhat / rstd saved);
-    ``fin = (gamma, beta, xhat, rstd, w, b, dos, S, Bq)``: ... and the H -> 1 output layer behind it (``out`` may be None)."""
+    ``fin``: also apply the encoder's final LayerNorm (out = LN(...), xhat / rstd saved) and, with ``fin.w`` set, the H -> 1
+    output layer behind it (``out`` may be None then).  A bare ``(gamma, beta, xhat, rstd)`` is read as Head(gamma, beta, xhat, rstd)."""
+    a = _ffn_desc(M, H, x, stats, gamma, beta, w1, b1, w2, b2, h, out, fin, att)
+    nk_att = a.att_Nk if att is not None else 0
+    if defer is not None:            # (encoder_fwd: the layers of a stack go out together, ffn_fwd_multi)
+        defer.append((a, 16.0 * M * H * H + 4.0 * M * nk_att * H))
+        return
+    _call("dosx_ffn_fwd", C.byref(a), _stream(),
+          w=lambda: (f"ffn_fwd[H{H}{',att' if nk_att else ''}]", "ffn_fwd_kernel", "mfma", 16.0 * M * H * H + 4.0 * M * nk_att * H))
+
+
+def _ffn_desc(M: int, H: int, x, stats, gamma, beta, w1, b1, w2, b2, h, out, fin: Optional[Head], att: Optional[AttFwd]) -> "Ffn":
     a = Ffn()
     a.M, a.H = int(M), int(H)
     a.x, a.ldx = x.data_ptr(), int(x.stride(0))
@@ -450,29 +516,24 @@ def ffn_fwd(M: int, H: int, x: torch.Tensor, stats: Optional[torch.Tensor], gamm
     a.h, a.ldh = h.data_ptr(), int(h.stride(0))
     if out is not None:
         a.out, a.ldo = out.data_ptr(), int(out.stride(0))
-    nk_att = 0
-    if att is not None:
-        # the attention half of the layer in the same launch (include/dosx.h: DosxFfn.att_*): ``x`` is then the layer input
-        # and att = dict(kvhat, gamma0, beta0, Nk, Bk, Bq, Sq, qs, qb, probs, qstats, x1, st1, mask=None)
-        a.att_kvhat, a.att_gamma0, a.att_beta0 = att["kvhat"].data_ptr(), att["gamma0"].data_ptr(), att["beta0"].data_ptr()
-        a.att_mask = _p(att.get("mask"))
-        a.att_probs, a.att_qstats = att["probs"].data_ptr(), att["qstats"].data_ptr()
-        a.att_x1, a.att_ldx1, a.att_st1 = att["x1"].data_ptr(), int(att["x1"].stride(0)), att["st1"].data_ptr()
-        a.att_Nk, a.att_Bk, a.att_Bq, a.att_Sq = int(att["Nk"]), int(att["Bk"]), int(att["Bq"]), int(att["Sq"])
-        a.att_qs, a.att_qb = int(att["qs"]), int(att["qb"])
-        a.att_aligned = int(bool(att.get("aligned", False)))
-        if att.get("key_ptr") is not None:
-            a.att_key_ptr = att["key_ptr"].data_ptr()
-        nk_att = a.att_Nk
+    if att is not None:             # the attention half of the layer in the same launch: ``x`` is then the layer input
+        a.att_kvhat, a.att_gamma0, a.att_beta0 = att.kvhat.data_ptr(), att.gamma0.data_ptr(), att.beta0.data_ptr()
+        a.att_mask = _p(att.mask)
+        a.att_probs, a.att_qstats = att.probs.data_ptr(), att.qstats.data_ptr()
+        a.att_x1, a.att_ldx1, a.att_st1 = att.x1.data_ptr(), int(att.x1.stride(0)), att.st1.data_ptr()
+        a.att_Nk, a.att_Bk, a.att_Bq, a.att_Sq = int(att.Nk), int(att.Bk), int(att.Bq), int(att.Sq)
+        a.att_qs, a.att_qb = int(att.qs), int(att.qb)
+        a.att_aligned = int(bool(att.aligned))
+        if att.key_ptr is not None:
+            a.att_key_ptr = att.key_ptr.data_ptr()
     if fin is not None:
-        a.fin_gamma, a.fin_beta, a.fin_xhat, a.fin_rstd = (t.data_ptr() for t in fin[:4])
-        if len(fin) > 4:          # (.., w, b, dos [Bq,S], S, Bq): the model head's H -> 1 output layer on the normalised rows
-            a.fin_w, a.fin_b, a.fin_dos, a.fin_S, a.fin_Bq = fin[4].data_ptr(), fin[5].data_ptr(), fin[6].data_ptr(), int(fin[7]), int(fin[8])
-    if defer is not None:            # (encoder_fwd: the layers of a stack go out together, ffn_fwd_multi)
-        defer.append((a, 16.0 * M * H * H + 4.0 * M * nk_att * H))
-        return
-    _call("dosx_ffn_fwd", C.byref(a), _stream(),
-          w=lambda: (f"ffn_fwd[H{H}{',att' if nk_att else ''}]", "ffn_fwd_kernel", "mfma", 16.0 * M * H * H + 4.0 * M * nk_att * H))
+        if not isinstance(fin, Head):      # a bare (gamma, beta, xhat, rstd) - Head's four required fields, in their order - is
+            gamma_f, beta_f, xhat_f, rstd_f = fin          # still taken (the final LayerNorm alone); any other length raises
+            fin = Head(gamma_f, beta_f, xhat_f, rstd_f)
+        a.fin_gamma, a.fin_beta, a.fin_xhat, a.fin_rstd = fin.gamma.data_ptr(), fin.beta.data_ptr(), fin.xhat.data_ptr(), fin.rstd.data_ptr()
+        if fin.w is not None:      # the model head's H -> 1 output layer on the normalised rows
+            a.fin_w, a.fin_b, a.fin_dos, a.fin_S, a.fin_Bq = fin.w.data_ptr(), fin.b.data_ptr(), fin.dos.data_ptr(), int(fin.S), int(fin.Bq)
+    return a
 
 
 FFN_MULTI_MAX = 2          # layers per dosx_ffn_fwd_multi launch (csrc/ffn.hip)
@@ -506,21 +567,29 @@ def ffn_att_bwd_partial_rows(Sq: int, Bq: int) -> int:
 
 
 def ffn_bwd(M: int, H: int, dy: torch.Tensor, h: torch.Tensor, x: torch.Tensor, stats: torch.Tensor, gamma, w1, w2,
-            dh: torch.Tensor, dx: Optional[torch.Tensor], partials: torch.Tensor, fin=None, att=None) -> None:
+            dh: torch.Tensor, dx: Optional[torch.Tensor], partials: torch.Tensor, fin: Optional[Head] = None,
+            att: Optional[AttBwd] = None) -> None:
     """dh = (dy W2) o [h>0], dx = dy + LN1_bwd(dh W1), LN1 dgamma|dbeta partial rows — one launch
-    (include/dosx.h: DosxFfnBwd).  ``fin = (gamma, xhat, rstd, dy_out)``: ``dy`` is the gradient behind the encoder's
-    final LayerNorm, whose backward runs first in the same launch (dy_out receives the result, the partial rows two more
-    column groups)."""
+    (include/dosx.h: DosxFfnBwd).  ``fin``: ``dy`` is the gradient behind the encoder's final LayerNorm, whose backward runs
+    first in the same launch (fin.dy receives the result, the partial rows two more column groups); with ``fin.w`` set the
+    H -> 1 output layer's backward in front of it (``dy`` None: fin.ddos is the incoming gradient)."""
+    a = _ffn_bwd_desc(M, H, dy, h, x, stats, gamma, w1, w2, dh, dx, partials, fin, att)
+    nk_att = a.att_Nk if att is not None else 0
+    _call("dosx_ffn_bwd", C.byref(a), _stream(),
+          w=lambda: (f"ffn_bwd[H{H}{',att' if nk_att else ''}]", "ffn_bwd_kernel", "mfma", 16.0 * M * H * H + 10.0 * M * nk_att * H))
+
+
+def _ffn_bwd_desc(M: int, H: int, dy, h, x, stats, gamma, w1, w2, dh, dx, partials, fin: Optional[Head], att: Optional[AttBwd]):
     a = _lib.FfnBwd()
     if fin is not None:
-        a.fin_gamma, a.fin_xhat, a.fin_rstd, a.fin_dy = (t.data_ptr() for t in fin[:4])
-        if len(fin) > 4:          # (.., ddos [Bq,S], w, beta, S, Bq): the H -> 1 output layer in front of that LayerNorm
-            a.fin_ddos, a.fin_w, a.fin_beta, a.fin_S, a.fin_Bq = fin[4].data_ptr(), fin[5].data_ptr(), fin[6].data_ptr(), int(fin[7]), int(fin[8])
+        a.fin_gamma, a.fin_xhat, a.fin_rstd, a.fin_dy = fin.gamma.data_ptr(), fin.xhat.data_ptr(), fin.rstd.data_ptr(), fin.dy.data_ptr()
+        if fin.w is not None:      # the H -> 1 output layer in front of that LayerNorm
+            a.fin_ddos, a.fin_w, a.fin_beta, a.fin_S, a.fin_Bq = fin.ddos.data_ptr(), fin.w.data_ptr(), fin.beta.data_ptr(), int(fin.S), int(fin.Bq)
     a.M, a.H = int(M), int(H)
     if dy is not None:
         a.dy, a.lddy = dy.data_ptr(), int(dy.stride(0))
     else:
-        a.lddy = int(fin[3].stride(0))
+        a.lddy = int(fin.dy.stride(0))
     a.h, a.ldh = h.data_ptr(), int(h.stride(0))
     a.x, a.ldx = x.data_ptr(), int(x.stride(0))
     a.stats, a.gamma = stats.data_ptr(), gamma.data_ptr()
@@ -529,25 +598,19 @@ def ffn_bwd(M: int, H: int, dy: torch.Tensor, h: torch.Tensor, x: torch.Tensor, 
     if dx is not None:
         a.dx, a.lddx = dx.data_ptr(), int(dx.stride(0))
     a.partials, a.partial_ld = partials.data_ptr(), int(partials.stride(0))
-    nk_att = 0
-    if att is not None:
-        # the attention half's backward in the same launch (include/dosx.h: DosxFfnBwd.att_*): att = dict(x, kvhat, gamma0, beta0,
-        # probs, qstats, mask, dxin, partials_q, partials_kv, dkv_part, dkv_cnt, dkvhat, accumulate, Nk, Bk, Bq, Sq, qs, qb,
-        # key_ptr=None)
-        a.att_x, a.att_ldxin = att["x"].data_ptr(), int(att["x"].stride(0))
-        a.att_kvhat, a.att_gamma0, a.att_beta0 = att["kvhat"].data_ptr(), att["gamma0"].data_ptr(), att["beta0"].data_ptr()
-        a.att_probs, a.att_qstats, a.att_mask = att["probs"].data_ptr(), att["qstats"].data_ptr(), _p(att.get("mask"))
-        a.att_dxin, a.att_lddxin = att["dxin"].data_ptr(), int(att["dxin"].stride(0))
-        a.att_partials_q, a.att_partials_kv = att["partials_q"], att["partials_kv"]
-        a.att_dkv_part, a.att_dkv_cnt = att["dkv_part"].data_ptr(), att["dkv_cnt"]
-        a.att_dkvhat, a.att_dkv_accumulate = att["dkvhat"].data_ptr(), int(att["accumulate"])
-        a.att_Nk, a.att_Bk, a.att_Bq, a.att_Sq = int(att["Nk"]), int(att["Bk"]), int(att["Bq"]), int(att["Sq"])
-        a.att_qs, a.att_qb = int(att["qs"]), int(att["qb"])
-        if att.get("key_ptr") is not None:
-            a.att_key_ptr = att["key_ptr"].data_ptr()
-        nk_att = a.att_Nk
-    _call("dosx_ffn_bwd", C.byref(a), _stream(),
-          w=lambda: (f"ffn_bwd[H{H}{',att' if nk_att else ''}]", "ffn_bwd_kernel", "mfma", 16.0 * M * H * H + 10.0 * M * nk_att * H))
+    if att is not None:             # the attention half's backward in the same launch
+        a.att_x, a.att_ldxin = att.x.data_ptr(), int(att.x.stride(0))
+        a.att_kvhat, a.att_gamma0, a.att_beta0 = att.kvhat.data_ptr(), att.gamma0.data_ptr(), att.beta0.data_ptr()
+        a.att_probs, a.att_qstats, a.att_mask = att.probs.data_ptr(), att.qstats.data_ptr(), _p(att.mask)
+        a.att_dxin, a.att_lddxin = att.dxin.data_ptr(), int(att.dxin.stride(0))
+        a.att_partials_q, a.att_partials_kv = att.partials_q, att.partials_kv
+        a.att_dkv_part, a.att_dkv_cnt = att.dkv_part.data_ptr(), att.dkv_cnt
+        a.att_dkvhat, a.att_dkv_accumulate = att.dkvhat.data_ptr(), int(att.accumulate)
+        a.att_Nk, a.att_Bk, a.att_Bq, a.att_Sq = int(att.Nk), int(att.Bk), int(att.Bq), int(att.Sq)
+        a.att_qs, a.att_qb = int(att.qs), int(att.qb)
+        if att.key_ptr is not None:
+            a.att_key_ptr = att.key_ptr.data_ptr()
+    return a
 
 
 MLP_LN_MAX_ROWS = 4096
@@ -1024,6 +1087,10 @@ class GradSink:
             if RECORDER.active:
                 RECORDER.prog.append((self.main.wait_stream, (self.side,)))
             self._forked = False
+
+    def keep(self, *tensors) -> None:
+        """Keep ``tensors`` (None entries are skipped) alive until release(): work queued on a side stream still reads them."""
+        self._keep.extend(t for t in tensors if t is not None)
 
     def scratch(self, *shape) -> torch.Tensor:
         t = alloc(self.device, *shape)

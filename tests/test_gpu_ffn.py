@@ -159,7 +159,7 @@ def test_ffn_fused_forward(M, H):
     # same launch with the encoder's final LayerNorm fused into the row epilogue
     fg, fb = rnd(H, seed=8), rnd(H, seed=9)
     xhat, rstd_o, y = torch.empty(M, H, device=DEV), torch.empty(M, device=DEV), torch.empty(M, H, device=DEV)
-    o.ffn_fwd(M, H, x, stats, g, b, w1, b1, w2, b2, h, y, fin=(fg, fb, xhat, rstd_o))
+    o.ffn_fwd(M, H, x, stats, g, b, w1, b1, w2, b2, h, y, fin=o.Head(fg, fb, xhat, rstd_o))
     mu2 = ref.mean(1, keepdim=True)
     rs2 = 1 / torch.sqrt(ref.var(1, unbiased=False, keepdim=True) + 1e-5)
     assert err(xhat, (ref - mu2) * rs2) < 5e-5 and err(rstd_o, rs2[:, 0]) < 5e-5
@@ -199,7 +199,7 @@ def test_ffn_fused_backward(M, H):
 
 @pytest.mark.parametrize("H,S,B", [(128, 51, 8), (64, 51, 3), (128, 7, 1)])
 @pytest.mark.parametrize("mode", ["cross", "self"])
-def test_final_layernorm_backward_inside_ffn_bwd(H, S, B, mode, monkeypatch):
+def test_final_layernorm_backward_inside_ffn_bwd(H, S, B, mode):
     """The encoder's final LayerNorm backward (layers/transformer.py:76-77) fused into the last layer's ffn_bwd launch
     against the stand-alone dosx_layernorm_bwd launch it replaces and against torch autograd on the same module math."""
     from dostransformer_amd import functional as Fn
@@ -216,13 +216,13 @@ def test_final_layernorm_backward_inside_ffn_bwd(H, S, B, mode, monkeypatch):
     w = torch.randn(S, B, H, generator=gen).to(DEV)
 
     def run(fused):
-        monkeypatch.setattr(Fn, "_FUSED_FIN_BWD", fused)
         enc.zero_grad(set_to_none=True)
         x = x0.clone().requires_grad_(True)
         kv = kv0.clone().requires_grad_(True)
-        y = enc(x, kv, kv) if mode == "cross" else enc(x, x, x)
-        (y * w).sum().backward()
-        torch.cuda.synchronize()
+        with Fn.forms(_FUSED_FIN_BWD=fused):
+            y = enc(x, kv, kv) if mode == "cross" else enc(x, x, x)
+            (y * w).sum().backward()
+            torch.cuda.synchronize()
         g = {n: p.grad.clone() for n, p in enc.named_parameters() if p.grad is not None}
         return y.detach().clone(), x.grad.clone(), (kv.grad.clone() if mode == "cross" else None), g
 
@@ -239,7 +239,7 @@ def test_final_layernorm_backward_inside_ffn_bwd(H, S, B, mode, monkeypatch):
 
 
 @pytest.mark.parametrize("H,S,B", [(128, 51, 4), (64, 51, 3)])
-def test_head_inside_ffn_kernels_matches_standalone_launches(H, S, B, monkeypatch):
+def test_head_inside_ffn_kernels_matches_standalone_launches(H, S, B):
     """Final LayerNorm + out_layer in the last ffn_fwd epilogue / first ffn_bwd prologue of the source encoder against the
     ln_rowdot(_bwd) launches they replace: same DOS, same gradients (fp32 rounding of a different summation tree only)."""
     from dostransformer_amd import functional as Fn
@@ -251,13 +251,12 @@ def test_head_inside_ffn_kernels_matches_standalone_launches(H, S, B, monkeypatc
     g = collate(synth.phonon_crystals(B, 77, torch.float32)).to(DEV)
 
     def run(fused):
-        monkeypatch.setattr(Fn, "_FUSED_HEAD_FWD", fused)
-        monkeypatch.setattr(Fn, "_FUSED_FIN_BWD", fused)
         model.zero_grad(set_to_none=True)
-        out = model(g)
-        loss = (out[0] ** 2).sum() + 0.5 * (out[2] ** 2).sum()
-        loss.backward()
-        torch.cuda.synchronize()
+        with Fn.forms(_FUSED_HEAD_FWD=fused, _FUSED_FIN_BWD=fused):
+            out = model(g)
+            loss = (out[0] ** 2).sum() + 0.5 * (out[2] ** 2).sum()
+            loss.backward()
+            torch.cuda.synchronize()
         return [o.detach().clone() for o in (out[0], out[2])], {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None}
 
     o1, g1 = run(True)
@@ -360,15 +359,11 @@ def test_encoder_layer_with_attention_inside_the_ffn_launch(Sq, Bq, Nk, Bk, H, b
     qs, qb = (1, 0) if bcast else (Bq, 1)
     seed = torch.tensor([1234], dtype=torch.int64, device=DEV)
     res = {}
-    cap, cap_al, al, rf = Fn._ATT_FFN_MAX_ROWS, Fn._ATT_ALIGNED_MAX_WGS, Fn._ATT_ALIGNED, Fn._ATT_ROWS_FIRST
     for fused in (False, True):
-        Fn._FUSED_ATT_FFN = fused
         # (the shipped policy fuses by shape; the kernels take any: force the form under test)
-        Fn._ATT_FFN_MAX_ROWS = (1 << 30) if form == "rows" else 0
-        Fn._ATT_ALIGNED, Fn._ATT_ALIGNED_MAX_WGS, Fn._ATT_ROWS_FIRST = form == "aligned", 1 << 30, form == "rows"
-        fab = Fn._FUSED_ATT_BWD
-        Fn._FUSED_ATT_BWD = fused and form == "aligned"      # (round 5: ... and the attention half's backward inside dosx_ffn_bwd)
-        try:
+        with Fn.forms(_FUSED_ATT_FFN=fused, _ATT_FFN_MAX_ROWS=(1 << 30) if form == "rows" else 0, _ATT_ALIGNED=form == "aligned",
+                      _ATT_ALIGNED_MAX_WGS=1 << 30, _ATT_ROWS_FIRST=form == "rows",
+                      _FUSED_ATT_BWD=fused and form == "aligned"):      # (round 5: ... and the attention half's backward inside dosx_ffn_bwd)
             o.KERNEL_TIMER.reset(enabled=False)
             y, ctx = Fn.encoder_fwd(P, "e", x, Sq, Bq, qs, qb, kvhat, Nk, Bk, H, T, drop=(drop, seed, 0) if drop > 0 else None)
             G = {k: torch.zeros_like(v) for k, v in P.items()}
@@ -378,24 +373,21 @@ def test_encoder_layer_with_attention_inside_the_ffn_launch(Sq, Bq, Nk, Bk, H, b
             dx = Fn.encoder_bwd(P, G, "e", ctx, dy, dkv, sink)
             sink.flush()
             torch.cuda.synchronize()
-            res[fused] = (y, ctx[0], dx, dkv, {k: v.clone() for k, v in G.items()})
-        finally:
-            Fn._FUSED_ATT_FFN = True
-            Fn._ATT_FFN_MAX_ROWS, Fn._ATT_ALIGNED_MAX_WGS, Fn._ATT_ALIGNED, Fn._ATT_ROWS_FIRST = cap, cap_al, al, rf
-            Fn._FUSED_ATT_BWD = fab
+            res[fused] = (y, ctx.layers, dx, dkv, {k: v.clone() for k, v in G.items()})
     (y0, lay0, dx0, dkv0, G0), (y1, lay1, dx1, dkv1, G1) = res[False], res[True]
     rel = lambda a, b: float((a - b).abs().max() / (b.abs().max() + 1e-12))
     assert rel(y1, y0) < 5e-6
     for t in range(T):
-        for name, idx in (("x1", 3), ("probs", 4), ("qstats", 5), ("st1", 6), ("h", 7)):
-            assert not torch.isnan(lay1[t][idx]).any(), (t, name)
-            assert rel(lay1[t][idx], lay0[t][idx]) < 1e-5, (t, name, rel(lay1[t][idx], lay0[t][idx]))
+        for name in ("x1", "probs", "qstats", "st1", "h"):
+            a1, a0 = getattr(lay1[t], name), getattr(lay0[t], name)
+            assert not torch.isnan(a1).any(), (t, name)
+            assert rel(a1, a0) < 1e-5, (t, name, rel(a1, a0))
         if drop > 0:
-            assert torch.equal(lay1[t][8], lay0[t][8])                  # same Philox draws
+            assert torch.equal(lay1[t].mask, lay0[t].mask)                  # same Philox draws
     # A ReLU gate whose pre-activation is below fp32 resolution may flip between the two forms (their sums run in another order:
     # the aligned form multiplies on the MFMA) - ~1e-6 of the 4H x rows gates: one flip moves ONE row of the gradients by O(1e-3)
     # of their maximum.  Without a flip the gradients agree to rounding; with flips, everywhere but in those rows.
-    flips = sum(int(((lay1[t][7] > 0) != (lay0[t][7] > 0)).sum()) for t in range(T))
+    flips = sum(int(((lay1[t].h > 0) != (lay0[t].h > 0)).sum()) for t in range(T))
     if flips == 0:
         assert rel(dx1, dx0) < 2e-5 and rel(dkv1, dkv0) < 2e-5
         for k in G0:
@@ -464,19 +456,15 @@ def test_encoder_stack_layers_in_one_launch(Sq, Bq, Nk, Bk, H, T, bcast, final):
     kvhat = torch.randn(Nk * Bk, H, generator=gen).to(DEV)
     qs, qb = (1, 0) if bcast else (Bq, 1)
     res = {}
-    saved = Fn._FFN_MULTI
-    try:
-        for multi in (False, True):
-            Fn._FFN_MULTI = multi
+    for multi in (False, True):
+        with Fn.forms(_FFN_MULTI=multi):
             y, ctx = Fn.encoder_fwd(P, "e", x, Sq, Bq, qs, qb, kvhat, Nk, Bk, H, T, final_ln=final)
             torch.cuda.synchronize()
-            res[multi] = (y, ctx)
-    finally:
-        Fn._FFN_MULTI = saved
+        res[multi] = (y, ctx)
     (y0, c0), (y1, c1) = res[False], res[True]
     assert bool(torch.isfinite(y1).all()) and torch.equal(y0, y1)
-    for l0, l1 in zip(c0[0], c1[0]):
-        for u, v in zip(l0[3:8], l1[3:8]):              # x1, probs, qstats, st1, h
-            assert torch.equal(u, v)
+    for l0, l1 in zip(c0.layers, c1.layers):
+        for name in ("x1", "probs", "qstats", "st1", "h"):
+            assert torch.equal(getattr(l0, name), getattr(l1, name)), name
     if final:
-        assert torch.equal(c0[1][0], c1[1][0]) and torch.equal(c0[1][1], c1[1][1])
+        assert torch.equal(c0.fin.xhat, c1.fin.xhat) and torch.equal(c0.fin.rstd, c1.fin.rstd)

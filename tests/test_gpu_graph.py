@@ -641,12 +641,10 @@ def test_factored_edge_weight_gradient_equals_the_plain_one(kind):
     m0 = mk()
     sd0 = {k: v.detach().clone() for k, v in m0.state_dict().items()}
     grads, params, outs = {}, {}, {}
-    min_gf, last_gf, heads_gf = Fn._FACTOR_MIN_GF, Fn._FACTOR_LAST_MIN_GF, Fn._FACTOR_HEADS_MIN_GF
     for fac in (False, True):
-        Fn._FACTOR_EDGE_WGRAD, Fn._FACTOR_MIN_GF = fac, 0.0        # (the shipped policy factors from 4 GF; the path takes any size)
-        Fn._FACTOR_LAST_MIN_GF = 0.0 if fac else 1e9               # ... and the last layer's aggregate-first form with it
-        Fn._FACTOR_HEADS_MIN_GF = 0.0 if fac else 1e9              # ... and the output heads' per-crystal K-segments (res_pre)
-        try:
+        with Fn.forms(_FACTOR_EDGE_WGRAD=fac, _FACTOR_MIN_GF=0.0,             # (the shipped policy factors from 4 GF; the path takes any size)
+                      _FACTOR_LAST_MIN_GF=0.0 if fac else 1e9,                # ... and the last layer's aggregate-first form with it
+                      _FACTOR_HEADS_MIN_GF=0.0 if fac else 1e9):              # ... and the output heads' per-crystal K-segments (res_pre)
             for replay in (False, True):
                 model = mk()
                 model.load_state_dict(sd0)
@@ -661,8 +659,6 @@ def test_factored_edge_weight_gradient_equals_the_plain_one(kind):
                     tr.step(gp)
                 torch.cuda.synchronize()
                 params[(fac, replay)] = {k: v.detach().clone() for k, v in model.state_dict().items()}
-        finally:
-            Fn._FACTOR_EDGE_WGRAD, Fn._FACTOR_MIN_GF, Fn._FACTOR_LAST_MIN_GF, Fn._FACTOR_HEADS_MIN_GF = True, min_gf, last_gf, heads_gf
     n_real, n_pad = g.meta.num_nodes, gp.meta.num_nodes
     for u, v in zip(outs[(True, False)], outs[(False, False)]):
         if u.shape[0] == n_pad:                          # node embeddings: the ghost rows are finite don't-cares (batch.pad_batch) -
@@ -827,13 +823,11 @@ def test_fused_factored_edge_layer_equals_the_plain_one(kind, H):
     m0 = mk()
     sd0 = {k: v.detach().clone() for k, v in m0.state_dict().items()}
     grads, params, outs = {}, {}, {}
-    saved = (Fn._FACTOR_EDGE_WGRAD, Fn._FACTOR_MIN_GF, Fn._FACTOR_FUSED, Fn._EDGE_ONE_LAUNCH, Fn._EDGE_ONE_LAUNCH_BWD)
-    try:
-        # plain: gathered-concat GEMM; rowkernels: round 4's factored form; epilogues: gathers / node sums inside dosx_gemm;
-        # fused: the shipped default - hidden <= 128: EdgeModel forward and backward one launch each (csrc/edge_mlp.hip)
-        for form in ("plain", "rowkernels", "epilogues", "fused"):
-            Fn._FACTOR_EDGE_WGRAD, Fn._FACTOR_MIN_GF, Fn._FACTOR_FUSED = form != "plain", 0.0, form in ("epilogues", "fused")
-            Fn._EDGE_ONE_LAUNCH = Fn._EDGE_ONE_LAUNCH_BWD = form == "fused"
+    # plain: gathered-concat GEMM; rowkernels: round 4's factored form; epilogues: gathers / node sums inside dosx_gemm;
+    # fused: the shipped default - hidden <= 128: EdgeModel forward and backward one launch each (csrc/edge_mlp.hip)
+    for form in ("plain", "rowkernels", "epilogues", "fused"):
+        with Fn.forms(_FACTOR_EDGE_WGRAD=form != "plain", _FACTOR_MIN_GF=0.0, _FACTOR_FUSED=form in ("epilogues", "fused"),
+                      _EDGE_ONE_LAUNCH=form == "fused", _EDGE_ONE_LAUNCH_BWD=form == "fused"):
             for replay in (False, True):
                 model = mk()
                 model.load_state_dict(sd0)
@@ -847,8 +841,6 @@ def test_fused_factored_edge_layer_equals_the_plain_one(kind, H):
                     tr.step(gp)
                 torch.cuda.synchronize()
                 params[(form, replay)] = {k: v.detach().clone() for k, v in model.state_dict().items()}
-    finally:
-        Fn._FACTOR_EDGE_WGRAD, Fn._FACTOR_MIN_GF, Fn._FACTOR_FUSED, Fn._EDGE_ONE_LAUNCH, Fn._EDGE_ONE_LAUNCH_BWD = saved
     n_real, n_pad = g.meta.num_nodes, gp.meta.num_nodes
     for other in ("plain", "rowkernels", "epilogues"):
         for u, v in zip(outs[("fused", False)], outs[(other, False)]):
@@ -896,22 +888,18 @@ def test_edge_model_forward_in_one_launch(n, H, fat, mean, last):
     m = M_()
     m.src, m.dst, m.num_nodes, m.num_edges, m.seg_tile, m.rowptr_dst = src, dst, n, E, tiles, rp
     res = {}
-    saved = (Fn._FACTOR_MIN_GF, Fn._FACTOR_FUSED, Fn._EDGE_ONE_LAUNCH)
-    try:
-        for one in (False, True, True):
-            Fn._FACTOR_MIN_GF, Fn._FACTOR_FUSED, Fn._EDGE_ONE_LAUNCH = 0.0, True, one
-            a = Fn.SegList([o.seg(x, rmap=o.rowmap(idx=src)), o.seg(x, rmap=o.rowmap(idx=dst)), o.seg(e)], [x, e])
-            a.factor = (x, e, m)
-            agg = torch.full((n, H), float("nan"), device=DEV)
-            e_out = None if last else torch.full((E, H), float("nan"), device=DEV)
+    for one in (False, True, True):
+        a = Fn.SegList([o.seg(x, rmap=o.rowmap(idx=src)), o.seg(x, rmap=o.rowmap(idx=dst)), o.seg(e)], [x, e])
+        a.factor = (x, e, m)
+        agg = torch.full((n, H), float("nan"), device=DEV)
+        e_out = None if last else torch.full((E, H), float("nan"), device=DEV)
+        with Fn.forms(_FACTOR_MIN_GF=0.0, _FACTOR_FUSED=True, _EDGE_ONE_LAUNCH=one):
             _, ctx = Fn.mlp_ln_fwd(P, "k", a, E, H, segsum=(tiles, rp, scale, agg, e, e_out))
-            torch.cuda.synchronize()
-            if one and True in res:
-                r = res[True]
-                assert torch.equal(agg, r[0]) and torch.equal(ctx[1], r[2]) and (last or torch.equal(e_out, r[1]))
-            res[one] = (agg, e_out, ctx[1].clone(), ctx[2].clone())
-    finally:
-        Fn._FACTOR_MIN_GF, Fn._FACTOR_FUSED, Fn._EDGE_ONE_LAUNCH = saved
+        torch.cuda.synchronize()
+        if one and True in res:
+            r = res[True]
+            assert torch.equal(agg, r[0]) and torch.equal(ctx.xhat, r[2]) and (last or torch.equal(e_out, r[1]))
+        res[one] = (agg, e_out, ctx.xhat.clone(), ctx.rstd.clone())
     (agg0, e0, xh0, rs0), (agg1, e1, xh1, rs1) = res[False], res[True]
     assert bool(torch.isfinite(agg1).all()) and bool(torch.isfinite(xh1).all())
     assert err(xh1, xh0) < 1e-5 and err(rs1, rs0) < 1e-5
@@ -1051,8 +1039,8 @@ def test_mlp_ln_fused_matches_reference(M, H, with_res, monkeypatch):
     # against the two-GEMM path (same arithmetic, different tiling: fp32 rounding only)
     assert float((y1 - y0).abs().max()) <= 5e-6 * sc(y0)
     assert float((d1 - d0).abs().max()) <= 5e-6 * sc(d0)
-    assert float((c1[1] - c0[1]).abs().max()) <= 5e-6 * sc(c0[1])          # xhat
-    assert float((c1[2] - c0[2]).abs().max()) <= 5e-6 * sc(c0[2])          # rstd
+    assert float((c1.xhat - c0.xhat).abs().max()) <= 5e-6 * sc(c0.xhat)
+    assert float((c1.rstd - c0.rstd).abs().max()) <= 5e-6 * sc(c0.rstd)
     for k in G1:
         assert float((G1[k] - G0[k]).abs().max()) <= 2e-5 * sc(G0[k]), k
 
@@ -1104,7 +1092,7 @@ def test_mlp_ln_forward_also_multiplies_the_next_layers_node_products(M, H):
     ops.gemm_pair(dict(M=M, N=2 * H, segs=[seg(y0)], w=W1n[:, :H], out=ref[:, :2 * H]),
                   dict(M=M, N=2 * H, segs=[seg(y0)], w=W1n[:, H:2 * H], out=ref[:, 2 * H:]))
     torch.cuda.synchronize()
-    assert torch.equal(y0, y1) and torch.equal(c0[1], c1[1]) and torch.equal(c0[2], c1[2])
+    assert torch.equal(y0, y1) and torch.equal(c0.xhat, c1.xhat) and torch.equal(c0.rstd, c1.rstd)
     assert not torch.isnan(pq).any()
     assert float((pq - ref).abs().max()) <= 5e-6 * float(ref.abs().max())
     exact = torch.cat([y0.double() @ W1n[:, :H].double().t(), y0.double() @ W1n[:, H:2 * H].double().t()], 1)
@@ -1357,7 +1345,7 @@ def test_node_encoder_and_first_node_products_in_one_column_split_launch(M, Fa, 
     z, y, pq = got[0]
     assert all(torch.equal(u, v) for g_ in got[1:] for u, v in zip(g_, got[0]))
     assert bool(torch.isfinite(z).all()) and bool(torch.isfinite(y).all()) and bool(torch.isfinite(pq).all())
-    assert err(z, ctx0[1]) < 5e-6 and err(y, y0) < 5e-6 and err(pq, pq0) < 1e-5
+    assert err(z, ctx0.z) < 5e-6 and err(y, y0) < 5e-6 and err(pq, pq0) < 1e-5
     z64 = x.double() @ P["k.0.weight"].double().T + P["k.0.bias"].double()
     y64 = torch.where(z64 >= 0, z64, 0.25 * z64) @ P["k.2.weight"].double().T + P["k.2.bias"].double()
     pq64 = torch.cat([y64 @ W1[:, :H].double().T, y64 @ W1[:, H:2 * H].double().T], 1)

@@ -263,12 +263,10 @@ def _enc_params(H, T, seed):
     return P
 
 
-def _encoder_case(shape, drop, monkeypatch=None, off=None):
+def _encoder_case(shape, drop, off=None):          # off: the switch the caller has turned off around this call (printed)
     from oracle import dos_oracle as O
     from dostransformer_amd import functional as Fn
     Sq, B, H, T, counts, Nk = ENC_SHAPES[shape]
-    if off is not None:
-        monkeypatch.setattr(Fn, off, False)
     o = ops()
     P = _enc_params(H, T, 11)
     G = {k: torch.zeros_like(v) for k, v in P.items()}
@@ -336,9 +334,10 @@ def test_encoder_over_own_keys(shape, drop):
 
 @pytest.mark.parametrize("drop", [False, True], ids=["nodrop", "drop"])
 @pytest.mark.parametrize("off", ["_FUSED_ATT_FFN", "_ATT_ALIGNED", "_FUSED_ATT_BWD"])
-def test_encoder_over_own_keys_on_separate_launches(off, drop, monkeypatch):
-    figs = _encoder_case("nk37_h64", drop, monkeypatch, off)
-    _enc_assert(figs)
+def test_encoder_over_own_keys_on_separate_launches(off, drop):
+    from dostransformer_amd import functional as Fn
+    with Fn.forms(**{off: False}):
+        _enc_assert(_encoder_case("nk37_h64", drop, off))
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -301,7 +301,117 @@ def test_size_policies_of_the_factored_forms():
     _assert_switch_surface()           # ... and are no switches any more
 
 
-_ENV_SWITCHES = {"DOSX_LIB", "DOSX_FFN_BF16X3", "DOSX_DP_MID_BUCKET", "DOSX_DP_CHECK"}
+def test_attention_forms_at_the_baseline_encoder_shapes():
+    """functional.attention_form_fwd / attention_bwd_in_ffn (host-only: switches + the library's support functions) at the
+    BASELINE encoder shapes (Sq, Bq, Nk, Bk, H): the Phonon-DOS step (cfg2) has no stand-alone attention launch left, forward
+    or backward; hidden 256 (Electron-DOS) keeps the attention kernels; relu / res dropout runs every layer unfused."""
+    from dostransformer_amd import functional as Fn
+    A = Fn.AttForm
+    phonon = {"cross": ((51, 64, 12, 64, 128), A.ROWS_IN_FFN), "self": ((51, 128, 51, 128, 128), A.ALIGNED_IN_FFN),
+              "source": ((51, 128, 12, 64, 128), A.ALIGNED_IN_FFN)}
+    edos = {"cross": (201, 64, 30, 64, 256), "self": (201, 128, 201, 128, 256), "source": (201, 128, 30, 64, 256)}   # (201 bins; any atom count)
+    fdrop = (0.1, 0.1, None, 0)
+    for name, ((Sq, Bq, Nk, Bk, H), want) in phonon.items():
+        assert Fn.attention_form_fwd(Sq * Bq, Sq, Bq, Nk, H, None) is want, name
+        assert Fn.attention_form_fwd(Sq * Bq, Sq, Bq, Nk, H, fdrop) is A.STANDALONE, name
+        assert Fn.attention_bwd_in_ffn(Sq, Bq, Nk, H, fdrop=False), name
+        assert not Fn.attention_bwd_in_ffn(Sq, Bq, Nk, H, fdrop=True), name
+    for name, (Sq, Bq, Nk, Bk, H) in edos.items():
+        assert Fn.attention_form_fwd(Sq * Bq, Sq, Bq, Nk, H, None) is A.STANDALONE, name
+        assert Fn.attention_form_fwd(Sq * Bq, Sq, Bq, Nk, H, fdrop) is A.STANDALONE, name
+        assert not Fn.attention_bwd_in_ffn(Sq, Bq, Nk, H, fdrop=False), name
+    for Sq, Bq, Nk, H in ((51, 64, 12, 256), (7, 3, 1, 256), (51, 128, 51, 256)):          # hidden 256 at any shape
+        assert Fn.attention_form_fwd(Sq * Bq, Sq, Bq, Nk, H, None) is A.STANDALONE
+        assert not Fn.attention_bwd_in_ffn(Sq, Bq, Nk, H, fdrop=False)
+
+
+def test_forms_scope_sets_and_restores_the_policy_globals():
+    """functional.forms: the override scope of the tests - restores on normal exit and on an exception, a nested scope hands back
+    the OUTER scope's value, and a name that is not one of the module's policy globals is refused (nothing set)."""
+    from dostransformer_amd import functional as Fn
+    before = (Fn._FFN_MULTI, Fn._ATT_FFN_MAX_ROWS, Fn._FACTOR_MIN_GF)
+    assert before == (True, 4096, 0.5)
+    with Fn.forms(_FFN_MULTI=False, _ATT_FFN_MAX_ROWS=0):
+        assert (Fn._FFN_MULTI, Fn._ATT_FFN_MAX_ROWS, Fn._FACTOR_MIN_GF) == (False, 0, 0.5)
+        assert Fn.attention_form_fwd(51 * 64, 51, 64, 12, 128, None) is Fn.AttForm.ALIGNED_IN_FFN        # (the functions read them)
+        with Fn.forms(_ATT_FFN_MAX_ROWS=7, _FACTOR_MIN_GF=0.0):
+            assert (Fn._FFN_MULTI, Fn._ATT_FFN_MAX_ROWS, Fn._FACTOR_MIN_GF) == (False, 7, 0.0)
+        assert (Fn._FFN_MULTI, Fn._ATT_FFN_MAX_ROWS, Fn._FACTOR_MIN_GF) == (False, 0, 0.5)
+    assert (Fn._FFN_MULTI, Fn._ATT_FFN_MAX_ROWS, Fn._FACTOR_MIN_GF) == before
+    with pytest.raises(ZeroDivisionError):
+        with Fn.forms(_FFN_MULTI=False, _FUSED_ATT_BWD=False):
+            assert not Fn._FUSED_ATT_BWD
+            1 / 0
+    assert Fn._FFN_MULTI is True and Fn._FUSED_ATT_BWD is True
+    for bad in ("_NO_SUCH_FORM", "DROP_MASK_LOG", "forms", "_rows32", "ops"):
+        with pytest.raises(AttributeError):
+            with Fn.forms(_FFN_MULTI=False, **{bad: 1}):
+                pass
+        assert Fn._FFN_MULTI is True
+    assert not hasattr(Fn, "_NO_SUCH_FORM") and Fn.DROP_MASK_LOG is None
+
+
+def test_ffn_descriptors_take_the_head_fields_by_name():
+    """ops._ffn_desc / _ffn_bwd_desc (descriptor construction without a launch): every DosxFfn / DosxFfnBwd ``fin_*`` field holds
+    the address of the ops.Head field of that name, with and without the output layer; the attention records likewise."""
+    from dostransformer_amd import ops
+    H, S, Bq, Nk, Bk = 8, 5, 3, 4, 3
+    M = S * Bq
+    t = lambda *shape: torch.zeros(*shape)              # distinct CPU allocations: only their addresses are read
+    x, stats, g, b, w1, b1, w2, b2, h, out = t(M, H), t(M, 2), t(H), t(H), t(4 * H, H), t(4 * H), t(H, 4 * H), t(H), t(M, 4 * H), t(M, H)
+    fwd = ops.Head(gamma=t(H), beta=t(H), xhat=t(M, H), rstd=t(M), w=t(H), b=t(1), dos=t(Bq, S), S=S, Bq=Bq)
+    a = ops._ffn_desc(M, H, x, stats, g, b, w1, b1, w2, b2, h, None, fwd, None)
+    for name in ("gamma", "beta", "xhat", "rstd", "w", "b", "dos"):
+        assert getattr(a, "fin_" + name) == getattr(fwd, name).data_ptr(), name
+    assert (a.fin_S, a.fin_Bq, a.out) == (S, Bq, None)
+    assert len({getattr(a, "fin_" + n) for n in ("gamma", "beta", "xhat", "rstd", "w", "b", "dos")}) == 7
+    ln = ops.Head(t(H), t(H), t(M, H), t(M))            # the final LayerNorm alone: no output-layer field is set
+    a = ops._ffn_desc(M, H, x, stats, g, b, w1, b1, w2, b2, h, out, ln, None)
+    assert [getattr(a, "fin_" + n) for n in ("gamma", "beta", "xhat", "rstd")] == [v.data_ptr() for v in ln[:4]]
+    assert (a.fin_w, a.fin_b, a.fin_dos, a.fin_S, a.fin_Bq) == (None, None, None, 0, 0) and a.out == out.data_ptr()
+    bare = ops._ffn_desc(M, H, x, stats, g, b, w1, b1, w2, b2, h, out, tuple(ln[:4]), None)      # Head's required fields, unnamed
+    assert all(getattr(bare, "fin_" + n) == getattr(a, "fin_" + n) for n in ("gamma", "beta", "xhat", "rstd", "w", "dos", "S"))
+    with pytest.raises(ValueError):                     # ... and nothing longer: the output layer goes in by name only
+        ops._ffn_desc(M, H, x, stats, g, b, w1, b1, w2, b2, h, None, tuple(fwd[:4]) + (fwd.w, fwd.b, fwd.dos, S, Bq), None)
+    a = ops._ffn_desc(M, H, x, stats, g, b, w1, b1, w2, b2, h, out, None, None)
+    assert (a.fin_gamma, a.fin_xhat, a.att_kvhat, a.att_Nk) == (None, None, None, 0)
+
+    dy, dh, dx, part = t(M, H), t(M, 4 * H), t(M, H), t(1, 5 * H + 4)
+    bwd = ops.Head(gamma=t(H), beta=t(H), xhat=t(M, H), rstd=t(M), w=t(H), ddos=t(Bq, S), dy=t(M, H), S=S, Bq=Bq,
+                   keys=("ln.weight", "ln.bias", "out.weight", "out.bias"))
+    d = ops._ffn_bwd_desc(M, H, None, h, x, stats, g, w1, w2, dh, dx, part, bwd, None)
+    for name in ("gamma", "xhat", "rstd", "dy", "ddos", "w", "beta"):
+        assert getattr(d, "fin_" + name) == getattr(bwd, name).data_ptr(), name
+    assert (d.fin_S, d.fin_Bq, d.dy, d.lddy) == (S, Bq, None, H)
+    lnb = ops.Head(t(H), t(H), t(M, H), t(M), dy=t(M, H))
+    d = ops._ffn_bwd_desc(M, H, dy, h, x, stats, g, w1, w2, dh, dx, part, lnb, None)
+    for name in ("gamma", "xhat", "rstd", "dy"):
+        assert getattr(d, "fin_" + name) == getattr(lnb, name).data_ptr(), name
+    assert (d.fin_ddos, d.fin_w, d.fin_beta, d.fin_S, d.fin_Bq) == (None, None, None, 0, 0) and d.dy == dy.data_ptr()
+
+    kp = torch.zeros(Bk + 1, dtype=torch.int32)
+    af = ops.AttFwd(kvhat=t(Nk * Bk, H), gamma0=t(H), beta0=t(H), Nk=Nk, Bk=Bk, Bq=Bq, Sq=S, qs=Bq, qb=1, probs=t(Bq, S, Nk),
+                    qstats=t(M, 2), x1=t(M, H), st1=t(M, 2), mask=t(Bq, S, Nk), aligned=True, key_ptr=kp)
+    a = ops._ffn_desc(M, H, x, None, g, b, w1, b1, w2, b2, h, out, None, af)
+    for name in ("kvhat", "gamma0", "beta0", "probs", "qstats", "x1", "st1", "mask", "key_ptr"):
+        assert getattr(a, "att_" + name) == getattr(af, name).data_ptr(), name
+    assert (a.att_Nk, a.att_Bk, a.att_Bq, a.att_Sq, a.att_qs, a.att_qb, a.att_aligned) == (Nk, Bk, Bq, S, Bq, 1, 1)
+    ab = ops.AttBwd(x=t(M, H), kvhat=t(Nk * Bk, H), gamma0=t(H), beta0=t(H), probs=t(Bq, S, Nk), qstats=t(M, 2), dxin=t(M, H),
+                    partials_q=4096, partials_kv=8192, dkv_part=t(Bq * Nk, H), dkv_cnt=12288, dkvhat=t(Nk * Bk, H), accumulate=1,
+                    Nk=Nk, Bk=Bk, Bq=Bq, Sq=S, qs=Bq, qb=1)
+    d = ops._ffn_bwd_desc(M, H, dy, h, x, stats, g, w1, w2, dh, None, part, None, ab)
+    for name in ("x", "kvhat", "gamma0", "beta0", "probs", "qstats", "dxin", "dkv_part", "dkvhat"):
+        assert getattr(d, "att_" + name) == getattr(ab, name).data_ptr(), name
+    assert (d.att_partials_q, d.att_partials_kv, d.att_dkv_cnt, d.att_dkv_accumulate) == (4096, 8192, 12288, 1)
+    assert (d.att_mask, d.att_key_ptr, d.dx) == (None, None, None) and (d.att_Nk, d.att_Bk, d.att_Bq, d.att_Sq) == (Nk, Bk, Bq, S)
+    with pytest.raises(TypeError):
+        ops.AttFwd(kvhat=af.kvhat, gamma0=af.gamma0, beta0=af.beta0, Nk=Nk, Bk=Bk, Bq=Bq, Sq=S, qs=Bq, qb=1, probs=af.probs,
+                   qstats=af.qstats, x1=af.x1, st1=af.st1, msk=None)                     # a misspelt optional field is an error
+    with pytest.raises(TypeError):                                                       # ... and so is an unknown gemm keyword
+        ops.gemm(2, 2, [ops.seg(t(2, 2))], t(2, 2), t(2, 2), biass=None)
+
+
+_ENV_SWITCHES ={"DOSX_LIB", "DOSX_FFN_BF16X3", "DOSX_DP_MID_BUCKET", "DOSX_DP_CHECK"}
 _REMOVED_SWITCHES = {
     "functional": ("_NODE_CHAIN", "_FLUSH_AFTER_CHAIN", "_DENSE_CHAIN", "_SPLIT_LATE_FLUSH", "_LATE_SELF_FLUSH", "_MID_HOOK_LATE",
                    "_GNN_FLUSH_BEFORE_NODE", "_NODE_GRAD_ONE_LAUNCH", "_FACTOR_DGRAD", "_FACTOR_ONE_LAUNCH_ALWAYS", "_ENC_CS",

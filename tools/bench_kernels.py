@@ -189,14 +189,14 @@ def layer_case(name, Sq, Bq, Nk, Bk, H):
     def two():
         ops.attention_fwd(a)
         ops.ffn_fwd(M, H, x1, st1, g1, b1n, w1, b1, w2, b2, h, out)
-    att = dict(kvhat=kv, gamma0=g0, beta0=b0, Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=Bq, qb=1, probs=probs, qstats=qs, x1=x1, st1=st1)
+    att = ops.AttFwd(kvhat=kv, gamma0=g0, beta0=b0, Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=Bq, qb=1, probs=probs, qstats=qs, x1=x1, st1=st1)
     us2 = timeit(two)
     usa = timeit(lambda: ops.attention_fwd(a))
     usf = timeit(lambda: ops.ffn_fwd(M, H, x1, st1, g1, b1n, w1, b1, w2, b2, h, out))
     us1 = timeit(lambda: ops.ffn_fwd(M, H, x, None, g1, b1n, w1, b1, w2, b2, h, out, att=att)) if ops.ffn_att_supported(H, Nk) else float("nan")
     usl = float("nan")
     if ops.ffn_att_aligned_supported(H, Nk):
-        att2 = dict(att, aligned=True)
+        att2 = att._replace(aligned=True)
         usl = timeit(lambda: ops.ffn_fwd(M, H, x, None, g1, b1n, w1, b1, w2, b2, h, out, att=att2))
     print(f"layer {name:30s} Sq={Sq} Bq={Bq} Nk={Nk} H={H}: one launch {us1:6.1f} us (per-row keys) / {usl:6.1f} us (crystal-aligned tiles) | "
           f"attention {usa:5.1f} + ffn {usf:5.1f} us, back to back {us2:6.1f} us")

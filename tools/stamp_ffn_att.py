@@ -16,9 +16,9 @@ for Nk, Bk in ((12, 64), (51, 128)):
     o = 4 * H * H + 4 * H
     w2, b2 = flat[o:o + 4 * H * H].view(H, 4 * H), flat[o + 4 * H * H:]
     h, out = torch.empty(M, 4 * H, device="cuda"), torch.empty(M, H, device="cuda")
-    att = dict(kvhat=kv, gamma0=g, beta0=b, Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=Bq, qb=1, probs=torch.empty(Bq, Sq, Nk, device="cuda"),
-               qstats=torch.empty(M, 2, device="cuda"), x1=torch.empty(M, H, device="cuda"), st1=torch.empty(M, 2, device="cuda"),
-               mask=None, aligned=True)
+    att = ops.AttFwd(kvhat=kv, gamma0=g, beta0=b, Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=Bq, qb=1, probs=torch.empty(Bq, Sq, Nk, device="cuda"),
+                     qstats=torch.empty(M, 2, device="cuda"), x1=torch.empty(M, H, device="cuda"), st1=torch.empty(M, 2, device="cuda"),
+                     mask=None, aligned=True)
     for _ in range(5):
         ops.ffn_fwd(M, H, x, None, g, b, w1, b1, w2, b2, h, out, att=att)
     torch.cuda.synchronize()
