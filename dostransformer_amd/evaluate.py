@@ -2,11 +2,17 @@
 libdosx-backed modules.  Same signatures and return values as upstream, so
 ``main_eDOS.py:135-139`` / ``main_phDOS.py:124-128`` can import them from here unchanged; the metrics stay on
 the device until the end of a batch (upstream round-trips every batch through sklearn on the host).
+
+``test_per_crystal(predictor, ds)`` is the same evaluation at the reference's own setting, ``batch_size = 1``
+(`main_eDOS.py:55-56`, `main_phDOS.py:52-55`), run in batched passes: the returned numbers are means over the crystals of
+per-crystal metrics, which is what "the mean over batches" is when every batch holds one crystal.  ``test`` / ``test_phonon``
+fed bigger batches return something else (one R2 over each flattened batch, a short last batch weighted like a full one).
 """
 from __future__ import annotations
 
-from typing import Callable, Iterable, Optional
+from typing import Callable, Iterable, List, NamedTuple, Optional
 
+import numpy as np
 import torch
 
 
@@ -78,3 +84,96 @@ def test(model, data_loader: Iterable, criterion: Optional[Callable] = None, r2:
             n += 1
     preds_y = [[ids, torch.cat(preds).cpu().numpy(), torch.cat(ys).cpu().numpy(), torch.cat(embs).cpu().numpy()]]
     return float(rmse) / n, float(mse) / n, float(mae) / n, r2s / n, preds_y
+
+
+# ---- the reference's evaluation at batch_size = 1, in batched passes ------------------------------------------------------------
+def per_crystal_metrics_host(pred: torch.Tensor, y: torch.Tensor, clamp0: bool = False) -> torch.Tensor:
+    """[C,4] float64 = (rmse, mse, mae, r2) of every row of ``pred`` against the same row of ``y`` ([C,S], any device): what
+    `utils.py:76-89` / `:127-139` compute for a batch of ONE crystal, in torch float64.  ``clamp0``: both are clamped at 0 first
+    (`utils.py:74-76`, eDOS).  r2 = 1 - sum (y-p)^2 / sum (y-mean(y))^2, the mean taken first; a constant target gives what IEEE
+    division gives (-inf, or NaN when the error is 0 too), like ``r2`` on that row.  This is the definition that
+    ``dosx_eval_metrics`` implements on the GPU (``ops.eval_metrics``); only the order of the sums differs."""
+    p, t = pred.detach().to(torch.float64), y.detach().to(torch.float64)
+    t = t.reshape(p.shape)
+    if p.dim() != 2 or p.shape[1] < 1:
+        raise ValueError(f"per_crystal_metrics_host: [C,S] rows with S >= 1, got {tuple(p.shape)}")
+    if clamp0:
+        p, t = torch.clamp(p, min=0.0), torch.clamp(t, min=0.0)
+    S = p.shape[1]
+    d = t - p
+    sse = (d * d).sum(1)
+    mse = sse / S
+    sst = ((t - t.sum(1, keepdim=True) / S) ** 2).sum(1)
+    return torch.stack([torch.sqrt(mse), mse, d.abs().sum(1) / S, 1.0 - sse / sst], 1)
+
+
+class PerCrystalResult(NamedTuple):
+    """What ``test_per_crystal`` returns.  rmse, mse, mae, r2: the reference's return values at batch_size = 1 (means over the
+    crystals).  per_crystal: [C,4] float64 on the device, rows in the order of ``indices``.  preds, y: [C,S] in the program's
+    dtype (eDOS: clamped at 0).  embeddings [C,H] (sum-pooled node embeddings, `utils.py:91`) and mp_id: eDOS only, else None."""
+    rmse: float
+    mse: float
+    mae: float
+    r2: float
+    per_crystal: torch.Tensor
+    preds: torch.Tensor
+    y: torch.Tensor
+    embeddings: Optional[torch.Tensor]
+    mp_id: Optional[List]
+
+    def as_reference(self):
+        """The tuple the reference's loop returns: (rmse, mse, mae, r2) for phonon (`utils.py:143`), (rmse, mse, mae, r2,
+        [[mp_id, preds, y, embeddings]]) with numpy arrays for eDOS (`utils.py:112`)."""
+        head = (self.rmse, self.mse, self.mae, self.r2)
+        if self.embeddings is None:
+            return head
+        return head + ([[self.mp_id, self.preds.cpu().numpy(), self.y.cpu().numpy(), self.embeddings.cpu().numpy()]],)
+
+
+def test_per_crystal(predictor, ds, indices=None, batch_size: int = 64) -> PerCrystalResult:
+    """`utils.test` / `utils.test_phonon` over the crystals ``indices`` (default: all, in order) of a ``loader.DeviceDataset`` at
+    the reference's batch size 1, computed in passes of ``batch_size`` crystals: ``predictor`` - a ``predict.Predictor`` with
+    ``per_crystal_keys=True``, or a ``Predictor64`` whose module has ``set_per_crystal_keys(True)`` - gives every crystal its
+    batch-1 outputs from a batched pass, ``dosx_eval_metrics`` turns each row into its four metrics on the device, and the four
+    means are read back once at the end.  Every chunk runs with the n_max of the whole selection (few recorded shapes), which is
+    valid only because per-crystal keys make the outputs independent of it: without the flag this raises ``ValueError``."""
+    from . import ops
+    flag = getattr(predictor, "per_crystal_keys", None)
+    if flag is None:
+        flag = getattr(predictor.model, "per_crystal_keys", False)
+    if not flag:
+        raise ValueError("test_per_crystal needs per-crystal keys (Predictor(model, per_crystal_keys=True), or "
+                         "model.set_per_crystal_keys(True) under Predictor64): without them a batched pass does not give the "
+                         "batch-size-1 outputs the reference's metrics are computed from")
+    if batch_size < 1:
+        raise ValueError(f"test_per_crystal: batch_size must be positive, got {batch_size}")
+    idx = np.arange(len(ds), dtype=np.int64) if indices is None else np.asarray(list(indices), np.int64)
+    C = int(idx.shape[0])
+    if C == 0:
+        raise ValueError("test_per_crystal: no crystals selected")
+    predictor.eval()
+    edos = predictor.kind != "phonon"
+    n_max = int(ds.n_nodes[idx].max())
+    dev, table, embeddings = ds.device, None, None
+    for row0 in range(0, C, batch_size):
+        slot, N = predictor._run_dataset(ds, idx[row0:row0 + batch_size], n_max)
+        _, x, dos_system = slot.out
+        B, S = dos_system.shape
+        if table is None:
+            table = torch.empty(C, 4, dtype=torch.float64, device=dev)
+            preds, ys = torch.empty(C, S, dtype=dos_system.dtype, device=dev), torch.empty(C, S, dtype=dos_system.dtype, device=dev)
+            if edos:
+                embeddings = torch.empty(C, x.shape[1], dtype=torch.float32, device=dev)
+        rows = slice(row0, row0 + B)
+        # (outside the bucket's recording: the output pointers move with the chunk)
+        ops.eval_metrics(dos_system, predictor._target(slot).view(B, S), table[rows], clamp0=edos, pred_out=preds[rows], y_out=ys[rows])
+        if edos:
+            # the bucket's graph_ptr ends at its N real nodes: the ghost rows behind them belong to no crystal's sum
+            H = x.shape[1]
+            ops.graph_pool(x, slot.g.meta.graph_ptr, embeddings[rows].data_ptr(), H, B, H)
+    rmse, mse, mae, r2_ = table.mean(0).tolist()                       # the one transfer
+    mp_id = [ds.mp_id[i] for i in idx] if edos and ds.mp_id is not None else None
+    return PerCrystalResult(rmse, mse, mae, r2_, table, preds, ys, embeddings, mp_id)
+
+
+test_per_crystal.__test__ = False          # (a library function named like the reference's, not a pytest test)

@@ -1513,6 +1513,34 @@ def loss_edos(pg, ps, y_ft, beta, B, S, B_global, dpg, dps, loss_partial):
                                   _stream())
 
 
+def eval_metrics(pred: torch.Tensor, y: torch.Tensor, metrics: torch.Tensor, clamp0: bool = False,
+                 pred_out: Optional[torch.Tensor] = None, y_out: Optional[torch.Tensor] = None) -> None:
+    """metrics[b] = (rmse, mse, mae, r2) of row b of pred against row b of y, in float64 - the reference's metrics of a batch of
+    one crystal (include/dosx.h: dosx_eval_metrics / dosx_eval_metrics_f64).  pred, y: [B,S], both float32 or both float64;
+    metrics: [B,4] float64; ``clamp0``: clamp both at 0 first (eDOS); pred_out / y_out ([B,S], the inputs' dtype) receive the
+    clamped values.  The outputs may be row slices of larger tables."""
+    dt = pred.dtype
+    if dt not in (torch.float32, torch.float64):
+        raise TypeError(f"eval_metrics: float32 or float64 predictions, got {dt}")
+    ins = {"pred": pred, "y": y, "pred_out": pred_out, "y_out": y_out}
+    for k, t in ins.items():
+        if t is not None and (t.dtype != dt or not t.is_cuda):
+            raise TypeError(f"eval_metrics: {k} must be a {dt} CUDA tensor like pred, got {t.dtype} on {t.device}")
+    if metrics.dtype != torch.float64 or not metrics.is_cuda:
+        raise TypeError(f"eval_metrics: metrics must be a float64 CUDA tensor, got {metrics.dtype} on {metrics.device}")
+    if pred.dim() != 2 or pred.shape[1] < 1 or any(t is not None and t.shape != pred.shape for t in ins.values()) \
+            or tuple(metrics.shape) != (pred.shape[0], 4):
+        raise ValueError("eval_metrics: " + ", ".join(f"{k} {tuple(t.shape)}" for k, t in ins.items() if t is not None)
+                         + f", metrics {tuple(metrics.shape)}: want [B,S] (S >= 1) everywhere and metrics [B,4]")
+    for k, t in list(ins.items()) + [("metrics", metrics)]:
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"eval_metrics: {k} must be contiguous (rows of a table are), got strides {t.stride()}")
+    B, S = int(pred.shape[0]), int(pred.shape[1])
+    _call("dosx_eval_metrics" if dt == torch.float32 else "dosx_eval_metrics_f64", pred.data_ptr(), y.data_ptr(), B, S,
+          int(bool(clamp0)), metrics.data_ptr(), _p(pred_out), _p(y_out), _stream(),
+          w=lambda: ("eval_metrics", "eval_metrics_kernel", "hbm", 3.0 * pred.element_size() * B * S))
+
+
 def sum_to(src, n, dst):
     _call("dosx_sum", _p(src), int(n), _p(dst), _stream())
 

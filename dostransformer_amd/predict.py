@@ -22,12 +22,14 @@ bitwise those of ``model(batch)``.  Per-crystal keys stay the module's own switc
 """
 from __future__ import annotations
 
+from typing import Optional
+
 import torch
 
 from . import functional64 as F64
 from . import ops
 from ._models import DOSTransformerBase
-from .batch import CrystalBatch, graph_meta
+from .batch import CrystalBatch, bucket_sizes, graph_meta
 from .slots import Slot, padded_to_bucket
 
 
@@ -94,6 +96,60 @@ class _Predictor:
         dg, xL, ds = slot.out
         return dg, xL[:n_real], ds
 
+    def _tables(self, ds):
+        """The dataset's feature tables in the dtype of this predictor's slots."""
+        return ds._f32_tables()
+
+    def forward_dataset(self, ds, indices, n_max: Optional[int] = None):
+        """The forward pass on the crystals ``indices`` of a device-resident ``loader.DeviceDataset``, what ``step_dataset`` is
+        for training: the batch is collated STRAIGHT INTO the static buffers of its (ghost-padded) shape bucket, targets included,
+        and the bucket's program runs - recorded on the bucket's first visit, replayed afterwards.  Returns
+        ``((dos_global, x[:n_real], dos_system), target)``: the outputs of ``self(ds.collate(indices, n_max=n_max))`` and the
+        bucket's target buffer (``phdos`` [B,S] / ``y_ft`` [B*S]), all aliasing static buffers that the next call on the bucket
+        overwrites.  ``n_max`` may exceed the selection's largest crystal, so that one value serves a whole split; only with
+        per-crystal keys do the outputs not depend on it.  These buckets are kept apart from those of ``__call__``."""
+        slot, N = self._run_dataset(ds, indices, n_max)
+        dg, xL, dsys = slot.out
+        return (dg, xL[:N], dsys), self._target(slot)
+
+    def _target(self, slot: Slot) -> torch.Tensor:
+        return slot.g["phdos" if self.kind == "phonon" else "y_ft"]
+
+    def _run_dataset(self, ds, indices, n_max: Optional[int] = None):
+        """forward_dataset's work; returns (the bucket - outputs in ``slot.out``, metadata in ``slot.g.meta`` -, real node count)."""
+        model, who = self.model, type(self).__name__
+        self._require(model)
+        if model.training and getattr(model, "_attn_drop", 0.0) > 0.0:
+            raise RuntimeError(f"{who} replays an inference program: call model.eval() first (attention dropout is "
+                               "active in training mode)")
+        dev = model._module_device()
+        if dev.type != "cuda":
+            raise RuntimeError(f"{who} runs only on an MI355X through libdosx (no CPU fallback)")
+        fp = model._ensure_flat(dev, None)
+        if fp is not self._fp:                # parameters were re-homed: recorded pointers are stale
+            self._fp, self._slots = fp, {}
+        idx, N, E, n_max = ds.bucket_dims(indices, n_max)
+        B = int(idx.shape[0])
+        n_pad, e_pad = bucket_sizes(N, E, *self.bucket)
+        key = (n_pad, e_pad, B, n_max) + self._key_tail() + ("dataset",)
+        slot = self._slots.get(key)
+        fresh = slot is None
+        if fresh:
+            t = self._tables(ds)
+            slot = Slot.empty(self.kind, dev, self._dtype, B, n_pad, e_pad, n_max, int(t["x"].shape[1]), int(t["edge"].shape[1]),
+                              int(t["target"].shape[1]), tiled=self._dtype == torch.float32)
+        ds.collate_into(slot.g, idx, slot.collate_scratch())
+        slot._loaded = None                                        # (the static buffers now hold a batch no object stands for)
+        slot.set_real_nodes(N)
+        if fresh:
+            self.slot_misses += 1
+            self._record(slot, fp)
+            self._slots[key] = slot
+        else:
+            self.slot_hits += 1
+            slot.prog.run()
+        return slot, N
+
 
 class Predictor(_Predictor):
     _dtype = torch.float32
@@ -127,6 +183,9 @@ class Predictor64(_Predictor):
 
     def _key_tail(self) -> tuple:
         return (bool(self.model.per_crystal_keys), bool(F64.SOFTMAX64))
+
+    def _tables(self, ds):
+        return ds._f64_tables()
 
     def _forward(self, fp, slot):
         g, B = slot.g, slot.g.meta.num_graphs

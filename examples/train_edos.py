@@ -50,6 +50,9 @@ def parse_args(argv=None):
     ap.add_argument("--structures", type=int, default=0,
                     help="build the graphs of this many synthetic structures with featurize.build_edos_all (0: off)")
     ap.add_argument("--eval_batch_size", type=int, default=1, help="main_eDOS.py:55-56 evaluates at batch size 1")
+    ap.add_argument("--eval-per-crystal", type=int, default=0, metavar="N",
+                    help="N > 0: the batch-size-1 metrics from batched passes of N crystals (evaluate.test_per_crystal, "
+                         "per-crystal keys) instead of --eval_batch_size forwards")
     ap.add_argument("--out", default="edos_best.pt")
     ap.add_argument("--per-crystal-keys", action="store_true",
                     help="train over each crystal's own atoms (and its phantom node) - what the batch-size-1 evaluation computes")
@@ -88,8 +91,15 @@ def main(argv=None):
     bucket = (32, 512)
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=bucket, promote=0.08,
                       per_crystal_keys=args.per_crystal_keys)      # AdamW(lr, weight_decay=1e-2), `:91`
-    predictor = Predictor(model, bucket=bucket)
+    predictor = Predictor(model, bucket=bucket, per_crystal_keys=args.eval_per_crystal > 0)
     criterion_2 = torch.nn.L1Loss()                                                       # `main_eDOS.py:93`
+
+    def run_test(name):
+        """`utils.test` on a split -> (rmse, mse, mae, r2, ...): the reference's batch-size-1 numbers either way."""
+        if args.eval_per_crystal > 0:
+            return evaluate.test_per_crystal(predictor, ds[name], batch_size=args.eval_per_crystal).as_reference()
+        return evaluate.test(predictor, ds[name].batches(args.eval_batch_size), criterion_2, evaluate.r2)
+
     nmax_train = int(ds["train"].n_nodes.max())
 
     best_rmse = best_mae = 1000.0
@@ -110,7 +120,7 @@ def main(argv=None):
         if (epoch + 1) % min(args.eval, args.epochs):              # (a run shorter than --eval evaluates at its last epoch)
             continue
         # `main_eDOS.py:132-152`: validate; a new best in RMSE or MAE re-evaluates the test split (and, here, saves)
-        v_rmse, v_mse, v_mae, v_r2, _ = evaluate.test(predictor, ds["valid"].batches(args.eval_batch_size), criterion_2, evaluate.r2)
+        v_rmse, v_mse, v_mae, v_r2, _ = run_test("valid")
         print(f"[ {epoch + 1} epochs ]valid_rmse:{v_rmse:.4f}|valid_mse:{v_mse:.4f}|valid_mae:{v_mae:.4f}|valid_r2:{v_r2:.4f}")
         improved = v_rmse < best_rmse or v_mae < best_mae
         if v_rmse < best_rmse:
@@ -119,7 +129,7 @@ def main(argv=None):
             best_mae = v_mae
         if improved:
             best_epoch = epoch + 1
-            test_m = evaluate.test(predictor, ds["test"].batches(args.eval_batch_size), criterion_2, evaluate.r2)[:4]
+            test_m = run_test("test")[:4]
             print("[ {} epochs ]System:test_rmse:{:.4f}|test_mse:{:.4f}|test_mae:{:.4f}|test_r2:{:.4f}".format(epoch + 1, *test_m))
             checkpoint.save(args.out, model, trainer, extra={"epoch": epoch + 1, "valid_rmse": v_rmse, "test": list(test_m)})
         best_losses.append(best_rmse)

@@ -57,7 +57,12 @@ def main(argv=None):
     ap.add_argument("--replay", action="store_true", help="with --float64 --fused: replay recorded launch lists, one per shape bucket (step_dataset + Predictor64)")
     ap.add_argument("--per-crystal-keys", action="store_true",
                     help="fp32 trainer: attend over each crystal's own atoms - what the reference's batch_size = 1 training computes")
+    ap.add_argument("--eval-per-crystal", type=int, default=0, metavar="N",
+                    help="N > 0: validate and test with the reference's batch-size-1 metrics, from batched passes of N crystals "
+                         "(evaluate.test_per_crystal; fp32 run, or --float64 --fused --replay)")
     args = ap.parse_args(argv)
+    if args.eval_per_crystal > 0 and args.float64 and not args.replay:
+        ap.error("--eval-per-crystal needs a replayed predictor: the fp32 run, or --float64 --fused --replay")
     if args.fused and not args.float64:
         ap.error("--fused selects the float64 trainer: use it with --float64 (the fp32 run is fused already)")
     if args.replay and not args.fused:
@@ -84,7 +89,8 @@ def main(argv=None):
     # within the first epoch (ghost padding is exact; it costs a few per cent of extra rows)
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=(32, 1024), promote=0.08,
                       per_crystal_keys=args.per_crystal_keys)
-    predictor = Predictor(model, bucket=(32, 1024))
+    predictor = Predictor(model, bucket=(32, 1024), per_crystal_keys=args.eval_per_crystal > 0)
+    run_test = _tester(args, predictor, ds)
     best, history = float("inf"), []
     for epoch in range(args.epochs):
         model.train()
@@ -95,15 +101,24 @@ def main(argv=None):
         loss = float(torch.stack(losses).mean())                  # one host read per epoch
         dt = time.perf_counter() - t0
         history.append(loss)
-        rmse, mse, mae, r2v = evaluate.test_phonon(predictor, ds["valid"].batches(args.batch_size))
+        rmse, mse, mae, r2v = run_test("valid")
         print(f"[epoch {epoch + 1}/{args.epochs}] loss {loss:.4f} | {seen / dt:8.0f} crystals/s | "
               f"valid rmse {rmse:.4f} mse {mse:.4f} mae {mae:.4f} r2 {r2v:.4f}")
         if rmse < best:
             best = rmse
             checkpoint.save(args.out, model, trainer)
-            t = evaluate.test_phonon(predictor, ds["test"].batches(args.batch_size))
+            t = run_test("test")
             print(f"            test rmse {t[0]:.4f} mse {t[1]:.4f} mae {t[2]:.4f} r2 {t[3]:.4f}   (saved {args.out})")
     return {"best_valid_rmse": best, "train_loss": history}
+
+
+def _tester(args, evaluator, ds):
+    """name of a split -> (rmse, mse, mae, r2).  --eval-per-crystal N: the reference's numbers (main_phDOS.py:52-55 evaluates at
+    batch size 1) from passes of N crystals through a predictor with per-crystal keys; otherwise test_phonon over batches of
+    --batch-size, whose R2 and means are those of the batches."""
+    if args.eval_per_crystal > 0:
+        return lambda name: evaluate.test_per_crystal(evaluator, ds[name], batch_size=args.eval_per_crystal).as_reference()
+    return lambda name: evaluate.test_phonon(evaluator, ds[name].batches(args.batch_size))
 
 
 def train_float64(args, ds, dev):
@@ -154,7 +169,8 @@ def train_float64_fused(args, ds, dev):
     bucket = (32, 1024)
     trainer = Trainer64(model, lr=args.lr, beta=args.beta, replay=args.replay, bucket=bucket if args.replay else None,
                         promote=0.08 if args.replay else 0.0)
-    evaluator = Predictor64(model, bucket=bucket) if args.replay else model
+    evaluator = Predictor64(model, bucket=bucket) if args.replay else model       # (the module's per-crystal keys are on)
+    run_test = _tester(args, evaluator, ds)
     train = ds["train"]
     n_max = int(train.n_nodes.max())
     best, history = float("inf"), []
@@ -169,7 +185,7 @@ def train_float64_fused(args, ds, dev):
         loss = float(torch.stack(losses).mean())                  # one host read per epoch
         dt = time.perf_counter() - t0
         history.append(loss)
-        rmse, mse, mae, r2v = evaluate.test_phonon(evaluator, ds["valid"].batches(args.batch_size))
+        rmse, mse, mae, r2v = run_test("valid")
         print(f"[epoch {epoch + 1}/{args.epochs}] loss {loss:.4f} | {seen / dt:8.0f} crystals/s | "
               f"valid rmse {rmse:.4f} mse {mse:.4f} mae {mae:.4f} r2 {r2v:.4f}"
               + (f" | slots {trainer.slot_misses} recorded, {trainer.slot_hits} replayed ({trainer.slot_promoted} promoted)"
@@ -177,7 +193,7 @@ def train_float64_fused(args, ds, dev):
         if rmse < best:
             best = rmse
             checkpoint.save(args.out, model, trainer)
-            t = evaluate.test_phonon(evaluator, ds["test"].batches(args.batch_size))
+            t = run_test("test")
             print(f"            test rmse {t[0]:.4f} mse {t[1]:.4f} mae {t[2]:.4f} r2 {t[3]:.4f}   (saved {args.out})")
     return {"best_valid_rmse": best, "train_loss": history}
 

@@ -1184,6 +1184,23 @@ int dosx_loss_phonon_f64(const double* pg, const double* ps, const double* y, do
 int dosx_adamw_f64(double* p, const double* g, double* m, double* v, int64_t n, double lr, double beta1, double beta2,
                    double eps, double weight_decay, int step, dosx_stream_t stream);
 
+/* ---- evaluation metrics (csrc/eval.hip) -----------------------------------------------------------------------------------
+ * utils.py:76-89 / :127-139 evaluated one crystal at a time (what the reference computes at batch_size = 1).
+ * pred, y: [B,S] rows with unit inner stride, rows S apart.  clamp0 != 0: both are clamped at 0 first (utils.py:74-76).
+ * metrics [B,4] = rmse, mse, mae, r2 of each row, accumulated in float64:
+ *   mse = sum (y-p)^2 / S,  rmse = sqrt(mse),  mae = sum |p-y| / S,
+ *   r2 = 1 - sum (y-p)^2 / sum (y - mean(y))^2   (mean first, then the squares: two passes, no E[y^2]-E[y]^2)
+ * r2 of a row with a constant target is what IEEE division gives (-inf, or NaN when the error is 0 too), like evaluate.r2 on
+ * that row - as far as the row's mean is exact in float64 (sum / S of S equal numbers is, when the partial sums are).
+ * pred_out / y_out: NULL, or [B,S] rows that receive the (clamped) values - the preds / y that utils.test concatenates; they may
+ * be pred / y themselves, not each other's input.
+ * One wavefront per row, every sum in a fixed order that depends on S alone: a row's result does not depend on B or on where
+ * the row stands in the launch.  B = 0 is a no-op; S < 1, B < 0 and NULL pred / y / metrics are refused with -22 and a message. */
+int dosx_eval_metrics(const float* pred, const float* y, int B, int S, int clamp0, double* metrics, float* pred_out, float* y_out,
+                      dosx_stream_t stream);
+int dosx_eval_metrics_f64(const double* pred, const double* y, int B, int S, int clamp0, double* metrics, double* pred_out,
+                          double* y_out, dosx_stream_t stream);
+
 const char* dosx_last_error(void);
 int dosx_version(void);
 
