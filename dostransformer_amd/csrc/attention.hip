@@ -1330,14 +1330,9 @@ size_t dkv_smem(const Geo& g, int kg) {
   return sizeof(float) * (stage > epi ? stage : epi);
 }
 
-inline int attn_nj3() {               // DOSX_ATTN_NJ3=0: the 33-48-key shapes on the 64-entry row phases again (A/B)
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DOSX_ATTN_NJ3");
-    v = (e && atoi(e) == 0) ? 4 : 3;
-  }
-  return v;
-}
+// NJ = keys per lane of the row phases, in units of 16.  3: 33-48 keys - the 41-key Electron-DOS cross attention - runs
+// the softmax phases on 48 instead of 64 entries per row; the MFMA tiles stay 32 keys wide
+inline int attn_nj(int Nk) { return Nk <= 16 ? 1 : (Nk <= 48 ? 3 : (Nk <= 64 ? 4 : (Nk <= 208 ? 13 : 20))); }
 
 constexpr int MAX_FUSED_NK = 320;      // the score row of a query lives in LDS
 
@@ -1378,9 +1373,7 @@ extern "C" int dosx_attention_fwd(const DosxAttn* ap, dosx_stream_t stream) {
   const size_t smem = fwd_smem(g, res);
   DOSX_CHECK_ARG(smem <= 160 * 1024, "dosx_attention_fwd: LDS need %zu > 160 KiB", smem);
   const dim3 grid(ceil_div(a.Sq, QT), a.Bq);
-  // (NJ = keys per lane of the row phases, in units of 16.  3: 33-48 keys - the 41-key Electron-DOS cross attention - runs
-  //  the softmax phases on 48 instead of 64 entries per row; the MFMA tiles stay 32 keys wide)
-  const int nj = a.Nk <= 16 ? 1 : (a.Nk <= 48 ? attn_nj3() : (a.Nk <= 64 ? 4 : (a.Nk <= 208 ? 13 : 20)));
+  const int nj = attn_nj(a.Nk);
   const bool kp = a.key_ptr != nullptr;          // per-crystal key counts: the KP instantiations
 #define DOSX_FWDS1(NJ_, RES_, KP_)                                                                          \
   do {                                                                                                      \
@@ -1438,7 +1431,7 @@ extern "C" int dosx_attention_bwd(const DosxAttn* ap, dosx_stream_t stream) {
   const dim3 grid(ceil_div(a.Sq, QT), a.Bq);
   const bool kp = a.key_ptr != nullptr;          // per-crystal key counts: the KP instantiations
   if (!(a.flags & DOSX_ATTN_BWD_DKV_HALF)) {
-    const int nj = a.Nk <= 16 ? 1 : (a.Nk <= 48 ? attn_nj3() : (a.Nk <= 64 ? 4 : (a.Nk <= 208 ? 13 : 20)));
+    const int nj = attn_nj(a.Nk);
 #define DOSX_DQS1(NJ_, PKV_, RES_, KP_)                                                                     \
   do {                                                                                                      \
     static bool attr_dq = false;                                                                            \

@@ -717,19 +717,12 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
   ASTAMP(63);
 }
 
-int g_al_mode = -1;
-inline int al_mode() {
-  // DOSX_ATTN_ALIGNED: 0 = never, 1 = hidden > 128 only, 2 = every shape these kernels take (default: faster than attention.hip's
-  // at every BASELINE shape with <= 64 keys, profiles/r05_kernel_microbench.log `attn`)
-  if (g_al_mode < 0) {
-    const char* e = getenv("DOSX_ATTN_ALIGNED");
-    g_al_mode = e ? atoi(e) : 2;
-  }
-  return g_al_mode;
-}
+// which shapes take these kernels (dosx_attention_aligned_mode): 0 = none, 1 = hidden > 128 only, 2 = every shape they cover
+// (the default: faster than attention.hip's at every BASELINE shape with <= 64 keys, profiles/r05_kernel_microbench.log `attn`)
+int g_al_mode = 2;
 
 inline bool al_shape_ok(const DosxAttn& a) {
-  const int m = al_mode();
+  const int m = g_al_mode;
   return m > 0 && a.flags == 0 && a.Nk >= 1 && a.Nk <= 64 && (a.H == 64 || a.H == 128 || a.H == 256) && (m > 1 || a.H > 128) &&
          a.qstats != nullptr;
 }
@@ -824,7 +817,7 @@ int attn_aligned_bwd(const DosxAttn& a, hipStream_t st) {
 }  // namespace dosx_detail
 
 extern "C" int dosx_attention_aligned_mode(int mode) {
-  const int prev = al_mode();
+  const int prev = g_al_mode;
   if (mode >= 0) g_al_mode = mode > 2 ? 2 : mode;
   return prev;
 }

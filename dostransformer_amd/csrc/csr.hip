@@ -556,9 +556,7 @@ extern "C" int dosx_collate_padded(const DosxCollate* dp, dosx_stream_t stream) 
   if (d.seg_tile) {
     DOSX_CHECK_ARG(d.T > 0 && d.tile_rows > 0 && d.out_tile_ptr && d.tile_off_all && d.tile_e_all && d.tile_n_all && d.tile_p_all,
                    "dosx_collate_padded: seg_tile needs T, tile_rows and the per-crystal tile tables");
-    static int greedy = -1;
-    if (greedy < 0) { const char* e = getenv("DOSX_COLLATE_GREEDY_TILES"); greedy = e ? atoi(e) : 1; }
-    if (greedy && d.N <= GT_MAXN) {
+    if (d.N <= GT_MAXN) {          // greedy tiles over the whole batch; beyond the kernel's LDS table, crystal-aligned tiles
       const size_t smem = sizeof(int) * 4 * (size_t)(d.N + 1);
       static bool attr_set = false;
       if (!attr_set) {

@@ -1494,14 +1494,16 @@ static size_t ffn_att_bwd_floats(int H, int Nk, int R) {
   return m > red ? m : red;
 }
 
-static int ffn_bwd_att_rows(int Sq, int Bq);
+// ---- host launch policy: the settled constants (to re-run an experiment, edit one and load the build through DOSX_LIB) ----
+constexpr int FFN_HALF_MAX_WG = 128;   // grids of up to this many 32-row workgroups run as 16-row ones: half a round either way, so halve its latency
 
-static int ffn_chunk(int H) {
-  static int forced = -1;
-  if (forced < 0) { const char* e = getenv("DOSX_FFN_KB"); forced = e ? atoi(e) : 0; }
-  if (forced == 32) return 32;
-  return (H % 64) == 0 ? 64 : 32;
-}
+// k-chunk of the weight tiles: 64 wide halves the barriers per tile where the hidden width allows it
+static int ffn_chunk(int H) { return (H % 64) == 0 ? 64 : 32; }
+
+static bool ffn_bwd_half(int M) { return ceil_div(M, 32) <= FFN_HALF_MAX_WG; }
+
+// rows per workgroup of the crystal-aligned launches (DosxFfn.att_aligned, DosxFfnBwd.att_*): 16 while the 32-row grid is at most half a round
+static int ffn_bwd_att_rows(int Sq, int Bq) { return Bq * ceil_div(Sq, 32) <= FFN_HALF_MAX_WG ? 16 : 32; }
 
 extern "C" int dosx_ffn_supported(int H) { return (H % 32) == 0 && H >= 32 && H <= 128; }
 extern "C" int dosx_ffn_att_supported(int H, int Nk) { return dosx_ffn_supported(H) && Nk >= 1 && Nk <= 16; }
@@ -1530,10 +1532,8 @@ static int ffn_fwd_prepare(const DosxFfn& a, FfnPlan& pl) {
   const long long span = (const char*)a.w1 > (const char*)a.w2 ? (const char*)a.w1 - (const char*)a.w2 : (const char*)a.w2 - (const char*)a.w1;
   DOSX_CHECK_ARG(span + (long long)16 * a.H * a.H < 0x7fffffffLL, "dosx_ffn_fwd: fc1 / fc2 weights more than 2 GiB apart");
   const int H = a.H, H4 = 4 * H;
-  static int half_max = -1;
-  if (half_max < 0) { const char* e = getenv("DOSX_FFN_HALF_MAX"); half_max = e ? atoi(e) : 128; }
   const bool aligned = att && a.att_aligned != 0;        // crystal-aligned tiles (ATT = 2): grid = Bq x ceil(Sq / R)
-  pl.half = aligned ? ffn_bwd_att_rows(a.att_Sq, a.att_Bq) == 16 : ceil_div(a.M, 32) <= half_max;   // 16-row workgroups while the 32-row grid is one partial round
+  pl.half = aligned ? ffn_bwd_att_rows(a.att_Sq, a.att_Bq) == 16 : ffn_bwd_half(a.M);   // 16-row workgroups while the 32-row grid is one partial round
   const int R = pl.half ? 16 : 32;
   pl.kb = ffn_chunk(H);
   pl.mode = aligned ? 2 : (att ? 1 : 0);
@@ -1628,20 +1628,8 @@ extern "C" int dosx_ffn_fwd_multi(const DosxFfn* descs, int n, dosx_stream_t str
   return 0;
 }
 
-static int ffn_bwd_half(int M) {
-  static int half_max = -1;
-  if (half_max < 0) { const char* e = getenv("DOSX_FFN_HALF_MAX"); half_max = e ? atoi(e) : 128; }
-  return ceil_div(M, 32) <= half_max;
-}
-
 extern "C" int dosx_ffn_bwd_partial_rows(int M) { return M <= 0 ? 0 : ceil_div(M, ffn_bwd_half(M) ? 16 : 32); }
 
-// rows per workgroup of the crystal-aligned backward launch (DosxFfnBwd.att_*): 16 while the 32-row grid is at most half a round
-static int ffn_bwd_att_rows(int Sq, int Bq) {
-  static int half_max = -1;
-  if (half_max < 0) { const char* e = getenv("DOSX_FFN_HALF_MAX"); half_max = e ? atoi(e) : 128; }
-  return Bq * ceil_div(Sq, 32) <= half_max ? 16 : 32;
-}
 // whether dosx_ffn_bwd takes the att_* fields for this shape: hidden 64 / 128 (64-wide weight chunks), <= 64 keys, and the
 // attention tiles fit the launch's LDS;  *_partial_rows: workgroups = partial rows of such a launch
 extern "C" int dosx_ffn_att_bwd_supported(int H, int Nk, int Sq, int Bq) {

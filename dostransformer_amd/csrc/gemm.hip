@@ -1250,16 +1250,16 @@ int seg_vec_ok(const DosxSeg* segs, int nseg) {
   return 1;
 }
 
-int gemm_bn(int M, int N, int epi) {
+// ---- host tile policy: the settled constants (to re-run an experiment, edit one and load the build through DOSX_LIB) ----
+constexpr int GEMM_HALF_MAX_WG = 128;      // grids of up to this many 32-row workgroups run as 16-row tiles: one partial round either way, so halve its latency
+constexpr int GEMM_SPLIT_MAX_TAIL_WG = 160;  // a tail of more workgroups than this fills most of a round: splitting it off buys nothing
+constexpr int WGRAD_NT2_MIN_ROWS = 16384;  // 128 x 64 weight-gradient tiles from this many rows: 25 % fewer L2 bytes per flop against half as many workgroups
+constexpr int WGRAD_MAX_SPLIT = 8;         // M-splits of a weight-gradient tile: partial tiles the last arriver reads back against ~12 k clk fixed cost per workgroup
+
+// column tile: 128 unless the epilogue needs the whole row in one workgroup
+int gemm_bn(int N, int epi) {
   const bool full_row = (epi == DOSX_EPI_LN || epi == DOSX_EPI_PRELU_LN_BWD || epi == DOSX_EPI_ROWLN_BWD || epi == DOSX_EPI_PRELU_LN_BWD_SEG);
   if (full_row) return N <= 128 ? 128 : (N <= 256 ? 256 : 512);
-  static int forced = -1;
-  if (forced < 0) {
-    const char* e = getenv("DOSX_GEMM_BN");
-    forced = e ? atoi(e) : 0;
-  }
-  if (forced == 128 || forced == 256 || forced == 512) return N >= forced ? forced : 128;
-  (void)M;
   return 128;
 }
 
@@ -1269,74 +1269,49 @@ int gemm_bn(int M, int N, int epi) {
 // resource, see gemm_kernel) but also halve the number of workgroups: use them when the grid still
 // fills the 256 CUs, or when the 32-row grid would run a nearly empty second round.
 inline int gemm_rt(int M, int N, int epi) {
-  static int forced = -2, half_max = -1, ht3 = 1;
-  if (forced == -2) {
-    const char* e = getenv("DOSX_GEMM_RT");
-    forced = e ? atoi(e) : -1;
-    const char* h = getenv("DOSX_GEMM_HALF_MAX");
-    half_max = h ? atoi(h) : 128;
-    const char* t = getenv("DOSX_GEMM_HT3");
-    ht3 = t ? atoi(t) : 1;
-  }
   if (M <= 16) return 0;
-  if (forced >= 0 && forced <= 3 && !(forced >= 2 && gemm_bn(M, N, epi) == 512)) return M <= BM && forced >= 2 ? 1 : forced;
-  const int ntiles = ceil_div(N, gemm_bn(M, N, epi));
+  const int bn = gemm_bn(N, epi), ntiles = ceil_div(N, bn);
   const int wg1 = ceil_div(M, BM) * ntiles, wg2 = ceil_div(M, 2 * BM) * ntiles;
   // HALF (16-row) tiles: a kernel this small is one partial round of workgroups whichever way it is cut, so its
   // duration is one workgroup's latency - halve that
-  if (wg1 <= half_max) return 0;
+  if (wg1 <= GEMM_HALF_MAX_WG) return 0;
   if (M <= BM) return 1;
-  if (gemm_bn(M, N, epi) == 512) return 1;
+  if (bn == 512) return 1;
   // one column tile, more 32-row blocks than CUs: 48-row workgroups (three 16-row sub-tiles) if those fit one round -
   // the busiest CU then holds 48 rows instead of 64 (M = 9000: 188 workgroups instead of 282 / 141)
-  if (ht3 && ntiles == 1 && wg1 > 256 && ceil_div(M, 48) <= 256) return 3;
+  if (ntiles == 1 && wg1 > 256 && ceil_div(M, 48) <= 256) return 3;
   if (wg2 >= 192) return 2;
   if (wg1 > 256 && wg1 <= 400 && wg2 >= 128) return 2;
   return 1;
 }
 
-// TAIL SPLIT (round 4).  A grid of W workgroups on 256 CUs runs ceil(W / 256) rounds: 804 tiles of 64 x 128 (the Electron-DOS
+// TAIL SPLIT.  A grid of W workgroups on 256 CUs runs ceil(W / 256) rounds: 804 tiles of 64 x 128 (the Electron-DOS
 // feed-forward GEMMs, M = 25728) take 4 rounds where 3.14 would do - measured 137.0 us against 99.5 us for M = 24576 (768 tiles:
-// 3 full rounds), i.e. 37 us for the last 4.7 % of the rows (profiles/r04_ab_gemm_tiles.log).  Such a call becomes TWO launches:
-// the rows of the full rounds with the large tile, then the remaining rows as their own small problem under the normal tile
-// policy (16- / 32- / 48-row tiles: one short round).  Returns the first row of the tail (0 = no split).
-// RESULT of the first form - TWO launches, the tail behind the full rounds - (profiles/r04_ab_gemm_split.log): a tile of a quarter of the rows is NOT a quarter of the time - its k-loop is the same
-// 32 chunks of barrier + weight-tile staging - so the 1152-row tail takes 26 us instead of 37 (fc2 forward 137.7 -> 126.5 us,
-// fc1 input gradient 130.8 -> 120.4), the M = 12864 calls lose (65.9 -> 74.0 us) and the Electron-DOS step is 1.8 % SLOWER
-// (7.54 -> 7.67 ms, four interleaved pairs), configs[4]'s shard 3.7 %.  SECOND form (shipped): the same split in ONE launch -
-// gemm_mixed_kernel, the tail's 32- / 48-row tiles at the end of the grid, no launch boundary in between: the same kernel
-// times (fc2 forward 138.9 -> 126.5 us, fc1 input gradient 129.9 -> 119.5), and the steps no longer lose: Electron-DOS
-// 7.40 ms either way (its forward tails already run as a concurrent chain), configs[4]'s shard 7.28 -> 7.23 ms
-// (profiles/r04_ab_gemm_mixed.log).  DOSX_GEMM_SPLIT=0 switches it off.
+// 3 full rounds), i.e. 37 us for the last 4.7 % of the rows (profiles/r04_ab_gemm_tiles.log).  Such a call runs the rows of the
+// full rounds with the large tile and the remaining rows as 32- / 48-row tiles at the end of the SAME grid (gemm_mixed_kernel):
+// fc2 forward 138.9 -> 126.5 us, fc1 input gradient 129.9 -> 119.5 us (profiles/r04_ab_gemm_mixed.log).  The two-launch form
+// lost per step: DESIGN.md 5.1.  Returns the first row of the tail (0 = no split).
 inline int gemm_tail_split(int M, int N, int epi) {
-  static int on = -1, max_tail = 160;
-  if (on < 0) {
-    const char* e = getenv("DOSX_GEMM_SPLIT");
-    on = e ? atoi(e) : 1;          // (the one-launch mixed-height form; the two-launch form lost 2-4 % per step)
-    const char* t = getenv("DOSX_GEMM_SPLIT_MAXTAIL");
-    if (t) max_tail = atoi(t);
-  }
   // (the mixed-height kernel exists for the plain / ReLU-mask epilogues on 128-column tiles and for the LayerNorm-backward
   //  epilogue on one 256-column tile: the feed-forward GEMMs of a hidden-256 model and the plain large GEMMs around them)
-  if (!on) return 0;
-  const int bn_ = gemm_bn(M, N, epi);
+  const int bn_ = gemm_bn(N, epi);
   if (bn_ == 512 && (epi == DOSX_EPI_LN || epi == DOSX_EPI_PRELU_LN_BWD) && gemm_rt(M, N, epi) == 1) {
     // Round 5: the 512-column row-epilogue GEMMs of the hidden-256 message passing (E = 17880 edge rows: 559 tiles of 32 rows, one
     // workgroup per CU = 2.18 rounds run as 3 - 64.9 us against 49.8 at E = 16384, 81.1 / 61.3 with the PReLU-LayerNorm-backward
     // epilogue; the 32-crystal shard: 42.8 against 23.9 us, tools/exp/r5_quant512.py): the rows of the full rounds as 32-row tiles,
     // the rest as 16-row tiles (16 x 16 x 4 MFMA) behind them in the same grid
     const int full = M / (256 * BM), tail_wg = ceil_div(M - full * 256 * BM, BM);
-    if (full < 1 || tail_wg == 0 || tail_wg > max_tail) return 0;
+    if (full < 1 || tail_wg == 0 || tail_wg > GEMM_SPLIT_MAX_TAIL_WG) return 0;
     return full * 256 * BM;
   }
   if (!((bn_ == 128 && (epi == DOSX_EPI_BIAS_ACT || epi == DOSX_EPI_RELU_MASK)) || (bn_ == 256 && epi == DOSX_EPI_ROWLN_BWD))) return 0;
   if (gemm_rt(M, N, epi) != 2) return 0;                   // the large-problem regime only (64-row tiles)
-  const int gy = ceil_div(N, gemm_bn(M, N, epi));
+  const int gy = ceil_div(N, bn_);
   if (256 % gy) return 0;
   const int rows_round = 256 / gy * 2 * BM;                // rows of one full round of 64-row tiles
   const int full = M / rows_round;
   const int tail_wg = ceil_div(M - full * rows_round, 2 * BM) * gy;
-  if (full < 1 || tail_wg == 0 || tail_wg > max_tail) return 0;
+  if (full < 1 || tail_wg == 0 || tail_wg > GEMM_SPLIT_MAX_TAIL_WG) return 0;
   return full * rows_round;
 }
 
@@ -1363,7 +1338,7 @@ static int gemm_plan(const DosxGemm& g, GemmLaunch& L) {
     L.vecA = L.vecA && aligned16(g.pro_gamma) && aligned16(g.pro_beta);
   L.vecW = ((g.ldw & 3) == 0) && aligned16(g.w) && (g.w_layout == 0 ? (g.K & 3) == 0 : (g.N & 3) == 0);
   L.rt = gemm_rt(g.M, g.N, g.epi);
-  int bn = gemm_bn(g.M, g.N, g.epi);
+  int bn = gemm_bn(g.N, g.epi);
   if ((g.stats_out || g.norm_out) && bn < g.N) bn = g.N <= 256 ? 256 : 512;
   if (bn == 512 && L.rt >= 2) L.rt = 1;
   if (g.epi == DOSX_EPI_SEGSUM || g.epi == DOSX_EPI_PRELU_LN_BWD_SEG) {          // node-aligned 48-row tiles, one column tile
@@ -1375,7 +1350,7 @@ static int gemm_plan(const DosxGemm& g, GemmLaunch& L) {
 
 // ---- vector-ALU "sliver" GEMM (round 4) ----------------------------------------------------------------------------------
 // C[M,N] = A[M,K] . W[K,N] (+ R[M,N]) for the SMALL plain dgrad GEMMs of the backward pass (w_layout 1, no prologue, no
-// bias / activation; up to DOSX_SLIVER_MAX_GF GF - an experiment, OFF by default): 256 threads = 16 x 16, a 64 x 64 output tile, 4 x 4 per thread, k-chunks of 16
+// bias / activation; up to dosx_set_sliver_max_gf GF - an experiment, OFF by default): 256 threads = 16 x 16, a 64 x 64 output tile, 4 x 4 per thread, k-chunks of 16
 // through 8.5 KB of LDS (A chunk stored k-major), the next chunk prefetched into registers, PACKED fp32 FMAs on the vector ALU
 // (v_pk_fma_f32: the same 157 TF/s peak as the fp32 MFMA), raised wave priority.  Why: these kernels run while a
 // weight-gradient group owns the chip - two workgroups of 8 waves / 107 VGPRs / 75 KB of LDS per CU, their matrix waves
@@ -1435,16 +1410,12 @@ __global__ __launch_bounds__(256) void sliver_gemm_kernel(const DosxGemm g) {
 }
 
 // which calls take the sliver kernel (host side): plain dgrad GEMMs small enough that latency under a weight-gradient group,
-// not throughput, is what they cost.  DOSX_SLIVER_MAX_GF / dosx_set_sliver_max_gf: the flop limit in GF; DEFAULT 0 = never.
+// not throughput, is what they cost.  dosx_set_sliver_max_gf: the flop limit in GF; DEFAULT 0 = never.
 // Measured in the step (tools/exp/ab_sliver*.sh, tools/exp/sliver_sites.sh): the routed kernels do get faster
 // (Electron-DOS: the head dgrads 237 -> 101 us, the node-MLP dgrad 99 -> 65 us) but the kernels BEHIND them then wait longer
 // for the same weight-gradient group - the step moves by -0.2 .. -0.4 % (Electron-DOS) and by +-1 % box-to-box noise (Phonon-DOS).
-static double g_sliver_max_flop = -1.0;
+static double g_sliver_max_flop = 0.0;
 static bool sliver_ok(const DosxGemm& g) {
-  if (g_sliver_max_flop < 0.0) {
-    const char* e = getenv("DOSX_SLIVER_MAX_GF");
-    g_sliver_max_flop = (e ? atof(e) : 0.0) * 1e9;
-  }
   const double max_flop = g_sliver_max_flop;
   if (max_flop <= 0.0 || 2.0 * g.M * (double)g.N * g.K > max_flop) return false;
   const bool ident_out = g.out_map.d >= (1 << 30) && g.out_map.idx == nullptr && g.out_map.c == 1 && g.out_map.off == 0;
@@ -1645,12 +1616,7 @@ static int launch_gemm_pair(const GemmLaunch& A, const GemmLaunch& B, hipStream_
 extern "C" int dosx_gemm_pair(const DosxGemm* ap, const DosxGemm* bp, dosx_stream_t stream) {
   DOSX_CHECK_ARG(ap != nullptr && bp != nullptr, "dosx_gemm_pair: null descriptor");
   const DosxGemm &a = *ap, &b = *bp;
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("DOSX_GEMM_PAIR");
-    on = e ? atoi(e) : 1;
-  }
-  bool one = on && a.M > 0 && b.M > 0 && a.N == b.N && a.N > 0 && a.w_layout == 0 && b.w_layout == 0 && a.pro == DOSX_PRO_NONE &&
+  bool one = a.M > 0 && b.M > 0 && a.N == b.N && a.N > 0 && a.w_layout == 0 && b.w_layout == 0 && a.pro == DOSX_PRO_NONE &&
              b.pro == DOSX_PRO_NONE && a.epi == DOSX_EPI_BIAS_ACT && b.epi == DOSX_EPI_BIAS_ACT && !sliver_ok(a) && !sliver_ok(b);
   GemmLaunch A, B;
   int bn = 0;
@@ -1660,7 +1626,7 @@ extern "C" int dosx_gemm_pair(const DosxGemm* ap, const DosxGemm* bp, dosx_strea
     bn = gemm_plan(a, A);
     one = gemm_plan(b, B) == bn && bn <= 256 && A.vecA && A.vecW && B.vecA && B.vecW;
   }
-  if (!one && on && a.M > 0 && b.M > 0 && a.N == b.N && a.N == 128 && a.w_layout == 1 && b.w_layout == 1 && a.pro == DOSX_PRO_NONE &&
+  if (!one && a.M > 0 && b.M > 0 && a.N == b.N && a.N == 128 && a.w_layout == 1 && b.w_layout == 1 && a.pro == DOSX_PRO_NONE &&
       b.pro == DOSX_PRO_NONE && a.epi == DOSX_EPI_PRELU_BWD && b.epi == DOSX_EPI_PRELU_BWD && !sliver_ok(a) && !sliver_ok(b)) {
     // The two encoders' backward (node rows: 16-row tiles; edge rows: 48-row tiles) at the tail of the step: each problem at
     // ITS tile height in one grid (gemm_mixed_kernel with two independent descriptors; partial rows numbered per problem)
@@ -2175,7 +2141,6 @@ struct WgradGroup {
   DosxReduceJob rjob[WG_MAX_RJOBS];
   int rfirst[WG_MAX_RJOBS + 1];
   int nr;
-  int block_off;     // this launch covers the blocks [block_off, block_off + gridDim.x) of the group (dosx_grad_flush: rounds)
 };
 static_assert(sizeof(WgradGroup) <= 4064, "WgradGroup must fit the kernel argument segment");
 
@@ -2191,7 +2156,7 @@ __global__ __launch_bounds__(512, DOSX_WGRAD_OCC) void wgrad_grouped_kernel(cons
   // the job table is read where it lies, in the kernel-argument segment (scalar loads through a constant-address-space
   // pointer): indexing the by-value parameter with a run-time index made hipcc copy the whole 4 KB table to scratch
   const WgradGroup& G = *(const WgradGroup*)__builtin_amdgcn_kernarg_segment_ptr();
-  const int bx = (int)blockIdx.x + G.block_off;
+  const int bx = (int)blockIdx.x;
   if (bx >= G.first_block[G.n]) {
     // ---- a reduction block: 2 slices of 256 elements (one per half of the workgroup) ----
     const int rb = bx - G.first_block[G.n];
@@ -2296,15 +2261,7 @@ namespace {
 // eDOS H = 256 (M = 17880 / 25728) 8.29-8.38 -> 8.16-8.20 ms per step, the grouped launches 418 -> 398 us; the Phonon-DOS
 // step (M <= 9344: 35 chunks per workgroup at 8 splits) is 0.5 % SLOWER with them - half as many workgroups of twice the
 // length leave more of the 512 slots idle at the end of a group than the 25 % fewer L2 bytes per flop give back.
-int wgrad_nt(int M, int N) {
-  static int force = -1;
-  if (force < 0) {
-    const char* e = getenv("DOSX_WGRAD_NT");       // 1 / 2: every job that can (tests, tools/exp/ab_nt*.sh)
-    force = e ? atoi(e) : 0;
-  }
-  if (N < 2 * WT || force == 1) return 1;
-  return (force == 2 || M >= 16384) ? 2 : 1;
-}
+int wgrad_nt(int M, int N) { return N < 2 * WT ? 1 : (M >= WGRAD_NT2_MIN_ROWS ? 2 : 1); }
 }  // namespace
 
 extern "C" int dosx_wgrad_splits(int M, int N, int K) {
@@ -2313,37 +2270,20 @@ extern "C" int dosx_wgrad_splits(int M, int N, int K) {
   int s = ceil_div(512, tiles);
   const int cap = ceil_div(M, 128);
   if (s > cap) s = cap;
-  static int max_split = 0;
-  if (max_split == 0) {
-    const char* e = getenv("DOSX_WGRAD_MAXSPLIT");
-    // 8 (round 3, finished mode): half the partial tiles the last arriver has to read back, workgroups twice as long
-    // against ~12k clk of fixed prologue + publish cost each: GNN-layer-pair group alone 76 -> 69 us, encoder-stack group
-    // 54 -> 47 us, step 1.277 -> 1.271 ms (16 was the optimum of round 2's slab + reduce_partials scheme)
-    max_split = e ? atoi(e) : 8;
-    if (max_split < 1) max_split = 8;
-  }
-  // The cap scales with M (round 4): 8 is the optimum where it was tuned - the BASELINE shapes, M <= 25728 rows, whose jobs
+  // WGRAD_MAX_SPLIT = 8 (finished mode): half the partial tiles the last arriver has to read back, workgroups twice as long
+  // against ~12k clk of fixed prologue + publish cost each: GNN-layer-pair group alone 76 -> 69 us, encoder-stack group
+  // 54 -> 47 us, step 1.277 -> 1.271 ms (16 was the optimum of the earlier slab + reduce_partials scheme).
+  // The cap scales with M: 8 is the optimum where it was tuned - the BASELINE shapes, M <= 25728 rows, whose jobs
   // run in groups that fill the chip together - but a LONG job (M > 32768) with few tiles is a grid of tiles x 8 <= 128-192
   // workgroups on 256 CUs whatever its length (M = 262144, N = 512, K = 128: 17.5 % of the MFMA peak).  Every workgroup keeps
   // at least 4096 rows (128 chunks of MFMAs against its ~12 k clk of fixed cost), up to the 64 partial tiles a counter /
   // scratch slot set is laid out for; the last arriver of a tile then sums up to 64 partials, 8 loads in flight at a time.
+  // (A cap on a workgroup's lifetime in chunks was measured and rejected: DESIGN.md 5.1.)
   int cap_m = M / 4096;
   if (cap_m > 64) cap_m = 64;
-  if (s > (max_split > cap_m ? max_split : cap_m)) s = max_split > cap_m ? max_split : cap_m;
-  // ... but no workgroup lives longer than max_chunks 32-row chunks: a weight-gradient workgroup cannot be pre-empted, and a
-  // kernel of the dgrad chain that arrives while long-lived ones hold the CUs waits for them (eDOS, M = 25728 rows at 8
-  // splits: 100 chunks = ~70 us per workgroup; the two 15-us head dgrad GEMMs behind the self encoder took 228 us each)
-  static int max_chunks = -1;
-  if (max_chunks < 0) {
-    const char* e = getenv("DOSX_WGRAD_MAXCHUNKS");
-    max_chunks = e ? atoi(e) : 0;
-  }
-  if (max_chunks > 0) {
-    const int need = ceil_div(M, BM * max_chunks);
-    if (s < need) s = need < 64 ? need : 64;
-  }
-  if (s < 1) s = 1;
-  return s;
+  const int max_split = WGRAD_MAX_SPLIT > cap_m ? WGRAD_MAX_SPLIT : cap_m;
+  if (s > max_split) s = max_split;
+  return s < 1 ? 1 : s;
 }
 
 extern "C" int dosx_wgrad_tiles(int N, int K) { return ceil_div(N, WT) * ceil_div(K, WT); }
@@ -2488,29 +2428,9 @@ extern "C" int dosx_grad_flush(const DosxWgrad* jobs, int n_jobs, const DosxRedu
     if (G.n == 0 && G.nr == 0) return 0;
     G.first_block[G.n] = blocks_total;
     G.rfirst[G.nr] = rblocks;
-    // DOSX_WGRAD_ROUND (round 4, default 0 = one launch per group): the group as successive launches of at most r workgroups
-    // ("auto": 512 for groups of up to 1024 workgroups, else 1024).  A kernel of the dgrad chain that arrives while a
-    // weight-gradient grid is being dispatched waits until a CU is EMPTY (its workgroups need > 100 KB of LDS / > 128 VGPRs; a
-    // freed half-CU slot is refilled at once from the weight-gradient grid's backlog); at a launch boundary the backlog is
-    // empty and CUs drain completely.  Measured (tools/exp/ab_round*.sh, profiles/r04_ab_wgrad_round.log, interleaved): "auto"
-    // takes 0.3-0.6 % off the Phonon-DOS step, 0.4-0.6 % off the Electron-DOS step, 0.9 % off its T4 / 32-crystal shard -
-    // and costs the weight-gradient kernels themselves 23 % (387 vs 314 us of kernel time per cfg2 step: every boundary is a
-    // tail of partly idle CUs), i.e. the chain gains slightly more than the groups lose.  Not worth a dominant kernel at
-    // 0.26 instead of 0.32 of its roofline: off by default.
-    static int round = -2;
-    if (round == -2) {
-      const char* e = getenv("DOSX_WGRAD_ROUND");
-      round = !e ? 0 : (e[0] == 'a' ? -1 : atoi(e));
-    }
-    const int total = blocks_total + rblocks;
-    int per = total;
-    if (round > 0) per = round;
-    else if (round < 0) per = total <= 1024 ? 512 : 1024;
-    for (int off = 0; off < total; off += per) {
-      G.block_off = off;
-      hipLaunchKernelGGL(wgrad_grouped_kernel, dim3(total - off < per ? total - off : per), dim3(512), 0, st, G);
-      DOSX_LAUNCH_CHECK();
-    }
+    // one launch per group (cutting a group into rounds of workgroups was measured and rejected: DESIGN.md 5.1)
+    hipLaunchKernelGGL(wgrad_grouped_kernel, dim3(blocks_total + rblocks), dim3(512), 0, st, G);
+    DOSX_LAUNCH_CHECK();
     G.n = 0;
     G.nr = 0;
     blocks_total = 0;

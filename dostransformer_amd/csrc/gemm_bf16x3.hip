@@ -4,18 +4,20 @@
 // and the six products whose weight is >= 2^-16 of the leading one
 //     x.w ~ hi.hi + hi.mid + mid.hi + mid.mid + hi.lo + lo.hi
 // accumulated in the MFMA's fp32 accumulators (the dropped terms are <= 2^-24 |x||w| per product: the size of ONE fp32 rounding
-// of that product).  NOT the product path: the training / inference programs run the exact-fp32 kernels of gemm.hip; this kernel
-// is measured next to them (bench.py `secondary.split_bf16`, tools/bench_kernels.py --what bf16x3) and checked against float64 at
-// the SAME tolerance as dosx_gemm (tests/test_gpu_gemm.py).
+// of that product).  OPT-IN in the product: with DOSX_FFN_BF16X3=1 functional.encoder_fwd / encoder_bwd run the plain feed-forward
+// GEMMs (fc1 forward, fc2 forward, fc2's ReLU-masked input gradient) through this kernel; by default the programs run the exact-fp32
+// kernels of gemm.hip.  Measured next to them (bench.py `secondary.split_bf16`, tools/bench_kernels.py --what bf16x3)
+// and checked against float64 at the SAME tolerance as dosx_gemm (tests/test_gpu_gemm.py).
 //
 // The split happens ON THE FLY in the staging path (global fp32 -> registers -> 3 x v_cvt_pk_bf16_f32 + 2 subtractions per pair
 // -> three bf16 planes in LDS): the kernel takes the same fp32 buffers as dosx_gemm, HBM / L2 traffic is that of the fp32 kernel
 // (4 bytes per element, not 6), and the vector ALU - idle next to the matrix pipe - pays for it (~3.5 lane-ops per element).
-// Workgroup = 8 waves, wave-specialised like gemm.hip: 4 matrix waves (tile 128 x 128, wave: 64 x 64 = 2 x 2
-// v_mfma_f32_32x32x16_bf16 tiles; per 16 k-columns 6 + 6 fragments by ds_read_b128 and 24 MFMAs = 768 cycles) + 4 staging waves
-// (loads, split, LDS writes); 32 k-columns per stage, two stages.  LDS rows are padded to 40 bf16 (80 bytes): a quarter wave's
-// 16 b128 reads then cover all 64 banks exactly once.  (First form, all four waves doing both jobs at 16 columns per stage:
-// 25 % MFMA-busy - every wave serialised reads -> MFMAs -> conversions -> barrier; tools/exp/r6_pmc_bx.sh.)
+// Workgroup = 8 waves on a 256 x 128 tile (4 waves on 128 x 128 for short k ranges), wave: 64 x 64 = 2 x 2
+// v_mfma_f32_32x32x16_bf16 tiles, 3 + 3 fragments by ds_read_b128 and 24 MFMAs per 16 k-columns.  EVERY wave stages and multiplies:
+// 16 k-columns per stage, two LDS buffers, two register sets (a stage is loaded two iterations ahead), and a wave converts the next
+// stage BETWEEN its four quadrants' MFMA groups, so that its vector-ALU work runs in the shadow of its own matrix instructions.
+// LDS rows are padded to 24 bf16 (48 bytes).  (A wave-specialised form - 4 matrix + 4 staging waves - and a first form that
+// serialised reads -> MFMAs -> conversions -> barrier in every wave, 25 % MFMA-busy, came before it; tools/exp/r6_pmc_bx.sh.)
 // Weight layouts: 0 = [N][K] (nn.Linear: forward), 1 = [K][N] (the same matrix read k-major: input gradients) - transposed while
 // it is written to LDS.
 #include "common.h"
@@ -27,6 +29,7 @@ typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 
 constexpr int BX_BN = 128, BX_BK = 16, BX_LDK = BX_BK + 8;
+constexpr int BX_TALL_MIN_K = 512;     // host policy: 256-row tiles (half the W traffic per flop) above this k range, 128-row ones (two workgroups per CU) up to it
 
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
@@ -250,9 +253,7 @@ extern "C" int dosx_gemm_bf16x3(const float* A, int lda, const float* W, int ldw
   hipStream_t s = to_stream(stream);
   // tile height: 128 rows (two workgroups per CU) while a problem's k range is short - the tile prologue and the C write of one
   // workgroup then run under the other's products; 256 rows (half the W traffic per flop) for long k ranges
-  static int force = -1;
-  if (force < 0) { const char* e = getenv("DOSX_BF16X3_BM"); force = e ? atoi(e) : 0; }
-  const bool tall = force ? force == 256 : K > 512;
+  const bool tall = K > BX_TALL_MIN_K;
   if (tall) return w_layout ? launch_bf16x3<1, 256>(A, lda, W, ldw, bias, C, ldc, M, N, K, act, res, ldres, mask, ldmask, s) : launch_bf16x3<0, 256>(A, lda, W, ldw, bias, C, ldc, M, N, K, act, res, ldres, mask, ldmask, s);
   return w_layout ? launch_bf16x3<1, 128>(A, lda, W, ldw, bias, C, ldc, M, N, K, act, res, ldres, mask, ldmask, s) : launch_bf16x3<0, 128>(A, lda, W, ldw, bias, C, ldc, M, N, K, act, res, ldres, mask, ldmask, s);
 }

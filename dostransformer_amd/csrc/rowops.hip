@@ -645,6 +645,10 @@ __global__ __launch_bounds__(256) void copy_many_kernel(const CopyLaunch L) {
 
 }  // namespace
 
+// host policy: rows up to this width take ln_prelu_bwd_lean_kernel (64 registers, 4 KB of LDS: it fits next to a weight-gradient
+// group instead of waiting for an empty CU), wider ones the general form
+constexpr int LN_LEAN_MAX_W = 512;
+
 #define CHECK_H4(H) DOSX_CHECK_ARG((H) > 0 && ((H) & 3) == 0, "%s: H=%d must be a multiple of 4", __func__, (H))
 
 extern "C" int dosx_layernorm(const float* x, const float* gamma, const float* beta, float* y, float* xhat, float* rstd,
@@ -709,15 +713,6 @@ extern "C" int dosx_ln_rowdot_bwd(const float* ddos, const float* xhat, const fl
   return 0;
 }
 
-static bool ln_lean_on() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("DOSX_LN_LEAN");
-    on = e ? atoi(e) : 1;
-  }
-  return on != 0;
-}
-
 extern "C" int dosx_ln_prelu_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma,
                                  const float* beta, const float* alpha, float* dz, float* partials, int M, int W,
                                  dosx_stream_t stream) {
@@ -725,7 +720,7 @@ extern "C" int dosx_ln_prelu_bwd(const float* dy, const float* xhat, const float
   CHECK_H4(W);
   DOSX_CHECK_ARG(dy && xhat && rstd && gamma && beta && alpha && dz && partials, "dosx_ln_prelu_bwd: bad args");
   DOSX_CHECK_ARG(W <= 256 * LNW_K, "dosx_ln_prelu_bwd: row width %d > %d", W, 256 * LNW_K);
-  if (W <= 512 && ln_lean_on())
+  if (W <= LN_LEAN_MAX_W)
     hipLaunchKernelGGL(ln_prelu_bwd_lean_kernel, dim3(ceil_div(M, 32)), dim3(256), ((size_t)(2 * W) + 4) * sizeof(float),
                        to_stream(stream), dy, nullptr, nullptr, xhat, rstd, gamma, beta, alpha, dz, partials, M, W);
   else
@@ -742,12 +737,9 @@ extern "C" int dosx_ln_prelu_bwd_gather(const float* dy, const int32_t* idx, con
   CHECK_H4(W);
   DOSX_CHECK_ARG(dy && idx && xhat && rstd && gamma && beta && alpha && dz && partials, "dosx_ln_prelu_bwd_gather: bad args");
   DOSX_CHECK_ARG(W <= 256 * LNW_K, "dosx_ln_prelu_bwd_gather: row width %d > %d", W, 256 * LNW_K);
-  if (W <= 512 && ln_lean_on())
+  if (W <= LN_LEAN_MAX_W)
     hipLaunchKernelGGL(ln_prelu_bwd_lean_kernel, dim3(ceil_div(M, 32)), dim3(256), ((size_t)(2 * W) + 4) * sizeof(float),
                        to_stream(stream), dy, idx, scale, xhat, rstd, gamma, beta, alpha, dz, partials, M, W);
-  else if (W <= 512)        // (two float4 column groups per lane: half the registers of the general form)
-    hipLaunchKernelGGL((ln_bwd_wide_kernel<2, 2>), dim3(ceil_div(M, 32)), dim3(256), (4 * (size_t)(2 * W) + 4) * sizeof(float),
-                       to_stream(stream), dy, nullptr, xhat, rstd, gamma, beta, nullptr, alpha, dz, partials, M, W, 0, 1, idx, scale);
   else
     hipLaunchKernelGGL((ln_bwd_wide_kernel<2>), dim3(ceil_div(M, 32)), dim3(256), (4 * (size_t)(2 * W) + 4) * sizeof(float),
                        to_stream(stream), dy, nullptr, xhat, rstd, gamma, beta, nullptr, alpha, dz, partials, M, W, 0, 1, idx, scale);

@@ -158,7 +158,7 @@ typedef struct DosxGemm {
 
 /* exact number of workgroup rows dosx_gemm writes into `partials` for this epilogue: ceil(M/32) for
  * the row-wise epilogues, ceil(M/32)*ceil(N/128) for the element-wise PRELU_BWD epilogue. */
-/* Experiment switch (round 4, default 0 = off; also DOSX_SLIVER_MAX_GF in the environment): plain dgrad GEMMs (w_layout 1, no
+/* Experiment switch (round 4, default 0 = off; this setter is the only way to turn it on): plain dgrad GEMMs (w_layout 1, no
  * prologue / bias / activation, one segment, identity out / residual maps) of up to `gf` GFLOP run on a vector-ALU kernel whose
  * workgroups (4 waves, 56 VGPRs, 8.5 KB of LDS) fit next to two resident weight-gradient workgroups. */
 int dosx_set_sliver_max_gf(double gf);
@@ -437,7 +437,7 @@ typedef struct DosxAttn {
 int dosx_attention_pkv_supported(int Nk, int H);
 /* Which shapes dosx_attention_fwd / dosx_attention_bwd (one-launch form: dkv_part + dkv_cnt) route to the crystal-aligned
  * kernels (csrc/attention_aligned.hip: flags 0, Nk <= 64, H in {64, 128, 256}): 0 = none (attention.hip's kernels), 1 = H > 128
- * only, 2 = all of them (the default; also from the environment variable DOSX_ATTN_ALIGNED).  Sets the mode unless `mode` < 0;
+ * only, 2 = all of them (the default).  Sets the mode unless `mode` < 0;
  * returns the previous one. */
 int dosx_attention_aligned_mode(int mode);
 int dosx_attention_fwd(const DosxAttn* a, dosx_stream_t stream);
@@ -646,7 +646,8 @@ typedef struct DosxHeadsBwd {
 int dosx_heads_bwd_supported(int H);
 int dosx_heads_bwd(const DosxHeadsBwd* a, dosx_stream_t stream);
 
-/* Split-bf16 GEMM (round 6, csrc/gemm_bf16x3.hip) - a MEASUREMENT next to dosx_gemm, not part of any training / inference program:
+/* Split-bf16 GEMM (round 6, csrc/gemm_bf16x3.hip) - OPT-IN: with DOSX_FFN_BF16X3=1 functional.encoder_fwd / encoder_bwd run the
+ * plain feed-forward GEMMs through it; by default every program runs dosx_gemm's exact-fp32 kernels:
  *     C[M,N] = epi( A[M,K] . op(W) + bias[N] )      w_layout 0: W is [N][K] (nn.Linear), 1: W is [K][N]
  *     epi: relu (act = 1), then + res[M,N] (optional), then zero where mask[M,N] <= 0 (optional: dosx_gemm's EPI_RELU_MASK)
  * fp32 operands and result; every element is split into three bf16 terms on the fly and the six leading products run on the

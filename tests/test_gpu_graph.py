@@ -211,8 +211,8 @@ def test_device_greedy_tiles_equal_the_host_table_with_overfull_and_isolated_nod
     """collate_greedy_tiles_kernel against batch.seg_tiles_host + pad_seg_tiles on batches that exercise every rule of the packing:
     nodes of more than 48 incoming edges (chunk tiles; a remainder that shares its tile; exactly 96 = two full chunks), isolated
     nodes at the start of the batch, behind a full last chunk (absorbed by that chunk's tile), between crystals and at the end,
-    single-crystal batches, repeated crystals; and the crystal-aligned fallback table stays valid (DOSX_COLLATE_GREEDY_TILES=0 is
-    read once per process, so the fallback is checked through its invariants in test_collate_into_matches_pad_batch's history)."""
+    single-crystal batches, repeated crystals.  (Every batch here fits the greedy kernel; collate_pad_tiles_kernel, the
+    crystal-aligned table of batches beyond its node limit, is not run by this test.)"""
     from dostransformer_amd import synth
     from dostransformer_amd.batch import bucket_sizes, collate, pad_batch
     from dostransformer_amd.loader import DeviceDataset

@@ -444,8 +444,28 @@ def _assert_switch_surface():
     assert not hasattr(GradSink, "use_wgrad_stream") and GradSink.use_side_stream is False
 
 
+def _assert_library_switch_surface():
+    """The C library reads no process variable outside the diagnostic stamps build: every getenv of csrc/ lies inside an
+    `#ifdef DOSX_STAMPS ... #endif` region (the guard logic of test_no_work_skipping_switch_ships_in_the_package).  Its runtime
+    selectors are the two setters of include/dosx.h, dosx_attention_aligned_mode and dosx_set_sliver_max_gf."""
+    import pathlib
+    import re
+    root = pathlib.Path(__file__).resolve().parent.parent / "dostransformer_amd" / "csrc"
+    files = sorted(f for ext in ("*.hip", "*.cpp", "*.h") for f in root.glob(ext))
+    assert len(files) > 20
+    seen = 0
+    for f in files:
+        src = f.read_text()
+        for m in re.finditer(r"getenv", src):
+            guard = src.rfind("#ifdef DOSX_STAMPS", 0, m.start())
+            assert guard >= 0 and src.find("#endif", guard) > m.start(), f"{f.name}: getenv outside the stamps build"
+            seen += 1
+    assert seen == 1                       # (DOSX_DEBUG_SKIP_WGRAD of the stamps build: the scan does see what it looks for)
+
+
 def test_only_the_documented_switches_read_the_environment():
     _assert_switch_surface()
+    _assert_library_switch_surface()
 
 
 def test_bucket_promotion_picks_the_smallest_live_bucket_that_fits():

@@ -363,3 +363,80 @@ def test_gemm_kernel_name_matches_the_tile_choice():
     buf = C.create_string_buffer(96)
     assert lib.dosx_gemm_kernel_name(C.byref(g), buf, 96) == 0
     assert buf.value == b"gemm_kernel<3, 2, 0, 0, 1, 1>"       # 48-row tiles, 256 columns, LN epilogue (edge GEMM1 at cfg2)
+
+
+# ---- the host policies of the library, pinned ----------------------------------------------------------------------------
+_POLICY_M = (1, 16, 17, 32, 33, 100, 3264, 4096, 4097, 6528, 8192, 8193, 9000, 12288, 12289, 12864, 13056, 16383, 16384, 17880,
+             24576, 25728, 32769, 262144)
+_POLICY_NK = (64, 128, 256, 384, 512, 1024)
+# (label, M, N, K, w_layout, pro, epi, lda, fake stats_out / norm_out address): what dosx_gemm_kernel_name is asked for
+_POLICY_GEMMS = (
+    ("edge_gemm1_ln", 9000, 256, 384, 0, "NONE", "LN", 384, None),               # test_gemm_kernel_name_matches_the_tile_choice
+    ("tail_split_relu_mask", 25728, 128, 512, 1, "NONE", "RELU_MASK", 512, None),
+    ("ln_512_columns", 17880, 512, 256, 0, "NONE", "LN", 256, None),
+    ("prelu_ln_bwd_512_columns", 17880, 512, 256, 1, "NONE", "PRELU_LN_BWD", 256, None),
+    ("unaligned_atom_features", 1554, 128, 118, 0, "NONE", "BIAS_ACT", 118, None),
+    ("one_half_tile", 16, 128, 128, 0, "NONE", "BIAS_ACT", 128, None),
+    ("small_grid", 100, 256, 256, 0, "NONE", "BIAS_ACT", 256, None),
+    ("fc1_forward", 12864, 512, 128, 0, "NONE", "BIAS_ACT", 128, None),
+    ("fc1_forward_rowln", 25728, 512, 128, 0, "ROWLN", "BIAS_ACT", 128, None),
+    ("rowln_bwd_256_columns", 25728, 256, 512, 1, "NONE", "ROWLN_BWD", 512, None),
+    ("prelu_ln_bwd", 9000, 256, 256, 1, "NONE", "PRELU_LN_BWD", 256, None),
+    ("prelu_bwd", 9000, 128, 128, 1, "NONE", "PRELU_BWD", 128, None),
+    ("stats_out_256_columns", 6528, 256, 128, 0, "NONE", "BIAS_ACT", 128, "stats_out"),
+    ("norm_out_512_columns", 6528, 512, 128, 0, "NONE", "BIAS_ACT", 128, "norm_out"),
+    ("segsum", 4000, 128, 256, 0, "LN_PRELU", "SEGSUM", 256, None),
+)
+
+
+def _host_policy_table(lib):
+    """Every exported host decision of csrc/gemm.hip and csrc/ffn.hip over a grid that straddles each threshold the policies
+    contain, as JSON-ready lists in the order of the loops below."""
+    from dostransformer_amd import _abi, _lib
+    epis = sorted(v for k, v in vars(_abi).items() if k.startswith("DOSX_EPI_"))
+    assert epis == list(range(8))
+    t = {}
+    t["gemm_partial_rows"] = [lib.dosx_gemm_partial_rows(M, N, e) for M in _POLICY_M for N in (64, 128, 256, 512) for e in epis]
+    t["wgrad_splits"] = [lib.dosx_wgrad_splits(M, N, K) for M in _POLICY_M for N in _POLICY_NK for K in _POLICY_NK]
+    t["wgrad_scratch_floats"] = [lib.dosx_wgrad_scratch_floats(N, K, s) for N in _POLICY_NK for K in _POLICY_NK for s in (1, 2, 8, 64)]
+    t["ffn_bwd_partial_rows"] = [lib.dosx_ffn_bwd_partial_rows(M) for M in _POLICY_M]
+    shapes = ((51, 64), (51, 1), (128, 64), (200, 8), (64, 64), (65, 64), (32, 128), (32, 129))    # 128 workgroups of 32 rows and one more
+    t["ffn_att_bwd_partial_rows"] = [lib.dosx_ffn_att_bwd_partial_rows(Sq, Bq) for Sq, Bq in shapes]
+    t["ffn_att_aligned_rows"] = [lib.dosx_ffn_att_aligned_rows(Sq, Bq) for Sq, Bq in shapes]
+    hs, nks = (32, 64, 96, 128, 160), (1, 16, 17, 48, 64, 65)
+    t["ffn_att_aligned_supported"] = [lib.dosx_ffn_att_aligned_supported(H, Nk) for H in hs for Nk in nks]
+    t["ffn_att_bwd_supported"] = [lib.dosx_ffn_att_bwd_supported(H, Nk, Sq, Bq) for H in hs for Nk in nks for Sq, Bq in shapes[:4]]
+    names = {}
+    for label, M, N, K, wl, pro, epi, lda, extra in _POLICY_GEMMS:
+        g = _lib.Gemm()
+        g.M, g.N, g.K, g.nseg, g.w_layout = M, N, K, 1, wl
+        g.pro, g.epi = getattr(_abi, "DOSX_PRO_" + pro), getattr(_abi, "DOSX_EPI_" + epi)
+        g.a[0].ld, g.a[0].width, g.ldw = lda, K, (K if wl == 0 else N)
+        if extra:
+            setattr(g, extra, 0x10000)                   # (an address that is only tested against NULL)
+        buf = C.create_string_buffer(96)
+        assert lib.dosx_gemm_kernel_name(C.byref(g), buf, 96) == 0
+        names[label] = buf.value.decode()
+    t["gemm_kernel_name"] = names
+    return t
+
+
+def test_host_policies_are_those_of_the_commit_that_folded_their_switches():
+    """tests/golden/host_policy.json was recorded from a library built at the commit BEFORE the getenv tuning switches of
+    csrc/ were folded into constants, with no DOSX_* variable set
+    (DOSX_LIB=<that build> python -c "import json; from tests.test_lib_abi import _host_policy_table as t; from
+    dostransformer_amd import _lib; print(json.dumps(t(_lib.load())))"): tile heights, column tiles, tail splits, weight-gradient
+    splits and scratch sizes, the feed-forward half-tile threshold and chunk width are what they were, value for value."""
+    import json
+    from tests.util import GOLDEN, dosx_lib
+    want = json.load(open(os.path.join(GOLDEN, "host_policy.json")))
+    got = _host_policy_table(dosx_lib().load())
+    assert sorted(got) == sorted(want)
+    for k in want:
+        assert got[k] == want[k], k
+    assert len(want["gemm_partial_rows"]) == 24 * 4 * 8 and len(want["wgrad_splits"]) == 24 * 36 and len(want["gemm_kernel_name"]) >= 12
+    # the table is not degenerate: every tile height and the tail split occur
+    assert want["gemm_kernel_name"]["edge_gemm1_ln"] == "gemm_kernel<3, 2, 0, 0, 1, 1>"
+    assert want["gemm_kernel_name"]["unaligned_atom_features"].endswith("0, 0, 0>")
+    assert {n.split("<")[1][0] for n in want["gemm_kernel_name"].values()} == set("0123")
+    assert set(want["wgrad_splits"]) >= {1, 8, 64} and set(want["ffn_att_aligned_rows"]) == {16, 32}

@@ -442,7 +442,7 @@ def main():
                                       ("eDOS fc2 fwd", 25728, 256, 1024, 0), ("eDOS fc1 dgrad", 25728, 256, 1024, 1),
                                       ("roofline scale", 262144, 512, 128, 0), ("square 8192", 8192, 8192, 8192, 0)):
             bf16x3_case(name, M_, N_, K_, wl_)
-    if w == "edosffn":      # the four feed-forward GEMMs of the Electron-DOS step (tile-policy experiments: DOSX_GEMM_RT / _BN)
+    if w == "edosffn":      # the four feed-forward GEMMs of the Electron-DOS step (what the tile policy of csrc/gemm.hip - gemm_rt, gemm_bn, gemm_tail_split - is tuned on)
         for M_ in (201 * 128, 24576, 201 * 64):
             gemm_case("eDOS fc1 fwd (rowLN pro)", M_, 1024, 256, pro=ops.PRO_ROWLN)
             gemm_case("eDOS fc1 fwd, plain A", M_, 1024, 256)

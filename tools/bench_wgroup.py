@@ -86,7 +86,6 @@ def run(name, descs):
 
 
 if __name__ == "__main__":
-    print("DOSX_WGRAD_OCC =", os.environ.get("DOSX_WGRAD_OCC", "(default)"), " DOSX_WGRAD_MAXSPLIT =", os.environ.get("DOSX_WGRAD_MAXSPLIT", "(default)"))
     run("GNN layer pair (factored)", gnn_layer_factored() + gnn_layer_factored())
     run("one GNN layer (factored)", gnn_layer_factored())
     run("GNN layer pair (gathered concat)", gnn_layer() + gnn_layer())
