@@ -175,11 +175,28 @@ class GraphnetworkBase(FusedModel):
         unused = "GN_encoder.node_encoder_prompt" if width == expected else "GN_encoder.node_encoder"
         return tuple(f"{unused}.{s}" for s in ("0.weight", "0.bias", "1.weight", "2.weight", "2.bias"))
 
-    def _program_fwd(self, P, g, m):
+    # the fp32 programs of this family (functional.graphnetwork_fwd / _bwd; embedder_eDOS.mlp overrides them)
+    _fwd_fn = staticmethod(Fn.graphnetwork_fwd)
+
+    @staticmethod
+    def _bwd_fn(P, G, cfg, m, saved, ddos, dx, sink, factored_head=False):
+        Fn.graphnetwork_bwd(P, G, cfg, m, saved, ddos, dx, sink, factored_head=factored_head)
+
+    # A crystal's outputs do not depend on its batch mates: no dense key batch, no attention (evaluate.test_per_crystal)
+    batch_independent = True
+
+    def _require_fp32_program(self, who: str) -> None:
+        """train.Trainer / predict.Predictor run the fp32 program on the flat buffer: a float64 Graphnetwork_phonon (float64
+        live parameters: functional64) stays with model(batch), loss.backward() and torch.optim.AdamW."""
+        if self._flat_dtype(None) == torch.float64:
+            raise DosxError(f"{who} runs the fp32 program; this {type(self).__name__} has float64 parameters and runs the "
+                            f"float64 one: train it with model(batch), loss.backward() and torch.optim.AdamW")
+
+    def _program_fwd(self, P, g, m, factored_head: bool = False):
         if P["embeddings.weight"].dtype == torch.float64:
             dos, ctx = F64.graphnetwork_phonon_fwd(P, self._cfg, g, m)
             return dos, ctx
-        dos, xL, ctx = Fn.graphnetwork_fwd(P, self._cfg, g, m)
+        dos, xL, ctx = self._fwd_fn(P, self._cfg, g, m, factored_head=factored_head)
         return (dos, xL, ctx) if self._returns_x else (dos, ctx)
 
     def _program_bwd(self, P, G, m, saved, grads, sink):
@@ -192,8 +209,8 @@ class GraphnetworkBase(FusedModel):
         dx = grads[1] if self._returns_x else None
         if ddos is None:
             ddos = torch.zeros(m.num_graphs, self._cfg.S, device=P["embeddings.weight"].device)
-        Fn.graphnetwork_bwd(P, G, self._cfg, m, saved, ddos.float().contiguous(),
-                            None if dx is None else dx.float().contiguous(), sink)
+        self._bwd_fn(P, G, self._cfg, m, saved, ddos.float().contiguous(),
+                     None if dx is None else dx.float().contiguous(), sink)
 
     def forward(self, g):
         out = self._run(g)

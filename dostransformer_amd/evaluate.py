@@ -133,7 +133,8 @@ class PerCrystalResult(NamedTuple):
 def test_per_crystal(predictor, ds, indices=None, batch_size: int = 64) -> PerCrystalResult:
     """`utils.test` / `utils.test_phonon` over the crystals ``indices`` (default: all, in order) of a ``loader.DeviceDataset`` at
     the reference's batch size 1, computed in passes of ``batch_size`` crystals: ``predictor`` - a ``predict.Predictor`` with
-    ``per_crystal_keys=True``, or a ``Predictor64`` whose module has ``set_per_crystal_keys(True)`` - gives every crystal its
+    ``per_crystal_keys=True``, a ``Predictor64`` whose module has ``set_per_crystal_keys(True)``, or a predictor whose
+    ``batch_independent`` is True (the GNN-only baselines: no attention; the metrics come from their one DOS output) - gives every crystal its
     batch-1 outputs from a batched pass, ``dosx_eval_metrics`` turns each row into its four metrics on the device, and the four
     means are read back once at the end.  Every chunk runs with the n_max of the whole selection (few recorded shapes), which is
     valid only because per-crystal keys make the outputs independent of it: without the flag this raises ``ValueError``."""
@@ -141,7 +142,7 @@ def test_per_crystal(predictor, ds, indices=None, batch_size: int = 64) -> PerCr
     flag = getattr(predictor, "per_crystal_keys", None)
     if flag is None:
         flag = getattr(predictor.model, "per_crystal_keys", False)
-    if not flag:
+    if not flag and not getattr(predictor, "batch_independent", False):
         raise ValueError("test_per_crystal needs per-crystal keys (Predictor(model, per_crystal_keys=True), or "
                          "model.set_per_crystal_keys(True) under Predictor64): without them a batched pass does not give the "
                          "batch-size-1 outputs the reference's metrics are computed from")
@@ -157,7 +158,7 @@ def test_per_crystal(predictor, ds, indices=None, batch_size: int = 64) -> PerCr
     dev, table, embeddings = ds.device, None, None
     for row0 in range(0, C, batch_size):
         slot, N = predictor._run_dataset(ds, idx[row0:row0 + batch_size], n_max)
-        _, x, dos_system = slot.out
+        dos_system, x = predictor._eval_outputs(slot)
         B, S = dos_system.shape
         if table is None:
             table = torch.empty(C, 4, dtype=torch.float64, device=dev)

@@ -1849,28 +1849,50 @@ def _dostransformer_bwd_wide(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, 
     sink.flush()
 
 
-# ---- GNN-only variants (graphnetwork_phonon.py:48-72, graphnetwork.py:26-43) -----------------------
-def graphnetwork_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta):
-    H, S, B = cfg.H, cfg.S, m.num_graphs
+# ---- GNN-only variants (graphnetwork_phonon.py:48-72, graphnetwork.py:26-43, mlp.py:22-35) -----------
+def _pair_head_fwd(P: Params, cfg: ModelCfg, B: int, graph: torch.Tensor, factored: bool):
+    """out_layer on cat[emb[s] | graph[b]] over all (s, b) -> (dos [B,S], what _pair_head_bwd needs).  ``factored``: the first
+    Linear as E1[s] + C[b] (two small products on the column halves of its weight) and the rest in one launch
+    (ops.pair_head_fwd) - nothing of S * B rows exists; else the S * B-row product of the autograd path."""
+    H, S = cfg.H, cfg.S
     dev = P["embeddings.weight"].device
-    expected = 118 if cfg.kind == "phonon" else 200          # graphnetwork_phonon.py:150-153 / graphnetwork.py:96-99
-    node_key = "GN_encoder.node_encoder" if g.x.shape[1] == expected else "GN_encoder.node_encoder_prompt"
-    xL, u, ctrunk = gnn_trunk_fwd(P, cfg, g, m, node_key)
-    graph, dec_segs = decoder_fwd(P, cfg, m, xL, u)
-    emb = P["embeddings.weight"]
+    emb, W0 = P["embeddings.weight"], P["out_layer.0.weight"]
+    dos = _empty(dev, B, S)
+    if factored:
+        E1, Cg = _empty(dev, S, H), _empty(dev, B, H)
+        ops.gemm(S, H, [seg(emb)], W0[:, :H], E1, bias=P["out_layer.0.bias"])
+        ops.gemm(B, H, [seg(graph)], W0[:, H:], Cg)
+        ops.pair_head_fwd(E1, Cg, P["out_layer.2.weight"], P["out_layer.2.bias"], dos, 0.01)
+        return dos, None, (E1, Cg, graph)
     a = SegList([seg(emb, rmap=rowmap(d=B, m=1, c=0)), seg(graph, rmap=rowmap(d=B, m=0, c=1))], [emb, graph])
     hid = _empty(dev, S * B, H)
-    ops.gemm(S * B, H, a.segs, P["out_layer.0.weight"], hid, bias=P["out_layer.0.bias"], act=ACT_LEAKY, act_slope=0.01)
-    dos = _empty(dev, B, S)
+    ops.gemm(S * B, H, a.segs, W0, hid, bias=P["out_layer.0.bias"], act=ACT_LEAKY, act_slope=0.01)
     ops.rowdot(hid, P["out_layer.2.weight"], P["out_layer.2.bias"], dos, S, B, H)
-    return dos, xL, GraphNetCtx(ctrunk, dec_segs, a, hid, xL)
+    return dos, a, hid
 
 
-def graphnetwork_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, ddos: torch.Tensor,
-                     dx_ext: Optional[torch.Tensor], sink: GradSink) -> None:
-    ctrunk, dec_segs, a, hid = ctx.trunk, ctx.dec_segs, ctx.a, ctx.hid
-    H, S, B, N = cfg.H, cfg.S, m.num_graphs, m.num_nodes
+def _pair_head_bwd(P: Params, G: Params, cfg: ModelCfg, B: int, a, hid, ddos: torch.Tensor, sink: GradSink) -> torch.Tensor:
+    """Backward of _pair_head_fwd: the gradients of out_layer.* and embeddings.weight; returns dL/dgraph [B,H]."""
+    H, S = cfg.H, cfg.S
     dev = ddos.device
+    W0 = P["out_layer.0.weight"]
+    dgraph = _empty(dev, B, H)
+    if a is None:                                  # factored: hid = (E1, C, graph)
+        E1, Cg, graph = hid
+        emb = P["embeddings.weight"]
+        rows = ops.pair_head_partial_rows(S, B)
+        part = sink.scratch(rows, H + 1)
+        dE1, dC = _empty(dev, S, H), _empty(dev, B, H)
+        ops.pair_head_bwd(ddos, E1, Cg, P["out_layer.2.weight"], dE1, dC, part, 0.01)
+        sink.add(part, 0, G["out_layer.2.weight"], rows, H + 1, H)
+        sink.add(part, H, G["out_layer.2.bias"], rows, H + 1, 1)
+        GW0 = G["out_layer.0.weight"]
+        # the two column halves of dW0 are separate jobs written in place (DosxWgrad.ldd); db0 = sum_s dE1 rides on the first
+        _wgrad_linear(sink, G, "out_layer.0.weight", "out_layer.0.bias", S, H, seg(dE1), [seg(emb)], keep=(dE1,), dst=GW0[:, :H])
+        _wgrad_linear(sink, G, "out_layer.0.weight", None, B, H, seg(dC), [seg(graph)], keep=(dC, graph), dst=GW0[:, H:])
+        ops.gemm(S, H, [seg(dE1)], W0[:, :H], G["embeddings.weight"], w_layout=1)
+        ops.gemm(B, H, [seg(dC)], W0[:, H:], dgraph, w_layout=1)
+        return dgraph
     rows = S * B
     r32 = _rows32(rows)
     part = sink.scratch(r32, H + 1)
@@ -1881,17 +1903,69 @@ def graphnetwork_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, ddo
     dpre = _empty(dev, rows, H)
     ops.act_bwd(dhid, hid, 0.01, dpre)
     _wgrad_linear(sink, G, "out_layer.0.weight", "out_layer.0.bias", rows, H, seg(dpre), a.segs, keep=(dpre,))
-    W0 = P["out_layer.0.weight"]
     Rs = _empty(dev, S, H)
     ops.reduce_rows(dpre.data_ptr(), H, Rs.data_ptr(), H, S, B, B, 1, H)          # sum over the batch
     ops.gemm(S, H, [seg(Rs)], W0[:, :H], G["embeddings.weight"], w_layout=1)
     Rb = _empty(dev, B, H)
     ops.reduce_rows(dpre.data_ptr(), H, Rb.data_ptr(), H, B, S, 1, B, H)          # sum over the energy bins
-    dgraph = _empty(dev, B, H)
     ops.gemm(B, H, [seg(Rb)], W0[:, H:], dgraph, w_layout=1)
-    dxL = ops.zeros(dev, N, H)
+    return dgraph
+
+
+def graphnetwork_node_key(cfg: ModelCfg, g) -> str:
+    expected = 118 if cfg.kind == "phonon" else 200          # graphnetwork_phonon.py:150-153 / graphnetwork.py:96-99
+    return "GN_encoder.node_encoder" if g.x.shape[1] == expected else "GN_encoder.node_encoder_prompt"
+
+
+def graphnetwork_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta, factored_head: bool = False):
+    """``factored_head``: the output head on its rank structure (_pair_head_fwd; train.Trainer / predict.Predictor); the default
+    keeps the S * B-row product of the autograd module path."""
+    xL, u, ctrunk = gnn_trunk_fwd(P, cfg, g, m, graphnetwork_node_key(cfg, g))
+    graph, dec_segs = decoder_fwd(P, cfg, m, xL, u)
+    dos, a, hid = _pair_head_fwd(P, cfg, m.num_graphs, graph, factored_head)
+    return dos, xL, GraphNetCtx(ctrunk, dec_segs, a, hid, xL)
+
+
+def graphnetwork_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, ddos: torch.Tensor,
+                     dx_ext: Optional[torch.Tensor], sink: GradSink, factored_head: bool = False) -> None:
+    ctrunk, dec_segs, a, hid = ctx.trunk, ctx.dec_segs, ctx.a, ctx.hid
+    if factored_head != (a is None):
+        raise ValueError("graphnetwork_bwd: factored_head differs from the forward pass that made this context")
+    H, N = cfg.H, m.num_nodes
+    dgraph = _pair_head_bwd(P, G, cfg, m.num_graphs, a, hid, ddos, sink)
+    dxL = ops.zeros(ddos.device, N, H)
     du_seg = decoder_bwd(P, G, cfg, m, dec_segs, dgraph, dxL, sink)
     if dx_ext is not None:
         dxL.add_(dx_ext)
     gnn_trunk_bwd(P, G, cfg, m, ctrunk, dxL, du_seg, sink)
+    sink.flush()
+
+
+def mlp_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta, factored_head: bool = False):
+    """`embedder_eDOS/mlp.py:22-35`: Graphnetwork without processors - node encoder, global encoder, decoder, output head.  The
+    edge encoder's output is unused upstream (`:27`) and is not computed; no edge list is read.  Returns dos, x0 (the encoder
+    output), ctx."""
+    H, N, B = cfg.H, m.num_nodes, m.num_graphs
+    node_key = graphnetwork_node_key(cfg, g)
+    xin = _f32(g.x)
+    with ops.graph_rows():
+        x0, cn = mlp_prelu_fwd(P, node_key, SegList([seg(xin)], [xin]), N, H)
+    glob = _f32(g.glob).reshape(B, 2)
+    u, cu = mlp_prelu_fwd(P, "GN_encoder.global_encoder", SegList([seg(glob)], [glob]), B, H)
+    graph, dec_segs = decoder_fwd(P, cfg, m, x0, u)
+    dos, a, hid = _pair_head_fwd(P, cfg, B, graph, factored_head)
+    return dos, x0, GraphNetCtx(TrunkCtx(cn, None, cu, None, node_key), dec_segs, a, hid, x0)
+
+
+def mlp_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, ddos: torch.Tensor, sink: GradSink,
+            factored_head: bool = False) -> None:
+    ctrunk, dec_segs, a, hid = ctx.trunk, ctx.dec_segs, ctx.a, ctx.hid
+    if factored_head != (a is None):
+        raise ValueError("mlp_bwd: factored_head differs from the forward pass that made this context")
+    dgraph = _pair_head_bwd(P, G, cfg, m.num_graphs, a, hid, ddos, sink)
+    dx0 = ops.zeros(ddos.device, m.num_nodes, cfg.H)
+    du_seg = decoder_bwd(P, G, cfg, m, dec_segs, dgraph, dx0, sink)
+    with ops.graph_rows():
+        mlp_prelu_bwd(P, G, ctrunk.node_key, ctrunk.node, dx0, sink, tail=True)
+    mlp_prelu_bwd(P, G, "GN_encoder.global_encoder", ctrunk.glob, None, sink, dy_seg=du_seg, tail=True)
     sink.flush()

@@ -1373,6 +1373,53 @@ def heads_bwd(S: int, B: int, H: int, dkvs, kvs, rstd, ddosin, dosin, slope: flo
           w=lambda: (f"heads_bwd[H{H}]", f"heads_bwd_kernel<{H}>", "mfma", 2.0 * S * B * H * 2 * H))
 
 
+def _pair_head_desc(who: str, e1, c, w2, slope: float):
+    """The operands both pair-head launches read: e1 [S,H], c [B,H], w2 [H] (or [1,H], nn.Linear(H, 1).weight)."""
+    _chk_f32(e1, c, w2)
+    if e1.dim() != 2 or c.dim() != 2 or e1.shape[1] != c.shape[1] or w2.numel() != e1.shape[1]:
+        raise ValueError(f"{who}: e1 [S,H], c [B,H], w2 [H], got {tuple(e1.shape)}, {tuple(c.shape)}, {tuple(w2.shape)}")
+    if not (e1.is_contiguous() and c.is_contiguous() and w2.is_contiguous()):
+        raise ValueError(f"{who}: e1, c and w2 must be contiguous")
+    d = _lib.PairHead()
+    d.S, d.B, d.H, d.slope = int(e1.shape[0]), int(c.shape[0]), int(e1.shape[1]), float(slope)
+    d.e1, d.c, d.w2 = e1.data_ptr(), c.data_ptr(), w2.data_ptr()
+    return d
+
+
+def pair_head_partial_rows(S: int, B: int) -> int:
+    return int(_lib.load().dosx_pair_head_partial_rows(int(S), int(B)))
+
+
+def pair_head_fwd(e1, c, w2, b2, dos, slope: float = 0.01) -> None:
+    """dos[b, s] = b2 + sum_h w2[h] * leaky(e1[s, h] + c[b, h]) in one launch (include/dosx.h: DosxPairHead); dos: [B,S]."""
+    d = _pair_head_desc("pair_head_fwd", e1, c, w2, slope)
+    _chk_f32(b2, dos)
+    if tuple(dos.shape) != (d.B, d.S) or not dos.is_contiguous() or b2.numel() != 1:
+        raise ValueError(f"pair_head_fwd: dos must be a contiguous [B,S] = [{d.B},{d.S}] and b2 one element, got "
+                         f"{tuple(dos.shape)}, {tuple(b2.shape)}")
+    d.b2, d.dos = b2.data_ptr(), dos.data_ptr()
+    S, B, H = d.S, d.B, d.H
+    _call("dosx_pair_head_fwd", C.byref(d), _stream(),
+          w=lambda: (f"pair_head_fwd[H{H}]", "pair_head_fwd_kernel", "hbm", 4.0 * (S * H + B * H + S * B)))
+
+
+def pair_head_bwd(ddos, e1, c, w2, de1, dc, partials, slope: float = 0.01) -> None:
+    """The backward of pair_head_fwd from ddos [B,S] in one launch: de1 [S,H], dc [B,H] and ``partials``
+    [pair_head_partial_rows(S, B), H + 1] whose column sums are dw2 (H) and db2 (GradSink.add)."""
+    d = _pair_head_desc("pair_head_bwd", e1, c, w2, slope)
+    _chk_f32(ddos, de1, dc, partials)
+    rows = pair_head_partial_rows(d.S, d.B)
+    ok = (tuple(ddos.shape) == (d.B, d.S) and de1.shape == e1.shape and dc.shape == c.shape
+          and tuple(partials.shape) == (rows, d.H + 1))
+    if not ok or not all(t.is_contiguous() for t in (ddos, de1, dc, partials)):
+        raise ValueError(f"pair_head_bwd: contiguous ddos [B,S], de1 [S,H], dc [B,H], partials [{rows},H+1] wanted, got "
+                         f"{tuple(ddos.shape)}, {tuple(de1.shape)}, {tuple(dc.shape)}, {tuple(partials.shape)}")
+    d.ddos, d.de1, d.dc, d.partials = ddos.data_ptr(), de1.data_ptr(), dc.data_ptr(), partials.data_ptr()
+    S, B, H = d.S, d.B, d.H
+    _call("dosx_pair_head_bwd", C.byref(d), _stream(),
+          w=lambda: (f"pair_head_bwd[H{H}]", "pair_head_bwd_kernel", "hbm", 4.0 * (3 * S * H + 2 * B * H + S * B)))
+
+
 def gemm_bf16x3_supported(M: int, N: int, K: int) -> bool:
     return bool(_lib.load().dosx_gemm_bf16x3_supported(int(M), int(N), int(K)))
 

@@ -16,6 +16,12 @@ It quacks like the module for the evaluation loops: ``evaluate.test(Predictor(mo
 cross attentions of a BATCHED forward attend over each crystal's own atoms only (``DosxAttn.key_ptr`` = the batch's graph_ptr):
 B crystals in one pass give what B batch-1 forwards give (to fp32 rounding), at the batched rate.
 
+``Predictor(model)`` also takes the GNN-only baselines - ``Graphnetwork``, ``Graphnetwork_phonon`` (fp32 parameters) and
+``embedder_eDOS.mlp.mlp`` - and returns what THEIR forward returns: ``(dos, x)`` for ``Graphnetwork``, ``dos`` for the other two,
+bitwise the eval-mode ``functional.graphnetwork_fwd(factored_head=True)`` (the output head on its rank structure, as
+``train.Trainer`` runs it).  They have no attention, so ``per_crystal_keys=True`` is refused and ``batch_independent`` is True:
+``evaluate.test_per_crystal`` takes such a predictor as it is.
+
 ``Predictor64(model)`` is the same for a ``DOSTransformer_phonon`` set to the float64 program
 (``model.double().set_program_dtype(torch.float64)``): the float64 forward program on ghost-padded buckets, outputs in float64,
 bitwise those of ``model(batch)``.  Per-crystal keys stay the module's own switch (``model.set_per_crystal_keys``).
@@ -28,7 +34,8 @@ import torch
 
 from . import functional64 as F64
 from . import ops
-from ._models import DOSTransformerBase
+from ._lib import DosxError
+from ._models import DOSTransformerBase, GraphnetworkBase
 from .batch import CrystalBatch, bucket_sizes, graph_meta
 from .slots import Slot, padded_to_bucket
 
@@ -93,12 +100,30 @@ class _Predictor:
             self.slot_hits += 1
             slot.load(g, m)
             slot.prog.run()
+        return self._outputs(slot, n_real)
+
+    def _outputs(self, slot: Slot, n_real: int):
+        """What the module's forward returns, from a bucket's output buffers (node rows cut to the real ones)."""
         dg, xL, ds = slot.out
         return dg, xL[:n_real], ds
+
+    def _eval_outputs(self, slot: Slot):
+        """(the DOS prediction the metrics are computed from [B,S], node embeddings [N_pad,H]) of a bucket (evaluate.test_per_crystal)."""
+        _, x, dos_system = slot.out
+        return dos_system, x
+
+    @property
+    def batch_independent(self) -> bool:
+        """True when a crystal's outputs do not depend on its batch mates whatever the flags (models without attention)."""
+        return bool(getattr(self.model, "batch_independent", False))
 
     def _tables(self, ds):
         """The dataset's feature tables in the dtype of this predictor's slots."""
         return ds._f32_tables()
+
+    def _width_batch(self, ds):
+        """What ``_ensure_flat`` gets for a dataset pass in place of a batch (None: the model's parameters do not depend on it)."""
+        return None
 
     def forward_dataset(self, ds, indices, n_max: Optional[int] = None):
         """The forward pass on the crystals ``indices`` of a device-resident ``loader.DeviceDataset``, what ``step_dataset`` is
@@ -109,8 +134,7 @@ class _Predictor:
         overwrites.  ``n_max`` may exceed the selection's largest crystal, so that one value serves a whole split; only with
         per-crystal keys do the outputs not depend on it.  These buckets are kept apart from those of ``__call__``."""
         slot, N = self._run_dataset(ds, indices, n_max)
-        dg, xL, dsys = slot.out
-        return (dg, xL[:N], dsys), self._target(slot)
+        return self._outputs(slot, N), self._target(slot)
 
     def _target(self, slot: Slot) -> torch.Tensor:
         return slot.g["phdos" if self.kind == "phonon" else "y_ft"]
@@ -125,7 +149,7 @@ class _Predictor:
         dev = model._module_device()
         if dev.type != "cuda":
             raise RuntimeError(f"{who} runs only on an MI355X through libdosx (no CPU fallback)")
-        fp = model._ensure_flat(dev, None)
+        fp = model._ensure_flat(dev, self._width_batch(ds))
         if fp is not self._fp:                # parameters were re-homed: recorded pointers are stale
             self._fp, self._slots = fp, {}
         idx, N, E, n_max = ds.bucket_dims(indices, n_max)
@@ -154,18 +178,42 @@ class _Predictor:
 class Predictor(_Predictor):
     _dtype = torch.float32
 
-    def __init__(self, model: DOSTransformerBase, bucket=(8, 128), per_crystal_keys: bool = False):
+    def __init__(self, model, bucket=(8, 128), per_crystal_keys: bool = False):
         super().__init__(model, bucket)
+        self._baseline = isinstance(model, GraphnetworkBase)
+        if self._baseline and per_crystal_keys:
+            raise DosxError(f"Predictor({type(model).__name__}, per_crystal_keys=True): the model has no attention - a crystal's "
+                            f"output never depends on its batch mates (Predictor(model).batch_independent)")
         self.per_crystal_keys = bool(per_crystal_keys)
 
     @staticmethod
     def _require(model) -> None:
-        if not isinstance(model, DOSTransformerBase):
-            raise TypeError("Predictor drives DOSTransformer / DOSTransformer_phonon modules")
+        if not isinstance(model, (DOSTransformerBase, GraphnetworkBase)):
+            raise TypeError("Predictor drives DOSTransformer / DOSTransformer_phonon / Graphnetwork / Graphnetwork_phonon / mlp modules")
         model._require_fp32_program("Predictor")
+
+    def _width_batch(self, ds):
+        if not self._baseline:
+            return None
+        from .train import _Width            # (which node encoder is live follows the dataset's node-feature width)
+        return _Width(int(ds._f32_tables()["x"].shape[1]))
+
+    def _outputs(self, slot: Slot, n_real: int):
+        if not self._baseline:
+            return super()._outputs(slot, n_real)
+        out = slot.out
+        return (out[0], out[1][:n_real]) if self.model._returns_x else out[0]
+
+    def _eval_outputs(self, slot: Slot):
+        if not self._baseline:
+            return super()._eval_outputs(slot)
+        return slot.out[0], slot.keep.xL       # (mlp: its encoder output - what its decoder pools)
 
     def _forward(self, fp, slot):
         g = slot.g
+        if self._baseline:
+            out = self.model._program_fwd(fp.P, g, g.meta, factored_head=True)
+            return out[:-1], out[-1]
         dg, xL, ds, keep = self.model._program_fwd(fp.P, g, g.meta, per_crystal_keys=self.per_crystal_keys)
         return (dg, xL, ds), keep
 

@@ -25,7 +25,7 @@ import torch
 from . import functional as Fn
 from . import ops
 from ._lib import DosxError, from_environ
-from ._models import DOSTransformerBase, _SEED_MOD, rank_seed_offset
+from ._models import DOSTransformerBase, GraphnetworkBase, _SEED_MOD, rank_seed_offset
 from .batch import CrystalBatch, bucket_sizes, graph_meta, pad_batch
 from .slots import Slot, SlotCache
 
@@ -115,6 +115,13 @@ class _AdamWState:
             seed.add_(1)
 
 
+class _Width:
+    """Stands in for a batch where only the node-feature width matters (FusedModel._extra_dead reads ``g.x.shape[1]``)."""
+
+    def __init__(self, width: int):
+        self.x = torch.empty(0, int(width))
+
+
 class Trainer(_AdamWState, SlotCache):
     """AdamW(lr, weight_decay=1e-2) training of a DOSTransformer(_phonon) module, all on libdosx.
 
@@ -128,14 +135,34 @@ class Trainer(_AdamWState, SlotCache):
     phonon model and evaluates both (`main_phDOS.py:52-55`, `main_eDOS.py:55-56`); for eDOS the phantom node counts as an atom, as
     it does there.  Eager, ``replay=True`` and ``graph=True`` alike (the bucket's own ``graph_ptr`` is the operand); the loss is
     unchanged.  Not under data parallelism.
+
+    The GNN-only baselines - ``Graphnetwork``, ``Graphnetwork_phonon`` (fp32 parameters) and ``embedder_eDOS.mlp.mlp`` - train through
+    the same step (eager, ``replay=True``, ``graph=True``, ``step_dataset``, checkpoints) with their output head on its rank
+    structure (``functional.graphnetwork_fwd(factored_head=True)``) and the drivers' loss on their ONE output: phonon
+    ``sqrt(mean_all (dos - y)^2)`` (`main_phDOS.py:109-111`), eDOS ``mean_b sqrt(mean_s (dos - max(y, 0))^2)`` (`main_eDOS.py:111-118`).
+    With one output there is no ``beta`` to weigh (anything but 1.0 is refused), no attention to give per-crystal keys, and no
+    data parallelism yet; ``n_global`` must be the batch's own count.  Which node encoder is dead follows the input width and is
+    fixed by the first batch: a later batch of the other width is refused.
     """
 
     def __init__(self, model: DOSTransformerBase, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2,
                  betas=(0.9, 0.999), eps: float = 1e-8, dist=None, graph: bool = False, replay: bool = False,
                  bucket=(8, 128), max_slots: int = 32, promote: float = 0.0, per_crystal_keys: bool = False):
-        if not isinstance(model, DOSTransformerBase):
-            raise TypeError("Trainer drives DOSTransformer / DOSTransformer_phonon modules")
+        if not isinstance(model, (DOSTransformerBase, GraphnetworkBase)):
+            raise TypeError("Trainer drives DOSTransformer / DOSTransformer_phonon / Graphnetwork / Graphnetwork_phonon / mlp modules")
         model._require_fp32_program("Trainer")
+        self._baseline = isinstance(model, GraphnetworkBase)
+        self._dead = None                 # baselines: the dead-parameter set of the first batch's input width
+        if self._baseline:
+            name = type(model).__name__
+            if float(beta) != 1.0:
+                raise ValueError(f"Trainer({name}): beta={beta} - the model has ONE output and its loss no second term to weigh; "
+                                 f"only the default 1.0 is accepted")
+            if per_crystal_keys:
+                raise DosxError(f"Trainer({name}, per_crystal_keys=True): the model has no attention - a crystal's output "
+                                f"never depends on its batch mates")
+            if dist is not None:
+                raise DosxError(f"Trainer({name}, dist=...): data parallelism is not implemented for the GNN-only baselines")
         if per_crystal_keys and dist is not None:
             raise DosxError("Trainer(per_crystal_keys=True) is a single-GPU mode: not with dist (data parallelism)")
         self._per_crystal_keys = bool(per_crystal_keys)
@@ -181,6 +208,10 @@ class Trainer(_AdamWState, SlotCache):
             st_n_global = m.num_graphs
         model, dev, cfg = self.model, fp.flat.device, self.model._cfg
         B, S = m.num_graphs, cfg.S
+        if self._baseline:
+            out = model._program_fwd(fp.P, g, m, factored_head=True)
+            y = Fn._f32(g.phdos).reshape(B, S) if self.kind == "phonon" else Fn._f32(g.y_ft).reshape(-1)
+            return {"ctx": out[-1], "dos": out[0], "out": out[:-1] if model._returns_x else out[0], "B": B, "S": S, "y": y}
         dg, xL, ds, (ctx, dos) = model._program_fwd(fp.P, g, m, bump_seed=False,     # (step() bumps the dropout seed)
                                                     per_crystal_keys=self._per_crystal_keys)
         st = {"ctx": ctx, "dos": dos, "out": (dg, xL, ds), "B": B, "S": S}
@@ -198,6 +229,8 @@ class Trainer(_AdamWState, SlotCache):
         """loss gradient + backward program.  n_global: crystals in the un-sharded batch."""
         dev, cfg = fp.flat.device, self.model._cfg
         B, S, dos = st["B"], st["S"], st["dos"]
+        if self._baseline:
+            return self._part_b_baseline(fp, m, st, n_global)
         ddos = Fn._empty(dev, *dos.shape)
         if self.kind == "phonon":
             loss = Fn._empty(dev, 1)
@@ -219,6 +252,46 @@ class Trainer(_AdamWState, SlotCache):
         Fn.dostransformer_bwd(fp.P, fp.G, cfg, m, st["ctx"], ddos, None, sink, mid_hook=self._mid_hook(fp))
         sink.release()
         return loss
+
+    def _part_b_baseline(self, fp, m, st, n_global: int):
+        """One-output loss + backward program of a GNN-only baseline.  The loss entries in their one-output use (include/dosx.h:
+        ps = pg, beta = 0: the loss is rmse(pg) exactly, the second gradient goes to scratch)."""
+        dev = fp.flat.device
+        B, S, dos = st["B"], st["S"], st["dos"]
+        if int(n_global) != B:
+            raise ValueError(f"Trainer({type(self.model).__name__}): n_global={n_global} but the batch holds {B} crystals "
+                             f"(no data parallelism for the GNN-only baselines)")
+        ddos, scr = Fn._empty(dev, B, S), Fn._empty(dev, B, S)
+        if self.kind == "phonon":
+            loss = Fn._empty(dev, 1)
+            ops.loss_phonon(dos, dos, st["y"], None, 0.0, ddos, scr, loss, B * S)
+            loss = loss[0]
+        else:
+            lp = Fn._empty(dev, B + 1)
+            ops.loss_edos(dos, dos, st["y"], 0.0, B, S, B, ddos, scr, lp)
+            ops.sum_to(lp, B, lp[B:])
+            loss = lp[B]
+        sink = ops.GradSink(dev)
+        self.model._bwd_fn(fp.P, fp.G, self.model._cfg, m, st["ctx"], ddos, None, sink, factored_head=True)
+        sink.release()
+        return loss
+
+    def _flat_for(self, dev, g, width: Optional[int] = None):
+        """The model's flat parameters for a batch (or, step_dataset, an input width).  Baselines: which node encoder is dead
+        follows the width; the first batch fixes it for this trainer."""
+        model = self.model
+        if not self._baseline:
+            return model._ensure_flat(dev, g)
+        if g is None:
+            g = _Width(width)
+        dead = model._extra_dead(g)
+        if self._dead is None:
+            self._dead = dead
+        elif dead != self._dead:
+            raise DosxError(f"Trainer({type(model).__name__}): this batch has node features of width {g.x.shape[1]}, which selects "
+                            f"the other node encoder than the trainer's first batch did - its dead-parameter set (and the "
+                            f"optimizer's layout) is fixed by the first batch")
+        return model._ensure_flat(dev, g)
 
     # ---- data parallel: early gradient bucket ------------------------------------------------------
     def _mid_hook(self, fp):
@@ -289,7 +362,7 @@ class Trainer(_AdamWState, SlotCache):
         model = self.model
         dev = model._module_device()
         model._require_fp32_program("Trainer")
-        fp = model._ensure_flat(dev, g)
+        fp = self._flat_for(dev, g)
         self._state(fp)
         m = graph_meta(g, dev)
         ng = self._n_global(m.num_graphs, n_global, g)
@@ -385,7 +458,7 @@ class Trainer(_AdamWState, SlotCache):
         model = self.model
         dev = model._module_device()
         model._require_fp32_program("Trainer")
-        fp = model._ensure_flat(dev, g)
+        fp = self._flat_for(dev, g)
         self._state(fp)
         m = g.meta
         if m is None or m.edge_perm is not None:
@@ -417,7 +490,7 @@ class Trainer(_AdamWState, SlotCache):
         model = self.model
         dev = model._module_device()
         model._require_fp32_program("Trainer")
-        fp = model._ensure_flat(dev, None)
+        fp = self._flat_for(dev, None, int(ds._f32_tables()["x"].shape[1]))
         self._state(fp)
         idx, N, E, n_max = ds.bucket_dims(indices, n_max)
         B = int(idx.shape[0])

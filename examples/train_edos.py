@@ -11,6 +11,12 @@ featurize.build_edos_all - the route a list of real structures takes (`data/mat2
 
     python examples/train_edos.py --epochs 10 --crystals 512 --batch_size 64
     python examples/train_edos.py --structures 256 --epochs 1
+
+--embedder graphnetwork / mlp trains the reference's GNN-only baselines (`main_eDOS.py:71-81`) through the same Trainer and
+Predictor: their output head runs on its rank structure, the loss is the driver's on their one output, and evaluation always goes
+through evaluate.test_per_crystal (these models have no attention: batched passes ARE the batch-size-1 numbers).
+
+    python examples/train_edos.py --embedder graphnetwork --epochs 10
 """
 import argparse
 import os
@@ -44,6 +50,7 @@ def parse_args(argv=None):
     ap.add_argument("--attn_drop", type=float, default=0.0)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--beta", type=float, default=1.0)
+    ap.add_argument("--embedder", default="DOSTransformer", choices=["DOSTransformer", "graphnetwork", "mlp"])   # `utils.py:38`
     # (not upstream: the data source and the output file)
     ap.add_argument("--crystals", type=int, default=512, help="synthetic graphs to generate when no --pickle is given")
     ap.add_argument("--pickle", default=None)
@@ -85,19 +92,29 @@ def main(argv=None):
     print(f"train_dataset_len:{len(ds['train'])}\nvalid_dataset_len:{len(ds['valid'])}\ntest_dataset_len:{len(ds['test'])}")
 
     n_atom, n_bond = int(crystals[0]["x"].shape[1]), int(crystals[0]["edge_attr"].shape[1])
-    model = DOSTransformer(args.layers, args.transformer, n_atom, n_bond, 2, args.hidden, dev, args.attn_drop).to(dev)
+    baseline = args.embedder != "DOSTransformer"
+    if args.embedder == "graphnetwork":                             # `main_eDOS.py:71-81`
+        from dostransformer_amd.embedder_eDOS.graphnetwork import Graphnetwork
+        model = Graphnetwork(args.layers, n_atom, n_bond, 2, args.hidden, 201, dev).to(dev)
+    elif args.embedder == "mlp":
+        from dostransformer_amd.embedder_eDOS.mlp import mlp
+        model = mlp(args.layers, n_atom, n_bond, 2, args.hidden, 201, dev).to(dev)
+    else:
+        model = DOSTransformer(args.layers, args.transformer, n_atom, n_bond, 2, args.hidden, dev, args.attn_drop).to(dev)
+    if baseline and (args.per_crystal_keys or args.beta != 1.0):
+        raise SystemExit(f"--embedder {args.embedder} has one output and no attention: --beta and --per-crystal-keys do not apply")
     # coarse shape buckets: reshuffled batches fall into a few dozen (N, E) buckets, each recorded once (ghost padding is
     # exact); every batch pads its keys to the training set's largest crystal so that n_max is not a bucket dimension
     bucket = (32, 512)
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=bucket, promote=0.08,
                       per_crystal_keys=args.per_crystal_keys)      # AdamW(lr, weight_decay=1e-2), `:91`
-    predictor = Predictor(model, bucket=bucket, per_crystal_keys=args.eval_per_crystal > 0)
+    predictor = Predictor(model, bucket=bucket, per_crystal_keys=args.eval_per_crystal > 0 and not baseline)
     criterion_2 = torch.nn.L1Loss()                                                       # `main_eDOS.py:93`
 
     def run_test(name):
         """`utils.test` on a split -> (rmse, mse, mae, r2, ...): the reference's batch-size-1 numbers either way."""
-        if args.eval_per_crystal > 0:
-            return evaluate.test_per_crystal(predictor, ds[name], batch_size=args.eval_per_crystal).as_reference()
+        if args.eval_per_crystal > 0 or baseline:
+            return evaluate.test_per_crystal(predictor, ds[name], batch_size=args.eval_per_crystal or 64).as_reference()
         return evaluate.test(predictor, ds[name].batches(args.eval_batch_size), criterion_2, evaluate.r2)
 
     nmax_train = int(ds["train"].n_nodes.max())

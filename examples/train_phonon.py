@@ -20,6 +20,12 @@ keys as above, with the reference's loss of the batch as a whole - ONE rmse over
 the GPU straight into its bucket's static buffers (Trainer64.step_dataset) and evaluation replays too (predict.Predictor64).
 
     python examples/train_phonon.py --float64 --fused --replay --epochs 2 --crystals 128 --hidden 64
+
+--embedder graphnetwork trains the reference's GNN-only baseline (main_phDOS.py:74-76) through the fp32 Trainer and Predictor: its
+output head runs on its rank structure, the loss is the driver's on its one output, and evaluation goes through
+evaluate.test_per_crystal (no attention: batched passes ARE the batch-size-1 numbers).  fp32 only.
+
+    python examples/train_phonon.py --embedder graphnetwork --epochs 5
 """
 import argparse
 import os
@@ -45,6 +51,7 @@ def main(argv=None):
     ap.add_argument("--hidden", type=int, default=128)
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--beta", type=float, default=1.0)
+    ap.add_argument("--embedder", default="DOSTransformer_phonon", choices=["DOSTransformer_phonon", "graphnetwork"])   # utils.py:38
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--r-max", type=float, default=4.0)       # main_phDOS.py:21
@@ -65,6 +72,9 @@ def main(argv=None):
         ap.error("--eval-per-crystal needs a replayed predictor: the fp32 run, or --float64 --fused --replay")
     if args.fused and not args.float64:
         ap.error("--fused selects the float64 trainer: use it with --float64 (the fp32 run is fused already)")
+    baseline = args.embedder == "graphnetwork"
+    if baseline and (args.float64 or args.per_crystal_keys or args.beta != 1.0):
+        ap.error("--embedder graphnetwork: the fused fp32 path only (one output, no attention): no --float64, --per-crystal-keys, --beta")
     if args.replay and not args.fused:
         ap.error("--replay belongs to --float64 --fused (the fp32 run always replays)")
     dev = torch.device("cuda:0")
@@ -84,12 +94,18 @@ def main(argv=None):
 
     if args.float64:
         return train_float64_fused(args, ds, dev) if args.fused else train_float64(args, ds, dev)
-    model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).to(dev)
+    if baseline:
+        from dostransformer_amd.embedder_phDOS.graphnetwork_phonon import Graphnetwork_phonon
+        model = Graphnetwork_phonon(args.layers, 118, 4, args.hidden, 51, dev).to(dev)
+        if args.eval_per_crystal <= 0:
+            args.eval_per_crystal = args.batch_size      # (its predictor returns one DOS: the per-crystal evaluator reads it)
+    else:
+        model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).to(dev)
     # coarse shape buckets: reshuffled batches then fall into a few dozen (N, E, n_max) buckets that are all recorded
     # within the first epoch (ghost padding is exact; it costs a few per cent of extra rows)
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=(32, 1024), promote=0.08,
                       per_crystal_keys=args.per_crystal_keys)
-    predictor = Predictor(model, bucket=(32, 1024), per_crystal_keys=args.eval_per_crystal > 0)
+    predictor = Predictor(model, bucket=(32, 1024), per_crystal_keys=args.eval_per_crystal > 0 and not baseline)
     run_test = _tester(args, predictor, ds)
     best, history = float("inf"), []
     for epoch in range(args.epochs):

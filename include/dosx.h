@@ -483,7 +483,12 @@ int dosx_rowdot_bwd(const float* ddos, const float* x, const float* w, float* dx
  *   dosx_sse2 writes sse[0..1]; dosx_loss_phonon_bwd consumes (possibly all-reduced) sse and
  *   `count` = global number of elements.
  * eDOS (main_eDOS.py:111-123): loss = mean_b rmse_b(global) + beta * mean_b rmse_b(system),
- *   target clamped at 0; `B_global` = number of crystals in the un-sharded batch. */
+ *   target clamped at 0; `B_global` = number of crystals in the un-sharded batch.
+ * ONE-OUTPUT callers (the GNN-only baselines: main_phDOS.py:109-111 / main_eDOS.py:111-118 with their single DOS output) use the
+ *   same entries: ps = pg (inputs may alias: they are only read), beta = 0, dps = scratch of the same size (distinct from dpg).
+ *   Then loss = rmse(pg) + 0 * rmse(pg) = the one-output loss EXACTLY (every rmse is finite), dpg is its gradient, and dps
+ *   receives 0 (or NaN where the rmse is 0: 0/0 - scratch, never read).  That is within the contract above; nothing here
+ *   depends on beta != 0 or on pg != ps. */
 int dosx_sse2(const float* pg, const float* ps, const float* y, float* sse, int count, dosx_stream_t stream);
 int dosx_loss_phonon_bwd(const float* pg, const float* ps, const float* y, const float* sse, float beta,
                          double count_global, float* dpg, float* dps, float* loss, int count,
@@ -645,6 +650,33 @@ typedef struct DosxHeadsBwd {
 } DosxHeadsBwd;
 int dosx_heads_bwd_supported(int H);
 int dosx_heads_bwd(const DosxHeadsBwd* a, dosx_stream_t stream);
+
+/* The output head of the GNN-only baselines (graphnetwork_phonon.py:26,66-70, graphnetwork.py:22,38-42, mlp.py:20,30-34) on its rank
+ * structure (csrc/pair_head.hip).  The head's input row (s, b) is cat[emb[s] | graph[b]], so its first Linear is e1[s] + c[b] with
+ * e1 = emb . W0[:, :H]^T + b0 and c = graph . W0[:, H:]^T (two small dosx_gemm calls); then, one launch each:
+ *   dosx_pair_head_fwd:  dos[b, s] = b2[0] + sum_h w2[h] * leaky(e1[s, h] + c[b, h])              leaky(p) = p > 0 ? p : slope * p
+ *   dosx_pair_head_bwd:  gate = e1[s, h] + c[b, h] > 0 ? 1 : slope                                (torch's rule: 0 takes slope)
+ *                        de1[s, h] = w2[h] * sum_b ddos[b, s] * gate      dc[b, h] = w2[h] * sum_s ddos[b, s] * gate
+ *                        partials[s] = [ sum_b ddos[b, s] * leaky(e1[s, :] + c[b, :])  (H)  |  sum_b ddos[b, s] ]
+ *     - dosx_pair_head_partial_rows(S, B) (= S) rows of H + 1 floats whose column sums are dw2 and db2 (dosx_reduce_partials).
+ * No tensor of S * B * H elements is read or written.  Every sum is one thread's sequential chain (dc: four of them added in a
+ * fixed order): no float atomics, two launches on the same operands give the same bits.  e1, c, de1, dc are contiguous rows of H
+ * floats, 16-byte aligned like w2; dos and ddos are [B, S] row-major.  H % 8 == 0, H <= 512, any S, B >= 1 with S * B * H < 2^31;
+ * anything else is refused with -22.  The forward reads e1, c, w2, b2 and writes dos; the backward reads e1, c, w2, ddos and
+ * writes de1, dc, partials; the other side's fields may be NULL. */
+typedef struct DosxPairHead {
+  int32_t S, B, H;
+  float slope;                                                /* leaky_relu negative slope (0.01) */
+  const float* e1; const float* c;                            /* [S, H], [B, H] */
+  const float* w2; const float* b2;                           /* [H], [1] */
+  float* dos;                                                 /* [B, S] OUT (forward) */
+  const float* ddos;                                          /* [B, S] (backward) */
+  float* de1; float* dc;                                      /* [S, H], [B, H] OUT (backward) */
+  float* partials;                                            /* [S, H + 1] OUT (backward) */
+} DosxPairHead;
+int dosx_pair_head_partial_rows(int S, int B);
+int dosx_pair_head_fwd(const DosxPairHead* a, dosx_stream_t stream);
+int dosx_pair_head_bwd(const DosxPairHead* a, dosx_stream_t stream);
 
 /* Split-bf16 GEMM (round 6, csrc/gemm_bf16x3.hip) - OPT-IN: with DOSX_FFN_BF16X3=1 functional.encoder_fwd / encoder_bwd run the
  * plain feed-forward GEMMs through it; by default every program runs dosx_gemm's exact-fp32 kernels:
