@@ -1513,7 +1513,9 @@ static int gemm_validate(const DosxGemm& g) {
   DOSX_CHECK_ARG(g.w && (g.out || g.epi == DOSX_EPI_SEGSUM), "dosx_gemm: null w/out");
   const bool full_row = (g.epi == DOSX_EPI_LN || g.epi == DOSX_EPI_PRELU_LN_BWD || g.epi == DOSX_EPI_ROWLN_BWD || g.epi == DOSX_EPI_PRELU_LN_BWD_SEG);
   DOSX_CHECK_ARG(!full_row || g.N <= 512, "dosx_gemm: row-wise epilogue needs N <= 512 (hidden <= 256), got %d", g.N);
-  DOSX_CHECK_ARG(!g.stats_out || g.N <= 128 * 4, "dosx_gemm: stats_out needs N <= 512");
+  // (only the plain epilogue writes stats_out, yet gemm_plan widens the column tile for it: behind PRELU_BWD the call would
+  //  then fill one partial row per row block where dosx_gemm_partial_rows promises one per 128 columns)
+  DOSX_CHECK_ARG(!g.stats_out || (g.N <= 128 * 4 && g.epi == DOSX_EPI_BIAS_ACT), "dosx_gemm: stats_out needs the plain epilogue and N <= 512");
   DOSX_CHECK_ARG(!g.norm_out || (g.N <= 128 * 4 && g.norm_rstd && g.epi == DOSX_EPI_BIAS_ACT && aligned16(g.norm_out)),
                  "dosx_gemm: norm_out needs the plain epilogue, N <= 512 and norm_rstd");
   DOSX_CHECK_ARG(g.out_map.d > 0, "dosx_gemm: out_map.d must be > 0");

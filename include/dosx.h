@@ -101,7 +101,7 @@ typedef struct DosxGemm {
   const float* res;
   int32_t ldr;
   DosxRowMap res_map;
-  float* stats_out;   /* optional [M,2]: mean, rstd of the final output rows (needs N <= tile) */
+  float* stats_out;   /* EPI_BIAS_ACT only (refused behind any other epilogue), optional [M,2], N <= 512: mean, rstd of the final output rows */
   float* aux_out;     /* EPI_LN: rstd [M] */
   const float* aux;   /* backward epilogues: xhat / h / x / z, [M, ldaux] */
   int32_t ldaux;

@@ -440,3 +440,86 @@ def test_host_policies_are_those_of_the_commit_that_folded_their_switches():
     assert want["gemm_kernel_name"]["unaligned_atom_features"].endswith("0, 0, 0>")
     assert {n.split("<")[1][0] for n in want["gemm_kernel_name"].values()} == set("0123")
     assert set(want["wgrad_splits"]) >= {1, 8, 64} and set(want["ffn_att_aligned_rows"]) == {16, 32}
+
+
+def test_gemm_census_is_complete():
+    """tests/gemm_census.py lists every instantiation of gemm_kernel / gemm_mixed_kernel / gemm_pair_kernel a valid descriptor
+    reaches.  (1) dosx_gemm_kernel_name over the policy grid of M, tile-straddling N, every family, stats_out / norm_out set and
+    clear names nothing without a census row; (2) every row's shapes still select the kernel the row names, leave one row / all
+    but one row in the last tile, and are the smallest that do; a tail split shows in dosx_gemm_partial_rows exactly where the
+    census says; (3) what the census lists as refused is refused, before any launch.  A new instantiation or a moved policy
+    threshold fails here, on the CPU."""
+    from dostransformer_amd import _abi, _lib
+    from tests import gemm_census as cen
+    lib = _lib.load()
+    name = lambda M, N, fam, pro, epi, extra="", K=64: cen.kernel_name(lib, cen.fake_desc(M, N, K, fam, pro, epi, extra))
+    known = {}
+    for fam, pro, epi, extra, kernel, *_ in cen.ROWS + cen.REFUSED:
+        known.setdefault((fam, pro, epi), set()).add(kernel)
+    for fam, pro, epi, kernel, *_ in cen.SEG_ROWS:
+        known.setdefault((fam, pro, epi), set()).add(kernel)
+    assert len({k for v in known.values() for k in v}) == len(cen.ROWS) + len(cen.SEG_ROWS) + len(cen.REFUSED)   # no kernel twice
+    assert cen.n_instantiations() == 117
+    # (1) the sweep.  Left out: what gemm_validate refuses by shape alone (a full-row epilogue, stats_out or norm_out beyond 512
+    # columns, node-aligned tiles beyond 256) and norm_out behind another epilogue than the plain one
+    full_row = ("LN", "PRELU_LN_BWD", "ROWLN_BWD", "PRELU_LN_BWD_SEG")
+    swept = set()
+    for fam, (wl, vec, pros, epis) in cen.FAMILIES.items():
+        for pro in pros:
+            for epi in epis:
+                for extra in ("", "stats", "norm"):
+                    if extra == "norm" and epi != "BIAS_ACT":
+                        continue
+                    for N in cen.SWEEP_N:
+                        if N > 512 and (extra or epi in full_row) or N > 256 and epi in ("SEGSUM", "PRELU_LN_BWD_SEG"):
+                            continue
+                        for M in _POLICY_M:
+                            k = name(M, N, fam, pro, epi, extra)
+                            assert k in known[(fam, pro, epi)], (k, fam, pro, epi, extra, M, N)
+                            swept.add(k)
+    assert len(swept) == len(cen.ROWS) + len(cen.SEG_ROWS) + len(cen.REFUSED)              # and the grid reaches every row
+    # (2) the rows
+    for fam, pro, epi, extra, kernel, *shapes in cen.ROWS:
+        h = cen.tile_rows(kernel)
+        for N, m_one, m_short in shapes:
+            assert m_one % h == 1 and m_short % h == h - 1 and min(m_one, m_short) > h, (kernel, N)
+            for M in (m_one, m_short):
+                assert name(M, N, fam, pro, epi, extra) == kernel, (kernel, M, N)
+                assert extra or not cen.is_split(lib, M, N, epi, kernel), (kernel, M, N)
+            assert m_one - h <= h or name(m_one - h, N, fam, pro, epi, extra) != kernel, (kernel, N, "not the smallest")
+    for fam, pro, epi, kernel, n_full, n_rag in cen.SEG_ROWS:
+        assert {name(M, N, fam, pro, epi) for M in (1, 700, 20000) for N in (n_full, n_rag)} == {kernel}
+    for fam, pro, epi, mixed, head, *shapes in cen.MIXED_ROWS:
+        ha, hb = (cen.TILE_ROWS[int(v)] for v in re.match(r"gemm_mixed_kernel<(\d), (\d)", mixed).groups())
+        assert ha == cen.tile_rows(head) and mixed.split(", ", 2)[2] == head.split(", ", 1)[1]      # same NTW, WL, PRO, VEC, EPI
+        for N, m_one, m_short, p_one, p_short in shapes:
+            for M, p in ((m_one, p_one), (m_short, p_short)):
+                assert name(M, N, fam, pro, epi) == head and cen.is_split(lib, M, N, epi, head), (mixed, M, N)
+                assert lib.dosx_gemm_partial_rows(M, N, getattr(_abi, "DOSX_EPI_" + epi)) == p, (mixed, M, N)
+                tiles = -(-N // (128 * int(head.split(", ")[1])))                     # column tiles: 256 / tiles head tiles a round
+                full = M // (256 // tiles * ha) * (256 // tiles * ha)
+                assert p == full // ha + -(-(M - full) // hb) and (M - full) % hb in (1, hb - 1), (mixed, M, N)
+    for kernel, head, extra, n_full, n_rag, m1, m2 in cen.PAIR_ROWS:
+        rt, ntw = re.match(r"gemm_pair_kernel<(\d), (\d)>", kernel).groups()
+        assert head == f"gemm_kernel<{rt}, {ntw}, 0, 0, 1, 0>"
+        for N in (n_full, n_rag):
+            assert name(m1 + m2, N, "plain_nk", "NONE", "BIAS_ACT", extra) == head, (kernel, N)
+            for M in (m1, m2):                                       # (each problem alone plans the same column tile)
+                assert name(M, N, "plain_nk", "NONE", "BIAS_ACT", extra).split(", ")[1] == ntw, (kernel, M, N)
+    kernel, head_a, head_b, N, m1, m2 = cen.PAIR_MIXED
+    assert name(m1, N, "bwd", "NONE", "PRELU_BWD") == head_a and name(m2, N, "bwd", "NONE", "PRELU_BWD") == head_b
+    assert not cen.is_split(lib, m1, N, "PRELU_BWD", head_a) and not cen.is_split(lib, m2, N, "PRELU_BWD", head_b)
+    # (3) refused before any launch (the addresses are never dereferenced)
+    ident = _lib.RowMap(1 << 30, 0, 1, 0, None)
+
+    def refused(g, msg):
+        g.a[0].p, g.a[0].map, g.w, g.out, g.ldo, g.out_map = 0x10000, ident, 0x20000, 0x30000, g.N, ident
+        g.pro_gamma = g.pro_beta = g.pro_alpha = g.pro_stats = g.aux = g.epi_alpha = 0x40000
+        g.ldaux = g.N
+        assert lib.dosx_gemm(C.byref(g), None) == -22 and msg.encode() in lib.dosx_last_error(), (msg, lib.dosx_last_error())
+
+    for fam, pro, epi, extra, kernel, M, N, msg in cen.REFUSED:
+        assert name(M, N, fam, pro, epi, extra) == kernel
+        refused(cen.fake_desc(M, N, 64, fam, pro, epi, extra), msg)
+    # no descriptor reaches the generic staging path with N % 4 != 0: the output rows are stored as float4
+    refused(cen.fake_desc(100, 130, 41, "generic_nk", "NONE", "BIAS_ACT"), "4-float aligned")
