@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "dkv_reduce.h"
 
 // Diagnostic build only (-DDOSX_STAMPS): wave 0 of workgroup (0,0) records s_memtime at phase boundaries.
 #ifdef DOSX_STAMPS
@@ -623,9 +624,6 @@ __global__ __launch_bounds__(512) void attn_fwd_stream_kernel(const DosxAttn a) 
 // <= 12 atoms, self attention over 51 bins): that kernel re-streamed every dO / x row and the dS round trip through HBM
 // behind one barrier per 16 queries - 27 us per launch for 0.08 GF - where this costs 32-64 MFMAs per wave.
 constexpr int DKR = 16;          // key rows per reduction group = partial-sum rows per crystal: ceil(Nk / 16)
-template <bool SC1, bool KP>
-__device__ __forceinline__ void dkv_reduce_group(const DosxAttn& a, const int nqt, const int grp, const int ngroups,
-                                                 const int bk, float (*Pp)[2 * 256], const int tid);
 
 template <int NJ, bool PKV, bool RESIDENT, bool KP>
 __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(const DosxAttn a) {
@@ -933,23 +931,18 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_stream_kernel(const DosxAttn 
       // publish, every wave drains, barrier, one ticket per workgroup on the key crystal's counter).  The workgroup that
       // draws the last ticket of crystal bk - rep * tiles arrive - runs the reduction groups the stand-alone
       // attn_dkv_reduce_kernel would run, in the same order with the same arithmetic: bitwise the two-launch result.
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      int* flag = reinterpret_cast<int*>(sm);
-      const int arrivers = (a.Bq / a.Bk) * (int)gridDim.x;
-      if (tid == 0) *flag = dosx_ticket(a.dkv_cnt + bk);
-      __syncthreads();
-      const bool last = *flag == arrivers - 1;
+      // (the staging waves 4-7 have returned: the 256 threads of the matrix waves are the workgroup from here on)
+      const int nqt = (int)gridDim.x;
+      const bool last = dosx_last_arriver_wg(a.dkv_cnt, bk, (a.Bq / a.Bk) * nqt, reinterpret_cast<int*>(sm), tid);
       __syncthreads();                                  // (the flag word is about to be overwritten by the reduction's LDS rows)
       if (last) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const int ngroups = (Nk + DKR - 1) / DKR;
-        float (*PpR)[2 * 256] = reinterpret_cast<float (*)[2 * 256]>(sm);
-        for (int grp = 0; grp < ngroups; ++grp) {
-          dkv_reduce_group<true, KP>(a, (int)gridDim.x, grp, ngroups, bk, PpR, tid);
+        const DkvReduce r = dkv_reduce_operands(a);
+        for (int grp = 0; grp < (Nk + DKR - 1) / DKR; ++grp) {
+          dosx_dkv_reduce<KCB, 0, 4, KP, 1, 256, true>(r, nqt, nqt, bk, grp, sm, tid);     // sm: [16][2 * 256]
           __syncthreads();
         }
-        if (tid == 0) __hip_atomic_store(a.dkv_cnt + bk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) dosx_counter_reset(a.dkv_cnt + bk);
       }
     }
   }
@@ -1221,91 +1214,15 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(const DosxAttn a) {
   }
 }
 
-// Sum of the partial key gradients + the key-side chain rule (see attn_bwd_dq_stream_kernel<.., PKV>):
-//   d[j]       = sum_{i < Bq/Bk} sum_{tile} part[bk + i*Bk][tile][j][:]          (fixed order: deterministic)
-//   dkvhat[j] (+)= d[j] * gamma0 ;  partial dgamma0 += d[j] * k̂[j] ;  partial dbeta0 += d[j]
-// One workgroup per (16 key rows, crystal), one quarter wave per key row, the partials of a row fetched 4 at a time.
-// (First version: one workgroup per crystal walking its rows 16 at a time - 7.3 us avg at cfg2, 67 us for the 37 MB of
-// partials of an eDOS cross-attention layer on 64 workgroups.)
-// One group of DKR key rows of crystal bk, by 256 threads (tid256); Pp: [16][512] floats of LDS; ngroups = ceil(Nk / DKR).
-// SC1: the partials were published by OTHER workgroups of this launch (fused form: the last arriving dq workgroup of a
-// crystal runs this) - every load of them is then an sc1 load (bypasses this CU's L1).  Contains a barrier.
-template <bool SC1, bool KP>
-__device__ __forceinline__ void dkv_reduce_group(const DosxAttn& a, const int nqt, const int grp, const int ngroups,
-                                                 const int bk, float (*Pp)[2 * 256], const int tid) {
-  const int lane = tid & 63, wave = tid >> 6, q16 = lane & 15, slot = wave * 4 + (lane >> 4);
-  const int H = a.H, Nk = a.Nk, rep = a.Bq / a.Bk;
-  const int j = grp * DKR + slot;
-  const bool jv = j < dosx_live_keys<KP>(a.key_ptr, bk, Nk);  // (KP: a row past the crystal's own keys is no key - zeros)
-  const int jc = jv ? j : 0;
-  const size_t krow = ((size_t)jc * a.Bk + bk) * H;
-  float4 g0[KCB], d[KCB], kh[KCB], d0[KCB];
-#pragma unroll
-  for (int k = 0; k < KCB; ++k) {
-    const int c = q16 * 4 + 64 * k, cc = c < H ? c : 0;
-    g0[k] = ld4(a.gamma0 + cc);
-    kh[k] = (!KP || jv) ? ld4(a.kvhat + krow + cc) : f4zero();
-    d0[k] = (a.dkv_accumulate && (!KP || jv)) ? ld4(a.dkvhat + krow + cc) : f4zero();
-    d[k] = f4zero();
-  }
-  const int np = (KP && !jv) ? 0 : rep * nqt;        // partials of this key row, in (i, tile) order (none for a row that is no key)
-  const size_t pstride = (size_t)Nk * H;             // between consecutive tiles of one query batch entry
-  const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)a.dkv_part, 0, 0x7fffffff, 0x00020000);
-  for (int p0 = 0; p0 < np; p0 += 4) {
-    float4 v[4][KCB];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int pi = min(p0 + u, np - 1), i = pi / nqt, t = pi % nqt;
-      const size_t off = ((size_t)(bk + i * a.Bk) * nqt + t) * pstride + (size_t)jc * H;
-#pragma unroll
-      for (int k = 0; k < KCB; ++k) {
-        const int c = q16 * 4 + 64 * k;
-        if constexpr (SC1)
-          v[u][k] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rP, (uint32_t)((off + (c < H ? c : 0)) * 4), 0, 16));
-        else
-          v[u][k] = ld4(a.dkv_part + off + (c < H ? c : 0));
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (p0 + u < np) {
-#pragma unroll
-        for (int k = 0; k < KCB; ++k) d[k] = f4add(d[k], v[u][k]);
-      }
-  }
-#pragma unroll
-  for (int k = 0; k < KCB; ++k) {
-    const int c = q16 * 4 + 64 * k;
-    float4 pg = f4zero(), pb = f4zero();
-    if (jv && c < H) {
-      pg = make_float4(d[k].x * kh[k].x, d[k].y * kh[k].y, d[k].z * kh[k].z, d[k].w * kh[k].w);
-      pb = d[k];
-      st4(a.dkvhat + krow + c, make_float4(d[k].x * g0[k].x + d0[k].x, d[k].y * g0[k].y + d0[k].y,
-                                           d[k].z * g0[k].z + d0[k].z, d[k].w * g0[k].w + d0[k].w));
-    }
-    if constexpr (KP) {
-      if (!jv && j < Nk && c < H && !a.dkv_accumulate) st4(a.dkvhat + ((size_t)j * a.Bk + bk) * H + c, f4zero());
-    }
-    if (c < 256) {
-      st4(&Pp[slot][c], pg);
-      st4(&Pp[slot][256 + c], pb);
-    }
-  }
-  __syncthreads();
-  float* prow = a.partials_kv + ((size_t)bk * ngroups + grp) * 2 * H;
-  for (int c = tid; c < 2 * H; c += 256) {
-    const int o = (c / H) * 256 + (c % H);
-    float t = 0.f;
-#pragma unroll
-    for (int sl = 0; sl < 16; ++sl) t += Pp[sl][o];
-    prow[c] = t;
-  }
-}
-
+// The key gradient from the shares attn_bwd_dq_stream_kernel<.., PKV> left in dkv_part (dkv_reduce.h; one share per query tile:
+// wpc = nqt): one workgroup per (DKR = 16 key rows, crystal), one quarter wave per key row, the shares of a row fetched 4 at a
+// time.  (First version: one workgroup per crystal walking its rows 16 at a time - 7.3 us avg at cfg2, 67 us for the 37 MB of
+// partials of an eDOS cross-attention layer on 64 workgroups.)  The fused tail of the dq kernel runs the same groups in order.
 template <bool KP>
 __global__ __launch_bounds__(256) void attn_dkv_reduce_kernel(const DosxAttn a, int nqt) {
   __shared__ float Pp[16][2 * 256];                 // per quarter-wave slot: [dgamma | dbeta] (H <= 256)
-  dkv_reduce_group<false, KP>(a, nqt, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y, Pp, (int)threadIdx.x);
+  const DkvReduce r = dkv_reduce_operands(a);
+  dosx_dkv_reduce<KCB, 0, 4, KP, 1, 256, false>(r, nqt, nqt, (int)blockIdx.y, (int)blockIdx.x, &Pp[0][0], (int)threadIdx.x);
 }
 
 size_t fwd_smem(const Geo& g, bool resident = false) {      // (resident: all key chunks at once + the four partial score tiles)

@@ -11,13 +11,13 @@
 // tile per workgroup, keys re-staged per tile, 4 matrix waves) ran at 9-13 % of the fp32 MFMA peak in the Electron-DOS step.
 // Backward: a workgroup keeps its share of dK^ = P'^T.dO + dS^T.Q in registers ACROSS its tiles (one [Nk, H] share per
 // workgroup instead of one per tile), publishes it to its slot of dkv_part, takes a ticket on the key crystal's counter, and the
-// last arriver sums the shares in (query batch entry, workgroup) order, applies the key-side chain rule and writes dkvhat and the
-// key-side [dgamma | dbeta] partial rows - DosxAttn's one-launch contract (include/dosx.h: dkv_part + dkv_cnt).  The query-side
+// last arriver finishes the key gradient (dkv_reduce.h) - DosxAttn's one-launch contract (include/dosx.h).  The query-side
 // [dgamma | dbeta] partial rows: one per WORKGROUP in row (bq * nqt + w), the rows of the tiles it also owned are zeroed.
 // Deterministic: fixed tile -> workgroup assignment, fixed summation orders.
 #include <stdlib.h>
 
 #include "common.h"
+#include "dkv_reduce.h"
 #include "mma16.h"
 
 #ifdef DOSX_STAMPS
@@ -354,93 +354,6 @@ __global__ __launch_bounds__(512) void attn_al_fwd_kernel(const DosxAttn a, cons
 // ------------------------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------------------------
-// Sum of the np = rep * wpc shares of key crystal bk's gradient (share (i, w) in slot ((bk + i Bk) nqt + w) of dkv_part), all
-// <= 64 key rows at once (two per quarter-wave slot), key-side chain rule, dkvhat (+)=, and per group of 16 key rows the
-// [dgamma | dbeta] partial row (slots added in row order: the layout dosx_attention_bwd's dkv_part path documents).
-// Pp: [64][2 * 64 NG] floats of LDS.  Contains a barrier.
-template <int NG, bool KP>
-__device__ __forceinline__ void al_dkv_reduce(const DosxAttn& a, const int nqt, const int wpc, const int bk, float* __restrict__ Pp,
-                                              const int tid) {
-  constexpr int HP = 64 * NG, U = NG <= 2 ? 4 : 2;
-  const int lane = tid & 63, q16 = lane & 15, slot = tid >> 4;                 // 32 slots
-  constexpr int H = 64 * NG;
-  const int Nk = a.Nk, rep = a.Bq / a.Bk, ngroups = (Nk + 15) / 16;
-  const int nk = dosx_live_keys<KP>(a.key_ptr, bk, Nk);  // (KP: a row past the crystal's own keys is no key - zeros)
-  const int np = (KP && slot >= nk) ? 0 : rep * wpc;     // (KP: neither of this slot's rows is a key - nothing to sum)
-  const size_t pstride = (size_t)Nk * H;
-  const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)a.dkv_part, 0, 0x7fffffff, 0x00020000);
-  float4 g0[NG], d[2][NG], kh[2][NG], d0[2][NG];
-  bool jv[2];
-  size_t krow[2];
-#pragma unroll
-  for (int k = 0; k < NG; ++k) g0[k] = ld4(a.gamma0 + ((q16 * 4 + 64 * k) < H ? (q16 * 4 + 64 * k) : 0));
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const int j = slot + 32 * p;
-    jv[p] = j < nk;
-    krow[p] = ((size_t)(jv[p] ? j : 0) * a.Bk + bk) * H;
-#pragma unroll
-    for (int k = 0; k < NG; ++k) {
-      const int c = q16 * 4 + 64 * k, cc = c < H ? c : 0;
-      kh[p][k] = (!KP || jv[p]) ? ld4(a.kvhat + krow[p] + cc) : f4zero();
-      d0[p][k] = (a.dkv_accumulate && (!KP || jv[p])) ? ld4(a.dkvhat + krow[p] + cc) : f4zero();
-      d[p][k] = f4zero();
-    }
-  }
-  for (int p0 = 0; p0 < np; p0 += U) {
-    float4 v[2][U][NG];
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int pi = min(p0 + u, np - 1), i = pi / wpc, ww = pi - i * wpc;
-        const size_t off = ((size_t)(bk + i * a.Bk) * nqt + ww) * pstride + (size_t)(jv[p] ? slot + 32 * p : 0) * H;
-#pragma unroll
-        for (int k = 0; k < NG; ++k) {
-          const int c = q16 * 4 + 64 * k;
-          v[p][u][k] = (KP && !jv[p]) ? f4zero()         // (no key: nothing was published for it, nothing is fetched)
-                                      : __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rP, (uint32_t)((off + (c < H ? c : 0)) * 4), 0, 16));   // sc1
-        }
-      }
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-        if (p0 + u < np) {
-#pragma unroll
-          for (int k = 0; k < NG; ++k) d[p][k] = f4add(d[p][k], v[p][u][k]);
-        }
-  }
-#pragma unroll
-  for (int p = 0; p < 2; ++p)
-#pragma unroll
-    for (int k = 0; k < NG; ++k) {
-      const int c = q16 * 4 + 64 * k;
-      float4 pg = f4zero(), pb = f4zero();
-      if (jv[p] && c < H) {
-        pg = make_float4(d[p][k].x * kh[p][k].x, d[p][k].y * kh[p][k].y, d[p][k].z * kh[p][k].z, d[p][k].w * kh[p][k].w);
-        pb = d[p][k];
-        st4(a.dkvhat + krow[p] + c, make_float4(d[p][k].x * g0[k].x + d0[p][k].x, d[p][k].y * g0[k].y + d0[p][k].y,
-                                                d[p][k].z * g0[k].z + d0[p][k].z, d[p][k].w * g0[k].w + d0[p][k].w));
-      }
-      if constexpr (KP) {
-        if (!jv[p] && slot + 32 * p < Nk && c < H && !a.dkv_accumulate)
-          st4(a.dkvhat + ((size_t)(slot + 32 * p) * a.Bk + bk) * H + c, f4zero());
-      }
-      st4(Pp + (slot + 32 * p) * 2 * HP + c, pg);
-      st4(Pp + (slot + 32 * p) * 2 * HP + HP + c, pb);
-    }
-  __syncthreads();
-  for (int o = tid; o < ngroups * 2 * H; o += 512) {
-    const int grp = o / (2 * H), c = o - grp * 2 * H;
-    const int col = (c / H) * HP + (c % H);
-    float t = 0.f;
-#pragma unroll
-    for (int sl = 0; sl < 16; ++sl) t += Pp[(grp * 16 + sl) * 2 * HP + col];
-    a.partials_kv[((size_t)bk * ngroups + grp) * 2 * H + c] = t;
-  }
-}
-
 template <int NG, bool KP>
 __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, const AlGeo geo) {
   DOSX_SET_MAIN_PRIO();
@@ -701,18 +614,14 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
   }
   // ---- ticket: the last arriving workgroup of key crystal bk finishes its key gradient ----
   ASTAMP(61);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  int* flag = reinterpret_cast<int*>(sm);
-  const int arrivers = (a.Bq / a.Bk) * wpc;
-  if (tid == 0) *flag = dosx_ticket(a.dkv_cnt + bk);
-  __syncthreads();
-  const bool last = *flag == arrivers - 1;
+  const bool last = dosx_last_arriver_wg(a.dkv_cnt, bk, (a.Bq / a.Bk) * wpc, reinterpret_cast<int*>(sm), tid);
   __syncthreads();                     // (the flag word is about to be overwritten by the reduction's LDS rows)
   if (last) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    al_dkv_reduce<NG, KP>(a, nqt, wpc, bk, sm, tid);
-    if (tid == 0) __hip_atomic_store(a.dkv_cnt + bk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // all <= 64 key rows at once, two per quarter-wave slot: sm = [64][2 * 64 NG] floats (al_bwd_smem)
+    const DkvReduce r = dkv_reduce_operands(a);
+    dosx_dkv_reduce<NG, 64 * NG, NG <= 2 ? 4 : 2, KP, 2, 512, true>(r, nqt, wpc, bk, 0, sm, tid);
+    if (tid == 0) dosx_counter_reset(a.dkv_cnt + bk);
   }
   ASTAMP(63);
 }

@@ -186,3 +186,30 @@ __device__ __forceinline__ float dosx_psum_one(int nk) {
 __device__ __forceinline__ int dosx_ticket(int* counter) {
   return __hip_atomic_fetch_add(counter, 1, DOSX_TICKET_ORDER, __HIP_MEMORY_SCOPE_AGENT);
 }
+// The hand-over of a last-arriver reduction, behind the publishing stores.  Workgroup-wide: every wave drains, barrier, thread 0
+// draws the ticket into `flag_word` (LDS), barrier; true in the workgroup that drew the last of `arrivers` tickets.  Every thread
+// of the workgroup that is still running calls it.  A caller that reuses flag_word's LDS puts one more barrier behind it.
+// (The counter array comes by reference, its element's index and the caller's tid / lane as values: pointer and address are then
+// formed where the hand-written sequence formed them, inside the one-lane branch, and wgrad_finish and the edge kernels compile
+// to the instruction streams they had.)
+// The last arriver then issues `__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront")` (no instruction: it keeps the compiler from
+// moving the read-back loads above the ticket) in front of its sc1 loads, and ends with dosx_counter_reset.
+__device__ __forceinline__ bool dosx_last_arriver_wg(int* const& counters, int index, int arrivers, int* flag_word, int tid) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (tid == 0) *flag_word = dosx_ticket(counters + index);
+  __syncthreads();
+  return *flag_word == arrivers - 1;
+}
+// Wave-wide, where ONE wave published everything that is handed over: no barrier, lane 0 draws, the wave reads its ticket.
+__device__ __forceinline__ bool dosx_last_arriver_wave(int* const& counters, int index, int arrivers, int lane) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  int tk = 0;
+  if (lane == 0) tk = dosx_ticket(counters + index);
+  tk = __builtin_amdgcn_readfirstlane(tk);
+  return tk == arrivers - 1;
+}
+// by one lane of the last arriver, once it has read everything back: the counter is zero again for the next launch
+__device__ __forceinline__ void dosx_counter_reset(int* counter) {
+  __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}

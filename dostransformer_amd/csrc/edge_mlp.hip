@@ -321,11 +321,7 @@ __global__ __launch_bounds__(512) void edge_fwd_kernel(const DosxEdgeMlp a) {
       for (int r = 0; r < re; ++r) t = f4add(t, f4add(ld4(Cs + r * LDC + lane * 4), b3v));
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i32, t), rP, (uint32_t)(((size_t)bx * H + lane * 4) * 4), 0, 16);   // sc1
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    int tk = 0;
-    if (lane == 0) tk = dosx_ticket(a.seg_cnt + t0);
-    tk = __builtin_amdgcn_readfirstlane(tk);
-    if (tk == nc - 1) {
+    if (dosx_last_arriver_wave(a.seg_cnt, t0, nc, lane)) {
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       const float sc = a.seg_scale ? a.seg_scale[n] : 1.f;
       if (con) {
@@ -337,7 +333,7 @@ __global__ __launch_bounds__(512) void edge_fwd_kernel(const DosxEdgeMlp a) {
         }
         st4(a.seg_agg + (size_t)n * H + lane * 4, make_float4(t.x * sc, t.y * sc, t.z * sc, t.w * sc));
       }
-      if (lane == 0) __hip_atomic_store(a.seg_cnt + t0, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (lane == 0) dosx_counter_reset(a.seg_cnt + t0);
     }
   }
   for (int n = nfirst + wave; n < nhi; n += 8) {
@@ -586,11 +582,7 @@ __global__ __launch_bounds__(512) void edge_bwd_kernel(const DosxEdgeMlpBwd a) {
             for (int r = 0; r < re; ++r) t = f4add(t, ld4(T + r * LDT + lane * 4));
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i32, t), rP, (uint32_t)(((size_t)bx * NH + lane * 4) * 4), 0, 16);   // sc1
           }
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          int tk = 0;
-          if (lane == 0) tk = dosx_ticket(a.seg_cnt + t0);
-          tk = __builtin_amdgcn_readfirstlane(tk);
-          if (tk == nc - 1) {
+          if (dosx_last_arriver_wave(a.seg_cnt, t0, nc, lane)) {
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             if (on) {
               float4 t = f4zero();
@@ -601,7 +593,7 @@ __global__ __launch_bounds__(512) void edge_bwd_kernel(const DosxEdgeMlpBwd a) {
               }
               st4(a.seg_agg + (size_t)n * NH + lane * 4, t);
             }
-            if (lane == 0) __hip_atomic_store(a.seg_cnt + t0, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (lane == 0) dosx_counter_reset(a.seg_cnt + t0);
           }
         }
         for (int n = nfirst + (wave - 4); n < nhi; n += 4) {

@@ -12,6 +12,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "dkv_reduce.h"
 #include "mma16.h"
 
 typedef int v4i32 __attribute__((ext_vector_type(4)));
@@ -753,99 +754,12 @@ __global__ __launch_bounds__(512) void ffn_fwd_multi_kernel(const FfnMulti A) {
 //   c: quarter wave per row - dS = P o (dP' - sum P dP') scale,        Ql = LN0(x) g0 + b0
 //      dP' = (dP + dO.b0) o M with a dropout mask; P' = P o M       f: dK^ share = P'^T . dO + dS^T . Ql  [NkP, H] -> the tile's slot
 //   d: dq = dS . Ks -> Ds                                              of dkv_part (write-through), ticket on the key crystal's
-//                                                                      counter, the last arriver reduces (ffn_dkv_reduce)
+//                                                                      counter, the last arriver reduces (dkv_reduce.h)   
 // Same saved tensors, scratch layout (dkv_part [Bq][tiles][Nk][H], partials_q [Bq][tiles][2H], partials_kv [Bk][groups][2H]) and
 // summation orders of the partials as the stand-alone kernel with 32-query tiles, so the two forms are interchangeable per layer.
 struct AttBwdSm {
   float *Os, *Ds, *Ql, *Sp, *Ks, *Sc, *Ss, *Ps2, *Pp;
 };
-
-// ALL key rows of crystal bk at once (<= 64: two rows per quarter-wave slot, their loads requested together - the last arriving
-// tile runs this alone at the end of its launch, so it is one round trip, not one per group): sum of the partial key gradients in
-// (query batch entry, tile) order, key-side chain rule, dkvhat (+)=, and per group of 16 key rows the [dg0 | db0] partial row,
-// slots added in row order - the arithmetic and orders of attention.hip's dkv_reduce_group.  Pp: [64][256] floats of LDS.
-// Contains a barrier.
-template <bool KP>
-__device__ __forceinline__ void ffn_dkv_reduce(const DosxFfnBwd& a, const int nqt, const int bk, float* __restrict__ Pp, const int tid) {
-  const int lane = tid & 63, q16 = lane & 15, slot = tid >> 4;                 // 32 slots
-  const int H = a.H, Nk = a.att_Nk, rep = a.att_Bq / a.att_Bk, ngroups = (Nk + 15) / 16;
-  const int nk = dosx_live_keys<KP>(a.att_key_ptr, bk, Nk);  // (KP: a row past the crystal's own keys is no key - zeros)
-  const int np = (KP && slot >= nk) ? 0 : rep * nqt;     // (KP: neither of this slot's rows is a key - nothing to sum)
-  const UDiv dnqt(nqt);
-  const size_t pstride = (size_t)Nk * H;
-  const __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)a.att_dkv_part, 0, 0x7fffffff, 0x00020000);
-  float4 g0[2], d[2][2], kh[2][2], d0[2][2];
-  bool jv[2];
-  size_t krow[2];
-#pragma unroll
-  for (int k = 0; k < 2; ++k) g0[k] = ld4(a.att_gamma0 + ((q16 * 4 + 64 * k) < H ? (q16 * 4 + 64 * k) : 0));
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    const int j = slot + 32 * p;
-    jv[p] = j < nk;
-    krow[p] = ((size_t)(jv[p] ? j : 0) * a.att_Bk + bk) * H;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int c = q16 * 4 + 64 * k, cc = c < H ? c : 0;
-      kh[p][k] = (!KP || jv[p]) ? ld4(a.att_kvhat + krow[p] + cc) : f4zero();
-      d0[p][k] = (a.att_dkv_accumulate && (!KP || jv[p])) ? ld4(a.att_dkvhat + krow[p] + cc) : f4zero();
-      d[p][k] = f4zero();
-    }
-  }
-  for (int p0 = 0; p0 < np; p0 += 4) {
-    float4 v[2][4][2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int pi = min(p0 + u, np - 1), i = dnqt.div(pi), t = pi - i * nqt;
-        const size_t off = ((size_t)(bk + i * a.att_Bk) * nqt + t) * pstride + (size_t)(jv[p] ? slot + 32 * p : 0) * H;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-          const int c = q16 * 4 + 64 * k;
-          v[p][u][k] = (KP && !jv[p]) ? f4zero()         // (no key: nothing was published for it, nothing is fetched)
-                                      : __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rP, (uint32_t)((off + (c < H ? c : 0)) * 4), 0, 16));   // sc1
-        }
-      }
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (p0 + u < np) {
-#pragma unroll
-          for (int k = 0; k < 2; ++k) d[p][k] = f4add(d[p][k], v[p][u][k]);
-        }
-  }
-#pragma unroll
-  for (int p = 0; p < 2; ++p)
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int c = q16 * 4 + 64 * k;
-      float4 pg = f4zero(), pb = f4zero();
-      if (jv[p] && c < H) {
-        pg = make_float4(d[p][k].x * kh[p][k].x, d[p][k].y * kh[p][k].y, d[p][k].z * kh[p][k].z, d[p][k].w * kh[p][k].w);
-        pb = d[p][k];
-        st4(a.att_dkvhat + krow[p] + c, make_float4(d[p][k].x * g0[k].x + d0[p][k].x, d[p][k].y * g0[k].y + d0[p][k].y,
-                                                    d[p][k].z * g0[k].z + d0[p][k].z, d[p][k].w * g0[k].w + d0[p][k].w));
-      }
-      if constexpr (KP) {
-        if (!jv[p] && slot + 32 * p < Nk && c < H && !a.att_dkv_accumulate)
-          st4(a.att_dkvhat + ((size_t)(slot + 32 * p) * a.att_Bk + bk) * H + c, f4zero());
-      }
-      st4(Pp + (slot + 32 * p) * 256 + c, pg);
-      st4(Pp + (slot + 32 * p) * 256 + 128 + c, pb);
-    }
-  __syncthreads();
-  const UDiv dH(H), d2H(2 * H);
-  for (int o = tid; o < ngroups * 2 * H; o += 512) {
-    const int grp = d2H.div(o), c = o - grp * 2 * H;
-    const int hi = dH.div(c), col = hi * 128 + (c - hi * H);
-    float t = 0.f;
-#pragma unroll
-    for (int sl = 0; sl < 16; ++sl) t += Pp[(grp * 16 + sl) * 256 + col];
-    a.att_partials_kv[((size_t)bk * ngroups + grp) * 2 * H + c] = t;
-  }
-}
 
 // the global operands of the attention epilogue's row phases + this thread's share of the crystal's key rows: requested by
 // ffn_bwd_kernel right behind its row epilogue, so the round trip runs under the column-sum block in between
@@ -1080,20 +994,18 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
   }
   // ---- publish / ticket: the last arriving tile of key crystal bk finishes its key gradient ----
   FSTAMP(25);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
+  const bool last = dosx_last_arriver_wg(a.att_dkv_cnt, bk, (a.att_Bq / a.att_Bk) * nqt, reinterpret_cast<int*>(sm), tid);
   FSTAMP(26);
-  int* flag = reinterpret_cast<int*>(sm);
-  const int arrivers = (a.att_Bq / a.att_Bk) * nqt;
-  if (tid == 0) *flag = dosx_ticket(a.att_dkv_cnt + bk);
-  __syncthreads();
-  const bool last = *flag == arrivers - 1;
   __syncthreads();                                  // (the flag word is about to be overwritten by the reduction's LDS rows)
   FSTAMP(27);
   if (last) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    ffn_dkv_reduce<KP>(a, nqt, bk, sm, tid);
-    if (tid == 0) __hip_atomic_store(a.att_dkv_cnt + bk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // all <= 64 key rows at once, two per quarter-wave slot - the last arriving tile runs this alone at the end of its launch,
+    // so it is one round trip, not one per group; sm = [64][256] floats
+    const DkvReduce r = {a.att_kvhat, a.att_gamma0, a.att_dkv_part, a.att_dkvhat, a.att_partials_kv, a.att_key_ptr,
+                         a.H, a.att_Nk, a.att_Bq, a.att_Bk, a.att_dkv_accumulate};
+    dosx_dkv_reduce<2, 0, 4, KP, 2, 512, true>(r, nqt, nqt, bk, 0, sm, tid);
+    if (tid == 0) dosx_counter_reset(a.att_dkv_cnt + bk);
     FSTAMP(28);
   }
 }

@@ -1049,6 +1049,8 @@ __device__ __forceinline__ void gemm_body(const GemmLaunch& L, const int bid) { 
         for (int r = 0; r < re; ++r) t = f4add(t, f4add(ld4(&Cs[r * LDC + lane * 4 + 256 * j]), biasv[j]));
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i32, t), rP, (uint32_t)(((size_t)bx * N + gcol[j]) * 4), 0, 16);   // sc1
       }
+      // (common.h: dosx_last_arriver_wave spelled out - with the helper inlined here the compiler lays this branch out with two
+      //  more scalar instructions, and the hottest kernels of the step keep their instruction stream)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       int tk = 0;
       if (lane == 0) tk = dosx_ticket(g.seg_cnt + t0);
@@ -1775,14 +1777,10 @@ __device__ __forceinline__ void wgrad_finish(const DosxWgrad& g, float* __restri
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i32, v[h]), rS, voff + h * 512 * 16, (uint32_t)z * zstride, 16);   // aux 16 = sc1
   if (do_bias && tid < TN && n0 + tid < N)
     __hip_atomic_store(g.slab_bias + (size_t)z * nbp + n0 + tid, bsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);        // (sc1 store)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // EVERY storing wave drains its write-through stores
-  __syncthreads();
-  WSTAMP(62);
-  int* flag = reinterpret_cast<int*>(Sm + W_FLAG);
-  if (tid == 0) *flag = dosx_ticket(g.counters + tile);
-  __syncthreads();
+  const bool last = dosx_last_arriver_wg(g.counters, tile, ns, reinterpret_cast<int*>(Sm + W_FLAG), tid);
+  WSTAMP(62);                                             // (the hand-over is one call: drained and ticket known together)
   WSTAMP(63);
-  if (*flag != ns - 1) return;                            // not the last arriver of this tile
+  if (!last) return;                                      // not the last arriver of this tile
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // (no instruction: keeps the loads below the ticket)
   // ---- last arriver: sum the nsplit partial tiles in split order (sc1 loads, all issued before the first add) ----
   constexpr int ZB = 16 / NT;                             // loads in flight per lane and float4 slot
@@ -1810,7 +1808,7 @@ __device__ __forceinline__ void wgrad_finish(const DosxWgrad& g, float* __restri
     }
   }
   write_dst(v, bfin);
-  if (tid == 0) __hip_atomic_store(g.counters + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
+  if (tid == 0) dosx_counter_reset(g.counters + tile);    // ready for the next launch
 }
 
 template <int PRO, int VEC, int FAST, int NT = 1>

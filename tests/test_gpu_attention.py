@@ -583,3 +583,99 @@ def test_attention_forward_also_writes_the_next_layernorm(Sq, Bq, Nk, H):
     a.kvhat, a.probs = big_kv.data_ptr(), big_p.data_ptr()
     with pytest.raises(DosxError, match="ln1_out"):
         o.attention_fwd(a)
+
+
+# (Sq, Bq, Nk, Bk, H) and the forms that take the shape: "two" = attention.hip, dq launch + attn_dkv_reduce_kernel; "one" =
+# attention.hip, the dq launch's last arriver; "aligned" = csrc/attention_aligned.hip (hidden 64 / 128 / 256 only).  64 is the
+# largest Nk <= 64 with dosx_attention_pkv_supported(Nk, 256), so attention.hip's forms run the last shape as it stands.
+_DKV_REDUCE_SHAPES = [
+    ((33, 3, 1, 3, 32), ("two", "one")),               # one key; lanes with c >= H
+    ((70, 6, 17, 2, 96), ("two", "one")),              # 9 shares: a ragged last round; second row group with one row; half a column block
+    ((7, 4, 16, 1, 64), ("two", "one", "aligned")),    # 4 shares: exactly one round
+    ((40, 2, 33, 2, 128), ("two", "one", "aligned")),  # first row of the second row-per-slot
+    ((65, 150, 64, 5, 64), ("two", "one", "aligned")),  # aligned: 1 workgroup for 3 tiles per query batch entry, 30 of them per crystal
+    ((65, 5, 64, 5, 256), ("two", "one", "aligned")),  # aligned: NG 4, two shares per round, odd share count
+]
+
+
+@pytest.mark.parametrize("per_crystal", [False, True], ids=["all_keys", "key_ptr"])
+@pytest.mark.parametrize("accumulate", [0, 1], ids=["fresh", "accumulate"])
+@pytest.mark.parametrize("shape,form", [(s, f) for s, fs in _DKV_REDUCE_SHAPES for f in fs],
+                         ids=[f"{'x'.join(map(str, s))}-{f}" for s, fs in _DKV_REDUCE_SHAPES for f in fs])
+def test_key_gradient_is_the_sum_of_the_published_shares(shape, form, accumulate, per_crystal):
+    """The key-gradient reduction alone (csrc/dkv_reduce.h), apart from the tile arithmetic: dkv_part starts as NaN, so after
+    dosx_attention_bwd a [Nk, H] slot that is still all NaN was not published, and with key_ptr the rows >= n of a published
+    slot are still NaN.  In float64, d[j] = sum of the published shares of key row j; then
+        dkvhat[j] = base * accumulate + d[j] * gamma0,   partials_kv[bk][g] = [sum_{j in g} d[j] * k^[j] | sum_{j in g} d[j]],
+    each element within (n_addends + 2) * 2^-23 * sum |addends| (n_addends fp32 values are summed into it: sequential fp32
+    sums of n terms are off by at most (n - 1) 2^-24 sum |terms|, one more rounding each for the product and the base), and the
+    rows >= n exactly 0.0 (fresh) or exactly base (accumulate)."""
+    from dostransformer_amd import _lib
+    from dostransformer_amd._lib import Attn
+    Sq, Bq, Nk, Bk, H = shape
+    lib, o = _lib.load(), ops()
+    assert lib.dosx_attention_pkv_supported(Nk, H)
+    x, kv = rnd(Sq * Bq, H, seed=1), rnd(Nk * Bk, H, seed=2)
+    gam, bet = rnd(H, seed=3), 0.3 * rnd(H, seed=4)
+    dout, base = rnd(Sq * Bq, H, seed=5), rnd(Nk * Bk, H, seed=6)
+    counts = [Nk] * Bk
+    kp = None
+    if per_crystal:
+        choices = sorted({min(c, Nk) for c in (0, 1, 16, 17, Nk)})
+        counts = [choices[(len(choices) - 2 - bk) % len(choices)] for bk in range(Bk)]
+        kp = torch.tensor([0] + list(np.cumsum(counts)), dtype=torch.int32, device=DEV)
+    nan = lambda *s: torch.full(s, float("nan"), device=DEV)
+    nqt, ng = (Sq + 31) // 32, (Nk + 15) // 16
+    a = Attn()
+    a.Sq, a.Bq, a.Nk, a.Bk, a.H, a.q_stride_s, a.q_stride_b = Sq, Bq, Nk, Bk, H, Bq, 1
+    out, probs, qstats, ostats = nan(Sq * Bq, H), nan(Bq, Sq, Nk), nan(Sq * Bq, 2), nan(Sq * Bq, 2)
+    a.x, a.kvhat, a.gamma0, a.beta0 = x.data_ptr(), kv.data_ptr(), gam.data_ptr(), bet.data_ptr()
+    a.out, a.probs, a.qstats, a.out_stats = out.data_ptr(), probs.data_ptr(), qstats.data_ptr(), ostats.data_ptr()
+    a.key_ptr = kp.data_ptr() if kp is not None else None
+    dx, dkv, part, kvp = nan(Sq * Bq, H), (base.clone() if accumulate else nan(Nk * Bk, H)), nan(Bq * nqt + Bk * ng, 2 * H), nan(Bq * nqt * Nk, H)
+    a.dout, a.dx, a.dscores, a.dkvhat, a.dkv_accumulate = dout.data_ptr(), dx.data_ptr(), None, dkv.data_ptr(), accumulate
+    a.partials_q, a.partials_kv = part.data_ptr(), part.data_ptr() + 4 * Bq * nqt * 2 * H
+    a.dkv_part = kvp.data_ptr()
+    a.dkv_cnt = None if form == "two" else o.COUNTERS.take(DEV, Bk)
+    prev = lib.dosx_attention_aligned_mode(2 if form == "aligned" else 0)
+    try:
+        o.attention_fwd(a)
+        o.attention_bwd(a)
+        torch.cuda.synchronize()
+    finally:
+        lib.dosx_attention_aligned_mode(prev)
+    # ---- the shares the launch published ----
+    rep = Bq // Bk
+    S = kvp.reshape(Bq, nqt, Nk, H).double()
+    blank = torch.isnan(S)
+    pub = ~blank.all(3).all(2)                                              # [Bq, nqt]
+    n_q = torch.tensor(counts, device=DEV).repeat(rep)                      # keys of query batch entry bq = bk + i Bk
+    live = torch.arange(Nk, device=DEV)[None, :] < n_q[:, None]             # [Bq, Nk]
+    assert torch.equal(~blank, (pub[:, :, None, None] & live[:, None, :, None]).expand_as(blank))
+    assert bool(pub.any(1)[n_q > 0].all()) and not bool(pub[n_q == 0].any())
+    if form != "aligned":
+        assert bool(pub[n_q > 0].all())                                     # one share per query tile
+    S = torch.where(blank, torch.zeros_like(S), S).reshape(rep, Bk, nqt, Nk, H)
+    d, dabs = S.sum((0, 2)), S.abs().sum((0, 2))                            # [Bk, Nk, H]
+    nsh = pub.reshape(rep, Bk, nqt).sum((0, 2)).double()                    # shares per crystal
+    u = 2.0 ** -23
+    # ---- dkvhat ----
+    g64, b64 = gam.double(), base.reshape(Nk, Bk, H).double().transpose(0, 1)
+    got = dkv.reshape(Nk, Bk, H).double().transpose(0, 1)                   # [Bk, Nk, H]
+    want = b64 * accumulate + d * g64
+    bound = (nsh[:, None, None] + accumulate + 2) * u * (dabs * g64.abs() + b64.abs() * accumulate)
+    excess = ((got - want).abs() - bound).max().item()
+    rows_past = ~live[:Bk]                                                  # [Bk, Nk]
+    print(f"dkvhat: max |err| {float((got - want).abs().max()):.3e}, max bound {float(bound.max()):.3e}, shares/crystal {nsh.tolist()}")
+    assert not torch.isnan(got).any() and excess <= 0, excess
+    assert torch.equal(got[rows_past], (b64 * accumulate)[rows_past])
+    # ---- partials_kv ----
+    k64 = kv.reshape(Nk, Bk, H).double().transpose(0, 1)
+    pad = lambda t: torch.cat([t, torch.zeros(Bk, ng * 16 - Nk, H, device=DEV, dtype=torch.float64)], 1).reshape(Bk, ng, 16, H)
+    want_p = torch.cat([pad(d * k64).sum(2), pad(d).sum(2)], 2)             # [Bk, ng, 2H]
+    abs_p = torch.cat([pad(dabs * k64.abs()).sum(2), pad(dabs).sum(2)], 2)
+    rows_g = torch.cat([live[:Bk], torch.zeros(Bk, ng * 16 - Nk, dtype=torch.bool, device=DEV)], 1).reshape(Bk, ng, 16).sum(2).double()
+    bound_p = (nsh[:, None, None] * rows_g[:, :, None] + 2) * u * abs_p
+    got_p = part[Bq * nqt:].reshape(Bk, ng, 2 * H).double()
+    print(f"partials_kv: max |err| {float((got_p - want_p).abs().max()):.3e}, max bound {float(bound_p.max()):.3e}")
+    assert not torch.isnan(got_p).any() and ((got_p - want_p).abs() - bound_p).max().item() <= 0
