@@ -16,6 +16,7 @@
 // Deterministic: fixed tile -> workgroup assignment, fixed summation orders.
 #include <stdlib.h>
 
+#include "attn_rows.h"
 #include "common.h"
 #include "dkv_reduce.h"
 #include "mma16.h"
@@ -222,27 +223,14 @@ __global__ __launch_bounds__(512) void attn_al_fwd_kernel(const DosxAttn a, cons
     const size_t r = (size_t)s * a.Bq + bq;          // global row (valid memory also for the clamped duplicates)
     // ---- A: LayerNorm-0, the key gamma folded into q -> Qs ----
     float mean, rstd;
-    {
-      float u = 0.f;
+    dosx_row16_stats<NG>(xr, on, invH, mean, rstd);
 #pragma unroll
-      for (int k = 0; k < NG; ++k) u += (xr[k].x + xr[k].y) + (xr[k].z + xr[k].w);
-      mean = row16_sum(u) * invH;
-      u = 0.f;
-#pragma unroll
-      for (int k = 0; k < NG; ++k) {
-        if (!on[k]) continue;
-        const float p0 = xr[k].x - mean, p1 = xr[k].y - mean, p2 = xr[k].z - mean, p3 = xr[k].w - mean;
-        u += (p0 * p0 + p1 * p1) + (p2 * p2 + p3 * p3);
-      }
-      rstd = rsqrtf(row16_sum(u) * invH + DOSX_LN_EPS);
-#pragma unroll
-      for (int k = 0; k < NG; ++k) {
-        if (!on[k]) continue;
-        const float4 v = xr[k];
-        const float4 q = make_float4((v.x - mean) * rstd * g0[k].x + b0[k].x, (v.y - mean) * rstd * g0[k].y + b0[k].y,
-                                     (v.z - mean) * rstd * g0[k].z + b0[k].z, (v.w - mean) * rstd * g0[k].w + b0[k].w);
-        st4(Qs + lr * LDK + q16 * 4 + 64 * k, make_float4(q.x * g0[k].x, q.y * g0[k].y, q.z * g0[k].z, q.w * g0[k].w));
-      }
+    for (int k = 0; k < NG; ++k) {                     // (written out here and in ffn_att_tile: shared, it cost that kernel one VGPR)
+      if (!on[k]) continue;
+      const float4 v = xr[k];
+      const float4 q = make_float4((v.x - mean) * rstd * g0[k].x + b0[k].x, (v.y - mean) * rstd * g0[k].y + b0[k].y,
+                                   (v.z - mean) * rstd * g0[k].z + b0[k].z, (v.w - mean) * rstd * g0[k].w + b0[k].w);
+      st4(Qs + lr * LDK + q16 * 4 + 64 * k, make_float4(q.x * g0[k].x, q.y * g0[k].y, q.z * g0[k].z, q.w * g0[k].w));
     }
     if (t + wpc < nqt) load_x(t + wpc, xn);           // the next tile's rows: in flight under this tile's products
     const int so = t == w ? 0 : (t == w + wpc ? 16 : 48);     // (stamps of the first two tiles)
@@ -255,10 +243,10 @@ __global__ __launch_bounds__(512) void attn_al_fwd_kernel(const DosxAttn a, cons
     __syncthreads();
     ASTAMP(so + 4);
     // ---- C: exact fp32 softmax of this quarter wave's row; P written out; P o mask -> Sc ----
-    float psum = 1.f;
+    float psum;
     {
       float* Sr = Sc + lr * 68;
-      float v[4], mx = -INFINITY;
+      float v[4];
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
         const int j = q16 + 16 * jj;
@@ -267,33 +255,8 @@ __global__ __launch_bounds__(512) void attn_al_fwd_kernel(const DosxAttn a, cons
           v[jj] = Sr[j];
           for (int kq = 1; kq < KS; ++kq) v[jj] += Sr[kq * R * 68 + j];
         }
-        mx = fmaxf(mx, v[jj]);
       }
-      mx = row16_max(mx);
-      float sum = 0.f;
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const float e = (q16 + 16 * jj) < nk ? expf(v[jj] - mx) : 0.f;
-        v[jj] = e;
-        sum += e;
-      }
-      const float inv = dosx_softmax_inv<KP>(row16_sum(sum));
-      const size_t prow = ((size_t)bq * Sq + s) * Nk;
-      float ps = 0.f;
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const int j = q16 + 16 * jj;
-        if (j >= NkP) continue;
-        float pm = 0.f;
-        if (j < Nk) {
-          const float pr = v[jj] * inv;                // (0 beyond nk)
-          pm = (a.drop_mask && (!KP || j < nk)) ? pr * a.drop_mask[prow + j] : pr;
-          if (rv) a.probs[prow + j] = pr;              // the un-dropped P (the backward reads it)
-        }
-        Sr[j] = pm;                                    // (zeros beyond nk: the padded keys of the second product)
-        ps += pm;
-      }
-      psum = a.drop_mask ? row16_sum(ps) : dosx_psum_one<KP>(nk);
+      psum = dosx_att_softmax_row<KP>(v, nk, Nk, NkP, q16, a.drop_mask, a.probs, ((size_t)bq * Sq + s) * Nk, rv, Sr);
     }
     ASTAMP(so + 5);
     __syncthreads();
@@ -306,9 +269,8 @@ __global__ __launch_bounds__(512) void attn_al_fwd_kernel(const DosxAttn a, cons
     // ---- E: x1 = O o g0 + b0 sum(P o mask) + x; both rows of statistics ----
     {
       float4 x1[NG];
-      float u = 0.f;
 #pragma unroll
-      for (int k = 0; k < NG; ++k) {
+      for (int k = 0; k < NG; ++k) {                   // (written out here and in ffn_att_tile: shared, it cost that kernel one VGPR)
         const int c = q16 * 4 + 64 * k;
         x1[k] = f4zero();
         if (!on[k]) continue;
@@ -316,28 +278,16 @@ __global__ __launch_bounds__(512) void attn_al_fwd_kernel(const DosxAttn a, cons
         x1[k] = make_float4(o.x * g0[k].x + b0[k].x * psum + xr[k].x, o.y * g0[k].y + b0[k].y * psum + xr[k].y,
                             o.z * g0[k].z + b0[k].z * psum + xr[k].z, o.w * g0[k].w + b0[k].w * psum + xr[k].w);
         if (rv) st4(a.out + r * H + c, x1[k]);
-        u += (x1[k].x + x1[k].y) + (x1[k].z + x1[k].w);
       }
       if (a.out_stats) {
-        const float mean1 = row16_sum(u) * invH;
-        u = 0.f;
-#pragma unroll
-        for (int k = 0; k < NG; ++k) {
-          if (!on[k]) continue;
-          const float p0 = x1[k].x - mean1, p1 = x1[k].y - mean1, p2 = x1[k].z - mean1, p3 = x1[k].w - mean1;
-          u += (p0 * p0 + p1 * p1) + (p2 * p2 + p3 * p3);
-        }
-        const float rstd1 = rsqrtf(row16_sum(u) * invH + DOSX_LN_EPS);
+        float mean1, rstd1;
+        dosx_row16_stats<NG>(x1, on, invH, mean1, rstd1);
         if (rv && q16 == 0) { a.out_stats[2 * r] = mean1; a.out_stats[2 * r + 1] = rstd1; }
         if (a.ln1_out && rv) {         // the next LayerNorm on the row still in registers (DosxAttn.ln1_*)
+          float4 g1[NG], b1[NG];
 #pragma unroll
-          for (int k = 0; k < NG; ++k) {
-            const int c = q16 * 4 + 64 * k;
-            const float4 g1 = ld4(a.ln1_gamma + c), b1 = ld4(a.ln1_beta + c);
-            st4(a.ln1_out + r * H + c,
-                make_float4((x1[k].x - mean1) * rstd1 * g1.x + b1.x, (x1[k].y - mean1) * rstd1 * g1.y + b1.y,
-                            (x1[k].z - mean1) * rstd1 * g1.z + b1.z, (x1[k].w - mean1) * rstd1 * g1.w + b1.w));
-          }
+          for (int k = 0; k < NG; ++k) { g1[k] = ld4(a.ln1_gamma + q16 * 4 + 64 * k); b1[k] = ld4(a.ln1_beta + q16 * 4 + 64 * k); }
+          dosx_att_ln_row<NG>(x1, on, mean1, rstd1, g1, b1, a.ln1_out + r * H, q16);
         }
       }
       if (rv && q16 == 0) { a.qstats[2 * r] = mean; a.qstats[2 * r + 1] = rstd; }
@@ -440,6 +390,7 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
       }
     }
     // ---- a: dO -> Os (zeros beyond the data);  Ds = dO o g0;  cq = dO . b0 (dropout only) ----
+    // (hand-written, like ffn_att_bwd_tile's: as a shared phase it cost the NG = 1 instantiations one VGPR)
     float cq = 0.f;
     {
       float u = 0.f;
@@ -464,30 +415,13 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
     __syncthreads();
     ASTAMP(so + 4);
     // ---- c: dS = P o (dP' - sum_j P dP') scale -> Ss;  P' = P o M -> Ps2 (zeros beyond Nk / the data); in place, row-wise ----
-    {
-      float dp[4], dot = 0.f;
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const int j = q16 + 16 * jj;
-        float u = 0.f;
-        if (j < nk) {
-          u = Sc[lr * 68 + j];
+    dosx_att_bwd_ds_row(
+        [&](const int j) {
+          float u = Sc[lr * 68 + j];
           if (KS > 1) u += Sc[R * 68 + lr * 68 + j];
-        }
-        if (a.drop_mask) u = (u + cq) * mk[jj];
-        if (j < nk) dot += pr[jj] * u;
-        dp[jj] = u;
-      }
-      dot = row16_sum(dot);
-#pragma unroll
-      for (int jj = 0; jj < 4; ++jj) {
-        const int j = q16 + 16 * jj;
-        if (j >= NkP) continue;
-        const bool v = j < nk && rv;
-        Ss[lr * 68 + j] = v ? pr[jj] * (dp[jj] - dot) * scale : 0.f;
-        Ps2[lr * 68 + j] = v ? pr[jj] * mk[jj] : 0.f;
-      }
-    }
+          return u;
+        },
+        pr, mk, a.drop_mask != nullptr, cq, nk, NkP, rv, scale, q16, Ss + lr * 68, Ps2 + lr * 68);
     // this row's query + LayerNorm-0 statistics (phase e): in flight under phase d
     float4 xr[NG];
     {
@@ -506,40 +440,9 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
     ASTAMP(so + 8);
     // ---- e: LayerNorm-0 backward on the query rows + residual -> dx; query-side dg0 / db0 (kept per row slot across the
     //         tiles); Ql = LN0(x) g0 + b0 over this quarter wave's own row of Ds ----
-    {
-      float4 d[NG], xh[NG];
-      float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < NG; ++k) {
-        d[k] = f4zero(); xh[k] = f4zero();
-        if (!(on[k] && rv)) continue;
-        float4 dd = ld4(Ds + lr * LDK + q16 * 4 + 64 * k);
-        dd = make_float4(dd.x * g0[k].x, dd.y * g0[k].y, dd.z * g0[k].z, dd.w * g0[k].w);
-        const float4 xv = xr[k];
-        const float4 h = make_float4((xv.x - mean) * rstd, (xv.y - mean) * rstd, (xv.z - mean) * rstd, (xv.w - mean) * rstd);
-        d[k] = dd; xh[k] = h;
-        pg[k] = f4add(pg[k], make_float4(dd.x * h.x, dd.y * h.y, dd.z * h.z, dd.w * h.w));
-        pb[k] = f4add(pb[k], dd);
-        const float4 dh = make_float4(dd.x * g0[k].x, dd.y * g0[k].y, dd.z * g0[k].z, dd.w * g0[k].w);
-        s1 += (dh.x + dh.y) + (dh.z + dh.w);
-        s2 += (dh.x * h.x + dh.y * h.y) + (dh.z * h.z + dh.w * h.w);
-      }
-      s1 = row16_sum(s1) * invH; s2 = row16_sum(s2) * invH;
-#pragma unroll
-      for (int k = 0; k < NG; ++k) {
-        if (!on[k]) continue;
-        const float4 dd = d[k], h = xh[k];
-        if (rv) {
-          const float4 go = ld4(Os + lr * LDK + q16 * 4 + 64 * k);      // (this row's dO: the residual path)
-          st4(a.dx + orow * H + q16 * 4 + 64 * k,
-              make_float4(rstd * (dd.x * g0[k].x - s1 - h.x * s2) + go.x, rstd * (dd.y * g0[k].y - s1 - h.y * s2) + go.y,
-                          rstd * (dd.z * g0[k].z - s1 - h.z * s2) + go.z, rstd * (dd.w * g0[k].w - s1 - h.w * s2) + go.w));
-        }
-        st4(Ds + lr * LDK + q16 * 4 + 64 * k,
-            rv ? make_float4(h.x * g0[k].x + b0[k].x, h.y * g0[k].y + b0[k].y, h.z * g0[k].z + b0[k].z, h.w * g0[k].w + b0[k].w)
-               : f4zero());
-      }
-    }
+    dosx_att_bwd_ln0_row<NG, true>(Ds + lr * LDK, xr, on, g0, b0, mean, rstd, invH, rv,
+                                   [&](const int k) { return ld4(Os + lr * LDK + q16 * 4 + 64 * k); },   // (this row's dO)
+                                   a.dx + orow * H, Ds + lr * LDK, q16, pg, pb);
     ASTAMP(so + 9);
     __syncthreads();
     ASTAMP(so + 10);

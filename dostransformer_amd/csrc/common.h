@@ -164,8 +164,6 @@ __device__ __forceinline__ float dosx_psum_one(int nk) {
   else return 1.f;
 }
 
-// Row statistics of a row held as `per` float4 per lane of one wave (whole row over 64 lanes).
-// Two-pass (mean, then centred second moment) like torch's LayerNorm; eps = 1e-5.
 #define DOSX_LN_EPS 1e-5f
 
 // ---- in-launch reductions: publish / ticket / read-back (gemm.hip wgrad_finish + EPI_SEGSUM, attention.hip dK/dV) ----------

@@ -11,6 +11,7 @@
 // Needs H % 32 == 0 and H <= 128 (tile: 32 x 516 floats); larger H uses the two-GEMM path.
 #include <stdlib.h>
 
+#include "attn_rows.h"
 #include "common.h"
 #include "dkv_reduce.h"
 #include "mma16.h"
@@ -38,6 +39,8 @@ constexpr int FBN = 128;         // columns per chunk / per column block
 // One query row of the fused attention prologue (ffn_fwd_kernel<.., ATT = true>), by one QUARTER wave: lane q16 owns the
 // float4 columns 4 q16 + 64 k (k < 2: H <= 128).  Writes probs / qstats / x1 / st1 of row m0 + lr and the LN1-normalised row
 // into the Xs tile.
+// (Its statistics and phase-E arithmetic stay written out: ffn_fwd_multi_kernel<.., ATT = 1> sits at 255 VGPRs, and dosx_row16_stats
+//  alone brought it 8 bytes of scratch.)
 template <bool KP>
 __device__ __forceinline__ void ffn_att_row(const DosxFfn& a, float* __restrict__ Xs, const int LDX, const int lr, const int m0,
                                             const int lane) {
@@ -215,19 +218,8 @@ __device__ __forceinline__ void ffn_att_tile(const DosxFfn& a, float* __restrict
         if (e < 16 * dosx_live_tiles<KP, 4>(nk0, NkP >> 4) * h4) st4(Ks + j * LDK + c, kr[i]);
       }
     }
-    float t = 0.f;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) t += (xr[k].x + xr[k].y) + (xr[k].z + xr[k].w);
-    mean = row16_sum(t) * invH;
-    t = 0.f;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      if (!on[k]) continue;
-      const float p0 = xr[k].x - mean, p1 = xr[k].y - mean, p2 = xr[k].z - mean, p3 = xr[k].w - mean;
-      t += (p0 * p0 + p1 * p1) + (p2 * p2 + p3 * p3);
-    }
-    rstd = rsqrtf(row16_sum(t) * invH + DOSX_LN_EPS);
-    if (rowok) {
+    dosx_row16_stats<2>(xr, on, invH, mean, rstd);
+    if (rowok) {      // (the q store stays written out here and in attn_al_fwd_kernel: shared, it cost this kernel one VGPR)
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
         if (!on[k]) continue;
@@ -269,7 +261,7 @@ __device__ __forceinline__ void ffn_att_tile(const DosxFfn& a, float* __restrict
   const int nk = KP ? nk0 : dosx_live_keys_fwd<KP>(a.att_key_ptr, bk_, Nk);
   if (rowok) {
     float* Sr = Sc + lr * 68;
-    float v[4], mx = -INFINITY;
+    float v[4];
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
       const int j = q16 + 16 * jj;
@@ -278,33 +270,8 @@ __device__ __forceinline__ void ffn_att_tile(const DosxFfn& a, float* __restrict
         v[jj] = Sr[j];
         for (int kq = 1; kq < KS; ++kq) v[jj] += Qs[R * LDK + (kq - 1) * R * 68 + lr * 68 + j];
       }
-      mx = fmaxf(mx, v[jj]);
     }
-    mx = row16_max(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const float e = (q16 + 16 * jj) < nk ? expf(v[jj] - mx) : 0.f;
-      v[jj] = e;
-      sum += e;
-    }
-    const float inv = dosx_softmax_inv<KP>(row16_sum(sum));
-    const size_t prow = ((size_t)al_bq * Sq + s) * Nk;
-    float ps = 0.f;
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int j = q16 + 16 * jj;
-      if (j >= NkP) continue;
-      float pm = 0.f;
-      if (j < Nk) {
-        const float pr = v[jj] * inv;
-        pm = (a.att_mask && (!KP || j < nk)) ? pr * a.att_mask[prow + j] : pr;
-        if (rv) a.att_probs[prow + j] = pr;            // the un-dropped P (the backward reads it)
-      }
-      Sr[j] = pm;                                      // (zeros beyond Nk: the padded keys of the second product)
-      ps += pm;
-    }
-    psum = a.att_mask ? row16_sum(ps) : dosx_psum_one<KP>(nk);
+    psum = dosx_att_softmax_row<KP>(v, nk, Nk, NkP, q16, a.att_mask, a.att_probs, ((size_t)al_bq * Sq + s) * Nk, rv, Sr);
   }
   FSTAMP(13);
   __syncthreads();
@@ -325,9 +292,8 @@ __device__ __forceinline__ void ffn_att_tile(const DosxFfn& a, float* __restrict
   // ---- E: residual, statistics, LN1 -> Xs ----
   if (rowok) {
     float4 x1[2];
-    float t = 0.f;
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < 2; ++k) {                      // (the x1 loop stays written out, as in attn_al_fwd_kernel: shared, it cost one VGPR here)
       const int c = q16 * 4 + 64 * k;
       x1[k] = f4zero();
       if (!on[k]) continue;
@@ -335,29 +301,14 @@ __device__ __forceinline__ void ffn_att_tile(const DosxFfn& a, float* __restrict
       x1[k] = make_float4(o.x * g0[k].x + b0[k].x * psum + xr[k].x, o.y * g0[k].y + b0[k].y * psum + xr[k].y,
                           o.z * g0[k].z + b0[k].z * psum + xr[k].z, o.w * g0[k].w + b0[k].w * psum + xr[k].w);
       if (rv) st4(a.att_x1 + (size_t)r * a.att_ldx1 + c, x1[k]);
-      t += (x1[k].x + x1[k].y) + (x1[k].z + x1[k].w);
     }
-    const float mean1 = row16_sum(t) * invH;
-    t = 0.f;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      if (!on[k]) continue;
-      const float p0 = x1[k].x - mean1, p1 = x1[k].y - mean1, p2 = x1[k].z - mean1, p3 = x1[k].w - mean1;
-      t += (p0 * p0 + p1 * p1) + (p2 * p2 + p3 * p3);
-    }
-    const float rstd1 = rsqrtf(row16_sum(t) * invH + DOSX_LN_EPS);
+    float mean1, rstd1;
+    dosx_row16_stats<2>(x1, on, invH, mean1, rstd1);
     if (rv && q16 == 0) {
       a.att_qstats[2 * (size_t)r] = mean; a.att_qstats[2 * (size_t)r + 1] = rstd;
       a.att_st1[2 * (size_t)r] = mean1;   a.att_st1[2 * (size_t)r + 1] = rstd1;
     }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      if (!on[k]) continue;
-      const float4 vv = x1[k];
-      st4(Xs + lr * LDX + q16 * 4 + 64 * k,
-          make_float4((vv.x - mean1) * rstd1 * g1[k].x + bb1[k].x, (vv.y - mean1) * rstd1 * g1[k].y + bb1[k].y,
-                      (vv.z - mean1) * rstd1 * g1[k].z + bb1[k].z, (vv.w - mean1) * rstd1 * g1[k].w + bb1[k].w));
-    }
+    dosx_att_ln_row<2>(x1, on, mean1, rstd1, g1, bb1, Xs + lr * LDX, q16);
   }
 }
 
@@ -835,6 +786,7 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
   FSTAMP(17);
   // ---- a: dO rows (left in Os by the row epilogue; zeros beyond the data) -> Ds = dO o g0;  cq = dO . b0 (dropout only) ----
   float cq = 0.f;
+  // (hand-written in both kernels: the shared form cost attn_al_bwd_kernel<1, .> one VGPR)
   if (rowok) {
     float t = 0.f;
 #pragma unroll
@@ -869,30 +821,14 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
   FSTAMP(20);
   __syncthreads();
   // ---- c: dS = P o (dP' - sum_j P dP') scale -> Ss;  P' = P o M -> Ps2 (zeros beyond Nk / the data) ----
-  if (rowok) {
-    float dp[4], dot = 0.f;
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int j = q16 + 16 * jj;
-      float t = 0.f;
-      if (j < nk) {
-        t = L.Sc[lr * 68 + j];
-        for (int kq = 1; kq < KS; ++kq) t += L.Sp[(kq - 1) * R * 68 + lr * 68 + j];
-      }
-      if (a.att_mask) t = (t + cq) * mk[jj];
-      if (j < nk) dot += pr[jj] * t;
-      dp[jj] = t;
-    }
-    dot = row16_sum(dot);
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int j = q16 + 16 * jj;
-      if (j >= NkP) continue;
-      const bool v = j < nk && rv;
-      L.Ss[lr * 68 + j] = v ? pr[jj] * (dp[jj] - dot) * scale : 0.f;
-      L.Ps2[lr * 68 + j] = v ? pr[jj] * mk[jj] : 0.f;
-    }
-  }
+  if (rowok)
+    dosx_att_bwd_ds_row(
+        [&](const int j) {
+          float t = L.Sc[lr * 68 + j];
+          for (int kq = 1; kq < KS; ++kq) t += L.Sp[(kq - 1) * R * 68 + lr * 68 + j];
+          return t;
+        },
+        pr, mk, a.att_mask != nullptr, cq, nk, NkP, rv, scale, q16, L.Ss + lr * 68, L.Ps2 + lr * 68);
   FSTAMP(21);
   __syncthreads();
   // ---- d: dq = dS . Ks -> Ds ----
@@ -912,38 +848,9 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
   // ---- e: LayerNorm-0 backward on the query rows + residual -> dxin; query-side dg0 / db0; Ql = LN0(x) g0 + b0 ----
   {
     float4 pg[2] = {f4zero(), f4zero()}, pb[2] = {f4zero(), f4zero()};
-    if (rowok) {
-      float4 d[2], xh[2];
-      float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        d[k] = f4zero(); xh[k] = f4zero();
-        if (!(on[k] && rv)) continue;
-        float4 dd = ld4(L.Ds + lr * LDK + q16 * 4 + 64 * k);
-        dd = make_float4(dd.x * g0[k].x, dd.y * g0[k].y, dd.z * g0[k].z, dd.w * g0[k].w);
-        const float4 xv = xr[k];
-        const float4 h = make_float4((xv.x - mean) * rstd, (xv.y - mean) * rstd, (xv.z - mean) * rstd, (xv.w - mean) * rstd);
-        d[k] = dd; xh[k] = h;
-        pg[k] = make_float4(dd.x * h.x, dd.y * h.y, dd.z * h.z, dd.w * h.w);
-        pb[k] = dd;
-        const float4 dh = make_float4(dd.x * g0[k].x, dd.y * g0[k].y, dd.z * g0[k].z, dd.w * g0[k].w);
-        s1 += (dh.x + dh.y) + (dh.z + dh.w);
-        s2 += (dh.x * h.x + dh.y * h.y) + (dh.z * h.z + dh.w * h.w);
-      }
-      s1 = row16_sum(s1) * invH; s2 = row16_sum(s2) * invH;
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        if (!on[k]) continue;
-        const float4 dd = d[k], h = xh[k];
-        if (rv)
-          st4(a.att_dxin + orow * a.att_lddxin + q16 * 4 + 64 * k,
-              make_float4(rstd * (dd.x * g0[k].x - s1 - h.x * s2) + go[k].x, rstd * (dd.y * g0[k].y - s1 - h.y * s2) + go[k].y,
-                          rstd * (dd.z * g0[k].z - s1 - h.z * s2) + go[k].z, rstd * (dd.w * g0[k].w - s1 - h.w * s2) + go[k].w));
-        st4(L.Ql + lr * LDK + q16 * 4 + 64 * k,
-            rv ? make_float4(h.x * g0[k].x + b0[k].x, h.y * g0[k].y + b0[k].y, h.z * g0[k].z + b0[k].z, h.w * g0[k].w + b0[k].w)
-               : f4zero());
-      }
-    }
+    if (rowok)
+      dosx_att_bwd_ln0_row<2, false>(L.Ds + lr * LDK, xr, on, g0, b0, mean, rstd, invH, rv, [&](const int k) { return go[k]; },
+                                     a.att_dxin + orow * a.att_lddxin, L.Ql + lr * LDK, q16, pg, pb);
     // quarter-wave slots [32][2][128] (R = 16: the upper sixteen hold zeros)
     const int slot = wave * 4 + g4;
 #pragma unroll

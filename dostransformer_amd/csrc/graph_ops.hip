@@ -6,6 +6,7 @@
 // Rows are H floats; `lpr` = min(64, H/4) lanes own one row as float4, so a wave streams
 // 64/lpr rows per step with fully coalesced 16-B accesses.
 #include "common.h"
+#include "rowstat.h"
 
 namespace {
 
@@ -356,25 +357,7 @@ __global__ __launch_bounds__(256) void dense_normalize_kernel(const float* __res
   const int lane = threadIdx.x & 63;
   const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (n >= N) return;
-  const float* row = x + (size_t)n * H;
-  float s1 = 0.f;
-  for (int c = lane * 4; c < H; c += 256) {
-    const float4 v = ld4(row + c);
-    s1 += v.x + v.y + v.z + v.w;
-  }
-  const float mean = wave_sum(s1) / (float)H;
-  float s2 = 0.f;
-  for (int c = lane * 4; c < H; c += 256) {
-    const float4 v = ld4(row + c);
-    const float a = v.x - mean, b = v.y - mean, c2 = v.z - mean, d = v.w - mean;
-    s2 += a * a + b * b + c2 * c2 + d * d;
-  }
-  const float rstd = rsqrtf(wave_sum(s2) / (float)H + DOSX_LN_EPS);
-  float* o = kvhat + (size_t)dense_row[n] * H;
-  for (int c = lane * 4; c < H; c += 256) {
-    const float4 v = ld4(row + c);
-    st4(o + c, make_float4((v.x - mean) * rstd, (v.y - mean) * rstd, (v.z - mean) * rstd, (v.w - mean) * rstd));
-  }
+  const float rstd = dosx_wave_rownorm(x + (size_t)n * H, kvhat + (size_t)dense_row[n] * H, H, lane);
   if (lane == 0) rstd_nodes[n] = rstd;
 }
 
@@ -397,24 +380,7 @@ __global__ __launch_bounds__(256) void dense_normalize_slots_kernel(const float*
     for (int c = lane * 4; c < H; c += 256) st4(o + c, f4zero());
     return;
   }
-  const float* row = x + (size_t)n * H;
-  float s1 = 0.f;
-  for (int c = lane * 4; c < H; c += 256) {
-    const float4 v = ld4(row + c);
-    s1 += v.x + v.y + v.z + v.w;
-  }
-  const float mean = wave_sum(s1) / (float)H;
-  float s2 = 0.f;
-  for (int c = lane * 4; c < H; c += 256) {
-    const float4 v = ld4(row + c);
-    const float a = v.x - mean, b2 = v.y - mean, c2 = v.z - mean, d = v.w - mean;
-    s2 += a * a + b2 * b2 + c2 * c2 + d * d;
-  }
-  const float rstd = rsqrtf(wave_sum(s2) / (float)H + DOSX_LN_EPS);
-  for (int c = lane * 4; c < H; c += 256) {
-    const float4 v = ld4(row + c);
-    st4(o + c, make_float4((v.x - mean) * rstd, (v.y - mean) * rstd, (v.z - mean) * rstd, (v.w - mean) * rstd));
-  }
+  const float rstd = dosx_wave_rownorm(x + (size_t)n * H, o, H, lane);
   if (lane == 0) rstd_nodes[n] = rstd;
 }
 
@@ -504,25 +470,7 @@ __global__ __launch_bounds__(256) void rownorm_kernel(const float* __restrict__ 
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= M) return;
-  const float* row = x + (size_t)r * H;
-  float s1 = 0.f;
-  for (int c = lane * 4; c < H; c += 256) {
-    const float4 v = ld4(row + c);
-    s1 += v.x + v.y + v.z + v.w;
-  }
-  const float mean = wave_sum(s1) / (float)H;
-  float s2 = 0.f;
-  for (int c = lane * 4; c < H; c += 256) {
-    const float4 v = ld4(row + c);
-    const float a = v.x - mean, b = v.y - mean, c2 = v.z - mean, d = v.w - mean;
-    s2 += a * a + b * b + c2 * c2 + d * d;
-  }
-  const float rstd = rsqrtf(wave_sum(s2) / (float)H + DOSX_LN_EPS);
-  for (int c = lane * 4; c < H; c += 256) {
-    const float4 v = ld4(row + c);
-    st4(xhat + (size_t)r * H + c,
-        make_float4((v.x - mean) * rstd, (v.y - mean) * rstd, (v.z - mean) * rstd, (v.w - mean) * rstd));
-  }
+  const float rstd = dosx_wave_rownorm(x + (size_t)r * H, xhat + (size_t)r * H, H, lane);
   if (lane == 0) rstd_out[r] = rstd;
 }
 
@@ -595,13 +543,7 @@ __global__ __launch_bounds__(256) void mask_residual_kernel(const float* a, int 
   }
   if (stats == nullptr) return;
   const float mean = wave_sum(s1) / (float)H;
-  float s2 = 0.f;
-  for (int c = lane * 4; c < H; c += 256) {                 // (this lane re-reads what it has just written)
-    const float4 v = ld4(out + (size_t)r * ldo + c);
-    const float x0 = v.x - mean, x1 = v.y - mean, x2 = v.z - mean, x3 = v.w - mean;
-    s2 += x0 * x0 + x1 * x1 + x2 * x2 + x3 * x3;
-  }
-  const float rstd = rsqrtf(wave_sum(s2) / (float)H + DOSX_LN_EPS);
+  const float rstd = dosx_wave_row_rstd(out + (size_t)r * ldo, H, lane, mean);   // (this lane re-reads what it has just written)
   if (lane == 0) {
     stats[2 * (size_t)r] = mean;
     stats[2 * (size_t)r + 1] = rstd;

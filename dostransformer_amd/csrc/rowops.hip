@@ -3,6 +3,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "rowstat.h"
 
 namespace {
 
@@ -15,19 +16,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= M) return;
   const float* row = x + (size_t)r * H;
-  float s1 = 0.f;
-  for (int c = lane * 4; c < H; c += 256) {
-    const float4 v = ld4(row + c);
-    s1 += v.x + v.y + v.z + v.w;
-  }
-  const float mean = wave_sum(s1) / (float)H;
-  float s2 = 0.f;
-  for (int c = lane * 4; c < H; c += 256) {
-    const float4 v = ld4(row + c);
-    const float a = v.x - mean, b = v.y - mean, c2 = v.z - mean, d = v.w - mean;
-    s2 += a * a + b * b + c2 * c2 + d * d;
-  }
-  const float rstd = rsqrtf(wave_sum(s2) / (float)H + DOSX_LN_EPS);
+  float mean, rstd;
+  dosx_wave_row_stats(row, H, lane, mean, rstd);
   for (int c = lane * 4; c < H; c += 256) {
     const float4 v = ld4(row + c), g = ld4(gamma + c), b = ld4(beta + c);
     const float4 h = make_float4((v.x - mean) * rstd, (v.y - mean) * rstd, (v.z - mean) * rstd, (v.w - mean) * rstd);
@@ -368,19 +358,8 @@ __global__ __launch_bounds__(256) void ln_rowdot_kernel(const float* __restrict_
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= S * Bq) return;
   const float* row = x + (size_t)r * H;
-  float s1 = 0.f;
-  for (int c = lane * 4; c < H; c += 256) {
-    const float4 v = ld4(row + c);
-    s1 += v.x + v.y + v.z + v.w;
-  }
-  const float mean = wave_sum(s1) / (float)H;
-  float s2 = 0.f;
-  for (int c = lane * 4; c < H; c += 256) {
-    const float4 v = ld4(row + c);
-    const float a = v.x - mean, bb = v.y - mean, c2 = v.z - mean, d = v.w - mean;
-    s2 += a * a + bb * bb + c2 * c2 + d * d;
-  }
-  const float rstd = rsqrtf(wave_sum(s2) / (float)H + DOSX_LN_EPS);
+  float mean, rstd;
+  dosx_wave_row_stats(row, H, lane, mean, rstd);
   float dot = 0.f;
   for (int c = lane * 4; c < H; c += 256) {
     const float4 v = ld4(row + c), g = ld4(gamma + c), bt = ld4(beta + c), ww = ld4(w + c);
