@@ -108,7 +108,9 @@ class DOSTransformerBase(FusedModel):
             raise DosxError(f"{who} drives a DOSTransformer_phonon set to the float64 program "
                             f"(model.double().set_program_dtype(torch.float64)), got {type(self).__name__}"
                             + (f" with program_dtype {self._program_dtype}" if ours else "")
-                            + ": the fp32 program is train.Trainer's / predict.Predictor's")
+                            + ": the fp32 program is train.Trainer's / predict.Predictor's"
+                            + ("; a float64 Graphnetwork_phonon is train64.GraphnetworkTrainer64's / predict.Predictor64's"
+                               if isinstance(self, GraphnetworkBase) else ""))
 
     def _check_train_flags(self):
         pass          # (kept for callers of round 1: attention dropout is implemented now)
@@ -187,10 +189,21 @@ class GraphnetworkBase(FusedModel):
 
     def _require_fp32_program(self, who: str) -> None:
         """train.Trainer / predict.Predictor run the fp32 program on the flat buffer: a float64 Graphnetwork_phonon (float64
-        live parameters: functional64) stays with model(batch), loss.backward() and torch.optim.AdamW."""
+        live parameters: functional64) is train64.GraphnetworkTrainer64's and predict.Predictor64's."""
         if self._flat_dtype(None) == torch.float64:
             raise DosxError(f"{who} runs the fp32 program; this {type(self).__name__} has float64 parameters and runs the "
-                            f"float64 one: train it with model(batch), loss.backward() and torch.optim.AdamW")
+                            f"float64 one: train it with train64.GraphnetworkTrainer64 and predict with predict.Predictor64")
+
+    def _require_f64_baseline(self, who: str) -> None:
+        """The float64 drivers of the GNN-only baseline (train64.GraphnetworkTrainer64, predict.Predictor64) take a
+        Graphnetwork_phonon whose live parameters are all float64 (``model.double()``) and whose hidden width the float64 program
+        takes, and nothing else; called on the class (``GraphnetworkBase._require_f64_baseline(model, who)``) for whatever they
+        are given."""
+        ours = isinstance(self, GraphnetworkBase) and self._cfg.kind == "phonon"
+        if not (ours and self._flat_dtype(None) == torch.float64):          # (mixed dtypes, hidden > MAX_HIDDEN: its own DosxError)
+            raise DosxError(f"{who} drives a Graphnetwork_phonon with float64 parameters (model.double()), got "
+                            f"{type(self).__name__}" + (" with fp32 parameters: that is train.Trainer's / predict.Predictor's"
+                                                        if ours else ""))
 
     def _program_fwd(self, P, g, m, factored_head: bool = False):
         if P["embeddings.weight"].dtype == torch.float64:

@@ -1,6 +1,7 @@
 """Checkpoint I/O (the reference has none).  The model part is a plain ``state_dict`` in the
 reference's key layout, so weights move both ways between this build and upstream-trained
-models; the optimizer part is ``Trainer.state_dict()`` (AdamW moments keyed by parameter name)."""
+models; the optimizer part is the trainer's ``state_dict()`` - ``train.Trainer``, ``train64.Trainer64`` and
+``train64.GraphnetworkTrainer64`` share one vocabulary (AdamW moments keyed by parameter name, in the flat buffer's dtype)."""
 from __future__ import annotations
 
 from typing import Optional

@@ -36,7 +36,8 @@ def _pool_sum(x: torch.Tensor, g, num_graphs: int) -> torch.Tensor:
 
 
 def test_phonon(model, data_loader: Iterable, criterion: Optional[Callable] = None, r2: Callable = r2, device=None):
-    """`utils.py:117-143`.  Returns (rmse, mse, mae, r2), each the mean over batches of the per-batch value."""
+    """`utils.py:117-143`.  Returns (rmse, mse, mae, r2), each the mean over batches of the per-batch value.  A model with ONE
+    output (Graphnetwork_phonon, or a predictor of it: its forward returns ``dos`` alone) is measured on that output."""
     criterion = criterion if criterion is not None else torch.nn.L1Loss()
     model.eval()
     n = 0
@@ -45,7 +46,8 @@ def test_phonon(model, data_loader: Iterable, criterion: Optional[Callable] = No
         for batch in data_loader:
             if device is not None:
                 batch.to(device)
-            preds_global, _, preds_system = model(batch)
+            out = model(batch)
+            preds_global, preds_system = (out, out) if torch.is_tensor(out) else (out[0], out[2])
             y = batch.phdos.reshape(preds_global.shape[0], -1).to(preds_system.dtype)
             mse_sys = ((y - preds_system) ** 2).mean(dim=1)
             rmse = rmse + torch.sqrt(mse_sys).mean()

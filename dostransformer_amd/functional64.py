@@ -14,12 +14,20 @@ train64.Trainer64 records this program (ops.RECORDER) and replays it on static b
 through ops.alloc64 / ops.keep_alive, and the torch casts in its body (``_f64``, ``g.system.to(int32)``, ``ddos.to(float64)``)
 hand back their argument when it already has the dtype and layout the kernels read - which the slot buffers have.
 
-The DOSTransformer_phonon program is padding-safe: it runs on a ghost-padded batch (``batch.pad_batch``, or a bucket filled by
-``DeviceDataset.collate_into``).  Forward, no kernel reduces across rows other than over a node's own edges (CSR row pointers) or
-a crystal's own atoms (``graph_ptr``), so the real rows are bitwise those of the unpadded batch; backward, the sum pool's
-gradient reads a spare zero row B for the ghost nodes (``_dpool_rows``) and every gradient that reaches a ghost row is an exact
-zero, so the parameter gradients differ from the unpadded ones only by how the row sums of ``wgrad64`` / ``colsum64`` are
-grouped.  (Graphnetwork_phonon's program is not: its sum-pool backward still indexes [B, H] rows.)
+The DOSTransformer_phonon program and the FACTORED Graphnetwork_phonon program (``factored_head=True``) are padding-safe: they
+run on a ghost-padded batch (``batch.pad_batch``, or a bucket filled by ``DeviceDataset.collate_into``).  Forward, no kernel
+reduces across rows other than over a node's own edges (CSR row pointers) or a crystal's own atoms (``graph_ptr``), so the real
+rows are bitwise those of the unpadded batch; backward, the sum pool's gradient reads a spare zero row B for the ghost nodes
+(``_dpool_rows``) and every gradient that reaches a ghost row is an exact zero, so the parameter gradients differ from the
+unpadded ones only by how the row sums of ``wgrad64`` / ``colsum64`` are grouped.  (Graphnetwork_phonon's default, unfactored
+program is not: its sum-pool backward still indexes [B, H] rows.)
+
+Graphnetwork_phonon has two programs.  The default one is what ``model(batch)`` runs: the head's first Linear as one product
+over the S * B rows cat[emb[s] | graph[b]], with a torch transpose at either end - it is the autograd path and not recordable.
+``factored_head=True`` (train64.GraphnetworkTrainer64, predict.Predictor64) runs the head on its rank structure, as
+``functional.graphnetwork_fwd(factored_head=True)`` does in fp32: E1 = emb . W0[:, :H]^T + b0 and C = graph . W0[:, H:]^T, then
+one float64 launch each way (csrc/pair_head_f64.hip) that reads and writes dos / ddos as [B, S].  It holds no tensor of S * B
+rows and no torch kernel, so it is recorded and replayed like the DOSTransformer_phonon program.
 """
 from __future__ import annotations
 
@@ -33,8 +41,8 @@ from . import functional as Fn
 from . import ops
 from .ops import (ACT64_LEAKY, ACT64_PRELU, ACT64_RELU, act_bwd64, alloc64, attention64, attention_bwd64, colsum64,
                   dense_rows64, dense_rows_bwd64, edge_feat_sh1_64, gather_bwd64, gemm64, graph_pool64, index_sum64,
-                  layernorm64, layernorm_bwd64, reduce_rows64, rows_add64, rowmap, seg64, segment_mean64, segment_mean_bwd64,
-                  wgrad64)
+                  layernorm64, layernorm_bwd64, pair_head_bwd64, pair_head_fwd64, pair_head_partial_rows, reduce_rows64, rows_add64,
+                  rowmap, seg64, segment_mean64, segment_mean_bwd64, wgrad64)
 
 Params = Dict[str, torch.Tensor]
 
@@ -157,10 +165,85 @@ def _gnn_trunk_bwd(P: Params, G: Params, cfg, m: GraphMeta, ctx, dx: torch.Tenso
     _mlp_prelu_bwd(P, G, enc, cx, dx)
 
 
-def graphnetwork_phonon_fwd(P: Params, cfg, g, m: GraphMeta):
-    """-> (dos [B, S], saved context)."""
+def _is_padded(g) -> bool:
+    """A ghost-padded batch (batch.pad_batch) or bucket (slots.Slot.empty): it carries its real node count."""
+    return getattr(g, "real_nodes", None) is not None
+
+
+def _dpool_rows(dev, B: int, H: int, padded: bool) -> torch.Tensor:
+    """The sum pool's gradient buffer, [B + 1, H]: the GEMM writes rows [0, B); row B is what a ghost node's ``node_graph``
+    entry (= B, batch.pad_batch) gathers.  It is zeroed here by torch - once, when the buffer is made, and so outside a recorded
+    launch list, which keeps the buffer alive and never writes that row again.  An unpadded batch never reads it."""
+    dpool = alloc64(dev, B + 1, H)
+    if padded:
+        dpool[B:].zero_()
+    return dpool
+
+
+class _FactoredCtx64(NamedTuple):
+    """graphnetwork_phonon_fwd(factored_head=True).  padded: the batch is ghost-padded (_dpool_rows)."""
+    trunk: tuple
+    xL: torch.Tensor
+    pool: torch.Tensor
+    graph: torch.Tensor
+    E1: torch.Tensor
+    C: torch.Tensor
+    padded: bool
+
+
+def _pair_head_fwd(P: Params, cfg, B: int, graph: torch.Tensor):
+    """out_layer on cat[emb[s] | graph[b]] over all (s, b), on its rank structure -> (dos [B, S], E1 [S, H], C [B, H]): the first
+    Linear is E1[s] + C[b], one small product with each column half of its weight; the rest is one launch."""
+    H, S, dev = cfg.H, cfg.S, graph.device
+    W0 = P["out_layer.0.weight"]
+    E1 = gemm64(S, H, [seg64(P["embeddings.weight"])], W0[:, :H], alloc64(dev, S, H), bias=P["out_layer.0.bias"])
+    C = gemm64(B, H, [seg64(graph)], W0[:, H:], alloc64(dev, B, H))
+    dos = alloc64(dev, B, S)
+    pair_head_fwd64(E1, C, P["out_layer.2.weight"], P["out_layer.2.bias"], dos, 0.01)
+    return dos, E1, C
+
+
+def _pair_head_bwd(P: Params, G: Params, cfg, B: int, graph, E1, C, ddos: torch.Tensor) -> torch.Tensor:
+    """Backward of _pair_head_fwd: the gradients of out_layer.* and embeddings.weight; returns dL/dgraph [B, H]."""
+    H, S, dev = cfg.H, cfg.S, E1.device
+    emb, W0, dW0 = P["embeddings.weight"], P["out_layer.0.weight"], G["out_layer.0.weight"]
+    dE1, dC = alloc64(dev, S, H), alloc64(dev, B, H)
+    part = alloc64(dev, pair_head_partial_rows(S, B), H + 1)
+    pair_head_bwd64(ddos.to(torch.float64).contiguous(), E1, C, P["out_layer.2.weight"], dE1, dC, part, 0.01)
+    colsum64(part[:, :H], G["out_layer.2.weight"])
+    colsum64(part[:, H:], G["out_layer.2.bias"])
+    wgrad64(S, dE1, [seg64(emb)], dW0[:, :H])                                          # the two column halves, written in place
+    wgrad64(B, dC, [seg64(graph)], dW0[:, H:])
+    colsum64(dE1, G["out_layer.0.bias"])
+    gemm64(S, H, [seg64(dE1)], W0[:, :H], G["embeddings.weight"], w_layout=1)
+    return gemm64(B, H, [seg64(dC)], W0[:, H:], alloc64(dev, B, H), w_layout=1)
+
+
+def _factored_fwd(P: Params, cfg, g, m: GraphMeta, enc: str):
+    H, B = cfg.H, m.num_graphs
+    x, ctrunk = _gnn_trunk_fwd(P, cfg, g, m, enc)
+    pool = graph_pool64(x, m.graph_ptr, B)
+    graph = gemm64(B, H, [seg64(pool)], P["GN_decoder.mlp.0.weight"], alloc64(x.device, B, H), bias=P["GN_decoder.mlp.0.bias"])
+    dos, E1, C = _pair_head_fwd(P, cfg, B, graph)
+    return dos, _FactoredCtx64(ctrunk, x, pool, graph, E1, C, _is_padded(g))
+
+
+def _factored_bwd(P: Params, G: Params, cfg, m: GraphMeta, ctx: _FactoredCtx64, ddos: torch.Tensor) -> None:
+    H, B, N = cfg.H, m.num_graphs, m.num_nodes
+    dev = ctx.E1.device
+    dgraph = _pair_head_bwd(P, G, cfg, B, ctx.graph, ctx.E1, ctx.C, ddos)
+    _linear_grads(G, "GN_decoder.mlp.0", B, dgraph, [seg64(ctx.pool)])
+    dpool = gemm64(B, H, [seg64(dgraph)], P["GN_decoder.mlp.0.weight"], _dpool_rows(dev, B, H, ctx.padded), w_layout=1)
+    _gnn_trunk_bwd(P, G, cfg, m, ctx.trunk, rows_add64(N, dpool, ia=m.node_graph))     # backward of the sum pool
+
+
+def graphnetwork_phonon_fwd(P: Params, cfg, g, m: GraphMeta, factored_head: bool = False):
+    """-> (dos [B, S], saved context).  ``factored_head``: the output head on its rank structure (the module docstring;
+    train64.GraphnetworkTrainer64 / predict.Predictor64) - recordable and padding-safe; the default is the module's own path."""
     H, S, B = cfg.H, cfg.S, m.num_graphs
     enc = "GN_encoder.node_encoder" if g.x.shape[1] == 118 else "GN_encoder.node_encoder_prompt"   # :150-153
+    if factored_head:
+        return _factored_fwd(P, cfg, g, m, enc)
     x, ctrunk = _gnn_trunk_fwd(P, cfg, g, m, enc)
     pool = graph_pool64(x, m.graph_ptr, B)
     graph = gemm64(B, H, [seg64(pool)], P["GN_decoder.mlp.0.weight"], alloc64(x.device, B, H), bias=P["GN_decoder.mlp.0.bias"])
@@ -174,8 +257,13 @@ def graphnetwork_phonon_fwd(P: Params, cfg, g, m: GraphMeta):
     return dos, (ctrunk, pool, (head, graph), hid_pre, hid)     # graph: keeps the memory `head` points to
 
 
-def graphnetwork_phonon_bwd(P: Params, G: Params, cfg, m: GraphMeta, saved, ddos: torch.Tensor) -> None:
+def graphnetwork_phonon_bwd(P: Params, G: Params, cfg, m: GraphMeta, saved, ddos: torch.Tensor,
+                            factored_head: bool = False) -> None:
     """Writes the gradient of every live parameter into G from ddos [B, S]."""
+    if factored_head != isinstance(saved, _FactoredCtx64):
+        raise ValueError("graphnetwork_phonon_bwd: factored_head differs from the forward pass that made this context")
+    if factored_head:
+        return _factored_bwd(P, G, cfg, m, saved, ddos)
     ctrunk, pool, (head, _), hid_pre, hid = saved
     H, S, B, N = cfg.H, cfg.S, m.num_graphs, m.num_nodes
     dev = ddos.device
@@ -198,21 +286,6 @@ def graphnetwork_phonon_bwd(P: Params, G: Params, cfg, m: GraphMeta, saved, ddos
 
 
 # ---- DOSTransformer_phonon ------------------------------------------------------------------------------------------------
-def _is_padded(g) -> bool:
-    """A ghost-padded batch (batch.pad_batch) or bucket (slots.Slot.empty): it carries its real node count."""
-    return getattr(g, "real_nodes", None) is not None
-
-
-def _dpool_rows(dev, B: int, H: int, padded: bool) -> torch.Tensor:
-    """The sum pool's gradient buffer, [B + 1, H]: the GEMM writes rows [0, B); row B is what a ghost node's ``node_graph``
-    entry (= B, batch.pad_batch) gathers.  It is zeroed here by torch - once, when the buffer is made, and so outside a recorded
-    launch list, which keeps the buffer alive and never writes that row again.  An unpadded batch never reads it."""
-    dpool = alloc64(dev, B + 1, H)
-    if padded:
-        dpool[B:].zero_()
-    return dpool
-
-
 class _EncoderLayer64(NamedTuple):
     """One layer of _encoder_fwd: LayerNorm 0 of the queries (normalised rows, 1 / std, output), the attention dropout mask or
     None, the softmax weights, LayerNorm 1 of the attention half's output (normalised rows, 1 / std, output), relu(fc1)."""

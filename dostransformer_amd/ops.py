@@ -2029,3 +2029,40 @@ def adamw64(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, 
         raise ValueError(f"adamw64: n = {n} of buffers with {p.numel()}, {g.numel()}, {m.numel()}, {v.numel()} elements")
     _call("dosx_adamw_f64", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), int(n), float(lr), float(beta1), float(beta2),
           float(eps), float(weight_decay), int(step), _stream())
+
+
+# float64 pair head of Graphnetwork_phonon (csrc/pair_head_f64.hip), used by functional64's factored program
+def _pair_head_desc64(who: str, e1, c, w2, slope: float):
+    """The operands both float64 pair-head launches read: e1 [S,H], c [B,H], w2 [H] (or [1,H], nn.Linear(H, 1).weight)."""
+    _chk_c64(e1, c, w2)
+    if e1.dim() != 2 or c.dim() != 2 or e1.shape[1] != c.shape[1] or w2.numel() != e1.shape[1]:
+        raise ValueError(f"{who}: e1 [S,H], c [B,H], w2 [H], got {tuple(e1.shape)}, {tuple(c.shape)}, {tuple(w2.shape)}")
+    d = _lib.PairHead64()
+    d.S, d.B, d.H, d.slope = int(e1.shape[0]), int(c.shape[0]), int(e1.shape[1]), float(slope)
+    d.e1, d.c, d.w2 = e1.data_ptr(), c.data_ptr(), w2.data_ptr()
+    return d
+
+
+def pair_head_fwd64(e1, c, w2, b2, dos, slope: float = 0.01) -> None:
+    """dos[b, s] = b2 + sum_h w2[h] * leaky(e1[s, h] + c[b, h]) in float64, one launch (include/dosx.h: DosxPairHead64); dos: [B,S]."""
+    d = _pair_head_desc64("pair_head_fwd64", e1, c, w2, slope)
+    _chk_c64(b2, dos)
+    if tuple(dos.shape) != (d.B, d.S) or b2.numel() != 1:
+        raise ValueError(f"pair_head_fwd64: dos must be a contiguous [B,S] = [{d.B},{d.S}] and b2 one element, got "
+                         f"{tuple(dos.shape)}, {tuple(b2.shape)}")
+    d.b2, d.dos = b2.data_ptr(), dos.data_ptr()
+    _call("dosx_pair_head_fwd_f64", C.byref(d), _stream())
+
+
+def pair_head_bwd64(ddos, e1, c, w2, de1, dc, partials, slope: float = 0.01) -> None:
+    """The backward of pair_head_fwd64 from ddos [B,S] in one launch: de1 [S,H], dc [B,H] and ``partials``
+    [pair_head_partial_rows(S, B), H + 1] whose column sums (colsum64) are dw2 (H) and db2."""
+    d = _pair_head_desc64("pair_head_bwd64", e1, c, w2, slope)
+    _chk_c64(ddos, de1, dc, partials)
+    rows = pair_head_partial_rows(d.S, d.B)
+    if not (tuple(ddos.shape) == (d.B, d.S) and de1.shape == e1.shape and dc.shape == c.shape
+            and tuple(partials.shape) == (rows, d.H + 1)):
+        raise ValueError(f"pair_head_bwd64: contiguous ddos [B,S], de1 [S,H], dc [B,H], partials [{rows},H+1] wanted, got "
+                         f"{tuple(ddos.shape)}, {tuple(de1.shape)}, {tuple(dc.shape)}, {tuple(partials.shape)}")
+    d.ddos, d.de1, d.dc, d.partials = ddos.data_ptr(), de1.data_ptr(), dc.data_ptr(), partials.data_ptr()
+    _call("dosx_pair_head_bwd_f64", C.byref(d), _stream())

@@ -25,6 +25,11 @@ bitwise the eval-mode ``functional.graphnetwork_fwd(factored_head=True)`` (the o
 ``Predictor64(model)`` is the same for a ``DOSTransformer_phonon`` set to the float64 program
 (``model.double().set_program_dtype(torch.float64)``): the float64 forward program on ghost-padded buckets, outputs in float64,
 bitwise those of ``model(batch)``.  Per-crystal keys stay the module's own switch (``model.set_per_crystal_keys``).
+
+``Predictor64(model)`` also takes a ``Graphnetwork_phonon`` with float64 parameters (``model.double()``), as ``Predictor`` takes
+the fp32 baselines: it returns ``dos`` in float64, bitwise ``functional64.graphnetwork_phonon_fwd(factored_head=True)`` (the
+output head on its rank structure, as ``train64.GraphnetworkTrainer64`` runs it) on the ghost-padded bucket, and
+``batch_independent`` is True.
 """
 from __future__ import annotations
 
@@ -225,19 +230,43 @@ class Predictor64(_Predictor):
     module's per-crystal-keys switch and ``functional64.SOFTMAX64`` are part of a slot's key."""
     _dtype = torch.float64
 
+    def __init__(self, model, bucket=(8, 128)):
+        super().__init__(model, bucket)
+        self._baseline = isinstance(model, GraphnetworkBase)
+
     @staticmethod
     def _require(model) -> None:
-        DOSTransformerBase._require_f64_program(model, "Predictor64")
+        if isinstance(model, GraphnetworkBase):
+            GraphnetworkBase._require_f64_baseline(model, "Predictor64")
+        else:
+            DOSTransformerBase._require_f64_program(model, "Predictor64")
 
     def _key_tail(self) -> tuple:
+        if self._baseline:                     # no attention: the (padded) shape alone decides the launch list
+            return ()
         return (bool(self.model.per_crystal_keys), bool(F64.SOFTMAX64))
 
     def _tables(self, ds):
         return ds._f64_tables()
 
+    def _width_batch(self, ds):
+        if not self._baseline:
+            return None
+        from .train import _Width            # (which node encoder is live follows the dataset's node-feature width)
+        return _Width(int(ds._f64_tables()["x"].shape[1]))
+
+    def _outputs(self, slot: Slot, n_real: int):
+        return slot.out[0] if self._baseline else super()._outputs(slot, n_real)
+
+    def _eval_outputs(self, slot: Slot):
+        return (slot.out[0], slot.keep.xL) if self._baseline else super()._eval_outputs(slot)
+
     def _forward(self, fp, slot):
         g, B = slot.g, slot.g.meta.num_graphs
         F64.require_replayable(g, slot.fields, fp.flat.device, "Predictor64")
+        if self._baseline:
+            dos, ctx = F64.graphnetwork_phonon_fwd(fp.P, self.model._cfg, g, g.meta, factored_head=True)
+            return (dos,), ctx
         dos, xL, ctx = F64.dostransformer_phonon_fwd(fp.P, self.model._cfg, g, g.meta, drop=None,
                                                      per_crystal_keys=self.model.per_crystal_keys)
         return (dos[:B], xL, dos[B:]), ctx

@@ -15,6 +15,10 @@ batch is run as it is.  ``step_dataset(ds, indices)`` collates a selection of a 
 replays - and ``promote`` lets a bucket that is asked for the first time run in a slightly larger live one instead of
 recording.  ``predict.Predictor64`` is the forward-only counterpart.
 
+``GraphnetworkTrainer64`` is the same step for the GNN-only baseline ``Graphnetwork_phonon`` with float64 parameters (the
+reference trains every phonon embedder in float64, `main_phDOS.py:15-16,70-72`): the factored float64 program
+(``functional64.graphnetwork_phonon_fwd(factored_head=True)``), the loss entry on the model's one output, the flat AdamW.
+
 Limits: single GPU (no ``dist``), no HIP-graph mode.
 """
 from __future__ import annotations
@@ -27,10 +31,10 @@ import torch
 from . import functional64 as F64
 from . import ops
 from ._lib import DosxError
-from ._models import DOSTransformerBase
+from ._models import DOSTransformerBase, GraphnetworkBase
 from .batch import GraphMeta, bucket_sizes, graph_meta, pad_batch
 from .slots import Slot, SlotCache
-from .train import _AdamWState
+from .train import _AdamWState, _Width
 
 
 class Trainer64(_AdamWState, SlotCache):
@@ -50,9 +54,11 @@ class Trainer64(_AdamWState, SlotCache):
     time in a live larger one instead of recording it (``slot_promoted`` counts those steps; 0: never).
     """
 
+    _who = "Trainer64"            # what this driver calls itself in its refusals
+
     def __init__(self, model, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2, betas=(0.9, 0.999),
                  eps: float = 1e-8, replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0):
-        DOSTransformerBase._require_f64_program(model, "Trainer64")
+        self._require_model(model)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, tuple(betas), eps
         self.replay = bool(replay)
         self.max_slots = int(max_slots)
@@ -72,16 +78,21 @@ class Trainer64(_AdamWState, SlotCache):
         self._seen = {}
 
     # ---- the step ------------------------------------------------------------------------------------------------------
+    def _require_model(self, model) -> None:
+        """The one model check of this driver - at construction and again in front of every step: a DOSTransformer_phonon set
+        to the float64 program.  A subclass that drives another module overrides it."""
+        DOSTransformerBase._require_f64_program(model, self._who)
+
     def _refuse(self, g) -> None:
         """What a step cannot run on - raised before anything (the dropout seed included) has changed."""
-        DOSTransformerBase._require_f64_program(self.model, "Trainer64")
+        self._require_model(self.model)
         if self.bucket is None and getattr(g, "real_nodes", None) is not None:
-            raise DosxError("Trainer64: ghost-padded batches (batch.pad_batch) are refused without bucket=(node_step, "
+            raise DosxError(f"{self._who}: ghost-padded batches (batch.pad_batch) are refused without bucket=(node_step, "
                             "edge_step) - slots are keyed by the exact shape of an unpadded batch")
 
-    def _prepare(self, g):
+    def _prepare(self, g, ds=None):
         """-> (flat parameters, dropout operand); everything that may touch the host or torch's RNG (first use: flattening, the
-        dropout seed) happens here, in front of any recording."""
+        dropout seed) happens here, in front of any recording.  ``g`` is None for a dataset step, which passes ``ds``."""
         model = self.model
         dev = model._module_device()
         fp = model._ensure_flat(dev, g)
@@ -135,7 +146,7 @@ class Trainer64(_AdamWState, SlotCache):
 
     def _slot_step(self, fp, g, m: GraphMeta, drop) -> torch.Tensor:
         if m.edge_perm is not None:
-            raise ValueError("Trainer64(replay=True) needs batches with destination-sorted edges (collate(sort_edges=True))")
+            raise ValueError(f"{self._who}(replay=True) needs batches with destination-sorted edges (collate(sort_edges=True))")
         if self.bucket is not None and getattr(g, "real_nodes", None) is None:       # not padded yet: pad on the fly
             g = pad_batch(g, *bucket_sizes(m.num_nodes, m.num_edges, *self.bucket))
             m = g.meta
@@ -154,7 +165,7 @@ class Trainer64(_AdamWState, SlotCache):
     def _record(self, slot: Slot, fp, drop) -> None:
         """Run the step once on the slot's static buffers while recording every launch."""
         g, m = slot.g, slot.g.meta
-        F64.require_replayable(g, slot.fields, fp.flat.device, "Trainer64")
+        F64.require_replayable(g, slot.fields, fp.flat.device, self._who)
         with ops.recording_scope():
             ops.RECORDER.begin()
             slot.loss, slot.out = self._program(fp, g, m, drop)
@@ -170,12 +181,12 @@ class Trainer64(_AdamWState, SlotCache):
         serves a whole dataset (with per-crystal keys and no dropout the numbers do not depend on it)."""
         if not (self.replay and self.bucket is not None):
             return self.step(ds.collate(indices, n_max=n_max))
-        DOSTransformerBase._require_f64_program(self.model, "Trainer64")
+        self._require_model(self.model)
         idx, N, E, n_max = ds.bucket_dims(indices, n_max)
         B = int(idx.shape[0])
         n_pad, e_pad = bucket_sizes(N, E, *self.bucket)
         self._bump_dropout_seed()
-        fp, drop = self._prepare(None)
+        fp, drop = self._prepare(None, ds)
         key = self._key(n_pad, e_pad, B, n_max, drop)
         slot = self._lookup(key, allow_promote=True)
         fresh = slot is None
@@ -207,3 +218,70 @@ class Trainer64(_AdamWState, SlotCache):
         loss = self.forward_backward(g, _bump=False)
         self.optimizer_step()
         return loss
+
+
+class GraphnetworkTrainer64(Trainer64):
+    """``Trainer64`` for the GNN-only baseline: AdamW training of a ``Graphnetwork_phonon`` whose live parameters are all float64
+    (``model.double()``, hidden <= functional64.MAX_HIDDEN), all on libdosx.  The step is the factored float64 program
+    (``functional64.graphnetwork_phonon_fwd / _bwd(factored_head=True)``: the output head on its rank structure,
+    csrc/pair_head_f64.hip), the float64 loss entry in its one-output use (``ps = pg``, ``beta = 0``: the loss is
+    ``sqrt(mean (dos - y)^2)`` exactly, `main_phDOS.py:109-111`) and the flat float64 AdamW - what ``model(batch)`` -> torch loss
+    -> ``loss.backward()`` -> ``torch.optim.AdamW`` computes, to float64 rounding.  ``last_outputs`` is ``dos`` [B, S].
+
+    The model has ONE output, so there is no ``beta`` to weigh (passing one raises), no attention - no per-crystal keys, no
+    dropout, no softmax switch: a slot's key is its (padded) shape.  Which node encoder is dead (``node_encoder`` against
+    ``node_encoder_prompt``) follows the node-feature width and is fixed by the first batch or dataset; a batch of the other
+    width is refused.  ``replay``, ``bucket``, ``promote``, ``step_dataset``, ``state_dict`` / ``load_state_dict`` and
+    ``max_slots`` are ``Trainer64``'s.  Limits: single GPU, no HIP-graph mode."""
+    _who = "GraphnetworkTrainer64"
+
+    def __init__(self, model, lr: float = 1e-4, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
+                 replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0, **unknown):
+        if "beta" in unknown:
+            raise ValueError(f"GraphnetworkTrainer64: beta={unknown['beta']} - the model has ONE output and its loss no second "
+                             f"term to weigh")
+        if unknown:
+            raise TypeError(f"GraphnetworkTrainer64() got an unexpected keyword argument {sorted(unknown)[0]!r}")
+        super().__init__(model, lr=lr, beta=1.0, weight_decay=weight_decay, betas=betas, eps=eps, replay=replay,
+                         max_slots=max_slots, bucket=bucket, promote=promote)
+        self._dead = None                 # the dead-parameter set of the first batch's node-feature width
+
+    def _require_model(self, model) -> None:
+        GraphnetworkBase._require_f64_baseline(model, self._who)
+
+    def _flat_for(self, dev, g, width: Optional[int] = None):
+        """The model's flat parameters for a batch (or, step_dataset, an input width): which node encoder is dead follows the
+        width, and the first batch fixes it for this trainer (as train.Trainer._flat_for does for the fp32 baselines)."""
+        model = self.model
+        if g is None:
+            g = _Width(width)
+        dead = model._extra_dead(g)
+        if self._dead is None:
+            self._dead = dead
+        elif dead != self._dead:
+            raise DosxError(f"{self._who}: this batch has node features of width {g.x.shape[1]}, which selects the other node "
+                            f"encoder than the trainer's first batch did - its dead-parameter set (and the optimizer's layout) "
+                            f"is fixed by the first batch")
+        return model._ensure_flat(dev, g)
+
+    def _prepare(self, g, ds=None):
+        dev = self.model._module_device()
+        fp = self._flat_for(dev, g, None if ds is None else int(ds._f64_tables()["x"].shape[1]))
+        self._state(fp)
+        return fp, None
+
+    def _program(self, fp, g, m: GraphMeta, drop):
+        cfg, dev = self.model._cfg, fp.flat.device
+        B, S = m.num_graphs, cfg.S
+        dos, ctx = F64.graphnetwork_phonon_fwd(fp.P, cfg, g, m, factored_head=True)
+        y = F64._f64(g.phdos).reshape(B, S)
+        ddos, scratch, loss = ops.alloc64(dev, B, S), ops.alloc64(dev, B, S), ops.alloc64(dev, 1)
+        ops.loss_phonon64(dos, dos, y, 0.0, ddos, scratch, loss)
+        F64.graphnetwork_phonon_bwd(fp.P, fp.G, cfg, m, ctx, ddos, factored_head=True)
+        return loss[0], dos
+
+    def _set_outputs(self, out, n_real: Optional[int]) -> None:
+        self.last_outputs = out
+
+    def _key(self, n: int, e: int, B: int, n_max: int, drop) -> tuple:
+        return (n, e, B, n_max)

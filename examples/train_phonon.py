@@ -23,9 +23,16 @@ the GPU straight into its bucket's static buffers (Trainer64.step_dataset) and e
 
 --embedder graphnetwork trains the reference's GNN-only baseline (main_phDOS.py:74-76) through the fp32 Trainer and Predictor: its
 output head runs on its rank structure, the loss is the driver's on its one output, and evaluation goes through
-evaluate.test_per_crystal (no attention: batched passes ARE the batch-size-1 numbers).  fp32 only.
+evaluate.test_per_crystal (no attention: batched passes ARE the batch-size-1 numbers).
 
     python examples/train_phonon.py --embedder graphnetwork --epochs 5
+
+--embedder graphnetwork --float64 trains the baseline as the reference does (main_phDOS.py:15-16,70-72): model(batch), the driver's
+loss on its one output, loss.backward(), torch.optim.AdamW.  With --fused the same step runs through train64.GraphnetworkTrainer64
+(the float64 head on its rank structure, float64 loss and AdamW kernels), with --replay from recorded launch lists per shape
+bucket and evaluation through predict.Predictor64.
+
+    python examples/train_phonon.py --embedder graphnetwork --float64 --fused --replay --epochs 2 --crystals 128 --hidden 64
 """
 import argparse
 import os
@@ -73,8 +80,8 @@ def main(argv=None):
     if args.fused and not args.float64:
         ap.error("--fused selects the float64 trainer: use it with --float64 (the fp32 run is fused already)")
     baseline = args.embedder == "graphnetwork"
-    if baseline and (args.float64 or args.per_crystal_keys or args.beta != 1.0):
-        ap.error("--embedder graphnetwork: the fused fp32 path only (one output, no attention): no --float64, --per-crystal-keys, --beta")
+    if baseline and (args.per_crystal_keys or args.beta != 1.0):
+        ap.error("--embedder graphnetwork: one output, no attention: no --per-crystal-keys, --beta")
     if args.replay and not args.fused:
         ap.error("--replay belongs to --float64 --fused (the fp32 run always replays)")
     dev = torch.device("cuda:0")
@@ -137,17 +144,36 @@ def _tester(args, evaluator, ds):
     return lambda name: evaluate.test_phonon(evaluator, ds[name].batches(args.batch_size))
 
 
+def _baseline64(args, dev):
+    from dostransformer_amd.embedder_phDOS.graphnetwork_phonon import Graphnetwork_phonon
+    return Graphnetwork_phonon(args.layers, 118, 4, args.hidden, 51, dev).double().to(dev)
+
+
 def train_float64(args, ds, dev):
     """Eager float64 training: model(batch), loss.backward(), torch.optim.AdamW (the fp32 drivers Trainer / Predictor refuse
-    a float64 module).  evaluate.test_phonon takes the module itself."""
-    model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).double()
-    model = model.set_program_dtype(torch.float64).set_per_crystal_keys(True).to(dev)
+    a float64 module).  evaluate.test_phonon takes the module itself.  --embedder graphnetwork: the baseline's one output under
+    the reference's loss of the batch, ONE rmse over all of its elements (main_phDOS.py:109-111)."""
+    baseline = args.embedder == "graphnetwork"
+    if baseline:
+        model = _baseline64(args, dev)
+    else:
+        model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).double()
+        model = model.set_program_dtype(torch.float64).set_per_crystal_keys(True).to(dev)
     opt = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=1e-2)       # main_phDOS.py:92
     best, history = float("inf"), []
     for epoch in range(args.epochs):
         model.train()
         t0, total, seen = time.perf_counter(), torch.zeros((), dtype=torch.float64, device=dev), 0
         for batch in ds["train"].batches(args.batch_size, shuffle=True, seed=args.seed + epoch):
+            if baseline:
+                dos = model(batch)
+                rmse_all = torch.sqrt(((dos - batch.phdos.reshape(dos.shape).to(torch.float64)) ** 2).mean())
+                opt.zero_grad()
+                rmse_all.backward()
+                opt.step()
+                total += rmse_all.detach() * batch.num_graphs
+                seen += batch.num_graphs
+                continue
             dos_global, _, dos_system = model(batch)
             y = batch.phdos.reshape(dos_global.shape[0], -1).to(torch.float64)
             # the reference's loss of one batch-size-1 sample, for every crystal of the batch; summed, so the gradient is
@@ -177,14 +203,19 @@ def train_float64_fused(args, ds, dev):
     """float64 training through train64.Trainer64: forward program, loss kernel, backward program, flat AdamW - the loss stays
     on the device, one host read per epoch.  --replay: shape buckets as in the fp32 run, every shuffled selection collated on
     the device straight into its bucket (step_dataset, one n_max for the whole dataset - with per-crystal keys the numbers do
-    not depend on it) and evaluation through Predictor64.  The checkpoint carries the optimizer state (Trainer64.state_dict)."""
+    not depend on it) and evaluation through Predictor64.  The checkpoint carries the optimizer state (Trainer64.state_dict).
+    --embedder graphnetwork: the same through train64.GraphnetworkTrainer64 (one output, no keys to switch)."""
     from dostransformer_amd.predict import Predictor64
-    from dostransformer_amd.train64 import Trainer64
-    model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).double()
-    model = model.set_program_dtype(torch.float64).set_per_crystal_keys(True).to(dev)
+    from dostransformer_amd.train64 import GraphnetworkTrainer64, Trainer64
     bucket = (32, 1024)
-    trainer = Trainer64(model, lr=args.lr, beta=args.beta, replay=args.replay, bucket=bucket if args.replay else None,
-                        promote=0.08 if args.replay else 0.0)
+    slots = dict(replay=args.replay, bucket=bucket if args.replay else None, promote=0.08 if args.replay else 0.0)
+    if args.embedder == "graphnetwork":
+        model = _baseline64(args, dev)
+        trainer = GraphnetworkTrainer64(model, lr=args.lr, **slots)
+    else:
+        model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).double()
+        model = model.set_program_dtype(torch.float64).set_per_crystal_keys(True).to(dev)
+        trainer = Trainer64(model, lr=args.lr, beta=args.beta, **slots)
     evaluator = Predictor64(model, bucket=bucket) if args.replay else model       # (the module's per-crystal keys are on)
     run_test = _tester(args, evaluator, ds)
     train = ds["train"]

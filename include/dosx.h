@@ -678,6 +678,24 @@ int dosx_pair_head_partial_rows(int S, int B);
 int dosx_pair_head_fwd(const DosxPairHead* a, dosx_stream_t stream);
 int dosx_pair_head_bwd(const DosxPairHead* a, dosx_stream_t stream);
 
+/* The float64 twin (csrc/pair_head_f64.hip), for the float64 program of Graphnetwork_phonon (functional64, factored_head): the
+ * contract above in double, e1 and c from two dosx_gemm_f64 calls, partials [dosx_pair_head_partial_rows(S, B), H + 1] doubles
+ * whose column sums (dosx_colsum_f64, ld = H + 1) are dw2 and db2.  Every sum is one thread's sequential chain, plus a fixed
+ * 16-lane tree in the forward and the fixed four-term sum of dc: no atomics, the same bits on every run.  e1, c, w2, de1, dc are
+ * 16-byte aligned rows of H doubles; H % 8 == 0, H <= 512, S, B >= 1, S * B * H < 2^31; anything else is refused with -22. */
+typedef struct DosxPairHead64 {
+  int32_t S, B, H;
+  double slope;                                               /* leaky_relu negative slope (0.01) */
+  const double* e1; const double* c;                          /* [S, H], [B, H] */
+  const double* w2; const double* b2;                         /* [H], [1] */
+  double* dos;                                                /* [B, S] OUT (forward) */
+  const double* ddos;                                         /* [B, S] (backward) */
+  double* de1; double* dc;                                    /* [S, H], [B, H] OUT (backward) */
+  double* partials;                                           /* [S, H + 1] OUT (backward) */
+} DosxPairHead64;
+int dosx_pair_head_fwd_f64(const DosxPairHead64* a, dosx_stream_t stream);
+int dosx_pair_head_bwd_f64(const DosxPairHead64* a, dosx_stream_t stream);
+
 /* Split-bf16 GEMM (round 6, csrc/gemm_bf16x3.hip) - OPT-IN: with DOSX_FFN_BF16X3=1 functional.encoder_fwd / encoder_bwd run the
  * plain feed-forward GEMMs through it; by default every program runs dosx_gemm's exact-fp32 kernels:
  *     C[M,N] = epi( A[M,K] . op(W) + bias[N] )      w_layout 0: W is [N][K] (nn.Linear), 1: W is [K][N]
