@@ -281,6 +281,9 @@ def collate(crystals: Iterable[Dict[str, object]], sort_edges: bool = True,
     if "mp_id" in crystals[0]:
         fields["mp_id"] = [c["mp_id"] for c in crystals]
 
+    from . import validate
+    if validate.ENABLED:            # before any metadata is derived from the arrays (a bad index would be a bincount / gather there)
+        validate.check_batch(CrystalBatch(fields, len(crystals)), n_max=n_max, finite=validate.FINITE)
     ei = fields["edge_index"].numpy()
     meta = _build_meta_host(ei, fields["batch"].numpy(), len(crystals), n_max, presorted=False)
     if sort_edges and meta.edge_perm is not None:
@@ -302,6 +305,10 @@ def graph_meta(g, device=None, n_max: Optional[int] = None) -> GraphMeta:
     arrays — the same host round trip the reference pays in ``to_dense_batch``.
     """
     m = getattr(g, _META_KEY, None) if not isinstance(g, CrystalBatch) else g.meta
+    if m is None or (n_max is not None and m.n_max != n_max):
+        from . import validate
+        if validate.ENABLED:        # a batch object seen for the first time: checked before _build_meta_host / ops.csr_build read it
+            validate.check_batch(g, n_max=n_max, finite=validate.FINITE)
     if (m is None or (n_max is not None and m.n_max != n_max)) and torch.is_tensor(g.edge_index) and g.edge_index.is_cuda:
         # foreign batch already on the GPU (the reference's loop: `batch.to(device)` then `model(batch)`,
         # main_eDOS.py:106-109): derive everything on the device; the only host read is the 4-byte n_max, and not

@@ -27,7 +27,11 @@ def _plain(v, where: str):
 
 
 def save(path: str, model: torch.nn.Module, trainer=None, extra: Optional[dict] = None) -> None:
+    """With ``trainer``: its ``check()`` runs first, so a checkpoint is never written on top of a reported exchange stall
+    (``ops.check_exchanges`` raises :class:`DosxError`, nothing is written)."""
     extra = _plain(extra or {}, "extra")
+    if trainer is not None and hasattr(trainer, "check"):
+        trainer.check()
     ckpt = {"format": "dostransformer_amd/1",
             "model": {k: v.detach().cpu() for k, v in model.state_dict().items()},
             "optimizer": trainer.state_dict() if trainer is not None else None,

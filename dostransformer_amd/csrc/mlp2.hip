@@ -509,6 +509,23 @@ __global__ __launch_bounds__(512) void mlp_ln_bwd_kernel(const DosxMlpLnBwd a) {
 typedef int v2i32 __attribute__((ext_vector_type(2)));
 typedef int v4i32_ __attribute__((ext_vector_type(4)));
 
+// STALL REPORT.  The poll below is bounded, so a sibling that never arrives (the grid was not co-resident) costs a wrong tile and
+// not a hung GPU - and that wrong tile must not stay silent.  g_cs_status = {code, kernel id, tile, stalls} is sticky device state,
+// file-local (the library is built without relocatable device code): cs_report_stall counts every report and the first one keeps
+// its kernel and tile (compare-and-swap on the code word).  dosx_exchange_status copies it out / clears it; ops.check_exchanges
+// raises on it.  Nothing is poisoned in between: every number produced after a report and before the next check is untrustworthy.
+__device__ int32_t g_cs_status[4];
+__device__ __forceinline__ void cs_report_stall(const int kernel_id, const int tile) {
+  atomicAdd(&g_cs_status[3], 1);
+  if (atomicCAS(&g_cs_status[0], 0, DOSX_EXCHANGE_STALLED) == 0) {
+    __hip_atomic_store(&g_cs_status[1], kernel_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&g_cs_status[2], tile, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+// KID: the calling kernel's DOSX_EXCHANGE_KERNEL_* id, NS: its siblings per tile (tile = blockIdx.x / NS in all three kernels) -
+// both compile-time, so the arriving path carries no new operand and executes no new memory operation; the report is the cold
+// branch behind the poll, taken only when the poll ended on its bound instead of on the target.
+template <int KID, int NS>
 __device__ __forceinline__ void cs_publish_done_and_wait(int* cnt, const int target) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // this wave's published stores have completed at the coherent level
   __syncthreads();
@@ -516,6 +533,7 @@ __device__ __forceinline__ void cs_publish_done_and_wait(int* cnt, const int tar
     dosx_ticket(cnt);
     int it = 0;
     while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target && ++it < (1 << 21)) __builtin_amdgcn_s_sleep(1);
+    if (it >= (1 << 21)) cs_report_stall(KID, (int)blockIdx.x / NS);
   }
   __syncthreads();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");    // (compiler only: the read-back below stays below)
@@ -602,7 +620,7 @@ __global__ __launch_bounds__(256) void mlp_ln_cs_fwd_kernel(const DosxMlpLn a) {
     }
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2i32, z), rZ, (uint32_t)(((size_t)(m0 + row) * NH + 32 * j + 2 * q) * 4), 0, 16);   // sc1
   }
-  cs_publish_done_and_wait(cnt, NS);
+  cs_publish_done_and_wait<DOSX_EXCHANGE_KERNEL_MLP_LN_CS_FWD, NS>(cnt, NS);
   // ---- row phase on the WHOLE tile (every sibling): LayerNorm statistics (two-pass, like torch), xhat / rstd out (rows dealt
   //      over the siblings), prelu(xhat * gamma + beta) -> T ----
   {
@@ -675,7 +693,7 @@ __global__ __launch_bounds__(256) void mlp_ln_cs_fwd_kernel(const DosxMlpLn a) {
     }
   }
   if (rvalid) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, o), rO, (uint32_t)(((size_t)grow * a.ldo + 16 * j + q) * 4), 0, 16);   // sc1
-  cs_publish_done_and_wait(cnt, 2 * NS);
+  cs_publish_done_and_wait<DOSX_EXCHANGE_KERNEL_MLP_LN_CS_FWD, NS>(cnt, 2 * NS);
   {
     constexpr int LDO = NO + 4, OG = NO / 64;       // out tile [16][NO + 4] in T; float4 groups per lane
     const int rr = min(grow, M - 1);
@@ -778,7 +796,7 @@ __global__ __launch_bounds__(256) void enc_cs_fwd_kernel(const DosxEncCs a) {
     z += b0v;
     if (rvalid) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, z), rZ, (uint32_t)(((size_t)grow * H + 16 * j + q) * 4), 0, 16);   // sc1
   }
-  cs_publish_done_and_wait(cnt, NS);
+  cs_publish_done_and_wait<DOSX_EXCHANGE_KERNEL_ENC_CS_FWD, NS>(cnt, NS);
   // ---- PReLU(z tile) -> T ----
 #pragma unroll
   for (int i = 0; i < OG; ++i) {
@@ -807,7 +825,7 @@ __global__ __launch_bounds__(256) void enc_cs_fwd_kernel(const DosxEncCs a) {
     o += b2v;
     if (rvalid) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, o), rO, (uint32_t)(((size_t)grow * a.ldo + 16 * j + q) * 4), 0, 16);   // sc1
   }
-  cs_publish_done_and_wait(cnt, 2 * NS);
+  cs_publish_done_and_wait<DOSX_EXCHANGE_KERNEL_ENC_CS_FWD, NS>(cnt, 2 * NS);
   // ---- pq: 64 columns of x0 . [Wa | Wb]^T ----
   {
 #pragma unroll
@@ -965,7 +983,7 @@ __global__ __launch_bounds__(256) void mlp_ln_cs_bwd_kernel(const DosxMlpLnBwd a
       const int n = m0 + j + NS * ns;
       if (n < M) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4i32_, v), rS, (uint32_t)(((size_t)n * NH + 4 * c4) * 4), 0, 16);   // sc1
     }
-    cs_publish_done_and_wait(cnt, NS * ++xphase);
+    cs_publish_done_and_wait<DOSX_EXCHANGE_KERNEL_MLP_LN_CS_BWD, NS>(cnt, NS * ++xphase);
     // ---- part 3: 16 columns of dx = res + res2 + aggS Wa + aggD Wb (this wave: H of the 4H reduction) ----
     const int sgp = wave >> 1, kl0 = (wave & 1) * H;
     if (sgp == 0) {
@@ -990,7 +1008,7 @@ __global__ __launch_bounds__(256) void mlp_ln_cs_bwd_kernel(const DosxMlpLnBwd a
       for (int w = 0; w < 4; ++w) o += Rd[(w * 16 + row) * LDR + q];
       if (rvalid) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, o), rY, (uint32_t)(((size_t)grow * a.lddy + 16 * j + q) * 4), 0, 16);   // sc1
     }
-    cs_publish_done_and_wait(cnt, NS * ++xphase);
+    cs_publish_done_and_wait<DOSX_EXCHANGE_KERNEL_MLP_LN_CS_BWD, NS>(cnt, NS * ++xphase);
 #pragma unroll
     for (int i = 0; i < OG; ++i)
       st4(Ys + row * LDY + 4 * q + 64 * i,
@@ -1061,7 +1079,7 @@ __global__ __launch_bounds__(256) void mlp_ln_cs_bwd_kernel(const DosxMlpLnBwd a
     }
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2i32, z), rZ, (uint32_t)(((size_t)(m0 + row) * NH + 32 * j + 2 * q) * 4), 0, 16);   // sc1
   }
-  cs_publish_done_and_wait(cnt, NS * ++xphase);
+  cs_publish_done_and_wait<DOSX_EXCHANGE_KERNEL_MLP_LN_CS_BWD, NS>(cnt, NS * ++xphase);
   // ---- row phase on the whole tile: PReLU backward, LayerNorm backward; dz out (rows dealt over the siblings) and -> T ----
   {
     const float invN = 1.f / (float)NH;
@@ -1149,7 +1167,33 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // hidden / 64 for the NodeModel's shapes (K, NH, NO) = (2, 2, 1) x hidden, hidden in {64, 128, 256}; 0: anything else
 inline int node_shape(int K, int NH, int NO) { return (K == NH && NH == 2 * NO && (NO == 64 || NO == 128 || NO == 256)) ? NO / 64 : 0; }
 
+// the status' way out (dosx_exchange_status) and the test-only way in (dosx_exchange_selftest): one thread each
+__global__ void cs_status_kernel(int32_t* out4, const int clear) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    out4[i] = __hip_atomic_load(&g_cs_status[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (clear) __hip_atomic_store(&g_cs_status[i], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+__global__ void cs_selftest_kernel(const int kernel_id, const int tile) { cs_report_stall(kernel_id, tile); }
+
 }  // namespace
+
+extern "C" int dosx_exchange_status(int32_t* out4, int clear, dosx_stream_t stream) {
+  DOSX_CHECK_ARG(out4 != nullptr, "dosx_exchange_status: null output (4 int32 words of device memory)");
+  hipLaunchKernelGGL(cs_status_kernel, dim3(1), dim3(1), 0, to_stream(stream), out4, clear);
+  DOSX_LAUNCH_CHECK();
+  return 0;
+}
+
+// TEST ONLY: files one report through cs_report_stall - the path a stalled exchange takes - without any exchange stalling
+extern "C" int dosx_exchange_selftest(int kernel_id, int tile, dosx_stream_t stream) {
+  DOSX_CHECK_ARG(kernel_id >= DOSX_EXCHANGE_KERNEL_MLP_LN_CS_FWD && kernel_id <= DOSX_EXCHANGE_KERNEL_MLP_LN_CS_BWD && tile >= 0,
+                 "dosx_exchange_selftest: kernel id %d (1..3) / tile %d (>= 0)", kernel_id, tile);
+  hipLaunchKernelGGL(cs_selftest_kernel, dim3(1), dim3(1), 0, to_stream(stream), kernel_id, tile);
+  DOSX_LAUNCH_CHECK();
+  return 0;
+}
 
 extern "C" int dosx_mlp_ln_supported(int K, int NH, int NO) {
   return K % 128 == 0 && K >= 128 && K <= 512 && NH % 128 == 0 && NH >= 128 && NH <= 512 && NO % 64 == 0 && NO >= 64 &&

@@ -175,6 +175,7 @@ def test_per_crystal(predictor, ds, indices=None, batch_size: int = 64) -> PerCr
             H = x.shape[1]
             ops.graph_pool(x, slot.g.meta.graph_ptr, embeddings[rows].data_ptr(), H, B, H)
     rmse, mse, mae, r2_ = table.mean(0).tolist()                       # the one transfer
+    ops.check_exchanges(dev)            # (the host has just waited for the device: a stalled exchange voids these metrics)
     mp_id = [ds.mp_id[i] for i in idx] if edos and ds.mp_id is not None else None
     return PerCrystalResult(rmse, mse, mae, r2_, table, preds, ys, embeddings, mp_id)
 

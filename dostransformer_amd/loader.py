@@ -14,7 +14,7 @@ from typing import Dict, Iterator, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, validate
 from .batch import SEG_TILE_ROWS, CrystalBatch, GraphMeta, _EDGE_FIELDS, seg_tile_bound, seg_tiles_host
 
 
@@ -32,9 +32,11 @@ class DeviceDataset:
         self.edge_ptr = np.concatenate([[0], np.cumsum(n_edges)]).astype(np.int64)
         srcs, dsts, perms, rpd, rps, invd, edge_feats = [], [], [], [], [], [], {k: [] for k in _EDGE_FIELDS}
         tiles_e, tiles_n, tiles_p, tile_cnt = [], [], [], []     # per-crystal node-aligned row tiles (message GEMM, EPI_SEGSUM)
-        for c in crystals:
+        for ci, c in enumerate(crystals):
             ei = c["edge_index"].numpy().astype(np.int64)
             n = int(c["x"].shape[0])
+            if validate.ENABLED:
+                self._check_crystal(ci, c, ei, n)
             order = np.argsort(ei[1], kind="stable")                      # destination-sorted, like batch.collate
             s, d = ei[0][order], ei[1][order]
             deg_in = np.bincount(d, minlength=n)
@@ -73,6 +75,49 @@ class DeviceDataset:
 
     def __len__(self) -> int:
         return self.num_crystals
+
+    @staticmethod
+    def _check_crystal(ci: int, c: Dict[str, object], ei: np.ndarray, n: int) -> None:
+        """validate.enable(): one crystal's LOCAL arrays against the batch rules (a one-crystal batch), before anything is derived."""
+        one = CrystalBatch({"edge_index": torch.from_numpy(ei), "batch": torch.zeros(n, dtype=torch.int64),
+                            **{k: c[k] for k in validate.FINITE_FIELDS if k in c and torch.is_tensor(c[k])}}, 1)
+        if "system" in c:
+            one["system"] = torch.as_tensor(c["system"]).reshape(1).to(torch.int64)
+        try:
+            validate.check_batch(one, finite=validate.FINITE)
+        except validate.DosxError as e:
+            raise validate.DosxError(f"crystal {ci} of the dataset: {e}") from None
+
+    def validate(self, finite: bool = True, batch_size: int = 4096) -> "validate.Report":
+        """The explicit whole-dataset check: the resident crystals, ``batch_size`` at a time, collated on the device and checked by
+        ``dosx_batch_check`` (rules R1-R7 with sorted edges required, as the dataset stores them), and with ``finite`` every
+        resident floating-point table once as a whole.  Raises :class:`DosxError` on the first violation (indices are those of the
+        offending chunk, whose crystal range the message names); returns the summed :class:`validate.Report` of a clean dataset."""
+        total = validate.empty_report()
+        for i in range(0, self.num_crystals, int(batch_size)):
+            sel = np.arange(i, min(i + int(batch_size), self.num_crystals))
+            try:
+                rep = validate.check_batch(self.collate(sel), require_sorted=True)
+            except validate.DosxError as e:
+                raise validate.DosxError(f"crystals [{sel[0]}, {sel[-1] + 1}) of the dataset: {e}") from None
+            total[0::2] = np.minimum(total[0::2].astype(np.int64) + rep.words[0::2], validate.INT32_MAX)
+        tables = []
+        if finite:
+            tables = [("x", self._x)] + [(k, v) for k, v in self._edge.items()] + \
+                     [(k, v) for k, v in self._graph.items() if v.is_floating_point()]
+        words = validate.empty_report(validate.NUM_RULES + len(tables))
+        words[:2 * validate.NUM_RULES] = total
+        if tables:
+            slots = torch.from_numpy(validate.empty_report(len(tables))).to(self.device)
+            for k, (_, t) in enumerate(tables):
+                validate.finite_check_device(t, slots[2 * k:])
+            words[2 * validate.NUM_RULES:] = slots.cpu().numpy()
+        rep = validate.Report(words, tuple(k for k, _ in tables))
+        bad = [f"{k}: {rep.nonfinite(k)[0]} non-finite elements, first at element {rep.nonfinite(k)[1]} of the table"
+               for k, _ in tables if rep.nonfinite(k)[0]]
+        if bad:
+            raise validate.DosxError("invalid dataset: " + " | ".join(bad))
+        return rep
 
     def collate(self, indices: Sequence[int], n_max: Optional[int] = None) -> CrystalBatch:
         idx = np.asarray(list(indices), np.int64)

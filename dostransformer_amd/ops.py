@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import weakref
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -856,18 +857,21 @@ class _CounterPool:
     def __init__(self):
         self._bufs = {}
         self._graph_owned = []
+        self._recorded = []          # weak references to the counters of recorded programs / captured graphs (zero_fill)
 
     def take(self, device, n: int) -> int:
         n = int(n)
         if RECORDER.active:
             t = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
             RECORDER.keep.append(t)
+            self._recorded.append(weakref.ref(t))
             return t.data_ptr()
         if torch.cuda.is_current_stream_capturing():
             # a captured HIP graph replays for as long as it lives, like a recorded program: counters of its own (the
             # allocation belongs to the graph's memory pool; the zero fill becomes a memset node of the graph)
             t = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
             self._graph_owned.append(t)
+            self._recorded.append(weakref.ref(t))
             return t.data_ptr()
         key = str(device)
         ent = self._bufs.get(key)
@@ -888,8 +892,59 @@ class _CounterPool:
     def poison(self) -> None:
         self._bufs = {}
 
+    def zero_fill(self, device=None) -> None:
+        """A stalled column-split exchange was reported (check_exchanges): its launch left tickets behind.  Synchronise and zero every
+        counter the pool knows - the eager rings and, through weak references, the counters recorded programs and captured graphs
+        own for as long as they live."""
+        torch.cuda.synchronize(device)
+        for ent in self._bufs.values():
+            ent[0].zero_()
+            ent[1] = 0
+        live = []
+        for r in self._recorded:
+            t = r()
+            if t is not None:
+                t.zero_()
+                live.append(r)
+        self._recorded = live
+        torch.cuda.synchronize(device)
+
 
 COUNTERS = _CounterPool()
+
+EXCHANGE_KERNELS = {_abi.DOSX_EXCHANGE_KERNEL_MLP_LN_CS_FWD: "mlp_ln_cs_fwd", _abi.DOSX_EXCHANGE_KERNEL_ENC_CS_FWD: "enc_cs_fwd",
+                    _abi.DOSX_EXCHANGE_KERNEL_MLP_LN_CS_BWD: "mlp_ln_cs_bwd"}
+
+
+def exchange_status(device, clear: bool = False):
+    """The sticky stall status of the column-split exchanges (csrc/mlp2.hip) as four ints ``(code, kernel id, tile, stalls)``:
+    one one-thread launch on the current stream and one 16-byte read-back (which waits for that stream)."""
+    out = torch.empty(4, dtype=torch.int32, device=device)
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.load().dosx_exchange_status(out.data_ptr(), int(bool(clear)), _stream()), "dosx_exchange_status")
+    return tuple(int(v) for v in out.cpu().tolist())
+
+
+def exchange_selftest(device, kernel_id: int, tile: int) -> None:
+    """TEST ONLY: file one stall report for (kernel id, tile) without any exchange stalling (dosx_exchange_selftest)."""
+    with torch.cuda.device(torch.device(device)):
+        _lib.check(_lib.load().dosx_exchange_selftest(int(kernel_id), int(tile), _stream()), "dosx_exchange_selftest")
+
+
+def check_exchanges(device) -> None:
+    """Raise :class:`DosxError` if a column-split exchange reported a stall since the last clean check.  The status is cleared and
+    the counter pool zero-filled first (the stalled launch left tickets behind), so the process can go on - but every number the
+    device produced since the last clean check is untrustworthy: outputs are not poisoned in between."""
+    code, kid, tile, stalls = exchange_status(device)
+    if code == 0:
+        return
+    COUNTERS.zero_fill(device)
+    exchange_status(device, clear=True)
+    raise _lib.DosxError(
+        f"column-split exchange stalled: kernel {EXCHANGE_KERNELS.get(kid, f'#{kid}')}, tile {tile} gave up waiting for its siblings "
+        f"({stalls} stall{'s' if stalls != 1 else ''} reported since the last clean check) and went on with a partly published "
+        f"tile.  Every number produced since the last clean check is untrustworthy: parameters, optimizer state and predictions "
+        f"included.  The status is cleared and the arrival counters are zeroed.")
 
 
 def wgrad_desc(M: int, N: int, dy: Seg, segs: Sequence[Seg], slab: Optional[torch.Tensor], slab_bias: Optional[torch.Tensor],

@@ -65,6 +65,13 @@ class _Predictor:
         self.model.eval()
         return self
 
+    def check(self) -> None:
+        """Raise :class:`DosxError` if a column-split exchange reported a stall since the last clean check (``ops.check_exchanges``);
+        one small read-back: call it once per evaluation."""
+        dev = self.model._module_device()
+        if dev.type == "cuda":
+            ops.check_exchanges(dev)
+
     def _key_tail(self) -> tuple:
         return ()
 

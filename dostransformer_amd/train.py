@@ -107,6 +107,14 @@ class _AdamWState:
         self.lr, self.eps, self.wd = h.get("lr", self.lr), h.get("eps", self.eps), h.get("weight_decay", self.wd)
         self.betas, self.beta = tuple(h.get("betas", self.betas)), h.get("beta", self.beta)
 
+    def check(self) -> None:
+        """Raise :class:`DosxError` if a column-split exchange of any step since the last clean check reported a stall
+        (``ops.check_exchanges``): one small read-back, so call it where the host waits for the device anyway - per evaluation,
+        before a checkpoint - not per step.  A module that is not on the GPU has launched nothing: nothing to check."""
+        dev = self.model._module_device()
+        if dev.type == "cuda":
+            ops.check_exchanges(dev)
+
     def _bump_dropout_seed(self) -> None:
         """Attention dropout draws its masks from a device-resident seed inside the (possibly recorded) program; one bump
         per step, issued here so that it is never part of a recording."""

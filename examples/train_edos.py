@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dostransformer_amd import checkpoint, evaluate, featurize, synth  # noqa: E402
+from dostransformer_amd import checkpoint, evaluate, featurize, synth, validate  # noqa: E402
 from dostransformer_amd.embedder_eDOS.DOSTransformer import DOSTransformer  # noqa: E402
 from dostransformer_amd.loader import DeviceDataset  # noqa: E402
 from dostransformer_amd.predict import Predictor  # noqa: E402
@@ -61,17 +61,31 @@ def parse_args(argv=None):
                     help="N > 0: the batch-size-1 metrics from batched passes of N crystals (evaluate.test_per_crystal, "
                          "per-crystal keys) instead of --eval_batch_size forwards")
     ap.add_argument("--out", default="edos_best.pt")
+    ap.add_argument("--no-validate", action="store_true",
+                    help="skip batch validation (validate.enable: every crystal and every first-seen batch is checked for out-of-range "
+                         "indices, cross-crystal edges, bad crystal-system labels and NaN / inf before a kernel reads it)")
     ap.add_argument("--per-crystal-keys", action="store_true",
                     help="train over each crystal's own atoms (and its phantom node) - what the batch-size-1 evaluation computes")
     return ap.parse_args(argv)
 
 
 def main(argv=None):
+    """_main() with batch validation on (--no-validate: off); the process-wide switch gets its earlier setting back on the way out,
+    so a caller that imports this module and runs main() is left as it was."""
+    state = validate.ENABLED, validate.FINITE
+    try:
+        return _main(argv)
+    finally:
+        validate.enable(*state)
+
+
+def _main(argv=None):
     args = parse_args(argv)
     dev = torch.device(f"cuda:{args.device}")
     torch.cuda.set_device(dev)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)                                    # `main_eDOS.py:20-23`
+    validate.enable(not args.no_validate, finite=True)
 
     if args.structures:
         # structures -> graphs on the GPU; the element table stands in for the matscholar embedding (`mat2graph.py:33-47`)
@@ -138,6 +152,7 @@ def main(argv=None):
             continue
         # `main_eDOS.py:132-152`: validate; a new best in RMSE or MAE re-evaluates the test split (and, here, saves)
         v_rmse, v_mse, v_mae, v_r2, _ = run_test("valid")
+        trainer.check()                                            # once per evaluation: a stalled exchange voids the epoch
         print(f"[ {epoch + 1} epochs ]valid_rmse:{v_rmse:.4f}|valid_mse:{v_mse:.4f}|valid_mae:{v_mae:.4f}|valid_r2:{v_r2:.4f}")
         improved = v_rmse < best_rmse or v_mae < best_mae
         if v_rmse < best_rmse:

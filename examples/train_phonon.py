@@ -44,7 +44,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dostransformer_amd import checkpoint, evaluate, featurize, synth  # noqa: E402
+from dostransformer_amd import checkpoint, evaluate, featurize, ops, synth, validate  # noqa: E402
 from dostransformer_amd.embedder_phDOS.DOSTransformer_phonon import DOSTransformer_phonon  # noqa: E402
 from dostransformer_amd.loader import DeviceDataset  # noqa: E402
 from dostransformer_amd.predict import Predictor  # noqa: E402
@@ -52,6 +52,16 @@ from dostransformer_amd.train import Trainer  # noqa: E402
 
 
 def main(argv=None):
+    """_main() with batch validation on (--no-validate: off); the process-wide switch gets its earlier setting back on the way out,
+    so a caller that imports this module and runs main() is left as it was."""
+    state = validate.ENABLED, validate.FINITE
+    try:
+        return _main(argv)
+    finally:
+        validate.enable(*state)
+
+
+def _main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=3)          # utils.py:29-42 defaults
     ap.add_argument("--transformer", type=int, default=2)
@@ -66,6 +76,9 @@ def main(argv=None):
     ap.add_argument("--pickle", default=None)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="phonon_best.pt")
+    ap.add_argument("--no-validate", action="store_true",
+                    help="skip batch validation (validate.enable: every crystal and every first-seen batch is checked for out-of-range "
+                         "indices, cross-crystal edges, bad crystal-system labels and NaN / inf before a kernel reads it)")
     ap.add_argument("--float64", action="store_true", help="the reference's float64 training with per-crystal keys")
     ap.add_argument("--fused", action="store_true", help="with --float64: train64.Trainer64 instead of autograd + torch.optim.AdamW")
     ap.add_argument("--replay", action="store_true", help="with --float64 --fused: replay recorded launch lists, one per shape bucket (step_dataset + Predictor64)")
@@ -86,6 +99,7 @@ def main(argv=None):
         ap.error("--replay belongs to --float64 --fused (the fp32 run always replays)")
     dev = torch.device("cuda:0")
     torch.manual_seed(args.seed)
+    validate.enable(not args.no_validate, finite=True)
 
     entries = pickle.load(open(args.pickle, "rb")) if args.pickle else synth.phonon_structures(args.crystals, args.seed)
     t0 = time.perf_counter()
@@ -125,6 +139,7 @@ def main(argv=None):
         dt = time.perf_counter() - t0
         history.append(loss)
         rmse, mse, mae, r2v = run_test("valid")
+        trainer.check()                                           # once per evaluation: a stalled exchange voids the epoch
         print(f"[epoch {epoch + 1}/{args.epochs}] loss {loss:.4f} | {seen / dt:8.0f} crystals/s | "
               f"valid rmse {rmse:.4f} mse {mse:.4f} mae {mae:.4f} r2 {r2v:.4f}")
         if rmse < best:
@@ -189,6 +204,7 @@ def train_float64(args, ds, dev):
         dt = time.perf_counter() - t0
         history.append(loss)
         rmse, mse, mae, r2v = evaluate.test_phonon(model, ds["valid"].batches(args.batch_size))
+        ops.check_exchanges(dev)                                    # (no trainer object here: the same check, once per evaluation)
         print(f"[epoch {epoch + 1}/{args.epochs}] loss per crystal {loss:.4f} | {seen / dt:8.0f} crystals/s | "
               f"valid rmse {rmse:.4f} mse {mse:.4f} mae {mae:.4f} r2 {r2v:.4f}")
         if rmse < best:
@@ -233,6 +249,7 @@ def train_float64_fused(args, ds, dev):
         dt = time.perf_counter() - t0
         history.append(loss)
         rmse, mse, mae, r2v = run_test("valid")
+        trainer.check()
         print(f"[epoch {epoch + 1}/{args.epochs}] loss {loss:.4f} | {seen / dt:8.0f} crystals/s | "
               f"valid rmse {rmse:.4f} mse {mse:.4f} mae {mae:.4f} r2 {r2v:.4f}"
               + (f" | slots {trainer.slot_misses} recorded, {trainer.slot_hits} replayed ({trainer.slot_promoted} promoted)"

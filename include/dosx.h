@@ -807,6 +807,20 @@ typedef struct DosxMlpLnBwd {
 int dosx_mlp_ln_bwd_partial_rows(int M);
 int dosx_mlp_ln_bwd(const DosxMlpLnBwd* a, dosx_stream_t stream);
 
+/* STALL REPORT of the column-split exchanges above.  Their poll for the siblings' tickets is bounded; a poll that ends on its
+ * bound instead of on the target used to fall through in silence.  Now thread 0 of that workgroup reports into a sticky device
+ * status {code, kernel id, tile, stalls}: code = DOSX_EXCHANGE_STALLED from the first report on, kernel id / tile those of the FIRST
+ * report, stalls the number of reports.  Outputs are NOT poisoned: between a stall and the host's next look at the status every
+ * number the device produces is untrustworthy, and the stalled launch leaves tickets on its counters.
+ *   dosx_exchange_status: a one-thread kernel copies the four words to out4 (caller-owned device memory) and, with clear != 0,
+ *     zeroes the status behind the copy.  Stream-ordered, no sync.
+ *   dosx_exchange_selftest: TEST ONLY - a one-thread kernel that files one report for (kernel_id, tile) and does nothing else.  It
+ *     is how the report path is exercised: no test or tool may make a real exchange stall. */
+enum { DOSX_EXCHANGE_OK = 0, DOSX_EXCHANGE_STALLED = 1 };
+enum { DOSX_EXCHANGE_KERNEL_MLP_LN_CS_FWD = 1, DOSX_EXCHANGE_KERNEL_ENC_CS_FWD = 2, DOSX_EXCHANGE_KERNEL_MLP_LN_CS_BWD = 3 };
+int dosx_exchange_status(int32_t* out4, int clear, dosx_stream_t stream);
+int dosx_exchange_selftest(int kernel_id, int tile, dosx_stream_t stream);
+
 /* The EdgeModel of one message-passing layer + the aggregation behind it in ONE launch (round 5; SURVEY.md §7 step 4;
  * DOSTransformer_phonon.py:186-197,209 and the edge residual :84), first Linear FACTORED (see DosxGemm.add_p):
  *     z    = e . Wc^T + b1 + pq[src[r], 0:2H] + pq[dst[r], 2H:4H]          Wc = first Linear's weight block [2H, H], row stride ldw1
@@ -888,6 +902,43 @@ int dosx_csr_build(const long long* edge_index, const long long* batch, int N, i
                    long long* edge_perm, int32_t* rowptr_dst, int32_t* perm_src, int32_t* rowptr_src,
                    int32_t* graph_ptr, int32_t* node_graph, int32_t* dense_row, float* inv_deg, int32_t* n_max,
                    void* workspace, size_t ws_bytes, dosx_stream_t stream);
+
+/* BATCH VALIDATION (csrc/validate.hip; dostransformer_amd/validate.py) - the fail-loudly path in front of dosx_csr_build and of
+ * every kernel that dereferences a batch: the caller's OWN arrays in the reference schema are checked before any metadata is
+ * derived from them.  Lengths come from the caller's tensor shapes alone, every value is classified from the value itself, and
+ * batch[src] is read only after src passed its range test, so the checker reads nothing outside the arrays whatever they hold.
+ *   R1  an edge endpoint outside [0, N)                                             offender: edge
+ *   R2  both endpoints in range, batch[src] != batch[dst] (an edge between crystals) offender: edge
+ *   R3  batch[i] outside [0, B), or batch[i] < batch[i-1], or batch[0] != 0          offender: node
+ *   R4  a crystal of [0, B) that owns no node                                        offender: crystal
+ *   R5  system[b] outside [0, prompts)  (system != NULL)                             offender: crystal
+ *   R6  n_max > 0 and a crystal owns more than n_max nodes                           offender: crystal
+ *   R7  require_sorted != 0 and dst[e] < dst[e-1]                                    offender: edge
+ * (R4 / R6 count the nodes whose batch value is the crystal's, wherever they stand.)
+ * report: DOSX_CHECK_RULES pairs {count, first}, rule r at report[2(r-1)], caller-owned device memory that the caller
+ * initialises to {0, INT32_MAX}; count = violations of the rule (saturating at INT32_MAX), first = the smallest offending index.
+ * A sum and a minimum: the pair does not depend on the order of the (vector) atomics that form it.
+ * crystal_count: B int32 words of caller-owned device scratch (zeroed here, stream-ordered).  No sync, no allocation.
+ * The grid: DOSX_CHECK_THREADS threads, at most DOSX_CHECK_MAX_BLOCKS workgroups that stride over edges and nodes. */
+#define DOSX_CHECK_RULES 7
+#define DOSX_CHECK_THREADS 256
+#define DOSX_CHECK_MAX_BLOCKS 1024
+typedef struct DosxBatchCheck {
+  const long long* edge_index;     /* [2,E] int64: sources, then destinations */
+  const long long* batch;          /* [N] int64 */
+  const long long* system;         /* [B] int64, may be NULL (no R5) */
+  int32_t N, E, B;
+  int32_t n_max;                   /* 0: not given (no R6) */
+  int32_t prompts;                 /* rows of the prompt table: 7 for both models */
+  int32_t require_sorted;          /* != 0: R7 */
+  int32_t* crystal_count;          /* [B] scratch */
+} DosxBatchCheck;
+int dosx_batch_check(const DosxBatchCheck* d, int32_t* report, dosx_stream_t stream);
+/* Non-finite elements (NaN, +-inf) of one contiguous tensor of n elements: report_slot = one {count, first} pair with the
+ * conventions above (an index past INT32_MAX - 1 is reported as INT32_MAX - 1).  16-byte loads with scalar head / tail;
+ * memory-bound: meant for a whole resident dataset table as much as for a batch. */
+int dosx_finite_check_f32(const float* p, int64_t n, int32_t* report_slot, dosx_stream_t stream);
+int dosx_finite_check_f64(const double* p, int64_t n, int32_t* report_slot, dosx_stream_t stream);
 
 /* Collate on the device: the dataset is resident with per-crystal destination-sorted edges and cached
  * local CSR (`*_all` arrays, crystal c owns nodes [node_ptr_all[c], node_ptr_all[c+1]) and edges likewise; its cached
