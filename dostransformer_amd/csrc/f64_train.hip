@@ -91,6 +91,36 @@ __global__ __launch_bounds__(ADAMW64_THREADS) void adamw_f64_kernel(double* __re
   }
 }
 
+// adamw_f64_kernel behind a gradient guard (include/dosx.h: DosxStepGuard): adamw64_one on g * clip (clip = 1.0: g itself, bit
+// for bit), the verdict of dosx_grad_guard_f64 read from device memory by every thread (plain uniform loads of a record no one
+// writes during this launch); skip != 0 returns before any store.
+__global__ __launch_bounds__(ADAMW64_THREADS) void adamw_guarded_f64_kernel(double* __restrict__ p, const double* __restrict__ g,
+                                                                            double* __restrict__ m, double* __restrict__ v, size_t n,
+                                                                            double decay, double omb1, double b2, double omb2,
+                                                                            double eps, const DosxStepGuard* __restrict__ rec) {
+  if (rec->skip != 0) return;
+  const double clip = rec->clip, step_size = rec->step_size, bc2_sqrt = rec->bc2_scale;
+  const size_t n2 = n >> 1;
+  double2* p2 = reinterpret_cast<double2*>(p);
+  const double2* g2 = reinterpret_cast<const double2*>(g);
+  double2* m2 = reinterpret_cast<double2*>(m);
+  double2* v2 = reinterpret_cast<double2*>(v);
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (size_t i = tid; i < n2; i += (size_t)gridDim.x * blockDim.x) {
+    double2 pp = p2[i], mm = m2[i], vv = v2[i];
+    const double2 gg = g2[i];
+    adamw64_one(pp.x, gg.x * clip, mm.x, vv.x, decay, omb1, b2, omb2, eps, step_size, bc2_sqrt);
+    adamw64_one(pp.y, gg.y * clip, mm.y, vv.y, decay, omb1, b2, omb2, eps, step_size, bc2_sqrt);
+    p2[i] = pp; m2[i] = mm; v2[i] = vv;
+  }
+  if (tid == 0 && (n & 1)) {
+    const size_t i = n - 1;
+    double pj = p[i], mj = m[i], vj = v[i];
+    adamw64_one(pj, g[i] * clip, mj, vj, decay, omb1, b2, omb2, eps, step_size, bc2_sqrt);
+    p[i] = pj; m[i] = mj; v[i] = vj;
+  }
+}
+
 }  // namespace
 
 extern "C" int dosx_loss_phonon_f64(const double* pg, const double* ps, const double* y, double beta, double* dpg, double* dps,
@@ -118,6 +148,23 @@ extern "C" int dosx_adamw_f64(double* p, const double* g, double* m, double* v, 
   if (wgs < 1) wgs = 1;
   hipLaunchKernelGGL(adamw_f64_kernel, dim3((unsigned)wgs), dim3(ADAMW64_THREADS), 0, to_stream(stream), p, g, m, v, (size_t)n,
                      1.0 - lr * weight_decay, 1.0 - beta1, beta2, 1.0 - beta2, eps, lr / bc1, sqrt(bc2));
+  DOSX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int dosx_adamw_guarded_f64(double* p, const double* g, double* m, double* v, int64_t n, double lr, double beta1,
+                                      double beta2, double eps, double weight_decay, const void* guard, dosx_stream_t stream) {
+  DOSX_CHECK_ARG(p && g && m && v && guard, "dosx_adamw_guarded_f64: NULL buffer or record");
+  DOSX_CHECK_ARG(n >= 0, "dosx_adamw_guarded_f64: n must not be negative, got %lld", (long long)n);
+  DOSX_CHECK_ARG(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                   reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(guard)) & 15) == 0,
+                 "dosx_adamw_guarded_f64: buffers must be 16-byte aligned");
+  if (n == 0) return 0;
+  size_t wgs = ((size_t)n / 2 + ADAMW64_THREADS - 1) / ADAMW64_THREADS;      // dosx_adamw_f64's grid
+  if (wgs > (size_t)ADAMW64_MAX_WGS) wgs = ADAMW64_MAX_WGS;
+  if (wgs < 1) wgs = 1;
+  hipLaunchKernelGGL(adamw_guarded_f64_kernel, dim3((unsigned)wgs), dim3(ADAMW64_THREADS), 0, to_stream(stream), p, g, m, v,
+                     (size_t)n, 1.0 - lr * weight_decay, 1.0 - beta1, beta2, 1.0 - beta2, eps, static_cast<const DosxStepGuard*>(guard));
   DOSX_LAUNCH_CHECK();
   return 0;
 }

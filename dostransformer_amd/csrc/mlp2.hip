@@ -1186,6 +1186,19 @@ extern "C" int dosx_exchange_status(int32_t* out4, int clear, dosx_stream_t stre
   return 0;
 }
 
+// the device address of the status words, for a kernel of another file that reads them (step_guard.hip: a stalled step is skipped)
+extern "C" int dosx_exchange_status_address(unsigned long long* address_out) {
+  DOSX_CHECK_ARG(address_out != nullptr, "dosx_exchange_status_address: null output (one host word)");
+  void* p = nullptr;
+  const hipError_t e = hipGetSymbolAddress(&p, HIP_SYMBOL(g_cs_status));
+  if (e != hipSuccess || p == nullptr) {
+    dosx_set_error("dosx_exchange_status_address: hipGetSymbolAddress failed: %s", hipGetErrorString(e));
+    return -5;
+  }
+  *address_out = (unsigned long long)reinterpret_cast<uintptr_t>(p);
+  return 0;
+}
+
 // TEST ONLY: files one report through cs_report_stall - the path a stalled exchange takes - without any exchange stalling
 extern "C" int dosx_exchange_selftest(int kernel_id, int tile, dosx_stream_t stream) {
   DOSX_CHECK_ARG(kernel_id >= DOSX_EXCHANGE_KERNEL_MLP_LN_CS_FWD && kernel_id <= DOSX_EXCHANGE_KERNEL_MLP_LN_CS_BWD && tile >= 0,

@@ -564,6 +564,46 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
   }
 }
 
+// adamw_kernel behind a gradient guard (include/dosx.h: DosxStepGuard): the same element expressions, with the verdict of
+// dosx_grad_guard_f32 read from device memory by every thread (plain uniform loads of a record no one writes during this launch) -
+// skip != 0 returns before any store, clip stands where grad_scale stood, the two bias-correction scalars are the record's.
+__global__ void adamw_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                     float* __restrict__ v, size_t n, float decay, float beta1, float beta2, float eps,
+                                     const DosxStepGuard* __restrict__ rec) {
+  if (rec->skip != 0) return;
+  const float gscale = (float)rec->clip;
+  const float step_size = (float)rec->step_size;
+  const float inv_bc2s = (float)rec->bc2_scale;
+  const size_t n4 = n >> 2;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    float4 pp = ld4(p + 4 * i), gg = ld4(g + 4 * i), mm = ld4(m + 4 * i), vv = ld4(v + 4 * i);
+    float* P = &pp.x; float* G = &gg.x; float* Mm = &mm.x; float* V = &vv.x;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float gr = G[j] * gscale;
+      float pj = P[j] * decay;
+      const float mj = Mm[j] + (gr - Mm[j]) * (1.f - beta1);
+      const float vj = V[j] * beta2 + (1.f - beta2) * gr * gr;
+      const float denom = sqrtf(vj) * inv_bc2s + eps;
+      pj -= step_size * (mj / denom);
+      P[j] = pj; Mm[j] = mj; V[j] = vj;
+    }
+    st4(p + 4 * i, pp); st4(m + 4 * i, mm); st4(v + 4 * i, vv);
+  }
+  // tail (n not a multiple of 4)
+  const size_t t0 = n4 << 2;
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (tid < n - t0) {
+    const size_t i = t0 + tid;
+    const float gr = g[i] * gscale;
+    float pj = p[i] * decay;
+    const float mj = m[i] + (gr - m[i]) * (1.f - beta1);
+    const float vj = v[i] * beta2 + (1.f - beta2) * gr * gr;
+    pj -= step_size * (mj / (sqrtf(vj) * inv_bc2s + eps));
+    p[i] = pj; m[i] = mj; v[i] = vj;
+  }
+}
+
 // Philox4x32-10 (Salmon et al., SC'11): counter-based, so element i's draw depends only on (seed, stream_id, i)
 __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
 #pragma unroll
@@ -807,6 +847,24 @@ extern "C" int dosx_adamw(float* p, const float* g, float* m, float* v, int64_t 
   if (g1 < 1) g1 = 1;
   hipLaunchKernelGGL(adamw_kernel, dim3((int)g1), dim3(256), 0, to_stream(stream), p, g, m, v, (size_t)n, decay, beta1,
                      beta2, eps, step_size, inv_bc2s, grad_scale);
+  DOSX_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int dosx_adamw_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                                  float eps, float weight_decay, const void* guard, dosx_stream_t stream) {
+  DOSX_CHECK_ARG(p && g && m && v && guard, "dosx_adamw_guarded: NULL buffer or record");
+  DOSX_CHECK_ARG(n >= 0, "dosx_adamw_guarded: n must not be negative, got %lld", (long long)n);
+  DOSX_CHECK_ARG(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                   reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(guard)) & 15) == 0,
+                 "dosx_adamw_guarded: buffers must be 16-byte aligned");
+  if (n == 0) return 0;
+  const float decay = 1.f - lr * weight_decay;
+  size_t g1 = ((size_t)n / 4 + 255) / 256;                 // dosx_adamw's grid
+  if (g1 > 4096) g1 = 4096;
+  if (g1 < 1) g1 = 1;
+  hipLaunchKernelGGL(adamw_guarded_kernel, dim3((int)g1), dim3(256), 0, to_stream(stream), p, g, m, v, (size_t)n, decay, beta1,
+                     beta2, eps, static_cast<const DosxStepGuard*>(guard));
   DOSX_LAUNCH_CHECK();
   return 0;
 }

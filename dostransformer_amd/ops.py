@@ -1653,6 +1653,61 @@ def adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1
           w=lambda: ("adamw", "adamw_kernel", "hbm", 28.0 * n))
 
 
+# ---- guarded optimizer step (csrc/step_guard.hip; include/dosx.h: DosxStepGuard) -----------------------------------------------
+_GUARD_WORDS = C.sizeof(_abi.StepGuard) // 8
+_STATUS_ADDRESS: dict = {}
+
+
+def guard_buffers(device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(record, workspace) of one guarded trainer, both zeroed: the record as 12 float64 words (a DosxStepGuard; word 1 is
+    ``norm``), the workspace of DOSX_GUARD_WORKSPACE_BYTES.  torch's allocations are 16-byte aligned."""
+    rec = torch.zeros(_GUARD_WORDS, dtype=torch.float64, device=device)
+    ws = torch.zeros(_abi.DOSX_GUARD_WORKSPACE_BYTES // 8, dtype=torch.int64, device=device)
+    return rec, ws
+
+
+def guard_read(rec: torch.Tensor) -> "_abi.StepGuard":
+    """The record on the host: one 96-byte read-back (which waits for the current stream)."""
+    return _abi.StepGuard.from_buffer_copy(rec.cpu().numpy().tobytes())
+
+
+def exchange_status_address(device) -> int:
+    """Device address of the exchanges' sticky stall status on ``device`` (dosx_exchange_status_address), asked for once."""
+    dev = torch.device(device)
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    if idx not in _STATUS_ADDRESS:
+        out = C.c_ulonglong(0)
+        with torch.cuda.device(idx):
+            _lib.check(_lib.load().dosx_exchange_status_address(C.byref(out)), "dosx_exchange_status_address")
+        _STATUS_ADDRESS[idx] = int(out.value)
+    return _STATUS_ADDRESS[idx]
+
+
+def grad_guard(g: torch.Tensor, n: int, rec: torch.Tensor, ws: torch.Tensor, max_norm: Optional[float], lr: float, beta1: float,
+               beta2: float, step: int, status_address: Optional[int] = None) -> None:
+    """Statistics of the first n elements of the flat gradient ``g`` (fp32 or float64) into the record: norm, clip coefficient,
+    non-finite count and first index, the skip verdict and the bias-correction scalars of the guarded AdamW behind it.
+    ``max_norm`` None: no clipping; ``status_address``: :func:`exchange_status_address`, a stalled step is then skipped too."""
+    if g.dtype not in (torch.float32, torch.float64) or not g.is_cuda or not g.is_contiguous():
+        raise TypeError(f"grad_guard: a contiguous float32 / float64 CUDA gradient, got {g.dtype} on {g.device}")
+    if not 0 <= n <= g.numel():
+        raise ValueError(f"grad_guard: n = {n} of a gradient with {g.numel()} elements")
+    if rec.dtype != torch.float64 or rec.numel() < _GUARD_WORDS or ws.numel() * ws.element_size() < _abi.DOSX_GUARD_WORKSPACE_BYTES:
+        raise ValueError("grad_guard: record / workspace are not those of guard_buffers")
+    f32 = g.dtype == torch.float32
+    _call("dosx_grad_guard_f32" if f32 else "dosx_grad_guard_f64", g.data_ptr(), int(n), -1.0 if max_norm is None else float(max_norm),
+          status_address, float(lr), float(beta1), float(beta2), int(step), rec.data_ptr(), ws.data_ptr(), _stream(),
+          w=lambda: ("grad_guard", "grad_guard_kernel", "hbm", float(g.element_size()) * n))
+
+
+def adamw_guarded(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, rec):
+    """:func:`adamw` behind :func:`grad_guard`: skip, clip coefficient and bias correction come from the record."""
+    _chk_f32(p, g, m, v)
+    _call("dosx_adamw_guarded", _p(p), _p(g), _p(m), _p(v), int(n), float(lr), float(beta1), float(beta2), float(eps),
+          float(weight_decay), rec.data_ptr(), _stream(),
+          w=lambda: ("adamw_guarded", "adamw_guarded_kernel", "hbm", 28.0 * n))
+
+
 def dropout_mask(mask: torch.Tensor, p: float, seed_dev: torch.Tensor, stream_id: int) -> None:
     """mask <- {0, 1/(1-p)} multipliers (include/dosx.h: dosx_dropout_mask); seed_dev: 1-element int64 device tensor."""
     assert mask.dtype == torch.float32 and mask.is_contiguous() and seed_dev.dtype == torch.int64 and seed_dev.is_cuda
@@ -2084,6 +2139,17 @@ def adamw64(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, 
         raise ValueError(f"adamw64: n = {n} of buffers with {p.numel()}, {g.numel()}, {m.numel()}, {v.numel()} elements")
     _call("dosx_adamw_f64", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), int(n), float(lr), float(beta1), float(beta2),
           float(eps), float(weight_decay), int(step), _stream())
+
+
+def adamw64_guarded(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, n: int, lr: float, beta1: float,
+                    beta2: float, eps: float, weight_decay: float, rec: torch.Tensor) -> None:
+    """:func:`adamw64` behind :func:`grad_guard`: skip, clip coefficient and bias correction come from the record."""
+    _chk_c64(p, g, m, v)
+    if min(p.numel(), g.numel(), m.numel(), v.numel()) < n:
+        raise ValueError(f"adamw64_guarded: n = {n} of buffers with {p.numel()}, {g.numel()}, {m.numel()}, {v.numel()} elements")
+    _call("dosx_adamw_guarded_f64", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), int(n), float(lr), float(beta1),
+          float(beta2), float(eps), float(weight_decay), rec.data_ptr(), _stream(),
+          w=lambda: ("adamw_guarded_f64", "adamw_guarded_f64_kernel", "hbm", 56.0 * n))
 
 
 # float64 pair head of Graphnetwork_phonon (csrc/pair_head_f64.hip), used by functional64's factored program

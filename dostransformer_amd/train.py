@@ -27,6 +27,7 @@ from . import ops
 from ._lib import DosxError, from_environ
 from ._models import DOSTransformerBase, GraphnetworkBase, _SEED_MOD, rank_seed_offset
 from .batch import CrystalBatch, bucket_sizes, graph_meta, pad_batch
+from .guard import StepGuard
 from .slots import Slot, SlotCache
 
 # Data parallel: a THIRD gradient bucket (GN_decoder + message-passing layers L-1 .. 1: 1.9 of the GNN trunk's 3.0 MB at the
@@ -40,9 +41,10 @@ _DP_MID_BUCKET = from_environ("DOSX_DP_MID_BUCKET", "0") == "1"
 _DP_CHECK = from_environ("DOSX_DP_CHECK", "0") == "1"
 
 
-class _AdamWState:
+class _AdamWState(StepGuard):
     """What Trainer and train64.Trainer64 share: the AdamW moments laid out like the model's flat parameters (in the flat
-    buffer's dtype), their checkpoint in ``torch.optim.AdamW`` vocabulary and the per-step bump of the dropout seed.  Expects
+    buffer's dtype), their checkpoint in ``torch.optim.AdamW`` vocabulary, the per-step bump of the dropout seed and the
+    gradient guard of the optimizer step (``guard.StepGuard``: ``max_grad_norm`` / ``skip_nonfinite``).  Expects
     ``model``, ``_fp``, ``_m``, ``_v``, ``_slots``, ``step_count`` and the hyper-parameters ``lr``, ``betas``, ``eps``, ``wd``, ``beta``."""
 
     def _state(self, fp):
@@ -80,7 +82,7 @@ class _AdamWState:
         # the dropout seed is stored WITHOUT the saving rank's offset (rank-independent base + steps taken): every rank of a
         # resumed data-parallel job re-applies its own offset and goes on drawing the masks its uninterrupted self would have
         seed = getattr(self.model, "_drop_seed", None)
-        return {"step": self.step_count, "exp_avg": views(m), "exp_avg_sq": views(v),
+        return {"step": self._applied_steps(), "exp_avg": views(m), "exp_avg_sq": views(v),
                 "drop_seed_base": None if seed is None else (int(seed.item()) - rank_seed_offset()) % _SEED_MOD,
                 "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "beta": self.beta}}
 
@@ -96,6 +98,7 @@ class _AdamWState:
                 m[o:o + k].copy_(sd["exp_avg"][n].reshape(-1).to(m.device, m.dtype))
                 v[o:o + k].copy_(sd["exp_avg_sq"][n].reshape(-1).to(v.device, v.dtype))
         self.step_count = int(sd["step"])
+        self._guard_reset()                # (the applied count starts here: nothing skipped since)
         val = None
         if sd.get("drop_seed_base") is not None:     # resume draws the masks THIS rank's uninterrupted run would have drawn
             val = (int(sd["drop_seed_base"]) + rank_seed_offset()) % _SEED_MOD
@@ -110,10 +113,23 @@ class _AdamWState:
     def check(self) -> None:
         """Raise :class:`DosxError` if a column-split exchange of any step since the last clean check reported a stall
         (``ops.check_exchanges``): one small read-back, so call it where the host waits for the device anyway - per evaluation,
-        before a checkpoint - not per step.  A module that is not on the GPU has launched nothing: nothing to check."""
+        before a checkpoint - not per step.  A module that is not on the GPU has launched nothing: nothing to check.
+
+        A guarded trainer (``max_grad_norm`` / ``skip_nonfinite``) also raises when steps were skipped since the last check,
+        naming the first one and the parameter whose gradient was not finite; by then ``step_count`` is the applied count, the
+        guard's counts are zeroed and the slots dropped, so the process can go on."""
         dev = self.model._module_device()
-        if dev.type == "cuda":
+        if dev.type != "cuda":
+            return
+        skipped = self._guard_settle()
+        try:
             ops.check_exchanges(dev)
+        except DosxError as e:
+            if skipped is None:
+                raise
+            raise DosxError(f"{e}  {skipped}") from None
+        if skipped is not None:
+            raise DosxError(skipped)
 
     def _bump_dropout_seed(self) -> None:
         """Attention dropout draws its masks from a device-resident seed inside the (possibly recorded) program; one bump
@@ -151,11 +167,19 @@ class Trainer(_AdamWState, SlotCache):
     With one output there is no ``beta`` to weigh (anything but 1.0 is refused), no attention to give per-crystal keys, and no
     data parallelism yet; ``n_global`` must be the batch's own count.  Which node encoder is dead follows the input width and is
     fixed by the first batch: a later batch of the other width is refused.
+
+    ``max_grad_norm=X`` / ``skip_nonfinite=True`` put the optimizer step behind a gradient guard (``guard.StepGuard``): what
+    ``torch.nn.utils.clip_grad_norm_(params, X)`` between ``backward()`` and ``optimizer.step()`` and a GradScaler-style "skip
+    if non-finite" do, decided on the device - one statistics launch over the flat gradient and an AdamW that reads the
+    verdict, no host read.  A step whose gradient holds a NaN / inf (or that follows a reported exchange stall) leaves
+    parameters and moments untouched and does not advance AdamW's time; ``grad_norm`` / ``guard_report()`` say what happened,
+    ``check()`` raises.  Every mode; not under data parallelism.  Off by default: the step then issues exactly the launches it issued without these arguments.
     """
 
     def __init__(self, model: DOSTransformerBase, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2,
                  betas=(0.9, 0.999), eps: float = 1e-8, dist=None, graph: bool = False, replay: bool = False,
-                 bucket=(8, 128), max_slots: int = 32, promote: float = 0.0, per_crystal_keys: bool = False):
+                 bucket=(8, 128), max_slots: int = 32, promote: float = 0.0, per_crystal_keys: bool = False,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         if not isinstance(model, (DOSTransformerBase, GraphnetworkBase)):
             raise TypeError("Trainer drives DOSTransformer / DOSTransformer_phonon / Graphnetwork / Graphnetwork_phonon / mlp modules")
         model._require_fp32_program("Trainer")
@@ -174,6 +198,7 @@ class Trainer(_AdamWState, SlotCache):
         if per_crystal_keys and dist is not None:
             raise DosxError("Trainer(per_crystal_keys=True) is a single-GPU mode: not with dist (data parallelism)")
         self._per_crystal_keys = bool(per_crystal_keys)
+        self._init_guard("Trainer", max_grad_norm, skip_nonfinite, dist)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, betas, eps
         self.dist = dist
         self.graph = graph
@@ -546,6 +571,8 @@ class Trainer(_AdamWState, SlotCache):
     def optimizer_step(self) -> None:
         fp = self._fp if self._fp is not None else self.model.flat_params()
         m, v = self._state(fp)
+        if self.guarded:                              # (never with dist: refused at construction)
+            return self._guarded_optimizer_step(fp, m, v)
         if self.dist is not None:
             if self._early_work is not None:          # early (+ mid) bucket already in flight: only the last bucket is exposed
                 if self._mid_work is not None:

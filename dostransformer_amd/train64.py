@@ -52,13 +52,17 @@ class Trainer64(_AdamWState, SlotCache):
     as it is) and slots are keyed by the padded shape; without ``replay`` a padded batch is run as it is and nothing is padded.
     ``promote``: the largest relative excess of node / edge rows at which ``step_dataset`` runs a bucket it sees for the first
     time in a live larger one instead of recording it (``slot_promoted`` counts those steps; 0: never).
+    ``max_grad_norm`` / ``skip_nonfinite``: the optimizer step behind the gradient guard (``guard.StepGuard``), as on
+    ``train.Trainer``: clipping and "skip if non-finite" decided on the device, ``grad_norm`` / ``guard_report()`` / ``check()``.
     """
 
     _who = "Trainer64"            # what this driver calls itself in its refusals
 
     def __init__(self, model, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2, betas=(0.9, 0.999),
-                 eps: float = 1e-8, replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0):
+                 eps: float = 1e-8, replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
         self._require_model(model)
+        self._init_guard(self._who, max_grad_norm, skip_nonfinite)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, tuple(betas), eps
         self.replay = bool(replay)
         self.max_slots = int(max_slots)
@@ -209,6 +213,8 @@ class Trainer64(_AdamWState, SlotCache):
         """The flat AdamW launch, issued behind the (recorded) program: ``step`` changes every step."""
         fp = self._fp if self._fp is not None else self.model.flat_params()
         m, v = self._state(fp)
+        if self.guarded:
+            return self._guarded_optimizer_step(fp, m, v)
         self.step_count += 1
         ops.adamw64(fp.flat, fp.grad, m, v, fp.total, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count)
 
@@ -236,14 +242,16 @@ class GraphnetworkTrainer64(Trainer64):
     _who = "GraphnetworkTrainer64"
 
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
-                 replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0, **unknown):
+                 replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, **unknown):
         if "beta" in unknown:
             raise ValueError(f"GraphnetworkTrainer64: beta={unknown['beta']} - the model has ONE output and its loss no second "
                              f"term to weigh")
         if unknown:
             raise TypeError(f"GraphnetworkTrainer64() got an unexpected keyword argument {sorted(unknown)[0]!r}")
         super().__init__(model, lr=lr, beta=1.0, weight_decay=weight_decay, betas=betas, eps=eps, replay=replay,
-                         max_slots=max_slots, bucket=bucket, promote=promote)
+                         max_slots=max_slots, bucket=bucket, promote=promote, max_grad_norm=max_grad_norm,
+                         skip_nonfinite=skip_nonfinite)
         self._dead = None                 # the dead-parameter set of the first batch's node-feature width
 
     def _require_model(self, model) -> None:

@@ -29,6 +29,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from dostransformer_amd import checkpoint, evaluate, featurize, synth, validate  # noqa: E402
+from dostransformer_amd._lib import DosxError  # noqa: E402
 from dostransformer_amd.embedder_eDOS.DOSTransformer import DOSTransformer  # noqa: E402
 from dostransformer_amd.loader import DeviceDataset  # noqa: E402
 from dostransformer_amd.predict import Predictor  # noqa: E402
@@ -66,6 +67,11 @@ def parse_args(argv=None):
                          "indices, cross-crystal edges, bad crystal-system labels and NaN / inf before a kernel reads it)")
     ap.add_argument("--per-crystal-keys", action="store_true",
                     help="train over each crystal's own atoms (and its phantom node) - what the batch-size-1 evaluation computes")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                    help="clip the gradient norm to X on the device (what clip_grad_norm_ does in a torch loop); steps with a "
+                         "non-finite gradient are skipped")
+    ap.add_argument("--skip-nonfinite", action="store_true",
+                    help="skip a step whose gradient holds a NaN / inf instead of writing it into the parameters")
     return ap.parse_args(argv)
 
 
@@ -121,7 +127,8 @@ def _main(argv=None):
     # exact); every batch pads its keys to the training set's largest crystal so that n_max is not a bucket dimension
     bucket = (32, 512)
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=bucket, promote=0.08,
-                      per_crystal_keys=args.per_crystal_keys)      # AdamW(lr, weight_decay=1e-2), `:91`
+                      per_crystal_keys=args.per_crystal_keys,      # AdamW(lr, weight_decay=1e-2), `:91`
+                      max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
     predictor = Predictor(model, bucket=bucket, per_crystal_keys=args.eval_per_crystal > 0 and not baseline)
     criterion_2 = torch.nn.L1Loss()                                                       # `main_eDOS.py:93`
 
@@ -152,7 +159,12 @@ def _main(argv=None):
             continue
         # `main_eDOS.py:132-152`: validate; a new best in RMSE or MAE re-evaluates the test split (and, here, saves)
         v_rmse, v_mse, v_mae, v_r2, _ = run_test("valid")
-        trainer.check()                                            # once per evaluation: a stalled exchange voids the epoch
+        try:
+            trainer.check()                                        # once per evaluation: a stalled exchange voids the epoch
+        except DosxError as e:                                     # behind the gradient guard skipped steps changed nothing:
+            if not trainer.guarded:                                # report them and go on
+                raise
+            print(f"warning: {e}")
         print(f"[ {epoch + 1} epochs ]valid_rmse:{v_rmse:.4f}|valid_mse:{v_mse:.4f}|valid_mae:{v_mae:.4f}|valid_r2:{v_r2:.4f}")
         improved = v_rmse < best_rmse or v_mae < best_mae
         if v_rmse < best_rmse:

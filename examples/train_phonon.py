@@ -87,7 +87,14 @@ def _main(argv=None):
     ap.add_argument("--eval-per-crystal", type=int, default=0, metavar="N",
                     help="N > 0: validate and test with the reference's batch-size-1 metrics, from batched passes of N crystals "
                          "(evaluate.test_per_crystal; fp32 run, or --float64 --fused --replay)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X",
+                    help="fused trainers: clip the gradient norm to X on the device (what clip_grad_norm_ does in a torch loop); "
+                         "steps with a non-finite gradient are skipped")
+    ap.add_argument("--skip-nonfinite", action="store_true",
+                    help="fused trainers: skip a step whose gradient holds a NaN / inf instead of writing it into the parameters")
     args = ap.parse_args(argv)
+    if (args.clip_grad_norm is not None or args.skip_nonfinite) and args.float64 and not args.fused:
+        ap.error("--clip-grad-norm / --skip-nonfinite belong to the fused trainers: the fp32 run, or --float64 --fused")
     if args.eval_per_crystal > 0 and args.float64 and not args.replay:
         ap.error("--eval-per-crystal needs a replayed predictor: the fp32 run, or --float64 --fused --replay")
     if args.fused and not args.float64:
@@ -125,7 +132,7 @@ def _main(argv=None):
     # coarse shape buckets: reshuffled batches then fall into a few dozen (N, E, n_max) buckets that are all recorded
     # within the first epoch (ghost padding is exact; it costs a few per cent of extra rows)
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=(32, 1024), promote=0.08,
-                      per_crystal_keys=args.per_crystal_keys)
+                      per_crystal_keys=args.per_crystal_keys, **_guard_args(args))
     predictor = Predictor(model, bucket=(32, 1024), per_crystal_keys=args.eval_per_crystal > 0 and not baseline)
     run_test = _tester(args, predictor, ds)
     best, history = float("inf"), []
@@ -139,7 +146,7 @@ def _main(argv=None):
         dt = time.perf_counter() - t0
         history.append(loss)
         rmse, mse, mae, r2v = run_test("valid")
-        trainer.check()                                           # once per evaluation: a stalled exchange voids the epoch
+        _check(trainer)                                           # once per evaluation: a stalled exchange voids the epoch
         print(f"[epoch {epoch + 1}/{args.epochs}] loss {loss:.4f} | {seen / dt:8.0f} crystals/s | "
               f"valid rmse {rmse:.4f} mse {mse:.4f} mae {mae:.4f} r2 {r2v:.4f}")
         if rmse < best:
@@ -215,6 +222,22 @@ def train_float64(args, ds, dev):
     return {"best_valid_rmse": best, "train_loss": history}
 
 
+def _guard_args(args):
+    return dict(max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
+
+
+def _check(trainer):
+    """trainer.check(); behind the gradient guard skipped steps left parameters and moments untouched, so the run reports them and
+    goes on - without it a reported stall ends the run, as before."""
+    from dostransformer_amd._lib import DosxError
+    try:
+        trainer.check()
+    except DosxError as e:
+        if not trainer.guarded:
+            raise
+        print(f"            warning: {e}")
+
+
 def train_float64_fused(args, ds, dev):
     """float64 training through train64.Trainer64: forward program, loss kernel, backward program, flat AdamW - the loss stays
     on the device, one host read per epoch.  --replay: shape buckets as in the fp32 run, every shuffled selection collated on
@@ -227,11 +250,11 @@ def train_float64_fused(args, ds, dev):
     slots = dict(replay=args.replay, bucket=bucket if args.replay else None, promote=0.08 if args.replay else 0.0)
     if args.embedder == "graphnetwork":
         model = _baseline64(args, dev)
-        trainer = GraphnetworkTrainer64(model, lr=args.lr, **slots)
+        trainer = GraphnetworkTrainer64(model, lr=args.lr, **slots, **_guard_args(args))
     else:
         model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).double()
         model = model.set_program_dtype(torch.float64).set_per_crystal_keys(True).to(dev)
-        trainer = Trainer64(model, lr=args.lr, beta=args.beta, **slots)
+        trainer = Trainer64(model, lr=args.lr, beta=args.beta, **slots, **_guard_args(args))
     evaluator = Predictor64(model, bucket=bucket) if args.replay else model       # (the module's per-crystal keys are on)
     run_test = _tester(args, evaluator, ds)
     train = ds["train"]
@@ -249,7 +272,7 @@ def train_float64_fused(args, ds, dev):
         dt = time.perf_counter() - t0
         history.append(loss)
         rmse, mse, mae, r2v = run_test("valid")
-        trainer.check()
+        _check(trainer)
         print(f"[epoch {epoch + 1}/{args.epochs}] loss {loss:.4f} | {seen / dt:8.0f} crystals/s | "
               f"valid rmse {rmse:.4f} mse {mse:.4f} mae {mae:.4f} r2 {r2v:.4f}"
               + (f" | slots {trainer.slot_misses} recorded, {trainer.slot_hits} replayed ({trainer.slot_promoted} promoted)"

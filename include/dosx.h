@@ -1286,6 +1286,66 @@ int dosx_loss_phonon_f64(const double* pg, const double* ps, const double* y, do
 int dosx_adamw_f64(double* p, const double* g, double* m, double* v, int64_t n, double lr, double beta1, double beta2,
                    double eps, double weight_decay, int step, dosx_stream_t stream);
 
+/* ---- guarded optimizer step (csrc/step_guard.hip; the guarded AdamW kernels stand beside the unguarded ones) ---------------
+ * What a fused trainer has in place of `clip_grad_norm_` and of a GradScaler-style "skip if non-finite": one statistics launch
+ * over the flat gradient, behind the recorded program and in front of the AdamW launch, and an AdamW that reads its verdict
+ * from device memory.  No host read anywhere in the step.
+ *
+ * DosxStepGuard: the device-resident record, one per trainer, 16-byte aligned, zero-initialised by its owner.
+ *   this step:  sumsq = sum of g[i]^2 over the FINITE elements (accumulated in double for both dtypes), norm = sqrt(sumsq),
+ *               clip = max_norm / (norm + 1e-6) where that is < 1, else exactly 1.0 (also without a max_norm) - torch's
+ *               clip_grad_norm_ coefficient; n_bad / first_bad = count and lowest flat index of the non-finite elements
+ *               (first_bad = -1: none); skip = 0 / 1; reason = DOSX_GUARD_* bits; step_size / bc2_scale = the two
+ *               bias-correction scalars the guarded AdamW applies; t = the AdamW time they stand for.
+ *   sticky (until the owner zeroes them): applied / skipped = steps counted since then; first_skip_step / first_skip_reason /
+ *               first_skip_bad = attempt number, reason and first_bad of the FIRST skipped step.
+ * reason: NONFINITE - an element with all exponent bits set (NaN, +-inf); OVERFLOW - sumsq itself is not finite although every
+ *   element is (float64 only: an element of magnitude beyond ~1e154 squares to inf) - such a gradient is treated like a
+ *   non-finite one; STALLED - exchange_status[0] != 0 (the sticky stall status of the column-split exchanges above: every step
+ *   is skipped until the owner has cleared it).
+ *
+ * dosx_grad_guard_f32 / _f64: one launch over g[0, n).  DOSX_GUARD_THREADS threads; min(ceil(n / (16 / sizeof(T)) /
+ *   DOSX_GUARD_THREADS), DOSX_GUARD_MAX_BLOCKS) workgroups (at least 1: dosx_grad_guard_blocks) that stride over the 16-byte
+ *   vectors, the < 16-byte tail goes to the first threads of the grid one element each.  Each workgroup publishes {sum of
+ *   squares, bad count, first bad} to its slot of the workspace slab and draws a ticket (csrc/common.h: publish / ticket /
+ *   last arriver); the workgroup that draws the last ticket reads all slots back - thread t the slots t, t + 256, ... in rising
+ *   order, then a fixed tree over the threads - finishes the record and zeroes the counter.  Nobody waits for anybody: no poll,
+ *   nothing that can stall.  The grid and every summation order are functions of n alone: the record is bitwise run to run.
+ *   max_norm < 0: no clipping (clip = 1.0).  exchange_status: NULL or the device address dosx_exchange_status_address gives.
+ *   step: the caller's 1-based ATTEMPT count; lr, beta1, beta2 as the unguarded AdamW entry takes them.  With skipped == 0 the
+ *   record receives the bias-correction scalars the unguarded entry computes on the host for `step` (computed by the same
+ *   host expressions: a guarded run in which nothing trips is bit for bit the unguarded run); otherwise they are recomputed on
+ *   the device in double with pow() for t = step - skipped: a skipped step does not advance AdamW's time.
+ *   fp32: step_size = (float)(lr / bc1), bc2_scale = (float)(1 / sqrt(bc2)); float64: step_size = lr / bc1, bc2_scale = sqrt(bc2).
+ *   workspace: DOSX_GUARD_WORKSPACE_BYTES of 16-byte aligned device memory, zeroed once by its owner, private to one stream.
+ * dosx_adamw_guarded / _f64: dosx_adamw (grad_scale = clip) / dosx_adamw_f64 (on g * clip) with skip, clip and the two scalars read
+ *   from the record by every thread (plain uniform loads); skip != 0 returns before any store.  g is never written.
+ * All four refuse NULL operands, n < 0, step < 1, a NaN max_norm and buffers off a 16-byte boundary with -22 and a message. */
+enum { DOSX_GUARD_NONFINITE = 1, DOSX_GUARD_OVERFLOW = 2, DOSX_GUARD_STALLED = 4 };
+#define DOSX_GUARD_THREADS 256
+#define DOSX_GUARD_MAX_BLOCKS 256
+#define DOSX_GUARD_WORKSPACE_BYTES 6208
+typedef struct DosxStepGuard {
+  double sumsq, norm, clip;
+  double step_size, bc2_scale;
+  int64_t n_bad, first_bad;
+  int64_t first_skip_bad;
+  int32_t skip, reason, t;
+  int32_t applied, skipped, first_skip_step, first_skip_reason;
+  int32_t reserved;
+} DosxStepGuard;
+int dosx_grad_guard_blocks(int64_t n, int elem_bytes);
+/* the device address of the four status words of dosx_exchange_status on the current device, written to *address_out (HOST memory) */
+int dosx_exchange_status_address(unsigned long long* address_out);
+int dosx_grad_guard_f32(const float* g, int64_t n, double max_norm, const int32_t* exchange_status, float lr, float beta1,
+                        float beta2, int step, void* guard, void* workspace, dosx_stream_t stream);
+int dosx_grad_guard_f64(const double* g, int64_t n, double max_norm, const int32_t* exchange_status, double lr, double beta1,
+                        double beta2, int step, void* guard, void* workspace, dosx_stream_t stream);
+int dosx_adamw_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, const void* guard, dosx_stream_t stream);
+int dosx_adamw_guarded_f64(double* p, const double* g, double* m, double* v, int64_t n, double lr, double beta1, double beta2,
+                           double eps, double weight_decay, const void* guard, dosx_stream_t stream);
+
 /* ---- evaluation metrics (csrc/eval.hip) -----------------------------------------------------------------------------------
  * utils.py:76-89 / :127-139 evaluated one crystal at a time (what the reference computes at batch_size = 1).
  * pred, y: [B,S] rows with unit inner stride, rows S apart.  clamp0 != 0: both are clamped at 0 first (utils.py:74-76).
