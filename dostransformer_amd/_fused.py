@@ -7,6 +7,9 @@
 * parameters the reference never uses (``self_attn.in_proj_*``, ``self_attn.out_proj.*``,
   ``node_mlp_1.*``, ``alpha`` — SURVEY.md §0.2/§0.6) stay outside: they get ``grad = None`` and are
   therefore skipped by AdamW exactly like upstream.
+* fine-tuning: ``requires_grad`` is read when the buffer is laid out - trainable parameters first, frozen ones behind them
+  (``FlatParams.n_train``); a frozen parameter keeps its views, gets ``grad = None`` and is stepped by nobody
+  (``FusedModel.freeze`` / ``train_only`` / ``update_trainable``).
 * one ``torch.autograd.Function`` spans the whole model: forward runs the forward program and keeps
   its activations, backward runs the backward program and publishes ``param.grad`` as views of the
   flat gradient buffer (no per-parameter copies).
@@ -50,33 +53,64 @@ def is_last_param(name: str) -> bool:
     return name.startswith(_LAST)
 
 
+class GradViews(dict):
+    """The gradient views of a :class:`FlatParams`, name -> view, with the frozen set the backward programs prune by
+    (functional: ``wgrad_needed`` / ``trunk_cut`` / ``first_encoder_cut``).  The two cuts are decided once, when the views are
+    made: the per-step path reads two attributes and scans nothing."""
+
+    def __init__(self, views, frozen=()):
+        super().__init__(views)
+        self.frozen = frozenset(frozen)
+        self.cut_trunk = Fn.trunk_cut(self.keys(), self.frozen)
+        self.cut_first = Fn.first_encoder_cut(self.keys(), self.frozen)
+
+
+def frozen_live_names(module: nn.Module, extra_dead=()) -> frozenset:
+    """Names of the live parameters whose ``requires_grad`` is off (one scan of the module: not for the per-step path)."""
+    return frozenset(n for n, p in module.named_parameters()
+                     if not p.requires_grad and not (is_dead_param(n) or n in extra_dead))
+
+
 class FlatParams:
     """Flat parameter + gradient storage for the live parameters of a module: fp32, or fp64 for a module that runs the
-    float64 program (FusedModel._flat_dtype)."""
+    float64 program (FusedModel._flat_dtype).
+
+    ``requires_grad`` is read HERE, once: the trainable parameters come first, ``flat[:n_train]``, the frozen ones behind them.
+    Everything that steps or measures "the gradient" takes ``(buffer, n_train)``; a frozen parameter keeps its ``P`` view (the
+    forward reads it) and its ``G`` view (fused launches write partial rows there: no null destinations) and nothing reads
+    the latter.  ``frozen`` is the snapshot; ``FusedModel.update_trainable()`` takes a new one."""
 
     def __init__(self, module: nn.Module, device: torch.device, extra_dead=(), dtype: torch.dtype = torch.float32):
         live = [(n, p) for n, p in module.named_parameters() if not (is_dead_param(n) or n in extra_dead)]
+        frozen = [x for x in live if not x[1].requires_grad]
+        live = [x for x in live if x[1].requires_grad]
         # layout: [ last bucket (encoders + layer 0) | mid bucket (rest of the GNN trunk) | early bucket (everything else) ],
-        # each in module order; [last | mid] together are the "late" slice flat[:n_late]
+        # each in module order; [last | mid] together are the "late" slice flat[:n_late]; then the frozen parameters
         ordered = [x for x in live if is_last_param(x[0])] + [x for x in live if is_late_param(x[0]) and not is_last_param(x[0])] + \
                   [x for x in live if not is_late_param(x[0])]
+        n_live = len(ordered)
+        ordered += frozen
         names, params = [n for n, _ in ordered], [p for _, p in ordered]
-        offs, tot, n_late, n_last = [], 0, 0, 0
-        for n, p in ordered:
+        offs, tot, n_late, n_last, n_train = [], 0, 0, 0, 0
+        for i, (n, p) in enumerate(ordered):
             offs.append(tot)
             tot += (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
-            if is_late_param(n):
-                n_late = tot
-            if is_last_param(n):
-                n_last = tot
+            if i < n_live:
+                n_train = tot
+                if is_late_param(n):
+                    n_late = tot
+                if is_last_param(n):
+                    n_last = tot
         self.names, self.offsets, self.total = names, offs, tot
+        self.n_train = n_train        # floats: flat[:n_train] the trainable parameters, flat[n_train:] the frozen ones
+        self.frozen = frozenset(n for n, _ in frozen)
         self.n_late = n_late          # floats: flat[:n_late] is the GNN trunk, flat[n_late:] the early bucket
         self.n_last = n_last          # floats: flat[:n_last] the last bucket, flat[n_last:n_late] the mid bucket
         self.dtype = dtype
         self.flat = torch.zeros(tot, device=device, dtype=dtype)
         self.grad = torch.zeros(tot, device=device, dtype=dtype)
         self.P: Dict[str, torch.Tensor] = {}
-        self.G: Dict[str, torch.Tensor] = {}
+        G: Dict[str, torch.Tensor] = {}
         self.params: Dict[str, nn.Parameter] = {}
         with torch.no_grad():
             for n, p, o in zip(names, params, offs):
@@ -84,8 +118,9 @@ class FlatParams:
                 view.copy_(p.detach().to(device=device, dtype=dtype))
                 p.data = view
                 self.P[n] = view
-                self.G[n] = self.grad[o:o + p.numel()].view(p.shape)
+                G[n] = self.grad[o:o + p.numel()].view(p.shape)
                 self.params[n] = p
+        self.G = GradViews(G, self.frozen)
         for n, p in module.named_parameters():       # dead parameters just follow the module's device
             if n not in self.P and p.device != device:
                 p.data = p.data.to(device)
@@ -96,8 +131,15 @@ class FlatParams:
         return self.flat.device == device and self.anchor.data_ptr() == self.anchor_ptr and \
             self.anchor.dtype == self.dtype
 
+    def trainable_names(self) -> List[str]:
+        return [n for n in self.names if n not in self.frozen]
+
     def publish_grads(self, G: Dict[str, torch.Tensor], accumulate_into_existing: bool) -> None:
+        """``param.grad`` of the trainable parameters; a frozen one keeps ``grad is None``, as under autograd."""
+        frozen = self.frozen
         for n, p in self.params.items():
+            if n in frozen:
+                continue
             if p.grad is None or not accumulate_into_existing:
                 p.grad = G[n]
             else:
@@ -124,7 +166,7 @@ class _ModelFn(torch.autograd.Function):
         if busy:
             # true accumulation (two backward() calls without zero_grad): use a scratch gradient buffer
             gbuf = torch.zeros_like(fp.grad)
-            G = {n: gbuf[o:o + fp.P[n].numel()].view(fp.P[n].shape) for n, o in zip(fp.names, fp.offsets)}
+            G = GradViews({n: gbuf[o:o + fp.P[n].numel()].view(fp.P[n].shape) for n, o in zip(fp.names, fp.offsets)}, fp.frozen)
         else:
             G = fp.G
         sink = ops.GradSink(fp.flat.device)
@@ -185,6 +227,64 @@ class FusedModel(nn.Module):
 
     def flat_params(self, g=None) -> FlatParams:
         return self._ensure_flat(self._module_device(), g)
+
+    # ---- fine-tuning: which parameters train (host only) ---------------------------------------------------------------
+    # ``requires_grad`` is the single source of truth.  It is READ when the flat buffer is built or rebuilt and by
+    # update_trainable(); no step scans the parameters.  freeze() / train_only() call update_trainable() themselves; after a bare
+    # ``p.requires_grad_(...)`` the caller does, and a trainer's check() reports a snapshot that went stale.
+    def _live_named(self):
+        dead = getattr(self, "_flat_dead", ())
+        return [(n, p) for n, p in self.named_parameters() if not (is_dead_param(n) or n in dead)]
+
+    def _match(self, who: str, prefixes) -> None:
+        if not prefixes:
+            raise ValueError(f"{type(self).__name__}.{who}: no prefix given")
+        names = [n for n, _ in self._live_named()]
+        for pre in prefixes:
+            if not isinstance(pre, str) or not any(n.startswith(pre) for n in names):
+                raise ValueError(f"{type(self).__name__}.{who}: prefix {pre!r} matches no live parameter")
+
+    def freeze(self, *prefixes: str):
+        """``requires_grad_(False)`` on every live parameter whose name starts with one of ``prefixes`` (a prefix that matches
+        none raises ValueError naming it), then update_trainable().  Returns self."""
+        self._match("freeze", prefixes)
+        for n, p in self._live_named():
+            if n.startswith(tuple(prefixes)):
+                p.requires_grad_(False)
+        self.update_trainable()
+        return self
+
+    def train_only(self, *prefixes: str):
+        """Exactly the live parameters whose name starts with one of ``prefixes`` train, every other one is frozen (a prefix
+        that matches none raises ValueError naming it), then update_trainable().  Returns self."""
+        self._match("train_only", prefixes)
+        for n, p in self._live_named():
+            p.requires_grad_(n.startswith(tuple(prefixes)))
+        self.update_trainable()
+        return self
+
+    def trainable_names(self) -> List[str]:
+        """Names of the live parameters that train, in module order (read from ``requires_grad``, not from the snapshot)."""
+        return [n for n, p in self._live_named() if p.requires_grad]
+
+    def update_trainable(self) -> bool:
+        """Re-read ``requires_grad`` and rebuild the flat buffer if the frozen set changed (values are carried over; a trainer
+        re-homes its moments by name and drops its recorded slots at its next step).  True: rebuilt.  Nothing to do before the
+        first forward: the buffer is laid out from the flags when it is built."""
+        fp = self._flat
+        if fp is None:
+            return False
+        dead = getattr(self, "_flat_dead", ())
+        if frozen_live_names(self, dead) == fp.frozen:
+            return False
+        new = FlatParams(self, fp.flat.device, dead, fp.dtype)
+        object.__setattr__(self, "_flat", new)
+        return True
+
+    def trainable_stale(self) -> bool:
+        """True: ``requires_grad`` changed since the flat buffer was laid out and update_trainable() has not run (one scan)."""
+        fp = self._flat
+        return fp is not None and frozen_live_names(self, getattr(self, "_flat_dead", ())) != fp.frozen
 
     def _run(self, g):
         dev = self._module_device()

@@ -1317,9 +1317,15 @@ extern "C" int dosx_attention_bwd(const DosxAttn* ap, dosx_stream_t stream) {
   DOSX_CHECK_ARG(ap, "dosx_attention_bwd: null");
   const DosxAttn& a = *ap;
   if (int rc = check_attn(a, "dosx_attention_bwd")) return rc;
-  DOSX_CHECK_ARG(a.dout && a.dx && (a.dscores || pkv_ok(a)) && a.dkvhat && a.partials_q && a.partials_kv,
+  // DQ_HALF with dkvhat == NULL: the query-only backward, a complete call - no key gradient is wanted (keys from frozen
+  // parameters), no DKV half follows; dkv_part / dkv_cnt / partials_kv may be NULL, and dscores too where the crystal-aligned
+  // kernel takes the shape (the streamed and the general dq kernels need it as their scratch)
+  const bool qo = (a.flags & DOSX_ATTN_BWD_DQ_HALF) && !(a.flags & DOSX_ATTN_BWD_DKV_HALF) && a.dkvhat == nullptr;
+  DOSX_CHECK_ARG(a.dout && a.dx && a.partials_q && (qo || ((a.dscores || pkv_ok(a)) && a.dkvhat && a.partials_kv)),
                  "dosx_attention_bwd: null operand");
+  DOSX_CHECK_ARG(!qo || !a.dkv_cnt, "dosx_attention_bwd: the query-only backward (DQ_HALF, dkvhat NULL) takes no dkv_cnt");
   if (const int rc = dosx_detail::attn_aligned_bwd(a, to_stream(stream))) return rc < 0 ? rc : 0;
+  DOSX_CHECK_ARG(!qo || a.dscores || pkv_ok(a), "dosx_attention_bwd: query-only backward of this shape needs the dscores scratch");
   if (a.Nk > MAX_FUSED_NK) return dosx_detail::attn_general_bwd(a, to_stream(stream));
   const Geo g = make_geo(a.H, a.Nk);
   const int kg = a.Nk > 32 ? 2 : 1;

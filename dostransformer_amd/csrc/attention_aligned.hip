@@ -304,7 +304,13 @@ __global__ __launch_bounds__(512) void attn_al_fwd_kernel(const DosxAttn a, cons
 // ------------------------------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------------------------------
-template <int NG, bool KP>
+// QO (DOSX_ATTN_BWD_DQ_HALF with dkvhat == NULL: the query-only backward, for keys that come from frozen parameters): phases a - e
+// as they are, their P' / Ql stores to LDS included (the row phases stay the text the full form compiles: with the two stores taken
+// out of this kernel, the results with a dropout mask were no longer bitwise the full form's - the instantiation compiled to other
+// arithmetic; ffn_att_bwd_tile's query-only form does drop them and stays bitwise, tests/test_gpu_attention_query_only.py) - dx and partials_q are bitwise the full
+// form's - without phase f, the publication, the ticket and the last arriver's reduction; dkv_part / dkv_cnt / partials_kv /
+// dkvhat are not touched.
+template <int NG, bool KP, bool QO = false>
 __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, const AlGeo geo) {
   DOSX_SET_MAIN_PRIO();
   extern __shared__ __align__(16) float sm[];
@@ -447,6 +453,7 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
     __syncthreads();
     ASTAMP(so + 10);
     // ---- f: this workgroup's share of dK + dV += P'^T . dO + dS^T . Ql   ([NkP keys] x [R queries] . [R queries] x [H]) ----
+    if constexpr (!QO) {
 #pragma unroll
     for (int i = 0; i < NJW; ++i) {
       // job i of this wave: key tile jt, column tile ct - jt a compile-time value (or one of two), ct = the wave's own column
@@ -473,13 +480,14 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
       }
       __builtin_amdgcn_sched_barrier(0);               // (one job's 32 fragments at a time: the unrolled jobs must not be merged)
     }
+    }
     ASTAMP(so + 11);
     __syncthreads();                   // (the next tile's phase a overwrites Os / Ds)
     ASTAMP(so + 12);
   }
   ASTAMP(60);
   // ---- publish this workgroup's share (write-through) ----
-  {
+  if constexpr (!QO) {
     float* part = a.dkv_part + ((size_t)bq * nqt + w) * (size_t)Nk * H;
 #pragma unroll
     for (int i = 0; i < NJW; ++i) {
@@ -515,6 +523,7 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
       for (int c = tid; c < 2 * H; c += 512) z[c] = 0.f;
     }
   }
+  if constexpr (QO) return;
   // ---- ticket: the last arriving workgroup of key crystal bk finishes its key gradient ----
   ASTAMP(61);
   const bool last = dosx_last_arriver_wg(a.dkv_cnt, bk, (a.Bq / a.Bk) * wpc, reinterpret_cast<int*>(sm), tid);
@@ -533,9 +542,12 @@ __global__ __launch_bounds__(512) void attn_al_bwd_kernel(const DosxAttn a, cons
 // (the default: faster than attention.hip's at every BASELINE shape with <= 64 keys, profiles/r05_kernel_microbench.log `attn`)
 int g_al_mode = 2;
 
-inline bool al_shape_ok(const DosxAttn& a) {
+// the query-only backward: the dq half alone, no key gradient wanted
+inline bool al_query_only(const DosxAttn& a) { return a.flags == DOSX_ATTN_BWD_DQ_HALF && a.dkvhat == nullptr; }
+
+inline bool al_shape_ok(const DosxAttn& a, const bool query_only = false) {
   const int m = g_al_mode;
-  return m > 0 && a.flags == 0 && a.Nk >= 1 && a.Nk <= 64 && (a.H == 64 || a.H == 128 || a.H == 256) && (m > 1 || a.H > 128) &&
+  return m > 0 && (a.flags == 0 || query_only) && a.Nk >= 1 && a.Nk <= 64 && (a.H == 64 || a.H == 128 || a.H == 256) && (m > 1 || a.H > 128) &&
          a.qstats != nullptr;
 }
 
@@ -599,28 +611,31 @@ int attn_aligned_fwd(const DosxAttn& a, hipStream_t st) {
 }
 
 int attn_aligned_bwd(const DosxAttn& a, hipStream_t st) {
-  if (!al_shape_ok(a) || !a.dkv_part || !a.dkv_cnt) return 0;
+  const bool qo = al_query_only(a);
+  if (!al_shape_ok(a, qo) || (!qo && (!a.dkv_part || !a.dkv_cnt))) return 0;
   const AlGeo g = al_geo(a, true);
   if (g.KS > 2) return 0;
   const size_t smem = al_bwd_smem(a);
-  if (smem > 160 * 1024 || (size_t)a.Bq * ceil_div(a.Sq, R) * a.Nk * a.H * 4 >= 0x7fffffffull) return 0;
+  if (smem > 160 * 1024 || (!qo && (size_t)a.Bq * ceil_div(a.Sq, R) * a.Nk * a.H * 4 >= 0x7fffffffull)) return 0;
   const dim3 grid(a.Bq * g.wpc);
-#define DOSX_ALB1(NG_, KP_)                                                                                              \
+#define DOSX_ALB1(NG_, KP_, QO_)                                                                                         \
   do {                                                                                                                   \
     static bool attr_set = false;                                                                                        \
     if (!attr_set) {                                                                                                     \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_al_bwd_kernel<NG_, KP_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_al_bwd_kernel<NG_, KP_, QO_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
       attr_set = true;                                                                                                   \
     }                                                                                                                    \
-    hipLaunchKernelGGL((attn_al_bwd_kernel<NG_, KP_>), grid, dim3(512), smem, st, a, g);                                 \
+    hipLaunchKernelGGL((attn_al_bwd_kernel<NG_, KP_, QO_>), grid, dim3(512), smem, st, a, g);                            \
   } while (0)
-#define DOSX_ALB(NG_) do { if (a.key_ptr) DOSX_ALB1(NG_, true); else DOSX_ALB1(NG_, false); } while (0)
+#define DOSX_ALB2(NG_, KP_) do { if (qo) DOSX_ALB1(NG_, KP_, true); else DOSX_ALB1(NG_, KP_, false); } while (0)
+#define DOSX_ALB(NG_) do { if (a.key_ptr) DOSX_ALB2(NG_, true); else DOSX_ALB2(NG_, false); } while (0)
   switch (ceil_div(a.H, 64)) {
     case 1: DOSX_ALB(1); break;
     case 2: DOSX_ALB(2); break;
     default: DOSX_ALB(4);
   }
 #undef DOSX_ALB
+#undef DOSX_ALB2
 #undef DOSX_ALB1
   DOSX_LAUNCH_CHECK();
   return 1;

@@ -66,8 +66,9 @@ __device__ __forceinline__ void dosx_att_ln_row(const float4 (&x)[NG], const boo
 
 // ---- backward c: dp(j) = the row's dP of live key j, the caller's partial tiles summed in its own order; dP' = (dP + cq) o M with
 // a dropout mask; dS = P o (dP' - sum_j P dP') scale -> ss_row, P' = P o M -> ps_row (zeros beyond nk / the data, up to NkP).
-// (ss_row may be the row dp(j) reads: in place) ----
-template <class DP>
+// (ss_row may be the row dp(j) reads: in place).  QO (query-only backward: no key gradient is wanted): P' feeds only the
+// dK + dV share and is not stored, ps_row is not touched ----
+template <bool QO = false, class DP>
 __device__ __forceinline__ void dosx_att_bwd_ds_row(DP&& dp, const float (&pr)[4], const float (&mk)[4], const bool drop,
                                                     const float cq, const int nk, const int NkP, const bool rv, const float scale,
                                                     const int q16, float* ss_row, float* ps_row) {
@@ -88,14 +89,14 @@ __device__ __forceinline__ void dosx_att_bwd_ds_row(DP&& dp, const float (&pr)[4
     if (j >= NkP) continue;
     const bool v = j < nk && rv;
     ss_row[j] = v ? pr[jj] * (d[jj] - dot) * scale : 0.f;
-    ps_row[j] = v ? pr[jj] * mk[jj] : 0.f;
+    if constexpr (!QO) ps_row[j] = v ? pr[jj] * mk[jj] : 0.f;
   }
 }
 
 // ---- backward e: dq_ln = (dS . K^) o g0 (dq_row); LayerNorm-0 backward + the residual dO (go(k)) -> dx_row; the row's dgamma0 /
 // dbeta0 terms -> pg / pb (ACC: added to them, the caller keeps them across tiles); Ql = LN0(x) g0 + b0 -> ql_row (zeros beyond
-// the data) ----
-template <int NG, bool ACC, class GO>
+// the data); QO (query-only backward): Ql feeds only the dK + dV share and is not stored, ql_row is not touched ----
+template <int NG, bool ACC, bool QO = false, class GO>
 __device__ __forceinline__ void dosx_att_bwd_ln0_row(const float* dq_row, const float4 (&xr)[NG], const bool (&on)[NG],
                                                      const float4 (&g0)[NG], const float4 (&b0)[NG], const float mean,
                                                      const float rstd, const float invH, const bool rv, GO&& go, float* dx_row,
@@ -129,8 +130,9 @@ __device__ __forceinline__ void dosx_att_bwd_ln0_row(const float* dq_row, const 
           make_float4(rstd * (dd.x * g0[k].x - s1 - h.x * s2) + r.x, rstd * (dd.y * g0[k].y - s1 - h.y * s2) + r.y,
                       rstd * (dd.z * g0[k].z - s1 - h.z * s2) + r.z, rstd * (dd.w * g0[k].w - s1 - h.w * s2) + r.w));
     }
-    st4(ql_row + q16 * 4 + 64 * k,
-        rv ? make_float4(h.x * g0[k].x + b0[k].x, h.y * g0[k].y + b0[k].y, h.z * g0[k].z + b0[k].z, h.w * g0[k].w + b0[k].w)
-           : f4zero());
+    if constexpr (!QO)
+      st4(ql_row + q16 * 4 + 64 * k,
+          rv ? make_float4(h.x * g0[k].x + b0[k].x, h.y * g0[k].y + b0[k].y, h.z * g0[k].z + b0[k].z, h.w * g0[k].w + b0[k].w)
+             : f4zero());
   }
 }

@@ -750,7 +750,10 @@ __device__ __forceinline__ void ffn_att_bwd_prefetch(const DosxFfnBwd& a, AttBwd
   }
 }
 
-template <int R, bool KP>
+// QO (DosxFfnBwd.att_dkvhat == NULL: the query-only form, for keys that come from frozen parameters): phases a - e as they are -
+// dh, att_dxin, every partial column and att_partials_q are bitwise the full form's - without the P' / Ql stores that feed only
+// phase f, without phase f, the ticket and the last arriver's reduction; att_dkv_part / att_dkv_cnt / att_partials_kv are not read.
+template <int R, bool KP, bool QO>
 __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __restrict__ sm, const AttBwdSm& L, const AttBwdRegs& q,
                                                  const int al_s0, const int al_bq, const int tile, const int nqt, const int tid) {
   const int H = a.H, LDK = a.H + 4;
@@ -822,7 +825,7 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
   __syncthreads();
   // ---- c: dS = P o (dP' - sum_j P dP') scale -> Ss;  P' = P o M -> Ps2 (zeros beyond Nk / the data) ----
   if (rowok)
-    dosx_att_bwd_ds_row(
+    dosx_att_bwd_ds_row<QO>(
         [&](const int j) {
           float t = L.Sc[lr * 68 + j];
           for (int kq = 1; kq < KS; ++kq) t += L.Sp[(kq - 1) * R * 68 + lr * 68 + j];
@@ -849,7 +852,7 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
   {
     float4 pg[2] = {f4zero(), f4zero()}, pb[2] = {f4zero(), f4zero()};
     if (rowok)
-      dosx_att_bwd_ln0_row<2, false>(L.Ds + lr * LDK, xr, on, g0, b0, mean, rstd, invH, rv, [&](const int k) { return go[k]; },
+      dosx_att_bwd_ln0_row<2, false, QO>(L.Ds + lr * LDK, xr, on, g0, b0, mean, rstd, invH, rv, [&](const int k) { return go[k]; },
                                      a.att_dxin + orow * a.att_lddxin, L.Ql + lr * LDK, q16, pg, pb);
     // quarter-wave slots [32][2][128] (R = 16: the upper sixteen hold zeros)
     const int slot = wave * 4 + g4;
@@ -872,6 +875,7 @@ __device__ __forceinline__ void ffn_att_bwd_tile(const DosxFfnBwd& a, float* __r
     }
   }
   FSTAMP(24);
+  if constexpr (QO) return;
   // ---- f: this tile's share of dK + dV: [NkP keys] x [R queries] . [R queries] x [H] -> its slot of dkv_part (write-through) ----
   {
     float* part = a.att_dkv_part + ((size_t)al_bq * nqt + tile) * (size_t)Nk * H;
@@ -925,7 +929,7 @@ constexpr int BLDW = FBN + 4;    // 132: padded rows of a k-major weight chunk
 // ATT = 2 (round 5): CRYSTAL-ALIGNED tiles like ffn_fwd_kernel<.., 2> (a workgroup = R consecutive query rows s of ONE query
 // batch entry, row r = s * Bq + bq, grid = Bq x ceil(Sq / R)), and the attention half's backward behind the row epilogue
 // (ffn_att_bwd_tile): dx1 never reaches HBM, the layer's backward is one launch.
-template <bool HALF, int KB, int ATTK = 0>
+template <bool HALF, int KB, int ATTK = 0, bool QO = false>
 __global__ __launch_bounds__(512, DOSX_FFN_BWD_OCC) void ffn_bwd_kernel(const DosxFfnBwd a) {
   // ATTK = ATT, or 4 = ATT 2 with per-crystal key counts (DosxFfnBwd.att_key_ptr: the KP forms of the attention epilogue)
   constexpr int ATT = ATTK >= 3 ? ATTK - 2 : ATTK;
@@ -1296,7 +1300,7 @@ __global__ __launch_bounds__(512, DOSX_FFN_BWD_OCC) void ffn_bwd_kernel(const Do
     L.Pp = L.Sp;
     (void)NkP;
     FSTAMP(16);
-    ffn_att_bwd_tile<R, KP>(a, sm, L, attq, al_s0, al_bq, al_tile, al_tpc, tid);
+    ffn_att_bwd_tile<R, KP, QO>(a, sm, L, attq, al_s0, al_bq, al_tile, al_tpc, tid);
     FSTAMP(29);
   }
 }
@@ -1481,8 +1485,9 @@ extern "C" int dosx_ffn_bwd(const DosxFfnBwd* ap, dosx_stream_t stream) {
   const bool att = a.att_kvhat != nullptr;
   if (att) {
     DOSX_CHECK_ARG(dosx_ffn_att_bwd_supported(H, a.att_Nk, a.att_Sq, a.att_Bq) && ffn_chunk(H) == 64, "dosx_ffn_bwd: fused attention backward unsupported for H=%d Nk=%d", H, a.att_Nk);
-    DOSX_CHECK_ARG(a.att_x && a.att_gamma0 && a.att_beta0 && a.att_probs && a.att_qstats && a.att_dxin && a.att_partials_q && a.att_partials_kv &&
-                       a.att_dkv_part && a.att_dkv_cnt && a.att_dkvhat && a.att_Bk > 0 && a.att_Bq % a.att_Bk == 0 && a.att_Sq * a.att_Bq == a.M &&
+    // (att_dkvhat == NULL: the query-only form - no key gradient, its scratch, counters and key-side partial rows may be NULL too)
+    DOSX_CHECK_ARG(a.att_x && a.att_gamma0 && a.att_beta0 && a.att_probs && a.att_qstats && a.att_dxin && a.att_partials_q &&
+                       (!a.att_dkvhat || (a.att_partials_kv && a.att_dkv_part && a.att_dkv_cnt)) && a.att_Bk > 0 && a.att_Bq % a.att_Bk == 0 && a.att_Sq * a.att_Bq == a.M &&
                        (a.att_ldxin & 3) == 0 && (a.att_lddxin & 3) == 0 && a.att_qs >= 0 && a.att_qb >= 0,
                    "dosx_ffn_bwd: fused attention backward needs x / gamma0 / beta0 / probs / qstats / dxin / partials / dkv scratch + counters and Sq * Bq == M");
   }
@@ -1502,10 +1507,19 @@ extern "C" int dosx_ffn_bwd(const DosxFfnBwd* ap, dosx_stream_t stream) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_bwd_kernel<true, 64, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_bwd_kernel<false, 64, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_bwd_kernel<true, 64, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_bwd_kernel<false, 64, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_bwd_kernel<true, 64, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_bwd_kernel<false, 64, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ffn_bwd_kernel<true, 64, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr_set = true;
   }
   const dim3 grid(att ? a.att_Bq * ceil_div(a.att_Sq, R) : ceil_div(a.M, R));
-  if (att && a.att_key_ptr && half) hipLaunchKernelGGL((ffn_bwd_kernel<true, 64, 4>), grid, dim3(512), smem, to_stream(stream), a);
+  const bool qo = att && !a.att_dkvhat;
+  if (qo && a.att_key_ptr && half) hipLaunchKernelGGL((ffn_bwd_kernel<true, 64, 4, true>), grid, dim3(512), smem, to_stream(stream), a);
+  else if (qo && a.att_key_ptr) hipLaunchKernelGGL((ffn_bwd_kernel<false, 64, 4, true>), grid, dim3(512), smem, to_stream(stream), a);
+  else if (qo && half) hipLaunchKernelGGL((ffn_bwd_kernel<true, 64, 2, true>), grid, dim3(512), smem, to_stream(stream), a);
+  else if (qo) hipLaunchKernelGGL((ffn_bwd_kernel<false, 64, 2, true>), grid, dim3(512), smem, to_stream(stream), a);
+  else if (att && a.att_key_ptr && half) hipLaunchKernelGGL((ffn_bwd_kernel<true, 64, 4>), grid, dim3(512), smem, to_stream(stream), a);
   else if (att && a.att_key_ptr) hipLaunchKernelGGL((ffn_bwd_kernel<false, 64, 4>), grid, dim3(512), smem, to_stream(stream), a);
   else if (att && half) hipLaunchKernelGGL((ffn_bwd_kernel<true, 64, 2>), grid, dim3(512), smem, to_stream(stream), a);
   else if (att) hipLaunchKernelGGL((ffn_bwd_kernel<false, 64, 2>), grid, dim3(512), smem, to_stream(stream), a);

@@ -286,6 +286,8 @@ def _wgrad_linear(sink: GradSink, G: Params, wkey: str, bkey: Optional[str], M: 
     ``keep``: the tensor(s) behind ``dy`` that the caller may drop before the side stream has run)."""
     if wkey not in G:
         return
+    if not wgrad_needed(getattr(G, "frozen", ()), wkey, bkey):       # (fine-tuning: nothing steps this Linear)
+        return
     K = sum(s.width for s in segs)
     ns = ops.wgrad_splits(M, N, K)
     if tail:
@@ -303,7 +305,7 @@ def _wgrad_linear(sink: GradSink, G: Params, wkey: str, bkey: Optional[str], M: 
     # operands' buffers exist, which may be in front of the launch that fills them (the fused final-LayerNorm backward writes dY of
     # the last layer's fc2 job inside the ffn_bwd launch that follows).  Round 6 removed the launch-as-described mode
     # (DOSX_GROUP_WGRAD=0): it had been unsound since those fusions and nothing ran it.
-    sink.defer_wgrad(ops.wgrad_desc(M, N, dy, segs, slab, slab_b, ns, **kw), keep)
+    sink.defer_wgrad(ops.wgrad_desc(M, N, dy, segs, slab, slab_b, ns, **kw), keep, key=wkey)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -881,6 +883,54 @@ def attention_bwd_in_ffn(Sq: int, Bq: int, Nk: int, H: int, fdrop: bool) -> bool
                 and ops.ffn_att_bwd_partial_rows(Sq, Bq) <= _ATT_ALIGNED_MAX_WGS)
 
 
+# ---- fine-tuning: what a frozen set prunes from the backward programs.  Host-only policies on parameter NAMES; the frozen set
+# travels with G (``_fused.GradViews.frozen``; a plain dict has none: nothing is pruned), and the two cuts are decided once, when
+# the views are made (``G.cut_trunk`` / ``G.cut_first``).  Pruning removes launches and jobs; what still runs computes what it
+# computed before.
+_TRUNK = ("GN_encoder.", "stacked_processor.", "GN_decoder.")
+
+
+def frozen_of(G: Params) -> frozenset:
+    return getattr(G, "frozen", frozenset())
+
+
+def wgrad_needed(frozen, wkey: str, bkey: Optional[str]) -> bool:
+    """Whether the weight-gradient job of a Linear is issued: not when its weight and the bias the job serves (if any) are both
+    frozen.  A job that serves a trainable bias next to a frozen weight runs whole."""
+    return not (wkey in frozen and (bkey is None or bkey in frozen))
+
+
+def table_needed(frozen, key: str) -> bool:
+    """Whether the row reduction into an embedding table's gradient is launched."""
+    return key not in frozen
+
+
+def trunk_cut(names, frozen) -> bool:
+    """The backward ends in front of the GNN trunk - no dense-key backward, no decoder backward, no gnn_trunk_bwd, no products
+    that only feed them - when every GN_encoder. / stacked_processor. / GN_decoder. parameter is frozen."""
+    trunk = [n for n in names if n.startswith(_TRUNK)]
+    return bool(trunk) and all(n in frozen for n in trunk)
+
+
+def first_encoder_cut(names, frozen) -> bool:
+    """... and there is no backward of the ``transformer`` encoder either when, in addition, every ``transformer.`` parameter
+    and ``embeddings.weight`` are frozen: its input gradient then reaches frozen parameters only."""
+    first = [n for n in names if n.startswith("transformer.") or n == "embeddings.weight"]
+    return trunk_cut(names, frozen) and bool(first) and all(n in frozen for n in first)
+
+
+def attention_query_only(names, frozen, pre: str, layer: int) -> bool:
+    """Whether layer ``layer`` of the cross-attention encoder ``pre`` needs no key gradient: its keys come from a frozen trunk
+    (trunk_cut) AND its layer_norms.0 is frozen - that LayerNorm is applied to the keys too, so its own gradient needs the
+    key-side partial rows.  ``transformer_self`` never qualifies: its keys are its own inputs.  encoder_bwd then runs the
+    layer's attention backward in its query-only form: DosxFfnBwd.att_dkvhat == NULL inside dosx_ffn_bwd, DOSX_ATTN_BWD_DQ_HALF
+    with dkvhat == NULL as a complete dosx_attention_bwd call elsewhere."""
+    if pre not in ("transformer", "transformer_source") or not trunk_cut(names, frozen):
+        return False
+    ln = f"{pre}.layers.{layer}.layer_norms.0."
+    return ln + "weight" in frozen and ln + "bias" in frozen
+
+
 def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int, qb: int, kvhat: torch.Tensor,
                 Nk: int, Bk: int, H: int, T: int, final_ln: bool = True, drop=None, head: Optional[Head] = None, fdrop=None, key_ptr=None):
     """x: query rows (row (s,bq) at (s*qs + bq*qb)); kvhat: [Nk*Bk, H] normalised keys (stale across layers).
@@ -1086,6 +1136,7 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx: EncoderCtx, dy: Optional[to
         sink.add(part, 0, G[pre + ".layer_norm.weight"], r32, 2 * H, H)
         sink.add(part, H, G[pre + ".layer_norm.bias"], r32, 2 * H, H)
     nqt, nkt = (Sq + 31) // 32, (Nk + 31) // 32
+    frozen, cut_trunk = frozen_of(G), bool(getattr(G, "cut_trunk", False))
     for t in reversed(range(T)):
         lp = f"{pre}.layers.{t}"
         lay = ctx.layers[t]
@@ -1107,7 +1158,18 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx: EncoderCtx, dy: Optional[to
         small = bool(_lib_load().dosx_attention_pkv_supported(int(Nk), int(H)))
         att_in_ffn = attention_bwd_in_ffn(Sq, Bq, Nk, H, fdrop=fm is not None)
         att_bwd_args = None
-        if att_in_ffn:
+        # fine-tuning: keys from a frozen trunk under a frozen layer_norms.0 - no key gradient (attention_query_only; the trunk
+        # condition is the views' own cut_trunk, decided when they were made)
+        q_only = bool(cut_trunk and pre != "transformer_self" and
+                      lp + ".layer_norms.0.weight" in frozen and lp + ".layer_norms.0.bias" in frozen)
+        if att_in_ffn and q_only:
+            nqt_al = ops.ffn_att_bwd_partial_rows(Sq, Bq) // Bq
+            part_a = sink.scratch(Bq * nqt_al, 2 * H)                          # (the query-side rows only; nobody reduces them)
+            dxin_a = _empty(dev, rows, H)
+            att_bwd_args = AttBwd(x=x_in, kvhat=kvhat, gamma0=g0, beta0=b0, probs=probs, qstats=qstats, mask=mask, dxin=dxin_a,
+                                  partials_q=part_a.data_ptr(), partials_kv=None, dkv_part=None, dkv_cnt=None, dkvhat=None,
+                                  accumulate=0, Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=qs, qb=qb, key_ptr=key_ptr)
+        elif att_in_ffn:
             nqt_al = ops.ffn_att_bwd_partial_rows(Sq, Bq) // Bq                # query tiles per batch entry (16- or 32-row tiles)
             npart_a = Bq * nqt_al + Bk * ((Nk + 15) // 16)
             part_a = sink.scratch(npart_a, 2 * H)
@@ -1153,16 +1215,19 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx: EncoderCtx, dy: Optional[to
         # `kvp` and the dk+dv half is a small reduction over those partials; larger key sets (201 eDOS bins) stream the
         # dS round trip through `dsc` into the dkv kernel
         if att_in_ffn:          # (the attention half ran inside the ffn_bwd launch above)
-            sink.add(part_a, 0, G[lp + ".layer_norms.0.weight"], npart_a, 2 * H, H)
-            sink.add(part_a, H, G[lp + ".layer_norms.0.bias"], npart_a, 2 * H, H)
+            if not q_only:      # (query-only: layer_norms.0 is frozen, its key-side partial rows do not exist)
+                sink.add(part_a, 0, G[lp + ".layer_norms.0.weight"], npart_a, 2 * H, H)
+                sink.add(part_a, H, G[lp + ".layer_norms.0.bias"], npart_a, 2 * H, H)
             sink.keep(mask, x_in)
             dx = dxin_a
             continue
-        npart = Bq * nqt + Bk * ((Nk + 15) // 16 if small else nkt)        # key-side partial rows: per 16 / 32 keys
+        npart = Bq * nqt + (0 if q_only else Bk * ((Nk + 15) // 16 if small else nkt))   # key-side partial rows: per 16 / 32 keys
         part = sink.scratch(npart, 2 * H)
         dxin = _empty(dev, rows, H)
-        dsc = None if small else _empty(dev, Bq, Sq, Nk)
-        kvp = sink.scratch(Bq * nqt * Nk, H) if small else None
+        # (query-only: the dq half alone is the whole call, include/dosx.h; dscores is the scratch of the streamed / general dq
+        #  kernels, the crystal-aligned one ignores it)
+        dsc = None if (small and not q_only) else _empty(dev, Bq, Sq, Nk)
+        kvp = sink.scratch(Bq * nqt * Nk, H) if (small and not q_only) else None
         acc = 0 if (dkv_fresh and t == T - 1) else 1
 
         dout_att = dx1
@@ -1173,19 +1238,22 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx: EncoderCtx, dy: Optional[to
         def desc(flags):
             a = _attn_desc(Sq, Bq, Nk, Bk, H, qs, qb, x_in, kvhat, g0, b0)
             a.probs, a.qstats = probs.data_ptr(), qstats.data_ptr()
-            a.dout, a.dx, a.dkvhat, a.dkv_accumulate = dout_att.data_ptr(), dxin.data_ptr(), dkvhat.data_ptr(), acc
+            a.dout, a.dx, a.dkvhat, a.dkv_accumulate = dout_att.data_ptr(), dxin.data_ptr(), None if q_only else dkvhat.data_ptr(), acc
             if fm is not None:
                 flags |= ops.ATTN_NO_RESIDUAL
             a.dscores = dsc.data_ptr() if dsc is not None else None
             a.dkv_part = kvp.data_ptr() if kvp is not None else None
             a.drop_mask = mask.data_ptr() if mask is not None else None
             a.partials_q = part.data_ptr()
-            a.partials_kv = part.data_ptr() + 4 * Bq * nqt * 2 * H
+            a.partials_kv = None if q_only else part.data_ptr() + 4 * Bq * nqt * 2 * H
             a.flags = flags
             if key_ptr is not None:
                 a.key_ptr = key_ptr.data_ptr()
             return a
-        if small:
+        if q_only:
+            ops.attention_bwd(desc(ops.ATTN_BWD_DQ_HALF))
+            sink.keep(dsc, mask)
+        elif small:
             # ONE launch: every (query tile, crystal) workgroup publishes its share of dK + dV and the last one of a key
             # crystal to arrive finishes that crystal's key gradient (include/dosx.h: DosxAttn.dkv_cnt) - no reduction
             # launch, no side-stream round trip
@@ -1207,8 +1275,9 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx: EncoderCtx, dy: Optional[to
                 sink.keep(dsc, mask)
             else:
                 sink.on_side(lambda a2=a2: ops.attention_bwd(a2), (dx1, dxin) + tuple(t_ for t_ in (dsc, mask) if t_ is not None))
-        sink.add(part, 0, G[lp + ".layer_norms.0.weight"], npart, 2 * H, H)
-        sink.add(part, H, G[lp + ".layer_norms.0.bias"], npart, 2 * H, H)
+        if not q_only:                     # (query-only: layer_norms.0 is frozen, its key-side partial rows do not exist)
+            sink.add(part, 0, G[lp + ".layer_norms.0.weight"], npart, 2 * H, H)
+            sink.add(part, H, G[lp + ".layer_norms.0.bias"], npart, 2 * H, H)
         if fm is not None:                 # + the residual path of the attention half
             sink.keep(dout_att)
             dsum = _empty(dev, rows, H)
@@ -1616,6 +1685,9 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
     dev = ddos.device
     rows2 = S * 2 * B
     r32 = _rows32(rows2)
+    # fine-tuning (trunk_cut / first_encoder_cut above): a frozen trunk ends the program behind the first encoder's backward -
+    # dx_ext reaches frozen parameters only and is dropped with it - and a frozen first encoder + energy table takes that away too
+    frozen, cut, cut_first = frozen_of(G), bool(getattr(G, "cut_trunk", False)), bool(getattr(G, "cut_first", False))
     gf, bf = P["transformer_source.layer_norm.weight"], P["transformer_source.layer_norm.bias"]
     head = None
     if head_fused_bwd(H, cfg.T) and ddos.is_contiguous():
@@ -1662,7 +1734,8 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
         ops.rownorm_bwd_act(dkvs, kvs, rstd_s, ddosin, dosin, 0.01, dpre, rows2, H)
     map0, map1 = rowmap(d=B, m=2 * B, c=1, off=0), rowmap(d=B, m=2 * B, c=1, off=B)
     R = _empty(dev, 2 * B, H)            # sum over the energy axis of dpre (filled on the side stream below)
-    if len(a_g.keep) > 2 and "fc.weight" in G and "fc_prompt.weight" in G:
+    heads_factored = len(a_g.keep) > 2 and "fc.weight" in G and "fc_prompt.weight" in G
+    if heads_factored:
         # the same factoring for the weight gradients: the column blocks that multiply the per-crystal inputs are
         # (sum_s dpre[s, b]) (x) [graph_b (| prompt_b)] - B-row jobs on R - and only the E1 block keeps its S * B rows
         E1_, graph_ = a_g.keep[0], a_g.keep[1]
@@ -1677,7 +1750,7 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
     else:
         _wgrad_linear(sink, G, "fc.weight", "fc.bias", S * B, H, seg(dpre, rmap=map0), a_g.segs, keep=(dpre,))
         _wgrad_linear(sink, G, "fc_prompt.weight", "fc_prompt.bias", S * B, H, seg(dpre, rmap=map1), a_s.segs, keep=(dpre,))
-    if not heads_one:
+    if not heads_one and not cut_first:
         ops.gemm(S * B, H, [seg(dpre, rmap=map0)], Wfc[:, :H], dE1, w_layout=1)
         ops.gemm(S * B, H, [seg(dpre, rmap=map1)], Wfp[:, :H], dE1, w_layout=1, res=dE1)
     if sink.wside is not None and late_flush:
@@ -1690,25 +1763,40 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
     hp = H // 2
     dprow = _empty(dev, B, hp)
 
+    need_prompt = table_needed(frozen, cfg.prompt_key)
+    # (R also feeds the factored heads' B-row weight-gradient jobs)
+    need_R = (not cut) or need_prompt or (heads_factored and ("fc.weight" not in frozen or "fc_prompt.weight" not in frozen))
+
     def _const_inputs_bwd():
         ops.reduce_rows(dpre.data_ptr(), H, R.data_ptr(), H, 2 * B, S, 1, 2 * B, H)
-        ops.gemm(B, H, [seg(R[:B])], Wfc[:, H:2 * H], dgraph, w_layout=1)
-        ops.gemm(B, H, [seg(R[B:])], Wfp[:, H:2 * H], dgraph, w_layout=1, res=dgraph)
-        ops.gemm(B, hp, [seg(R[B:])], Wfp[:, 2 * H:], dprow, w_layout=1)
-        ops.embed_rows_bwd(dprow.data_ptr(), hp, sysidx, G[cfg.prompt_key], B, G[cfg.prompt_key].shape[0], hp)
-        # the decoder's dgrad needs only dgraph: it runs here, off the main chain, and its pooled block is added to the
-        # node gradient by the dense-key backward launch below (one launch on the main stream instead of three)
-        box_d["dcat"] = decoder_dgrad(P, cfg, m, dec_segs, dgraph)
+        if not cut:
+            ops.gemm(B, H, [seg(R[:B])], Wfc[:, H:2 * H], dgraph, w_layout=1)
+            ops.gemm(B, H, [seg(R[B:])], Wfp[:, H:2 * H], dgraph, w_layout=1, res=dgraph)
+        if need_prompt:
+            ops.gemm(B, hp, [seg(R[B:])], Wfp[:, 2 * H:], dprow, w_layout=1)
+            ops.embed_rows_bwd(dprow.data_ptr(), hp, sysidx, G[cfg.prompt_key], B, G[cfg.prompt_key].shape[0], hp)
+        if not cut:
+            # the decoder's dgrad needs only dgraph: it runs here, off the main chain, and its pooled block is added to the
+            # node gradient by the dense-key backward launch below (one launch on the main stream instead of three)
+            box_d["dcat"] = decoder_dgrad(P, cfg, m, dec_segs, dgraph)
     box_d = {}
-    sink.on_side(_const_inputs_bwd, (dpre, R, dgraph, dprow))
+    if need_R:
+        sink.on_side(_const_inputs_bwd, (dpre, R, dgraph, dprow))
     # first encoder (queries = energy embeddings broadcast over the batch)
-    dX1 = encoder_bwd(P, G, "transformer", c1, dE1, dkv, sink, kv_needed_next=True)
+    dX1 = None if cut_first else encoder_bwd(P, G, "transformer", c1, dE1, dkv, sink, kv_needed_next=True)
     # Every gradient of the transformer stacks, the heads and the embeddings is complete (or queued on the side
     # stream) here; what follows only touches the GNN trunk's parameters.  mid_hook: data-parallel training reduces
     # and all-reduces that early bucket now, underneath the GNN backward (train.Trainer).
     sink.join()          # dkv (dense keys): the earlier layers' key-gradient kernels ran on the side stream
     # gradient of the energy embeddings (sum over the batch): nobody waits for it - side stream, under the GNN backward
-    sink.on_side(lambda: ops.reduce_rows(dX1.data_ptr(), H, G["embeddings.weight"].data_ptr(), H, S, B, B, 1, H), (dX1,))
+    if dX1 is not None and table_needed(frozen, "embeddings.weight"):
+        sink.on_side(lambda: ops.reduce_rows(dX1.data_ptr(), H, G["embeddings.weight"].data_ptr(), H, S, B, B, 1, H), (dX1,))
+    if cut:              # (frozen trunk: the key gradient dkv, dgraph and dx_ext have no consumer)
+        sink.keep(dkv, dE1)
+        if mid_hook is not None:
+            mid_hook(sink)
+        sink.flush()
+        return
     late_hook = None
     if mid_hook is not None:          # (after the join: the early bucket's reduction must not sit between the main
         if H <= _MID_HOOK_LATE_MAX_H and dx_ext is None and cfg.L >= 1:
@@ -1820,24 +1908,37 @@ def _dostransformer_bwd_wide(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, 
     _wgrad_linear(sink, G, "fc.weight", "fc.bias", S * B, H, seg(dpre, rmap=map0), a_g.segs, keep=(dpre,))
     _wgrad_linear(sink, G, "fc_prompt.weight", "fc_prompt.bias", S * B, H, seg(dpre, rmap=map1), a_s.segs, keep=(dpre,))
     Wfc, Wfp = P["fc.weight"], P["fc_prompt.weight"]
+    # fine-tuning: the cuts of dostransformer_bwd
+    frozen, cut, cut_first = frozen_of(G), bool(getattr(G, "cut_trunk", False)), bool(getattr(G, "cut_first", False))
+    need_prompt = table_needed(frozen, cfg.prompt_key)
     dE1 = _empty(dev, S * B, H)
-    ops.gemm(S * B, H, [seg(dpre, rmap=map0)], Wfc[:, :H], dE1, w_layout=1)
-    ops.gemm(S * B, H, [seg(dpre, rmap=map1)], Wfp[:, :H], dE1, w_layout=1, res=dE1)
+    if not cut_first:
+        ops.gemm(S * B, H, [seg(dpre, rmap=map0)], Wfc[:, :H], dE1, w_layout=1)
+        ops.gemm(S * B, H, [seg(dpre, rmap=map1)], Wfp[:, :H], dE1, w_layout=1, res=dE1)
     R = _empty(dev, 2 * B, H)                                        # graph / prompt inputs are constant over the energy axis
     dgraph = _empty(dev, B, H)
     hp = H // 2
     dprow = _empty(dev, B, hp)
-    ops.reduce_rows(dpre.data_ptr(), H, R.data_ptr(), H, 2 * B, S, 1, 2 * B, H)
-    ops.gemm(B, H, [seg(R[:B])], Wfc[:, H:2 * H], dgraph, w_layout=1)
-    ops.gemm(B, H, [seg(R[B:])], Wfp[:, H:2 * H], dgraph, w_layout=1, res=dgraph)
-    ops.gemm(B, hp, [seg(R[B:])], Wfp[:, 2 * H:], dprow, w_layout=1)
-    ops.embed_rows_bwd(dprow.data_ptr(), hp, sysidx, G[cfg.prompt_key], B, G[cfg.prompt_key].shape[0], hp)
+    if not cut or need_prompt:
+        ops.reduce_rows(dpre.data_ptr(), H, R.data_ptr(), H, 2 * B, S, 1, 2 * B, H)
+    if not cut:
+        ops.gemm(B, H, [seg(R[:B])], Wfc[:, H:2 * H], dgraph, w_layout=1)
+        ops.gemm(B, H, [seg(R[B:])], Wfp[:, H:2 * H], dgraph, w_layout=1, res=dgraph)
+    if need_prompt:
+        ops.gemm(B, hp, [seg(R[B:])], Wfp[:, 2 * H:], dprow, w_layout=1)
+        ops.embed_rows_bwd(dprow.data_ptr(), hp, sysidx, G[cfg.prompt_key], B, G[cfg.prompt_key].shape[0], hp)
     sink.keep(R, dprow)
-    dX1, dk1, dv1 = encoder_kv_bwd(P, G, "transformer", c1, dE1, sink)
-    ops.reduce_rows(dX1.data_ptr(), H, G["embeddings.weight"].data_ptr(), H, S, B, B, 1, H)       # sum over the batch
-    sink.keep(dX1, dE1)
+    if not cut_first:
+        dX1, dk1, dv1 = encoder_kv_bwd(P, G, "transformer", c1, dE1, sink)
+        if table_needed(frozen, "embeddings.weight"):
+            ops.reduce_rows(dX1.data_ptr(), H, G["embeddings.weight"].data_ptr(), H, S, B, B, 1, H)       # sum over the batch
+        sink.keep(dX1, dE1)
     if mid_hook is not None:
         mid_hook(sink)
+    if cut:                  # (frozen trunk: the key / value gradients, dgraph and dx_ext have no consumer)
+        sink.keep(dk3, dv3)
+        sink.flush()
+        return
     ddense = _sum_rows(dev, [dk1, dv1, dk3, dv3], nmax * B, H, sink)
     dxL = _empty(dev, N, H)
     ops.dense_slots_bwd(ddense, m.dense_row, dxL, N, H, False, ghost_row=nmax * B)
@@ -1933,6 +2034,10 @@ def graphnetwork_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, ddo
         raise ValueError("graphnetwork_bwd: factored_head differs from the forward pass that made this context")
     H, N = cfg.H, m.num_nodes
     dgraph = _pair_head_bwd(P, G, cfg, m.num_graphs, a, hid, ddos, sink)
+    if getattr(G, "cut_trunk", False):       # fine-tuning: a frozen trunk ends the program behind the head (trunk_cut)
+        sink.keep(dgraph)
+        sink.flush()
+        return
     dxL = ops.zeros(ddos.device, N, H)
     du_seg = decoder_bwd(P, G, cfg, m, dec_segs, dgraph, dxL, sink)
     if dx_ext is not None:
@@ -1963,6 +2068,10 @@ def mlp_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, ddos: torch.
     if factored_head != (a is None):
         raise ValueError("mlp_bwd: factored_head differs from the forward pass that made this context")
     dgraph = _pair_head_bwd(P, G, cfg, m.num_graphs, a, hid, ddos, sink)
+    if getattr(G, "cut_trunk", False):       # fine-tuning: a frozen trunk ends the program behind the head (trunk_cut)
+        sink.keep(dgraph)
+        sink.flush()
+        return
     dx0 = ops.zeros(ddos.device, m.num_nodes, cfg.H)
     du_seg = decoder_bwd(P, G, cfg, m, dec_segs, dgraph, dx0, sink)
     with ops.graph_rows():

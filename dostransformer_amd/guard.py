@@ -95,10 +95,10 @@ class StepGuard:
         dev = fp.flat.device
         rec, ws = self._guard_buffers(dev)
         self.step_count += 1
-        ops.grad_guard(fp.grad, fp.total, rec, ws, self.max_grad_norm, self.lr, self.betas[0], self.betas[1], self.step_count,
+        ops.grad_guard(fp.grad, fp.n_train, rec, ws, self.max_grad_norm, self.lr, self.betas[0], self.betas[1], self.step_count,
                        self._guard_status)
         fn = ops.adamw_guarded if fp.flat.dtype == torch.float32 else ops.adamw64_guarded
-        fn(fp.flat, fp.grad, m, v, fp.total, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, rec)
+        fn(fp.flat, fp.grad, m, v, fp.n_train, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, rec)
 
     @property
     def grad_norm(self) -> torch.Tensor:

@@ -283,6 +283,23 @@ def _call(name: str, *args, w=None) -> None:
         if w is not None:
             RECORDER.work[len(RECORDER.prog)] = w()
         RECORDER.prog.append((fn, args))
+    if CALL_LOG is not None:
+        CALL_LOG.append(name)
+
+
+CALL_LOG: Optional[list] = None       # a list: receives the name of every libdosx entry point issued (call_log)
+
+
+@contextlib.contextmanager
+def call_log():
+    """Scope whose libdosx calls are listed by name, in issue order: ``with call_log() as names: ...`` (what an eagerly issued
+    or graph-captured step launched: train.Trainer.program_stats; a recorded one has its Program)."""
+    global CALL_LOG
+    before, CALL_LOG = CALL_LOG, []
+    try:
+        yield CALL_LOG
+    finally:
+        CALL_LOG = before
 
 
 def alloc(device, *shape) -> torch.Tensor:
@@ -469,7 +486,8 @@ class AttFwd(NamedTuple):
 
 class AttBwd(NamedTuple):
     """The attention half's backward inside dosx_ffn_bwd (include/dosx.h: DosxFfnBwd.att_*).  partials_q / partials_kv / dkv_cnt
-    are device addresses (the two halves of one partial-row buffer; ops.COUNTERS.take)."""
+    are device addresses (the two halves of one partial-row buffer; ops.COUNTERS.take).  ``dkvhat`` None: the query-only form -
+    no key gradient; ``partials_kv`` / ``dkv_part`` / ``dkv_cnt`` may then be None too (nothing touches them)."""
     x: torch.Tensor
     kvhat: torch.Tensor
     gamma0: torch.Tensor
@@ -478,10 +496,10 @@ class AttBwd(NamedTuple):
     qstats: torch.Tensor
     dxin: torch.Tensor
     partials_q: int
-    partials_kv: int
-    dkv_part: torch.Tensor
-    dkv_cnt: int
-    dkvhat: torch.Tensor
+    partials_kv: Optional[int]
+    dkv_part: Optional[torch.Tensor]
+    dkv_cnt: Optional[int]
+    dkvhat: Optional[torch.Tensor]
     accumulate: int
     Nk: int
     Bk: int
@@ -577,7 +595,8 @@ def ffn_bwd(M: int, H: int, dy: torch.Tensor, h: torch.Tensor, x: torch.Tensor, 
     a = _ffn_bwd_desc(M, H, dy, h, x, stats, gamma, w1, w2, dh, dx, partials, fin, att)
     nk_att = a.att_Nk if att is not None else 0
     _call("dosx_ffn_bwd", C.byref(a), _stream(),
-          w=lambda: (f"ffn_bwd[H{H}{',att' if nk_att else ''}]", "ffn_bwd_kernel", "mfma", 16.0 * M * H * H + 10.0 * M * nk_att * H))
+          w=lambda: (f"ffn_bwd[H{H}{',att' if nk_att else ''}{',q' if att is not None and att.dkvhat is None else ''}]", "ffn_bwd_kernel",
+                     "mfma", 16.0 * M * H * H + (6.0 if att is not None and att.dkvhat is None else 10.0) * M * nk_att * H))
 
 
 def _ffn_bwd_desc(M: int, H: int, dy, h, x, stats, gamma, w1, w2, dh, dx, partials, fin: Optional[Head], att: Optional[AttBwd]):
@@ -604,9 +623,10 @@ def _ffn_bwd_desc(M: int, H: int, dy, h, x, stats, gamma, w1, w2, dh, dx, partia
         a.att_kvhat, a.att_gamma0, a.att_beta0 = att.kvhat.data_ptr(), att.gamma0.data_ptr(), att.beta0.data_ptr()
         a.att_probs, a.att_qstats, a.att_mask = att.probs.data_ptr(), att.qstats.data_ptr(), _p(att.mask)
         a.att_dxin, a.att_lddxin = att.dxin.data_ptr(), int(att.dxin.stride(0))
-        a.att_partials_q, a.att_partials_kv = att.partials_q, att.partials_kv
-        a.att_dkv_part, a.att_dkv_cnt = att.dkv_part.data_ptr(), att.dkv_cnt
-        a.att_dkvhat, a.att_dkv_accumulate = att.dkvhat.data_ptr(), int(att.accumulate)
+        a.att_partials_q = att.partials_q
+        if att.dkvhat is not None:
+            a.att_partials_kv, a.att_dkv_part, a.att_dkv_cnt = att.partials_kv, att.dkv_part.data_ptr(), att.dkv_cnt
+            a.att_dkvhat, a.att_dkv_accumulate = att.dkvhat.data_ptr(), int(att.accumulate)
         a.att_Nk, a.att_Bk, a.att_Bq, a.att_Sq = int(att.Nk), int(att.Bk), int(att.Bq), int(att.Sq)
         a.att_qs, a.att_qb = int(att.qs), int(att.qb)
         if att.key_ptr is not None:
@@ -1071,6 +1091,7 @@ class GradSink:
             self.wside = GradSink._side_streams[k2]
         self._forked = False
         self._wforked = False
+        self.wgrad_keys: List[Optional[str]] = []      # one entry per weight-gradient job deferred to this sink
 
     @staticmethod
     def side_stream(device):
@@ -1085,11 +1106,14 @@ class GradSink:
     # Weight-gradient jobs are collected and issued as ONE grouped launch at the next flush instead of one kernel each on
     # the side stream (interleaved they cost the dgrad chain ~0.45 ms per step of interference: round 1).
 
-    def defer_wgrad(self, desc, keep=()) -> None:
+    def defer_wgrad(self, desc, keep=(), key: Optional[str] = None) -> None:
+        """``key``: the name of the weight the job serves; ``wgrad_keys`` lists them in the order the jobs were described
+        (what a pruned backward program is counted by: train.Trainer.program_stats)."""
         self._keep.extend(keep)
         if not hasattr(self, "_wjobs"):
             self._wjobs = []
         self._wjobs.append(desc)
+        self.wgrad_keys.append(key)
 
     def _take_wjobs(self):
         jobs = getattr(self, "_wjobs", [])

@@ -52,6 +52,9 @@ class _AdamWState(StepGuard):
         ``load_state_dict``, a different dead-parameter set, ...) the moments follow BY NAME instead of being reset:
         ``step_count`` keeps counting, so zeroed moments would silently corrupt the bias correction."""
         if self._fp is not fp:
+            if getattr(self, "dist", None) is not None and fp.n_train != fp.total:
+                raise DosxError(f"{type(self).__name__}(dist=...) with frozen parameters ({len(fp.frozen)} of {len(fp.names)}): "
+                                f"fine-tuning is a single-GPU mode, not with dist (data parallelism)")
             m, v = torch.zeros_like(fp.flat), torch.zeros_like(fp.flat)
             old = self._fp
             if old is not None and self._m is not None:
@@ -74,7 +77,12 @@ class _AdamWState(StepGuard):
     def state_dict(self) -> dict:
         """Optimizer state keyed by the reference's parameter names, in ``torch.optim.AdamW`` vocabulary
         (``exp_avg`` / ``exp_avg_sq`` / ``step``); together with ``model.state_dict()`` (reference key
-        layout) this is a complete resume point."""
+        layout) this is a complete resume point.  Every live parameter has an entry, frozen ones included (their
+        moments are whatever they were when they were frozen: zero if they never trained), so a file loads into a trainer with
+        another frozen set, by name; with anything frozen, ``trainable`` lists the names that were training (no such key: all).
+
+        The trainer keeps ONE ``step`` for all parameters: a parameter unfrozen in the middle of a run starts from zero moments
+        under the run's bias correction, where ``torch.optim.AdamW`` would start a step count of its own for it."""
         fp = self._fp if self._fp is not None else self.model.flat_params()
         m, v = self._state(fp)
         views = lambda buf: {n: buf[o:o + fp.P[n].numel()].view(fp.P[n].shape).detach().cpu().clone()
@@ -82,9 +90,12 @@ class _AdamWState(StepGuard):
         # the dropout seed is stored WITHOUT the saving rank's offset (rank-independent base + steps taken): every rank of a
         # resumed data-parallel job re-applies its own offset and goes on drawing the masks its uninterrupted self would have
         seed = getattr(self.model, "_drop_seed", None)
-        return {"step": self._applied_steps(), "exp_avg": views(m), "exp_avg_sq": views(v),
-                "drop_seed_base": None if seed is None else (int(seed.item()) - rank_seed_offset()) % _SEED_MOD,
-                "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "beta": self.beta}}
+        sd = {"step": self._applied_steps(), "exp_avg": views(m), "exp_avg_sq": views(v),
+              "drop_seed_base": None if seed is None else (int(seed.item()) - rank_seed_offset()) % _SEED_MOD,
+              "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "beta": self.beta}}
+        if fp.frozen:                      # (an all-trainable run writes the file it always wrote: no key = every name trains)
+            sd["trainable"] = fp.trainable_names()
+        return sd
 
     def load_state_dict(self, sd: dict) -> None:
         fp = self._fp if self._fp is not None else self.model.flat_params()
@@ -117,7 +128,14 @@ class _AdamWState(StepGuard):
 
         A guarded trainer (``max_grad_norm`` / ``skip_nonfinite``) also raises when steps were skipped since the last check,
         naming the first one and the parameter whose gradient was not finite; by then ``step_count`` is the applied count, the
-        guard's counts are zeroed and the slots dropped, so the process can go on."""
+        guard's counts are zeroed and the slots dropped, so the process can go on.
+
+        Also raises when the model's ``requires_grad`` flags no longer match the snapshot the flat buffer was laid out from
+        (``FusedModel.update_trainable()`` is the missing call)."""
+        if self.model.trainable_stale():
+            raise DosxError(f"{type(self.model).__name__}: requires_grad changed since the flat parameters were laid out, and the "
+                            f"steps since then trained the earlier set - call model.update_trainable() after changing the flags "
+                            f"(model.freeze() / model.train_only() do)")
         dev = self.model._module_device()
         if dev.type != "cuda":
             return
@@ -174,6 +192,15 @@ class Trainer(_AdamWState, SlotCache):
     verdict, no host read.  A step whose gradient holds a NaN / inf (or that follows a reported exchange stall) leaves
     parameters and moments untouched and does not advance AdamW's time; ``grad_norm`` / ``guard_report()`` say what happened,
     ``check()`` raises.  Every mode; not under data parallelism.  Off by default: the step then issues exactly the launches it issued without these arguments.
+
+    Fine-tuning: ``requires_grad`` decides which parameters train (``model.freeze(...)`` / ``model.train_only(...)``, or the flags
+    themselves followed by ``model.update_trainable()``).  A frozen parameter and its two moments are bitwise untouched by a step,
+    weight decay included - torch's behaviour for ``grad is None`` - and the guard's norm covers the trainable gradient only.  The
+    flags are read when the flat buffer is laid out, never per step; the backward program drops the weight-gradient jobs of frozen
+    Linears, ends in front of a frozen GNN trunk (and a frozen first encoder), and runs a cross attention over frozen keys without
+    its key gradient (functional.wgrad_needed / trunk_cut / first_encoder_cut / attention_query_only); ``program_stats()`` shows
+    what is left.  Every model and mode; not under data parallelism.  With nothing frozen the layout, the launches and the bits
+    are what they were.
     """
 
     def __init__(self, model: DOSTransformerBase, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2,
@@ -197,6 +224,9 @@ class Trainer(_AdamWState, SlotCache):
                 raise DosxError(f"Trainer({name}, dist=...): data parallelism is not implemented for the GNN-only baselines")
         if per_crystal_keys and dist is not None:
             raise DosxError("Trainer(per_crystal_keys=True) is a single-GPU mode: not with dist (data parallelism)")
+        if dist is not None and len(model.trainable_names()) != len(model._live_named()):
+            raise DosxError("Trainer(dist=...) with frozen parameters: fine-tuning is a single-GPU mode, not with dist (data "
+                            "parallelism)")
         self._per_crystal_keys = bool(per_crystal_keys)
         self._init_guard("Trainer", max_grad_norm, skip_nonfinite, dist)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, betas, eps
@@ -283,6 +313,7 @@ class Trainer(_AdamWState, SlotCache):
         sink = ops.GradSink(dev)
         sink.gnn_hook = self._gnn_hook(fp)          # (functional.gnn_bwd calls it behind the flush that completes layers L-1 .. 1)
         Fn.dostransformer_bwd(fp.P, fp.G, cfg, m, st["ctx"], ddos, None, sink, mid_hook=self._mid_hook(fp))
+        self._wgrad_keys = sink.wgrad_keys
         sink.release()
         return loss
 
@@ -306,6 +337,7 @@ class Trainer(_AdamWState, SlotCache):
             loss = lp[B]
         sink = ops.GradSink(dev)
         self.model._bwd_fn(fp.P, fp.G, self.model._cfg, m, st["ctx"], ddos, None, sink, factored_head=True)
+        self._wgrad_keys = sink.wgrad_keys
         sink.release()
         return loss
 
@@ -399,12 +431,14 @@ class Trainer(_AdamWState, SlotCache):
         self._state(fp)
         m = graph_meta(g, dev)
         ng = self._n_global(m.num_graphs, n_global, g)
-        with torch.no_grad():
+        with torch.no_grad(), ops.call_log() as names:
             st = self._part_a(fp, g, m, ng)
             self.last_outputs = st["out"]
             if self.kind == "phonon" and self.dist is not None:
                 self.dist.all_reduce_sse(st["sse"])
-            return self._part_b(fp, m, st, ng)
+            loss = self._part_b(fp, m, st, ng)
+        self._stats = self._make_stats(names)
+        return loss
 
     # ---- graph path ------------------------------------------------------------------------------
     def _capture(self, slot: Slot, fp, ng: int) -> None:
@@ -419,14 +453,16 @@ class Trainer(_AdamWState, SlotCache):
             torch.cuda.current_stream().wait_stream(side)
             torch.cuda.synchronize()
             slot.graph_a = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(slot.graph_a):
-                st = self._part_a(fp, g, m, ng)
-                if not split:
-                    loss = self._part_b(fp, m, st, ng)
-            if split:
-                slot.graph_b = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(slot.graph_b, pool=slot.graph_a.pool()):
-                    loss = self._part_b(fp, m, st, ng)
+            with ops.call_log() as names:
+                with torch.cuda.graph(slot.graph_a):
+                    st = self._part_a(fp, g, m, ng)
+                    if not split:
+                        loss = self._part_b(fp, m, st, ng)
+                if split:
+                    slot.graph_b = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(slot.graph_b, pool=slot.graph_a.pool()):
+                        loss = self._part_b(fp, m, st, ng)
+        slot.stats = self._make_stats(names)
         slot.keep = (st, loss)            # keeps the graph-owned outputs from being recycled
         slot.loss, slot.out, slot.sse = loss, st["out"], st.get("sse")
 
@@ -455,6 +491,7 @@ class Trainer(_AdamWState, SlotCache):
             plan.append(("prog", last))
             self._rec_parts = []
         slot.plan, slot.prog = plan, plan[0][1]
+        slot.stats = self._make_stats([fn.__name__ for kind, prog in plan if kind == "prog" for fn, _ in prog.prog])
         slot.keep = (st, loss)
         slot.loss, slot.out, slot.sse = loss, st["out"], st.get("sse")
 
@@ -462,10 +499,11 @@ class Trainer(_AdamWState, SlotCache):
         """The step on a bucket whose static buffers hold the batch: record / capture on first use, replay afterwards."""
         if fresh and self.replay:
             self._record(slot, fp, ng)       # this IS the step for this batch (run + record)
-            self.last_outputs = slot.out
+            self.last_outputs, self._stats = slot.out, slot.stats
             return slot.loss
         if fresh:
             self._capture(slot, fp, ng)
+        self._stats = getattr(slot, "stats", None)
         if self.replay:
             for kind, prog in slot.plan:
                 if kind == "prog":
@@ -567,6 +605,24 @@ class Trainer(_AdamWState, SlotCache):
         self.optimizer_step()
         return loss
 
+    # ---- what the step launched ------------------------------------------------------------------
+    def _make_stats(self, entries) -> dict:
+        entries = list(entries)
+        keys = list(getattr(self, "_wgrad_keys", ()))
+        return {"launches": sum(1 for e in entries if e.startswith("dosx_")), "wgrad_jobs": len(keys), "entries": entries,
+                "wgrad_keys": keys}
+
+    def program_stats(self) -> dict:
+        """What the last step's program (forward, loss, backward; not the optimizer) consisted of - of the recording when the step
+        was replayed, of the capture when it ran from HIP graphs, else of the eagerly issued step itself: ``entries`` the names
+        of its entries in issue order (a recorded program's ``Program.prog``: libdosx entry points plus the stream fork / join
+        operations), ``launches`` how many of them are libdosx calls, ``wgrad_jobs`` how many weight-gradient jobs the backward
+        deferred to its GradSink and ``wgrad_keys`` the weight each of them serves.  What a frozen set pruned shows here."""
+        st = getattr(self, "_stats", None)
+        if st is None:
+            raise DosxError("program_stats: no step has run yet")
+        return dict(st)
+
     # ---- optimizer -------------------------------------------------------------------------------
     def optimizer_step(self) -> None:
         fp = self._fp if self._fp is not None else self.model.flat_params()
@@ -587,8 +643,9 @@ class Trainer(_AdamWState, SlotCache):
                 assert self._mid_work is None
                 self.dist.all_reduce_grads(fp.grad)
         self.step_count += 1
-        ops.adamw(fp.flat, fp.grad, m, v, fp.total, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                  self.step_count, 1.0)
+        if fp.n_train:                                # (flat[n_train:] are the frozen parameters: nothing steps them)
+            ops.adamw(fp.flat, fp.grad, m, v, fp.n_train, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
+                      self.step_count, 1.0)
 
     def step(self, g, n_global: Optional[int] = None) -> torch.Tensor:
         self._bump_dropout_seed()

@@ -216,7 +216,8 @@ class Trainer64(_AdamWState, SlotCache):
         if self.guarded:
             return self._guarded_optimizer_step(fp, m, v)
         self.step_count += 1
-        ops.adamw64(fp.flat, fp.grad, m, v, fp.total, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count)
+        if fp.n_train:
+            ops.adamw64(fp.flat, fp.grad, m, v, fp.n_train, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count)
 
     def step(self, g) -> torch.Tensor:
         self._refuse(g)

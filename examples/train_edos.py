@@ -17,6 +17,12 @@ Predictor: their output head runs on its rank structure, the loss is the driver'
 through evaluate.test_per_crystal (these models have no attention: batched passes ARE the batch-size-1 numbers).
 
     python examples/train_edos.py --embedder graphnetwork --epochs 10
+
+Fine-tuning: --init CKPT loads a trained model (the optimizer starts fresh), --train-only / --freeze take parameter-name
+prefixes (FusedModel.train_only / freeze; the prompt table of this model is spelt `promt_token`, as upstream).  Frozen
+parameters are bitwise untouched - no weight decay either - and the backward program drops what only they needed.
+
+    python examples/train_edos.py --init edos_best.pt --train-only promt_token fc_prompt --epochs 20 --out edos_ft.pt
 """
 import argparse
 import os
@@ -72,6 +78,12 @@ def parse_args(argv=None):
                          "non-finite gradient are skipped")
     ap.add_argument("--skip-nonfinite", action="store_true",
                     help="skip a step whose gradient holds a NaN / inf instead of writing it into the parameters")
+    ap.add_argument("--init", default=None, metavar="CKPT",
+                    help="fine-tuning: load the model from this checkpoint (checkpoint.save's file or a bare state_dict); the optimizer starts fresh")
+    ap.add_argument("--train-only", nargs="+", default=None, metavar="PREFIX",
+                    help="fine-tuning: train exactly the parameters whose names start with one of these prefixes, freeze the rest")
+    ap.add_argument("--freeze", nargs="+", default=None, metavar="PREFIX",
+                    help="fine-tuning: freeze the parameters whose names start with one of these prefixes")
     return ap.parse_args(argv)
 
 
@@ -121,6 +133,17 @@ def _main(argv=None):
         model = mlp(args.layers, n_atom, n_bond, 2, args.hidden, 201, dev).to(dev)
     else:
         model = DOSTransformer(args.layers, args.transformer, n_atom, n_bond, 2, args.hidden, dev, args.attn_drop).to(dev)
+    # fine-tuning: the model from a checkpoint (a fresh optimizer), then the frozen set - the trainer reads requires_grad
+    if args.init:
+        checkpoint.load(args.init, model)
+    if args.train_only:
+        model.train_only(*args.train_only)
+    if args.freeze:
+        model.freeze(*args.freeze)
+    if args.train_only or args.freeze:
+        names = set(model.trainable_names())
+        print(f"fine-tuning: {len(names)} parameter tensors ({sum(p.numel() for k, p in model.named_parameters() if k in names)} "
+              f"elements) train, the rest is frozen")
     if baseline and (args.per_crystal_keys or args.beta != 1.0):
         raise SystemExit(f"--embedder {args.embedder} has one output and no attention: --beta and --per-crystal-keys do not apply")
     # coarse shape buckets: reshuffled batches fall into a few dozen (N, E) buckets, each recorded once (ghost padding is

@@ -33,6 +33,13 @@ loss on its one output, loss.backward(), torch.optim.AdamW.  With --fused the sa
 bucket and evaluation through predict.Predictor64.
 
     python examples/train_phonon.py --embedder graphnetwork --float64 --fused --replay --epochs 2 --crystals 128 --hidden 64
+
+Fine-tuning: --init CKPT loads a trained model (the optimizer starts fresh), --train-only / --freeze take parameter-name
+prefixes (FusedModel.train_only / freeze).  Frozen parameters are bitwise untouched - no weight decay either - and the backward
+program drops what only they needed: with the GNN trunk frozen it ends behind the first encoder.  Every mode above takes them.
+
+    python examples/train_phonon.py --init phonon_best.pt --train-only prompt_token fc_prompt --epochs 2 --out phonon_ft.pt
+    python examples/train_phonon.py --init phonon_best.pt --freeze GN_encoder stacked_processor GN_decoder --epochs 2
 """
 import argparse
 import os
@@ -92,6 +99,12 @@ def _main(argv=None):
                          "steps with a non-finite gradient are skipped")
     ap.add_argument("--skip-nonfinite", action="store_true",
                     help="fused trainers: skip a step whose gradient holds a NaN / inf instead of writing it into the parameters")
+    ap.add_argument("--init", default=None, metavar="CKPT",
+                    help="fine-tuning: load the model from this checkpoint (checkpoint.save's file or a bare state_dict); the optimizer starts fresh")
+    ap.add_argument("--train-only", nargs="+", default=None, metavar="PREFIX",
+                    help="fine-tuning: train exactly the parameters whose names start with one of these prefixes, freeze the rest")
+    ap.add_argument("--freeze", nargs="+", default=None, metavar="PREFIX",
+                    help="fine-tuning: freeze the parameters whose names start with one of these prefixes")
     args = ap.parse_args(argv)
     if (args.clip_grad_norm is not None or args.skip_nonfinite) and args.float64 and not args.fused:
         ap.error("--clip-grad-norm / --skip-nonfinite belong to the fused trainers: the fp32 run, or --float64 --fused")
@@ -129,6 +142,7 @@ def _main(argv=None):
             args.eval_per_crystal = args.batch_size      # (its predictor returns one DOS: the per-crystal evaluator reads it)
     else:
         model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).to(dev)
+    _fine_tune(args, model)
     # coarse shape buckets: reshuffled batches then fall into a few dozen (N, E, n_max) buckets that are all recorded
     # within the first epoch (ghost padding is exact; it costs a few per cent of extra rows)
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=(32, 1024), promote=0.08,
@@ -157,6 +171,23 @@ def _main(argv=None):
     return {"best_valid_rmse": best, "train_loss": history}
 
 
+def _fine_tune(args, model):
+    """--init / --train-only / --freeze: the model from a checkpoint (no optimizer state: a fresh one), then the frozen set.
+    ``requires_grad`` is what every driver reads - the fused trainers through the flat layout, torch.optim.AdamW through
+    ``grad is None``."""
+    if args.init:
+        checkpoint.load(args.init, model)
+    if args.train_only:
+        model.train_only(*args.train_only)
+    if args.freeze:
+        model.freeze(*args.freeze)
+    if args.train_only or args.freeze:
+        names = model.trainable_names()
+        n = sum(p.numel() for k, p in model.named_parameters() if k in set(names))
+        print(f"fine-tuning: {len(names)} parameter tensors ({n} elements) train, the rest is frozen")
+    return model
+
+
 def _tester(args, evaluator, ds):
     """name of a split -> (rmse, mse, mae, r2).  --eval-per-crystal N: the reference's numbers (main_phDOS.py:52-55 evaluates at
     batch size 1) from passes of N crystals through a predictor with per-crystal keys; otherwise test_phonon over batches of
@@ -181,6 +212,7 @@ def train_float64(args, ds, dev):
     else:
         model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).double()
         model = model.set_program_dtype(torch.float64).set_per_crystal_keys(True).to(dev)
+    _fine_tune(args, model)
     opt = torch.optim.AdamW(model.parameters(), lr=args.lr, weight_decay=1e-2)       # main_phDOS.py:92
     best, history = float("inf"), []
     for epoch in range(args.epochs):
@@ -249,11 +281,12 @@ def train_float64_fused(args, ds, dev):
     bucket = (32, 1024)
     slots = dict(replay=args.replay, bucket=bucket if args.replay else None, promote=0.08 if args.replay else 0.0)
     if args.embedder == "graphnetwork":
-        model = _baseline64(args, dev)
+        model = _fine_tune(args, _baseline64(args, dev))
         trainer = GraphnetworkTrainer64(model, lr=args.lr, **slots, **_guard_args(args))
     else:
         model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).double()
         model = model.set_program_dtype(torch.float64).set_per_crystal_keys(True).to(dev)
+        _fine_tune(args, model)
         trainer = Trainer64(model, lr=args.lr, beta=args.beta, **slots, **_guard_args(args))
     evaluator = Predictor64(model, bucket=bucket) if args.replay else model       # (the module's per-crystal keys are on)
     run_test = _tester(args, evaluator, ds)

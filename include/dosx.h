@@ -377,7 +377,10 @@ int dosx_layernorm_bwd(const float* dy, const float* xhat, const float* rstd, co
  *  through one-wave-per-row kernels with the same results contract (csrc/attention_general.hip; they need `dscores`). */
 /* BWD_*_HALF: the two-kernel form of dosx_attention_bwd (dq half: needs dout,P -> dx,dS ; dkv half: needs dS -> dkvhat) issued
  * as TWO calls - one with DOSX_ATTN_BWD_DQ_HALF, one with DOSX_ATTN_BWD_DKV_HALF, e.g. the dkv half on a second stream (only the
- * final key-gradient consumers need it).  A caller that sets one flag owes the other call: together they are the whole backward. */
+ * final key-gradient consumers need it).  A caller that sets one flag owes the other call: together they are the whole backward.
+ * The exception: DOSX_ATTN_BWD_DQ_HALF with dkvhat == NULL is a COMPLETE call, the query-only backward for keys that come from
+ * frozen parameters - dx and partials_q are the whole backward's, bit for bit, no key gradient exists and no DKV half follows;
+ * dkv_part / dkv_cnt / partials_kv may be NULL, dscores too where Nk <= 64 routes to the crystal-aligned kernel. */
 enum { DOSX_ATTN_RAW_Q = 1, DOSX_ATTN_NO_RESIDUAL = 2, DOSX_ATTN_BWD_DKV_HALF = 4, DOSX_ATTN_BWD_DQ_HALF = 8 };
 typedef struct DosxAttn {
   int32_t Sq, Bq, Nk, Bk, H;
@@ -601,7 +604,10 @@ typedef struct DosxFfnBwd {
    *   by the forward; att_kvhat [Nk * Bk, H]: the pre-normalised keys; att_dxin [M, att_lddxin]: gradient w.r.t. the layer input;
    *   att_partials_q [Bq * tiles, 2H], att_partials_kv [Bk * ceil(Nk / 16), 2H], att_dkv_part [Bq * tiles * Nk, H] scratch,
    *   att_dkv_cnt [Bk] arrival counters (zero before and after), att_dkvhat (+)= the key gradient (att_dkv_accumulate)
-   * - the fields of DosxAttn with the same names, same layouts (32-query tiles), same summation orders. */
+   * - the fields of DosxAttn with the same names, same layouts (32-query tiles), same summation orders.
+   *   att_dkvhat == NULL selects the QUERY-ONLY form, for keys that come from frozen parameters: no key gradient is computed,
+   *   att_dkv_part / att_dkv_cnt / att_partials_kv are not touched and may be NULL too; dh, att_dxin, every column of `partials`
+   *   and att_partials_q are bitwise the full form's. */
   const float* att_x; int32_t att_ldxin;
   const float* att_kvhat; const float* att_gamma0; const float* att_beta0;
   const float* att_probs; const float* att_qstats; const float* att_mask;
