@@ -121,7 +121,115 @@ __global__ __launch_bounds__(ADAMW64_THREADS) void adamw_guarded_f64_kernel(doub
   }
 }
 
+// adamw_f64_kernel / adamw_guarded_f64_kernel with parameter groups (include/dosx.h: DosxAdamWGroups): adamw64_one with decay and
+// step_size looked up per 64-element chunk.  The table arrives by value and is only ever indexed by constants: the first
+// DOSX_ADAMW_MAX_GROUPS lanes of a workgroup stage one {decay, step_size} pair each into LDS, once, behind one barrier (a double2
+// never straddles a chunk: 32 neighbouring lanes share the byte and the pair).  GUARDED: skip / clip / bc2_scale from the record;
+// rec->t == step: the host's step_size_k, else lr_k / (1 - beta1^t) by grad_guard_kernel's expression.
+struct AdamW64GroupTable {
+  double decay[DOSX_ADAMW_MAX_GROUPS], step_size[DOSX_ADAMW_MAX_GROUPS], lr[DOSX_ADAMW_MAX_GROUPS];
+  int n_groups;
+};
+
+template <bool GUARDED>
+__global__ __launch_bounds__(ADAMW64_THREADS) void adamw_grouped_f64_kernel(double* __restrict__ p, const double* __restrict__ g,
+                                                                            double* __restrict__ m, double* __restrict__ v, size_t n,
+                                                                            const uint8_t* __restrict__ chunk_group,
+                                                                            const AdamW64GroupTable tab, double beta1, double omb1,
+                                                                            double b2, double omb2, double eps, double bc2_sqrt,
+                                                                            int step, const DosxStepGuard* __restrict__ rec) {
+  __shared__ double2 s_tab[DOSX_ADAMW_MAX_GROUPS];
+  bool host_step = true;
+  int t = step;
+  double clip = 1.0;
+  if constexpr (GUARDED) {
+    if (rec->skip != 0) return;
+    clip = rec->clip;
+    bc2_sqrt = rec->bc2_scale;
+    t = rec->t;
+    host_step = t == step || t < 1;
+  }
+  const int lane = (int)threadIdx.x;
+  if (lane < DOSX_ADAMW_MAX_GROUPS) {
+    double d = 0.0, s = 0.0, lr = 0.0;
+#pragma unroll
+    for (int k = 0; k < DOSX_ADAMW_MAX_GROUPS; ++k)
+      if (lane == k) { d = tab.decay[k]; s = tab.step_size[k]; lr = tab.lr[k]; }
+    if constexpr (GUARDED) {
+      if (!host_step) {
+        const double bc1 = 1.0 - pow(beta1, (double)t);
+        s = lr / bc1;
+      }
+    }
+    s_tab[lane] = make_double2(d, s);
+  }
+  __syncthreads();
+  const unsigned n_groups = (unsigned)tab.n_groups;
+  const size_t n2 = n >> 1;
+  double2* p2 = reinterpret_cast<double2*>(p);
+  const double2* g2 = reinterpret_cast<const double2*>(g);
+  double2* m2 = reinterpret_cast<double2*>(m);
+  double2* v2 = reinterpret_cast<double2*>(v);
+  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (size_t i = tid; i < n2; i += (size_t)gridDim.x * blockDim.x) {
+    unsigned k = chunk_group[i >> 5];                    // 32 double2 per 64-element chunk
+    if (k >= n_groups) k = 0;
+    const double2 ds = s_tab[k];
+    double2 pp = p2[i], mm = m2[i], vv = v2[i];
+    const double2 gg = g2[i];
+    if constexpr (GUARDED) {
+      adamw64_one(pp.x, gg.x * clip, mm.x, vv.x, ds.x, omb1, b2, omb2, eps, ds.y, bc2_sqrt);
+      adamw64_one(pp.y, gg.y * clip, mm.y, vv.y, ds.x, omb1, b2, omb2, eps, ds.y, bc2_sqrt);
+    } else {
+      adamw64_one(pp.x, gg.x, mm.x, vv.x, ds.x, omb1, b2, omb2, eps, ds.y, bc2_sqrt);
+      adamw64_one(pp.y, gg.y, mm.y, vv.y, ds.x, omb1, b2, omb2, eps, ds.y, bc2_sqrt);
+    }
+    p2[i] = pp; m2[i] = mm; v2[i] = vv;
+  }
+}
+
+// the host half of both grouped float64 entries: dosx_adamw_f64's expressions, once per group
+template <bool GUARDED>
+int adamw_grouped_f64_launch(const char* who, double* p, const double* g, double* m, double* v, int64_t n, const void* chunk_group,
+                             const DosxAdamWGroups* groups, double beta1, double beta2, double eps, int step, const void* guard,
+                             dosx_stream_t stream) {
+  if (int rc = dosx_adamw_grouped_check(who, p, g, m, v, n, chunk_group, groups, step, GUARDED, guard)) return rc;
+  if (n == 0) return 0;
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  AdamW64GroupTable tab = {};
+  tab.n_groups = groups->n_groups;
+  for (int k = 0; k < groups->n_groups; ++k) {
+    const double lr = groups->lr[k], weight_decay = groups->weight_decay[k];
+    tab.lr[k] = lr;
+    tab.step_size[k] = lr / bc1;
+    tab.decay[k] = 1.0 - lr * weight_decay;
+  }
+  size_t wgs = ((size_t)n / 2 + ADAMW64_THREADS - 1) / ADAMW64_THREADS;      // dosx_adamw_f64's grid
+  if (wgs > (size_t)ADAMW64_MAX_WGS) wgs = ADAMW64_MAX_WGS;
+  if (wgs < 1) wgs = 1;
+  hipLaunchKernelGGL(adamw_grouped_f64_kernel<GUARDED>, dim3((unsigned)wgs), dim3(ADAMW64_THREADS), 0, to_stream(stream), p, g, m, v,
+                     (size_t)n, static_cast<const uint8_t*>(chunk_group), tab, beta1, 1.0 - beta1, beta2, 1.0 - beta2, eps, sqrt(bc2),
+                     step, static_cast<const DosxStepGuard*>(guard));
+  DOSX_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace
+
+extern "C" int dosx_adamw_grouped_f64(double* p, const double* g, double* m, double* v, int64_t n, const void* chunk_group,
+                                      const DosxAdamWGroups* groups, double beta1, double beta2, double eps, int step,
+                                      dosx_stream_t stream) {
+  return adamw_grouped_f64_launch<false>("dosx_adamw_grouped_f64", p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step,
+                                         nullptr, stream);
+}
+
+extern "C" int dosx_adamw_grouped_guarded_f64(double* p, const double* g, double* m, double* v, int64_t n, const void* chunk_group,
+                                              const DosxAdamWGroups* groups, double beta1, double beta2, double eps, int step,
+                                              const void* guard, dosx_stream_t stream) {
+  return adamw_grouped_f64_launch<true>("dosx_adamw_grouped_guarded_f64", p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step,
+                                        guard, stream);
+}
 
 extern "C" int dosx_loss_phonon_f64(const double* pg, const double* ps, const double* y, double beta, double* dpg, double* dps,
                                     double* loss, double* sse, int count, dosx_stream_t stream) {

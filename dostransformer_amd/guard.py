@@ -97,6 +97,8 @@ class StepGuard:
         self.step_count += 1
         ops.grad_guard(fp.grad, fp.n_train, rec, ws, self.max_grad_norm, self.lr, self.betas[0], self.betas[1], self.step_count,
                        self._guard_status)
+        if getattr(self, "_groups", None) is not None:      # parameter groups: the per-group step sizes are not the record's
+            return self._grouped_optimizer_step(fp, m, v, rec) if fp.n_train else None
         fn = ops.adamw_guarded if fp.flat.dtype == torch.float32 else ops.adamw64_guarded
         fn(fp.flat, fp.grad, m, v, fp.n_train, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, rec)
 

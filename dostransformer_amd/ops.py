@@ -1732,6 +1732,60 @@ def adamw_guarded(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, rec):
           w=lambda: ("adamw_guarded", "adamw_guarded_kernel", "hbm", 28.0 * n))
 
 
+# ---- AdamW with parameter groups (include/dosx.h: DosxAdamWGroups; the host side is param_groups.py) ---------------------------
+def adamw_groups(groups, into: "Optional[_abi.AdamWGroups]" = None) -> "_abi.AdamWGroups":
+    """The host struct of the grouped launches from ``(lr, weight_decay)`` pairs, one per group (a struct is passed through)."""
+    if isinstance(groups, _abi.AdamWGroups):
+        return groups
+    groups = list(groups)
+    if not 1 <= len(groups) <= _abi.DOSX_ADAMW_MAX_GROUPS:
+        raise ValueError(f"adamw_groups: 1 to {_abi.DOSX_ADAMW_MAX_GROUPS} groups, got {len(groups)}")
+    st = into if into is not None else _abi.AdamWGroups()
+    st.n_groups = len(groups)
+    for k, (lr, wd) in enumerate(groups):
+        st.lr[k], st.weight_decay[k] = float(lr), float(wd)
+    return st
+
+
+def _chk_grouped(who: str, dtype, p, g, m, v, n: int, chunk_group) -> int:
+    """The operands of a grouped AdamW launch: four flat CUDA buffers of ``dtype`` with at least n elements and a uint8 chunk
+    map with at least n / 64 entries on their device - what the kernel indexes, checked here because the C entry cannot."""
+    n = int(n)
+    for t in (p, g, m, v):
+        if t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+            raise TypeError(f"{who}: contiguous {dtype} CUDA buffers, got {t.dtype} on {t.device}")
+    if not 0 <= n <= min(p.numel(), g.numel(), m.numel(), v.numel()):
+        raise ValueError(f"{who}: n = {n} of buffers with {p.numel()}, {g.numel()}, {m.numel()}, {v.numel()} elements")
+    if n % _abi.DOSX_ADAMW_GROUP_CHUNK:
+        raise ValueError(f"{who}: n = {n} is not a multiple of {_abi.DOSX_ADAMW_GROUP_CHUNK}")
+    if chunk_group.dtype != torch.uint8 or chunk_group.device != p.device or not chunk_group.is_contiguous() or \
+            chunk_group.numel() < n // _abi.DOSX_ADAMW_GROUP_CHUNK:
+        raise ValueError(f"{who}: the chunk map must be a contiguous uint8 tensor of at least {n // _abi.DOSX_ADAMW_GROUP_CHUNK} "
+                         f"entries on {p.device}, got {chunk_group.dtype} x {chunk_group.numel()} on {chunk_group.device}")
+    return n
+
+
+def adamw_grouped(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, grad_scale=1.0):
+    """:func:`adamw` with parameter groups: ``chunk_group[c]`` names the group of the elements [64c, 64c + 64), ``groups`` is
+    ``(lr, weight_decay)`` per group (or the struct of :func:`adamw_groups`).  Bit for bit :func:`adamw` on every run of chunks
+    of one group with that group's values."""
+    n = _chk_grouped("adamw_grouped", torch.float32, p, g, m, v, n, chunk_group)
+    st = adamw_groups(groups)
+    _call("dosx_adamw_grouped", _p(p), _p(g), _p(m), _p(v), n, chunk_group.data_ptr(), C.byref(st), float(beta1), float(beta2),
+          float(eps), int(step), float(grad_scale), _stream(),
+          w=lambda: ("adamw_grouped", "adamw_grouped_kernel", "hbm", 28.0 * n + n / 64.0))
+
+
+def adamw_grouped_guarded(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, rec):
+    """:func:`adamw_grouped` behind :func:`grad_guard`: skip, clip and bc2_scale come from the record, the step size of group k
+    is what the record would hold had the guard been called with ``lr_k``.  ``step``: the attempt count the guard was given."""
+    n = _chk_grouped("adamw_grouped_guarded", torch.float32, p, g, m, v, n, chunk_group)
+    st = adamw_groups(groups)
+    _call("dosx_adamw_grouped_guarded", _p(p), _p(g), _p(m), _p(v), n, chunk_group.data_ptr(), C.byref(st), float(beta1),
+          float(beta2), float(eps), int(step), rec.data_ptr(), _stream(),
+          w=lambda: ("adamw_grouped_guarded", "adamw_grouped_kernel", "hbm", 28.0 * n + n / 64.0))
+
+
 def dropout_mask(mask: torch.Tensor, p: float, seed_dev: torch.Tensor, stream_id: int) -> None:
     """mask <- {0, 1/(1-p)} multipliers (include/dosx.h: dosx_dropout_mask); seed_dev: 1-element int64 device tensor."""
     assert mask.dtype == torch.float32 and mask.is_contiguous() and seed_dev.dtype == torch.int64 and seed_dev.is_cuda
@@ -2174,6 +2228,25 @@ def adamw64_guarded(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.
     _call("dosx_adamw_guarded_f64", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), int(n), float(lr), float(beta1),
           float(beta2), float(eps), float(weight_decay), rec.data_ptr(), _stream(),
           w=lambda: ("adamw_guarded_f64", "adamw_guarded_f64_kernel", "hbm", 56.0 * n))
+
+
+def adamw64_grouped(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step) -> None:
+    """:func:`adamw64` with parameter groups (see :func:`adamw_grouped`): bit for bit :func:`adamw64` on every run of chunks of
+    one group with that group's ``(lr, weight_decay)``."""
+    n = _chk_grouped("adamw64_grouped", torch.float64, p, g, m, v, n, chunk_group)
+    st = adamw_groups(groups)
+    _call("dosx_adamw_grouped_f64", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, chunk_group.data_ptr(), C.byref(st),
+          float(beta1), float(beta2), float(eps), int(step), _stream(),
+          w=lambda: ("adamw_grouped_f64", "adamw_grouped_f64_kernel", "hbm", 56.0 * n + n / 64.0))
+
+
+def adamw64_grouped_guarded(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, rec) -> None:
+    """:func:`adamw64_grouped` behind :func:`grad_guard` (see :func:`adamw_grouped_guarded`)."""
+    n = _chk_grouped("adamw64_grouped_guarded", torch.float64, p, g, m, v, n, chunk_group)
+    st = adamw_groups(groups)
+    _call("dosx_adamw_grouped_guarded_f64", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, chunk_group.data_ptr(),
+          C.byref(st), float(beta1), float(beta2), float(eps), int(step), rec.data_ptr(), _stream(),
+          w=lambda: ("adamw_grouped_guarded_f64", "adamw_grouped_f64_kernel", "hbm", 56.0 * n + n / 64.0))
 
 
 # float64 pair head of Graphnetwork_phonon (csrc/pair_head_f64.hip), used by functional64's factored program

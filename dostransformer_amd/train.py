@@ -22,8 +22,10 @@ from typing import Optional
 
 import torch
 
+from . import _abi
 from . import functional as Fn
 from . import ops
+from . import param_groups as _pg
 from ._lib import DosxError, from_environ
 from ._models import DOSTransformerBase, GraphnetworkBase, _SEED_MOD, rank_seed_offset
 from .batch import CrystalBatch, bucket_sizes, graph_meta, pad_batch
@@ -71,7 +73,42 @@ class _AdamWState(StepGuard):
                         v[o:o + k].copy_(self._v[oo:oo + k])
             self._m, self._v, self._fp = m, v, fp
             self._slots = OrderedDict()
+            if self._groups is not None:       # the chunk map belongs to the layout: rebuilt wherever the moments are re-homed
+                self._chunk_group = _pg.chunk_map(fp, _pg.assignment(self._groups)).to(fp.flat.device)
         return self._m, self._v
+
+    # ---- parameter groups (param_groups.py; include/dosx.h: DosxAdamWGroups) -------------------------------------------
+    _groups = None                    # None: one lr / weight_decay, the ungrouped launch; else [{"lr", "weight_decay", "names"}]
+    _chunk_group = None               # uint8 device tensor, one entry per 64 elements of flat[:n_train], of the layout in _fp
+    _groups_host = None               # the kernel's host struct, filled from _groups at every optimizer step
+
+    def _init_param_groups(self, who: str, groups, dist=None) -> None:
+        """``param_groups=`` of a trainer's constructor; call it once ``model``, ``lr`` and ``wd`` are set."""
+        self._groups = self._chunk_group = self._groups_host = None
+        if groups is None:
+            return
+        if dist is not None:
+            raise DosxError(f"{who}(param_groups=...) is a single-GPU mode: not with dist (data parallelism)")
+        self._groups = _pg.resolve(self.model, groups, self.lr, self.wd)
+        self._groups_host = _abi.AdamWGroups()
+
+    @property
+    def param_groups(self):
+        """None without ``param_groups=``; else the list of ``{"lr", "weight_decay", "names"}`` the optimizer step reads at
+        EVERY step - entry 0 the parameters no group names (at the ``lr`` / ``weight_decay`` of construction), entry ``i + 1``
+        the constructor's group ``i``.  Assigning ``trainer.param_groups[k]["lr"]`` between steps is a learning-rate schedule:
+        nothing is re-recorded, nothing waits for the device.  ``names`` are fixed at construction."""
+        return self._groups
+
+    def _grouped_optimizer_step(self, fp, m, v, rec=None) -> None:
+        """The grouped launch where the ungrouped step issues ``ops.adamw`` / ``ops.adamw64`` (``rec``: their guarded forms)."""
+        st = ops.adamw_groups([(grp["lr"], grp["weight_decay"]) for grp in self._groups], into=self._groups_host)
+        f32 = fp.flat.dtype == torch.float32
+        args = (fp.flat, fp.grad, m, v, fp.n_train, self._chunk_group, st, self.betas[0], self.betas[1], self.eps, self.step_count)
+        if rec is not None:
+            (ops.adamw_grouped_guarded if f32 else ops.adamw64_grouped_guarded)(*args, rec)
+        else:
+            (ops.adamw_grouped if f32 else ops.adamw64_grouped)(*args)
 
     # ---- checkpoint / resume (SURVEY.md §8f-4; absent upstream) ------------------------------------
     def state_dict(self) -> dict:
@@ -95,6 +132,9 @@ class _AdamWState(StepGuard):
               "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "beta": self.beta}}
         if fp.frozen:                      # (an all-trainable run writes the file it always wrote: no key = every name trains)
             sd["trainable"] = fp.trainable_names()
+        if self._groups is not None:       # (a run without groups writes the file it always wrote)
+            sd["param_groups"] = [{"lr": grp["lr"], "weight_decay": grp["weight_decay"], "names": list(grp["names"])}
+                                  for grp in self._groups]
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
@@ -120,6 +160,10 @@ class _AdamWState(StepGuard):
         h = sd.get("hyper", {})
         self.lr, self.eps, self.wd = h.get("lr", self.lr), h.get("eps", self.eps), h.get("weight_decay", self.wd)
         self.betas, self.beta = tuple(h.get("betas", self.betas)), h.get("beta", self.beta)
+        saved = sd.get("param_groups")
+        if self._groups is not None and saved is not None and len(saved) == len(self._groups):
+            for grp, old in zip(self._groups, saved):      # by group index; another number of groups: the trainer keeps its own
+                grp["lr"], grp["weight_decay"] = float(old["lr"]), float(old["weight_decay"])
 
     def check(self) -> None:
         """Raise :class:`DosxError` if a column-split exchange of any step since the last clean check reported a stall
@@ -201,12 +245,18 @@ class Trainer(_AdamWState, SlotCache):
     its key gradient (functional.wgrad_needed / trunk_cut / first_encoder_cut / attention_query_only); ``program_stats()`` shows
     what is left.  Every model and mode; not under data parallelism.  With nothing frozen the layout, the launches and the bits
     are what they were.
+
+    ``param_groups=[{"params": prefix | [prefixes], "lr": ..., "weight_decay": ...}]``: ``torch.optim.AdamW``'s parameter groups
+    with name prefixes for tensors (``param_groups.py``: ``resolve``, ``no_decay``, ``layerwise``) - still ONE flat AdamW launch,
+    which looks decay and step size up per 64-element chunk of the flat buffer; bit for bit the ungrouped kernel applied tensor by
+    tensor with each tensor's values.  ``trainer.param_groups`` is read at every step: assigning ``["lr"]`` is a schedule.  With
+    the guard, with frozen parameters, every mode; not under data parallelism.  None (the default): the launch it always was.
     """
 
     def __init__(self, model: DOSTransformerBase, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2,
                  betas=(0.9, 0.999), eps: float = 1e-8, dist=None, graph: bool = False, replay: bool = False,
                  bucket=(8, 128), max_slots: int = 32, promote: float = 0.0, per_crystal_keys: bool = False,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None):
         if not isinstance(model, (DOSTransformerBase, GraphnetworkBase)):
             raise TypeError("Trainer drives DOSTransformer / DOSTransformer_phonon / Graphnetwork / Graphnetwork_phonon / mlp modules")
         model._require_fp32_program("Trainer")
@@ -230,6 +280,7 @@ class Trainer(_AdamWState, SlotCache):
         self._per_crystal_keys = bool(per_crystal_keys)
         self._init_guard("Trainer", max_grad_norm, skip_nonfinite, dist)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, betas, eps
+        self._init_param_groups("Trainer", param_groups, dist)
         self.dist = dist
         self.graph = graph
         self.replay = replay
@@ -643,7 +694,9 @@ class Trainer(_AdamWState, SlotCache):
                 assert self._mid_work is None
                 self.dist.all_reduce_grads(fp.grad)
         self.step_count += 1
-        if fp.n_train:                                # (flat[n_train:] are the frozen parameters: nothing steps them)
+        if fp.n_train and self._groups is not None:
+            self._grouped_optimizer_step(fp, m, v)
+        elif fp.n_train:                              # (flat[n_train:] are the frozen parameters: nothing steps them)
             ops.adamw(fp.flat, fp.grad, m, v, fp.n_train, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
                       self.step_count, 1.0)
 

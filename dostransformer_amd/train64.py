@@ -54,16 +54,18 @@ class Trainer64(_AdamWState, SlotCache):
     time in a live larger one instead of recording it (``slot_promoted`` counts those steps; 0: never).
     ``max_grad_norm`` / ``skip_nonfinite``: the optimizer step behind the gradient guard (``guard.StepGuard``), as on
     ``train.Trainer``: clipping and "skip if non-finite" decided on the device, ``grad_norm`` / ``guard_report()`` / ``check()``.
+    ``param_groups``: per-group ``lr`` / ``weight_decay`` in the one flat float64 AdamW launch, as on ``train.Trainer``.
     """
 
     _who = "Trainer64"            # what this driver calls itself in its refusals
 
     def __init__(self, model, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2, betas=(0.9, 0.999),
                  eps: float = 1e-8, replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None):
         self._require_model(model)
         self._init_guard(self._who, max_grad_norm, skip_nonfinite)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, tuple(betas), eps
+        self._init_param_groups(self._who, param_groups)
         self.replay = bool(replay)
         self.max_slots = int(max_slots)
         if self.max_slots < 1:
@@ -216,7 +218,9 @@ class Trainer64(_AdamWState, SlotCache):
         if self.guarded:
             return self._guarded_optimizer_step(fp, m, v)
         self.step_count += 1
-        if fp.n_train:
+        if fp.n_train and self._groups is not None:
+            self._grouped_optimizer_step(fp, m, v)
+        elif fp.n_train:
             ops.adamw64(fp.flat, fp.grad, m, v, fp.n_train, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count)
 
     def step(self, g) -> torch.Tensor:
@@ -244,7 +248,7 @@ class GraphnetworkTrainer64(Trainer64):
 
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, **unknown):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None, **unknown):
         if "beta" in unknown:
             raise ValueError(f"GraphnetworkTrainer64: beta={unknown['beta']} - the model has ONE output and its loss no second "
                              f"term to weigh")
@@ -252,7 +256,7 @@ class GraphnetworkTrainer64(Trainer64):
             raise TypeError(f"GraphnetworkTrainer64() got an unexpected keyword argument {sorted(unknown)[0]!r}")
         super().__init__(model, lr=lr, beta=1.0, weight_decay=weight_decay, betas=betas, eps=eps, replay=replay,
                          max_slots=max_slots, bucket=bucket, promote=promote, max_grad_norm=max_grad_norm,
-                         skip_nonfinite=skip_nonfinite)
+                         skip_nonfinite=skip_nonfinite, param_groups=param_groups)
         self._dead = None                 # the dead-parameter set of the first batch's node-feature width
 
     def _require_model(self, model) -> None:

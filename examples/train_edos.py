@@ -23,6 +23,12 @@ prefixes (FusedModel.train_only / freeze; the prompt table of this model is spel
 parameters are bitwise untouched - no weight decay either - and the backward program drops what only they needed.
 
     python examples/train_edos.py --init edos_best.pt --train-only promt_token fc_prompt --epochs 20 --out edos_ft.pt
+
+Optimizer parameter groups (next to --init / --freeze / --train-only): --group PREFIX[,PREFIX...]:lr=X[:wd=Y] (repeatable) trains
+the named parameters at their own rate / weight decay, --no-decay-norms keeps biases, norms, slopes, embeddings and prompt tokens
+out of the weight decay, --layerwise-lr-decay D lowers the rate layer by layer towards the input (param_groups.py).
+
+    python examples/train_edos.py --init edos_best.pt --group GN_encoder.,stacked_processor.,GN_decoder.:lr=1e-5 --no-decay-norms
 """
 import argparse
 import os
@@ -34,7 +40,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dostransformer_amd import checkpoint, evaluate, featurize, synth, validate  # noqa: E402
+from dostransformer_amd import checkpoint, evaluate, featurize, param_groups, synth, validate  # noqa: E402
 from dostransformer_amd._lib import DosxError  # noqa: E402
 from dostransformer_amd.embedder_eDOS.DOSTransformer import DOSTransformer  # noqa: E402
 from dostransformer_amd.loader import DeviceDataset  # noqa: E402
@@ -84,6 +90,7 @@ def parse_args(argv=None):
                     help="fine-tuning: train exactly the parameters whose names start with one of these prefixes, freeze the rest")
     ap.add_argument("--freeze", nargs="+", default=None, metavar="PREFIX",
                     help="fine-tuning: freeze the parameters whose names start with one of these prefixes")
+    param_groups.add_arguments(ap)
     return ap.parse_args(argv)
 
 
@@ -149,9 +156,13 @@ def _main(argv=None):
     # coarse shape buckets: reshuffled batches fall into a few dozen (N, E) buckets, each recorded once (ghost padding is
     # exact); every batch pads its keys to the training set's largest crystal so that n_max is not a bucket dimension
     bucket = (32, 512)
+    groups = param_groups.from_args(model, args, args.lr)          # --group / --no-decay-norms / --layerwise-lr-decay (None: none)
+    if groups is not None:
+        for k, grp in enumerate(param_groups.resolve(model, groups, args.lr, 1e-2)):
+            print(f"param group {k}: lr {grp['lr']:.3g} weight_decay {grp['weight_decay']:.3g}, {len(grp['names'])} tensors")
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=bucket, promote=0.08,
                       per_crystal_keys=args.per_crystal_keys,      # AdamW(lr, weight_decay=1e-2), `:91`
-                      max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
+                      max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, param_groups=groups)
     predictor = Predictor(model, bucket=bucket, per_crystal_keys=args.eval_per_crystal > 0 and not baseline)
     criterion_2 = torch.nn.L1Loss()                                                       # `main_eDOS.py:93`
 

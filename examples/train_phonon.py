@@ -40,6 +40,13 @@ program drops what only they needed: with the GNN trunk frozen it ends behind th
 
     python examples/train_phonon.py --init phonon_best.pt --train-only prompt_token fc_prompt --epochs 2 --out phonon_ft.pt
     python examples/train_phonon.py --init phonon_best.pt --freeze GN_encoder stacked_processor GN_decoder --epochs 2
+
+Optimizer parameter groups (fused trainers; next to --init / --freeze / --train-only): --group PREFIX[,PREFIX...]:lr=X[:wd=Y]
+(repeatable) trains the named parameters at their own rate / weight decay, --no-decay-norms keeps biases, norms, slopes,
+embeddings and prompt tokens out of the weight decay, --layerwise-lr-decay D lowers the rate layer by layer towards the input.
+
+    python examples/train_phonon.py --init phonon_best.pt --group GN_encoder.,stacked_processor.,GN_decoder.:lr=1e-5 --no-decay-norms
+    python examples/train_phonon.py --float64 --fused --layerwise-lr-decay 0.8 --epochs 2 --crystals 128 --hidden 64
 """
 import argparse
 import os
@@ -51,7 +58,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dostransformer_amd import checkpoint, evaluate, featurize, ops, synth, validate  # noqa: E402
+from dostransformer_amd import checkpoint, evaluate, featurize, ops, param_groups, synth, validate  # noqa: E402
 from dostransformer_amd.embedder_phDOS.DOSTransformer_phonon import DOSTransformer_phonon  # noqa: E402
 from dostransformer_amd.loader import DeviceDataset  # noqa: E402
 from dostransformer_amd.predict import Predictor  # noqa: E402
@@ -105,9 +112,12 @@ def _main(argv=None):
                     help="fine-tuning: train exactly the parameters whose names start with one of these prefixes, freeze the rest")
     ap.add_argument("--freeze", nargs="+", default=None, metavar="PREFIX",
                     help="fine-tuning: freeze the parameters whose names start with one of these prefixes")
+    param_groups.add_arguments(ap)
     args = ap.parse_args(argv)
     if (args.clip_grad_norm is not None or args.skip_nonfinite) and args.float64 and not args.fused:
         ap.error("--clip-grad-norm / --skip-nonfinite belong to the fused trainers: the fp32 run, or --float64 --fused")
+    if param_groups.wanted(args) and args.float64 and not args.fused:
+        ap.error("--group / --no-decay-norms / --layerwise-lr-decay belong to the fused trainers: the fp32 run, or --float64 --fused")
     if args.eval_per_crystal > 0 and args.float64 and not args.replay:
         ap.error("--eval-per-crystal needs a replayed predictor: the fp32 run, or --float64 --fused --replay")
     if args.fused and not args.float64:
@@ -146,7 +156,7 @@ def _main(argv=None):
     # coarse shape buckets: reshuffled batches then fall into a few dozen (N, E, n_max) buckets that are all recorded
     # within the first epoch (ghost padding is exact; it costs a few per cent of extra rows)
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=(32, 1024), promote=0.08,
-                      per_crystal_keys=args.per_crystal_keys, **_guard_args(args))
+                      per_crystal_keys=args.per_crystal_keys, param_groups=_groups(args, model), **_guard_args(args))
     predictor = Predictor(model, bucket=(32, 1024), per_crystal_keys=args.eval_per_crystal > 0 and not baseline)
     run_test = _tester(args, predictor, ds)
     best, history = float("inf"), []
@@ -186,6 +196,16 @@ def _fine_tune(args, model):
         n = sum(p.numel() for k, p in model.named_parameters() if k in set(names))
         print(f"fine-tuning: {len(names)} parameter tensors ({n} elements) train, the rest is frozen")
     return model
+
+
+def _groups(args, model):
+    """--group / --no-decay-norms / --layerwise-lr-decay -> the trainer's ``param_groups=`` (None: none given), after the frozen set:
+    a group may name frozen parameters, they stay untouched."""
+    groups = param_groups.from_args(model, args, args.lr)
+    if groups is not None:
+        for k, grp in enumerate(param_groups.resolve(model, groups, args.lr, 1e-2)):
+            print(f"param group {k}: lr {grp['lr']:.3g} weight_decay {grp['weight_decay']:.3g}, {len(grp['names'])} tensors")
+    return groups
 
 
 def _tester(args, evaluator, ds):
@@ -282,12 +302,12 @@ def train_float64_fused(args, ds, dev):
     slots = dict(replay=args.replay, bucket=bucket if args.replay else None, promote=0.08 if args.replay else 0.0)
     if args.embedder == "graphnetwork":
         model = _fine_tune(args, _baseline64(args, dev))
-        trainer = GraphnetworkTrainer64(model, lr=args.lr, **slots, **_guard_args(args))
+        trainer = GraphnetworkTrainer64(model, lr=args.lr, param_groups=_groups(args, model), **slots, **_guard_args(args))
     else:
         model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).double()
         model = model.set_program_dtype(torch.float64).set_per_crystal_keys(True).to(dev)
         _fine_tune(args, model)
-        trainer = Trainer64(model, lr=args.lr, beta=args.beta, **slots, **_guard_args(args))
+        trainer = Trainer64(model, lr=args.lr, beta=args.beta, param_groups=_groups(args, model), **slots, **_guard_args(args))
     evaluator = Predictor64(model, bucket=bucket) if args.replay else model       # (the module's per-crystal keys are on)
     run_test = _tester(args, evaluator, ds)
     train = ds["train"]

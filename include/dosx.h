@@ -1352,6 +1352,47 @@ int dosx_adamw_guarded(float* p, const float* g, float* m, float* v, int64_t n, 
 int dosx_adamw_guarded_f64(double* p, const double* g, double* m, double* v, int64_t n, double lr, double beta1, double beta2,
                            double eps, double weight_decay, const void* guard, dosx_stream_t stream);
 
+/* ---- AdamW with parameter groups (the kernels stand beside the ungrouped ones: csrc/rowops.hip, csrc/f64_train.hip) ---------
+ * torch.optim.AdamW's param groups on the flat buffers: every DOSX_ADAMW_GROUP_CHUNK elements of the flat buffer carry one
+ * byte that names their group, each group has its own lr and weight_decay; beta1, beta2, eps and the step count are shared.
+ *
+ * chunk_group: DEVICE memory, n / DOSX_ADAMW_GROUP_CHUNK bytes (uint8); byte c is the group of the elements [64c, 64c + 64).
+ *   Built once per layout, only read here.  A byte >= n_groups cannot be seen from the host without a read-back: the kernel
+ *   steps such a chunk as group 0.
+ * groups: HOST memory, read during the call (nothing of it is referenced afterwards).  lr[k], weight_decay[k] for k < n_groups;
+ *   both arrays have DOSX_ADAMW_MAX_GROUPS entries.
+ * Element arithmetic: that of dosx_adamw / dosx_adamw_f64, the same expressions in the same order; only decay and step_size are
+ *   per group, computed on the host by the ungrouped entries' expressions -
+ *   fp32: step_size_k = (float)((double)(float)lr_k / bc1), decay_k = 1.f - (float)lr_k * (float)wd_k; float64: lr_k / bc1,
+ *   1.0 - lr_k * wd_k.  A launch over a run of chunks of group k is bit for bit the ungrouped launch over it with (lr_k, wd_k).
+ * Guarded forms: as dosx_adamw_guarded / _f64 - skip != 0 returns before any store, clip stands where grad_scale stood (fp32) /
+ *   multiplies g (float64), bc2_scale is the record's.  The record holds ONE step size, so the per-group one is the host's
+ *   step_size_k when the record's t equals `step` (nothing skipped so far: the caller's 1-based attempt count IS AdamW's time),
+ *   else it is recomputed on the device by dosx_grad_guard's expression, bc1 = 1 - pow(beta1, (double)t), lr_k / bc1 (rounded
+ *   through float for fp32): what dosx_grad_guard_* writes when called with lr_k.
+ * Grid: the ungrouped entry's (16-byte vectors, 256 threads, the same cap, grid-stride); a vector never straddles a chunk.
+ * All four refuse with -22 and a message: NULL operands, n < 0, step < 1, n % DOSX_ADAMW_GROUP_CHUNK != 0, n_groups outside
+ *   [1, DOSX_ADAMW_MAX_GROUPS], a NaN or negative lr / weight_decay of a used group, p / g / m / v (or the record) off a
+ *   16-byte boundary.  n = 0 is a no-op. */
+#define DOSX_ADAMW_MAX_GROUPS 16
+#define DOSX_ADAMW_GROUP_CHUNK 64
+typedef struct DosxAdamWGroups {
+  int32_t n_groups, reserved;
+  double lr[16], weight_decay[16];
+} DosxAdamWGroups;
+int dosx_adamw_grouped(float* p, const float* g, float* m, float* v, int64_t n, const void* chunk_group,
+                       const DosxAdamWGroups* groups, float beta1, float beta2, float eps, int step, float grad_scale,
+                       dosx_stream_t stream);
+int dosx_adamw_grouped_f64(double* p, const double* g, double* m, double* v, int64_t n, const void* chunk_group,
+                           const DosxAdamWGroups* groups, double beta1, double beta2, double eps, int step,
+                           dosx_stream_t stream);
+int dosx_adamw_grouped_guarded(float* p, const float* g, float* m, float* v, int64_t n, const void* chunk_group,
+                               const DosxAdamWGroups* groups, float beta1, float beta2, float eps, int step, const void* guard,
+                               dosx_stream_t stream);
+int dosx_adamw_grouped_guarded_f64(double* p, const double* g, double* m, double* v, int64_t n, const void* chunk_group,
+                                   const DosxAdamWGroups* groups, double beta1, double beta2, double eps, int step,
+                                   const void* guard, dosx_stream_t stream);
+
 /* ---- evaluation metrics (csrc/eval.hip) -----------------------------------------------------------------------------------
  * utils.py:76-89 / :127-139 evaluated one crystal at a time (what the reference computes at batch_size = 1).
  * pred, y: [B,S] rows with unit inner stride, rows S apart.  clamp0 != 0: both are clamped at 0 first (utils.py:74-76).
