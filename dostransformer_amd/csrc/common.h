@@ -41,31 +41,6 @@ void dosx_set_error(const char* fmt, ...);
 static inline hipStream_t to_stream(dosx_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 
-// What the four dosx_adamw_grouped* entries (rowops.hip, f64_train.hip) refuse in front of their launch, in one place.
-// `guard`: the record of a guarded entry, NULL with has_guard = false for the unguarded ones.
-static_assert(sizeof(((DosxAdamWGroups*)0)->lr) / sizeof(double) == DOSX_ADAMW_MAX_GROUPS, "DosxAdamWGroups holds DOSX_ADAMW_MAX_GROUPS");
-static inline int dosx_adamw_grouped_check(const char* who, const void* p, const void* g, const void* m, const void* v, int64_t n,
-                                           const void* chunk_group, const DosxAdamWGroups* groups, int step, bool has_guard,
-                                           const void* guard) {
-  DOSX_CHECK_ARG(p && g && m && v && chunk_group && groups && (guard || !has_guard), "%s: NULL buffer, chunk map, groups%s", who,
-                 has_guard ? " or record" : "");
-  DOSX_CHECK_ARG(n >= 0, "%s: n must not be negative, got %lld", who, (long long)n);
-  DOSX_CHECK_ARG(step >= 1, "%s: step is the 1-based step count, got %d", who, step);
-  DOSX_CHECK_ARG(n % DOSX_ADAMW_GROUP_CHUNK == 0, "%s: n must be a multiple of %d (one chunk_group byte per %d elements), got %lld",
-                 who, DOSX_ADAMW_GROUP_CHUNK, DOSX_ADAMW_GROUP_CHUNK, (long long)n);
-  DOSX_CHECK_ARG(groups->n_groups >= 1 && groups->n_groups <= DOSX_ADAMW_MAX_GROUPS, "%s: n_groups must be in [1, %d], got %d", who,
-                 DOSX_ADAMW_MAX_GROUPS, groups->n_groups);
-  for (int k = 0; k < groups->n_groups; ++k) {
-    DOSX_CHECK_ARG(groups->lr[k] >= 0.0, "%s: lr[%d] must be a non-negative number, got %g", who, k, groups->lr[k]);
-    DOSX_CHECK_ARG(groups->weight_decay[k] >= 0.0, "%s: weight_decay[%d] must be a non-negative number, got %g", who, k,
-                   groups->weight_decay[k]);
-  }
-  DOSX_CHECK_ARG(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                   reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(guard)) & 15) == 0,
-                 "%s: buffers must be 16-byte aligned", who);
-  return 0;
-}
-
 __device__ __forceinline__ int dosx_map_row(const DosxRowMap& rm, int r) {
   int t;
   if (rm.d >= (1 << 30)) t = r * rm.c + rm.off;     // no div/mod part (identity maps): skip the two integer divisions

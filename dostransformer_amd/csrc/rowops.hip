@@ -1,5 +1,5 @@
 // Row-wise kernels: LayerNorm (+backward), the fused final-LN + out_layer dot product, the
-// callers' losses and the flat AdamW step (gfx950).  One wave per row, float4 lanes.
+// callers' losses (gfx950).  One wave per row, float4 lanes.
 #include <math.h>
 
 #include "common.h"
@@ -531,144 +531,6 @@ __global__ __launch_bounds__(256) void sum_kernel(const float* __restrict__ src,
   if (threadIdx.x == 0) dst[0] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                             float* __restrict__ v, size_t n, float decay, float beta1, float beta2, float eps,
-                             float step_size, float inv_bc2s, float gscale) {
-  const size_t n4 = n >> 2;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    float4 pp = ld4(p + 4 * i), gg = ld4(g + 4 * i), mm = ld4(m + 4 * i), vv = ld4(v + 4 * i);
-    float* P = &pp.x; float* G = &gg.x; float* Mm = &mm.x; float* V = &vv.x;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float gr = G[j] * gscale;
-      float pj = P[j] * decay;
-      const float mj = Mm[j] + (gr - Mm[j]) * (1.f - beta1);
-      const float vj = V[j] * beta2 + (1.f - beta2) * gr * gr;
-      const float denom = sqrtf(vj) * inv_bc2s + eps;
-      pj -= step_size * (mj / denom);
-      P[j] = pj; Mm[j] = mj; V[j] = vj;
-    }
-    st4(p + 4 * i, pp); st4(m + 4 * i, mm); st4(v + 4 * i, vv);
-  }
-  // tail (n not a multiple of 4)
-  const size_t t0 = n4 << 2;
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (tid < n - t0) {
-    const size_t i = t0 + tid;
-    const float gr = g[i] * gscale;
-    float pj = p[i] * decay;
-    const float mj = m[i] + (gr - m[i]) * (1.f - beta1);
-    const float vj = v[i] * beta2 + (1.f - beta2) * gr * gr;
-    pj -= step_size * (mj / (sqrtf(vj) * inv_bc2s + eps));
-    p[i] = pj; m[i] = mj; v[i] = vj;
-  }
-}
-
-// adamw_kernel behind a gradient guard (include/dosx.h: DosxStepGuard): the same element expressions, with the verdict of
-// dosx_grad_guard_f32 read from device memory by every thread (plain uniform loads of a record no one writes during this launch) -
-// skip != 0 returns before any store, clip stands where grad_scale stood, the two bias-correction scalars are the record's.
-__global__ void adamw_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                     float* __restrict__ v, size_t n, float decay, float beta1, float beta2, float eps,
-                                     const DosxStepGuard* __restrict__ rec) {
-  if (rec->skip != 0) return;
-  const float gscale = (float)rec->clip;
-  const float step_size = (float)rec->step_size;
-  const float inv_bc2s = (float)rec->bc2_scale;
-  const size_t n4 = n >> 2;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    float4 pp = ld4(p + 4 * i), gg = ld4(g + 4 * i), mm = ld4(m + 4 * i), vv = ld4(v + 4 * i);
-    float* P = &pp.x; float* G = &gg.x; float* Mm = &mm.x; float* V = &vv.x;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float gr = G[j] * gscale;
-      float pj = P[j] * decay;
-      const float mj = Mm[j] + (gr - Mm[j]) * (1.f - beta1);
-      const float vj = V[j] * beta2 + (1.f - beta2) * gr * gr;
-      const float denom = sqrtf(vj) * inv_bc2s + eps;
-      pj -= step_size * (mj / denom);
-      P[j] = pj; Mm[j] = mj; V[j] = vj;
-    }
-    st4(p + 4 * i, pp); st4(m + 4 * i, mm); st4(v + 4 * i, vv);
-  }
-  // tail (n not a multiple of 4)
-  const size_t t0 = n4 << 2;
-  const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (tid < n - t0) {
-    const size_t i = t0 + tid;
-    const float gr = g[i] * gscale;
-    float pj = p[i] * decay;
-    const float mj = m[i] + (gr - m[i]) * (1.f - beta1);
-    const float vj = v[i] * beta2 + (1.f - beta2) * gr * gr;
-    pj -= step_size * (mj / (sqrtf(vj) * inv_bc2s + eps));
-    p[i] = pj; m[i] = mj; v[i] = vj;
-  }
-}
-
-// adamw_kernel / adamw_guarded_kernel with parameter groups (include/dosx.h: DosxAdamWGroups): the same element expressions, decay
-// and step_size looked up per 64-element chunk.  The table arrives by value and is only ever indexed by constants: the first
-// DOSX_ADAMW_MAX_GROUPS lanes of a workgroup stage one {decay, step_size} pair each into LDS, once, behind one barrier; the loop reads
-// the pair of its chunk's group from there (a float4 never straddles a chunk: 16 neighbouring lanes share the byte and the pair).
-// GUARDED: skip / clip / bc2_scale from the record; the record's one step size is not ours - rec->t == step: the host's
-// step_size_k, else lr_k / (1 - beta1^t) by grad_guard_kernel's expression.
-struct AdamWGroupTable {
-  float decay[DOSX_ADAMW_MAX_GROUPS], step_size[DOSX_ADAMW_MAX_GROUPS], lr[DOSX_ADAMW_MAX_GROUPS];
-  int n_groups;
-};
-
-template <bool GUARDED>
-__global__ __launch_bounds__(256) void adamw_grouped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                            float* __restrict__ v, size_t n, const uint8_t* __restrict__ chunk_group,
-                                                            const AdamWGroupTable tab, float beta1, float beta2, float eps,
-                                                            float inv_bc2s, float gscale, int step,
-                                                            const DosxStepGuard* __restrict__ rec) {
-  __shared__ float2 s_tab[DOSX_ADAMW_MAX_GROUPS];
-  bool host_step = true;
-  int t = step;
-  if constexpr (GUARDED) {
-    if (rec->skip != 0) return;
-    gscale = (float)rec->clip;
-    inv_bc2s = (float)rec->bc2_scale;
-    t = rec->t;
-    host_step = t == step || t < 1;
-  }
-  const int tid = (int)threadIdx.x;
-  if (tid < DOSX_ADAMW_MAX_GROUPS) {
-    float d = 0.f, s = 0.f, lr = 0.f;
-#pragma unroll
-    for (int k = 0; k < DOSX_ADAMW_MAX_GROUPS; ++k)
-      if (tid == k) { d = tab.decay[k]; s = tab.step_size[k]; lr = tab.lr[k]; }
-    if constexpr (GUARDED) {
-      if (!host_step) {
-        const double bc1 = 1.0 - pow((double)beta1, (double)t);
-        s = (float)((double)lr / bc1);
-      }
-    }
-    s_tab[tid] = make_float2(d, s);
-  }
-  __syncthreads();
-  const unsigned n_groups = (unsigned)tab.n_groups;
-  const size_t n4 = n >> 2;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-    unsigned k = chunk_group[i >> 4];                    // 16 float4 per 64-element chunk
-    if (k >= n_groups) k = 0;
-    const float2 ds = s_tab[k];
-    const float decay = ds.x, step_size = ds.y;
-    float4 pp = ld4(p + 4 * i), gg = ld4(g + 4 * i), mm = ld4(m + 4 * i), vv = ld4(v + 4 * i);
-    float* P = &pp.x; float* G = &gg.x; float* Mm = &mm.x; float* V = &vv.x;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float gr = G[j] * gscale;
-      float pj = P[j] * decay;
-      const float mj = Mm[j] + (gr - Mm[j]) * (1.f - beta1);
-      const float vj = V[j] * beta2 + (1.f - beta2) * gr * gr;
-      const float denom = sqrtf(vj) * inv_bc2s + eps;
-      pj -= step_size * (mj / denom);
-      P[j] = pj; Mm[j] = mj; V[j] = vj;
-    }
-    st4(p + 4 * i, pp); st4(m + 4 * i, mm); st4(v + 4 * i, vv);
-  }
-}
-
 // Philox4x32-10 (Salmon et al., SC'11): counter-based, so element i's draw depends only on (seed, stream_id, i)
 __device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
 #pragma unroll
@@ -894,86 +756,6 @@ extern "C" int dosx_sum(const float* src, int n, float* dst, dosx_stream_t strea
   hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, to_stream(stream), src, n, dst);
   DOSX_LAUNCH_CHECK();
   return 0;
-}
-
-extern "C" int dosx_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
-                          float eps, float weight_decay, int step, float grad_scale, dosx_stream_t stream) {
-  if (n <= 0) return 0;
-  DOSX_CHECK_ARG(p && g && m && v && step >= 1, "dosx_adamw: bad args");
-  DOSX_CHECK_ARG(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                   reinterpret_cast<uintptr_t>(v)) & 15) == 0, "dosx_adamw: buffers must be 16-byte aligned");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const float inv_bc2s = (float)(1.0 / sqrt(bc2));
-  const float decay = 1.f - lr * weight_decay;
-  size_t g1 = ((size_t)n / 4 + 255) / 256;
-  if (g1 > 4096) g1 = 4096;
-  if (g1 < 1) g1 = 1;
-  hipLaunchKernelGGL(adamw_kernel, dim3((int)g1), dim3(256), 0, to_stream(stream), p, g, m, v, (size_t)n, decay, beta1,
-                     beta2, eps, step_size, inv_bc2s, grad_scale);
-  DOSX_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int dosx_adamw_guarded(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
-                                  float eps, float weight_decay, const void* guard, dosx_stream_t stream) {
-  DOSX_CHECK_ARG(p && g && m && v && guard, "dosx_adamw_guarded: NULL buffer or record");
-  DOSX_CHECK_ARG(n >= 0, "dosx_adamw_guarded: n must not be negative, got %lld", (long long)n);
-  DOSX_CHECK_ARG(((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                   reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(guard)) & 15) == 0,
-                 "dosx_adamw_guarded: buffers must be 16-byte aligned");
-  if (n == 0) return 0;
-  const float decay = 1.f - lr * weight_decay;
-  size_t g1 = ((size_t)n / 4 + 255) / 256;                 // dosx_adamw's grid
-  if (g1 > 4096) g1 = 4096;
-  if (g1 < 1) g1 = 1;
-  hipLaunchKernelGGL(adamw_guarded_kernel, dim3((int)g1), dim3(256), 0, to_stream(stream), p, g, m, v, (size_t)n, decay, beta1,
-                     beta2, eps, static_cast<const DosxStepGuard*>(guard));
-  DOSX_LAUNCH_CHECK();
-  return 0;
-}
-
-// the host half of both grouped fp32 entries: dosx_adamw's expressions, once per group
-template <bool GUARDED>
-static int adamw_grouped_launch(const char* who, float* p, const float* g, float* m, float* v, int64_t n, const void* chunk_group,
-                                const DosxAdamWGroups* groups, float beta1, float beta2, float eps, int step, float grad_scale,
-                                const void* guard, dosx_stream_t stream) {
-  if (int rc = dosx_adamw_grouped_check(who, p, g, m, v, n, chunk_group, groups, step, GUARDED, guard)) return rc;
-  if (n == 0) return 0;
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float inv_bc2s = (float)(1.0 / sqrt(bc2));
-  AdamWGroupTable tab = {};
-  tab.n_groups = groups->n_groups;
-  for (int k = 0; k < groups->n_groups; ++k) {
-    const float lr = (float)groups->lr[k], weight_decay = (float)groups->weight_decay[k];
-    tab.lr[k] = lr;
-    tab.step_size[k] = (float)((double)lr / bc1);
-    tab.decay[k] = 1.f - lr * weight_decay;
-  }
-  size_t g1 = ((size_t)n / 4 + 255) / 256;                 // dosx_adamw's grid
-  if (g1 > 4096) g1 = 4096;
-  if (g1 < 1) g1 = 1;
-  hipLaunchKernelGGL(adamw_grouped_kernel<GUARDED>, dim3((int)g1), dim3(256), 0, to_stream(stream), p, g, m, v, (size_t)n,
-                     static_cast<const uint8_t*>(chunk_group), tab, beta1, beta2, eps, inv_bc2s, grad_scale, step,
-                     static_cast<const DosxStepGuard*>(guard));
-  DOSX_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int dosx_adamw_grouped(float* p, const float* g, float* m, float* v, int64_t n, const void* chunk_group,
-                                  const DosxAdamWGroups* groups, float beta1, float beta2, float eps, int step, float grad_scale,
-                                  dosx_stream_t stream) {
-  return adamw_grouped_launch<false>("dosx_adamw_grouped", p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, grad_scale,
-                                     nullptr, stream);
-}
-
-extern "C" int dosx_adamw_grouped_guarded(float* p, const float* g, float* m, float* v, int64_t n, const void* chunk_group,
-                                          const DosxAdamWGroups* groups, float beta1, float beta2, float eps, int step,
-                                          const void* guard, dosx_stream_t stream) {
-  return adamw_grouped_launch<true>("dosx_adamw_grouped_guarded", p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, 1.f,
-                                    guard, stream);
 }
 
 extern "C" int dosx_copy_many(const DosxCopyJob* jobs_host, int n_jobs, dosx_stream_t stream) {

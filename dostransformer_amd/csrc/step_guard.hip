@@ -6,6 +6,7 @@
 // unchanged: sc1 publishes, dosx_last_arriver_wg, sc1 read-back, dosx_counter_reset - and the last arriver sums them in an order
 // that depends on the grid alone, which depends on n alone.  No workgroup waits for another one: there is no poll.
 #include "common.h"
+#include "adamw_scalars.h"
 
 #include <limits.h>
 #include <math.h>
@@ -24,8 +25,8 @@ static_assert((GUARD_THREADS & (GUARD_THREADS - 1)) == 0, "the tree below halves
 // what the finishing thread needs beside the partials
 struct GuardScalars {
   double max_norm;                 // < 0: none
-  double lr, beta1, beta2;
-  double host_step_size, host_bc2_scale;      // the unguarded entry's scalars for t = step
+  double lr, beta1, beta2;                     // (of an fp32 entry: floats, widened exactly)
+  double host_step_size, host_bc2_scale;      // the unguarded entry's scalars for t = step (adamw_scalars.h)
   int step;
 };
 
@@ -146,10 +147,8 @@ __global__ __launch_bounds__(GUARD_THREADS) void grad_guard_kernel(const T* __re
   const int t = a.step - skipped;
   double step_size = a.host_step_size, bc2_scale = a.host_bc2_scale;
   if (skipped != 0 && t >= 1) {
-    const double bc1 = 1.0 - pow(a.beta1, (double)t);
-    const double bc2 = 1.0 - pow(a.beta2, (double)t);
-    if constexpr (PER == 4) { step_size = (double)(float)(a.lr / bc1); bc2_scale = (double)(float)(1.0 / sqrt(bc2)); }
-    else { step_size = a.lr / bc1; bc2_scale = sqrt(bc2); }
+    step_size = (double)adamw_step_size<T>((T)a.lr, (T)a.beta1, t);
+    bc2_scale = (double)adamw_bc2_scale<T>((T)a.beta2, t);
   }
   rec->sumsq = sumsq; rec->norm = norm; rec->clip = clip;
   rec->step_size = step_size; rec->bc2_scale = bc2_scale;
@@ -161,11 +160,11 @@ __global__ __launch_bounds__(GUARD_THREADS) void grad_guard_kernel(const T* __re
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 template <typename T>
-int grad_guard(const char* who, const T* g, int64_t n, double max_norm, const int32_t* status, const GuardScalars& a, void* guard,
-               void* workspace, dosx_stream_t stream) {
+int grad_guard(const char* who, const T* g, int64_t n, double max_norm, const int32_t* status, T lr, T beta1, T beta2, int step,
+               void* guard, void* workspace, dosx_stream_t stream) {
   DOSX_CHECK_ARG(g && guard && workspace, "%s: NULL gradient, record or workspace", who);
   DOSX_CHECK_ARG(n >= 0, "%s: n must not be negative, got %lld", who, (long long)n);
-  DOSX_CHECK_ARG(a.step >= 1, "%s: step is the 1-based attempt count, got %d", who, a.step);
+  DOSX_CHECK_ARG(step >= 1, "%s: step is the 1-based attempt count, got %d", who, step);
   DOSX_CHECK_ARG(max_norm == max_norm, "%s: max_norm is NaN (negative: no clipping)", who);
   DOSX_CHECK_ARG(aligned16(g) && aligned16(guard) && aligned16(workspace), "%s: buffers must be 16-byte aligned", who);
   DOSX_CHECK_ARG((reinterpret_cast<uintptr_t>(status) & 3) == 0, "%s: exchange_status must be 4-byte aligned", who);
@@ -174,6 +173,8 @@ int grad_guard(const char* who, const T* g, int64_t n, double max_norm, const in
   long long* slab_bad = reinterpret_cast<long long*>(slab_sum + GUARD_MAX_BLOCKS);
   long long* slab_first = slab_bad + GUARD_MAX_BLOCKS;
   const long long blocks = guard_blocks<T>((long long)n);
+  const GuardScalars a{max_norm, (double)lr, (double)beta1, (double)beta2, (double)adamw_step_size<T>(lr, beta1, step),
+                       (double)adamw_bc2_scale<T>(beta2, step), step};
   hipLaunchKernelGGL(grad_guard_kernel<T>, dim3((unsigned)blocks), dim3(GUARD_THREADS), 0, to_stream(stream), g, (long long)n,
                      reinterpret_cast<int*>(ws), slab_sum, slab_bad, slab_first, status, static_cast<DosxStepGuard*>(guard), a);
   DOSX_LAUNCH_CHECK();
@@ -189,24 +190,10 @@ extern "C" int dosx_grad_guard_blocks(int64_t n, int elem_bytes) {
 
 extern "C" int dosx_grad_guard_f32(const float* g, int64_t n, double max_norm, const int32_t* exchange_status, float lr, float beta1,
                                    float beta2, int step, void* guard, void* workspace, dosx_stream_t stream) {
-  GuardScalars a{max_norm, (double)lr, (double)beta1, (double)beta2, 0.0, 0.0, step};
-  if (step >= 1) {                                         // dosx_adamw's host expressions
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    a.host_step_size = (double)(float)((double)lr / bc1);
-    a.host_bc2_scale = (double)(float)(1.0 / sqrt(bc2));
-  }
-  return grad_guard<float>("dosx_grad_guard_f32", g, n, max_norm, exchange_status, a, guard, workspace, stream);
+  return grad_guard<float>("dosx_grad_guard_f32", g, n, max_norm, exchange_status, lr, beta1, beta2, step, guard, workspace, stream);
 }
 
 extern "C" int dosx_grad_guard_f64(const double* g, int64_t n, double max_norm, const int32_t* exchange_status, double lr,
                                    double beta1, double beta2, int step, void* guard, void* workspace, dosx_stream_t stream) {
-  GuardScalars a{max_norm, lr, beta1, beta2, 0.0, 0.0, step};
-  if (step >= 1) {                                         // dosx_adamw_f64's host expressions
-    const double bc1 = 1.0 - pow(beta1, (double)step);
-    const double bc2 = 1.0 - pow(beta2, (double)step);
-    a.host_step_size = lr / bc1;
-    a.host_bc2_scale = sqrt(bc2);
-  }
-  return grad_guard<double>("dosx_grad_guard_f64", g, n, max_norm, exchange_status, a, guard, workspace, stream);
+  return grad_guard<double>("dosx_grad_guard_f64", g, n, max_norm, exchange_status, lr, beta1, beta2, step, guard, workspace, stream);
 }

@@ -59,8 +59,8 @@ def locate(fp, index: int) -> Optional[Tuple[Optional[str], int]]:
 
 
 class StepGuard:
-    """The guard of a trainer (mixed into ``train._AdamWState``).  Expects ``_fp``, ``_slots``, ``step_count`` and the AdamW
-    hyper-parameters.  ``step_count`` counts ATTEMPTS since the record was last zeroed plus the applied steps before that:
+    """The guard of a trainer (mixed into ``train._AdamWState``).  Expects ``_fp``, ``_slots``, ``step_count``, ``_adamw_launch``
+    and the AdamW hyper-parameters.  ``step_count`` counts ATTEMPTS since the record was last zeroed plus the applied steps before that:
     the record's ``skipped`` is the difference to the applied count, and ``_guard_settle`` folds it in."""
 
     max_grad_norm: Optional[float] = None
@@ -91,16 +91,12 @@ class StepGuard:
         return self._guard_rec, self._guard_ws
 
     def _guarded_optimizer_step(self, fp, m, v) -> None:
-        """statistics launch + guarded AdamW, where the unguarded step issues ``ops.adamw`` / ``ops.adamw64``"""
-        dev = fp.flat.device
-        rec, ws = self._guard_buffers(dev)
+        """statistics launch + the AdamW launch behind its record (``train._AdamWState._adamw_launch``)"""
+        rec, ws = self._guard_buffers(fp.flat.device)
         self.step_count += 1
         ops.grad_guard(fp.grad, fp.n_train, rec, ws, self.max_grad_norm, self.lr, self.betas[0], self.betas[1], self.step_count,
                        self._guard_status)
-        if getattr(self, "_groups", None) is not None:      # parameter groups: the per-group step sizes are not the record's
-            return self._grouped_optimizer_step(fp, m, v, rec) if fp.n_train else None
-        fn = ops.adamw_guarded if fp.flat.dtype == torch.float32 else ops.adamw64_guarded
-        fn(fp.flat, fp.grad, m, v, fp.n_train, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, rec)
+        self._adamw_launch(fp, m, v, rec)
 
     @property
     def grad_norm(self) -> torch.Tensor:

@@ -1671,12 +1671,6 @@ def sum_to(src, n, dst):
     _call("dosx_sum", _p(src), int(n), _p(dst), _stream())
 
 
-def adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
-    _call("dosx_adamw", _p(p), _p(g), _p(m), _p(v), int(n), float(lr), float(beta1), float(beta2), float(eps),
-          float(weight_decay), int(step), float(grad_scale), _stream(),
-          w=lambda: ("adamw", "adamw_kernel", "hbm", 28.0 * n))
-
-
 # ---- guarded optimizer step (csrc/step_guard.hip; include/dosx.h: DosxStepGuard) -----------------------------------------------
 _GUARD_WORDS = C.sizeof(_abi.StepGuard) // 8
 _STATUS_ADDRESS: dict = {}
@@ -1724,15 +1718,7 @@ def grad_guard(g: torch.Tensor, n: int, rec: torch.Tensor, ws: torch.Tensor, max
           w=lambda: ("grad_guard", "grad_guard_kernel", "hbm", float(g.element_size()) * n))
 
 
-def adamw_guarded(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, rec):
-    """:func:`adamw` behind :func:`grad_guard`: skip, clip coefficient and bias correction come from the record."""
-    _chk_f32(p, g, m, v)
-    _call("dosx_adamw_guarded", _p(p), _p(g), _p(m), _p(v), int(n), float(lr), float(beta1), float(beta2), float(eps),
-          float(weight_decay), rec.data_ptr(), _stream(),
-          w=lambda: ("adamw_guarded", "adamw_guarded_kernel", "hbm", 28.0 * n))
-
-
-# ---- AdamW with parameter groups (include/dosx.h: DosxAdamWGroups; the host side is param_groups.py) ---------------------------
+# ---- AdamW on the flat buffers (csrc/adamw.hip): plain, guarded, with parameter groups, fp32 and float64 ---------------------------
 def adamw_groups(groups, into: "Optional[_abi.AdamWGroups]" = None) -> "_abi.AdamWGroups":
     """The host struct of the grouped launches from ``(lr, weight_decay)`` pairs, one per group (a struct is passed through)."""
     if isinstance(groups, _abi.AdamWGroups):
@@ -1747,43 +1733,63 @@ def adamw_groups(groups, into: "Optional[_abi.AdamWGroups]" = None) -> "_abi.Ada
     return st
 
 
-def _chk_grouped(who: str, dtype, p, g, m, v, n: int, chunk_group) -> int:
-    """The operands of a grouped AdamW launch: four flat CUDA buffers of ``dtype`` with at least n elements and a uint8 chunk
-    map with at least n / 64 entries on their device - what the kernel indexes, checked here because the C entry cannot."""
-    n = int(n)
+def _adamw(who: str, dtype, p, g, m, v, n, beta1, beta2, eps, lr=None, weight_decay=None, step=None, grad_scale=None,
+           chunk_group=None, groups=None, rec=None) -> None:
+    """All eight AdamW launches: the entry follows from ``dtype``, ``rec`` (the record of :func:`grad_guard`: the guarded
+    entries) and ``groups`` (the grouped ones).  The operands are checked here because the C entry cannot: four contiguous CUDA
+    buffers of ``dtype`` with at least n elements and, grouped, n a multiple of 64 and a uint8 chunk map of at least n / 64
+    entries on their device - what the kernel indexes."""
+    f32, grouped, n = dtype == torch.float32, groups is not None, int(n)
     for t in (p, g, m, v):
         if t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
             raise TypeError(f"{who}: contiguous {dtype} CUDA buffers, got {t.dtype} on {t.device}")
     if not 0 <= n <= min(p.numel(), g.numel(), m.numel(), v.numel()):
         raise ValueError(f"{who}: n = {n} of buffers with {p.numel()}, {g.numel()}, {m.numel()}, {v.numel()} elements")
-    if n % _abi.DOSX_ADAMW_GROUP_CHUNK:
-        raise ValueError(f"{who}: n = {n} is not a multiple of {_abi.DOSX_ADAMW_GROUP_CHUNK}")
-    if chunk_group.dtype != torch.uint8 or chunk_group.device != p.device or not chunk_group.is_contiguous() or \
-            chunk_group.numel() < n // _abi.DOSX_ADAMW_GROUP_CHUNK:
-        raise ValueError(f"{who}: the chunk map must be a contiguous uint8 tensor of at least {n // _abi.DOSX_ADAMW_GROUP_CHUNK} "
-                         f"entries on {p.device}, got {chunk_group.dtype} x {chunk_group.numel()} on {chunk_group.device}")
-    return n
+    args = [p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n]
+    if grouped:
+        chunks = n // _abi.DOSX_ADAMW_GROUP_CHUNK
+        if n % _abi.DOSX_ADAMW_GROUP_CHUNK:
+            raise ValueError(f"{who}: n = {n} is not a multiple of {_abi.DOSX_ADAMW_GROUP_CHUNK}")
+        if chunk_group.dtype != torch.uint8 or chunk_group.device != p.device or not chunk_group.is_contiguous() or \
+                chunk_group.numel() < chunks:
+            raise ValueError(f"{who}: the chunk map must be a contiguous uint8 tensor of at least {chunks} entries on {p.device}, "
+                             f"got {chunk_group.dtype} x {chunk_group.numel()} on {chunk_group.device}")
+        st = adamw_groups(groups)
+        args += [chunk_group.data_ptr(), C.byref(st), float(beta1), float(beta2), float(eps), int(step)]
+    else:
+        args += [float(lr), float(beta1), float(beta2), float(eps), float(weight_decay)] + ([int(step)] if rec is None else [])
+    if rec is not None:
+        args.append(rec.data_ptr())
+    elif f32:
+        args.append(float(grad_scale))
+    site = "adamw" + ("_grouped" if grouped else "") + ("_guarded" if rec is not None else "") + ("" if f32 else "_f64")
+    _call("dosx_" + site, *args, _stream(),
+          w=lambda: (site, "adamw_kernel", "hbm", (28.0 if f32 else 56.0) * n + (n / 64.0 if grouped else 0.0)))
+
+
+def adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
+    """torch.optim.AdamW's update of the first n elements of the flat fp32 buffers, on ``g * grad_scale`` (dosx_adamw)."""
+    _adamw("adamw", torch.float32, p, g, m, v, n, beta1, beta2, eps, lr, weight_decay, step, grad_scale)
+
+
+def adamw_guarded(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, rec):
+    """:func:`adamw` behind :func:`grad_guard`: skip, clip coefficient and bias correction come from the record."""
+    _adamw("adamw_guarded", torch.float32, p, g, m, v, n, beta1, beta2, eps, lr, weight_decay, rec=rec)
 
 
 def adamw_grouped(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, grad_scale=1.0):
     """:func:`adamw` with parameter groups: ``chunk_group[c]`` names the group of the elements [64c, 64c + 64), ``groups`` is
     ``(lr, weight_decay)`` per group (or the struct of :func:`adamw_groups`).  Bit for bit :func:`adamw` on every run of chunks
     of one group with that group's values."""
-    n = _chk_grouped("adamw_grouped", torch.float32, p, g, m, v, n, chunk_group)
-    st = adamw_groups(groups)
-    _call("dosx_adamw_grouped", _p(p), _p(g), _p(m), _p(v), n, chunk_group.data_ptr(), C.byref(st), float(beta1), float(beta2),
-          float(eps), int(step), float(grad_scale), _stream(),
-          w=lambda: ("adamw_grouped", "adamw_grouped_kernel", "hbm", 28.0 * n + n / 64.0))
+    _adamw("adamw_grouped", torch.float32, p, g, m, v, n, beta1, beta2, eps, step=step, grad_scale=grad_scale,
+           chunk_group=chunk_group, groups=groups)
 
 
 def adamw_grouped_guarded(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, rec):
     """:func:`adamw_grouped` behind :func:`grad_guard`: skip, clip and bc2_scale come from the record, the step size of group k
     is what the record would hold had the guard been called with ``lr_k``.  ``step``: the attempt count the guard was given."""
-    n = _chk_grouped("adamw_grouped_guarded", torch.float32, p, g, m, v, n, chunk_group)
-    st = adamw_groups(groups)
-    _call("dosx_adamw_grouped_guarded", _p(p), _p(g), _p(m), _p(v), n, chunk_group.data_ptr(), C.byref(st), float(beta1),
-          float(beta2), float(eps), int(step), rec.data_ptr(), _stream(),
-          w=lambda: ("adamw_grouped_guarded", "adamw_grouped_kernel", "hbm", 28.0 * n + n / 64.0))
+    _adamw("adamw_grouped_guarded", torch.float32, p, g, m, v, n, beta1, beta2, eps, step=step, chunk_group=chunk_group,
+           groups=groups, rec=rec)
 
 
 def dropout_mask(mask: torch.Tensor, p: float, seed_dev: torch.Tensor, stream_id: int) -> None:
@@ -2194,7 +2200,7 @@ def index_sum64(src: torch.Tensor, idx: torch.Tensor, out: torch.Tensor, accumul
     return out
 
 
-# float64 training step (csrc/f64_train.hip), used by train64.Trainer64
+# float64 training step (csrc/f64_train.hip, csrc/adamw.hip), used by train64.Trainer64
 def loss_phonon64(pg: torch.Tensor, ps: torch.Tensor, y: torch.Tensor, beta: float, dpg: torch.Tensor, dps: torch.Tensor,
                   loss: torch.Tensor, sse: Optional[torch.Tensor] = None) -> None:
     """loss[0] = rmse(pg, y) + beta rmse(ps, y) over all elements, dpg / dps its gradient, sse (optional, 2 elements) the two sums
@@ -2212,41 +2218,25 @@ def loss_phonon64(pg: torch.Tensor, ps: torch.Tensor, y: torch.Tensor, beta: flo
 def adamw64(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, n: int, lr: float, beta1: float, beta2: float,
             eps: float, weight_decay: float, step: int) -> None:
     """torch.optim.AdamW's update of the first n elements of the flat fp64 buffers (include/dosx.h: dosx_adamw_f64)."""
-    _chk_c64(p, g, m, v)
-    if min(p.numel(), g.numel(), m.numel(), v.numel()) < n:
-        raise ValueError(f"adamw64: n = {n} of buffers with {p.numel()}, {g.numel()}, {m.numel()}, {v.numel()} elements")
-    _call("dosx_adamw_f64", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), int(n), float(lr), float(beta1), float(beta2),
-          float(eps), float(weight_decay), int(step), _stream())
+    _adamw("adamw64", torch.float64, p, g, m, v, n, beta1, beta2, eps, lr, weight_decay, step)
 
 
 def adamw64_guarded(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, n: int, lr: float, beta1: float,
                     beta2: float, eps: float, weight_decay: float, rec: torch.Tensor) -> None:
     """:func:`adamw64` behind :func:`grad_guard`: skip, clip coefficient and bias correction come from the record."""
-    _chk_c64(p, g, m, v)
-    if min(p.numel(), g.numel(), m.numel(), v.numel()) < n:
-        raise ValueError(f"adamw64_guarded: n = {n} of buffers with {p.numel()}, {g.numel()}, {m.numel()}, {v.numel()} elements")
-    _call("dosx_adamw_guarded_f64", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), int(n), float(lr), float(beta1),
-          float(beta2), float(eps), float(weight_decay), rec.data_ptr(), _stream(),
-          w=lambda: ("adamw_guarded_f64", "adamw_guarded_f64_kernel", "hbm", 56.0 * n))
+    _adamw("adamw64_guarded", torch.float64, p, g, m, v, n, beta1, beta2, eps, lr, weight_decay, rec=rec)
 
 
 def adamw64_grouped(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step) -> None:
     """:func:`adamw64` with parameter groups (see :func:`adamw_grouped`): bit for bit :func:`adamw64` on every run of chunks of
     one group with that group's ``(lr, weight_decay)``."""
-    n = _chk_grouped("adamw64_grouped", torch.float64, p, g, m, v, n, chunk_group)
-    st = adamw_groups(groups)
-    _call("dosx_adamw_grouped_f64", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, chunk_group.data_ptr(), C.byref(st),
-          float(beta1), float(beta2), float(eps), int(step), _stream(),
-          w=lambda: ("adamw_grouped_f64", "adamw_grouped_f64_kernel", "hbm", 56.0 * n + n / 64.0))
+    _adamw("adamw64_grouped", torch.float64, p, g, m, v, n, beta1, beta2, eps, step=step, chunk_group=chunk_group, groups=groups)
 
 
 def adamw64_grouped_guarded(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, rec) -> None:
     """:func:`adamw64_grouped` behind :func:`grad_guard` (see :func:`adamw_grouped_guarded`)."""
-    n = _chk_grouped("adamw64_grouped_guarded", torch.float64, p, g, m, v, n, chunk_group)
-    st = adamw_groups(groups)
-    _call("dosx_adamw_grouped_guarded_f64", p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, chunk_group.data_ptr(),
-          C.byref(st), float(beta1), float(beta2), float(eps), int(step), rec.data_ptr(), _stream(),
-          w=lambda: ("adamw_grouped_guarded_f64", "adamw_grouped_f64_kernel", "hbm", 56.0 * n + n / 64.0))
+    _adamw("adamw64_grouped_guarded", torch.float64, p, g, m, v, n, beta1, beta2, eps, step=step, chunk_group=chunk_group,
+           groups=groups, rec=rec)
 
 
 # float64 pair head of Graphnetwork_phonon (csrc/pair_head_f64.hip), used by functional64's factored program

@@ -100,15 +100,34 @@ class _AdamWState(StepGuard):
         nothing is re-recorded, nothing waits for the device.  ``names`` are fixed at construction."""
         return self._groups
 
-    def _grouped_optimizer_step(self, fp, m, v, rec=None) -> None:
-        """The grouped launch where the ungrouped step issues ``ops.adamw`` / ``ops.adamw64`` (``rec``: their guarded forms)."""
-        st = ops.adamw_groups([(grp["lr"], grp["weight_decay"]) for grp in self._groups], into=self._groups_host)
-        f32 = fp.flat.dtype == torch.float32
-        args = (fp.flat, fp.grad, m, v, fp.n_train, self._chunk_group, st, self.betas[0], self.betas[1], self.eps, self.step_count)
-        if rec is not None:
-            (ops.adamw_grouped_guarded if f32 else ops.adamw64_grouped_guarded)(*args, rec)
+    # ---- optimizer -------------------------------------------------------------------------------------------------------
+    def _adamw_launch(self, fp, m, v, rec=None) -> None:
+        """The optimizer's one launch for ``step_count``, the only place that chooses among the ``ops.adamw*`` functions: fp32 or
+        float64 by the flat buffer, behind the guard's record ``rec`` or not, with the trainer's parameter groups or its one
+        ``lr`` / ``wd``.  ``flat[n_train:]`` are the frozen parameters, nothing steps them: no launch when everything is frozen."""
+        if not fp.n_train:
+            return
+        grouped, guarded = self._groups is not None, rec is not None
+        name = ("adamw" if fp.flat.dtype == torch.float32 else "adamw64") + ("_grouped" if grouped else "") + ("_guarded" if guarded else "")
+        if grouped:
+            st = ops.adamw_groups([(grp["lr"], grp["weight_decay"]) for grp in self._groups], into=self._groups_host)
+            args = (self._chunk_group, st, self.betas[0], self.betas[1], self.eps, self.step_count)
         else:
-            (ops.adamw_grouped if f32 else ops.adamw64_grouped)(*args)
+            args = (self.lr, self.betas[0], self.betas[1], self.eps, self.wd) + (() if guarded else (self.step_count,))
+        getattr(ops, name)(fp.flat, fp.grad, m, v, fp.n_train, *args, *((rec,) if guarded else ()))
+
+    def _reduce_gradients(self, fp) -> None:
+        """Between the backward and the unguarded optimizer launch: nothing here; Trainer finishes its ``dist`` all-reduces."""
+
+    def optimizer_step(self) -> None:
+        """The flat AdamW launch, issued behind the (recorded) program: ``step`` changes every step."""
+        fp = self._fp if self._fp is not None else self.model.flat_params()
+        m, v = self._state(fp)
+        if self.guarded:                              # (never with dist: refused at construction)
+            return self._guarded_optimizer_step(fp, m, v)
+        self._reduce_gradients(fp)
+        self.step_count += 1
+        self._adamw_launch(fp, m, v)
 
     # ---- checkpoint / resume (SURVEY.md §8f-4; absent upstream) ------------------------------------
     def state_dict(self) -> dict:
@@ -675,11 +694,7 @@ class Trainer(_AdamWState, SlotCache):
         return dict(st)
 
     # ---- optimizer -------------------------------------------------------------------------------
-    def optimizer_step(self) -> None:
-        fp = self._fp if self._fp is not None else self.model.flat_params()
-        m, v = self._state(fp)
-        if self.guarded:                              # (never with dist: refused at construction)
-            return self._guarded_optimizer_step(fp, m, v)
+    def _reduce_gradients(self, fp) -> None:
         if self.dist is not None:
             if self._early_work is not None:          # early (+ mid) bucket already in flight: only the last bucket is exposed
                 if self._mid_work is not None:
@@ -693,12 +708,6 @@ class Trainer(_AdamWState, SlotCache):
             else:
                 assert self._mid_work is None
                 self.dist.all_reduce_grads(fp.grad)
-        self.step_count += 1
-        if fp.n_train and self._groups is not None:
-            self._grouped_optimizer_step(fp, m, v)
-        elif fp.n_train:                              # (flat[n_train:] are the frozen parameters: nothing steps them)
-            ops.adamw(fp.flat, fp.grad, m, v, fp.n_train, self.lr, self.betas[0], self.betas[1], self.eps, self.wd,
-                      self.step_count, 1.0)
 
     def step(self, g, n_global: Optional[int] = None) -> torch.Tensor:
         self._bump_dropout_seed()

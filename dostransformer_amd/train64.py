@@ -210,19 +210,6 @@ class Trainer64(_AdamWState, SlotCache):
         self.optimizer_step()
         return loss
 
-    # ---- optimizer -----------------------------------------------------------------------------------------------------
-    def optimizer_step(self) -> None:
-        """The flat AdamW launch, issued behind the (recorded) program: ``step`` changes every step."""
-        fp = self._fp if self._fp is not None else self.model.flat_params()
-        m, v = self._state(fp)
-        if self.guarded:
-            return self._guarded_optimizer_step(fp, m, v)
-        self.step_count += 1
-        if fp.n_train and self._groups is not None:
-            self._grouped_optimizer_step(fp, m, v)
-        elif fp.n_train:
-            ops.adamw64(fp.flat, fp.grad, m, v, fp.n_train, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count)
-
     def step(self, g) -> torch.Tensor:
         self._refuse(g)
         self._bump_dropout_seed()

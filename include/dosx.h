@@ -506,7 +506,7 @@ int dosx_loss_edos(const float* pg, const float* ps, const float* y_ft, float be
  * per-crystal shares written by dosx_loss_edos. */
 int dosx_sum(const float* src, int n, float* dst, dosx_stream_t stream);
 
-/* torch.optim.AdamW step on a flat buffer (main_eDOS.py:93,127): decoupled weight decay.
+/* torch.optim.AdamW step on a flat buffer (main_eDOS.py:93,127): decoupled weight decay (csrc/adamw.hip).
  * `step` is the 1-based step count. */
 int dosx_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                float eps, float weight_decay, int step, float grad_scale, dosx_stream_t stream);
@@ -1273,7 +1273,7 @@ int dosx_dense_rows_bwd_f64(const double* dout, const double* xhat, const double
 int dosx_index_sum_f64(const double* src, int ld_src, const int32_t* idx, int n_src, double* dst, int ld_dst, int n_dst,
                        int W, int accumulate, dosx_stream_t stream);
 
-/* ---- float64 training step (csrc/f64_train.hip) --------------------------------------------------------------------------
+/* ---- float64 training step (csrc/f64_train.hip; the AdamW entry: csrc/adamw.hip) -------------------------------------------
  * The tail of train64.Trainer64's step: phonon loss + gradient and the flat AdamW update on double operands.
  *
  * dosx_loss_phonon_f64: the float64 twin of dosx_loss_phonon (main_phDOS.py:109-114), one launch, one workgroup:
@@ -1292,7 +1292,7 @@ int dosx_loss_phonon_f64(const double* pg, const double* ps, const double* y, do
 int dosx_adamw_f64(double* p, const double* g, double* m, double* v, int64_t n, double lr, double beta1, double beta2,
                    double eps, double weight_decay, int step, dosx_stream_t stream);
 
-/* ---- guarded optimizer step (csrc/step_guard.hip; the guarded AdamW kernels stand beside the unguarded ones) ---------------
+/* ---- guarded optimizer step (csrc/step_guard.hip; the guarded AdamW entries: csrc/adamw.hip) ------------------------------
  * What a fused trainer has in place of `clip_grad_norm_` and of a GradScaler-style "skip if non-finite": one statistics launch
  * over the flat gradient, behind the recorded program and in front of the AdamW launch, and an AdamW that reads its verdict
  * from device memory.  No host read anywhere in the step.
@@ -1352,7 +1352,7 @@ int dosx_adamw_guarded(float* p, const float* g, float* m, float* v, int64_t n, 
 int dosx_adamw_guarded_f64(double* p, const double* g, double* m, double* v, int64_t n, double lr, double beta1, double beta2,
                            double eps, double weight_decay, const void* guard, dosx_stream_t stream);
 
-/* ---- AdamW with parameter groups (the kernels stand beside the ungrouped ones: csrc/rowops.hip, csrc/f64_train.hip) ---------
+/* ---- AdamW with parameter groups (instantiations of the ungrouped entries' kernel and launcher: csrc/adamw.hip) -------------
  * torch.optim.AdamW's param groups on the flat buffers: every DOSX_ADAMW_GROUP_CHUNK elements of the flat buffer carry one
  * byte that names their group, each group has its own lr and weight_decay; beta1, beta2, eps and the step count are shared.
  *

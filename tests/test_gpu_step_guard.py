@@ -1,5 +1,5 @@
-"""The guarded optimizer step's kernels on a real MI355X (csrc/step_guard.hip: dosx_grad_guard_f32 / _f64; csrc/rowops.hip:
-dosx_adamw_guarded; csrc/f64_train.hip: dosx_adamw_guarded_f64), each called directly, for fp32 and float64 gradients.
+"""The guarded optimizer step's kernels on a real MI355X (csrc/step_guard.hip: dosx_grad_guard_f32 / _f64; csrc/adamw.hip:
+dosx_adamw_guarded, dosx_adamw_guarded_f64), each called directly, for fp32 and float64 gradients.
 
 Every gradient buffer is n + 8 long with NaN behind n: a kernel that read past n would count a non-finite element.  The
 statistics are held to a long-double reference within bounds counted from the kernel's own summation order (section 1), the

@@ -1,4 +1,4 @@
-"""The tail of every training step - the final LayerNorm family, the losses, the flat AdamW step (csrc/rowops.hip) and the small
+"""The tail of every training step - the final LayerNorm family, the losses (csrc/rowops.hip), the flat AdamW step (csrc/adamw.hip) and the small
 utilities around them (csrc/graph_ops.hip: embed / reduce rows, act_bwd, graph pooling, seg_count_scale) - each kernel called
 directly and held element by element to a float64 torch reference on the same fp32 inputs: |got - ref64| <= c * 2^-24 * scale64
 (gpu_util.bound_ratio), scale64 the element's own operand magnitude, c counted from the kernel's roundings (the derivation stands

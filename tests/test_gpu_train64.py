@@ -1,4 +1,4 @@
-"""The fused float64 training step on a real MI355X: dosx_loss_phonon_f64 and dosx_adamw_f64 (csrc/f64_train.hip) against
+"""The fused float64 training step on a real MI355X: dosx_loss_phonon_f64 (csrc/f64_train.hip) and dosx_adamw_f64 (csrc/adamw.hip) against
 float64 torch / a long-double host reference, and train64.Trainer64 - eager against the hand-written loop (model(batch), torch
 loss, loss.backward(), torch.optim.AdamW) and against the float64 oracle run crystal by crystal, replay against eager (bitwise),
 checkpoint and resume (bitwise).  Bounds: the project's float64 bars (tests/test_gpu_f64.py): losses 1e-12 relative, gradients
@@ -132,7 +132,7 @@ def test_loss_phonon64_wrapper_checks_dtype_and_layout():
 #                                           difference: 15.  Together <= 16 against |p| + step_size (|m| + |g|) / denom
 C_ADAM_M, C_ADAM_V, C_ADAM_P = 4, 6, 16
 B1, B2, EPS = 0.9, 0.999, 1e-8
-ADAM64_SWEEP = 2048 * 256 * 2               # doubles one sweep of the capped grid covers (csrc/f64_train.hip)
+ADAM64_SWEEP = 2048 * 256 * 2               # doubles one sweep of the capped grid covers (csrc/adamw.hip)
 
 
 def _adam_ref(p, g, m, v, step, lr, wd):

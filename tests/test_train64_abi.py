@@ -1,4 +1,4 @@
-"""CPU-only checks of the float64 training step's entry points (csrc/f64_train.hip) and of train64.Trainer64's refusals:
+"""CPU-only checks of the float64 training step's entry points (csrc/f64_train.hip, csrc/adamw.hip) and of train64.Trainer64's refusals:
 declared, replayable, prototyped with double hyper-parameters; arguments are refused before any launch; which modules
 Trainer64 takes.  (Exports, thunks and argument types against the header: tests/test_lib_abi.py, for the whole header.)"""
 import os

@@ -18,6 +18,17 @@ def dosx_lib():
     return _lib
 
 
+def in_all_three_builds(src):
+    """True when csrc/Makefile compiles ``src`` into libdosx.so and into both diagnostic builds: it stands in SRCS, and the
+    `stamps` and `acqrel` recipes take every .hip file of SRCS."""
+    import re
+    text = open(os.path.join(os.path.dirname(GOLDEN), "..", "dostransformer_amd", "csrc", "Makefile")).read()
+    srcs = re.search(r"^SRCS = (.*)$", text, re.M).group(1).split()
+    recipes = re.findall(r"^\t\$\(HIPCC\) .* -shared -o build/libdosx_(stamps|acqrel)\.so (.*)$", text, re.M)
+    return src in srcs and sorted(k for k, _ in recipes) == ["acqrel", "stamps"] and \
+        all(r.startswith("$(filter %.hip,$(SRCS)) ") for _, r in recipes)
+
+
 def load(name):
     return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
 
