@@ -2,6 +2,8 @@
 // (grad_guard_kernel after a skipped step, the grouped guarded kernels when the record's t is not the caller's step): every
 // mode of the optimizer step promises the bits of the plain one, so every place that needs a scalar calls these.
 // T = float: dosx_adamw's roundings (the powers and quotients in double, the result rounded once); T = double: torch's.
+// adamw_ema_decay, the decay schedule of the weight average (DosxAdamWEma), lives here under the same rule: the launcher
+// evaluates it for the caller's step, a guarded EMA kernel for the record's t when that is another one.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -26,3 +28,15 @@ __host__ __device__ inline T adamw_bc2_scale(T beta2, int t) {
 // 1 - lr wd, in T
 template <typename T>
 __host__ __device__ inline T adamw_decay(T lr, T weight_decay) { return (T)1 - lr * weight_decay; }
+
+// the decay of the weight average (DosxAdamWEma) at t = AdamW's time - t0 steps of averaging: min(decay, (1 + t) / (10 + t)) under
+// warm-up (torch-ema's / timm's schedule), else decay; in double, rounded once to T
+template <typename T>
+__host__ __device__ inline T adamw_ema_decay(double decay, int warmup, int t) {
+  double d = decay;
+  if (warmup) {
+    const double w = (1.0 + (double)t) / (10.0 + (double)t);
+    if (w < d) d = w;
+  }
+  return (T)d;
+}

@@ -1733,27 +1733,32 @@ def adamw_groups(groups, into: "Optional[_abi.AdamWGroups]" = None) -> "_abi.Ada
     return st
 
 
+def ema_decay_at(decay: float, warmup: bool, t: int, dtype=torch.float32) -> float:
+    """The decay the EMA launches apply after ``t`` steps of averaging, rounded to ``dtype`` (dosx_adamw_ema_decay: the
+    kernel's own expression, evaluated on the host)."""
+    return float(_lib.load().dosx_adamw_ema_decay(float(decay), int(bool(warmup)), int(t), 4 if dtype == torch.float32 else 8))
+
+
 def _adamw(who: str, dtype, p, g, m, v, n, beta1, beta2, eps, lr=None, weight_decay=None, step=None, grad_scale=None,
-           chunk_group=None, groups=None, rec=None) -> None:
-    """All eight AdamW launches: the entry follows from ``dtype``, ``rec`` (the record of :func:`grad_guard`: the guarded
-    entries) and ``groups`` (the grouped ones).  The operands are checked here because the C entry cannot: four contiguous CUDA
-    buffers of ``dtype`` with at least n elements and, grouped, n a multiple of 64 and a uint8 chunk map of at least n / 64
-    entries on their device - what the kernel indexes."""
+           chunk_group=None, groups=None, rec=None, ema=None) -> None:
+    """All AdamW launches: the entry follows from ``dtype``, ``rec`` (the record of :func:`grad_guard`: the guarded
+    entries), ``groups`` (the grouped ones) and ``ema`` (``(buffer, decay, warmup, t0)``: the same launch also keeps the
+    exponential moving average of ``p`` in ``buffer`` - dosx_adamw_ema / _f64, which take every form's operands and ``step``
+    always).  The operands are checked here because the C entry cannot: contiguous CUDA buffers of ``dtype`` with at least n
+    elements and, grouped, n a multiple of 64 and a uint8 chunk map of at least n / 64 entries on their device - what the
+    kernel indexes."""
     f32, grouped, n = dtype == torch.float32, groups is not None, int(n)
-    for t in (p, g, m, v):
-        if t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
-            raise TypeError(f"{who}: contiguous {dtype} CUDA buffers, got {t.dtype} on {t.device}")
-    if not 0 <= n <= min(p.numel(), g.numel(), m.numel(), v.numel()):
-        raise ValueError(f"{who}: n = {n} of buffers with {p.numel()}, {g.numel()}, {m.numel()}, {v.numel()} elements")
+    bufs = (p, g, m, v) + ((ema[0],) if ema is not None else ())
+    for t in bufs:
+        if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.device != p.device:
+            raise TypeError(f"{who}: contiguous {dtype} CUDA buffers on one device, got {t.dtype} on {t.device}")
+    if not 0 <= n <= min(t.numel() for t in bufs):
+        raise ValueError(f"{who}: n = {n} of buffers with {', '.join(str(t.numel()) for t in bufs)} elements")
+    if ema is not None:
+        return _adamw_ema(who, f32, bufs, n, beta1, beta2, eps, lr, weight_decay, step, grad_scale, chunk_group, groups, rec, ema)
     args = [p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n]
     if grouped:
-        chunks = n // _abi.DOSX_ADAMW_GROUP_CHUNK
-        if n % _abi.DOSX_ADAMW_GROUP_CHUNK:
-            raise ValueError(f"{who}: n = {n} is not a multiple of {_abi.DOSX_ADAMW_GROUP_CHUNK}")
-        if chunk_group.dtype != torch.uint8 or chunk_group.device != p.device or not chunk_group.is_contiguous() or \
-                chunk_group.numel() < chunks:
-            raise ValueError(f"{who}: the chunk map must be a contiguous uint8 tensor of at least {chunks} entries on {p.device}, "
-                             f"got {chunk_group.dtype} x {chunk_group.numel()} on {chunk_group.device}")
+        _chunk_map_ok(who, chunk_group, n, p.device)
         st = adamw_groups(groups)
         args += [chunk_group.data_ptr(), C.byref(st), float(beta1), float(beta2), float(eps), int(step)]
     else:
@@ -1767,29 +1772,78 @@ def _adamw(who: str, dtype, p, g, m, v, n, beta1, beta2, eps, lr=None, weight_de
           w=lambda: (site, "adamw_kernel", "hbm", (28.0 if f32 else 56.0) * n + (n / 64.0 if grouped else 0.0)))
 
 
-def adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
-    """torch.optim.AdamW's update of the first n elements of the flat fp32 buffers, on ``g * grad_scale`` (dosx_adamw)."""
-    _adamw("adamw", torch.float32, p, g, m, v, n, beta1, beta2, eps, lr, weight_decay, step, grad_scale)
+def _chunk_map_ok(who: str, chunk_group, n: int, device) -> None:
+    chunks = n // _abi.DOSX_ADAMW_GROUP_CHUNK
+    if n % _abi.DOSX_ADAMW_GROUP_CHUNK:
+        raise ValueError(f"{who}: n = {n} is not a multiple of {_abi.DOSX_ADAMW_GROUP_CHUNK}")
+    if chunk_group.dtype != torch.uint8 or chunk_group.device != device or not chunk_group.is_contiguous() or \
+            chunk_group.numel() < chunks:
+        raise ValueError(f"{who}: the chunk map must be a contiguous uint8 tensor of at least {chunks} entries on {device}, "
+                         f"got {chunk_group.dtype} x {chunk_group.numel()} on {chunk_group.device}")
 
 
-def adamw_guarded(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, rec):
-    """:func:`adamw` behind :func:`grad_guard`: skip, clip coefficient and bias correction come from the record."""
-    _adamw("adamw_guarded", torch.float32, p, g, m, v, n, beta1, beta2, eps, lr, weight_decay, rec=rec)
+def _adamw_ema(who, f32, bufs, n, beta1, beta2, eps, lr, weight_decay, step, grad_scale, chunk_group, groups, rec, ema) -> None:
+    """:func:`_adamw` with an average: the one entry per type, the absent operands of the form as NULL / 0."""
+    p, g, m, v, e = bufs
+    _, decay, warmup, t0 = ema
+    if step is None:
+        raise ValueError(f"{who}: an EMA launch needs step (AdamW's time, guarded: the attempt count the guard was given)")
+    st = None
+    if groups is not None:
+        _chunk_map_ok(who, chunk_group, n, p.device)
+        st = adamw_groups(groups)
+    desc = _abi.AdamWEma(e.data_ptr(), float(decay), int(bool(warmup)), int(t0))
+    args = [p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, 0.0 if lr is None else float(lr), float(beta1), float(beta2),
+            float(eps), 0.0 if weight_decay is None else float(weight_decay), int(step)]
+    if f32:
+        args.append(1.0 if grad_scale is None else float(grad_scale))
+    args += [_p(chunk_group) if st is not None else None, C.byref(st) if st is not None else None, _p(rec), C.byref(desc)]
+    site = "adamw_ema" + ("" if f32 else "_f64")
+    _call("dosx_" + site, *args, _stream(),
+          w=lambda: (site, "adamw_kernel", "hbm", (36.0 if f32 else 72.0) * n + (n / 64.0 if st is not None else 0.0)))
 
 
-def adamw_grouped(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, grad_scale=1.0):
+def swap_buffers(a: torch.Tensor, b: torch.Tensor, n: Optional[int] = None) -> None:
+    """Exchange the first ``n`` elements (default: all) of two contiguous CUDA buffers of one dtype in one launch
+    (dosx_swap_buffers); ``n`` elements must be a multiple of 16 bytes."""
+    if a.dtype != b.dtype or not a.is_cuda or a.device != b.device or not (a.is_contiguous() and b.is_contiguous()):
+        raise TypeError(f"swap_buffers: two contiguous CUDA buffers of one dtype on one device, got {a.dtype} on {a.device} and "
+                        f"{b.dtype} on {b.device}")
+    n = min(a.numel(), b.numel()) if n is None else int(n)
+    if not 0 <= n <= min(a.numel(), b.numel()):
+        raise ValueError(f"swap_buffers: n = {n} of buffers with {a.numel()} and {b.numel()} elements")
+    nbytes = n * a.element_size()
+    _call("dosx_swap_buffers", a.data_ptr(), b.data_ptr(), nbytes, _stream(),
+          w=lambda: ("swap_buffers", "swap_kernel", "hbm", 4.0 * nbytes))
+
+
+def adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, ema=None):
+    """torch.optim.AdamW's update of the first n elements of the flat fp32 buffers, on ``g * grad_scale`` (dosx_adamw).
+    ``ema=(buffer, decay, warmup, t0)``, here and on the seven functions below: the launch also keeps the exponential moving
+    average of the parameters (dosx_adamw_ema / _f64); p, m, v are bitwise those without it."""
+    _adamw("adamw", torch.float32, p, g, m, v, n, beta1, beta2, eps, lr, weight_decay, step, grad_scale, ema=ema)
+
+
+def adamw_guarded(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, rec, step=None, ema=None):
+    """:func:`adamw` behind :func:`grad_guard`: skip, clip coefficient and bias correction come from the record.  ``step``
+    (the attempt count the guard was given) is read with ``ema`` only."""
+    _adamw("adamw_guarded", torch.float32, p, g, m, v, n, beta1, beta2, eps, lr, weight_decay, step=step if ema is not None else None,
+           rec=rec, ema=ema)
+
+
+def adamw_grouped(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, grad_scale=1.0, ema=None):
     """:func:`adamw` with parameter groups: ``chunk_group[c]`` names the group of the elements [64c, 64c + 64), ``groups`` is
     ``(lr, weight_decay)`` per group (or the struct of :func:`adamw_groups`).  Bit for bit :func:`adamw` on every run of chunks
     of one group with that group's values."""
     _adamw("adamw_grouped", torch.float32, p, g, m, v, n, beta1, beta2, eps, step=step, grad_scale=grad_scale,
-           chunk_group=chunk_group, groups=groups)
+           chunk_group=chunk_group, groups=groups, ema=ema)
 
 
-def adamw_grouped_guarded(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, rec):
+def adamw_grouped_guarded(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, rec, ema=None):
     """:func:`adamw_grouped` behind :func:`grad_guard`: skip, clip and bc2_scale come from the record, the step size of group k
     is what the record would hold had the guard been called with ``lr_k``.  ``step``: the attempt count the guard was given."""
     _adamw("adamw_grouped_guarded", torch.float32, p, g, m, v, n, beta1, beta2, eps, step=step, chunk_group=chunk_group,
-           groups=groups, rec=rec)
+           groups=groups, rec=rec, ema=ema)
 
 
 def dropout_mask(mask: torch.Tensor, p: float, seed_dev: torch.Tensor, stream_id: int) -> None:
@@ -2216,27 +2270,31 @@ def loss_phonon64(pg: torch.Tensor, ps: torch.Tensor, y: torch.Tensor, beta: flo
 
 
 def adamw64(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, n: int, lr: float, beta1: float, beta2: float,
-            eps: float, weight_decay: float, step: int) -> None:
-    """torch.optim.AdamW's update of the first n elements of the flat fp64 buffers (include/dosx.h: dosx_adamw_f64)."""
-    _adamw("adamw64", torch.float64, p, g, m, v, n, beta1, beta2, eps, lr, weight_decay, step)
+            eps: float, weight_decay: float, step: int, ema=None) -> None:
+    """torch.optim.AdamW's update of the first n elements of the flat fp64 buffers (include/dosx.h: dosx_adamw_f64).
+    ``ema``: as on :func:`adamw`, here and on the three functions below."""
+    _adamw("adamw64", torch.float64, p, g, m, v, n, beta1, beta2, eps, lr, weight_decay, step, ema=ema)
 
 
 def adamw64_guarded(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, n: int, lr: float, beta1: float,
-                    beta2: float, eps: float, weight_decay: float, rec: torch.Tensor) -> None:
-    """:func:`adamw64` behind :func:`grad_guard`: skip, clip coefficient and bias correction come from the record."""
-    _adamw("adamw64_guarded", torch.float64, p, g, m, v, n, beta1, beta2, eps, lr, weight_decay, rec=rec)
+                    beta2: float, eps: float, weight_decay: float, rec: torch.Tensor, step=None, ema=None) -> None:
+    """:func:`adamw64` behind :func:`grad_guard`: skip, clip coefficient and bias correction come from the record.  ``step``
+    (the attempt count the guard was given) is read with ``ema`` only."""
+    _adamw("adamw64_guarded", torch.float64, p, g, m, v, n, beta1, beta2, eps, lr, weight_decay, step=step if ema is not None else None,
+           rec=rec, ema=ema)
 
 
-def adamw64_grouped(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step) -> None:
+def adamw64_grouped(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, ema=None) -> None:
     """:func:`adamw64` with parameter groups (see :func:`adamw_grouped`): bit for bit :func:`adamw64` on every run of chunks of
     one group with that group's ``(lr, weight_decay)``."""
-    _adamw("adamw64_grouped", torch.float64, p, g, m, v, n, beta1, beta2, eps, step=step, chunk_group=chunk_group, groups=groups)
+    _adamw("adamw64_grouped", torch.float64, p, g, m, v, n, beta1, beta2, eps, step=step, chunk_group=chunk_group, groups=groups,
+           ema=ema)
 
 
-def adamw64_grouped_guarded(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, rec) -> None:
+def adamw64_grouped_guarded(p, g, m, v, n, chunk_group, groups, beta1, beta2, eps, step, rec, ema=None) -> None:
     """:func:`adamw64_grouped` behind :func:`grad_guard` (see :func:`adamw_grouped_guarded`)."""
     _adamw("adamw64_grouped_guarded", torch.float64, p, g, m, v, n, beta1, beta2, eps, step=step, chunk_group=chunk_group,
-           groups=groups, rec=rec)
+           groups=groups, rec=rec, ema=ema)
 
 
 # float64 pair head of Graphnetwork_phonon (csrc/pair_head_f64.hip), used by functional64's factored program

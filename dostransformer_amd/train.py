@@ -29,6 +29,7 @@ from . import param_groups as _pg
 from ._lib import DosxError, from_environ
 from ._models import DOSTransformerBase, GraphnetworkBase, _SEED_MOD, rank_seed_offset
 from .batch import CrystalBatch, bucket_sizes, graph_meta, pad_batch
+from .ema import WeightEma
 from .guard import StepGuard
 from .slots import Slot, SlotCache
 
@@ -43,16 +44,20 @@ _DP_MID_BUCKET = from_environ("DOSX_DP_MID_BUCKET", "0") == "1"
 _DP_CHECK = from_environ("DOSX_DP_CHECK", "0") == "1"
 
 
-class _AdamWState(StepGuard):
+class _AdamWState(StepGuard, WeightEma):
     """What Trainer and train64.Trainer64 share: the AdamW moments laid out like the model's flat parameters (in the flat
     buffer's dtype), their checkpoint in ``torch.optim.AdamW`` vocabulary, the per-step bump of the dropout seed and the
-    gradient guard of the optimizer step (``guard.StepGuard``: ``max_grad_norm`` / ``skip_nonfinite``).  Expects
+    gradient guard of the optimizer step (``guard.StepGuard``: ``max_grad_norm`` / ``skip_nonfinite``) and the exponential moving
+    average of the weights the AdamW launch keeps (``ema.WeightEma``: ``ema_decay`` / ``ema_warmup``, re-homed by name with the
+    moments).  Expects
     ``model``, ``_fp``, ``_m``, ``_v``, ``_slots``, ``step_count`` and the hyper-parameters ``lr``, ``betas``, ``eps``, ``wd``, ``beta``."""
 
     def _state(self, fp):
         """AdamW moments laid out like ``fp``.  When the parameters are re-homed (module moved to another device after
         ``load_state_dict``, a different dead-parameter set, ...) the moments follow BY NAME instead of being reset:
         ``step_count`` keeps counting, so zeroed moments would silently corrupt the bias correction."""
+        if self._ema_block:                # (also what a freeze() / update_trainable() inside the block runs into)
+            self._ema_refuse("_state (step, forward_backward, optimizer_step, state_dict, load_state_dict)")
         if self._fp is not fp:
             if getattr(self, "dist", None) is not None and fp.n_train != fp.total:
                 raise DosxError(f"{type(self).__name__}(dist=...) with frozen parameters ({len(fp.frozen)} of {len(fp.names)}): "
@@ -71,6 +76,7 @@ class _AdamWState(StepGuard):
                             raise RuntimeError(f"parameter {n} changed size under a running optimizer")
                         m[o:o + k].copy_(self._m[oo:oo + k])
                         v[o:o + k].copy_(self._v[oo:oo + k])
+            self._ema_rehome(fp, old)
             self._m, self._v, self._fp = m, v, fp
             self._slots = OrderedDict()
             if self._groups is not None:       # the chunk map belongs to the layout: rebuilt wherever the moments are re-homed
@@ -104,7 +110,8 @@ class _AdamWState(StepGuard):
     def _adamw_launch(self, fp, m, v, rec=None) -> None:
         """The optimizer's one launch for ``step_count``, the only place that chooses among the ``ops.adamw*`` functions: fp32 or
         float64 by the flat buffer, behind the guard's record ``rec`` or not, with the trainer's parameter groups or its one
-        ``lr`` / ``wd``.  ``flat[n_train:]`` are the frozen parameters, nothing steps them: no launch when everything is frozen."""
+        ``lr`` / ``wd``, keeping the weight average (``ema=``) or not.  ``flat[n_train:]`` are the frozen parameters, nothing steps
+        them (nor their average, which is the parameter itself): no launch when everything is frozen."""
         if not fp.n_train:
             return
         grouped, guarded = self._groups is not None, rec is not None
@@ -114,13 +121,19 @@ class _AdamWState(StepGuard):
             args = (self._chunk_group, st, self.betas[0], self.betas[1], self.eps, self.step_count)
         else:
             args = (self.lr, self.betas[0], self.betas[1], self.eps, self.wd) + (() if guarded else (self.step_count,))
-        getattr(ops, name)(fp.flat, fp.grad, m, v, fp.n_train, *args, *((rec,) if guarded else ()))
+        kw = {}
+        if self._ema_decay is not None:
+            kw["ema"] = self._ema_operand()
+            if guarded and not grouped:       # (the other three forms take the step anyway)
+                kw["step"] = self.step_count
+        getattr(ops, name)(fp.flat, fp.grad, m, v, fp.n_train, *args, *((rec,) if guarded else ()), **kw)
 
     def _reduce_gradients(self, fp) -> None:
         """Between the backward and the unguarded optimizer launch: nothing here; Trainer finishes its ``dist`` all-reduces."""
 
     def optimizer_step(self) -> None:
         """The flat AdamW launch, issued behind the (recorded) program: ``step`` changes every step."""
+        self._ema_refuse("optimizer_step")
         fp = self._fp if self._fp is not None else self.model.flat_params()
         m, v = self._state(fp)
         if self.guarded:                              # (never with dist: refused at construction)
@@ -138,7 +151,10 @@ class _AdamWState(StepGuard):
         another frozen set, by name; with anything frozen, ``trainable`` lists the names that were training (no such key: all).
 
         The trainer keeps ONE ``step`` for all parameters: a parameter unfrozen in the middle of a run starts from zero moments
-        under the run's bias correction, where ``torch.optim.AdamW`` would start a step count of its own for it."""
+        under the run's bias correction, where ``torch.optim.AdamW`` would start a step count of its own for it.
+
+        With ``ema_decay``, and only then: ``ema`` (the averaged weights, by name) and ``ema_hyper`` (``decay``, ``warmup``, ``t0``)."""
+        self._ema_refuse("state_dict")
         fp = self._fp if self._fp is not None else self.model.flat_params()
         m, v = self._state(fp)
         views = lambda buf: {n: buf[o:o + fp.P[n].numel()].view(fp.P[n].shape).detach().cpu().clone()
@@ -154,9 +170,11 @@ class _AdamWState(StepGuard):
         if self._groups is not None:       # (a run without groups writes the file it always wrote)
             sd["param_groups"] = [{"lr": grp["lr"], "weight_decay": grp["weight_decay"], "names": list(grp["names"])}
                                   for grp in self._groups]
+        self._ema_save(sd, views)
         return sd
 
     def load_state_dict(self, sd: dict) -> None:
+        self._ema_refuse("load_state_dict")
         fp = self._fp if self._fp is not None else self.model.flat_params()
         m, v = self._state(fp)
         missing = [n for n in fp.names if n not in sd["exp_avg"] or n not in sd["exp_avg_sq"]]
@@ -183,6 +201,7 @@ class _AdamWState(StepGuard):
         if self._groups is not None and saved is not None and len(saved) == len(self._groups):
             for grp, old in zip(self._groups, saved):      # by group index; another number of groups: the trainer keeps its own
                 grp["lr"], grp["weight_decay"] = float(old["lr"]), float(old["weight_decay"])
+        self._ema_load(sd, fp)
 
     def check(self) -> None:
         """Raise :class:`DosxError` if a column-split exchange of any step since the last clean check reported a stall
@@ -270,12 +289,19 @@ class Trainer(_AdamWState, SlotCache):
     which looks decay and step size up per 64-element chunk of the flat buffer; bit for bit the ungrouped kernel applied tensor by
     tensor with each tensor's values.  ``trainer.param_groups`` is read at every step: assigning ``["lr"]`` is a schedule.  With
     the guard, with frozen parameters, every mode; not under data parallelism.  None (the default): the launch it always was.
+
+    ``ema_decay=d`` (``ema_warmup=True``): the AdamW launch also keeps an exponential moving average of the weights
+    (``ema.WeightEma``; ``ema' = ema + (p' - ema)(1 - d_t)``, ``d_t = min(d, (1 + t) / (10 + t))`` under warm-up) - a step the guard
+    skips leaves it alone.  ``with trainer.ema_weights():`` evaluates under it, ``trainer.ema_state_dict()`` exports it,
+    ``state_dict()`` carries it.  Every mode, with the guard, frozen parameters and groups; not under data parallelism.  None
+    (the default): the launch and the checkpoint it always was.
     """
 
     def __init__(self, model: DOSTransformerBase, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2,
                  betas=(0.9, 0.999), eps: float = 1e-8, dist=None, graph: bool = False, replay: bool = False,
                  bucket=(8, 128), max_slots: int = 32, promote: float = 0.0, per_crystal_keys: bool = False,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
         if not isinstance(model, (DOSTransformerBase, GraphnetworkBase)):
             raise TypeError("Trainer drives DOSTransformer / DOSTransformer_phonon / Graphnetwork / Graphnetwork_phonon / mlp modules")
         model._require_fp32_program("Trainer")
@@ -300,6 +326,7 @@ class Trainer(_AdamWState, SlotCache):
         self._init_guard("Trainer", max_grad_norm, skip_nonfinite, dist)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, betas, eps
         self._init_param_groups("Trainer", param_groups, dist)
+        self._init_ema("Trainer", ema_decay, ema_warmup, dist)
         self.dist = dist
         self.graph = graph
         self.replay = replay
@@ -492,6 +519,7 @@ class Trainer(_AdamWState, SlotCache):
     def forward_backward(self, g, n_global: Optional[int] = None, _bump: bool = True) -> torch.Tensor:
         """Forward + loss + backward; leaves the gradients in the flat buffer.  Returns the loss
         (0-dim device tensor; for eDOS under data parallelism it is this rank's share)."""
+        self._ema_refuse("forward_backward")
         if _bump:                      # a direct forward_backward() + optimizer_step() loop draws fresh dropout masks too
             self._bump_dropout_seed()
         model = self.model
@@ -626,6 +654,7 @@ class Trainer(_AdamWState, SlotCache):
         included) and the bucket's recorded program is replayed — no intermediate batch object, no padding ops, no
         slot copy.  Same numbers as ``step(ds.collate(indices))`` (the counterpart of the loop body `main_phDOS.py:104-118`
         with a shuffling DataLoader)."""
+        self._ema_refuse("step_dataset")
         if not (self.replay or self.graph):
             return self.step(ds.collate(indices, n_max=n_max), n_global)
         model = self.model
@@ -710,6 +739,7 @@ class Trainer(_AdamWState, SlotCache):
                 self.dist.all_reduce_grads(fp.grad)
 
     def step(self, g, n_global: Optional[int] = None) -> torch.Tensor:
+        self._ema_refuse("step")
         self._bump_dropout_seed()
         loss = self._graph_step(g, n_global) if (self.graph or self.replay) else self.forward_backward(g, n_global, _bump=False)
         self.optimizer_step()

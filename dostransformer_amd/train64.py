@@ -55,17 +55,21 @@ class Trainer64(_AdamWState, SlotCache):
     ``max_grad_norm`` / ``skip_nonfinite``: the optimizer step behind the gradient guard (``guard.StepGuard``), as on
     ``train.Trainer``: clipping and "skip if non-finite" decided on the device, ``grad_norm`` / ``guard_report()`` / ``check()``.
     ``param_groups``: per-group ``lr`` / ``weight_decay`` in the one flat float64 AdamW launch, as on ``train.Trainer``.
+    ``ema_decay`` / ``ema_warmup``: a float64 exponential moving average of the weights kept by that launch, as on
+    ``train.Trainer``: ``ema_weights()``, ``ema_state_dict()``, the ``ema`` keys of ``state_dict()``.
     """
 
     _who = "Trainer64"            # what this driver calls itself in its refusals
 
     def __init__(self, model, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2, betas=(0.9, 0.999),
                  eps: float = 1e-8, replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
         self._require_model(model)
         self._init_guard(self._who, max_grad_norm, skip_nonfinite)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, tuple(betas), eps
         self._init_param_groups(self._who, param_groups)
+        self._init_ema(self._who, ema_decay, ema_warmup)
         self.replay = bool(replay)
         self.max_slots = int(max_slots)
         if self.max_slots < 1:
@@ -122,6 +126,7 @@ class Trainer64(_AdamWState, SlotCache):
 
     def forward_backward(self, g, _bump: bool = True) -> torch.Tensor:
         """Forward + loss + backward; leaves the gradients in the flat buffer.  Returns the loss (0-dim float64 device tensor)."""
+        self._ema_refuse("forward_backward")
         if _bump:                      # a direct forward_backward() + optimizer_step() loop draws fresh dropout masks too
             self._refuse(g)
             self._bump_dropout_seed()
@@ -185,6 +190,7 @@ class Trainer64(_AdamWState, SlotCache):
         bitwise ``step(pad_batch(ds.collate(indices, n_max=n_max), *bucket_sizes(N, E, *bucket)))``.  Otherwise it is
         ``step(ds.collate(indices, n_max=n_max))``.  ``n_max`` may exceed the selection's largest crystal, so that one value
         serves a whole dataset (with per-crystal keys and no dropout the numbers do not depend on it)."""
+        self._ema_refuse("step_dataset")
         if not (self.replay and self.bucket is not None):
             return self.step(ds.collate(indices, n_max=n_max))
         self._require_model(self.model)
@@ -211,6 +217,7 @@ class Trainer64(_AdamWState, SlotCache):
         return loss
 
     def step(self, g) -> torch.Tensor:
+        self._ema_refuse("step")
         self._refuse(g)
         self._bump_dropout_seed()
         loss = self.forward_backward(g, _bump=False)
@@ -235,7 +242,8 @@ class GraphnetworkTrainer64(Trainer64):
 
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
-                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None, **unknown):
+                 max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None,
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True, **unknown):
         if "beta" in unknown:
             raise ValueError(f"GraphnetworkTrainer64: beta={unknown['beta']} - the model has ONE output and its loss no second "
                              f"term to weigh")
@@ -243,7 +251,7 @@ class GraphnetworkTrainer64(Trainer64):
             raise TypeError(f"GraphnetworkTrainer64() got an unexpected keyword argument {sorted(unknown)[0]!r}")
         super().__init__(model, lr=lr, beta=1.0, weight_decay=weight_decay, betas=betas, eps=eps, replay=replay,
                          max_slots=max_slots, bucket=bucket, promote=promote, max_grad_norm=max_grad_norm,
-                         skip_nonfinite=skip_nonfinite, param_groups=param_groups)
+                         skip_nonfinite=skip_nonfinite, param_groups=param_groups, ema_decay=ema_decay, ema_warmup=ema_warmup)
         self._dead = None                 # the dead-parameter set of the first batch's node-feature width
 
     def _require_model(self, model) -> None:

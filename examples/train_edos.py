@@ -90,8 +90,16 @@ def parse_args(argv=None):
                     help="fine-tuning: train exactly the parameters whose names start with one of these prefixes, freeze the rest")
     ap.add_argument("--freeze", nargs="+", default=None, metavar="PREFIX",
                     help="fine-tuning: freeze the parameters whose names start with one of these prefixes")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY",
+                    help="keep an exponential moving average of the weights inside the AdamW launch (decay in [0, 1), e.g. 0.999); every "
+                         "evaluation also reports the metrics under the averaged weights, and the checkpoint carries both weight sets")
+    ap.add_argument("--no-ema-warmup", action="store_true", help="with --ema: the decay from the first step on, no min(decay, (1 + t) / (10 + t))")
+    ap.add_argument("--save-ema", default=None, metavar="PATH", help="with --ema: write the averaged model alone to PATH at the end of the run")
     param_groups.add_arguments(ap)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if (args.no_ema_warmup or args.save_ema) and args.ema is None:
+        ap.error("--no-ema-warmup / --save-ema need --ema DECAY")
+    return args
 
 
 def main(argv=None):
@@ -162,7 +170,8 @@ def _main(argv=None):
             print(f"param group {k}: lr {grp['lr']:.3g} weight_decay {grp['weight_decay']:.3g}, {len(grp['names'])} tensors")
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=bucket, promote=0.08,
                       per_crystal_keys=args.per_crystal_keys,      # AdamW(lr, weight_decay=1e-2), `:91`
-                      max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, param_groups=groups)
+                      max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, param_groups=groups,
+                      ema_decay=args.ema, ema_warmup=not args.no_ema_warmup)
     predictor = Predictor(model, bucket=bucket, per_crystal_keys=args.eval_per_crystal > 0 and not baseline)
     criterion_2 = torch.nn.L1Loss()                                                       # `main_eDOS.py:93`
 
@@ -200,6 +209,10 @@ def _main(argv=None):
                 raise
             print(f"warning: {e}")
         print(f"[ {epoch + 1} epochs ]valid_rmse:{v_rmse:.4f}|valid_mse:{v_mse:.4f}|valid_mae:{v_mae:.4f}|valid_r2:{v_r2:.4f}")
+        if args.ema is not None:                                   # the same evaluator under the averaged weights: a swap launch in, one out
+            with trainer.ema_weights():
+                e = run_test("valid")[:4]
+            print("[ {} epochs ]ema_valid_rmse:{:.4f}|ema_valid_mse:{:.4f}|ema_valid_mae:{:.4f}|ema_valid_r2:{:.4f}".format(epoch + 1, *e))
         improved = v_rmse < best_rmse or v_mae < best_mae
         if v_rmse < best_rmse:
             best_rmse = v_rmse
@@ -210,11 +223,19 @@ def _main(argv=None):
             test_m = run_test("test")[:4]
             print("[ {} epochs ]System:test_rmse:{:.4f}|test_mse:{:.4f}|test_mae:{:.4f}|test_r2:{:.4f}".format(epoch + 1, *test_m))
             checkpoint.save(args.out, model, trainer, extra={"epoch": epoch + 1, "valid_rmse": v_rmse, "test": list(test_m)})
+            if args.ema is not None:
+                with trainer.ema_weights():
+                    e = run_test("test")[:4]
+                print("[ {} epochs ]System:ema_test_rmse:{:.4f}|ema_test_mse:{:.4f}|ema_test_mae:{:.4f}|ema_test_r2:{:.4f}".format(epoch + 1, *e))
         best_losses.append(best_rmse)
         print("**System [Best epoch: {}] Best RMSE: {:.4f}|Best MSE: {:.4f} |Best MAE: {:.4f}|Best R2: {:.4f}**".format(best_epoch, *test_m))
         if len(best_losses) > int(args.es / args.eval) and best_losses[-1] == best_losses[-int(args.es / 5)]:   # `:166-167`
             print("Early stop!!")
             break
+    if args.save_ema:                                              # the averaged model alone: checkpoint.load(PATH, plain_model) reads it
+        with trainer.ema_weights():
+            checkpoint.save(args.save_ema, model, extra={"ema_decay": trainer.ema_decay})
+        print(f"averaged weights saved to {args.save_ema}")
     return {"best_epoch": best_epoch, "best_valid_rmse": best_rmse, "test": test_m, "train_loss": history}
 
 

@@ -47,6 +47,12 @@ embeddings and prompt tokens out of the weight decay, --layerwise-lr-decay D low
 
     python examples/train_phonon.py --init phonon_best.pt --group GN_encoder.,stacked_processor.,GN_decoder.:lr=1e-5 --no-decay-norms
     python examples/train_phonon.py --float64 --fused --layerwise-lr-decay 0.8 --epochs 2 --crystals 128 --hidden 64
+
+Averaged weights (fused trainers): --ema DECAY keeps an exponential moving average of the weights inside the AdamW launch
+(--no-ema-warmup: the decay from the first step on).  Every evaluation also prints the metrics under the averaged weights
+(trainer.ema_weights()), the checkpoint carries both weight sets, --save-ema PATH writes the averaged model alone.
+
+    python examples/train_phonon.py --ema 0.999 --eval-per-crystal 64 --save-ema phonon_ema.pt
 """
 import argparse
 import os
@@ -112,8 +118,18 @@ def _main(argv=None):
                     help="fine-tuning: train exactly the parameters whose names start with one of these prefixes, freeze the rest")
     ap.add_argument("--freeze", nargs="+", default=None, metavar="PREFIX",
                     help="fine-tuning: freeze the parameters whose names start with one of these prefixes")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY",
+                    help="fused trainers: keep an exponential moving average of the weights inside the AdamW launch (decay in [0, 1), "
+                         "e.g. 0.999); every evaluation also reports the metrics under the averaged weights, and the checkpoint "
+                         "carries both weight sets")
+    ap.add_argument("--no-ema-warmup", action="store_true", help="with --ema: the decay from the first step on, no min(decay, (1 + t) / (10 + t))")
+    ap.add_argument("--save-ema", default=None, metavar="PATH", help="with --ema: write the averaged model alone to PATH at the end of the run")
     param_groups.add_arguments(ap)
     args = ap.parse_args(argv)
+    if args.ema is not None and args.float64 and not args.fused:
+        ap.error("--ema belongs to the fused trainers: the fp32 run, or --float64 --fused")
+    if (args.no_ema_warmup or args.save_ema) and args.ema is None:
+        ap.error("--no-ema-warmup / --save-ema need --ema DECAY")
     if (args.clip_grad_norm is not None or args.skip_nonfinite) and args.float64 and not args.fused:
         ap.error("--clip-grad-norm / --skip-nonfinite belong to the fused trainers: the fp32 run, or --float64 --fused")
     if param_groups.wanted(args) and args.float64 and not args.fused:
@@ -156,7 +172,8 @@ def _main(argv=None):
     # coarse shape buckets: reshuffled batches then fall into a few dozen (N, E, n_max) buckets that are all recorded
     # within the first epoch (ghost padding is exact; it costs a few per cent of extra rows)
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=(32, 1024), promote=0.08,
-                      per_crystal_keys=args.per_crystal_keys, param_groups=_groups(args, model), **_guard_args(args))
+                      per_crystal_keys=args.per_crystal_keys, param_groups=_groups(args, model), **_guard_args(args),
+                      **_ema_args(args))
     predictor = Predictor(model, bucket=(32, 1024), per_crystal_keys=args.eval_per_crystal > 0 and not baseline)
     run_test = _tester(args, predictor, ds)
     best, history = float("inf"), []
@@ -173,12 +190,36 @@ def _main(argv=None):
         _check(trainer)                                           # once per evaluation: a stalled exchange voids the epoch
         print(f"[epoch {epoch + 1}/{args.epochs}] loss {loss:.4f} | {seen / dt:8.0f} crystals/s | "
               f"valid rmse {rmse:.4f} mse {mse:.4f} mae {mae:.4f} r2 {r2v:.4f}")
+        _ema_report(args, trainer, run_test, "valid")
         if rmse < best:
             best = rmse
             checkpoint.save(args.out, model, trainer)
             t = run_test("test")
             print(f"            test rmse {t[0]:.4f} mse {t[1]:.4f} mae {t[2]:.4f} r2 {t[3]:.4f}   (saved {args.out})")
+            _ema_report(args, trainer, run_test, "test")
+    _save_ema(args, model, trainer)
     return {"best_valid_rmse": best, "train_loss": history}
+
+
+def _ema_args(args):
+    return dict(ema_decay=args.ema, ema_warmup=not args.no_ema_warmup)
+
+
+def _ema_report(args, trainer, run_test, name):
+    """--ema: the split's metrics under the averaged weights - one swap launch in, the same evaluator (nothing re-recorded), one out."""
+    if args.ema is None:
+        return
+    with trainer.ema_weights():
+        t = run_test(name)
+    print(f"            ema {name} rmse {t[0]:.4f} mse {t[1]:.4f} mae {t[2]:.4f} r2 {t[3]:.4f}")
+
+
+def _save_ema(args, model, trainer):
+    """--save-ema PATH: the averaged model alone, as a checkpoint any plain module loads (checkpoint.load(PATH, model))."""
+    if args.save_ema:
+        with trainer.ema_weights():
+            checkpoint.save(args.save_ema, model, extra={"ema_decay": trainer.ema_decay})
+        print(f"averaged weights saved to {args.save_ema}")
 
 
 def _fine_tune(args, model):
@@ -302,12 +343,14 @@ def train_float64_fused(args, ds, dev):
     slots = dict(replay=args.replay, bucket=bucket if args.replay else None, promote=0.08 if args.replay else 0.0)
     if args.embedder == "graphnetwork":
         model = _fine_tune(args, _baseline64(args, dev))
-        trainer = GraphnetworkTrainer64(model, lr=args.lr, param_groups=_groups(args, model), **slots, **_guard_args(args))
+        trainer = GraphnetworkTrainer64(model, lr=args.lr, param_groups=_groups(args, model), **slots, **_guard_args(args),
+                                        **_ema_args(args))
     else:
         model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).double()
         model = model.set_program_dtype(torch.float64).set_per_crystal_keys(True).to(dev)
         _fine_tune(args, model)
-        trainer = Trainer64(model, lr=args.lr, beta=args.beta, param_groups=_groups(args, model), **slots, **_guard_args(args))
+        trainer = Trainer64(model, lr=args.lr, beta=args.beta, param_groups=_groups(args, model), **slots, **_guard_args(args),
+                            **_ema_args(args))
     evaluator = Predictor64(model, bucket=bucket) if args.replay else model       # (the module's per-crystal keys are on)
     run_test = _tester(args, evaluator, ds)
     train = ds["train"]
@@ -330,11 +373,14 @@ def train_float64_fused(args, ds, dev):
               f"valid rmse {rmse:.4f} mse {mse:.4f} mae {mae:.4f} r2 {r2v:.4f}"
               + (f" | slots {trainer.slot_misses} recorded, {trainer.slot_hits} replayed ({trainer.slot_promoted} promoted)"
                  if args.replay else ""))
+        _ema_report(args, trainer, run_test, "valid")
         if rmse < best:
             best = rmse
             checkpoint.save(args.out, model, trainer)
             t = run_test("test")
             print(f"            test rmse {t[0]:.4f} mse {t[1]:.4f} mae {t[2]:.4f} r2 {t[3]:.4f}   (saved {args.out})")
+            _ema_report(args, trainer, run_test, "test")
+    _save_ema(args, model, trainer)
     return {"best_valid_rmse": best, "train_loss": history}
 
 

@@ -1393,6 +1393,49 @@ int dosx_adamw_grouped_guarded_f64(double* p, const double* g, double* m, double
                                    const DosxAdamWGroups* groups, double beta1, double beta2, double eps, int step,
                                    const void* guard, dosx_stream_t stream);
 
+/* ---- AdamW that also keeps an exponential moving average of the parameters (the EMA instantiations: csrc/adamw.hip) ---------
+ * What torch.optim.swa_utils.AveragedModel with an EMA multi_avg_fn, torch-ema and timm's ModelEma do in a second pass over the
+ * parameters: here the thread that holds the new parameter p' in registers also updates the average,
+ *     ema' = ema + (p' - ema) (1 - d_t)        fp32: fmaf(fmaf(p', 1.f, -ema), omd, ema); float64: fma(p' - ema, omd, ema)
+ * with omd = (T)1 - (T)d_t: the expression of the first-moment update with g := p', m := ema, 1 - beta1 := omd (vector body and
+ * scalar tail alike), so the bits of ema' are those the plain entry leaves in m for these operands.  p', m', v' are bit for bit
+ * those of the launch without the average; ema is read and written with the same 16-byte accesses, nothing else is.
+ * Traffic: 36 B (fp32) / 72 B (float64) per parameter against 28 / 56.
+ *
+ * DosxAdamWEma (HOST memory, read during the call): ema = DEVICE buffer laid out like p, at least n elements, 16-byte aligned,
+ *   not p; decay in [0, 1); warmup != 0: d_t = min(decay, (1 + t) / (10 + t)), else d_t = decay, with t = T_adamw - t0 - AdamW's
+ *   time (`step` of the unguarded forms, the record's t of the guarded ones: a skipped step does not advance the warm-up) less
+ *   t0, AdamW's time when averaging began.  d_t is evaluated in double and rounded once to the buffers' type, on the host for
+ *   `step` and - guarded, when the record's t is not `step` - on the device by the same function (dosx_adamw_ema_decay gives
+ *   it: elem_bytes 4 -> rounded through float, else double; t as above).
+ * dosx_adamw_ema / _f64: ONE entry per type for the four forms.  chunk_group and groups: both NULL - one (lr, weight_decay), the
+ *   arguments - or both given - dosx_adamw_grouped*'s operands, lr and weight_decay are not read.  guard: NULL, or the record of
+ *   dosx_grad_guard_* - then the launch is dosx_adamw_guarded* / _grouped_guarded*'s (grad_scale is not read, `step` is the attempt
+ *   count the guard was given); skip != 0 returns before any store, the one to ema included.
+ * Refused with -22 and a message: what the form in question refuses (n = 0 is a no-op behind the checks), a chunk map without
+ *   groups or the reverse, a NULL descriptor or ema, ema off a 16-byte boundary, ema overlapping p, decay NaN or outside [0, 1),
+ *   t0 < 0 or t0 >= step.
+ *
+ * dosx_swap_buffers: a[0, bytes) <-> b[0, bytes) in one launch (16-byte vectors, DOSX_SWAP_THREADS threads, at most
+ *   DOSX_SWAP_MAX_BLOCKS workgroups that stride over the vectors) - what puts the average in the parameters' place and back;
+ *   blind to the element type.  Refuses NULL, bytes < 0, bytes % 16 != 0, buffers off a 16-byte boundary and buffers that
+ *   overlap with -22 and a message; bytes = 0 is a no-op. */
+#define DOSX_SWAP_THREADS 256
+#define DOSX_SWAP_MAX_BLOCKS 2048
+typedef struct DosxAdamWEma {
+  void* ema;
+  double decay;
+  int32_t warmup, t0;
+} DosxAdamWEma;
+int dosx_adamw_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                   float weight_decay, int step, float grad_scale, const void* chunk_group, const DosxAdamWGroups* groups,
+                   const void* guard, const DosxAdamWEma* ema, dosx_stream_t stream);
+int dosx_adamw_ema_f64(double* p, const double* g, double* m, double* v, int64_t n, double lr, double beta1, double beta2,
+                       double eps, double weight_decay, int step, const void* chunk_group, const DosxAdamWGroups* groups,
+                       const void* guard, const DosxAdamWEma* ema, dosx_stream_t stream);
+double dosx_adamw_ema_decay(double decay, int warmup, int t, int elem_bytes);
+int dosx_swap_buffers(void* a, void* b, int64_t bytes, dosx_stream_t stream);
+
 /* ---- evaluation metrics (csrc/eval.hip) -----------------------------------------------------------------------------------
  * utils.py:76-89 / :127-139 evaluated one crystal at a time (what the reference computes at batch_size = 1).
  * pred, y: [B,S] rows with unit inner stride, rows S apart.  clamp0 != 0: both are clamped at 0 first (utils.py:74-76).
