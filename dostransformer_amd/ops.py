@@ -1671,6 +1671,53 @@ def sum_to(src, n, dst):
     _call("dosx_sum", _p(src), int(n), _p(dst), _stream())
 
 
+# per-crystal losses (csrc/loss_rows.hip; include/dosx.h: dosx_loss_rows / dosx_loss_rows_f64): the trainers' names -> enumerators
+LOSS_KINDS = {"crystal_rmse": _abi.DOSX_LOSS_RMSE, "mse": _abi.DOSX_LOSS_MSE, "mae": _abi.DOSX_LOSS_MAE, "huber": _abi.DOSX_LOSS_HUBER}
+
+
+def _loss_rows(who: str, dt: torch.dtype, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global) -> None:
+    if isinstance(kind, str):
+        if kind not in LOSS_KINDS:
+            raise ValueError(f"{who}: kind {kind!r} is not one of {sorted(LOSS_KINDS)}")
+        kind = LOSS_KINDS[kind]
+    if int(kind) == _abi.DOSX_LOSS_HUBER and (delta is None or not 0.0 < float(delta) < float("inf")):
+        raise ValueError(f"{who}: the Huber kind needs a finite delta > 0, got {delta}")
+    ts = {"pg": pg, "ps": ps, "y": y, "dpg": dpg, "dps": dps, "per_crystal": per_crystal, "loss": loss}
+    for k, t in ts.items():
+        if k in ("pg", "y", "dpg", "loss") and t is None:
+            raise TypeError(f"{who}: {k} is required (only ps with dps, and per_crystal, may be None)")
+        if t is not None and (t.dtype != dt or not t.is_cuda):
+            raise TypeError(f"{who}: {k} must be a {dt} CUDA tensor, got {t.dtype} on {t.device}")
+    if (ps is None) != (dps is None):
+        raise ValueError(f"{who}: ps and dps are both given (two outputs) or both None (one output)")
+    if pg.dim() != 2 or pg.shape[0] < 1 or pg.shape[1] < 1:
+        raise ValueError(f"{who}: pg {tuple(pg.shape)}: want [B,S] with B, S >= 1")
+    B, S = int(pg.shape[0]), int(pg.shape[1])
+    if any(t is not None and t.numel() != B * S for t in (ps, y, dpg, dps)) or loss.numel() < 1 or \
+            (per_crystal is not None and per_crystal.numel() != B):
+        raise ValueError(f"{who}: " + ", ".join(f"{k} {tuple(t.shape)}" for k, t in ts.items() if t is not None)
+                         + ": want B*S elements in ps, y, dpg, dps, B in per_crystal and at least 1 in loss")
+    for k, t in ts.items():
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"{who}: {k} must be contiguous (row slices of a table are), got strides {t.stride()}")
+    _call("dosx_loss_rows" if dt == torch.float32 else "dosx_loss_rows_f64", pg.data_ptr(), _p(ps), y.data_ptr(), B, S,
+          B if B_global is None else int(B_global), int(kind), int(bool(clamp_target)), float(beta),
+          0.0 if delta is None else float(delta), dpg.data_ptr(), _p(dps), _p(per_crystal), loss.data_ptr(), _stream(),
+          w=lambda: ("loss_rows", "loss_rows_kernel", "hbm", (2.0 if ps is None else 3.0) * pg.element_size() * 2 * B * S,
+                     1 if per_crystal is None else 2))
+
+
+def loss_rows(pg: torch.Tensor, ps: Optional[torch.Tensor], y: torch.Tensor, kind, *, clamp_target: bool = False,
+              beta: float = 1.0, delta: Optional[float] = None, dpg: torch.Tensor, dps: Optional[torch.Tensor] = None,
+              per_crystal: Optional[torch.Tensor] = None, loss: torch.Tensor, B_global: Optional[int] = None) -> None:
+    """Per-crystal loss of the [B,S] predictions pg (and ps) against y with its gradient (include/dosx.h: dosx_loss_rows):
+    ``l_b = f(pg_b) + beta f(ps_b)`` with f the crystal's RMSE, MSE, MAE or Huber(``delta``) term - ``kind`` a key of
+    :data:`LOSS_KINDS` or its enumerator -, ``per_crystal[b] = l_b`` (optional), ``loss[0] = sum_b l_b / B_global`` (default B) and
+    dpg / dps the gradient of loss[0].  ``clamp_target``: the eDOS target ``max(y, 0)``.  ``ps = dps = None``: a model with one
+    output.  All float32, contiguous (row slices of larger tables are); a crystal whose RMSE is 0 gets a zero gradient."""
+    _loss_rows("loss_rows", torch.float32, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global)
+
+
 # ---- guarded optimizer step (csrc/step_guard.hip; include/dosx.h: DosxStepGuard) -----------------------------------------------
 _GUARD_WORDS = C.sizeof(_abi.StepGuard) // 8
 _STATUS_ADDRESS: dict = {}
@@ -2267,6 +2314,13 @@ def loss_phonon64(pg: torch.Tensor, ps: torch.Tensor, y: torch.Tensor, beta: flo
                          f"dps {tuple(dps.shape)}, loss {tuple(loss.shape)}" + ("" if sse is None else f", sse {tuple(sse.shape)}"))
     _call("dosx_loss_phonon_f64", pg.data_ptr(), ps.data_ptr(), y.data_ptr(), float(beta), dpg.data_ptr(), dps.data_ptr(),
           loss.data_ptr(), _p(sse), count, _stream())
+
+
+def loss_rows64(pg: torch.Tensor, ps: Optional[torch.Tensor], y: torch.Tensor, kind, *, clamp_target: bool = False,
+                beta: float = 1.0, delta: Optional[float] = None, dpg: torch.Tensor, dps: Optional[torch.Tensor] = None,
+                per_crystal: Optional[torch.Tensor] = None, loss: torch.Tensor, B_global: Optional[int] = None) -> None:
+    """:func:`loss_rows` on float64 operands (include/dosx.h: dosx_loss_rows_f64)."""
+    _loss_rows("loss_rows64", torch.float64, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global)
 
 
 def adamw64(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, n: int, lr: float, beta1: float, beta2: float,

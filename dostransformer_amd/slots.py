@@ -62,6 +62,7 @@ class Slot:
         self.prog = None                           # the first (or only) recorded program
         self.plan = []                             # train.Trainer(replay=True): programs separated by the collectives
         self.keep = self.loss = self.out = self.sse = None
+        self.crystal = None                        # per-crystal losses of the step (trainers' loss=...), else None
         self.scratch = None
         self._loaded = None
 

@@ -238,6 +238,42 @@ class _AdamWState(StepGuard, WeightEma):
         if seed is not None and self.model.training and getattr(self.model, "_attn_drop", 0.0) > 0.0:
             seed.add_(1)
 
+    # ---- the objective (ops.LOSS_KINDS; include/dosx.h: dosx_loss_rows / dosx_loss_rows_f64) ----------------------------------
+    loss = None                       # None: the reference driver's loss, the launches the step always issued; else a key of LOSS_KINDS
+    huber_delta = None
+    crystal_losses = None             # [B] device tensor, the last step's l_b (valid until the next step); None under the default
+
+    def _init_loss(self, who: str, loss, huber_delta, dist=None) -> None:
+        """``loss=`` / ``huber_delta=`` of a trainer's constructor.  Constructor arguments like ``beta``: not part of ``state_dict()``."""
+        self.loss = self.huber_delta = self.crystal_losses = None
+        names = ", ".join(repr(k) for k in ops.LOSS_KINDS)
+        if loss is not None and loss not in ops.LOSS_KINDS:
+            raise ValueError(f"{who}(loss={loss!r}): not one of {names} (or None: the reference's loss)")
+        if loss == "huber":
+            if huber_delta is None or not 0.0 < float(huber_delta) < float("inf"):
+                raise ValueError(f"{who}(loss='huber') needs a finite huber_delta > 0, got {huber_delta}")
+        elif huber_delta is not None:
+            raise ValueError(f"{who}(loss={loss!r}, huber_delta={huber_delta}): huber_delta belongs to loss='huber' alone "
+                             f"(loss is None or one of {names})")
+        if loss is not None and dist is not None:
+            raise DosxError(f"{who}(loss=...) is a single-GPU mode: not with dist (data parallelism)")
+        self.loss, self.huber_delta = loss, None if huber_delta is None else float(huber_delta)
+
+    def _loss_rows(self, alloc, dev, pg, ps, y, clamp: bool, dpg, dps):
+        """The one launch site of the per-crystal losses: -> (per-crystal l_b [B], loss 0-dim), both on static buffers when
+        the step is being recorded.  ``ps = dps = None``: a one-output model (``beta`` is not read then)."""
+        B = int(pg.shape[0])
+        per, loss = alloc(dev, B), alloc(dev, 1)
+        fn = ops.loss_rows if pg.dtype == torch.float32 else ops.loss_rows64
+        fn(pg, ps, y, self.loss, clamp_target=clamp, beta=self.beta, delta=self.huber_delta, dpg=dpg, dps=dps, per_crystal=per,
+           loss=loss, B_global=B)
+        return per, loss[0]
+
+    def _require_whole_batch(self, B: int, n_global) -> None:
+        if self.loss is not None and int(n_global) != int(B):
+            raise ValueError(f"{type(self).__name__}(loss={self.loss!r}): n_global={n_global} but the batch holds {B} crystals "
+                             f"(the per-crystal losses are a single-GPU mode)")
+
 
 class _Width:
     """Stands in for a batch where only the node-feature width matters (FusedModel._extra_dead reads ``g.x.shape[1]``)."""
@@ -257,8 +293,9 @@ class Trainer(_AdamWState, SlotCache):
     ``transformer_source`` attend over each crystal's own atoms, forward and backward, instead of the rows that pad it to the
     batch's largest crystal - the step then learns what the reference computes at ``batch_size = 1``, where it trains the
     phonon model and evaluates both (`main_phDOS.py:52-55`, `main_eDOS.py:55-56`); for eDOS the phantom node counts as an atom, as
-    it does there.  Eager, ``replay=True`` and ``graph=True`` alike (the bucket's own ``graph_ptr`` is the operand); the loss is
-    unchanged.  Not under data parallelism.
+    it does there.  Eager, ``replay=True`` and ``graph=True`` alike (the bucket's own ``graph_ptr`` is the operand).  The switch does
+    not touch the loss: the default phonon loss is still ONE RMSE pooled over the batch, whose gradient is not the mean of the
+    batch-1 gradients - ``loss="crystal_rmse"`` is the objective that matches batch-1 training.  Not under data parallelism.
 
     The GNN-only baselines - ``Graphnetwork``, ``Graphnetwork_phonon`` (fp32 parameters) and ``embedder_eDOS.mlp.mlp`` - train through
     the same step (eager, ``replay=True``, ``graph=True``, ``step_dataset``, checkpoints) with their output head on its rank
@@ -295,13 +332,24 @@ class Trainer(_AdamWState, SlotCache):
     skips leaves it alone.  ``with trainer.ema_weights():`` evaluates under it, ``trainer.ema_state_dict()`` exports it,
     ``state_dict()`` carries it.  Every mode, with the guard, frozen parameters and groups; not under data parallelism.  None
     (the default): the launch and the checkpoint it always was.
+
+    ``loss="crystal_rmse" | "mse" | "mae" | "huber"`` (``huber_delta=X`` with the last, and only with it) replaces the driver's loss
+    by the mean over crystals of each crystal's own RMSE, MSE, MAE or ``torch.nn.HuberLoss(delta=X)`` term, ``f(dos_global) + beta
+    f(dos_system)`` for the two-output models - one entry, ``dosx_loss_rows`` (csrc/loss_rows.hip), in place of the loss launches;
+    eDOS models keep their target clamp.  ``"crystal_rmse"`` is the reference's phonon objective at its ``batch_size = 1`` (with
+    ``per_crystal_keys=True`` a step on B crystals follows the mean of the B batch-1 gradients); on an eDOS model it is the default
+    objective and trains the same bits.  ``trainer.crystal_losses`` is then the last step's per-crystal losses, a ``[B]`` device
+    tensor (under replay a view of the bucket's static buffer) valid until the next step.  Every mode, with the guard, frozen
+    parameters, groups and the average; ``n_global`` must be the batch's own count; not under data parallelism.  A constructor
+    argument like ``beta``: not in ``state_dict()``.  None (the default): the reference's loss, the launches it always issued.
     """
 
     def __init__(self, model: DOSTransformerBase, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2,
                  betas=(0.9, 0.999), eps: float = 1e-8, dist=None, graph: bool = False, replay: bool = False,
                  bucket=(8, 128), max_slots: int = 32, promote: float = 0.0, per_crystal_keys: bool = False,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True, loss: Optional[str] = None,
+                 huber_delta: Optional[float] = None):
         if not isinstance(model, (DOSTransformerBase, GraphnetworkBase)):
             raise TypeError("Trainer drives DOSTransformer / DOSTransformer_phonon / Graphnetwork / Graphnetwork_phonon / mlp modules")
         model._require_fp32_program("Trainer")
@@ -327,6 +375,7 @@ class Trainer(_AdamWState, SlotCache):
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, betas, eps
         self._init_param_groups("Trainer", param_groups, dist)
         self._init_ema("Trainer", ema_decay, ema_warmup, dist)
+        self._init_loss("Trainer", loss, huber_delta, dist)
         self.dist = dist
         self.graph = graph
         self.replay = replay
@@ -368,6 +417,7 @@ class Trainer(_AdamWState, SlotCache):
             st_n_global = m.num_graphs
         model, dev, cfg = self.model, fp.flat.device, self.model._cfg
         B, S = m.num_graphs, cfg.S
+        self._require_whole_batch(B, st_n_global)
         if self._baseline:
             out = model._program_fwd(fp.P, g, m, factored_head=True)
             y = Fn._f32(g.phdos).reshape(B, S) if self.kind == "phonon" else Fn._f32(g.y_ft).reshape(-1)
@@ -377,6 +427,9 @@ class Trainer(_AdamWState, SlotCache):
         st = {"ctx": ctx, "dos": dos, "out": (dg, xL, ds), "B": B, "S": S}
         if self.kind == "phonon":
             st["y"] = Fn._f32(g.phdos).reshape(B, S)
+            if self.loss is not None:      # a per-crystal loss: one entry in _part_b, no SSE pair
+                st["split_loss"] = False
+                return st
             st["sse"] = Fn._empty(dev, 2)
             st["split_loss"] = self.dist is not None or int(st_n_global) != B
             if st["split_loss"]:           # two-phase loss: ranks exchange the SSE pair in between, and / or the loss is
@@ -392,7 +445,9 @@ class Trainer(_AdamWState, SlotCache):
         if self._baseline:
             return self._part_b_baseline(fp, m, st, n_global)
         ddos = Fn._empty(dev, *dos.shape)
-        if self.kind == "phonon":
+        if self.loss is not None:          # eDOS clamps its target at 0 (main_eDOS.py:113), phonon does not; n_global == B (_part_a)
+            st["crystal"], loss = self._loss_rows(Fn._empty, dev, dos[:B], dos[B:], st["y"], self.kind != "phonon", ddos[:B], ddos[B:])
+        elif self.kind == "phonon":
             loss = Fn._empty(dev, 1)
             if st["split_loss"] or int(n_global) != B:
                 if not st["split_loss"]:
@@ -416,12 +471,17 @@ class Trainer(_AdamWState, SlotCache):
 
     def _part_b_baseline(self, fp, m, st, n_global: int):
         """One-output loss + backward program of a GNN-only baseline.  The loss entries in their one-output use (include/dosx.h:
-        ps = pg, beta = 0: the loss is rmse(pg) exactly, the second gradient goes to scratch)."""
+        ps = pg, beta = 0: the loss is rmse(pg) exactly, the second gradient goes to scratch); with ``loss=...`` the per-crystal
+        entry in its own one-output form (ps == NULL)."""
         dev = fp.flat.device
         B, S, dos = st["B"], st["S"], st["dos"]
         if int(n_global) != B:
             raise ValueError(f"Trainer({type(self.model).__name__}): n_global={n_global} but the batch holds {B} crystals "
                              f"(no data parallelism for the GNN-only baselines)")
+        if self.loss is not None:          # the one-output form of the entry: no second gradient, no scratch
+            ddos = Fn._empty(dev, B, S)
+            st["crystal"], loss = self._loss_rows(Fn._empty, dev, dos, None, st["y"], self.kind != "phonon", ddos, None)
+            return self._bwd_baseline(fp, m, st, ddos, loss)
         ddos, scr = Fn._empty(dev, B, S), Fn._empty(dev, B, S)
         if self.kind == "phonon":
             loss = Fn._empty(dev, 1)
@@ -432,7 +492,10 @@ class Trainer(_AdamWState, SlotCache):
             ops.loss_edos(dos, dos, st["y"], 0.0, B, S, B, ddos, scr, lp)
             ops.sum_to(lp, B, lp[B:])
             loss = lp[B]
-        sink = ops.GradSink(dev)
+        return self._bwd_baseline(fp, m, st, ddos, loss)
+
+    def _bwd_baseline(self, fp, m, st, ddos, loss):
+        sink = ops.GradSink(fp.flat.device)
         self.model._bwd_fn(fp.P, fp.G, self.model._cfg, m, st["ctx"], ddos, None, sink, factored_head=True)
         self._wgrad_keys = sink.wgrad_keys
         sink.release()
@@ -536,6 +599,7 @@ class Trainer(_AdamWState, SlotCache):
                 self.dist.all_reduce_sse(st["sse"])
             loss = self._part_b(fp, m, st, ng)
         self._stats = self._make_stats(names)
+        self.crystal_losses = st.get("crystal")
         return loss
 
     # ---- graph path ------------------------------------------------------------------------------
@@ -562,7 +626,7 @@ class Trainer(_AdamWState, SlotCache):
                         loss = self._part_b(fp, m, st, ng)
         slot.stats = self._make_stats(names)
         slot.keep = (st, loss)            # keeps the graph-owned outputs from being recycled
-        slot.loss, slot.out, slot.sse = loss, st["out"], st.get("sse")
+        slot.loss, slot.out, slot.sse, slot.crystal = loss, st["out"], st.get("sse"), st.get("crystal")
 
     def _record(self, slot: Slot, fp, ng: int) -> None:
         """Run the step once on the slot's static buffers while recording every launch."""
@@ -591,13 +655,13 @@ class Trainer(_AdamWState, SlotCache):
         slot.plan, slot.prog = plan, plan[0][1]
         slot.stats = self._make_stats([fn.__name__ for kind, prog in plan if kind == "prog" for fn, _ in prog.prog])
         slot.keep = (st, loss)
-        slot.loss, slot.out, slot.sse = loss, st["out"], st.get("sse")
+        slot.loss, slot.out, slot.sse, slot.crystal = loss, st["out"], st.get("sse"), st.get("crystal")
 
     def _run_slot(self, slot: Slot, fp, ng: int, fresh: bool) -> torch.Tensor:
         """The step on a bucket whose static buffers hold the batch: record / capture on first use, replay afterwards."""
         if fresh and self.replay:
             self._record(slot, fp, ng)       # this IS the step for this batch (run + record)
-            self.last_outputs, self._stats = slot.out, slot.stats
+            self.last_outputs, self._stats, self.crystal_losses = slot.out, slot.stats, slot.crystal
             return slot.loss
         if fresh:
             self._capture(slot, fp, ng)
@@ -620,7 +684,7 @@ class Trainer(_AdamWState, SlotCache):
             if slot.graph_b is not None:
                 self.dist.all_reduce_sse(slot.sse)
                 slot.graph_b.replay()
-        self.last_outputs = slot.out
+        self.last_outputs, self.crystal_losses = slot.out, slot.crystal
         return slot.loss
 
     def _graph_step(self, g: CrystalBatch, n_global: Optional[int]) -> torch.Tensor:
@@ -636,6 +700,7 @@ class Trainer(_AdamWState, SlotCache):
             g = pad_batch(g, *bucket_sizes(m.num_nodes, m.num_edges, *self.bucket))
             m = g.meta
         ng = self._n_global(m.num_graphs, n_global, g)
+        self._require_whole_batch(m.num_graphs, ng)              # (before a slot is made, not inside its recording)
         key = (m.num_nodes, m.num_edges, m.num_graphs, m.n_max, ng, m.seg_tile is not None)
         slot = self._lookup(key)
         fresh = slot is None
@@ -687,6 +752,7 @@ class Trainer(_AdamWState, SlotCache):
                 if lo != hi:
                     raise ValueError(f"ranks stepped on {lo}..{hi} crystals without an explicit n_global")
             ng = B * self.dist.world
+        self._require_whole_batch(B, ng)
         tiled = True
         key = (n_pad, e_pad, B, n_max, ng, tiled)
         slot = self._lookup(key, allow_promote=True)

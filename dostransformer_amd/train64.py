@@ -57,6 +57,10 @@ class Trainer64(_AdamWState, SlotCache):
     ``param_groups``: per-group ``lr`` / ``weight_decay`` in the one flat float64 AdamW launch, as on ``train.Trainer``.
     ``ema_decay`` / ``ema_warmup``: a float64 exponential moving average of the weights kept by that launch, as on
     ``train.Trainer``: ``ema_weights()``, ``ema_state_dict()``, the ``ema`` keys of ``state_dict()``.
+    ``loss`` / ``huber_delta``: a per-crystal objective in place of the pooled RMSE (``"crystal_rmse"``, ``"mse"``, ``"mae"``,
+    ``"huber"``: ``dosx_loss_rows_f64``), as on ``train.Trainer``; ``crystal_losses`` is then the last step's ``[B]`` float64
+    per-crystal losses.  With ``set_per_crystal_keys(True)`` a ``"crystal_rmse"`` step follows the mean of the reference's
+    batch-1 gradients.  None (the default): the launches it always issued.
     """
 
     _who = "Trainer64"            # what this driver calls itself in its refusals
@@ -64,12 +68,15 @@ class Trainer64(_AdamWState, SlotCache):
     def __init__(self, model, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2, betas=(0.9, 0.999),
                  eps: float = 1e-8, replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = True):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True, loss: Optional[str] = None,
+                 huber_delta: Optional[float] = None):
         self._require_model(model)
         self._init_guard(self._who, max_grad_norm, skip_nonfinite)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, tuple(betas), eps
         self._init_param_groups(self._who, param_groups)
         self._init_ema(self._who, ema_decay, ema_warmup)
+        self._init_loss(self._who, loss, huber_delta)
+        self._crystal = None              # the per-crystal losses of the program just issued (loss=...), else None
         self.replay = bool(replay)
         self.max_slots = int(max_slots)
         if self.max_slots < 1:
@@ -115,10 +122,15 @@ class Trainer64(_AdamWState, SlotCache):
         B, S = m.num_graphs, cfg.S
         dos, xL, ctx = F64.dostransformer_phonon_fwd(fp.P, cfg, g, m, drop=drop, per_crystal_keys=model.per_crystal_keys)
         y = F64._f64(g.phdos).reshape(B, S)
-        ddos, loss = ops.alloc64(dev, 2 * B, S), ops.alloc64(dev, 1)
-        ops.loss_phonon64(dos[:B], dos[B:], y, self.beta, ddos[:B], ddos[B:], loss)
+        ddos = ops.alloc64(dev, 2 * B, S)
+        if self.loss is not None:
+            self._crystal, loss = self._loss_rows(ops.alloc64, dev, dos[:B], dos[B:], y, False, ddos[:B], ddos[B:])
+        else:
+            loss = ops.alloc64(dev, 1)
+            ops.loss_phonon64(dos[:B], dos[B:], y, self.beta, ddos[:B], ddos[B:], loss)
+            loss = loss[0]
         F64.dostransformer_phonon_bwd(fp.P, fp.G, cfg, m, ctx, ddos, None)
-        return loss[0], (dos[:B], xL, dos[B:])
+        return loss, (dos[:B], xL, dos[B:])
 
     def _set_outputs(self, out, n_real: Optional[int]) -> None:
         """(dos_global, x_L, dos_system) of the step; the ghost rows of a padded batch's x_L are cut off."""
@@ -137,6 +149,7 @@ class Trainer64(_AdamWState, SlotCache):
                 return self._slot_step(fp, g, m, drop)
             loss, out = self._program(fp, g, m, drop)
             self._set_outputs(out, getattr(g, "real_nodes", None))
+            self.crystal_losses = self._crystal
             return loss
 
     # ---- replay --------------------------------------------------------------------------------------------------------
@@ -153,6 +166,7 @@ class Trainer64(_AdamWState, SlotCache):
         else:
             slot.prog.run()
         self._set_outputs(slot.out, getattr(slot.g, "real_nodes", None))
+        self.crystal_losses = slot.crystal
         return slot.loss
 
     def _slot_step(self, fp, g, m: GraphMeta, drop) -> torch.Tensor:
@@ -181,6 +195,7 @@ class Trainer64(_AdamWState, SlotCache):
             ops.RECORDER.begin()
             slot.loss, slot.out = self._program(fp, g, m, drop)
             slot.prog = ops.RECORDER.end()
+        slot.crystal = self._crystal
 
     def step_dataset(self, ds, indices, n_max: Optional[int] = None) -> torch.Tensor:
         """One training step on the crystals ``indices`` of a device-resident ``loader.DeviceDataset`` (float64 tables:
@@ -237,13 +252,15 @@ class GraphnetworkTrainer64(Trainer64):
     dropout, no softmax switch: a slot's key is its (padded) shape.  Which node encoder is dead (``node_encoder`` against
     ``node_encoder_prompt``) follows the node-feature width and is fixed by the first batch or dataset; a batch of the other
     width is refused.  ``replay``, ``bucket``, ``promote``, ``step_dataset``, ``state_dict`` / ``load_state_dict`` and
-    ``max_slots`` are ``Trainer64``'s.  Limits: single GPU, no HIP-graph mode."""
+    ``max_slots`` are ``Trainer64``'s, and so are ``loss`` / ``huber_delta`` (the entry's one-output form: ``ps == NULL``, no scratch
+    gradient) with ``crystal_losses``.  Limits: single GPU, no HIP-graph mode."""
     _who = "GraphnetworkTrainer64"
 
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None,
-                 ema_decay: Optional[float] = None, ema_warmup: bool = True, **unknown):
+                 ema_decay: Optional[float] = None, ema_warmup: bool = True, loss: Optional[str] = None,
+                 huber_delta: Optional[float] = None, **unknown):
         if "beta" in unknown:
             raise ValueError(f"GraphnetworkTrainer64: beta={unknown['beta']} - the model has ONE output and its loss no second "
                              f"term to weigh")
@@ -251,7 +268,8 @@ class GraphnetworkTrainer64(Trainer64):
             raise TypeError(f"GraphnetworkTrainer64() got an unexpected keyword argument {sorted(unknown)[0]!r}")
         super().__init__(model, lr=lr, beta=1.0, weight_decay=weight_decay, betas=betas, eps=eps, replay=replay,
                          max_slots=max_slots, bucket=bucket, promote=promote, max_grad_norm=max_grad_norm,
-                         skip_nonfinite=skip_nonfinite, param_groups=param_groups, ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         skip_nonfinite=skip_nonfinite, param_groups=param_groups, ema_decay=ema_decay, ema_warmup=ema_warmup,
+                         loss=loss, huber_delta=huber_delta)
         self._dead = None                 # the dead-parameter set of the first batch's node-feature width
 
     def _require_model(self, model) -> None:
@@ -283,10 +301,15 @@ class GraphnetworkTrainer64(Trainer64):
         B, S = m.num_graphs, cfg.S
         dos, ctx = F64.graphnetwork_phonon_fwd(fp.P, cfg, g, m, factored_head=True)
         y = F64._f64(g.phdos).reshape(B, S)
-        ddos, scratch, loss = ops.alloc64(dev, B, S), ops.alloc64(dev, B, S), ops.alloc64(dev, 1)
-        ops.loss_phonon64(dos, dos, y, 0.0, ddos, scratch, loss)
+        ddos = ops.alloc64(dev, B, S)
+        if self.loss is not None:          # the one-output form of the entry: no second gradient, no scratch
+            self._crystal, loss = self._loss_rows(ops.alloc64, dev, dos, None, y, False, ddos, None)
+        else:
+            scratch, loss = ops.alloc64(dev, B, S), ops.alloc64(dev, 1)
+            ops.loss_phonon64(dos, dos, y, 0.0, ddos, scratch, loss)
+            loss = loss[0]
         F64.graphnetwork_phonon_bwd(fp.P, fp.G, cfg, m, ctx, ddos, factored_head=True)
-        return loss[0], dos
+        return loss, dos
 
     def _set_outputs(self, out, n_real: Optional[int]) -> None:
         self.last_outputs = out

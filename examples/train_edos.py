@@ -95,10 +95,17 @@ def parse_args(argv=None):
                          "evaluation also reports the metrics under the averaged weights, and the checkpoint carries both weight sets")
     ap.add_argument("--no-ema-warmup", action="store_true", help="with --ema: the decay from the first step on, no min(decay, (1 + t) / (10 + t))")
     ap.add_argument("--save-ema", default=None, metavar="PATH", help="with --ema: write the averaged model alone to PATH at the end of the run")
+    ap.add_argument("--loss", default="reference", choices=["reference", "crystal_rmse", "mse", "mae", "huber"],
+                    help="the training objective: the reference's (mean of the per-crystal RMSEs, main_eDOS.py:111-123) or the mean over "
+                         "crystals of each crystal's own RMSE / MSE / MAE / Huber term (target clamped at 0 as there); on this model "
+                         "crystal_rmse is the reference's objective through the per-crystal entry")
+    ap.add_argument("--huber-delta", type=float, default=None, metavar="X", help="with --loss huber: torch.nn.HuberLoss's delta")
     param_groups.add_arguments(ap)
     args = ap.parse_args(argv)
     if (args.no_ema_warmup or args.save_ema) and args.ema is None:
         ap.error("--no-ema-warmup / --save-ema need --ema DECAY")
+    if (args.loss == "huber") != (args.huber_delta is not None):
+        ap.error("--huber-delta X belongs to --loss huber, and --loss huber needs it")
     return args
 
 
@@ -171,7 +178,8 @@ def _main(argv=None):
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=bucket, promote=0.08,
                       per_crystal_keys=args.per_crystal_keys,      # AdamW(lr, weight_decay=1e-2), `:91`
                       max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, param_groups=groups,
-                      ema_decay=args.ema, ema_warmup=not args.no_ema_warmup)
+                      ema_decay=args.ema, ema_warmup=not args.no_ema_warmup,
+                      loss=None if args.loss == "reference" else args.loss, huber_delta=args.huber_delta)
     predictor = Predictor(model, bucket=bucket, per_crystal_keys=args.eval_per_crystal > 0 and not baseline)
     criterion_2 = torch.nn.L1Loss()                                                       # `main_eDOS.py:93`
 

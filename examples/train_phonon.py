@@ -124,8 +124,18 @@ def _main(argv=None):
                          "carries both weight sets")
     ap.add_argument("--no-ema-warmup", action="store_true", help="with --ema: the decay from the first step on, no min(decay, (1 + t) / (10 + t))")
     ap.add_argument("--save-ema", default=None, metavar="PATH", help="with --ema: write the averaged model alone to PATH at the end of the run")
+    ap.add_argument("--loss", default="reference", choices=["reference", "crystal_rmse", "mse", "mae", "huber"],
+                    help="fused trainers: the training objective - the reference driver's (ONE RMSE pooled over the batch, "
+                         "main_phDOS.py:109-114) or the mean over crystals of each crystal's own RMSE / MSE / MAE / Huber term; "
+                         "crystal_rmse is what the reference optimises at its batch_size = 1 (with --per-crystal-keys, or --float64 "
+                         "--fused, a step follows the mean of the batch-1 gradients)")
+    ap.add_argument("--huber-delta", type=float, default=None, metavar="X", help="with --loss huber: torch.nn.HuberLoss's delta")
     param_groups.add_arguments(ap)
     args = ap.parse_args(argv)
+    if (args.loss == "huber") != (args.huber_delta is not None):
+        ap.error("--huber-delta X belongs to --loss huber, and --loss huber needs it")
+    if args.loss != "reference" and args.float64 and not args.fused:
+        ap.error("--loss belongs to the fused trainers: the fp32 run, or --float64 --fused")
     if args.ema is not None and args.float64 and not args.fused:
         ap.error("--ema belongs to the fused trainers: the fp32 run, or --float64 --fused")
     if (args.no_ema_warmup or args.save_ema) and args.ema is None:
@@ -173,7 +183,7 @@ def _main(argv=None):
     # within the first epoch (ghost padding is exact; it costs a few per cent of extra rows)
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=(32, 1024), promote=0.08,
                       per_crystal_keys=args.per_crystal_keys, param_groups=_groups(args, model), **_guard_args(args),
-                      **_ema_args(args))
+                      **_ema_args(args), **_loss_args(args))
     predictor = Predictor(model, bucket=(32, 1024), per_crystal_keys=args.eval_per_crystal > 0 and not baseline)
     run_test = _tester(args, predictor, ds)
     best, history = float("inf"), []
@@ -203,6 +213,10 @@ def _main(argv=None):
 
 def _ema_args(args):
     return dict(ema_decay=args.ema, ema_warmup=not args.no_ema_warmup)
+
+
+def _loss_args(args):
+    return dict(loss=None if args.loss == "reference" else args.loss, huber_delta=args.huber_delta)
 
 
 def _ema_report(args, trainer, run_test, name):
@@ -344,13 +358,13 @@ def train_float64_fused(args, ds, dev):
     if args.embedder == "graphnetwork":
         model = _fine_tune(args, _baseline64(args, dev))
         trainer = GraphnetworkTrainer64(model, lr=args.lr, param_groups=_groups(args, model), **slots, **_guard_args(args),
-                                        **_ema_args(args))
+                                        **_ema_args(args), **_loss_args(args))
     else:
         model = DOSTransformer_phonon(args.layers, args.transformer, 118, 4, args.hidden, dev, 0.0).double()
         model = model.set_program_dtype(torch.float64).set_per_crystal_keys(True).to(dev)
         _fine_tune(args, model)
         trainer = Trainer64(model, lr=args.lr, beta=args.beta, param_groups=_groups(args, model), **slots, **_guard_args(args),
-                            **_ema_args(args))
+                            **_ema_args(args), **_loss_args(args))
     evaluator = Predictor64(model, bucket=bucket) if args.replay else model       # (the module's per-crystal keys are on)
     run_test = _tester(args, evaluator, ds)
     train = ds["train"]

@@ -1292,6 +1292,36 @@ int dosx_loss_phonon_f64(const double* pg, const double* ps, const double* y, do
 int dosx_adamw_f64(double* p, const double* g, double* m, double* v, int64_t n, double lr, double beta1, double beta2,
                    double eps, double weight_decay, int step, dosx_stream_t stream);
 
+/* ---- per-crystal losses (csrc/loss_rows.hip) -------------------------------------------------------------------------------
+ * The objective a fused trainer is asked for with `loss=`: every crystal's own term, averaged over the crystals - what the
+ * reference's drivers optimise at batch_size = 1, where the phonon model is trained (main_phDOS.py:52-55, 109-114: the RMSE of
+ * ONE crystal per step) and what main_eDOS.py:111-123 spells out per crystal; MSE, MAE and Huber are the other metrics
+ * utils.test / utils.test_phonon report and torch.nn.HuberLoss.  pg, ps, y, dpg, dps: [B,S] row-major; forward + gradient.
+ *
+ *   t = clamp_target ? max(y, 0) : y  (main_eDOS.py:113 `torch.where(y < 0, 0, y)`; phonon: clamp_target = 0),  r = p - t
+ *   f(p_b):  DOSX_LOSS_RMSE  sqrt(mean_s r^2)      DOSX_LOSS_MSE  mean_s r^2      DOSX_LOSS_MAE  mean_s |r|
+ *            DOSX_LOSS_HUBER mean_s h(r),  h(r) = r^2 / 2 where |r| <= delta, else delta (|r| - delta / 2)   (torch.nn.HuberLoss;
+ *            |r| == delta is the quadratic branch); delta is read by this kind alone, which requires it finite and > 0
+ *   l_b = f(pg_b) + beta f(ps_b);   per_crystal[b] = l_b (per_crystal may be NULL);   loss[0] = (1 / B_global) sum_b l_b
+ *   dpg, dps = d loss[0] / d pg, d ps.  `B_global`: crystals in the un-sharded batch (as dosx_loss_edos).
+ * One-output models: ps == NULL with dps == NULL; then l_b = f(pg_b) and beta is not read (no `ps = pg, beta = 0` scratch here).
+ * A crystal whose RMSE is exactly 0 gets a zero gradient for that output, never 0 / 0 (the rule of dosx_loss_phonon_f64).  The MAE
+ * subgradient at r == 0 is 0 (torch.sign).  A NaN / inf prediction - or target - reaches that crystal's l_b, loss[0] and the
+ * crystal's gradient rows, and no other crystal's rows: the step guard sees it.  ONE exception, the one dosx_loss_edos has:
+ * under clamp_target the clamp is fmax(y, 0), which turns a NaN TARGET into 0.
+ * Deterministic: lane l of a crystal's wavefront adds the elements l, l + 64, ... in order, one wave reduction; loss[0] adds
+ * the rounded shares l_b / B_global in dosx_sum's order; no atomics - two runs are bitwise equal.  kind = RMSE with clamp_target
+ * and two outputs is dosx_loss_edos + dosx_sum bit for bit: dpg, dps, per_crystal[b] / B_global = its loss_partial[b], loss[0].
+ * Launches: with per_crystal two (rows, then the total in one workgroup); without, one workgroup does both (same bits).
+ * Both refuse with -22 and a message: a NULL pg, y, dpg or loss; ps / dps not both set or both NULL; B, S or B_global <= 0; a
+ * kind outside the enumerators; DOSX_LOSS_HUBER with delta <= 0 or not finite; B * S >= 2^31. */
+enum { DOSX_LOSS_RMSE = 0, DOSX_LOSS_MSE = 1, DOSX_LOSS_MAE = 2, DOSX_LOSS_HUBER = 3 };
+int dosx_loss_rows(const float* pg, const float* ps, const float* y, int B, int S, int B_global, int kind, int clamp_target,
+                   float beta, float delta, float* dpg, float* dps, float* per_crystal, float* loss, dosx_stream_t stream);
+int dosx_loss_rows_f64(const double* pg, const double* ps, const double* y, int B, int S, int B_global, int kind,
+                       int clamp_target, double beta, double delta, double* dpg, double* dps, double* per_crystal, double* loss,
+                       dosx_stream_t stream);
+
 /* ---- guarded optimizer step (csrc/step_guard.hip; the guarded AdamW entries: csrc/adamw.hip) ------------------------------
  * What a fused trainer has in place of `clip_grad_norm_` and of a GradScaler-style "skip if non-finite": one statistics launch
  * over the flat gradient, behind the recorded program and in front of the AdamW launch, and an AdamW that reads its verdict
