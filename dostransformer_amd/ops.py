@@ -1864,6 +1864,40 @@ def swap_buffers(a: torch.Tensor, b: torch.Tensor, n: Optional[int] = None) -> N
           w=lambda: ("swap_buffers", "swap_kernel", "hbm", 4.0 * nbytes))
 
 
+def _grad_accumulate(who: str, dt: torch.dtype, dst, a, b, n, sdst, sa, sb) -> None:
+    ts = {"dst": dst, "a": a, "b": b, "sdst": sdst, "sa": sa, "sb": sb}
+    for k, t in ts.items():
+        if t is None:
+            if k in ("dst", "a"):
+                raise TypeError(f"{who}: {k} is required")
+            continue
+        if t.dtype != dt or not t.is_cuda or t.device != dst.device or not t.is_contiguous():
+            raise TypeError(f"{who}: {k} must be a contiguous {dt} CUDA tensor on dst's device, got {t.dtype} on {t.device}, "
+                            f"strides {t.stride()}")
+    vecs = [t for t in (dst, a, b) if t is not None]
+    n = min(t.numel() for t in vecs) if n is None else int(n)
+    if not 0 <= n <= min(t.numel() for t in vecs):
+        raise ValueError(f"{who}: n = {n} of buffers with {', '.join(str(t.numel()) for t in vecs)} elements")
+    if (sdst is None) != (sa is None) or (sb is not None and sdst is None):
+        raise ValueError(f"{who}: sdst and sa go together, sb only with them (all three None: no scalar)")
+    if any(t is not None and t.numel() < 1 for t in (sdst, sa, sb)):
+        raise ValueError(f"{who}: a scalar operand without an element")
+    _call("dosx_grad_accumulate" if dt == torch.float32 else "dosx_grad_accumulate_f64", dst.data_ptr(), a.data_ptr(), _p(b), n,
+          _p(sdst), _p(sa), _p(sb), _stream(),
+          w=lambda: ("grad_accumulate", "grad_accumulate_kernel", "hbm", (2.0 if b is None else 3.0) * dst.element_size() * n))
+
+
+def grad_accumulate(dst: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None, n: Optional[int] = None, *,
+                    sdst: Optional[torch.Tensor] = None, sa: Optional[torch.Tensor] = None,
+                    sb: Optional[torch.Tensor] = None) -> None:
+    """``dst[:n] = a[:n] + b[:n]`` in one launch, ``dst[:n] = a[:n]`` when ``b`` is None (dosx_grad_accumulate): how the fused
+    trainers sum the flat gradients of the batches of one optimizer step.  ``dst`` may be ``a`` or ``b`` itself, no other
+    overlap; ``n`` defaults to the shortest buffer.  ``sdst`` / ``sa`` / ``sb``: the same for element 0 of three scalars
+    (``sdst[0] = sa[0] + sb[0]``, a copy when ``sb`` is None).  fp32, contiguous, 16-byte aligned; every element is one IEEE add -
+    bit for bit ``torch.add(a, b)``."""
+    _grad_accumulate("grad_accumulate", torch.float32, dst, a, b, n, sdst, sa, sb)
+
+
 def adamw(p, g, m, v, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, ema=None):
     """torch.optim.AdamW's update of the first n elements of the flat fp32 buffers, on ``g * grad_scale`` (dosx_adamw).
     ``ema=(buffer, decay, warmup, t0)``, here and on the seven functions below: the launch also keeps the exponential moving
@@ -2321,6 +2355,13 @@ def loss_rows64(pg: torch.Tensor, ps: Optional[torch.Tensor], y: torch.Tensor, k
                 per_crystal: Optional[torch.Tensor] = None, loss: torch.Tensor, B_global: Optional[int] = None) -> None:
     """:func:`loss_rows` on float64 operands (include/dosx.h: dosx_loss_rows_f64)."""
     _loss_rows("loss_rows64", torch.float64, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global)
+
+
+def grad_accumulate64(dst: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None, n: Optional[int] = None, *,
+                      sdst: Optional[torch.Tensor] = None, sa: Optional[torch.Tensor] = None,
+                      sb: Optional[torch.Tensor] = None) -> None:
+    """:func:`grad_accumulate` on float64 operands (include/dosx.h: dosx_grad_accumulate_f64)."""
+    _grad_accumulate("grad_accumulate64", torch.float64, dst, a, b, n, sdst, sa, sb)
 
 
 def adamw64(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, n: int, lr: float, beta1: float, beta2: float,

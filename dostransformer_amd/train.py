@@ -78,6 +78,7 @@ class _AdamWState(StepGuard, WeightEma):
                         v[o:o + k].copy_(self._v[oo:oo + k])
             self._ema_rehome(fp, old)
             self._m, self._v, self._fp = m, v, fp
+            self._acc = self._acc_loss = None      # (the window's accumulator belongs to the layout: made anew at the next window)
             self._slots = OrderedDict()
             if self._groups is not None:       # the chunk map belongs to the layout: rebuilt wherever the moments are re-homed
                 self._chunk_group = _pg.chunk_map(fp, _pg.assignment(self._groups)).to(fp.flat.device)
@@ -259,20 +260,101 @@ class _AdamWState(StepGuard, WeightEma):
             raise DosxError(f"{who}(loss=...) is a single-GPU mode: not with dist (data parallelism)")
         self.loss, self.huber_delta = loss, None if huber_delta is None else float(huber_delta)
 
-    def _loss_rows(self, alloc, dev, pg, ps, y, clamp: bool, dpg, dps):
+    def _loss_rows(self, alloc, dev, pg, ps, y, clamp: bool, dpg, dps, B_global: Optional[int] = None):
         """The one launch site of the per-crystal losses: -> (per-crystal l_b [B], loss 0-dim), both on static buffers when
-        the step is being recorded.  ``ps = dps = None``: a one-output model (``beta`` is not read then)."""
+        the step is being recorded.  ``ps = dps = None``: a one-output model (``beta`` is not read then).  ``B_global``: the
+        count the mean is taken over - the batch's own outside an accumulation window, the window's total inside one."""
         B = int(pg.shape[0])
+        if B_global is None:
+            B_global = B if self._window_total is None else self._window_total
         per, loss = alloc(dev, B), alloc(dev, 1)
         fn = ops.loss_rows if pg.dtype == torch.float32 else ops.loss_rows64
         fn(pg, ps, y, self.loss, clamp_target=clamp, beta=self.beta, delta=self.huber_delta, dpg=dpg, dps=dps, per_crystal=per,
-           loss=loss, B_global=B)
+           loss=loss, B_global=int(B_global))
         return per, loss[0]
 
+    def _whole_or_window(self, B: int, n_global) -> bool:
+        """True when ``n_global`` is the batch's own count - or, inside an accumulation window, the window's total (the internal
+        route by which a micro-batch is normalised by a count that is not its own; callers cannot reach it)."""
+        return int(n_global) == int(B) or (self._window_total is not None and int(n_global) == self._window_total)
+
     def _require_whole_batch(self, B: int, n_global) -> None:
-        if self.loss is not None and int(n_global) != int(B):
+        if self.loss is not None and not self._whole_or_window(B, n_global):
             raise ValueError(f"{type(self).__name__}(loss={self.loss!r}): n_global={n_global} but the batch holds {B} crystals "
                              f"(the per-crystal losses are a single-GPU mode)")
+
+    # ---- gradient accumulation: several batches, one optimizer step (include/dosx.h: dosx_grad_accumulate; DESIGN.md 9.9) -----
+    _acc = None                       # the window's accumulator, laid out like the moments; made at the first window with K > 1
+    _acc_loss = None                  # [1]: the window's loss, summed by the same launches
+    _window_total = None              # inside a window: T, the crystals of all its micro-batches; None outside
+
+    def _window_checks(self, what: str, K: int) -> None:
+        """What a window cannot run on and that its length alone decides - raised before the dropout seed, the accumulator or
+        any slot is touched."""
+        who = self._ema_who
+        self._ema_refuse(what)
+        if K == 0:
+            raise ValueError(f"{who}.{what}: an empty window - pass at least one batch")
+        if getattr(self, "dist", None) is not None:
+            raise DosxError(f"{who}.{what} is a single-GPU mode: not with dist (data parallelism)")
+        if K > 1 and self.loss is None and self.model._cfg.kind == "phonon":
+            raise DosxError(f"{who}.{what}: the reference's phonon loss is ONE RMSE pooled over the batch - its gradient needs "
+                            f"every micro-batch's squared error before any backward, so it does not accumulate over {K} batches; "
+                            f"build the trainer with loss=\"crystal_rmse\" (the reference's own objective at its batch size 1) or "
+                            f"another per-crystal loss")
+        if K > 1 and not self.model.trainable_names():
+            raise DosxError(f"{who}.{what}: every parameter is frozen - there is no gradient to accumulate")
+
+    @staticmethod
+    def _crystals_of(g) -> int:
+        """crystals in a batch object, without a host read (``system`` has one entry per crystal)"""
+        return int(g.num_graphs if hasattr(g, "num_graphs") else g.system.shape[0])
+
+    def _window_sizes(self, what: str, counts) -> list:
+        sizes = [int(c) for c in counts]
+        for k, B in enumerate(sizes):
+            if B < 1:
+                raise ValueError(f"{self._ema_who}.{what}: batch {k} of the window is empty")
+        return sizes
+
+    def _window(self, what: str, sizes, run) -> torch.Tensor:
+        """One optimizer step on the micro-batches ``k < len(sizes)`` (``sizes[k]`` crystals each, at least two of them):
+        ``run(k)`` issues micro-batch k's ordinary program - normalised by the window's total, which ``_window_total`` carries -
+        and returns its loss; behind each program ONE ``dosx_grad_accumulate`` launch on the main stream, outside the recording,
+        where the optimizer launch goes: copy into the accumulator (k = 0: nothing stale is ever read), accumulator += gradient,
+        and for the last one gradient = accumulator + gradient - the flat gradient buffer then holds ((G1 + G2) + G3) + ..., and
+        the guard, AdamW, ``.grad`` and ``guard_report()`` work on it unchanged.  The same launches sum the losses.  Nothing of the
+        optimizer's is touched before the last launch: an exception in between leaves parameters, moments, average and
+        ``step_count`` alone, and the next window starts with a copy."""
+        K, T = len(sizes), sum(sizes)
+        accumulate = None
+        crystals, off, fp0 = None, 0, None
+        self._window_total = T
+        try:
+            for k in range(K):
+                loss = run(k)
+                fp = self._fp
+                if k == 0:
+                    fp0 = fp
+                    if self._acc is None:
+                        self._acc, self._acc_loss = torch.empty_like(fp.flat), torch.empty(1, dtype=fp.flat.dtype, device=fp.flat.device)
+                    accumulate = ops.grad_accumulate if fp.flat.dtype == torch.float32 else ops.grad_accumulate64
+                    accumulate(self._acc, fp.grad, None, fp.n_train, sdst=self._acc_loss, sa=loss)
+                elif fp is not fp0:
+                    raise DosxError(f"{self._ema_who}.{what}: the flat parameters were laid out anew inside a window (batch {k})")
+                else:
+                    accumulate(self._acc if k < K - 1 else fp.grad, self._acc, fp.grad, fp.n_train, sdst=self._acc_loss,
+                               sa=self._acc_loss, sb=loss)
+                if self.crystal_losses is not None:          # (a slot's [B] buffer is overwritten when the slot runs again)
+                    if crystals is None:
+                        crystals = torch.empty(T, dtype=self.crystal_losses.dtype, device=self.crystal_losses.device)
+                    crystals[off:off + sizes[k]].copy_(self.crystal_losses)
+                off += sizes[k]
+        finally:
+            self._window_total = None
+        self.crystal_losses = crystals
+        self.optimizer_step()
+        return self._acc_loss[0]
 
 
 class _Width:
@@ -342,6 +424,11 @@ class Trainer(_AdamWState, SlotCache):
     tensor (under replay a view of the bucket's static buffer) valid until the next step.  Every mode, with the guard, frozen
     parameters, groups and the average; ``n_global`` must be the batch's own count; not under data parallelism.  A constructor
     argument like ``beta``: not in ``state_dict()``.  None (the default): the reference's loss, the launches it always issued.
+
+    ``step_accumulate([g1, g2, ...])`` / ``step_dataset_accumulate(ds, [idx1, idx2, ...])``: gradient accumulation - ONE optimizer
+    step on the objective of the concatenated batch, every micro-batch through its ordinary program with the loss divided by the
+    window's crystal count, one ``dosx_grad_accumulate`` launch behind each (see ``step_accumulate``).  ``step`` and
+    ``step_dataset`` issue the launches they always issued.
     """
 
     def __init__(self, model: DOSTransformerBase, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2,
@@ -446,7 +533,8 @@ class Trainer(_AdamWState, SlotCache):
             return self._part_b_baseline(fp, m, st, n_global)
         ddos = Fn._empty(dev, *dos.shape)
         if self.loss is not None:          # eDOS clamps its target at 0 (main_eDOS.py:113), phonon does not; n_global == B (_part_a)
-            st["crystal"], loss = self._loss_rows(Fn._empty, dev, dos[:B], dos[B:], st["y"], self.kind != "phonon", ddos[:B], ddos[B:])
+            st["crystal"], loss = self._loss_rows(Fn._empty, dev, dos[:B], dos[B:], st["y"], self.kind != "phonon", ddos[:B], ddos[B:],
+                                                  B_global=n_global)         # ... or, inside a window, the window's total
         elif self.kind == "phonon":
             loss = Fn._empty(dev, 1)
             if st["split_loss"] or int(n_global) != B:
@@ -475,12 +563,13 @@ class Trainer(_AdamWState, SlotCache):
         entry in its own one-output form (ps == NULL)."""
         dev = fp.flat.device
         B, S, dos = st["B"], st["S"], st["dos"]
-        if int(n_global) != B:
+        if not self._whole_or_window(B, n_global):
             raise ValueError(f"Trainer({type(self.model).__name__}): n_global={n_global} but the batch holds {B} crystals "
                              f"(no data parallelism for the GNN-only baselines)")
         if self.loss is not None:          # the one-output form of the entry: no second gradient, no scratch
             ddos = Fn._empty(dev, B, S)
-            st["crystal"], loss = self._loss_rows(Fn._empty, dev, dos, None, st["y"], self.kind != "phonon", ddos, None)
+            st["crystal"], loss = self._loss_rows(Fn._empty, dev, dos, None, st["y"], self.kind != "phonon", ddos, None,
+                                                  B_global=n_global)
             return self._bwd_baseline(fp, m, st, ddos, loss)
         ddos, scr = Fn._empty(dev, B, S), Fn._empty(dev, B, S)
         if self.kind == "phonon":
@@ -489,7 +578,7 @@ class Trainer(_AdamWState, SlotCache):
             loss = loss[0]
         else:
             lp = Fn._empty(dev, B + 1)
-            ops.loss_edos(dos, dos, st["y"], 0.0, B, S, B, ddos, scr, lp)
+            ops.loss_edos(dos, dos, st["y"], 0.0, B, S, int(n_global), ddos, scr, lp)     # (B, or a window's total)
             ops.sum_to(lp, B, lp[B:])
             loss = lp[B]
         return self._bwd_baseline(fp, m, st, ddos, loss)
@@ -722,6 +811,12 @@ class Trainer(_AdamWState, SlotCache):
         self._ema_refuse("step_dataset")
         if not (self.replay or self.graph):
             return self.step(ds.collate(indices, n_max=n_max), n_global)
+        loss = self._dataset_program(ds, indices, n_global, n_max)
+        self.optimizer_step()
+        return loss
+
+    def _dataset_program(self, ds, indices, n_global: Optional[int], n_max: Optional[int]) -> torch.Tensor:
+        """``step_dataset`` (replay / graph mode) up to the optimizer: collate into the bucket, bump the seed, run the slot."""
         model = self.model
         dev = model._module_device()
         model._require_fp32_program("Trainer")
@@ -767,7 +862,6 @@ class Trainer(_AdamWState, SlotCache):
         loss = self._run_slot(slot, fp, ng, fresh)
         if fresh:
             self._slots[key] = slot
-        self.optimizer_step()
         return loss
 
     # ---- what the step launched ------------------------------------------------------------------
@@ -810,3 +904,46 @@ class Trainer(_AdamWState, SlotCache):
         loss = self._graph_step(g, n_global) if (self.graph or self.replay) else self.forward_backward(g, n_global, _bump=False)
         self.optimizer_step()
         return loss
+
+    # ---- gradient accumulation ---------------------------------------------------------------------
+    def step_accumulate(self, batches) -> torch.Tensor:
+        """ONE optimizer step on the objective of the concatenated batch, computed micro-batch by micro-batch: what a torch loop
+        gets from ``backward()`` on several batches before one ``optimizer.step()`` - with every loss normalised by the window's
+        crystal count ``T = sum B_k``, not by its own, so that ragged batches still give the mean over crystals.  Each batch
+        runs its ordinary program (eager, ``replay`` or ``graph``; the slots an epoch recorded are reused, keyed with ``T``) and
+        one ``dosx_grad_accumulate`` launch behind it sums the flat gradients in the fixed order ``((G1 + G2) + G3) + ...``;
+        then one guard verdict (on the SUM: a non-finite value in any micro-batch skips the whole window), one AdamW launch, one
+        update of the weight average, ``step_count + 1``.  Returns the window's loss, a 0-dim device tensor (a trainer-owned
+        scalar, valid until the next window); ``crystal_losses`` is the ``[T]`` concatenation in micro-batch order,
+        ``last_outputs`` / ``program_stats()`` describe the last micro-batch, the dropout seed advances once per micro-batch.
+        One batch is ``step()`` bit for bit.  Every objective that is a sum over crystals divided by a count: the eDOS default loss
+        and every ``loss=``; the reference's pooled phonon RMSE is refused for more than one batch (``loss="crystal_rmse"`` is
+        the reference's own batch-1 objective).  Not under data parallelism, not inside ``ema_weights()``.  Whatever can be known
+        before a launch raises before anything has changed; an exception in the middle of a window leaves parameters, moments,
+        average and ``step_count`` untouched."""
+        batches = list(batches)
+        self._window_checks("step_accumulate", len(batches))
+        sizes = self._window_sizes("step_accumulate", (self._crystals_of(g) for g in batches))
+        if len(batches) == 1:
+            return self.step(batches[0])
+        T = sum(sizes)
+
+        def run(k):
+            self._bump_dropout_seed()
+            if self.graph or self.replay:
+                return self._graph_step(batches[k], T)
+            return self.forward_backward(batches[k], T, _bump=False)
+        return self._window("step_accumulate", sizes, run)
+
+    def step_dataset_accumulate(self, ds, index_lists, n_max: Optional[int] = None) -> torch.Tensor:
+        """``step_accumulate`` on selections of a device-resident ``loader.DeviceDataset``: each ``indices`` of ``index_lists`` is
+        collated straight into its bucket as ``step_dataset`` does; bitwise ``step_accumulate([ds.collate(i) ...])``."""
+        index_lists = list(index_lists)
+        self._window_checks("step_dataset_accumulate", len(index_lists))
+        sizes = self._window_sizes("step_dataset_accumulate", (len(i) for i in index_lists))
+        if len(index_lists) == 1:
+            return self.step_dataset(ds, index_lists[0], n_max=n_max)
+        if not (self.replay or self.graph):
+            return self.step_accumulate([ds.collate(i, n_max=n_max) for i in index_lists])
+        T = sum(sizes)
+        return self._window("step_dataset_accumulate", sizes, lambda k: self._dataset_program(ds, index_lists[k], T, n_max))

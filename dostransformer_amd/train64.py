@@ -61,6 +61,8 @@ class Trainer64(_AdamWState, SlotCache):
     ``"huber"``: ``dosx_loss_rows_f64``), as on ``train.Trainer``; ``crystal_losses`` is then the last step's ``[B]`` float64
     per-crystal losses.  With ``set_per_crystal_keys(True)`` a ``"crystal_rmse"`` step follows the mean of the reference's
     batch-1 gradients.  None (the default): the launches it always issued.
+    ``step_accumulate`` / ``step_dataset_accumulate``: several micro-batches, one optimizer step on the objective of the
+    concatenated batch, as on ``train.Trainer`` (needs ``loss=`` for more than one batch).
     """
 
     _who = "Trainer64"            # what this driver calls itself in its refusals
@@ -155,9 +157,15 @@ class Trainer64(_AdamWState, SlotCache):
     # ---- replay --------------------------------------------------------------------------------------------------------
     def _key(self, n: int, e: int, B: int, n_max: int, drop) -> tuple:
         """What decides the launch list: the (padded) shape, then per-crystal keys, dropout on / off (train / eval mode, p > 0),
-        the tests' fp64-softmax switch - a slot recorded under one setting is never replayed under another."""
+        the tests' fp64-softmax switch, the loss weight and - last - the count the recorded loss launch divides by (the batch's
+        own, or an accumulation window's total) - a slot recorded under one setting is never replayed under another."""
         return (n, e, B, n_max, bool(self.model.per_crystal_keys), drop is not None, None if drop is None else drop[0],
-                bool(F64.SOFTMAX64), float(self.beta))
+                bool(F64.SOFTMAX64), float(self.beta), self._b_global(B))
+
+    def _b_global(self, B: int) -> int:
+        """The count the recorded loss launch divides by (the last field of a slot's key): the batch's own, or - inside an
+        accumulation window - the window's total."""
+        return int(B) if self._window_total is None else self._window_total
 
     def _run_slot(self, slot: Slot, fp, drop, fresh: bool) -> torch.Tensor:
         """The step on a slot whose static buffers hold the batch: recorded on first use, replayed afterwards."""
@@ -208,6 +216,12 @@ class Trainer64(_AdamWState, SlotCache):
         self._ema_refuse("step_dataset")
         if not (self.replay and self.bucket is not None):
             return self.step(ds.collate(indices, n_max=n_max))
+        loss = self._dataset_program(ds, indices, n_max)
+        self.optimizer_step()
+        return loss
+
+    def _dataset_program(self, ds, indices, n_max: Optional[int]) -> torch.Tensor:
+        """``step_dataset`` (``replay`` with ``bucket``) up to the optimizer: bump the seed, collate into the bucket, run the slot."""
         self._require_model(self.model)
         idx, N, E, n_max = ds.bucket_dims(indices, n_max)
         B = int(idx.shape[0])
@@ -228,7 +242,6 @@ class Trainer64(_AdamWState, SlotCache):
             loss = self._run_slot(slot, fp, drop, fresh)
         if fresh:
             self._slots[key] = slot
-        self.optimizer_step()
         return loss
 
     def step(self, g) -> torch.Tensor:
@@ -238,6 +251,39 @@ class Trainer64(_AdamWState, SlotCache):
         loss = self.forward_backward(g, _bump=False)
         self.optimizer_step()
         return loss
+
+    # ---- gradient accumulation -------------------------------------------------------------------------------------------
+    def step_accumulate(self, batches) -> torch.Tensor:
+        """ONE optimizer step on the objective of the concatenated batch, micro-batch by micro-batch, as
+        ``train.Trainer.step_accumulate``: every batch runs its ordinary float64 program with its per-crystal loss normalised by
+        the window's crystal count (the last field of a slot's key), one ``dosx_grad_accumulate_f64`` launch behind each sums the
+        flat gradients in the order ``((G1 + G2) + G3) + ...``, then one guard verdict, one AdamW launch, one update of the
+        average.  Needs ``loss=`` for more than one batch (the default pooled RMSE does not accumulate); one batch is ``step()``."""
+        batches = list(batches)
+        self._window_checks("step_accumulate", len(batches))
+        sizes = self._window_sizes("step_accumulate", (self._crystals_of(g) for g in batches))
+        for g in batches:
+            self._refuse(g)
+        if len(batches) == 1:
+            return self.step(batches[0])
+
+        def run(k):
+            self._bump_dropout_seed()
+            return self.forward_backward(batches[k], _bump=False)
+        return self._window("step_accumulate", sizes, run)
+
+    def step_dataset_accumulate(self, ds, index_lists, n_max: Optional[int] = None) -> torch.Tensor:
+        """``step_accumulate`` on selections of a device-resident float64 ``loader.DeviceDataset``, each collated as
+        ``step_dataset`` does: bitwise the batch-object form."""
+        index_lists = list(index_lists)
+        self._window_checks("step_dataset_accumulate", len(index_lists))
+        sizes = self._window_sizes("step_dataset_accumulate", (len(i) for i in index_lists))
+        self._require_model(self.model)
+        if len(index_lists) == 1:
+            return self.step_dataset(ds, index_lists[0], n_max=n_max)
+        if not (self.replay and self.bucket is not None):
+            return self.step_accumulate([ds.collate(i, n_max=n_max) for i in index_lists])
+        return self._window("step_dataset_accumulate", sizes, lambda k: self._dataset_program(ds, index_lists[k], n_max))
 
 
 class GraphnetworkTrainer64(Trainer64):
@@ -315,4 +361,4 @@ class GraphnetworkTrainer64(Trainer64):
         self.last_outputs = out
 
     def _key(self, n: int, e: int, B: int, n_max: int, drop) -> tuple:
-        return (n, e, B, n_max)
+        return (n, e, B, n_max, self._b_global(B))

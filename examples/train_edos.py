@@ -29,6 +29,11 @@ the named parameters at their own rate / weight decay, --no-decay-norms keeps bi
 out of the weight decay, --layerwise-lr-decay D lowers the rate layer by layer towards the input (param_groups.py).
 
     python examples/train_edos.py --init edos_best.pt --group GN_encoder.,stacked_processor.,GN_decoder.:lr=1e-5 --no-decay-norms
+
+Gradient accumulation: --accumulate K groups K consecutive batches of the epoch into one optimizer step on the objective of their
+concatenation (every loss, the reference's included: each is a mean over crystals).
+
+    python examples/train_edos.py --accumulate 4 --batch_size 16
 """
 import argparse
 import os
@@ -100,8 +105,13 @@ def parse_args(argv=None):
                          "crystals of each crystal's own RMSE / MSE / MAE / Huber term (target clamped at 0 as there); on this model "
                          "crystal_rmse is the reference's objective through the per-crystal entry")
     ap.add_argument("--huber-delta", type=float, default=None, metavar="X", help="with --loss huber: torch.nn.HuberLoss's delta")
+    ap.add_argument("--accumulate", type=int, default=1, metavar="K",
+                    help="one optimizer step per K consecutive batches of the epoch, on the objective of their concatenation "
+                         "(gradient accumulation: trainer.step_dataset_accumulate; the last window of an epoch may be shorter)")
     param_groups.add_arguments(ap)
     args = ap.parse_args(argv)
+    if args.accumulate < 1:
+        ap.error("--accumulate K: K is at least 1")
     if (args.no_ema_warmup or args.save_ema) and args.ema is None:
         ap.error("--no-ema-warmup / --save-ema need --ema DECAY")
     if (args.loss == "huber") != (args.huber_delta is not None):
@@ -199,10 +209,14 @@ def _main(argv=None):
         model.train()
         t0, losses, seen = time.perf_counter(), [], 0
         order = rng.permutation(len(ds["train"]))                                         # DataLoader(shuffle=True), `:54`
-        for i in range(0, len(order), args.batch_size):
-            idx = order[i:i + args.batch_size]
-            losses.append(trainer.step_dataset(ds["train"], idx, n_max=nmax_train))       # the loop body `:104-127`
-            seen += len(idx)
+        cuts = [order[i:i + args.batch_size] for i in range(0, len(order), args.batch_size)]
+        for w in range(0, len(cuts), args.accumulate):
+            sels = cuts[w:w + args.accumulate]                                            # --accumulate K: the last window may be shorter
+            if args.accumulate == 1:
+                losses.append(trainer.step_dataset(ds["train"], sels[0], n_max=nmax_train))   # the loop body `:104-127`
+            else:                                                                         # (the window's loss: a scalar the trainer owns)
+                losses.append(trainer.step_dataset_accumulate(ds["train"], sels, n_max=nmax_train).clone())
+            seen += sum(len(idx) for idx in sels)
         loss = float(torch.stack(losses).mean())                                          # one host read per epoch
         history.append(loss)
         print(f"[ epoch {epoch + 1}/{args.epochs} ]  Total Loss: {loss:.4f}   ({seen / (time.perf_counter() - t0):.0f} crystals/s)")

@@ -53,6 +53,12 @@ Averaged weights (fused trainers): --ema DECAY keeps an exponential moving avera
 (trainer.ema_weights()), the checkpoint carries both weight sets, --save-ema PATH writes the averaged model alone.
 
     python examples/train_phonon.py --ema 0.999 --eval-per-crystal 64 --save-ema phonon_ema.pt
+
+Gradient accumulation (fused trainers): --accumulate K groups K consecutive batches of the epoch into one optimizer step on the
+objective of their concatenation (trainer.step_accumulate / step_dataset_accumulate; the last window of an epoch may be shorter).
+The reference's pooled RMSE does not accumulate, so K > 1 needs one of the per-crystal --loss kinds.
+
+    python examples/train_phonon.py --accumulate 4 --batch-size 16 --loss crystal_rmse --per-crystal-keys
 """
 import argparse
 import os
@@ -130,8 +136,18 @@ def _main(argv=None):
                          "crystal_rmse is what the reference optimises at its batch_size = 1 (with --per-crystal-keys, or --float64 "
                          "--fused, a step follows the mean of the batch-1 gradients)")
     ap.add_argument("--huber-delta", type=float, default=None, metavar="X", help="with --loss huber: torch.nn.HuberLoss's delta")
+    ap.add_argument("--accumulate", type=int, default=1, metavar="K",
+                    help="fused trainers: one optimizer step per K consecutive batches, on the objective of their concatenation "
+                         "(gradient accumulation; K > 1 needs a per-crystal --loss)")
     param_groups.add_arguments(ap)
     args = ap.parse_args(argv)
+    if args.accumulate < 1:
+        ap.error("--accumulate K: K is at least 1")
+    if args.accumulate > 1 and args.float64 and not args.fused:
+        ap.error("--accumulate belongs to the fused trainers: the fp32 run, or --float64 --fused")
+    if args.accumulate > 1 and args.loss == "reference":
+        ap.error("--accumulate K > 1: the reference's pooled RMSE does not accumulate over batches - pick --loss crystal_rmse "
+                 "(its own batch-1 objective), mse, mae or huber")
     if (args.loss == "huber") != (args.huber_delta is not None):
         ap.error("--huber-delta X belongs to --loss huber, and --loss huber needs it")
     if args.loss != "reference" and args.float64 and not args.fused:
@@ -190,9 +206,10 @@ def _main(argv=None):
     for epoch in range(args.epochs):
         model.train()
         t0, losses, seen = time.perf_counter(), [], 0
-        for batch in ds["train"].batches(args.batch_size, shuffle=True, seed=args.seed + epoch):
-            losses.append(trainer.step(batch))
-            seen += batch.num_graphs
+        for window in _windows(ds["train"].batches(args.batch_size, shuffle=True, seed=args.seed + epoch), args.accumulate):
+            # (a window's loss lives in a scalar the trainer owns: cloned)
+            losses.append(trainer.step(window[0]) if args.accumulate == 1 else trainer.step_accumulate(window).clone())
+            seen += sum(batch.num_graphs for batch in window)
         loss = float(torch.stack(losses).mean())                  # one host read per epoch
         dt = time.perf_counter() - t0
         history.append(loss)
@@ -209,6 +226,18 @@ def _main(argv=None):
             _ema_report(args, trainer, run_test, "test")
     _save_ema(args, model, trainer)
     return {"best_valid_rmse": best, "train_loss": history}
+
+
+def _windows(items, k):
+    """--accumulate K: the items of an epoch in lists of K consecutive ones; the last list may be shorter."""
+    window = []
+    for item in items:
+        window.append(item)
+        if len(window) == k:
+            yield window
+            window = []
+    if window:
+        yield window
 
 
 def _ema_args(args):
@@ -374,10 +403,12 @@ def train_float64_fused(args, ds, dev):
         model.train()
         t0, losses, seen = time.perf_counter(), [], 0
         order = np.random.default_rng(args.seed + epoch).permutation(len(train))
-        for i in range(0, len(order), args.batch_size):
-            sel = order[i:i + args.batch_size]
-            losses.append(trainer.step_dataset(train, sel, n_max=n_max).clone())     # (replay: the loss lives in the slot's buffer)
-            seen += len(sel)
+        for sels in _windows((order[i:i + args.batch_size] for i in range(0, len(order), args.batch_size)), args.accumulate):
+            if args.accumulate == 1:
+                losses.append(trainer.step_dataset(train, sels[0], n_max=n_max).clone())     # (replay: the loss lives in the slot's buffer)
+            else:
+                losses.append(trainer.step_dataset_accumulate(train, sels, n_max=n_max).clone())
+            seen += sum(len(sel) for sel in sels)
         loss = float(torch.stack(losses).mean())                  # one host read per epoch
         dt = time.perf_counter() - t0
         history.append(loss)

@@ -1466,6 +1466,32 @@ int dosx_adamw_ema_f64(double* p, const double* g, double* m, double* v, int64_t
 double dosx_adamw_ema_decay(double decay, int warmup, int t, int elem_bytes);
 int dosx_swap_buffers(void* a, void* b, int64_t bytes, dosx_stream_t stream);
 
+/* ---- gradient accumulation over the batches of one optimizer step (csrc/grad_accumulate.hip) ---------------------------------
+ * What a torch loop gets from calling backward() on several batches before one optimizer.step(): the backward program
+ * OVERWRITES the flat gradient, so a fused trainer adds the micro-batches' gradients with one launch behind each program
+ * (train.py: step_accumulate).
+ *   dst[i] = a[i] + b[i] for i < n;  b == NULL: dst[i] = a[i] - the first batch of a window: dst is never read, so an
+ *   accumulator needs no zeroing and a stale NaN in it cannot reach a window.
+ *   dst may be exactly a or exactly b; any other overlap of dst with a or b is refused (a and b are only read).
+ *   The scalar triple does the same for one element, by one thread: sdst[0] = sa[0] + sb[0], or sdst[0] = sa[0] when sb == NULL
+ *   (whatever b is) - the window's loss, without a torch kernel or a host read.  All three NULL: skipped.  sdst may be sa or sb;
+ *   no scalar may lie inside dst[0, n), nor sdst inside a[0, n) / b[0, n).
+ * One kernel template over the element type: 16-byte loads and stores (float4 / double2), DOSX_ACCUM_THREADS threads, min(ceil(n /
+ * (16 / sizeof(T)) / DOSX_ACCUM_THREADS), DOSX_ACCUM_MAX_BLOCKS) workgroups (at least 1) that stride over the vectors; the
+ * < 16-byte tail goes to the first threads of the grid, one element each.  Every element is ONE IEEE add: no multiply, so nothing
+ * to contract, and no atomics - two runs are bitwise equal, and the result is bit for bit `a + b` of torch on the same device.
+ * A NaN or an inf passes through like any other value (the step guard is what judges the sum); the copy form copies bits (-0.0).
+ * Both refuse with -22 and a message that starts with the entry's name, before any launch: a NULL dst or a; n < 0; dst, a or b
+ * off a 16-byte boundary; a partial overlap; an sdst without sa or an sa without sdst (an sb without them); a scalar off its
+ * element's alignment or inside the vectors as above.  n == 0 returns 0 without a launch (the scalar triple is then not
+ * carried out either). */
+#define DOSX_ACCUM_THREADS 256
+#define DOSX_ACCUM_MAX_BLOCKS 2048
+int dosx_grad_accumulate(float* dst, const float* a, const float* b, int64_t n, float* sdst, const float* sa, const float* sb,
+                         dosx_stream_t stream);
+int dosx_grad_accumulate_f64(double* dst, const double* a, const double* b, int64_t n, double* sdst, const double* sa,
+                             const double* sb, dosx_stream_t stream);
+
 /* ---- evaluation metrics (csrc/eval.hip) -----------------------------------------------------------------------------------
  * utils.py:76-89 / :127-139 evaluated one crystal at a time (what the reference computes at batch_size = 1).
  * pred, y: [B,S] rows with unit inner stride, rows S apart.  clamp0 != 0: both are clamped at 0 first (utils.py:74-76).
