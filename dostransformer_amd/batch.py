@@ -248,7 +248,8 @@ def collate(crystals: Iterable[Dict[str, object]], sort_edges: bool = True,
     Per crystal: ``x [n,Fa]``, ``edge_index [2,e]`` (local ids), and any of
     ``edge_vec [e,3]`` / ``edge_attr [e,Fb]``, ``glob [2]``, ``system`` scalar,
     ``phdos [1,51]``, ``y_ft [201]``, ``mp_id`` str (`utils.py:291-301`,
-    `mat2graph.py:81-107`).  ``n_max`` may be forced larger than this batch's own
+    `mat2graph.py:81-107`), ``weight`` scalar (a per-crystal sample weight -> ``[B]``, the
+    trainers' ``sample_weights=True``).  ``n_max`` may be forced larger than this batch's own
     maximum: data-parallel shards must pad to the GLOBAL batch's maximum to
     reproduce the single-process result.
     """
@@ -278,6 +279,9 @@ def collate(crystals: Iterable[Dict[str, object]], sort_edges: bool = True,
             fields[k] = torch.stack([torch.as_tensor(c[k]).reshape(()) for c in crystals]).to(torch.int64)
     if "phdos" in crystals[0]:
         fields["phdos"] = torch.cat([c["phdos"].reshape(1, -1) for c in crystals], 0)
+    if "weight" in crystals[0]:              # per-crystal sample weight, a scalar -> [B] in the features' dtype
+        wdt = fields["x"].dtype if fields["x"].is_floating_point() else torch.float32
+        fields["weight"] = torch.stack([torch.as_tensor(c["weight"]).reshape(()).to(wdt) for c in crystals])
     if "mp_id" in crystals[0]:
         fields["mp_id"] = [c["mp_id"] for c in crystals]
 
@@ -399,6 +403,8 @@ def split_crystals(g: CrystalBatch) -> List[Dict[str, object]]:
             c["system"] = g.system.cpu()[b]
         if "phdos" in g:
             c["phdos"] = g.phdos.cpu()[b:b + 1]
+        if "weight" in g:
+            c["weight"] = g.weight.cpu()[b]
         if "mp_id" in g:
             c["mp_id"] = g.mp_id[b]
         out.append(c)

@@ -132,14 +132,19 @@ class PerCrystalResult(NamedTuple):
         return head + ([[self.mp_id, self.preds.cpu().numpy(), self.y.cpu().numpy(), self.embeddings.cpu().numpy()]],)
 
 
-def test_per_crystal(predictor, ds, indices=None, batch_size: int = 64) -> PerCrystalResult:
+def test_per_crystal(predictor, ds, indices=None, batch_size: int = 64, weights=None) -> PerCrystalResult:
     """`utils.test` / `utils.test_phonon` over the crystals ``indices`` (default: all, in order) of a ``loader.DeviceDataset`` at
     the reference's batch size 1, computed in passes of ``batch_size`` crystals: ``predictor`` - a ``predict.Predictor`` with
     ``per_crystal_keys=True``, a ``Predictor64`` whose module has ``set_per_crystal_keys(True)``, or a predictor whose
     ``batch_independent`` is True (the GNN-only baselines: no attention; the metrics come from their one DOS output) - gives every crystal its
     batch-1 outputs from a batched pass, ``dosx_eval_metrics`` turns each row into its four metrics on the device, and the four
     means are read back once at the end.  Every chunk runs with the n_max of the whole selection (few recorded shapes), which is
-    valid only because per-crystal keys make the outputs independent of it: without the flag this raises ``ValueError``."""
+    valid only because per-crystal keys make the outputs independent of it: without the flag this raises ``ValueError``.
+
+    ``weights``: a [C] tensor or sequence, one weight per selected crystal in the order of ``indices`` - or True for the
+    dataset's own (``ds.weights[indices]``): ``rmse``, ``mse``, ``mae`` and ``r2`` are then the weighted means ``sum_c w_c m_c /
+    sum_c w_c`` of the per-crystal table, formed in float64 on the device and read back in the same single transfer;
+    ``per_crystal`` is unchanged.  None (the default): the plain means."""
     from . import ops
     flag = getattr(predictor, "per_crystal_keys", None)
     if flag is None:
@@ -154,6 +159,17 @@ def test_per_crystal(predictor, ds, indices=None, batch_size: int = 64) -> PerCr
     C = int(idx.shape[0])
     if C == 0:
         raise ValueError("test_per_crystal: no crystals selected")
+    w = None
+    if weights is not None:
+        if weights is True:
+            if ds.weights is None:
+                raise ValueError("test_per_crystal(weights=True): the dataset holds no weights (ds.set_weights(w))")
+            w = ds.weights.index_select(0, torch.from_numpy(idx).to(ds.device)).to(torch.float64)
+        else:
+            w = weights if torch.is_tensor(weights) else torch.as_tensor(weights, dtype=torch.float64)
+            w = w.detach().to(ds.device, torch.float64).reshape(-1)
+        if w.numel() != C:
+            raise ValueError(f"test_per_crystal: {w.numel()} weights for {C} crystals")
     predictor.eval()
     edos = predictor.kind != "phonon"
     n_max = int(ds.n_nodes[idx].max())
@@ -174,7 +190,8 @@ def test_per_crystal(predictor, ds, indices=None, batch_size: int = 64) -> PerCr
             # the bucket's graph_ptr ends at its N real nodes: the ghost rows behind them belong to no crystal's sum
             H = x.shape[1]
             ops.graph_pool(x, slot.g.meta.graph_ptr, embeddings[rows].data_ptr(), H, B, H)
-    rmse, mse, mae, r2_ = table.mean(0).tolist()                       # the one transfer
+    means = table.mean(0) if w is None else (table * w[:, None]).sum(0) / w.sum()
+    rmse, mse, mae, r2_ = means.tolist()                               # the one transfer
     ops.check_exchanges(dev)            # (the host has just waited for the device: a stalled exchange voids these metrics)
     mp_id = [ds.mp_id[i] for i in idx] if edos and ds.mp_id is not None else None
     return PerCrystalResult(rmse, mse, mae, r2_, table, preds, ys, embeddings, mp_id)

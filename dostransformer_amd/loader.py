@@ -70,11 +70,59 @@ class DeviceDataset:
                 self._graph[k] = f(torch.stack([c[k].reshape(-1) for c in crystals], 0))
         if "system" in crystals[0]:
             self._graph["system"] = torch.stack([torch.as_tensor(c["system"]).reshape(()) for c in crystals]).to(torch.int64).to(self.device)
+        if "weight" in crystals[0]:           # per-crystal sample weights (trainers' sample_weights=True), a graph-level table
+            self._graph["weight"] = self._checked_weights([c["weight"] for c in crystals], C)
         self.mp_id = [c["mp_id"] for c in crystals] if "mp_id" in crystals[0] else None
         self.num_crystals = C
 
     def __len__(self) -> int:
         return self.num_crystals
+
+    # ---- per-crystal sample weights ----------------------------------------------------------------------------------------
+    def _checked_weights(self, w, C: int) -> torch.Tensor:
+        """[C] weights as the resident table holds them (the dataset's floating-point dtype, on the device), checked ON THE HOST:
+        this is where bad weights are caught - the step never looks (include/dosx.h: negative or non-finite weights are
+        undefined in the loss kernel)."""
+        if not torch.is_tensor(w):
+            w = torch.tensor([float(v) for v in w], dtype=torch.float64)
+        h = w.detach().to("cpu", torch.float64).reshape(-1)
+        if h.numel() != C:
+            raise ValueError(f"DeviceDataset: {h.numel()} weights for {C} crystals")
+        if not bool(torch.isfinite(h).all()):
+            raise ValueError(f"DeviceDataset: weight {int((~torch.isfinite(h)).nonzero()[0])} is not finite")
+        if bool((h < 0).any()):
+            raise ValueError(f"DeviceDataset: weight {int((h < 0).nonzero()[0])} is negative")
+        dt = self._x.dtype if self._x.is_floating_point() else torch.float32
+        return h.to(dt).to(self.device)
+
+    @property
+    def weights(self) -> Optional[torch.Tensor]:
+        """The resident [C] sample weights (None: the dataset has none).  Write them with :meth:`set_weights`."""
+        return self._graph.get("weight")
+
+    def set_weights(self, w) -> None:
+        """Give every crystal a sample weight (``w``: [C], finite and >= 0, checked here on the host, once).  Written IN PLACE
+        into the resident table - and into its copies in the programs' dtypes -, which the weighted loss launch of
+        ``step_dataset`` reads at every step, like ``param_groups[k]["lr"]``: new weights between epochs (a curriculum, crystals
+        dropped with 0) re-record nothing and wait for nothing.  A dataset built without weights gets its table here."""
+        new = self._checked_weights(w, self.num_crystals)
+        cur = self._graph.get("weight")
+        if cur is None:
+            self._graph["weight"] = cur = new
+        else:
+            cur.copy_(new)
+        for name, dt in (("_tables32", torch.float32), ("_tables64", torch.float64)):
+            t = getattr(self, name, None)
+            if t is None:
+                continue
+            if t.get("weight") is None:
+                t["weight"] = cur.to(dt).contiguous()
+            elif t["weight"] is not cur:
+                t["weight"].copy_(cur)
+
+    def _weight_table(self, dt: torch.dtype) -> Optional[torch.Tensor]:
+        w = self._graph.get("weight")
+        return None if w is None else w.to(dt).contiguous()
 
     @staticmethod
     def _check_crystal(ci: int, c: Dict[str, object], ei: np.ndarray, n: int) -> None:
@@ -152,7 +200,7 @@ class DeviceDataset:
         sel64 = sel.to(torch.int64)
         for k, v in self._graph.items():
             g = v.index_select(0, sel64)
-            fields[k] = g if k in ("phdos", "system") else g.reshape(-1)
+            fields[k] = g if k in ("phdos", "system", "weight") else g.reshape(-1)
         if self.mp_id is not None:
             fields["mp_id"] = [self.mp_id[i] for i in idx]
         # the message GEMM's tile table: the selected crystals' tables with the batch offsets added - the table
@@ -174,7 +222,7 @@ class DeviceDataset:
             t = {"x": self._x.to(torch.float32).contiguous(), "edge": self._edge[ek].to(torch.float32).contiguous(),
                  "edge_key": ek, "target": self._graph[tk].to(torch.float32).contiguous(), "target_key": tk,
                  "glob": self._graph["glob"].to(torch.float32).contiguous() if "glob" in self._graph else None,
-                 "system": self._graph["system"].to(torch.int32).contiguous()}
+                 "system": self._graph["system"].to(torch.int32).contiguous(), "weight": self._weight_table(torch.float32)}
             self._tables32 = t
         return t
 
@@ -189,7 +237,7 @@ class DeviceDataset:
             f64 = lambda v: v.to(torch.float64).contiguous()
             t = {"x": f64(self._x), "edge": f64(self._edge["edge_vec"]), "edge_key": "edge_vec",
                  "target": f64(self._graph["phdos"]), "target_key": "phdos", "glob": None,
-                 "system": self._graph["system"].to(torch.int32).contiguous()}
+                 "system": self._graph["system"].to(torch.int32).contiguous(), "weight": self._weight_table(torch.float64)}
             self._tables64 = t
         return t
 

@@ -1675,7 +1675,8 @@ def sum_to(src, n, dst):
 LOSS_KINDS = {"crystal_rmse": _abi.DOSX_LOSS_RMSE, "mse": _abi.DOSX_LOSS_MSE, "mae": _abi.DOSX_LOSS_MAE, "huber": _abi.DOSX_LOSS_HUBER}
 
 
-def _loss_rows(who: str, dt: torch.dtype, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global) -> None:
+def _loss_rows(who: str, dt: torch.dtype, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global,
+               weights=None, weight_index=None, bin_weights=None) -> None:
     if isinstance(kind, str):
         if kind not in LOSS_KINDS:
             raise ValueError(f"{who}: kind {kind!r} is not one of {sorted(LOSS_KINDS)}")
@@ -1700,22 +1701,61 @@ def _loss_rows(who: str, dt: torch.dtype, pg, ps, y, kind, clamp_target, beta, d
     for k, t in ts.items():
         if t is not None and not t.is_contiguous():
             raise ValueError(f"{who}: {k} must be contiguous (row slices of a table are), got strides {t.stride()}")
-    _call("dosx_loss_rows" if dt == torch.float32 else "dosx_loss_rows_f64", pg.data_ptr(), _p(ps), y.data_ptr(), B, S,
-          B if B_global is None else int(B_global), int(kind), int(bool(clamp_target)), float(beta),
-          0.0 if delta is None else float(delta), dpg.data_ptr(), _p(dps), _p(per_crystal), loss.data_ptr(), _stream(),
-          w=lambda: ("loss_rows", "loss_rows_kernel", "hbm", (2.0 if ps is None else 3.0) * pg.element_size() * 2 * B * S,
-                     1 if per_crystal is None else 2))
+    args = (pg.data_ptr(), _p(ps), y.data_ptr(), B, S, B if B_global is None else int(B_global), int(kind),
+            int(bool(clamp_target)), float(beta), 0.0 if delta is None else float(delta), dpg.data_ptr(), _p(dps), _p(per_crystal),
+            loss.data_ptr())
+    work = lambda: ("loss_rows", "loss_rows_kernel", "hbm", (2.0 if ps is None else 3.0) * pg.element_size() * 2 * B * S,
+                    1 if per_crystal is None else 2)
+    if weights is None and weight_index is None and bin_weights is None:        # today's callers issue today's launch
+        _call("dosx_loss_rows" if dt == torch.float32 else "dosx_loss_rows_f64", *args, _stream(), w=work)
+        return
+    if weights is None:
+        if weight_index is not None:
+            raise ValueError(f"{who}: weight_index selects out of weights, which is None")
+    else:
+        if weights.dtype != dt or not weights.is_cuda:
+            raise TypeError(f"{who}: weights must be a {dt} CUDA tensor, got {weights.dtype} on {weights.device}")
+        if weights.dim() != 1 or not weights.is_contiguous():
+            raise ValueError(f"{who}: weights must be a contiguous 1-D tensor, got shape {tuple(weights.shape)} strides "
+                             f"{weights.stride()}")
+        if weight_index is None and weights.numel() != B:
+            raise ValueError(f"{who}: weights has {weights.numel()} entries for {B} crystals (a longer table needs weight_index)")
+        if weight_index is not None and weights.numel() < 1:
+            raise ValueError(f"{who}: weight_index selects out of an empty weights table")
+    if weight_index is not None:
+        if weight_index.dtype != torch.int32 or not weight_index.is_cuda:
+            raise TypeError(f"{who}: weight_index must be an int32 CUDA tensor, got {weight_index.dtype} on {weight_index.device}")
+        if weight_index.dim() != 1 or weight_index.numel() != B or not weight_index.is_contiguous():
+            raise ValueError(f"{who}: weight_index must be a contiguous [B] = [{B}] tensor, got shape {tuple(weight_index.shape)} "
+                             f"strides {weight_index.stride()}")
+    if bin_weights is not None:
+        if bin_weights.dtype != dt or not bin_weights.is_cuda:
+            raise TypeError(f"{who}: bin_weights must be a {dt} CUDA tensor, got {bin_weights.dtype} on {bin_weights.device}")
+        if bin_weights.dim() != 1 or bin_weights.numel() != S or not bin_weights.is_contiguous():
+            raise ValueError(f"{who}: bin_weights must be a contiguous [S] = [{S}] tensor, got shape {tuple(bin_weights.shape)} "
+                             f"strides {bin_weights.stride()}")
+    _call("dosx_loss_rows_w" if dt == torch.float32 else "dosx_loss_rows_w_f64", *args, _p(weights), _p(weight_index),
+          _p(bin_weights), _stream(), w=work)
 
 
 def loss_rows(pg: torch.Tensor, ps: Optional[torch.Tensor], y: torch.Tensor, kind, *, clamp_target: bool = False,
               beta: float = 1.0, delta: Optional[float] = None, dpg: torch.Tensor, dps: Optional[torch.Tensor] = None,
-              per_crystal: Optional[torch.Tensor] = None, loss: torch.Tensor, B_global: Optional[int] = None) -> None:
+              per_crystal: Optional[torch.Tensor] = None, loss: torch.Tensor, B_global: Optional[int] = None,
+              weights: Optional[torch.Tensor] = None, weight_index: Optional[torch.Tensor] = None,
+              bin_weights: Optional[torch.Tensor] = None) -> None:
     """Per-crystal loss of the [B,S] predictions pg (and ps) against y with its gradient (include/dosx.h: dosx_loss_rows):
     ``l_b = f(pg_b) + beta f(ps_b)`` with f the crystal's RMSE, MSE, MAE or Huber(``delta``) term - ``kind`` a key of
     :data:`LOSS_KINDS` or its enumerator -, ``per_crystal[b] = l_b`` (optional), ``loss[0] = sum_b l_b / B_global`` (default B) and
     dpg / dps the gradient of loss[0].  ``clamp_target``: the eDOS target ``max(y, 0)``.  ``ps = dps = None``: a model with one
-    output.  All float32, contiguous (row slices of larger tables are); a crystal whose RMSE is 0 gets a zero gradient."""
-    _loss_rows("loss_rows", torch.float32, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global)
+    output.  All float32, contiguous (row slices of larger tables are); a crystal whose RMSE is 0 gets a zero gradient.
+
+    ``weights`` / ``weight_index`` / ``bin_weights`` (include/dosx.h: dosx_loss_rows_w): sample weights ``w_b`` - ``weights[b]``, or
+    ``weights[weight_index[b]]`` out of a whole dataset's table with ``weight_index`` the batch's [B] int32 selection (its entries
+    must lie inside the table: nothing here reads them) - and [S] energy-bin weights ``v_s`` (sum > 0): ``loss[0] = sum_b w_b l_b /
+    B_global`` with f the ``v``-weighted means, ``per_crystal[b]`` still the crystal's own ``l_b``; ``w_b == 0`` writes zero
+    gradient rows and a zero share whatever the crystal holds.  All three None: the unweighted entry, the launch it always was."""
+    _loss_rows("loss_rows", torch.float32, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global,
+               weights, weight_index, bin_weights)
 
 
 # ---- guarded optimizer step (csrc/step_guard.hip; include/dosx.h: DosxStepGuard) -----------------------------------------------
@@ -2352,9 +2392,12 @@ def loss_phonon64(pg: torch.Tensor, ps: torch.Tensor, y: torch.Tensor, beta: flo
 
 def loss_rows64(pg: torch.Tensor, ps: Optional[torch.Tensor], y: torch.Tensor, kind, *, clamp_target: bool = False,
                 beta: float = 1.0, delta: Optional[float] = None, dpg: torch.Tensor, dps: Optional[torch.Tensor] = None,
-                per_crystal: Optional[torch.Tensor] = None, loss: torch.Tensor, B_global: Optional[int] = None) -> None:
-    """:func:`loss_rows` on float64 operands (include/dosx.h: dosx_loss_rows_f64)."""
-    _loss_rows("loss_rows64", torch.float64, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global)
+                per_crystal: Optional[torch.Tensor] = None, loss: torch.Tensor, B_global: Optional[int] = None,
+                weights: Optional[torch.Tensor] = None, weight_index: Optional[torch.Tensor] = None,
+                bin_weights: Optional[torch.Tensor] = None) -> None:
+    """:func:`loss_rows` on float64 operands (include/dosx.h: dosx_loss_rows_f64 / dosx_loss_rows_w_f64)."""
+    _loss_rows("loss_rows64", torch.float64, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global,
+               weights, weight_index, bin_weights)
 
 
 def grad_accumulate64(dst: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None, n: Optional[int] = None, *,

@@ -37,12 +37,15 @@ class Slot:
     - a torch cast inside the recording would not be replayed.  The buffers of a padded shape carry ``real_nodes`` (the real
     node count of the batch they hold), like a ``pad_batch`` batch."""
 
-    def __init__(self, g, m: GraphMeta, kind: str, dtype: torch.dtype, targets: bool = True):
-        """Buffers made from (and holding) batch ``g`` with metadata ``m``, on the device of ``m``; torch copies only."""
+    def __init__(self, g, m: GraphMeta, kind: str, dtype: torch.dtype, targets: bool = True, weights: bool = False):
+        """Buffers made from (and holding) batch ``g`` with metadata ``m``, on the device of ``m``; torch copies only.
+        ``weights``: also a static ``weight`` buffer, [B] sample weights filled with the other fields (trainers' sample_weights)."""
         dev = m.src.device
         fields = ["x", "system"] + (["edge_vec"] if kind == "phonon" else ["edge_attr", "glob"])
         if targets:
             fields.append("phdos" if kind == "phonon" else "y_ft")
+        if weights:
+            fields.append("weight")
         f = {k: torch.empty(g[k].shape, dtype=dtype if g[k].is_floating_point() else torch.int32, device=dev).copy_(g[k])
              for k in fields}
         f["edge_index"], f["batch"] = getattr(g, "edge_index", None), getattr(g, "batch", None)     # never read by the kernels
@@ -68,8 +71,11 @@ class Slot:
 
     @classmethod
     def empty(cls, kind: str, device, dtype: torch.dtype, B: int, n_pad: int, e_pad: int, n_max: int, Fa: int, Fe: int,
-              S: int, tiled: bool = False) -> "Slot":
-        """Uninitialised static buffers of a bucket, to be filled by ``DeviceDataset.collate_into`` (no source batch)."""
+              S: int, tiled: bool = False, weight_table: Optional[torch.Tensor] = None) -> "Slot":
+        """Uninitialised static buffers of a bucket, to be filled by ``DeviceDataset.collate_into`` (no source batch).
+        ``weight_table``: the dataset's resident [C] sample weights in ``dtype`` - the bucket then carries the table itself as
+        ``weight`` and the selection ``collate_into`` leaves in its index scratch as ``weight_index``: the loss launch gathers,
+        no [B] staging buffer and nothing for the collate kernels to do."""
         flt = lambda *s: torch.empty(*s, dtype=dtype, device=device)
         i32 = lambda *s: torch.empty(*s, dtype=torch.int32, device=device)
         f = {"x": flt(n_pad, Fa), "system": i32(B)}
@@ -86,6 +92,8 @@ class Slot:
                          seg_tile=i32(3, seg_tile_bound(n_pad, e_pad, B) + 1) if tiled else None)
         self = cls.__new__(cls)
         self._setup(CrystalBatch(f, B, meta), fields)
+        if weight_table is not None:
+            self.g["weight"], self.g["weight_index"] = weight_table, self.collate_scratch()["small"][:B]
         return self
 
     def collate_scratch(self):

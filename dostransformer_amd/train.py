@@ -260,18 +260,87 @@ class _AdamWState(StepGuard, WeightEma):
             raise DosxError(f"{who}(loss=...) is a single-GPU mode: not with dist (data parallelism)")
         self.loss, self.huber_delta = loss, None if huber_delta is None else float(huber_delta)
 
-    def _loss_rows(self, alloc, dev, pg, ps, y, clamp: bool, dpg, dps, B_global: Optional[int] = None):
+    def _loss_rows(self, alloc, dev, pg, ps, y, clamp: bool, dpg, dps, B_global: Optional[int] = None, weights=(None, None)):
         """The one launch site of the per-crystal losses: -> (per-crystal l_b [B], loss 0-dim), both on static buffers when
         the step is being recorded.  ``ps = dps = None``: a one-output model (``beta`` is not read then).  ``B_global``: the
-        count the mean is taken over - the batch's own outside an accumulation window, the window's total inside one."""
+        count the mean is taken over - the batch's own outside an accumulation window, the window's total inside one.
+        ``weights``: what ``_batch_weights`` returned for the batch; with them or with ``bin_weights=`` the weighted entry."""
         B = int(pg.shape[0])
         if B_global is None:
             B_global = B if self._window_total is None else self._window_total
         per, loss = alloc(dev, B), alloc(dev, 1)
         fn = ops.loss_rows if pg.dtype == torch.float32 else ops.loss_rows64
         fn(pg, ps, y, self.loss, clamp_target=clamp, beta=self.beta, delta=self.huber_delta, dpg=dpg, dps=dps, per_crystal=per,
-           loss=loss, B_global=int(B_global))
+           loss=loss, B_global=int(B_global), weights=weights[0], weight_index=weights[1],
+           bin_weights=self._bin_operand(dev, pg.dtype))
         return per, loss[0]
+
+    # ---- sample weights and energy-bin weights (include/dosx.h: dosx_loss_rows_w / dosx_loss_rows_w_f64; DESIGN.md 9.10) --------
+    sample_weights = False            # True: every batch carries a [B] field `weight`, step_dataset reads the dataset's table
+    bin_weights = None                # None, or the [S] energy-bin weights as given (float64, on the host)
+    _bin_dev = None                   # ... on the device in the program's dtype, moved there once
+
+    def _init_weights(self, who: str, sample_weights, bin_weights, dist=None) -> None:
+        """``sample_weights=`` / ``bin_weights=`` of a trainer's constructor; call it after ``_init_loss``.  Constructor arguments
+        like ``beta`` and ``loss``: not part of ``state_dict()``."""
+        self.sample_weights, self.bin_weights, self._bin_dev = bool(sample_weights), None, None
+        if not self.sample_weights and bin_weights is None:
+            return
+        what = " and ".join(n for n, on in (("sample_weights=True", self.sample_weights), ("bin_weights=...", bin_weights is not None)) if on)
+        if dist is not None:
+            raise DosxError(f"{who}({what}) is a single-GPU mode: not with dist (data parallelism)")
+        if self.loss is None:
+            raise ValueError(f"{who}({what}) weighs the per-crystal losses: pass loss=\"crystal_rmse\" (on an eDOS model the default "
+                             f"objective, bit for bit) or another of {', '.join(repr(k) for k in ops.LOSS_KINDS)}")
+        if bin_weights is None:
+            return
+        v = bin_weights if torch.is_tensor(bin_weights) else torch.as_tensor(bin_weights, dtype=torch.float64)
+        v = v.detach().to("cpu", torch.float64).clone()
+        S = int(self.model._cfg.S)
+        if v.dim() != 1 or v.numel() != S:
+            raise ValueError(f"{who}(bin_weights=...): shape {tuple(v.shape)}, want [S] = [{S}], one weight per energy bin")
+        if not bool(torch.isfinite(v).all()) or bool((v < 0).any()):
+            raise ValueError(f"{who}(bin_weights=...): every bin weight must be finite and >= 0")
+        if not float(v.sum()) > 0.0:
+            raise ValueError(f"{who}(bin_weights=...): the bin weights sum to 0 - no bin would be left in the loss")
+        self.bin_weights = v
+
+    def _bin_operand(self, dev, dtype):
+        if self.bin_weights is None:
+            return None
+        if self._bin_dev is None or self._bin_dev.device != dev or self._bin_dev.dtype != dtype:
+            if self._bin_dev is not None:      # (the module moved: the recordings hold the old buffer's address)
+                self._slots = OrderedDict()
+            self._bin_dev = self.bin_weights.to(dev, dtype).contiguous()
+        return self._bin_dev
+
+    def _require_weight(self, what: str, g) -> None:
+        """``sample_weights=True``: the batch must carry ``weight`` - raised before anything is launched."""
+        if self.sample_weights and not (hasattr(g, "weight") and torch.is_tensor(g.weight) and g.weight.is_floating_point()
+                                        and g.weight.numel() == self._crystals_of(g)):
+            raise ValueError(f"{self._ema_who}.{what}: sample_weights=True, but the batch has no floating-point graph-level field "
+                             f"`weight` of [B] = [{self._crystals_of(g)}] entries (DeviceDataset crystals with a \"weight\", or "
+                             f"g.weight = ...)")
+
+    def _require_weight_table(self, what: str, ds, tables):
+        """``sample_weights=True``: the dataset's resident weight table in the program's dtype, or the refusal."""
+        if not self.sample_weights:
+            return None
+        w = tables.get("weight")
+        if w is None:
+            raise ValueError(f"{self._ema_who}.{what}: sample_weights=True, but the dataset holds no weights (crystals with a "
+                             f"\"weight\", or ds.set_weights(w))")
+        return w
+
+    def _batch_weights(self, g, cast):
+        """(w, w_index) of batch ``g`` for ``_loss_rows``: ``g.weight`` converted as the target is (``cast``; a slot's static
+        buffer comes back as it is), with ``g.weight_index`` where a dataset step left its table and the bucket's selection."""
+        if not self.sample_weights:
+            return (None, None)
+        wi = getattr(g, "weight_index", None)
+        if wi is None:
+            self._require_weight("step", g)
+        return (cast(g.weight).reshape(-1), wi)
 
     def _whole_or_window(self, B: int, n_global) -> bool:
         """True when ``n_global`` is the batch's own count - or, inside an accumulation window, the window's total (the internal
@@ -429,6 +498,15 @@ class Trainer(_AdamWState, SlotCache):
     step on the objective of the concatenated batch, every micro-batch through its ordinary program with the loss divided by the
     window's crystal count, one ``dosx_grad_accumulate`` launch behind each (see ``step_accumulate``).  ``step`` and
     ``step_dataset`` issue the launches they always issued.
+
+    ``sample_weights=True`` / ``bin_weights=[S]`` (with one of the four ``loss=`` kinds): torch's ``(w * per_sample_loss).mean()`` -
+    ``loss = sum_b w_b l_b / B`` with the per-crystal terms ``sum_s v_s e(r) / sum_s v_s`` under energy-bin weights ``v`` - through
+    ``dosx_loss_rows_w`` in place of ``dosx_loss_rows``, no other launch.  ``step(g)`` reads the batch's ``[B]`` field
+    ``g.weight``; ``step_dataset`` hands the kernel the dataset's resident table (``DeviceDataset.set_weights``: checked on the
+    host once, written in place, read at every step) and the bucket's selection, and the launch gathers.  All-ones weights train
+    the unweighted bits; a weight of exactly 0 takes a crystal out whatever it holds (a NaN target included: the guard does not
+    trip); ``crystal_losses`` stay the crystals' own unweighted losses.  Every mode, windows, the guard, frozen parameters, groups
+    and the average; constructor arguments like ``loss``: not in ``state_dict()``; not under data parallelism.
     """
 
     def __init__(self, model: DOSTransformerBase, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2,
@@ -436,7 +514,7 @@ class Trainer(_AdamWState, SlotCache):
                  bucket=(8, 128), max_slots: int = 32, promote: float = 0.0, per_crystal_keys: bool = False,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None,
                  ema_decay: Optional[float] = None, ema_warmup: bool = True, loss: Optional[str] = None,
-                 huber_delta: Optional[float] = None):
+                 huber_delta: Optional[float] = None, sample_weights: bool = False, bin_weights=None):
         if not isinstance(model, (DOSTransformerBase, GraphnetworkBase)):
             raise TypeError("Trainer drives DOSTransformer / DOSTransformer_phonon / Graphnetwork / Graphnetwork_phonon / mlp modules")
         model._require_fp32_program("Trainer")
@@ -463,6 +541,7 @@ class Trainer(_AdamWState, SlotCache):
         self._init_param_groups("Trainer", param_groups, dist)
         self._init_ema("Trainer", ema_decay, ema_warmup, dist)
         self._init_loss("Trainer", loss, huber_delta, dist)
+        self._init_weights("Trainer", sample_weights, bin_weights, dist)
         self.dist = dist
         self.graph = graph
         self.replay = replay
@@ -505,13 +584,14 @@ class Trainer(_AdamWState, SlotCache):
         model, dev, cfg = self.model, fp.flat.device, self.model._cfg
         B, S = m.num_graphs, cfg.S
         self._require_whole_batch(B, st_n_global)
+        w = self._batch_weights(g, Fn._f32)          # (refuses a batch without `weight` before anything is launched)
         if self._baseline:
             out = model._program_fwd(fp.P, g, m, factored_head=True)
             y = Fn._f32(g.phdos).reshape(B, S) if self.kind == "phonon" else Fn._f32(g.y_ft).reshape(-1)
-            return {"ctx": out[-1], "dos": out[0], "out": out[:-1] if model._returns_x else out[0], "B": B, "S": S, "y": y}
+            return {"ctx": out[-1], "dos": out[0], "out": out[:-1] if model._returns_x else out[0], "B": B, "S": S, "y": y, "w": w}
         dg, xL, ds, (ctx, dos) = model._program_fwd(fp.P, g, m, bump_seed=False,     # (step() bumps the dropout seed)
                                                     per_crystal_keys=self._per_crystal_keys)
-        st = {"ctx": ctx, "dos": dos, "out": (dg, xL, ds), "B": B, "S": S}
+        st = {"ctx": ctx, "dos": dos, "out": (dg, xL, ds), "B": B, "S": S, "w": w}
         if self.kind == "phonon":
             st["y"] = Fn._f32(g.phdos).reshape(B, S)
             if self.loss is not None:      # a per-crystal loss: one entry in _part_b, no SSE pair
@@ -534,7 +614,8 @@ class Trainer(_AdamWState, SlotCache):
         ddos = Fn._empty(dev, *dos.shape)
         if self.loss is not None:          # eDOS clamps its target at 0 (main_eDOS.py:113), phonon does not; n_global == B (_part_a)
             st["crystal"], loss = self._loss_rows(Fn._empty, dev, dos[:B], dos[B:], st["y"], self.kind != "phonon", ddos[:B], ddos[B:],
-                                                  B_global=n_global)         # ... or, inside a window, the window's total
+                                                  B_global=n_global,         # ... or, inside a window, the window's total
+                                                  weights=st["w"])
         elif self.kind == "phonon":
             loss = Fn._empty(dev, 1)
             if st["split_loss"] or int(n_global) != B:
@@ -569,7 +650,7 @@ class Trainer(_AdamWState, SlotCache):
         if self.loss is not None:          # the one-output form of the entry: no second gradient, no scratch
             ddos = Fn._empty(dev, B, S)
             st["crystal"], loss = self._loss_rows(Fn._empty, dev, dos, None, st["y"], self.kind != "phonon", ddos, None,
-                                                  B_global=n_global)
+                                                  B_global=n_global, weights=st["w"])
             return self._bwd_baseline(fp, m, st, ddos, loss)
         ddos, scr = Fn._empty(dev, B, S), Fn._empty(dev, B, S)
         if self.kind == "phonon":
@@ -790,11 +871,14 @@ class Trainer(_AdamWState, SlotCache):
             m = g.meta
         ng = self._n_global(m.num_graphs, n_global, g)
         self._require_whole_batch(m.num_graphs, ng)              # (before a slot is made, not inside its recording)
+        self._require_weight("step", g)
         key = (m.num_nodes, m.num_edges, m.num_graphs, m.n_max, ng, m.seg_tile is not None)
+        if self.sample_weights:               # (the last field of a dataset step's key is its table: this batch brings its own)
+            key += (None,)
         slot = self._lookup(key)
         fresh = slot is None
-        if fresh:
-            slot = Slot(g, m, self.kind, torch.float32)       # (graph mode captures on the slot's own copy of this batch)
+        if fresh:                             # (graph mode captures on the slot's own copy of this batch)
+            slot = Slot(g, m, self.kind, torch.float32, weights=self.sample_weights)
         else:
             slot.load(g)
         loss = self._run_slot(slot, fp, ng, fresh)
@@ -820,6 +904,7 @@ class Trainer(_AdamWState, SlotCache):
         model = self.model
         dev = model._module_device()
         model._require_fp32_program("Trainer")
+        table = self._require_weight_table("step_dataset", ds, ds._f32_tables())
         fp = self._flat_for(dev, None, int(ds._f32_tables()["x"].shape[1]))
         self._state(fp)
         idx, N, E, n_max = ds.bucket_dims(indices, n_max)
@@ -850,12 +935,14 @@ class Trainer(_AdamWState, SlotCache):
         self._require_whole_batch(B, ng)
         tiled = True
         key = (n_pad, e_pad, B, n_max, ng, tiled)
+        if table is not None:                 # another dataset's table: slots of its own, never a stale pointer
+            key += (table.data_ptr(),)
         slot = self._lookup(key, allow_promote=True)
         fresh = slot is None
         if fresh:
             t = ds._f32_tables()
             slot = Slot.empty(self.kind, dev, torch.float32, B, n_pad, e_pad, n_max, int(t["x"].shape[1]),
-                              int(t["edge"].shape[1]), int(t["target"].shape[1]), tiled=tiled)
+                              int(t["edge"].shape[1]), int(t["target"].shape[1]), tiled=tiled, weight_table=table)
         ds.collate_into(slot.g, idx, slot.collate_scratch())
         slot._loaded = None                                        # (the static buffers now hold a batch no object stands for)
         self._bump_dropout_seed()
@@ -900,6 +987,7 @@ class Trainer(_AdamWState, SlotCache):
 
     def step(self, g, n_global: Optional[int] = None) -> torch.Tensor:
         self._ema_refuse("step")
+        self._require_weight("step", g)
         self._bump_dropout_seed()
         loss = self._graph_step(g, n_global) if (self.graph or self.replay) else self.forward_backward(g, n_global, _bump=False)
         self.optimizer_step()
@@ -924,6 +1012,8 @@ class Trainer(_AdamWState, SlotCache):
         batches = list(batches)
         self._window_checks("step_accumulate", len(batches))
         sizes = self._window_sizes("step_accumulate", (self._crystals_of(g) for g in batches))
+        for g in batches:
+            self._require_weight("step_accumulate", g)
         if len(batches) == 1:
             return self.step(batches[0])
         T = sum(sizes)

@@ -63,6 +63,10 @@ class Trainer64(_AdamWState, SlotCache):
     batch-1 gradients.  None (the default): the launches it always issued.
     ``step_accumulate`` / ``step_dataset_accumulate``: several micro-batches, one optimizer step on the objective of the
     concatenated batch, as on ``train.Trainer`` (needs ``loss=`` for more than one batch).
+    ``sample_weights`` / ``bin_weights``: float64 per-crystal weights (the batch's ``weight`` field, or - ``step_dataset`` - the
+    dataset's resident table gathered by the loss launch) and ``[S]`` energy-bin weights in the per-crystal loss
+    (``dosx_loss_rows_w_f64``), as on ``train.Trainer``; they need ``loss=``.  With sample weights a slot's key ends in the table's
+    address (``None`` for a batch-object slot).
     """
 
     _who = "Trainer64"            # what this driver calls itself in its refusals
@@ -71,13 +75,14 @@ class Trainer64(_AdamWState, SlotCache):
                  eps: float = 1e-8, replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None,
                  ema_decay: Optional[float] = None, ema_warmup: bool = True, loss: Optional[str] = None,
-                 huber_delta: Optional[float] = None):
+                 huber_delta: Optional[float] = None, sample_weights: bool = False, bin_weights=None):
         self._require_model(model)
         self._init_guard(self._who, max_grad_norm, skip_nonfinite)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, tuple(betas), eps
         self._init_param_groups(self._who, param_groups)
         self._init_ema(self._who, ema_decay, ema_warmup)
         self._init_loss(self._who, loss, huber_delta)
+        self._init_weights(self._who, sample_weights, bin_weights)
         self._crystal = None              # the per-crystal losses of the program just issued (loss=...), else None
         self.replay = bool(replay)
         self.max_slots = int(max_slots)
@@ -105,6 +110,7 @@ class Trainer64(_AdamWState, SlotCache):
     def _refuse(self, g) -> None:
         """What a step cannot run on - raised before anything (the dropout seed included) has changed."""
         self._require_model(self.model)
+        self._require_weight("step", g)
         if self.bucket is None and getattr(g, "real_nodes", None) is not None:
             raise DosxError(f"{self._who}: ghost-padded batches (batch.pad_batch) are refused without bucket=(node_step, "
                             "edge_step) - slots are keyed by the exact shape of an unpadded batch")
@@ -122,11 +128,12 @@ class Trainer64(_AdamWState, SlotCache):
         """forward program, loss kernel, backward program on the batch ``g``: -> (loss, outputs)."""
         model, cfg, dev = self.model, self.model._cfg, fp.flat.device
         B, S = m.num_graphs, cfg.S
+        w = self._batch_weights(g, F64._f64)         # (refuses a batch without `weight` before anything is launched)
         dos, xL, ctx = F64.dostransformer_phonon_fwd(fp.P, cfg, g, m, drop=drop, per_crystal_keys=model.per_crystal_keys)
         y = F64._f64(g.phdos).reshape(B, S)
         ddos = ops.alloc64(dev, 2 * B, S)
         if self.loss is not None:
-            self._crystal, loss = self._loss_rows(ops.alloc64, dev, dos[:B], dos[B:], y, False, ddos[:B], ddos[B:])
+            self._crystal, loss = self._loss_rows(ops.alloc64, dev, dos[:B], dos[B:], y, False, ddos[:B], ddos[B:], weights=w)
         else:
             loss = ops.alloc64(dev, 1)
             ops.loss_phonon64(dos[:B], dos[B:], y, self.beta, ddos[:B], ddos[B:], loss)
@@ -184,10 +191,12 @@ class Trainer64(_AdamWState, SlotCache):
             g = pad_batch(g, *bucket_sizes(m.num_nodes, m.num_edges, *self.bucket))
             m = g.meta
         key = self._key(m.num_nodes, m.num_edges, m.num_graphs, m.n_max, drop)
+        if self.sample_weights:               # (the last field of a dataset step's key is its table: this batch brings its own)
+            key += (None,)
         slot = self._lookup(key)
         fresh = slot is None
         if fresh:
-            slot = Slot(g, m, "phonon", torch.float64)
+            slot = Slot(g, m, "phonon", torch.float64, weights=self.sample_weights)
         else:
             slot.load(g, m)
         loss = self._run_slot(slot, fp, drop, fresh)
@@ -223,18 +232,21 @@ class Trainer64(_AdamWState, SlotCache):
     def _dataset_program(self, ds, indices, n_max: Optional[int]) -> torch.Tensor:
         """``step_dataset`` (``replay`` with ``bucket``) up to the optimizer: bump the seed, collate into the bucket, run the slot."""
         self._require_model(self.model)
+        table = self._require_weight_table("step_dataset", ds, ds._f64_tables())
         idx, N, E, n_max = ds.bucket_dims(indices, n_max)
         B = int(idx.shape[0])
         n_pad, e_pad = bucket_sizes(N, E, *self.bucket)
         self._bump_dropout_seed()
         fp, drop = self._prepare(None, ds)
         key = self._key(n_pad, e_pad, B, n_max, drop)
+        if table is not None:                 # another dataset's table: slots of its own, never a stale pointer
+            key += (table.data_ptr(),)
         slot = self._lookup(key, allow_promote=True)
         fresh = slot is None
         if fresh:
             t = ds._f64_tables()
             slot = Slot.empty("phonon", fp.flat.device, torch.float64, B, n_pad, e_pad, n_max, int(t["x"].shape[1]),
-                              int(t["edge"].shape[1]), int(t["target"].shape[1]))
+                              int(t["edge"].shape[1]), int(t["target"].shape[1]), weight_table=table)
         ds.collate_into(slot.g, idx, slot.collate_scratch())
         slot._loaded = None                                        # (the static buffers now hold a batch no object stands for)
         slot.set_real_nodes(N)
@@ -306,7 +318,7 @@ class GraphnetworkTrainer64(Trainer64):
                  replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None,
                  ema_decay: Optional[float] = None, ema_warmup: bool = True, loss: Optional[str] = None,
-                 huber_delta: Optional[float] = None, **unknown):
+                 huber_delta: Optional[float] = None, sample_weights: bool = False, bin_weights=None, **unknown):
         if "beta" in unknown:
             raise ValueError(f"GraphnetworkTrainer64: beta={unknown['beta']} - the model has ONE output and its loss no second "
                              f"term to weigh")
@@ -315,7 +327,7 @@ class GraphnetworkTrainer64(Trainer64):
         super().__init__(model, lr=lr, beta=1.0, weight_decay=weight_decay, betas=betas, eps=eps, replay=replay,
                          max_slots=max_slots, bucket=bucket, promote=promote, max_grad_norm=max_grad_norm,
                          skip_nonfinite=skip_nonfinite, param_groups=param_groups, ema_decay=ema_decay, ema_warmup=ema_warmup,
-                         loss=loss, huber_delta=huber_delta)
+                         loss=loss, huber_delta=huber_delta, sample_weights=sample_weights, bin_weights=bin_weights)
         self._dead = None                 # the dead-parameter set of the first batch's node-feature width
 
     def _require_model(self, model) -> None:
@@ -345,11 +357,12 @@ class GraphnetworkTrainer64(Trainer64):
     def _program(self, fp, g, m: GraphMeta, drop):
         cfg, dev = self.model._cfg, fp.flat.device
         B, S = m.num_graphs, cfg.S
+        w = self._batch_weights(g, F64._f64)
         dos, ctx = F64.graphnetwork_phonon_fwd(fp.P, cfg, g, m, factored_head=True)
         y = F64._f64(g.phdos).reshape(B, S)
         ddos = ops.alloc64(dev, B, S)
         if self.loss is not None:          # the one-output form of the entry: no second gradient, no scratch
-            self._crystal, loss = self._loss_rows(ops.alloc64, dev, dos, None, y, False, ddos, None)
+            self._crystal, loss = self._loss_rows(ops.alloc64, dev, dos, None, y, False, ddos, None, weights=w)
         else:
             scratch, loss = ops.alloc64(dev, B, S), ops.alloc64(dev, 1)
             ops.loss_phonon64(dos, dos, y, 0.0, ddos, scratch, loss)

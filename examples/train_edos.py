@@ -34,6 +34,13 @@ Gradient accumulation: --accumulate K groups K consecutive batches of the epoch 
 concatenation (every loss, the reference's included: each is a mean over crystals).
 
     python examples/train_edos.py --accumulate 4 --batch_size 16
+
+Weighted losses (with a per-crystal --loss; on this model --loss crystal_rmse is the reference's objective): --balance-systems
+[POWER] weighs every training crystal by count[its crystal system] ** -POWER, normalised to mean 1 (weights.balanced; the loss
+launch gathers the weights out of the dataset's table); --fermi-weight CENTER,WIDTH[,FLOOR] weighs the 201 energy bins by a
+Gaussian bump around bin CENTER on a floor (weights.fermi_window).
+
+    python examples/train_edos.py --loss crystal_rmse --balance-systems 0.5 --fermi-weight 100,20,0.25
 """
 import argparse
 import os
@@ -45,7 +52,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dostransformer_amd import checkpoint, evaluate, featurize, param_groups, synth, validate  # noqa: E402
+from dostransformer_amd import checkpoint, evaluate, featurize, param_groups, synth, validate, weights  # noqa: E402
 from dostransformer_amd._lib import DosxError  # noqa: E402
 from dostransformer_amd.embedder_eDOS.DOSTransformer import DOSTransformer  # noqa: E402
 from dostransformer_amd.loader import DeviceDataset  # noqa: E402
@@ -108,8 +115,24 @@ def parse_args(argv=None):
     ap.add_argument("--accumulate", type=int, default=1, metavar="K",
                     help="one optimizer step per K consecutive batches of the epoch, on the objective of their concatenation "
                          "(gradient accumulation: trainer.step_dataset_accumulate; the last window of an epoch may be shorter)")
+    ap.add_argument("--balance-systems", type=float, nargs="?", const=1.0, default=None, metavar="POWER",
+                    help="class-balanced sample weights over the 7 crystal systems: w ~ count[system] ** -POWER (default 1), mean 1 "
+                         "over the training set (weights.balanced; Trainer(sample_weights=True)); needs a per-crystal --loss")
+    ap.add_argument("--fermi-weight", default=None, metavar="CENTER,WIDTH[,FLOOR]",
+                    help="energy-bin weights: a Gaussian bump of WIDTH bins around bin CENTER on a floor in [0, 1] (default 0) "
+                         "(weights.fermi_window; Trainer(bin_weights=...)); needs a per-crystal --loss")
     param_groups.add_arguments(ap)
     args = ap.parse_args(argv)
+    if (args.balance_systems is not None or args.fermi_weight is not None) and args.loss == "reference":
+        ap.error("--balance-systems / --fermi-weight weigh the per-crystal losses: pass --loss crystal_rmse (this model's reference "
+                 "objective through the per-crystal entry) or another per-crystal --loss")
+    if args.fermi_weight is not None:
+        try:
+            fw = [float(x) for x in args.fermi_weight.split(",")]
+            assert len(fw) in (2, 3)
+        except (ValueError, AssertionError):
+            ap.error("--fermi-weight CENTER,WIDTH[,FLOOR]: two or three numbers")
+        args.fermi_weight = fw
     if args.accumulate < 1:
         ap.error("--accumulate K: K is at least 1")
     if (args.no_ema_warmup or args.save_ema) and args.ema is None:
@@ -185,7 +208,13 @@ def _main(argv=None):
     if groups is not None:
         for k, grp in enumerate(param_groups.resolve(model, groups, args.lr, 1e-2)):
             print(f"param group {k}: lr {grp['lr']:.3g} weight_decay {grp['weight_decay']:.3g}, {len(grp['names'])} tensors")
+    if args.balance_systems is not None:                           # resident table: set once, gathered by every loss launch
+        sysw = weights.balanced(ds["train"]._graph["system"].cpu(), power=args.balance_systems)
+        ds["train"].set_weights(sysw)
+        print(f"--balance-systems {args.balance_systems:g}: sample weights {float(sysw.min()):.3g} .. {float(sysw.max()):.3g}, mean 1")
+    bin_w = None if args.fermi_weight is None else weights.fermi_window(201, *args.fermi_weight)
     trainer = Trainer(model, lr=args.lr, beta=args.beta, replay=True, bucket=bucket, promote=0.08,
+                      sample_weights=args.balance_systems is not None, bin_weights=bin_w,
                       per_crystal_keys=args.per_crystal_keys,      # AdamW(lr, weight_decay=1e-2), `:91`
                       max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, param_groups=groups,
                       ema_decay=args.ema, ema_warmup=not args.no_ema_warmup,

@@ -59,6 +59,12 @@ objective of their concatenation (trainer.step_accumulate / step_dataset_accumul
 The reference's pooled RMSE does not accumulate, so K > 1 needs one of the per-crystal --loss kinds.
 
     python examples/train_phonon.py --accumulate 4 --batch-size 16 --loss crystal_rmse --per-crystal-keys
+
+Class-balanced training (fused trainers, with a per-crystal --loss): --balance-systems [POWER] weighs every training crystal by
+count[its crystal system] ** -POWER (default 1), normalised to mean 1 (weights.balanced -> DeviceDataset.set_weights ->
+Trainer(sample_weights=True): the loss becomes sum_b w_b l_b / B, the weights ride on the batch or are gathered by the loss launch).
+
+    python examples/train_phonon.py --loss crystal_rmse --per-crystal-keys --balance-systems 0.5
 """
 import argparse
 import os
@@ -70,7 +76,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dostransformer_amd import checkpoint, evaluate, featurize, ops, param_groups, synth, validate  # noqa: E402
+from dostransformer_amd import checkpoint, evaluate, featurize, ops, param_groups, synth, validate, weights  # noqa: E402
 from dostransformer_amd.embedder_phDOS.DOSTransformer_phonon import DOSTransformer_phonon  # noqa: E402
 from dostransformer_amd.loader import DeviceDataset  # noqa: E402
 from dostransformer_amd.predict import Predictor  # noqa: E402
@@ -139,8 +145,14 @@ def _main(argv=None):
     ap.add_argument("--accumulate", type=int, default=1, metavar="K",
                     help="fused trainers: one optimizer step per K consecutive batches, on the objective of their concatenation "
                          "(gradient accumulation; K > 1 needs a per-crystal --loss)")
+    ap.add_argument("--balance-systems", type=float, nargs="?", const=1.0, default=None, metavar="POWER",
+                    help="fused trainers: class-balanced sample weights over the 7 crystal systems, w ~ count[system] ** -POWER "
+                         "(default 1), mean 1 over the training set (weights.balanced; sample_weights=True); needs a per-crystal --loss")
     param_groups.add_arguments(ap)
     args = ap.parse_args(argv)
+    if args.balance_systems is not None and args.loss == "reference":
+        ap.error("--balance-systems weighs the per-crystal losses: pick --loss crystal_rmse (the reference's own batch-1 objective), "
+                 "mse, mae or huber")
     if args.accumulate < 1:
         ap.error("--accumulate K: K is at least 1")
     if args.accumulate > 1 and args.float64 and not args.fused:
@@ -184,6 +196,10 @@ def _main(argv=None):
     split = {"valid": perm[:n_val], "test": perm[n_val:2 * n_val], "train": perm[2 * n_val:]}
     ds = {k: DeviceDataset([crystals[i] for i in idx], dev, dtype=torch.float64 if args.float64 else None)
           for k, idx in split.items()}
+    if args.balance_systems is not None:                           # resident table: set once, read by every loss launch
+        sysw = weights.balanced(ds["train"]._graph["system"].cpu(), power=args.balance_systems)
+        ds["train"].set_weights(sysw)
+        print(f"--balance-systems {args.balance_systems:g}: sample weights {float(sysw.min()):.3g} .. {float(sysw.max()):.3g}, mean 1")
 
     if args.float64:
         return train_float64_fused(args, ds, dev) if args.fused else train_float64(args, ds, dev)
@@ -245,7 +261,8 @@ def _ema_args(args):
 
 
 def _loss_args(args):
-    return dict(loss=None if args.loss == "reference" else args.loss, huber_delta=args.huber_delta)
+    return dict(loss=None if args.loss == "reference" else args.loss, huber_delta=args.huber_delta,
+                sample_weights=args.balance_systems is not None)
 
 
 def _ema_report(args, trainer, run_test, name):

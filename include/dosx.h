@@ -1322,6 +1322,36 @@ int dosx_loss_rows_f64(const double* pg, const double* ps, const double* y, int 
                        int clamp_target, double beta, double delta, double* dpg, double* dps, double* per_crystal, double* loss,
                        dosx_stream_t stream);
 
+/* ---- weighted per-crystal losses (csrc/loss_rows.hip, the same kernels under two further template flags) --------------------
+ * dosx_loss_rows / _f64 with per-crystal sample weights and energy-bin weights - torch's `(w * per_sample_loss).mean()`:
+ *   w        sample weights, or NULL for all ones
+ *   w_index  NULL: w_b = w[b], w has B entries.  Otherwise w_b = w[w_index[b]]: w is a whole dataset's table, w_index the batch's
+ *            selection (every entry inside the table: the caller's contract, nothing here knows its length) - gathered inside
+ *            the loss launch, no extra launch and no [B] staging tensor.  w_index without w is refused.
+ *   bin_w    [S] energy-bin weights v_s, or NULL for unweighted
+ * With t and r = p - t as above:
+ *   V = sum_s v_s, computed by every wavefront with the lane-strided loop and the wave reduction of the crystal sums: fixed
+ *       order, bitwise run to run, no host read of bin_w.  Without bin_w: v_s = 1, V = S.
+ *   f(p_b):  RMSE sqrt(sum_s v_s r^2 / V)    MSE sum_s v_s r^2 / V    MAE sum_s v_s |r| / V    HUBER sum_s v_s h(r) / V
+ *   l_b = f(pg_b) + beta f(ps_b);   per_crystal[b] = l_b - NOT multiplied by w_b: it stays the crystal's own loss
+ *   loss[0] = (1 / B_global) sum_b w_b l_b - divided by the crystal count, not by the sum of the weights: weights that average
+ *       to 1 keep the loss scale, and B_global keeps its meaning inside an accumulation window
+ *   dpg, dps = d loss[0] / d pg, d ps
+ * w_b enters the gradient's coefficient as (w_b / B_global) and the share as (l_b w_b) / B_global, each product rounded: all-ones
+ * w with bin_w == NULL is dosx_loss_rows bit for bit, and a power-of-two multiple of one w_b scales that crystal's rows exactly.
+ * w_b == 0: the crystal's gradient rows are written as +0.0 and its share of loss[0] is exactly 0 whatever its predictions and
+ * targets hold, NaN and inf included; per_crystal[b] is still its l_b and may be NaN.  Negative or non-finite weights are
+ * undefined here: the owners of a weight table check them once on the host.  v_s == 0 removes bin s from sums and gradients (a
+ * NaN in it too); V == 0 is the caller's error (0 / 0 everywhere) - the trainers refuse such a bin_w at construction.
+ * Launches as above (two with per_crystal, one without; the same bits).  Refused with -22 and a message: everything
+ * dosx_loss_rows refuses; w_index without w; w or bin_w lying inside pg, ps, y, dpg or dps. */
+int dosx_loss_rows_w(const float* pg, const float* ps, const float* y, int B, int S, int B_global, int kind, int clamp_target,
+                     float beta, float delta, float* dpg, float* dps, float* per_crystal, float* loss, const float* w,
+                     const int32_t* w_index, const float* bin_w, dosx_stream_t stream);
+int dosx_loss_rows_w_f64(const double* pg, const double* ps, const double* y, int B, int S, int B_global, int kind,
+                         int clamp_target, double beta, double delta, double* dpg, double* dps, double* per_crystal, double* loss,
+                         const double* w, const int32_t* w_index, const double* bin_w, dosx_stream_t stream);
+
 /* ---- guarded optimizer step (csrc/step_guard.hip; the guarded AdamW entries: csrc/adamw.hip) ------------------------------
  * What a fused trainer has in place of `clip_grad_norm_` and of a GradScaler-style "skip if non-finite": one statistics launch
  * over the flat gradient, behind the recorded program and in front of the AdamW launch, and an AdamW that reads its verdict
