@@ -77,7 +77,7 @@ def source_hash() -> str:
     root = os.path.dirname(_HERE)
     files = sorted(glob.glob(os.path.join(_HERE, "csrc", "*.hip")) + glob.glob(os.path.join(_HERE, "csrc", "*.h")) +
                    glob.glob(os.path.join(_HERE, "csrc", "*.cpp")))
-    files += [os.path.join(root, "include", "dosx.h")] + [os.path.join(_HERE, f) for f in ("functional.py", "ops.py", "train.py")]
+    files += [os.path.join(root, "include", "dosx.h")] + [os.path.join(_HERE, f) for f in ("functional.py", "ops.py", "train.py", "trainer_base.py")]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.relpath(f, root).encode())

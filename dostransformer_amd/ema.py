@@ -4,9 +4,9 @@
 every parameter after ``optimizer.step()``.  The fused trainers have no place for that pass - and it would know nothing of a step
 the gradient guard skipped on the device.  With ``ema_decay=`` the one flat AdamW launch also updates the average
 (``ops.adamw*(..., ema=...)``; include/dosx.h: DosxAdamWEma, dosx_adamw_ema / _f64): the thread that holds the new parameter in
-registers reads and writes one more buffer.  This module is the host side: :class:`WeightEma`, the mixin ``train._AdamWState``
-carries - the buffer and its re-homing, ``ema_weights()`` (evaluate under the average: one ``dosx_swap_buffers`` launch in, one
-out), ``ema_state_dict()`` and the checkpoint keys.
+registers reads and writes one more buffer.  This module is the host side: :class:`WeightEma`, the mixin
+``trainer_base.TrainerBase`` carries - the buffer and its re-homing, ``ema_weights()`` (evaluate under the average: one
+``dosx_swap_buffers`` launch in, one out), ``ema_state_dict()`` and the checkpoint keys.
 """
 from __future__ import annotations
 
@@ -38,23 +38,22 @@ def schedule(decay: float, warmup: bool, t: int) -> float:
 
 
 class WeightEma:
-    """The weight average of a trainer (mixed into ``train._AdamWState``).  Expects ``model``, ``_fp``, ``_state`` and
-    ``_applied_steps``.  ``_ema`` is laid out like ``fp.flat``, in its dtype; ``_ema_t0`` is AdamW's time when averaging began."""
+    """The weight average of a trainer (mixed into ``trainer_base.TrainerBase``).  Expects ``model``, ``dist``, ``_who`` (what
+    the driver calls itself in its refusals), ``_fp``, ``_state`` and ``_applied_steps``.  ``_ema`` is laid out like ``fp.flat``,
+    in its dtype; ``_ema_t0`` is AdamW's time when averaging began."""
 
-    _ema_who = "trainer"              # what the driver calls itself in its refusals (_init_ema)
     _ema_decay: Optional[float] = None
     ema_warmup: bool = True
     _ema = None
     _ema_t0 = 0
     _ema_block = False                # True inside ema_weights(): flat holds the average, _ema the parameters
 
-    def _init_ema(self, who: str, ema_decay, ema_warmup, dist=None) -> None:
-        self._ema_who = who
-        self._ema_decay = check_decay(who, ema_decay)
+    def _init_ema(self, ema_decay, ema_warmup) -> None:
+        self._ema_decay = check_decay(self._who, ema_decay)
         self.ema_warmup = bool(ema_warmup)
         self._ema, self._ema_t0, self._ema_block = None, 0, False
-        if self._ema_decay is not None and dist is not None:
-            raise DosxError(f"{who}(ema_decay=...) is a single-GPU mode: not with dist (data parallelism)")
+        if self._ema_decay is not None and self.dist is not None:
+            raise DosxError(f"{self._who}(ema_decay=...) is a single-GPU mode: not with dist (data parallelism)")
 
     @property
     def ema_decay(self) -> Optional[float]:
@@ -65,15 +64,15 @@ class WeightEma:
     @ema_decay.setter
     def ema_decay(self, value) -> None:
         if self._ema_decay is None:
-            raise DosxError(f"{self._ema_who}: built without ema_decay=, there is no average to set a decay for")
-        value = check_decay(self._ema_who, value)
+            raise DosxError(f"{self._who}: built without ema_decay=, there is no average to set a decay for")
+        value = check_decay(self._who, value)
         if value is None:
-            raise ValueError(f"{self._ema_who}: ema_decay cannot be switched off on a running trainer")
+            raise ValueError(f"{self._who}: ema_decay cannot be switched off on a running trainer")
         self._ema_decay = value
 
     def _ema_refuse(self, what: str) -> None:
         if self._ema_block:
-            raise DosxError(f"{self._ema_who}.{what} inside `{BLOCK}` - the model holds the averaged weights there, and the "
+            raise DosxError(f"{self._who}.{what} inside `{BLOCK}` - the model holds the averaged weights there, and the "
                             f"trained ones come back when the block ends; nothing trains, freezes or checkpoints in between")
 
     def _ema_rehome(self, fp, old) -> None:
@@ -103,7 +102,7 @@ class WeightEma:
 
     def _ema_require(self, what: str):
         if self._ema_decay is None:
-            raise DosxError(f"{self._ema_who}.{what}: this trainer keeps no weight average (ema_decay=)")
+            raise DosxError(f"{self._who}.{what}: this trainer keeps no weight average (ema_decay=)")
         fp = self._fp if self._fp is not None else self.model.flat_params()
         if not self._ema_block:
             self._state(fp)
@@ -119,7 +118,7 @@ class WeightEma:
         ``state_dict`` / ``load_state_dict`` raise :class:`DosxError`, and so does the end of a block in which the model's
         frozen set was changed (the trained parameters are put back first).  The block does not nest.  A module that is not
         on the GPU is refused: the swap is a device launch."""
-        who = self._ema_who
+        who = self._who
         if self._ema_block:
             raise DosxError(f"{who}.ema_weights: `{BLOCK}` does not nest")
         dev = self.model._module_device()
@@ -187,5 +186,5 @@ class WeightEma:
                 k = fp.P[n].numel()
                 self._ema[o:o + k].copy_(saved[n].reshape(-1).to(self._ema.device, self._ema.dtype))
         h = sd.get("ema_hyper", {})
-        self._ema_decay = check_decay(self._ema_who, h.get("decay", self._ema_decay))
+        self._ema_decay = check_decay(self._who, h.get("decay", self._ema_decay))
         self.ema_warmup, self._ema_t0 = bool(h.get("warmup", self.ema_warmup)), int(h.get("t0", 0))

@@ -4,8 +4,8 @@ The fused trainers run backward and AdamW back to back, so there is no place for
 ``GradScaler``-style skip in between.  With ``max_grad_norm=`` / ``skip_nonfinite=`` a trainer issues one statistics launch over
 its flat gradient (``ops.grad_guard``) and an AdamW that reads the verdict from a device-resident record
 (``ops.adamw_guarded`` / ``ops.adamw64_guarded``; include/dosx.h: DosxStepGuard) - no host read in the step.  This module is
-the host side: :class:`StepGuard`, the mixin ``train._AdamWState`` carries, and :class:`GuardReport`, what one read-back of
-the record says.
+the host side: :class:`StepGuard`, the mixin ``trainer_base.TrainerBase`` carries, and :class:`GuardReport`, what one
+read-back of the record says.
 """
 from __future__ import annotations
 
@@ -59,23 +59,25 @@ def locate(fp, index: int) -> Optional[Tuple[Optional[str], int]]:
 
 
 class StepGuard:
-    """The guard of a trainer (mixed into ``train._AdamWState``).  Expects ``_fp``, ``_slots``, ``step_count``, ``_adamw_launch``
-    and the AdamW hyper-parameters.  ``step_count`` counts ATTEMPTS since the record was last zeroed plus the applied steps before that:
-    the record's ``skipped`` is the difference to the applied count, and ``_guard_settle`` folds it in."""
+    """The guard of a trainer (mixed into ``trainer_base.TrainerBase``).  Expects ``dist``, ``_who``, ``_fp``, ``_slots``,
+    ``step_count``, ``_adamw_launch`` and the AdamW hyper-parameters.  ``step_count`` counts ATTEMPTS since the record was last
+    zeroed plus the applied steps before that: the record's ``skipped`` is the difference to the applied count, and
+    ``_guard_settle`` folds it in."""
 
     max_grad_norm: Optional[float] = None
     skip_nonfinite: bool = False
     _guard_rec = _guard_ws = None
     _guard_status = None              # device address of the exchanges' stall status on the record's device
 
-    def _init_guard(self, who: str, max_grad_norm, skip_nonfinite, dist=None) -> None:
+    def _init_guard(self, max_grad_norm, skip_nonfinite) -> None:
+        who = self._who
         if max_grad_norm is not None:
             max_grad_norm = float(max_grad_norm)
             if math.isnan(max_grad_norm) or max_grad_norm < 0.0:
                 raise ValueError(f"{who}: max_grad_norm must be a non-negative number or None, got {max_grad_norm}")
         self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
         self._guard_rec = self._guard_ws = None
-        if self.guarded and dist is not None:
+        if self.guarded and self.dist is not None:
             raise DosxError(f"{who}(max_grad_norm / skip_nonfinite) is a single-GPU mode: not with dist (data parallelism)")
 
     @property
@@ -91,7 +93,7 @@ class StepGuard:
         return self._guard_rec, self._guard_ws
 
     def _guarded_optimizer_step(self, fp, m, v) -> None:
-        """statistics launch + the AdamW launch behind its record (``train._AdamWState._adamw_launch``)"""
+        """statistics launch + the AdamW launch behind its record (``trainer_base.TrainerBase._adamw_launch``)"""
         rec, ws = self._guard_buffers(fp.flat.device)
         self.step_count += 1
         ops.grad_guard(fp.grad, fp.n_train, rec, ws, self.max_grad_norm, self.lr, self.betas[0], self.betas[1], self.step_count,

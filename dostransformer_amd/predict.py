@@ -207,7 +207,7 @@ class Predictor(_Predictor):
     def _width_batch(self, ds):
         if not self._baseline:
             return None
-        from .train import _Width            # (which node encoder is live follows the dataset's node-feature width)
+        from .trainer_base import _Width            # (which node encoder is live follows the dataset's node-feature width)
         return _Width(int(ds._f32_tables()["x"].shape[1]))
 
     def _outputs(self, slot: Slot, n_real: int):
@@ -259,7 +259,7 @@ class Predictor64(_Predictor):
     def _width_batch(self, ds):
         if not self._baseline:
             return None
-        from .train import _Width            # (which node encoder is live follows the dataset's node-feature width)
+        from .trainer_base import _Width            # (which node encoder is live follows the dataset's node-feature width)
         return _Width(int(ds._f64_tables()["x"].shape[1]))
 
     def _outputs(self, slot: Slot, n_real: int):

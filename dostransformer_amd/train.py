@@ -22,16 +22,13 @@ from typing import Optional
 
 import torch
 
-from . import _abi
 from . import functional as Fn
 from . import ops
-from . import param_groups as _pg
 from ._lib import DosxError, from_environ
-from ._models import DOSTransformerBase, GraphnetworkBase, _SEED_MOD, rank_seed_offset
-from .batch import CrystalBatch, bucket_sizes, graph_meta, pad_batch
-from .ema import WeightEma
-from .guard import StepGuard
-from .slots import Slot, SlotCache
+from ._models import DOSTransformerBase, GraphnetworkBase
+from .batch import graph_meta
+from .slots import Slot
+from .trainer_base import TrainerBase
 
 # Data parallel: a THIRD gradient bucket (GN_decoder + message-passing layers L-1 .. 1: 1.9 of the GNN trunk's 3.0 MB at the
 # headline shape) all-reduced from the flush at layer 0, under layer 0's backward, so that only 1.1 MB stay behind the step
@@ -44,396 +41,7 @@ _DP_MID_BUCKET = from_environ("DOSX_DP_MID_BUCKET", "0") == "1"
 _DP_CHECK = from_environ("DOSX_DP_CHECK", "0") == "1"
 
 
-class _AdamWState(StepGuard, WeightEma):
-    """What Trainer and train64.Trainer64 share: the AdamW moments laid out like the model's flat parameters (in the flat
-    buffer's dtype), their checkpoint in ``torch.optim.AdamW`` vocabulary, the per-step bump of the dropout seed and the
-    gradient guard of the optimizer step (``guard.StepGuard``: ``max_grad_norm`` / ``skip_nonfinite``) and the exponential moving
-    average of the weights the AdamW launch keeps (``ema.WeightEma``: ``ema_decay`` / ``ema_warmup``, re-homed by name with the
-    moments).  Expects
-    ``model``, ``_fp``, ``_m``, ``_v``, ``_slots``, ``step_count`` and the hyper-parameters ``lr``, ``betas``, ``eps``, ``wd``, ``beta``."""
-
-    def _state(self, fp):
-        """AdamW moments laid out like ``fp``.  When the parameters are re-homed (module moved to another device after
-        ``load_state_dict``, a different dead-parameter set, ...) the moments follow BY NAME instead of being reset:
-        ``step_count`` keeps counting, so zeroed moments would silently corrupt the bias correction."""
-        if self._ema_block:                # (also what a freeze() / update_trainable() inside the block runs into)
-            self._ema_refuse("_state (step, forward_backward, optimizer_step, state_dict, load_state_dict)")
-        if self._fp is not fp:
-            if getattr(self, "dist", None) is not None and fp.n_train != fp.total:
-                raise DosxError(f"{type(self).__name__}(dist=...) with frozen parameters ({len(fp.frozen)} of {len(fp.names)}): "
-                                f"fine-tuning is a single-GPU mode, not with dist (data parallelism)")
-            m, v = torch.zeros_like(fp.flat), torch.zeros_like(fp.flat)
-            old = self._fp
-            if old is not None and self._m is not None:
-                old_off = dict(zip(old.names, old.offsets))
-                with torch.no_grad():
-                    for n, o in zip(fp.names, fp.offsets):
-                        oo = old_off.get(n)
-                        if oo is None:
-                            continue
-                        k = fp.P[n].numel()
-                        if old.P[n].numel() != k:
-                            raise RuntimeError(f"parameter {n} changed size under a running optimizer")
-                        m[o:o + k].copy_(self._m[oo:oo + k])
-                        v[o:o + k].copy_(self._v[oo:oo + k])
-            self._ema_rehome(fp, old)
-            self._m, self._v, self._fp = m, v, fp
-            self._acc = self._acc_loss = None      # (the window's accumulator belongs to the layout: made anew at the next window)
-            self._slots = OrderedDict()
-            if self._groups is not None:       # the chunk map belongs to the layout: rebuilt wherever the moments are re-homed
-                self._chunk_group = _pg.chunk_map(fp, _pg.assignment(self._groups)).to(fp.flat.device)
-        return self._m, self._v
-
-    # ---- parameter groups (param_groups.py; include/dosx.h: DosxAdamWGroups) -------------------------------------------
-    _groups = None                    # None: one lr / weight_decay, the ungrouped launch; else [{"lr", "weight_decay", "names"}]
-    _chunk_group = None               # uint8 device tensor, one entry per 64 elements of flat[:n_train], of the layout in _fp
-    _groups_host = None               # the kernel's host struct, filled from _groups at every optimizer step
-
-    def _init_param_groups(self, who: str, groups, dist=None) -> None:
-        """``param_groups=`` of a trainer's constructor; call it once ``model``, ``lr`` and ``wd`` are set."""
-        self._groups = self._chunk_group = self._groups_host = None
-        if groups is None:
-            return
-        if dist is not None:
-            raise DosxError(f"{who}(param_groups=...) is a single-GPU mode: not with dist (data parallelism)")
-        self._groups = _pg.resolve(self.model, groups, self.lr, self.wd)
-        self._groups_host = _abi.AdamWGroups()
-
-    @property
-    def param_groups(self):
-        """None without ``param_groups=``; else the list of ``{"lr", "weight_decay", "names"}`` the optimizer step reads at
-        EVERY step - entry 0 the parameters no group names (at the ``lr`` / ``weight_decay`` of construction), entry ``i + 1``
-        the constructor's group ``i``.  Assigning ``trainer.param_groups[k]["lr"]`` between steps is a learning-rate schedule:
-        nothing is re-recorded, nothing waits for the device.  ``names`` are fixed at construction."""
-        return self._groups
-
-    # ---- optimizer -------------------------------------------------------------------------------------------------------
-    def _adamw_launch(self, fp, m, v, rec=None) -> None:
-        """The optimizer's one launch for ``step_count``, the only place that chooses among the ``ops.adamw*`` functions: fp32 or
-        float64 by the flat buffer, behind the guard's record ``rec`` or not, with the trainer's parameter groups or its one
-        ``lr`` / ``wd``, keeping the weight average (``ema=``) or not.  ``flat[n_train:]`` are the frozen parameters, nothing steps
-        them (nor their average, which is the parameter itself): no launch when everything is frozen."""
-        if not fp.n_train:
-            return
-        grouped, guarded = self._groups is not None, rec is not None
-        name = ("adamw" if fp.flat.dtype == torch.float32 else "adamw64") + ("_grouped" if grouped else "") + ("_guarded" if guarded else "")
-        if grouped:
-            st = ops.adamw_groups([(grp["lr"], grp["weight_decay"]) for grp in self._groups], into=self._groups_host)
-            args = (self._chunk_group, st, self.betas[0], self.betas[1], self.eps, self.step_count)
-        else:
-            args = (self.lr, self.betas[0], self.betas[1], self.eps, self.wd) + (() if guarded else (self.step_count,))
-        kw = {}
-        if self._ema_decay is not None:
-            kw["ema"] = self._ema_operand()
-            if guarded and not grouped:       # (the other three forms take the step anyway)
-                kw["step"] = self.step_count
-        getattr(ops, name)(fp.flat, fp.grad, m, v, fp.n_train, *args, *((rec,) if guarded else ()), **kw)
-
-    def _reduce_gradients(self, fp) -> None:
-        """Between the backward and the unguarded optimizer launch: nothing here; Trainer finishes its ``dist`` all-reduces."""
-
-    def optimizer_step(self) -> None:
-        """The flat AdamW launch, issued behind the (recorded) program: ``step`` changes every step."""
-        self._ema_refuse("optimizer_step")
-        fp = self._fp if self._fp is not None else self.model.flat_params()
-        m, v = self._state(fp)
-        if self.guarded:                              # (never with dist: refused at construction)
-            return self._guarded_optimizer_step(fp, m, v)
-        self._reduce_gradients(fp)
-        self.step_count += 1
-        self._adamw_launch(fp, m, v)
-
-    # ---- checkpoint / resume (SURVEY.md §8f-4; absent upstream) ------------------------------------
-    def state_dict(self) -> dict:
-        """Optimizer state keyed by the reference's parameter names, in ``torch.optim.AdamW`` vocabulary
-        (``exp_avg`` / ``exp_avg_sq`` / ``step``); together with ``model.state_dict()`` (reference key
-        layout) this is a complete resume point.  Every live parameter has an entry, frozen ones included (their
-        moments are whatever they were when they were frozen: zero if they never trained), so a file loads into a trainer with
-        another frozen set, by name; with anything frozen, ``trainable`` lists the names that were training (no such key: all).
-
-        The trainer keeps ONE ``step`` for all parameters: a parameter unfrozen in the middle of a run starts from zero moments
-        under the run's bias correction, where ``torch.optim.AdamW`` would start a step count of its own for it.
-
-        With ``ema_decay``, and only then: ``ema`` (the averaged weights, by name) and ``ema_hyper`` (``decay``, ``warmup``, ``t0``)."""
-        self._ema_refuse("state_dict")
-        fp = self._fp if self._fp is not None else self.model.flat_params()
-        m, v = self._state(fp)
-        views = lambda buf: {n: buf[o:o + fp.P[n].numel()].view(fp.P[n].shape).detach().cpu().clone()
-                             for n, o in zip(fp.names, fp.offsets)}
-        # the dropout seed is stored WITHOUT the saving rank's offset (rank-independent base + steps taken): every rank of a
-        # resumed data-parallel job re-applies its own offset and goes on drawing the masks its uninterrupted self would have
-        seed = getattr(self.model, "_drop_seed", None)
-        sd = {"step": self._applied_steps(), "exp_avg": views(m), "exp_avg_sq": views(v),
-              "drop_seed_base": None if seed is None else (int(seed.item()) - rank_seed_offset()) % _SEED_MOD,
-              "hyper": {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "beta": self.beta}}
-        if fp.frozen:                      # (an all-trainable run writes the file it always wrote: no key = every name trains)
-            sd["trainable"] = fp.trainable_names()
-        if self._groups is not None:       # (a run without groups writes the file it always wrote)
-            sd["param_groups"] = [{"lr": grp["lr"], "weight_decay": grp["weight_decay"], "names": list(grp["names"])}
-                                  for grp in self._groups]
-        self._ema_save(sd, views)
-        return sd
-
-    def load_state_dict(self, sd: dict) -> None:
-        self._ema_refuse("load_state_dict")
-        fp = self._fp if self._fp is not None else self.model.flat_params()
-        m, v = self._state(fp)
-        missing = [n for n in fp.names if n not in sd["exp_avg"] or n not in sd["exp_avg_sq"]]
-        if missing:
-            raise KeyError(f"optimizer state lacks {missing[:3]}{'...' if len(missing) > 3 else ''}")
-        with torch.no_grad():
-            for n, o in zip(fp.names, fp.offsets):
-                k = fp.P[n].numel()
-                m[o:o + k].copy_(sd["exp_avg"][n].reshape(-1).to(m.device, m.dtype))
-                v[o:o + k].copy_(sd["exp_avg_sq"][n].reshape(-1).to(v.device, v.dtype))
-        self.step_count = int(sd["step"])
-        self._guard_reset()                # (the applied count starts here: nothing skipped since)
-        val = None
-        if sd.get("drop_seed_base") is not None:     # resume draws the masks THIS rank's uninterrupted run would have drawn
-            val = (int(sd["drop_seed_base"]) + rank_seed_offset()) % _SEED_MOD
-        elif sd.get("drop_seed") is not None:        # (files of round 3: the saving rank's own seed)
-            val = int(sd["drop_seed"])
-        if val is not None:
-            object.__setattr__(self.model, "_drop_seed", torch.tensor([val], dtype=torch.int64, device=m.device))
-        h = sd.get("hyper", {})
-        self.lr, self.eps, self.wd = h.get("lr", self.lr), h.get("eps", self.eps), h.get("weight_decay", self.wd)
-        self.betas, self.beta = tuple(h.get("betas", self.betas)), h.get("beta", self.beta)
-        saved = sd.get("param_groups")
-        if self._groups is not None and saved is not None and len(saved) == len(self._groups):
-            for grp, old in zip(self._groups, saved):      # by group index; another number of groups: the trainer keeps its own
-                grp["lr"], grp["weight_decay"] = float(old["lr"]), float(old["weight_decay"])
-        self._ema_load(sd, fp)
-
-    def check(self) -> None:
-        """Raise :class:`DosxError` if a column-split exchange of any step since the last clean check reported a stall
-        (``ops.check_exchanges``): one small read-back, so call it where the host waits for the device anyway - per evaluation,
-        before a checkpoint - not per step.  A module that is not on the GPU has launched nothing: nothing to check.
-
-        A guarded trainer (``max_grad_norm`` / ``skip_nonfinite``) also raises when steps were skipped since the last check,
-        naming the first one and the parameter whose gradient was not finite; by then ``step_count`` is the applied count, the
-        guard's counts are zeroed and the slots dropped, so the process can go on.
-
-        Also raises when the model's ``requires_grad`` flags no longer match the snapshot the flat buffer was laid out from
-        (``FusedModel.update_trainable()`` is the missing call)."""
-        if self.model.trainable_stale():
-            raise DosxError(f"{type(self.model).__name__}: requires_grad changed since the flat parameters were laid out, and the "
-                            f"steps since then trained the earlier set - call model.update_trainable() after changing the flags "
-                            f"(model.freeze() / model.train_only() do)")
-        dev = self.model._module_device()
-        if dev.type != "cuda":
-            return
-        skipped = self._guard_settle()
-        try:
-            ops.check_exchanges(dev)
-        except DosxError as e:
-            if skipped is None:
-                raise
-            raise DosxError(f"{e}  {skipped}") from None
-        if skipped is not None:
-            raise DosxError(skipped)
-
-    def _bump_dropout_seed(self) -> None:
-        """Attention dropout draws its masks from a device-resident seed inside the (possibly recorded) program; one bump
-        per step, issued here so that it is never part of a recording."""
-        seed = getattr(self.model, "_drop_seed", None)
-        if seed is not None and self.model.training and getattr(self.model, "_attn_drop", 0.0) > 0.0:
-            seed.add_(1)
-
-    # ---- the objective (ops.LOSS_KINDS; include/dosx.h: dosx_loss_rows / dosx_loss_rows_f64) ----------------------------------
-    loss = None                       # None: the reference driver's loss, the launches the step always issued; else a key of LOSS_KINDS
-    huber_delta = None
-    crystal_losses = None             # [B] device tensor, the last step's l_b (valid until the next step); None under the default
-
-    def _init_loss(self, who: str, loss, huber_delta, dist=None) -> None:
-        """``loss=`` / ``huber_delta=`` of a trainer's constructor.  Constructor arguments like ``beta``: not part of ``state_dict()``."""
-        self.loss = self.huber_delta = self.crystal_losses = None
-        names = ", ".join(repr(k) for k in ops.LOSS_KINDS)
-        if loss is not None and loss not in ops.LOSS_KINDS:
-            raise ValueError(f"{who}(loss={loss!r}): not one of {names} (or None: the reference's loss)")
-        if loss == "huber":
-            if huber_delta is None or not 0.0 < float(huber_delta) < float("inf"):
-                raise ValueError(f"{who}(loss='huber') needs a finite huber_delta > 0, got {huber_delta}")
-        elif huber_delta is not None:
-            raise ValueError(f"{who}(loss={loss!r}, huber_delta={huber_delta}): huber_delta belongs to loss='huber' alone "
-                             f"(loss is None or one of {names})")
-        if loss is not None and dist is not None:
-            raise DosxError(f"{who}(loss=...) is a single-GPU mode: not with dist (data parallelism)")
-        self.loss, self.huber_delta = loss, None if huber_delta is None else float(huber_delta)
-
-    def _loss_rows(self, alloc, dev, pg, ps, y, clamp: bool, dpg, dps, B_global: Optional[int] = None, weights=(None, None)):
-        """The one launch site of the per-crystal losses: -> (per-crystal l_b [B], loss 0-dim), both on static buffers when
-        the step is being recorded.  ``ps = dps = None``: a one-output model (``beta`` is not read then).  ``B_global``: the
-        count the mean is taken over - the batch's own outside an accumulation window, the window's total inside one.
-        ``weights``: what ``_batch_weights`` returned for the batch; with them or with ``bin_weights=`` the weighted entry."""
-        B = int(pg.shape[0])
-        if B_global is None:
-            B_global = B if self._window_total is None else self._window_total
-        per, loss = alloc(dev, B), alloc(dev, 1)
-        fn = ops.loss_rows if pg.dtype == torch.float32 else ops.loss_rows64
-        fn(pg, ps, y, self.loss, clamp_target=clamp, beta=self.beta, delta=self.huber_delta, dpg=dpg, dps=dps, per_crystal=per,
-           loss=loss, B_global=int(B_global), weights=weights[0], weight_index=weights[1],
-           bin_weights=self._bin_operand(dev, pg.dtype))
-        return per, loss[0]
-
-    # ---- sample weights and energy-bin weights (include/dosx.h: dosx_loss_rows_w / dosx_loss_rows_w_f64; DESIGN.md 9.10) --------
-    sample_weights = False            # True: every batch carries a [B] field `weight`, step_dataset reads the dataset's table
-    bin_weights = None                # None, or the [S] energy-bin weights as given (float64, on the host)
-    _bin_dev = None                   # ... on the device in the program's dtype, moved there once
-
-    def _init_weights(self, who: str, sample_weights, bin_weights, dist=None) -> None:
-        """``sample_weights=`` / ``bin_weights=`` of a trainer's constructor; call it after ``_init_loss``.  Constructor arguments
-        like ``beta`` and ``loss``: not part of ``state_dict()``."""
-        self.sample_weights, self.bin_weights, self._bin_dev = bool(sample_weights), None, None
-        if not self.sample_weights and bin_weights is None:
-            return
-        what = " and ".join(n for n, on in (("sample_weights=True", self.sample_weights), ("bin_weights=...", bin_weights is not None)) if on)
-        if dist is not None:
-            raise DosxError(f"{who}({what}) is a single-GPU mode: not with dist (data parallelism)")
-        if self.loss is None:
-            raise ValueError(f"{who}({what}) weighs the per-crystal losses: pass loss=\"crystal_rmse\" (on an eDOS model the default "
-                             f"objective, bit for bit) or another of {', '.join(repr(k) for k in ops.LOSS_KINDS)}")
-        if bin_weights is None:
-            return
-        v = bin_weights if torch.is_tensor(bin_weights) else torch.as_tensor(bin_weights, dtype=torch.float64)
-        v = v.detach().to("cpu", torch.float64).clone()
-        S = int(self.model._cfg.S)
-        if v.dim() != 1 or v.numel() != S:
-            raise ValueError(f"{who}(bin_weights=...): shape {tuple(v.shape)}, want [S] = [{S}], one weight per energy bin")
-        if not bool(torch.isfinite(v).all()) or bool((v < 0).any()):
-            raise ValueError(f"{who}(bin_weights=...): every bin weight must be finite and >= 0")
-        if not float(v.sum()) > 0.0:
-            raise ValueError(f"{who}(bin_weights=...): the bin weights sum to 0 - no bin would be left in the loss")
-        self.bin_weights = v
-
-    def _bin_operand(self, dev, dtype):
-        if self.bin_weights is None:
-            return None
-        if self._bin_dev is None or self._bin_dev.device != dev or self._bin_dev.dtype != dtype:
-            if self._bin_dev is not None:      # (the module moved: the recordings hold the old buffer's address)
-                self._slots = OrderedDict()
-            self._bin_dev = self.bin_weights.to(dev, dtype).contiguous()
-        return self._bin_dev
-
-    def _require_weight(self, what: str, g) -> None:
-        """``sample_weights=True``: the batch must carry ``weight`` - raised before anything is launched."""
-        if self.sample_weights and not (hasattr(g, "weight") and torch.is_tensor(g.weight) and g.weight.is_floating_point()
-                                        and g.weight.numel() == self._crystals_of(g)):
-            raise ValueError(f"{self._ema_who}.{what}: sample_weights=True, but the batch has no floating-point graph-level field "
-                             f"`weight` of [B] = [{self._crystals_of(g)}] entries (DeviceDataset crystals with a \"weight\", or "
-                             f"g.weight = ...)")
-
-    def _require_weight_table(self, what: str, ds, tables):
-        """``sample_weights=True``: the dataset's resident weight table in the program's dtype, or the refusal."""
-        if not self.sample_weights:
-            return None
-        w = tables.get("weight")
-        if w is None:
-            raise ValueError(f"{self._ema_who}.{what}: sample_weights=True, but the dataset holds no weights (crystals with a "
-                             f"\"weight\", or ds.set_weights(w))")
-        return w
-
-    def _batch_weights(self, g, cast):
-        """(w, w_index) of batch ``g`` for ``_loss_rows``: ``g.weight`` converted as the target is (``cast``; a slot's static
-        buffer comes back as it is), with ``g.weight_index`` where a dataset step left its table and the bucket's selection."""
-        if not self.sample_weights:
-            return (None, None)
-        wi = getattr(g, "weight_index", None)
-        if wi is None:
-            self._require_weight("step", g)
-        return (cast(g.weight).reshape(-1), wi)
-
-    def _whole_or_window(self, B: int, n_global) -> bool:
-        """True when ``n_global`` is the batch's own count - or, inside an accumulation window, the window's total (the internal
-        route by which a micro-batch is normalised by a count that is not its own; callers cannot reach it)."""
-        return int(n_global) == int(B) or (self._window_total is not None and int(n_global) == self._window_total)
-
-    def _require_whole_batch(self, B: int, n_global) -> None:
-        if self.loss is not None and not self._whole_or_window(B, n_global):
-            raise ValueError(f"{type(self).__name__}(loss={self.loss!r}): n_global={n_global} but the batch holds {B} crystals "
-                             f"(the per-crystal losses are a single-GPU mode)")
-
-    # ---- gradient accumulation: several batches, one optimizer step (include/dosx.h: dosx_grad_accumulate; DESIGN.md 9.9) -----
-    _acc = None                       # the window's accumulator, laid out like the moments; made at the first window with K > 1
-    _acc_loss = None                  # [1]: the window's loss, summed by the same launches
-    _window_total = None              # inside a window: T, the crystals of all its micro-batches; None outside
-
-    def _window_checks(self, what: str, K: int) -> None:
-        """What a window cannot run on and that its length alone decides - raised before the dropout seed, the accumulator or
-        any slot is touched."""
-        who = self._ema_who
-        self._ema_refuse(what)
-        if K == 0:
-            raise ValueError(f"{who}.{what}: an empty window - pass at least one batch")
-        if getattr(self, "dist", None) is not None:
-            raise DosxError(f"{who}.{what} is a single-GPU mode: not with dist (data parallelism)")
-        if K > 1 and self.loss is None and self.model._cfg.kind == "phonon":
-            raise DosxError(f"{who}.{what}: the reference's phonon loss is ONE RMSE pooled over the batch - its gradient needs "
-                            f"every micro-batch's squared error before any backward, so it does not accumulate over {K} batches; "
-                            f"build the trainer with loss=\"crystal_rmse\" (the reference's own objective at its batch size 1) or "
-                            f"another per-crystal loss")
-        if K > 1 and not self.model.trainable_names():
-            raise DosxError(f"{who}.{what}: every parameter is frozen - there is no gradient to accumulate")
-
-    @staticmethod
-    def _crystals_of(g) -> int:
-        """crystals in a batch object, without a host read (``system`` has one entry per crystal)"""
-        return int(g.num_graphs if hasattr(g, "num_graphs") else g.system.shape[0])
-
-    def _window_sizes(self, what: str, counts) -> list:
-        sizes = [int(c) for c in counts]
-        for k, B in enumerate(sizes):
-            if B < 1:
-                raise ValueError(f"{self._ema_who}.{what}: batch {k} of the window is empty")
-        return sizes
-
-    def _window(self, what: str, sizes, run) -> torch.Tensor:
-        """One optimizer step on the micro-batches ``k < len(sizes)`` (``sizes[k]`` crystals each, at least two of them):
-        ``run(k)`` issues micro-batch k's ordinary program - normalised by the window's total, which ``_window_total`` carries -
-        and returns its loss; behind each program ONE ``dosx_grad_accumulate`` launch on the main stream, outside the recording,
-        where the optimizer launch goes: copy into the accumulator (k = 0: nothing stale is ever read), accumulator += gradient,
-        and for the last one gradient = accumulator + gradient - the flat gradient buffer then holds ((G1 + G2) + G3) + ..., and
-        the guard, AdamW, ``.grad`` and ``guard_report()`` work on it unchanged.  The same launches sum the losses.  Nothing of the
-        optimizer's is touched before the last launch: an exception in between leaves parameters, moments, average and
-        ``step_count`` alone, and the next window starts with a copy."""
-        K, T = len(sizes), sum(sizes)
-        accumulate = None
-        crystals, off, fp0 = None, 0, None
-        self._window_total = T
-        try:
-            for k in range(K):
-                loss = run(k)
-                fp = self._fp
-                if k == 0:
-                    fp0 = fp
-                    if self._acc is None:
-                        self._acc, self._acc_loss = torch.empty_like(fp.flat), torch.empty(1, dtype=fp.flat.dtype, device=fp.flat.device)
-                    accumulate = ops.grad_accumulate if fp.flat.dtype == torch.float32 else ops.grad_accumulate64
-                    accumulate(self._acc, fp.grad, None, fp.n_train, sdst=self._acc_loss, sa=loss)
-                elif fp is not fp0:
-                    raise DosxError(f"{self._ema_who}.{what}: the flat parameters were laid out anew inside a window (batch {k})")
-                else:
-                    accumulate(self._acc if k < K - 1 else fp.grad, self._acc, fp.grad, fp.n_train, sdst=self._acc_loss,
-                               sa=self._acc_loss, sb=loss)
-                if self.crystal_losses is not None:          # (a slot's [B] buffer is overwritten when the slot runs again)
-                    if crystals is None:
-                        crystals = torch.empty(T, dtype=self.crystal_losses.dtype, device=self.crystal_losses.device)
-                    crystals[off:off + sizes[k]].copy_(self.crystal_losses)
-                off += sizes[k]
-        finally:
-            self._window_total = None
-        self.crystal_losses = crystals
-        self.optimizer_step()
-        return self._acc_loss[0]
-
-
-class _Width:
-    """Stands in for a batch where only the node-feature width matters (FusedModel._extra_dead reads ``g.x.shape[1]``)."""
-
-    def __init__(self, width: int):
-        self.x = torch.empty(0, int(width))
-
-
-class Trainer(_AdamWState, SlotCache):
+class Trainer(TrainerBase):
     """AdamW(lr, weight_decay=1e-2) training of a DOSTransformer(_phonon) module, all on libdosx.
 
     ``dist``: optional :class:`dostransformer_amd.dist.DataParallel` — shards are per-rank batches,
@@ -509,6 +117,10 @@ class Trainer(_AdamWState, SlotCache):
     and the average; constructor arguments like ``loss``: not in ``state_dict()``; not under data parallelism.
     """
 
+    _who = "Trainer"
+    _dtype = torch.float32
+    _tiled = True
+
     def __init__(self, model: DOSTransformerBase, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2,
                  betas=(0.9, 0.999), eps: float = 1e-8, dist=None, graph: bool = False, replay: bool = False,
                  bucket=(8, 128), max_slots: int = 32, promote: float = 0.0, per_crystal_keys: bool = False,
@@ -519,9 +131,9 @@ class Trainer(_AdamWState, SlotCache):
             raise TypeError("Trainer drives DOSTransformer / DOSTransformer_phonon / Graphnetwork / Graphnetwork_phonon / mlp modules")
         model._require_fp32_program("Trainer")
         self._baseline = isinstance(model, GraphnetworkBase)
-        self._dead = None                 # baselines: the dead-parameter set of the first batch's input width
         if self._baseline:
             name = type(model).__name__
+            self._first_width_fixes_dead = True
             if float(beta) != 1.0:
                 raise ValueError(f"Trainer({name}): beta={beta} - the model has ONE output and its loss no second term to weigh; "
                                  f"only the default 1.0 is accepted")
@@ -536,13 +148,13 @@ class Trainer(_AdamWState, SlotCache):
             raise DosxError("Trainer(dist=...) with frozen parameters: fine-tuning is a single-GPU mode, not with dist (data "
                             "parallelism)")
         self._per_crystal_keys = bool(per_crystal_keys)
-        self._init_guard("Trainer", max_grad_norm, skip_nonfinite, dist)
-        self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, betas, eps
-        self._init_param_groups("Trainer", param_groups, dist)
-        self._init_ema("Trainer", ema_decay, ema_warmup, dist)
-        self._init_loss("Trainer", loss, huber_delta, dist)
-        self._init_weights("Trainer", sample_weights, bin_weights, dist)
         self.dist = dist
+        self._init_guard(max_grad_norm, skip_nonfinite)
+        self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, betas, eps
+        self._init_param_groups(param_groups)
+        self._init_ema(ema_decay, ema_warmup)
+        self._init_loss(loss, huber_delta)
+        self._init_weights(sample_weights, bin_weights)
         self.graph = graph
         self.replay = replay
         # (node, edge) granularity of the shape buckets unpadded batches are ghost-padded to in graph / replay mode: a
@@ -583,8 +195,7 @@ class Trainer(_AdamWState, SlotCache):
             st_n_global = m.num_graphs
         model, dev, cfg = self.model, fp.flat.device, self.model._cfg
         B, S = m.num_graphs, cfg.S
-        self._require_whole_batch(B, st_n_global)
-        w = self._batch_weights(g, Fn._f32)          # (refuses a batch without `weight` before anything is launched)
+        w = self._batch_weights(g)                   # (refuses a batch without `weight` before anything is launched)
         if self._baseline:
             out = model._program_fwd(fp.P, g, m, factored_head=True)
             y = Fn._f32(g.phdos).reshape(B, S) if self.kind == "phonon" else Fn._f32(g.y_ft).reshape(-1)
@@ -594,7 +205,7 @@ class Trainer(_AdamWState, SlotCache):
         st = {"ctx": ctx, "dos": dos, "out": (dg, xL, ds), "B": B, "S": S, "w": w}
         if self.kind == "phonon":
             st["y"] = Fn._f32(g.phdos).reshape(B, S)
-            if self.loss is not None:      # a per-crystal loss: one entry in _part_b, no SSE pair
+            if self.loss is not None:      # a per-crystal loss: one entry in _loss_launch, no SSE pair
                 st["split_loss"] = False
                 return st
             st["sse"] = Fn._empty(dev, 2)
@@ -605,88 +216,56 @@ class Trainer(_AdamWState, SlotCache):
             st["y"] = Fn._f32(g.y_ft).reshape(-1)
         return st
 
+    def _loss_launch(self, dev, st, pg, ps, beta: float, n_global: int):
+        """The loss of the step with its gradient, for both output counts: -> (ddos, loss).  Two outputs: ``pg``, ``ps`` are
+        the halves of ``dos`` and ``ddos`` is laid out like it.  One output (the GNN-only baselines): ``ps is pg`` and
+        ``beta = 0`` - the drivers' loss entries in their one-output use (include/dosx.h: the loss is rmse(pg) exactly, the
+        second gradient goes to scratch); with ``loss=...`` the per-crystal entry in its own one-output form (ps == NULL: no
+        second gradient, no scratch)."""
+        B, S, y = st["B"], st["S"], st["y"]
+        one = ps is pg
+        ddos = Fn._empty(dev, B if one else 2 * B, S)
+        dpg = ddos if one else ddos[:B]
+        if self.loss is not None:          # eDOS clamps its target at 0 (main_eDOS.py:113), phonon does not; n_global == B
+            st["crystal"], loss = self._loss_rows(Fn._empty, dev, pg, None if one else ps, y, self.kind != "phonon", dpg,
+                                                  None if one else ddos[B:],
+                                                  B_global=n_global,         # ... or, inside a window, the window's total
+                                                  weights=st["w"])
+            return ddos, loss
+        dps = Fn._empty(dev, B, S) if one else ddos[B:]
+        if self.kind == "phonon":
+            loss = Fn._empty(dev, 1)
+            split = st.get("split_loss", False)
+            if split or int(n_global) != B:
+                if not split:
+                    raise RuntimeError("n_global differs between the two halves of the step")
+                ops.loss_phonon_bwd(pg, ps, y, st["sse"], beta, float(n_global * S), dpg, dps, loss, B * S)
+            else:                          # one launch: SSE pair, loss and gradient (normalised by B*S: n_global == B)
+                ops.loss_phonon(pg, ps, y, st.get("sse"), beta, dpg, dps, loss, B * S)
+            return ddos, loss[0]
+        lp = Fn._empty(dev, B + 1)
+        ops.loss_edos(pg, ps, y, beta, B, S, int(n_global), dpg, dps, lp)     # (B, the global count, or a window's total)
+        ops.sum_to(lp, B, lp[B:])
+        return ddos, lp[B]
+
     def _part_b(self, fp, m, st, n_global: int):
         """loss gradient + backward program.  n_global: crystals in the un-sharded batch."""
         dev, cfg = fp.flat.device, self.model._cfg
-        B, S, dos = st["B"], st["S"], st["dos"]
-        if self._baseline:
-            return self._part_b_baseline(fp, m, st, n_global)
-        ddos = Fn._empty(dev, *dos.shape)
-        if self.loss is not None:          # eDOS clamps its target at 0 (main_eDOS.py:113), phonon does not; n_global == B (_part_a)
-            st["crystal"], loss = self._loss_rows(Fn._empty, dev, dos[:B], dos[B:], st["y"], self.kind != "phonon", ddos[:B], ddos[B:],
-                                                  B_global=n_global,         # ... or, inside a window, the window's total
-                                                  weights=st["w"])
-        elif self.kind == "phonon":
-            loss = Fn._empty(dev, 1)
-            if st["split_loss"] or int(n_global) != B:
-                if not st["split_loss"]:
-                    raise RuntimeError("n_global differs between the two halves of the step")
-                ops.loss_phonon_bwd(dos[:B], dos[B:], st["y"], st["sse"], self.beta, float(n_global * S), ddos[:B],
-                                    ddos[B:], loss, B * S)
-            else:                          # one launch: SSE pair, loss and gradient (normalised by B*S: n_global == B)
-                ops.loss_phonon(dos[:B], dos[B:], st["y"], st["sse"], self.beta, ddos[:B], ddos[B:], loss, B * S)
-            loss = loss[0]
-        else:
-            lp = Fn._empty(dev, B + 1)
-            ops.loss_edos(dos[:B], dos[B:], st["y"], self.beta, B, S, n_global, ddos[:B], ddos[B:], lp)
-            ops.sum_to(lp, B, lp[B:])
-            loss = lp[B]
-        sink = ops.GradSink(dev)
-        sink.gnn_hook = self._gnn_hook(fp)          # (functional.gnn_bwd calls it behind the flush that completes layers L-1 .. 1)
-        Fn.dostransformer_bwd(fp.P, fp.G, cfg, m, st["ctx"], ddos, None, sink, mid_hook=self._mid_hook(fp))
-        self._wgrad_keys = sink.wgrad_keys
-        sink.release()
-        return loss
-
-    def _part_b_baseline(self, fp, m, st, n_global: int):
-        """One-output loss + backward program of a GNN-only baseline.  The loss entries in their one-output use (include/dosx.h:
-        ps = pg, beta = 0: the loss is rmse(pg) exactly, the second gradient goes to scratch); with ``loss=...`` the per-crystal
-        entry in its own one-output form (ps == NULL)."""
-        dev = fp.flat.device
-        B, S, dos = st["B"], st["S"], st["dos"]
-        if not self._whole_or_window(B, n_global):
-            raise ValueError(f"Trainer({type(self.model).__name__}): n_global={n_global} but the batch holds {B} crystals "
+        B, dos = st["B"], st["dos"]
+        if self._baseline and not self._whole_or_window(B, n_global):
+            raise ValueError(f"{self._who_with_model()}: n_global={n_global} but the batch holds {B} crystals "
                              f"(no data parallelism for the GNN-only baselines)")
-        if self.loss is not None:          # the one-output form of the entry: no second gradient, no scratch
-            ddos = Fn._empty(dev, B, S)
-            st["crystal"], loss = self._loss_rows(Fn._empty, dev, dos, None, st["y"], self.kind != "phonon", ddos, None,
-                                                  B_global=n_global, weights=st["w"])
-            return self._bwd_baseline(fp, m, st, ddos, loss)
-        ddos, scr = Fn._empty(dev, B, S), Fn._empty(dev, B, S)
-        if self.kind == "phonon":
-            loss = Fn._empty(dev, 1)
-            ops.loss_phonon(dos, dos, st["y"], None, 0.0, ddos, scr, loss, B * S)
-            loss = loss[0]
+        pg, ps, beta = (dos, dos, 0.0) if self._baseline else (dos[:B], dos[B:], self.beta)
+        ddos, loss = self._loss_launch(dev, st, pg, ps, beta, n_global)
+        sink = ops.GradSink(dev)
+        if self._baseline:
+            self.model._bwd_fn(fp.P, fp.G, cfg, m, st["ctx"], ddos, None, sink, factored_head=True)
         else:
-            lp = Fn._empty(dev, B + 1)
-            ops.loss_edos(dos, dos, st["y"], 0.0, B, S, int(n_global), ddos, scr, lp)     # (B, or a window's total)
-            ops.sum_to(lp, B, lp[B:])
-            loss = lp[B]
-        return self._bwd_baseline(fp, m, st, ddos, loss)
-
-    def _bwd_baseline(self, fp, m, st, ddos, loss):
-        sink = ops.GradSink(fp.flat.device)
-        self.model._bwd_fn(fp.P, fp.G, self.model._cfg, m, st["ctx"], ddos, None, sink, factored_head=True)
+            sink.gnn_hook = self._gnn_hook(fp)      # (functional.gnn_bwd calls it behind the flush that completes layers L-1 .. 1)
+            Fn.dostransformer_bwd(fp.P, fp.G, cfg, m, st["ctx"], ddos, None, sink, mid_hook=self._mid_hook(fp))
         self._wgrad_keys = sink.wgrad_keys
         sink.release()
         return loss
-
-    def _flat_for(self, dev, g, width: Optional[int] = None):
-        """The model's flat parameters for a batch (or, step_dataset, an input width).  Baselines: which node encoder is dead
-        follows the width; the first batch fixes it for this trainer."""
-        model = self.model
-        if not self._baseline:
-            return model._ensure_flat(dev, g)
-        if g is None:
-            g = _Width(width)
-        dead = model._extra_dead(g)
-        if self._dead is None:
-            self._dead = dead
-        elif dead != self._dead:
-            raise DosxError(f"Trainer({type(model).__name__}): this batch has node features of width {g.x.shape[1]}, which selects "
-                            f"the other node encoder than the trainer's first batch did - its dead-parameter set (and the "
-                            f"optimizer's layout) is fixed by the first batch")
-        return model._ensure_flat(dev, g)
 
     # ---- data parallel: early gradient bucket ------------------------------------------------------
     def _mid_hook(self, fp):
@@ -738,30 +317,80 @@ class Trainer(_AdamWState, SlotCache):
         with torch.cuda.stream(stream):
             self._mid_work = self.dist.all_reduce_grads_async(fp.grad[fp.n_last:fp.n_late])
 
-    def _n_global(self, B: int, n_global: Optional[int], g=None) -> int:
-        """Crystals in the un-sharded batch: the caller's value, else what the sharder recorded on the batch
-        (``dist.shard_batch``), else — last resort, a blocking collective + host read — the sum over ranks."""
+    def _n_global(self, B: int, n_global: Optional[int], g=None, ds=None) -> int:
+        """Crystals in the un-sharded batch: the caller's value, else - inside an accumulation window - the window's total, else
+        what the sharder recorded on the batch (``dist.shard_batch``), else — a batch object's last resort, a blocking
+        collective + host read — the sum over ranks.  A dataset step (``ds``) has neither collective nor host read:
+
+        without an explicit n_global the ranks of a data-parallel job must draw EQUALLY sized shards every step, then
+        n_global = B * world.  That holds for every batch of an epoch, the last one included, iff all ranks hold equally many
+        crystals and cut them with the same batch size - checked ONCE per dataset (one blocking min/max over ranks at its first
+        step); ragged shards must pass the true n_global, or the loss would be normalised by the wrong count
+        (`main_phDOS.py:109-114` is ONE rmse over the un-sharded batch).  DOSX_DP_CHECK=1 cross-checks B itself across the
+        ranks on every step (debugging; blocking)."""
         if n_global is not None:
             return int(n_global)
-        ng = getattr(g, "n_global", None) if g is not None else None
+        if self._window_total is not None:
+            return self._window_total
+        ng = getattr(g, "n_global", None)
         if ng is not None:
             return int(ng)
-        return self.dist.global_count(B) if self.dist is not None else B
+        if self.dist is None:
+            return B
+        if ds is None:
+            return self.dist.global_count(B)
+        if not any(d is ds for d in self._ds_checked):
+            lo, hi = self.dist.min_max(len(ds))
+            if lo != hi:
+                raise ValueError(f"data-parallel ranks hold {lo}..{hi} crystals: with ragged shards the last batches of "
+                                 f"an epoch differ in size across ranks - pass the global batch size as n_global")
+            self._ds_checked.append(ds)
+        if _DP_CHECK:
+            lo, hi = self.dist.min_max(B)
+            if lo != hi:
+                raise ValueError(f"ranks stepped on {lo}..{hi} crystals without an explicit n_global")
+        return B * self.dist.world
+
+    # ---- what the shared driver (trainer_base.TrainerBase) asks -----------------------------------
+    def _slotted(self, dataset: bool) -> bool:
+        return bool(self.graph or self.replay)
+
+    def _who_with_model(self) -> str:
+        return f"Trainer({type(self.model).__name__})"
+
+    def _prepare(self, g, ds, B: int, n_global: Optional[int]):
+        """-> (flat parameters, n_global resolved): see ``_n_global``."""
+        model = self.model
+        model._require_fp32_program("Trainer")
+        fp = self._flat_for(model._module_device(), g, None if ds is None else int(ds._f32_tables()["x"].shape[1]))
+        self._state(fp)
+        ng = self._n_global(B, n_global, g, ds)
+        self._require_whole_batch(B, ng)              # (before a slot is made, not inside its recording)
+        return fp, ng
+
+    def _extra(self, fp, ng: int) -> int:
+        return ng                     # (the fp32 program makes its dropout seed itself, inside the step)
+
+    def _key(self, n: int, e: int, B: int, n_max: int, ng: int, tiled: bool) -> tuple:
+        return (n, e, B, n_max, ng, tiled)
+
+    def _slot_meta(self, g, dev):
+        m = g.meta
+        if m is None or m.edge_perm is not None:
+            raise ValueError("graph mode needs batches from collate(sort_edges=True) (+ pad_batch)")
+        return m
 
     # ---- eager path ------------------------------------------------------------------------------
     def forward_backward(self, g, n_global: Optional[int] = None, _bump: bool = True) -> torch.Tensor:
         """Forward + loss + backward; leaves the gradients in the flat buffer.  Returns the loss
         (0-dim device tensor; for eDOS under data parallelism it is this rank's share)."""
         self._ema_refuse("forward_backward")
-        if _bump:                      # a direct forward_backward() + optimizer_step() loop draws fresh dropout masks too
-            self._bump_dropout_seed()
-        model = self.model
-        dev = model._module_device()
-        model._require_fp32_program("Trainer")
-        fp = self._flat_for(dev, g)
-        self._state(fp)
-        m = graph_meta(g, dev)
-        ng = self._n_global(m.num_graphs, n_global, g)
+        # (_bump: a direct forward_backward() + optimizer_step() loop draws fresh dropout masks too)
+        fp, ng = self._context(g, None, self._crystals_of(g), n_global, _bump)
+        return self._eager(fp, g, ng)
+
+    def _eager(self, fp, g, ng: int) -> torch.Tensor:
+        m = graph_meta(g, fp.flat.device)
         with torch.no_grad(), ops.call_log() as names:
             st = self._part_a(fp, g, m, ng)
             self.last_outputs = st["out"]
@@ -857,100 +486,6 @@ class Trainer(_AdamWState, SlotCache):
         self.last_outputs, self.crystal_losses = slot.out, slot.crystal
         return slot.loss
 
-    def _graph_step(self, g: CrystalBatch, n_global: Optional[int]) -> torch.Tensor:
-        model = self.model
-        dev = model._module_device()
-        model._require_fp32_program("Trainer")
-        fp = self._flat_for(dev, g)
-        self._state(fp)
-        m = g.meta
-        if m is None or m.edge_perm is not None:
-            raise ValueError("graph mode needs batches from collate(sort_edges=True) (+ pad_batch)")
-        if getattr(g, "real_nodes", None) is None:               # not padded yet: pad on the fly
-            g = pad_batch(g, *bucket_sizes(m.num_nodes, m.num_edges, *self.bucket))
-            m = g.meta
-        ng = self._n_global(m.num_graphs, n_global, g)
-        self._require_whole_batch(m.num_graphs, ng)              # (before a slot is made, not inside its recording)
-        self._require_weight("step", g)
-        key = (m.num_nodes, m.num_edges, m.num_graphs, m.n_max, ng, m.seg_tile is not None)
-        if self.sample_weights:               # (the last field of a dataset step's key is its table: this batch brings its own)
-            key += (None,)
-        slot = self._lookup(key)
-        fresh = slot is None
-        if fresh:                             # (graph mode captures on the slot's own copy of this batch)
-            slot = Slot(g, m, self.kind, torch.float32, weights=self.sample_weights)
-        else:
-            slot.load(g)
-        loss = self._run_slot(slot, fp, ng, fresh)
-        if fresh:                             # (registered once recorded: a failed first step leaves no empty recording behind)
-            self._slots[key] = slot
-        return loss
-
-    def step_dataset(self, ds, indices, n_global: Optional[int] = None, n_max: Optional[int] = None) -> torch.Tensor:
-        """One training step on the crystals ``indices`` of a device-resident ``loader.DeviceDataset``: the batch is
-        collated by ``dosx_collate_padded`` STRAIGHT INTO the static buffers of its shape bucket (ghost padding
-        included) and the bucket's recorded program is replayed — no intermediate batch object, no padding ops, no
-        slot copy.  Same numbers as ``step(ds.collate(indices))`` (the counterpart of the loop body `main_phDOS.py:104-118`
-        with a shuffling DataLoader)."""
-        self._ema_refuse("step_dataset")
-        if not (self.replay or self.graph):
-            return self.step(ds.collate(indices, n_max=n_max), n_global)
-        loss = self._dataset_program(ds, indices, n_global, n_max)
-        self.optimizer_step()
-        return loss
-
-    def _dataset_program(self, ds, indices, n_global: Optional[int], n_max: Optional[int]) -> torch.Tensor:
-        """``step_dataset`` (replay / graph mode) up to the optimizer: collate into the bucket, bump the seed, run the slot."""
-        model = self.model
-        dev = model._module_device()
-        model._require_fp32_program("Trainer")
-        table = self._require_weight_table("step_dataset", ds, ds._f32_tables())
-        fp = self._flat_for(dev, None, int(ds._f32_tables()["x"].shape[1]))
-        self._state(fp)
-        idx, N, E, n_max = ds.bucket_dims(indices, n_max)
-        B = int(idx.shape[0])
-        n_pad, e_pad = bucket_sizes(N, E, *self.bucket)
-        # No per-step collective and no host read: without an explicit n_global the ranks of a data-parallel job must draw
-        # EQUALLY sized shards every step, then n_global = B * world.  That holds for every batch of an epoch, the last one
-        # included, iff all ranks hold equally many crystals and cut them with the same batch size - checked ONCE per
-        # dataset (one blocking min/max over ranks at its first step); ragged shards must pass the true n_global, or the
-        # loss would be normalised by the wrong count (`main_phDOS.py:109-114` is ONE rmse over the un-sharded batch).
-        # DOSX_DP_CHECK=1 cross-checks B itself across the ranks on every step (debugging; blocking).
-        if n_global is not None:
-            ng = int(n_global)
-        elif self.dist is None:
-            ng = B
-        else:
-            if not any(d is ds for d in self._ds_checked):
-                lo, hi = self.dist.min_max(len(ds))
-                if lo != hi:
-                    raise ValueError(f"data-parallel ranks hold {lo}..{hi} crystals: with ragged shards the last batches of "
-                                     f"an epoch differ in size across ranks - pass the global batch size as n_global")
-                self._ds_checked.append(ds)
-            if _DP_CHECK:
-                lo, hi = self.dist.min_max(B)
-                if lo != hi:
-                    raise ValueError(f"ranks stepped on {lo}..{hi} crystals without an explicit n_global")
-            ng = B * self.dist.world
-        self._require_whole_batch(B, ng)
-        tiled = True
-        key = (n_pad, e_pad, B, n_max, ng, tiled)
-        if table is not None:                 # another dataset's table: slots of its own, never a stale pointer
-            key += (table.data_ptr(),)
-        slot = self._lookup(key, allow_promote=True)
-        fresh = slot is None
-        if fresh:
-            t = ds._f32_tables()
-            slot = Slot.empty(self.kind, dev, torch.float32, B, n_pad, e_pad, n_max, int(t["x"].shape[1]),
-                              int(t["edge"].shape[1]), int(t["target"].shape[1]), tiled=tiled, weight_table=table)
-        ds.collate_into(slot.g, idx, slot.collate_scratch())
-        slot._loaded = None                                        # (the static buffers now hold a batch no object stands for)
-        self._bump_dropout_seed()
-        loss = self._run_slot(slot, fp, ng, fresh)
-        if fresh:
-            self._slots[key] = slot
-        return loss
-
     # ---- what the step launched ------------------------------------------------------------------
     def _make_stats(self, entries) -> dict:
         entries = list(entries)
@@ -984,56 +519,3 @@ class Trainer(_AdamWState, SlotCache):
             else:
                 assert self._mid_work is None
                 self.dist.all_reduce_grads(fp.grad)
-
-    def step(self, g, n_global: Optional[int] = None) -> torch.Tensor:
-        self._ema_refuse("step")
-        self._require_weight("step", g)
-        self._bump_dropout_seed()
-        loss = self._graph_step(g, n_global) if (self.graph or self.replay) else self.forward_backward(g, n_global, _bump=False)
-        self.optimizer_step()
-        return loss
-
-    # ---- gradient accumulation ---------------------------------------------------------------------
-    def step_accumulate(self, batches) -> torch.Tensor:
-        """ONE optimizer step on the objective of the concatenated batch, computed micro-batch by micro-batch: what a torch loop
-        gets from ``backward()`` on several batches before one ``optimizer.step()`` - with every loss normalised by the window's
-        crystal count ``T = sum B_k``, not by its own, so that ragged batches still give the mean over crystals.  Each batch
-        runs its ordinary program (eager, ``replay`` or ``graph``; the slots an epoch recorded are reused, keyed with ``T``) and
-        one ``dosx_grad_accumulate`` launch behind it sums the flat gradients in the fixed order ``((G1 + G2) + G3) + ...``;
-        then one guard verdict (on the SUM: a non-finite value in any micro-batch skips the whole window), one AdamW launch, one
-        update of the weight average, ``step_count + 1``.  Returns the window's loss, a 0-dim device tensor (a trainer-owned
-        scalar, valid until the next window); ``crystal_losses`` is the ``[T]`` concatenation in micro-batch order,
-        ``last_outputs`` / ``program_stats()`` describe the last micro-batch, the dropout seed advances once per micro-batch.
-        One batch is ``step()`` bit for bit.  Every objective that is a sum over crystals divided by a count: the eDOS default loss
-        and every ``loss=``; the reference's pooled phonon RMSE is refused for more than one batch (``loss="crystal_rmse"`` is
-        the reference's own batch-1 objective).  Not under data parallelism, not inside ``ema_weights()``.  Whatever can be known
-        before a launch raises before anything has changed; an exception in the middle of a window leaves parameters, moments,
-        average and ``step_count`` untouched."""
-        batches = list(batches)
-        self._window_checks("step_accumulate", len(batches))
-        sizes = self._window_sizes("step_accumulate", (self._crystals_of(g) for g in batches))
-        for g in batches:
-            self._require_weight("step_accumulate", g)
-        if len(batches) == 1:
-            return self.step(batches[0])
-        T = sum(sizes)
-
-        def run(k):
-            self._bump_dropout_seed()
-            if self.graph or self.replay:
-                return self._graph_step(batches[k], T)
-            return self.forward_backward(batches[k], T, _bump=False)
-        return self._window("step_accumulate", sizes, run)
-
-    def step_dataset_accumulate(self, ds, index_lists, n_max: Optional[int] = None) -> torch.Tensor:
-        """``step_accumulate`` on selections of a device-resident ``loader.DeviceDataset``: each ``indices`` of ``index_lists`` is
-        collated straight into its bucket as ``step_dataset`` does; bitwise ``step_accumulate([ds.collate(i) ...])``."""
-        index_lists = list(index_lists)
-        self._window_checks("step_dataset_accumulate", len(index_lists))
-        sizes = self._window_sizes("step_dataset_accumulate", (len(i) for i in index_lists))
-        if len(index_lists) == 1:
-            return self.step_dataset(ds, index_lists[0], n_max=n_max)
-        if not (self.replay or self.graph):
-            return self.step_accumulate([ds.collate(i, n_max=n_max) for i in index_lists])
-        T = sum(sizes)
-        return self._window("step_dataset_accumulate", sizes, lambda k: self._dataset_program(ds, index_lists[k], T, n_max))

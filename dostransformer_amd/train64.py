@@ -32,12 +32,12 @@ from . import functional64 as F64
 from . import ops
 from ._lib import DosxError
 from ._models import DOSTransformerBase, GraphnetworkBase
-from .batch import GraphMeta, bucket_sizes, graph_meta, pad_batch
-from .slots import Slot, SlotCache
-from .train import _AdamWState, _Width
+from .batch import GraphMeta, graph_meta
+from .slots import Slot
+from .trainer_base import TrainerBase
 
 
-class Trainer64(_AdamWState, SlotCache):
+class Trainer64(TrainerBase):
     """AdamW(lr, weight_decay=1e-2) training of a ``DOSTransformer_phonon`` set to the float64 program
     (``model.double().set_program_dtype(torch.float64)``), all on libdosx: what ``model(batch)`` -> torch loss ->
     ``loss.backward()`` -> ``torch.optim.AdamW`` computes, without autograd and the per-tensor optimizer.
@@ -67,9 +67,14 @@ class Trainer64(_AdamWState, SlotCache):
     dataset's resident table gathered by the loss launch) and ``[S]`` energy-bin weights in the per-crystal loss
     (``dosx_loss_rows_w_f64``), as on ``train.Trainer``; they need ``loss=``.  With sample weights a slot's key ends in the table's
     address (``None`` for a batch-object slot).
+    ``step(g, n_global=None)`` / ``step_dataset(ds, indices, n_global=None, n_max=None)`` are the drivers' shared methods
+    (``trainer_base.TrainerBase``) and carry ``train.Trainer``'s ``n_global``: this driver is single-GPU and refuses any value
+    but the batch's own count - pass ``n_max`` by keyword.
     """
 
-    _who = "Trainer64"            # what this driver calls itself in its refusals
+    _who = "Trainer64"
+    _dtype = torch.float64
+    dist = None                   # single GPU
 
     def __init__(self, model, lr: float = 1e-4, beta: float = 1.0, weight_decay: float = 1e-2, betas=(0.9, 0.999),
                  eps: float = 1e-8, replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
@@ -77,12 +82,12 @@ class Trainer64(_AdamWState, SlotCache):
                  ema_decay: Optional[float] = None, ema_warmup: bool = True, loss: Optional[str] = None,
                  huber_delta: Optional[float] = None, sample_weights: bool = False, bin_weights=None):
         self._require_model(model)
-        self._init_guard(self._who, max_grad_norm, skip_nonfinite)
+        self._init_guard(max_grad_norm, skip_nonfinite)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, tuple(betas), eps
-        self._init_param_groups(self._who, param_groups)
-        self._init_ema(self._who, ema_decay, ema_warmup)
-        self._init_loss(self._who, loss, huber_delta)
-        self._init_weights(self._who, sample_weights, bin_weights)
+        self._init_param_groups(param_groups)
+        self._init_ema(ema_decay, ema_warmup)
+        self._init_loss(loss, huber_delta)
+        self._init_weights(sample_weights, bin_weights)
         self._crystal = None              # the per-crystal losses of the program just issued (loss=...), else None
         self.replay = bool(replay)
         self.max_slots = int(max_slots)
@@ -101,43 +106,75 @@ class Trainer64(_AdamWState, SlotCache):
         self.slot_hits = self.slot_misses = self.slot_promoted = 0
         self._seen = {}
 
-    # ---- the step ------------------------------------------------------------------------------------------------------
+    # ---- what the shared driver (trainer_base.TrainerBase) asks ----------------------------------------------------------------
     def _require_model(self, model) -> None:
         """The one model check of this driver - at construction and again in front of every step: a DOSTransformer_phonon set
         to the float64 program.  A subclass that drives another module overrides it."""
         DOSTransformerBase._require_f64_program(model, self._who)
 
-    def _refuse(self, g) -> None:
-        """What a step cannot run on - raised before anything (the dropout seed included) has changed."""
+    def _refuse(self, what: str, g) -> None:
         self._require_model(self.model)
-        self._require_weight("step", g)
+        super()._refuse(what, g)
         if self.bucket is None and getattr(g, "real_nodes", None) is not None:
             raise DosxError(f"{self._who}: ghost-padded batches (batch.pad_batch) are refused without bucket=(node_step, "
                             "edge_step) - slots are keyed by the exact shape of an unpadded batch")
 
-    def _prepare(self, g, ds=None):
-        """-> (flat parameters, dropout operand); everything that may touch the host or torch's RNG (first use: flattening, the
-        dropout seed) happens here, in front of any recording.  ``g`` is None for a dataset step, which passes ``ds``."""
-        model = self.model
-        dev = model._module_device()
-        fp = model._ensure_flat(dev, g)
+    def _slotted(self, dataset: bool) -> bool:
+        return bool(self.replay and (self.bucket is not None or not dataset))
+
+    def _prepare(self, g, ds, B: int, n_global: Optional[int]):
+        """-> (flat parameters, the batch's own count).  Single GPU: any other ``n_global`` is refused."""
+        if n_global is not None and not self._whole_or_window(B, n_global):
+            raise ValueError(f"{self._who}: n_global={n_global} but the batch holds {B} crystals (a single-GPU driver: no data "
+                             f"parallelism)")
+        dev = self.model._module_device()
+        fp = self._flat_for(dev, g, None if ds is None else int(ds._f64_tables()["x"].shape[1]))
         self._state(fp)
-        return fp, model._dropout(dev, False)
+        return fp, B
+
+    def _extra(self, fp, count: int):
+        """The dropout operand: None in eval mode / p = 0, else (p, seed) - the first use makes the seed."""
+        return self.model._dropout(fp.flat.device, False)
+
+    def _key(self, n: int, e: int, B: int, n_max: int, drop, tiled: bool) -> tuple:
+        """What decides the launch list: the (padded) shape, then per-crystal keys, dropout on / off (train / eval mode, p > 0),
+        the tests' fp64-softmax switch, the loss weight and - last - the count the recorded loss launch divides by (the batch's
+        own, or an accumulation window's total) - a slot recorded under one setting is never replayed under another.  (The
+        message-GEMM tile table is the fp32 program's: ``tiled`` decides nothing here.)"""
+        return (n, e, B, n_max, bool(self.model.per_crystal_keys), drop is not None, None if drop is None else drop[0],
+                bool(F64.SOFTMAX64), float(self.beta), self._loss_count(B))
+
+    def _slot_meta(self, g, dev):
+        m = graph_meta(g, dev)
+        if m.edge_perm is not None:
+            raise ValueError(f"{self._who}(replay=True) needs batches with destination-sorted edges (collate(sort_edges=True))")
+        return m
+
+    # ---- the program ---------------------------------------------------------------------------------------------------
+    def _loss_launch(self, dev, pg, ps, y, w, beta: float):
+        """The loss of the step with its gradient, for both output counts: -> (ddos, loss).  Two outputs: ``pg``, ``ps`` are
+        the halves of ``dos`` and ``ddos`` is laid out like it.  One output (the GNN-only baseline): ``ps is pg`` and
+        ``beta = 0`` - the loss entry in its one-output use (the loss is rmse(pg) exactly, the second gradient goes to scratch);
+        with ``loss=...`` the per-crystal entry in its own one-output form (ps == NULL: no second gradient, no scratch)."""
+        B, S = pg.shape
+        one = ps is pg
+        ddos = ops.alloc64(dev, B if one else 2 * B, S)
+        dpg = ddos if one else ddos[:B]
+        if self.loss is not None:
+            self._crystal, loss = self._loss_rows(ops.alloc64, dev, pg, None if one else ps, y, False, dpg,
+                                                  None if one else ddos[B:], weights=w)
+            return ddos, loss
+        dps, loss = ops.alloc64(dev, B, S) if one else ddos[B:], ops.alloc64(dev, 1)
+        ops.loss_phonon64(pg, ps, y, beta, dpg, dps, loss)
+        return ddos, loss[0]
 
     def _program(self, fp, g, m: GraphMeta, drop):
         """forward program, loss kernel, backward program on the batch ``g``: -> (loss, outputs)."""
-        model, cfg, dev = self.model, self.model._cfg, fp.flat.device
+        model, cfg = self.model, self.model._cfg
         B, S = m.num_graphs, cfg.S
-        w = self._batch_weights(g, F64._f64)         # (refuses a batch without `weight` before anything is launched)
+        w = self._batch_weights(g)                   # (refuses a batch without `weight` before anything is launched)
         dos, xL, ctx = F64.dostransformer_phonon_fwd(fp.P, cfg, g, m, drop=drop, per_crystal_keys=model.per_crystal_keys)
-        y = F64._f64(g.phdos).reshape(B, S)
-        ddos = ops.alloc64(dev, 2 * B, S)
-        if self.loss is not None:
-            self._crystal, loss = self._loss_rows(ops.alloc64, dev, dos[:B], dos[B:], y, False, ddos[:B], ddos[B:], weights=w)
-        else:
-            loss = ops.alloc64(dev, 1)
-            ops.loss_phonon64(dos[:B], dos[B:], y, self.beta, ddos[:B], ddos[B:], loss)
-            loss = loss[0]
+        ddos, loss = self._loss_launch(fp.flat.device, dos[:B], dos[B:], F64._f64(g.phdos).reshape(B, S), w, self.beta)
         F64.dostransformer_phonon_bwd(fp.P, fp.G, cfg, m, ctx, ddos, None)
         return loss, (dos[:B], xL, dos[B:])
 
@@ -149,31 +186,17 @@ class Trainer64(_AdamWState, SlotCache):
         """Forward + loss + backward; leaves the gradients in the flat buffer.  Returns the loss (0-dim float64 device tensor)."""
         self._ema_refuse("forward_backward")
         if _bump:                      # a direct forward_backward() + optimizer_step() loop draws fresh dropout masks too
-            self._refuse(g)
-            self._bump_dropout_seed()
-        fp, drop = self._prepare(g)
-        m = graph_meta(g, fp.flat.device)
+            self._refuse("step", g)
+        return self._batch_program(g, None, _bump)
+
+    def _eager(self, fp, g, drop) -> torch.Tensor:
         with torch.no_grad():
-            if self.replay:
-                return self._slot_step(fp, g, m, drop)
-            loss, out = self._program(fp, g, m, drop)
-            self._set_outputs(out, getattr(g, "real_nodes", None))
-            self.crystal_losses = self._crystal
-            return loss
+            loss, out = self._program(fp, g, graph_meta(g, fp.flat.device), drop)
+        self._set_outputs(out, getattr(g, "real_nodes", None))
+        self.crystal_losses = self._crystal
+        return loss
 
     # ---- replay --------------------------------------------------------------------------------------------------------
-    def _key(self, n: int, e: int, B: int, n_max: int, drop) -> tuple:
-        """What decides the launch list: the (padded) shape, then per-crystal keys, dropout on / off (train / eval mode, p > 0),
-        the tests' fp64-softmax switch, the loss weight and - last - the count the recorded loss launch divides by (the batch's
-        own, or an accumulation window's total) - a slot recorded under one setting is never replayed under another."""
-        return (n, e, B, n_max, bool(self.model.per_crystal_keys), drop is not None, None if drop is None else drop[0],
-                bool(F64.SOFTMAX64), float(self.beta), self._b_global(B))
-
-    def _b_global(self, B: int) -> int:
-        """The count the recorded loss launch divides by (the last field of a slot's key): the batch's own, or - inside an
-        accumulation window - the window's total."""
-        return int(B) if self._window_total is None else self._window_total
-
     def _run_slot(self, slot: Slot, fp, drop, fresh: bool) -> torch.Tensor:
         """The step on a slot whose static buffers hold the batch: recorded on first use, replayed afterwards."""
         if fresh:
@@ -184,118 +207,15 @@ class Trainer64(_AdamWState, SlotCache):
         self.crystal_losses = slot.crystal
         return slot.loss
 
-    def _slot_step(self, fp, g, m: GraphMeta, drop) -> torch.Tensor:
-        if m.edge_perm is not None:
-            raise ValueError(f"{self._who}(replay=True) needs batches with destination-sorted edges (collate(sort_edges=True))")
-        if self.bucket is not None and getattr(g, "real_nodes", None) is None:       # not padded yet: pad on the fly
-            g = pad_batch(g, *bucket_sizes(m.num_nodes, m.num_edges, *self.bucket))
-            m = g.meta
-        key = self._key(m.num_nodes, m.num_edges, m.num_graphs, m.n_max, drop)
-        if self.sample_weights:               # (the last field of a dataset step's key is its table: this batch brings its own)
-            key += (None,)
-        slot = self._lookup(key)
-        fresh = slot is None
-        if fresh:
-            slot = Slot(g, m, "phonon", torch.float64, weights=self.sample_weights)
-        else:
-            slot.load(g, m)
-        loss = self._run_slot(slot, fp, drop, fresh)
-        if fresh:
-            self._slots[key] = slot
-        return loss
-
     def _record(self, slot: Slot, fp, drop) -> None:
         """Run the step once on the slot's static buffers while recording every launch."""
         g, m = slot.g, slot.g.meta
         F64.require_replayable(g, slot.fields, fp.flat.device, self._who)
-        with ops.recording_scope():
+        with ops.recording_scope(), torch.no_grad():
             ops.RECORDER.begin()
             slot.loss, slot.out = self._program(fp, g, m, drop)
             slot.prog = ops.RECORDER.end()
         slot.crystal = self._crystal
-
-    def step_dataset(self, ds, indices, n_max: Optional[int] = None) -> torch.Tensor:
-        """One training step on the crystals ``indices`` of a device-resident ``loader.DeviceDataset`` (float64 tables:
-        ``DeviceDataset(..., dtype=torch.float64)`` holds them without a copy).  With ``replay`` and ``bucket`` the batch is
-        collated by ``dosx_collate_padded_f64`` STRAIGHT INTO the static buffers of its shape bucket, ghost padding included, and
-        the bucket's recorded program is replayed (recorded on first use, or - ``promote`` - run in a live larger bucket):
-        bitwise ``step(pad_batch(ds.collate(indices, n_max=n_max), *bucket_sizes(N, E, *bucket)))``.  Otherwise it is
-        ``step(ds.collate(indices, n_max=n_max))``.  ``n_max`` may exceed the selection's largest crystal, so that one value
-        serves a whole dataset (with per-crystal keys and no dropout the numbers do not depend on it)."""
-        self._ema_refuse("step_dataset")
-        if not (self.replay and self.bucket is not None):
-            return self.step(ds.collate(indices, n_max=n_max))
-        loss = self._dataset_program(ds, indices, n_max)
-        self.optimizer_step()
-        return loss
-
-    def _dataset_program(self, ds, indices, n_max: Optional[int]) -> torch.Tensor:
-        """``step_dataset`` (``replay`` with ``bucket``) up to the optimizer: bump the seed, collate into the bucket, run the slot."""
-        self._require_model(self.model)
-        table = self._require_weight_table("step_dataset", ds, ds._f64_tables())
-        idx, N, E, n_max = ds.bucket_dims(indices, n_max)
-        B = int(idx.shape[0])
-        n_pad, e_pad = bucket_sizes(N, E, *self.bucket)
-        self._bump_dropout_seed()
-        fp, drop = self._prepare(None, ds)
-        key = self._key(n_pad, e_pad, B, n_max, drop)
-        if table is not None:                 # another dataset's table: slots of its own, never a stale pointer
-            key += (table.data_ptr(),)
-        slot = self._lookup(key, allow_promote=True)
-        fresh = slot is None
-        if fresh:
-            t = ds._f64_tables()
-            slot = Slot.empty("phonon", fp.flat.device, torch.float64, B, n_pad, e_pad, n_max, int(t["x"].shape[1]),
-                              int(t["edge"].shape[1]), int(t["target"].shape[1]), weight_table=table)
-        ds.collate_into(slot.g, idx, slot.collate_scratch())
-        slot._loaded = None                                        # (the static buffers now hold a batch no object stands for)
-        slot.set_real_nodes(N)
-        with torch.no_grad():
-            loss = self._run_slot(slot, fp, drop, fresh)
-        if fresh:
-            self._slots[key] = slot
-        return loss
-
-    def step(self, g) -> torch.Tensor:
-        self._ema_refuse("step")
-        self._refuse(g)
-        self._bump_dropout_seed()
-        loss = self.forward_backward(g, _bump=False)
-        self.optimizer_step()
-        return loss
-
-    # ---- gradient accumulation -------------------------------------------------------------------------------------------
-    def step_accumulate(self, batches) -> torch.Tensor:
-        """ONE optimizer step on the objective of the concatenated batch, micro-batch by micro-batch, as
-        ``train.Trainer.step_accumulate``: every batch runs its ordinary float64 program with its per-crystal loss normalised by
-        the window's crystal count (the last field of a slot's key), one ``dosx_grad_accumulate_f64`` launch behind each sums the
-        flat gradients in the order ``((G1 + G2) + G3) + ...``, then one guard verdict, one AdamW launch, one update of the
-        average.  Needs ``loss=`` for more than one batch (the default pooled RMSE does not accumulate); one batch is ``step()``."""
-        batches = list(batches)
-        self._window_checks("step_accumulate", len(batches))
-        sizes = self._window_sizes("step_accumulate", (self._crystals_of(g) for g in batches))
-        for g in batches:
-            self._refuse(g)
-        if len(batches) == 1:
-            return self.step(batches[0])
-
-        def run(k):
-            self._bump_dropout_seed()
-            return self.forward_backward(batches[k], _bump=False)
-        return self._window("step_accumulate", sizes, run)
-
-    def step_dataset_accumulate(self, ds, index_lists, n_max: Optional[int] = None) -> torch.Tensor:
-        """``step_accumulate`` on selections of a device-resident float64 ``loader.DeviceDataset``, each collated as
-        ``step_dataset`` does: bitwise the batch-object form."""
-        index_lists = list(index_lists)
-        self._window_checks("step_dataset_accumulate", len(index_lists))
-        sizes = self._window_sizes("step_dataset_accumulate", (len(i) for i in index_lists))
-        self._require_model(self.model)
-        if len(index_lists) == 1:
-            return self.step_dataset(ds, index_lists[0], n_max=n_max)
-        if not (self.replay and self.bucket is not None):
-            return self.step_accumulate([ds.collate(i, n_max=n_max) for i in index_lists])
-        return self._window("step_dataset_accumulate", sizes, lambda k: self._dataset_program(ds, index_lists[k], n_max))
 
 
 class GraphnetworkTrainer64(Trainer64):
@@ -313,6 +233,7 @@ class GraphnetworkTrainer64(Trainer64):
     ``max_slots`` are ``Trainer64``'s, and so are ``loss`` / ``huber_delta`` (the entry's one-output form: ``ps == NULL``, no scratch
     gradient) with ``crystal_losses``.  Limits: single GPU, no HIP-graph mode."""
     _who = "GraphnetworkTrainer64"
+    _first_width_fixes_dead = True
 
     def __init__(self, model, lr: float = 1e-4, weight_decay: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8,
                  replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
@@ -328,50 +249,23 @@ class GraphnetworkTrainer64(Trainer64):
                          max_slots=max_slots, bucket=bucket, promote=promote, max_grad_norm=max_grad_norm,
                          skip_nonfinite=skip_nonfinite, param_groups=param_groups, ema_decay=ema_decay, ema_warmup=ema_warmup,
                          loss=loss, huber_delta=huber_delta, sample_weights=sample_weights, bin_weights=bin_weights)
-        self._dead = None                 # the dead-parameter set of the first batch's node-feature width
 
     def _require_model(self, model) -> None:
         GraphnetworkBase._require_f64_baseline(model, self._who)
 
-    def _flat_for(self, dev, g, width: Optional[int] = None):
-        """The model's flat parameters for a batch (or, step_dataset, an input width): which node encoder is dead follows the
-        width, and the first batch fixes it for this trainer (as train.Trainer._flat_for does for the fp32 baselines)."""
-        model = self.model
-        if g is None:
-            g = _Width(width)
-        dead = model._extra_dead(g)
-        if self._dead is None:
-            self._dead = dead
-        elif dead != self._dead:
-            raise DosxError(f"{self._who}: this batch has node features of width {g.x.shape[1]}, which selects the other node "
-                            f"encoder than the trainer's first batch did - its dead-parameter set (and the optimizer's layout) "
-                            f"is fixed by the first batch")
-        return model._ensure_flat(dev, g)
-
-    def _prepare(self, g, ds=None):
-        dev = self.model._module_device()
-        fp = self._flat_for(dev, g, None if ds is None else int(ds._f64_tables()["x"].shape[1]))
-        self._state(fp)
-        return fp, None
+    def _extra(self, fp, count: int):
+        return None                   # (no attention, no dropout)
 
     def _program(self, fp, g, m: GraphMeta, drop):
-        cfg, dev = self.model._cfg, fp.flat.device
-        B, S = m.num_graphs, cfg.S
-        w = self._batch_weights(g, F64._f64)
+        cfg = self.model._cfg
+        w = self._batch_weights(g)
         dos, ctx = F64.graphnetwork_phonon_fwd(fp.P, cfg, g, m, factored_head=True)
-        y = F64._f64(g.phdos).reshape(B, S)
-        ddos = ops.alloc64(dev, B, S)
-        if self.loss is not None:          # the one-output form of the entry: no second gradient, no scratch
-            self._crystal, loss = self._loss_rows(ops.alloc64, dev, dos, None, y, False, ddos, None, weights=w)
-        else:
-            scratch, loss = ops.alloc64(dev, B, S), ops.alloc64(dev, 1)
-            ops.loss_phonon64(dos, dos, y, 0.0, ddos, scratch, loss)
-            loss = loss[0]
+        ddos, loss = self._loss_launch(fp.flat.device, dos, dos, F64._f64(g.phdos).reshape(m.num_graphs, cfg.S), w, 0.0)
         F64.graphnetwork_phonon_bwd(fp.P, fp.G, cfg, m, ctx, ddos, factored_head=True)
         return loss, dos
 
     def _set_outputs(self, out, n_real: Optional[int]) -> None:
         self.last_outputs = out
 
-    def _key(self, n: int, e: int, B: int, n_max: int, drop) -> tuple:
-        return (n, e, B, n_max, self._b_global(B))
+    def _key(self, n: int, e: int, B: int, n_max: int, drop, tiled: bool) -> tuple:
+        return (n, e, B, n_max, self._loss_count(B))

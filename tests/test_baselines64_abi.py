@@ -165,7 +165,7 @@ def test_graphnetwork_trainer64_state_dict_is_trainer64s():
 
 def test_the_first_width_fixes_the_dead_node_encoder():
     from dostransformer_amd._lib import DosxError
-    from dostransformer_amd.train import _Width
+    from dostransformer_amd.trainer_base import _Width
     from dostransformer_amd.train64 import GraphnetworkTrainer64
     H, cpu = 16, torch.device("cpu")
     for first, other, dead, live in ((118, 118 + H // 2, "node_encoder_prompt.", "node_encoder."),

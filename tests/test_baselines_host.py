@@ -173,7 +173,8 @@ def test_trainer_and_predictor_accept_the_baselines_and_refuse_what_they_cannot_
 
 def test_trainer_fixes_the_dead_set_with_the_first_batch_and_checks_n_global():
     from dostransformer_amd._lib import DosxError
-    from dostransformer_amd.train import Trainer, _Width
+    from dostransformer_amd.train import Trainer
+    from dostransformer_amd.trainer_base import _Width
     for model in _modules():
         expected = 118 if model._cfg.kind == "phonon" else 200
         tr = Trainer(model)

@@ -287,7 +287,7 @@ def test_checkpointed_dropout_seed_is_rank_independent(monkeypatch):
     """Trainer.state_dict stores the dropout seed WITHOUT the saving rank's offset; a rank that loads it
     re-applies its own offset, so resumed data-parallel ranks keep drawing different masks for their different shards - the
     masks their uninterrupted selves would have drawn."""
-    from dostransformer_amd import _models, synth, train
+    from dostransformer_amd import _models, synth, train, trainer_base
     from dostransformer_amd.batch import collate
     from dostransformer_amd.embedder_phDOS.DOSTransformer_phonon import DOSTransformer_phonon
     off = lambda r: (0x9E3779B97F4A7C15 * (r + 1)) % _models._SEED_MOD
@@ -295,7 +295,7 @@ def test_checkpointed_dropout_seed_is_rank_independent(monkeypatch):
     seeds = {}
     for r in (0, 3):
         monkeypatch.setattr(_models, "rank_seed_offset", lambda r=r: off(r))
-        monkeypatch.setattr(train, "rank_seed_offset", lambda r=r: off(r))
+        monkeypatch.setattr(trainer_base, "rank_seed_offset", lambda r=r: off(r))
         torch.manual_seed(11)
         model = DOSTransformer_phonon(2, 1, 118, 4, 64, DEV, 0.25).to(DEV)
         tr = train.Trainer(model)
@@ -305,7 +305,7 @@ def test_checkpointed_dropout_seed_is_rank_independent(monkeypatch):
         seeds[r] = (int(model._drop_seed.item()), tr.state_dict())
     assert seeds[0][0] != seeds[3][0] and seeds[0][1]["drop_seed_base"] == seeds[3][1]["drop_seed_base"]
     # rank 3 resumes from the file rank 0 wrote: it gets ITS seed back, not rank 0's
-    monkeypatch.setattr(train, "rank_seed_offset", lambda: off(3))
+    monkeypatch.setattr(trainer_base, "rank_seed_offset", lambda: off(3))
     monkeypatch.setattr(_models, "rank_seed_offset", lambda: off(3))
     torch.manual_seed(99)
     model = DOSTransformer_phonon(2, 1, 118, 4, 64, DEV, 0.25).to(DEV)

@@ -590,3 +590,40 @@ def test_shared_lookup_counts_hits_misses_promotions_and_evicts_the_oldest():
     assert Trainer._lookup is SlotCache._lookup and Trainer64._lookup is SlotCache._lookup
     _lookup_walk(Trainer(m32, replay=True, max_slots=2, promote=0.08))
     _lookup_walk(Trainer64(m64, replay=True, bucket=(8, 128), max_slots=2, promote=0.08))
+
+
+def test_the_three_trainers_share_one_step_driver():
+    """step, step_accumulate, step_dataset, step_dataset_accumulate and _flat_for are written once, in trainer_base.TrainerBase:
+    train.Trainer, train64.Trainer64 and train64.GraphnetworkTrainer64 resolve them to the same function objects."""
+    from dostransformer_amd import train
+    from dostransformer_amd.train64 import GraphnetworkTrainer64, Trainer64
+    from dostransformer_amd.trainer_base import TrainerBase
+    for name in ("step", "step_accumulate", "step_dataset", "step_dataset_accumulate", "_flat_for"):
+        for cls in (train.Trainer, Trainer64, GraphnetworkTrainer64):
+            assert getattr(cls, name) is getattr(TrainerBase, name), (cls.__name__, name)
+    assert not hasattr(train, "_AdamWState")
+
+
+def test_a_refused_dataset_step_leaves_the_dropout_seed_alone():
+    """Every refusal that can be known before a launch comes before the seed bump: a slotted step_dataset with a foreign
+    n_global raises and the seed is what it was (fp32 and float64 driver)."""
+    from dostransformer_amd.embedder_phDOS.DOSTransformer_phonon import DOSTransformer_phonon
+    from dostransformer_amd.train import Trainer
+    from dostransformer_amd.train64 import Trainer64
+
+    class Dataset:                                          # what the refused step reads of a loader.DeviceDataset
+        def bucket_dims(self, indices, n_max):
+            return torch.as_tensor(indices), 9, 40, 5
+
+        def _f32_tables(self):
+            return {"x": torch.empty(0, 118)}
+        _f64_tables = _f32_tables
+    torch.manual_seed(0)
+    m64 = DOSTransformer_phonon(2, 1, 118, 4, 16, "cpu", 0.25).double().set_program_dtype(torch.float64)
+    for tr in (Trainer(DOSTransformer_phonon(2, 1, 118, 4, 16, "cpu", 0.25), replay=True, loss="crystal_rmse"),
+               Trainer64(m64, replay=True, bucket=(8, 128), loss="crystal_rmse")):
+        tr.model.train()
+        object.__setattr__(tr.model, "_drop_seed", torch.tensor([7], dtype=torch.int64))
+        with pytest.raises(ValueError, match="n_global=4"):
+            tr.step_dataset(Dataset(), [0, 1, 2], n_global=4)
+        assert int(tr.model._drop_seed) == 7 and tr.step_count == 0 and len(tr._slots) == 0

@@ -118,7 +118,7 @@ def test_chunk_map_follows_the_flat_layout(kind):
 
 
 def test_trainer_rebuilds_the_chunk_map_with_the_layout():
-    """_AdamWState._state is where the moments are re-homed - and the chunk map with them: after freeze() / update_trainable() the
+    """TrainerBase._state is where the moments are re-homed - and the chunk map with them: after freeze() / update_trainable() the
     trainer's map is the new layout's.  Without groups no map is built."""
     from dostransformer_amd import param_groups as pg
     from dostransformer_amd.train import Trainer
