@@ -198,3 +198,47 @@ def test_per_crystal(predictor, ds, indices=None, batch_size: int = 64, weights=
 
 
 test_per_crystal.__test__ = False          # (a library function named like the reference's, not a pytest test)
+
+
+class FunctionalsResult(NamedTuple):
+    """What ``functionals_per_crystal`` returns.  pred, y: [C,K] float64 on the device, ``F_k`` of every crystal's prediction
+    and target (times its ``scale``); mae: [K] host floats, the mean over the crystals of ``|pred - y|``; names: the K rows.
+    ratio_pred, ratio_y [C,R] (device), ratio_mae [R] and ratio_names: the same for the table's declared ratios (empty: R = 0)."""
+    pred: torch.Tensor
+    y: torch.Tensor
+    mae: List[float]
+    names: List[str]
+    ratio_pred: torch.Tensor
+    ratio_y: torch.Tensor
+    ratio_mae: List[float]
+    ratio_names: List[str]
+
+
+def functionals_per_crystal(result: PerCrystalResult, fn, scale=None) -> FunctionalsResult:
+    """The linear functionals ``fn`` (a ``functionals.Functionals`` or a [K,S] table: cumulative DOS, moments, a window, C_V(T))
+    of the predictions and targets ``test_per_crystal`` left on the device - one ``dosx_eval_functionals`` launch in float64, no
+    host copy of ``preds`` / ``y``.  ``scale``: None, or [C] factors, one per crystal in the result's order (eDOS: the ``y_max``
+    that undoes the target's normalisation; a ratio does not depend on it).  The declared ratios (``centre = m1 / m0``) are
+    formed from those values in float64 on the device.  Every mean absolute error comes back in ONE transfer."""
+    from . import functionals as _fn
+    from . import ops
+    fn = _fn.as_functionals(fn)
+    preds, ys = result.preds, result.y
+    C, S = int(preds.shape[0]), int(preds.shape[1])
+    if fn.S != S:
+        raise ValueError(f"functionals_per_crystal: the table has {fn.S} columns, the result {S} energy bins")
+    dev = preds.device
+    sc = None
+    if scale is not None:
+        sc = scale if torch.is_tensor(scale) else torch.as_tensor(scale, dtype=torch.float64)
+        sc = sc.detach().to(dev, torch.float64).reshape(-1).contiguous()
+        if sc.numel() != C:
+            raise ValueError(f"functionals_per_crystal: {sc.numel()} scales for {C} crystals")
+    out = torch.empty(C, 2, fn.K, dtype=torch.float64, device=dev)
+    ops.eval_functionals(preds.contiguous(), ys.contiguous(), fn.table.to(dev, preds.dtype).contiguous(), out, scale=sc)
+    fp, fy = out[:, 0], out[:, 1]
+    num = torch.tensor([a for _, a, _ in fn.ratios], dtype=torch.int64, device=dev)
+    den = torch.tensor([b for _, _, b in fn.ratios], dtype=torch.int64, device=dev)
+    rp, ry = fp[:, num] / fp[:, den], fy[:, num] / fy[:, den]
+    maes = torch.cat([(fp - fy).abs().mean(0), (rp - ry).abs().mean(0)]).tolist()          # the one transfer
+    return FunctionalsResult(fp, fy, maes[:fn.K], list(fn.names), rp, ry, maes[fn.K:], [n for n, _, _ in fn.ratios])

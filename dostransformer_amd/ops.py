@@ -1667,16 +1667,49 @@ def eval_metrics(pred: torch.Tensor, y: torch.Tensor, metrics: torch.Tensor, cla
           w=lambda: ("eval_metrics", "eval_metrics_kernel", "hbm", 3.0 * pred.element_size() * B * S))
 
 
+def eval_functionals(pred: torch.Tensor, y: torch.Tensor, table: torch.Tensor, out: torch.Tensor,
+                     scale: Optional[torch.Tensor] = None) -> None:
+    """out[b,0,k] = F_k(pred_b) scale_b and out[b,1,k] = F_k(y_b) scale_b, ``F_k(p) = sum_s table[k,s] p_s``, in float64
+    (include/dosx.h: dosx_eval_functionals / dosx_eval_functionals_f64).  pred, y: [B,S] and table: [K,S], all float32 or all
+    float64; out: [B,2,K] float64; scale: None or [B] float64 (e.g. the eDOS ``y_max``).  Any S, K >= 1; B = 0 launches nothing."""
+    dt = pred.dtype
+    if dt not in (torch.float32, torch.float64):
+        raise TypeError(f"eval_functionals: float32 or float64 predictions, got {dt}")
+    for k, t in (("pred", pred), ("y", y), ("table", table)):
+        if t.dtype != dt or not t.is_cuda:
+            raise TypeError(f"eval_functionals: {k} must be a {dt} CUDA tensor like pred, got {t.dtype} on {t.device}")
+    for k, t in (("out", out), ("scale", scale)):
+        if t is not None and (t.dtype != torch.float64 or not t.is_cuda):
+            raise TypeError(f"eval_functionals: {k} must be a float64 CUDA tensor, got {t.dtype} on {t.device}")
+    if pred.dim() != 2 or pred.shape[1] < 1 or y.shape != pred.shape or table.dim() != 2 or table.shape[0] < 1 or \
+            table.shape[1] != pred.shape[1] or tuple(out.shape) != (pred.shape[0], 2, table.shape[0]) or \
+            (scale is not None and tuple(scale.shape) != (pred.shape[0],)):
+        raise ValueError(f"eval_functionals: pred {tuple(pred.shape)}, y {tuple(y.shape)}, table {tuple(table.shape)}, out "
+                         f"{tuple(out.shape)}" + ("" if scale is None else f", scale {tuple(scale.shape)}")
+                         + ": want [B,S], [B,S], [K,S] (S, K >= 1), [B,2,K] and [B]")
+    for k, t in (("pred", pred), ("y", y), ("table", table), ("out", out), ("scale", scale)):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"eval_functionals: {k} must be contiguous, got strides {t.stride()}")
+    B, S, K = int(pred.shape[0]), int(pred.shape[1]), int(table.shape[0])
+    _call("dosx_eval_functionals" if dt == torch.float32 else "dosx_eval_functionals_f64", pred.data_ptr(), y.data_ptr(), B, S,
+          _p(scale), table.data_ptr(), K, out.data_ptr(), _stream(),
+          w=lambda: ("eval_functionals", "eval_functionals_kernel", "hbm", pred.element_size() * (2.0 * B * S + K * S) + 16.0 * B * K))
+
+
 def sum_to(src, n, dst):
     _call("dosx_sum", _p(src), int(n), _p(dst), _stream())
 
 
 # per-crystal losses (csrc/loss_rows.hip; include/dosx.h: dosx_loss_rows / dosx_loss_rows_f64): the trainers' names -> enumerators
 LOSS_KINDS = {"crystal_rmse": _abi.DOSX_LOSS_RMSE, "mse": _abi.DOSX_LOSS_MSE, "mae": _abi.DOSX_LOSS_MAE, "huber": _abi.DOSX_LOSS_HUBER}
+# linear functionals next to them (csrc/loss_functional.hip; include/dosx.h: dosx_loss_rows_fn / dosx_loss_rows_fn_f64)
+FUNCTIONAL_KINDS = {"sq": _abi.DOSX_FN_SQ, "abs": _abi.DOSX_FN_ABS}
+FUNCTIONAL_MAX = 512               # K and S of a table in the loss
 
 
 def _loss_rows(who: str, dt: torch.dtype, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global,
-               weights=None, weight_index=None, bin_weights=None) -> None:
+               weights=None, weight_index=None, bin_weights=None, functionals=None, functional_kind="sq",
+               functional_weight=1.0) -> None:
     if isinstance(kind, str):
         if kind not in LOSS_KINDS:
             raise ValueError(f"{who}: kind {kind!r} is not one of {sorted(LOSS_KINDS)}")
@@ -1706,7 +1739,7 @@ def _loss_rows(who: str, dt: torch.dtype, pg, ps, y, kind, clamp_target, beta, d
             loss.data_ptr())
     work = lambda: ("loss_rows", "loss_rows_kernel", "hbm", (2.0 if ps is None else 3.0) * pg.element_size() * 2 * B * S,
                     1 if per_crystal is None else 2)
-    if weights is None and weight_index is None and bin_weights is None:        # today's callers issue today's launch
+    if weights is None and weight_index is None and bin_weights is None and functionals is None:   # today's callers issue today's launch
         _call("dosx_loss_rows" if dt == torch.float32 else "dosx_loss_rows_f64", *args, _stream(), w=work)
         return
     if weights is None:
@@ -1734,15 +1767,36 @@ def _loss_rows(who: str, dt: torch.dtype, pg, ps, y, kind, clamp_target, beta, d
         if bin_weights.dim() != 1 or bin_weights.numel() != S or not bin_weights.is_contiguous():
             raise ValueError(f"{who}: bin_weights must be a contiguous [S] = [{S}] tensor, got shape {tuple(bin_weights.shape)} "
                              f"strides {bin_weights.stride()}")
-    _call("dosx_loss_rows_w" if dt == torch.float32 else "dosx_loss_rows_w_f64", *args, _p(weights), _p(weight_index),
-          _p(bin_weights), _stream(), w=work)
+    if functionals is None:
+        _call("dosx_loss_rows_w" if dt == torch.float32 else "dosx_loss_rows_w_f64", *args, _p(weights), _p(weight_index),
+              _p(bin_weights), _stream(), w=work)
+        return
+    if isinstance(functional_kind, str):
+        if functional_kind not in FUNCTIONAL_KINDS:
+            raise ValueError(f"{who}: functional_kind {functional_kind!r} is not one of {sorted(FUNCTIONAL_KINDS)}")
+        functional_kind = FUNCTIONAL_KINDS[functional_kind]
+    lam = float(functional_weight)
+    if not 0.0 <= lam < float("inf"):
+        raise ValueError(f"{who}: functional_weight must be finite and >= 0, got {functional_weight}")
+    if functionals.dtype != dt or not functionals.is_cuda:
+        raise TypeError(f"{who}: functionals must be a {dt} CUDA tensor, got {functionals.dtype} on {functionals.device}")
+    if functionals.dim() != 2 or functionals.shape[1] != S or not functionals.is_contiguous() or \
+            not 1 <= functionals.shape[0] <= FUNCTIONAL_MAX or S > FUNCTIONAL_MAX:
+        raise ValueError(f"{who}: functionals must be a contiguous [K,S] = [K,{S}] table with K, S <= {FUNCTIONAL_MAX}, got shape "
+                         f"{tuple(functionals.shape)} strides {functionals.stride()}")
+    K = int(functionals.shape[0])
+    fwork = lambda: ("loss_rows_fn", "loss_fn_kernel", "hbm", (2.0 if ps is None else 3.0) * pg.element_size() * 2 * B * S
+                     + pg.element_size() * K * S, 1 if per_crystal is None else 2)
+    _call("dosx_loss_rows_fn" if dt == torch.float32 else "dosx_loss_rows_fn_f64", *args, _p(weights), _p(weight_index),
+          _p(bin_weights), functionals.data_ptr(), K, int(functional_kind), lam, _stream(), w=fwork)
 
 
 def loss_rows(pg: torch.Tensor, ps: Optional[torch.Tensor], y: torch.Tensor, kind, *, clamp_target: bool = False,
               beta: float = 1.0, delta: Optional[float] = None, dpg: torch.Tensor, dps: Optional[torch.Tensor] = None,
               per_crystal: Optional[torch.Tensor] = None, loss: torch.Tensor, B_global: Optional[int] = None,
               weights: Optional[torch.Tensor] = None, weight_index: Optional[torch.Tensor] = None,
-              bin_weights: Optional[torch.Tensor] = None) -> None:
+              bin_weights: Optional[torch.Tensor] = None, functionals: Optional[torch.Tensor] = None,
+              functional_kind="sq", functional_weight: float = 1.0) -> None:
     """Per-crystal loss of the [B,S] predictions pg (and ps) against y with its gradient (include/dosx.h: dosx_loss_rows):
     ``l_b = f(pg_b) + beta f(ps_b)`` with f the crystal's RMSE, MSE, MAE or Huber(``delta``) term - ``kind`` a key of
     :data:`LOSS_KINDS` or its enumerator -, ``per_crystal[b] = l_b`` (optional), ``loss[0] = sum_b l_b / B_global`` (default B) and
@@ -1753,9 +1807,15 @@ def loss_rows(pg: torch.Tensor, ps: Optional[torch.Tensor], y: torch.Tensor, kin
     ``weights[weight_index[b]]`` out of a whole dataset's table with ``weight_index`` the batch's [B] int32 selection (its entries
     must lie inside the table: nothing here reads them) - and [S] energy-bin weights ``v_s`` (sum > 0): ``loss[0] = sum_b w_b l_b /
     B_global`` with f the ``v``-weighted means, ``per_crystal[b]`` still the crystal's own ``l_b``; ``w_b == 0`` writes zero
-    gradient rows and a zero share whatever the crystal holds.  All three None: the unweighted entry, the launch it always was."""
+    gradient rows and a zero share whatever the crystal holds.  All three None: the unweighted entry, the launch it always was.
+
+    ``functionals`` / ``functional_kind`` / ``functional_weight`` (include/dosx.h: dosx_loss_rows_fn): a [K,S] table of linear
+    functionals ``F_k(p) = sum_s table[k,s] p_s`` (K, S <= 512) whose differences ``u_k = F_k(p_b) - F_k(t_b)`` add
+    ``functional_weight / K * sum_k e(u_k)`` to each output's term, ``e(u) = u^2`` (``"sq"``) or ``|u|`` (``"abs"``) - the same
+    launch, the rows written once.  ``per_crystal[b]`` includes the term.  Without a table the call is the one it was; with a
+    table and ``functional_weight == 0`` the library runs the weighted kernels, bit for bit."""
     _loss_rows("loss_rows", torch.float32, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global,
-               weights, weight_index, bin_weights)
+               weights, weight_index, bin_weights, functionals, functional_kind, functional_weight)
 
 
 # ---- guarded optimizer step (csrc/step_guard.hip; include/dosx.h: DosxStepGuard) -----------------------------------------------
@@ -2394,10 +2454,11 @@ def loss_rows64(pg: torch.Tensor, ps: Optional[torch.Tensor], y: torch.Tensor, k
                 beta: float = 1.0, delta: Optional[float] = None, dpg: torch.Tensor, dps: Optional[torch.Tensor] = None,
                 per_crystal: Optional[torch.Tensor] = None, loss: torch.Tensor, B_global: Optional[int] = None,
                 weights: Optional[torch.Tensor] = None, weight_index: Optional[torch.Tensor] = None,
-                bin_weights: Optional[torch.Tensor] = None) -> None:
-    """:func:`loss_rows` on float64 operands (include/dosx.h: dosx_loss_rows_f64 / dosx_loss_rows_w_f64)."""
+                bin_weights: Optional[torch.Tensor] = None, functionals: Optional[torch.Tensor] = None,
+                functional_kind="sq", functional_weight: float = 1.0) -> None:
+    """:func:`loss_rows` on float64 operands (include/dosx.h: dosx_loss_rows_f64 / dosx_loss_rows_w_f64 / dosx_loss_rows_fn_f64)."""
     _loss_rows("loss_rows64", torch.float64, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global,
-               weights, weight_index, bin_weights)
+               weights, weight_index, bin_weights, functionals, functional_kind, functional_weight)
 
 
 def grad_accumulate64(dst: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None, n: Optional[int] = None, *,

@@ -115,6 +115,16 @@ class Trainer(TrainerBase):
     the unweighted bits; a weight of exactly 0 takes a crystal out whatever it holds (a NaN target included: the guard does not
     trip); ``crystal_losses`` stay the crystals' own unweighted losses.  Every mode, windows, the guard, frozen parameters, groups
     and the average; constructor arguments like ``loss``: not in ``state_dict()``; not under data parallelism.
+
+    ``functionals=<functionals.Functionals | [K,S] tensor>`` with ``functional_kind="sq" | "abs"`` and ``functional_weight=lam``
+    (with one of the four ``loss=`` kinds): a penalty on K linear functionals of the DOS next to the pointwise term, ``l_b += lam / K
+    sum_k e(F_k(p_b) - F_k(t_b))`` per output (``beta`` on the second), ``e = u^2`` or ``|u|`` - with ``functionals.cumulative(S)``
+    the Cramer or the Wasserstein-1 distance between the cumulative DOS curves - through ``dosx_loss_rows_fn`` in place of the
+    loss launch, no other launch.  K, S <= 512.  The table lives in ONE trainer-owned device buffer:
+    ``set_functionals(table)`` of the same shape writes it in place, nothing is re-recorded, the next replayed step reads it
+    (a schedule on the term is a rescaled table); ``lam`` is recorded with the launch.  ``crystal_losses`` include the term.
+    ``functional_weight=0`` trains the bits of the trainer without a table.  Every mode, windows, the guard, frozen parameters,
+    groups, the average and the weights; constructor arguments: not in ``state_dict()``; not under data parallelism.
     """
 
     _who = "Trainer"
@@ -126,7 +136,8 @@ class Trainer(TrainerBase):
                  bucket=(8, 128), max_slots: int = 32, promote: float = 0.0, per_crystal_keys: bool = False,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None,
                  ema_decay: Optional[float] = None, ema_warmup: bool = True, loss: Optional[str] = None,
-                 huber_delta: Optional[float] = None, sample_weights: bool = False, bin_weights=None):
+                 huber_delta: Optional[float] = None, sample_weights: bool = False, bin_weights=None,
+                 functionals=None, functional_kind: str = "sq", functional_weight: float = 1.0):
         if not isinstance(model, (DOSTransformerBase, GraphnetworkBase)):
             raise TypeError("Trainer drives DOSTransformer / DOSTransformer_phonon / Graphnetwork / Graphnetwork_phonon / mlp modules")
         model._require_fp32_program("Trainer")
@@ -155,6 +166,7 @@ class Trainer(TrainerBase):
         self._init_ema(ema_decay, ema_warmup)
         self._init_loss(loss, huber_delta)
         self._init_weights(sample_weights, bin_weights)
+        self._init_functionals(functionals, functional_kind, functional_weight)
         self.graph = graph
         self.replay = replay
         # (node, edge) granularity of the shape buckets unpadded batches are ghost-padded to in graph / replay mode: a

@@ -67,6 +67,8 @@ class Trainer64(TrainerBase):
     dataset's resident table gathered by the loss launch) and ``[S]`` energy-bin weights in the per-crystal loss
     (``dosx_loss_rows_w_f64``), as on ``train.Trainer``; they need ``loss=``.  With sample weights a slot's key ends in the table's
     address (``None`` for a batch-object slot).
+    ``functionals`` / ``functional_kind`` / ``functional_weight``: a ``[K,S]`` table of linear functionals of the DOS penalised next
+    to the pointwise term (``dosx_loss_rows_fn_f64``), ``set_functionals(table)`` in place, as on ``train.Trainer``; they need ``loss=``.
     ``step(g, n_global=None)`` / ``step_dataset(ds, indices, n_global=None, n_max=None)`` are the drivers' shared methods
     (``trainer_base.TrainerBase``) and carry ``train.Trainer``'s ``n_global``: this driver is single-GPU and refuses any value
     but the batch's own count - pass ``n_max`` by keyword.
@@ -80,7 +82,8 @@ class Trainer64(TrainerBase):
                  eps: float = 1e-8, replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None,
                  ema_decay: Optional[float] = None, ema_warmup: bool = True, loss: Optional[str] = None,
-                 huber_delta: Optional[float] = None, sample_weights: bool = False, bin_weights=None):
+                 huber_delta: Optional[float] = None, sample_weights: bool = False, bin_weights=None,
+                 functionals=None, functional_kind: str = "sq", functional_weight: float = 1.0):
         self._require_model(model)
         self._init_guard(max_grad_norm, skip_nonfinite)
         self.model, self.lr, self.beta, self.wd, self.betas, self.eps = model, lr, beta, weight_decay, tuple(betas), eps
@@ -88,6 +91,7 @@ class Trainer64(TrainerBase):
         self._init_ema(ema_decay, ema_warmup)
         self._init_loss(loss, huber_delta)
         self._init_weights(sample_weights, bin_weights)
+        self._init_functionals(functionals, functional_kind, functional_weight)
         self._crystal = None              # the per-crystal losses of the program just issued (loss=...), else None
         self.replay = bool(replay)
         self.max_slots = int(max_slots)
@@ -239,7 +243,8 @@ class GraphnetworkTrainer64(Trainer64):
                  replay: bool = False, max_slots: int = 32, bucket=None, promote: float = 0.0,
                  max_grad_norm: Optional[float] = None, skip_nonfinite: bool = False, param_groups=None,
                  ema_decay: Optional[float] = None, ema_warmup: bool = True, loss: Optional[str] = None,
-                 huber_delta: Optional[float] = None, sample_weights: bool = False, bin_weights=None, **unknown):
+                 huber_delta: Optional[float] = None, sample_weights: bool = False, bin_weights=None,
+                 functionals=None, functional_kind: str = "sq", functional_weight: float = 1.0, **unknown):
         if "beta" in unknown:
             raise ValueError(f"GraphnetworkTrainer64: beta={unknown['beta']} - the model has ONE output and its loss no second "
                              f"term to weigh")
@@ -248,7 +253,8 @@ class GraphnetworkTrainer64(Trainer64):
         super().__init__(model, lr=lr, beta=1.0, weight_decay=weight_decay, betas=betas, eps=eps, replay=replay,
                          max_slots=max_slots, bucket=bucket, promote=promote, max_grad_norm=max_grad_norm,
                          skip_nonfinite=skip_nonfinite, param_groups=param_groups, ema_decay=ema_decay, ema_warmup=ema_warmup,
-                         loss=loss, huber_delta=huber_delta, sample_weights=sample_weights, bin_weights=bin_weights)
+                         loss=loss, huber_delta=huber_delta, sample_weights=sample_weights, bin_weights=bin_weights,
+                         functionals=functionals, functional_kind=functional_kind, functional_weight=functional_weight)
 
     def _require_model(self, model) -> None:
         GraphnetworkBase._require_f64_baseline(model, self._who)

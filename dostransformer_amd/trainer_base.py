@@ -2,7 +2,7 @@
 
 State: the AdamW moments laid out like the model's flat parameters with their checkpoint, the gradient guard
 (``guard.StepGuard``), the weight average (``ema.WeightEma``), parameter groups, the objective (``loss=``) with its sample and
-energy-bin weights, the accumulation window and the bucket table (``slots.SlotCache``).
+energy-bin weights and its linear functionals, the accumulation window and the bucket table (``slots.SlotCache``).
 
 Driver: the public step methods - ``step``, ``step_accumulate``, ``step_dataset``, ``step_dataset_accumulate`` - and the two slot
 flows behind them (a batch object copied into its bucket; a dataset selection collated straight into it), written once.  A
@@ -18,6 +18,7 @@ import torch
 from . import _abi
 from . import functional as Fn
 from . import functional64 as F64
+from . import functionals as _fn
 from . import ops
 from . import param_groups as _pg
 from ._lib import DosxError
@@ -310,7 +311,7 @@ class TrainerBase(StepGuard, WeightEma, SlotCache):
         fn = ops.loss_rows if self._dtype == torch.float32 else ops.loss_rows64
         fn(pg, ps, y, self.loss, clamp_target=clamp, beta=self.beta, delta=self.huber_delta, dpg=dpg, dps=dps, per_crystal=per,
            loss=loss, B_global=int(B_global), weights=weights[0], weight_index=weights[1],
-           bin_weights=self._bin_operand(dev))
+           bin_weights=self._bin_operand(dev), **self._functional_operands(dev))
         return per, loss[0]
 
     # ---- sample weights and energy-bin weights (include/dosx.h: dosx_loss_rows_w / dosx_loss_rows_w_f64) --------
@@ -352,6 +353,69 @@ class TrainerBase(StepGuard, WeightEma, SlotCache):
                 self._slots = OrderedDict()
             self._bin_dev = self.bin_weights.to(dev, self._dtype).contiguous()
         return self._bin_dev
+
+    # ---- linear functionals of the DOS in the loss (include/dosx.h: dosx_loss_rows_fn / dosx_loss_rows_fn_f64) ----
+    functionals = None                # None, or the functionals.Functionals whose table the loss reads (float64, on the host)
+    functional_kind = "sq"
+    functional_weight = 1.0           # lam: recorded with the launch, fixed for the trainer's life
+    _fn_dev = None                    # the table on the device in the program's dtype: ONE buffer, written in place ever after
+
+    def _init_functionals(self, functionals, functional_kind="sq", functional_weight=1.0) -> None:
+        """``functionals=`` / ``functional_kind=`` / ``functional_weight=`` of a trainer's constructor; call it after
+        ``_init_weights``.  Constructor arguments like ``loss``: not part of ``state_dict()``."""
+        who = self._who
+        self.functionals, self.functional_kind, self.functional_weight, self._fn_dev = None, "sq", 1.0, None
+        if functionals is None:
+            if functional_kind != "sq" or float(functional_weight) != 1.0:
+                raise ValueError(f"{who}(functional_kind={functional_kind!r}, functional_weight={functional_weight}) without "
+                                 f"functionals=...: there is no table they could apply to")
+            return
+        if self.dist is not None:
+            raise DosxError(f"{who}(functionals=...) is a single-GPU mode: not with dist (data parallelism)")
+        if self.loss is None:
+            raise ValueError(f"{who}(functionals=...) adds a term to the per-crystal losses: pass loss=\"crystal_rmse\" (on an eDOS "
+                             f"model the default objective, bit for bit) or another of {', '.join(repr(k) for k in ops.LOSS_KINDS)}")
+        if functional_kind not in ops.FUNCTIONAL_KINDS:
+            raise ValueError(f"{who}(functional_kind={functional_kind!r}): not one of "
+                             f"{', '.join(repr(k) for k in ops.FUNCTIONAL_KINDS)}")
+        lam = float(functional_weight)
+        if not 0.0 <= lam < float("inf"):
+            raise ValueError(f"{who}(functional_weight={functional_weight}): must be finite and >= 0")
+        self.functionals = self._checked_functionals(f"{who}(functionals=...)", functionals)
+        self.functional_kind, self.functional_weight = functional_kind, lam
+
+    def _checked_functionals(self, what: str, fn):
+        fn = _fn.as_functionals(fn)                   # (2-D and finite: its constructor)
+        S, top = int(self.model._cfg.S), ops.FUNCTIONAL_MAX
+        if fn.S != S:
+            raise ValueError(f"{what}: the table has {fn.S} columns, the model {S} energy bins - want [K,S] = [K,{S}]")
+        if fn.K > top or fn.S > top:
+            raise ValueError(f"{what}: [K,S] = [{fn.K},{fn.S}], the loss takes at most {top} functionals of at most {top} bins")
+        return fn
+
+    def set_functionals(self, functionals) -> None:
+        """Replace the table by another of the SAME shape, in place: the trainer's one device buffer is overwritten, nothing is
+        re-recorded, and the next step - replayed or not - reads the new values.  A schedule on the term is a rescaled table
+        (``fn.scaled(c)``: ``"sq"`` scales with c^2, ``"abs"`` with c); ``functional_weight`` itself stays what was recorded."""
+        if self.functionals is None:
+            raise ValueError(f"{self._who}.set_functionals: the trainer was built without functionals=...")
+        fn = self._checked_functionals(f"{self._who}.set_functionals", functionals)
+        if fn.K != self.functionals.K:
+            raise ValueError(f"{self._who}.set_functionals: [K,S] = [{fn.K},{fn.S}], the trainer's table is "
+                             f"[{self.functionals.K},{self.functionals.S}] - the recorded launches hold its shape")
+        self.functionals = fn
+        if self._fn_dev is not None:
+            self._fn_dev.copy_(fn.table.to(self._dtype))
+
+    def _functional_operands(self, dev) -> dict:
+        """The keyword operands of ``ops.loss_rows`` for the term; none without a table: the call it always was."""
+        if self.functionals is None:
+            return {}
+        if self._fn_dev is None or self._fn_dev.device != dev:
+            if self._fn_dev is not None:       # (the module moved: the recordings hold the old buffer's address)
+                self._slots = OrderedDict()
+            self._fn_dev = self.functionals.table.to(dev, self._dtype).contiguous()
+        return {"functionals": self._fn_dev, "functional_kind": self.functional_kind, "functional_weight": self.functional_weight}
 
     def _require_weight(self, what: str, g) -> None:
         """``sample_weights=True``: the batch must carry ``weight`` - raised before anything is launched."""

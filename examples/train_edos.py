@@ -52,7 +52,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dostransformer_amd import checkpoint, evaluate, featurize, param_groups, synth, validate, weights  # noqa: E402
+from dostransformer_amd import checkpoint, evaluate, featurize, functionals, param_groups, synth, validate, weights  # noqa: E402
 from dostransformer_amd._lib import DosxError  # noqa: E402
 from dostransformer_amd.embedder_eDOS.DOSTransformer import DOSTransformer  # noqa: E402
 from dostransformer_amd.loader import DeviceDataset  # noqa: E402
@@ -121,8 +121,28 @@ def parse_args(argv=None):
     ap.add_argument("--fermi-weight", default=None, metavar="CENTER,WIDTH[,FLOOR]",
                     help="energy-bin weights: a Gaussian bump of WIDTH bins around bin CENTER on a floor in [0, 1] (default 0) "
                          "(weights.fermi_window; Trainer(bin_weights=...)); needs a per-crystal --loss")
+    ap.add_argument("--cdf-loss", default=None, metavar="LAM[,sq|abs]",
+                    help="LAM times the distance between the cumulative DOS curves next to the per-crystal loss - sq (default): "
+                         "Cramer, abs: Wasserstein-1 (functionals.cumulative; Trainer(functionals=...)); needs a per-crystal --loss")
+    ap.add_argument("--report-moments", action="store_true",
+                    help="with --eval-per-crystal: the mean absolute errors of the zeroth, first and second moment of the DOS and of "
+                         "the band centre m1 / m0 (energies in bins from the middle of the grid), computed on the device "
+                         "(functionals.moments; evaluate.functionals_per_crystal)")
     param_groups.add_arguments(ap)
     args = ap.parse_args(argv)
+    if args.cdf_loss is not None:
+        parts = args.cdf_loss.split(",")
+        try:
+            lam, kind = float(parts[0]), (parts[1] if len(parts) > 1 else "sq")
+            assert len(parts) <= 2 and kind in ("sq", "abs") and 0.0 <= lam < float("inf")
+        except (ValueError, AssertionError):
+            ap.error("--cdf-loss LAM[,sq|abs]: a finite weight >= 0 and, optionally, the kind")
+        args.cdf_loss = (lam, kind)
+        if args.loss == "reference":
+            ap.error("--cdf-loss adds a term to the per-crystal losses: pass --loss crystal_rmse (this model's reference objective "
+                     "through the per-crystal entry) or another per-crystal --loss")
+    if args.report_moments and args.eval_per_crystal <= 0 and args.embedder == "DOSTransformer":
+        ap.error("--report-moments reads the per-crystal evaluator's outputs: pass --eval-per-crystal N")
     if (args.balance_systems is not None or args.fermi_weight is not None) and args.loss == "reference":
         ap.error("--balance-systems / --fermi-weight weigh the per-crystal losses: pass --loss crystal_rmse (this model's reference "
                  "objective through the per-crystal entry) or another per-crystal --loss")
@@ -218,14 +238,22 @@ def _main(argv=None):
                       per_crystal_keys=args.per_crystal_keys,      # AdamW(lr, weight_decay=1e-2), `:91`
                       max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, param_groups=groups,
                       ema_decay=args.ema, ema_warmup=not args.no_ema_warmup,
-                      loss=None if args.loss == "reference" else args.loss, huber_delta=args.huber_delta)
+                      loss=None if args.loss == "reference" else args.loss, huber_delta=args.huber_delta,
+                      **({} if args.cdf_loss is None else dict(functionals=functionals.cumulative(201, 1.0 / 201),
+                                                               functional_weight=args.cdf_loss[0], functional_kind=args.cdf_loss[1])))
     predictor = Predictor(model, bucket=bucket, per_crystal_keys=args.eval_per_crystal > 0 and not baseline)
     criterion_2 = torch.nn.L1Loss()                                                       # `main_eDOS.py:93`
 
     def run_test(name):
         """`utils.test` on a split -> (rmse, mse, mae, r2, ...): the reference's batch-size-1 numbers either way."""
         if args.eval_per_crystal > 0 or baseline:
-            return evaluate.test_per_crystal(predictor, ds[name], batch_size=args.eval_per_crystal or 64).as_reference()
+            res = evaluate.test_per_crystal(predictor, ds[name], batch_size=args.eval_per_crystal or 64)
+            if args.report_moments:                                  # from the outputs still on the device
+                e = torch.arange(201, dtype=torch.float64) - 100.0
+                mo = evaluate.functionals_per_crystal(res, functionals.moments(e, orders=(0, 1, 2), de=1.0))
+                print(f"            {name} moments mae " + "  ".join(f"{n} {v:.4g}" for n, v in zip(mo.names + mo.ratio_names,
+                                                                                                 mo.mae + mo.ratio_mae)))
+            return res.as_reference()
         return evaluate.test(predictor, ds[name].batches(args.eval_batch_size), criterion_2, evaluate.r2)
 
     nmax_train = int(ds["train"].n_nodes.max())

@@ -65,6 +65,13 @@ count[its crystal system] ** -POWER (default 1), normalised to mean 1 (weights.b
 Trainer(sample_weights=True): the loss becomes sum_b w_b l_b / B, the weights ride on the batch or are gathered by the loss launch).
 
     python examples/train_phonon.py --loss crystal_rmse --per-crystal-keys --balance-systems 0.5
+
+A cumulative-DOS term (fused trainers, with a per-crystal --loss): --cdf-loss LAM[,sq|abs] adds LAM times the Cramer (sq) or the
+Wasserstein-1 (abs) distance between predicted and target cumulative DOS to every crystal's loss (functionals.cumulative ->
+Trainer(functionals=...): the same loss launch).  --report-heat-capacity T[,T...] prints, at every evaluation, the mean absolute
+error of the harmonic C_V(T) of the predicted DOS, computed on the device from the per-crystal evaluator's outputs.
+
+    python examples/train_phonon.py --loss crystal_rmse --cdf-loss 0.5 --eval-per-crystal 64 --report-heat-capacity 100,300,1000
 """
 import argparse
 import os
@@ -76,7 +83,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dostransformer_amd import checkpoint, evaluate, featurize, ops, param_groups, synth, validate, weights  # noqa: E402
+from dostransformer_amd import checkpoint, evaluate, featurize, functionals, ops, param_groups, synth, validate, weights  # noqa: E402
 from dostransformer_amd.embedder_phDOS.DOSTransformer_phonon import DOSTransformer_phonon  # noqa: E402
 from dostransformer_amd.loader import DeviceDataset  # noqa: E402
 from dostransformer_amd.predict import Predictor  # noqa: E402
@@ -148,8 +155,27 @@ def _main(argv=None):
     ap.add_argument("--balance-systems", type=float, nargs="?", const=1.0, default=None, metavar="POWER",
                     help="fused trainers: class-balanced sample weights over the 7 crystal systems, w ~ count[system] ** -POWER "
                          "(default 1), mean 1 over the training set (weights.balanced; sample_weights=True); needs a per-crystal --loss")
+    ap.add_argument("--cdf-loss", default=None, metavar="LAM[,sq|abs]",
+                    help="fused trainers: LAM times the distance between the cumulative DOS curves next to the per-crystal loss - sq "
+                         "(default): Cramer, abs: Wasserstein-1 (functionals.cumulative; functionals=...); needs a per-crystal --loss")
+    ap.add_argument("--report-heat-capacity", default=None, metavar="T[,T...]",
+                    help="with --eval-per-crystal: the mean absolute error of the harmonic C_V(T) (k_B per mode, on the 51-point grid "
+                         "over 0 .. 1000 cm^-1) of predicted against target DOS at the temperatures T in K, computed on the device "
+                         "(functionals.heat_capacity; evaluate.functionals_per_crystal)")
     param_groups.add_arguments(ap)
     args = ap.parse_args(argv)
+    args.cdf_loss = _parse_cdf(ap, args.cdf_loss)
+    if args.cdf_loss is not None and args.loss == "reference":
+        ap.error("--cdf-loss adds a term to the per-crystal losses: pick --loss crystal_rmse (the reference's own batch-1 objective), "
+                 "mse, mae or huber")
+    if args.report_heat_capacity is not None:
+        try:
+            args.report_heat_capacity = [float(t) for t in args.report_heat_capacity.split(",")]
+            assert args.report_heat_capacity and min(args.report_heat_capacity) > 0
+        except (ValueError, AssertionError):
+            ap.error("--report-heat-capacity T[,T...]: positive temperatures in K")
+        if args.eval_per_crystal <= 0 and args.embedder != "graphnetwork":
+            ap.error("--report-heat-capacity reads the per-crystal evaluator's outputs: pass --eval-per-crystal N")
     if args.balance_systems is not None and args.loss == "reference":
         ap.error("--balance-systems weighs the per-crystal losses: pick --loss crystal_rmse (the reference's own batch-1 objective), "
                  "mse, mae or huber")
@@ -260,9 +286,25 @@ def _ema_args(args):
     return dict(ema_decay=args.ema, ema_warmup=not args.no_ema_warmup)
 
 
-def _loss_args(args):
-    return dict(loss=None if args.loss == "reference" else args.loss, huber_delta=args.huber_delta,
-                sample_weights=args.balance_systems is not None)
+def _parse_cdf(ap, text):
+    """--cdf-loss LAM[,sq|abs] -> None or (lam, kind)"""
+    if text is None:
+        return None
+    parts = text.split(",")
+    try:
+        lam, kind = float(parts[0]), (parts[1] if len(parts) > 1 else "sq")
+        assert len(parts) <= 2 and kind in ("sq", "abs") and 0.0 <= lam < float("inf")
+    except (ValueError, AssertionError):
+        ap.error("--cdf-loss LAM[,sq|abs]: a finite weight >= 0 and, optionally, the kind")
+    return lam, kind
+
+
+def _loss_args(args, S=51):
+    kw = dict(loss=None if args.loss == "reference" else args.loss, huber_delta=args.huber_delta,
+              sample_weights=args.balance_systems is not None)
+    if args.cdf_loss is not None:          # the cumulative DOS on a grid of unit length: bin width 1 / S
+        kw.update(functionals=functionals.cumulative(S, 1.0 / S), functional_weight=args.cdf_loss[0], functional_kind=args.cdf_loss[1])
+    return kw
 
 
 def _ema_report(args, trainer, run_test, name):
@@ -314,7 +356,14 @@ def _tester(args, evaluator, ds):
     batch size 1) from passes of N crystals through a predictor with per-crystal keys; otherwise test_phonon over batches of
     --batch-size, whose R2 and means are those of the batches."""
     if args.eval_per_crystal > 0:
-        return lambda name: evaluate.test_per_crystal(evaluator, ds[name], batch_size=args.eval_per_crystal).as_reference()
+        def run(name):
+            res = evaluate.test_per_crystal(evaluator, ds[name], batch_size=args.eval_per_crystal)
+            if args.report_heat_capacity is not None:        # --report-heat-capacity: from the outputs still on the device
+                nu = torch.linspace(0.0, 1000.0, int(res.preds.shape[1]), dtype=torch.float64)
+                cv = evaluate.functionals_per_crystal(res, functionals.heat_capacity(nu, args.report_heat_capacity))
+                print(f"            {name} C_V mae " + "  ".join(f"{n} {e:.4g}" for n, e in zip(cv.names, cv.mae)))
+            return res.as_reference()
+        return run
     return lambda name: evaluate.test_phonon(evaluator, ds[name].batches(args.batch_size))
 
 

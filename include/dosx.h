@@ -1352,6 +1352,40 @@ int dosx_loss_rows_w_f64(const double* pg, const double* ps, const double* y, in
                          int clamp_target, double beta, double delta, double* dpg, double* dps, double* per_crystal, double* loss,
                          const double* w, const int32_t* w_index, const double* bin_w, dosx_stream_t stream);
 
+/* ---- linear functionals in the per-crystal losses (csrc/loss_functional.hip) ------------------------------------------------
+ * dosx_loss_rows_w / _w_f64 with a penalty on K linear functionals of the DOS next to the pointwise term: cumulative DOS (the
+ * Cramer / Wasserstein-1 distances), moments, windows, heat-capacity kernels - all one table fn_w [K,S], row-major, in the
+ * operands' type, F_k(p) = sum_s fn_w[k,s] p_s.  With t, r = p - t, f, beta, w_b, v_s and B_global exactly as above:
+ *   u_k(p_b) = sum_s fn_w[k,s] r_s                  (= F_k(p_b) - F_k(t_b); t is the clamped target under clamp_target)
+ *   h(p_b)   = (1 / K) sum_k e(u_k),   e(u) = u^2  (DOSX_FN_SQ)   or   |u|  (DOSX_FN_ABS)
+ *   l_b      = f(pg_b) + beta f(ps_b) + lam (h(pg_b) + beta h(ps_b))        (one-output models: l_b = f(pg_b) + lam h(pg_b))
+ *   per_crystal[b] = l_b      loss[0] = (1 / B_global) sum_b w_b l_b      dpg, dps = d loss[0] / d pg, d ps
+ * The gradient of the new term on element s is  coef lam / K sum_k e'(u_k) fn_w[k,s],  coef = w_b / B_global (times beta for ps),
+ * e'(u) = 2 u (SQ) or sign(u) (ABS) with sign(0) = 0 as torch.sign gives.  Bin weights v_s act on f only: the table carries its
+ * own weighting.  A lower-triangular table of ones times the bin width makes SQ the Cramer distance between the two cumulative
+ * DOS curves and ABS their Wasserstein-1 distance.  The rules of the entries above hold:
+ *   - w_b == 0: the crystal's rows are +0.0 and its share of loss[0] exactly 0 whatever it holds; per_crystal[b] is still its l_b
+ *   - a NaN / inf in crystal b reaches l_b, loss[0] and that crystal's rows, and no other crystal's rows
+ *   - an all-zero table row adds nothing; lam / K is ONE number formed on the host in the operands' type, so K -> 2 K with
+ *     lam -> 2 lam and K zero rows appended is the same call bit for bit
+ *   - every sum runs in a fixed order that depends on (S, K) alone - not on B or on where the crystal stands in the launch
+ *     (the order: the header comment of csrc/loss_functional.hip); no atomics, two runs are bitwise equal
+ * One wavefront per crystal; the residuals of both outputs, u_k and the gradient sums stay in registers, the table is read from
+ * global memory once per crystal, the rows are written once.  Launches as above (two with per_crystal, one without; the same
+ * bits).  Limits with a table: 1 <= S <= 512, 1 <= K <= 512.  fn_w == NULL or lam == 0: the dosx_loss_rows_w kernels, bit for
+ * bit (K is then not read).  Refused with -22 and a message that starts with the entry's name: everything dosx_loss_rows_w
+ * refuses; fn_kind outside the enumerators; lam not finite or < 0; with a table K < 1, K > 512, S > 512, or fn_w lying inside
+ * pg, ps, y, dpg or dps. */
+enum { DOSX_FN_SQ = 0, DOSX_FN_ABS = 1 };
+int dosx_loss_rows_fn(const float* pg, const float* ps, const float* y, int B, int S, int B_global, int kind, int clamp_target,
+                      float beta, float delta, float* dpg, float* dps, float* per_crystal, float* loss, const float* w,
+                      const int32_t* w_index, const float* bin_w, const float* fn_w, int K, int fn_kind, float lam,
+                      dosx_stream_t stream);
+int dosx_loss_rows_fn_f64(const double* pg, const double* ps, const double* y, int B, int S, int B_global, int kind,
+                          int clamp_target, double beta, double delta, double* dpg, double* dps, double* per_crystal, double* loss,
+                          const double* w, const int32_t* w_index, const double* bin_w, const double* fn_w, int K, int fn_kind,
+                          double lam, dosx_stream_t stream);
+
 /* ---- guarded optimizer step (csrc/step_guard.hip; the guarded AdamW entries: csrc/adamw.hip) ------------------------------
  * What a fused trainer has in place of `clip_grad_norm_` and of a GradScaler-style "skip if non-finite": one statistics launch
  * over the flat gradient, behind the recorded program and in front of the AdamW launch, and an AdamW that reads its verdict
@@ -1538,6 +1572,19 @@ int dosx_eval_metrics(const float* pred, const float* y, int B, int S, int clamp
                       dosx_stream_t stream);
 int dosx_eval_metrics_f64(const double* pred, const double* y, int B, int S, int clamp0, double* metrics, double* pred_out,
                           double* y_out, dosx_stream_t stream);
+
+/* ---- evaluation functionals (csrc/loss_functional.hip) ----------------------------------------------------------------------
+ * The integrated quantities a DOS is used through - cumulative DOS, band centre and width, states in a window, C_V(T) - of the
+ * predictions and targets evaluate.test_per_crystal leaves on the device: out [B,2,K] float64 holds F_k(pred_b) scale_b in
+ * out[b,0,k] and F_k(y_b) scale_b in out[b,1,k], F_k(p) = sum_s fn_w[k,s] p_s with fn_w [K,S] row-major in the operands' type.
+ * scale: NULL (1), or [B] float64 - e.g. the eDOS y_max that undoes the target's normalisation.  pred / y are taken as given.
+ * Products and sums in float64, one wavefront per row: lane l adds its elements l, l + 64, ... in rising order, one wave
+ * reduction per k - a fixed order that depends on (S, K) alone.  Any S, K >= 1; B = 0 is a no-op; S < 1, K < 1, B < 0 and a NULL
+ * pred / y / fn_w / out are refused with -22 and a message. */
+int dosx_eval_functionals(const float* pred, const float* y, int B, int S, const double* scale, const float* fn_w, int K,
+                          double* out, dosx_stream_t stream);
+int dosx_eval_functionals_f64(const double* pred, const double* y, int B, int S, const double* scale, const double* fn_w, int K,
+                              double* out, dosx_stream_t stream);
 
 const char* dosx_last_error(void);
 int dosx_version(void);
