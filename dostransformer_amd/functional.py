@@ -9,6 +9,7 @@ of ``2B`` "crystals" (branch-major inside the batch axis: bq = branch*B + b).
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import enum
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
@@ -872,15 +873,45 @@ def attention_form_fwd(rows: int, Sq: int, Bq: int, Nk: int, H: int, fdrop) -> A
     return AttForm.ROWS_IN_FFN if att_rows else AttForm.STANDALONE
 
 
-def attention_bwd_in_ffn(Sq: int, Bq: int, Nk: int, H: int, fdrop: bool) -> bool:
-    """Whether encoder_bwd runs a layer's attention backward inside its dosx_ffn_bwd launch (fdrop: the layer ran on the
-    relu / res dropout path, unfused).  Host-only, like attention_form_fwd."""
-    fused = ops.ffn_supported(H) and not fdrop
-    small = bool(_lib_load().dosx_attention_pkv_supported(int(Nk), int(H)))
+class FfnForm(enum.Enum):
+    """How the feed-forward half of an encoder layer runs, forward and backward (ffn_form)."""
+    ONE_LAUNCH = "one-launch"               # dosx_ffn_fwd / dosx_ffn_bwd: both GEMMs in one launch, the intermediate tile in LDS
+    GEMMS = "gemms"                         # the two-GEMM chain (hidden > 128)
+    DROPOUT = "dropout"                     # relu / res dropout: unfused, one explicit multiplier mask per dropout site
+
+
+def ffn_form(H: int, fdrop: bool) -> FfnForm:
+    """fdrop: relu / res dropout is on (forward) / the layer ran on that path (backward: EncoderLayer.fdrop_masks)."""
+    if fdrop:
+        return FfnForm.DROPOUT
+    return FfnForm.ONE_LAUNCH if ops.ffn_supported(H) else FfnForm.GEMMS
+
+
+class AttBwdForm(enum.Enum):
+    """Where the attention half of an encoder layer's backward runs (attention_form_bwd)."""
+    IN_FFN = "in-ffn"                       # inside the layer's dosx_ffn_bwd launch (DosxFfnBwd.att_*)
+    ONE_LAUNCH = "one-launch"               # one dosx_attention_bwd; the last workgroup of a key crystal sums its key gradient (dkv_cnt)
+    SPLIT = "split"                         # the dq half on the main stream, the dk + dv half behind it on the side stream
+
+
+def attention_form_bwd(Sq: int, Bq: int, Nk: int, H: int, fdrop: bool) -> AttBwdForm:
+    """The form encoder_bwd runs a layer's attention backward in (fdrop: the layer ran on the relu / res dropout path, unfused).
+    Host-only, like attention_form_fwd; derived when the backward runs, from the switches as they are then."""
+    # Nk <= 64 (atoms of a crystal, the 51 phonon bins): the dq kernel leaves every query tile's share of dK + dV in
+    # `kvp` and the dk+dv half is a small reduction over those partials; larger key sets (201 eDOS bins) stream the
+    # dS round trip through `dsc` into the dkv kernel
+    small = ops.attention_pkv_supported(Nk, H)
     # round 5: the attention half's backward INSIDE the feed-forward half's launch (crystal-aligned tiles, DosxFfnBwd.att_*):
     # the layer's backward is one launch and dL/dx1 never reaches HBM - while that grid is one round of workgroups
-    return bool(fused and small and _FUSED_ATT_BWD and ops.ffn_att_bwd_supported(H, Nk, Sq, Bq)
-                and ops.ffn_att_bwd_partial_rows(Sq, Bq) <= _ATT_ALIGNED_MAX_WGS)
+    if (ffn_form(H, fdrop) is FfnForm.ONE_LAUNCH and small and _FUSED_ATT_BWD and ops.ffn_att_bwd_supported(H, Nk, Sq, Bq)
+            and ops.ffn_att_bwd_partial_rows(Sq, Bq) <= _ATT_ALIGNED_MAX_WGS):
+        return AttBwdForm.IN_FFN
+    return AttBwdForm.ONE_LAUNCH if small else AttBwdForm.SPLIT
+
+
+def attention_bwd_in_ffn(Sq: int, Bq: int, Nk: int, H: int, fdrop: bool) -> bool:
+    """Whether encoder_bwd runs a layer's attention backward inside its dosx_ffn_bwd launch."""
+    return attention_form_bwd(Sq, Bq, Nk, H, fdrop) is AttBwdForm.IN_FFN
 
 
 # ---- fine-tuning: what a frozen set prunes from the backward programs.  Host-only policies on parameter NAMES; the frozen set
@@ -919,16 +950,149 @@ def first_encoder_cut(names, frozen) -> bool:
     return trunk_cut(names, frozen) and bool(first) and all(n in frozen for n in first)
 
 
+def _keys_unread_by(frozen, pre: str, layer: int) -> bool:
+    """The layer condition of the query-only attention backward: the layer's layer_norms.0 is frozen - that LayerNorm is applied
+    to the keys too, so its own gradient needs the key-side partial rows - and the encoder is not ``transformer_self``, whose keys
+    are its own inputs.  The trunk condition is the caller's (attention_query_only: on names; encoder_bwd: the views' cut_trunk)."""
+    ln = f"{pre}.layers.{layer}.layer_norms.0."
+    return pre != "transformer_self" and ln + "weight" in frozen and ln + "bias" in frozen
+
+
 def attention_query_only(names, frozen, pre: str, layer: int) -> bool:
     """Whether layer ``layer`` of the cross-attention encoder ``pre`` needs no key gradient: its keys come from a frozen trunk
-    (trunk_cut) AND its layer_norms.0 is frozen - that LayerNorm is applied to the keys too, so its own gradient needs the
-    key-side partial rows.  ``transformer_self`` never qualifies: its keys are its own inputs.  encoder_bwd then runs the
-    layer's attention backward in its query-only form: DosxFfnBwd.att_dkvhat == NULL inside dosx_ffn_bwd, DOSX_ATTN_BWD_DQ_HALF
-    with dkvhat == NULL as a complete dosx_attention_bwd call elsewhere."""
-    if pre not in ("transformer", "transformer_source") or not trunk_cut(names, frozen):
-        return False
-    ln = f"{pre}.layers.{layer}.layer_norms.0."
-    return ln + "weight" in frozen and ln + "bias" in frozen
+    (trunk_cut) AND _keys_unread_by holds.  encoder_bwd then runs the layer's attention backward in its query-only form:
+    DosxFfnBwd.att_dkvhat == NULL inside dosx_ffn_bwd, DOSX_ATTN_BWD_DQ_HALF with dkvhat == NULL as a complete
+    dosx_attention_bwd call elsewhere."""
+    return trunk_cut(names, frozen) and _keys_unread_by(frozen, pre, layer)
+
+
+# One function per FfnForm.  Each takes the layer's attention descriptor `a` (outputs x1 / probs / qstats / st1, key_ptr and the
+# attention dropout mask set) and the layer's record so far, launches the layer, and returns (x2, the completed record).
+def _fdrop_masks(dev, pre: str, t: int, rows: int, H: int, fdrop):
+    """The (res1, relu, res2) multiplier masks of layer t's relu / res dropout, one per site (None where its p is 0)."""
+    p_relu, p_res, fseed, fbase = fdrop
+
+    def draw(shape, p, k):
+        if p <= 0.0:
+            return None
+        m_ = _empty(dev, *shape)
+        ops.dropout_mask(m_, p, fseed, fbase + 3 * t + k)
+        if FDROP_MASK_LOG is not None:
+            FDROP_MASK_LOG.append((pre, t, ("res1", "relu", "res2")[k], m_))
+        return m_
+    return draw((rows, H), p_res, 0), draw((rows, 4 * H), p_relu, 1), draw((rows, H), p_res, 2)
+
+
+def _ffn_dropout_fwd(P: Params, lp: str, att: torch.Tensor, x: torch.Tensor, x1: torch.Tensor, st1: torch.Tensor, masks):
+    """x1 = x + att o M1 (+ its LayerNorm-1 statistics) ; hd = relu(fc1(LN1(x1))) o M2 ; x2 = x1 + fc2(hd) o M3  ->  (hd, x2):
+    the unfused layer behind its attention output, with explicit masks (encoder_fwd's DROPOUT form, encoder_kv_fwd)."""
+    (m1, m2, m3), dev, (rows, H) = masks, x1.device, x1.shape
+    ops.mask_residual(att, m1, x, x1, st1, rows, H)
+    h = _empty(dev, rows, 4 * H)
+    ops.gemm(rows, 4 * H, [seg(x1)], P[lp + ".fc1.weight"], h, pro=PRO_ROWLN, pro_gamma=P[lp + ".layer_norms.1.weight"],
+             pro_beta=P[lp + ".layer_norms.1.bias"], pro_stats=st1, bias=P[lp + ".fc1.bias"], act=ACT_RELU)
+    if m2 is not None:
+        ops.mask_residual(h, m2, None, h, None, rows, 4 * H)       # in place: h is the DROPPED activation from here on
+    y2, x2 = _empty(dev, rows, H), _empty(dev, rows, H)
+    ops.gemm(rows, H, [seg(h)], P[lp + ".fc2.weight"], y2, bias=P[lp + ".fc2.bias"])
+    ops.mask_residual(y2, m3, x1, x2, None, rows, H)
+    return h, x2
+
+
+def _final_ln_fwd(P: Params, pre: str, x: torch.Tensor, rows: int, H: int):
+    """An encoder's final LayerNorm as a launch of its own -> (output, FinalLN)."""
+    y, xhat, rstd = _empty(x.device, rows, H), _empty(x.device, rows, H), _empty(x.device, rows)
+    ops.layernorm(x, P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"], y, xhat, rstd, rows, H)
+    return y, FinalLN(xhat, rstd)
+
+
+def _layer_fwd_dropout(P: Params, pre: str, t: int, a: Attn, lyr: EncoderLayer, fdrop):
+    """FfnForm.DROPOUT: the attention kernel without its residual epilogue, then _ffn_dropout_fwd."""
+    dev, (rows, H) = lyr.x1.device, lyr.x1.shape
+    masks = _fdrop_masks(dev, pre, t, rows, H, fdrop)
+    a.flags |= ops.ATTN_NO_RESIDUAL                # out = the attention output alone
+    att = _empty(dev, rows, H)
+    a.out = att.data_ptr()
+    ops.attention_fwd(a)
+    assert lyr.qs == a.Bq and lyr.qb == 1, "relu / res dropout: dense query rows only (layers.TransformerEncoder)"
+    h, x2 = _ffn_dropout_fwd(P, f"{pre}.layers.{t}", att, lyr.x, lyr.x1, lyr.st1, masks)
+    return x2, lyr._replace(h=h, fdrop_masks=masks)
+
+
+def _layer_fwd_one_launch(P: Params, pre: str, t: int, a: Attn, lyr: EncoderLayer, att: AttForm, kvhat: torch.Tensor, key_ptr, stack,
+                          final_ln: bool, head: Optional[Head]):
+    """FfnForm.ONE_LAUNCH.  att: where the attention half runs - in front, as a launch of its own, or in the prologue of this
+    launch; the launch is then deferred to ``stack`` (encoder_fwd: ops.ffn_fwd_multi).  final_ln / head: this is the LAST layer and
+    the encoder's final LayerNorm / the model head runs in its row epilogue.  Returns (x2, record, the FinalLN it made or None)."""
+    lp = f"{pre}.layers.{t}"
+    x1, st1 = lyr.x1, lyr.st1
+    dev, (rows, H) = x1.device, x1.shape
+    att_fused = att is not AttForm.STANDALONE
+    if not att_fused:
+        if stack:                       # (this layer launches its attention on its own: what is pending goes first)
+            ops.ffn_fwd_multi(stack)
+            stack.clear()
+        ops.attention_fwd(a)
+    h = _empty(dev, rows, 4 * H)
+    x2 = _empty(dev, rows, H)
+    # both GEMMs of the feed-forward half in one launch (the 32 x 4H intermediate tile stays in LDS); the last
+    # layer also applies the encoder's final LayerNorm in its row epilogue
+    fin_fused = fin_args = None
+    if final_ln:
+        fin_fused = FinalLN(_empty(dev, rows, H), _empty(dev, rows))
+        fin_args = Head(P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"], fin_fused.xhat, fin_fused.rstd)
+    elif head is not None:
+        assert head_fused_fwd(H, t + 1) and head.w is not None
+        fin_args = head._replace(S=a.Sq, Bq=a.Bq)
+        x2 = None
+    att_args = None
+    if att_fused:
+        att_args = AttFwd(kvhat=kvhat, gamma0=P[lp + ".layer_norms.0.weight"], beta0=P[lp + ".layer_norms.0.bias"], Nk=a.Nk, Bk=a.Bk,
+                          Bq=a.Bq, Sq=a.Sq, qs=lyr.qs, qb=lyr.qb, probs=lyr.probs, qstats=lyr.qstats, x1=x1, st1=st1, mask=lyr.mask,
+                          aligned=att is AttForm.ALIGNED_IN_FFN, key_ptr=key_ptr)
+    ops.ffn_fwd(rows, H, lyr.x if att_fused else x1, None if att_fused else st1, P[lp + ".layer_norms.1.weight"],
+                P[lp + ".layer_norms.1.bias"], P[lp + ".fc1.weight"], P[lp + ".fc1.bias"], P[lp + ".fc2.weight"],
+                P[lp + ".fc2.bias"], h, x2, fin=fin_args, att=att_args, defer=stack if att_fused else None)
+    return x2, lyr._replace(h=h), fin_fused
+
+
+def _layer_fwd_gemms(P: Params, lp: str, a: Attn, lyr: EncoderLayer):
+    """FfnForm.GEMMS (hidden > 128; the in-ffn attention forms need the one-launch kernel: the attention half is stand-alone)."""
+    x1, st1 = lyr.x1, lyr.st1
+    dev, (rows, H) = x1.device, x1.shape
+    xln = None
+    if a.Nk <= 320:
+        # unfused feed-forward half (hidden > 128): the attention kernel also writes LN1 of its output rows - they are
+        # in its registers with their statistics - and fc1 reads a plain operand instead of normalising its A tile in the
+        # prologue of every one of its 4H / 128 column tiles (M = 25728: 163 -> 139 us, DosxAttn.ln1_out)
+        xln = _empty(dev, rows, H)
+        a.ln1_gamma, a.ln1_beta = P[lp + ".layer_norms.1.weight"].data_ptr(), P[lp + ".layer_norms.1.bias"].data_ptr()
+        a.ln1_out = xln.data_ptr()
+    ops.attention_fwd(a)
+    h = _empty(dev, rows, 4 * H)
+    x2 = _empty(dev, rows, H)
+
+    def ffn_rows(r0, r1):
+        if xln is not None and _bf16x3_ok(r1 - r0, 4 * H, H):
+            ops.gemm_bf16x3(xln[r0:r1], P[lp + ".fc1.weight"], h[r0:r1], bias=P[lp + ".fc1.bias"], act=ACT_RELU)
+        elif xln is not None:
+            ops.gemm(r1 - r0, 4 * H, [seg(xln[r0:r1])], P[lp + ".fc1.weight"], h[r0:r1], bias=P[lp + ".fc1.bias"], act=ACT_RELU)
+        else:
+            ops.gemm(r1 - r0, 4 * H, [seg(x1[r0:r1])], P[lp + ".fc1.weight"], h[r0:r1], pro=PRO_ROWLN,
+                     pro_gamma=P[lp + ".layer_norms.1.weight"], pro_beta=P[lp + ".layer_norms.1.bias"], pro_stats=st1[r0:r1],
+                     bias=P[lp + ".fc1.bias"], act=ACT_RELU)
+        if _bf16x3_ok(r1 - r0, H, 4 * H):
+            ops.gemm_bf16x3(h[r0:r1], P[lp + ".fc2.weight"], x2[r0:r1], bias=P[lp + ".fc2.bias"], res=x1[r0:r1])
+        else:
+            ops.gemm(r1 - r0, H, [seg(h[r0:r1])], P[lp + ".fc2.weight"], x2[r0:r1], bias=P[lp + ".fc2.bias"], res=x1[r0:r1])
+    mt = _ffn_tail_start(rows, H)
+    if mt:
+        # the rows beyond the last FULL round of 64-row tiles (25728 = 3 x 8192 + 1152) as their own two-GEMM chain on
+        # the side stream, next to the main rows instead of behind them as a fourth, 14 %-full round of workgroups
+        ops.concurrent(dev, lambda: ffn_rows(mt, rows), lambda: ffn_rows(0, mt))
+    else:
+        ffn_rows(0, rows)
+    return x2, lyr._replace(h=h, ln1=xln)    # (xln: the tail rows read it on the side stream)
 
 
 def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int, qb: int, kvhat: torch.Tensor,
@@ -953,15 +1117,12 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
         fdrop = None
     assert fdrop is None or head is None
     stack = [] if _FFN_MULTI else None      # round 6: the stack's layers in one launch when every layer is row-local (see below)
-    form = attention_form_fwd(rows, Sq, Bq, Nk, H, fdrop)
-    att_fused, att_aligned = form is not AttForm.STANDALONE, form is AttForm.ALIGNED_IN_FFN
+    att = attention_form_fwd(rows, Sq, Bq, Nk, H, fdrop)
+    ffn = ffn_form(H, fdrop is not None)
     for t in range(T):
         lp = f"{pre}.layers.{t}"
         g0, b0 = P[lp + ".layer_norms.0.weight"], P[lp + ".layer_norms.0.bias"]
-        x1 = _empty(dev, rows, H)
-        probs = _empty(dev, Bq, Sq, Nk)
-        qstats = _empty(dev, rows, 2)
-        st1 = _empty(dev, rows, 2)
+        x1, probs, qstats, st1 = _empty(dev, rows, H), _empty(dev, Bq, Sq, Nk), _empty(dev, rows, 2), _empty(dev, rows, 2)
         a = _attn_desc(Sq, Bq, Nk, Bk, H, qs, qb, x, kvhat, g0, b0)
         a.out, a.probs, a.qstats, a.out_stats = x1.data_ptr(), probs.data_ptr(), qstats.data_ptr(), st1.data_ptr()
         if key_ptr is not None:
@@ -974,110 +1135,23 @@ def encoder_fwd(P: Params, pre: str, x: torch.Tensor, Sq: int, Bq: int, qs: int,
             a.drop_mask = mask.data_ptr()
             if DROP_MASK_LOG is not None:
                 DROP_MASK_LOG.append((pre, t, mask))
-        fm = None
-        if fdrop is not None:
-            # relu / res dropout: x1 = x + attn o M1 ; hd = relu(fc1(LN1(x1))) o M2 ; x2 = x1 + fc2(hd) o M3
-            p_relu, p_res, fseed, fbase = fdrop
-
-            def draw(shape, p, k):
-                if p <= 0.0:
-                    return None
-                m_ = _empty(dev, *shape)
-                ops.dropout_mask(m_, p, fseed, fbase + 3 * t + k)
-                if FDROP_MASK_LOG is not None:
-                    FDROP_MASK_LOG.append((pre, t, ("res1", "relu", "res2")[k], m_))
-                return m_
-            m1, m2, m3 = draw((rows, H), p_res, 0), draw((rows, 4 * H), p_relu, 1), draw((rows, H), p_res, 2)
-            fm = (m1, m2, m3)
-            a.flags |= ops.ATTN_NO_RESIDUAL                # out = the attention output alone
-            att = _empty(dev, rows, H)
-            a.out = att.data_ptr()
-            ops.attention_fwd(a)
-            assert qs == Bq and qb == 1, "relu / res dropout: dense query rows only (layers.TransformerEncoder)"
-            ops.mask_residual(att, m1, x, x1, st1, rows, H)
-            h = _empty(dev, rows, 4 * H)
-            ops.gemm(rows, 4 * H, [seg(x1)], P[lp + ".fc1.weight"], h, pro=PRO_ROWLN,
-                     pro_gamma=P[lp + ".layer_norms.1.weight"], pro_beta=P[lp + ".layer_norms.1.bias"], pro_stats=st1,
-                     bias=P[lp + ".fc1.bias"], act=ACT_RELU)
-            if m2 is not None:
-                ops.mask_residual(h, m2, None, h, None, rows, 4 * H)       # in place: h is the DROPPED activation from here on
-            y2 = _empty(dev, rows, H)
-            ops.gemm(rows, H, [seg(h)], P[lp + ".fc2.weight"], y2, bias=P[lp + ".fc2.bias"])
-            x2 = _empty(dev, rows, H)
-            ops.mask_residual(y2, m3, x1, x2, None, rows, H)
-            lay.append(EncoderLayer(x, qs, qb, x1, probs, qstats, st1, h, mask, fm, None))
-            x, qs, qb = x2, Bq, 1
-            continue
-        xln = None
-        if not att_fused:
-            if stack:                       # (this layer launches its attention on its own: what is pending goes first)
-                ops.ffn_fwd_multi(stack)
-                stack.clear()
-            if not ops.ffn_supported(H) and Nk <= 320:
-                # unfused feed-forward half (hidden > 128): the attention kernel also writes LN1 of its output rows - they are
-                # in its registers with their statistics - and fc1 reads a plain operand instead of normalising its A tile in the
-                # prologue of every one of its 4H / 128 column tiles (M = 25728: 163 -> 139 us, DosxAttn.ln1_out)
-                xln = _empty(dev, rows, H)
-                a.ln1_gamma, a.ln1_beta = P[lp + ".layer_norms.1.weight"].data_ptr(), P[lp + ".layer_norms.1.bias"].data_ptr()
-                a.ln1_out = xln.data_ptr()
-            ops.attention_fwd(a)
-        h = _empty(dev, rows, 4 * H)
-        x2 = _empty(dev, rows, H)
-        if ops.ffn_supported(H):
-            # both GEMMs of the feed-forward half in one launch (the 32 x 4H intermediate tile stays in LDS); the last
-            # layer also applies the encoder's final LayerNorm in its row epilogue
-            fin_args = None
-            if final_ln and t == T - 1:
-                fin_fused = FinalLN(_empty(dev, rows, H), _empty(dev, rows))
-                fin_args = Head(P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"], fin_fused.xhat, fin_fused.rstd)
-            elif head is not None and t == T - 1:
-                assert not final_ln and head_fused_fwd(H, T) and head.w is not None
-                fin_args = head._replace(S=Sq, Bq=Bq)
-                x2 = None
-            att_args = None
-            if att_fused:
-                att_args = AttFwd(kvhat=kvhat, gamma0=g0, beta0=b0, Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=qs, qb=qb, probs=probs,
-                                  qstats=qstats, x1=x1, st1=st1, mask=mask, aligned=att_aligned, key_ptr=key_ptr)
-            ops.ffn_fwd(rows, H, x if att_fused else x1, None if att_fused else st1, P[lp + ".layer_norms.1.weight"],
-                        P[lp + ".layer_norms.1.bias"], P[lp + ".fc1.weight"], P[lp + ".fc1.bias"], P[lp + ".fc2.weight"],
-                        P[lp + ".fc2.bias"], h, x2, fin=fin_args, att=att_args, defer=stack if att_fused else None)
+        lyr = EncoderLayer(x, qs, qb, x1, probs, qstats, st1, None, mask, None, None)     # (h, fdrop_masks, ln1: the form's)
+        if ffn is FfnForm.DROPOUT:
+            x, lyr = _layer_fwd_dropout(P, pre, t, a, lyr, fdrop)
+        elif ffn is FfnForm.ONE_LAUNCH:
+            last = t == T - 1
+            x, lyr, fin_fused = _layer_fwd_one_launch(P, pre, t, a, lyr, att, kvhat, key_ptr, stack, final_ln and last, head if last else None)
         else:
-            def ffn_rows(r0, r1, x1=x1, st1=st1, h=h, x2=x2, lp=lp, xln=xln):
-                if xln is not None and _bf16x3_ok(r1 - r0, 4 * H, H):
-                    ops.gemm_bf16x3(xln[r0:r1], P[lp + ".fc1.weight"], h[r0:r1], bias=P[lp + ".fc1.bias"], act=ACT_RELU)
-                elif xln is not None:
-                    ops.gemm(r1 - r0, 4 * H, [seg(xln[r0:r1])], P[lp + ".fc1.weight"], h[r0:r1], bias=P[lp + ".fc1.bias"], act=ACT_RELU)
-                else:
-                    ops.gemm(r1 - r0, 4 * H, [seg(x1[r0:r1])], P[lp + ".fc1.weight"], h[r0:r1], pro=PRO_ROWLN,
-                             pro_gamma=P[lp + ".layer_norms.1.weight"], pro_beta=P[lp + ".layer_norms.1.bias"], pro_stats=st1[r0:r1],
-                             bias=P[lp + ".fc1.bias"], act=ACT_RELU)
-                if _bf16x3_ok(r1 - r0, H, 4 * H):
-                    ops.gemm_bf16x3(h[r0:r1], P[lp + ".fc2.weight"], x2[r0:r1], bias=P[lp + ".fc2.bias"], res=x1[r0:r1])
-                else:
-                    ops.gemm(r1 - r0, H, [seg(h[r0:r1])], P[lp + ".fc2.weight"], x2[r0:r1], bias=P[lp + ".fc2.bias"], res=x1[r0:r1])
-            mt = _ffn_tail_start(rows, H)
-            if mt:
-                # the rows beyond the last FULL round of 64-row tiles (25728 = 3 x 8192 + 1152) as their own two-GEMM chain on
-                # the side stream, next to the main rows instead of behind them as a fourth, 14 %-full round of workgroups
-                ops.concurrent(dev, lambda: ffn_rows(mt, rows), lambda: ffn_rows(0, mt))
-            else:
-                ffn_rows(0, rows)
-        lay.append(EncoderLayer(x, qs, qb, x1, probs, qstats, st1, h, mask, None, xln))    # (xln: the tail rows read it on the side stream)
-        x, qs, qb = x2, Bq, 1
+            x, lyr = _layer_fwd_gemms(P, lp, a, lyr)
+        lay.append(lyr)
+        qs, qb = Bq, 1
     if stack:
         # every transformer layer attends over the ORIGINAL keys (transformer.py:72-73): with the attention half inside the launch a
         # layer is row-local per tile, so the stack's layers run back to back in ONE launch (dosx_ffn_fwd_multi, two per launch)
         ops.ffn_fwd_multi(stack)
-    fin = None
-    if final_ln and fin_fused is not None:
-        fin = fin_fused                  # x already is the normalised output
-    elif final_ln:
-        y = _empty(dev, rows, H)
-        xhat = _empty(dev, rows, H)
-        rstd = _empty(dev, rows)
-        ops.layernorm(x, P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"], y, xhat, rstd, rows, H)
-        fin = FinalLN(xhat, rstd)
-        x = y
+    fin = fin_fused                      # (made by the last layer's launch: x already is the normalised output)
+    if final_ln and fin is None:
+        x, fin = _final_ln_fwd(P, pre, x, rows, H)
     return x, EncoderCtx(lay, fin, Sq, Bq, Nk, Bk, H, T, kvhat, key_ptr)
 
 
@@ -1101,6 +1175,216 @@ def head_fused_bwd(H: int, T: int) -> bool:
     return bool(ops.ffn_supported(H) and _FUSED_FIN_BWD and T > 0)
 
 
+def _add_ln(sink: GradSink, G: Params, key: str, part: torch.Tensor, n: int, ld: int, H: int) -> None:
+    """Queue the reductions of a LayerNorm's n partial rows [dgamma (H) | dbeta (H) | ...] of ``ld`` floats into G[key.weight / .bias]."""
+    sink.add(part, 0, G[key + ".weight"], n, ld, H)
+    sink.add(part, H, G[key + ".bias"], n, ld, H)
+
+
+def _final_ln_bwd(P: Params, G: Params, pre: str, ctx: EncoderCtx, dy: Optional[torch.Tensor], sink: GradSink, head: Optional[Head]):
+    """The backward of what follows an encoder's last layer: its final LayerNorm or, with ``head``, the model head.  Returns
+    (dx, fin): the gradient of the last layer's output and, when that backward rides in the last layer's ffn_bwd launch
+    (csrc/ffn.hip), its operands - dx = fin.dy is then written by that launch (_ffn_half_bwd_one_launch)."""
+    fin, Sq, Bq, H, T = ctx.fin, ctx.Sq, ctx.Bq, ctx.H, ctx.T
+    dev, rows = (dy if head is None else head.ddos).device, Sq * Bq
+    if head is not None:
+        assert dy is None and fin is None and head_fused_bwd(H, T) and head.w is not None and head.ddos is not None
+        dx = _empty(dev, rows, H)
+        return dx, head._replace(dy=dx, S=Sq, Bq=Bq)
+    if fin is None:
+        return dy, None
+    keys = (pre + ".layer_norm.weight", pre + ".layer_norm.bias")
+    last_one_launch = T > 0 and ffn_form(H, ctx.layers[T - 1].fdrop_masks is not None) is FfnForm.ONE_LAUNCH
+    if last_one_launch and _FUSED_FIN_BWD and dy.stride(1) == 1:
+        dx = _empty(dev, rows, H)
+        return dx, Head(P[keys[0]], P[keys[1]], fin.xhat, fin.rstd, dy=dx, keys=keys)
+    r32 = _rows32(rows)
+    part = sink.scratch(r32, 2 * H)
+    dx = _empty(dev, rows, H)
+    ops.layernorm_bwd(dy, fin.xhat, fin.rstd, P[keys[0]], dx, part, rows, H)
+    _add_ln(sink, G, pre + ".layer_norm", part, r32, 2 * H, H)
+    return dx, None
+
+
+# What the two halves of one encoder layer's backward share.  lp: the layer's parameter prefix; ctx / lay: the encoder's and the
+# layer's saved records; acc: DosxAttn.dkv_accumulate (0: this layer's key gradient overwrites dkvhat); q_only: the attention
+# half runs without its key gradient (attention_query_only).
+_LayerBwd = collections.namedtuple("_LayerBwd", "P G lp ctx lay sink dkvhat acc q_only")
+
+
+def _ffn_half_bwd_one_launch(L: _LayerBwd, dx: torch.Tensor, dy: Optional[torch.Tensor], fin: Optional[Head], in_ffn: bool) -> torch.Tensor:
+    """FfnForm.ONE_LAUNCH: both dgrad GEMMs + ReLU mask + LN1 backward + residual in one launch (csrc/ffn.hip).  dx: the gradient
+    of the layer's output x2.  fin (the last layer, _final_ln_bwd): the launch first makes dx from dy / fin.ddos.  in_ffn
+    (AttBwdForm.IN_FFN): the attention half rides in the launch too, and what comes back is the gradient of the layer's INPUT
+    instead of that of x1."""
+    P, G, lp, sink, Sq, Bq, H = L.P, L.G, L.lp, L.sink, L.ctx.Sq, L.ctx.Bq, L.ctx.H
+    dev, rows, h, x1, st1 = dx.device, Sq * Bq, L.lay.h, L.lay.x1, L.lay.st1
+    g1, b1 = P[lp + ".layer_norms.1.weight"], P[lp + ".layer_norms.1.bias"]
+    # fc2
+    _wgrad_linear(sink, G, lp + ".fc2.weight", lp + ".fc2.bias", rows, H, seg(dx), [seg(h)], keep=(dx,))
+    dh = _empty(dev, rows, 4 * H)
+    dx1 = _empty(dev, rows, H)
+    att_args, att_reductions = _att_half_bwd_in_ffn(L) if in_ffn else (None, None)
+    rgp = ops.ffn_att_bwd_partial_rows(Sq, Bq) if in_ffn else ops.ffn_bwd_partial_rows(rows)
+    pld = 2 * H if fin is None else (5 * H + 4 if fin.w is not None else 4 * H)
+    part = sink.scratch(rgp, pld)
+    ops.ffn_bwd(rows, H, dx if fin is None else dy, h, x1, st1, g1, P[lp + ".fc1.weight"], P[lp + ".fc2.weight"], dh,
+                None if in_ffn else dx1, part, fin=fin, att=att_args)
+    for i, key in enumerate(fin.keys if fin is not None else ()):      # LayerNorm weight, bias (, output weight, bias: one column)
+        sink.add(part, (2 + i) * H, G[key], rgp, pld, H if i < 3 else 1)
+    # fc1 (+ LN1 backward + residual: done by the launch above)
+    _wgrad_linear(sink, G, lp + ".fc1.weight", lp + ".fc1.bias", rows, 4 * H, seg(dh), [seg(x1)], keep=(dh,),
+                  pro=PRO_ROWLN, pro_gamma=g1, pro_beta=b1, pro_stats=st1)
+    _add_ln(sink, G, lp + ".layer_norms.1", part, rgp, pld, H)
+    if not in_ffn:
+        return dx1
+    att_reductions()
+    return att_args.dxin
+
+
+def _ffn_half_bwd_gemms(L: _LayerBwd, dx: torch.Tensor, bf16x3: bool = True) -> torch.Tensor:
+    """FfnForm.GEMMS, and FfnForm.DROPOUT with the layer's relu / res2 masks: the two dgrad GEMMs.  dx: the gradient of the
+    layer's output x2; returns that of x1.  bf16x3 False: never the opt-in split-bf16 GEMM (encoder_kv_bwd)."""
+    P, G, lp, sink, H = L.P, L.G, L.lp, L.sink, L.ctx.H
+    dev, rows, h, x1, st1, fm = dx.device, L.ctx.Sq * L.ctx.Bq, L.lay.h, L.lay.x1, L.lay.st1, L.lay.fdrop_masks
+    g1, b1 = P[lp + ".layer_norms.1.weight"], P[lp + ".layer_norms.1.bias"]
+    dx_res2 = dx                      # gradient of x2 (the residual path of the feed-forward half carries it unchanged)
+    if fm is not None and fm[2] is not None:           # x2 = x1 + y o M3: the fc2 output sees dx o M3
+        dy2 = _empty(dev, rows, H)
+        ops.mask_residual(dx, fm[2], None, dy2, None, rows, H)
+        dx = dy2
+    # fc2
+    _wgrad_linear(sink, G, lp + ".fc2.weight", lp + ".fc2.bias", rows, H, seg(dx), [seg(h)], keep=(dx,))
+    dh = _empty(dev, rows, 4 * H)
+    dx1 = _empty(dev, rows, H)
+    if bf16x3 and _bf16x3_ok(rows, 4 * H, H) and dx.is_contiguous():
+        ops.gemm_bf16x3(dx, P[lp + ".fc2.weight"], dh, w_layout=1, mask=h)
+    else:
+        ops.gemm(rows, 4 * H, [seg(dx)], P[lp + ".fc2.weight"], dh, w_layout=1, epi=EPI_RELU_MASK, aux=h)
+    if fm is not None and fm[1] is not None:       # h is the dropped activation: [h > 0] = [relu > 0][M2 > 0]; x 1/(1-p)
+        ops.mask_residual(dh, fm[1], None, dh, None, rows, 4 * H)
+    # fc1 (+ LN1 backward + residual)
+    # (the rows LN1(x1) that the forward's attention kernel may have left behind as a plain operand: measured 7.033 vs 7.036 ms - nothing)
+    _wgrad_linear(sink, G, lp + ".fc1.weight", lp + ".fc1.bias", rows, 4 * H, seg(dh), [seg(x1)], keep=(dh,),
+                  pro=PRO_ROWLN, pro_gamma=g1, pro_beta=b1, pro_stats=st1)
+    rgp = ops.gemm_partial_rows(rows, H, EPI_ROWLN_BWD)
+    part = sink.scratch(rgp, 2 * H)
+    ops.gemm(rows, H, [seg(dh)], P[lp + ".fc1.weight"], dx1, w_layout=1, epi=EPI_ROWLN_BWD, aux=x1, aux_stats=st1,
+             epi_gamma=g1, res=dx_res2, partials=part, partial_ld=2 * H)
+    _add_ln(sink, G, lp + ".layer_norms.1", part, rgp, 2 * H, H)
+    return dx1
+
+
+def _att_half_bwd_in_ffn(L: _LayerBwd):
+    """AttBwdForm.IN_FFN: operand construction only - the half rides in the layer's dosx_ffn_bwd launch
+    (_ffn_half_bwd_one_launch).  Returns (the launch's AttBwd, the reductions to queue behind the launch's own)."""
+    P, G, lp, lay, sink = L.P, L.G, L.lp, L.lay, L.sink
+    Sq, Bq, Nk, Bk, H = L.ctx.Sq, L.ctx.Bq, L.ctx.Nk, L.ctx.Bk, L.ctx.H
+    dev, q_only = L.dkvhat.device, L.q_only
+    nqt_al = ops.ffn_att_bwd_partial_rows(Sq, Bq) // Bq                    # query tiles per batch entry (16- or 32-row tiles)
+    # (query-only: the query-side rows only; nobody reduces them)
+    npart_a = Bq * nqt_al + (0 if q_only else Bk * ((Nk + 15) // 16))
+    part_a = sink.scratch(npart_a, 2 * H)
+    dxin_a = _empty(dev, Sq * Bq, H)
+    kvp_a = None if q_only else sink.scratch(Bq * nqt_al * Nk, H)
+    args = AttBwd(x=lay.x, kvhat=L.ctx.kvhat, gamma0=P[lp + ".layer_norms.0.weight"], beta0=P[lp + ".layer_norms.0.bias"], probs=lay.probs,
+                  qstats=lay.qstats, mask=lay.mask, dxin=dxin_a, partials_q=part_a.data_ptr(),
+                  partials_kv=None if q_only else part_a.data_ptr() + 4 * Bq * nqt_al * 2 * H, dkv_part=kvp_a,
+                  dkv_cnt=None if q_only else ops.COUNTERS.take(dev, Bk), dkvhat=None if q_only else L.dkvhat,
+                  accumulate=0 if q_only else L.acc, Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=lay.qs, qb=lay.qb, key_ptr=L.ctx.key_ptr)
+
+    def reductions():
+        if not q_only:      # (query-only: layer_norms.0 is frozen, its key-side partial rows do not exist)
+            _add_ln(sink, G, lp + ".layer_norms.0", part_a, npart_a, 2 * H, H)
+        sink.keep(lay.mask, lay.x)
+    return args, reductions
+
+
+def _att_bwd_operands(L: _LayerBwd, dx1: torch.Tensor, small: bool):
+    """The operands of a stand-alone dosx_attention_bwd (AttBwdForm.ONE_LAUNCH: small; SPLIT: not).  Returns (desc, dxin, dsc, finish):
+    desc(flags) makes a call's descriptor, finish() queues what follows the call(s) and returns the gradient of the layer's input."""
+    P, lp, lay, sink, q_only = L.P, L.lp, L.lay, L.sink, L.q_only
+    Sq, Bq, Nk, Bk, H, key_ptr = L.ctx.Sq, L.ctx.Bq, L.ctx.Nk, L.ctx.Bk, L.ctx.H, L.ctx.key_ptr
+    dev, rows = dx1.device, Sq * Bq
+    fm, mask = lay.fdrop_masks, lay.mask
+    nqt, nkt = (Sq + 31) // 32, (Nk + 31) // 32
+    npart = Bq * nqt + (0 if q_only else Bk * ((Nk + 15) // 16 if small else nkt))   # key-side partial rows: per 16 / 32 keys
+    part = sink.scratch(npart, 2 * H)
+    dxin = _empty(dev, rows, H)
+    # (query-only: the dq half alone is the whole call, include/dosx.h; dscores is the scratch of the streamed / general dq
+    #  kernels, the crystal-aligned one ignores it)
+    dsc = None if (small and not q_only) else _empty(dev, Bq, Sq, Nk)
+    kvp = sink.scratch(Bq * nqt * Nk, H) if (small and not q_only) else None
+    dout_att = dx1
+    if fm is not None:                 # x1 = x + attn o M1: the attention output sees dx1 o M1, x the plain dx1 (added below)
+        dout_att = _empty(dev, rows, H)
+        ops.mask_residual(dx1, fm[0], None, dout_att, None, rows, H)
+
+    def desc(flags):
+        a = _attn_desc(Sq, Bq, Nk, Bk, H, lay.qs, lay.qb, lay.x, L.ctx.kvhat, P[lp + ".layer_norms.0.weight"], P[lp + ".layer_norms.0.bias"])
+        a.probs, a.qstats = lay.probs.data_ptr(), lay.qstats.data_ptr()
+        a.dout, a.dx, a.dkvhat, a.dkv_accumulate = dout_att.data_ptr(), dxin.data_ptr(), None if q_only else L.dkvhat.data_ptr(), L.acc
+        if fm is not None:
+            flags |= ops.ATTN_NO_RESIDUAL
+        a.dscores, a.dkv_part, a.drop_mask = ops._p(dsc), ops._p(kvp), ops._p(mask)
+        a.partials_q, a.partials_kv = part.data_ptr(), None if q_only else part.data_ptr() + 4 * Bq * nqt * 2 * H
+        a.flags = flags
+        if key_ptr is not None:
+            a.key_ptr = key_ptr.data_ptr()
+        return a
+
+    def finish():       # behind the call(s): layer_norms.0's reductions and, on the relu / res dropout path, the residual sum
+        if not q_only:                     # (query-only: layer_norms.0 is frozen, its key-side partial rows do not exist)
+            _add_ln(sink, L.G, lp + ".layer_norms.0", part, npart, 2 * H, H)
+        if fm is None:
+            return dxin
+        sink.keep(dout_att)                # + the residual path of the attention half
+        dsum = _empty(dev, rows, H)
+        ops.mask_residual(dxin, None, dx1, dsum, None, rows, H)
+        return dsum
+    return desc, dxin, dsc, finish
+
+
+def _att_half_bwd_one_launch(L: _LayerBwd, dx1: torch.Tensor) -> torch.Tensor:
+    """AttBwdForm.ONE_LAUNCH.  dx1: the gradient of the attention half's output; returns that of the layer's input."""
+    desc, _, dsc, finish = _att_bwd_operands(L, dx1, True)
+    if L.q_only:
+        ops.attention_bwd(desc(ops.ATTN_BWD_DQ_HALF))
+        L.sink.keep(dsc, L.lay.mask)
+    else:
+        # ONE launch: every (query tile, crystal) workgroup publishes its share of dK + dV and the last one of a key
+        # crystal to arrive finishes that crystal's key gradient (include/dosx.h: DosxAttn.dkv_cnt) - no reduction
+        # launch, no side-stream round trip
+        a1 = desc(0)
+        a1.dkv_cnt = ops.COUNTERS.take(dx1.device, L.ctx.Bk)
+        ops.attention_bwd(a1)
+        L.sink.keep(L.lay.mask)
+    return finish()
+
+
+def _att_half_bwd_split(L: _LayerBwd, dx1: torch.Tensor, dkv_on_main: bool) -> torch.Tensor:
+    """AttBwdForm.SPLIT.  dkv_on_main: the caller consumes dkvhat right behind this layer (encoder_bwd: kv_needed_next, layer 0)."""
+    sink, mask = L.sink, L.lay.mask
+    desc, dxin, dsc, finish = _att_bwd_operands(L, dx1, False)
+    # dq (feeds the next layer's backward) on the main stream; dk+dv (feeds only the key-gradient
+    # consumers at the very end) on the side stream, in layer order so dkvhat accumulates in order
+    ops.attention_bwd(desc(ops.ATTN_BWD_DQ_HALF))
+    if L.q_only:
+        sink.keep(dsc, mask)
+    else:
+        a2 = desc(ops.ATTN_BWD_DKV_HALF)
+        if dkv_on_main:
+            # the caller consumes dkvhat right after this call: the LAST key-gradient kernel runs on the main stream
+            # (behind a join that is already satisfied - the earlier layers' reductions finished long ago) instead of
+            # bouncing main -> side -> main through two cross-queue events
+            sink.join()
+            ops.attention_bwd(a2)
+            sink.keep(dsc, mask)
+        else:
+            sink.on_side(lambda: ops.attention_bwd(a2), (dx1, dxin) + tuple(t_ for t_ in (dsc, mask) if t_ is not None))
+    return finish()
+
+
 def encoder_bwd(P: Params, G: Params, pre: str, ctx: EncoderCtx, dy: Optional[torch.Tensor], dkvhat: torch.Tensor, sink: GradSink,
                 dkv_fresh: bool = False, kv_needed_next: bool = False, head: Optional[Head] = None):
     """dy: grad of the encoder output (after the final LN if there is one).  Accumulates into dkvhat
@@ -1110,180 +1394,26 @@ def encoder_bwd(P: Params, G: Params, pre: str, ctx: EncoderCtx, dy: Optional[to
     (only when head_fused_bwd(H, T)): the encoder's output went through LN -> H->1 output layer (ops.ln_rowdot) and ddos is
     the gradient of that layer's output; their backward runs inside the last layer's ffn_bwd launch.
     Returns the gradient w.r.t. the (expanded [Sq*Bq, H]) query input."""
-    fin, Sq, Bq, Nk, Bk, H, T, kvhat, key_ptr = ctx.fin, ctx.Sq, ctx.Bq, ctx.Nk, ctx.Bk, ctx.H, ctx.T, ctx.kvhat, ctx.key_ptr
-    dev = kvhat.device
-    rows = Sq * Bq
-    r32 = _rows32(rows)
-    dx = dy
-    fused_all = ops.ffn_supported(H)
-    last_plain = T > 0 and ctx.layers[T - 1].fdrop_masks is None            # (a layer on the relu / res dropout path runs unfused)
-    fused = fused_all and last_plain
-    fin_fused = None        # the final LayerNorm's backward rides in the last layer's ffn_bwd launch (csrc/ffn.hip)
-    fin_keys = (pre + ".layer_norm.weight", pre + ".layer_norm.bias")
-    if head is not None:
-        assert dy is None and fin is None and head_fused_bwd(H, T)
-        assert head.w is not None and head.ddos is not None
-        fin_keys = head.keys
-        dx = _empty(dev, rows, H)
-        fin_fused = head._replace(dy=dx, S=Sq, Bq=Bq)
-    elif fin is not None and fused and _FUSED_FIN_BWD and T > 0 and dy.stride(1) == 1:
-        dx = _empty(dev, rows, H)
-        fin_fused = Head(P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"], fin.xhat, fin.rstd, dy=dx)
-    elif fin is not None:
-        part = sink.scratch(r32, 2 * H)
-        dx = _empty(dev, rows, H)
-        ops.layernorm_bwd(dy, fin.xhat, fin.rstd, P[pre + ".layer_norm.weight"], dx, part, rows, H)
-        sink.add(part, 0, G[pre + ".layer_norm.weight"], r32, 2 * H, H)
-        sink.add(part, H, G[pre + ".layer_norm.bias"], r32, 2 * H, H)
-    nqt, nkt = (Sq + 31) // 32, (Nk + 31) // 32
+    Sq, Bq, Nk, H, T = ctx.Sq, ctx.Bq, ctx.Nk, ctx.H, ctx.T
+    dx, fin_fused = _final_ln_bwd(P, G, pre, ctx, dy, sink, head)
     frozen, cut_trunk = frozen_of(G), bool(getattr(G, "cut_trunk", False))
     for t in reversed(range(T)):
-        lp = f"{pre}.layers.{t}"
         lay = ctx.layers[t]
-        x_in, qs, qb, x1, st1, h = lay.x, lay.qs, lay.qb, lay.x1, lay.st1, lay.h
-        probs, qstats, mask, fm = lay.probs, lay.qstats, lay.mask, lay.fdrop_masks
-        g1, b1 = P[lp + ".layer_norms.1.weight"], P[lp + ".layer_norms.1.bias"]
-        g0, b0 = P[lp + ".layer_norms.0.weight"], P[lp + ".layer_norms.0.bias"]
-        dx_res2 = dx                      # gradient of x2 (the residual path of the feed-forward half carries it unchanged)
-        if fm is not None and fm[2] is not None:           # x2 = x1 + y o M3: the fc2 output sees dx o M3
-            dy2 = _empty(dev, rows, H)
-            ops.mask_residual(dx, fm[2], None, dy2, None, rows, H)
-            dx = dy2
-        # fc2
-        _wgrad_linear(sink, G, lp + ".fc2.weight", lp + ".fc2.bias", rows, H, seg(dx), [seg(h)], keep=(dx,))
-        dh = _empty(dev, rows, 4 * H)
-        dx1 = _empty(dev, rows, H)
-        pld = 2 * H
-        fused = fused_all and fm is None
-        small = bool(_lib_load().dosx_attention_pkv_supported(int(Nk), int(H)))
-        att_in_ffn = attention_bwd_in_ffn(Sq, Bq, Nk, H, fdrop=fm is not None)
-        att_bwd_args = None
+        fdrop = lay.fdrop_masks is not None                 # (a layer on the relu / res dropout path runs unfused)
+        ffn, att = ffn_form(H, fdrop), attention_form_bwd(Sq, Bq, Nk, H, fdrop)
         # fine-tuning: keys from a frozen trunk under a frozen layer_norms.0 - no key gradient (attention_query_only; the trunk
         # condition is the views' own cut_trunk, decided when they were made)
-        q_only = bool(cut_trunk and pre != "transformer_self" and
-                      lp + ".layer_norms.0.weight" in frozen and lp + ".layer_norms.0.bias" in frozen)
-        if att_in_ffn and q_only:
-            nqt_al = ops.ffn_att_bwd_partial_rows(Sq, Bq) // Bq
-            part_a = sink.scratch(Bq * nqt_al, 2 * H)                          # (the query-side rows only; nobody reduces them)
-            dxin_a = _empty(dev, rows, H)
-            att_bwd_args = AttBwd(x=x_in, kvhat=kvhat, gamma0=g0, beta0=b0, probs=probs, qstats=qstats, mask=mask, dxin=dxin_a,
-                                  partials_q=part_a.data_ptr(), partials_kv=None, dkv_part=None, dkv_cnt=None, dkvhat=None,
-                                  accumulate=0, Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=qs, qb=qb, key_ptr=key_ptr)
-        elif att_in_ffn:
-            nqt_al = ops.ffn_att_bwd_partial_rows(Sq, Bq) // Bq                # query tiles per batch entry (16- or 32-row tiles)
-            npart_a = Bq * nqt_al + Bk * ((Nk + 15) // 16)
-            part_a = sink.scratch(npart_a, 2 * H)
-            dxin_a = _empty(dev, rows, H)
-            kvp_a = sink.scratch(Bq * nqt_al * Nk, H)
-            att_bwd_args = AttBwd(x=x_in, kvhat=kvhat, gamma0=g0, beta0=b0, probs=probs, qstats=qstats, mask=mask, dxin=dxin_a,
-                                  partials_q=part_a.data_ptr(), partials_kv=part_a.data_ptr() + 4 * Bq * nqt_al * 2 * H, dkv_part=kvp_a,
-                                  dkv_cnt=ops.COUNTERS.take(dev, Bk), dkvhat=dkvhat, accumulate=0 if (dkv_fresh and t == T - 1) else 1,
-                                  Nk=Nk, Bk=Bk, Bq=Bq, Sq=Sq, qs=qs, qb=qb, key_ptr=key_ptr)
-        if fused:           # both dgrad GEMMs + ReLU mask + LN1 backward + residual in one launch (csrc/ffn.hip)
-            rgp = ops.ffn_att_bwd_partial_rows(Sq, Bq) if att_in_ffn else ops.ffn_bwd_partial_rows(rows)
-            with_fin = fin_fused is not None and t == T - 1
-            pld = (5 * H + 4 if head is not None else 4 * H) if with_fin else 2 * H
-            part = sink.scratch(rgp, pld)
-            ops.ffn_bwd(rows, H, dy if with_fin else dx, h, x1, st1, g1, P[lp + ".fc1.weight"], P[lp + ".fc2.weight"], dh,
-                        None if att_in_ffn else dx1, part, fin=fin_fused if with_fin else None, att=att_bwd_args)
-            if with_fin:
-                sink.add(part, 2 * H, G[fin_keys[0]], rgp, pld, H)
-                sink.add(part, 3 * H, G[fin_keys[1]], rgp, pld, H)
-                if head is not None:
-                    sink.add(part, 4 * H, G[fin_keys[2]], rgp, pld, H)
-                    sink.add(part, 5 * H, G[fin_keys[3]], rgp, pld, 1)
+        q_only = cut_trunk and _keys_unread_by(frozen, pre, t)
+        L = _LayerBwd(P, G, f"{pre}.layers.{t}", ctx, lay, sink, dkvhat, 0 if (dkv_fresh and t == T - 1) else 1, q_only)
+        if ffn is FfnForm.ONE_LAUNCH:
+            dx = _ffn_half_bwd_one_launch(L, dx, dy, fin_fused if t == T - 1 else None, att is AttBwdForm.IN_FFN)
         else:
-            if _bf16x3_ok(rows, 4 * H, H) and dx.is_contiguous():
-                ops.gemm_bf16x3(dx, P[lp + ".fc2.weight"], dh, w_layout=1, mask=h)
-            else:
-                ops.gemm(rows, 4 * H, [seg(dx)], P[lp + ".fc2.weight"], dh, w_layout=1, epi=EPI_RELU_MASK, aux=h)
-            if fm is not None and fm[1] is not None:       # h is the dropped activation: [h > 0] = [relu > 0][M2 > 0]; x 1/(1-p)
-                ops.mask_residual(dh, fm[1], None, dh, None, rows, 4 * H)
-        # fc1 (+ LN1 backward + residual)
-        # (the rows LN1(x1) that the forward's attention kernel may have left behind as a plain operand: measured 7.033 vs 7.036 ms - nothing)
-        _wgrad_linear(sink, G, lp + ".fc1.weight", lp + ".fc1.bias", rows, 4 * H, seg(dh), [seg(x1)], keep=(dh,),
-                      pro=PRO_ROWLN, pro_gamma=g1, pro_beta=b1, pro_stats=st1)
-        if not fused:
-            rgp = ops.gemm_partial_rows(rows, H, EPI_ROWLN_BWD)
-            part = sink.scratch(rgp, 2 * H)
-            ops.gemm(rows, H, [seg(dh)], P[lp + ".fc1.weight"], dx1, w_layout=1, epi=EPI_ROWLN_BWD, aux=x1, aux_stats=st1,
-                     epi_gamma=g1, res=dx_res2, partials=part, partial_ld=2 * H)
-        sink.add(part, 0, G[lp + ".layer_norms.1.weight"], rgp, pld, H)
-        sink.add(part, H, G[lp + ".layer_norms.1.bias"], rgp, pld, H)
+            dx = _ffn_half_bwd_gemms(L, dx)
         # attention (+ LN0 backward on the query side + residual); key side accumulates into dkvhat
-        # Nk <= 64 (atoms of a crystal, the 51 phonon bins): the dq kernel leaves every query tile's share of dK + dV in
-        # `kvp` and the dk+dv half is a small reduction over those partials; larger key sets (201 eDOS bins) stream the
-        # dS round trip through `dsc` into the dkv kernel
-        if att_in_ffn:          # (the attention half ran inside the ffn_bwd launch above)
-            if not q_only:      # (query-only: layer_norms.0 is frozen, its key-side partial rows do not exist)
-                sink.add(part_a, 0, G[lp + ".layer_norms.0.weight"], npart_a, 2 * H, H)
-                sink.add(part_a, H, G[lp + ".layer_norms.0.bias"], npart_a, 2 * H, H)
-            sink.keep(mask, x_in)
-            dx = dxin_a
-            continue
-        npart = Bq * nqt + (0 if q_only else Bk * ((Nk + 15) // 16 if small else nkt))   # key-side partial rows: per 16 / 32 keys
-        part = sink.scratch(npart, 2 * H)
-        dxin = _empty(dev, rows, H)
-        # (query-only: the dq half alone is the whole call, include/dosx.h; dscores is the scratch of the streamed / general dq
-        #  kernels, the crystal-aligned one ignores it)
-        dsc = None if (small and not q_only) else _empty(dev, Bq, Sq, Nk)
-        kvp = sink.scratch(Bq * nqt * Nk, H) if (small and not q_only) else None
-        acc = 0 if (dkv_fresh and t == T - 1) else 1
-
-        dout_att = dx1
-        if fm is not None:                 # x1 = x + attn o M1: the attention output sees dx1 o M1, x the plain dx1 (added below)
-            dout_att = _empty(dev, rows, H)
-            ops.mask_residual(dx1, fm[0], None, dout_att, None, rows, H)
-
-        def desc(flags):
-            a = _attn_desc(Sq, Bq, Nk, Bk, H, qs, qb, x_in, kvhat, g0, b0)
-            a.probs, a.qstats = probs.data_ptr(), qstats.data_ptr()
-            a.dout, a.dx, a.dkvhat, a.dkv_accumulate = dout_att.data_ptr(), dxin.data_ptr(), None if q_only else dkvhat.data_ptr(), acc
-            if fm is not None:
-                flags |= ops.ATTN_NO_RESIDUAL
-            a.dscores = dsc.data_ptr() if dsc is not None else None
-            a.dkv_part = kvp.data_ptr() if kvp is not None else None
-            a.drop_mask = mask.data_ptr() if mask is not None else None
-            a.partials_q = part.data_ptr()
-            a.partials_kv = None if q_only else part.data_ptr() + 4 * Bq * nqt * 2 * H
-            a.flags = flags
-            if key_ptr is not None:
-                a.key_ptr = key_ptr.data_ptr()
-            return a
-        if q_only:
-            ops.attention_bwd(desc(ops.ATTN_BWD_DQ_HALF))
-            sink.keep(dsc, mask)
-        elif small:
-            # ONE launch: every (query tile, crystal) workgroup publishes its share of dK + dV and the last one of a key
-            # crystal to arrive finishes that crystal's key gradient (include/dosx.h: DosxAttn.dkv_cnt) - no reduction
-            # launch, no side-stream round trip
-            a1 = desc(0)
-            a1.dkv_cnt = ops.COUNTERS.take(dev, Bk)
-            ops.attention_bwd(a1)
-            sink.keep(mask)
-        else:
-            # dq (feeds the next layer's backward) on the main stream; dk+dv (feeds only the key-gradient
-            # consumers at the very end) on the side stream, in layer order so dkvhat accumulates in order
-            ops.attention_bwd(desc(ops.ATTN_BWD_DQ_HALF))
-            a2 = desc(ops.ATTN_BWD_DKV_HALF)
-            if kv_needed_next and t == 0:
-                # the caller consumes dkvhat right after this call: the LAST key-gradient kernel runs on the main stream
-                # (behind a join that is already satisfied - the earlier layers' reductions finished long ago) instead of
-                # bouncing main -> side -> main through two cross-queue events
-                sink.join()
-                ops.attention_bwd(a2)
-                sink.keep(dsc, mask)
-            else:
-                sink.on_side(lambda a2=a2: ops.attention_bwd(a2), (dx1, dxin) + tuple(t_ for t_ in (dsc, mask) if t_ is not None))
-        if not q_only:                     # (query-only: layer_norms.0 is frozen, its key-side partial rows do not exist)
-            sink.add(part, 0, G[lp + ".layer_norms.0.weight"], npart, 2 * H, H)
-            sink.add(part, H, G[lp + ".layer_norms.0.bias"], npart, 2 * H, H)
-        if fm is not None:                 # + the residual path of the attention half
-            sink.keep(dout_att)
-            dsum = _empty(dev, rows, H)
-            ops.mask_residual(dxin, None, dx1, dsum, None, rows, H)
-            dxin = dsum
-        dx = dxin
+        if att is AttBwdForm.ONE_LAUNCH:
+            dx = _att_half_bwd_one_launch(L, dx)
+        elif att is AttBwdForm.SPLIT:
+            dx = _att_half_bwd_split(L, dx, kv_needed_next and t == 0)
     return dx
 
 
@@ -1332,79 +1462,33 @@ def encoder_kv_fwd(P: Params, pre: str, x: torch.Tensor, xk: torch.Tensor, xv: t
                 DROP_MASK_LOG.append((pre, t, amask))
         att = _empty(dev, rows, H)
         ops.attn_pv(probs, amask, v, att, Sq, Bq, Nk, Bk, H)
-        m1 = m2 = m3 = None
-        if fdrop is not None:
-            p_relu, p_res, fseed, fbase = fdrop
-
-            def draw(shape, p, kk):
-                if p <= 0.0:
-                    return None
-                m_ = _empty(dev, *shape)
-                ops.dropout_mask(m_, p, fseed, fbase + 3 * t + kk)
-                if FDROP_MASK_LOG is not None:
-                    FDROP_MASK_LOG.append((pre, t, ("res1", "relu", "res2")[kk], m_))
-                return m_
-            m1, m2, m3 = draw((rows, H), p_res, 0), draw((rows, 4 * H), p_relu, 1), draw((rows, H), p_res, 2)
+        masks = _fdrop_masks(dev, pre, t, rows, H, fdrop) if fdrop is not None else (None, None, None)
         x1, st1 = _empty(dev, rows, H), _empty(dev, rows, 2)
-        ops.mask_residual(att, m1, x, x1, st1, rows, H)
-        h = _empty(dev, rows, 4 * H)
-        ops.gemm(rows, 4 * H, [seg(x1)], P[lp + ".fc1.weight"], h, pro=PRO_ROWLN, pro_gamma=P[lp + ".layer_norms.1.weight"],
-                 pro_beta=P[lp + ".layer_norms.1.bias"], pro_stats=st1, bias=P[lp + ".fc1.bias"], act=ACT_RELU)
-        if m2 is not None:
-            ops.mask_residual(h, m2, None, h, None, rows, 4 * H)
-        y2, x2 = _empty(dev, rows, H), _empty(dev, rows, H)
-        ops.gemm(rows, H, [seg(h)], P[lp + ".fc2.weight"], y2, bias=P[lp + ".fc2.bias"])
-        ops.mask_residual(y2, m3, x1, x2, None, rows, H)
-        lay.append(EncoderKVLayer(q, qh, qr, k, kh, kr, v, vh, vr, probs, amask, x1, st1, h, (m1, m2, m3)))
+        h, x2 = _ffn_dropout_fwd(P, lp, att, x, x1, st1, masks)
+        lay.append(EncoderKVLayer(q, qh, qr, k, kh, kr, v, vh, vr, probs, amask, x1, st1, h, masks))
         x = x2
     fin = None
     if final_ln:
-        y, xhat, rstd = _empty(dev, rows, H), _empty(dev, rows, H), _empty(dev, rows)
-        ops.layernorm(x, P[pre + ".layer_norm.weight"], P[pre + ".layer_norm.bias"], y, xhat, rstd, rows, H)
-        fin, x = FinalLN(xhat, rstd), y
+        x, fin = _final_ln_fwd(P, pre, x, rows, H)
     return x, EncoderKVCtx(lay, fin, Sq, Bq, Nk, Bk, H, T)
 
 
 def encoder_kv_bwd(P: Params, G: Params, pre: str, ctx, dy: torch.Tensor, sink: GradSink):
     """Returns (dx [Sq*Bq,H], dxk [Nk*Bk,H], dxv [Nk*Bk,H])."""
-    fin, Sq, Bq, Nk, Bk, H, T = ctx.fin, ctx.Sq, ctx.Bq, ctx.Nk, ctx.Bk, ctx.H, ctx.T
+    Sq, Bq, Nk, Bk, H, T = ctx.Sq, ctx.Bq, ctx.Nk, ctx.Bk, ctx.H, ctx.T
     dev = dy.device
     rows, krows = Sq * Bq, Nk * Bk
     r32, k32 = _rows32(rows), _rows32(krows)
-    dx = dy
-    if fin is not None:
-        part = sink.scratch(r32, 2 * H)
-        dx = _empty(dev, rows, H)
-        ops.layernorm_bwd(dy, fin.xhat, fin.rstd, P[pre + ".layer_norm.weight"], dx, part, rows, H)
-        sink.add(part, 0, G[pre + ".layer_norm.weight"], r32, 2 * H, H)
-        sink.add(part, H, G[pre + ".layer_norm.bias"], r32, 2 * H, H)
+    dx, _ = _final_ln_bwd(P, G, pre, ctx, dy, sink, None)      # (a launch of its own: every layer here carries masks, none is one launch)
     dxk = dxv = None
     for t in reversed(range(T)):
         lp = f"{pre}.layers.{t}"
         lay = ctx.layers[t]
         q, qh, qr, k, kh, kr, v, vh, vr = lay.q, lay.qh, lay.qr, lay.k, lay.kh, lay.kr, lay.v, lay.vh, lay.vr
-        probs, amask, x1, st1, h, (m1, m2, m3) = lay.probs, lay.amask, lay.x1, lay.st1, lay.h, lay.fdrop_masks
+        probs, amask, m1 = lay.probs, lay.amask, lay.fdrop_masks[0]
         g0 = P[lp + ".layer_norms.0.weight"]
-        g1, b1 = P[lp + ".layer_norms.1.weight"], P[lp + ".layer_norms.1.bias"]
-        dx2 = dx
-        dyf = dx2
-        if m3 is not None:
-            dyf = _empty(dev, rows, H)
-            ops.mask_residual(dx2, m3, None, dyf, None, rows, H)
-        _wgrad_linear(sink, G, lp + ".fc2.weight", lp + ".fc2.bias", rows, H, seg(dyf), [seg(h)], keep=(dyf,))
-        dh = _empty(dev, rows, 4 * H)
-        ops.gemm(rows, 4 * H, [seg(dyf)], P[lp + ".fc2.weight"], dh, w_layout=1, epi=EPI_RELU_MASK, aux=h)
-        if m2 is not None:
-            ops.mask_residual(dh, m2, None, dh, None, rows, 4 * H)
-        _wgrad_linear(sink, G, lp + ".fc1.weight", lp + ".fc1.bias", rows, 4 * H, seg(dh), [seg(x1)], keep=(dh,),
-                      pro=PRO_ROWLN, pro_gamma=g1, pro_beta=b1, pro_stats=st1)
-        rgp = ops.gemm_partial_rows(rows, H, EPI_ROWLN_BWD)
-        part = sink.scratch(rgp, 2 * H)
-        dx1 = _empty(dev, rows, H)
-        ops.gemm(rows, H, [seg(dh)], P[lp + ".fc1.weight"], dx1, w_layout=1, epi=EPI_ROWLN_BWD, aux=x1, aux_stats=st1,
-                 epi_gamma=g1, res=dx2, partials=part, partial_ld=2 * H)
-        sink.add(part, 0, G[lp + ".layer_norms.1.weight"], rgp, 2 * H, H)
-        sink.add(part, H, G[lp + ".layer_norms.1.bias"], rgp, 2 * H, H)
+        # the feed-forward half is encoder_bwd's two-GEMM one (no key gradient rides on it, no split-bf16 GEMM: the forward has none)
+        dx1 = _ffn_half_bwd_gemms(_LayerBwd(P, G, lp, ctx, lay, sink, None, 0, False), dx, bf16x3=False)
         datt = dx1
         if m1 is not None:
             datt = _empty(dev, rows, H)
@@ -1424,8 +1508,7 @@ def encoder_kv_bwd(P: Params, G: Params, pre: str, ctx, dy: torch.Tensor, sink: 
         ops.layernorm_bwd(dk, kh, kr, g0, dk_in, pk, krows, H)
         ops.layernorm_bwd(dv, vh, vr, g0, dv_in, pv, krows, H)
         for prt, n32 in ((pq, r32), (pk, k32), (pv, k32)):
-            sink.add(prt, 0, G[lp + ".layer_norms.0.weight"], n32, 2 * H, H)
-            sink.add(prt, H, G[lp + ".layer_norms.0.bias"], n32, 2 * H, H)
+            _add_ln(sink, G, lp + ".layer_norms.0", prt, n32, 2 * H, H)
         dsum = _empty(dev, rows, H)
         ops.mask_residual(dxq, None, dx1, dsum, None, rows, H)          # + the residual path of the attention half
         dx = dsum
@@ -1436,7 +1519,7 @@ def encoder_kv_bwd(P: Params, G: Params, pre: str, ctx, dy: torch.Tensor, sink: 
             ops.mask_residual(dk_in, None, dxk, nk_, None, krows, H)
             ops.mask_residual(dv_in, None, dxv, nv_, None, krows, H)
             dxk, dxv = nk_, nv_
-        sink.keep(datt, dv, dk, dq, dpd, ds, dxq, dk_in, dv_in, dx1, dyf)
+        sink.keep(datt, dv, dk, dq, dpd, ds, dxq, dk_in, dv_in, dx1)
     return dx, dxk, dxv
 
 
@@ -1671,6 +1754,44 @@ def dostransformer_fwd(P: Params, cfg: ModelCfg, g, m: GraphMeta, drop=None, per
     return dos, xL, ctx
 
 
+def _out_head_bwd(P: Params, G: Params, ctx, ddos: torch.Tensor, S: int, B2: int, H: int, sink: GradSink) -> torch.Tensor:
+    """Backward of the model head as a launch of its own (ops.ln_rowdot: the source encoder's LayerNorm + out_layer on [S * B2, H]
+    rows) -> the gradient of the source encoder's output."""
+    rows2 = S * B2
+    r32 = _rows32(rows2)
+    pld = 3 * H + 1
+    part = sink.scratch(r32, pld)
+    dx = _empty(ddos.device, rows2, H)
+    ops.ln_rowdot_bwd(ddos, ctx.xhat_f, ctx.rstd_f, P["transformer_source.layer_norm.weight"], P["transformer_source.layer_norm.bias"],
+                      P["out_layer.weight"], dx, part, S, B2, H)
+    sink.add(part, 0, G["transformer_source.layer_norm.weight"], r32, pld, H)
+    sink.add(part, H, G["transformer_source.layer_norm.bias"], r32, pld, H)
+    sink.add(part, 2 * H, G["out_layer.weight"], r32, pld, H)
+    sink.add(part, 3 * H, G["out_layer.bias"], r32, pld, 1)
+    return dx
+
+
+def _const_inputs_bwd(P: Params, G: Params, cfg: ModelCfg, S: int, B: int, dpre: torch.Tensor, R: torch.Tensor, dgraph: torch.Tensor,
+                      dprow: torch.Tensor, sysidx: torch.Tensor, cut: bool, need_prompt: bool, decoder=None):
+    """The heads' graph / prompt inputs are constant over the energy axis: reduce dpre over s first (R [2B, H]), then [B, H]
+    products - dgraph (not with ``cut``: the frozen trunk is its only consumer) and the prompt rows' gradient into their table
+    (``need_prompt``).  decoder = (m, dec_segs): ... and the decoder's input-gradient product behind them, returned."""
+    H, hp = cfg.H, cfg.H // 2
+    Wfc, Wfp = P["fc.weight"], P["fc_prompt.weight"]
+    ops.reduce_rows(dpre.data_ptr(), H, R.data_ptr(), H, 2 * B, S, 1, 2 * B, H)
+    if not cut:
+        ops.gemm(B, H, [seg(R[:B])], Wfc[:, H:2 * H], dgraph, w_layout=1)
+        ops.gemm(B, H, [seg(R[B:])], Wfp[:, H:2 * H], dgraph, w_layout=1, res=dgraph)
+    if need_prompt:
+        ops.gemm(B, hp, [seg(R[B:])], Wfp[:, 2 * H:], dprow, w_layout=1)
+        ops.embed_rows_bwd(dprow.data_ptr(), hp, sysidx, G[cfg.prompt_key], B, G[cfg.prompt_key].shape[0], hp)
+    if decoder is not None and not cut:
+        # the decoder's dgrad needs only dgraph: it runs here, off the main chain, and its pooled block is added to the
+        # node gradient by the dense-key backward launch (one launch on the main stream instead of three)
+        return decoder_dgrad(P, cfg, decoder[0], decoder[1], dgraph)
+    return None
+
+
 def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, ddos: torch.Tensor,
                        dx_ext: Optional[torch.Tensor], sink: GradSink, mid_hook=None) -> None:
     """Backward; ddos [2B,S] (rows [0,B): d dos_global, [B,2B): d dos_system); dx_ext: optional
@@ -1684,26 +1805,16 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
     nmax = m.n_max
     dev = ddos.device
     rows2 = S * 2 * B
-    r32 = _rows32(rows2)
     # fine-tuning (trunk_cut / first_encoder_cut above): a frozen trunk ends the program behind the first encoder's backward -
     # dx_ext reaches frozen parameters only and is dropped with it - and a frozen first encoder + energy table takes that away too
     frozen, cut, cut_first = frozen_of(G), bool(getattr(G, "cut_trunk", False)), bool(getattr(G, "cut_first", False))
-    gf, bf = P["transformer_source.layer_norm.weight"], P["transformer_source.layer_norm.bias"]
-    head = None
+    dx = head = None
     if head_fused_bwd(H, cfg.T) and ddos.is_contiguous():
         # output layer + final LayerNorm backward inside the source encoder's first ffn_bwd launch
-        dx = None
-        head = Head(gf, bf, xhat_f, rstd_f, w=P["out_layer.weight"], ddos=ddos,
-                    keys=("transformer_source.layer_norm.weight", "transformer_source.layer_norm.bias", "out_layer.weight", "out_layer.bias"))
+        head = Head(P["transformer_source.layer_norm.weight"], P["transformer_source.layer_norm.bias"], xhat_f, rstd_f, w=P["out_layer.weight"],
+                    ddos=ddos, keys=("transformer_source.layer_norm.weight", "transformer_source.layer_norm.bias", "out_layer.weight", "out_layer.bias"))
     else:
-        pld = 3 * H + 1
-        part = sink.scratch(r32, pld)
-        dx = _empty(dev, rows2, H)
-        ops.ln_rowdot_bwd(ddos, xhat_f, rstd_f, gf, bf, P["out_layer.weight"], dx, part, S, 2 * B, H)
-        sink.add(part, 0, G["transformer_source.layer_norm.weight"], r32, pld, H)
-        sink.add(part, H, G["transformer_source.layer_norm.bias"], r32, pld, H)
-        sink.add(part, 2 * H, G["out_layer.weight"], r32, pld, H)
-        sink.add(part, 3 * H, G["out_layer.bias"], r32, pld, 1)
+        dx = _out_head_bwd(P, G, ctx, ddos, S, 2 * B, H, sink)
     # key gradient of the two cross attentions (dense [nmax*B (+1 spare), H] layout): the first layer processed overwrites
     # every key row, so no zero fill; the spare row (dense slot of ghost nodes) is never read (dense_normalize_bwd's ghost_row)
     dkv = _empty(dev, nmax * B + 1, H)
@@ -1760,28 +1871,16 @@ def dostransformer_bwd(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, d
     # graph / prompt inputs are constant over the energy axis: reduce over s first, then a [2B,H] GEMM.  Their
     # consumers (decoder backward, prompt-embedding gradient) come after the first encoder's backward: side stream.
     dgraph = _empty(dev, B, H)
-    hp = H // 2
-    dprow = _empty(dev, B, hp)
+    dprow = _empty(dev, B, H // 2)
 
     need_prompt = table_needed(frozen, cfg.prompt_key)
     # (R also feeds the factored heads' B-row weight-gradient jobs)
     need_R = (not cut) or need_prompt or (heads_factored and ("fc.weight" not in frozen or "fc_prompt.weight" not in frozen))
 
-    def _const_inputs_bwd():
-        ops.reduce_rows(dpre.data_ptr(), H, R.data_ptr(), H, 2 * B, S, 1, 2 * B, H)
-        if not cut:
-            ops.gemm(B, H, [seg(R[:B])], Wfc[:, H:2 * H], dgraph, w_layout=1)
-            ops.gemm(B, H, [seg(R[B:])], Wfp[:, H:2 * H], dgraph, w_layout=1, res=dgraph)
-        if need_prompt:
-            ops.gemm(B, hp, [seg(R[B:])], Wfp[:, 2 * H:], dprow, w_layout=1)
-            ops.embed_rows_bwd(dprow.data_ptr(), hp, sysidx, G[cfg.prompt_key], B, G[cfg.prompt_key].shape[0], hp)
-        if not cut:
-            # the decoder's dgrad needs only dgraph: it runs here, off the main chain, and its pooled block is added to the
-            # node gradient by the dense-key backward launch below (one launch on the main stream instead of three)
-            box_d["dcat"] = decoder_dgrad(P, cfg, m, dec_segs, dgraph)
     box_d = {}
-    if need_R:
-        sink.on_side(_const_inputs_bwd, (dpre, R, dgraph, dprow))
+    if need_R:          # (with the decoder's dgrad behind it: dcat)
+        sink.on_side(lambda: box_d.update(dcat=_const_inputs_bwd(P, G, cfg, S, B, dpre, R, dgraph, dprow, sysidx, cut, need_prompt,
+                                                                 decoder=(m, dec_segs))), (dpre, R, dgraph, dprow))
     # first encoder (queries = energy embeddings broadcast over the batch)
     dX1 = None if cut_first else encoder_bwd(P, G, "transformer", c1, dE1, dkv, sink, kv_needed_next=True)
     # Every gradient of the transformer stacks, the heads and the embeddings is complete (or queued on the side
@@ -1883,21 +1982,12 @@ def _dostransformer_fwd_wide(P: Params, cfg: ModelCfg, g, m: GraphMeta, dr):
 def _dostransformer_bwd_wide(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, ctx, ddos: torch.Tensor,
                              dx_ext: Optional[torch.Tensor], sink: GradSink, mid_hook=None) -> None:
     ctrunk, c1, c2, c3, dec_segs, sysidx, prow = ctx.trunk, ctx.c1, ctx.c2, ctx.c3, ctx.dec_segs, ctx.sysidx, ctx.prow
-    dosin, a_g, a_s, xhat_f, rstd_f = ctx.dosin, ctx.a_g, ctx.a_s, ctx.xhat_f, ctx.rstd_f
+    dosin, a_g, a_s = ctx.dosin, ctx.a_g, ctx.a_s
     H, S, B, N = cfg.H, cfg.S, m.num_graphs, m.num_nodes
     nmax = m.n_max
     dev = ddos.device
     rows2 = S * 2 * B
-    r32 = _rows32(rows2)
-    pld = 3 * H + 1
-    part = sink.scratch(r32, pld)
-    dx = _empty(dev, rows2, H)
-    ops.ln_rowdot_bwd(ddos, xhat_f, rstd_f, P["transformer_source.layer_norm.weight"], P["transformer_source.layer_norm.bias"],
-                      P["out_layer.weight"], dx, part, S, 2 * B, H)
-    sink.add(part, 0, G["transformer_source.layer_norm.weight"], r32, pld, H)
-    sink.add(part, H, G["transformer_source.layer_norm.bias"], r32, pld, H)
-    sink.add(part, 2 * H, G["out_layer.weight"], r32, pld, H)
-    sink.add(part, 3 * H, G["out_layer.bias"], r32, pld, 1)
+    dx = _out_head_bwd(P, G, ctx, ddos, S, 2 * B, H, sink)
     dhs, dk3, dv3 = encoder_kv_bwd(P, G, "transformer_source", c3, dx, sink)
     ddosin, dk2, dv2 = encoder_kv_bwd(P, G, "transformer_self", c2, dhs, sink)
     dsum = _sum_rows(dev, [ddosin, dk2, dv2], rows2, H, sink)        # dosin is query, key and value of the self encoder
@@ -1917,16 +2007,9 @@ def _dostransformer_bwd_wide(P: Params, G: Params, cfg: ModelCfg, m: GraphMeta, 
         ops.gemm(S * B, H, [seg(dpre, rmap=map1)], Wfp[:, :H], dE1, w_layout=1, res=dE1)
     R = _empty(dev, 2 * B, H)                                        # graph / prompt inputs are constant over the energy axis
     dgraph = _empty(dev, B, H)
-    hp = H // 2
-    dprow = _empty(dev, B, hp)
+    dprow = _empty(dev, B, H // 2)
     if not cut or need_prompt:
-        ops.reduce_rows(dpre.data_ptr(), H, R.data_ptr(), H, 2 * B, S, 1, 2 * B, H)
-    if not cut:
-        ops.gemm(B, H, [seg(R[:B])], Wfc[:, H:2 * H], dgraph, w_layout=1)
-        ops.gemm(B, H, [seg(R[B:])], Wfp[:, H:2 * H], dgraph, w_layout=1, res=dgraph)
-    if need_prompt:
-        ops.gemm(B, hp, [seg(R[B:])], Wfp[:, 2 * H:], dprow, w_layout=1)
-        ops.embed_rows_bwd(dprow.data_ptr(), hp, sysidx, G[cfg.prompt_key], B, G[cfg.prompt_key].shape[0], hp)
+        _const_inputs_bwd(P, G, cfg, S, B, dpre, R, dgraph, dprow, sysidx, cut, need_prompt)
     sink.keep(R, dprow)
     if not cut_first:
         dX1, dk1, dv1 = encoder_kv_bwd(P, G, "transformer", c1, dE1, sink)

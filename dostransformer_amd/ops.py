@@ -581,6 +581,12 @@ def ffn_att_bwd_supported(H: int, Nk: int, Sq: int, Bq: int) -> bool:
     return bool(_lib.load().dosx_ffn_att_bwd_supported(int(H), int(Nk), int(Sq), int(Bq)))
 
 
+def attention_pkv_supported(Nk: int, H: int) -> bool:
+    """Whether dosx_attention_bwd keeps every query tile's share of dK + dV in ``dkv_part`` (small key sets) instead of
+    streaming the scores' gradient through ``dscores``."""
+    return bool(_lib.load().dosx_attention_pkv_supported(int(Nk), int(H)))
+
+
 def ffn_att_bwd_partial_rows(Sq: int, Bq: int) -> int:
     return _lib.load().dosx_ffn_att_bwd_partial_rows(int(Sq), int(Bq))
 

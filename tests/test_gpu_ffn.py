@@ -468,3 +468,55 @@ def test_encoder_stack_layers_in_one_launch(Sq, Bq, Nk, Bk, H, T, bcast, final):
             assert torch.equal(getattr(l0, name), getattr(l1, name)), name
     if final:
         assert torch.equal(c0.fin.xhat, c1.fin.xhat) and torch.equal(c0.fin.rstd, c1.fin.rstd)
+
+
+_FWD_ONE = ["dosx_ffn_fwd_multi"]
+_FWD_ATT = ["dosx_attention_fwd", "dosx_ffn_fwd"] * 2
+_FWD_DROPOUT = ["dosx_dropout_mask", "dosx_attention_fwd", "dosx_mask_residual", "dosx_gemm", "dosx_mask_residual", "dosx_gemm",
+                "dosx_mask_residual"] * 2 + ["dosx_layernorm"]
+_BWD_DROPOUT = ["dosx_layernorm_bwd"] + ["dosx_gemm", "dosx_mask_residual", "dosx_gemm", "dosx_mask_residual", "dosx_attention_bwd",
+                                         "dosx_mask_residual"] * 2
+
+
+@pytest.mark.parametrize("form,H,Nk,relu_drop,fwd,bwd", [
+    ("IN_FFN", 64, 12, 0.0, _FWD_ONE, ["dosx_ffn_bwd"] * 2),
+    ("ONE_LAUNCH", 32, 12, 0.0, _FWD_ONE, ["dosx_ffn_bwd", "dosx_attention_bwd"] * 2),
+    ("SPLIT", 64, 70, 0.0, _FWD_ATT, ["dosx_ffn_bwd", "dosx_attention_bwd", "dosx_attention_bwd"] * 2),
+    ("DROPOUT", 64, 12, 0.3, _FWD_DROPOUT, _BWD_DROPOUT)])
+def test_each_named_form_issues_its_entries(form, H, Nk, relu_drop, fwd, bwd):
+    """functional.ffn_form / attention_form_bwd name the program: a two-layer encoder (Sq 51, Bq 4, Bk 2), forward and backward
+    under ops.call_log(), at the smallest shapes that reach each form - the form is named beforehand, then the entries are the
+    form's.  Numerics are the oracle tests'; this pins name <-> launch list."""
+    from dostransformer_amd import functional as Fn
+    Sq, Bq, Bk, T = 51, 4, 2, 2
+    fdrop = relu_drop > 0.0
+    want_ffn = Fn.FfnForm.DROPOUT if fdrop else Fn.FfnForm.ONE_LAUNCH
+    want_att = Fn.AttBwdForm.ONE_LAUNCH if fdrop else Fn.AttBwdForm[form]
+    assert Fn.ffn_form(H, fdrop) is want_ffn and Fn.attention_form_bwd(Sq, Bq, Nk, H, fdrop) is want_att
+    assert Fn.attention_bwd_in_ffn(Sq, Bq, Nk, H, fdrop) == (form == "IN_FFN")
+    gen = torch.Generator().manual_seed(H + Nk)
+    P = {}
+    for t in range(T):
+        for k, shp in ((".layer_norms.0.weight", (H,)), (".layer_norms.0.bias", (H,)), (".layer_norms.1.weight", (H,)), (".layer_norms.1.bias", (H,)),
+                       (".fc1.weight", (4 * H, H)), (".fc1.bias", (4 * H,)), (".fc2.weight", (H, 4 * H)), (".fc2.bias", (H,))):
+            v = torch.randn(*shp, generator=gen) * (0.1 if "bias" in k else (shp[-1] ** -0.5 if len(shp) == 2 else 1.0))
+            P[f"e.layers.{t}" + k] = (1.0 + 0.1 * v if "layer_norms" in k and "weight" in k else v)
+    P["e.layer_norm.weight"], P["e.layer_norm.bias"] = 1 + 0.1 * torch.randn(H, generator=gen), 0.1 * torch.randn(H, generator=gen)
+    P = Fn.pack_params({k: v.to(DEV) for k, v in P.items()})
+    G = {k: torch.zeros_like(v) for k, v in P.items()}
+    x, dy = torch.randn(Sq * Bq, H, generator=gen).to(DEV), torch.randn(Sq * Bq, H, generator=gen).to(DEV)
+    kvhat = torch.randn(Nk * Bk, H, generator=gen).to(DEV)
+    dkv = torch.zeros(Nk * Bk, H, device=DEV)
+    seed = torch.tensor([11], dtype=torch.int64, device=DEV)
+    o = ops()
+    with o.call_log() as names_fwd:
+        y, ctx = Fn.encoder_fwd(P, "e", x, Sq, Bq, Bq, 1, kvhat, Nk, Bk, H, T, fdrop=(relu_drop, 0.0, seed, 1000) if fdrop else None)
+    sink = o.GradSink(x.device)
+    with o.call_log() as names_bwd:
+        dx = Fn.encoder_bwd(P, G, "e", ctx, dy, dkv, sink)
+    sink.flush()
+    sink.release()
+    torch.cuda.synchronize()
+    assert names_fwd == fwd and names_bwd == bwd, (names_fwd, names_bwd)
+    assert bool(torch.isfinite(y).all()) and bool(torch.isfinite(dx).all()) and bool(dkv.abs().sum() > 0)
+    assert all(bool(G[k].abs().sum() > 0) for k in G), [k for k in G if not bool(G[k].abs().sum() > 0)]

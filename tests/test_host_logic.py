@@ -325,6 +325,47 @@ def test_attention_forms_at_the_baseline_encoder_shapes():
         assert not Fn.attention_bwd_in_ffn(Sq, Bq, Nk, H, fdrop=False)
 
 
+def test_backward_forms_at_the_baseline_encoder_shapes():
+    """functional.attention_form_bwd / ffn_form name what encoder_bwd dispatches on.  Expected values: the booleans the unnamed
+    code computed (attention_bwd_in_ffn, dosx_attention_pkv_supported), evaluated on the CPU build.  The Phonon-DOS step runs
+    every attention backward inside its layer's dosx_ffn_bwd; hidden 256 splits the 201-key self attention and runs the 30-key
+    cross attentions as one launch; relu / res dropout never rides in the feed-forward launch."""
+    from dostransformer_amd import functional as Fn, ops
+    A, F = Fn.AttBwdForm, Fn.FfnForm
+    shapes = {"phonon cross": ((51, 64, 12, 128), A.IN_FFN, A.ONE_LAUNCH), "phonon self": ((51, 128, 51, 128), A.IN_FFN, A.ONE_LAUNCH),
+              "phonon source": ((51, 128, 12, 128), A.IN_FFN, A.ONE_LAUNCH), "edos cross": ((201, 64, 30, 256), A.ONE_LAUNCH, A.ONE_LAUNCH),
+              "edos self": ((201, 128, 201, 256), A.SPLIT, A.SPLIT), "edos source": ((201, 128, 30, 256), A.ONE_LAUNCH, A.ONE_LAUNCH)}
+    for name, ((Sq, Bq, Nk, H), want, want_fdrop) in shapes.items():
+        assert Fn.attention_form_bwd(Sq, Bq, Nk, H, False) is want, name
+        assert Fn.attention_form_bwd(Sq, Bq, Nk, H, True) is want_fdrop, name
+    assert ops.attention_pkv_supported(30, 256) and not ops.attention_pkv_supported(201, 256)
+    assert [Fn.ffn_form(H, False) for H in (32, 64, 128, 256, 512)] == [F.ONE_LAUNCH] * 3 + [F.GEMMS] * 2
+    assert all(Fn.ffn_form(H, True) is F.DROPOUT for H in (32, 128, 256))
+    # (Sq, Bq) on either side of the 256-workgroup bound of the in-ffn form; key counts around the 16- and 64-key limits
+    assert ops.ffn_att_bwd_partial_rows(51, 64) == Fn._ATT_ALIGNED_MAX_WGS < ops.ffn_att_bwd_partial_rows(51, 400)
+    for H in (32, 64, 128, 256):
+        for Nk in (1, 16, 17, 64, 65, 201):
+            for Sq, Bq in ((51, 64), (51, 400)):
+                for fdrop in (False, True):
+                    form = Fn.attention_form_bwd(Sq, Bq, Nk, H, fdrop)
+                    assert Fn.attention_bwd_in_ffn(Sq, Bq, Nk, H, fdrop) == (form is A.IN_FFN), (H, Nk, Sq, Bq, fdrop)
+                    assert (form is A.IN_FFN) == (H in (64, 128) and Nk <= 64 and Bq == 64 and not fdrop), (H, Nk, Sq, Bq, fdrop)
+                    assert (form is A.SPLIT) == (Nk > 64), (H, Nk, Sq, Bq, fdrop)
+    with Fn.forms(_FUSED_ATT_BWD=False):                      # (derived when asked, from the switches as they are then)
+        assert Fn.attention_form_bwd(51, 64, 12, 128, False) is A.ONE_LAUNCH
+    # one query-only rule: the layer condition is shared, the trunk condition is each caller's
+    names = [f"{p}.layers.{t}.layer_norms.0.{w}" for p in ("transformer", "transformer_self", "transformer_source") for t in range(2)
+             for w in ("weight", "bias")] + ["GN_encoder.node_encoder.0.weight", "stacked_processor.0.x", "GN_decoder.0.weight"]
+    trunk = frozenset(n for n in names if n.startswith(Fn._TRUNK))
+    for pre in ("transformer", "transformer_self", "transformer_source"):
+        ln0 = frozenset(f"{pre}.layers.1.layer_norms.0.{w}" for w in ("weight", "bias"))
+        for frozen in (trunk | ln0, ln0, trunk, trunk | {sorted(ln0)[0]}):
+            for t in range(2):
+                layer = Fn._keys_unread_by(frozen, pre, t)
+                assert layer == (pre != "transformer_self" and t == 1 and ln0 <= frozen), (pre, t, sorted(frozen))
+                assert Fn.attention_query_only(names, frozen, pre, t) == (Fn.trunk_cut(names, frozen) and layer), (pre, t, sorted(frozen))
+
+
 def test_forms_scope_sets_and_restores_the_policy_globals():
     """functional.forms: the override scope of the tests - restores on normal exit and on an exception, a nested scope hands back
     the OUTER scope's value, and a name that is not one of the module's policy globals is refused (nothing set)."""
