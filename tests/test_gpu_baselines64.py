@@ -10,12 +10,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.f64_ref import SENT, check_sum, guarded as _guarded
 from tests.util import batch_from, load, maxabs, rmse, sub
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-SENT = 12345.0
-U64 = 2.0 ** -53
 SLOPE = 0.01
 L_ = 3
 BUCKET = (8, 128)
@@ -69,14 +68,6 @@ def _reference(e1, c, w2, b2, ddos):
     return ref, mag
 
 
-def _guarded(*shape):
-    """A NaN-filled contiguous float64 buffer, 16-byte aligned, between two sentinel pairs; -> (view, whole allocation)."""
-    n = int(np.prod(shape))
-    whole = torch.full((n + 4,), SENT, dtype=torch.float64, device=DEV)
-    whole[2:2 + n] = float("nan")
-    return whole[2:2 + n].view(*shape), whole
-
-
 def _run_kernels(e1, c, w2, b2, ddos):
     o = _ops()
     S, H = e1.shape
@@ -106,12 +97,7 @@ def test_pair_head64_kernels_against_long_double(S, B, H):
     got = _run_kernels(*operands)
     ref, mag = _reference(*operands)
     n = dict(dos=H, de1=B, dc=S, dw2=S * B, db2=S * B)
-    worst = {}
-    for k in ref:
-        err = np.abs(got[k].cpu().numpy().astype(np.longdouble) - ref[k])
-        bound = np.longdouble((n[k] + 4) * U64) * mag[k]
-        worst[k] = float(np.max(err / np.maximum(bound, np.finfo(np.longdouble).tiny)))
-        assert bool(np.all(err <= bound)), (k, worst[k])
+    worst = {k: check_sum(got[k], ref[k], mag[k], n[k]) for k in ref}           # asserts the bound per element
     print(f"pair_head64 S{S} B{B} H{H}: worst error / bound " + ", ".join(f"{k} {w:.3f}" for k, w in worst.items()))
     again = _run_kernels(*operands)
     assert all(torch.equal(got[k], again[k]) for k in got)                   # fixed summation order: bitwise run to run

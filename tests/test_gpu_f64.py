@@ -1,5 +1,6 @@
 """float64 program on a real MI355X (csrc/f64.hip, dostransformer_amd/functional64.py): the kernels against float64 torch,
-and Graphnetwork_phonon in float64 against the reference's fixture and the float64 oracle."""
+and Graphnetwork_phonon in float64 against the reference's fixture and the float64 oracle.  The edges of the elementwise, row
+and graph kernels (tails, strides, absent operands, the grid cap) against long double: tests/test_gpu_f64_kernels.py."""
 import math
 
 import pytest
