@@ -223,6 +223,9 @@ def functionals_per_crystal(result: PerCrystalResult, fn, scale=None) -> Functio
     from . import functionals as _fn
     from . import ops
     fn = _fn.as_functionals(fn)
+    if fn.norm_rows:
+        raise ValueError("functionals_per_crystal: the table has normalised rows, which only the loss divides - report a ratio through "
+                         "the plain table's declared ratios (functionals.moments: centre = m1 / m0)")
     preds, ys = result.preds, result.y
     C, S = int(preds.shape[0]), int(preds.shape[1])
     if fn.S != S:

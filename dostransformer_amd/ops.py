@@ -1715,7 +1715,7 @@ FUNCTIONAL_MAX = 512               # K and S of a table in the loss
 
 def _loss_rows(who: str, dt: torch.dtype, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global,
                weights=None, weight_index=None, bin_weights=None, functionals=None, functional_kind="sq",
-               functional_weight=1.0) -> None:
+               functional_weight=1.0, functional_denominator=None, functional_norm_rows=0, functional_floor=None) -> None:
     if isinstance(kind, str):
         if kind not in LOSS_KINDS:
             raise ValueError(f"{who}: kind {kind!r} is not one of {sorted(LOSS_KINDS)}")
@@ -1745,6 +1745,13 @@ def _loss_rows(who: str, dt: torch.dtype, pg, ps, y, kind, clamp_target, beta, d
             loss.data_ptr())
     work = lambda: ("loss_rows", "loss_rows_kernel", "hbm", (2.0 if ps is None else 3.0) * pg.element_size() * 2 * B * S,
                     1 if per_crystal is None else 2)
+    norm_rows = int(functional_norm_rows)
+    if norm_rows < 0:
+        raise ValueError(f"{who}: functional_norm_rows must be >= 0, got {functional_norm_rows}")
+    if norm_rows == 0 and (functional_denominator is not None or functional_floor is not None):
+        raise ValueError(f"{who}: functional_denominator / functional_floor belong to functional_norm_rows > 0 normalised rows")
+    if norm_rows > 0 and functionals is None:
+        raise ValueError(f"{who}: functional_norm_rows={norm_rows} without functionals: there is no table whose rows they could be")
     if weights is None and weight_index is None and bin_weights is None and functionals is None:   # today's callers issue today's launch
         _call("dosx_loss_rows" if dt == torch.float32 else "dosx_loss_rows_f64", *args, _stream(), w=work)
         return
@@ -1793,6 +1800,27 @@ def _loss_rows(who: str, dt: torch.dtype, pg, ps, y, kind, clamp_target, beta, d
     K = int(functionals.shape[0])
     fwork = lambda: ("loss_rows_fn", "loss_fn_kernel", "hbm", (2.0 if ps is None else 3.0) * pg.element_size() * 2 * B * S
                      + pg.element_size() * K * S, 1 if per_crystal is None else 2)
+    if norm_rows > 0:                  # the last norm_rows rows over the floored denominator functional: the normalised entry
+        den = functional_denominator
+        if norm_rows > K:
+            raise ValueError(f"{who}: functional_norm_rows={norm_rows} of a table of K = {K} rows")
+        if den is None or den.dtype != dt or not den.is_cuda:
+            raise TypeError(f"{who}: functional_denominator must be a {dt} CUDA tensor, got "
+                            f"{'None' if den is None else f'{den.dtype} on {den.device}'}")
+        if den.dim() != 1 or den.numel() != S or not den.is_contiguous():
+            raise ValueError(f"{who}: functional_denominator must be a contiguous [S] = [{S}] tensor, got shape {tuple(den.shape)} "
+                             f"strides {den.stride()}")
+        if functional_floor is None or not 0.0 < float(functional_floor) < float("inf"):
+            raise ValueError(f"{who}: functional_floor must be finite and > 0, got {functional_floor}")
+        d = _abi.FnNorm()
+        d.fn_w, d.fn_den, d.K, d.K_norm, d.fn_kind = functionals.data_ptr(), den.data_ptr(), K, norm_rows, int(functional_kind)
+        d.lam, d.den_floor = lam, float(functional_floor)
+        nwork = lambda: ("loss_rows_fn_norm", "loss_fnn_kernel", "hbm", (2.0 if ps is None else 3.0) * pg.element_size() * 2 * B * S
+                         + pg.element_size() * (K + 1) * S, 1 if per_crystal is None else 2)
+        # the descriptor form: a recorded call carries at most 19 integer-class arguments (include/dosx.h: DosxFnNorm)
+        _call("dosx_loss_rows_fn_norm_desc" if dt == torch.float32 else "dosx_loss_rows_fn_norm_desc_f64", *args, _p(weights),
+              _p(weight_index), _p(bin_weights), C.byref(d), _stream(), w=nwork)
+        return
     _call("dosx_loss_rows_fn" if dt == torch.float32 else "dosx_loss_rows_fn_f64", *args, _p(weights), _p(weight_index),
           _p(bin_weights), functionals.data_ptr(), K, int(functional_kind), lam, _stream(), w=fwork)
 
@@ -1802,7 +1830,8 @@ def loss_rows(pg: torch.Tensor, ps: Optional[torch.Tensor], y: torch.Tensor, kin
               per_crystal: Optional[torch.Tensor] = None, loss: torch.Tensor, B_global: Optional[int] = None,
               weights: Optional[torch.Tensor] = None, weight_index: Optional[torch.Tensor] = None,
               bin_weights: Optional[torch.Tensor] = None, functionals: Optional[torch.Tensor] = None,
-              functional_kind="sq", functional_weight: float = 1.0) -> None:
+              functional_kind="sq", functional_weight: float = 1.0, functional_denominator: Optional[torch.Tensor] = None,
+              functional_norm_rows: int = 0, functional_floor: Optional[float] = None) -> None:
     """Per-crystal loss of the [B,S] predictions pg (and ps) against y with its gradient (include/dosx.h: dosx_loss_rows):
     ``l_b = f(pg_b) + beta f(ps_b)`` with f the crystal's RMSE, MSE, MAE or Huber(``delta``) term - ``kind`` a key of
     :data:`LOSS_KINDS` or its enumerator -, ``per_crystal[b] = l_b`` (optional), ``loss[0] = sum_b l_b / B_global`` (default B) and
@@ -1819,9 +1848,17 @@ def loss_rows(pg: torch.Tensor, ps: Optional[torch.Tensor], y: torch.Tensor, kin
     functionals ``F_k(p) = sum_s table[k,s] p_s`` (K, S <= 512) whose differences ``u_k = F_k(p_b) - F_k(t_b)`` add
     ``functional_weight / K * sum_k e(u_k)`` to each output's term, ``e(u) = u^2`` (``"sq"``) or ``|u|`` (``"abs"``) - the same
     launch, the rows written once.  ``per_crystal[b]`` includes the term.  Without a table the call is the one it was; with a
-    table and ``functional_weight == 0`` the library runs the weighted kernels, bit for bit."""
+    table and ``functional_weight == 0`` the library runs the weighted kernels, bit for bit.
+
+    ``functional_denominator`` / ``functional_norm_rows`` / ``functional_floor`` (include/dosx.h: dosx_loss_rows_fn_norm): the LAST
+    ``functional_norm_rows`` rows of the table are divided by ``D+ = max(sum_s functional_denominator[s] x_s, functional_floor)`` on
+    both sides, ``u_k = F_k(p_b) / D+(p_b) - F_k(t_b) / D+(t_b)`` - a band centre, a mean frequency, the cumulative curve of the
+    shape; a floored denominator is a constant in the gradient.  The denominator is a [S] tensor like the table, the floor finite
+    and > 0.  Such rows alone leave the scale of the prediction free: the pointwise term or a plain row carries it.  With
+    ``functional_norm_rows == 0`` the call is the one above and the other two must be None."""
     _loss_rows("loss_rows", torch.float32, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global,
-               weights, weight_index, bin_weights, functionals, functional_kind, functional_weight)
+               weights, weight_index, bin_weights, functionals, functional_kind, functional_weight, functional_denominator,
+               functional_norm_rows, functional_floor)
 
 
 # ---- guarded optimizer step (csrc/step_guard.hip; include/dosx.h: DosxStepGuard) -----------------------------------------------
@@ -2461,10 +2498,13 @@ def loss_rows64(pg: torch.Tensor, ps: Optional[torch.Tensor], y: torch.Tensor, k
                 per_crystal: Optional[torch.Tensor] = None, loss: torch.Tensor, B_global: Optional[int] = None,
                 weights: Optional[torch.Tensor] = None, weight_index: Optional[torch.Tensor] = None,
                 bin_weights: Optional[torch.Tensor] = None, functionals: Optional[torch.Tensor] = None,
-                functional_kind="sq", functional_weight: float = 1.0) -> None:
-    """:func:`loss_rows` on float64 operands (include/dosx.h: dosx_loss_rows_f64 / dosx_loss_rows_w_f64 / dosx_loss_rows_fn_f64)."""
+                functional_kind="sq", functional_weight: float = 1.0, functional_denominator: Optional[torch.Tensor] = None,
+                functional_norm_rows: int = 0, functional_floor: Optional[float] = None) -> None:
+    """:func:`loss_rows` on float64 operands (include/dosx.h: dosx_loss_rows_f64 / dosx_loss_rows_w_f64 / dosx_loss_rows_fn_f64 /
+    dosx_loss_rows_fn_norm_f64)."""
     _loss_rows("loss_rows64", torch.float64, pg, ps, y, kind, clamp_target, beta, delta, dpg, dps, per_crystal, loss, B_global,
-               weights, weight_index, bin_weights, functionals, functional_kind, functional_weight)
+               weights, weight_index, bin_weights, functionals, functional_kind, functional_weight, functional_denominator,
+               functional_norm_rows, functional_floor)
 
 
 def grad_accumulate64(dst: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None, n: Optional[int] = None, *,

@@ -125,6 +125,10 @@ class Trainer(TrainerBase):
     (a schedule on the term is a rescaled table); ``lam`` is recorded with the launch.  ``crystal_losses`` include the term.
     ``functional_weight=0`` trains the bits of the trainer without a table.  Every mode, windows, the guard, frozen parameters,
     groups, the average and the weights; constructor arguments: not in ``state_dict()``; not under data parallelism.
+    A ``Functionals`` with normalised rows (``functionals.centre``, ``normalised_cumulative``, ``normalised``: rows over one floored
+    denominator functional, ``u_k = F_k(p) / max(D(p), floor) - F_k(t) / max(D(t), floor)``) trains on the ratios through
+    ``dosx_loss_rows_fn_norm_desc``: the buffer holds table and denominator, ``set_functionals`` writes both and
+    refuses another K, number of normalised rows or floor.  Such rows alone leave the scale of the prediction free.
     """
 
     _who = "Trainer"

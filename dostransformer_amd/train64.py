@@ -68,7 +68,8 @@ class Trainer64(TrainerBase):
     (``dosx_loss_rows_w_f64``), as on ``train.Trainer``; they need ``loss=``.  With sample weights a slot's key ends in the table's
     address (``None`` for a batch-object slot).
     ``functionals`` / ``functional_kind`` / ``functional_weight``: a ``[K,S]`` table of linear functionals of the DOS penalised next
-    to the pointwise term (``dosx_loss_rows_fn_f64``), ``set_functionals(table)`` in place, as on ``train.Trainer``; they need ``loss=``.
+    to the pointwise term (``dosx_loss_rows_fn_f64``; with normalised rows ``dosx_loss_rows_fn_norm_desc_f64``),
+    ``set_functionals(table)`` in place, as on ``train.Trainer``; they need ``loss=``.
     ``step(g, n_global=None)`` / ``step_dataset(ds, indices, n_global=None, n_max=None)`` are the drivers' shared methods
     (``trainer_base.TrainerBase``) and carry ``train.Trainer``'s ``n_global``: this driver is single-GPU and refuses any value
     but the batch's own count - pass ``n_max`` by keyword.

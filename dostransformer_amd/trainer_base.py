@@ -10,6 +10,7 @@ driver answers a small set of hooks: the program's dtype, what a step cannot run
 step's context, the slot key, and the program itself - eager and on a slot."""
 from __future__ import annotations
 
+import struct
 from collections import OrderedDict
 from typing import Optional
 
@@ -355,10 +356,12 @@ class TrainerBase(StepGuard, WeightEma, SlotCache):
         return self._bin_dev
 
     # ---- linear functionals of the DOS in the loss (include/dosx.h: dosx_loss_rows_fn / dosx_loss_rows_fn_f64) ----
+    # ---- and rows of the table over one floored denominator functional (dosx_loss_rows_fn_norm / _f64) -----------
     functionals = None                # None, or the functionals.Functionals whose table the loss reads (float64, on the host)
     functional_kind = "sq"
     functional_weight = 1.0           # lam: recorded with the launch, fixed for the trainer's life
-    _fn_dev = None                    # the table on the device in the program's dtype: ONE buffer, written in place ever after
+    _fn_dev = None                    # the table (and behind it the denominator) on the device in the program's dtype: ONE buffer,
+    #                                   written in place ever after
 
     def _init_functionals(self, functionals, functional_kind="sq", functional_weight=1.0) -> None:
         """``functionals=`` / ``functional_kind=`` / ``functional_weight=`` of a trainer's constructor; call it after
@@ -396,16 +399,31 @@ class TrainerBase(StepGuard, WeightEma, SlotCache):
     def set_functionals(self, functionals) -> None:
         """Replace the table by another of the SAME shape, in place: the trainer's one device buffer is overwritten, nothing is
         re-recorded, and the next step - replayed or not - reads the new values.  A schedule on the term is a rescaled table
-        (``fn.scaled(c)``: ``"sq"`` scales with c^2, ``"abs"`` with c); ``functional_weight`` itself stays what was recorded."""
+        (``fn.scaled(c)``: ``"sq"`` scales with c^2, ``"abs"`` with c); ``functional_weight`` itself stays what was recorded.
+        With normalised rows (``functionals.centre`` ...; include/dosx.h: dosx_loss_rows_fn_norm) the table AND the denominator are
+        written; their count and the floor are part of the recorded launch, so another count or floor is refused."""
         if self.functionals is None:
             raise ValueError(f"{self._who}.set_functionals: the trainer was built without functionals=...")
         fn = self._checked_functionals(f"{self._who}.set_functionals", functionals)
         if fn.K != self.functionals.K:
             raise ValueError(f"{self._who}.set_functionals: [K,S] = [{fn.K},{fn.S}], the trainer's table is "
                              f"[{self.functionals.K},{self.functionals.S}] - the recorded launches hold its shape")
+        if fn.K_norm != self.functionals.K_norm:
+            raise ValueError(f"{self._who}.set_functionals: {fn.K_norm} normalised rows, the trainer's table has "
+                             f"{self.functionals.K_norm} - the recorded launches hold their count")
+        if fn.K_norm and struct.pack("<d", fn.floor) != struct.pack("<d", self.functionals.floor):
+            raise ValueError(f"{self._who}.set_functionals: floor {fn.floor!r}, the trainer's is {self.functionals.floor!r} - the "
+                             f"recorded launches hold the floor (the table and the denominator are what is written in place)")
         self.functionals = fn
         if self._fn_dev is not None:
-            self._fn_dev.copy_(fn.table.to(self._dtype))
+            self._fn_dev.copy_(self._fn_host(fn))
+
+    def _fn_host(self, fn) -> torch.Tensor:
+        """What the device buffer holds, in the program's dtype: the table, plain rows first (``Functionals.device_layout``), and
+        with normalised rows the denominator as one more row behind it.  Without any: the table as it is, the buffer of 9.12."""
+        if not fn.K_norm:
+            return fn.table.to(self._dtype)
+        return torch.cat([fn.device_layout()[0], fn.denominator[None, :]]).to(self._dtype)
 
     def _functional_operands(self, dev) -> dict:
         """The keyword operands of ``ops.loss_rows`` for the term; none without a table: the call it always was."""
@@ -414,8 +432,13 @@ class TrainerBase(StepGuard, WeightEma, SlotCache):
         if self._fn_dev is None or self._fn_dev.device != dev:
             if self._fn_dev is not None:       # (the module moved: the recordings hold the old buffer's address)
                 self._slots = OrderedDict()
-            self._fn_dev = self.functionals.table.to(dev, self._dtype).contiguous()
-        return {"functionals": self._fn_dev, "functional_kind": self.functional_kind, "functional_weight": self.functional_weight}
+            self._fn_dev = self._fn_host(self.functionals).to(dev).contiguous()
+        fn, K = self.functionals, self.functionals.K
+        kw = {"functionals": self._fn_dev, "functional_kind": self.functional_kind, "functional_weight": self.functional_weight}
+        if fn.K_norm:                          # K_norm and the floor are recorded with the launch; table and denominator are read
+            kw.update(functionals=self._fn_dev[:K], functional_denominator=self._fn_dev[K], functional_norm_rows=fn.K_norm,
+                      functional_floor=fn.floor)
+        return kw
 
     def _require_weight(self, what: str, g) -> None:
         """``sample_weights=True``: the batch must carry ``weight`` - raised before anything is launched."""

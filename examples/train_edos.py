@@ -121,26 +121,47 @@ def parse_args(argv=None):
     ap.add_argument("--fermi-weight", default=None, metavar="CENTER,WIDTH[,FLOOR]",
                     help="energy-bin weights: a Gaussian bump of WIDTH bins around bin CENTER on a floor in [0, 1] (default 0) "
                          "(weights.fermi_window; Trainer(bin_weights=...)); needs a per-crystal --loss")
-    ap.add_argument("--cdf-loss", default=None, metavar="LAM[,sq|abs]",
+    ap.add_argument("--cdf-loss", default=None, metavar="LAM[,sq|abs[,norm]]",
                     help="LAM times the distance between the cumulative DOS curves next to the per-crystal loss - sq (default): "
-                         "Cramer, abs: Wasserstein-1 (functionals.cumulative; Trainer(functionals=...)); needs a per-crystal --loss")
+                         "Cramer, abs: Wasserstein-1 (functionals.cumulative; Trainer(functionals=...)); a third part `norm` compares "
+                         "the curves as shapes, each over its own total (functionals.normalised_cumulative); needs a per-crystal --loss")
+    ap.add_argument("--band-centre-loss", default=None, metavar="LAM[,sq|abs]",
+                    help="LAM times the (squared: sq, default; absolute: abs) error of the band centre m1 / m0 next to the per-crystal "
+                         "loss, on a grid of unit length (functionals.centre); needs a per-crystal --loss.  One functional term per "
+                         "run; a normalised term leaves the scale of the prediction free, the per-crystal loss carries it")
+    ap.add_argument("--functional-floor", type=float, default=None, metavar="X",
+                    help="floor of the denominator m0 of --band-centre-loss / --cdf-loss ...,norm (default: 1e-3 times the median m0 "
+                         "of the clamped training targets, printed)")
     ap.add_argument("--report-moments", action="store_true",
                     help="with --eval-per-crystal: the mean absolute errors of the zeroth, first and second moment of the DOS and of "
                          "the band centre m1 / m0 (energies in bins from the middle of the grid), computed on the device "
                          "(functionals.moments; evaluate.functionals_per_crystal)")
     param_groups.add_arguments(ap)
     args = ap.parse_args(argv)
-    if args.cdf_loss is not None:
-        parts = args.cdf_loss.split(",")
+    for flag, norm in (("cdf_loss", True), ("band_centre_loss", False)):
+        text, name = getattr(args, flag), "--" + flag.replace("_", "-")
+        if text is None:
+            continue
+        parts = text.split(",")
         try:
             lam, kind = float(parts[0]), (parts[1] if len(parts) > 1 else "sq")
-            assert len(parts) <= 2 and kind in ("sq", "abs") and 0.0 <= lam < float("inf")
+            assert len(parts) <= (3 if norm else 2) and kind in ("sq", "abs") and 0.0 <= lam < float("inf")
+            assert len(parts) < 3 or parts[2] == "norm"
         except (ValueError, AssertionError):
-            ap.error("--cdf-loss LAM[,sq|abs]: a finite weight >= 0 and, optionally, the kind")
-        args.cdf_loss = (lam, kind)
+            ap.error(f"{name} LAM[,sq|abs{'[,norm]' if norm else ''}]: a finite weight >= 0 and, optionally, the kind"
+                     + (" and `norm`" if norm else ""))
+        setattr(args, flag, (lam, kind, len(parts) == 3))
         if args.loss == "reference":
-            ap.error("--cdf-loss adds a term to the per-crystal losses: pass --loss crystal_rmse (this model's reference objective "
+            ap.error(f"{name} adds a term to the per-crystal losses: pass --loss crystal_rmse (this model's reference objective "
                      "through the per-crystal entry) or another per-crystal --loss")
+    if args.cdf_loss is not None and args.band_centre_loss is not None:
+        ap.error("--cdf-loss and --band-centre-loss: one functional term per run (a trainer takes one table with one weight and one "
+                 "kind: functionals.stack(...) in code)")
+    if args.functional_floor is not None:
+        if args.band_centre_loss is None and not (args.cdf_loss is not None and args.cdf_loss[2]):
+            ap.error("--functional-floor belongs to --band-centre-loss or --cdf-loss LAM,KIND,norm")
+        if not 0.0 < args.functional_floor < float("inf"):
+            ap.error("--functional-floor X: finite and > 0")
     if args.report_moments and args.eval_per_crystal <= 0 and args.embedder == "DOSTransformer":
         ap.error("--report-moments reads the per-crystal evaluator's outputs: pass --eval-per-crystal N")
     if (args.balance_systems is not None or args.fermi_weight is not None) and args.loss == "reference":
@@ -160,6 +181,26 @@ def parse_args(argv=None):
     if (args.loss == "huber") != (args.huber_delta is not None):
         ap.error("--huber-delta X belongs to --loss huber, and --loss huber needs it")
     return args
+
+
+def _functional_args(args, train, S=201):
+    """--cdf-loss / --band-centre-loss -> the trainer's functionals= arguments, on a grid of unit length: bin width 1 / S.  The floor
+    of a normalised term: --functional-floor, or 1e-3 times the median m0 of the clamped training targets, computed once."""
+    flag = args.band_centre_loss or args.cdf_loss
+    if flag is None:
+        return {}
+    lam, kind, norm = flag
+    if args.band_centre_loss is None and not norm:
+        return dict(functionals=functionals.cumulative(S, 1.0 / S), functional_weight=lam, functional_kind=kind)
+    floor = args.functional_floor
+    if floor is None:
+        floor = 1e-3 * float((train._graph["y_ft"].double().clamp(min=0.0).sum(1) / S).median())
+        print(f"--functional-floor {floor:.6g}   (1e-3 x the median m0 of the {len(train)} training targets)")
+    if args.band_centre_loss is not None:
+        fn = functionals.centre((torch.arange(S, dtype=torch.float64) + 0.5) / S, floor, de=1.0 / S)
+    else:
+        fn = functionals.normalised_cumulative(S, floor, 1.0 / S)
+    return dict(functionals=fn, functional_weight=lam, functional_kind=kind)
 
 
 def main(argv=None):
@@ -239,8 +280,7 @@ def _main(argv=None):
                       max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite, param_groups=groups,
                       ema_decay=args.ema, ema_warmup=not args.no_ema_warmup,
                       loss=None if args.loss == "reference" else args.loss, huber_delta=args.huber_delta,
-                      **({} if args.cdf_loss is None else dict(functionals=functionals.cumulative(201, 1.0 / 201),
-                                                               functional_weight=args.cdf_loss[0], functional_kind=args.cdf_loss[1])))
+                      **_functional_args(args, ds["train"]))
     predictor = Predictor(model, bucket=bucket, per_crystal_keys=args.eval_per_crystal > 0 and not baseline)
     criterion_2 = torch.nn.L1Loss()                                                       # `main_eDOS.py:93`
 

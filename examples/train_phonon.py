@@ -72,6 +72,15 @@ Trainer(functionals=...): the same loss launch).  --report-heat-capacity T[,T...
 error of the harmonic C_V(T) of the predicted DOS, computed on the device from the per-crystal evaluator's outputs.
 
     python examples/train_phonon.py --loss crystal_rmse --cdf-loss 0.5 --eval-per-crystal 64 --report-heat-capacity 100,300,1000
+
+Normalised functionals (rows over one floored denominator, functionals.centre / functionals.normalised_cumulative): --mean-frequency-loss
+LAM[,sq|abs] penalises the error of the mean frequency m1 / m0 (on a grid of unit length), --cdf-loss LAM,sq|abs,norm compares the
+cumulative curves of the DOS as SHAPES, each over its own total.  One functional term per run.  Such a term leaves the scale of the
+prediction free; the per-crystal --loss next to it carries the scale.  --functional-floor X is the floor of the denominator m0 (below
+it the denominator is the constant X); without it the driver takes 1e-3 times the median m0 of the training targets and prints it.
+
+    python examples/train_phonon.py --loss crystal_rmse --mean-frequency-loss 0.5
+    python examples/train_phonon.py --loss crystal_rmse --cdf-loss 0.5,abs,norm --functional-floor 1e-4
 """
 import argparse
 import os
@@ -155,7 +164,13 @@ def _main(argv=None):
     ap.add_argument("--balance-systems", type=float, nargs="?", const=1.0, default=None, metavar="POWER",
                     help="fused trainers: class-balanced sample weights over the 7 crystal systems, w ~ count[system] ** -POWER "
                          "(default 1), mean 1 over the training set (weights.balanced; sample_weights=True); needs a per-crystal --loss")
-    ap.add_argument("--cdf-loss", default=None, metavar="LAM[,sq|abs]",
+    ap.add_argument("--mean-frequency-loss", default=None, metavar="LAM[,sq|abs]",
+                    help="LAM times the (squared: sq, default; absolute: abs) error of the mean frequency m1 / m0 next to the per-crystal "
+                         "loss, on a grid of unit length (functionals.centre; functionals=...); needs a per-crystal --loss")
+    ap.add_argument("--functional-floor", type=float, default=None, metavar="X",
+                    help="floor of the denominator m0 of --mean-frequency-loss / --cdf-loss ...,norm (default: 1e-3 times the median m0 "
+                         "of the training targets, printed)")
+    ap.add_argument("--cdf-loss", default=None, metavar="LAM[,sq|abs[,norm]]",
                     help="fused trainers: LAM times the distance between the cumulative DOS curves next to the per-crystal loss - sq "
                          "(default): Cramer, abs: Wasserstein-1 (functionals.cumulative; functionals=...); needs a per-crystal --loss")
     ap.add_argument("--report-heat-capacity", default=None, metavar="T[,T...]",
@@ -164,7 +179,17 @@ def _main(argv=None):
                          "(functionals.heat_capacity; evaluate.functionals_per_crystal)")
     param_groups.add_arguments(ap)
     args = ap.parse_args(argv)
-    args.cdf_loss = _parse_cdf(ap, args.cdf_loss)
+    args.cdf_loss = _parse_cdf(ap, "--cdf-loss", args.cdf_loss, norm=True)
+    args.mean_frequency_loss = _parse_cdf(ap, "--mean-frequency-loss", args.mean_frequency_loss)
+    if args.cdf_loss is not None and args.mean_frequency_loss is not None:
+        ap.error("--cdf-loss and --mean-frequency-loss: one functional term per run (a trainer takes one table with one weight and one "
+                 "kind: functionals.stack(...) in code)")
+    if args.mean_frequency_loss is not None and args.loss == "reference":
+        ap.error("--mean-frequency-loss adds a term to the per-crystal losses: pick --loss crystal_rmse or another per-crystal --loss")
+    if args.functional_floor is not None and not (args.mean_frequency_loss is not None or (args.cdf_loss or (0, 0, False))[2]):
+        ap.error("--functional-floor belongs to --mean-frequency-loss or --cdf-loss LAM,KIND,norm")
+    if args.functional_floor is not None and not 0.0 < args.functional_floor < float("inf"):
+        ap.error("--functional-floor X: finite and > 0")
     if args.cdf_loss is not None and args.loss == "reference":
         ap.error("--cdf-loss adds a term to the per-crystal losses: pick --loss crystal_rmse (the reference's own batch-1 objective), "
                  "mse, mae or huber")
@@ -227,6 +252,7 @@ def _main(argv=None):
         ds["train"].set_weights(sysw)
         print(f"--balance-systems {args.balance_systems:g}: sample weights {float(sysw.min()):.3g} .. {float(sysw.max()):.3g}, mean 1")
 
+    args.functional_term = _functional_term(args, ds["train"])
     if args.float64:
         return train_float64_fused(args, ds, dev) if args.fused else train_float64(args, ds, dev)
     if baseline:
@@ -286,24 +312,45 @@ def _ema_args(args):
     return dict(ema_decay=args.ema, ema_warmup=not args.no_ema_warmup)
 
 
-def _parse_cdf(ap, text):
-    """--cdf-loss LAM[,sq|abs] -> None or (lam, kind)"""
+def _parse_cdf(ap, flag, text, norm=False):
+    """FLAG LAM[,sq|abs[,norm]] -> None or (lam, kind, normalised); the third part only where `norm` allows it"""
     if text is None:
         return None
     parts = text.split(",")
     try:
         lam, kind = float(parts[0]), (parts[1] if len(parts) > 1 else "sq")
-        assert len(parts) <= 2 and kind in ("sq", "abs") and 0.0 <= lam < float("inf")
+        assert len(parts) <= (3 if norm else 2) and kind in ("sq", "abs") and 0.0 <= lam < float("inf")
+        assert len(parts) < 3 or parts[2] == "norm"
     except (ValueError, AssertionError):
-        ap.error("--cdf-loss LAM[,sq|abs]: a finite weight >= 0 and, optionally, the kind")
-    return lam, kind
+        ap.error(f"{flag} LAM[,sq|abs{'[,norm]' if norm else ''}]: a finite weight >= 0 and, optionally, the kind"
+                 + (" and `norm`" if norm else ""))
+    return lam, kind, len(parts) == 3
 
 
-def _loss_args(args, S=51):
+def _functional_term(args, train, S=51):
+    """--cdf-loss / --mean-frequency-loss -> None or (Functionals, lam, kind), on a grid of unit length: bin width 1 / S.  The floor
+    of a normalised term: --functional-floor, or 1e-3 times the median m0 of the training targets, computed once."""
+    flag = args.mean_frequency_loss or args.cdf_loss
+    if flag is None:
+        return None
+    lam, kind, norm = flag
+    if args.mean_frequency_loss is None and not norm:
+        return functionals.cumulative(S, 1.0 / S), lam, kind
+    floor = args.functional_floor
+    if floor is None:
+        floor = 1e-3 * float((train._graph["phdos"].double().sum(1) / S).median())
+        print(f"--functional-floor {floor:.6g}   (1e-3 x the median m0 of the {len(train)} training targets)")
+    if args.mean_frequency_loss is not None:
+        return functionals.centre((torch.arange(S, dtype=torch.float64) + 0.5) / S, floor, de=1.0 / S), lam, kind
+    return functionals.normalised_cumulative(S, floor, 1.0 / S), lam, kind
+
+
+def _loss_args(args):
     kw = dict(loss=None if args.loss == "reference" else args.loss, huber_delta=args.huber_delta,
               sample_weights=args.balance_systems is not None)
-    if args.cdf_loss is not None:          # the cumulative DOS on a grid of unit length: bin width 1 / S
-        kw.update(functionals=functionals.cumulative(S, 1.0 / S), functional_weight=args.cdf_loss[0], functional_kind=args.cdf_loss[1])
+    if args.functional_term is not None:
+        fn, lam, kind = args.functional_term
+        kw.update(functionals=fn, functional_weight=lam, functional_kind=kind)
     return kw
 
 

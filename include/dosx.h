@@ -1386,6 +1386,56 @@ int dosx_loss_rows_fn_f64(const double* pg, const double* ps, const double* y, i
                           const double* w, const int32_t* w_index, const double* bin_w, const double* fn_w, int K, int fn_kind,
                           double lam, dosx_stream_t stream);
 
+/* ---- normalised functionals in the per-crystal losses (csrc/loss_functional.hip) ------------------------------------------
+ * dosx_loss_rows_fn with the LAST K_norm rows of the table divided by one common denominator functional - a band centre or a
+ * mean frequency m1 / m0, C_V(T) per mode, the cumulative curve of the DOS as a shape.  t, f, beta, w_b, v_s, B_global, e, lam
+ * and K exactly as above; the table fn_w [K,S] is unchanged, its first K - K_norm rows are the plain rows of above.  New
+ * operands: fn_den [S] in the operands' type, den_floor > 0 and K_norm.
+ *   D(x)   = sum_s fn_den[s] x_s          D+(x) = max(D(x), den_floor)
+ *   plain row k:       u_k(p) = F_k(p) - F_k(t)
+ *   normalised row k:  u_k(p) = F_k(p) / D+(p)  -  F_k(t) / D+(t)
+ *   h(p)   = (1 / K) sum_k e(u_k)         l_b = f(pg_b) + beta f(ps_b) + lam (h(pg_b) + beta h(ps_b))
+ * (t is the clamped target under clamp_target.)  For a normalised row, with q_k = F_k(p) / D+(p),
+ *   d u_k / d p_s = fn_w[k,s] / D+ - [D(p) > den_floor] q_k fn_den[s] / D+ :
+ * a floored denominator is a constant (torch's clamp(min=) subgradient away from equality).  The gradient of the term on
+ * element s is  coef lam / K ( sum_k c_k fn_w[k,s] - [D > den_floor] A fn_den[s] ),  c_k = e'(u_k) on plain rows and
+ * e'(u_k) / D+ on normalised rows,  A = sum_{k normalised} e'(u_k) q_k / D+.  A purely normalised objective leaves the scale of
+ * the prediction free (sum_s p_s d/dp_s of such a term is 0 where D > den_floor): the pointwise term, or a plain row, carries it.
+ * The rules of dosx_loss_rows_fn hold: a NaN stays inside its crystal, w_b == 0 writes +0.0 rows, per_crystal[b] = l_b unweighted,
+ * fixed summation orders that depend on (S, K, K_norm) alone (the header comment of csrc/loss_functional.hip), no atomics, the
+ * same launches and limits (S, K <= 512).  K_norm == 0 (fn_den is then not read), fn_w == NULL or lam == 0: dosx_loss_rows_fn's
+ * own launches under this entry's name, bit for bit.  Refused with -22 and a message that starts with the entry's name:
+ * everything dosx_loss_rows_fn refuses; K_norm < 0, or K_norm > K with a table; K_norm > 0 with fn_den == NULL; den_floor not
+ * finite or <= 0; fn_den lying inside pg, ps, y, dpg or dps.
+ *
+ * dosx_loss_rows_fn_norm_desc / _desc_f64: the same call - the same checks under their own names, the same kernels - with the
+ * table's side in a DosxFnNorm, read on the host when the call is issued.  These are the forms a recorded step holds: a DosxCall
+ * carries 19 integer-class arguments, the entries above have 21.  lam and den_floor are converted to the operands' type;
+ * reserved is not read.  A NULL descriptor is refused. */
+typedef struct DosxFnNorm {
+  const void* fn_w;    /* [K,S] in the operands' type, or NULL */
+  const void* fn_den;  /* [S] in the operands' type; may be NULL with K_norm == 0 */
+  int32_t K, K_norm, fn_kind, reserved;
+  double lam, den_floor;
+} DosxFnNorm;
+int dosx_loss_rows_fn_norm(const float* pg, const float* ps, const float* y, int B, int S, int B_global, int kind,
+                           int clamp_target, float beta, float delta, float* dpg, float* dps, float* per_crystal, float* loss,
+                           const float* w, const int32_t* w_index, const float* bin_w, const float* fn_w, int K, int fn_kind,
+                           float lam, const float* fn_den, int K_norm, float den_floor, dosx_stream_t stream);
+int dosx_loss_rows_fn_norm_f64(const double* pg, const double* ps, const double* y, int B, int S, int B_global, int kind,
+                               int clamp_target, double beta, double delta, double* dpg, double* dps, double* per_crystal,
+                               double* loss, const double* w, const int32_t* w_index, const double* bin_w, const double* fn_w,
+                               int K, int fn_kind, double lam, const double* fn_den, int K_norm, double den_floor,
+                               dosx_stream_t stream);
+int dosx_loss_rows_fn_norm_desc(const float* pg, const float* ps, const float* y, int B, int S, int B_global, int kind,
+                                int clamp_target, float beta, float delta, float* dpg, float* dps, float* per_crystal, float* loss,
+                                const float* w, const int32_t* w_index, const float* bin_w, const DosxFnNorm* fn,
+                                dosx_stream_t stream);
+int dosx_loss_rows_fn_norm_desc_f64(const double* pg, const double* ps, const double* y, int B, int S, int B_global, int kind,
+                                    int clamp_target, double beta, double delta, double* dpg, double* dps, double* per_crystal,
+                                    double* loss, const double* w, const int32_t* w_index, const double* bin_w,
+                                    const DosxFnNorm* fn, dosx_stream_t stream);
+
 /* ---- guarded optimizer step (csrc/step_guard.hip; the guarded AdamW entries: csrc/adamw.hip) ------------------------------
  * What a fused trainer has in place of `clip_grad_norm_` and of a GradScaler-style "skip if non-finite": one statistics launch
  * over the flat gradient, behind the recorded program and in front of the AdamW launch, and an AdamW that reads its verdict
