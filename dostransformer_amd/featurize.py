@@ -66,17 +66,38 @@ def _get(entry, key):
     return getattr(entry, key)
 
 
+def _derived_systems(entries, mode: str, table: Dict[str, int], lower: bool, symprec: float, device) -> Optional[List[int]]:
+    """The ``crystal_system=`` modes of ``build_data_all`` / ``build_edos_all``: None for "given" (the labels are read entry by
+    entry as before), else one code per entry from ``symmetry.resolve_labels`` ("derive": where the entry carries no label,
+    "check": everywhere, a mismatch or an INCONSISTENT crystal raises)."""
+    if mode == "given":
+        return None
+    from . import symmetry
+
+    def name(e):
+        v = e.get("crystal_system") if isinstance(e, dict) else getattr(e, "crystal_system", None)
+        return None if v is None or str(v) == "" else (str(v).lower() if lower else v)
+
+    names = [name(e) for e in entries]
+    return symmetry.resolve_labels(entries, mode, [table.get(v, 6) for v in names], [v is not None for v in names],
+                                   symprec=symprec, device=device)
+
+
 def build_data_all(entries: Sequence, r_max: float = 5.0, device="cuda:0", masses: Optional[Sequence[float]] = None,
-                   dtype: torch.dtype = torch.float64) -> List[Dict[str, object]]:
+                   dtype: torch.dtype = torch.float64, crystal_system: str = "given", symprec: float = 0.1) -> List[Dict[str, object]]:
     """`utils.py:249-303` for a whole dataset at once.  Returns one dict per entry with the reference's ``Data``
     fields: pos, lattice, symbol, x, z, edge_index (row 0 = central atom, row 1 = neighbour), edge_shift, edge_vec,
-    edge_len (rounded to 2 decimals, `:276`), phdos [1,51], system, mp_id — host tensors, ``dtype`` floating point."""
+    edge_len (rounded to 2 decimals, `:276`), phdos [1,51], system, mp_id — host tensors, ``dtype`` floating point.
+    ``crystal_system``: "given" reads ``entry.crystal_system`` (an unknown name is code 6, as in the reference); "derive" labels
+    the entries that carry none from their structure (``symmetry.crystal_systems`` at ``symprec``); "check" derives every label
+    and raises on the first that disagrees.  Both raise on a crystal whose operations match no point group."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("build_data_all runs the neighbour search on an MI355X through libdosx (no CPU fallback)")
     entries = list(entries)
     if not entries:
         return []
+    derived = _derived_systems(entries, crystal_system, CRYSTAL_SYSTEMS, False, symprec, dev)
     mass = torch.tensor(ATOMIC_MASSES if masses is None else list(masses), dtype=torch.float64)
     if mass.numel() != len(SYMBOLS):
         raise ValueError(f"masses must have {len(SYMBOLS)} entries")
@@ -100,7 +121,7 @@ def build_data_all(entries: Sequence, r_max: float = 5.0, device="cuda:0", masse
         ev = vec[a:b]
         x = torch.zeros(len(z), len(SYMBOLS), dtype=dtype)
         x[torch.arange(len(z)), z] = mass[z].to(dtype)
-        system = CRYSTAL_SYSTEMS.get(_get(e, "crystal_system"), 6)
+        system = CRYSTAL_SYSTEMS.get(_get(e, "crystal_system"), 6) if derived is None else derived[c]
         out.append({
             "pos": torch.from_numpy(pos[c]).to(dtype), "lattice": torch.from_numpy(cell[c]).to(dtype).unsqueeze(0),
             "symbol": sym[c], "x": x, "z": eye[z],
@@ -137,7 +158,8 @@ def load_elem_feats(path_or_mapping, symbols: Sequence[str] = tuple(SYMBOLS[:100
 
 
 def build_edos_all(entries: Sequence[dict], elem_feats, radius: float = 8.0, max_num_nbr: int = 12, step: float = 0.2,
-                   device="cuda:0", normalize_target: bool = True) -> List[Dict[str, object]]:
+                   device="cuda:0", normalize_target: bool = True, crystal_system: str = "given",
+                   symprec: float = 0.1) -> List[Dict[str, object]]:
     """`data/mat2graph.py:81-107,120-243` for a whole dataset at once.  ``entries``: dicts with ``numbers`` (Z) or
     ``symbols``, ``positions`` (Cartesian), ``cell`` (rows = lattice vectors) and optionally ``glob`` ([energy_per_atom,
     formation_energy_per_atom]), ``crystal_system`` (name, any case), ``y_ft``, ``y``, ``mp_id``.  ``elem_feats [Zmax, F]``:
@@ -146,13 +168,15 @@ def build_edos_all(entries: Sequence[dict], elem_feats, radius: float = 8.0, max
     [2, K*n] int64 (row 0 = atom i K times, row 1 = its neighbours by rank; a padded rank points at atom 0, `:222-227`),
     edge_attr [K*n, G] fp32, glob [2], system, y_ft [201] (divided by its maximum when ``normalize_target``, `:86-88`; zeros
     when the entry has none), y_max, mp_id, pos — and y when the entry has one.  The order inside a distance tie is the key of
-    include/dosx.h (DosxKnn); the reference leaves it to pymatgen."""
+    include/dosx.h (DosxKnn); the reference leaves it to pymatgen.  ``crystal_system`` / ``symprec``: as in ``build_data_all``
+    ("given", "derive" or "check")."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("build_edos_all runs the neighbour selection on an MI355X through libdosx (no CPU fallback)")
     entries = list(entries)
     if not entries:
         return []
+    derived = _derived_systems(entries, crystal_system, _SYSTEM_CODES, True, symprec, dev)
     table = torch.as_tensor(np.asarray(elem_feats, np.float64))
     if table.dim() != 2:
         raise ValueError("elem_feats must be a [Z, F] table")
@@ -191,7 +215,7 @@ def build_edos_all(entries: Sequence[dict], elem_feats, radius: float = 8.0, max
             "edge_attr": attr[a * K:b * K].clone(),
             "glob": torch.tensor(np.asarray(e["glob"], np.float64), dtype=torch.float32).reshape(2) if e.get("glob") is not None
             else torch.zeros(2),
-            "system": torch.tensor(_SYSTEM_CODES.get(str(e.get("crystal_system", "")).lower(), 6)),
+            "system": torch.tensor(_SYSTEM_CODES.get(str(e.get("crystal_system", "")).lower(), 6) if derived is None else derived[c]),
             "y_ft": y_ft / y_max if has_y and normalize_target else y_ft,
             "y_max": y_max,
             "mp_id": e.get("mp_id", f"entry-{c}"),

@@ -2207,6 +2207,49 @@ def knn_graph(pos: torch.Tensor, cell: torch.Tensor, atom_ptr: torch.Tensor, rad
     return out
 
 
+def _sym_descriptor(d, cell, frac, species, atom_ptr, symprec, n_min, n_max):
+    assert frac.is_cuda and frac.dtype == torch.float64 and cell.dtype == torch.float64
+    assert species.dtype == torch.int32 and atom_ptr.dtype == torch.int32
+    cell, frac, species, atom_ptr = cell.contiguous(), frac.contiguous(), species.contiguous(), atom_ptr.contiguous()
+    Cn, N = int(cell.shape[0]), int(frac.shape[0])
+    assert frac.shape == (N, 3) and cell.shape == (Cn, 3, 3) and atom_ptr.shape == (Cn + 1,) and species.shape == (N,)
+    d.C, d.N, d.n_min, d.n_max, d.symprec = Cn, N, int(n_min), int(n_max), float(symprec)
+    d.cell, d.frac, d.species, d.atom_ptr = cell.data_ptr(), frac.data_ptr(), species.data_ptr(), atom_ptr.data_ptr()
+    return (cell, frac, species, atom_ptr), Cn, N
+
+
+def sym_translations(cell: torch.Tensor, frac: torch.Tensor, species: torch.Tensor, atom_ptr: torch.Tensor,
+                     symprec: float, n_min: int, n_max: int) -> torch.Tensor:
+    """Pure translations of C crystals in one launch (include/dosx.h: dosx_sym_translations).  ``cell [C,3,3]`` fp64
+    Delaunay-reduced (rows = lattice vectors), ``frac [N,3]`` fp64 fractional rows, ``species [N]`` and ``atom_ptr [C+1]`` int32,
+    all on the GPU; ``n_min`` / ``n_max``: atoms of the smallest / largest crystal (the caller built ``atom_ptr``).  Returns
+    ``flag [N]`` uint8: 1 where ``frac[j] - frac[ref]`` is a pure translation of j's crystal."""
+    d = _lib.SymTranslations()
+    keep, Cn, N = _sym_descriptor(d, cell, frac, species, atom_ptr, symprec, n_min, n_max)
+    flag = torch.zeros(N, dtype=torch.uint8, device=frac.device)
+    d.flag = flag.data_ptr()
+    _call("dosx_sym_translations", C.byref(d), _stream())
+    return flag
+
+
+def sym_point_group(cell: torch.Tensor, frac: torch.Tensor, species: torch.Tensor, atom_ptr: torch.Tensor,
+                    symprec: float, n_min: int, n_max: int):
+    """Point groups of C reduced primitive cells in one launch (include/dosx.h: dosx_sym_point_group); arguments as
+    ``sym_translations``.  Returns a dict of device tensors: ``n_lattice_ops [C]``, ``n_ops [C]`` int32, ``ops [C,48,9]`` int8
+    (the kept matrices in lexicographic order, zeros after them), ``hist [C,5]`` int32 (distinct proper parts by trace -1..3),
+    ``code [C]`` int32 (0..6 the reference's crystal-system codes, 7 = INCONSISTENT)."""
+    d = _lib.SymPointGroup()
+    keep, Cn, N = _sym_descriptor(d, cell, frac, species, atom_ptr, symprec, n_min, n_max)
+    dev = frac.device
+    out = {"n_lattice_ops": torch.zeros(Cn, dtype=torch.int32, device=dev), "n_ops": torch.zeros(Cn, dtype=torch.int32, device=dev),
+           "ops": torch.zeros(Cn, 48, 9, dtype=torch.int8, device=dev), "hist": torch.zeros(Cn, 5, dtype=torch.int32, device=dev),
+           "code": torch.full((Cn,), 7, dtype=torch.int32, device=dev)}
+    for key, t in out.items():
+        setattr(d, key, t.data_ptr())
+    _call("dosx_sym_point_group", C.byref(d), _stream())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # float64 program (csrc/f64.hip, include/dosx.h "float64 program"): thin wrappers, used by functional64.py
 # ---------------------------------------------------------------------------------------------------------------------

@@ -81,6 +81,10 @@ def parse_args(argv=None):
     ap.add_argument("--pickle", default=None)
     ap.add_argument("--structures", type=int, default=0,
                     help="build the graphs of this many synthetic structures with featurize.build_edos_all (0: off)")
+    ap.add_argument("--crystal-system", default="given", choices=["given", "derive", "check"],
+                    help="with --structures: prompt labels as the entries give them; derived from the structure where an entry has "
+                         "none; or every label derived and compared with the given one (a mismatch stops the run)")
+    ap.add_argument("--symprec", type=float, default=0.1, metavar="X", help="with --crystal-system derive / check: distance tolerance in angstrom")
     ap.add_argument("--eval_batch_size", type=int, default=1, help="main_eDOS.py:55-56 evaluates at batch size 1")
     ap.add_argument("--eval-per-crystal", type=int, default=0, metavar="N",
                     help="N > 0: the batch-size-1 metrics from batched passes of N crystals (evaluate.test_per_crystal, "
@@ -226,7 +230,8 @@ def _main(argv=None):
         table = featurize.load_elem_feats({s: v for s, v in zip(featurize.SYMBOLS[:100],
                                                                 np.random.default_rng(args.seed).normal(size=(100, 200)))})
         t0 = time.perf_counter()
-        crystals = featurize.build_edos_all(synth.edos_structures(args.structures, args.seed), table, device=dev)
+        crystals = featurize.build_edos_all(synth.edos_structures(args.structures, args.seed), table, device=dev,
+                                            crystal_system=args.crystal_system, symprec=args.symprec)
         print(f"built {len(crystals)} crystal graphs from structures in {time.perf_counter() - t0:.2f} s")
     elif args.pickle:
         crystals = pickle.load(open(args.pickle, "rb"))

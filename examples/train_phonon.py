@@ -123,6 +123,10 @@ def _main(argv=None):
     ap.add_argument("--crystals", type=int, default=512)
     ap.add_argument("--pickle", default=None)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--crystal-system", default="given", choices=["given", "derive", "check"],
+                    help="prompt labels: as the entries give them; derived from the structure where an entry has none; or every "
+                         "label derived and compared with the given one (symmetry.crystal_systems; a mismatch stops the run)")
+    ap.add_argument("--symprec", type=float, default=0.1, metavar="X", help="with --crystal-system derive / check: distance tolerance in angstrom")
     ap.add_argument("--out", default="phonon_best.pt")
     ap.add_argument("--no-validate", action="store_true",
                     help="skip batch validation (validate.enable: every crystal and every first-seen batch is checked for out-of-range "
@@ -239,7 +243,8 @@ def _main(argv=None):
     entries = pickle.load(open(args.pickle, "rb")) if args.pickle else synth.phonon_structures(args.crystals, args.seed)
     t0 = time.perf_counter()
     crystals = featurize.build_data_all(entries, r_max=args.r_max, device=dev,
-                                        dtype=torch.float64 if args.float64 else torch.float32)
+                                        dtype=torch.float64 if args.float64 else torch.float32,
+                                        crystal_system=args.crystal_system, symprec=args.symprec)
     print(f"{len(crystals)} crystals -> graphs in {time.perf_counter() - t0:.2f} s "
           f"({sum(c['edge_index'].shape[1] for c in crystals)} edges)")
     perm = np.random.default_rng(args.seed).permutation(len(crystals))

@@ -1072,6 +1072,68 @@ typedef struct DosxKnn {
 } DosxKnn;
 int dosx_knn_graph(const DosxKnn* d, dosx_stream_t stream);
 
+/* The crystal system of C crystals from their structures (the prompt label `entry.crystal_system` of `utils.py:277-290`, which
+ * the reference takes from Materials-Project metadata, i.e. pymatgen / spglib; neither is in the reference tree nor pinned, so
+ * this comment is the contract - PARITY UNPINNED at that boundary: spglib's angle tolerance and refinement are not restated, and a
+ * structure within symprec of a symmetry change may be labelled differently there).  All arithmetic is float64 without fused
+ * multiply-adds.  `cell [C][3][3]` = a basis A, rows = lattice vectors; `frac [N][3]` = fractional rows x with r = x A;
+ * `species [N]` >= 0; crystal c owns atoms [atom_ptr[c], atom_ptr[c+1]); symprec in Angstrom (0.1 is Materials Project's).
+ *   distance       of a moved atom y to atom k:  d = y - x_k ,  d -= rint(d) ,  c_a = (d0*A[0][a] + d1*A[1][a]) + d2*A[2][a] ,
+ *                  r2 = (c0*c0 + c1*c1) + c2*c2 ;  y "lands on" k when r2 < symprec*symprec and species[k] is y's species.
+ *   reference atom the first atom of the rarest species, ties to the smallest species number.
+ *   (a) the caller Delaunay-reduces every cell (dostransformer_amd/symmetry.py: delaunay_reduce) before either call.
+ *   (b) dosx_sym_translations: flag[j] = 1 iff j is another atom of the reference atom's species and, with t = x_j - x_ref,
+ *       y = x_i + t lands on some k for EVERY atom i; 0 otherwise (other species and the reference atom included).  The caller
+ *       takes the lattice generated by A and the n_t flagged t (volume V / (n_t + 1)), Delaunay-reduces it and re-expresses all
+ *       atoms in it; coincident copies stay.
+ *   (c) dosx_sym_point_group, lattice operations: integer W with entries in {-1, 0, 1} and |det W| = 1 whose images
+ *       a_i' = (W[i][0]*A[0] + W[i][1]*A[1]) + W[i][2]*A[2] keep the six lengths |a_0|, |a_1|, |a_2|, |a_0+a_1|, |a_0+a_2|,
+ *       |a_1+a_2| : | |v'| - |v| | < symprec , |v| = sqrt((v0*v0 + v1*v1) + v2*v2).  n_lattice_ops counts them; more than 48
+ *       is no lattice's holohedry: code 7, n_ops 0, nothing kept.
+ *   (d) structure operations: W is kept iff for some atom j of the reference species, with
+ *       t = x_j - ((xr0*W[0] + xr1*W[1]) + xr2*W[2])  (xr = x_ref),  y = ((xi0*W[0] + xi1*W[1]) + xi2*W[2]) + t lands on some k
+ *       for every atom i.  ops [C][48][9] int8: the n_ops kept matrices, row-major, in the lexicographic order of their nine
+ *       entries; zeros after them.
+ *   (e) hist [C][5]: the DISTINCT proper parts det(W) * W counted by trace -1, 0, 1, 2, 3 (2-, 3-, 4-, 6-fold rotations,
+ *       identity).  code [C]: the histogram must be one of the eleven proper point groups (N2 N3 N4 N6 | order | code)
+ *         1: 0 0 0 0 | 1 | 6     2: 1 0 0 0 | 2 | 5     222: 3 0 0 0 | 4 | 4    4: 1 0 2 0 | 4 | 2    422: 5 0 2 0 | 8 | 2
+ *         3: 0 2 0 0 | 3 | 3    32: 3 2 0 0 | 6 | 3       6: 1 2 0 2 | 6 | 1  622: 7 2 0 2 | 12 | 1   23: 3 8 0 0 | 12 | 0
+ *         432: 9 8 6 0 | 24 | 0
+ *       with one identity, as many distinct proper parts as the order, and n_ops once or twice the order; the codes are the
+ *       reference's (0 Cubic, 1 Hexagonal, 2 Tetragonal, 3 Trigonal, 4 Orthorhombic, 5 Monoclinic, 6 triclinic).  Anything
+ *       else is INCONSISTENT: code 7, never a silent 6.
+ * One workgroup per crystal; coordinates and species are staged in LDS up to 1024 atoms and read from global memory beyond.
+ * Every "some" / "every" search may stop early, which cannot change the answer; there are no atomics and the outputs are a pure
+ * function of the crystal.  n_min / n_max: the smallest / largest number of atoms of a crystal, stated by the caller (atom_ptr
+ * lives on the device); the kernels leave a crystal they find outside [1, n_max] untouched.  Refused with rc -22 before any
+ * launch: null descriptor, C <= 0, N <= 0, n_min <= 0 (an empty crystal), n_max < n_min or >= 2^21, symprec <= 0 or NaN, a
+ * null buffer. */
+typedef struct DosxSymTranslations {
+  int32_t C, N, n_min, n_max;
+  double symprec;
+  const double* cell;       /* [C][3][3] Delaunay-reduced, rows = lattice vectors */
+  const double* frac;       /* [N][3] fractional rows in that basis */
+  const int32_t* species;   /* [N] */
+  const int32_t* atom_ptr;  /* [C+1] */
+  void* flag;               /* [N] one byte per atom */
+} DosxSymTranslations;
+int dosx_sym_translations(const DosxSymTranslations* d, dosx_stream_t stream);
+
+typedef struct DosxSymPointGroup {
+  int32_t C, N, n_min, n_max;
+  double symprec;
+  const double* cell;       /* [C][3][3] reduced primitive cells */
+  const double* frac;       /* [N][3] */
+  const int32_t* species;   /* [N] */
+  const int32_t* atom_ptr;  /* [C+1] */
+  int32_t* n_lattice_ops;   /* [C] */
+  int32_t* n_ops;           /* [C] */
+  void* ops;                /* [C][48][9] int8 */
+  int32_t* hist;            /* [C][5] */
+  int32_t* code;            /* [C] */
+} DosxSymPointGroup;
+int dosx_sym_point_group(const DosxSymPointGroup* d, dosx_stream_t stream);
+
 /* Replay of a recorded launch list (the host side of train.Trainer(replay=True), see csrc/replay.cpp): `n` calls are
  * issued in order.  A call names its callee by `op` (from dosx_replay_op: every `int dosx_*` entry point of this header,
  * plus "hipEventRecord" / "hipStreamWaitEvent" for stream fork/join) and carries the callee's integer-class arguments in
