@@ -24,11 +24,13 @@ from __future__ import annotations
 from typing import Dict, List, Optional, Sequence
 
 import json
+import re
 
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, spectra
+from ._lib import DosxError
 from .synth import E_BINS
 
 SYMBOLS = ("H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr "
@@ -83,14 +85,40 @@ def _derived_systems(entries, mode: str, table: Dict[str, int], lower: bool, sym
                                    symprec=symprec, device=device)
 
 
+def _field(entry, key):
+    """``entry[key]`` / ``entry.key``, None when the entry has none."""
+    return entry.get(key) if isinstance(entry, dict) else getattr(entry, key, None)
+
+
+def _raw_targets(which: List[int], energies, values, targets, kind: str, dev, shift=None, normalize: bool = True):
+    """One ``spectra.broaden`` launch for the entries ``which``; a spectrum that cannot be turned into a target raises, with the
+    entry's index in place of its position in the launch."""
+    if targets.on_uncovered not in ("raise", "keep"):
+        raise ValueError(f"on_uncovered must be 'raise' or 'keep', got {targets.on_uncovered!r}")
+    res = spectra.broaden(energies, values, targets.grid, targets.sigma, shift=shift, kind=kind, cutoff=targets.cutoff,
+                          normalize=normalize, device=dev)
+    try:
+        res.report.raise_if_bad(uncovered=targets.on_uncovered == "raise")
+    except DosxError as err:
+        raise DosxError(re.sub(r"crystal (\d+):", lambda m: f"crystal {which[int(m.group(1))]}:", str(err), count=1)) from None
+    return res
+
+
 def build_data_all(entries: Sequence, r_max: float = 5.0, device="cuda:0", masses: Optional[Sequence[float]] = None,
-                   dtype: torch.dtype = torch.float64, crystal_system: str = "given", symprec: float = 0.1) -> List[Dict[str, object]]:
+                   dtype: torch.dtype = torch.float64, crystal_system: str = "given", symprec: float = 0.1,
+                   targets=None) -> List[Dict[str, object]]:
     """`utils.py:249-303` for a whole dataset at once.  Returns one dict per entry with the reference's ``Data``
     fields: pos, lattice, symbol, x, z, edge_index (row 0 = central atom, row 1 = neighbour), edge_shift, edge_vec,
     edge_len (rounded to 2 decimals, `:276`), phdos [1,51], system, mp_id — host tensors, ``dtype`` floating point.
     ``crystal_system``: "given" reads ``entry.crystal_system`` (an unknown name is code 6, as in the reference); "derive" labels
     the entries that carry none from their structure (``symmetry.crystal_systems`` at ``symprec``); "check" derives every label
-    and raises on the first that disagrees.  Both raise on a crystal whose operations match no point group."""
+    and raises on the first that disagrees.  Both raise on a crystal whose operations match no point group.
+    ``targets``: a ``spectra.PhononTargets(grid, sigma)`` builds ``phdos [1, grid.bins]`` for every entry that carries none, from
+    its ``frequencies`` (mode frequencies, with optional ``weights``: points) or from ``dos = {"energies", "densities"}`` (a
+    tabulated curve), one ``spectra.broaden`` launch per kind.  A spectrum with non-finite or unsorted samples raises; a curve
+    that ends inside the window raises unless ``on_uncovered="keep"``, and such an entry's dict says so in ``covered`` (a bool
+    tensor, present on built entries only).  An entry with a finished ``phdos`` keeps it; None (default) reads ``entry.phdos``
+    as before."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("build_data_all runs the neighbour search on an MI355X through libdosx (no CPU fallback)")
@@ -114,6 +142,27 @@ def build_data_all(entries: Sequence, r_max: float = 5.0, device="cuda:0", masse
     src, dst = nl["src"].cpu().long(), nl["dst"].cpu().long()
     shift, vec, eptr = nl["shift"].cpu(), nl["edge_vec"].cpu(), nl["edge_ptr"].cpu().tolist()
     eye = torch.eye(len(SYMBOLS), dtype=dtype)
+    built = {}                                      # entry index -> (phdos [S] float64, covered), from raw spectra
+    if targets is not None:
+        raw = [c for c, e in enumerate(entries) if _field(e, "phdos") is None]
+        modes = [c for c in raw if _field(entries[c], "frequencies") is not None]
+        curves = [c for c in raw if c not in modes and _field(entries[c], "dos") is not None]
+        if len(modes) + len(curves) != len(raw):
+            missing = next(c for c in raw if c not in modes and c not in curves)
+            raise ValueError(f"entry {missing}: no phdos, no frequencies and no dos to build one from")
+        if modes:
+            freq = [np.asarray(_field(entries[c], "frequencies"), np.float64).reshape(-1) for c in modes]
+            wts = [np.ones_like(f) if _field(entries[c], "weights") is None else
+                   np.asarray(_field(entries[c], "weights"), np.float64).reshape(-1) for c, f in zip(modes, freq)]
+            res = _raw_targets(modes, freq, wts, targets, "points", dev, normalize=targets.normalize)
+            rows = (res.y_norm if targets.normalize else res.y).cpu()
+            built.update({c: (rows[k].clone(), res.report.covered[k].clone()) for k, c in enumerate(modes)})
+        if curves:
+            dos = [_field(entries[c], "dos") for c in curves]
+            res = _raw_targets(curves, [d["energies"] for d in dos], [d["densities"] for d in dos], targets, "curve", dev,
+                               normalize=targets.normalize)
+            rows = (res.y_norm if targets.normalize else res.y).cpu()
+            built.update({c: (rows[k].clone(), res.report.covered[k].clone()) for k, c in enumerate(curves)})
     out = []
     for c, e in enumerate(entries):
         z = torch.tensor([_Z_OF[s] for s in sym[c]], dtype=torch.int64)
@@ -128,9 +177,11 @@ def build_data_all(entries: Sequence, r_max: float = 5.0, device="cuda:0", masse
             "edge_index": torch.stack([src[a:b], dst[a:b]], 0),
             "edge_shift": shift[a:b].to(dtype), "edge_vec": ev.to(dtype),
             "edge_len": torch.from_numpy(np.around(ev.norm(dim=1).numpy(), decimals=2)),
-            "phdos": torch.as_tensor(np.asarray(_get(e, "phdos"), np.float64)).reshape(1, -1).to(dtype),
+            "phdos": (built[c][0] if c in built else torch.as_tensor(np.asarray(_get(e, "phdos"), np.float64))).reshape(1, -1).to(dtype),
             "system": torch.tensor(system), "mp_id": _get(e, "mp_id"),
         })
+        if c in built:
+            out[-1]["covered"] = built[c][1]
     return out
 
 
@@ -159,7 +210,7 @@ def load_elem_feats(path_or_mapping, symbols: Sequence[str] = tuple(SYMBOLS[:100
 
 def build_edos_all(entries: Sequence[dict], elem_feats, radius: float = 8.0, max_num_nbr: int = 12, step: float = 0.2,
                    device="cuda:0", normalize_target: bool = True, crystal_system: str = "given",
-                   symprec: float = 0.1) -> List[Dict[str, object]]:
+                   symprec: float = 0.1, targets=None) -> List[Dict[str, object]]:
     """`data/mat2graph.py:81-107,120-243` for a whole dataset at once.  ``entries``: dicts with ``numbers`` (Z) or
     ``symbols``, ``positions`` (Cartesian), ``cell`` (rows = lattice vectors) and optionally ``glob`` ([energy_per_atom,
     formation_energy_per_atom]), ``crystal_system`` (name, any case), ``y_ft``, ``y``, ``mp_id``.  ``elem_feats [Zmax, F]``:
@@ -169,7 +220,12 @@ def build_edos_all(entries: Sequence[dict], elem_feats, radius: float = 8.0, max
     edge_attr [K*n, G] fp32, glob [2], system, y_ft [201] (divided by its maximum when ``normalize_target``, `:86-88`; zeros
     when the entry has none), y_max, mp_id, pos — and y when the entry has one.  The order inside a distance tie is the key of
     include/dosx.h (DosxKnn); the reference leaves it to pymatgen.  ``crystal_system`` / ``symprec``: as in ``build_data_all``
-    ("given", "derive" or "check")."""
+    ("given", "derive" or "check").  ``targets``: a ``spectra.EdosTargets(grid, sigma)`` builds the targets of every entry that
+    has ``dos = {"energies", "densities", "efermi"}`` and no ``y_ft``, relative to ``efermi`` on ``grid``: ``y_ft`` = the curve
+    broadened by ``sigma`` (``spectra.broaden``; over its maximum when ``normalize_target``) with that maximum as ``y_max``, and
+    ``y`` = the raw curve resampled (``spectra.resample``; likewise over its maximum) - one launch each for the whole dataset.  A
+    spectrum with non-finite or unsorted samples raises; one that ends inside the window raises unless ``on_uncovered="keep"``,
+    and the entry's dict says so in ``covered`` (a bool tensor, present on built entries only).  None (default): as before."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("build_edos_all runs the neighbour selection on an MI355X through libdosx (no CPU fallback)")
@@ -201,6 +257,19 @@ def build_edos_all(entries: Sequence[dict], elem_feats, radius: float = 8.0, max
                        centers=torch.from_numpy(centers).to(dev), var=float(step))
     nbr = kg["nbr_idx"].cpu().long()
     attr = kg["edge_attr"].cpu()
+    built = {}                                      # entry index -> (y_ft, y_max, y, covered), from raw spectra
+    if targets is not None:
+        raw = [c for c, e in enumerate(entries) if e.get("y_ft") is None and e.get("dos") is not None]
+        if raw:
+            dos = [entries[c]["dos"] for c in raw]
+            es, vs, ef = [d["energies"] for d in dos], [d["densities"] for d in dos], [float(d["efermi"]) for d in dos]
+            smooth = _raw_targets(raw, es, vs, targets, "curve", dev, shift=ef, normalize=normalize_target)
+            plain = spectra.resample(es, vs, targets.grid, shift=ef, normalize=normalize_target, device=dev)
+            y_ft = (smooth.y_norm if normalize_target else smooth.y).float().cpu()
+            y_raw = (plain.y_norm if normalize_target else plain.y).float().cpu()
+            y_top = smooth.y_max.float().cpu()
+            built.update({c: (y_ft[k].clone(), y_top[k].clone(), y_raw[k].clone(), smooth.report.covered[k].clone())
+                          for k, c in enumerate(raw)})
     out = []
     for c, e in enumerate(entries):
         a, b, nc = int(atom_ptr[c]), int(atom_ptr[c + 1]), int(n[c])
@@ -209,6 +278,8 @@ def build_edos_all(entries: Sequence[dict], elem_feats, radius: float = 8.0, max
         has_y = e.get("y_ft") is not None
         y_ft = torch.tensor(np.asarray(e["y_ft"]), dtype=torch.float32).reshape(-1) if has_y else torch.zeros(E_BINS)
         y_max = y_ft.max() if has_y else torch.tensor(0.0)
+        if c in built:                              # (already normalised by the launch that made it)
+            y_ft, y_max = built[c][0], built[c][1]
         item = {
             "x": x,
             "edge_index": torch.stack([torch.arange(nc).repeat_interleave(K), nbr[a:b].reshape(-1)], 0),
@@ -221,7 +292,9 @@ def build_edos_all(entries: Sequence[dict], elem_feats, radius: float = 8.0, max
             "mp_id": e.get("mp_id", f"entry-{c}"),
             "pos": torch.from_numpy(pos[c]).float(),
         }
-        if e.get("y") is not None:
+        if c in built:
+            item["y"], item["covered"] = built[c][2], built[c][3]
+        elif e.get("y") is not None:
             y = torch.tensor(np.asarray(e["y"]), dtype=torch.float32).reshape(-1)
             item["y"] = y / y.max() if normalize_target else y
         out.append(item)

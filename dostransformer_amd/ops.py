@@ -2250,6 +2250,54 @@ def sym_point_group(cell: torch.Tensor, frac: torch.Tensor, species: torch.Tenso
     return out
 
 
+def _spectra_descriptor(d, ptr, e, v, shift, e0, de, bins, n_min, n_max, normalize):
+    """Fills the fields DosxSpectra and DosxSpectraInterp share; returns (tensors to keep alive, outputs)."""
+    assert ptr.is_cuda and ptr.dtype == torch.int32 and e.dtype == v.dtype == shift.dtype == torch.float64
+    ptr, e, v, shift = ptr.contiguous(), e.contiguous(), v.contiguous(), shift.contiguous()
+    Cn, T, S = int(shift.shape[0]), int(e.shape[0]), int(bins)
+    assert ptr.shape == (Cn + 1,) and e.shape == v.shape == (T,) and shift.shape == (Cn,)
+    dev, rows = ptr.device, max(S, 0)
+    out = {"y": torch.empty(Cn, rows, dtype=torch.float64, device=dev), "y_max": torch.empty(Cn, dtype=torch.float64, device=dev),
+           "area": torch.empty(Cn, dtype=torch.float64, device=dev), "report": torch.empty(Cn, 4, dtype=torch.int32, device=dev)}
+    if normalize:
+        out["y_norm"] = torch.empty(Cn, rows, dtype=torch.float64, device=dev)
+    d.C, d.T, d.S, d.n_min, d.n_max, d.e0, d.de = Cn, T, S, int(n_min), int(n_max), float(e0), float(de)
+    d.ptr, d.shift = ptr.data_ptr(), shift.data_ptr()
+    if T:                                            # (an empty tensor has a null address)
+        d.e, d.v = e.data_ptr(), v.data_ptr()
+    for key, t in out.items():
+        setattr(d, key, t.data_ptr())
+    return (ptr, e, v, shift), out
+
+
+def spectra_broaden(ptr: torch.Tensor, e: torch.Tensor, v: torch.Tensor, shift: torch.Tensor, sigma: torch.Tensor, e0: float,
+                    de: float, bins: int, n_min: int, n_max: int, kind: int = _abi.DOSX_SPECTRA_CURVE, cutoff: float = 6.0,
+                    normalize: bool = False):
+    """Gaussian broadening of the raw spectra of C crystals onto the grid ``e0 + de * s``, ``s < bins``, in one launch
+    (include/dosx.h: dosx_spectra_broaden).  ``ptr [C+1]`` int32, ``e [T]`` / ``v [T]`` fp64 (crystal c owns
+    ``[ptr[c], ptr[c+1])``), ``shift [C]`` / ``sigma [C]`` fp64, all on the GPU; ``kind``: ``_abi.DOSX_SPECTRA_CURVE`` (a tabulated
+    density, trapezoid weights) or ``DOSX_SPECTRA_POINTS`` (delta peaks); ``n_min`` / ``n_max``: samples of the smallest / largest
+    crystal (the caller built ``ptr``).  Returns a dict of device tensors: ``y [C,bins]``, ``y_max [C]``, ``area [C]`` fp64,
+    ``report [C,4]`` int32 (n_inside, covered, bad, unsorted), and with ``normalize`` also ``y_norm [C,bins]``."""
+    d = _lib.Spectra()
+    assert sigma.dtype == torch.float64 and sigma.shape == shift.shape
+    sigma = sigma.contiguous()
+    keep, out = _spectra_descriptor(d, ptr, e, v, shift, e0, de, bins, n_min, n_max, normalize)
+    d.kind, d.cutoff, d.sigma = int(kind), float(cutoff), sigma.data_ptr()
+    _call("dosx_spectra_broaden", C.byref(d), _stream())
+    return out
+
+
+def spectra_interp(ptr: torch.Tensor, e: torch.Tensor, v: torch.Tensor, shift: torch.Tensor, e0: float, de: float, bins: int,
+                   n_min: int, n_max: int, normalize: bool = False):
+    """Linear interpolation of C tabulated curves at the grid ``e0 + de * s``, zero outside each curve, in one launch
+    (include/dosx.h: dosx_spectra_interp); arguments and result as ``spectra_broaden``."""
+    d = _lib.SpectraInterp()
+    keep, out = _spectra_descriptor(d, ptr, e, v, shift, e0, de, bins, n_min, n_max, normalize)
+    _call("dosx_spectra_interp", C.byref(d), _stream())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # float64 program (csrc/f64.hip, include/dosx.h "float64 program"): thin wrappers, used by functional64.py
 # ---------------------------------------------------------------------------------------------------------------------

@@ -142,3 +142,46 @@ def edos_structures(count: int, seed: int):
                     "glob": rng.normal(size=2), "crystal_system": systems[int(rng.integers(0, 7))],
                     "y_ft": dos * rng.uniform(5.0, 50.0), "mp_id": f"synth-{k}"})
     return out
+
+
+def raw_edos(entries, seed: int):
+    """``entries`` (``edos_structures``) with a synthetic *raw* electron DOS in place of the finished target: each gets ``dos =
+    {"energies", "densities", "efermi"}`` - a smooth non-negative density tabulated at 1500-3000 points of the calculation's own
+    grid, which reaches from 11-14 below to 9-12 above its own Fermi level - and loses ``y_ft``.  Input of
+    ``featurize.build_edos_all(..., targets=spectra.EdosTargets(...))``."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    out = []
+    for e in entries:
+        efermi = float(rng.uniform(-3.0, 7.0))
+        energies = np.linspace(efermi - rng.uniform(11.0, 14.0), efermi + rng.uniform(9.0, 12.0), int(rng.integers(1500, 3001)))
+        dens = sum(a * np.exp(-((energies - efermi - c) / w) ** 2) for a, c, w in
+                   zip(rng.uniform(0.5, 4.0, 12), rng.uniform(-10.0, 8.0, 12), rng.uniform(0.05, 1.2, 12)))
+        e = {k: v for k, v in e.items() if k != "y_ft"}
+        e["dos"] = {"energies": energies, "densities": dens, "efermi": efermi}
+        out.append(e)
+    return out
+
+
+def raw_phonon(entries, seed: int):
+    """``entries`` (``phonon_structures``) with synthetic *raw* phonon spectra in place of ``phdos``: even entries get
+    ``frequencies`` (3 n branches at 64 q-points, between 0 and 0.9 of a cut-off of their own) with ``weights`` (the q-points'
+    weights over 3 n), odd entries a tabulated ``dos = {"energies", "densities"}`` from 0 to 1.2 times that cut-off.  Input of
+    ``featurize.build_data_all(..., targets=spectra.PhononTargets(...))``."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    out = []
+    for k, e in enumerate(entries):
+        n, top = len(e["symbols"]), float(rng.uniform(8.0, 30.0))
+        e = {key: v for key, v in e.items() if key != "phdos"}
+        if k % 2 == 0:
+            centre = np.sort(rng.uniform(0.05, 0.85, 3 * n))
+            e["frequencies"] = top * np.clip(centre[None, :] + rng.normal(0.0, 0.03, (64, 3 * n)), 0.0, 0.9).reshape(-1)
+            e["weights"] = np.repeat(rng.dirichlet(np.ones(64)), 3 * n) / (3 * n)
+        else:
+            energies = np.linspace(0.0, 1.2 * top, int(rng.integers(400, 1201)))
+            dens = sum(a * np.exp(-((energies / top - c) / w) ** 2) for a, c, w in
+                       zip(rng.uniform(0.2, 1.0, 5), rng.uniform(0.1, 0.9, 5), rng.uniform(0.02, 0.15, 5)))
+            e["dos"] = {"energies": energies, "densities": dens}
+        out.append(e)
+    return out

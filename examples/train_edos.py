@@ -52,7 +52,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dostransformer_amd import checkpoint, evaluate, featurize, functionals, param_groups, synth, validate, weights  # noqa: E402
+from dostransformer_amd import checkpoint, evaluate, featurize, functionals, param_groups, spectra, synth, validate, weights  # noqa: E402
 from dostransformer_amd._lib import DosxError  # noqa: E402
 from dostransformer_amd.embedder_eDOS.DOSTransformer import DOSTransformer  # noqa: E402
 from dostransformer_amd.loader import DeviceDataset  # noqa: E402
@@ -85,6 +85,9 @@ def parse_args(argv=None):
                     help="with --structures: prompt labels as the entries give them; derived from the structure where an entry has "
                          "none; or every label derived and compared with the given one (a mismatch stops the run)")
     ap.add_argument("--symprec", type=float, default=0.1, metavar="X", help="with --crystal-system derive / check: distance tolerance in angstrom")
+    ap.add_argument("--raw-dos", type=float, default=None, metavar="SIGMA",
+                    help="with --structures: give the structures synthetic raw spectra (synth.raw_edos) and build y_ft / y from them on "
+                         "the GPU, broadened by SIGMA eV (featurize.build_edos_all(targets=spectra.EdosTargets(...)))")
     ap.add_argument("--eval_batch_size", type=int, default=1, help="main_eDOS.py:55-56 evaluates at batch size 1")
     ap.add_argument("--eval-per-crystal", type=int, default=0, metavar="N",
                     help="N > 0: the batch-size-1 metrics from batched passes of N crystals (evaluate.test_per_crystal, "
@@ -229,9 +232,14 @@ def _main(argv=None):
         # structures -> graphs on the GPU; the element table stands in for the matscholar embedding (`mat2graph.py:33-47`)
         table = featurize.load_elem_feats({s: v for s, v in zip(featurize.SYMBOLS[:100],
                                                                 np.random.default_rng(args.seed).normal(size=(100, 200)))})
+        entries, targets = synth.edos_structures(args.structures, args.seed), None
+        if args.raw_dos is not None:
+            # raw spectra -> targets on the GPU; the window (-8 .. 6 eV around the Fermi level) is this example's, not the paper's
+            entries = synth.raw_edos(entries, args.seed)
+            targets = spectra.EdosTargets(spectra.Grid.linspace(-8.0, 6.0, synth.E_BINS), args.raw_dos)
         t0 = time.perf_counter()
-        crystals = featurize.build_edos_all(synth.edos_structures(args.structures, args.seed), table, device=dev,
-                                            crystal_system=args.crystal_system, symprec=args.symprec)
+        crystals = featurize.build_edos_all(entries, table, device=dev, crystal_system=args.crystal_system, symprec=args.symprec,
+                                            targets=targets)
         print(f"built {len(crystals)} crystal graphs from structures in {time.perf_counter() - t0:.2f} s")
     elif args.pickle:
         crystals = pickle.load(open(args.pickle, "rb"))

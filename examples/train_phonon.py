@@ -92,7 +92,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from dostransformer_amd import checkpoint, evaluate, featurize, functionals, ops, param_groups, synth, validate, weights  # noqa: E402
+from dostransformer_amd import checkpoint, evaluate, featurize, functionals, ops, param_groups, spectra, synth, validate, weights  # noqa: E402
 from dostransformer_amd.embedder_phDOS.DOSTransformer_phonon import DOSTransformer_phonon  # noqa: E402
 from dostransformer_amd.loader import DeviceDataset  # noqa: E402
 from dostransformer_amd.predict import Predictor  # noqa: E402
@@ -127,6 +127,10 @@ def _main(argv=None):
                     help="prompt labels: as the entries give them; derived from the structure where an entry has none; or every "
                          "label derived and compared with the given one (symmetry.crystal_systems; a mismatch stops the run)")
     ap.add_argument("--symprec", type=float, default=0.1, metavar="X", help="with --crystal-system derive / check: distance tolerance in angstrom")
+    ap.add_argument("--raw-dos", type=float, default=None, metavar="SIGMA",
+                    help="build phdos on the GPU from raw spectra broadened by SIGMA: mode frequencies with q-point weights, or a tabulated "
+                         "DOS (featurize.build_data_all(targets=spectra.PhononTargets(...))); synthetic structures get synthetic spectra "
+                         "(synth.raw_phonon), a --pickle's entries bring their own `frequencies` / `dos`")
     ap.add_argument("--out", default="phonon_best.pt")
     ap.add_argument("--no-validate", action="store_true",
                     help="skip batch validation (validate.enable: every crystal and every first-seen batch is checked for out-of-range "
@@ -241,10 +245,16 @@ def _main(argv=None):
     validate.enable(not args.no_validate, finite=True)
 
     entries = pickle.load(open(args.pickle, "rb")) if args.pickle else synth.phonon_structures(args.crystals, args.seed)
+    targets = None
+    if args.raw_dos is not None:
+        # raw spectra -> phdos on the GPU; the window (0 .. 7.5 in the synthetic spectra's unit) is this example's, not the paper's
+        if not args.pickle:
+            entries = synth.raw_phonon(entries, args.seed)
+        targets = spectra.PhononTargets(spectra.Grid.linspace(0.0, 7.5, synth.PH_BINS, unit="THz"), args.raw_dos)
     t0 = time.perf_counter()
     crystals = featurize.build_data_all(entries, r_max=args.r_max, device=dev,
                                         dtype=torch.float64 if args.float64 else torch.float32,
-                                        crystal_system=args.crystal_system, symprec=args.symprec)
+                                        crystal_system=args.crystal_system, symprec=args.symprec, targets=targets)
     print(f"{len(crystals)} crystals -> graphs in {time.perf_counter() - t0:.2f} s "
           f"({sum(c['edge_index'].shape[1] for c in crystals)} edges)")
     perm = np.random.default_rng(args.seed).permutation(len(crystals))

@@ -1134,6 +1134,68 @@ typedef struct DosxSymPointGroup {
 } DosxSymPointGroup;
 int dosx_sym_point_group(const DosxSymPointGroup* d, dosx_stream_t stream);
 
+/* DOS targets of C crystals from their raw spectra (csrc/spectra.hip): Gaussian broadening onto a grid (dosx_spectra_broaden) and
+ * linear resampling onto it (dosx_spectra_interp).  The reference reads finished targets (`data/mat2graph.py:81-92`:
+ * `densities_total_1_ft`, `densities_total_1`) and never shows how they are made, so this comment is the contract; the numpy twin
+ * is dostransformer_amd/spectra.py.  Every input and every operation is float64, one rounding per operation as written, no fused
+ * multiply-adds.  Crystal c owns the samples [ptr[c], ptr[c+1]) of `e` (energies) and `v` (values), n = their number.
+ *   grid      E_s = e0 + de * (double)s ,  s = 0..S-1.
+ *   samples   ec_i = e_i - shift[c]  (shift = the Fermi level; 0 for phonons).
+ *   weights   DOSX_SPECTRA_POINTS: w_i = v_i (delta peaks: mode frequencies with q-point weights; any order, n = 0 allowed).
+ *             DOSX_SPECTRA_CURVE: v is a density tabulated on strictly ascending e, n >= 2; trapezoid weights of the raw e:
+ *             w_0 = v_0 * (0.5 * (e_1 - e_0)) ,  w_i = v_i * (0.5 * (e_{i+1} - e_{i-1})) ,  w_{n-1} = v_{n-1} * (0.5 * (e_{n-1} - e_{n-2})).
+ *   broaden   g = 1 / (sigma[c] * 2.5066282746310002)  (the double nearest sqrt(2 pi)) ;  per bin s and sample i:
+ *             x = (E_s - ec_i) / sigma[c]  (a true division) ;  the term is kept iff fabs(x) <= cutoff ;
+ *             t_i = (w_i * g) * exp(-0.5 * (x * x)) ;  y[c][s] starts at 0.0 and the kept t_i are added to it in ascending i.
+ *             A dropped term adds nothing, not even a +0.0.  Only exp may differ from another implementation, by its last
+ *             place.  The order of summation depends on (n, S) alone: no atomics, bitwise the same from run to run.
+ *   interp    (curves) outside [ec_0, ec_{n-1}] (or when a comparison with E_s is unordered) y = 0 ; otherwise j = the last index
+ *             with ec_j <= E_s ;  j = n-1 gives v_{n-1} ;  else  y = v_j + (v_{j+1} - v_j) * ((E_s - ec_j) / (ec_{j+1} - ec_j)).
+ *   y_max [C] the row maximum (S >= 1: never -inf).   area [C] = de * (((y_0 + y_1) + y_2) + ...), ascending s.
+ *   y_norm    (optional, NULL = skip) y / y_max, zeros where y_max <= 0.
+ *   report    [C][4] int32: n_inside = samples with lo <= ec_i <= hi, lo = E_0 - (cutoff * sigma[c]), hi = E_{S-1} + (cutoff *
+ *             sigma[c]) (interp: lo = E_0, hi = E_{S-1}) ;  covered = (ec_0 <= E_0 && ec_{n-1} >= E_{S-1}) for a curve, 1 for
+ *             points ;  bad = samples with a non-finite e_i or v_i, plus 1 for a shift[c] that is not finite, plus 1 for a
+ *             sigma[c] that is not a finite number above 0 ;  unsorted = for a curve the number of i with e_{i+1} <= e_i.
+ * A crystal with bad > 0, or a curve with unsorted > 0, gets NaN in its row of y and y_norm and in y_max and area, and its counts;
+ * no other crystal's row is touched.  n_min / n_max: the smallest / largest n, stated by the caller (ptr lives on the device); a
+ * crystal the kernel finds outside [n_min, n_max] or outside [0, T] gets the NaN row and the report (0, 0, -1, 0), and none of its
+ * samples is read.  One 256-lane workgroup per crystal, one launch per call.  Refused with rc -22 before any launch: null
+ * descriptor, C <= 0, T < 0, S outside [1, 1024], e0 or de not finite, de <= 0 with S > 1, cutoff <= 0 or NaN, an unknown kind,
+ * n_min < 0, a curve with n_min < 2, n_max < n_min or n_max >= 2^20, a null ptr / shift / sigma / y / y_max / area / report, and
+ * with T > 0 a null e / v. */
+enum { DOSX_SPECTRA_POINTS = 0, DOSX_SPECTRA_CURVE = 1 };
+typedef struct DosxSpectra {
+  int32_t C, T, S, kind, n_min, n_max;
+  double e0, de, cutoff;
+  const int32_t* ptr;       /* [C+1] */
+  const double* e;          /* [T] */
+  const double* v;          /* [T] */
+  const double* shift;      /* [C] */
+  const double* sigma;      /* [C] */
+  double* y;                /* [C][S] */
+  double* y_max;            /* [C] */
+  double* area;             /* [C] */
+  double* y_norm;           /* [C][S], may be NULL */
+  int32_t* report;          /* [C][4]: n_inside, covered, bad, unsorted */
+} DosxSpectra;
+int dosx_spectra_broaden(const DosxSpectra* d, dosx_stream_t stream);
+
+typedef struct DosxSpectraInterp {
+  int32_t C, T, S, reserved, n_min, n_max;
+  double e0, de;
+  const int32_t* ptr;       /* [C+1] */
+  const double* e;          /* [T] strictly ascending inside a crystal */
+  const double* v;          /* [T] */
+  const double* shift;      /* [C] */
+  double* y;                /* [C][S] */
+  double* y_max;            /* [C] */
+  double* area;             /* [C] */
+  double* y_norm;           /* [C][S], may be NULL */
+  int32_t* report;          /* [C][4] */
+} DosxSpectraInterp;
+int dosx_spectra_interp(const DosxSpectraInterp* d, dosx_stream_t stream);
+
 /* Replay of a recorded launch list (the host side of train.Trainer(replay=True), see csrc/replay.cpp): `n` calls are
  * issued in order.  A call names its callee by `op` (from dosx_replay_op: every `int dosx_*` entry point of this header,
  * plus "hipEventRecord" / "hipStreamWaitEvent" for stream fork/join) and carries the callee's integer-class arguments in
